@@ -23,6 +23,10 @@ Prints ONE JSON line on rank 0 (see the task contract) with two extra objects:
                   same workload, 1 host thread (the reference ships single-threaded: OpenMP off); r_threads: the same
                   with one host thread per agent (what the reference's asynchronous mode starts)
 `value` is the MEDIAN of REPLAYS replays of the driver's window (value_samples lists them).
+
+`--dump-outputs DIR` writes what the last timed iteration (of the last replay at N = 1) left to its caller -- the whole
+iterate X, 2f, the gradient norms and the next selected agent -- as DIR/<name>.npy, so that two builds run with the same
+arguments (same dataset, same seeded start point) can be compared output for output.
 """
 import argparse
 import json
@@ -361,7 +365,39 @@ def parse():
     ap.add_argument("--cpu-steps", type=int, default=0, help="oracle iterations for cpu_baseline (0 = auto)")
     ap.add_argument("--cpu-c4-staircase", action="store_true",
                     help="also run the CPU port through the whole tiers.pyfg staircase (minutes)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (the iterate X, 2f, the "
+                         "gradient norms, the next selected agent) as DIR/<name>.npy in float64 (rank 0 writes)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, arrays, limit=DUMP_LIMIT_BYTES):
+    """DIR/<name>.npy in float64; when the whole set exceeds `limit`, each array larger than its share is replaced by a
+    fixed sample of its entries (seed 0, sorted flat indices, written beside it as <name>_sample_index.npy)"""
+    os.makedirs(directory, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    share = limit // (2 * len(arrays))
+    out = {}
+    for name, a in arrays.items():
+        if sum(v.nbytes for v in arrays.values()) > limit and a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // 16, replace=False))
+            out[name + "_sample"], out[name + "_sample_index"] = a.ravel()[idx], idx.astype(np.float64)
+        else:
+            out[name] = a
+    for name, a in out.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
+def dump_last_step(directory, X, cost2, gradnorm, block_norms, next_selected):
+    """what the caller of the timed path holds after its last step: the whole iterate and that step's evaluation"""
+    dump_outputs(directory, {"X": X, "cost_2f": cost2, "gradnorm": gradnorm, "block_gradnorms": block_norms,
+                             "next_selected": next_selected})
 
 
 def spawn_ranks(args):
@@ -401,25 +437,28 @@ def run_single(args, da, torch, ds, X0):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         c2 = gn = 0.0
+        bn = None
         for _ in range(count):
             c2, gn, bn, selected = s.iterate(selected)
         s.synchronize()
         torch.cuda.synchronize()
-        return time.perf_counter() - t0, c2, gn, selected
+        return time.perf_counter() - t0, c2, gn, bn, selected
 
     # the driver's window is a few milliseconds: it is replayed REPLAYS times from the start point (same warm-up, same
     # K iterations of the same trajectory) and `value` is the median; every sample is printed
     samples = []
     for _ in range(REPLAYS):
         selected = warm()
-        dt, c2, gn, selected = window(args.steps, selected)
+        dt, c2, gn, bn, selected = window(args.steps, selected)
         samples.append(dt)
     dt = float(np.median(samples))
     run_single.samples = samples
+    if args.dump_outputs:
+        dump_last_step(args.dump_outputs, s.get_X(), c2, gn, bn, selected)
     sustained = None
     if not args.headline_only:
         first = args.warmup + 1 + args.steps
-        dts, c2s, gns, selected = window(SUSTAINED_STEPS, selected)
+        dts, c2s, gns, _, selected = window(SUSTAINED_STEPS, selected)
         sustained = {"steps": SUSTAINED_STEPS, "first_iteration": first + 1, "value": SUSTAINED_STEPS / dts,
                      "unit": "RBCD iterations/s", "ms_per_step": 1e3 * dts / SUSTAINED_STEPS,
                      "final_cost_2f": c2s, "final_gradnorm": gns}
@@ -449,8 +488,12 @@ class RankDriver:
         self.ex.set_X(X)
 
     def step(self, selected):
-        c2, gn, bn, nxt = self.ex.iterate(selected)
+        c2, gn, self.bn, nxt = self.ex.iterate(selected)
         return c2, gn, nxt
+
+    def gather_X(self):
+        """the whole X on every rank (collective)"""
+        return self.ex.gather_X()
 
     def tick(self, agents):
         self.ex.tick(agents)
@@ -529,7 +572,12 @@ def run_multi(args, da, torch, dist, ds, X0, rank, world):
         state = drv.step(state[2])
     drv.exchange_stats(1)
     dt, state = drv.timed(lambda prev: drv.step((prev or state)[2]), args.steps)
-    return drv, dt, state[0], state[1], drv.exchange_stats(args.steps)
+    stats = drv.exchange_stats(args.steps)
+    if args.dump_outputs:
+        X = drv.gather_X()
+        if rank == 0:
+            dump_last_step(args.dump_outputs, X, state[0], state[1], drv.bn, state[2])
+    return drv, dt, state[0], state[1], stats
 
 
 class CollectiveDriver:
@@ -625,7 +673,7 @@ class CollectiveDriver:
         self.allreduce(self.evalbuf)
         with self.torch.cuda.stream(self.ts):
             h = self.evalbuf.cpu().numpy()
-        bn = np.sqrt(h[0::2])
+        self.bn = bn = np.sqrt(h[0::2])
         cost2 = float(h[1::2].sum())  # 2 f = sum_b <X_b, X_b Q_bb + G_b>
         return cost2, float(np.sqrt(h[0::2].sum())), int(np.argmax(bn))
 
@@ -640,6 +688,23 @@ class CollectiveDriver:
 
     def set_X(self, X):
         self.s.set_X(X)
+
+    def gather_X(self):
+        """the whole X on every rank (collective): each rank contributes the column blocks of the agents it hosts
+        (agent a: poses a * per .. of the contiguous partition, the last agent up to n), the others add zeros"""
+        s, dh = self.s, self.s.ds.d + 1
+        s.synchronize()
+        X = s.get_X()
+        per = s.ds.n // self.R
+        mine = np.zeros(X.shape)
+        for a in range(self.R):
+            if self.owner[a] == self.rank:
+                c0, c1 = a * per * dh, (s.k if a == self.R - 1 else (a + 1) * per * dh)
+                mine[:, c0:c1] = X[:, c0:c1]
+        t = self.torch.from_numpy(mine)
+        t = t if self.staged else t.to(self.dev)
+        self.dist.all_reduce(t)
+        return t.cpu().numpy()
 
     def exchange_stats(self, iterations):
         return {"transport": self.transport}

@@ -25,14 +25,48 @@ def run_bench(extra, env_extra=None, timeout=900):
     return json.loads(last, parse_constant=lambda t: pytest.fail("non-finite constant " + t))
 
 
-def test_headline_line_of_the_one_gpu_run():
-    line = run_bench(["--steps", "20", "--warmup", "5", "--headline-only"])
+def test_headline_line_of_the_one_gpu_run(tmp_path):
+    line = run_bench(["--steps", "20", "--warmup", "5", "--headline-only", "--dump-outputs", str(tmp_path)])
     assert line["n_gpus"] == 1 and line["steps"] == 20 and line["warmup"] == 5 and line["value"] > 100
     assert abs(line["value"] * line["ms_per_step"] - 1e3) < 1.0
     assert line["config"]["workload"].startswith("sphere2500") and line["vs_baseline"] is None
     with open(os.path.join(ROOT, "gpurun_out", "bench_detail.json")) as fh:
         detail = json.load(fh)
     assert abs(detail["value"] - line["value"]) <= 1e-5 * line["value"]
+    check_last_step_dump(tmp_path, detail)
+
+
+def check_last_step_dump(path, detail):
+    """the dump holds the outputs of the last timed step: the evaluation the line reports, and the whole iterate X it
+    was taken at (2f recomputed from the dumped X by the CPU oracle)"""
+    import numpy as np
+    import common
+    from oracle import orc
+    X = np.load(path / "X.npy")
+    assert X.dtype == np.float64 and X.shape == (5, 4 * 2500) and np.isfinite(X).all()
+    c2 = float(np.load(path / "cost_2f.npy"))
+    assert c2 == detail["config"]["final_cost_2f"]
+    assert float(np.load(path / "gradnorm.npy")) == detail["config"]["final_gradnorm"]
+    dso = common.oracle_dataset("sphere2500")
+    assert abs(2 * orc.Problem(5, dso.d, dso.n, orc.build_Q_pgo(dso)).f(X) - c2) <= 1e-9 * abs(c2)
+    bn = np.load(path / "block_gradnorms.npy")
+    assert bn.shape == (5,) and np.isfinite(bn).all() and 0 <= int(np.load(path / "next_selected.npy")) < 5
+    return X
+
+
+@pytest.mark.parametrize("transport", ["library exchange", "collectives"])
+def test_two_rank_dump_is_the_whole_last_step(tmp_path, transport):
+    env = {"DCORA_DIST_BACKEND": "gloo"}
+    if transport == "collectives":
+        env["DCORA_BENCH_COLLECTIVES"] = "1"
+    line = run_bench(["--gpus", "2", "--steps", "6", "--warmup", "2", "--headline-only", "--dump-outputs",
+                      str(tmp_path)], env)
+    assert line["n_gpus"] == 2 and line["steps"] == 6
+    fallback = line["process_group"]["transport"] == "torch.distributed collectives (fallback)"
+    assert fallback == (transport == "collectives"), line["process_group"]
+    import bench
+    with open(bench.DETAIL_PATH) as fh:  # where bench.py leaves the whole line
+        check_last_step_dump(tmp_path, json.load(fh))
 
 
 def test_two_rank_rehearsal_prints_the_scaling_series():

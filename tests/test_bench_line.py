@@ -124,3 +124,22 @@ def test_n1_cache_is_ignored_on_any_provenance_mismatch(tmp_path, monkeypatch):
     bench.cache_store(stale)
     c, why = bench.cache_load(Args)
     assert c is None and "lib_sha16" in why
+
+
+def test_dump_outputs_writes_float64_arrays_within_the_size_limit(tmp_path):
+    import numpy as np
+    X = np.arange(5 * 400, dtype=np.float64).reshape(5, 400)
+    bench.dump_outputs(str(tmp_path / "all"), {"X": X, "cost_2f": 2.5, "next_selected": 3})
+    assert sorted(os.listdir(tmp_path / "all")) == ["X.npy", "cost_2f.npy", "next_selected.npy"]
+    assert np.array_equal(np.load(tmp_path / "all" / "X.npy"), X)
+    assert np.load(tmp_path / "all" / "next_selected.npy").dtype == np.float64
+    # over the limit: the large array is replaced by a fixed sample of its entries and their flat indices
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), {"X": X, "cost_2f": 2.5}, limit=4000)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["X_sample.npy", "X_sample_index.npy", "cost_2f.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 4000 + 128 * len(files)  # + npy headers
+    idx = np.load(tmp_path / "a" / "X_sample_index.npy")
+    assert np.array_equal(np.load(tmp_path / "a" / "X_sample.npy"), X.ravel()[idx.astype(np.int64)])
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))

@@ -171,16 +171,14 @@ def test_pyfg_with_priors_and_pose_landmark_edges(built, name):
 
 def test_tiers_sizes_match_survey(built):
     """tiers.pyfg has k = 37 094 and nnz(Q) = 279 108 -- checked on single_drone (shipped fixture)
-    through both builders, and on tiers itself when the reference tree is mounted"""
+    through both builders, and on tiers itself (shipped fixture)"""
     from oracle import orc
     import dcora_amd as da
     ds = da.RADataset(ra_path("single_drone"))
     assert (ds.d, ds.n, ds.l, ds.b, ds.k) == (3, 1754, 1754, 1, 8771)
     assert abs(ds.Q.to_scipy() - ds.Q.to_scipy().T).max() < 1e-9
-    tiers = "/root/reference/data/tiers.pyfg"
-    if os.path.exists(tiers):
-        t = da.RADataset(tiers)
-        assert (t.d, t.n, t.l, t.b, t.k, t.Q.nnz) == (2, 9768, 7789, 1, 37094, 279108)
+    t = da.RADataset(ra_path("tiers"))
+    assert (t.d, t.n, t.l, t.b, t.k, t.Q.nnz) == (2, 9768, 7789, 1, 37094, 279108)
 
 
 @pytest.mark.gpu
