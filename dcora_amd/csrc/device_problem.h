@@ -290,13 +290,15 @@ class DeviceProblem {
   int escape_saddle(const double *Xopt, double theta, const double *v, double gtol, double pgtol, bool second_order,
                     double *Xout, int *success);
 
-  // ---- device-resident solve: X0.p holds the start point; on return *Xres points at the result buffer ----
-  // The fused path returns without synchronising: the result lives in Xres->p[(*ctl_out)->cur] (device-side
-  // pick), statistics are fetched later with fetch_result().  Other paths return ctl_out = nullptr and a
-  // resolved pointer in Xres->p[0].
-  int optimize_dev(const dcora_ropt_params &prm, Buf2 *Xres, const SolverCtl **ctl_out);
+  // ---- device-resident solve: X0.p holds the start point.  Returns without synchronising: the result lies in X0 / X1
+  // as ctl->cur picks (RTR) or in X1 (RGD); fetch_result() finishes a pending solve and returns its statistics.
+  int optimize_dev(const dcora_ropt_params &prm);
   int fetch_result(dcora_ropt_result *res);
-  int result_index() const { return cur_after_fetch_; }  // synchronises when a fused solve is still in flight
+  // where the last solve left its result: for kernels that pick on the device, X.p[(*c)->cur & 1] (X.p[0] when *c is
+  // null) ...
+  Buf2 result_pick(const SolverCtl **c) const;
+  // ... and resolved on the host for everyone else (synchronises while a solve is pending)
+  int result(double **X);
   // scalars of an arbitrary point on device: f and |rgrad| (synchronises)
   int eval_dev(const double *Xd, double *f, double *gradnorm);
 
@@ -305,11 +307,13 @@ class DeviceProblem {
   bool use_pc() const;  // dense preconditioner, step + product + projection in one launch (k_fused_pc)
 
  private:
-  int rtr_dev(const dcora_ropt_params &prm, dcora_ropt_result *res, double **Xres);
-  int rtr_dev_fused(const dcora_ropt_params &prm);
-  int rgd_dev(const dcora_ropt_params &prm, dcora_ropt_result *res, double **Xres);
+  enum class TcgForm { generic, split, pc, run };  // generic layout / B, C / B + C in one launch / k_tcg_run
+  struct RtrForm;
+  int rtr_dev(const dcora_ropt_params &prm, TcgForm form);
+  int rgd_dev(const dcora_ropt_params &prm);
   int seq_ = 0;            // launch sequence number, monotonic across solves (HostFlags words are never reset)
-  bool pending_ = false;   // a fused solve has been enqueued and its statistics not yet fetched
+  bool pending_ = false;   // an RTR solve has been enqueued and its statistics not yet fetched
+  bool rgd_ = false;       // the last solve was RGD: its result is X1
   double t0_ms_ = 0;
   dcora_ropt_result last_res_{};
   int cur_after_fetch_ = 0;

@@ -661,36 +661,22 @@ int DeviceProblem::optimize(const dcora_ropt_params &prm, const double *X0h, dou
   DCORA_HIP(hipSetDevice(device));
   int rc = upload(X0h, X0.p, nelem());
   if (rc) return rc;
-  Buf2 Xres{{nullptr, nullptr}};
-  const SolverCtl *c = nullptr;
-  rc = optimize_dev(prm, &Xres, &c);
-  if (rc) return rc;
-  dcora_ropt_result r{};
-  rc = fetch_result(&r);  // synchronises; also resolves which buffer holds the accepted iterate
-  if (rc) return rc;
-  if (res_out) *res_out = r;
-  return download(c ? (cur_after_fetch_ ? X1.p : X0.p) : Xres.p[0], Xout, nelem());
+  double *X = nullptr;
+  if ((rc = optimize_dev(prm)) || (rc = result(&X)) || (rc = fetch_result(res_out))) return rc;
+  return download(X, Xout, nelem());
 }
 
-int DeviceProblem::optimize_dev(const dcora_ropt_params &prm, Buf2 *Xres, const SolverCtl **ctl_out) {
-  *ctl_out = nullptr;
+int DeviceProblem::optimize_dev(const dcora_ropt_params &prm) {
   pending_ = false;
-  if (prm.method == 0 && fused) {
-    if (!has_precond) {
-      set_last_error("RTR requires the preconditioner (ref src/QuadraticProblem.cpp:78-82)");
-      return DCORA_ERR_NO_PRECONDITIONER;
-    }
-    const int rc = rtr_dev_fused(prm);
-    if (rc) return rc;
-    *Xres = Xb();
-    *ctl_out = ctl.p;
-    pending_ = true;
-    return DCORA_OK;
+  rgd_ = prm.method != 0;
+  if (rgd_) return rgd_dev(prm);
+  if (!has_precond) {
+    set_last_error("RTR requires the preconditioner (ref src/QuadraticProblem.cpp:78-82)");
+    return DCORA_ERR_NO_PRECONDITIONER;
   }
-  double *p = nullptr;
-  const int rc = (prm.method == 0) ? rtr_dev(prm, &last_res_, &p) : rgd_dev(prm, &last_res_, &p);
-  *Xres = Buf2{{p, p}};
-  return rc;
+  TcgForm form = TcgForm::generic;
+  if (fused) form = !use_pc() ? TcgForm::split : (tcg_run_ok && !concurrent_solves) ? TcgForm::run : TcgForm::pc;
+  return rtr_dev(prm, form);
 }
 
 int DeviceProblem::fetch_result(dcora_ropt_result *res_out) {
@@ -718,8 +704,20 @@ int DeviceProblem::fetch_result(dcora_ropt_result *res_out) {
   return DCORA_OK;
 }
 
-// one preconditioned Riemannian gradient step (ref src/QuadraticOptimizer.cpp:123-150)
-int DeviceProblem::rgd_dev(const dcora_ropt_params &prm, dcora_ropt_result *res_out, double **Xres) {
+Buf2 DeviceProblem::result_pick(const SolverCtl **c) const {
+  *c = rgd_ ? nullptr : ctl.p;
+  return rgd_ ? buf1(X1.p) : Xb();
+}
+
+int DeviceProblem::result(double **X) {
+  const int rc = fetch_result(nullptr);
+  if (rc) return rc;
+  *X = cur_after_fetch_ ? X1.p : X0.p;
+  return DCORA_OK;
+}
+
+// one preconditioned Riemannian gradient step (ref src/QuadraticOptimizer.cpp:123-150); the result is X1
+int DeviceProblem::rgd_dev(const dcora_ropt_params &prm) {
   const auto t0 = std::chrono::steady_clock::now();
   double f0 = 0, g0 = 0;
   int rc = eval_dev(X0.p, &f0, &g0);
@@ -739,19 +737,17 @@ int DeviceProblem::rgd_dev(const dcora_ropt_params &prm, dcora_ropt_result *res_
   double f1 = 0, g1 = 0;
   rc = eval_dev(X1.p, &f1, &g1);
   if (rc) return rc;
-  if (res_out) {
-    res_out->success = 1;
-    res_out->fInit = f0;
-    res_out->gradNormInit = g0;
-    res_out->fOpt = f1;
-    res_out->gradNormOpt = g1;
-    res_out->elapsedMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    res_out->tCGStatus = 4;
-    res_out->outer_iterations = 1;
-    res_out->inner_iterations = 0;
-    res_out->accepted_steps = 1;
-  }
-  *Xres = X1.p;
+  last_res_.success = 1;
+  last_res_.fInit = f0;
+  last_res_.gradNormInit = g0;
+  last_res_.fOpt = f1;
+  last_res_.gradNormOpt = g1;
+  last_res_.elapsedMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  last_res_.tCGStatus = 4;
+  last_res_.outer_iterations = 1;
+  last_res_.inner_iterations = 0;
+  last_res_.accepted_steps = 1;
+  cur_after_fetch_ = 1;
   return DCORA_OK;
 }
 
@@ -773,151 +769,6 @@ bool spin_until(Pred p, double timeout_s) {
 }
 }  // namespace
 
-// RTRNewton with preconditioned Steihaug-Toint tCG, fully device-resident: the host enqueues the kernel
-// sequence, stays at most kLookahead tCG iterations ahead of the GPU and learns about terminations from
-// host-mapped flags.  (ref src/QuadraticOptimizer.cpp:52-108, 234-280; ROPTLIB semantics: SURVEY.md 3.4)
-int DeviceProblem::rtr_dev(const dcora_ropt_params &prm, dcora_ropt_result *res_out, double **Xres) {
-  if (!has_precond) {
-    set_last_error("RTR requires the preconditioner (ref src/QuadraticProblem.cpp:78-82)");
-    return DCORA_ERR_NO_PRECONDITIONER;
-  }
-  constexpr int kLookahead = 2;
-  const auto t0 = std::chrono::steady_clock::now();
-  const bool single = (prm.RTR_iterations == 1);
-  SolverCtl h;
-  std::memset(&h, 0, sizeof h);
-  h.tol = prm.gradnorm_tol;
-  h.Delta = prm.RTR_initial_radius;
-  h.maxDelta = single ? prm.RTR_initial_radius : 5 * prm.RTR_initial_radius;  // :240-241, :259-260
-  h.max_outer = single ? 12 : prm.RTR_iterations;                              // :254-273 (<= 11 retries)
-  h.stop_on_accept = single ? 1 : 0;
-  h.max_inner = prm.RTR_tCG_iterations;
-  h.outer_done_stamp = INT_MAX;
-  h.tcg_done_stamp = INT_MAX;
-  h.tcg_status = 4;
-  DCORA_HIP(hipMemcpyAsync(ctl.p, &h, sizeof h, hipMemcpyHostToDevice, st));
-  DCORA_HIP(hipStreamSynchronize(st));  // h lives on this stack frame
-  hf->last_seq_done = 0;
-  hf->tcg_done_seq = 0;
-  hf->outer_done_seq = 0;
-  hf->go_seq = 0;
-  hf->reject_seq = 0;
-  SolverCtl *c = ctl.p;
-  const long N = nelem();
-  const CsrDev Qv = Q.view();
-  const double *Gp = has_G ? G.p : nullptr;
-  const int nA = npA(), nP = npPose(), nV = npVec();
-  int seq = 0;
-  auto timed_out = [&]() {
-    set_last_error("rtr_dev: device did not make progress (spin timeout)");
-    return DCORA_ERR_HIP;
-  };
-
-  // f(x0), grad(x0)
-  // (enq_qapply, not the CSR kernel directly: the number of partial slots npA() counts follows the Q-apply kernel that
-  // runs -- block-CSR for large pose graphs)
-  enq_qapply(Xb(), 0, Gp, EGb(), 0, pA.p, Gate{c, ++seq, 0});
-  launch_rgrad(st, m, Xb(), EGb(), RGb(), Sb(), 0, pB.p, Gate{c, ++seq, 0});
-  launch_rtr_init(st, pA.p, nA, pB.p, nP, c, hf_dev, ++seq);
-  int last_pace_seq = seq;
-
-  std::vector<int> upd2_seq((size_t)std::max(1, h.max_inner));
-  const SpFold sfg = sparse_precond ? sp.fold_generic() : SpFold();
-  // H d in one launch (k_spmm_dir_fix) when every long row is a Euclidean column and the partial slots fit
-  const bool hess_fused = hess_one_launch();
-  for (int outer = 0; outer < h.max_outer; ++outer) {
-    // wait for the previous decision (rtr_init / rtr_decide) before committing to another outer iteration
-    if (!spin_until([&] { return hf->last_seq_done >= last_pace_seq || hf->outer_done_seq != 0; }, 20.0))
-      return timed_out();
-    if (hf->outer_done_seq != 0) break;
-    if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 5.0) break;  // TimeBound :252
-
-    // ---- tCG ----
-    launch_tcg_begin(st, N, RGb(), eta.p, Heta.p, res.p, c, ++seq);
-    const int tcg_first_seq = seq;
-    enq_minv(buf1(res.p), Zt.p, nullptr, 0, Gate{c, ++seq, 1});
-    launch_tangent(st, m, Xb(), Zt.p, z.p, res.p, p3.p, nullptr, 0, c, hf_dev, ++seq, 1, 0);
-    // the direction update (k_tcg_init, then k_tcg_update2 of the previous iteration) rides in the Hessian SpMM of
-    // the next one (k_spmm_dir); the direction ping-pongs between two buffers
-    double *const db[2] = {delta.p, delta2.p};
-    for (int j = 0; j < h.max_inner; ++j) {
-      if (j >= kLookahead) {
-        const int need = upd2_seq[j - kLookahead];
-        if (!spin_until(
-                [&] {
-                  return hf->last_seq_done >= need || hf->tcg_done_seq >= tcg_first_seq || hf->outer_done_seq != 0;
-                },
-                20.0))
-          return timed_out();
-      }
-      if (hf->tcg_done_seq >= tcg_first_seq) break;
-      double *const dcur = db[j & 1];
-      int nP1 = nP;
-      if (hess_fused) {
-        nP1 = launch_spmm_dir_fix(st, m, Qv, Xb(), Sb(), z.p, db[(j + 1) & 1], dcur, Hd.p, p3.p, nP, p1.p, c, ++seq, j);
-      } else {
-        launch_spmm_dir(st, m.r, Qv, z.p, db[(j + 1) & 1], dcur, W.p, p3.p, nP, c, ++seq, j);
-        launch_hessfix(st, m, Xb(), Sb(), dcur, W.p, Hd.p, p1.p, Gate{c, ++seq, 2});
-      }
-      // sparse preconditioner: its two permutations (and the hub correction) ride in the kernels either side of the
-      // level replay -- two launches fewer per tCG iteration
-      launch_tcg_update1(st, N, dcur, Hd.p, eta.p, Heta.p, res.p, p1.p, nP1, p2.p, c, hf_dev, ++seq, j, m.r, sfg);
-      if (sfg.y) {
-        // as in rtr_dev_fused: only the replay's first launch is enqueued before update1's verdict is known
-        const int seqB = seq;
-        bool timed = false;
-        const std::function<bool()> verdict = [&]() {
-          if (!spin_until(
-                  [&] {
-                    return hf->go_seq >= seqB || hf->tcg_done_seq >= tcg_first_seq || hf->outer_done_seq != 0;
-                  },
-                  20.0)) {
-            timed = true;
-            return false;
-          }
-          return !(hf->tcg_done_seq >= tcg_first_seq || hf->outer_done_seq != 0);
-        };
-        sp.apply(st, m.r, buf1(res.p), Zt.p, Gate{c, ++seq, 2}, true, &verdict);
-        if (timed) return timed_out();
-        if (hf->tcg_done_seq >= tcg_first_seq || hf->outer_done_seq != 0) break;
-      } else
-        enq_minv(buf1(res.p), Zt.p, p2.p, nV, Gate{c, ++seq, 2});
-      launch_tangent(st, m, Xb(), Zt.p, z.p, res.p, p3.p, p2.p, nV, c, hf_dev, ++seq, 2, j, sfg);
-      // the inner loop exhausted: the bookkeeping of the last direction update (status TR_MAXITER) has no next SpMM
-      if (j == h.max_inner - 1) launch_tcg_update2(st, N, z.p, dcur, p3.p, nP, c, hf_dev, ++seq, j);
-      upd2_seq[j] = seq;
-    }
-    // ---- trial point, model ratio, acceptance ----
-    launch_retract(st, m, Xb(), eta.p, 1.0, Xb(), 1, RGb(), Heta.p, pC.p, Gate{c, ++seq, 1});
-    enq_qapply(Xb(), 1, Gp, EGb(), 1, pA.p, Gate{c, ++seq, 1});
-    launch_rgrad(st, m, Xb(), EGb(), RGb(), Sb(), 1, pB.p, Gate{c, ++seq, 1});
-    launch_rtr_decide(st, pA.p, nA, pB.p, nP, pC.p, nP, c, hf_dev, ++seq);
-    last_pace_seq = seq;
-  }
-  DCORA_HIP(hipMemcpyAsync(&h, ctl.p, sizeof h, hipMemcpyDeviceToHost, st));
-  DCORA_HIP(hipStreamSynchronize(st));
-  DCORA_HIP(hipGetLastError());
-  *Xres = (h.cur & 1) ? X1.p : X0.p;
-  if (res_out) {
-    res_out->success = 1;
-    res_out->fInit = h.fInit;
-    res_out->gradNormInit = h.gradNormInit;
-    res_out->fOpt = h.f1;
-    res_out->gradNormOpt = h.ngf;
-    res_out->elapsedMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    res_out->tCGStatus = h.tcg_status;
-    res_out->outer_iterations = h.outer_it;
-    res_out->inner_iterations = h.inner_total;
-    res_out->accepted_steps = h.accepted;
-  }
-  return DCORA_OK;
-}
-
-// Same algorithm with the fused kernels of solver_fused.hip: per tCG iteration
-//   A (direction update + Q-apply + Riemannian Hessian correction + <d,Hd>)
-//   B (step length + vector updates + |r|^2 + dense preconditioner slices)
-//   C (stopping rule + slice sum + tangent projection + <z,r>)
-// B + C as one launch (k_fused_pc) where that form wins; DCORA_SOLVER_BC = pc / split forces one or the other
 // sum of the HIP-event times of the k_tcg_run launches recorded since the last read (gated no-op launches included)
 int DeviceProblem::profile_tcg_read(double *launches, double *total_us) {
   DCORA_HIP(hipSetDevice(device));
@@ -942,7 +793,254 @@ bool DeviceProblem::use_pc() const {
   return fused_pc_ready(m, ldm);
 }
 
-int DeviceProblem::rtr_dev_fused(const dcora_ropt_params &prm) {
+// What an RTR solve enqueues in each tCG form; DeviceProblem::rtr_dev paces it.  The forms:
+//   generic: the thread-per-variable kernels of kernels.hip, any layout -- per tCG iteration the Hessian SpMM with the
+//            direction update folded in (k_spmm_dir [+ k_hessfix], or k_spmm_dir_fix), k_tcg_update1, the
+//            preconditioner, k_tangent;
+//   split:   the fused kernels of solver_fused.hip (SE layout, r <= 8) -- per tCG iteration A (direction update +
+//            Q-apply + Riemannian Hessian correction + <d,Hd>), B (step length + vector updates + |r|^2 + dense
+//            preconditioner slices; with the sparse preconditioner its level replay follows), C (stopping rule + slice
+//            sum + tangent projection + <z,r>);
+//   pc:      A, then B + C in one launch (k_fused_pc, dense preconditioner) where that form wins; DCORA_SOLVER_BC = pc /
+//            split forces one or the other;
+//   run:     the whole tCG run of an RTR iteration as ONE launch (k_tcg_run) where the grid is co-resident and no
+//            other solve shares the device's launch path.  A run that gives up (tcg_abort_seq) or a launch that is
+//            refused switches it off for this problem: the iteration is taken again on the pc launches.
+struct DeviceProblem::RtrForm {
+  DeviceProblem &p;
+  TcgForm form;
+  int &seq;
+  const int solve_first;
+  SolverCtl *const c;
+  const CsrDev Qv;
+  const BsrDev Qbv;
+  const double *const Gp;
+  const long N;
+  const int nA, nP, nV, nPB;
+  const bool sparse;
+  // generic: the sparse preconditioner's permutations (and hub correction) ride in k_tcg_update1 / k_tangent; H d in
+  // one launch (k_spmm_dir_fix) when every long row is a Euclidean column and the partial slots fit
+  const SpFold sfg;
+  const bool hess_fused;
+  // fused forms
+  const int nPG;
+  const double *const Mi;  // null: B only updates, the sparse levels follow
+  // without hubs the sparse preconditioner's two permutations ride in B (scatter of the residual) and C (gather of z)
+  const bool folded;
+  const SpFold sf;
+  const int nsl;
+  const int nZ;  // <z, r> partial slots A sums in its prologue
+  // cost + gradient of an evaluation in one launch where the kernel exists (small CSR blocks; large blocks: the same
+  // on the block structure, k_spmm_bsrq<.., GRAD>), else Q-apply + rgrad
+  const bool gf, gfb;
+  unsigned *const sync_p;  // the run form's grid-step counters, zeroed by k_rtr_init / k_rtr_decide
+  const int nsync;
+  double *const dbuf[2];
+  double *const rbuf[2];
+
+  RtrForm(DeviceProblem &p_, TcgForm f, int &seq_)
+      : p(p_), form(f), seq(seq_), solve_first(seq_ + 1), c(p.ctl.p), Qv(p.Q.view()),
+        Qbv(p.has_bsr ? p.Qb.view() : BsrDev{}), Gp(p.has_G ? p.G.p : nullptr), N(p.nelem()), nA(p.npA()),
+        nP(p.npPose()), nV(p.npVec()), nPB(fused_pose_blocks(p.m)), sparse(p.sparse_precond),
+        sfg(f == TcgForm::generic && sparse ? p.sp.fold_generic() : SpFold()),
+        hess_fused(f == TcgForm::generic && p.hess_one_launch()),
+        nPG(sparse ? fused_update_grid(p.m) : fused_precond_grid(p.m)), Mi(sparse ? nullptr : p.Minv.p),
+        folded(sparse && p.sp.foldable()), sf(folded ? p.sp.fold() : SpFold{}), nsl(sparse ? 1 : -1),
+        nZ(f == TcgForm::pc || f == TcgForm::run ? fused_pc_blocks(p.m) : nPB),
+        gf(f != TcgForm::generic && !p.has_bsr && p.Q.n_long == 0), gfb(f != TcgForm::generic && p.has_bsr),
+        sync_p(f == TcgForm::run ? p.tcg_sync.p : nullptr), nsync(f == TcgForm::run ? tcg_run_sync_words() : 0),
+        dbuf{p.delta.p, p.delta2.p}, rbuf{p.res.p, p.res2.p} {}
+
+  bool outer_done() const { return p.hf->outer_done_seq >= solve_first; }
+  bool stopped(int tcg_first) const { return p.hf->tcg_done_seq >= tcg_first || outer_done(); }
+  int nAe() const { return gf ? nPB : nA; }  // {<XQ,X>, <X,G>} partial slots of an evaluation
+
+  // f and the Riemannian gradient at buffer `sel` (the trial point: sel = 1); sel = 0 starts the solve with null gates
+  // (its control block is armed by k_rtr_init, which follows).  Returns the |grad|^2 partial slots written.
+  int eval(int sel) {
+    const auto g = [&] {
+      ++seq;
+      return sel ? Gate{c, seq, 1} : Gate{};
+    };
+    const Buf2 kNoBuf{{nullptr, nullptr}};  // EG of the block-structure evaluation: nobody reads it
+    if (form == TcgForm::generic) {
+      // (enq_qapply, not the CSR kernel directly: the number of partial slots npA() counts follows the Q-apply kernel
+      // that runs -- block-CSR for large pose graphs; the thread-per-pose rgrad whatever `group` says)
+      p.enq_qapply(p.Xb(), sel, Gp, p.EGb(), sel, p.pA.p, g());
+      launch_rgrad(p.st, p.m, p.Xb(), p.EGb(), p.RGb(), p.Sb(), sel, p.pB.p, g());
+      return nP;
+    }
+    if (gf) return launch_fused_grad(p.st, p.m, Qv, p.Xb(), Gp, p.EGb(), p.RGb(), p.Sb(), sel, p.pA.p, p.pB.p, nullptr, g());
+    if (gfb)
+      return launch_fused_grad_bsr(p.st, p.m.r, p.m.d, Qbv, p.Xb(), Gp, kNoBuf, p.RGb(), p.Sb(), sel, p.pA.p, p.pB.p,
+                                   nullptr, g());
+    p.enq_qapply(p.Xb(), sel, Gp, p.EGb(), sel, p.pA.p, g());
+    return p.enq_rgrad(p.Xb(), p.EGb(), p.RGb(), p.Sb(), sel, p.pB.p, g());
+  }
+
+  // The first block of an RTR iteration, z0 = P grad (generic: k_tcg_begin, the preconditioner, k_tangent; fused: B in
+  // "first" mode, B + C in one launch, or the whole run).  Gated by the RTR loop's own stamp, it picks the accepted
+  // iterate's buffers from the control block when it starts.  Returns the seq of its first launch, < 0 when a launch
+  // failed (the error is set).
+  int first() {
+    switch (form) {
+      case TcgForm::generic: {
+        launch_tcg_begin(p.st, N, p.RGb(), p.eta.p, p.Heta.p, p.res.p, c, ++seq);
+        const int s = seq;
+        p.enq_minv(buf1(p.res.p), p.Zt.p, nullptr, 0, Gate{c, ++seq, 1});
+        launch_tangent(p.st, p.m, p.Xb(), p.Zt.p, p.z.p, p.res.p, p.p3.p, nullptr, 0, c, p.hf_dev, ++seq, 1, 0);
+        return s;
+      }
+      case TcgForm::run: {
+        const int s = launch_run();
+        if (s != 0) return s;
+        // refused: the device does not grant the run its dynamic LDS -- the same fall-back as a run that gave up
+        p.tcg_run_ok = false;
+        form = TcgForm::pc;
+      }
+        [[fallthrough]];
+      case TcgForm::pc:
+        if (launch_fused_pc(p.st, p.m, p.ldm, Mi, p.RGb(), p.Xb(), nullptr, nullptr, p.eta.p, p.Heta.p, nullptr, rbuf[0],
+                            p.z.p, nullptr, 0, p.p3.p, c, p.hf_dev, ++seq, 0, 1) < 0) {
+          set_last_error("k_fused_pc could not be launched on this device");
+          return -1;
+        }
+        return seq;
+      case TcgForm::split:
+        launch_fused_precond(p.st, p.m, p.ldm, Mi, p.RGb(), nullptr, nullptr, p.eta.p, p.Heta.p, nullptr, rbuf[0],
+                             p.Zpart.p, nullptr, 0, p.p2.p, c, p.hf_dev, ++seq, 0, 1, sf);
+        return seq;
+    }
+    return -1;
+  }
+  // k_tcg_run, between HIP events when profiled; returns its seq, 0 when the launch was refused, -1 on a failure
+  int launch_run() {
+    hipEvent_t e1 = nullptr;
+    if (p.profile_tcg_runs) {
+      while (p.run_events.size() < p.run_events_used + 2) {
+        hipEvent_t e = nullptr;
+        if (hipEventCreate(&e) != hipSuccess) {
+          set_last_error("hipEventCreate failed (k_tcg_run profile)");
+          return -1;
+        }
+        p.run_events.push_back(e);
+      }
+      (void)hipEventRecord(p.run_events[p.run_events_used], p.st);
+      e1 = p.run_events[p.run_events_used + 1];
+      p.run_events_used += 2;
+    }
+    if (launch_tcg_run(p.st, p.m, p.ldm, Mi, Qv, p.RGb(), p.Xb(), p.Sb(), dbuf[0], dbuf[1], p.Hd.p, p.eta.p, p.Heta.p,
+                       p.z.p, p.p1.p, p.p3.p, p.pC.p, p.tcg_sync.p, c, p.hf_dev, ++seq) < 0) {
+      if (e1) p.run_events_used -= 2;
+      return 0;
+    }
+    if (e1) (void)hipEventRecord(e1, p.st);
+    return seq;
+  }
+  // The rest of the first block in the split form: the sparse replay and C.  A rejected step (k_rtr_decide said so in
+  // reject_seq) left the iterate and its gradient where they were: z0 is the one of the iteration before, whose
+  // unprojected form the finish kernel kept in W (free on this path) -- one application of the sparse preconditioner
+  // less per rejection (0.25 per RBCD iteration on the 100k lattice).
+  void rest(bool rejected) {
+    if (form != TcgForm::split) return;
+    if (sparse && rejected) {
+      launch_fused_finish(p.st, p.m, p.Xb(), p.W.p, rbuf[0], p.z.p, nullptr, 0, p.p3.p, c, p.hf_dev, ++seq, 0, 1, 1,
+                          SpFold{});
+      return;
+    }
+    if (sparse) p.sp.apply(p.st, p.m.r, buf1(rbuf[0]), p.Zpart.p, Gate{c, ++seq, 1}, folded);
+    launch_fused_finish(p.st, p.m, p.Xb(), p.Zpart.p, rbuf[0], p.z.p, nullptr, 0, p.p3.p, c, p.hf_dev, ++seq, 0, 1, nsl,
+                        sf, sparse ? p.W.p : nullptr);
+  }
+
+  // The sparse replay behind the verdict of the step kernel just enqueued (k_tcg_update1 / B), which decides whether
+  // the tCG run goes on (boundary, negative curvature).  The replay's launches behind a step that stopped are no-ops of
+  // ~4 us each, and runs of one or two iterations are the rule on the large blocks.  So only the replay's FIRST launch
+  // is enqueued on speculation: the host reads the verdict while the GPU runs it, and enqueues the rest only behind a
+  // step that went on.  (The same pacing on the dense one-launch form measured slower -- 1846 -> 1729-1857 it/s on the
+  // headline: its trace holds 69 gated no-op launches among 38 800, and waiting for a verdict there only opens gaps --
+  // and is not kept.)  Returns 1: the run goes on, 0: it stopped, -1: spin timeout.
+  int replay(Buf2 R, double *Z, bool levels_only, int tcg_first) {
+    const int seq_step = seq;
+    bool timed = false;
+    const std::function<bool()> verdict = [&]() {
+      if (!spin_until([&] { return p.hf->go_seq >= seq_step || stopped(tcg_first); }, 20.0)) {
+        timed = true;
+        return false;
+      }
+      return !stopped(tcg_first);
+    };
+    p.sp.apply(p.st, p.m.r, R, Z, Gate{c, ++seq, 2}, levels_only, &verdict);
+    if (timed) return -1;
+    return stopped(tcg_first) ? 0 : 1;
+  }
+
+  // tCG iteration j; the direction ping-pongs between two buffers (the fused forms' residual too).  Returns 1: the
+  // run goes on, 0: it stopped, -1: spin timeout.
+  int tcg_iter(int j, int max_inner, int tcg_first) {
+    const int par = j & 1;
+    if (form == TcgForm::generic) {
+      // the direction update (the tCG recurrence: iteration 0 starts it, later ones finish iteration j - 1) rides in
+      // the Hessian SpMM (k_spmm_dir)
+      double *const dcur = dbuf[par];
+      int nP1 = nP;
+      if (hess_fused) {
+        nP1 = launch_spmm_dir_fix(p.st, p.m, Qv, p.Xb(), p.Sb(), p.z.p, dbuf[par ^ 1], dcur, p.Hd.p, p.p3.p, nP, p.p1.p,
+                                  c, ++seq, j);
+      } else {
+        launch_spmm_dir(p.st, p.m.r, Qv, p.z.p, dbuf[par ^ 1], dcur, p.W.p, p.p3.p, nP, c, ++seq, j);
+        launch_hessfix(p.st, p.m, p.Xb(), p.Sb(), dcur, p.W.p, p.Hd.p, p.p1.p, Gate{c, ++seq, 2});
+      }
+      launch_tcg_update1(p.st, N, dcur, p.Hd.p, p.eta.p, p.Heta.p, p.res.p, p.p1.p, nP1, p.p2.p, c, p.hf_dev, ++seq, j,
+                         p.m.r, sfg);
+      if (sfg.y) {
+        const int go = replay(buf1(p.res.p), p.Zt.p, true, tcg_first);
+        if (go <= 0) return go;
+      } else {
+        p.enq_minv(buf1(p.res.p), p.Zt.p, p.p2.p, nV, Gate{c, ++seq, 2});
+      }
+      launch_tangent(p.st, p.m, p.Xb(), p.Zt.p, p.z.p, p.res.p, p.p3.p, p.p2.p, nV, c, p.hf_dev, ++seq, 2, j, sfg);
+      // the inner loop exhausted: the bookkeeping of the last direction update (status TR_MAXITER) has no next SpMM
+      if (j == max_inner - 1) launch_tcg_update2(p.st, N, p.z.p, dcur, p.p3.p, nP, c, p.hf_dev, ++seq, j);
+      return 1;
+    }
+    const int nP1 = launch_fused_hess(p.st, p.m, Qv, p.z.p, dbuf[par ^ 1], dbuf[par], p.Xb(), p.Sb(), p.Hd.p, p.p3.p,
+                                      nZ, p.p1.p, c, ++seq, j, p.has_bsr ? &Qbv : nullptr);
+    if (form == TcgForm::pc) {
+      launch_fused_pc(p.st, p.m, p.ldm, Mi, p.RGb(), p.Xb(), dbuf[par], p.Hd.p, p.eta.p, p.Heta.p, rbuf[par],
+                      rbuf[par ^ 1], p.z.p, p.p1.p, nP1, p.p3.p, c, p.hf_dev, ++seq, j, 0, p.pC.p);
+      return 1;
+    }
+    launch_fused_precond(p.st, p.m, p.ldm, Mi, p.RGb(), dbuf[par], p.Hd.p, p.eta.p, p.Heta.p, rbuf[par], rbuf[par ^ 1],
+                         p.Zpart.p, p.p1.p, nP1, p.p2.p, c, p.hf_dev, ++seq, j, 0, sf);
+    if (sparse) {
+      const int go = replay(buf1(rbuf[par ^ 1]), p.Zpart.p, folded, tcg_first);
+      if (go <= 0) return go;
+    }
+    launch_fused_finish(p.st, p.m, p.Xb(), p.Zpart.p, rbuf[par ^ 1], p.z.p, p.p2.p, nPG, p.p3.p, c, p.hf_dev, ++seq, j,
+                        0, nsl, sf);
+    return 1;
+  }
+
+  // the trial point; returns the {<eta, grad>, <eta, H eta>} partial slots written
+  int trial() {
+    switch (form) {
+      case TcgForm::generic:
+        launch_retract(p.st, p.m, p.Xb(), p.eta.p, 1.0, p.Xb(), 1, p.RGb(), p.Heta.p, p.pC.p, Gate{c, ++seq, 1});
+        return nP;
+      case TcgForm::split:
+        return p.enq_retract(p.Xb(), p.eta.p, 1.0, p.Xb(), 1, p.RGb(), p.Heta.p, p.pC.p, Gate{c, ++seq, 1});
+      default:  // the kernel that ended the tCG run has retracted already, one partial pair per workgroup
+        return nZ;
+    }
+  }
+};
+
+// RTRNewton with preconditioned Steihaug-Toint tCG, fully device-resident: the host enqueues the kernel sequence of
+// the form (RtrForm), stays at most kLookahead tCG iterations ahead of the GPU and learns about terminations from
+// host-mapped flags.  Returns without synchronising.  (ref src/QuadraticOptimizer.cpp:52-108, 234-280; ROPTLIB
+// semantics: SURVEY.md 3.4)
+int DeviceProblem::rtr_dev(const dcora_ropt_params &prm, TcgForm form) {
   constexpr int kLookahead = 2;
   const auto t0 = std::chrono::steady_clock::now();
   t0_ms_ = std::chrono::duration<double, std::milli>(t0.time_since_epoch()).count();
@@ -959,105 +1057,38 @@ int DeviceProblem::rtr_dev_fused(const dcora_ropt_params &prm) {
     seq_ = 0;
   }
   int &seq = seq_;
-  SolverCtl *c = ctl.p;
-  CtlInit ci;  // written by k_rtr_init, the third kernel of the solve: the first two run with a null gate
+  RtrForm f(*this, form, seq);
+  CtlInit ci;  // written by k_rtr_init, which follows the start point's evaluation (that runs with null gates)
   ci.enable = 1;
   ci.tol = prm.gradnorm_tol;
   ci.Delta = prm.RTR_initial_radius;
-  ci.maxDelta = single ? prm.RTR_initial_radius : 5 * prm.RTR_initial_radius;
+  ci.maxDelta = single ? prm.RTR_initial_radius : 5 * prm.RTR_initial_radius;  // :240-241, :259-260
   ci.max_outer = max_outer;
   ci.stop_on_accept = single ? 1 : 0;
   ci.max_inner = max_inner;
-  const int solve_first = seq + 1;
-  const CsrDev Qv = Q.view();
-  const BsrDev Qbv = has_bsr ? Qb.view() : BsrDev{};
-  const double *Gp = has_G ? G.p : nullptr;
-  const int nA = npA(), nPB = fused_pose_blocks(m);
-  const int nPG = sparse_precond ? fused_update_grid(m) : fused_precond_grid(m);
-  const double *Mi = sparse_precond ? nullptr : Minv.p;  // null: B only updates, the sparse levels follow
-  // without hubs the sparse preconditioner's two permutations ride in B (scatter of the residual) and C (gather of z)
-  const bool folded = sparse_precond && sp.foldable();
-  const SpFold sf = folded ? sp.fold() : SpFold{};
-  const int nsl = sparse_precond ? 1 : -1;
-  // With the sparse preconditioner the host enqueues the replay behind the step-length kernel's verdict (below); the
-  // same pacing on the dense one-launch form measured slower (1846 -> 1729-1857 it/s on the headline: its trace holds 69
-  // gated no-op launches among 38 800, and waiting for a verdict there only opens gaps) and is not kept.
-  // dense preconditioner: B and C are ONE launch (k_fused_pc); DCORA_SOLVER_BC=split keeps the three-launch form
-  const bool pc = use_pc();
-  // dense one-launch form: the whole tCG run of an RTR iteration as ONE launch (k_tcg_run) where the grid is co-resident
-  // and no other solve shares the device's launch path; a run that gives up (tcg_abort_seq) switches the form off for
-  // this problem and the iteration is repeated on the launches
-  bool run_form = pc && tcg_run_ok && !concurrent_solves;
-  unsigned *sync_p = run_form ? tcg_sync.p : nullptr;
-  const int nsync = run_form ? tcg_run_sync_words() : 0;
-  const int nZ = pc ? fused_pc_blocks(m) : nPB;  // <z, r> partial slots A sums in its prologue
-  double *dbuf[2] = {delta.p, delta2.p};
-  double *rbuf[2] = {res.p, res2.p};
   auto timed_out = [&]() {
-    set_last_error("rtr_dev_fused: device did not make progress (spin timeout)");
+    set_last_error("rtr_dev: device did not make progress (spin timeout)");
     return DCORA_ERR_HIP;
   };
-  auto outer_done = [&]() { return hf->outer_done_seq >= solve_first; };
-  // f(x0), grad(x0) from buffer 0 (null gate: the control block of this solve does not exist yet)
-  // cost + gradient of an evaluation in one launch where the kernel exists (small CSR blocks), else Q-apply + rgrad
-  const bool gf = !has_bsr && Q.n_long == 0;
-  const bool gfb = has_bsr;       // large blocks: the same in one launch on the block structure (k_spmm_bsrq<.., GRAD>)
-  const Buf2 kNoBuf{{nullptr, nullptr}};  // EG of the fused evaluation: nobody reads it, so it is not written
-  const int nAe = gf ? nPB : nA;  // {<XQ,X>, <X,G>} partial slots of an evaluation
-  int nG;
-  ++seq;
-  if (gf) {
-    nG = launch_fused_grad(st, m, Qv, Xb(), Gp, EGb(), RGb(), Sb(), 0, pA.p, pB.p, nullptr, Gate{});
-  } else if (gfb) {
-    nG = launch_fused_grad_bsr(st, m.r, m.d, Qbv, Xb(), Gp, kNoBuf, RGb(), Sb(), 0, pA.p, pB.p, nullptr, Gate{});
-  } else {
-    enq_qapply(Xb(), 0, Gp, EGb(), 0, pA.p, Gate{});
-    ++seq;
-    nG = enq_rgrad(Xb(), EGb(), RGb(), Sb(), 0, pB.p, Gate{});
-  }
-  launch_rtr_init(st, pA.p, nAe, pB.p, nG, c, hf_dev, ++seq, ci, sync_p, nsync);
-  int last_pace_seq = seq;
-  std::vector<int> fin_seq((size_t)std::max(1, max_inner));
-  // The first kernel of an RTR iteration (z0 = P grad: B in "first" mode, or B + C in one launch) needs nothing the host
-  // has to decide: it is gated by the RTR loop's own stamp and picks the accepted iterate's buffers from the control
-  // block when it starts.  So it is enqueued BEHIND k_rtr_init / k_rtr_decide at once, before the host has seen their
-  // verdict: the GPU runs it while the host reads the flag and enqueues the tCG iteration behind it, instead of idling
-  // for that round trip at every iteration (a loop that had ended leaves one gated no-op).  Returns its seq, < 0 when
-  // the launch failed.
-  auto enqueue_first = [&]() -> int {
-    if (run_form) {
-      hipEvent_t e1 = nullptr;
-      if (profile_tcg_runs) {
-        while (run_events.size() < run_events_used + 2) {
-          hipEvent_t e = nullptr;
-          if (hipEventCreate(&e) != hipSuccess) return -1;
-          run_events.push_back(e);
-        }
-        (void)hipEventRecord(run_events[run_events_used], st);
-        e1 = run_events[run_events_used + 1];
-        run_events_used += 2;
-      }
-      if (launch_tcg_run(st, m, ldm, Mi, Qv, RGb(), Xb(), Sb(), dbuf[0], dbuf[1], Hd.p, eta.p, Heta.p, z.p, p1.p, p3.p,
-                         pC.p, tcg_sync.p, c, hf_dev, ++seq) < 0)
-        return -1;
-      if (e1) (void)hipEventRecord(e1, st);
-      return seq;
-    }
-    if (pc) {
-      if (launch_fused_pc(st, m, ldm, Mi, RGb(), Xb(), nullptr, nullptr, eta.p, Heta.p, nullptr, rbuf[0], z.p, nullptr,
-                          0, p3.p, c, hf_dev, ++seq, 0, 1) < 0)
-        return -1;
-    } else {
-      launch_fused_precond(st, m, ldm, Mi, RGb(), nullptr, nullptr, eta.p, Heta.p, nullptr, rbuf[0], Zpart.p,
-                           nullptr, 0, p2.p, c, hf_dev, ++seq, 0, 1, sf);
-    }
-    return seq;
+  auto first_failed = [&]() -> int {
+    DCORA_HIP(hipStreamSynchronize(st));
+    return DCORA_ERR_HIP;
   };
   auto time_is_up = [&]() {  // TimeBound :252
     return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 5.0;
   };
-  int next_first_seq = time_is_up() ? 0 : enqueue_first();
-  auto run_gave_up = [&]() { return run_form && hf->tcg_abort_seq >= solve_first; };
+  auto run_gave_up = [&]() { return f.form == TcgForm::run && hf->tcg_abort_seq >= f.solve_first; };
+
+  // f(x0), grad(x0) from buffer 0
+  int nG = f.eval(0);
+  launch_rtr_init(st, pA.p, f.nAe(), pB.p, nG, f.c, hf_dev, ++seq, ci, f.sync_p, f.nsync);
+  int last_pace_seq = seq;
+  std::vector<int> last_seq((size_t)std::max(1, max_inner));  // of every tCG iteration's last launch
+  // The first block of an RTR iteration needs nothing the host has to decide, so it is enqueued BEHIND k_rtr_init /
+  // k_rtr_decide at once, before the host has seen their verdict: the GPU runs it while the host reads the flag and
+  // enqueues the tCG iteration behind it, instead of idling for that round trip at every iteration (a loop that had
+  // ended leaves gated no-ops).  0: the time bound had passed when it was due.
+  int next_first_seq = time_is_up() ? 0 : f.first();
   // The host runs ahead of the device by design, but it must not LEAVE while a one-launch run may still give up: the
   // recovery below is the only place that repeats the iteration, and what the caller enqueues next builds on its
   // result.  So with the run form the loop takes one more turn after the last iteration (`tail`), which only waits
@@ -1066,15 +1097,11 @@ int DeviceProblem::rtr_dev_fused(const dcora_ropt_params &prm) {
   // (Round 5: without it a last iteration whose run gave up was lost without a trace -- a flaky bit difference between
   // ranks sharing one GPU, where other ranks' waiting kernels keep the grid from being co-resident.)
   int last_run_seq = 0;
-  for (int outer = 0; outer < max_outer || (run_form && last_run_seq > 0); ++outer) {
+  for (int outer = 0; outer < max_outer || (f.form == TcgForm::run && last_run_seq > 0); ++outer) {
     const bool tail = outer >= max_outer;
-    if (!tail && next_first_seq < 0) {
-      DCORA_HIP(hipStreamSynchronize(st));
-      set_last_error("k_fused_pc could not be launched on this device");
-      return DCORA_ERR_HIP;
-    }
+    if (!tail && next_first_seq < 0) return first_failed();
     const int need_seq = tail ? last_run_seq : last_pace_seq;
-    if (!spin_until([&] { return hf->last_seq_done >= need_seq || outer_done() || run_gave_up(); }, 20.0))
+    if (!spin_until([&] { return hf->last_seq_done >= need_seq || f.outer_done() || run_gave_up(); }, 20.0))
       return timed_out();
     if (tail && !run_gave_up()) break;
     if (run_gave_up()) {
@@ -1084,95 +1111,39 @@ int DeviceProblem::rtr_dev_fused(const dcora_ropt_params &prm) {
       // nothing but scratch (eta, H eta, the trial point and the control block are written when a run ENDS).
       DCORA_HIP(hipStreamSynchronize(st));
       const int armed = INT_MAX;
-      DCORA_HIP(hipMemcpy(&c->outer_done_stamp, &armed, sizeof(int), hipMemcpyHostToDevice));
-      const bool before = hf->last_seq_done < last_pace_seq;  // the decision of iteration outer - 1 never ran
+      DCORA_HIP(hipMemcpy(&f.c->outer_done_stamp, &armed, sizeof(int), hipMemcpyHostToDevice));
+      if (hf->last_seq_done < last_pace_seq) --outer;  // the decision of iteration outer - 1 never ran
       hf->tcg_abort_seq = 0;
       tcg_run_ok = false;
-      run_form = false;
-      if (before) --outer;
-      next_first_seq = enqueue_first();
-      if (before) {
-        // the evaluation + decision of the repeated iteration follow below as usual
-      }
-      if (next_first_seq < 0) continue;
+      f.form = TcgForm::pc;
+      next_first_seq = f.first();
+      if (next_first_seq < 0) return first_failed();
     }
-    if (outer_done()) break;
+    if (f.outer_done()) break;
     if (next_first_seq == 0) break;  // the time bound had passed when this iteration's first kernel was due
-    // z0 = P(grad): B in "first" mode streams the preconditioner over grad, C projects and forms <z0, r0>
     const int tcg_first_seq = next_first_seq;
-    last_run_seq = run_form ? tcg_first_seq : 0;
-    if (!pc) {
-      // A rejected step (k_rtr_decide said so in reject_seq) left the iterate and its gradient where they were: z0 is
-      // the one of the iteration before, whose unprojected form the finish kernel kept in W (free on this path) --
-      // one application of the sparse preconditioner less per rejection (0.25 per RBCD iteration on the 100k lattice).
-      const bool reuse_z0 = sparse_precond && outer > 0 && hf->reject_seq == last_pace_seq;
-      if (reuse_z0) {
-        launch_fused_finish(st, m, Xb(), W.p, rbuf[0], z.p, nullptr, 0, p3.p, c, hf_dev, ++seq, 0, 1, 1, SpFold{});
-      } else {
-        if (sparse_precond) sp.apply(st, m.r, buf1(rbuf[0]), Zpart.p, Gate{c, ++seq, 1}, folded);
-        launch_fused_finish(st, m, Xb(), Zpart.p, rbuf[0], z.p, nullptr, 0, p3.p, c, hf_dev, ++seq, 0, 1, nsl, sf,
-                            sparse_precond ? W.p : nullptr);
-      }
-    }
-    for (int j = 0; j < max_inner && !run_form; ++j) {
+    last_run_seq = f.form == TcgForm::run ? tcg_first_seq : 0;
+    f.rest(outer > 0 && hf->reject_seq == last_pace_seq);
+    for (int j = 0; j < max_inner && f.form != TcgForm::run; ++j) {
       if (j >= kLookahead) {
-        const int need = fin_seq[j - kLookahead];
-        if (!spin_until(
-                [&] { return hf->last_seq_done >= need || hf->tcg_done_seq >= tcg_first_seq || outer_done(); }, 20.0))
+        const int need = last_seq[j - kLookahead];
+        if (!spin_until([&] { return hf->last_seq_done >= need || f.stopped(tcg_first_seq); }, 20.0))
           return timed_out();
       }
       if (hf->tcg_done_seq >= tcg_first_seq) break;
-      const int par = j & 1;
-      const int nP1 = launch_fused_hess(st, m, Qv, z.p, dbuf[par ^ 1], dbuf[par], Xb(), Sb(), Hd.p, p3.p, nZ, p1.p,
-                                        c, ++seq, j, has_bsr ? &Qbv : nullptr);
-      if (pc) {
-        launch_fused_pc(st, m, ldm, Mi, RGb(), Xb(), dbuf[par], Hd.p, eta.p, Heta.p, rbuf[par], rbuf[par ^ 1], z.p,
-                        p1.p, nP1, p3.p, c, hf_dev, ++seq, j, 0, pC.p);
-      } else {
-        launch_fused_precond(st, m, ldm, Mi, RGb(), dbuf[par], Hd.p, eta.p, Heta.p, rbuf[par], rbuf[par ^ 1],
-                             Zpart.p, p1.p, nP1, p2.p, c, hf_dev, ++seq, j, 0, sf);
-        if (sparse_precond) {
-          // B decides whether this tCG run goes on (boundary, negative curvature); the replay's launches behind a B
-          // that stopped are no-ops of ~4 us each, and runs of one or two iterations are the rule on the large
-          // blocks.  So only the replay's FIRST launch is enqueued on speculation: the host reads B's verdict while
-          // the GPU runs it, and enqueues the rest (and C) only behind a B that went on.
-          const int seqB = seq;
-          bool timed = false;
-          const std::function<bool()> verdict = [&]() {
-            if (!spin_until(
-                    [&] {
-                      return hf->go_seq >= seqB || hf->tcg_done_seq >= tcg_first_seq || outer_done();
-                    },
-                    20.0)) {
-              timed = true;
-              return false;
-            }
-            return !(hf->tcg_done_seq >= tcg_first_seq || outer_done());
-          };
-          sp.apply(st, m.r, buf1(rbuf[par ^ 1]), Zpart.p, Gate{c, ++seq, 2}, folded, &verdict);
-          if (timed) return timed_out();
-          if (hf->tcg_done_seq >= tcg_first_seq || outer_done()) break;
-        }
-        launch_fused_finish(st, m, Xb(), Zpart.p, rbuf[par ^ 1], z.p, p2.p, nPG, p3.p, c, hf_dev, ++seq, j, 0, nsl,
-                            sf);
-      }
-      fin_seq[j] = seq;
+      const int go = f.tcg_iter(j, max_inner, tcg_first_seq);
+      if (go < 0) return timed_out();
+      if (go == 0) break;
+      last_seq[j] = seq;
     }
-    // (one-launch dense form: the kernel that ended the tCG run has retracted already, one partial pair per workgroup)
-    const int nR = pc ? nZ : enq_retract(Xb(), eta.p, 1.0, Xb(), 1, RGb(), Heta.p, pC.p, Gate{c, ++seq, 1});
-    if (gf) {
-      nG = launch_fused_grad(st, m, Qv, Xb(), Gp, EGb(), RGb(), Sb(), 1, pA.p, pB.p, nullptr, Gate{c, ++seq, 1});
-    } else if (gfb) {
-      nG = launch_fused_grad_bsr(st, m.r, m.d, Qbv, Xb(), Gp, kNoBuf, RGb(), Sb(), 1, pA.p, pB.p, nullptr,
-                                 Gate{c, ++seq, 1});
-    } else {
-      enq_qapply(Xb(), 1, Gp, EGb(), 1, pA.p, Gate{c, ++seq, 1});
-      nG = enq_rgrad(Xb(), EGb(), RGb(), Sb(), 1, pB.p, Gate{c, ++seq, 1});
-    }
-    launch_rtr_decide(st, pA.p, nAe, pB.p, nG, pC.p, nR, c, hf_dev, ++seq, sync_p, nsync);
+    // ---- trial point, model ratio, acceptance ----
+    const int nR = f.trial();
+    nG = f.eval(1);
+    launch_rtr_decide(st, pA.p, f.nAe(), pB.p, nG, pC.p, nR, f.c, hf_dev, ++seq, f.sync_p, f.nsync);
     last_pace_seq = seq;
-    if (outer + 1 < max_outer) next_first_seq = time_is_up() ? 0 : enqueue_first();
+    if (outer + 1 < max_outer) next_first_seq = time_is_up() ? 0 : f.first();
   }
+  pending_ = true;
   return DCORA_OK;
 }
 

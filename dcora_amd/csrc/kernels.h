@@ -114,7 +114,8 @@ struct Gate {
 // ---- SpMM: Y = X * A (+ G); optional partial dots {sum (X*A) o X, sum X o G}, 2 per block ---------------
 int spmm_grid(int nrows, int r);
 // W = (-z + beta d_old) Q with the direction written to d_new and the tCG scalar recurrence of iteration `iter`
-// (k_tcg_init for iter 0, k_tcg_update2 of iteration iter - 1 otherwise) folded in
+// (iter 0: its start, z_r = d_Pd = <z, r>, e_Pe = e_Pd = 0; otherwise the update of iteration iter - 1, as k_tcg_update2
+// forms it after the last iteration) folded in
 // k_spmm_dir with k_hessfix folded in (one launch per tCG iteration of the generic layout); returns the number of
 // <delta, Hd> partial slots written to p1.  spmm_dir_fix_grid: 0 when r is too large for whole items per workgroup.
 int spmm_dir_fix_grid(const ManiDesc &m, int nrows);
@@ -189,8 +190,6 @@ void launch_rtr_init(hipStream_t st, const double *pA, int npA, const double *pB
                      HostFlags *hf, int seq, CtlInit ci = CtlInit(), unsigned *tcg_sync = nullptr, int nsync = 0);
 void launch_tcg_begin(hipStream_t st, long nelem, Buf2 grad, double *eta, double *Heta, double *res,
                       SolverCtl *ctl, int seq);
-void launch_tcg_init(hipStream_t st, long nelem, const double *z, const double *p3, int np3, double *delta,
-                     SolverCtl *ctl, int seq);
 void launch_tcg_update1(hipStream_t st, long nelem, const double *delta, const double *Hd, double *eta,
                         double *Heta, double *res, const double *p1, int np1, double *p2, SolverCtl *ctl,
                         HostFlags *hf, int seq, int iter, int r = 1, SpFold sf = SpFold());

@@ -274,7 +274,8 @@ __global__ __launch_bounds__(kBlock) void k_spmm(int r, CsrDev A, Buf2 Xb, int s
 // Generic-layout tCG, iteration `iter`: the direction update of the previous iteration folded into the Hessian SpMM.
 //   delta_new = -z + beta delta_old   (beta = <z, r>_new / <z, r>_old from the partials p3; iter 0: delta_new = -z)
 //   W = delta_new Q                   (delta_new formed in the gather, written for the block's own columns)
-// and the scalar recurrence of ROPTLIB's tCG_TR that k_tcg_init / k_tcg_update2 keep (block 0).  delta_old and
+// and the scalar recurrence of ROPTLIB's tCG_TR (block 0): iteration 0 starts it (z_r = d_Pd = <z, r>, e_Pe = e_Pd = 0),
+// later ones finish iteration iter - 1 as k_tcg_update2 does after the last one.  delta_old and
 // delta_new are different buffers: other workgroups still gather the old direction.
 // ------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void k_spmm_dir(int r, CsrDev A, const double *__restrict__ z,
@@ -1622,23 +1623,6 @@ __global__ __launch_bounds__(kBlock) void k_tcg_begin(long nelem, Buf2 gradb, do
     ctl->tcg_done_stamp = INT_MAX;
   }
 }
-// delta = -z, z_r = <z, r>, d_Pd = z_r, e_Pe = e_Pd = 0
-__global__ __launch_bounds__(kBlock) void k_tcg_init(long nelem, const double *__restrict__ z,
-                                                     const double *__restrict__ p3, int np3,
-                                                     double *__restrict__ delta, SolverCtl *ctl, int seq) {
-  if (gated(ctl, seq, 1)) return;
-  __shared__ double s_red[16];
-  const double z_r = sum_partials(p3, np3, 1, 0, s_red);
-  for (long i = (long)blockIdx.x * kBlock + threadIdx.x; i < nelem; i += (long)gridDim.x * kBlock)
-    delta[i] = -z[i];
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    ctl->z_r[0] = z_r;
-    ctl->d_Pd[0] = z_r;
-    ctl->e_Pe[0] = 0;
-    ctl->e_Pd[0] = 0;
-  }
-}
-
 __global__ __launch_bounds__(kBlock) void k_tcg_update1(long nelem, const double *__restrict__ delta,
                                                         const double *__restrict__ Hd, double *__restrict__ eta,
                                                         double *__restrict__ Heta, double *__restrict__ res,
@@ -1678,7 +1662,7 @@ __global__ __launch_bounds__(kBlock) void k_tcg_update1(long nelem, const double
   const double step =
       boundary ? (-e_Pd + sqrt(e_Pd * e_Pd + d_Pd * (Delta * Delta - e_Pe))) / d_Pd : alpha;
   // a run that goes on says so before the vector work: the host enqueues the sparse replay behind this verdict
-  // (DeviceProblem::rtr_dev); a run that stops writes tcg_done_seq below
+  // (DeviceProblem::RtrForm::replay); a run that stops writes tcg_done_seq below
   if (!boundary && blockIdx.x == 0 && threadIdx.x == 0) host_store(&hf->go_seq, seq);
   double acc = 0;
   if (in0) {
@@ -1799,10 +1783,6 @@ void launch_tcg_begin(hipStream_t st, long nelem, Buf2 grad, double *eta, double
                       SolverCtl *ctl, int seq) {
   hipLaunchKernelGGL(k_tcg_begin, dim3(vec_grid(nelem)), dim3(kBlock), 0, st, nelem, grad, eta, Heta, res, ctl,
                      seq);
-}
-void launch_tcg_init(hipStream_t st, long nelem, const double *z, const double *p3, int np3, double *delta,
-                     SolverCtl *ctl, int seq) {
-  hipLaunchKernelGGL(k_tcg_init, dim3(vec_grid(nelem)), dim3(kBlock), 0, st, nelem, z, p3, np3, delta, ctl, seq);
 }
 void launch_tcg_update1(hipStream_t st, long nelem, const double *delta, const double *Hd, double *eta,
                         double *Heta, double *res, const double *p1, int np1, double *p2, SolverCtl *ctl,

@@ -190,18 +190,9 @@ int RaRbcdSession::solve(RaAgentDev &a, const double *start, double **result) {
   launch_spmm(st, r, a.coupling.view(), buf1(Xg.p), 0, nullptr, buf1(pb.G.p), 0, nullptr, Gate{});
   pb.has_G = true;
   DCORA_HIP(hipMemcpyAsync(pb.X0.p, start, sizeof(double) * (size_t)r * a.k, hipMemcpyDeviceToDevice, st));
-  Buf2 Xres{{nullptr, nullptr}};
-  const SolverCtl *cs = nullptr;
-  int rc = pb.optimize_dev(opt.local, &Xres, &cs);
+  int rc = pb.optimize_dev(opt.local);
+  if (!rc) rc = pb.result(result);
   if (rc) return rc;
-  if (cs) {  // a solver that keeps its choice of buffer on the device: read it back
-    dcora_ropt_result tmp;
-    rc = pb.fetch_result(&tmp);
-    if (rc) return rc;
-    *result = pb.result_index() ? pb.X1.p : pb.X0.p;
-  } else {
-    *result = Xres.p[0];
-  }
   last_solver = &pb;
   return DCORA_OK;
 }

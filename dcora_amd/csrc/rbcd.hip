@@ -26,16 +26,18 @@ static void nesterov(hipStream_t st, const ManiDesc &m, int mode, int restart, i
     launch_nesterov(st, m, mode, restart & 1, skip_lo, skip_hi, alpha, gamma, X, V, Y, XPrev, Yloc, Xloc.p[0]);
 }
 
-// The thread-per-pose Nesterov kernels take one result pointer: when the solver left its choice of buffer on the
-// device (ctl), read it back first.  (The 8-lanes-per-pose kernels pick on the device.)
-static int resolve_pick(DeviceProblem &pb, Buf2 *Xres, const SolverCtl **cs) {
-  if (*cs == nullptr || group_kernels(pb.m)) return DCORA_OK;
-  dcora_ropt_result tmp;
-  const int rc = pb.fetch_result(&tmp);
-  if (rc) return rc;
-  double *picked = pb.result_index() ? pb.X1.p : pb.X0.p;
-  *Xres = Buf2{{picked, picked}};
-  *cs = nullptr;
+// Nesterov bookkeeping whose X is the result of pb's last solve: the 8-lanes-per-pose kernels pick its buffer on the
+// device, the thread-per-pose ones take it resolved on the host
+static int nesterov_solved(hipStream_t st, DeviceProblem &pb, int mode, double alpha, double gamma, double *X,
+                           double *V, double *Y, double *XPrev) {
+  const SolverCtl *c = nullptr;
+  Buf2 Xres = pb.result_pick(&c);
+  if (!group_kernels(pb.m)) {
+    const int rc = pb.result(&Xres.p[0]);
+    if (rc) return rc;
+    c = nullptr;
+  }
+  nesterov(st, pb.m, mode, 0, -1, -1, alpha, gamma, X, V, Y, XPrev, nullptr, Xres, c);
   return DCORA_OK;
 }
 
@@ -436,15 +438,10 @@ int RbcdSession::update_selected_agent(AgentDev &a, bool restart) {
             launch_spmm(st, r, a.coupling.view(), buf1(a.nbr[0].p), 0, nullptr, buf1(pb.G.p), 0, nullptr, Gate{});
             pb.has_G = true;
             last_solver = &pb;
-            Buf2 Xres{{nullptr, nullptr}};
-            const SolverCtl *cs = nullptr;
             DCORA_HIP(hipMemcpyAsync(pb.X0.p, XPrevg.p + off, B, hipMemcpyDeviceToDevice, st));
-            rc = pb.optimize_dev(opt.local, &Xres, &cs);
+            rc = pb.optimize_dev(opt.local);
+            if (!rc) rc = nesterov_solved(st, pb, 3, alpha, gamma, Xg.p + off, Vg.p + off, Yg.p + off, XPrevg.p + off);
             if (rc) return rc;
-            rc = resolve_pick(pb, &Xres, &cs);
-            if (rc) return rc;
-            nesterov(st, pb.m, 3, 0, -1, -1, alpha, gamma, Xg.p + off, Vg.p + off, Yg.p + off, XPrevg.p + off, nullptr,
-                     Xres, cs);
             // last_skipped stays true: `success` of Agent::iterate is the FIRST updateX's result, the restart's is
             // discarded (ref src/Agent.cpp:548-553), so iterate() returns false and readyToTerminate stays false
             solved = true;
@@ -459,8 +456,6 @@ int RbcdSession::update_selected_agent(AgentDev &a, bool restart) {
     const double *nsrc = a.detached ? a.nbr[opt.acceleration ? 1 : 0].p : Xg.p;
     launch_spmm(st, r, a.coupling.view(), buf1(nsrc), 0, nullptr, buf1(pb.G.p), 0, nullptr, Gate{});
     pb.has_G = true;
-    Buf2 Xres{{nullptr, nullptr}};
-    const SolverCtl *cs = nullptr;
     last_solver = &pb;
     if (opt.acceleration) {
       // (skipped only when the non-selected agents' launch of THIS round has taken the step already)
@@ -468,12 +463,9 @@ int RbcdSession::update_selected_agent(AgentDev &a, bool restart) {
         nesterov(st, pb.m, 1, 0, -1, -1, alpha, gamma, Xg.p + off, Vg.p + off, Yg.p + off, XPrevg.p + off, pb.X0.p,
                  Buf2{{nullptr, nullptr}}, nullptr);
       staged_selected_ = -1;
-      rc = pb.optimize_dev(opt.local, &Xres, &cs);
+      rc = pb.optimize_dev(opt.local);
+      if (!rc) rc = nesterov_solved(st, pb, 2, alpha, gamma, Xg.p + off, Vg.p + off, Yg.p + off, XPrevg.p + off);
       if (rc) return rc;
-      rc = resolve_pick(pb, &Xres, &cs);
-      if (rc) return rc;
-      nesterov(st, pb.m, 2, 0, -1, -1, alpha, gamma, Xg.p + off, Vg.p + off, Yg.p + off, XPrevg.p + off, nullptr, Xres,
-               cs);
       a.v_feasible = true;  // V = proj(V + gamma (X - Y))
       if (restart) {
         // restartNesterovAcceleration: X = XPrev; updateX(true, false); V = X; Y = X
@@ -489,12 +481,9 @@ int RbcdSession::update_selected_agent(AgentDev &a, bool restart) {
         }
         if (plain_ok) {
           DCORA_HIP(hipMemcpyAsync(pb.X0.p, XPrevg.p + off, B, hipMemcpyDeviceToDevice, st));
-          rc = pb.optimize_dev(opt.local, &Xres, &cs);
+          rc = pb.optimize_dev(opt.local);
+          if (!rc) rc = nesterov_solved(st, pb, 3, alpha, gamma, Xg.p + off, Vg.p + off, Yg.p + off, XPrevg.p + off);
           if (rc) return rc;
-          rc = resolve_pick(pb, &Xres, &cs);
-          if (rc) return rc;
-          nesterov(st, pb.m, 3, 0, -1, -1, alpha, gamma, Xg.p + off, Vg.p + off, Yg.p + off, XPrevg.p + off, nullptr,
-                   Xres, cs);
         } else {
           const Buf2 Xprev{{XPrevg.p + off, XPrevg.p + off}};
           nesterov(st, pb.m, 3, 0, -1, -1, alpha, gamma, Xg.p + off, Vg.p + off, Yg.p + off, XPrevg.p + off, nullptr,
@@ -504,15 +493,9 @@ int RbcdSession::update_selected_agent(AgentDev &a, bool restart) {
     } else {
       DCORA_HIP(hipMemcpyAsync(XPrevg.p + off, Xg.p + off, B, hipMemcpyDeviceToDevice, st));
       DCORA_HIP(hipMemcpyAsync(pb.X0.p, Xg.p + off, B, hipMemcpyDeviceToDevice, st));
-      rc = pb.optimize_dev(opt.local, &Xres, &cs);
-      if (rc) return rc;
-      if (cs) {  // resolve the device-side pick on the host (non-accelerated path is not latency critical)
-        dcora_ropt_result tmp;
-        rc = pb.fetch_result(&tmp);
-        if (rc) return rc;
-        Xres.p[0] = tmp.success && pb.result_index() ? pb.X1.p : pb.X0.p;
-      }
-      DCORA_HIP(hipMemcpyAsync(Xg.p + off, Xres.p[0], B, hipMemcpyDeviceToDevice, st));
+      double *Xres = nullptr;  // resolved on the host: the non-accelerated path is not latency critical
+      if ((rc = pb.optimize_dev(opt.local)) || (rc = pb.result(&Xres))) return rc;
+      DCORA_HIP(hipMemcpyAsync(Xg.p + off, Xres, B, hipMemcpyDeviceToDevice, st));
     }
   }
   return DCORA_OK;
@@ -814,23 +797,16 @@ int RbcdSession::solve_block(AgentDev &a, std::string *err, bool serial) {
   // k_tcg_run); otherwise side by side on the agents' own streams, on the launches per iteration
   hipStream_t run_on = serial ? st : a.own;
   pb.st = run_on;
-  Buf2 Xres{{nullptr, nullptr}};
-  const SolverCtl *cs = nullptr;
   pb.concurrent_solves = !serial;  // several solves share the device: no co-resident one-launch tCG run
-  int rc = pb.optimize_dev(opt.local, &Xres, &cs);
+  int rc = pb.optimize_dev(opt.local);
   pb.concurrent_solves = false;
   if (!rc) {
-    if (cs && group_kernels(pb.m)) {
-      nesterov(run_on, pb.m, 3, 0, -1, -1, 0.0, 0.0, Xg.p + off, Vg.p + off, Yg.p + off, XPrevg.p + off, nullptr, Xres,
-               cs);
+    if (group_kernels(pb.m)) {
+      rc = nesterov_solved(run_on, pb, 3, 0.0, 0.0, Xg.p + off, Vg.p + off, Yg.p + off, XPrevg.p + off);
     } else {
-      if (cs) {
-        dcora_ropt_result tmp;
-        rc = pb.fetch_result(&tmp);
-        Xres.p[0] = tmp.success && pb.result_index() ? pb.X1.p : pb.X0.p;
-      }
-      if (!rc && hipMemcpyAsync(Xg.p + off, Xres.p[0], B, hipMemcpyDeviceToDevice, run_on) != hipSuccess)
-        rc = DCORA_ERR_HIP;
+      double *Xres = nullptr;
+      rc = pb.result(&Xres);
+      if (!rc && hipMemcpyAsync(Xg.p + off, Xres, B, hipMemcpyDeviceToDevice, run_on) != hipSuccess) rc = DCORA_ERR_HIP;
     }
   }
   if (!rc && !serial && hipEventRecord(a.done, a.own) != hipSuccess) rc = DCORA_ERR_HIP;

@@ -839,7 +839,7 @@ __global__ __launch_bounds__(kBlock) void k_fused_precond(int r, int k, int ldm,
         ctl->tcg_done_stamp = seq;
         f_host_store(&hf->tcg_done_seq, seq);
       } else {
-        // the host enqueues what follows a B that goes on only once it knows (DeviceProblem::rtr_dev_fused)
+        // the host enqueues what follows a B that goes on only once it knows (DeviceProblem::RtrForm::replay)
         f_host_store(&hf->go_seq, seq);
       }
     }
@@ -1244,7 +1244,7 @@ __global__ __launch_bounds__(kPcBlock) void k_fused_pc(ManiDesc m, int ldm, int 
         ctl->tcg_done_stamp = seq;
         f_host_store(&hf->tcg_done_seq, seq);
       } else {
-        // the host enqueues what follows a B that goes on only once it knows (DeviceProblem::rtr_dev_fused)
+        // (the host waits for this word only behind the split form's B: DeviceProblem::RtrForm::replay)
         f_host_store(&hf->go_seq, seq);
       }
     }
