@@ -743,7 +743,7 @@ int DeviceProblem::rgd_dev(const dcora_ropt_params &prm) {
   last_res_.fOpt = f1;
   last_res_.gradNormOpt = g1;
   last_res_.elapsedMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  last_res_.tCGStatus = 4;
+  last_res_.tCGStatus = TR_MAXITER;
   last_res_.outer_iterations = 1;
   last_res_.inner_iterations = 0;
   last_res_.accepted_steps = 1;

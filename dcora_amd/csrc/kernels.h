@@ -86,6 +86,8 @@ struct SolverCtl {
   double alpha, e_Pe_n, norm_r0;
   int tcg_done_stamp, tcg_status, tcg_iters, inner_total, max_inner;
 };
+// how a tCG run ended (SolverCtl::tcg_status): ROPTLIB's tCGstatusSet, in its order
+enum TcgStatus : int { TR_NEGCURVTURE = 0, TR_EXCREGION = 1, TR_LCON = 2, TR_SCON = 3, TR_MAXITER = 4 };
 constexpr int kMaxAgents = 64;
 // results of one evaluation pass, in host-mapped memory
 struct EvalOut {
@@ -114,8 +116,7 @@ struct Gate {
 // ---- SpMM: Y = X * A (+ G); optional partial dots {sum (X*A) o X, sum X o G}, 2 per block ---------------
 int spmm_grid(int nrows, int r);
 // W = (-z + beta d_old) Q with the direction written to d_new and the tCG scalar recurrence of iteration `iter`
-// (iter 0: its start, z_r = d_Pd = <z, r>, e_Pe = e_Pd = 0; otherwise the update of iteration iter - 1, as k_tcg_update2
-// forms it after the last iteration) folded in
+// (tcg_rules.h) folded in
 // k_spmm_dir with k_hessfix folded in (one launch per tCG iteration of the generic layout); returns the number of
 // <delta, Hd> partial slots written to p1.  spmm_dir_fix_grid: 0 when r is too large for whole items per workgroup.
 int spmm_dir_fix_grid(const ManiDesc &m, int nrows);
@@ -153,7 +154,7 @@ struct SpFold {
   const double *hub_U = nullptr, *hub_x2 = nullptr;
 };
 // out = Proj_X(V); partial <out, R> when R != null.  When p2 != null the prologue evaluates the tCG
-// residual stopping rule |r| <= |r0| min(|r0|^theta, kappa) from the np2 partials of |r|^2.
+// residual stopping rule (tcg_rules.h) from the np2 partials of |r|^2.
 void launch_tangent(hipStream_t st, const ManiDesc &m, Buf2 X, const double *V, double *out, const double *R,
                     double *partials, const double *p2, int np2, SolverCtl *ctl, HostFlags *hf, int seq,
                     int gate, int iter, SpFold sf = SpFold());
@@ -292,7 +293,8 @@ void launch_g_nesterov(hipStream_t st, const ManiDesc &m, int mode, int restart,
                        Buf2 Xloc, const SolverCtl *ctl, double *inner_Yloc = nullptr);
 
 #if defined(__HIPCC__)
-// ---- wave-level sums on DPP row operations (device code only) ----
+// ---- device code only: the reductions and pacing primitives every kernel file shares ----
+// Wave-level sums on DPP row operations.
 // Moves inside the 16-lane rows (xor 1, xor 2, mirror of 8, mirror of 16) instead of __shfl_xor / ds_bpermute, which
 // goes through the LDS crossbar; the four row sums are then read as scalars.  Fixed order => reproducible.
 template <int CTRL>
@@ -314,6 +316,56 @@ __device__ __forceinline__ double wave_sum_dpp(double v) {
   v += dpp_move<0x141>(v);  // row_half_mirror
   v += dpp_move<0x140>(v);  // row_mirror
   return (readlane_f64(v, 0) + readlane_f64(v, 16)) + (readlane_f64(v, 32) + readlane_f64(v, 48));
+}
+__device__ __forceinline__ double wave_sum(double v) { return wave_sum_dpp(v); }
+// sum over the block, result broadcast to every thread; sm must hold >= 16 doubles
+__device__ __forceinline__ double block_sum(double v, double *sm) {
+  v = wave_sum(v);
+  const int w = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sm[w] = v;
+  __syncthreads();
+  double t = 0;
+  for (int i = 0; i < nw; ++i) t += sm[i];
+  return t;
+}
+__device__ __forceinline__ double sum_partials(const double *p, int np, int stride, int off, double *sm) {
+  double v = 0;
+  for (int i = threadIdx.x; i < np; i += blockDim.x) v += p[(size_t)i * stride + off];
+  return block_sum(v, sm);
+}
+// a word the host polls (HostFlags)
+__device__ __forceinline__ void host_store(volatile int *p, int v) {
+  __hip_atomic_store(const_cast<int *>(p), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// ---- the Gate rule (see Gate above) and the operand pick of a Buf2 ----
+__device__ __forceinline__ bool gated(const SolverCtl *ctl, int seq, int gate) {
+  if (ctl == nullptr || gate == 0) return false;
+  if (seq > ctl->outer_done_stamp) return true;
+  if (gate == 2 && seq > ctl->tcg_done_stamp) return true;
+  return false;
+}
+// the gate's two words requested early (with a kernel's other independent loads), tested later
+struct GateWords {
+  int outer, tcg;
+};
+__device__ __forceinline__ GateWords gate_words(const SolverCtl *ctl) {
+  GateWords w{0x7fffffff, 0x7fffffff};
+  if (ctl) {
+    w.outer = ctl->outer_done_stamp;
+    w.tcg = ctl->tcg_done_stamp;
+  }
+  return w;
+}
+__device__ __forceinline__ bool gated(const GateWords &w, const SolverCtl *ctl, int seq, int gate) {
+  if (ctl == nullptr || gate == 0) return false;
+  if (seq > w.outer) return true;
+  if (gate == 2 && seq > w.tcg) return true;
+  return false;
+}
+__device__ __forceinline__ double *pick(const Buf2 &b, const SolverCtl *ctl, int sel) {
+  return b.p[ctl ? ((ctl->cur ^ sel) & 1) : 0];
 }
 #endif
 

@@ -9,56 +9,13 @@
 //  * solver kernels read their trust-region / tCG scalars from a SolverCtl block in HBM and are no-ops once a
 //    termination stamp older than their own sequence number is set -- the host never waits for a scalar.
 #include "kernels.h"
+#include "tcg_rules.h"
 
 namespace dcora {
 
 // ------------------------------------------------------------------------------------------------------
 // helpers
 // ------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool gated(const SolverCtl *ctl, int seq, int gate) {
-  if (ctl == nullptr || gate == 0) return false;
-  if (seq > ctl->outer_done_stamp) return true;
-  if (gate == 2 && seq > ctl->tcg_done_stamp) return true;
-  return false;
-}
-// the gate's two words requested early (with a kernel's other independent loads), tested later
-struct GateWords {
-  int outer, tcg;
-};
-__device__ __forceinline__ GateWords gate_words(const SolverCtl *ctl) {
-  GateWords w{0x7fffffff, 0x7fffffff};
-  if (ctl) {
-    w.outer = ctl->outer_done_stamp;
-    w.tcg = ctl->tcg_done_stamp;
-  }
-  return w;
-}
-__device__ __forceinline__ bool gated(const GateWords &w, const SolverCtl *ctl, int seq, int gate) {
-  if (ctl == nullptr || gate == 0) return false;
-  if (seq > w.outer) return true;
-  if (gate == 2 && seq > w.tcg) return true;
-  return false;
-}
-__device__ __forceinline__ double *pick(const Buf2 &b, const SolverCtl *ctl, int sel) {
-  return b.p[ctl ? ((ctl->cur ^ sel) & 1) : 0];
-}
-__device__ __forceinline__ double wave_sum(double v) { return wave_sum_dpp(v); }
-// sum over the block, result broadcast to every thread; sm must hold >= 16 doubles
-__device__ __forceinline__ double block_sum(double v, double *sm) {
-  v = wave_sum(v);
-  const int w = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sm[w] = v;
-  __syncthreads();
-  double t = 0;
-  for (int i = 0; i < nw; ++i) t += sm[i];
-  return t;
-}
-__device__ __forceinline__ double sum_partials(const double *p, int np, int stride, int off, double *sm) {
-  double v = 0;
-  for (int i = threadIdx.x; i < np; i += blockDim.x) v += p[(size_t)i * stride + off];
-  return block_sum(v, sm);
-}
 // N sums of partial arrays at once for the single-block bookkeeping kernels: every load is issued before the first
 // reduction (one memory round trip instead of one per sum) and the N wave sums share one LDS exchange (two barriers
 // instead of 2 N).  p[q] has np[q] entries of stride st[q] at offset off[q]; sm must hold >= 4 N doubles.
@@ -85,9 +42,6 @@ __device__ __forceinline__ void sum_partials_n(const double *const (&p)[N], cons
     for (int i = 0; i < nw; ++i) t += sm[q * 4 + i];
     out[q] = t;
   }
-}
-__device__ __forceinline__ void host_store(volatile int *p, int v) {
-  __hip_atomic_store(const_cast<int *>(p), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 int vec_grid(long nelem) {
@@ -274,9 +228,9 @@ __global__ __launch_bounds__(kBlock) void k_spmm(int r, CsrDev A, Buf2 Xb, int s
 // Generic-layout tCG, iteration `iter`: the direction update of the previous iteration folded into the Hessian SpMM.
 //   delta_new = -z + beta delta_old   (beta = <z, r>_new / <z, r>_old from the partials p3; iter 0: delta_new = -z)
 //   W = delta_new Q                   (delta_new formed in the gather, written for the block's own columns)
-// and the scalar recurrence of ROPTLIB's tCG_TR (block 0): iteration 0 starts it (z_r = d_Pd = <z, r>, e_Pe = e_Pd = 0),
-// later ones finish iteration iter - 1 as k_tcg_update2 does after the last one.  delta_old and
-// delta_new are different buffers: other workgroups still gather the old direction.
+// and the scalar recurrence of ROPTLIB's tCG_TR (block 0, tcg_rules.h): iteration 0 starts it, later ones finish iteration
+// iter - 1 as k_tcg_update2 does after the last one.  delta_old and delta_new are different buffers: other workgroups
+// still gather the old direction.
 // ------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void k_spmm_dir(int r, CsrDev A, const double *__restrict__ z,
                                                      const double *__restrict__ d_old, double *__restrict__ d_new,
@@ -289,21 +243,12 @@ __global__ __launch_bounds__(kBlock) void k_spmm_dir(int r, CsrDev A, const doub
   __shared__ int s_last;
   const int par = (iter - 1) & 1;
   const double z_r_new = sum_partials(p3, np3, 1, 0, s_red);
-  const double beta = iter > 0 ? z_r_new / ctl->z_r[par] : 0.0;
+  const double beta = iter > 0 ? tcg_beta(z_r_new, ctl->z_r[par]) : 0.0;
   if (blockIdx.x == 0 && threadIdx.x == 0) {
-    if (iter == 0) {
-      ctl->z_r[0] = z_r_new;
-      ctl->d_Pd[0] = z_r_new;
-      ctl->e_Pe[0] = 0;
-      ctl->e_Pd[0] = 0;
-    } else {
-      const double alpha = ctl->alpha;
-      const double d_Pd = ctl->d_Pd[par], e_Pd = ctl->e_Pd[par];
-      ctl->z_r[par ^ 1] = z_r_new;
-      ctl->e_Pd[par ^ 1] = beta * (e_Pd + alpha * d_Pd);
-      ctl->d_Pd[par ^ 1] = z_r_new + beta * beta * d_Pd;
-      ctl->e_Pe[par ^ 1] = ctl->e_Pe_n;
-    }
+    if (iter == 0)
+      tcg_put_dir(ctl, 0, tcg_dir_start(z_r_new), 0.0);
+    else
+      tcg_put_dir(ctl, par ^ 1, tcg_dir_next(z_r_new, beta, ctl->alpha, ctl->d_Pd[par], ctl->e_Pd[par]), ctl->e_Pe_n);
   }
   const int RB = kBlock / r;
   const int nrb = (A.nrows + RB - 1) / RB;
@@ -478,21 +423,12 @@ __global__ __launch_bounds__(kBlock) void k_spmm_dir_fix(ManiDesc m, CsrDev A, B
   if (gated(gw, ctl, seq, 2)) return;
   for (int i = threadIdx.x + blockDim.x; i < np3; i += blockDim.x) pv += p3[i];
   const double z_r_new = block_sum(pv, s_red);
-  const double beta = iter > 0 ? z_r_new / zr_old : 0.0;
+  const double beta = iter > 0 ? tcg_beta(z_r_new, zr_old) : 0.0;
   if (blockIdx.x == 0 && threadIdx.x == 0) {
-    if (iter == 0) {
-      ctl->z_r[0] = z_r_new;
-      ctl->d_Pd[0] = z_r_new;
-      ctl->e_Pe[0] = 0;
-      ctl->e_Pd[0] = 0;
-    } else {
-      const double alpha = ctl->alpha;
-      const double d_Pd = ctl->d_Pd[par], e_Pd = ctl->e_Pd[par];
-      ctl->z_r[par ^ 1] = z_r_new;
-      ctl->e_Pd[par ^ 1] = beta * (e_Pd + alpha * d_Pd);
-      ctl->d_Pd[par ^ 1] = z_r_new + beta * beta * d_Pd;
-      ctl->e_Pe[par ^ 1] = ctl->e_Pe_n;
-    }
+    if (iter == 0)
+      tcg_put_dir(ctl, 0, tcg_dir_start(z_r_new), 0.0);
+    else
+      tcg_put_dir(ctl, par ^ 1, tcg_dir_next(z_r_new, beta, ctl->alpha, ctl->d_Pd[par], ctl->e_Pd[par]), ctl->e_Pe_n);
   }
   const double *X = pick(Xb, ctl, 0);
   const double *Sblk = pick(Sb, ctl, 0);
@@ -980,19 +916,10 @@ __global__ __launch_bounds__(kBlock) void k_tangent(ManiDesc m, Buf2 Xb, const d
   asm volatile("" ::"v"(pv), "v"(n0), "v"(x2_0), "s"(gw.outer), "s"(gw.tcg));
   if (gated(gw, ctl, seq, gate)) return;
   if (p2) {
-    // ROPTLIB tCG_TR stopping rule (theta = 1, kappa = 0.1): |r| <= |r0| min(|r0|^theta, kappa)
     for (int i = threadIdx.x + blockDim.x; i < np2; i += blockDim.x) pv += p2[i];
     const double nr = sqrt(block_sum(pv, s_red));
-    const double kappa = 0.1;
-    const double tempnum = n0;  // pow(n0, theta = 1)
-    if (nr <= n0 * fmin(tempnum, kappa)) {
-      if (blockIdx.x == 0 && threadIdx.x == 0) {
-        ctl->tcg_status = (kappa < tempnum) ? 2 : 3;
-        ctl->tcg_iters = iter + 1;
-        ctl->inner_total += iter + 1;
-        ctl->tcg_done_stamp = seq;
-        host_store(&hf->tcg_done_seq, seq);
-      }
+    if (tcg_residual_done(nr, n0)) {
+      if (blockIdx.x == 0 && threadIdx.x == 0) tcg_end_run(ctl, hf, seq, tcg_residual_status(n0), iter + 1);
       return;
     }
   }
@@ -1501,8 +1428,7 @@ __global__ __launch_bounds__(kBlock) void k_dense_apply(int r, int k, int ldm, c
   if (p2) {
     // residual already below the tCG stopping threshold: the next kernel records the termination
     const double nr = sqrt(sum_partials(p2, np2, 1, 0, s_red));
-    const double n0 = g.ctl->norm_r0;
-    if (nr <= n0 * fmin(n0, 0.1)) return;
+    if (tcg_residual_done(nr, g.ctl->norm_r0)) return;
   }
   const double *__restrict__ R = pick(Rb, g.ctl, 0);
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -1567,26 +1493,7 @@ __global__ __launch_bounds__(kBlock) void k_rtr_init(const double *pA, int npA, 
                                                      unsigned *tcg_sync, int nsync) {
   __shared__ double s_red[16];
   for (int i = threadIdx.x; i < nsync; i += kBlock) tcg_sync[i] = 0u;
-  if (ci.enable && threadIdx.x == 0) {  // start-of-solve control block (saves the separate k_ctl_init launch)
-    SolverCtl *c = ctl;
-    c->f2 = c->rho = 0;
-    c->Delta = ci.Delta;
-    c->maxDelta = ci.maxDelta;
-    c->tol = ci.tol;
-    c->cur = 0;
-    c->outer_it = 0;
-    c->max_outer = ci.max_outer;
-    c->accepted = 0;
-    c->last_accepted = 0;
-    c->stop_on_accept = ci.stop_on_accept;
-    c->outer_done_stamp = INT_MAX;
-    c->alpha = c->e_Pe_n = c->norm_r0 = 0;
-    c->tcg_done_stamp = INT_MAX;
-    c->tcg_status = 4;
-    c->tcg_iters = 0;
-    c->inner_total = 0;
-    c->max_inner = ci.max_inner;
-  }
+  if (ci.enable && threadIdx.x == 0) ctl_arm(ctl, ci);  // (saves the separate k_ctl_init launch)
   const double *const ps[3] = {pA, pA, pB};
   const int nps[3] = {npA, npA, npB}, sts[3] = {2, 2, 1}, offs[3] = {0, 1, 0};
   double sums[3];
@@ -1616,12 +1523,7 @@ __global__ __launch_bounds__(kBlock) void k_tcg_begin(long nelem, Buf2 gradb, do
     Heta[i] = 0;
     res[i] = grad[i];
   }
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    ctl->norm_r0 = ctl->ngf;
-    ctl->tcg_status = 4;
-    ctl->tcg_iters = 0;
-    ctl->tcg_done_stamp = INT_MAX;
-  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) tcg_begin_run(ctl, ctl->ngf);
 }
 __global__ __launch_bounds__(kBlock) void k_tcg_update1(long nelem, const double *__restrict__ delta,
                                                         const double *__restrict__ Hd, double *__restrict__ eta,
@@ -1656,11 +1558,10 @@ __global__ __launch_bounds__(kBlock) void k_tcg_update1(long nelem, const double
   if (gated(gw, ctl, seq, 2)) return;
   for (int i = threadIdx.x + blockDim.x; i < np1; i += blockDim.x) pv += p1[i];
   const double d_Hd = block_sum(pv, s_red);
-  const double alpha = z_r / d_Hd;
-  const double e_Pe_new = e_Pe + 2.0 * alpha * e_Pd + alpha * alpha * d_Pd;
-  const bool boundary = (d_Hd <= 0) || (e_Pe_new >= Delta * Delta);
-  const double step =
-      boundary ? (-e_Pd + sqrt(e_Pd * e_Pd + d_Pd * (Delta * Delta - e_Pe))) / d_Pd : alpha;
+  const double alpha = tcg_alpha(z_r, d_Hd);
+  const double e_Pe_new = tcg_e_Pe_new(alpha, d_Pd, e_Pe, e_Pd);
+  const bool boundary = tcg_boundary(d_Hd, e_Pe_new, Delta);
+  const double step = boundary ? tcg_tau(d_Pd, e_Pe, e_Pd, Delta) : alpha;
   // a run that goes on says so before the vector work: the host enqueues the sparse replay behind this verdict
   // (DeviceProblem::RtrForm::replay); a run that stops writes tcg_done_seq below
   if (!boundary && blockIdx.x == 0 && threadIdx.x == 0) host_store(&hf->go_seq, seq);
@@ -1695,13 +1596,7 @@ __global__ __launch_bounds__(kBlock) void k_tcg_update1(long nelem, const double
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     ctl->alpha = alpha;
     ctl->e_Pe_n = e_Pe_new;
-    if (boundary) {
-      ctl->tcg_status = (d_Hd <= 0) ? 0 : 1;
-      ctl->tcg_iters = iter + 1;
-      ctl->inner_total += iter + 1;
-      ctl->tcg_done_stamp = seq;
-      host_store(&hf->tcg_done_seq, seq);
-    }
+    if (boundary) tcg_end_run(ctl, hf, seq, tcg_boundary_status(d_Hd), iter + 1);
   }
 }
 
@@ -1712,23 +1607,12 @@ __global__ __launch_bounds__(kBlock) void k_tcg_update2(long nelem, const double
   __shared__ double s_red[16];
   const int par = iter & 1;
   const double z_r_new = sum_partials(p3, np3, 1, 0, s_red);
-  const double z_r_old = ctl->z_r[par];
-  const double beta = z_r_new / z_r_old;
+  const double beta = tcg_beta(z_r_new, ctl->z_r[par]);
   for (long i = (long)blockIdx.x * kBlock + threadIdx.x; i < nelem; i += (long)gridDim.x * kBlock)
     delta[i] = -z[i] + beta * delta[i];
   if (blockIdx.x == 0 && threadIdx.x == 0) {
-    const double alpha = ctl->alpha;
-    const double d_Pd = ctl->d_Pd[par], e_Pd = ctl->e_Pd[par];
-    ctl->z_r[par ^ 1] = z_r_new;
-    ctl->e_Pd[par ^ 1] = beta * (e_Pd + alpha * d_Pd);
-    ctl->d_Pd[par ^ 1] = z_r_new + beta * beta * d_Pd;
-    ctl->e_Pe[par ^ 1] = ctl->e_Pe_n;
-    if (iter + 1 >= ctl->max_inner) {  // loop exhausted: status stays TR_MAXITER
-      ctl->tcg_iters = iter + 1;
-      ctl->inner_total += iter + 1;
-      ctl->tcg_done_stamp = seq;
-      host_store(&hf->tcg_done_seq, seq);
-    }
+    tcg_put_dir(ctl, par ^ 1, tcg_dir_next(z_r_new, beta, ctl->alpha, ctl->d_Pd[par], ctl->e_Pd[par]), ctl->e_Pe_n);
+    if (iter + 1 >= ctl->max_inner) tcg_end_run_at_cap(ctl, hf, seq, iter + 1);
     host_store(&hf->last_seq_done, seq);
   }
 }
@@ -1751,7 +1635,7 @@ __global__ __launch_bounds__(kBlock) void k_rtr_decide(const double *pA, int npA
     ctl->f2 = f2;
     ctl->rho = rho;
     if (rho > 0.75) {
-      if (ctl->tcg_status == 0 || ctl->tcg_status == 1) ctl->Delta = fmin(2.0 * ctl->Delta, ctl->maxDelta);
+      if (ctl->tcg_status == TR_NEGCURVTURE || ctl->tcg_status == TR_EXCREGION) ctl->Delta = fmin(2.0 * ctl->Delta, ctl->maxDelta);
     } else if (rho < 0.25) {
       ctl->Delta *= 0.25;
     }

@@ -18,6 +18,7 @@
 #include <cstring>
 
 #include "kernels.h"
+#include "tcg_rules.h"
 
 namespace dcora {
 
@@ -25,38 +26,10 @@ namespace {
 
 constexpr int GW = 8;  // lanes per pose
 
-__device__ __forceinline__ bool f_gated(const SolverCtl *ctl, int seq, int gate) {
-  if (seq > ctl->outer_done_stamp) return true;
-  if (gate == 2 && seq > ctl->tcg_done_stamp) return true;
-  return false;
-}
-// Wave-wide sum, same value in every lane.  Data-parallel-primitive moves inside the 16-lane rows (xor 1, xor 2,
-// mirror of 8, mirror of 16: no LDS crossbar round trips as with __shfl_xor / ds_bpermute), then the four row sums
-// are read as scalars.  Fixed order => reproducible.
-template <int CTRL>
-__device__ __forceinline__ double f_dpp(double v) { return dpp_move<CTRL>(v); }
-__device__ __forceinline__ double f_wave_sum(double v) {
-#ifdef DCORA_WAVE_SUM_SHUFFLE  // A/B switch: the butterfly over ds_bpermute
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-#endif
-  return wave_sum_dpp(v);  // kernels.h
-}
-__device__ __forceinline__ double f_block_sum(double v, double *sm) {
-  v = f_wave_sum(v);
-  const int w = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sm[w] = v;
-  __syncthreads();
-  double t = 0;
-  for (int i = 0; i < nw; ++i) t += sm[i];
-  return t;
-}
-// Up to 64 partials: every wave loads them itself (lane l takes partial l) and sums them with f_wave_sum, so the
+// Up to 64 partials: every wave loads them itself (lane l takes partial l) and sums them with wave_sum, so the
 // total is known in every wave without a barrier or an LDS exchange; more partials go through the block reduction.
 // Up to 256 partials without a barrier: every wave loads all of them (lane l takes partials l, l + 64, l + 128, l + 192:
-// four predicated loads requested together) and sums them with f_wave_sum -- __syncthreads() drains vmcnt, i.e. it
+// four predicated loads requested together) and sums them with wave_sum -- __syncthreads() drains vmcnt, i.e. it
 // would wait for every gather the kernel has in flight behind the partials (measured in k_fused_hess with the 250
 // partials of k_fused_pc: 1.7 us at the reduction).  f_partial4_load / f_partial4_total; beyond 256 the block path.
 __device__ __forceinline__ double f_partial4_load(const double *__restrict__ p, int np) {
@@ -68,10 +41,7 @@ __device__ __forceinline__ double f_partial4_load(const double *__restrict__ p, 
 // f_partial_index is the index a thread loads, f_partial_total the matching reduction.
 __device__ __forceinline__ int f_partial_index(int np) { return np <= 64 ? (int)(threadIdx.x & 63u) : (int)threadIdx.x; }
 __device__ __forceinline__ double f_partial_total(double v, int np, double *sm) {
-  return np <= 64 ? f_wave_sum(v) : f_block_sum(v, sm);
-}
-__device__ __forceinline__ void f_host_store(volatile int *p, int v) {
-  __hip_atomic_store(const_cast<int *>(p), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  return np <= 64 ? wave_sum(v) : block_sum(v, sm);
 }
 // sum over the 8 lanes of a pose group (every lane of the wave must take part).  The result is re-broadcast from
 // the group's first lane: with FMA contraction the butterfly partial sums can differ in the last bit between
@@ -81,18 +51,12 @@ __device__ __forceinline__ void f_host_store(volatile int *p, int v) {
 // first, so every add below combines two rounded numbers and, addition being commutative, the eight lanes end with
 // bitwise the same sum (same tree as the xor butterfly it replaces).
 __device__ __forceinline__ double grp_sum(double v) {
-#ifdef DCORA_GRP_SUM_SHUFFLE  // A/B switch
-  v += __shfl_xor(v, 1, 64);
-  v += __shfl_xor(v, 2, 64);
-  v += __shfl_xor(v, 4, 64);
-  return __shfl(v, (int)(threadIdx.x & 63u & ~7u), 64);
-#endif
   asm volatile("" : "+v"(v));
-  v += f_dpp<0xB1>(v);   // quad_perm [1,0,3,2]
+  v += dpp_move<0xB1>(v);   // quad_perm [1,0,3,2]
   asm volatile("" : "+v"(v));
-  v += f_dpp<0x4E>(v);   // quad_perm [2,3,0,1]
+  v += dpp_move<0x4E>(v);   // quad_perm [2,3,0,1]
   asm volatile("" : "+v"(v));
-  v += f_dpp<0x141>(v);  // row_half_mirror: lane i <- lane 7 - i of its group of eight
+  v += dpp_move<0x141>(v);  // row_half_mirror: lane i <- lane 7 - i of its group of eight
   return v;
 }
 
@@ -401,22 +365,15 @@ __global__ __launch_bounds__(kBlock) void k_fused_hess(ManiDesc m, CsrDev Q, con
     gz[q] = z[oo];
     ga[q] = (iter > 0) ? d_old[oo] : 0.0;
   }
-  // ---- scalar recurrence (ROPTLIB tCG_TR): beta, e_Pd, d_Pd ----
-  const double z_r_new = p3_wave ? f_wave_sum(myp) : f_partial_total(myp, np3, s_red);
+  // ---- scalar recurrence (tcg_rules.h) ----
+  const double z_r_new = p3_wave ? wave_sum(myp) : f_partial_total(myp, np3, s_red);
   double beta = 0;
-  if (iter > 0) beta = z_r_new / c_zr;
+  if (iter > 0) beta = tcg_beta(z_r_new, c_zr);
   if (blockIdx.x == 0 && threadIdx.x == 0) {
-    if (iter == 0) {
-      ctl->z_r[0] = z_r_new;
-      ctl->d_Pd[0] = z_r_new;
-      ctl->e_Pe[0] = 0;
-      ctl->e_Pd[0] = 0;
-    } else {
-      ctl->z_r[par] = z_r_new;
-      ctl->e_Pd[par] = beta * (c_ePd + c_alpha * c_dPd);
-      ctl->d_Pd[par] = z_r_new + beta * beta * c_dPd;
-      ctl->e_Pe[par] = c_ePen;
-    }
+    if (iter == 0)
+      tcg_put_dir(ctl, 0, tcg_dir_start(z_r_new), 0.0);
+    else
+      tcg_put_dir(ctl, par, tcg_dir_next(z_r_new, beta, c_alpha, c_dPd, c_ePd), c_ePen);
   }
   // ---- phase 1 ----
   double acc = 0;
@@ -469,7 +426,7 @@ __global__ __launch_bounds__(kBlock) void k_fused_hess(ManiDesc m, CsrDev Q, con
   double dacc = 0;
 #pragma unroll
   for (int a = 0; a < DH; ++a) dacc += V.e[a] * W.e[a];
-  const double tot = f_block_sum(dacc, s_red);
+  const double tot = block_sum(dacc, s_red);
   if (threadIdx.x == 0) p1[blockIdx.x] = tot;
 }
 
@@ -485,7 +442,7 @@ __global__ __launch_bounds__(kBlock) void k_fused_grad(ManiDesc m, CsrDev Q, Buf
                                                        Buf2 EGb, Buf2 RGb, Buf2 Sb, int sel,
                                                        double *__restrict__ pA, double *__restrict__ pB,
                                                        double *__restrict__ posenorm, Gate g) {
-  if (g.ctl && g.gate && f_gated(g.ctl, g.seq, g.gate)) return;
+  if (gated(g.ctl, g.seq, g.gate)) return;
   __shared__ int s_ci[kHessTile];
   __shared__ double s_v[kHessTile];
   __shared__ double s_W[kBlock], s_X[kBlock];
@@ -587,9 +544,9 @@ __global__ __launch_bounds__(kBlock) void k_fused_grad(ManiDesc m, CsrDev Q, Buf
     if (gp < npose && tt == 0) posenorm[pose] = ps;
   }
   st_row<D>(RG + o, r, tt, pact, E);
-  const double t0 = f_block_sum(d0, s_red);
-  const double t1 = f_block_sum(d1, s_red);
-  const double t2 = f_block_sum(pact ? pa : 0.0, s_red);
+  const double t0 = block_sum(d0, s_red);
+  const double t1 = block_sum(d1, s_red);
+  const double t2 = block_sum(pact ? pa : 0.0, s_red);
   if (threadIdx.x == 0) {
     pA[2 * blockIdx.x] = t0;
     pA[2 * blockIdx.x + 1] = t1;
@@ -648,19 +605,12 @@ __global__ __launch_bounds__(kBlock) void k_fused_hess_bsr(ManiDesc m, BsrDev A,
   if (seq > st_o || seq > st_t) return;  // solve or tCG already finished: no-op (uniform over the grid)
   const double z_r_new = f_partial_total(myp, np3, s_red);
   double beta = 0;
-  if (iter > 0) beta = z_r_new / c_zr;
+  if (iter > 0) beta = tcg_beta(z_r_new, c_zr);
   if (blockIdx.x == 0 && threadIdx.x == 0) {
-    if (iter == 0) {
-      ctl->z_r[0] = z_r_new;
-      ctl->d_Pd[0] = z_r_new;
-      ctl->e_Pe[0] = 0;
-      ctl->e_Pd[0] = 0;
-    } else {
-      ctl->z_r[par] = z_r_new;
-      ctl->e_Pd[par] = beta * (c_ePd + c_alpha * c_dPd);
-      ctl->d_Pd[par] = z_r_new + beta * beta * c_dPd;
-      ctl->e_Pe[par] = c_ePen;
-    }
+    if (iter == 0)
+      tcg_put_dir(ctl, 0, tcg_dir_start(z_r_new), 0.0);
+    else
+      tcg_put_dir(ctl, par, tcg_dir_next(z_r_new, beta, c_alpha, c_dPd, c_ePd), c_ePen);
   }
   // ---- phase 1: W = d_new Q over the pose's block row, d_new = beta d_old - z formed in the gather ----
   Row<D> W, V;
@@ -729,7 +679,7 @@ __global__ __launch_bounds__(kBlock) void k_fused_hess_bsr(ManiDesc m, BsrDev A,
 #pragma unroll
   for (int a = 0; a < DH; ++a) dacc += V.e[a] * W.e[a];
   if (!pact) dacc = 0;
-  const double tot = f_block_sum(dacc, s_red);
+  const double tot = block_sum(dacc, s_red);
   if (threadIdx.x == 0) p1[blockIdx.x] = tot;
 }
 
@@ -823,33 +773,22 @@ __global__ __launch_bounds__(kBlock) void k_fused_precond(int r, int k, int ldm,
   bool boundary = false;
   if (!first) {
     const double d_Hd = f_partial_total(myp, np1, s_red);
-    const double z_r = c_zr, d_Pd = c_dPd, e_Pe = c_ePe, e_Pd = c_ePd;
-    const double Delta = c_Delta;
-    alpha = z_r / d_Hd;
-    const double e_Pe_new = e_Pe + 2.0 * alpha * e_Pd + alpha * alpha * d_Pd;
-    boundary = (d_Hd <= 0) || (e_Pe_new >= Delta * Delta);
-    step = boundary ? (-e_Pd + sqrt(e_Pd * e_Pd + d_Pd * (Delta * Delta - e_Pe))) / d_Pd : alpha;
+    alpha = tcg_alpha(c_zr, d_Hd);
+    const double e_Pe_new = tcg_e_Pe_new(alpha, c_dPd, c_ePe, c_ePd);
+    boundary = tcg_boundary(d_Hd, e_Pe_new, c_Delta);
+    step = boundary ? tcg_tau(c_dPd, c_ePe, c_ePd, c_Delta) : alpha;
     if (blockIdx.x == 0 && threadIdx.x == 0) {
       ctl->alpha = alpha;
       ctl->e_Pe_n = e_Pe_new;
       if (boundary) {
-        ctl->tcg_status = (d_Hd <= 0) ? 0 : 1;
-        ctl->tcg_iters = iter + 1;
-        ctl->inner_total += iter + 1;
-        ctl->tcg_done_stamp = seq;
-        f_host_store(&hf->tcg_done_seq, seq);
+        tcg_end_run(ctl, hf, seq, tcg_boundary_status(d_Hd), iter + 1);
       } else {
         // the host enqueues what follows a B that goes on only once it knows (DeviceProblem::RtrForm::replay)
-        f_host_store(&hf->go_seq, seq);
+        host_store(&hf->go_seq, seq);
       }
     }
   }
-  if (first && blockIdx.x == 0 && threadIdx.x == 0) {
-    ctl->norm_r0 = c_ngf;
-    ctl->tcg_status = 4;
-    ctl->tcg_iters = 0;
-    ctl->tcg_done_stamp = INT_MAX;
-  }
+  if (first && blockIdx.x == 0 && threadIdx.x == 0) tcg_begin_run(ctl, c_ngf);
   // ---- element-wise updates (each element exactly once over the grid) ----
   double acc2 = 0;
   if (own) {
@@ -888,7 +827,7 @@ __global__ __launch_bounds__(kBlock) void k_fused_precond(int r, int k, int ldm,
     }
   }
   if (!first) {
-    const double tot = f_block_sum(acc2, s_red);
+    const double tot = block_sum(acc2, s_red);
     if (threadIdx.x == 0) p2[blockIdx.x] = tot;
   }
   if (boundary || !HAS_M) return;
@@ -1044,17 +983,9 @@ __global__ __launch_bounds__(kBlock) void k_fused_finish(ManiDesc m, int nsplit,
     for (int i = e + 2 * kBlock; i < np2; i += kBlock) myp += p2[i];
   if (seq > st_o || (!first && seq > st_t)) return;  // finished: no-op (uniform over the grid)
   if (!first) {
-    const double nr = sqrt(f_block_sum(myp, s_red));
-    const double n0 = c_n0;
-    const double kappa = 0.1, tempnum = n0;  // theta = 1
-    if (nr <= n0 * fmin(tempnum, kappa)) {
-      if (blockIdx.x == 0 && threadIdx.x == 0) {
-        ctl->tcg_status = (kappa < tempnum) ? 2 : 3;
-        ctl->tcg_iters = iter + 1;
-        ctl->inner_total += iter + 1;
-        ctl->tcg_done_stamp = seq;
-        f_host_store(&hf->tcg_done_seq, seq);
-      }
+    const double nr = sqrt(block_sum(myp, s_red));
+    if (tcg_residual_done(nr, c_n0)) {
+      if (blockIdx.x == 0 && threadIdx.x == 0) tcg_end_run(ctl, hf, seq, tcg_residual_status(c_n0), iter + 1);
       return;
     }
   }
@@ -1070,16 +1001,11 @@ __global__ __launch_bounds__(kBlock) void k_fused_finish(ManiDesc m, int nsplit,
   double acc = 0;
 #pragma unroll
   for (int a = 0; a < DH; ++a) acc += Zr.e[a] * Rr.e[a];
-  const double tot = f_block_sum(acc, s_red);
+  const double tot = block_sum(acc, s_red);
   if (threadIdx.x == 0) p3[blockIdx.x] = tot;
   if (blockIdx.x == 0 && threadIdx.x == 0) {
-    if (!first && iter + 1 >= c_max_inner) {  // inner loop exhausted: status stays TR_MAXITER
-      ctl->tcg_iters = iter + 1;
-      ctl->inner_total += iter + 1;
-      ctl->tcg_done_stamp = seq;
-      f_host_store(&hf->tcg_done_seq, seq);
-    }
-    f_host_store(&hf->last_seq_done, seq);
+    if (!first && iter + 1 >= c_max_inner) tcg_end_run_at_cap(ctl, hf, seq, iter + 1);
+    host_store(&hf->last_seq_done, seq);
   }
 }
 
@@ -1218,8 +1144,8 @@ __global__ __launch_bounds__(kPcBlock) void k_fused_pc(ManiDesc m, int ldm, int 
       row_qf<D>(Yn);
       st_row<D>(Xb.p[cur ^ 1] + o, r, tt, pact, Yn);
     }
-    const double t0 = f_block_sum(a0, s_red);
-    const double t1 = f_block_sum(a1, s_red);
+    const double t0 = block_sum(a0, s_red);
+    const double t1 = block_sum(a1, s_red);
     if (threadIdx.x == 0) {
       pC[2 * blockIdx.x] = t0;
       pC[2 * blockIdx.x + 1] = t1;
@@ -1229,32 +1155,23 @@ __global__ __launch_bounds__(kPcBlock) void k_fused_pc(ManiDesc m, int ldm, int 
   double alpha = 0, step = 0;
   bool boundary = false;
   if (!first) {
-    const double d_Hd = np1 < 0 ? c_dPd + 1.0 : ((np1 <= 64) ? f_wave_sum(myp) : f_block_sum(myp, s_red));
-    alpha = c_zr / d_Hd;
-    const double e_Pe_new = c_ePe + 2.0 * alpha * c_ePd + alpha * alpha * c_dPd;
-    boundary = (d_Hd <= 0) || (e_Pe_new >= c_Delta * c_Delta);
-    step = boundary ? (-c_ePd + sqrt(c_ePd * c_ePd + c_dPd * (c_Delta * c_Delta - c_ePe))) / c_dPd : alpha;
+    const double d_Hd = np1 < 0 ? c_dPd + 1.0 : ((np1 <= 64) ? wave_sum(myp) : block_sum(myp, s_red));
+    alpha = tcg_alpha(c_zr, d_Hd);
+    const double e_Pe_new = tcg_e_Pe_new(alpha, c_dPd, c_ePe, c_ePd);
+    boundary = tcg_boundary(d_Hd, e_Pe_new, c_Delta);
+    step = boundary ? tcg_tau(c_dPd, c_ePe, c_ePd, c_Delta) : alpha;
     if (blockIdx.x == 0 && threadIdx.x == 0) {
       ctl->alpha = alpha;
       ctl->e_Pe_n = e_Pe_new;
       if (boundary) {
-        ctl->tcg_status = (d_Hd <= 0) ? 0 : 1;
-        ctl->tcg_iters = iter + 1;
-        ctl->inner_total += iter + 1;
-        ctl->tcg_done_stamp = seq;
-        f_host_store(&hf->tcg_done_seq, seq);
+        tcg_end_run(ctl, hf, seq, tcg_boundary_status(d_Hd), iter + 1);
       } else {
         // (the host waits for this word only behind the split form's B: DeviceProblem::RtrForm::replay)
-        f_host_store(&hf->go_seq, seq);
+        host_store(&hf->go_seq, seq);
       }
     }
   }
-  if (first && blockIdx.x == 0 && threadIdx.x == 0) {
-    ctl->norm_r0 = c_ngf;
-    ctl->tcg_status = 4;
-    ctl->tcg_iters = 0;
-    ctl->tcg_done_stamp = INT_MAX;
-  }
+  if (first && blockIdx.x == 0 && threadIdx.x == 0) tcg_begin_run(ctl, c_ngf);
   if (own) {
     const int lc = e / r, t = e - lc * r;
     if (first) {
@@ -1397,15 +1314,8 @@ __global__ __launch_bounds__(kPcBlock) void k_fused_pc(ManiDesc m, int ldm, int 
   // ---- residual stopping rule: every workgroup holds |r|^2 itself (same summation order everywhere) ----
   if (!first) {
     const double nr = sqrt(s_Z[NR * RM]);
-    const double kappa = 0.1, tempnum = c_n0;  // theta = 1
-    if (nr <= c_n0 * fmin(tempnum, kappa)) {
-      if (blockIdx.x == 0 && threadIdx.x == 0) {
-        ctl->tcg_status = (kappa < tempnum) ? 2 : 3;
-        ctl->tcg_iters = iter + 1;
-        ctl->inner_total += iter + 1;
-        ctl->tcg_done_stamp = seq;
-        f_host_store(&hf->tcg_done_seq, seq);
-      }
+    if (tcg_residual_done(nr, c_n0)) {
+      if (blockIdx.x == 0 && threadIdx.x == 0) tcg_end_run(ctl, hf, seq, tcg_residual_status(c_n0), iter + 1);
       retract_tail();
       return;
     }
@@ -1423,17 +1333,12 @@ __global__ __launch_bounds__(kPcBlock) void k_fused_pc(ManiDesc m, int ldm, int 
     double zacc = 0;
 #pragma unroll
     for (int a = 0; a < DH; ++a) zacc += Zr.e[a] * Rr.e[a];
-    const double tot = f_wave_sum(zacc);
+    const double tot = wave_sum(zacc);
     if (lane == 0) p3[blockIdx.x] = tot;
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) {
-    if (!first && iter + 1 >= c_max_inner) {  // inner loop exhausted: status stays TR_MAXITER
-      ctl->tcg_iters = iter + 1;
-      ctl->inner_total += iter + 1;
-      ctl->tcg_done_stamp = seq;
-      f_host_store(&hf->tcg_done_seq, seq);
-    }
-    f_host_store(&hf->last_seq_done, seq);
+    if (!first && iter + 1 >= c_max_inner) tcg_end_run_at_cap(ctl, hf, seq, iter + 1);
+    host_store(&hf->last_seq_done, seq);
   }
   if (!first && iter + 1 >= c_max_inner) retract_tail();
 }
@@ -1633,7 +1538,7 @@ __global__ __launch_bounds__(kPcBlock) void k_tcg_run(TcgRunArgs a) {
   // tCG scalars (the control block's, kept in registers by every thread: all of them see the same sums)
   double zr = 0, dPd = 0, ePe = 0, ePd = 0, alpha = 0, ePen = 0;
   const double n0 = c_ngf;
-  int status = 4, iters_done = 0;
+  int status = TR_MAXITER, iters_done = 0;
   unsigned gstep = 0;
   double acc[NR][RM];
   double nrm2 = 0;
@@ -1696,7 +1601,7 @@ __global__ __launch_bounds__(kPcBlock) void k_tcg_run(TcgRunArgs a) {
       double zacc = 0;
 #pragma unroll
       for (int aa = 0; aa < DH; ++aa) zacc += Zr.e[aa] * Rr.e[aa];
-      const double tot = f_wave_sum(zacc);
+      const double tot = wave_sum(zacc);
       if (lane == 0) st_coh(a.p3 + blockIdx.x, tot);
     }
   };
@@ -1710,12 +1615,8 @@ __global__ __launch_bounds__(kPcBlock) void k_tcg_run(TcgRunArgs a) {
       ctl->d_Pd[0] = ctl->d_Pd[1] = dPd;
       ctl->e_Pe[0] = ctl->e_Pe[1] = ePe;
       ctl->e_Pd[0] = ctl->e_Pd[1] = ePd;
-      ctl->tcg_status = status;
-      ctl->tcg_iters = iters_done;
-      ctl->inner_total += iters_done;
-      ctl->tcg_done_stamp = seq;
-      f_host_store(&a.hf->tcg_done_seq, seq);
-      f_host_store(&a.hf->last_seq_done, seq);
+      tcg_end_run(ctl, a.hf, seq, status, iters_done);
+      host_store(&a.hf->last_seq_done, seq);
     }
     __syncthreads();
     double a0 = 0, a1 = 0;
@@ -1735,8 +1636,8 @@ __global__ __launch_bounds__(kPcBlock) void k_tcg_run(TcgRunArgs a) {
       row_qf<D>(Yn);
       st_row<D>(a.X.p[cur ^ 1] + o, r, tt, pact, Yn);
     }
-    const double t0 = f_block_sum(a0, s_red);
-    const double t1 = f_block_sum(a1, s_red);
+    const double t0 = block_sum(a0, s_red);
+    const double t1 = block_sum(a1, s_red);
     if (threadIdx.x == 0) {
       a.pC[2 * blockIdx.x] = t0;
       a.pC[2 * blockIdx.x + 1] = t1;
@@ -1745,7 +1646,7 @@ __global__ __launch_bounds__(kPcBlock) void k_tcg_run(TcgRunArgs a) {
   auto give_up = [&]() {  // the grid is not co-resident: later kernels of this solve become no-ops, the host repeats
     if (threadIdx.x == 0) {
       ctl->outer_done_stamp = seq - 1;
-      f_host_store(&a.hf->tcg_abort_seq, seq);
+      host_store(&a.hf->tcg_abort_seq, seq);
     }
   };
   // ---- PC, first: z0 = Proj_X(grad Minv), res = grad, eta = H eta = 0 ----
@@ -1767,7 +1668,7 @@ __global__ __launch_bounds__(kPcBlock) void k_tcg_run(TcgRunArgs a) {
   project_z();
   RUN_STAMP(2);
   if (c_max_inner <= 0) {  // (no inner iterations allowed: the launch form leaves eta = 0 behind as well)
-    status = 4;
+    status = TR_MAXITER;
     finish();
     return;
   }
@@ -1801,21 +1702,14 @@ __global__ __launch_bounds__(kPcBlock) void k_tcg_run(TcgRunArgs a) {
       const int l = lane;
       const double pa = (l < np3) ? ld_coh(a.p3 + l) : 0.0, pb = (l + 64 < np3) ? ld_coh(a.p3 + l + 64) : 0.0;
       const double pcc = (l + 128 < np3) ? ld_coh(a.p3 + l + 128) : 0.0, pd = (l + 192 < np3) ? ld_coh(a.p3 + l + 192) : 0.0;
-      const double z_r_new = f_wave_sum((pa + pb) + (pcc + pd));
+      const double z_r_new = wave_sum((pa + pb) + (pcc + pd));
       double beta = 0;
-      if (iter > 0) beta = z_r_new / zr;
-      if (iter == 0) {
-        zr = z_r_new;
-        dPd = z_r_new;
-        ePe = 0;
-        ePd = 0;
-      } else {
-        const double c_ePd = ePd, c_alpha = alpha, c_dPd = dPd;
-        zr = z_r_new;
-        ePd = beta * (c_ePd + c_alpha * c_dPd);
-        dPd = z_r_new + beta * beta * c_dPd;
-        ePe = ePen;
-      }
+      if (iter > 0) beta = tcg_beta(z_r_new, zr);
+      const TcgDir dir = iter == 0 ? tcg_dir_start(z_r_new) : tcg_dir_next(z_r_new, beta, alpha, dPd, ePd);
+      zr = dir.z_r;
+      ePd = dir.e_Pd;
+      dPd = dir.d_Pd;
+      ePe = iter == 0 ? 0.0 : ePen;
       double accw = 0, dn = 0;
       if (own) {
 #pragma unroll
@@ -1898,21 +1792,20 @@ __global__ __launch_bounds__(kPcBlock) void k_tcg_run(TcgRunArgs a) {
         for (int w = 0; w < 4; ++w) tsum += wsum[w];
         part = tsum;
       }
-      d_Hd = f_wave_sum(part);
+      d_Hd = wave_sum(part);
     }
     const double c_zr = zr, c_dPd = dPd, c_ePe = ePe, c_ePd = ePd;
-    alpha = c_zr / d_Hd;
-    const double e_Pe_new = c_ePe + 2.0 * alpha * c_ePd + alpha * alpha * c_dPd;
-    const bool boundary = (d_Hd <= 0) || (e_Pe_new >= c_Delta * c_Delta);
-    const double step =
-        boundary ? (-c_ePd + sqrt(c_ePd * c_ePd + c_dPd * (c_Delta * c_Delta - c_ePe))) / c_dPd : alpha;
+    alpha = tcg_alpha(c_zr, d_Hd);
+    const double e_Pe_new = tcg_e_Pe_new(alpha, c_dPd, c_ePe, c_ePd);
+    const bool boundary = tcg_boundary(d_Hd, e_Pe_new, c_Delta);
+    const double step = boundary ? tcg_tau(c_dPd, c_ePe, c_ePd, c_Delta) : alpha;
     ePen = e_Pe_new;
     if (own) {
       o_eta = o_eta + step * o_d;
       o_Heta = o_Heta + step * o_h;
     }
     if (boundary) {
-      status = (d_Hd <= 0) ? 0 : 1;
+      status = tcg_boundary_status(d_Hd);
       iters_done = iter + 1;
       finish();
       return;
@@ -1941,10 +1834,8 @@ __global__ __launch_bounds__(kPcBlock) void k_tcg_run(TcgRunArgs a) {
     product();
     RUN_STAMP(8 + 7 * iter);
     {
-      const double nr = sqrt(s_Z[NR * RM]);
-      const double kappa = 0.1, tempnum = n0;  // theta = 1
-      if (nr <= n0 * fmin(tempnum, kappa)) {
-        status = (kappa < tempnum) ? 2 : 3;
+      if (tcg_residual_done(sqrt(s_Z[NR * RM]), n0)) {
+        status = tcg_residual_status(n0);
         iters_done = iter + 1;
         finish();
         return;
@@ -1969,7 +1860,7 @@ template <int D>
 __global__ __launch_bounds__(kBlock) void k_g_rgrad(ManiDesc m, Buf2 Xb, Buf2 EGb, Buf2 RGb, Buf2 Sb, int sel,
                                                     double *__restrict__ partials, double *__restrict__ posenorm,
                                                     Gate g) {
-  if (g.ctl && g.gate && f_gated(g.ctl, g.seq, g.gate)) return;
+  if (gated(g.ctl, g.seq, g.gate)) return;
   __shared__ double s_red[16];
   constexpr int DH = D + 1;
   const int idx = g.ctl ? ((g.ctl->cur ^ sel) & 1) : 0;
@@ -2005,7 +1896,7 @@ __global__ __launch_bounds__(kBlock) void k_g_rgrad(ManiDesc m, Buf2 Xb, Buf2 EG
     }
     if (RG) st_row<D>(RG + o, r, t, active, E);
   }
-  const double tot = f_block_sum(acc, s_red);
+  const double tot = block_sum(acc, s_red);
   if (threadIdx.x == 0 && partials) partials[blockIdx.x] = tot;
 }
 
@@ -2015,7 +1906,7 @@ __global__ __launch_bounds__(kBlock) void k_g_retract(ManiDesc m, Buf2 Xb, const
                                                       double alpha, Buf2 Ob, int selOut, Buf2 gradb,
                                                       const double *__restrict__ HV, double *__restrict__ partials,
                                                       Gate g) {
-  if (g.ctl && g.gate && f_gated(g.ctl, g.seq, g.gate)) return;
+  if (gated(g.ctl, g.seq, g.gate)) return;
   __shared__ double s_red[16];
   constexpr int DH = D + 1;
   const int cur = g.ctl ? (g.ctl->cur & 1) : 0;
@@ -2048,8 +1939,8 @@ __global__ __launch_bounds__(kBlock) void k_g_retract(ManiDesc m, Buf2 Xb, const
     st_row<D>(out + o, r, t, active, Y);
   }
   if (partials) {
-    const double t0 = f_block_sum(a0, s_red);
-    const double t1 = f_block_sum(a1, s_red);
+    const double t0 = block_sum(a0, s_red);
+    const double t1 = block_sum(a1, s_red);
     if (threadIdx.x == 0) {
       partials[2 * blockIdx.x] = t0;
       partials[2 * blockIdx.x + 1] = t1;
@@ -2195,9 +2086,9 @@ __device__ __forceinline__ int quad_bcast_i(int v) {
 }
 __device__ __forceinline__ double quad_sum(double v) {
   asm volatile("" : "+v"(v));
-  v += f_dpp<0xB1>(v);  // quad_perm [1,0,3,2]
+  v += dpp_move<0xB1>(v);  // quad_perm [1,0,3,2]
   asm volatile("" : "+v"(v));
-  v += f_dpp<0x4E>(v);  // quad_perm [2,3,0,1]
+  v += dpp_move<0x4E>(v);  // quad_perm [2,3,0,1]
   return v;
 }
 // Measured on the 100k lattice at r = 5, warm / cold us (gfx950, round 5): this form 22.6 / 27.5; its loads requested two
@@ -2209,7 +2100,7 @@ constexpr int kQBlock = 128;  // threads per workgroup: 32 poses, as the 8-lanes
 template <int D, int R, bool DOTS, bool GRAD>
 __global__ __launch_bounds__(kQBlock) void k_spmm_bsrq(BsrDev A, Buf2 Xb, int selX, const double *__restrict__ G, Buf2 Yb,
                                                        int selY, double *__restrict__ partials, Gate g, BsrGradOut go) {
-  if (g.ctl && g.gate && f_gated(g.ctl, g.seq, g.gate)) return;
+  if (gated(g.ctl, g.seq, g.gate)) return;
   constexpr int DH = D + 1, BS = DH * DH, PW = kQBlock / 4;
   // (pose, block) pairs whose loads a lane requests together: the four column indices of one index load, two at a time
   // at r >= 7 where four columns of the neighbours alone are 56-64 registers
@@ -2276,10 +2167,10 @@ __global__ __launch_bounds__(kQBlock) void k_spmm_bsrq(BsrDev A, Buf2 Xb, int se
       // pairs {0,1}, {2,3}: a lane keeps the column of its own parity and sends the other to its partner
       const double keep0 = odd ? acc[1][i] : acc[0][i], send0 = odd ? acc[0][i] : acc[1][i];
       const double keep1 = odd ? acc[3][i] : acc[2][i], send1 = odd ? acc[2][i] : acc[3][i];
-      const double t0 = keep0 + f_dpp<0xB1>(send0);  // columns (c & 1) over lanes c, c ^ 1
-      const double t1 = keep1 + f_dpp<0xB1>(send1);  // columns 2 + (c & 1)
+      const double t0 = keep0 + dpp_move<0xB1>(send0);  // columns (c & 1) over lanes c, c ^ 1
+      const double t1 = keep1 + dpp_move<0xB1>(send1);  // columns 2 + (c & 1)
       const double keep = upper ? t1 : t0, send = upper ? t0 : t1;
-      e[i] = keep + f_dpp<0x4E>(send);
+      e[i] = keep + dpp_move<0x4E>(send);
     }
     const size_t oc = ((size_t)(inr ? pose : 0) * DH + cc) * R;
     double xo[R], gg[R];
@@ -2350,15 +2241,15 @@ __global__ __launch_bounds__(kQBlock) void k_spmm_bsrq(BsrDev A, Buf2 Xb, int se
     }
   }
   if (DOTS) {
-    const double a = f_block_sum(d0, s_red);
-    const double b = f_block_sum(d1, s_red);
+    const double a = block_sum(d0, s_red);
+    const double b = block_sum(d1, s_red);
     if (threadIdx.x == 0) {
       partials[2 * blockIdx.x] = a;
       partials[2 * blockIdx.x + 1] = b;
     }
   }
   if (GRAD) {
-    const double cs = f_block_sum(dg, s_red);
+    const double cs = block_sum(dg, s_red);
     if (threadIdx.x == 0) go.pB[blockIdx.x] = cs;
   }
 }
@@ -2383,23 +2274,15 @@ int group_grid(int n) {
 __global__ void k_ctl_init(SolverCtl *c, double tol, double Delta, double maxDelta, int max_outer, int stop_on_accept,
                            int max_inner) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  c->f1 = c->ngf = c->f2 = c->rho = c->fInit = c->gradNormInit = 0;
-  c->Delta = Delta;
-  c->maxDelta = maxDelta;
-  c->tol = tol;
-  c->cur = 0;
-  c->outer_it = 0;
-  c->max_outer = max_outer;
-  c->accepted = 0;
-  c->last_accepted = 0;
-  c->stop_on_accept = stop_on_accept;
-  c->outer_done_stamp = INT_MAX;
-  c->alpha = c->e_Pe_n = c->norm_r0 = 0;
-  c->tcg_done_stamp = INT_MAX;
-  c->tcg_status = 4;
-  c->tcg_iters = 0;
-  c->inner_total = 0;
-  c->max_inner = max_inner;
+  c->f1 = c->ngf = c->fInit = c->gradNormInit = 0;
+  CtlInit ci;
+  ci.tol = tol;
+  ci.Delta = Delta;
+  ci.maxDelta = maxDelta;
+  ci.max_outer = max_outer;
+  ci.stop_on_accept = stop_on_accept;
+  ci.max_inner = max_inner;
+  ctl_arm(c, ci);
 }
 void launch_ctl_init(hipStream_t st, SolverCtl *c, double tol, double Delta, double maxDelta, int max_outer,
                      int stop_on_accept, int max_inner) {
@@ -2423,7 +2306,7 @@ __global__ __launch_bounds__(kBlock) void k_eval_partial(const int *__restrict__
   const int i0 = lo + sl * per, i1 = min(hi, i0 + per);
   double v = 0;
   for (int i = i0 + (int)threadIdx.x; i < i1; i += kBlock) v += posenorm[i];
-  v = f_block_sum(v, s_red);
+  v = block_sum(v, s_red);
   if (threadIdx.x == 0) part[blockIdx.x] = v;
 }
 __global__ __launch_bounds__(kBlock) void k_eval_finish(int R, const int *__restrict__ pose_start,
@@ -2449,7 +2332,7 @@ __global__ __launch_bounds__(kBlock) void k_eval_finish(int R, const int *__rest
 #pragma unroll
         for (int u = 0; u < 8; ++u) v += (i0 + 64 * u < hi) ? t8[u] : 0.0;
       }
-      v = f_wave_sum(v);
+      v = wave_sum(v);
       if (lane == 0) s_bn[b] = v;
     }
   } else if (part) {  // the slices of k_eval_partial, in slice order
@@ -2472,7 +2355,7 @@ __global__ __launch_bounds__(kBlock) void k_eval_finish(int R, const int *__rest
 #pragma unroll
         for (int u = 0; u < 8; ++u) v += (i0 + 64 * u < hi) ? t8[u] : 0.0;
       }
-      v = f_wave_sum(v);
+      v = wave_sum(v);
       if (lane == 0) s_bn[b] = v;
     }
   }
@@ -2492,8 +2375,8 @@ __global__ __launch_bounds__(kBlock) void k_eval_finish(int R, const int *__rest
       q1 += c8[u];
     }
   }
-  const double fq = f_block_sum(q0, s_red);  // (its barriers also publish s_bn)
-  const double fg = f_block_sum(q1, s_red);
+  const double fq = block_sum(q0, s_red);  // (its barriers also publish s_bn)
+  const double fg = block_sum(q1, s_red);
   if (threadIdx.x == 0) {
     double g2 = 0, best = -1;
     int arg = 0;

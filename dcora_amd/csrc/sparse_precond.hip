@@ -17,17 +17,10 @@ namespace dcora {
 
 namespace {
 
-__device__ __forceinline__ bool sp_gated(const SolverCtl *ctl, int seq, int gate) {
-  if (gate == 0 || ctl == nullptr) return false;
-  if (seq > ctl->outer_done_stamp) return true;
-  if (gate == 2 && seq > ctl->tcg_done_stamp) return true;
-  return false;
-}
-
 // y[0][j] = R[perm[j]]  (k unknowns of r values each)
 __global__ __launch_bounds__(kBlock) void k_sp_permute_in(int r, int k, const int *__restrict__ perm, Buf2 Rb,
                                                           double *__restrict__ y, Gate g) {
-  if (sp_gated(g.ctl, g.seq, g.gate)) return;
+  if (gated(g.ctl, g.seq, g.gate)) return;
   const double *__restrict__ R = Rb.p[g.ctl ? (g.ctl->cur & 1) : 0];
   const long n = (long)r * k;
   for (long e = (long)blockIdx.x * kBlock + threadIdx.x; e < n; e += (long)gridDim.x * kBlock) {
@@ -40,7 +33,7 @@ __global__ __launch_bounds__(kBlock) void k_sp_permute_out(int r, int k, const i
                                                            const int *__restrict__ out_off,
                                                            const double *__restrict__ y, double *__restrict__ Z,
                                                            Gate g) {
-  if (sp_gated(g.ctl, g.seq, g.gate)) return;
+  if (gated(g.ctl, g.seq, g.gate)) return;
   const long n = (long)r * k;
   for (long e = (long)blockIdx.x * kBlock + threadIdx.x; e < n; e += (long)gridDim.x * kBlock) {
     const int j = (int)(e / r), t = (int)(e - (long)j * r);
@@ -111,7 +104,7 @@ __device__ __forceinline__ void hub_x2(int r, const HubIn &H, const SolverCtl *c
 }
 // (a replay of fewer than two launches: the stage that found no launch to ride in)
 __global__ __launch_bounds__(kBlock) void k_sp_hub_stage(int r, HubIn H, const double *__restrict__ y0, Gate g) {
-  if (sp_gated(g.ctl, g.seq, g.gate)) return;
+  if (gated(g.ctl, g.seq, g.gate)) return;
   __shared__ double s_part[64 * 16];
   if (H.stage == 1)
     hub_slice<kBlock>(r, H, y0, blockIdx.x, s_part);
@@ -123,7 +116,7 @@ __global__ __launch_bounds__(kBlock) void k_sp_permute_out_hub(int r, int k, con
                                                                const int *__restrict__ out_off,
                                                                const double *__restrict__ y,
                                                                double *__restrict__ Z, HubDev H, Gate g) {
-  if (sp_gated(g.ctl, g.seq, g.gate)) return;
+  if (gated(g.ctl, g.seq, g.gate)) return;
   __shared__ double s_x2[64 * 16];
   const int h = H.h;
   for (int e = threadIdx.x; e < h * r; e += kBlock) {
@@ -276,7 +269,7 @@ __global__ __launch_bounds__(kMtBlock) void k_sp_mtile(const MWave *__restrict__
   // the hubs' dots over the input image (first launch only: nothing has written it yet); they are long chains of few
   // waves, so they take the grid's first workgroups (at its end they were a 3 us tail)
   if ((int)blockIdx.x < nhubwg) {
-    if (!sp_gated(g.ctl, g.seq, g.gate)) {
+    if (!gated(g.ctl, g.seq, g.gate)) {
       if (hub.stage == 1)
         hub_slice<kMtBlock>(r, hub, y, (int)blockIdx.x, &s_part[0][0][0]);
       else
@@ -289,7 +282,7 @@ __global__ __launch_bounds__(kMtBlock) void k_sp_mtile(const MWave *__restrict__
   ConstInts rp = (ConstInts)(recs + ((size_t)((int)blockIdx.x - nhubwg) * kMtWaves + wave));
   const int t_out = rp[0], t_carry = rp[1], t_nrows = rp[2], t_kind = rp[3], t_first = rp[4], t_n = rp[5], t_solo = rp[7];
   // the gate is tested AFTER the record has been requested: the two loads travel together
-  if (sp_gated(g.ctl, g.seq, g.gate)) return;
+  if (gated(g.ctl, g.seq, g.gate)) return;
   const int kq = lane >> 4, blk = (lane >> 2) & 3, li = lane & 3;  // operand roles: K entry, block, row (A) / pair (B)
   constexpr int NH = HALF ? 1 : 2;  // columns a lane holds per 8-column group
   const int jj = HALF ? li : 2 * li;
