@@ -504,7 +504,10 @@ class RbcdSession:
     """Agents + synchronous RBCD++ driver on the device (ref examples/MultiRobotExample.cpp:121-307)"""
 
     def __init__(self, ds, num_robots=5, r=5, acceleration=True, restart_interval=30, params=None, rank=0,
-                 world_size=1, device=0, stream=None):
+                 world_size=1, device=0, stream=None, robust=None, fixed_weight=None):
+        """robust: a robust.RobustCostParameters -> a session whose measurement weights update in place
+        (update_weights / set_weights / get_weights / robust_info); it starts with weight 1 on every loop closure whose
+        fixed_weight flag (m booleans, default none) is off (Agent::initializeRobustOptimization)"""
         self.ds, self.R, self.r = ds, num_robots, r
         self.k = (ds.d + 1) * ds.n
         o = RbcdOptions()
@@ -517,9 +520,20 @@ class RbcdSession:
         dsh = ds.handle()
         self.h = C.c_void_p()
         try:
-            check(capi.lib().dcora_rbcd_create(dsh, C.byref(o), C.byref(self.h)))
+            if robust is None:
+                check(capi.lib().dcora_rbcd_create(dsh, C.byref(o), C.byref(self.h)))
+            else:
+                fx = None
+                if fixed_weight is not None:
+                    fx = np.ascontiguousarray(fixed_weight, np.int32)
+                    if fx.shape != (ds.m,):
+                        raise ValueError("fixed_weight needs one flag per measurement")
+                check(capi.lib().dcora_rbcd_create_robust(dsh, C.byref(o), C.byref(robust.c),
+                                                          None if fx is None else fx.ctypes.data_as(C.c_void_p),
+                                                          C.byref(self.h)))
         finally:
             capi.lib().dcora_dataset_destroy(dsh)
+        self.m = ds.m
 
     def close(self):
         if getattr(self, "h", None):
@@ -580,6 +594,30 @@ class RbcdSession:
         r = ROptResult()
         check(capi.lib().dcora_rbcd_last_result(self.h, C.byref(r)))
         return r.as_dict()
+
+    # ---- robust sessions (created with robust=...) ----
+    def update_weights(self, reset_to_initial=False):
+        """Agent::updateMeasurementWeights of every agent on the current iterate; returns the loop closures'
+        {accepted, rejected, undecided} counts"""
+        c = np.zeros(3, np.int32)
+        check(capi.lib().dcora_rbcd_update_weights(self.h, int(bool(reset_to_initial)), c.ctypes.data_as(C.c_void_p)))
+        return {"accepted": int(c[0]), "rejected": int(c[1]), "undecided": int(c[2])}
+
+    def set_weights(self, w):
+        w = np.ascontiguousarray(w, np.float64)
+        if w.shape != (self.m,):
+            raise ValueError("set_weights needs one weight per measurement")
+        check(capi.lib().dcora_rbcd_set_weights(self.h, w))
+
+    def get_weights(self):
+        w = np.zeros(self.m)
+        check(capi.lib().dcora_rbcd_get_weights(self.h, w))
+        return w
+
+    def robust_info(self):
+        mu, n = C.c_double(), C.c_int()
+        check(capi.lib().dcora_rbcd_robust_info(self.h, C.byref(mu), C.byref(n)))
+        return {"mu": mu.value, "updates": n.value}
 
     # ---- multi-process pieces ----
     def X_device_ptr(self):

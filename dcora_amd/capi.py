@@ -142,6 +142,11 @@ SIGNATURES = {
     "dcora_rbcd_last_result": (C.c_int, [_vp, C.POINTER(ROptResult)]),
     "dcora_rbcd_profile_tcg_runs": (C.c_int, [_vp, C.c_int]),
     "dcora_rbcd_profile_tcg_read": (C.c_int, [_vp, _dp]),
+    "dcora_rbcd_create_robust": (C.c_int, [_vp, C.POINTER(RbcdOptions), C.POINTER(RobustParams), _vp, C.POINTER(_vp)]),
+    "dcora_rbcd_update_weights": (C.c_int, [_vp, C.c_int, _vp]),
+    "dcora_rbcd_set_weights": (C.c_int, [_vp, _dp]),
+    "dcora_rbcd_get_weights": (C.c_int, [_vp, _dp]),
+    "dcora_rbcd_robust_info": (C.c_int, [_vp, _PD, _PI]),
     "dcora_rbcd_X_device_ptr": (C.c_int, [_vp, C.POINTER(_vp)]),
     "dcora_rbcd_public_count": (C.c_int, [_vp, C.c_int, _PI]),
     "dcora_rbcd_public_indices": (C.c_int, [_vp, C.c_int, _ip]),

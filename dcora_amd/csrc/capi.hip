@@ -967,6 +967,67 @@ int dcora_rbcd_create(dcora_dataset_t ds, const dcora_rbcd_options *opt, dcora_r
   return DCORA_OK;
   DCORA_CATCH
 }
+// Agent::initializeRobustOptimization (ref src/Agent.cpp:1332-1346) of every agent at creation
+int dcora_rbcd_create_robust(dcora_dataset_t ds, const dcora_rbcd_options *opt, const dcora_robust_params *robust,
+                             const int *fixed_weight, dcora_rbcd_t *out) {
+  if (!ds || !opt || !robust || !out) return bad("null argument");
+  if (opt->world_size != 1) {
+    set_last_error("rbcd robust: only single-process sessions (world_size 1) update weights");
+    return DCORA_ERR_UNSUPPORTED;
+  }
+  DCORA_TRY
+  dcora_rbcd_s *h = new dcora_rbcd_s;
+  const int rc = h->s.init_robust(ds->ds, *opt, *robust, fixed_weight);
+  if (rc) {
+    delete h;
+    return rc;
+  }
+  *out = h;
+  return DCORA_OK;
+  DCORA_CATCH
+}
+namespace {
+// the robust entries' refusals: multi-process sessions first, then sessions without robust state
+int robust_session(dcora_rbcd_t s) {
+  if (!s) return bad("null");
+  if (s->s.opt.world_size != 1) {
+    set_last_error("rbcd robust: only single-process sessions (world_size 1) update weights");
+    return DCORA_ERR_UNSUPPORTED;
+  }
+  if (!s->s.robust) return bad("rbcd robust: the session was not created by dcora_rbcd_create_robust");
+  return DCORA_OK;
+}
+}  // namespace
+// Agent::updateMeasurementWeights (ref src/Agent.cpp:1397-1441) of every agent
+int dcora_rbcd_update_weights(dcora_rbcd_t s, int reset_to_initial, int counts[3]) {
+  const int rc = robust_session(s);
+  if (rc) return rc;
+  DCORA_TRY
+  return s->s.update_weights(reset_to_initial != 0, counts);
+  DCORA_CATCH
+}
+// Agent::setMeasurementWeight (ref src/Agent.cpp:1443-1454) of every measurement
+int dcora_rbcd_set_weights(dcora_rbcd_t s, const double *w) {
+  const int rc = robust_session(s);
+  if (rc) return rc;
+  if (!w) return bad("null argument");
+  DCORA_TRY
+  return s->s.set_weights(w);
+  DCORA_CATCH
+}
+int dcora_rbcd_get_weights(dcora_rbcd_t s, double *w) {
+  const int rc = robust_session(s);
+  if (rc) return rc;
+  if (!w) return bad("null argument");
+  return s->s.get_weights(w);
+}
+int dcora_rbcd_robust_info(dcora_rbcd_t s, double *mu, int *updates) {
+  const int rc = robust_session(s);
+  if (rc) return rc;
+  if (mu) *mu = s->s.robust->cost.mu();
+  if (updates) *updates = s->s.robust->updates;
+  return DCORA_OK;
+}
 int dcora_rbcd_destroy(dcora_rbcd_t s) {
   delete s;
   return DCORA_OK;

@@ -9,6 +9,8 @@
 #include "device_problem.h"
 #include "exchange_session.h"
 #include "host_graph.h"
+#include "host_robust.h"
+#include "robust.h"
 
 namespace dcora {
 
@@ -34,6 +36,24 @@ struct AgentDev {
   DevBuf<double> nbr[2];
   std::vector<char> got[2];
   bool last_skipped = false;
+};
+
+// Robust state of a session created by dcora_rbcd_create_robust (world_size 1): the agents' GNC loop inside one live
+// session (Agent::initializeRobustOptimization / updateMeasurementWeights, ref src/Agent.cpp:1332-1346, 1397-1441).
+// A weight change rebuilds the VALUES of Q_bb, the coupling blocks and the central Q on their creation patterns (a
+// weight of 0 leaves explicit zeros), and the preconditioners through the path creation takes.
+struct RobustSession {
+  explicit RobustSession(const dcora_robust_params &p) : cost(p), params(p) {}
+  RobustCost cost;
+  dcora_robust_params params;
+  int updates = 0;
+  std::vector<PoseMeas> meas;    // the dataset (global pose indices) with the current weights
+  std::vector<char> update;      // loop closures whose weight is not fixed: what updateMeasurementWeights rewrites
+  std::vector<char> meas_zero;   // weight 0 at creation: the patterns do not hold these measurements
+  RobustEdges edges;             // device copy of the measurements and of the weights
+  DevBuf<double> X_initial;      // the last set_X (robustOptNumResets: setXToInitialGuess)
+  std::vector<HostCsr> Qpat, Cpat;  // creation patterns (rp, ci) of every hosted agent's Q_bb and coupling block
+  HostCsr central_pat;
 };
 
 class RbcdSession : public ExchangeSession {
@@ -62,6 +82,13 @@ class RbcdSession : public ExchangeSession {
 
   ~RbcdSession();
   int init(const HostDataset &ds, const dcora_rbcd_options &o);
+  // robust sessions: weight 1 on every loop closure that is not fixed (fixed: m flags or null), then init
+  std::unique_ptr<RobustSession> robust;
+  int init_robust(const HostDataset &ds, const dcora_rbcd_options &o, const dcora_robust_params &p, const int *fixed);
+  // updateMeasurementWeights on the current iterate; counts (may be null): accepted, rejected, undecided closures
+  int update_weights(bool reset_to_initial, int counts[3]);
+  int set_weights(const double *w);  // all m weights; refused (session untouched) when one is negative or not finite
+  int get_weights(double *w) const;
   int set_X(const double *Xh);
   int get_X(double *Xh);
   int set_acceleration(bool on);
@@ -123,6 +150,8 @@ class RbcdSession : public ExchangeSession {
   int update_selected_agent(AgentDev &a, bool restart);
   hipEvent_t fork_ev_ = nullptr;
   int solve_block(AgentDev &a, std::string *err, bool serial = false);
+  int rebuild_values(const std::vector<PoseMeas> &meas);
+  int initialize_acceleration();
 };
 
 }  // namespace dcora

@@ -41,6 +41,26 @@ static int nesterov_solved(hipStream_t st, DeviceProblem &pb, int mode, double a
   return DCORA_OK;
 }
 
+// a measurement with global pose indices as the agents of the contiguous partition see it: owners and local indices
+static PoseMeas agent_local(const PoseMeas &mi, const Partition &P) {
+  PoseMeas e = mi;
+  e.r1 = P.robot_of(mi.p1);
+  e.r2 = P.robot_of(mi.p2);
+  e.p1 = mi.p1 - P.start(e.r1);
+  e.p2 = mi.p2 - P.start(e.r2);
+  return e;
+}
+
+// the pattern (rp, ci) of a matrix: what a robust session's later weights are scattered onto
+static HostCsr pattern_of(const HostCsr &A) {
+  HostCsr p;
+  p.n = A.n;
+  p.ncols = A.ncols;
+  p.rp = A.rp;
+  p.ci = A.ci;
+  return p;
+}
+
 RbcdSession::~RbcdSession() {
   if (eval_host) (void)hipHostFree((void *)eval_host);
   if (x_stage) (void)hipHostFree((void *)x_stage);
@@ -119,11 +139,7 @@ int RbcdSession::init(const HostDataset &ds, const dcora_rbcd_options &o) {
   std::vector<std::vector<PoseMeas>> touching(R);
   std::vector<std::set<int>> pub(R), nb(R), req(R);
   for (const PoseMeas &mi : ds.meas) {
-    PoseMeas e = mi;
-    e.r1 = P.robot_of(mi.p1);
-    e.r2 = P.robot_of(mi.p2);
-    e.p1 = mi.p1 - P.start(e.r1);
-    e.p2 = mi.p2 - P.start(e.r2);
+    const PoseMeas e = agent_local(mi, P);
     touching[e.r1].push_back(e);
     if (e.r2 != e.r1) {
       touching[e.r2].push_back(e);
@@ -201,6 +217,10 @@ int RbcdSession::init(const HostDataset &ds, const dcora_rbcd_options &o) {
     if (!rc) {
       HostCsr C = build_coupling_pgo(d, P, b, global);
       rc = a.coupling.upload(C);
+      if (robust) {
+        robust->Qpat[(size_t)b] = pattern_of(Qb);
+        robust->Cpat[(size_t)b] = pattern_of(C);
+      }
     }
     if (!rc) rc = stream_acquire(o.device, &a.own);
     if (!rc && hipEventCreateWithFlags(&a.done, hipEventDisableTiming) != hipSuccess) rc = DCORA_ERR_HIP;
@@ -223,6 +243,7 @@ int RbcdSession::init(const HostDataset &ds, const dcora_rbcd_options &o) {
     dcora_dims dims{r, d, n, 0, 0};
     central_rc = central->init(dims, Qc, nullptr, -1.0, o.device, st);
     if (central_rc) central_err = dcora_last_error();
+    if (robust) robust->central_pat = pattern_of(Qc);
   };
   {
     const size_t nh = hosted_ids.size();
@@ -280,6 +301,7 @@ int RbcdSession::set_X(const double *Xh) {
   DCORA_HIP(hipMemcpyAsync(Vg.p, Xg.p, B, hipMemcpyDeviceToDevice, st));
   DCORA_HIP(hipMemcpyAsync(Yg.p, Xg.p, B, hipMemcpyDeviceToDevice, st));
   DCORA_HIP(hipMemcpyAsync(XPrevg.p, Xg.p, B, hipMemcpyDeviceToDevice, st));
+  if (robust) DCORA_HIP(hipMemcpyAsync(robust->X_initial.p, Xg.p, B, hipMemcpyDeviceToDevice, st));
   DCORA_HIP(hipStreamSynchronize(st));
   gamma = alpha = 0;
   iteration = 0;
@@ -316,6 +338,291 @@ int RbcdSession::get_X(double *Xh) {
   DCORA_HIP(hipMemcpyAsync(x_stage, Xg.p, B, hipMemcpyDeviceToHost, st));
   DCORA_HIP(hipStreamSynchronize(st));
   std::memcpy(Xh, x_stage, B);
+  return DCORA_OK;
+}
+
+// ---- robust sessions -------------------------------------------------------------------------------------------
+// Agent::initializeRobustOptimization for every agent (ref src/Agent.cpp:1332-1346): weight 1 on every loop closure
+// whose weight is not fixed.  A loop closure is every measurement but odometry, i.e. but p2 == p1 + 1 inside one agent
+// of the contiguous partition (driver.loop_closure_mask).  With weights 1 the patterns are the largest any later
+// weights can give: they are kept, and a weight change only rewrites values.
+int RbcdSession::init_robust(const HostDataset &ds, const dcora_rbcd_options &o, const dcora_robust_params &p,
+                             const int *fixed) {
+  if (o.world_size != 1) {
+    set_last_error("rbcd robust: only single-process sessions (world_size 1) update weights");
+    return DCORA_ERR_UNSUPPORTED;
+  }
+  if (o.num_robots < 1 || ds.n / o.num_robots < 1) {
+    set_last_error("rbcd: bad num_robots / rank / world_size");
+    return DCORA_ERR_BAD_ARG;
+  }
+  if (p.cost_type < DCORA_ROBUST_L2 || p.cost_type > DCORA_ROBUST_GNC_TLS) {
+    set_last_error("rbcd robust: unknown robust cost type");
+    return DCORA_ERR_BAD_ARG;
+  }
+  for (const PoseMeas &q : ds.meas)
+    if (q.p1 < 0 || q.p1 >= ds.n || q.p2 < 0 || q.p2 >= ds.n) {
+      set_last_error("rbcd robust: pose index out of range");
+      return DCORA_ERR_BAD_ARG;
+    }
+  robust.reset(new RobustSession(p));
+  RobustSession &rs = *robust;
+  Partition Pt;
+  Pt.R = o.num_robots;
+  Pt.n = ds.n;
+  Pt.per = ds.n / o.num_robots;
+  HostDataset rds = ds;
+  const size_t m = rds.meas.size();
+  rs.update.assign(m, 0);
+  for (size_t e = 0; e < m; ++e) {
+    PoseMeas &q = rds.meas[e];
+    const bool odometry = Pt.robot_of(q.p1) == Pt.robot_of(q.p2) && q.p2 == q.p1 + 1;
+    if (odometry || (fixed && fixed[e])) continue;
+    rs.update[e] = 1;
+    q.weight = 1.0;
+  }
+  rs.meas = rds.meas;
+  rs.meas_zero.assign(m, 0);
+  for (size_t e = 0; e < m; ++e) rs.meas_zero[e] = rds.meas[e].weight == 0.0;
+  rs.Qpat.assign((size_t)o.num_robots, HostCsr());
+  rs.Cpat.assign((size_t)o.num_robots, HostCsr());
+  int rc = init(rds, o);
+  if (rc) return rc;
+  rc = rs.edges.upload(rds, rs.update);
+  if (rc) return rc;
+  DCORA_HIP(rs.X_initial.alloc((size_t)r * (d + 1) * n));
+  DCORA_HIP(hipMemsetAsync(rs.X_initial.p, 0, sizeof(double) * (size_t)r * (d + 1) * n, st));
+  DCORA_HIP(hipStreamSynchronize(st));
+  return DCORA_OK;
+}
+
+namespace {
+// the values of A on the pattern P (zeros where A has no entry); false when an entry of A lies outside P
+bool scatter_on_pattern(const HostCsr &A, const HostCsr &P, HostCsr *out) {
+  if (A.n != P.n || A.ncols != P.ncols) return false;
+  out->n = P.n;
+  out->ncols = P.ncols;
+  out->rp = P.rp;
+  out->ci = P.ci;
+  out->v.assign(P.ci.size(), 0.0);
+  for (int i = 0; i < A.n; ++i) {
+    int q = P.rp[i];
+    for (int k = A.rp[i]; k < A.rp[i + 1]; ++k) {
+      while (q < P.rp[i + 1] && P.ci[q] < A.ci[k]) ++q;
+      if (q == P.rp[i + 1] || P.ci[q] != A.ci[k]) return false;
+      out->v[q] = A.v[k];
+    }
+  }
+  return true;
+}
+}  // namespace
+
+// Graph::clearDataMatrices + constructDataMatrices with new weights (ref src/Agent.cpp:1416): Q_bb, the coupling
+// blocks and the central Q from the host builders that creation uses, so that every value equals a fresh session's
+// bit for bit; the values land on the creation patterns.  The preconditioners come from, and go into, the cache as at
+// creation: a new image is attached, an image somebody else still holds is never written.  The host work runs side by
+// side as in init: the agents' builds, then their preconditioners, beside the central Q's build.
+int RbcdSession::rebuild_values(const std::vector<PoseMeas> &meas) {
+  RobustSession &rs = *robust;
+  const int dh = d + 1;
+  // a pattern holds every entry of its creation weights; only a weight that was 0 then can reach outside it
+  for (size_t e = 0; e < meas.size(); ++e)
+    if (rs.meas_zero[e] && meas[e].weight != 0.0) {
+      set_last_error("rbcd robust: a weight that was 0 at creation cannot become nonzero (the session's patterns "
+                     "do not hold that measurement)");
+      return DCORA_ERR_BAD_ARG;
+    }
+  std::vector<std::vector<PoseMeas>> touching(R);
+  for (const PoseMeas &mi : meas) {
+    const PoseMeas e = agent_local(mi, P);
+    touching[e.r1].push_back(e);
+    if (e.r2 != e.r1) touching[e.r2].push_back(e);
+  }
+  std::vector<PoseMeas> global = meas;
+  for (PoseMeas &e : global) e.r1 = e.r2 = 0;
+  std::vector<int> hosted_ids;
+  for (const AgentDev &a : agents)
+    if (a.hosted && a.prob) hosted_ids.push_back(a.id);
+  const size_t nh = hosted_ids.size();
+  DCORA_HIP(hipSetDevice(opt.device));
+  // nothing of the session is in flight while its matrices and preconditioner images change
+  for (const AgentDev &a : agents)
+    if (a.own) DCORA_HIP(hipStreamSynchronize(a.own));
+  DCORA_HIP(hipStreamSynchronize(st));
+  HostCsr Qcs;
+  HostBsr cbsr;
+  bool central_ok = true;
+  std::thread central_th([&] {
+    if (!central) return;
+    central_ok = scatter_on_pattern(build_Q_pgo(d, n, 0, global), rs.central_pat, &Qcs);
+    if (central_ok && central->has_bsr) cbsr = bsr_from_csr(Qcs, dh);
+  });
+  struct Join {
+    std::thread &t;
+    ~Join() {
+      if (t.joinable()) t.join();
+    }
+  } join_central{central_th};
+  std::vector<HostCsr> Qn(nh), Qs(nh), Cs(nh);
+  std::vector<HostBsr> bsr(nh);
+  std::vector<char> ok(nh, 0);
+  {
+    std::atomic<size_t> next(0);
+    auto worker = [&] {
+      for (;;) {
+        const size_t i = next.fetch_add(1);
+        if (i >= nh) break;
+        const int b = hosted_ids[i];
+        Qn[i] = build_Q_pgo(d, agents[b].n, b, touching[b]);
+        ok[i] = scatter_on_pattern(Qn[i], rs.Qpat[(size_t)b], &Qs[i]) &&
+                scatter_on_pattern(build_coupling_pgo(d, P, b, global), rs.Cpat[(size_t)b], &Cs[i]);
+        if (ok[i] && agents[b].prob->has_bsr) bsr[i] = bsr_from_csr(Qs[i], dh);
+      }
+    };
+    std::vector<std::thread> th;
+    for (size_t t = 1; t < std::min<size_t>(nh, 8); ++t) th.emplace_back(worker);
+    worker();
+    for (std::thread &t : th) t.join();
+  }
+  for (size_t i = 0; i < nh; ++i)
+    if (!ok[i]) {
+      set_last_error("rbcd robust: the weights give a matrix entry outside the session's pattern");
+      return DCORA_ERR_BAD_ARG;
+    }
+  for (size_t i = 0; i < nh; ++i) {
+    AgentDev &a = agents[(size_t)hosted_ids[i]];
+    DeviceProblem &pb = *a.prob;
+    DCORA_HIP(hipMemcpyAsync(pb.Q.v.p, Qs[i].v.data(), sizeof(double) * Qs[i].v.size(), hipMemcpyHostToDevice, st));
+    if (pb.has_bsr)
+      DCORA_HIP(hipMemcpyAsync(pb.Qb.bv.p, bsr[i].bv.data(), sizeof(double) * bsr[i].bv.size(), hipMemcpyHostToDevice, st));
+    if (!Cs[i].v.empty())
+      DCORA_HIP(hipMemcpyAsync(a.coupling.v.p, Cs[i].v.data(), sizeof(double) * Cs[i].v.size(), hipMemcpyHostToDevice, st));
+  }
+  // the preconditioners of the new matrices, as init builds them: the dense batch first, then every problem attaches
+  if ((long)(n / R + 1) * dh <= kDensePrecondMaxK && nh > 1) {
+    std::vector<const HostCsr *> ptrs;
+    for (const HostCsr &Q : Qn) ptrs.push_back(&Q);
+    const int prc = precond_prebuild_dense(ptrs, 0.1, dh, opt.device);
+    if (prc) return prc;
+  }
+  std::vector<int> rcs(nh, DCORA_OK);
+  std::vector<std::string> errs(nh);
+  auto attach = [&](size_t i) {
+    if (hipSetDevice(opt.device) != hipSuccess) {
+      rcs[i] = DCORA_ERR_HIP;
+      return;
+    }
+    rcs[i] = agents[(size_t)hosted_ids[i]].prob->build_preconditioner(Qn[i], 0.1);
+    if (rcs[i]) errs[i] = dcora_last_error();
+  };
+  if (nh > 1 && (long)(n / R) * dh >= 1024) {  // (large blocks: host factorisations side by side, as in init)
+    std::atomic<size_t> next(0);
+    auto worker = [&] {
+      for (;;) {
+        const size_t i = next.fetch_add(1);
+        if (i >= nh) break;
+        attach(i);
+      }
+    };
+    std::vector<std::thread> th;
+    for (size_t t = 1; t < std::min<size_t>(nh, 8); ++t) th.emplace_back(worker);
+    worker();
+    for (std::thread &t : th) t.join();
+  } else {
+    for (size_t i = 0; i < nh; ++i) attach(i);
+  }
+  for (size_t i = 0; i < nh; ++i)
+    if (rcs[i]) {
+      set_last_error(errs[i]);
+      return rcs[i];
+    }
+  central_th.join();
+  if (!central_ok) {
+    set_last_error("rbcd robust: the weights give a matrix entry outside the session's pattern");
+    return DCORA_ERR_BAD_ARG;
+  }
+  if (central) {
+    DCORA_HIP(hipMemcpyAsync(central->Q.v.p, Qcs.v.data(), sizeof(double) * Qcs.v.size(), hipMemcpyHostToDevice, st));
+    if (central->has_bsr)
+      DCORA_HIP(hipMemcpyAsync(central->Qb.bv.p, cbsr.bv.data(), sizeof(double) * cbsr.bv.size(), hipMemcpyHostToDevice, st));
+  }
+  DCORA_HIP(hipStreamSynchronize(st));
+  return DCORA_OK;
+}
+
+// Agent::initializeAcceleration for every agent (ref src/Agent.cpp:1178-1187): XPrev = V = Y = X, gamma = alpha = 0,
+// no staged Nesterov step; unlike set_acceleration the iteration counter goes on (mIterationNumber)
+int RbcdSession::initialize_acceleration() {
+  staged_selected_ = -1;
+  const size_t B = sizeof(double) * (size_t)r * (d + 1) * n;
+  DCORA_HIP(hipMemcpyAsync(Vg.p, Xg.p, B, hipMemcpyDeviceToDevice, st));
+  DCORA_HIP(hipMemcpyAsync(Yg.p, Xg.p, B, hipMemcpyDeviceToDevice, st));
+  DCORA_HIP(hipMemcpyAsync(XPrevg.p, Xg.p, B, hipMemcpyDeviceToDevice, st));
+  DCORA_HIP(hipStreamSynchronize(st));
+  gamma = alpha = 0;
+  seq_advanced_ = false;
+  pending_reset_ = false;
+  for (AgentDev &a : agents) a.v_feasible = false;
+  return DCORA_OK;
+}
+
+// Agent::updateMeasurementWeights for every agent (ref src/Agent.cpp:1397-1441): the weights of the current iterate
+// (k_robust_weights reads the mirror Xg), the data matrices rebuilt, RobustCost::update, optionally X back to the
+// last set_X (robustOptNumResets), acceleration re-initialised
+int RbcdSession::update_weights(bool reset_to_initial, int counts[3]) {
+  RobustSession &rs = *robust;
+  DCORA_HIP(hipSetDevice(opt.device));
+  for (const AgentDev &a : agents)
+    if (a.own) DCORA_HIP(hipStreamSynchronize(a.own));
+  const size_t m = rs.meas.size();
+  std::vector<double> w(m);
+  double cnt[3] = {0, 0, 0};
+  if (m) {
+    launch_robust_weights(st, rs.edges, r, Xg.p, rs.params, rs.cost.mu());
+    DCORA_HIP(hipGetLastError());
+    DCORA_HIP(hipMemcpyAsync(w.data(), rs.edges.w.p, sizeof(double) * m, hipMemcpyDeviceToHost, st));
+    DCORA_HIP(hipMemcpyAsync(cnt, rs.edges.counts.p, sizeof(cnt), hipMemcpyDeviceToHost, st));
+  }
+  DCORA_HIP(hipStreamSynchronize(st));
+  std::vector<PoseMeas> meas = rs.meas;
+  for (size_t e = 0; e < m; ++e) meas[e].weight = w[e];
+  const int rc = rebuild_values(meas);
+  if (rc) {  // (the device's weights back to the ones the matrices still hold)
+    for (size_t e = 0; e < m; ++e) w[e] = rs.meas[e].weight;
+    if (m) DCORA_HIP(hipMemcpy(rs.edges.w.p, w.data(), sizeof(double) * m, hipMemcpyHostToDevice));
+    return rc;
+  }
+  rs.meas.swap(meas);
+  rs.cost.update();
+  rs.updates++;
+  if (reset_to_initial)
+    DCORA_HIP(hipMemcpyAsync(Xg.p, rs.X_initial.p, sizeof(double) * (size_t)r * (d + 1) * n, hipMemcpyDeviceToDevice, st));
+  const int rc2 = initialize_acceleration();
+  if (rc2) return rc2;
+  if (counts)
+    for (int c = 0; c < 3; ++c) counts[c] = (int)cnt[c];
+  return DCORA_OK;
+}
+
+int RbcdSession::set_weights(const double *w) {
+  RobustSession &rs = *robust;
+  const size_t m = rs.meas.size();
+  for (size_t e = 0; e < m; ++e)
+    if (!std::isfinite(w[e]) || w[e] < 0) {
+      set_last_error("rbcd robust: weights must be finite and >= 0");
+      return DCORA_ERR_BAD_ARG;
+    }
+  std::vector<PoseMeas> meas = rs.meas;
+  for (size_t e = 0; e < m; ++e) meas[e].weight = w[e];
+  const int rc = rebuild_values(meas);
+  if (rc) return rc;
+  rs.meas.swap(meas);
+  if (m) DCORA_HIP(hipMemcpy(rs.edges.w.p, w, sizeof(double) * m, hipMemcpyHostToDevice));
+  return initialize_acceleration();
+}
+
+int RbcdSession::get_weights(double *w) const {
+  for (size_t e = 0; e < robust->meas.size(); ++e) w[e] = robust->meas[e].weight;
   return DCORA_OK;
 }
 

@@ -1,9 +1,21 @@
 // Robust pose-graph optimisation drivers (robust.hip)
 #pragma once
 #include "../../include/dcora_hip.h"
+#include "device_problem.h"
 #include "host_graph.h"
 
 namespace dcora {
+// the measurement table of a robust RBCD session (rbcd.h), uploaded once at creation, and the weights in dataset order
+struct RobustEdges {
+  int m = 0, d = 0;
+  DevBuf<int> dp1, dp2, dupd;  // dupd: the weight is rewritten by the update (a loop closure whose weight is not fixed)
+  DevBuf<double> dR, dt, dk, dta, w, partials, counts;
+  int upload(const HostDataset &ds, const std::vector<char> &update);
+};
+// w[e] = RobustCost::weight(sqrt(error_e(X))) with RobustCost's mu for the edges flagged dupd; counts[3] = accepted,
+// rejected, undecided among them (per-block partials summed by one more launch: deterministic, no atomics)
+void launch_robust_weights(hipStream_t st, const RobustEdges &T, int r, const double *X, const dcora_robust_params &p,
+                           double mu);
 int measurement_errors(const HostDataset &ds, int r, const double *X, double *out, int device);
 int solve_pgo(const HostDataset &ds, const dcora_ropt_params &prm, const double *T0, double *Tout, int device,
               dcora_ropt_result *res);

@@ -10,6 +10,7 @@
 #include "device_problem.h"
 #include "host_graph.h"
 #include "host_robust.h"
+#include "robust.h"
 
 namespace dcora {
 
@@ -19,12 +20,10 @@ struct EdgeDev {
   const int *p1, *p2;
   const double *R, *t, *kappa, *tau;  // R: d*d per edge (column-major), t: d per edge
 };
-// one thread per edge: kappa |Y1 R - Y2|^2 + tau |p2 - p1 - Y1 t|^2 with Y r x d, p r-vectors (SE ordering)
+// kappa |Y1 R - Y2|^2 + tau |p2 - p1 - Y1 t|^2 of edge e with Y r x d, p r-vectors (SE ordering): one expression for
+// both kernels below, so the session's weight update sees the residuals dcora_measurement_errors reports, bit for bit
 template <int D>
-__global__ __launch_bounds__(kBlock) void k_measurement_errors(int r, int m, EdgeDev E, const double *__restrict__ X,
-                                                               double *__restrict__ out) {
-  const int e = blockIdx.x * kBlock + threadIdx.x;
-  if (e >= m) return;
+__device__ __forceinline__ double edge_error(int r, int e, const EdgeDev &E, const double *__restrict__ X) {
   constexpr int DH = D + 1;
   const double *X1 = X + (size_t)E.p1[e] * DH * r, *X2 = X + (size_t)E.p2[e] * DH * r;
   const double *Re = E.R + (size_t)e * D * D, *te = E.t + (size_t)e * D;
@@ -46,7 +45,67 @@ __global__ __launch_bounds__(kBlock) void k_measurement_errors(int r, int m, Edg
     for (int a = 0; a < D; ++a) s -= y1[a] * te[a];
     tr += s * s;
   }
-  out[e] = E.kappa[e] * rot + E.tau[e] * tr;
+  return E.kappa[e] * rot + E.tau[e] * tr;
+}
+
+// one thread per edge
+template <int D>
+__global__ __launch_bounds__(kBlock) void k_measurement_errors(int r, int m, EdgeDev E, const double *__restrict__ X,
+                                                               double *__restrict__ out) {
+  const int e = blockIdx.x * kBlock + threadIdx.x;
+  if (e >= m) return;
+  out[e] = edge_error<D>(r, e, E, X);
+}
+
+// RobustCost::weight (host_robust.cpp, ref src/DCORA_robust.cpp:56-100) with the same operations in the same order
+__device__ double robust_weight(const dcora_robust_params &p, double mu, double r) {
+  switch (p.cost_type) {
+    case DCORA_ROBUST_L2: return 1;
+    case DCORA_ROBUST_L1: return 1 / r;
+    case DCORA_ROBUST_HUBER: return r < p.HuberThreshold ? 1 : p.HuberThreshold / r;
+    case DCORA_ROBUST_TLS: return r < p.TLSThreshold ? 1 : 0;
+    case DCORA_ROBUST_GM: {
+      const double a = fma(r, r, 1.0);  // (the host build contracts 1 + r * r into this FMA)
+      return 1 / (a * a);
+    }
+    case DCORA_ROBUST_GNC_TLS: {
+      const double rSq = r * r, bSq = p.GNCBarc * p.GNCBarc;
+      const double ub = (mu + 1) / mu * bSq, lb = mu / (mu + 1) * bSq;
+      if (rSq >= ub) return 0;
+      if (rSq <= lb) return 1;
+      return sqrt(bSq * mu * (mu + 1) / rSq) - mu;
+    }
+  }
+  return 1;
+}
+
+// Agent::updateMeasurementWeights on the session's iterate (ref src/Agent.cpp:1397-1413): one thread per edge, the
+// edges flagged upd (loop closures whose weight is not fixed) get RobustCost::weight(sqrt(error)); the rest keep theirs.
+// Per-block partials of {accepted (w > 1 - 1e-8), rejected (w < 1e-8), undecided} among the updated edges.
+template <int D>
+__global__ __launch_bounds__(kBlock) void k_robust_weights(int r, int m, EdgeDev E, const int *__restrict__ upd,
+                                                           const double *__restrict__ X, dcora_robust_params p,
+                                                           double mu, double *__restrict__ w,
+                                                           double *__restrict__ partials) {
+  __shared__ double s_red[16];
+  const int e = blockIdx.x * kBlock + threadIdx.x;
+  double acc = 0, rej = 0, und = 0;
+  if (e < m && upd[e]) {
+    const double we = robust_weight(p, mu, sqrt(edge_error<D>(r, e, E, X)));
+    w[e] = we;
+    const double w_tol = 1e-8;
+    acc = we > 1 - w_tol ? 1 : 0;
+    rej = we < w_tol ? 1 : 0;
+    und = 1 - acc - rej;
+  }
+  acc = block_sum(acc, s_red);
+  rej = block_sum(rej, s_red);
+  und = block_sum(und, s_red);
+  if (threadIdx.x == 0) {
+    partials[(size_t)blockIdx.x * 3] = acc;
+    partials[(size_t)blockIdx.x * 3 + 1] = rej;
+    partials[(size_t)blockIdx.x * 3 + 2] = und;
+  }
 }
 
 int no_device() {
@@ -59,6 +118,59 @@ int no_device() {
 }
 
 }  // namespace
+
+int RobustEdges::upload(const HostDataset &ds, const std::vector<char> &update) {
+  m = (int)ds.meas.size();
+  d = ds.d;
+  if (m == 0) return DCORA_OK;
+  std::vector<int> p1((size_t)m), p2((size_t)m), up((size_t)m);
+  std::vector<double> R((size_t)m * d * d), t((size_t)m * d), ka((size_t)m), ta((size_t)m), wh((size_t)m);
+  for (int e = 0; e < m; ++e) {
+    const PoseMeas &q = ds.meas[e];
+    p1[e] = q.p1;
+    p2[e] = q.p2;
+    for (int i = 0; i < d * d; ++i) R[(size_t)e * d * d + i] = q.R[i];
+    for (int i = 0; i < d; ++i) t[(size_t)e * d + i] = q.t[i];
+    ka[e] = q.kappa;
+    ta[e] = q.tau;
+    wh[e] = q.weight;
+    up[e] = update[e] ? 1 : 0;
+  }
+  const int grid = (m + kBlock - 1) / kBlock;
+  DCORA_HIP(dp1.alloc(m));
+  DCORA_HIP(dp2.alloc(m));
+  DCORA_HIP(dupd.alloc(m));
+  DCORA_HIP(dR.alloc(R.size()));
+  DCORA_HIP(dt.alloc(t.size()));
+  DCORA_HIP(dk.alloc(m));
+  DCORA_HIP(dta.alloc(m));
+  DCORA_HIP(w.alloc(m));
+  DCORA_HIP(partials.alloc((size_t)grid * 3));
+  DCORA_HIP(counts.alloc(3));
+  DCORA_HIP(hipMemcpy(dp1.p, p1.data(), sizeof(int) * m, hipMemcpyHostToDevice));
+  DCORA_HIP(hipMemcpy(dp2.p, p2.data(), sizeof(int) * m, hipMemcpyHostToDevice));
+  DCORA_HIP(hipMemcpy(dupd.p, up.data(), sizeof(int) * m, hipMemcpyHostToDevice));
+  DCORA_HIP(hipMemcpy(dR.p, R.data(), sizeof(double) * R.size(), hipMemcpyHostToDevice));
+  DCORA_HIP(hipMemcpy(dt.p, t.data(), sizeof(double) * t.size(), hipMemcpyHostToDevice));
+  DCORA_HIP(hipMemcpy(dk.p, ka.data(), sizeof(double) * m, hipMemcpyHostToDevice));
+  DCORA_HIP(hipMemcpy(dta.p, ta.data(), sizeof(double) * m, hipMemcpyHostToDevice));
+  DCORA_HIP(hipMemcpy(w.p, wh.data(), sizeof(double) * m, hipMemcpyHostToDevice));
+  return DCORA_OK;
+}
+
+void launch_robust_weights(hipStream_t st, const RobustEdges &T, int r, const double *X, const dcora_robust_params &p,
+                           double mu) {
+  if (T.m == 0) return;
+  const EdgeDev E{T.dp1.p, T.dp2.p, T.dR.p, T.dt.p, T.dk.p, T.dta.p};
+  const int grid = (T.m + kBlock - 1) / kBlock;
+  if (T.d == 3)
+    hipLaunchKernelGGL(k_robust_weights<3>, dim3(grid), dim3(kBlock), 0, st, r, T.m, E, T.dupd.p, X, p, mu, T.w.p,
+                       T.partials.p);
+  else
+    hipLaunchKernelGGL(k_robust_weights<2>, dim3(grid), dim3(kBlock), 0, st, r, T.m, E, T.dupd.p, X, p, mu, T.w.p,
+                       T.partials.p);
+  launch_sum_partials(st, T.partials.p, grid, 3, 3, T.counts.p);
+}
 
 // X: r x (d+1) n host (SE ordering, r >= d); out: one squared error per measurement (weights not applied)
 int measurement_errors(const HostDataset &ds, int r, const double *X, double *out, int device) {

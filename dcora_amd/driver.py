@@ -144,6 +144,40 @@ def multi_robot_gnc_example(ds, X0, num_robots=5, r=5, robust=None, num_weight_u
                       "gradnorm": float(out["gradnorm"][-1])}}
 
 
+def multi_robot_gnc_session(ds, X0, num_robots=5, r=5, robust=None, num_weight_updates=10, inner_iters=30,
+                            rgrad_tol=0.1, max_final_iters=1000, acceleration=True, params=None, fixed=None,
+                            device=0):
+    """multi_robot_gnc_example's flow (same arguments, same outputs) in ONE session, as the reference's agents run it
+    (ref src/Agent.cpp:1280-1441): the session is created robust (weight 1 on every loop closure that is not fixed),
+    and each round's updateMeasurementWeights runs in place -- residuals and weights on the device from the session's
+    iterate, data matrices and preconditioners rebuilt, acceleration re-initialised, the iterate kept.
+
+    ds.vals[:, -1] (the weights) is updated in place.  Returns X, weights, per-round records."""
+    from . import robust as rb
+    robust = robust or rb.RobustCostParameters("GNC_TLS")
+    lc = loop_closure_mask(ds, num_robots)
+    if fixed is not None:
+        lc &= ~np.asarray(fixed, bool)
+    rounds = []
+    s = RbcdSession(ds, num_robots=num_robots, r=r, acceleration=acceleration, params=params, device=device,
+                    robust=robust, fixed_weight=fixed)
+    try:
+        s.set_X(np.asarray(X0, dtype=np.float64))
+        for _ in range(num_weight_updates):
+            out = s.run(max_iters=inner_iters, rgrad_tol=rgrad_tol)
+            c = s.update_weights()
+            rounds.append({"iterations": int(out["iters"]), "cost_2f": float(out["cost"][-1]),
+                           "accepted": c["accepted"], "rejected": c["rejected"]})
+        out = s.run(max_iters=max_final_iters, rgrad_tol=rgrad_tol)
+        X, w = s.get_X(), s.get_weights()
+    finally:
+        s.close()
+    ds.vals[:, -1] = w
+    return {"X": X, "weights": w.copy(), "loop_closures": lc, "rounds": rounds,
+            "final": {"iterations": int(out["iters"]), "cost_2f": float(out["cost"][-1]),
+                      "gradnorm": float(out["gradnorm"][-1])}}
+
+
 def multi_robot_raslam_example(ra, X0, r_min=None, r_max=100, max_iters=1000, rgrad_tol=0.1, min_eig_tol=1e-3,
                                gradient_tolerance=1e-4, preconditioned_gradient_tolerance=1e-4, acceleration=True,
                                params=None, device=0):

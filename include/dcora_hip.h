@@ -497,6 +497,28 @@ typedef struct {
   double HuberThreshold, TLSThreshold;
 } dcora_robust_params;
 void dcora_robust_params_default(dcora_robust_params *p);
+/* --- robust sessions: the agents' GNC loop inside one live session (world_size 1, pose-graph sessions) --- */
+/* dcora_rbcd_create with Agent::initializeRobustOptimization (ref src/Agent.cpp:1332-1346): weight 1 on every loop
+ * closure -- every measurement but odometry (p2 == p1 + 1 inside one agent of the contiguous partition) -- whose
+ * fixed_weight flag (m ints, may be NULL) is 0.  The matrices' patterns are those of these weights, the largest any
+ * later weights can give.  world_size > 1: DCORA_ERR_UNSUPPORTED. */
+int dcora_rbcd_create_robust(dcora_dataset_t ds, const dcora_rbcd_options *opt, const dcora_robust_params *robust,
+                             const int *fixed_weight, dcora_rbcd_t *out);
+/* Agent::updateMeasurementWeights (ref src/Agent.cpp:1397-1441): weight = RobustCost::weight(residual) of every
+ * non-fixed loop closure on the current iterate (on the device), Q_bb / coupling / central Q / preconditioners rebuilt
+ * in place, RobustCost::update(), reset_to_initial != 0: X = the last dcora_rbcd_set_X (robustOptNumResets), then
+ * initializeAcceleration (XPrev = V = Y = X, gamma = alpha = 0; the iteration count goes on).  counts (may be NULL):
+ * accepted (w > 1 - 1e-8), rejected (w < 1e-8), undecided among the updated closures.  The next three entries and this
+ * one return DCORA_ERR_BAD_ARG on a session not created by dcora_rbcd_create_robust, DCORA_ERR_UNSUPPORTED when
+ * world_size > 1. */
+int dcora_rbcd_update_weights(dcora_rbcd_t s, int reset_to_initial, int counts[3]);
+/* all m weights in dataset order (Agent::setMeasurementWeight of every measurement, ref src/Agent.cpp:1443-1454), then
+ * initializeAcceleration.  A weight that is negative or not finite, or a zero weight of creation made nonzero: the call
+ * is refused (DCORA_ERR_BAD_ARG) and the session left as it was. */
+int dcora_rbcd_set_weights(dcora_rbcd_t s, const double *w);
+int dcora_rbcd_get_weights(dcora_rbcd_t s, double *w);
+/* RobustCost's current mu (GNC-TLS) and the number of dcora_rbcd_update_weights calls so far (either may be NULL) */
+int dcora_rbcd_robust_info(dcora_rbcd_t s, double *mu, int *updates);
 /* RobustCost::weight(r) for n residuals after num_updates calls of RobustCost::update() (ref src/DCORA_robust.cpp:56-136) */
 int dcora_robust_weights(const dcora_robust_params *p, int num_updates, int n, const double *r, double *w);
 /* chi2inv (ref src/DCORA_utils.cpp:2103-2106), RobustCost::computeErrorThresholdAtQuantile (ref src/DCORA_robust.cpp:138-148) */
