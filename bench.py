@@ -16,13 +16,16 @@ rank a // ceil(R / N).  The data path between ranks is the library's neighbour e
 stores into IPC-mapped halo buffers over xGMI, flag words and the 2R evaluation scalars in a shared host segment);
 torch.distributed (backend nccl = RCCL) only brackets the timed region (barrier, MAX over ranks).
 
-Prints ONE JSON line on rank 0 (see the task contract) with two extra objects:
+Prints ONE JSON line on rank 0 (see the task contract).  `value` is the MEDIAN of REPLAYS replays of the driver's window
+(value_samples lists them).  A plain run does only what that line needs: set up, warm up, time the window, dump (below)
+and print.  `--full` adds every side measurement after the timed window, among them:
+  sustained    -- the same trajectory continued for SUSTAINED_STEPS more iterations
   roofline     -- the dominant kernel of the timed loop (k_fused_pc: step + vector updates + the dense preconditioner
                   product + projection of a tCG iteration in one launch) timed live with HIP events
   cpu_baseline -- the CPU oracle (oracle/, a port of the reference algorithm) on the same iteration window of the
                   same workload, 1 host thread (the reference ships single-threaded: OpenMP off); r_threads: the same
                   with one host thread per agent (what the reference's asynchronous mode starts)
-`value` is the MEDIAN of REPLAYS replays of the driver's window (value_samples lists them).
+and the other configurations (certified run, tiers, torus3D, the 100k lattice, the strong-scaling series).
 
 `--dump-outputs DIR` writes what the last timed iteration (of the last replay at N = 1) left to its caller -- the whole
 iterate X, 2f, the gradient norms and the next selected agent -- as DIR/<name>.npy, so that two builds run with the same
@@ -202,7 +205,7 @@ def compact_line(full, detail_path="gpurun_out/bench_detail.json", limit=LINE_LI
                       "timed_iterations": _short(cfg.get("timed_iterations"), 80),
                       "window_note": "early iterations are cheaper on both sides (tCG exits early): a --steps 20 "
                                      "--warmup 5 window reads ~1.6x the sustained rate; see sustained and "
-                                     "cpu_baseline.same_window_as_value",
+                                     "cpu_baseline.same_window_as_value (--full)",
                       "final_cost_2f": cfg.get("final_cost_2f"), "speedup_vs_cpu_port": cfg.get("speedup_vs_cpu_port")}
     vs = full.get("value_samples")
     if vs:
@@ -350,27 +353,34 @@ def parse():
     ap.add_argument("--dataset", default="sphere2500")
     ap.add_argument("--robots", type=int, default=5)
     ap.add_argument("--rank-r", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed window, run every side measurement (sustained window, roofline, CPU baseline, "
+                         "the other configurations); the --no-* and --cpu-* options below shape such a run")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-config5", action="store_true", help="skip the 100k-pose side measurement")
     ap.add_argument("--no-config4", action="store_true", help="skip the tiers.pyfg side measurement")
     ap.add_argument("--no-coloured", action="store_true",
                     help="skip the coloured simultaneous-update measurements (agents solving on concurrent host threads): "
-                         "rocprofv3 --kernel-trace of the WHOLE default run dies in its own buffers there (DESIGN.md 5)")
+                         "rocprofv3 --kernel-trace of a WHOLE --full run dies in its own buffers there (DESIGN.md 5)")
     ap.add_argument("--no-config3", action="store_true", help="skip the torus3D 8-agent side measurement")
     ap.add_argument("--headline-only", action="store_true",
-                    help="only the timed loop (for a kernel trace of exactly that loop): no side measurements")
+                    help="what a run without --full does: the timed loop alone (kept for the callers that name it)")
     ap.add_argument("--scaling-only", action="store_true",
-                    help="the timed loop + the strong-scaling series (scaling_100k_lattice) and nothing else: the "
-                         "rehearsal of the driver's N > 1 runs (tests/test_bench_gpu.py)")
+                    help="implies --full: the timed loop + the strong-scaling series (scaling_100k_lattice) and nothing "
+                         "else: the rehearsal of the driver's N > 1 runs (tests/test_bench_gpu.py)")
     ap.add_argument("--cpu-steps", type=int, default=0, help="oracle iterations for cpu_baseline (0 = auto)")
     ap.add_argument("--cpu-c4-staircase", action="store_true",
-                    help="also run the CPU port through the whole tiers.pyfg staircase (minutes)")
+                    help="implies --full: also run the CPU port through the whole tiers.pyfg staircase (minutes)")
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="after the timed steps, write what the last timed step computed (the iterate X, 2f, the "
                          "gradient norms, the next selected agent) as DIR/<name>.npy in float64 (rank 0 writes)")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    # both ask for side measurements, which only a --full run makes
+    args.full = args.full or args.scaling_only or args.cpu_c4_staircase
+    if args.full and args.headline_only:
+        ap.error("--headline-only contradicts --full (or --scaling-only, --cpu-c4-staircase)")
     return args
 
 
@@ -419,7 +429,7 @@ def initial_point(da, ds, r, seed=20250310):
 
 def run_single(args, da, torch, ds, X0):
     """the timed window the driver asks for (iterations warmup+2 .. warmup+1+steps of the trajectory from X0) and,
-    continuing the same trajectory, a sustained window of SUSTAINED_STEPS iterations"""
+    with --full, continuing the same trajectory, a sustained window of SUSTAINED_STEPS iterations"""
     t0 = time.perf_counter()
     s = da.RbcdSession(ds, num_robots=args.robots, r=args.rank_r)
     setup_s = time.perf_counter() - t0
@@ -456,7 +466,7 @@ def run_single(args, da, torch, ds, X0):
     if args.dump_outputs:
         dump_last_step(args.dump_outputs, s.get_X(), c2, gn, bn, selected)
     sustained = None
-    if not args.headline_only:
+    if args.full:
         first = args.warmup + 1 + args.steps
         dts, c2s, gns, _, selected = window(SUSTAINED_STEPS, selected)
         sustained = {"steps": SUSTAINED_STEPS, "first_iteration": first + 1, "value": SUSTAINED_STEPS / dts,
@@ -871,7 +881,7 @@ def agent_block(ds, R, b):
 
 
 def committed_profile(nbytes):
-    """numbers read from files under profiles/ (a rocprofv3 kernel trace of `bench.py --headline-only` and the PMC
+    """numbers read from files under profiles/ (a rocprofv3 kernel trace of a plain `bench.py` run and the PMC
     passes): NOT measured in this run, reported under their own key with their source"""
     import csv
     out = {"note": "read from committed rocprofv3 summaries, not measured in this run"}
@@ -1890,9 +1900,9 @@ def main():
                  "used_for": "barrier + MAX of the timed region only"}
         drv, dt, c2, gn, exch = run_multi(args, da, torch, dist, ds, X0, rank, world)
         group["transport"] = drv.transport
-        coloured = None if (args.headline_only or args.scaling_only) else coloured_sweeps(drv, X0, sweeps=40)
+        coloured = None if (not args.full or args.scaling_only) else coloured_sweeps(drv, X0, sweeps=40)
         drv.close()
-        if not args.headline_only:
+        if args.full:
             c3 = None if (args.no_config3 or args.scaling_only) else config3_multi(da, torch, dist, rank, world)
             c5 = None if (args.no_config5 or args.scaling_only) else config5_multi(da, torch, dist, rank, world)
             strong = None if args.no_config5 else strong_scaling_multi(da, torch, dist, rank, world)
@@ -1900,7 +1910,7 @@ def main():
         dist.destroy_process_group()
     else:
         s, dt, c2, gn, sustained, setup_s = run_single(args, da, torch, ds, X0)
-        coloured = None if (args.headline_only or args.scaling_only or SKIP_COLOURED) else \
+        coloured = None if (not args.full or args.scaling_only or SKIP_COLOURED) else \
             coloured_sweeps(SingleDriver(s), X0, sweeps=40)
     if rank != 0:
         return
@@ -1925,7 +1935,7 @@ def main():
                                        (args.warmup + 2, args.warmup + 1 + args.steps),
                    "window_note": "iterations early in the trajectory are cheaper on BOTH sides (tCG exits early): a short "
                                   "window such as the driver's --steps 20 --warmup 5 reads ~1.6 x the sustained rate; "
-                                  "`sustained` continues the same trajectory for %d more iterations and "
+                                  "with --full, `sustained` continues the same trajectory for %d more iterations and "
                                   "cpu_baseline.same_window_as_value is the CPU port over the same window" % SUSTAINED_STEPS,
                    "final_cost_2f": c2, "final_gradnorm": gn},
     }
@@ -1936,7 +1946,7 @@ def main():
     if group is not None:
         line["process_group"] = group
         line["exchange"] = exch
-    if args.headline_only:
+    if not args.full:
         emit(real_stdout, line)
         return
     if sustained is not None:

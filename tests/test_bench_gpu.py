@@ -26,14 +26,25 @@ def run_bench(extra, env_extra=None, timeout=900):
 
 
 def test_headline_line_of_the_one_gpu_run(tmp_path):
-    line = run_bench(["--steps", "20", "--warmup", "5", "--headline-only", "--dump-outputs", str(tmp_path)])
+    line = run_bench(["--steps", "20", "--warmup", "5", "--dump-outputs", str(tmp_path)])
     assert line["n_gpus"] == 1 and line["steps"] == 20 and line["warmup"] == 5 and line["value"] > 100
+    for key in ("sustained", "roofline", "cpu_baseline", "coloured_rbcd", "scaling_100k_lattice"):
+        assert key not in line, key  # a plain run measures only its window; side measurements need --full
     assert abs(line["value"] * line["ms_per_step"] - 1e3) < 1.0
     assert line["config"]["workload"].startswith("sphere2500") and line["vs_baseline"] is None
     with open(os.path.join(ROOT, "gpurun_out", "bench_detail.json")) as fh:
         detail = json.load(fh)
     assert abs(detail["value"] - line["value"]) <= 1e-5 * line["value"]
     check_last_step_dump(tmp_path, detail)
+
+
+def test_full_run_adds_the_side_measurements():
+    line = run_bench(["--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline", "--no-config3", "--no-config4",
+                      "--no-config5", "--no-coloured"])
+    assert line["steps"] == 20 and line["value"] > 100
+    assert line["sustained"]["steps"] == 300 and line["sustained"]["value"] > 100
+    assert line["roofline"]["unit"] == "GB/s" and line["roofline"]["achieved"] > 0
+    assert "value" in line["ms_to_certified_optimum"]
 
 
 def check_last_step_dump(path, detail):
@@ -59,8 +70,7 @@ def test_two_rank_dump_is_the_whole_last_step(tmp_path, transport):
     env = {"DCORA_DIST_BACKEND": "gloo"}
     if transport == "collectives":
         env["DCORA_BENCH_COLLECTIVES"] = "1"
-    line = run_bench(["--gpus", "2", "--steps", "6", "--warmup", "2", "--headline-only", "--dump-outputs",
-                      str(tmp_path)], env)
+    line = run_bench(["--gpus", "2", "--steps", "6", "--warmup", "2", "--dump-outputs", str(tmp_path)], env)
     assert line["n_gpus"] == 2 and line["steps"] == 6
     fallback = line["process_group"]["transport"] == "torch.distributed collectives (fallback)"
     assert fallback == (transport == "collectives"), line["process_group"]
@@ -70,7 +80,7 @@ def test_two_rank_dump_is_the_whole_last_step(tmp_path, transport):
 
 
 def test_two_rank_rehearsal_prints_the_scaling_series():
-    line = run_bench(["--gpus", "2", "--steps", "10", "--warmup", "3", "--scaling-only"],
+    line = run_bench(["--gpus", "2", "--steps", "10", "--warmup", "3", "--full", "--scaling-only"],
                      {"DCORA_DIST_BACKEND": "gloo"})
     assert line["n_gpus"] == 2 and line["value"] > 50
     sc = line["scaling_100k_lattice"]

@@ -143,3 +143,15 @@ def test_dump_outputs_writes_float64_arrays_within_the_size_limit(tmp_path):
     assert np.array_equal(np.load(tmp_path / "a" / "X_sample.npy"), X.ravel()[idx.astype(np.int64)])
     for f in files:
         assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
+
+
+def test_side_measurements_need_full(monkeypatch):
+    def parse(*flags):
+        monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "20", "--warmup", "5"] + list(flags))
+        return bench.parse()
+    assert parse().full is False and parse("--headline-only").full is False
+    assert parse("--full", "--no-config5").full is True
+    assert parse("--full", "--scaling-only").scaling_only is True
+    assert parse("--scaling-only").full is True and parse("--cpu-c4-staircase").full is True
+    with pytest.raises(SystemExit):
+        parse("--full", "--headline-only")
