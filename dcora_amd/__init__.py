@@ -420,6 +420,9 @@ def is_psd(S, block=1):
 def cert_prepare(Q, d, n, l=0, b=0, block=1, device=0, layout=0):
     """analysis of the PSD test of the dual certificate S = Q - Lambda ahead of time (dcora_cert_prepare): its pattern
     is known from Q's; meant for another host thread while the agents iterate"""
+    k = (d + 1) * n + l + b
+    if Q.n != k:  # the library cannot see the length of rp: it reads k + 1 entries
+        raise ValueError("Q is %d x %d, expected %d" % (Q.n, Q.n, k))
     dims = Dims(1, d, n, l, b, layout)
     check(capi.lib().dcora_cert_prepare(C.byref(dims), Q.rp, Q.ci, block, device))
 

@@ -46,6 +46,8 @@ class DeviceLanczos {
 std::vector<double> min_eig_second_start(const HostCsr &S, uint64_t seed);
 int device_min_eig(const HostCsr &S, int maxit, double min_eig_tol, int ncv, uint64_t seed, int device,
                    LanczosResult *out);
+// (row, col) of Lambda's entries, in the order of launch_lambda_blocks's values (cert.hip)
+void lambda_entries(const ManiDesc &m, std::vector<int> &I, std::vector<int> &J);
 int device_dual_certificate(const dcora_dims &dims, const double *Xh, const HostCsr &Q, int device, HostCsr *S);
 int host_is_psd(const HostCsr &S, int block, bool *psd);
 int device_fast_verification(const HostCsr &S, double eta, int block, int device, bool *psd, double *theta,

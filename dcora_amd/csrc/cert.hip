@@ -506,6 +506,24 @@ int device_min_eig(const HostCsr &S, int maxit, double min_eig_tol, int ncv, uin
 }
 
 // ref src/DCORA_utils.cpp:1898-1982
+// The entries of Lambda(X) in S = Q - Lambda (ref src/DCORA_utils.cpp:1898-1982): the d x d block of every rotation,
+// then the diagonal entry of every unit sphere, appended to I (rows) and J (columns).  The q-th entry appended is the
+// q-th value launch_lambda_blocks writes (rotation blocks column-major).
+void lambda_entries(const ManiDesc &m, std::vector<int> &I, std::vector<int> &J) {
+  for (int i = 0; i < m.n; ++i) {
+    const int c = m.rot_col(i);
+    for (int b = 0; b < m.d; ++b)
+      for (int a = 0; a < m.d; ++a) {
+        I.push_back(c + a);
+        J.push_back(c + b);
+      }
+  }
+  for (int i = 0; i < m.l; ++i) {
+    I.push_back(m.sphere_col(i));
+    J.push_back(m.sphere_col(i));
+  }
+}
+
 int device_dual_certificate(const dcora_dims &dims, const double *Xh, const HostCsr &Q, int device, HostCsr *S) {
   if (dims.r < 1 || dims.r > 16 || (dims.d != 2 && dims.d != 3) || dims.n < 0 || dims.l < 0 || dims.b < 0) {
     set_last_error("bad dims (need 1 <= r <= 16, d in {2,3})");
@@ -598,25 +616,19 @@ int device_dual_certificate(const dcora_dims &dims, const double *Xh, const Host
   }
   // S = Q - Lambda.  Lambda is block diagonal on entries that Q's own pattern holds (the d x d rotation blocks
   // and the unit-sphere diagonal): subtract in place on a copy of Q; fall back to a merge when an entry is absent.
+  std::vector<int> LI, LJ;
+  lambda_entries(m, LI, LJ);
   {
     HostCsr T = Q;
     bool all_found = true;
-    auto sub = [&](int i, int j, double val) {
-      const int *lo = T.ci.data() + T.rp[i], *hi = T.ci.data() + T.rp[i + 1];
-      const int *it = std::lower_bound(lo, hi, j);
-      if (it == hi || *it != j) {
+    for (size_t q = 0; q < LI.size() && all_found; ++q) {
+      const int *lo = T.ci.data() + T.rp[LI[q]], *hi = T.ci.data() + T.rp[LI[q] + 1];
+      const int *it = std::lower_bound(lo, hi, LJ[q]);
+      if (it == hi || *it != LJ[q])
         all_found = false;
-        return;
-      }
-      T.v[it - T.ci.data()] -= val;
-    };
-    const int d = m.d;
-    for (int i = 0; i < m.n && all_found; ++i) {
-      const int c = m.rot_col(i);
-      for (int a = 0; a < d; ++a)
-        for (int b = 0; b < d; ++b) sub(c + a, c + b, L[(size_t)i * d * d + a + b * d]);
+      else
+        T.v[it - T.ci.data()] -= L[q];
     }
-    for (int i = 0; i < m.l && all_found; ++i) sub(m.sphere_col(i), m.sphere_col(i), L[(size_t)m.n * d * d + i]);
     if (all_found) {
       *S = std::move(T);
       return DCORA_OK;
@@ -633,22 +645,9 @@ int device_dual_certificate(const dcora_dims &dims, const double *Xh, const Host
       J.push_back(Q.ci[p]);
       V.push_back(Q.v[p]);
     }
-  const int d = m.d;
-  for (int i = 0; i < m.n; ++i) {
-    const int c = m.rot_col(i);
-    for (int a = 0; a < d; ++a)
-      for (int b = 0; b < d; ++b) {
-        I.push_back(c + a);
-        J.push_back(c + b);
-        V.push_back(-L[(size_t)i * d * d + a + b * d]);
-      }
-  }
-  for (int i = 0; i < m.l; ++i) {
-    const int c = m.sphere_col(i);
-    I.push_back(c);
-    J.push_back(c);
-    V.push_back(-L[(size_t)m.n * d * d + i]);
-  }
+  I.insert(I.end(), LI.begin(), LI.end());
+  J.insert(J.end(), LJ.begin(), LJ.end());
+  for (size_t q = 0; q < LI.size(); ++q) V.push_back(-L[q]);
   *S = csr_from_coo(Q.n, Q.n, I, J, V);
   return DCORA_OK;
 }

@@ -4,6 +4,7 @@
 #include "device_problem.h"
 #include "env.h"
 #include "device_chol.h"
+#include "host_threads.h"
 #include "precond_cache.h"
 
 #include <algorithm>
@@ -14,7 +15,6 @@
 #include <cstring>
 #include <map>
 #include <mutex>
-#include <thread>
 
 namespace dcora {
 
@@ -315,35 +315,33 @@ int precond_prebuild_dense(const std::vector<const HostCsr *> &Qs, double reg, i
     std::vector<double *> outs;
     std::vector<long> nnzL(idx.size(), 0);
     // host work per matrix (the shifted copy; nnz(L) of the SPARSE factor from the pattern, what SURVEY 8(d) prices the
-    // preconditioner by) on threads of its own, beside the device's batch
-    std::vector<std::thread> th;
+    // preconditioner by) on threads of its own (t = 1 .. B), beside the device's batch (t = 0)
     for (size_t q = 0; q < idx.size(); ++q) Ms[q] = csr_shift_diag(*Qs[idx[q]], reg);
-    for (size_t q = 0; q < idx.size(); ++q)
-      th.emplace_back([&, q] {
-        CholSymbolic sym;
-        chol_symbolic(Ms[q], block, &sym);
-        long nz = 0;
-        for (const CholPiece &pc : sym.pieces) nz += (long)pc.c * (pc.c + 1) / 2 + (long)pc.m * pc.c;
-        nnzL[q] = nz;
-      });
-    struct Join {
-      std::vector<std::thread> &t;
-      ~Join() {
-        for (std::thread &x : t)
-          if (x.joinable()) x.join();
-      }
-    } join_guard{th};
-    for (size_t q = 0; q < idx.size(); ++q) {
-      auto buf = std::make_shared<DevBuf<double>>();
-      DCORA_HIP(buf->alloc((size_t)k * ldm + 16));
-      bufs.push_back(buf);
-      outs.push_back(buf->p);
-    }
-    for (const HostCsr &M : Ms) As.push_back(&M);
     std::vector<char> pd;
-    const int rc = device_dense_spd_inverse_batch(As, device, outs, ldm, &pd);
+    int rc = DCORA_OK;
+    auto batch = [&]() -> int {
+      for (size_t q = 0; q < idx.size(); ++q) {
+        auto buf = std::make_shared<DevBuf<double>>();
+        DCORA_HIP(buf->alloc((size_t)k * ldm + 16));
+        bufs.push_back(buf);
+        outs.push_back(buf->p);
+      }
+      for (const HostCsr &M : Ms) As.push_back(&M);
+      return device_dense_spd_inverse_batch(As, device, outs, ldm, &pd);
+    };
+    run_threads((int)idx.size() + 1, [&](int t) {
+      if (t == 0) {
+        rc = batch();
+        return;
+      }
+      const size_t q = (size_t)t - 1;
+      CholSymbolic sym;
+      chol_symbolic(Ms[q], block, &sym);
+      long nz = 0;
+      for (const CholPiece &pc : sym.pieces) nz += (long)pc.c * (pc.c + 1) / 2 + (long)pc.m * pc.c;
+      nnzL[q] = nz;
+    });
     if (rc) return rc;
-    for (std::thread &x : th) x.join();
     const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     for (size_t q = 0; q < idx.size(); ++q) {
       if (!pd[q]) continue;  // not positive definite somewhere in the batch: the problems build (and report) one by one

@@ -5,11 +5,11 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
-#include <thread>
 #include <vector>
 
 #include "device_chol.h"
 #include "env.h"
+#include "host_threads.h"
 
 namespace dcora {
 
@@ -137,11 +137,7 @@ void chol_symbolic(const HostCsr &A, int block, CholSymbolic *out, int top_unkno
       }
     };
     const int nt = n >= 20000 ? std::max(1, std::min(host_cpus_available(), 16)) : 1;
-    std::vector<std::thread> th;
-    for (int t = 1; t < nt; ++t)
-      th.emplace_back(rows_range, (int)((long long)n * t / nt), (int)((long long)n * (t + 1) / nt));
-    rows_range(0, (int)((long long)n / nt));
-    for (auto &t : th) t.join();
+    run_threads(nt, [&](int t) { rows_range((int)((long long)n * t / nt), (int)((long long)n * (t + 1) / nt)); });
   }
   lap("scatter map");
   // schedule: pieces by level (widest first), children by level of the parent and position among the siblings

@@ -9,7 +9,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <numeric>
-#include <thread>
 
 #include "host_partinv_int.h"
 #include "env.h"
@@ -282,11 +281,7 @@ bool build_partitioned_inverse_from(const HostCsr &A, const PiecewiseFactor &F, 
         for (int a = 0; a < m; ++a) w_row(&B[(size_t)a * c], Dinv, c, &p.W[(size_t)a * c]);
       }
     };
-    const int nt = std::max(1, std::min(nthreads, nord));
-    std::vector<std::thread> th;
-    for (int t = 1; t < nt; ++t) th.emplace_back(work);
-    work();
-    for (auto &t : th) t.join();
+    run_threads(std::max(1, std::min(nthreads, nord)), [&](int) { work(); });
   }
   const auto T2 = tnow();
   // ---- schedule and stored weights: the matrix-pipe schedule (host_partinv3.cpp) ----

@@ -2,10 +2,9 @@
 // Set-up time code, host only.
 #pragma once
 #include <algorithm>
-#include <atomic>
-#include <thread>
 #include <vector>
 
+#include "host_threads.h"
 #include "sparse_precond.h"
 
 namespace dcora {
@@ -26,25 +25,6 @@ struct Piece {
 };
 
 inline int pad4(int x) { return (x + 3) & ~3; }
-
-// body(i) for i in [0, n) on up to nthreads threads, dynamic chunks
-template <class F>
-void parallel_for(int n, int nthreads, int chunk, F body) {
-  nthreads = std::max(1, std::min(nthreads, (n + chunk - 1) / chunk));
-  std::atomic<int> next(0);
-  auto work = [&]() {
-    for (;;) {
-      const int i0 = next.fetch_add(chunk);
-      if (i0 >= n) break;
-      const int i1 = std::min(n, i0 + chunk);
-      for (int i = i0; i < i1; ++i) body(i);
-    }
-  };
-  std::vector<std::thread> th;
-  for (int t = 1; t < nthreads; ++t) th.emplace_back(work);
-  work();
-  for (auto &t : th) t.join();
-}
 
 // The stored weights are only RESERVED while a schedule is laid out; writing them -- 0.4 G doubles for the whole 100k
 // lattice -- is done afterwards, on the device where the sources are there, else by all host threads.  A fill is a

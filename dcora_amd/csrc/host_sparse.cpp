@@ -1,6 +1,7 @@
 // Host-side sparse helpers of the product (setup-time only; see host_sparse.h).
 #include "host_sparse.h"
 #include "env.h"
+#include "host_threads.h"
 
 #include <sched.h>
 
@@ -526,6 +527,19 @@ void prefill_splits(const NDGraph &G, const std::vector<int> &all, int leaf_node
         queue.pop_front();
         ++active;
       }
+      // a worker that throws gives its share back first: the others wait for active == 0 and would wait forever
+      struct Release {
+        std::mutex &mu;
+        std::condition_variable &cv;
+        int &active;
+        ~Release() {
+          {
+            std::lock_guard<std::mutex> lk(mu);
+            --active;
+          }
+          cv.notify_all();
+        }
+      } release{mu, cv, active};
       const std::vector<int> &cur = it.nodes;
       int how = 2;
       const bool leaf = (int)cur.size() <= leaf_nodes ||
@@ -538,25 +552,18 @@ void prefill_splits(const NDGraph &G, const std::vector<int> &all, int leaf_node
         how = split_component(G, cur, 1, comp_id, level, lid, order, sep, left, right);
         for (int u : cur) comp_id[(size_t)u] = -1;
       }
-      {
-        std::unique_lock<std::mutex> lk(mu);
-        if (!leaf && !cur.empty()) {
-          memo->map[SplitMemo::key(cur)].push_back(SplitMemo::Entry{cur, sep, left, right, how});
-          if (how == 0 || how == 1) {
-            const int d2 = how == 0 ? it.dep + 1 : it.dep;
-            queue.push_back(Item{std::move(left), d2});
-            queue.push_back(Item{std::move(right), d2});
-          }
+      if (!leaf && !cur.empty()) {
+        std::lock_guard<std::mutex> lk(mu);
+        memo->map[SplitMemo::key(cur)].push_back(SplitMemo::Entry{cur, sep, left, right, how});
+        if (how == 0 || how == 1) {
+          const int d2 = how == 0 ? it.dep + 1 : it.dep;
+          queue.push_back(Item{std::move(left), d2});
+          queue.push_back(Item{std::move(right), d2});
         }
-        --active;
       }
-      cv.notify_all();
     }
   };
-  std::vector<std::thread> pool;
-  for (int t = 1; t < nthreads; ++t) pool.emplace_back(worker);
-  worker();
-  for (std::thread &t : pool) t.join();
+  run_threads(nthreads, [&](int) { worker(); });
 }
 
 void nd_recurse(const NDGraph &G, std::vector<int> nodes, std::vector<int> &comp_id, int &next_cid,
@@ -1039,11 +1046,7 @@ bool SparseChol::factor(const HostCsr &A, int block, int top_unknowns) {
           }
       }
     };
-    const int nt = std::min<int>(nthreads, (int)tasks.size());
-    std::vector<std::thread> th;
-    for (int t = 1; t < nt; ++t) th.emplace_back(worker);
-    worker();
-    for (auto &t : th) t.join();
+    run_threads(std::min<int>(nthreads, (int)tasks.size()), [&](int) { worker(); });
     if (failed.load()) return false;
     // the separators above the tasks, deepest wave first; the separators of one wave are independent
     for (int dep = (int)waves.size() - 1; dep >= 1; --dep) {
@@ -1064,11 +1067,7 @@ bool SparseChol::factor(const HostCsr &A, int block, int top_unknowns) {
             }
         }
       };
-      const int wt = std::min<int>(nthreads, (int)wv.size());
-      std::vector<std::thread> wth;
-      for (int t = 1; t < wt; ++t) wth.emplace_back(wworker);
-      wworker();
-      for (auto &t : wth) t.join();
+      run_threads(std::min<int>(nthreads, (int)wv.size()), [&](int) { wworker(); });
       if (failed.load()) return false;
     }
   }
@@ -1135,10 +1134,7 @@ void SparseChol::dense_inverse(double *out, size_t ld, int nthreads) const {
       }
     }
   };
-  std::vector<std::thread> th;
-  for (int t = 1; t < nthreads; ++t) th.emplace_back(work, t);
-  work(0);
-  for (auto &t : th) t.join();
+  run_threads(nthreads, work);
 }
 
 }  // namespace dcora

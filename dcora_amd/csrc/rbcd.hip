@@ -1,6 +1,7 @@
 // RBCD++ session on the device (see rbcd.h).
 #include "rbcd.h"
 #include "env.h"
+#include "host_threads.h"
 
 #include <algorithm>
 #include <atomic>
@@ -9,7 +10,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <set>
-#include <thread>
 
 namespace dcora {
 
@@ -195,11 +195,10 @@ int RbcdSession::init(const HostDataset &ds, const dcora_rbcd_options &o) {
   std::vector<HostCsr> Qbs((size_t)R);
   if ((long)(n / R + 1) * dh <= kDensePrecondMaxK && hosted_ids.size() > 1) {
     std::vector<const HostCsr *> ptrs;
-    {
-      std::vector<std::thread> th;  // (a matrix takes a millisecond of host work: side by side)
-      for (int b : hosted_ids) th.emplace_back([&, b] { Qbs[(size_t)b] = build_Q_pgo(d, agents[b].n, b, touching[b]); });
-      for (std::thread &t : th) t.join();
-    }
+    run_threads((int)hosted_ids.size(), [&](int t) {  // (a matrix takes a millisecond of host work: side by side)
+      const int b = hosted_ids[(size_t)t];
+      Qbs[(size_t)b] = build_Q_pgo(d, agents[b].n, b, touching[b]);
+    });
     for (int b : hosted_ids) ptrs.push_back(&Qbs[(size_t)b]);
     const int prc = precond_prebuild_dense(ptrs, 0.1, dh, o.device);
     if (prc) return prc;
@@ -260,11 +259,7 @@ int RbcdSession::init(const HostDataset &ds, const dcora_rbcd_options &o) {
           rcs[i] = build_agent(hosted_ids[i], &errs[i]);
         }
       };
-      std::vector<std::thread> th;
-      th.emplace_back(build_central);
-      for (size_t t = 1; t < std::min<size_t>(nh, 8); ++t) th.emplace_back(worker);
-      worker();
-      for (std::thread &t : th) t.join();
+      run_threads((int)std::min<size_t>(nh, 8) + 1, [&](int t) { t == 1 ? build_central() : worker(); });
     } else {
       for (size_t i = 0; i < nh; ++i) rcs[i] = build_agent(hosted_ids[i], &errs[i]);
       build_central();
@@ -452,23 +447,15 @@ int RbcdSession::rebuild_values(const std::vector<PoseMeas> &meas) {
   HostCsr Qcs;
   HostBsr cbsr;
   bool central_ok = true;
-  std::thread central_th([&] {
-    if (!central) return;
-    central_ok = scatter_on_pattern(build_Q_pgo(d, n, 0, global), rs.central_pat, &Qcs);
-    if (central_ok && central->has_bsr) cbsr = bsr_from_csr(Qcs, dh);
-  });
-  struct Join {
-    std::thread &t;
-    ~Join() {
-      if (t.joinable()) t.join();
-    }
-  } join_central{central_th};
   std::vector<HostCsr> Qn(nh), Qs(nh), Cs(nh);
   std::vector<HostBsr> bsr(nh);
   std::vector<char> ok(nh, 0);
-  {
+  std::vector<int> rcs(nh, DCORA_OK);
+  std::vector<std::string> errs(nh);
+  // the agents' matrices, their uploads and preconditioners; the central Q is built beside them
+  auto rebuild_agents = [&]() -> int {
     std::atomic<size_t> next(0);
-    auto worker = [&] {
+    run_threads((int)std::min<size_t>(nh, 8), [&](int) {
       for (;;) {
         const size_t i = next.fetch_add(1);
         if (i >= nh) break;
@@ -478,65 +465,65 @@ int RbcdSession::rebuild_values(const std::vector<PoseMeas> &meas) {
                 scatter_on_pattern(build_coupling_pgo(d, P, b, global), rs.Cpat[(size_t)b], &Cs[i]);
         if (ok[i] && agents[b].prob->has_bsr) bsr[i] = bsr_from_csr(Qs[i], dh);
       }
-    };
-    std::vector<std::thread> th;
-    for (size_t t = 1; t < std::min<size_t>(nh, 8); ++t) th.emplace_back(worker);
-    worker();
-    for (std::thread &t : th) t.join();
-  }
-  for (size_t i = 0; i < nh; ++i)
-    if (!ok[i]) {
-      set_last_error("rbcd robust: the weights give a matrix entry outside the session's pattern");
-      return DCORA_ERR_BAD_ARG;
-    }
-  for (size_t i = 0; i < nh; ++i) {
-    AgentDev &a = agents[(size_t)hosted_ids[i]];
-    DeviceProblem &pb = *a.prob;
-    DCORA_HIP(hipMemcpyAsync(pb.Q.v.p, Qs[i].v.data(), sizeof(double) * Qs[i].v.size(), hipMemcpyHostToDevice, st));
-    if (pb.has_bsr)
-      DCORA_HIP(hipMemcpyAsync(pb.Qb.bv.p, bsr[i].bv.data(), sizeof(double) * bsr[i].bv.size(), hipMemcpyHostToDevice, st));
-    if (!Cs[i].v.empty())
-      DCORA_HIP(hipMemcpyAsync(a.coupling.v.p, Cs[i].v.data(), sizeof(double) * Cs[i].v.size(), hipMemcpyHostToDevice, st));
-  }
-  // the preconditioners of the new matrices, as init builds them: the dense batch first, then every problem attaches
-  if ((long)(n / R + 1) * dh <= kDensePrecondMaxK && nh > 1) {
-    std::vector<const HostCsr *> ptrs;
-    for (const HostCsr &Q : Qn) ptrs.push_back(&Q);
-    const int prc = precond_prebuild_dense(ptrs, 0.1, dh, opt.device);
-    if (prc) return prc;
-  }
-  std::vector<int> rcs(nh, DCORA_OK);
-  std::vector<std::string> errs(nh);
-  auto attach = [&](size_t i) {
-    if (hipSetDevice(opt.device) != hipSuccess) {
-      rcs[i] = DCORA_ERR_HIP;
-      return;
-    }
-    rcs[i] = agents[(size_t)hosted_ids[i]].prob->build_preconditioner(Qn[i], 0.1);
-    if (rcs[i]) errs[i] = dcora_last_error();
-  };
-  if (nh > 1 && (long)(n / R) * dh >= 1024) {  // (large blocks: host factorisations side by side, as in init)
-    std::atomic<size_t> next(0);
-    auto worker = [&] {
-      for (;;) {
-        const size_t i = next.fetch_add(1);
-        if (i >= nh) break;
-        attach(i);
+    });
+    for (size_t i = 0; i < nh; ++i)
+      if (!ok[i]) {
+        set_last_error("rbcd robust: the weights give a matrix entry outside the session's pattern");
+        return DCORA_ERR_BAD_ARG;
       }
-    };
-    std::vector<std::thread> th;
-    for (size_t t = 1; t < std::min<size_t>(nh, 8); ++t) th.emplace_back(worker);
-    worker();
-    for (std::thread &t : th) t.join();
-  } else {
-    for (size_t i = 0; i < nh; ++i) attach(i);
-  }
-  for (size_t i = 0; i < nh; ++i)
-    if (rcs[i]) {
-      set_last_error(errs[i]);
-      return rcs[i];
+    for (size_t i = 0; i < nh; ++i) {
+      AgentDev &a = agents[(size_t)hosted_ids[i]];
+      DeviceProblem &pb = *a.prob;
+      DCORA_HIP(hipMemcpyAsync(pb.Q.v.p, Qs[i].v.data(), sizeof(double) * Qs[i].v.size(), hipMemcpyHostToDevice, st));
+      if (pb.has_bsr)
+        DCORA_HIP(hipMemcpyAsync(pb.Qb.bv.p, bsr[i].bv.data(), sizeof(double) * bsr[i].bv.size(), hipMemcpyHostToDevice, st));
+      if (!Cs[i].v.empty())
+        DCORA_HIP(hipMemcpyAsync(a.coupling.v.p, Cs[i].v.data(), sizeof(double) * Cs[i].v.size(), hipMemcpyHostToDevice, st));
     }
-  central_th.join();
+    // the preconditioners of the new matrices, as init builds them: the dense batch first, then every problem attaches
+    if ((long)(n / R + 1) * dh <= kDensePrecondMaxK && nh > 1) {
+      std::vector<const HostCsr *> ptrs;
+      for (const HostCsr &Q : Qn) ptrs.push_back(&Q);
+      const int prc = precond_prebuild_dense(ptrs, 0.1, dh, opt.device);
+      if (prc) return prc;
+    }
+    auto attach = [&](size_t i) {
+      if (hipSetDevice(opt.device) != hipSuccess) {
+        rcs[i] = DCORA_ERR_HIP;
+        return;
+      }
+      rcs[i] = agents[(size_t)hosted_ids[i]].prob->build_preconditioner(Qn[i], 0.1);
+      if (rcs[i]) errs[i] = dcora_last_error();
+    };
+    if (nh > 1 && (long)(n / R) * dh >= 1024) {  // (large blocks: host factorisations side by side, as in init)
+      std::atomic<size_t> nxt(0);
+      run_threads((int)std::min<size_t>(nh, 8), [&](int) {
+        for (;;) {
+          const size_t i = nxt.fetch_add(1);
+          if (i >= nh) break;
+          attach(i);
+        }
+      });
+    } else {
+      for (size_t i = 0; i < nh; ++i) attach(i);
+    }
+    for (size_t i = 0; i < nh; ++i)
+      if (rcs[i]) {
+        set_last_error(errs[i]);
+        return rcs[i];
+      }
+    return DCORA_OK;
+  };
+  int rc = DCORA_OK;
+  run_threads(2, [&](int t) {
+    if (t == 0) {
+      rc = rebuild_agents();
+    } else if (central) {
+      central_ok = scatter_on_pattern(build_Q_pgo(d, n, 0, global), rs.central_pat, &Qcs);
+      if (central_ok && central->has_bsr) cbsr = bsr_from_csr(Qcs, dh);
+    }
+  });
+  if (rc) return rc;
   if (!central_ok) {
     set_last_error("rbcd robust: the weights give a matrix entry outside the session's pattern");
     return DCORA_ERR_BAD_ARG;
@@ -1194,11 +1181,7 @@ int RbcdSession::iterate_set(const int *set, int count, int allow_adjacent) {
     rcs[0] = solve_block(*work[0], &errs[0]);
   } else {
     // the solver paces each solve from the host (device_problem.hip): one host thread per concurrent solve
-    std::vector<std::thread> th;
-    for (size_t i = 1; i < work.size(); ++i)
-      th.emplace_back([&, i] { rcs[i] = solve_block(*work[i], &errs[i]); });
-    rcs[0] = solve_block(*work[0], &errs[0]);
-    for (std::thread &t : th) t.join();
+    run_threads((int)work.size(), [&](int i) { rcs[(size_t)i] = solve_block(*work[(size_t)i], &errs[(size_t)i]); });
   }
   last_solver = work.back()->prob.get();
   for (size_t i = 0; i < work.size(); ++i) {

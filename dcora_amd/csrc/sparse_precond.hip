@@ -465,7 +465,7 @@ bool DeviceWeightSink::fill_on_device(const std::vector<partinv::Fill> &fills, l
   DevBuf<double> dstage;
   if (stage_total > 0) {
     std::vector<double> hstage((size_t)stage_total);
-    partinv::parallel_for((int)slist.size(), std::max(1, nthreads), 4, [&](int i) {
+    parallel_for((int)slist.size(), std::max(1, nthreads), 4, [&](int i) {
       std::copy(slist[(size_t)i].first, slist[(size_t)i].first + slist[(size_t)i].second->doubles,
                 hstage.begin() + slist[(size_t)i].second->offset);
     });

@@ -18,7 +18,9 @@
  *     the handle's HIP stream without synchronising;
  *   - every function returns a dcora_status (0 = ok); nothing throws across
  *     the ABI.  The library fails loudly (DCORA_ERR_NO_DEVICE / DCORA_ERR_HIP)
- *     when no gfx950 device is usable: there is no CPU fallback.
+ *     when no gfx950 device is usable: there is no CPU fallback;
+ *   - a NULL handle or a NULL required pointer (one not documented as optional)
+ *     returns DCORA_ERR_BAD_ARG; the *_destroy functions accept NULL.
  */
 #ifndef DCORA_HIP_H_
 #define DCORA_HIP_H_
