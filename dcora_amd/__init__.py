@@ -503,6 +503,26 @@ def suboptimality_gap(r, d, n, X, psd, eta, lambda_min=None, l=0, b=0, lambda_bo
     return gap.value, neff.value
 
 
+def _rbcd_options(num_robots, r, acceleration, restart_interval, params, rank, world_size, device, stream):
+    o = RbcdOptions()
+    capi.lib().dcora_rbcd_options_default(C.byref(o))
+    o.num_robots, o.r, o.acceleration, o.restart_interval = num_robots, r, int(acceleration), restart_interval
+    if params is not None:
+        o.local = params.c
+    o.rank, o.world_size, o.device = rank, world_size, device
+    o.stream = stream  # raw hipStream_t (int) or None
+    return o
+
+
+def _fixed_flags(ds, fixed_weight):
+    if fixed_weight is None:
+        return None
+    fx = np.ascontiguousarray(fixed_weight, np.int32)
+    if fx.shape != (ds.m,):
+        raise ValueError("fixed_weight needs one flag per measurement")
+    return fx
+
+
 class RbcdSession:
     """Agents + synchronous RBCD++ driver on the device (ref examples/MultiRobotExample.cpp:121-307)"""
 
@@ -513,24 +533,14 @@ class RbcdSession:
         fixed_weight flag (m booleans, default none) is off (Agent::initializeRobustOptimization)"""
         self.ds, self.R, self.r = ds, num_robots, r
         self.k = (ds.d + 1) * ds.n
-        o = RbcdOptions()
-        capi.lib().dcora_rbcd_options_default(C.byref(o))
-        o.num_robots, o.r, o.acceleration, o.restart_interval = num_robots, r, int(acceleration), restart_interval
-        if params is not None:
-            o.local = params.c
-        o.rank, o.world_size, o.device = rank, world_size, device
-        o.stream = stream  # raw hipStream_t (int) or None
+        o = _rbcd_options(num_robots, r, acceleration, restart_interval, params, rank, world_size, device, stream)
         dsh = ds.handle()
         self.h = C.c_void_p()
         try:
             if robust is None:
                 check(capi.lib().dcora_rbcd_create(dsh, C.byref(o), C.byref(self.h)))
             else:
-                fx = None
-                if fixed_weight is not None:
-                    fx = np.ascontiguousarray(fixed_weight, np.int32)
-                    if fx.shape != (ds.m,):
-                        raise ValueError("fixed_weight needs one flag per measurement")
+                fx = _fixed_flags(ds, fixed_weight)
                 check(capi.lib().dcora_rbcd_create_robust(dsh, C.byref(o), C.byref(robust.c),
                                                           None if fx is None else fx.ctypes.data_as(C.c_void_p),
                                                           C.byref(self.h)))
@@ -671,9 +681,12 @@ class Exchange:
     created with rank / world_size; every rank creates the exchange under the same job name"""
     IPC, STAGED = 1, 2
 
-    def __init__(self, session, job_name):
+    def __init__(self, session, job_name, _handle=None):
         self.s = session
         self.h = C.c_void_p()
+        if _handle is not None:  # (made together with its session: robust_ranked_session)
+            self.h = _handle
+            return
         create = capi.lib().dcora_exchange_create_ra if isinstance(session, RaRbcdSession) else capi.lib().dcora_exchange_create
         check(create(session.h, job_name.encode(), C.byref(self.h)))
 
@@ -758,6 +771,52 @@ class Exchange:
 
     def barrier(self):
         check(capi.lib().dcora_exchange_barrier(self.h))
+
+    # ---- robust jobs (robust_ranked_session) ----
+    def update_weights(self, reset_to_initial=False):
+        """Agent::updateMeasurementWeights of every agent on every rank (collective); returns the loop closures'
+        {accepted, rejected, undecided} counts of the whole job"""
+        c = np.zeros(3, np.int32)
+        check(capi.lib().dcora_exchange_update_weights(self.h, int(bool(reset_to_initial)),
+                                                       c.ctypes.data_as(C.c_void_p)))
+        return {"accepted": int(c[0]), "rejected": int(c[1]), "undecided": int(c[2])}
+
+    def set_weights(self, w):
+        """all m weights in dataset order, the same on every rank (collective)"""
+        w = np.ascontiguousarray(w, np.float64)
+        if w.shape != (self.s.m,):
+            raise ValueError("set_weights needs one weight per measurement")
+        check(capi.lib().dcora_exchange_set_weights(self.h, w))
+
+    def get_weights(self):
+        """all m weights of the job, the same on every rank (collective)"""
+        w = np.zeros(self.s.m)
+        check(capi.lib().dcora_exchange_get_weights(self.h, w))
+        return w
+
+
+def robust_ranked_session(ds, job_name, num_robots=5, r=5, robust=None, fixed_weight=None, rank=0, world_size=1,
+                          device=0, acceleration=True, restart_interval=30, params=None, stream=None):
+    """(RbcdSession, Exchange) of one rank of a robust multi-rank job (dcora_rbcd_create_robust_ranks): the robust
+    session of RbcdSession(robust=...) for the agents this rank hosts, and its exchange under job_name.  Every rank
+    calls this with the same arguments but rank; weights change through the exchange (update_weights / set_weights /
+    get_weights), collectively.  The session's get_weights() is this rank's view (NaN for measurements touching none
+    of its agents)."""
+    from . import robust as rb
+    robust = robust or rb.RobustCostParameters("GNC_TLS")
+    o = _rbcd_options(num_robots, r, acceleration, restart_interval, params, rank, world_size, device, stream)
+    fx = _fixed_flags(ds, fixed_weight)
+    dsh = ds.handle()
+    hs, hx = C.c_void_p(), C.c_void_p()
+    try:
+        check(capi.lib().dcora_rbcd_create_robust_ranks(dsh, C.byref(o), C.byref(robust.c),
+                                                        None if fx is None else fx.ctypes.data_as(C.c_void_p),
+                                                        job_name.encode(), C.byref(hs), C.byref(hx)))
+    finally:
+        capi.lib().dcora_dataset_destroy(dsh)
+    s = RbcdSession.__new__(RbcdSession)
+    s.ds, s.R, s.r, s.k, s.m, s.h = ds, num_robots, r, (ds.d + 1) * ds.n, ds.m, hs
+    return s, Exchange(s, job_name, _handle=hx)
 
 
 class RaRbcdSession:

@@ -147,6 +147,8 @@ SIGNATURES = {
     "dcora_rbcd_set_weights": (C.c_int, [_vp, _dp]),
     "dcora_rbcd_get_weights": (C.c_int, [_vp, _dp]),
     "dcora_rbcd_robust_info": (C.c_int, [_vp, _PD, _PI]),
+    "dcora_rbcd_create_robust_ranks": (C.c_int, [_vp, C.POINTER(RbcdOptions), C.POINTER(RobustParams), _vp, C.c_char_p,
+                                                 C.POINTER(_vp), C.POINTER(_vp)]),
     "dcora_rbcd_X_device_ptr": (C.c_int, [_vp, C.POINTER(_vp)]),
     "dcora_rbcd_public_count": (C.c_int, [_vp, C.c_int, _PI]),
     "dcora_rbcd_public_indices": (C.c_int, [_vp, C.c_int, _ip]),
@@ -170,6 +172,9 @@ SIGNATURES = {
     "dcora_exchange_gather_X": (C.c_int, [_vp, _dp]),
     "dcora_exchange_barrier": (C.c_int, [_vp]),
     "dcora_exchange_all_ready": (C.c_int, [_vp, C.c_int, _PI]),
+    "dcora_exchange_update_weights": (C.c_int, [_vp, C.c_int, _vp]),
+    "dcora_exchange_set_weights": (C.c_int, [_vp, _dp]),
+    "dcora_exchange_get_weights": (C.c_int, [_vp, _dp]),
     "dcora_exchange_certify": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_double, _PI, _PD, _PD, _dp,
                                          C.POINTER(C.c_longlong), _PI]),
     "dcora_exchange_host_selftest": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, _PD]),

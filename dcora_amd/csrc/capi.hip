@@ -38,6 +38,7 @@ struct dcora_rbcd_s {
 };
 struct dcora_exchange_s {
   Exchange e;
+  RbcdSession *ranked = nullptr;  // the robust session it was created with (dcora_rbcd_create_robust_ranks)
 };
 
 namespace {
@@ -979,34 +980,65 @@ int dcora_rbcd_create_robust(dcora_dataset_t ds, const dcora_rbcd_options *opt, 
                              const int *fixed_weight, dcora_rbcd_t *out) {
   return abi_call({ds, opt, robust, out}, [&]() -> int {
     if (opt->world_size != 1) {
-      set_last_error("rbcd robust: only single-process sessions (world_size 1) update weights");
+      set_last_error("rbcd robust: dcora_rbcd_create_robust makes single-process sessions (world_size 1); a multi-rank "
+                     "job creates its sessions with dcora_rbcd_create_robust_ranks");
       return DCORA_ERR_UNSUPPORTED;
     }
     return create(out, [&](dcora_rbcd_s &h) { return h.s.init_robust(ds->ds, *opt, *robust, fixed_weight); });
   });
 }
+// the robust session of one rank and its exchange, created together: weight updates are collective
+int dcora_rbcd_create_robust_ranks(dcora_dataset_t ds, const dcora_rbcd_options *opt, const dcora_robust_params *robust,
+                                   const int *fixed_weight, const char *job_name, dcora_rbcd_t *session,
+                                   dcora_exchange_t *ex) {
+  return abi_call({ds, opt, robust, job_name, session, ex}, [&]() -> int {
+    std::unique_ptr<dcora_rbcd_s> h(new dcora_rbcd_s);
+    int rc = h->s.init_robust(ds->ds, *opt, *robust, fixed_weight, true);
+    if (rc) return rc;
+    std::unique_ptr<dcora_exchange_s> x(new dcora_exchange_s);
+    rc = x->e.init(&h->s, job_name, ds->ds.meas.size());
+    if (rc) return rc;
+    rc = x->e.publish_weights(h->s);
+    if (rc) return rc;
+    x->ranked = &h->s;
+    *session = h.release();
+    *ex = x.release();
+    return (int)DCORA_OK;
+  });
+}
 namespace {
 // the robust entries' refusals: multi-process sessions first, then sessions without robust state
 int robust_session(dcora_rbcd_t s) {
+  if (s->s.robust) return DCORA_OK;
   if (s->s.opt.world_size != 1) {
     set_last_error("rbcd robust: only single-process sessions (world_size 1) update weights");
     return DCORA_ERR_UNSUPPORTED;
   }
-  if (!s->s.robust) return bad("rbcd robust: the session was not created by dcora_rbcd_create_robust");
-  return DCORA_OK;
+  return bad("rbcd robust: the session was not created by dcora_rbcd_create_robust");
+}
+// ... and the session-level weight changes, which are not collective, on a session of dcora_rbcd_create_robust_ranks
+int local_robust_session(dcora_rbcd_t s, const char *collective) {
+  const int rc = robust_session(s);
+  if (rc || !s->s.robust->ranked) return rc;
+  set_last_error(std::string("rbcd robust: the session belongs to a multi-rank job (dcora_rbcd_create_robust_ranks): "
+                             "its weights change through ") + collective);
+  return DCORA_ERR_UNSUPPORTED;
+}
+int ranked_exchange(dcora_exchange_t ex) {
+  return ex->ranked ? DCORA_OK : bad("exchange robust: the exchange was not created by dcora_rbcd_create_robust_ranks");
 }
 }  // namespace
 // Agent::updateMeasurementWeights (ref src/Agent.cpp:1397-1441) of every agent
 int dcora_rbcd_update_weights(dcora_rbcd_t s, int reset_to_initial, int counts[3]) {
   return abi_call({s}, [&] {
-    const int rc = robust_session(s);
+    const int rc = local_robust_session(s, "dcora_exchange_update_weights");
     return rc ? rc : s->s.update_weights(reset_to_initial != 0, counts);
   });
 }
 // Agent::setMeasurementWeight (ref src/Agent.cpp:1443-1454) of every measurement
 int dcora_rbcd_set_weights(dcora_rbcd_t s, const double *w) {
   return abi_call({s, w}, [&] {
-    const int rc = robust_session(s);
+    const int rc = local_robust_session(s, "dcora_exchange_set_weights");
     return rc ? rc : s->s.set_weights(w);
   });
 }
@@ -1272,6 +1304,24 @@ int dcora_debug_exchange_leave_stale(const char *job_name, int world_size, int n
 }
 int dcora_exchange_barrier(dcora_exchange_t ex) {
   return abi_call({ex}, [&] { return ex->e.barrier(); });
+}
+int dcora_exchange_update_weights(dcora_exchange_t ex, int reset_to_initial, int counts[3]) {
+  return abi_call({ex, counts}, [&] {
+    const int rc = ranked_exchange(ex);
+    return rc ? rc : ex->e.update_weights(*ex->ranked, reset_to_initial != 0, counts);
+  });
+}
+int dcora_exchange_set_weights(dcora_exchange_t ex, const double *w) {
+  return abi_call({ex, w}, [&] {
+    const int rc = ranked_exchange(ex);
+    return rc ? rc : ex->e.set_weights(*ex->ranked, w);
+  });
+}
+int dcora_exchange_get_weights(dcora_exchange_t ex, double *w) {
+  return abi_call({ex, w}, [&] {
+    const int rc = ranked_exchange(ex);
+    return rc ? rc : ex->e.get_weights(w);
+  });
 }
 
 // ---- RBCD session, range-aided SLAM ----------------------------------------------------------------------------

@@ -66,7 +66,8 @@ extern std::atomic<int> g_probe_fault_rounds;  // test hook of the link check (d
 class Exchange {
  public:
   ~Exchange();
-  int init(ExchangeSession *s, const char *job_name);
+  // weights: doubles of the segment's weights area (the m weights of a robust job, dcora_rbcd_create_robust_ranks)
+  int init(ExchangeSession *s, const char *job_name, size_t weights = 0);
   int post(const int *agents, int count);
   int wait(const int *agents, int count);
   int post_arr(const int *agents, int count, int r, const double *arr);
@@ -84,6 +85,13 @@ class Exchange {
   int evaluate(double *cost2, double *gradnorm, double *block_norms, int *next_selected);
   int rbcd_iterate(int selected, double *cost2, double *gradnorm, double *block_norms, int *next_selected);
   int rbcd_tick(const int *set, int count, int allow_adjacent);
+  // Robust jobs (the session s was created by init_robust(..., ranked = true) and is the exchange's session):
+  // Agent::updateMeasurementWeights of every agent on every rank.  Each rank weights the edges touching its agents from
+  // its mirror, the owners store theirs into the weights area, counts are summed over the ranks.
+  int update_weights(RbcdSession &s, bool reset_to_initial, int counts[3]);
+  int set_weights(RbcdSession &s, const double *w);  // all m weights, the same on every rank
+  int get_weights(double *w);                        // all m weights of the job, from the weights area
+  int publish_weights(const RbcdSession &s);         // the owned edges' current weights into the area (creation)
   int barrier(double timeout_s = 120.0);
   int gather_X(double *Xh);
   // Agent::setX of every agent on every rank: sequence numbers restart with the Nesterov sequences
@@ -120,6 +128,7 @@ class Exchange {
   ShmEval *evals_ = nullptr;  // [parity][agent]
   double *staged_ = nullptr;  // [parity][agent][slot]
   double *xarea_ = nullptr;   // r x (d+1) n
+  size_t off_w_ = 0, w_doubles_ = 0;  // weights area: m doubles in dataset order, written by the edges' owners
   ShmRed *red_ = nullptr;        // [parity][rank]
   size_t off_red_ = 0;
   uint64_t red_seq_ = 0;
@@ -148,7 +157,7 @@ class Exchange {
 
   size_t halo_off(int parity, int agent) const { return ((size_t)parity * R_ + agent) * slot_; }
   int open_segment(const char *job_name, size_t bytes);
-  int map_segment(const char *job_name, size_t x_doubles);
+  int map_segment(const char *job_name, size_t x_doubles, size_t w_doubles = 0);
   int setup_ipc(bool attempt);
   int link_check();
   bool probe_round(uint64_t seq, std::string *why);

@@ -347,8 +347,9 @@ int Exchange::open_segment(const char *job_name, size_t bytes) {
   }
 }
 
-// shared segment: header | per-rank records | flags [2][R] | evaluation slots [2][R] | staged poses [2][R][slot] | X
-int Exchange::map_segment(const char *job_name, size_t x_doubles) {
+// shared segment: header | per-rank records | flags [2][R] | evaluation slots [2][R] | staged poses [2][R][slot] | X |
+// weights
+int Exchange::map_segment(const char *job_name, size_t x_doubles, size_t w_doubles) {
   const int R = R_;
   size_t off = align_up(sizeof(ShmHeader), 64);
   const size_t off_ranks = off;
@@ -374,6 +375,10 @@ int Exchange::map_segment(const char *job_name, size_t x_doubles) {
   off = align_up(off, 4096);
   off_x_ = off;
   off += sizeof(double) * x_doubles;
+  off = align_up(off, 64);
+  off_w_ = off;
+  w_doubles_ = w_doubles;
+  off += sizeof(double) * w_doubles;
   const size_t total = align_up(off, 4096);
   const int rc = open_segment(job_name, total);
   if (rc) return rc;
@@ -408,7 +413,7 @@ int Exchange::barrier(double timeout_s) {
   return DCORA_OK;
 }
 
-int Exchange::init(ExchangeSession *s, const char *job_name) {
+int Exchange::init(ExchangeSession *s, const char *job_name, size_t weights) {
   s_ = s;
   rank = s->x_rank();
   world = s->x_world();
@@ -445,7 +450,7 @@ int Exchange::init(ExchangeSession *s, const char *job_name) {
     if ((int)dests_[a].size() > kMaxDst) return fail("an agent has neighbours on more than 8 other ranks", DCORA_ERR_UNSUPPORTED);
   seq_.assign(R, 0);
 
-  int rc = map_segment(job_name, (size_t)s->x_rank_r() * (size_t)s->x_num_cols());
+  int rc = map_segment(job_name, (size_t)s->x_rank_r() * (size_t)s->x_num_cols(), weights);
   if (rc) return rc;
   {
     const hipError_t e = hipHostRegister(map_, map_bytes_, hipHostRegisterMapped | hipHostRegisterPortable);
@@ -981,6 +986,65 @@ int Exchange::gather_X(double *Xh) {
   if (rc) return rc;
   std::memcpy(Xh, xarea_, sizeof(double) * (size_t)s_->x_rank_r() * (size_t)s_->x_num_cols());
   return barrier();
+}
+
+// Collective weight update (ref src/Agent.cpp:1397-1441 on every agent of every rank), in the single session's order:
+// streams drained and the weights computed (compute_weights), the counts summed, the hosted matrices rebuilt,
+// RobustCost::update, X back to the last set_X if asked, acceleration re-initialised.  A shared edge is weighted on
+// both of its ranks from bitwise-equal mirror columns.  The weights area is written by the kernel while no rank reads
+// it: get_weights ends with a barrier, and the allreduce below is passed only once every rank's stores have landed.
+int Exchange::update_weights(RbcdSession &s, bool reset_to_initial, int counts[3]) {
+  if (!s.robust || !s.robust->ranked || (ExchangeSession *)&s != s_ || w_doubles_ != s.robust->meas.size())
+    return usage("update_weights: the exchange's session is not a ranked robust session", DCORA_ERR_BAD_ARG);
+  std::vector<double> w;
+  double cnt[3] = {0, 0, 0};
+  int rc = s.compute_weights((double *)(dev_map_ + off_w_), &w, cnt);
+  if (rc) return fail(std::string("update_weights: ") + dcora_last_error(), rc);
+  rc = allreduce_sum(cnt, 3);
+  if (rc) return rc;
+  if (reset_to_initial) {  // (every rank's mirror becomes the last set_X at once, as Exchange::set_X does)
+    rc = barrier();
+    if (rc) return rc;
+  }
+  rc = s.apply_weights(w, reset_to_initial);
+  if (rc) return fail(std::string("update_weights: ") + dcora_last_error(), rc);
+  if (reset_to_initial) {
+    rc = barrier();
+    if (rc) return rc;
+  }
+  for (int c = 0; c < 3; ++c) counts[c] = (int)cnt[c];
+  return DCORA_OK;
+}
+
+// Every rank receives the same w, and RbcdSession::set_weights checks all m weights before anything changes (negative
+// or not finite, or nonzero where creation had 0): a refusal is the same on every rank and leaves the job as it was,
+// with the exchange usable.  The owners then store their edges' weights into the area.
+int Exchange::set_weights(RbcdSession &s, const double *w) {
+  if (!s.robust || !s.robust->ranked || (ExchangeSession *)&s != s_ || w_doubles_ != s.robust->meas.size())
+    return usage("set_weights: the exchange's session is not a ranked robust session", DCORA_ERR_BAD_ARG);
+  const int rc = s.set_weights(w);
+  if (rc == DCORA_ERR_BAD_ARG) return rc;  // (refused on every rank alike, nothing changed)
+  if (rc) return fail(std::string("set_weights: ") + dcora_last_error(), rc);
+  return publish_weights(s);
+}
+
+// the weights the session holds for the edges this rank owns into the area (host stores), then a barrier
+int Exchange::publish_weights(const RbcdSession &s) {
+  const RobustSession &rs = *s.robust;
+  double *area = (double *)((char *)map_ + off_w_);
+  for (size_t e = 0; e < rs.meas.size() && e < w_doubles_; ++e) {
+    const PoseMeas &q = rs.meas[e];
+    if (owner_[(size_t)s.P.robot_of(q.p1)] == rank) area[e] = q.weight;
+  }
+  std::atomic_thread_fence(std::memory_order_release);
+  return barrier();
+}
+
+int Exchange::get_weights(double *w) {
+  if (w_doubles_ == 0) return usage("get_weights: the exchange was not created for a robust job", DCORA_ERR_BAD_ARG);
+  std::atomic_thread_fence(std::memory_order_acquire);
+  std::memcpy(w, (const char *)map_ + off_w_, sizeof(double) * w_doubles_);
+  return barrier();  // nobody writes the area again before every rank has read it
 }
 
 int Exchange::debug_leave_stale(const char *job_name, int world_, int R) {

@@ -38,10 +38,12 @@ struct AgentDev {
   bool last_skipped = false;
 };
 
-// Robust state of a session created by dcora_rbcd_create_robust (world_size 1): the agents' GNC loop inside one live
-// session (Agent::initializeRobustOptimization / updateMeasurementWeights, ref src/Agent.cpp:1332-1346, 1397-1441).
+// Robust state of a session created by dcora_rbcd_create_robust (world_size 1) or dcora_rbcd_create_robust_ranks (one
+// rank of a job, whose updates are collective: Exchange::update_weights): the agents' GNC loop inside one live session
+// (Agent::initializeRobustOptimization / updateMeasurementWeights, ref src/Agent.cpp:1332-1346, 1397-1441).
 // A weight change rebuilds the VALUES of Q_bb, the coupling blocks and the central Q on their creation patterns (a
-// weight of 0 leaves explicit zeros), and the preconditioners through the path creation takes.
+// weight of 0 leaves explicit zeros), and the preconditioners through the path creation takes.  A rank's matrices hold
+// only the edges touching its hosted agents: the weights of all other edges in `meas` are not kept up to date.
 struct RobustSession {
   explicit RobustSession(const dcora_robust_params &p) : cost(p), params(p) {}
   RobustCost cost;
@@ -51,6 +53,8 @@ struct RobustSession {
   std::vector<char> update;      // loop closures whose weight is not fixed: what updateMeasurementWeights rewrites
   std::vector<char> meas_zero;   // weight 0 at creation: the patterns do not hold these measurements
   RobustEdges edges;             // device copy of the measurements and of the weights
+  bool ranked = false;           // created by dcora_rbcd_create_robust_ranks
+  std::vector<int> edge_ids;     // the measurements in `edges` (dataset order): all, or those touching a hosted agent
   DevBuf<double> X_initial;      // the last set_X (robustOptNumResets: setXToInitialGuess)
   std::vector<HostCsr> Qpat, Cpat;  // creation patterns (rp, ci) of every hosted agent's Q_bb and coupling block
   HostCsr central_pat;
@@ -84,11 +88,17 @@ class RbcdSession : public ExchangeSession {
   int init(const HostDataset &ds, const dcora_rbcd_options &o);
   // robust sessions: weight 1 on every loop closure that is not fixed (fixed: m flags or null), then init
   std::unique_ptr<RobustSession> robust;
-  int init_robust(const HostDataset &ds, const dcora_rbcd_options &o, const dcora_robust_params &p, const int *fixed);
+  // ranked: a rank of a multi-rank job (world_size >= 1), its weight updates driven by the exchange
+  int init_robust(const HostDataset &ds, const dcora_rbcd_options &o, const dcora_robust_params &p, const int *fixed,
+                  bool ranked = false);
   // updateMeasurementWeights on the current iterate; counts (may be null): accepted, rejected, undecided closures
   int update_weights(bool reset_to_initial, int counts[3]);
+  // its two halves: the weights of the session's edges on the device (ranked: the owned ones also into shared_w,
+  // counts over the owned ones), then the matrices rebuilt and the rest of the update
+  int compute_weights(double *shared_w, std::vector<double> *w, double counts[3]);
+  int apply_weights(const std::vector<double> &w, bool reset_to_initial);
   int set_weights(const double *w);  // all m weights; refused (session untouched) when one is negative or not finite
-  int get_weights(double *w) const;
+  int get_weights(double *w) const;  // ranked: NaN for the edges touching no hosted agent
   int set_X(const double *Xh);
   int get_X(double *Xh);
   int set_acceleration(bool on);

@@ -341,10 +341,12 @@ int RbcdSession::get_X(double *Xh) {
 // whose weight is not fixed.  A loop closure is every measurement but odometry, i.e. but p2 == p1 + 1 inside one agent
 // of the contiguous partition (driver.loop_closure_mask).  With weights 1 the patterns are the largest any later
 // weights can give: they are kept, and a weight change only rewrites values.
+// A rank of a multi-rank job (ranked) builds the patterns of its hosted agents only and uploads the edges touching them.
 int RbcdSession::init_robust(const HostDataset &ds, const dcora_rbcd_options &o, const dcora_robust_params &p,
-                             const int *fixed) {
-  if (o.world_size != 1) {
-    set_last_error("rbcd robust: only single-process sessions (world_size 1) update weights");
+                             const int *fixed, bool ranked) {
+  if (o.world_size != 1 && !ranked) {
+    set_last_error("rbcd robust: only single-process sessions (world_size 1) update weights here; a multi-rank job "
+                   "creates its sessions with dcora_rbcd_create_robust_ranks");
     return DCORA_ERR_UNSUPPORTED;
   }
   if (o.num_robots < 1 || ds.n / o.num_robots < 1) {
@@ -383,7 +385,22 @@ int RbcdSession::init_robust(const HostDataset &ds, const dcora_rbcd_options &o,
   rs.Cpat.assign((size_t)o.num_robots, HostCsr());
   int rc = init(rds, o);
   if (rc) return rc;
-  rc = rs.edges.upload(rds, rs.update);
+  rs.ranked = ranked;
+  if (ranked) {
+    // the edges touching a hosted agent; the rank owns those whose p1 it hosts (every edge has one owner in the job)
+    std::vector<char> own;
+    for (size_t e = 0; e < m; ++e) {
+      const PoseMeas &q = rds.meas[e];
+      const bool h1 = agents[(size_t)P.robot_of(q.p1)].hosted, h2 = agents[(size_t)P.robot_of(q.p2)].hosted;
+      if (!h1 && !h2) continue;
+      rs.edge_ids.push_back((int)e);
+      own.push_back(h1 ? 1 : 0);
+    }
+    rc = rs.edges.upload_ranked(rds, rs.update, rs.edge_ids, own);
+  } else {
+    for (size_t e = 0; e < m; ++e) rs.edge_ids.push_back((int)e);
+    rc = rs.edges.upload(rds, rs.update);
+  }
   if (rc) return rc;
   DCORA_HIP(rs.X_initial.alloc((size_t)r * (d + 1) * n));
   DCORA_HIP(hipMemsetAsync(rs.X_initial.p, 0, sizeof(double) * (size_t)r * (d + 1) * n, st));
@@ -557,26 +574,50 @@ int RbcdSession::initialize_acceleration() {
 // (k_robust_weights reads the mirror Xg), the data matrices rebuilt, RobustCost::update, optionally X back to the
 // last set_X (robustOptNumResets), acceleration re-initialised
 int RbcdSession::update_weights(bool reset_to_initial, int counts[3]) {
+  std::vector<double> w;
+  double cnt[3] = {0, 0, 0};
+  int rc = compute_weights(nullptr, &w, cnt);
+  if (rc) return rc;
+  rc = apply_weights(w, reset_to_initial);
+  if (rc) return rc;
+  if (counts)
+    for (int c = 0; c < 3; ++c) counts[c] = (int)cnt[c];
+  return DCORA_OK;
+}
+
+// w: the weights of the session's edges (RobustSession::edge_ids order), counts as launch_robust_weights gives them
+int RbcdSession::compute_weights(double *shared_w, std::vector<double> *w, double counts[3]) {
   RobustSession &rs = *robust;
+  if (rs.ranked && !shared_w && !rs.edge_ids.empty()) {
+    set_last_error("rbcd robust: a ranked session's weights are computed by its exchange (dcora_exchange_update_weights)");
+    return DCORA_ERR_UNSUPPORTED;
+  }
   DCORA_HIP(hipSetDevice(opt.device));
   for (const AgentDev &a : agents)
     if (a.own) DCORA_HIP(hipStreamSynchronize(a.own));
-  const size_t m = rs.meas.size();
-  std::vector<double> w(m);
-  double cnt[3] = {0, 0, 0};
+  const size_t m = rs.edge_ids.size();
+  w->assign(m, 0.0);
+  for (int c = 0; c < 3; ++c) counts[c] = 0;
   if (m) {
-    launch_robust_weights(st, rs.edges, r, Xg.p, rs.params, rs.cost.mu());
+    launch_robust_weights(st, rs.edges, r, Xg.p, rs.params, rs.cost.mu(), shared_w);
     DCORA_HIP(hipGetLastError());
-    DCORA_HIP(hipMemcpyAsync(w.data(), rs.edges.w.p, sizeof(double) * m, hipMemcpyDeviceToHost, st));
-    DCORA_HIP(hipMemcpyAsync(cnt, rs.edges.counts.p, sizeof(cnt), hipMemcpyDeviceToHost, st));
+    DCORA_HIP(hipMemcpyAsync(w->data(), rs.edges.w.p, sizeof(double) * m, hipMemcpyDeviceToHost, st));
+    DCORA_HIP(hipMemcpyAsync(counts, rs.edges.counts.p, sizeof(double) * 3, hipMemcpyDeviceToHost, st));
   }
   DCORA_HIP(hipStreamSynchronize(st));
+  return DCORA_OK;
+}
+
+int RbcdSession::apply_weights(const std::vector<double> &w, bool reset_to_initial) {
+  RobustSession &rs = *robust;
+  const size_t m = rs.edge_ids.size();
   std::vector<PoseMeas> meas = rs.meas;
-  for (size_t e = 0; e < m; ++e) meas[e].weight = w[e];
+  for (size_t i = 0; i < m; ++i) meas[(size_t)rs.edge_ids[i]].weight = w[i];
   const int rc = rebuild_values(meas);
   if (rc) {  // (the device's weights back to the ones the matrices still hold)
-    for (size_t e = 0; e < m; ++e) w[e] = rs.meas[e].weight;
-    if (m) DCORA_HIP(hipMemcpy(rs.edges.w.p, w.data(), sizeof(double) * m, hipMemcpyHostToDevice));
+    std::vector<double> held(m);
+    for (size_t i = 0; i < m; ++i) held[i] = rs.meas[(size_t)rs.edge_ids[i]].weight;
+    if (m) DCORA_HIP(hipMemcpy(rs.edges.w.p, held.data(), sizeof(double) * m, hipMemcpyHostToDevice));
     return rc;
   }
   rs.meas.swap(meas);
@@ -584,11 +625,7 @@ int RbcdSession::update_weights(bool reset_to_initial, int counts[3]) {
   rs.updates++;
   if (reset_to_initial)
     DCORA_HIP(hipMemcpyAsync(Xg.p, rs.X_initial.p, sizeof(double) * (size_t)r * (d + 1) * n, hipMemcpyDeviceToDevice, st));
-  const int rc2 = initialize_acceleration();
-  if (rc2) return rc2;
-  if (counts)
-    for (int c = 0; c < 3; ++c) counts[c] = (int)cnt[c];
-  return DCORA_OK;
+  return initialize_acceleration();
 }
 
 int RbcdSession::set_weights(const double *w) {
@@ -604,12 +641,18 @@ int RbcdSession::set_weights(const double *w) {
   const int rc = rebuild_values(meas);
   if (rc) return rc;
   rs.meas.swap(meas);
-  if (m) DCORA_HIP(hipMemcpy(rs.edges.w.p, w, sizeof(double) * m, hipMemcpyHostToDevice));
+  const size_t me = rs.edge_ids.size();
+  std::vector<double> wl(me);
+  for (size_t i = 0; i < me; ++i) wl[i] = w[rs.edge_ids[i]];
+  if (me) DCORA_HIP(hipMemcpy(rs.edges.w.p, wl.data(), sizeof(double) * me, hipMemcpyHostToDevice));
   return initialize_acceleration();
 }
 
 int RbcdSession::get_weights(double *w) const {
-  for (size_t e = 0; e < robust->meas.size(); ++e) w[e] = robust->meas[e].weight;
+  const RobustSession &rs = *robust;
+  if (rs.ranked)
+    for (size_t e = 0; e < rs.meas.size(); ++e) w[e] = std::nan("");
+  for (int e : rs.edge_ids) w[e] = rs.meas[(size_t)e].weight;
   return DCORA_OK;
 }
 

@@ -8,14 +8,20 @@ namespace dcora {
 // the measurement table of a robust RBCD session (rbcd.h), uploaded once at creation, and the weights in dataset order
 struct RobustEdges {
   int m = 0, d = 0;
+  bool ranked = false;         // the edges of one rank of a multi-rank session (upload_ranked)
   DevBuf<int> dp1, dp2, dupd;  // dupd: the weight is rewritten by the update (a loop closure whose weight is not fixed)
+  DevBuf<int> down, dgidx;     // ranked: the rank owns the edge (hosts the agent of p1); the edge's dataset index
   DevBuf<double> dR, dt, dk, dta, w, partials, counts;
   int upload(const HostDataset &ds, const std::vector<char> &update);
+  // the edges ids (dataset order) of ds only; own: one flag per id
+  int upload_ranked(const HostDataset &ds, const std::vector<char> &update, const std::vector<int> &ids,
+                    const std::vector<char> &own);
 };
 // w[e] = RobustCost::weight(sqrt(error_e(X))) with RobustCost's mu for the edges flagged dupd; counts[3] = accepted,
-// rejected, undecided among them (per-block partials summed by one more launch: deterministic, no atomics)
+// rejected, undecided among them (per-block partials summed by one more launch: deterministic, no atomics).
+// Ranked edges: counts over the owned edges only, and the owned edges' weights also go to shared_w[dataset index]
 void launch_robust_weights(hipStream_t st, const RobustEdges &T, int r, const double *X, const dcora_robust_params &p,
-                           double mu);
+                           double mu, double *shared_w = nullptr);
 int measurement_errors(const HostDataset &ds, int r, const double *X, double *out, int device);
 int solve_pgo(const HostDataset &ds, const dcora_ropt_params &prm, const double *T0, double *Tout, int device,
               dcora_ropt_result *res);

@@ -20,6 +20,10 @@ struct EdgeDev {
   const int *p1, *p2;
   const double *R, *t, *kappa, *tau;  // R: d*d per edge (column-major), t: d per edge
 };
+struct RankedEdges {
+  const int *own, *gidx;  // the rank owns the edge (hosts the agent of p1); its index in the dataset
+  double *shared_w;       // device view of the exchange's weights area (m doubles, dataset order)
+};
 // kappa |Y1 R - Y2|^2 + tau |p2 - p1 - Y1 t|^2 of edge e with Y r x d, p r-vectors (SE ordering): one expression for
 // both kernels below, so the session's weight update sees the residuals dcora_measurement_errors reports, bit for bit
 template <int D>
@@ -82,11 +86,14 @@ __device__ double robust_weight(const dcora_robust_params &p, double mu, double 
 // Agent::updateMeasurementWeights on the session's iterate (ref src/Agent.cpp:1397-1413): one thread per edge, the
 // edges flagged upd (loop closures whose weight is not fixed) get RobustCost::weight(sqrt(error)); the rest keep theirs.
 // Per-block partials of {accepted (w > 1 - 1e-8), rejected (w < 1e-8), undecided} among the updated edges.
-template <int D>
+// Ranked (a session of one rank, RobustEdges::upload_ranked): the edges are those touching a hosted agent, X is the
+// rank's mirror; the edges the rank owns also store their weight into the shared segment at their dataset index
+// (plain stores, then a system-scope fence), and only they are counted, so that the job counts every edge once.
+template <int D, bool Ranked>
 __global__ __launch_bounds__(kBlock) void k_robust_weights(int r, int m, EdgeDev E, const int *__restrict__ upd,
                                                            const double *__restrict__ X, dcora_robust_params p,
                                                            double mu, double *__restrict__ w,
-                                                           double *__restrict__ partials) {
+                                                           double *__restrict__ partials, RankedEdges rk) {
   __shared__ double s_red[16];
   const int e = blockIdx.x * kBlock + threadIdx.x;
   double acc = 0, rej = 0, und = 0;
@@ -94,9 +101,15 @@ __global__ __launch_bounds__(kBlock) void k_robust_weights(int r, int m, EdgeDev
     const double we = robust_weight(p, mu, sqrt(edge_error<D>(r, e, E, X)));
     w[e] = we;
     const double w_tol = 1e-8;
-    acc = we > 1 - w_tol ? 1 : 0;
-    rej = we < w_tol ? 1 : 0;
-    und = 1 - acc - rej;
+    if (!Ranked || rk.own[e]) {
+      acc = we > 1 - w_tol ? 1 : 0;
+      rej = we < w_tol ? 1 : 0;
+      und = 1 - acc - rej;
+    }
+  }
+  if (Ranked) {
+    if (e < m && rk.own[e]) rk.shared_w[rk.gidx[e]] = w[e];
+    __threadfence_system();
   }
   acc = block_sum(acc, s_red);
   rej = block_sum(rej, s_red);
@@ -158,17 +171,49 @@ int RobustEdges::upload(const HostDataset &ds, const std::vector<char> &update) 
   return DCORA_OK;
 }
 
+// the edges of one rank: ids (dataset order) are those touching a hosted agent, own[i] flags the ones it owns
+int RobustEdges::upload_ranked(const HostDataset &ds, const std::vector<char> &update, const std::vector<int> &ids,
+                               const std::vector<char> &own) {
+  HostDataset sub;
+  sub.d = ds.d;
+  sub.n = ds.n;
+  std::vector<char> up;
+  for (int e : ids) {
+    sub.meas.push_back(ds.meas[(size_t)e]);
+    up.push_back(update[(size_t)e]);
+  }
+  int rc = upload(sub, up);
+  if (rc) return rc;
+  ranked = true;
+  if (m == 0) return DCORA_OK;
+  std::vector<int> ow(own.begin(), own.end());
+  DCORA_HIP(down.alloc(m));
+  DCORA_HIP(dgidx.alloc(m));
+  DCORA_HIP(hipMemcpy(down.p, ow.data(), sizeof(int) * m, hipMemcpyHostToDevice));
+  DCORA_HIP(hipMemcpy(dgidx.p, ids.data(), sizeof(int) * m, hipMemcpyHostToDevice));
+  return DCORA_OK;
+}
+
 void launch_robust_weights(hipStream_t st, const RobustEdges &T, int r, const double *X, const dcora_robust_params &p,
-                           double mu) {
+                           double mu, double *shared_w) {
   if (T.m == 0) return;
   const EdgeDev E{T.dp1.p, T.dp2.p, T.dR.p, T.dt.p, T.dk.p, T.dta.p};
   const int grid = (T.m + kBlock - 1) / kBlock;
-  if (T.d == 3)
-    hipLaunchKernelGGL(k_robust_weights<3>, dim3(grid), dim3(kBlock), 0, st, r, T.m, E, T.dupd.p, X, p, mu, T.w.p,
-                       T.partials.p);
-  else
-    hipLaunchKernelGGL(k_robust_weights<2>, dim3(grid), dim3(kBlock), 0, st, r, T.m, E, T.dupd.p, X, p, mu, T.w.p,
-                       T.partials.p);
+  const RankedEdges rk{T.down.p, T.dgidx.p, shared_w};
+  auto go = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, st, r, T.m, E, T.dupd.p, X, p, mu, T.w.p, T.partials.p, rk);
+  };
+  if (T.ranked) {
+    if (T.d == 3)
+      go(k_robust_weights<3, true>);
+    else
+      go(k_robust_weights<2, true>);
+  } else {
+    if (T.d == 3)
+      go(k_robust_weights<3, false>);
+    else
+      go(k_robust_weights<2, false>);
+  }
   launch_sum_partials(st, T.partials.p, grid, 3, 3, T.counts.p);
 }
 

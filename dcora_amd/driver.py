@@ -178,6 +178,60 @@ def multi_robot_gnc_session(ds, X0, num_robots=5, r=5, robust=None, num_weight_u
                       "gradnorm": float(out["gradnorm"][-1])}}
 
 
+def exchange_run(ex, max_iters=1000, rgrad_tol=0.1):
+    """RbcdSession.run across the ranks: greedy passes through Exchange.iterate until |rgrad| < rgrad_tol, at most
+    max_iters (the loop of dcora_rbcd_run, ref examples/MultiRobotExample.cpp:223-307)"""
+    cost, gn, sel = [], [], []
+    selected = 0
+    for _ in range(max_iters):
+        c2, g, _, nxt = ex.iterate(selected)
+        cost.append(c2)
+        gn.append(g)
+        sel.append(selected)
+        if g < rgrad_tol:
+            break
+        selected = nxt
+    return dict(iters=len(cost), cost=np.asarray(cost, float), gradnorm=np.asarray(gn, float),
+                selected=np.asarray(sel, np.int32))
+
+
+def multi_robot_gnc_ranks(ds, X0, num_robots=5, r=5, robust=None, num_weight_updates=10, inner_iters=30,
+                          rgrad_tol=0.1, max_final_iters=1000, acceleration=True, params=None, fixed=None, device=0,
+                          rank=0, world_size=1, job_name="gnc"):
+    """multi_robot_gnc_session on one rank of a multi-rank job (SPMD: every rank calls it with the same arguments but
+    rank): the ranks' robust sessions and their exchange (robust_ranked_session), the inner loops through
+    Exchange.iterate, every updateMeasurementWeights collective.  The same outputs on every rank: X gathered, the
+    job's weights.
+
+    ds.vals[:, -1] (the weights) is updated in place.  Returns X, weights, per-round records."""
+    from . import robust as rb
+    from . import robust_ranked_session
+    robust = robust or rb.RobustCostParameters("GNC_TLS")
+    lc = loop_closure_mask(ds, num_robots)
+    if fixed is not None:
+        lc &= ~np.asarray(fixed, bool)
+    rounds = []
+    s, ex = robust_ranked_session(ds, job_name, num_robots=num_robots, r=r, robust=robust, fixed_weight=fixed,
+                                  rank=rank, world_size=world_size, device=device, acceleration=acceleration,
+                                  params=params)
+    try:
+        ex.set_X(np.asarray(X0, dtype=np.float64))
+        for _ in range(num_weight_updates):
+            out = exchange_run(ex, max_iters=inner_iters, rgrad_tol=rgrad_tol)
+            c = ex.update_weights()
+            rounds.append({"iterations": int(out["iters"]), "cost_2f": float(out["cost"][-1]),
+                           "accepted": c["accepted"], "rejected": c["rejected"]})
+        out = exchange_run(ex, max_iters=max_final_iters, rgrad_tol=rgrad_tol)
+        X, w = ex.gather_X(), ex.get_weights()
+    finally:
+        ex.close()
+        s.close()
+    ds.vals[:, -1] = w
+    return {"X": X, "weights": w.copy(), "loop_closures": lc, "rounds": rounds,
+            "final": {"iterations": int(out["iters"]), "cost_2f": float(out["cost"][-1]),
+                      "gradnorm": float(out["gradnorm"][-1])}}
+
+
 def multi_robot_raslam_example(ra, X0, r_min=None, r_max=100, max_iters=1000, rgrad_tol=0.1, min_eig_tol=1e-3,
                                gradient_tolerance=1e-4, preconditioned_gradient_tolerance=1e-4, acceleration=True,
                                params=None, device=0):

@@ -499,11 +499,12 @@ typedef struct {
   double HuberThreshold, TLSThreshold;
 } dcora_robust_params;
 void dcora_robust_params_default(dcora_robust_params *p);
-/* --- robust sessions: the agents' GNC loop inside one live session (world_size 1, pose-graph sessions) --- */
+/* --- robust sessions: the agents' GNC loop inside one live session (pose-graph sessions; world_size 1 here, any
+ *     world_size through dcora_rbcd_create_robust_ranks below) --- */
 /* dcora_rbcd_create with Agent::initializeRobustOptimization (ref src/Agent.cpp:1332-1346): weight 1 on every loop
  * closure -- every measurement but odometry (p2 == p1 + 1 inside one agent of the contiguous partition) -- whose
  * fixed_weight flag (m ints, may be NULL) is 0.  The matrices' patterns are those of these weights, the largest any
- * later weights can give.  world_size > 1: DCORA_ERR_UNSUPPORTED. */
+ * later weights can give.  world_size > 1: DCORA_ERR_UNSUPPORTED (see dcora_rbcd_create_robust_ranks). */
 int dcora_rbcd_create_robust(dcora_dataset_t ds, const dcora_rbcd_options *opt, const dcora_robust_params *robust,
                              const int *fixed_weight, dcora_rbcd_t *out);
 /* Agent::updateMeasurementWeights (ref src/Agent.cpp:1397-1441): weight = RobustCost::weight(residual) of every
@@ -511,8 +512,8 @@ int dcora_rbcd_create_robust(dcora_dataset_t ds, const dcora_rbcd_options *opt, 
  * in place, RobustCost::update(), reset_to_initial != 0: X = the last dcora_rbcd_set_X (robustOptNumResets), then
  * initializeAcceleration (XPrev = V = Y = X, gamma = alpha = 0; the iteration count goes on).  counts (may be NULL):
  * accepted (w > 1 - 1e-8), rejected (w < 1e-8), undecided among the updated closures.  The next three entries and this
- * one return DCORA_ERR_BAD_ARG on a session not created by dcora_rbcd_create_robust, DCORA_ERR_UNSUPPORTED when
- * world_size > 1. */
+ * one return DCORA_ERR_BAD_ARG on a session created without robust state by dcora_rbcd_create (DCORA_ERR_UNSUPPORTED
+ * when its world_size > 1). */
 int dcora_rbcd_update_weights(dcora_rbcd_t s, int reset_to_initial, int counts[3]);
 /* all m weights in dataset order (Agent::setMeasurementWeight of every measurement, ref src/Agent.cpp:1443-1454), then
  * initializeAcceleration.  A weight that is negative or not finite, or a zero weight of creation made nonzero: the call
@@ -521,6 +522,30 @@ int dcora_rbcd_set_weights(dcora_rbcd_t s, const double *w);
 int dcora_rbcd_get_weights(dcora_rbcd_t s, double *w);
 /* RobustCost's current mu (GNC-TLS) and the number of dcora_rbcd_update_weights calls so far (either may be NULL) */
 int dcora_rbcd_robust_info(dcora_rbcd_t s, double *mu, int *updates);
+/* Robust sessions of a multi-rank job (one process per GPU, the agents spread over the ranks, public poses moved by
+ * dcora_exchange_*).  All calls are SPMD: every rank makes the same calls with the same arguments, and each gives on
+ * W ranks exactly what the single-process session gives (weights, counts and X bit for bit).
+ * dcora_rbcd_create_robust_ranks: the session of rank opt->rank of opt->world_size (world_size 1 included: that session
+ * is the one dcora_rbcd_create_robust makes) as dcora_rbcd_create_robust sets it up, together with its exchange
+ * (dcora_exchange_create under job_name).  Each rank builds and uploads what its hosted agents need only.  On such a
+ * session dcora_rbcd_update_weights and dcora_rbcd_set_weights return DCORA_ERR_UNSUPPORTED (they are not collective);
+ * dcora_rbcd_get_weights gives this rank's view: the weights its matrices hold for every measurement touching one of
+ * its agents, NaN for all others; dcora_rbcd_robust_info is unchanged.  Destroy the exchange before the session. */
+int dcora_rbcd_create_robust_ranks(dcora_dataset_t ds, const dcora_rbcd_options *opt, const dcora_robust_params *robust,
+                                   const int *fixed_weight, const char *job_name, dcora_rbcd_t *session,
+                                   dcora_exchange_t *ex);
+/* dcora_rbcd_update_weights of every agent on every rank, on the iterate that the last dcora_exchange_wait left in each
+ * rank's mirror: each rank weights the measurements touching its agents (one launch; a measurement shared by two ranks
+ * is weighted on both, to the same bits), the rank hosting p1 publishes the weight in the exchange's shared segment,
+ * counts[3] (accepted, rejected, undecided) are summed over the ranks and the same on every rank.  reset_to_initial:
+ * every rank's X back to the last dcora_exchange_set_X.  A failure on one rank fails the other ranks' next collective
+ * call (within DCORA_EXCHANGE_TIMEOUT_S), never a hang. */
+int dcora_exchange_update_weights(dcora_exchange_t ex, int reset_to_initial, int counts[3]);
+/* all m weights in dataset order, the same vector on every rank; checked in full on every rank before anything changes
+ * (the refusals of dcora_rbcd_set_weights, DCORA_ERR_BAD_ARG everywhere, the job left as it was) */
+int dcora_exchange_set_weights(dcora_exchange_t ex, const double *w);
+/* all m current weights of the job, the same on every rank */
+int dcora_exchange_get_weights(dcora_exchange_t ex, double *w);
 /* RobustCost::weight(r) for n residuals after num_updates calls of RobustCost::update() (ref src/DCORA_robust.cpp:56-136) */
 int dcora_robust_weights(const dcora_robust_params *p, int num_updates, int n, const double *r, double *w);
 /* chi2inv (ref src/DCORA_utils.cpp:2103-2106), RobustCost::computeErrorThresholdAtQuantile (ref src/DCORA_robust.cpp:138-148) */
