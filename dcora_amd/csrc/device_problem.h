@@ -93,6 +93,9 @@ struct DevCsr {
   DevBuf<double> v, long_part;
   int upload(const HostCsr &A);
   int upload(int nrows, int ncols, const int *rp, const int *ci, const double *v);
+  // new values on the uploaded pattern, asynchronous on st (A.v stays alive until st has been synchronised).  The
+  // long-row side structures (n_long, long_rows, long_cnt) come from rp alone, so they stand as they are.
+  int set_values(const HostCsr &A, hipStream_t st);
   CsrDev view() const {
     CsrDev c;
     c.nrows = nrows;
@@ -258,6 +261,11 @@ class DeviceProblem {
   int init(const dcora_dims &dims, const HostCsr &Qh, const double *Gh, double reg, int device_, hipStream_t shared);
   int set_G_host(const double *Gh);
   int build_preconditioner(const HostCsr &Qh, double reg);
+  // The values of a matrix with Q's own pattern into every image the problem keeps of Q: the CSR values and, when
+  // has_bsr, the block form (HostBsr's layout, derived into *stage).  Asynchronous on stream: the caller keeps
+  // Q_on_pattern and *stage alive until it has synchronised.  Everything else the images hold (CsrDev's long-row side
+  // structures, the block pattern) is derived from rp / ci only; the preconditioner is build_preconditioner's business.
+  int set_values(const HostCsr &Q_on_pattern, hipStream_t stream, std::vector<double> *stage);
 
   // ---- device-level building blocks (all enqueue on st, no sync) ----
   // EG = X Q + G, partials pA (npA slots of 2)

@@ -70,6 +70,14 @@ int DevBsr::upload(const HostBsr &B) {
   return DCORA_OK;
 }
 int DevCsr::upload(const HostCsr &A) { return upload(A.n, A.ncols, A.rp.data(), A.ci.data(), A.v.data()); }
+int DevCsr::set_values(const HostCsr &A, hipStream_t st) {
+  if (A.n != nrows || A.ncols != ncols || A.nnz() != nnz || (int)A.v.size() != nnz) {
+    set_last_error("set_values: the matrix does not have the uploaded pattern");
+    return DCORA_ERR_BAD_ARG;
+  }
+  if (nnz) DCORA_HIP(hipMemcpyAsync(v.p, A.v.data(), sizeof(double) * nnz, hipMemcpyHostToDevice, st));
+  return DCORA_OK;
+}
 
 // HostFlags words live in one host-mapped page per process, handed out slot by slot: hipHostMalloc per problem cost
 // more than the rest of a cached creation
@@ -270,6 +278,18 @@ int DeviceProblem::init(const dcora_dims &dims, const HostCsr &Qh, const double 
       DCORA_HIP(hipMemsetAsync(tcg_sync.p, 0, sizeof(unsigned) * (size_t)tcg_run_sync_words(), st));
     }
   }
+  return DCORA_OK;
+}
+
+int DeviceProblem::set_values(const HostCsr &Q_on_pattern, hipStream_t stream, std::vector<double> *stage) {
+  const int rc = Q.set_values(Q_on_pattern, stream);
+  if (rc || !has_bsr) return rc;
+  *stage = std::move(bsr_from_csr(Q_on_pattern, m.d + 1).bv);
+  if (stage->size() != Qb.bv.n) {
+    set_last_error("set_values: the matrix does not have the uploaded pattern");
+    return DCORA_ERR_BAD_ARG;
+  }
+  DCORA_HIP(hipMemcpyAsync(Qb.bv.p, stage->data(), sizeof(double) * stage->size(), hipMemcpyHostToDevice, stream));
   return DCORA_OK;
 }
 

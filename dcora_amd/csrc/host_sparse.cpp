@@ -87,6 +87,30 @@ HostBsr bsr_from_csr(const HostCsr &A, int bs) {
   return B;
 }
 
+HostCsr pattern_of(const HostCsr &A) {
+  HostCsr p;
+  p.n = A.n;
+  p.ncols = A.ncols;
+  p.rp = A.rp;
+  p.ci = A.ci;
+  return p;
+}
+
+bool scatter_on_pattern(const HostCsr &A, const HostCsr &P, HostCsr *out) {
+  if (A.n != P.n || A.ncols != P.ncols) return false;
+  *out = pattern_of(P);
+  out->v.assign(P.ci.size(), 0.0);
+  for (int i = 0; i < A.n; ++i) {
+    int q = P.rp[i];
+    for (int k = A.rp[i]; k < A.rp[i + 1]; ++k) {
+      while (q < P.rp[i + 1] && P.ci[q] < A.ci[k]) ++q;
+      if (q == P.rp[i + 1] || P.ci[q] != A.ci[k]) return false;
+      out->v[q] = A.v[k];
+    }
+  }
+  return true;
+}
+
 HostCsr csr_shift_diag(const HostCsr &A, double s) {
   HostCsr B;
   B.n = A.n;

@@ -27,6 +27,11 @@ struct HostBsr {
   int nblocks() const { return (int)bc.size(); }
 };
 HostBsr bsr_from_csr(const HostCsr &A, int bs);
+// the pattern (rp, ci) of a matrix, without values
+HostCsr pattern_of(const HostCsr &A);
+// the values of A on the pattern P (zeros where A has no entry); false when the shapes differ or an entry of A lies
+// outside P
+bool scatter_on_pattern(const HostCsr &A, const HostCsr &P, HostCsr *out);
 
 // builds a CSR from (row, col, val) triplets, summing duplicates, columns sorted inside rows
 HostCsr csr_from_coo(int nrows, int ncols, const std::vector<int> &I, const std::vector<int> &J,

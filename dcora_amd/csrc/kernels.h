@@ -56,7 +56,7 @@ struct CsrDev {
   int *long_cnt = nullptr;         // n_long arrival counters (zero between launches)
 };
 
-// block-CSR view of a pose-graph matrix: (d+1) x (d+1) dense blocks, row-major inside a block
+// block-CSR view of a pose-graph matrix: (d+1) x (d+1) dense blocks, column-major inside a block (HostBsr, host_sparse.h)
 struct BsrDev {
   int nbrows = 0;
   int nblocks = 0;

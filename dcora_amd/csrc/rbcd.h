@@ -2,6 +2,8 @@
 // (replaces Agent::iterate / updateX / getSharedStateDicts / updateNeighborStates, ref src/Agent.cpp:113-152,
 // 535-596, 844-906, 1158-1278, and the loop body of examples/MultiRobotExample.cpp:223-307).
 #pragma once
+#include <chrono>
+#include <functional>
 #include <memory>
 #include <string>
 #include <vector>
@@ -160,7 +162,21 @@ class RbcdSession : public ExchangeSession {
   int update_selected_agent(AgentDev &a, bool restart);
   hipEvent_t fork_ev_ = nullptr;
   int solve_block(AgentDev &a, std::string *err, bool serial = false);
+  // session assembly (rbcd.hip): the host matrices of the hosted agents -- Q[i] = Q_bb, C[i] = coupling block of agent
+  // ids[i] -- as the host builders give them
+  struct MeasSplit;
+  struct Assembly {
+    std::vector<int> ids;
+    std::vector<HostCsr> Q, C;
+  };
+  int assemble(const MeasSplit &split, const std::function<void(size_t, const Assembly &)> &each,
+               const std::function<int(const Assembly &)> &agents_ready,
+               const std::function<int(const HostCsr &)> &central_ready);
+  int attach_preconditioners(const std::vector<HostCsr> &Q, const std::function<int(size_t)> &attach);
+  std::chrono::steady_clock::time_point t0_;  // init began
+  void lap(const char *what) const;
   int rebuild_values(const std::vector<PoseMeas> &meas);
+  int adopt_weights(std::vector<PoseMeas> &meas, bool from_device, bool reset_to_initial);
   int initialize_acceleration();
 };
 

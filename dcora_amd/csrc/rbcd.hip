@@ -41,25 +41,39 @@ static int nesterov_solved(hipStream_t st, DeviceProblem &pb, int mode, double a
   return DCORA_OK;
 }
 
-// a measurement with global pose indices as the agents of the contiguous partition see it: owners and local indices
-static PoseMeas agent_local(const PoseMeas &mi, const Partition &P) {
-  PoseMeas e = mi;
-  e.r1 = P.robot_of(mi.p1);
-  e.r2 = P.robot_of(mi.p2);
-  e.p1 = mi.p1 - P.start(e.r1);
-  e.p2 = mi.p2 - P.start(e.r2);
-  return e;
-}
+namespace {
+constexpr double kPrecondReg = 0.1;  // reg = 1e-1 of the agents' (Q_bb + reg I)^-1, ref src/Graph.cpp:1906
+constexpr int kAgentThreads = 8;     // host threads of the per-agent set-up work, at most
 
-// the pattern (rp, ci) of a matrix: what a robust session's later weights are scattered onto
-static HostCsr pattern_of(const HostCsr &A) {
-  HostCsr p;
-  p.n = A.n;
-  p.ncols = A.ncols;
-  p.rp = A.rp;
-  p.ci = A.ci;
-  return p;
+// the first failing agent's status, its text as the last error
+int first_failure(const std::vector<int> &rcs, const std::vector<std::string> &errs) {
+  for (size_t i = 0; i < rcs.size(); ++i)
+    if (rcs[i]) {
+      set_last_error(errs[i]);
+      return rcs[i];
+    }
+  return DCORA_OK;
 }
+}  // namespace
+
+// Measurements with global pose indices as the host builders take them (the partition, ref
+// examples/MultiRobotExample.cpp:56-118): touching[b], with owners and local indices, is what agent b's Q_bb is built
+// from; global (r1 = r2 = 0) what the coupling blocks and the central Q are built from
+struct RbcdSession::MeasSplit {
+  std::vector<std::vector<PoseMeas>> touching;
+  std::vector<PoseMeas> global;
+  MeasSplit(const std::vector<PoseMeas> &meas, const Partition &P) : touching((size_t)P.R), global(meas) {
+    for (PoseMeas e : meas) {
+      e.r1 = P.robot_of(e.p1);
+      e.r2 = P.robot_of(e.p2);
+      e.p1 -= P.start(e.r1);
+      e.p2 -= P.start(e.r2);
+      touching[(size_t)e.r1].push_back(e);
+      if (e.r2 != e.r1) touching[(size_t)e.r2].push_back(e);
+    }
+    for (PoseMeas &e : global) e.r1 = e.r2 = 0;
+  }
+};
 
 RbcdSession::~RbcdSession() {
   if (eval_host) (void)hipHostFree((void *)eval_host);
@@ -75,7 +89,7 @@ RbcdSession::~RbcdSession() {
 }
 
 int RbcdSession::init(const HostDataset &ds, const dcora_rbcd_options &o) {
-  const auto t0 = std::chrono::steady_clock::now();
+  t0_ = std::chrono::steady_clock::now();
   opt = o;
   d = ds.d;
   n = ds.n;
@@ -132,31 +146,10 @@ int RbcdSession::init(const HostDataset &ds, const dcora_rbcd_options &o) {
   DCORA_HIP(evalbuf.alloc(2 * R + 16));
   DCORA_HIP(hipMemset(evalbuf.p, 0, sizeof(double) * (2 * R + 16)));
 
-  if (env::init_timing())
-    fprintf(stderr, "[session] buffers after %.1f ms\n",
-            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-  // partition (ref examples/MultiRobotExample.cpp:56-118)
-  std::vector<std::vector<PoseMeas>> touching(R);
-  std::vector<std::set<int>> pub(R), nb(R), req(R);
-  for (const PoseMeas &mi : ds.meas) {
-    const PoseMeas e = agent_local(mi, P);
-    touching[e.r1].push_back(e);
-    if (e.r2 != e.r1) {
-      touching[e.r2].push_back(e);
-      pub[e.r1].insert(mi.p1);
-      pub[e.r2].insert(mi.p2);
-      req[e.r1].insert(mi.p2);
-      req[e.r2].insert(mi.p1);
-      nb[e.r1].insert(e.r2);
-      nb[e.r2].insert(e.r1);
-    }
-  }
-  std::vector<PoseMeas> global = ds.meas;
-  for (PoseMeas &e : global) e.r1 = e.r2 = 0;
-
+  lap("buffers");
+  const MeasSplit split(ds.meas, P);
   agents.resize(R);
   std::vector<int> cs(R + 1);
-  std::vector<int> hosted_ids;
   for (int b = 0; b < R; ++b) {
     AgentDev &a = agents[b];
     a.id = b;
@@ -164,16 +157,26 @@ int RbcdSession::init(const HostDataset &ds, const dcora_rbcd_options &o) {
     a.col0 = P.start(b) * dh;
     cs[b] = a.col0;
     a.hosted = (b / ((R + o.world_size - 1) / o.world_size)) == o.rank;  // consecutive agents share a rank
-    a.public_poses.assign(pub[b].begin(), pub[b].end());
-    a.neighbors.assign(nb[b].begin(), nb[b].end());
-    a.required.assign(req[b].begin(), req[b].end());
+    // my public poses, my neighbours and the poses of theirs that I require: the two ends of every measurement of
+    // mine that another agent shares
+    std::set<int> pub, nb, req;
+    for (const PoseMeas &e : split.touching[(size_t)b]) {
+      if (e.r1 == e.r2) continue;
+      const bool first = e.r1 == b;
+      const int other = first ? e.r2 : e.r1;
+      pub.insert(P.start(b) + (first ? e.p1 : e.p2));
+      req.insert(P.start(other) + (first ? e.p2 : e.p1));
+      nb.insert(other);
+    }
+    a.public_poses.assign(pub.begin(), pub.end());
+    a.neighbors.assign(nb.begin(), nb.end());
+    a.required.assign(req.begin(), req.end());
     std::vector<int> cols;
     for (int p : a.public_poses)
       for (int c = 0; c < dh; ++c) cols.push_back(p * dh + c);
     DCORA_HIP(a.public_cols.alloc(std::max<size_t>(cols.size(), 1)));
     if (!cols.empty())
       DCORA_HIP(hipMemcpy(a.public_cols.p, cols.data(), sizeof(int) * cols.size(), hipMemcpyHostToDevice));
-    if (a.hosted) hosted_ids.push_back(b);
   }
   // the pose / column offsets of the agents: uploaded before the builds (a copy queued behind them waited 16 ms)
   cs[R] = dh * n;
@@ -187,104 +190,114 @@ int RbcdSession::init(const HostDataset &ds, const dcora_rbcd_options &o) {
     DCORA_HIP(hipStreamSynchronize(st));
   }
   DCORA_HIP(hipEventCreateWithFlags(&fork_ev_, hipEventDisableTiming));
-  // The hosted agents' problems (Q_bb, its preconditioner: host factorisation + inverse image, coupling block) are
-  // built side by side on host threads: the factorisation of one block is partly serial (the separators above the
-  // sub-trees), so eight blocks of the 100k lattice take 9 s one after the other and 2-3 s together.
-  // Blocks small enough for the dense inverse: all hosted agents' matrices first, their inverses in ONE batch of launches
-  // (five builds on five streams do not overlap: precond_prebuild_dense), then the problems attach to the cached images
-  std::vector<HostCsr> Qbs((size_t)R);
-  if ((long)(n / R + 1) * dh <= kDensePrecondMaxK && hosted_ids.size() > 1) {
-    std::vector<const HostCsr *> ptrs;
-    run_threads((int)hosted_ids.size(), [&](int t) {  // (a matrix takes a millisecond of host work: side by side)
-      const int b = hosted_ids[(size_t)t];
-      Qbs[(size_t)b] = build_Q_pgo(d, agents[b].n, b, touching[b]);
-    });
-    for (int b : hosted_ids) ptrs.push_back(&Qbs[(size_t)b]);
-    const int prc = precond_prebuild_dense(ptrs, 0.1, dh, o.device);
-    if (prc) return prc;
-    if (env::init_timing())
-      fprintf(stderr, "[session] dense inverses prebuilt after %.1f ms\n",
-              std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-  }
-  auto build_agent = [&](int b, std::string *err) -> int {
-    AgentDev &a = agents[b];
-    if (hipSetDevice(o.device) != hipSuccess) return DCORA_ERR_HIP;
-    HostCsr Qb = Qbs[(size_t)b].n > 0 ? std::move(Qbs[(size_t)b]) : build_Q_pgo(d, a.n, b, touching[b]);
-    a.prob.reset(new DeviceProblem);
-    dcora_dims dims{r, d, a.n, 0, 0};
-    int rc = a.prob->init(dims, Qb, nullptr, 0.1, o.device, st);  // reg = 1e-1, ref src/Graph.cpp:1906
-    if (!rc) {
-      HostCsr C = build_coupling_pgo(d, P, b, global);
-      rc = a.coupling.upload(C);
-      if (robust) {
-        robust->Qpat[(size_t)b] = pattern_of(Qb);
-        robust->Cpat[(size_t)b] = pattern_of(C);
-      }
-    }
-    if (!rc) rc = stream_acquire(o.device, &a.own);
-    if (!rc && hipEventCreateWithFlags(&a.done, hipEventDisableTiming) != hipSuccess) rc = DCORA_ERR_HIP;
-    if (rc && err) *err = dcora_last_error();
-    return rc;
-  };
-  // the whole-graph problem of the evaluation (Q of all poses, no preconditioner) depends on none of the agents: its
-  // assembly (0.15 s of one host thread for the 100k lattice) and upload run beside the agents' builds
-  int central_rc = DCORA_OK;
-  std::string central_err;
-  auto build_central = [&]() {
-    if (o.world_size != 1) return;
-    if (hipSetDevice(o.device) != hipSuccess) {
-      central_rc = DCORA_ERR_HIP;
-      central_err = "hipSetDevice failed";
-      return;
-    }
-    HostCsr Qc = build_Q_pgo(d, n, 0, global);
-    central.reset(new DeviceProblem);
-    dcora_dims dims{r, d, n, 0, 0};
-    central_rc = central->init(dims, Qc, nullptr, -1.0, o.device, st);
-    if (central_rc) central_err = dcora_last_error();
-    if (robust) robust->central_pat = pattern_of(Qc);
-  };
-  {
-    const size_t nh = hosted_ids.size();
-    std::vector<int> rcs(nh, DCORA_OK);
-    std::vector<std::string> errs(nh);
-    constexpr bool serial = false;
-    // small blocks build in well under a millisecond of host work each: threads only pay off for large ones
-    if (nh > 1 && !serial && (long)(n / R) * dh >= 1024) {
-      std::atomic<size_t> next(0);
-      auto worker = [&] {
-        for (;;) {
-          const size_t i = next.fetch_add(1);
-          if (i >= nh) break;
-          rcs[i] = build_agent(hosted_ids[i], &errs[i]);
-        }
-      };
-      run_threads((int)std::min<size_t>(nh, 8) + 1, [&](int t) { t == 1 ? build_central() : worker(); });
-    } else {
-      for (size_t i = 0; i < nh; ++i) rcs[i] = build_agent(hosted_ids[i], &errs[i]);
-      build_central();
-    }
-    for (size_t i = 0; i < nh; ++i)
-      if (rcs[i]) {
-        set_last_error(errs[i]);
-        return rcs[i];
-      }
-  }
-  const bool init_timing = env::init_timing();
-  if (init_timing)
-    fprintf(stderr, "[session] agents built after %.1f ms\n",
-            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-  if (central_rc) {
-    set_last_error(central_err);
-    return central_rc;
-  }
-  if (init_timing)
-    fprintf(stderr, "[session] ready after %.1f ms\n",
-            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+  const int rc = assemble(
+      split, nullptr,
+      [&](const Assembly &A) {
+        return attach_preconditioners(A.Q, [&](size_t i) {
+          AgentDev &a = agents[(size_t)A.ids[i]];
+          a.prob.reset(new DeviceProblem);
+          int rca = a.prob->init(dcora_dims{r, d, a.n, 0, 0}, A.Q[i], nullptr, kPrecondReg, o.device, st);
+          if (!rca) rca = a.coupling.upload(A.C[i]);
+          if (!rca && robust) {
+            robust->Qpat[(size_t)a.id] = pattern_of(A.Q[i]);
+            robust->Cpat[(size_t)a.id] = pattern_of(A.C[i]);
+          }
+          if (!rca) rca = stream_acquire(o.device, &a.own);
+          if (!rca && hipEventCreateWithFlags(&a.done, hipEventDisableTiming) != hipSuccess) rca = DCORA_ERR_HIP;
+          return rca;
+        });
+      },
+      [&](const HostCsr &Qc) {  // (the evaluation's problem: Q of all poses, no preconditioner)
+        central.reset(new DeviceProblem);
+        if (robust) robust->central_pat = pattern_of(Qc);
+        return central->init(dcora_dims{r, d, n, 0, 0}, Qc, nullptr, -1.0, o.device, st);
+      });
+  if (rc) return rc;
+  lap("agents built");
+  lap("ready");
   iteration = 0;
   gamma = alpha = 0;
-  setup_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  setup_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0_).count();
   return DCORA_OK;
+}
+
+// "[session] <what> after <ms since init began>" under DCORA_INIT_TIMING; silent once init has set setup_ms
+void RbcdSession::lap(const char *what) const {
+  if (setup_ms == 0 && env::init_timing())
+    fprintf(stderr, "[session] %s after %.1f ms\n", what,
+            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0_).count());
+}
+
+// The one path from a measurement list to the session's host matrices, at creation and on every re-weight: Q_bb and
+// the coupling block of each hosted agent and, in a single-process session, the central Q, all from the host builders.
+// The agents' matrices are built side by side on host threads (a matrix takes a millisecond of host work); each(i, A),
+// if given, runs on the thread that built those of agent A.ids[i], agents_ready(A) once all of them stand.  The
+// whole-graph problem of the evaluation depends on none of the agents: its assembly (0.15 s of one host thread for the
+// 100k lattice) and central_ready(Qc) run on a thread of their own beside all of that.  The agents' status is reported
+// before the central problem's.
+int RbcdSession::assemble(const MeasSplit &split, const std::function<void(size_t, const Assembly &)> &each,
+                          const std::function<int(const Assembly &)> &agents_ready,
+                          const std::function<int(const HostCsr &)> &central_ready) {
+  Assembly A;
+  for (const AgentDev &a : agents)
+    if (a.hosted) A.ids.push_back(a.id);
+  const int nh = (int)A.ids.size();
+  A.Q.resize((size_t)nh);
+  A.C.resize((size_t)nh);
+  int rc = DCORA_OK, central_rc = DCORA_OK;
+  std::string central_err;
+  run_threads(2, [&](int t) {
+    if (t == 0) {
+      parallel_for(nh, kAgentThreads, 1, [&](int i) {
+        const int b = A.ids[(size_t)i];
+        A.Q[(size_t)i] = build_Q_pgo(d, agents[(size_t)b].n, b, split.touching[(size_t)b]);
+        A.C[(size_t)i] = build_coupling_pgo(d, P, b, split.global);
+        if (each) each((size_t)i, A);
+      });
+      rc = agents_ready(A);
+    } else if (opt.world_size == 1) {
+      if (hipSetDevice(opt.device) != hipSuccess) {
+        central_rc = DCORA_ERR_HIP;
+        central_err = "hipSetDevice failed";
+        return;
+      }
+      central_rc = central_ready(build_Q_pgo(d, n, 0, split.global));
+      if (central_rc) central_err = dcora_last_error();
+    }
+  });
+  if (rc) return rc;
+  if (central_rc) set_last_error(central_err);
+  return central_rc;
+}
+
+// The preconditioners of the hosted agents' matrices Q (index i as in Assembly).  Blocks small enough for the dense
+// inverse: all inverses in ONE batch of launches first (five builds on five streams do not overlap), so that the
+// problems attach to the cached images.  Then attach(i) for every agent: DeviceProblem::init at creation,
+// build_preconditioner on a re-weight.  The factorisation of one large block is partly serial (the separators above
+// the sub-trees): eight blocks of the 100k lattice take 9 s one after the other and 2-3 s side by side on host
+// threads; small blocks take well under a millisecond of host work each, where threads do not pay off.
+int RbcdSession::attach_preconditioners(const std::vector<HostCsr> &Q, const std::function<int(size_t)> &attach) {
+  const int nh = (int)Q.size(), dh = d + 1;
+  const bool dense_batch = (long)(n / R + 1) * dh <= kDensePrecondMaxK && nh > 1;
+  const bool threads_pay = (long)(n / R) * dh >= 1024;
+  if (dense_batch) {
+    std::vector<const HostCsr *> ptrs;
+    for (const HostCsr &Qi : Q) ptrs.push_back(&Qi);
+    const int prc = precond_prebuild_dense(ptrs, kPrecondReg, dh, opt.device);
+    if (prc) return prc;
+    lap("dense inverses prebuilt");
+  }
+  std::vector<int> rcs((size_t)nh, DCORA_OK);
+  std::vector<std::string> errs((size_t)nh);
+  parallel_for(nh, threads_pay ? kAgentThreads : 1, 1, [&](int i) {
+    if (hipSetDevice(opt.device) != hipSuccess) {
+      rcs[(size_t)i] = DCORA_ERR_HIP;
+      return;
+    }
+    rcs[(size_t)i] = attach((size_t)i);
+    if (rcs[(size_t)i]) errs[(size_t)i] = dcora_last_error();
+  });
+  return first_failure(rcs, errs);
 }
 
 // Agent::setX + initializeAcceleration for every agent (ref src/Agent.cpp:64-77, 1178-1187)
@@ -408,35 +421,13 @@ int RbcdSession::init_robust(const HostDataset &ds, const dcora_rbcd_options &o,
   return DCORA_OK;
 }
 
-namespace {
-// the values of A on the pattern P (zeros where A has no entry); false when an entry of A lies outside P
-bool scatter_on_pattern(const HostCsr &A, const HostCsr &P, HostCsr *out) {
-  if (A.n != P.n || A.ncols != P.ncols) return false;
-  out->n = P.n;
-  out->ncols = P.ncols;
-  out->rp = P.rp;
-  out->ci = P.ci;
-  out->v.assign(P.ci.size(), 0.0);
-  for (int i = 0; i < A.n; ++i) {
-    int q = P.rp[i];
-    for (int k = A.rp[i]; k < A.rp[i + 1]; ++k) {
-      while (q < P.rp[i + 1] && P.ci[q] < A.ci[k]) ++q;
-      if (q == P.rp[i + 1] || P.ci[q] != A.ci[k]) return false;
-      out->v[q] = A.v[k];
-    }
-  }
-  return true;
-}
-}  // namespace
-
-// Graph::clearDataMatrices + constructDataMatrices with new weights (ref src/Agent.cpp:1416): Q_bb, the coupling
-// blocks and the central Q from the host builders that creation uses, so that every value equals a fresh session's
-// bit for bit; the values land on the creation patterns.  The preconditioners come from, and go into, the cache as at
-// creation: a new image is attached, an image somebody else still holds is never written.  The host work runs side by
-// side as in init: the agents' builds, then their preconditioners, beside the central Q's build.
+// Graph::clearDataMatrices + constructDataMatrices with new weights (ref src/Agent.cpp:1416) through the assembly of
+// creation.  The matrices as the builders give them (no explicit zeros) go to the preconditioners, so the cache sees the
+// keys of a fresh session: a new image is attached, an image somebody else still holds is never written.  Their values
+// scattered onto the creation patterns (a weight of 0 leaves explicit zeros) are what is uploaded.  Together: every
+// value of the re-weighted session equals a fresh session's bit for bit.
 int RbcdSession::rebuild_values(const std::vector<PoseMeas> &meas) {
   RobustSession &rs = *robust;
-  const int dh = d + 1;
   // a pattern holds every entry of its creation weights; only a weight that was 0 then can reach outside it
   for (size_t e = 0; e < meas.size(); ++e)
     if (rs.meas_zero[e] && meas[e].weight != 0.0) {
@@ -444,113 +435,44 @@ int RbcdSession::rebuild_values(const std::vector<PoseMeas> &meas) {
                      "do not hold that measurement)");
       return DCORA_ERR_BAD_ARG;
     }
-  std::vector<std::vector<PoseMeas>> touching(R);
-  for (const PoseMeas &mi : meas) {
-    const PoseMeas e = agent_local(mi, P);
-    touching[e.r1].push_back(e);
-    if (e.r2 != e.r1) touching[e.r2].push_back(e);
-  }
-  std::vector<PoseMeas> global = meas;
-  for (PoseMeas &e : global) e.r1 = e.r2 = 0;
-  std::vector<int> hosted_ids;
-  for (const AgentDev &a : agents)
-    if (a.hosted && a.prob) hosted_ids.push_back(a.id);
-  const size_t nh = hosted_ids.size();
   DCORA_HIP(hipSetDevice(opt.device));
   // nothing of the session is in flight while its matrices and preconditioner images change
   for (const AgentDev &a : agents)
     if (a.own) DCORA_HIP(hipStreamSynchronize(a.own));
   DCORA_HIP(hipStreamSynchronize(st));
+  const char *outside = "rbcd robust: the weights give a matrix entry outside the session's pattern";
+  // host images of the uploads (by agent id), alive until the stream has been synchronised
+  std::vector<HostCsr> Qs((size_t)R), Cs((size_t)R);
+  std::vector<std::vector<double>> stage((size_t)R);
+  std::vector<char> ok((size_t)R, 1);
   HostCsr Qcs;
-  HostBsr cbsr;
-  bool central_ok = true;
-  std::vector<HostCsr> Qn(nh), Qs(nh), Cs(nh);
-  std::vector<HostBsr> bsr(nh);
-  std::vector<char> ok(nh, 0);
-  std::vector<int> rcs(nh, DCORA_OK);
-  std::vector<std::string> errs(nh);
-  // the agents' matrices, their uploads and preconditioners; the central Q is built beside them
-  auto rebuild_agents = [&]() -> int {
-    std::atomic<size_t> next(0);
-    run_threads((int)std::min<size_t>(nh, 8), [&](int) {
-      for (;;) {
-        const size_t i = next.fetch_add(1);
-        if (i >= nh) break;
-        const int b = hosted_ids[i];
-        Qn[i] = build_Q_pgo(d, agents[b].n, b, touching[b]);
-        ok[i] = scatter_on_pattern(Qn[i], rs.Qpat[(size_t)b], &Qs[i]) &&
-                scatter_on_pattern(build_coupling_pgo(d, P, b, global), rs.Cpat[(size_t)b], &Cs[i]);
-        if (ok[i] && agents[b].prob->has_bsr) bsr[i] = bsr_from_csr(Qs[i], dh);
-      }
-    });
-    for (size_t i = 0; i < nh; ++i)
-      if (!ok[i]) {
-        set_last_error("rbcd robust: the weights give a matrix entry outside the session's pattern");
-        return DCORA_ERR_BAD_ARG;
-      }
-    for (size_t i = 0; i < nh; ++i) {
-      AgentDev &a = agents[(size_t)hosted_ids[i]];
-      DeviceProblem &pb = *a.prob;
-      DCORA_HIP(hipMemcpyAsync(pb.Q.v.p, Qs[i].v.data(), sizeof(double) * Qs[i].v.size(), hipMemcpyHostToDevice, st));
-      if (pb.has_bsr)
-        DCORA_HIP(hipMemcpyAsync(pb.Qb.bv.p, bsr[i].bv.data(), sizeof(double) * bsr[i].bv.size(), hipMemcpyHostToDevice, st));
-      if (!Cs[i].v.empty())
-        DCORA_HIP(hipMemcpyAsync(a.coupling.v.p, Cs[i].v.data(), sizeof(double) * Cs[i].v.size(), hipMemcpyHostToDevice, st));
-    }
-    // the preconditioners of the new matrices, as init builds them: the dense batch first, then every problem attaches
-    if ((long)(n / R + 1) * dh <= kDensePrecondMaxK && nh > 1) {
-      std::vector<const HostCsr *> ptrs;
-      for (const HostCsr &Q : Qn) ptrs.push_back(&Q);
-      const int prc = precond_prebuild_dense(ptrs, 0.1, dh, opt.device);
-      if (prc) return prc;
-    }
-    auto attach = [&](size_t i) {
-      if (hipSetDevice(opt.device) != hipSuccess) {
-        rcs[i] = DCORA_ERR_HIP;
-        return;
-      }
-      rcs[i] = agents[(size_t)hosted_ids[i]].prob->build_preconditioner(Qn[i], 0.1);
-      if (rcs[i]) errs[i] = dcora_last_error();
-    };
-    if (nh > 1 && (long)(n / R) * dh >= 1024) {  // (large blocks: host factorisations side by side, as in init)
-      std::atomic<size_t> nxt(0);
-      run_threads((int)std::min<size_t>(nh, 8), [&](int) {
-        for (;;) {
-          const size_t i = nxt.fetch_add(1);
-          if (i >= nh) break;
-          attach(i);
+  std::vector<double> cstage;
+  const int rc = assemble(
+      MeasSplit(meas, P),
+      [&](size_t i, const Assembly &A) {
+        const size_t b = (size_t)A.ids[i];
+        ok[b] = scatter_on_pattern(A.Q[i], rs.Qpat[b], &Qs[b]) && scatter_on_pattern(A.C[i], rs.Cpat[b], &Cs[b]);
+      },
+      [&](const Assembly &A) {
+        if (std::count(ok.begin(), ok.end(), 0)) {
+          set_last_error(outside);
+          return (int)DCORA_ERR_BAD_ARG;
         }
+        return attach_preconditioners(A.Q, [&](size_t i) {
+          const size_t b = (size_t)A.ids[i];
+          int rca = agents[b].prob->set_values(Qs[b], st, &stage[b]);
+          if (!rca) rca = agents[b].coupling.set_values(Cs[b], st);
+          return rca ? rca : agents[b].prob->build_preconditioner(A.Q[i], kPrecondReg);
+        });
+      },
+      [&](const HostCsr &Qc) {
+        if (scatter_on_pattern(Qc, rs.central_pat, &Qcs)) return central->set_values(Qcs, st, &cstage);
+        set_last_error(outside);
+        return (int)DCORA_ERR_BAD_ARG;
       });
-    } else {
-      for (size_t i = 0; i < nh; ++i) attach(i);
-    }
-    for (size_t i = 0; i < nh; ++i)
-      if (rcs[i]) {
-        set_last_error(errs[i]);
-        return rcs[i];
-      }
-    return DCORA_OK;
-  };
-  int rc = DCORA_OK;
-  run_threads(2, [&](int t) {
-    if (t == 0) {
-      rc = rebuild_agents();
-    } else if (central) {
-      central_ok = scatter_on_pattern(build_Q_pgo(d, n, 0, global), rs.central_pat, &Qcs);
-      if (central_ok && central->has_bsr) cbsr = bsr_from_csr(Qcs, dh);
-    }
-  });
+  const hipError_t synced = hipStreamSynchronize(st);  // (also after a failure: copies may be in flight)
   if (rc) return rc;
-  if (!central_ok) {
-    set_last_error("rbcd robust: the weights give a matrix entry outside the session's pattern");
-    return DCORA_ERR_BAD_ARG;
-  }
-  if (central) {
-    DCORA_HIP(hipMemcpyAsync(central->Q.v.p, Qcs.v.data(), sizeof(double) * Qcs.v.size(), hipMemcpyHostToDevice, st));
-    if (central->has_bsr)
-      DCORA_HIP(hipMemcpyAsync(central->Qb.bv.p, cbsr.bv.data(), sizeof(double) * cbsr.bv.size(), hipMemcpyHostToDevice, st));
-  }
-  DCORA_HIP(hipStreamSynchronize(st));
+  DCORA_HIP(synced);
   return DCORA_OK;
 }
 
@@ -608,24 +530,34 @@ int RbcdSession::compute_weights(double *shared_w, std::vector<double> *w, doubl
   return DCORA_OK;
 }
 
-int RbcdSession::apply_weights(const std::vector<double> &w, bool reset_to_initial) {
+// The shared tail of both ways to change weights: the matrices rebuilt for meas (rs.meas with the new weights), the
+// device's weights made the ones the matrices hold -- the old ones after a refusal, the new ones unless the device
+// computed them itself (from_device) --, optionally X back to the last set_X, acceleration re-initialised
+int RbcdSession::adopt_weights(std::vector<PoseMeas> &meas, bool from_device, bool reset_to_initial) {
   RobustSession &rs = *robust;
-  const size_t m = rs.edge_ids.size();
-  std::vector<PoseMeas> meas = rs.meas;
-  for (size_t i = 0; i < m; ++i) meas[(size_t)rs.edge_ids[i]].weight = w[i];
   const int rc = rebuild_values(meas);
-  if (rc) {  // (the device's weights back to the ones the matrices still hold)
+  if (!rc) rs.meas.swap(meas);
+  const size_t m = rs.edge_ids.size();
+  if (m && (rc || !from_device)) {
     std::vector<double> held(m);
     for (size_t i = 0; i < m; ++i) held[i] = rs.meas[(size_t)rs.edge_ids[i]].weight;
-    if (m) DCORA_HIP(hipMemcpy(rs.edges.w.p, held.data(), sizeof(double) * m, hipMemcpyHostToDevice));
-    return rc;
+    DCORA_HIP(hipMemcpy(rs.edges.w.p, held.data(), sizeof(double) * m, hipMemcpyHostToDevice));
   }
-  rs.meas.swap(meas);
-  rs.cost.update();
-  rs.updates++;
+  if (rc) return rc;
   if (reset_to_initial)
     DCORA_HIP(hipMemcpyAsync(Xg.p, rs.X_initial.p, sizeof(double) * (size_t)r * (d + 1) * n, hipMemcpyDeviceToDevice, st));
   return initialize_acceleration();
+}
+
+int RbcdSession::apply_weights(const std::vector<double> &w, bool reset_to_initial) {
+  RobustSession &rs = *robust;
+  std::vector<PoseMeas> meas = rs.meas;
+  for (size_t i = 0; i < rs.edge_ids.size(); ++i) meas[(size_t)rs.edge_ids[i]].weight = w[i];
+  const int rc = adopt_weights(meas, true, reset_to_initial);
+  if (rc) return rc;
+  rs.cost.update();
+  rs.updates++;
+  return DCORA_OK;
 }
 
 int RbcdSession::set_weights(const double *w) {
@@ -638,14 +570,7 @@ int RbcdSession::set_weights(const double *w) {
     }
   std::vector<PoseMeas> meas = rs.meas;
   for (size_t e = 0; e < m; ++e) meas[e].weight = w[e];
-  const int rc = rebuild_values(meas);
-  if (rc) return rc;
-  rs.meas.swap(meas);
-  const size_t me = rs.edge_ids.size();
-  std::vector<double> wl(me);
-  for (size_t i = 0; i < me; ++i) wl[i] = w[rs.edge_ids[i]];
-  if (me) DCORA_HIP(hipMemcpy(rs.edges.w.p, wl.data(), sizeof(double) * me, hipMemcpyHostToDevice));
-  return initialize_acceleration();
+  return adopt_weights(meas, false, false);
 }
 
 int RbcdSession::get_weights(double *w) const {

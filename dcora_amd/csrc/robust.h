@@ -5,13 +5,19 @@
 #include "host_graph.h"
 
 namespace dcora {
+// the measurements of a dataset on the device: p1, p2, R (d*d per edge, column-major), t (d per edge), kappa, tau
+struct EdgeTable {
+  DevBuf<int> dp1, dp2;
+  DevBuf<double> dR, dt, dk, dta;
+  int upload(const HostDataset &ds);
+};
 // the measurement table of a robust RBCD session (rbcd.h), uploaded once at creation, and the weights in dataset order
-struct RobustEdges {
+struct RobustEdges : EdgeTable {
   int m = 0, d = 0;
   bool ranked = false;         // the edges of one rank of a multi-rank session (upload_ranked)
-  DevBuf<int> dp1, dp2, dupd;  // dupd: the weight is rewritten by the update (a loop closure whose weight is not fixed)
+  DevBuf<int> dupd;  // dupd: the weight is rewritten by the update (a loop closure whose weight is not fixed)
   DevBuf<int> down, dgidx;     // ranked: the rank owns the edge (hosts the agent of p1); the edge's dataset index
-  DevBuf<double> dR, dt, dk, dta, w, partials, counts;
+  DevBuf<double> w, partials, counts;
   int upload(const HostDataset &ds, const std::vector<char> &update);
   // the edges ids (dataset order) of ds only; own: one flag per id
   int upload_ranked(const HostDataset &ds, const std::vector<char> &update, const std::vector<int> &ids,

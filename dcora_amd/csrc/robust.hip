@@ -130,44 +130,55 @@ int no_device() {
   return DCORA_OK;
 }
 
+EdgeDev edge_view(const EdgeTable &T) { return EdgeDev{T.dp1.p, T.dp2.p, T.dR.p, T.dt.p, T.dk.p, T.dta.p}; }
+
+template <class T>
+int to_device(const std::vector<T> &h, DevBuf<T> *dev) {
+  DCORA_HIP(dev->alloc(h.size()));
+  DCORA_HIP(hipMemcpy(dev->p, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice));
+  return DCORA_OK;
+}
+
 }  // namespace
+
+// the measurements of ds packed and uploaded: what EdgeDev points into
+int EdgeTable::upload(const HostDataset &ds) {
+  const int d = ds.d;
+  const size_t m = ds.meas.size();
+  std::vector<int> p1(m), p2(m);
+  std::vector<double> R(m * d * d), t(m * d), ka(m), ta(m);
+  for (size_t e = 0; e < m; ++e) {
+    const PoseMeas &q = ds.meas[e];
+    p1[e] = q.p1;
+    p2[e] = q.p2;
+    for (int i = 0; i < d * d; ++i) R[e * d * d + i] = q.R[i];
+    for (int i = 0; i < d; ++i) t[e * d + i] = q.t[i];
+    ka[e] = q.kappa;
+    ta[e] = q.tau;
+  }
+  int rc = to_device(p1, &dp1);
+  if (!rc) rc = to_device(p2, &dp2);
+  if (!rc) rc = to_device(R, &dR);
+  if (!rc) rc = to_device(t, &dt);
+  if (!rc) rc = to_device(ka, &dk);
+  if (!rc) rc = to_device(ta, &dta);
+  return rc;
+}
 
 int RobustEdges::upload(const HostDataset &ds, const std::vector<char> &update) {
   m = (int)ds.meas.size();
   d = ds.d;
   if (m == 0) return DCORA_OK;
-  std::vector<int> p1((size_t)m), p2((size_t)m), up((size_t)m);
-  std::vector<double> R((size_t)m * d * d), t((size_t)m * d), ka((size_t)m), ta((size_t)m), wh((size_t)m);
-  for (int e = 0; e < m; ++e) {
-    const PoseMeas &q = ds.meas[e];
-    p1[e] = q.p1;
-    p2[e] = q.p2;
-    for (int i = 0; i < d * d; ++i) R[(size_t)e * d * d + i] = q.R[i];
-    for (int i = 0; i < d; ++i) t[(size_t)e * d + i] = q.t[i];
-    ka[e] = q.kappa;
-    ta[e] = q.tau;
-    wh[e] = q.weight;
-    up[e] = update[e] ? 1 : 0;
-  }
-  const int grid = (m + kBlock - 1) / kBlock;
-  DCORA_HIP(dp1.alloc(m));
-  DCORA_HIP(dp2.alloc(m));
-  DCORA_HIP(dupd.alloc(m));
-  DCORA_HIP(dR.alloc(R.size()));
-  DCORA_HIP(dt.alloc(t.size()));
-  DCORA_HIP(dk.alloc(m));
-  DCORA_HIP(dta.alloc(m));
-  DCORA_HIP(w.alloc(m));
-  DCORA_HIP(partials.alloc((size_t)grid * 3));
+  std::vector<int> up(update.begin(), update.begin() + m);
+  for (int &u : up) u = u ? 1 : 0;
+  std::vector<double> wh((size_t)m);
+  for (int e = 0; e < m; ++e) wh[(size_t)e] = ds.meas[(size_t)e].weight;
+  int rc = EdgeTable::upload(ds);
+  if (!rc) rc = to_device(up, &dupd);
+  if (!rc) rc = to_device(wh, &w);
+  if (rc) return rc;
+  DCORA_HIP(partials.alloc((size_t)((m + kBlock - 1) / kBlock) * 3));
   DCORA_HIP(counts.alloc(3));
-  DCORA_HIP(hipMemcpy(dp1.p, p1.data(), sizeof(int) * m, hipMemcpyHostToDevice));
-  DCORA_HIP(hipMemcpy(dp2.p, p2.data(), sizeof(int) * m, hipMemcpyHostToDevice));
-  DCORA_HIP(hipMemcpy(dupd.p, up.data(), sizeof(int) * m, hipMemcpyHostToDevice));
-  DCORA_HIP(hipMemcpy(dR.p, R.data(), sizeof(double) * R.size(), hipMemcpyHostToDevice));
-  DCORA_HIP(hipMemcpy(dt.p, t.data(), sizeof(double) * t.size(), hipMemcpyHostToDevice));
-  DCORA_HIP(hipMemcpy(dk.p, ka.data(), sizeof(double) * m, hipMemcpyHostToDevice));
-  DCORA_HIP(hipMemcpy(dta.p, ta.data(), sizeof(double) * m, hipMemcpyHostToDevice));
-  DCORA_HIP(hipMemcpy(w.p, wh.data(), sizeof(double) * m, hipMemcpyHostToDevice));
   return DCORA_OK;
 }
 
@@ -186,18 +197,14 @@ int RobustEdges::upload_ranked(const HostDataset &ds, const std::vector<char> &u
   if (rc) return rc;
   ranked = true;
   if (m == 0) return DCORA_OK;
-  std::vector<int> ow(own.begin(), own.end());
-  DCORA_HIP(down.alloc(m));
-  DCORA_HIP(dgidx.alloc(m));
-  DCORA_HIP(hipMemcpy(down.p, ow.data(), sizeof(int) * m, hipMemcpyHostToDevice));
-  DCORA_HIP(hipMemcpy(dgidx.p, ids.data(), sizeof(int) * m, hipMemcpyHostToDevice));
-  return DCORA_OK;
+  rc = to_device(std::vector<int>(own.begin(), own.end()), &down);
+  return rc ? rc : to_device(ids, &dgidx);
 }
 
 void launch_robust_weights(hipStream_t st, const RobustEdges &T, int r, const double *X, const dcora_robust_params &p,
                            double mu, double *shared_w) {
   if (T.m == 0) return;
-  const EdgeDev E{T.dp1.p, T.dp2.p, T.dR.p, T.dt.p, T.dk.p, T.dta.p};
+  const EdgeDev E = edge_view(T);
   const int grid = (T.m + kBlock - 1) / kBlock;
   const RankedEdges rk{T.down.p, T.dgidx.p, shared_w};
   auto go = [&](auto kernel) {
@@ -224,40 +231,20 @@ int measurement_errors(const HostDataset &ds, int r, const double *X, double *ou
   DCORA_HIP(hipSetDevice(device));
   const int d = ds.d, m = (int)ds.meas.size();
   if (m == 0) return DCORA_OK;
-  std::vector<int> p1((size_t)m), p2((size_t)m);
-  std::vector<double> R((size_t)m * d * d), t((size_t)m * d), ka((size_t)m), ta((size_t)m);
-  for (int e = 0; e < m; ++e) {
-    const PoseMeas &q = ds.meas[e];
+  for (const PoseMeas &q : ds.meas)
     if (q.p1 < 0 || q.p1 >= ds.n || q.p2 < 0 || q.p2 >= ds.n) {
       set_last_error("measurement_errors: pose index out of range");
       return DCORA_ERR_BAD_ARG;
     }
-    p1[e] = q.p1;
-    p2[e] = q.p2;
-    for (int i = 0; i < d * d; ++i) R[(size_t)e * d * d + i] = q.R[i];
-    for (int i = 0; i < d; ++i) t[(size_t)e * d + i] = q.t[i];
-    ka[e] = q.kappa;
-    ta[e] = q.tau;
-  }
-  DevBuf<int> dp1, dp2;
-  DevBuf<double> dR, dt, dk, dta, dX, dout;
+  EdgeTable T;
+  rc = T.upload(ds);
+  if (rc) return rc;
+  DevBuf<double> dX, dout;
   const size_t N = (size_t)r * (d + 1) * ds.n;
-  DCORA_HIP(dp1.alloc(m));
-  DCORA_HIP(dp2.alloc(m));
-  DCORA_HIP(dR.alloc(R.size()));
-  DCORA_HIP(dt.alloc(t.size()));
-  DCORA_HIP(dk.alloc(m));
-  DCORA_HIP(dta.alloc(m));
   DCORA_HIP(dX.alloc(N));
   DCORA_HIP(dout.alloc(m));
-  DCORA_HIP(hipMemcpy(dp1.p, p1.data(), sizeof(int) * m, hipMemcpyHostToDevice));
-  DCORA_HIP(hipMemcpy(dp2.p, p2.data(), sizeof(int) * m, hipMemcpyHostToDevice));
-  DCORA_HIP(hipMemcpy(dR.p, R.data(), sizeof(double) * R.size(), hipMemcpyHostToDevice));
-  DCORA_HIP(hipMemcpy(dt.p, t.data(), sizeof(double) * t.size(), hipMemcpyHostToDevice));
-  DCORA_HIP(hipMemcpy(dk.p, ka.data(), sizeof(double) * m, hipMemcpyHostToDevice));
-  DCORA_HIP(hipMemcpy(dta.p, ta.data(), sizeof(double) * m, hipMemcpyHostToDevice));
   DCORA_HIP(hipMemcpy(dX.p, X, sizeof(double) * N, hipMemcpyHostToDevice));
-  EdgeDev E{dp1.p, dp2.p, dR.p, dt.p, dk.p, dta.p};
+  const EdgeDev E = edge_view(T);
   const int grid = (m + kBlock - 1) / kBlock;
   if (d == 3)
     hipLaunchKernelGGL(k_measurement_errors<3>, dim3(grid), dim3(kBlock), 0, nullptr, r, m, E, dX.p, dout.p);

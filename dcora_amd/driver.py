@@ -116,29 +116,56 @@ def multi_robot_gnc_example(ds, X0, num_robots=5, r=5, robust=None, num_weight_u
     ds.vals[:, -1] (the weights) is updated in place.  Returns X, weights, per-round records."""
     from . import robust as rb
     robust = robust or rb.RobustCostParameters("GNC_TLS")
+    lc = _gnc_mask(ds, num_robots, fixed)
+    w = ds.vals[:, -1]
+    w[lc] = 1.0
+    at = {}  # the iterate between the rounds' sessions
+
+    def run(iters):
+        s = RbcdSession(ds, num_robots=num_robots, r=r, acceleration=acceleration, params=params, device=device)
+        s.set_X(at["X"])
+        out = s.run(max_iters=iters, rgrad_tol=rgrad_tol)
+        at["X"] = s.get_X()
+        s.close()
+        return out
+
+    def reweight(u):
+        e = rb.measurement_errors(ds, at["X"], device=device)
+        w[lc] = rb.robust_weights(np.sqrt(e[lc]), robust, num_updates=u)
+        return int(np.sum(w[lc] > 1 - 1e-8)), int(np.sum(w[lc] < 1e-8))
+
+    return _gnc_loop(ds, lc, X0, num_weight_updates, inner_iters, max_final_iters, set_X=lambda X: at.update(X=X),
+                     run=run, reweight=reweight, read=lambda: (at["X"], w), close=lambda: None)
+
+
+def _gnc_mask(ds, num_robots, fixed):
     lc = loop_closure_mask(ds, num_robots)
     if fixed is not None:
         lc &= ~np.asarray(fixed, bool)
-    w = ds.vals[:, -1]
-    w[lc] = 1.0
-    X = np.asarray(X0, dtype=np.float64)
+    return lc
+
+
+def _counts(c):
+    return c["accepted"], c["rejected"]
+
+
+def _gnc_loop(ds, lc, X0, num_weight_updates, inner_iters, max_final_iters, set_X, run, reweight, read, close):
+    """The one flow of the three GNC drivers: set_X(X0); num_weight_updates rounds of run(inner_iters) -- the record
+    of RbcdSession.run -- then reweight(round) -> (accepted, rejected); run(max_final_iters) with the final weights;
+    read() -> X, weights; close(), whatever happened.  ds.vals[:, -1] receives the weights."""
     rounds = []
-
-    def rbcd(X, iters):
-        s = RbcdSession(ds, num_robots=num_robots, r=r, acceleration=acceleration, params=params, device=device)
-        s.set_X(X)
-        out = s.run(max_iters=iters, rgrad_tol=rgrad_tol)
-        Xn = s.get_X()
-        s.close()
-        return Xn, out
-
-    for u in range(num_weight_updates):
-        X, out = rbcd(X, inner_iters)
-        e = rb.measurement_errors(ds, X, device=device)
-        w[lc] = rb.robust_weights(np.sqrt(e[lc]), robust, num_updates=u)
-        rounds.append({"iterations": int(out["iters"]), "cost_2f": float(out["cost"][-1]),
-                       "accepted": int(np.sum(w[lc] > 1 - 1e-8)), "rejected": int(np.sum(w[lc] < 1e-8))})
-    X, out = rbcd(X, max_final_iters)
+    try:
+        set_X(np.asarray(X0, dtype=np.float64))
+        for u in range(num_weight_updates):
+            out = run(inner_iters)
+            accepted, rejected = reweight(u)
+            rounds.append({"iterations": int(out["iters"]), "cost_2f": float(out["cost"][-1]),
+                           "accepted": accepted, "rejected": rejected})
+        out = run(max_final_iters)
+        X, w = read()
+    finally:
+        close()
+    ds.vals[:, -1] = w
     return {"X": X, "weights": w.copy(), "loop_closures": lc, "rounds": rounds,
             "final": {"iterations": int(out["iters"]), "cost_2f": float(out["cost"][-1]),
                       "gradnorm": float(out["gradnorm"][-1])}}
@@ -154,28 +181,12 @@ def multi_robot_gnc_session(ds, X0, num_robots=5, r=5, robust=None, num_weight_u
 
     ds.vals[:, -1] (the weights) is updated in place.  Returns X, weights, per-round records."""
     from . import robust as rb
-    robust = robust or rb.RobustCostParameters("GNC_TLS")
-    lc = loop_closure_mask(ds, num_robots)
-    if fixed is not None:
-        lc &= ~np.asarray(fixed, bool)
-    rounds = []
     s = RbcdSession(ds, num_robots=num_robots, r=r, acceleration=acceleration, params=params, device=device,
-                    robust=robust, fixed_weight=fixed)
-    try:
-        s.set_X(np.asarray(X0, dtype=np.float64))
-        for _ in range(num_weight_updates):
-            out = s.run(max_iters=inner_iters, rgrad_tol=rgrad_tol)
-            c = s.update_weights()
-            rounds.append({"iterations": int(out["iters"]), "cost_2f": float(out["cost"][-1]),
-                           "accepted": c["accepted"], "rejected": c["rejected"]})
-        out = s.run(max_iters=max_final_iters, rgrad_tol=rgrad_tol)
-        X, w = s.get_X(), s.get_weights()
-    finally:
-        s.close()
-    ds.vals[:, -1] = w
-    return {"X": X, "weights": w.copy(), "loop_closures": lc, "rounds": rounds,
-            "final": {"iterations": int(out["iters"]), "cost_2f": float(out["cost"][-1]),
-                      "gradnorm": float(out["gradnorm"][-1])}}
+                    robust=robust or rb.RobustCostParameters("GNC_TLS"), fixed_weight=fixed)
+    return _gnc_loop(ds, _gnc_mask(ds, num_robots, fixed), X0, num_weight_updates, inner_iters, max_final_iters,
+                     set_X=s.set_X, run=lambda iters: s.run(max_iters=iters, rgrad_tol=rgrad_tol),
+                     reweight=lambda u: _counts(s.update_weights()), read=lambda: (s.get_X(), s.get_weights()),
+                     close=s.close)
 
 
 def exchange_run(ex, max_iters=1000, rgrad_tol=0.1):
@@ -206,30 +217,13 @@ def multi_robot_gnc_ranks(ds, X0, num_robots=5, r=5, robust=None, num_weight_upd
     ds.vals[:, -1] (the weights) is updated in place.  Returns X, weights, per-round records."""
     from . import robust as rb
     from . import robust_ranked_session
-    robust = robust or rb.RobustCostParameters("GNC_TLS")
-    lc = loop_closure_mask(ds, num_robots)
-    if fixed is not None:
-        lc &= ~np.asarray(fixed, bool)
-    rounds = []
-    s, ex = robust_ranked_session(ds, job_name, num_robots=num_robots, r=r, robust=robust, fixed_weight=fixed,
-                                  rank=rank, world_size=world_size, device=device, acceleration=acceleration,
-                                  params=params)
-    try:
-        ex.set_X(np.asarray(X0, dtype=np.float64))
-        for _ in range(num_weight_updates):
-            out = exchange_run(ex, max_iters=inner_iters, rgrad_tol=rgrad_tol)
-            c = ex.update_weights()
-            rounds.append({"iterations": int(out["iters"]), "cost_2f": float(out["cost"][-1]),
-                           "accepted": c["accepted"], "rejected": c["rejected"]})
-        out = exchange_run(ex, max_iters=max_final_iters, rgrad_tol=rgrad_tol)
-        X, w = ex.gather_X(), ex.get_weights()
-    finally:
-        ex.close()
-        s.close()
-    ds.vals[:, -1] = w
-    return {"X": X, "weights": w.copy(), "loop_closures": lc, "rounds": rounds,
-            "final": {"iterations": int(out["iters"]), "cost_2f": float(out["cost"][-1]),
-                      "gradnorm": float(out["gradnorm"][-1])}}
+    s, ex = robust_ranked_session(ds, job_name, num_robots=num_robots, r=r,
+                                  robust=robust or rb.RobustCostParameters("GNC_TLS"), fixed_weight=fixed, rank=rank,
+                                  world_size=world_size, device=device, acceleration=acceleration, params=params)
+    return _gnc_loop(ds, _gnc_mask(ds, num_robots, fixed), X0, num_weight_updates, inner_iters, max_final_iters,
+                     set_X=ex.set_X, run=lambda iters: exchange_run(ex, max_iters=iters, rgrad_tol=rgrad_tol),
+                     reweight=lambda u: _counts(ex.update_weights()), read=lambda: (ex.gather_X(), ex.get_weights()),
+                     close=lambda: (ex.close(), s.close()))
 
 
 def multi_robot_raslam_example(ra, X0, r_min=None, r_max=100, max_iters=1000, rgrad_tol=0.1, min_eig_tol=1e-3,

@@ -54,3 +54,18 @@ def test_host_setup_code_under_asan_ubsan(built, tmp_path):
     resid = [float(x) for x in re.findall(r"resid ([0-9.eE+-]+)", out.stdout)]
     assert len(resid) == 3 and max(resid) < 1e-8, out.stdout
     assert out.stdout.count("ok 1") == 12 and out.stdout.count("differ 0") == 3, out.stdout
+
+
+def test_csr_pattern_helpers_under_asan_ubsan(tmp_path):
+    """pattern_of / scatter_on_pattern, which a robust session's re-weighting stands on: identity on the own pattern,
+    explicit zeros on a wider one, refusal when an entry falls outside the pattern or the shapes differ"""
+    exe = str(tmp_path / "san_host_csr")
+    cmd = ["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+           "-fno-omit-frame-pointer", "-I", os.path.join(ROOT, "dcora_amd", "csrc"), "-I", os.path.join(ROOT, "include"),
+           os.path.join(common.HERE, "cpp", "san_host_csr.cpp")] + SRC + ["-lpthread", "-o", exe]
+    subprocess.run(cmd, check=True, capture_output=True, timeout=600)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=1")
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=env)
+    assert out.returncode == 0, out.stdout + out.stderr[-2000:]
+    assert "runtime error" not in out.stderr and "AddressSanitizer" not in out.stderr, out.stderr[-2000:]
+    assert out.stdout.count("ok ") == 9 and "FAILED" not in out.stdout, out.stdout
