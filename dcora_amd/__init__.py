@@ -171,6 +171,17 @@ class RADataset:
             self.agent_columns[rb] = (tuple(int(x) for x in dims3), own[:ka.value].copy())
         L.dcora_radataset_destroy(h)
 
+    def colours(self):
+        """(colours, number of colours) of the agents -- the robots owning poses, in id order -- as a session of this
+        file will colour them (dcora_radataset_agent_colours: host only, no device needed)"""
+        h = self.handle()
+        try:
+            col, nc = np.zeros(len(self.robots), np.int32), C.c_int()
+            check(capi.lib().dcora_radataset_agent_colours(h, col, C.byref(nc)))
+        finally:
+            capi.lib().dcora_radataset_destroy(h)
+        return col, nc.value
+
     def agent_blocks(self, robot, Q=None):
         """(n_a, l_a, b_a), own columns, Q_aa (Csr, agent ordering), coupling C (scipy k_a x k, global columns):
         the agent's local problem is 1/2 <Q_aa, X_a^T X_a> + <X_a, X_global C^T>"""
@@ -503,6 +514,15 @@ def suboptimality_gap(r, d, n, X, psd, eta, lambda_min=None, l=0, b=0, lambda_bo
     return gap.value, neff.value
 
 
+def _run_coloured(fn, h, max_sweeps, rgrad_tol):
+    """the coloured run loop of a session or an exchange: sweeps of one tick per colour, each followed by an evaluation"""
+    it = C.c_int()
+    cost, gn = np.zeros(max(max_sweeps, 1)), np.zeros(max(max_sweeps, 1))
+    check(fn(h, max_sweeps, rgrad_tol, C.byref(it), cost.ctypes.data_as(C.c_void_p), gn.ctypes.data_as(C.c_void_p)))
+    n = it.value
+    return dict(iters=n, cost=cost[:n], gradnorm=gn[:n])
+
+
 def _rbcd_options(num_robots, r, acceleration, restart_interval, params, rank, world_size, device, stream):
     o = RbcdOptions()
     capi.lib().dcora_rbcd_options_default(C.byref(o))
@@ -602,6 +622,11 @@ class RbcdSession:
                                         gn.ctypes.data_as(C.c_void_p), sel.ctypes.data_as(C.c_void_p)))
         n = it.value
         return dict(iters=n, cost=cost[:n], gradnorm=gn[:n], selected=sel[:n])
+
+    def run_coloured(self, max_sweeps=1000, rgrad_tol=0.1):
+        """sweeps of iterate_set per colour of colours(), each followed by evaluate(), until |rgrad| < rgrad_tol
+        (dcora_rbcd_run_coloured; acceleration off); iters counts sweeps"""
+        return _run_coloured(capi.lib().dcora_rbcd_run_coloured, self.h, max_sweeps, rgrad_tol)
 
     def last_result(self):
         r = ROptResult()
@@ -761,6 +786,10 @@ class Exchange:
         a = np.ascontiguousarray(agents, dtype=np.int32)
         check(capi.lib().dcora_exchange_rbcd_tick(self.h, a, a.size, int(allow_adjacent)))
 
+    def run_coloured(self, max_sweeps=1000, rgrad_tol=0.1):
+        """the sessions' run_coloured across the ranks: tick per colour, then evaluate (dcora_exchange_run_coloured)"""
+        return _run_coloured(capi.lib().dcora_exchange_run_coloured, self.h, max_sweeps, rgrad_tol)
+
     def set_X(self, X):
         check(capi.lib().dcora_exchange_set_X(self.h, F(X)))
 
@@ -884,6 +913,24 @@ class RaRbcdSession:
                                            sel.ctypes.data_as(C.c_void_p)))
         n = it.value
         return dict(iters=n, cost=cost[:n], gradnorm=gn[:n], selected=sel[:n])
+
+    def iterate_set(self, agents, allow_adjacent=False):
+        """the agents of the set update at the same time from one snapshot of the mirror (acceleration off)"""
+        a = np.ascontiguousarray(agents, dtype=np.int32)
+        check(capi.lib().dcora_ra_rbcd_iterate_set(self.h, a, a.size, int(allow_adjacent)))
+
+    def set_acceleration(self, on):
+        check(capi.lib().dcora_ra_rbcd_set_acceleration(self.h, int(bool(on))))
+
+    def colours(self):
+        col, nc = np.zeros(self.R, np.int32), C.c_int()
+        check(capi.lib().dcora_ra_rbcd_agent_colours(self.h, col, C.byref(nc)))
+        return col, nc.value
+
+    def run_coloured(self, max_sweeps=1000, rgrad_tol=0.1):
+        """sweeps of iterate_set per colour of colours(), each followed by evaluate(), until |rgrad| < rgrad_tol
+        (dcora_ra_rbcd_run_coloured); iters counts sweeps"""
+        return _run_coloured(capi.lib().dcora_ra_rbcd_run_coloured, self.h, max_sweeps, rgrad_tol)
 
     def last_result(self):
         r = ROptResult()

@@ -118,6 +118,7 @@ SIGNATURES = {
     "dcora_radataset_odometry_init": (C.c_int, [_vp, C.c_ulonglong, _dp]),
     "dcora_radataset_ownership": (C.c_int, [_vp, _vp, _vp, _vp]),
     "dcora_radataset_agent_columns": (C.c_int, [_vp, C.c_int, _ip, _vp, _PI]),
+    "dcora_radataset_agent_colours": (C.c_int, [_vp, _ip, _PI]),
     "dcora_graph_extract_agent_blocks": (C.c_int, [C.c_int, _ip, _ip, _dp, C.c_int, _ip, C.POINTER(_vp),
                                                    C.POINTER(_vp)]),
     "dcora_radataset_destroy": (C.c_int, [_vp]),
@@ -132,6 +133,7 @@ SIGNATURES = {
     "dcora_rbcd_iterate_set": (C.c_int, [_vp, _ip, C.c_int, C.c_int]),
     "dcora_rbcd_set_acceleration": (C.c_int, [_vp, C.c_int]),
     "dcora_rbcd_agent_colours": (C.c_int, [_vp, _ip, _PI]),
+    "dcora_rbcd_run_coloured": (C.c_int, [_vp, C.c_int, C.c_double, _PI, _vp, _vp]),
     "dcora_rbcd_evaluate": (C.c_int, [_vp, _PD, _PD, _vp, _PI]),
     "dcora_rbcd_agent_iterate": (C.c_int, [_vp, C.c_int, C.c_int]),
     "dcora_rbcd_agent_get_X": (C.c_int, [_vp, C.c_int, _dp]),
@@ -168,6 +170,7 @@ SIGNATURES = {
     "dcora_exchange_evaluate": (C.c_int, [_vp, _PD, _PD, _vp, _PI]),
     "dcora_exchange_rbcd_iterate": (C.c_int, [_vp, C.c_int, _PD, _PD, _vp, _PI]),
     "dcora_exchange_rbcd_tick": (C.c_int, [_vp, _ip, C.c_int, C.c_int]),
+    "dcora_exchange_run_coloured": (C.c_int, [_vp, C.c_int, C.c_double, _PI, _vp, _vp]),
     "dcora_exchange_set_X": (C.c_int, [_vp, _dp]),
     "dcora_exchange_gather_X": (C.c_int, [_vp, _dp]),
     "dcora_exchange_barrier": (C.c_int, [_vp]),
@@ -192,6 +195,10 @@ SIGNATURES = {
     "dcora_ra_rbcd_iterate": (C.c_int, [_vp, C.c_int, _PD, _PD, _vp, _PI]),
     "dcora_ra_rbcd_evaluate": (C.c_int, [_vp, _PD, _PD, _vp, _PI]),
     "dcora_ra_rbcd_run": (C.c_int, [_vp, C.c_int, C.c_double, _PI, _vp, _vp, _vp]),
+    "dcora_ra_rbcd_iterate_set": (C.c_int, [_vp, _ip, C.c_int, C.c_int]),
+    "dcora_ra_rbcd_set_acceleration": (C.c_int, [_vp, C.c_int]),
+    "dcora_ra_rbcd_agent_colours": (C.c_int, [_vp, _ip, _PI]),
+    "dcora_ra_rbcd_run_coloured": (C.c_int, [_vp, C.c_int, C.c_double, _PI, _vp, _vp]),
     "dcora_ra_rbcd_last_result": (C.c_int, [_vp, C.POINTER(ROptResult)]),
     "dcora_problem_time_qapply": (C.c_int, [_vp, C.c_int, _PD, _PD]),
     "dcora_problem_time_qapply_rotating": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int, _PD]),

@@ -115,6 +115,19 @@ int run_passes(Session &s, int max_iters, double rgrad_tol, int *iters_done, dou
   if (iters_done) *iters_done = it;
   return DCORA_OK;
 }
+// dcora_rbcd_run_coloured / dcora_ra_rbcd_run_coloured: sweeps of one tick per colour, each followed by the session's
+// central evaluation (evaluate: that call of the session)
+template <class Session, class Evaluate>
+int run_coloured(Session &s, Evaluate &&evaluate, int max_sweeps, double rgrad_tol, int *sweeps_done,
+                 double *cost2_trace, double *gradnorm_trace) {
+  std::vector<int> colours((size_t)s.R, 0);
+  int nc = 0;
+  const int rc = s.agent_colours(colours.data(), &nc);
+  if (rc) return rc;
+  return run_coloured_sweeps(
+      colours, nc, [&](const int *set, int count) { return s.iterate_set(set, count, 0); }, evaluate, max_sweeps,
+      rgrad_tol, sweeps_done, cost2_trace, gradnorm_trace);
+}
 }  // namespace
 
 extern "C" {
@@ -939,6 +952,17 @@ int dcora_radataset_agent_columns(dcora_radataset_t h, int robot, int *dims3, in
     return DCORA_OK;
   });
 }
+int dcora_radataset_agent_colours(dcora_radataset_t h, int *colours, int *ncolours) {
+  return abi_call({h, colours}, [&] {
+    std::vector<int> robots;
+    std::vector<std::vector<int>> nbr;
+    ra_agent_adjacency(h->ds, &robots, &nbr);
+    const int nc = greedy_agent_colours((int)robots.size(),
+                                        [&](int a) -> const std::vector<int> & { return nbr[(size_t)a]; }, colours);
+    if (ncolours) *ncolours = nc;
+    return DCORA_OK;
+  });
+}
 int dcora_graph_extract_agent_blocks(int k, const int *rp, const int *ci, const double *v, int k_a, const int *own,
                                      dcora_csr_t *Qaa, dcora_csr_t *C) {
   return abi_call({rp, ci, v, own, Qaa, C}, [&]() -> int {
@@ -1087,6 +1111,14 @@ int dcora_rbcd_set_acceleration(dcora_rbcd_t s, int acceleration) {
 }
 int dcora_rbcd_agent_colours(dcora_rbcd_t s, int *colours, int *ncolours) {
   return abi_call({s, colours}, [&] { return s->s.agent_colours(colours, ncolours); });
+}
+int dcora_rbcd_run_coloured(dcora_rbcd_t s, int max_sweeps, double rgrad_tol, int *sweeps_done, double *cost2_trace,
+                            double *gradnorm_trace) {
+  return abi_call({s}, [&] {
+    return run_coloured(
+        s->s, [&](double *c2, double *gn) { return s->s.evaluate_central(c2, gn, nullptr, nullptr); }, max_sweeps,
+        rgrad_tol, sweeps_done, cost2_trace, gradnorm_trace);
+  });
 }
 int dcora_rbcd_evaluate(dcora_rbcd_t s, double *cost2, double *gradnorm, double *block_norms, int *next_selected) {
   return abi_call({s}, [&] { return s->s.evaluate_central(cost2, gradnorm, block_norms, next_selected); });
@@ -1262,6 +1294,12 @@ int dcora_exchange_rbcd_iterate(dcora_exchange_t ex, int selected, double *cost2
 int dcora_exchange_rbcd_tick(dcora_exchange_t ex, const int *set, int count, int allow_adjacent) {
   return abi_call({ex, set}, [&] { return ex->e.rbcd_tick(set, count, allow_adjacent); });
 }
+int dcora_exchange_run_coloured(dcora_exchange_t ex, int max_sweeps, double rgrad_tol, int *sweeps_done,
+                                double *cost2_trace, double *gradnorm_trace) {
+  return abi_call({ex}, [&] {
+    return ex->e.run_coloured(max_sweeps, rgrad_tol, sweeps_done, cost2_trace, gradnorm_trace);
+  });
+}
 int dcora_exchange_set_X(dcora_exchange_t ex, const double *X) {
   return abi_call({ex, X}, [&] { return ex->e.set_X(X); });
 }
@@ -1368,6 +1406,25 @@ int dcora_ra_rbcd_run(dcora_ra_rbcd_t s, int max_iters, double rgrad_tol, int *i
                       double *gradnorm_trace, int *selected_trace) {
   return abi_call({s}, [&] {
     return run_passes(s->s, max_iters, rgrad_tol, iters_done, cost2_trace, gradnorm_trace, selected_trace);
+  });
+}
+int dcora_ra_rbcd_iterate_set(dcora_ra_rbcd_t s, const int *set, int count, int allow_adjacent) {
+  return abi_call({s}, [&] {
+    return count > 0 && !set ? bad("null argument") : s->s.iterate_set(set, count, allow_adjacent);
+  });
+}
+int dcora_ra_rbcd_set_acceleration(dcora_ra_rbcd_t s, int acceleration) {
+  return abi_call({s}, [&] { return s->s.set_acceleration(acceleration != 0); });
+}
+int dcora_ra_rbcd_agent_colours(dcora_ra_rbcd_t s, int *colours, int *ncolours) {
+  return abi_call({s, colours}, [&] { return s->s.agent_colours(colours, ncolours); });
+}
+int dcora_ra_rbcd_run_coloured(dcora_ra_rbcd_t s, int max_sweeps, double rgrad_tol, int *sweeps_done,
+                               double *cost2_trace, double *gradnorm_trace) {
+  return abi_call({s}, [&] {
+    return run_coloured(
+        s->s, [&](double *c2, double *gn) { return s->s.evaluate(c2, gn, nullptr, nullptr); }, max_sweeps, rgrad_tol,
+        sweeps_done, cost2_trace, gradnorm_trace);
   });
 }
 int dcora_ra_rbcd_last_result(dcora_ra_rbcd_t s, dcora_ropt_result *res) {

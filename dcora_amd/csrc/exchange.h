@@ -85,6 +85,8 @@ class Exchange {
   int evaluate(double *cost2, double *gradnorm, double *block_norms, int *next_selected);
   int rbcd_iterate(int selected, double *cost2, double *gradnorm, double *block_norms, int *next_selected);
   int rbcd_tick(const int *set, int count, int allow_adjacent);
+  // coloured sweeps across the ranks (run_coloured_sweeps): rbcd_tick per colour of the greedy colouring, then evaluate
+  int run_coloured(int max_sweeps, double rgrad_tol, int *sweeps_done, double *cost2_trace, double *gradnorm_trace);
   // Robust jobs (the session s was created by init_robust(..., ranked = true) and is the exchange's session):
   // Agent::updateMeasurementWeights of every agent on every rank.  Each rank weights the edges touching its agents from
   // its mirror, the owners store theirs into the weights area, counts are summed over the ranks.

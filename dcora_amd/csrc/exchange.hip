@@ -970,6 +970,17 @@ int Exchange::rbcd_tick(const int *set, int count, int allow_adjacent) {
   return wait(set, count);
 }
 
+int Exchange::run_coloured(int max_sweeps, double rgrad_tol, int *sweeps_done, double *cost2_trace,
+                           double *gradnorm_trace) {
+  std::vector<int> colours((size_t)R_, 0);
+  const int nc = greedy_agent_colours(R_, [&](int a) -> const std::vector<int> & { return *s_->x_agent(a).neighbors; },
+                                      colours.data());
+  return run_coloured_sweeps(
+      colours, nc, [&](const int *set, int count) { return rbcd_tick(set, count, 0); },
+      [&](double *c2, double *gn) { return evaluate(c2, gn, nullptr, nullptr); }, max_sweeps, rgrad_tol, sweeps_done,
+      cost2_trace, gradnorm_trace);
+}
+
 int Exchange::set_X(const double *Xh) {
   int rc = barrier();
   if (rc) return rc;

@@ -38,4 +38,33 @@ class ExchangeSession {
   virtual int x_stage_hosted(double *host_area) = 0;
 };
 
+
+// The coloured run loop of dcora_rbcd_run_coloured / dcora_ra_rbcd_run_coloured / dcora_exchange_run_coloured: a sweep is
+// one tick per colour (tick(set, count): the agents of that colour, in agent order), colours 0, 1, ... in order, followed
+// by one evaluation (evaluate(&cost2, &gradnorm)); it stops after the first sweep whose |rgrad| < rgrad_tol or after
+// max_sweeps.  Exactly the calls a caller of iterate_set / rbcd_tick and evaluate makes (the agents that fire together in
+// the asynchronous mode, ref src/Agent.cpp:650-678, made a schedule).  Trace entry s: the evaluation after sweep s.
+template <class Tick, class Evaluate>
+int run_coloured_sweeps(const std::vector<int> &colours, int ncolours, Tick &&tick, Evaluate &&evaluate, int max_sweeps,
+                        double rgrad_tol, int *sweeps_done, double *cost2_trace, double *gradnorm_trace) {
+  std::vector<std::vector<int>> sets((size_t)ncolours);
+  for (size_t a = 0; a < colours.size(); ++a) sets[(size_t)colours[a]].push_back((int)a);
+  int s = 0;
+  while (s < max_sweeps) {
+    for (const std::vector<int> &set : sets) {
+      const int rc = tick(set.data(), (int)set.size());
+      if (rc) return rc;
+    }
+    double c2 = 0, gn = 0;
+    const int rc = evaluate(&c2, &gn);
+    if (rc) return rc;
+    if (cost2_trace) cost2_trace[s] = c2;
+    if (gradnorm_trace) gradnorm_trace[s] = gn;
+    ++s;
+    if (gn < rgrad_tol) break;
+  }
+  if (sweeps_done) *sweeps_done = s;
+  return 0;
+}
+
 }  // namespace dcora

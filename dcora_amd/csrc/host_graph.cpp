@@ -549,4 +549,45 @@ void extract_agent_blocks(const HostCsr &Q, const std::vector<int> &own, HostCsr
   if (Qaa) *Qaa = csr_from_coo(ka, ka, I1, J1, V1);
   if (C) *C = csr_from_coo(ka, Q.n, I2, J2, V2);
 }
+
+int greedy_agent_colours(int R, const std::function<const std::vector<int> &(int)> &neighbors, int *colours) {
+  int nc = 0;
+  for (int b = 0; b < R; ++b) {
+    int c = 0;
+    for (bool clash = true; clash; c += clash) {
+      clash = false;
+      for (int q : neighbors(b))
+        if (q < b && colours[q] == c) clash = true;
+    }
+    colours[b] = c;
+    nc = std::max(nc, c + 1);
+  }
+  return nc;
+}
+
+void ra_agent_adjacency(const HostRADataset &ds, std::vector<int> *robots, std::vector<std::vector<int>> *neighbors) {
+  std::set<int> with_poses(ds.pose_robot.begin(), ds.pose_robot.end());
+  robots->assign(with_poses.begin(), with_poses.end());
+  std::map<int, int> agent_of;
+  for (size_t i = 0; i < robots->size(); ++i) agent_of[(*robots)[i]] = (int)i;
+  std::vector<std::set<int>> nbr(robots->size());
+  auto join = [&](int robot1, int robot2) {
+    const auto a = agent_of.find(robot1), b = agent_of.find(robot2);
+    if (a == agent_of.end() || b == agent_of.end() || a->second == b->second) return;
+    nbr[(size_t)a->second].insert(b->second);
+    nbr[(size_t)b->second].insert(a->second);
+  };
+  for (const PoseMeas &e : ds.pose_pose) join(ds.pose_robot[(size_t)e.p1], ds.pose_robot[(size_t)e.p2]);
+  for (const PoseLandmarkMeasH &e : ds.pose_landmark) join(ds.pose_robot[(size_t)e.i], ds.landmark_robot[(size_t)e.j]);
+  for (const RangeMeasH &e : ds.ranges) {
+    const int o1 = e.type1 ? ds.landmark_robot[(size_t)e.i] : ds.pose_robot[(size_t)e.i];
+    const int o2 = e.type2 ? ds.landmark_robot[(size_t)e.j] : ds.pose_robot[(size_t)e.j];
+    const int os = ds.sphere_robot[(size_t)e.l];
+    join(o1, o2);
+    join(o1, os);
+    join(o2, os);
+  }
+  neighbors->clear();
+  for (const std::set<int> &s : nbr) neighbors->emplace_back(s.begin(), s.end());
+}
 }  // namespace dcora

@@ -69,6 +69,14 @@ void ra_agent_columns(const HostRADataset &ds, int robot, int dims3[3], std::vec
 // C = Q[own, everything else] with GLOBAL column indices, so that the agent's linear term is G_a = X_global C^T
 // (the same restriction the reference assembles edge by edge, ref src/Graph.cpp:824-1772)
 void extract_agent_blocks(const HostCsr &Q, const std::vector<int> &own, HostCsr *Qaa, HostCsr *C);
+// Greedy colouring of an agent graph in agent order (smallest colour no lower-numbered neighbour holds): the one rule
+// of RbcdSession::agent_colours, RaRbcdSession::agent_colours, the exchange's coloured run and
+// dcora_radataset_agent_colours.  neighbors(a): the agents sharing a measurement with a.  Returns the number of colours.
+int greedy_agent_colours(int R, const std::function<const std::vector<int> &(int)> &neighbors, int *colours);
+// The agents of a range-aided problem (robots owning poses, in id order) and who shares a measurement with whom, from
+// the owners of every measurement's endpoints (a range also reaches its unit sphere).  Owners without poses (the
+// passive map agent) are no agents and are left out.
+void ra_agent_adjacency(const HostRADataset &ds, std::vector<int> *robots, std::vector<std::vector<int>> *neighbors);
 // chordalInitialization (ref src/DCORA_solver.cpp:218-268): T is d x (d+1) n column-major, pose 0 = identity
 // solve(A, block, nrhs, B, X): X = A^-1 B for a sparse SPD A, right-hand sides contiguous per unknown (B[i * nrhs + t]);
 // false when A is not positive definite.  nullptr: sparse Cholesky on the host.  The device variant is

@@ -9,6 +9,7 @@
 // iterate is a mirror that the coupling products (G_a = X_global C_a^T) and the central evaluation read.
 #pragma once
 #include <memory>
+#include <string>
 #include <vector>
 
 #include "device_problem.h"
@@ -30,6 +31,8 @@ struct RaAgentDev {
   DevBuf<int> own;                      // my columns in the global ordering
   DevBuf<double> X, V, Y, XPrev, tmp;   // r x k, my ordering
   double reg = 0;
+  hipStream_t own_st = nullptr;         // stream of my solve when several agents update at once (hosted agents only;
+  hipEvent_t done = nullptr;            // both owned by the session)
 };
 
 class RaRbcdSession : public ExchangeSession {
@@ -55,6 +58,11 @@ class RaRbcdSession : public ExchangeSession {
   int iterate(int selected, double *cost2, double *gradnorm, double *block_norms, int *next_selected);
   int evaluate(double *cost2, double *gradnorm, double *block_norms, int *next_selected);
   int last_result(dcora_ropt_result *res);
+  // simultaneous Agent::iterate(true) of a set of agents from one snapshot of the mirror (as RbcdSession::iterate_set)
+  int iterate_set(const int *set, int count, int allow_adjacent);
+  // greedy colouring of the agent graph: agents of one colour share no measurement
+  int agent_colours(int *colours, int *ncolours) const;
+  int set_acceleration(bool on);
   // the loop body in the phases the exchange interleaves with its posts and waits (one process per GPU)
   int phase_nonselected(int selected);
   int phase_selected(int selected);
@@ -81,7 +89,9 @@ class RaRbcdSession : public ExchangeSession {
   int x_phase_nonselected(int selected) override { return phase_nonselected(selected); }
   int x_phase_selected(int selected) override { return phase_selected(selected); }
   int x_phase_evaluate_dev(double *out_dev) override { return phase_evaluate_dev(out_dev); }
-  int x_iterate_set(const int *, int, int) override;
+  int x_iterate_set(const int *set, int count, int allow_adjacent) override {
+    return iterate_set(set, count, allow_adjacent);
+  }
   int x_set_X(const double *Xh) override { return set_X(Xh); }
   int x_stage_hosted(double *host_area) override;
 
@@ -89,6 +99,8 @@ class RaRbcdSession : public ExchangeSession {
   bool restart_now() const { return opt.acceleration && ((iteration + 1) % opt.restart_interval == 0); }
   int scatter(RaAgentDev &a);  // my X into the global mirror
   int solve(RaAgentDev &a, const double *start, double **result);
+  hipEvent_t fork_ev_ = nullptr;
+  int solve_block(RaAgentDev &a, std::string *err, bool own);
 };
 
 int device_precond_regularization(const HostCsr &Q, int device, double *reg);

@@ -1028,17 +1028,8 @@ int RbcdSession::iterate(int selected, double *cost2, double *gradnorm, double *
 // Greedy colouring in agent order (smallest colour not used by a neighbour).  Agents of one colour share no
 // measurement, so their simultaneous updates equal the same updates done one after the other.
 int RbcdSession::agent_colours(int *colours, int *ncolours) const {
-  int nc = 0;
-  for (int b = 0; b < R; ++b) {
-    int c = 0;
-    for (bool clash = true; clash; c += clash) {
-      clash = false;
-      for (int q : agents[b].neighbors)
-        if (q < b && colours[q] == c) clash = true;
-    }
-    colours[b] = c;
-    nc = std::max(nc, c + 1);
-  }
+  const int nc = greedy_agent_colours(R, [&](int b) -> const std::vector<int> & { return agents[(size_t)b].neighbors; },
+                                      colours);
   if (ncolours) *ncolours = nc;
   return DCORA_OK;
 }

@@ -3,6 +3,8 @@
     for r = r_min, r_min + 1, ...:
         agents at rank r, X = current point                       (:172-217)
         RBCD++ until |rgrad| < tol or max_iters                   (:223-307)   dcora_rbcd_run
+            (mode="coloured": sweeps of simultaneous updates, one tick per colour of the agent graph, non-accelerated --
+             the agents that fire together of src/Agent.cpp:650-678 as a schedule --      dcora_rbcd_run_coloured)
         S = Q - Lambda(X);  fastVerification(S, min_eig_tol)      (:320-334)   dcora_cert_*
         certified: done;  else escapeSaddle into rank r + 1       (:352-366)   dcora_problem_escape_saddle
 
@@ -18,9 +20,12 @@ from . import (QuadraticProblem, RbcdSession, build_Q_pgo, cert_prepare, dual_ce
 
 def multi_robot_example(ds, X0, num_robots=5, r_min=5, r_max=100, max_iters=1000, rgrad_tol=0.1, min_eig_tol=1e-3,
                         gradient_tolerance=1e-6, preconditioned_gradient_tolerance=1e-6, acceleration=True,
-                        params=None, device=0, refine_gap=False):
+                        params=None, device=0, refine_gap=False, mode="rbcd++"):
     """X0: r_min x (d+1) n start point.  Returns a dict: X (final rank x k), rank, certified, theta, per-level
-    records (rank, iterations, cost 2f, gradnorm, seconds of RBCD / certification / escape) and the traces."""
+    records (rank, iterations, cost 2f, gradnorm, seconds of RBCD / certification / escape, mode) and the traces.
+    mode: "rbcd++" (the reference driver's greedy accelerated passes) or "coloured" (each level runs run_coloured on a
+    non-accelerated session: `iterations` counts sweeps, max_iters caps them, `selected` holds -1)."""
+    _check_mode(mode)
     d, n = ds.d, ds.n
     k = (d + 1) * n
     Q = build_Q_pgo(ds)
@@ -40,10 +45,11 @@ def multi_robot_example(ds, X0, num_robots=5, r_min=5, r_max=100, max_iters=1000
             prep = threading.Thread(target=cert_prepare, args=(Q, d, n), kwargs=dict(block=d + 1, device=device),
                                     daemon=True)
             prep.start()
-        s = RbcdSession(ds, num_robots=num_robots, r=r, acceleration=acceleration, params=params, device=device)
+        s = RbcdSession(ds, num_robots=num_robots, r=r, acceleration=acceleration and mode == "rbcd++", params=params,
+                        device=device)
         s.set_X(X)
         t0 = time.perf_counter()
-        out = s.run(max_iters=max_iters, rgrad_tol=rgrad_tol)
+        out = _run_level(s, mode, max_iters, rgrad_tol)
         t1 = time.perf_counter()
         Xopt = s.get_X()
         total += out["iters"]
@@ -59,7 +65,7 @@ def multi_robot_example(ds, X0, num_robots=5, r_min=5, r_max=100, max_iters=1000
         lev = {"rank": r, "iterations": int(out["iters"]), "cost_2f": float(out["cost"][-1]),
                "gradnorm": float(out["gradnorm"][-1]), "setup_s": t0 - ts, "rbcd_s": t1 - t0,
                "certification_s": t2 - t1,
-               "certified": bool(psd), "theta": float(theta)}
+               "certified": bool(psd), "theta": float(theta), "mode": mode}
         # bound on f(X) - f* implied by the certificate (this library's addition, include/dcora_hip.h)
         lev["suboptimality_gap_f"], lev["n_eff"] = suboptimality_gap(r, d, n, Xopt, psd, min_eig_tol, lmin)
         if psd and refine_gap:  # a verified lower bound of lambda_min(S) instead of the -eta the test guarantees
@@ -90,6 +96,20 @@ def multi_robot_example(ds, X0, num_robots=5, r_min=5, r_max=100, max_iters=1000
     return {"X": X, "rank": X.shape[0], "certified": certified, "theta": float(theta), "total_iters": int(total),
             "suboptimality_gap_f": levels[-1]["suboptimality_gap_f"] if levels else None, "levels": levels, "cost": cat(cost, float), "gradnorm": cat(gradnorm, float),
             "selected": cat(selected, np.int32), "rank_trace": cat(rank, np.int32)}
+
+
+def _check_mode(mode):
+    if mode not in ("rbcd++", "coloured"):
+        raise ValueError('mode must be "rbcd++" or "coloured"')
+
+
+def _run_level(s, mode, max_iters, rgrad_tol):
+    """one level's loop on a session of either kind -> the record of its run()"""
+    if mode == "rbcd++":
+        return s.run(max_iters=max_iters, rgrad_tol=rgrad_tol)
+    out = s.run_coloured(max_sweeps=max_iters, rgrad_tol=rgrad_tol)
+    out["selected"] = np.full(out["iters"], -1, np.int32)
+    return out
 
 
 def loop_closure_mask(ds, num_robots):
@@ -228,12 +248,13 @@ def multi_robot_gnc_ranks(ds, X0, num_robots=5, r=5, robust=None, num_weight_upd
 
 def multi_robot_raslam_example(ra, X0, r_min=None, r_max=100, max_iters=1000, rgrad_tol=0.1, min_eig_tol=1e-3,
                                gradient_tolerance=1e-4, preconditioned_gradient_tolerance=1e-4, acceleration=True,
-                               params=None, device=0):
+                               params=None, device=0, mode="rbcd++"):
     """The multi-robot range-aided SLAM driver (ref examples/MultiRobotExample_RASLAM.cpp) over the C ABI: per level
     the agents' RBCD++ (dcora_ra_rbcd_*), the merged problem's dual certificate and fastVerification, escapeSaddle of
     the central problem into the next rank.  Defaults of the example: r_min = d, local RTR 200 x 200 at 1e-4,
-    |rgrad| < 0.1, eigenvalue tolerance 1e-3.  X0: r_min x k (RA ordering)."""
+    |rgrad| < 0.1, eigenvalue tolerance 1e-3.  X0: r_min x k (RA ordering).  mode: as multi_robot_example."""
     from . import RaRbcdSession, ROptParameters, precond_regularization
+    _check_mode(mode)
     d, n, l, b, k = ra.d, ra.n, ra.l, ra.b, ra.k
     r_min = d if r_min is None else r_min
     if params is None:
@@ -246,10 +267,10 @@ def multi_robot_raslam_example(ra, X0, r_min=None, r_max=100, max_iters=1000, rg
     r = r_min
     while r < r_max:
         ts = time.perf_counter()
-        s = RaRbcdSession(ra, r, acceleration=acceleration, params=params, device=device)
+        s = RaRbcdSession(ra, r, acceleration=acceleration and mode == "rbcd++", params=params, device=device)
         s.set_X(X)
         t0 = time.perf_counter()
-        out = s.run(max_iters=max_iters, rgrad_tol=rgrad_tol)
+        out = _run_level(s, mode, max_iters, rgrad_tol)
         t1 = time.perf_counter()
         Xopt = s.get_X()
         s.close()
@@ -260,7 +281,7 @@ def multi_robot_raslam_example(ra, X0, r_min=None, r_max=100, max_iters=1000, rg
         lev = {"rank": r, "iterations": int(out["iters"]), "cost_2f": float(out["cost"][-1]),
                "gradnorm": float(out["gradnorm"][-1]), "setup_s": t0 - ts, "rbcd_s": t1 - t0,
                "certification_s": t2 - t1,
-               "certified": bool(psd), "theta": float(theta)}
+               "certified": bool(psd), "theta": float(theta), "mode": mode}
         levels.append(lev)
         X = Xopt
         if psd:

@@ -3,10 +3,13 @@
 // numerical step runs on the MI355X:
 //
 //   multi-robot-example <num_robots> <file.g2o> [--rank r_min] [--iters N] [--rgrad-tol t] [--out trajectory.txt]
+//                       [--coloured]
 //
 //   for r = r_min, r_min + 1, ...                                              reference lines
 //     agents at rank r (one RBCD session), X = current point                   :172-217
 //     RBCD++ with greedy block selection until |rgrad| < tol or N iterations   :223-307   dcora_rbcd_iterate
+//       (--coloured: non-accelerated sweeps of simultaneous updates, one tick per colour of the agent graph -- the
+//        agents that fire together of src/Agent.cpp:650-678 as a schedule; N caps the sweeps)   dcora_rbcd_run_coloured
 //     S = Q - Lambda(X); fastVerification(S, 1e-3)                             :320-334   dcora_cert_*
 //     certified: suboptimality gap, rounding in the frame of pose 0, done      :336-350   dcora_round_align_trajectory
 //     else escapeSaddle into rank r + 1                                        :352-366   dcora_problem_escape_saddle
@@ -34,7 +37,7 @@ double now_ms() {
 
 int main(int argc, char **argv) {
   if (argc < 3) {
-    std::printf("usage: %s num_robots file.g2o [--rank r_min] [--iters N] [--rgrad-tol t] [--out file] [--quiet]\n", argv[0]);
+    std::printf("usage: %s num_robots file.g2o [--rank r_min] [--iters N] [--rgrad-tol t] [--out file] [--quiet] [--coloured]\n", argv[0]);
     return 1;
   }
   const unsigned num_robots = (unsigned)std::atoi(argv[1]);
@@ -43,13 +46,14 @@ int main(int argc, char **argv) {
   double RGradNormTol = 0.1;
   const double min_eig_num_tol = 1e-3, gradient_tolerance = 1e-6, preconditioned_gradient_tolerance = 1e-6;
   const char *out_path = nullptr;
-  bool quiet = false;
+  bool quiet = false, coloured = false;
   for (int i = 3; i < argc; ++i) {
     if (!std::strcmp(argv[i], "--rank") && i + 1 < argc) r_min = (unsigned)std::atoi(argv[++i]);
     else if (!std::strcmp(argv[i], "--iters") && i + 1 < argc) numIters = (unsigned)std::atoi(argv[++i]);
     else if (!std::strcmp(argv[i], "--rgrad-tol") && i + 1 < argc) RGradNormTol = std::atof(argv[++i]);
     else if (!std::strcmp(argv[i], "--out") && i + 1 < argc) out_path = argv[++i];
     else if (!std::strcmp(argv[i], "--quiet")) quiet = true;
+    else if (!std::strcmp(argv[i], "--coloured")) coloured = true;
   }
   if (dcora_device_count() < 1) {
     std::printf("no GPU: libdcora_hip has no CPU fallback\n");
@@ -102,13 +106,25 @@ int main(int argc, char **argv) {
       ++levels;
       double t0 = now_ms();
       DCORA::AgentParameters options((unsigned)d, r, num_robots);
-      options.acceleration = true;
+      options.acceleration = !coloured;
       auto team = DCORA::AgentTeam::create(ds, options);
       DCORA::check_status(dcora_rbcd_set_X(team->session(), Xcurr.data()), "setX");
       setup_ms += now_ms() - t0;
       t0 = now_ms();
       int selectedRobot = 0;
-      for (unsigned iter = 0; iter < numIters; ++iter) {
+      if (coloured) {
+        std::vector<double> c2((size_t)numIters + 1), gn((size_t)numIters + 1);
+        int sweeps = 0;
+        DCORA::check_status(dcora_rbcd_run_coloured(team->session(), (int)numIters, RGradNormTol, &sweeps, c2.data(), gn.data()),
+                            "run_coloured");
+        for (int q = 0; q < sweeps; ++q, ++totalIter)
+          if (!quiet) std::printf("Sweep = %u | cost = %.5f | gradnorm = %.5f\n", totalIter, c2[(size_t)q], gn[(size_t)q]);
+        if (sweeps > 0) {
+          cost2 = c2[(size_t)sweeps - 1];
+          gradnorm = gn[(size_t)sweeps - 1];
+        }
+      }
+      for (unsigned iter = 0; !coloured && iter < numIters; ++iter) {
         int next = selectedRobot;
         DCORA::check_status(dcora_rbcd_iterate(team->session(), selectedRobot, &cost2, &gradnorm, nullptr, &next), "iterate");
         if (!quiet)

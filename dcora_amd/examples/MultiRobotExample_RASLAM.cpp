@@ -3,11 +3,14 @@
 // Matrix-level functions -- host code stays C++, every numerical step runs on the MI355X:
 //
 //   multi-robot-example-raslam <file.pyfg> [--rank r_min] [--iters N] [--rgrad-tol t] [--seed s] [--quiet]
+//                              [--coloured]
 //
 //   X = odometry start of the CORA driver at rank d (examples/SingleRobotExample_RASLAM.cpp:92-150), lifted to r_min
 //   for r = r_min, r_min + 1, ...
 //     agents at rank r: one per robot of the file, each on its own poses, unit spheres and landmarks     dcora_ra_rbcd_create
 //     RBCD++ with greedy block selection until |rgrad| < tol or N iterations                             dcora_ra_rbcd_iterate
+//       (--coloured: non-accelerated sweeps of simultaneous updates, one tick per colour of the agent graph -- the agents
+//        that fire together of src/Agent.cpp:650-678 as a schedule; N caps the sweeps)                   dcora_ra_rbcd_run_coloured
 //     S = Q - Lambda(X) of the merged problem; fastVerification(S, 1e-3)                                 dcora_cert_*
 //     certified: done;  else escapeSaddle of the central problem into rank r + 1                         dcora_problem_escape_saddle
 //
@@ -31,7 +34,7 @@ double now_ms() {
 
 int main(int argc, char **argv) {
   if (argc < 2) {
-    std::printf("usage: %s file.pyfg [--rank r_min] [--iters N] [--rgrad-tol t] [--seed s] [--quiet]\n", argv[0]);
+    std::printf("usage: %s file.pyfg [--rank r_min] [--iters N] [--rgrad-tol t] [--seed s] [--quiet] [--coloured]\n", argv[0]);
     return 1;
   }
   const char *path = argv[1];
@@ -39,13 +42,14 @@ int main(int argc, char **argv) {
   unsigned long long seed = 20250310ull;
   double RGradNormTol = 0.1;
   const double min_eig_num_tol = 1e-3, gradient_tolerance = 1e-4, preconditioned_gradient_tolerance = 1e-4;
-  bool quiet = false;
+  bool quiet = false, coloured = false;
   for (int i = 2; i < argc; ++i) {
     if (!std::strcmp(argv[i], "--rank") && i + 1 < argc) r_min = std::atoi(argv[++i]);
     else if (!std::strcmp(argv[i], "--iters") && i + 1 < argc) numIters = std::atoi(argv[++i]);
     else if (!std::strcmp(argv[i], "--rgrad-tol") && i + 1 < argc) RGradNormTol = std::atof(argv[++i]);
     else if (!std::strcmp(argv[i], "--seed") && i + 1 < argc) seed = std::strtoull(argv[++i], nullptr, 10);
     else if (!std::strcmp(argv[i], "--quiet")) quiet = true;
+    else if (!std::strcmp(argv[i], "--coloured")) coloured = true;
   }
   if (dcora_device_count() < 1) {
     std::printf("no GPU: libdcora_hip has no CPU fallback\n");
@@ -85,7 +89,7 @@ int main(int argc, char **argv) {
       dcora_rbcd_options opt;
       dcora_rbcd_options_default(&opt);
       opt.r = r;
-      opt.acceleration = 1;
+      opt.acceleration = coloured ? 0 : 1;
       opt.local.RTR_iterations = 200;        // the example's local solver: RTR 200 x 200 at 1e-4
       opt.local.RTR_tCG_iterations = 200;
       opt.local.gradnorm_tol = 1e-4;
@@ -96,7 +100,18 @@ int main(int argc, char **argv) {
       setup_ms += now_ms() - t0;
       t0 = now_ms();
       int selected = 0;
-      for (int iter = 0; iter < numIters; ++iter) {
+      if (coloured) {
+        std::vector<double> c2((size_t)numIters + 1), gn((size_t)numIters + 1);
+        int sweeps = 0;
+        DCORA::check_status(dcora_ra_rbcd_run_coloured(s, numIters, RGradNormTol, &sweeps, c2.data(), gn.data()), "run_coloured");
+        for (int q = 0; q < sweeps; ++q, ++totalIter)
+          if (!quiet) std::printf("Sweep = %d | cost = %.5f | gradnorm = %.5f\n", totalIter, c2[(size_t)q], gn[(size_t)q]);
+        if (sweeps > 0) {
+          cost2 = c2[(size_t)sweeps - 1];
+          gradnorm = gn[(size_t)sweeps - 1];
+        }
+      }
+      for (int iter = 0; !coloured && iter < numIters; ++iter) {
         int next = selected;
         DCORA::check_status(dcora_ra_rbcd_iterate(s, selected, &cost2, &gradnorm, nullptr, &next), "iterate");
         if (!quiet)

@@ -260,6 +260,11 @@ int dcora_radataset_ownership(dcora_radataset_t ds, int *pose_robot, int *sphere
 /* Columns of the global RA ordering owned by `robot`, listed in that agent's own RA ordering
  * [rotations | unit spheres | translations | landmarks]; dims3 = {n_a, l_a, b_a}; own (k entries of room) may be NULL */
 int dcora_radataset_agent_columns(dcora_radataset_t ds, int robot, int *dims3, int *own, int *k_a);
+/* Host only: the colours dcora_ra_rbcd_agent_colours will give, before any session exists (a driver plans its ranks
+ * and its ticks with them; the agents that may fire together, ref src/Agent.cpp:650-678).  Agents = the robots that own
+ * poses, in id order; two are adjacent when a measurement has endpoints (or, for a range, its unit sphere) owned by
+ * both; greedy in agent order: the smallest colour no lower-numbered neighbour holds.  colours: one int per agent. */
+int dcora_radataset_agent_colours(dcora_radataset_t ds, int *colours, int *ncolours);
 /* An agent's share of a global quadratic form Q (k x k): Qaa = Q[own, own] in the agent's ordering and the coupling
  * C = Q[own, rest] (k_a x k, GLOBAL column indices), so that the agent's linear term is G_a = X_global C^T -- the
  * restriction the reference assembles measurement by measurement (ref src/Graph.cpp:824-1772) */
@@ -317,6 +322,14 @@ int dcora_rbcd_iterate_set(dcora_rbcd_t s, const int *set, int count, int allow_
 int dcora_rbcd_set_acceleration(dcora_rbcd_t s, int acceleration);
 /* greedy colouring of the agent graph (agents adjacent when they share a measurement): colours[num_robots] */
 int dcora_rbcd_agent_colours(dcora_rbcd_t s, int *colours, int *ncolours);
+/* The coloured run loop (the schedule this library gives the agents that fire together in the asynchronous mode, ref
+ * src/Agent.cpp:650-678): a sweep is one dcora_rbcd_iterate_set per colour of dcora_rbcd_agent_colours, colours 0, 1, ...
+ * in order, followed by one dcora_rbcd_evaluate; it stops after the first sweep whose |rgrad| < rgrad_tol, at most
+ * max_sweeps.  Exactly the calls a caller's own loop makes, so traces and X are the same bits.  Trace entry s (arrays
+ * of max_sweeps doubles, may be NULL) is the evaluation after sweep s.  Needs acceleration off, as a tick does;
+ * world_size 1 (ranks: dcora_exchange_run_coloured). */
+int dcora_rbcd_run_coloured(dcora_rbcd_t s, int max_sweeps, double rgrad_tol, int *sweeps_done, double *cost2_trace,
+                            double *gradnorm_trace);
 /* the central evaluation of dcora_rbcd_iterate alone (ref examples/MultiRobotExample.cpp:264-305); world_size 1 */
 int dcora_rbcd_evaluate(dcora_rbcd_t s, double *cost2, double *gradnorm, double *block_norms, int *next_selected);
 /* Agent::iterate(doOptimization) of ONE agent (ref src/Agent.cpp:535-596), for callers that keep the reference's
@@ -412,6 +425,11 @@ int dcora_exchange_rbcd_iterate(dcora_exchange_t ex, int selected, double *cost2
                                 double *block_norms, int *next_selected);
 /* dcora_rbcd_iterate_set across the ranks, followed by post + wait of the updated agents */
 int dcora_exchange_rbcd_tick(dcora_exchange_t ex, const int *set, int count, int allow_adjacent);
+/* dcora_rbcd_run_coloured / dcora_ra_rbcd_run_coloured across the ranks (ref src/Agent.cpp:650-678): per sweep one
+ * dcora_exchange_rbcd_tick per colour of the greedy colouring (every rank computes the same one from the agents'
+ * neighbour lists), then dcora_exchange_evaluate.  SPMD; sweeps_done and the traces are identical on every rank. */
+int dcora_exchange_run_coloured(dcora_exchange_t ex, int max_sweeps, double rgrad_tol, int *sweeps_done,
+                                double *cost2_trace, double *gradnorm_trace);
 /* dcora_rbcd_set_X on every rank between two barriers; dcora_rbcd_get_X of the whole X assembled from the ranks that
  * host each block (collective; X is valid on every rank) */
 int dcora_exchange_set_X(dcora_exchange_t ex, const double *X);
@@ -461,9 +479,9 @@ int dcora_ra_rbcd_create(dcora_radataset_t ds, const dcora_rbcd_options *opt, dc
 /* the same exchange for the agents of a multi-robot range-aided SLAM problem (ref examples/MultiRobotExample_RASLAM.cpp;
  * ownership by robot symbol, src/DCORA_utils.cpp:1370-1512): the session was created by dcora_ra_rbcd_create with
  * rank / world_size (agent i on rank i / ceil(R / world_size)); an agent's public variables are its poses, unit spheres
- * and landmarks that other agents' measurements reach.  dcora_exchange_set_X / _rbcd_iterate / _evaluate / _gather_X /
- * _post / _wait / _all_ready work as for pose graphs; _rbcd_tick and _certify are pose-graph calls (the range-aided
- * certificate is assembled from the gathered X: dcora_cert_dual_matrix + dcora_cert_fast_verification). */
+ * and landmarks that other agents' measurements reach.  Every dcora_exchange_* call but the weight updates of robust
+ * jobs works as for pose graphs: _set_X / _rbcd_iterate / _rbcd_tick / _run_coloured / _evaluate / _gather_X / _post /
+ * _wait / _all_ready / _certify (k = the merged problem's columns, Q = dcora_radataset_build_Q on rank 0). */
 int dcora_exchange_create_ra(dcora_ra_rbcd_t s, const char *job_name, dcora_exchange_t *out);
 int dcora_ra_rbcd_destroy(dcora_ra_rbcd_t s);
 /* number of agents and (robots != NULL) their robot ids ('A' = 0, ...) */
@@ -478,6 +496,17 @@ int dcora_ra_rbcd_evaluate(dcora_ra_rbcd_t s, double *cost2, double *gradnorm, d
 int dcora_ra_rbcd_run(dcora_ra_rbcd_t s, int max_iters, double rgrad_tol, int *iters_done, double *cost2_trace,
                       double *gradnorm_trace, int *selected_trace);
 int dcora_ra_rbcd_last_result(dcora_ra_rbcd_t s, dcora_ropt_result *res);
+/* as dcora_rbcd_iterate_set / _set_acceleration / _agent_colours / _run_coloured (agents that fire together, ref
+ * src/Agent.cpp:650-678; acceleration off as there, :651-653): every agent of the set reads its linear term, its start
+ * point and its XPrev from the mirror as it stood when the tick began, each hosted one solves on a HIP stream of its
+ * own, and no block returns to the mirror before all are staged.  Agents that share a measurement are refused unless
+ * allow_adjacent != 0; a colour of dcora_ra_rbcd_agent_colours ticks to the same result as dcora_ra_rbcd_iterate of
+ * its agents one after the other. */
+int dcora_ra_rbcd_iterate_set(dcora_ra_rbcd_t s, const int *set, int count, int allow_adjacent);
+int dcora_ra_rbcd_set_acceleration(dcora_ra_rbcd_t s, int acceleration);
+int dcora_ra_rbcd_agent_colours(dcora_ra_rbcd_t s, int *colours, int *ncolours);
+int dcora_ra_rbcd_run_coloured(dcora_ra_rbcd_t s, int max_sweeps, double rgrad_tol, int *sweeps_done,
+                               double *cost2_trace, double *gradnorm_trace);
 
 /* ------------------------------------------------------------------------- *
  * Robust estimation (replaces src/DCORA_robust.cpp and the robust parts of src/DCORA_solver.cpp)
