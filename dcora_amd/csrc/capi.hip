@@ -117,8 +117,8 @@ int run_passes(Session &s, int max_iters, double rgrad_tol, int *iters_done, dou
 }
 // dcora_rbcd_run_coloured / dcora_ra_rbcd_run_coloured: sweeps of one tick per colour, each followed by the session's
 // central evaluation (evaluate: that call of the session)
-template <class Session, class Evaluate>
-int run_coloured(Session &s, Evaluate &&evaluate, int max_sweeps, double rgrad_tol, int *sweeps_done,
+template <class Evaluate>
+int run_coloured(SessionCore &s, Evaluate &&evaluate, int max_sweeps, double rgrad_tol, int *sweeps_done,
                  double *cost2_trace, double *gradnorm_trace) {
   std::vector<int> colours((size_t)s.R, 0);
   int nc = 0;

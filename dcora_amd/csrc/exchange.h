@@ -67,7 +67,7 @@ class Exchange {
  public:
   ~Exchange();
   // weights: doubles of the segment's weights area (the m weights of a robust job, dcora_rbcd_create_robust_ranks)
-  int init(ExchangeSession *s, const char *job_name, size_t weights = 0);
+  int init(SessionCore *s, const char *job_name, size_t weights = 0);
   int post(const int *agents, int count);
   int wait(const int *agents, int count);
   int post_arr(const int *agents, int count, int r, const double *arr);
@@ -118,7 +118,7 @@ class Exchange {
   int num_peers() const;
 
  private:
-  ExchangeSession *s_ = nullptr;
+  SessionCore *s_ = nullptr;
   std::string name_;
   void *map_ = nullptr;
   size_t map_bytes_ = 0;

@@ -238,7 +238,7 @@ int Exchange::num_peers() const {
 }
 
 Exchange::~Exchange() {
-  if (s_) (void)hipSetDevice(s_->x_device());
+  if (s_) (void)hipSetDevice(s_->opt.device);
   for (int q = 0; q < kMaxRanks; ++q)
     if (opened_[q] && peer_halo_[q]) (void)hipIpcCloseMemHandle(peer_halo_[q]);
   if (registered_ && map_) (void)hipHostUnregister(map_);
@@ -413,34 +413,34 @@ int Exchange::barrier(double timeout_s) {
   return DCORA_OK;
 }
 
-int Exchange::init(ExchangeSession *s, const char *job_name, size_t weights) {
+int Exchange::init(SessionCore *s, const char *job_name, size_t weights) {
   s_ = s;
-  rank = s->x_rank();
-  world = s->x_world();
-  R_ = s->x_num_agents();
+  rank = s->opt.rank;
+  world = s->opt.world_size;
+  R_ = s->R;
   const int R = R_;
   if (world > kMaxRanks) return fail("too many ranks", DCORA_ERR_UNSUPPORTED);
   if (!job_name || !*job_name) return fail("empty job name", DCORA_ERR_BAD_ARG);
-  DCORA_HIP(hipSetDevice(s->x_device()));
+  DCORA_HIP(hipSetDevice(s->opt.device));
   const int per = (R + world - 1) / world;
   owner_.resize(R);
   size_t maxcols = 1;
   std::vector<int> hosted;
   for (int a = 0; a < R; ++a) {
-    const XAgentView v = s->x_agent(a);
+    const AgentCore &v = s->agent_core(a);
     owner_[a] = a / per;
-    maxcols = std::max(maxcols, (size_t)v.ncols);
+    maxcols = std::max(maxcols, (size_t)v.n_public_cols);
     if (v.hosted) hosted.push_back(a);
     if (v.hosted != (owner_[a] == rank)) return fail("agent-to-rank map out of step with the session", DCORA_ERR_BAD_ARG);
   }
   n_hosted_ = (int)hosted.size();
-  slot_ = align_up(maxcols * (size_t)s->x_rank_r(), 16);
+  slot_ = align_up(maxcols * (size_t)s->r, 16);
   dests_.assign(R, {});
   needed_.assign(R, 0);
   for (int a = 0; a < R; ++a) {
-    const XAgentView va = s->x_agent(a);
-    for (int q : *va.neighbors) {
-      const XAgentView vq = s->x_agent(q);
+    const AgentCore &va = s->agent_core(a);
+    for (int q : va.neighbors) {
+      const AgentCore &vq = s->agent_core(q);
       if (va.hosted && owner_[q] != rank && std::find(dests_[a].begin(), dests_[a].end(), owner_[q]) == dests_[a].end())
         dests_[a].push_back(owner_[q]);
       if (!va.hosted && vq.hosted) needed_[a] = 1;
@@ -450,7 +450,7 @@ int Exchange::init(ExchangeSession *s, const char *job_name, size_t weights) {
     if ((int)dests_[a].size() > kMaxDst) return fail("an agent has neighbours on more than 8 other ranks", DCORA_ERR_UNSUPPORTED);
   seq_.assign(R, 0);
 
-  int rc = map_segment(job_name, (size_t)s->x_rank_r() * (size_t)s->x_num_cols(), weights);
+  int rc = map_segment(job_name, (size_t)s->r * (size_t)s->num_cols(), weights);
   if (rc) return rc;
   {
     const hipError_t e = hipHostRegister(map_, map_bytes_, hipHostRegisterMapped | hipHostRegisterPortable);
@@ -465,9 +465,9 @@ int Exchange::init(ExchangeSession *s, const char *job_name, size_t weights) {
   {
     char bus[64] = {0};
     uint64_t h = 1469598103934665603ull;
-    if (hipDeviceGetPCIBusId(bus, (int)sizeof(bus), s->x_device()) != hipSuccess) {
+    if (hipDeviceGetPCIBusId(bus, (int)sizeof(bus), s->opt.device) != hipSuccess) {
       (void)hipGetLastError();
-      std::snprintf(bus, sizeof(bus), "device-%d", s->x_device());
+      std::snprintf(bus, sizeof(bus), "device-%d", s->opt.device);
     }
     for (const char *c = bus; *c; ++c) h = (h ^ (uint64_t)(unsigned char)*c) * 1099511628211ull;
     ranks_[rank].bus.store(h ? h : 1, std::memory_order_release);
@@ -568,7 +568,7 @@ int Exchange::setup_ipc(bool attempt) {
     }
   }
   (void)hipGetLastError();
-  ranks_[rank].device.store(s_->x_device());
+  ranks_[rank].device.store(s_->opt.device);
   ranks_[rank].pid.store((int)getpid());
   ranks_[rank].fine.store(ok && halo_finegrained_ ? 1 : 0);
   ranks_[rank].published.store(ok ? 1 : -1, std::memory_order_release);
@@ -584,9 +584,9 @@ int Exchange::setup_ipc(bool attempt) {
       break;
     }
     const int pd = ranks_[q].device.load();
-    if (pd != s_->x_device()) {
+    if (pd != s_->opt.device) {
       int can = 0;
-      if (hipDeviceCanAccessPeer(&can, s_->x_device(), pd) == hipSuccess && can) {
+      if (hipDeviceCanAccessPeer(&can, s_->opt.device, pd) == hipSuccess && can) {
         const hipError_t e = hipDeviceEnablePeerAccess(pd, 0);
         if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) no("hipDeviceEnablePeerAccess");
       }
@@ -606,9 +606,9 @@ int Exchange::setup_ipc(bool attempt) {
   // self-test: a pattern into my strip of every peer's test area, checked by the owner after the barrier
   if (ok) {
     for (int q : peers)
-      hipLaunchKernelGGL(k_selftest_write, dim3(1), dim3(64), 0, s_->x_stream(),
+      hipLaunchKernelGGL(k_selftest_write, dim3(1), dim3(64), 0, s_->st,
                          peer_halo_[q] + test_off + (size_t)ntest * rank, ntest, 1000.0 * (rank + 1));
-    if (hipStreamSynchronize(s_->x_stream()) != hipSuccess) no("self-test stores");
+    if (hipStreamSynchronize(s_->st) != hipSuccess) no("self-test stores");
     (void)hipGetLastError();
   }
   rc = barrier();
@@ -649,8 +649,8 @@ bool Exchange::probe_round(uint64_t seq, std::string *why) {
     if (ok && why) *why = m;
     ok = false;
   };
-  if (hipSetDevice(s_->x_device()) != hipSuccess) no("hipSetDevice");
-  hipStream_t st = s_->x_stream();
+  if (hipSetDevice(s_->opt.device) != hipSuccess) no("hipSetDevice");
+  hipStream_t st = s_->st;
   for (int q : peers) {
     if (!ok) break;
     double *dst = ipc ? peer_halo_[q] + probe_off_ + (size_t)rank * (kProbeDoubles + 8)
@@ -771,20 +771,20 @@ int Exchange::link_check() {
               DCORA_ERR_EXCHANGE_LINK);
 }
 
-int Exchange::post(const int *agents, int count) { return post_arr(agents, count, s_->x_rank_r(), s_->x_mirror()); }
-int Exchange::wait(const int *agents, int count) { return wait_arr(agents, count, s_->x_rank_r(), s_->x_mirror()); }
+int Exchange::post(const int *agents, int count) { return post_arr(agents, count, s_->r, s_->Xg.p); }
+int Exchange::wait(const int *agents, int count) { return wait_arr(agents, count, s_->r, s_->Xg.p); }
 
 // the same exchange for any r x (d+1)n array laid out like X (the certificate's vectors: r = 1)
 int Exchange::post_arr(const int *agents, int count, int r, const double *arr) {
   const auto t0 = Clock::now();
-  DCORA_HIP(hipSetDevice(s_->x_device()));
+  DCORA_HIP(hipSetDevice(s_->opt.device));
   const int R = R_;
   for (int i = 0; i < count; ++i) {
     const int a = agents[i];
     if (a < 0 || a >= R) return usage("post: agent out of range", DCORA_ERR_BAD_ARG);
     const uint64_t q = ++seq_[a];
-    const XAgentView ag = s_->x_agent(a);
-    if (!ag.hosted || dests_[a].empty() || ag.ncols == 0) continue;
+    const AgentCore &ag = s_->agent_core(a);
+    if (!ag.hosted || dests_[a].empty() || ag.n_public_cols == 0) continue;
     const int parity = (int)(q & 1);
     // Back-pressure: the slot of this parity was last written by post q - 2; every rank that reads it must have
     // scattered that post before it is overwritten (the evaluation's heartbeat used to be the only thing between a
@@ -815,11 +815,11 @@ int Exchange::post_arr(const int *agents, int count, int r, const double *arr) {
     } else {
       dst.base[dst.n++] = (double *)(dev_map_ + off_staged_) + halo_off(parity, a);
     }
-    const int ncols = ag.ncols;
+    const int ncols = ag.n_public_cols;
     const long N = (long)ncols * r;
     const int grid = (int)std::min<long>((N + kBlock - 1) / kBlock, 64);
     volatile uint64_t *flag = (volatile uint64_t *)(dev_map_ + off_flags_ + sizeof(ShmFlag) * ((size_t)parity * R + a));
-    hipLaunchKernelGGL(k_post_public, dim3(grid), dim3(kBlock), 0, s_->x_stream(), r, ncols, ag.cols_dev, arr, dst,
+    hipLaunchKernelGGL(k_post_public, dim3(grid), dim3(kBlock), 0, s_->st, r, ncols, ag.public_cols.p, arr, dst,
                        dflag, arrive_.p + a, flag, q);
     bytes_posted += 8.0 * N * dst.n;
     ++posts;
@@ -831,13 +831,13 @@ int Exchange::post_arr(const int *agents, int count, int r, const double *arr) {
 
 int Exchange::wait_arr(const int *agents, int count, int r, double *arr) {
   const auto t0 = Clock::now();
-  DCORA_HIP(hipSetDevice(s_->x_device()));
+  DCORA_HIP(hipSetDevice(s_->opt.device));
   const int R = R_;
   for (int i = 0; i < count; ++i) {
     const int a = agents[i];
     if (a < 0 || a >= R) return usage("wait: agent out of range", DCORA_ERR_BAD_ARG);
-    const XAgentView ag = s_->x_agent(a);
-    if (!needed_[a] || ag.ncols == 0) continue;
+    const AgentCore &ag = s_->agent_core(a);
+    if (!needed_[a] || ag.n_public_cols == 0) continue;
     const uint64_t want = seq_[a];
     const int parity = (int)(want & 1);
     const ShmFlag *f = flags_ + (size_t)parity * R + a;
@@ -860,13 +860,13 @@ int Exchange::wait_arr(const int *agents, int count, int r, double *arr) {
     // host-visible word when the poses are staged in the shared segment
     const uint64_t *dflag = ipc ? (const uint64_t *)(halo_.p + devflag_off_ + ((size_t)parity * R + a) * 8)
                                 : (const uint64_t *)(dev_map_ + off_flags_ + sizeof(ShmFlag) * ((size_t)parity * R + a));
-    const int ncols = ag.ncols;
+    const int ncols = ag.n_public_cols;
     const long N = (long)ncols * r;
     const int grid = (int)std::min<long>((N + kBlock - 1) / kBlock, 32);
     uint64_t *cons = (uint64_t *)(dev_map_ + off_consumed_ + sizeof(ShmFlag) * ((size_t)rank * R + a));
     uint32_t *failed = (uint32_t *)(dev_map_ + offsetof(ShmHeader, failed));
     // updateNeighborStates: into the local mirror of X
-    hipLaunchKernelGGL(k_wait_scatter, dim3(grid), dim3(kBlock), 0, s_->x_stream(), r, ncols, ag.cols_dev, src,
+    hipLaunchKernelGGL(k_wait_scatter, dim3(grid), dim3(kBlock), 0, s_->st, r, ncols, ag.public_cols.p, src,
                        arr, dflag, want, arrive2_.p + a, cons, failed);
     ++waits;
   }
@@ -878,14 +878,14 @@ int Exchange::wait_arr(const int *agents, int count, int r, double *arr) {
 // agents it hosts against the neighbours' public poses it holds, publishes two scalars per agent, reads everybody's
 int Exchange::evaluate(double *cost2, double *gradnorm, double *block_norms, int *next_selected) {
   const int R = R_;
-  int rc = s_->x_phase_evaluate_dev(evalbuf_.p);
+  int rc = s_->phase_evaluate_dev(evalbuf_.p);
   if (rc) return rc;
   const uint64_t want = ++eval_seq_;
   const int parity = (int)(want & 1);
   const size_t per_parity = (size_t)R + world;
   ShmEval *slots_dev = (ShmEval *)(dev_map_ + off_evals_) + (size_t)parity * per_parity;
   if (n_hosted_)
-    hipLaunchKernelGGL(k_eval_publish, dim3(1), dim3(64), 0, s_->x_stream(), n_hosted_, hosted_list_.p, evalbuf_.p, slots_dev,
+    hipLaunchKernelGGL(k_eval_publish, dim3(1), dim3(64), 0, s_->st, n_hosted_, hosted_list_.p, evalbuf_.p, slots_dev,
                        want);
   DCORA_HIP(hipGetLastError());
   const auto t0 = Clock::now();
@@ -943,13 +943,13 @@ int Exchange::rbcd_iterate(int selected, double *cost2, double *gradnorm, double
   std::vector<int> others;
   for (int a = 0; a < R; ++a)
     if (a != selected) others.push_back(a);
-  int rc = s_->x_phase_nonselected(selected);  // Agent::iterate(false) of the hosted non-selected agents
+  int rc = s_->phase_nonselected(selected);  // Agent::iterate(false) of the hosted non-selected agents
   if (rc) return rc;
   rc = post(others.data(), (int)others.size());
   if (rc) return rc;
   rc = wait(others.data(), (int)others.size());  // the selected agent's pull (and everybody's for the evaluation)
   if (rc) return rc;
-  rc = s_->x_phase_selected(selected);  // Agent::iterate(true) where the selected agent lives
+  rc = s_->phase_selected(selected);  // Agent::iterate(true) where the selected agent lives
   if (rc) return rc;
   rc = post(&selected, 1);
   if (rc) return rc;
@@ -958,12 +958,12 @@ int Exchange::rbcd_iterate(int selected, double *cost2, double *gradnorm, double
   int nxt = selected;
   rc = evaluate(cost2, gradnorm, block_norms, &nxt);
   if (rc) return rc;
-  if (next_selected) *next_selected = s_->x_agent(selected).neighbors->empty() ? selected : nxt;
+  if (next_selected) *next_selected = s_->agent_core(selected).neighbors.empty() ? selected : nxt;
   return DCORA_OK;
 }
 
 int Exchange::rbcd_tick(const int *set, int count, int allow_adjacent) {
-  int rc = s_->x_iterate_set(set, count, allow_adjacent);
+  int rc = s_->iterate_set(set, count, allow_adjacent);
   if (rc) return rc;
   rc = post(set, count);
   if (rc) return rc;
@@ -973,8 +973,8 @@ int Exchange::rbcd_tick(const int *set, int count, int allow_adjacent) {
 int Exchange::run_coloured(int max_sweeps, double rgrad_tol, int *sweeps_done, double *cost2_trace,
                            double *gradnorm_trace) {
   std::vector<int> colours((size_t)R_, 0);
-  const int nc = greedy_agent_colours(R_, [&](int a) -> const std::vector<int> & { return *s_->x_agent(a).neighbors; },
-                                      colours.data());
+  int nc = 0;
+  s_->agent_colours(colours.data(), &nc);
   return run_coloured_sweeps(
       colours, nc, [&](const int *set, int count) { return rbcd_tick(set, count, 0); },
       [&](double *c2, double *gn) { return evaluate(c2, gn, nullptr, nullptr); }, max_sweeps, rgrad_tol, sweeps_done,
@@ -984,7 +984,7 @@ int Exchange::run_coloured(int max_sweeps, double rgrad_tol, int *sweeps_done, d
 int Exchange::set_X(const double *Xh) {
   int rc = barrier();
   if (rc) return rc;
-  rc = s_->x_set_X(Xh);
+  rc = s_->set_X(Xh);
   if (rc) return rc;
   return barrier();
 }
@@ -995,7 +995,7 @@ int Exchange::gather_X(double *Xh) {
   if (rc) return rc;
   rc = barrier();
   if (rc) return rc;
-  std::memcpy(Xh, xarea_, sizeof(double) * (size_t)s_->x_rank_r() * (size_t)s_->x_num_cols());
+  std::memcpy(Xh, xarea_, sizeof(double) * (size_t)s_->r * (size_t)s_->num_cols());
   return barrier();
 }
 
@@ -1005,7 +1005,7 @@ int Exchange::gather_X(double *Xh) {
 // both of its ranks from bitwise-equal mirror columns.  The weights area is written by the kernel while no rank reads
 // it: get_weights ends with a barrier, and the allreduce below is passed only once every rank's stores have landed.
 int Exchange::update_weights(RbcdSession &s, bool reset_to_initial, int counts[3]) {
-  if (!s.robust || !s.robust->ranked || (ExchangeSession *)&s != s_ || w_doubles_ != s.robust->meas.size())
+  if (!s.robust || !s.robust->ranked || &s != s_ || w_doubles_ != s.robust->meas.size())
     return usage("update_weights: the exchange's session is not a ranked robust session", DCORA_ERR_BAD_ARG);
   std::vector<double> w;
   double cnt[3] = {0, 0, 0};
@@ -1031,7 +1031,7 @@ int Exchange::update_weights(RbcdSession &s, bool reset_to_initial, int counts[3
 // or not finite, or nonzero where creation had 0): a refusal is the same on every rank and leaves the job as it was,
 // with the exchange usable.  The owners then store their edges' weights into the area.
 int Exchange::set_weights(RbcdSession &s, const double *w) {
-  if (!s.robust || !s.robust->ranked || (ExchangeSession *)&s != s_ || w_doubles_ != s.robust->meas.size())
+  if (!s.robust || !s.robust->ranked || &s != s_ || w_doubles_ != s.robust->meas.size())
     return usage("set_weights: the exchange's session is not a ranked robust session", DCORA_ERR_BAD_ARG);
   const int rc = s.set_weights(w);
   if (rc == DCORA_ERR_BAD_ARG) return rc;  // (refused on every rank alike, nothing changed)

@@ -105,13 +105,13 @@ int Exchange::certify(const HostCsr *Qglobal, double eta, int *certified, double
   RbcdSession *pgo = dynamic_cast<RbcdSession *>(s_);
   RaRbcdSession *ras = dynamic_cast<RaRbcdSession *>(s_);
   if (!pgo && !ras) return usage("certify: unknown session kind", DCORA_ERR_UNSUPPORTED);
-  const int device = s_->x_device();
-  hipStream_t st = s_->x_stream();
+  const int device = s_->opt.device;
+  hipStream_t st = s_->st;
   DCORA_HIP(hipSetDevice(device));
-  const int R = s_->x_num_agents(), r = s_->x_rank_r(), ktot = (int)s_->x_num_cols();
+  const int R = s_->R, r = s_->r, ktot = (int)s_->num_cols();
   const dcora_dims dims = pgo ? dcora_dims{r, pgo->d, pgo->n, 0, 0} : dcora_dims{r, ras->d, ras->n, ras->l, ras->b, DCORA_LAYOUT_RA};
   const int chol_block = pgo ? pgo->d + 1 : 1;
-  double *mirror = s_->x_mirror();
+  double *mirror = s_->Xg.p;
   if (certified) *certified = 0;
   if (theta) *theta = 0;
   if (lambda_min) *lambda_min = 0;

@@ -8,7 +8,6 @@
 #include <string>
 
 #include "cert.h"
-#include "host_threads.h"
 
 namespace dcora {
 
@@ -25,14 +24,10 @@ int device_precond_regularization(const HostCsr &Q, int device, double *reg) {
 }
 
 RaRbcdSession::~RaRbcdSession() {
-  for (RaAgentDev &a : agents) {
-    if (a.own_st) stream_release(device_of_stream_, a.own_st);
-    if (a.done) (void)hipEventDestroy(a.done);
-  }
-  if (fork_ev_) (void)hipEventDestroy(fork_ev_);
+  for (RaAgentDev &a : agents) release_tick_resources(a);
   agents.clear();
   central.reset();
-  if (st) stream_release(device_of_stream_, st);
+  release_stream();
 }
 
 int RaRbcdSession::init(const HostRADataset &ds, const dcora_rbcd_options &o) {
@@ -77,9 +72,8 @@ int RaRbcdSession::init(const HostRADataset &ds, const dcora_rbcd_options &o) {
     return DCORA_ERR_UNSUPPORTED;
   }
   {
-    const int rcs = stream_acquire(o.device, &st);
+    const int rcs = acquire_stream(nullptr);
     if (rcs) return rcs;
-    device_of_stream_ = o.device;
   }
   const HostCsr Q = build_Q_ra(ds);
   const size_t N = (size_t)r * k;
@@ -87,7 +81,7 @@ int RaRbcdSession::init(const HostRADataset &ds, const dcora_rbcd_options &o) {
   DCORA_HIP(hipMemset(Xg.p, 0, sizeof(double) * N));
   DCORA_HIP(evalbuf.alloc(R + 8));
   agents.resize(R);
-  const int per = (R + o.world_size - 1) / o.world_size;  // consecutive agents share a rank, as in the pose-graph session
+  const int per = (R + o.world_size - 1) / o.world_size;  // consecutive agents share a rank
   std::vector<int> owner_of((size_t)k, -1);               // global column -> agent
   std::vector<std::set<int>> pub((size_t)R), nbr((size_t)R);
   int idx = 0;
@@ -139,16 +133,18 @@ int RaRbcdSession::init(const HostRADataset &ds, const dcora_rbcd_options &o) {
     DCORA_HIP(a.Y.alloc(Na));
     DCORA_HIP(a.XPrev.alloc(Na));
     DCORA_HIP(a.tmp.alloc(Na));
-    rc = stream_acquire(o.device, &a.own_st);  // (at most kMaxAgents of them: R <= kMaxAgents)
+    rc = acquire_tick_resources(a);
     if (rc) return rc;
-    DCORA_HIP(hipEventCreateWithFlags(&a.done, hipEventDisableTiming));
   }
-  DCORA_HIP(hipEventCreateWithFlags(&fork_ev_, hipEventDisableTiming));
+  {
+    const int rc = create_fork_event();
+    if (rc) return rc;
+  }
   for (int i = 0; i < R; ++i) {
     RaAgentDev &a = agents[(size_t)i];
     a.neighbors.assign(nbr[(size_t)i].begin(), nbr[(size_t)i].end());
     std::vector<int> pc(pub[(size_t)i].begin(), pub[(size_t)i].end());
-    a.n_public = (int)pc.size();
+    a.n_public_cols = (int)pc.size();
     DCORA_HIP(a.public_cols.alloc(std::max<size_t>(pc.size(), 1)));
     if (!pc.empty()) DCORA_HIP(hipMemcpy(a.public_cols.p, pc.data(), sizeof(int) * pc.size(), hipMemcpyHostToDevice));
   }
@@ -211,17 +207,10 @@ int RaRbcdSession::solve(RaAgentDev &a, const double *start, double **result) {
 // Agent::iterate(false) of the hosted non-selected agents (ref src/Agent.cpp:535-551, 1202-1214): the shared Nesterov
 // sequences advance once per round on every rank alike
 int RaRbcdSession::phase_nonselected(int selected) {
-  if (selected < 0 || selected >= R) {
-    set_last_error("ra_rbcd: selected agent out of range");
-    return DCORA_ERR_BAD_ARG;
-  }
+  if (const int rc = check_selected(selected)) return rc;
   DCORA_HIP(hipSetDevice(opt.device));
-  iteration++;
+  advance_sequences();
   const bool accel = opt.acceleration != 0;
-  if (accel) {  // updateGamma / updateAlpha (ref src/Agent.cpp:1189-1200)
-    gamma = (1 + std::sqrt(1 + 4.0 * R * R * gamma * gamma)) / (2.0 * R);
-    alpha = 1.0 / (gamma * R);
-  }
   const bool restart = restart_now();
   // Y = proj((1 - alpha) X + alpha V), X = Y, V = proj(V)
   for (int i = 0; i < R; ++i) {
@@ -247,10 +236,7 @@ int RaRbcdSession::phase_nonselected(int selected) {
 
 // Agent::iterate(true) of the selected agent, where it lives
 int RaRbcdSession::phase_selected(int selected) {
-  if (selected < 0 || selected >= R) {
-    set_last_error("ra_rbcd: selected agent out of range");
-    return DCORA_ERR_BAD_ARG;
-  }
+  if (const int rc = check_selected(selected)) return rc;
   DCORA_HIP(hipSetDevice(opt.device));
   const bool accel = opt.acceleration != 0;
   const bool restart = restart_now();
@@ -320,16 +306,7 @@ int RaRbcdSession::phase_evaluate_dev(double *out_dev) {
   return DCORA_OK;
 }
 
-// Greedy colouring in agent order, the rule of RbcdSession::agent_colours.  Agents of one colour share no measurement,
-// so their simultaneous updates equal the same updates done one after the other.
-int RaRbcdSession::agent_colours(int *colours, int *ncolours) const {
-  const int nc = greedy_agent_colours(R, [&](int a) -> const std::vector<int> & { return agents[(size_t)a].neighbors; },
-                                      colours);
-  if (ncolours) *ncolours = nc;
-  return DCORA_OK;
-}
-
-// initializeAcceleration / acceleration off for every agent (ref src/Agent.cpp:1178-1187), as RbcdSession::set_acceleration
+// initializeAcceleration / acceleration off for every agent (ref src/Agent.cpp:1178-1187)
 int RaRbcdSession::set_acceleration(bool on) {
   DCORA_HIP(hipSetDevice(opt.device));
   opt.acceleration = on ? 1 : 0;
@@ -345,98 +322,25 @@ int RaRbcdSession::set_acceleration(bool on) {
   return DCORA_OK;
 }
 
-// local solve of one agent of a tick from the G / X0 staged by iterate_set, then its block into the mirror.  On the
-// agent's own stream (side by side with the set's other solves) or, own == false, on the session's stream.
-int RaRbcdSession::solve_block(RaAgentDev &a, std::string *err, bool own) {
-  auto fail = [&](int rc) {
-    if (err) *err = dcora_last_error();
-    return rc;
-  };
-  if (hipSetDevice(opt.device) != hipSuccess) return fail(DCORA_ERR_HIP);
+// the tick's staging: XPrev, G_a = X_mirror C_a^T (launch_spmm, as solve() forms it) and the start point
+int RaRbcdSession::stage(AgentCore &core) {
+  RaAgentDev &a = static_cast<RaAgentDev &>(core);
   DeviceProblem &pb = *a.prob;
   const size_t Ba = sizeof(double) * (size_t)r * a.k;
-  hipStream_t keep = pb.st;
-  hipStream_t run_on = own ? a.own_st : st;
-  pb.st = run_on;
-  pb.concurrent_solves = own;  // several solves share the device
-  int rc = pb.optimize_dev(opt.local);
-  pb.concurrent_solves = false;
-  double *res = nullptr;
-  if (!rc) rc = pb.result(&res);  // (the solver paces from the host: this waits for run_on)
-  if (!rc && hipMemcpyAsync(a.X.p, res, Ba, hipMemcpyDeviceToDevice, run_on) != hipSuccess) rc = DCORA_ERR_HIP;
-  if (!rc) launch_scatter_cols(run_on, r, a.k, a.own.p, a.X.p, Xg.p);
-  if (!rc && own && hipEventRecord(a.done, a.own_st) != hipSuccess) rc = DCORA_ERR_HIP;
-  pb.st = keep;
-  return rc ? fail(rc) : DCORA_OK;
+  DCORA_HIP(hipMemcpyAsync(a.XPrev.p, a.X.p, Ba, hipMemcpyDeviceToDevice, st));
+  launch_spmm(st, r, a.coupling.view(), buf1(Xg.p), 0, nullptr, buf1(pb.G.p), 0, nullptr, Gate{});
+  pb.has_G = true;
+  DCORA_HIP(hipMemcpyAsync(pb.X0.p, a.X.p, Ba, hipMemcpyDeviceToDevice, st));
+  return DCORA_OK;
 }
 
-// One tick in which the agents of `set` run Agent::iterate(true) at the same time, every one of them seeing the mirror
-// as it was when the tick began (what concurrently firing agents of the asynchronous mode see, ref src/Agent.cpp:650-678;
-// non-accelerated like that mode, :651-653): the contract of RbcdSession::iterate_set.  Every agent's G_a = X_mirror C_a^T
-// (launch_spmm, as solve() forms it), start point and XPrev are staged on the session's stream before the fork event, and
-// blocks go back into the mirror only behind it: agents' columns are disjoint and no solve reads the mirror, so for
-// agents that share no measurement the tick equals one-after-the-other updates, and for adjacent ones it is well defined.
-int RaRbcdSession::iterate_set(const int *set, int count, int allow_adjacent) {
-  if (opt.acceleration) {
-    set_last_error("ra_rbcd: simultaneous updates need acceleration off (ref src/Agent.cpp:651-653)");
-    return DCORA_ERR_UNSUPPORTED;
-  }
-  if (!set || count < 1 || count > R) {
-    set_last_error("ra_rbcd: bad agent set");
-    return DCORA_ERR_BAD_ARG;
-  }
-  std::vector<char> in((size_t)R, 0);
-  for (int i = 0; i < count; ++i) {
-    if (set[i] < 0 || set[i] >= R || in[(size_t)set[i]]) {
-      set_last_error("ra_rbcd: agent set has an id out of range or twice");
-      return DCORA_ERR_BAD_ARG;
-    }
-    in[(size_t)set[i]] = 1;
-  }
-  if (!allow_adjacent)
-    for (int i = 0; i < count; ++i)
-      for (int q : agents[(size_t)set[i]].neighbors)
-        if (in[(size_t)q]) {
-          set_last_error("ra_rbcd: agents " + std::to_string(set[i]) + " and " + std::to_string(q) +
-                         " share measurements; pass allow_adjacent to update them from one snapshot anyway");
-          return DCORA_ERR_BAD_ARG;
-        }
-  DCORA_HIP(hipSetDevice(opt.device));
-  iteration++;
-  std::vector<RaAgentDev *> work;
-  for (int i = 0; i < count; ++i)
-    if (agents[(size_t)set[i]].hosted) work.push_back(&agents[(size_t)set[i]]);
-  if (work.empty()) return DCORA_OK;
-  // snapshot: every G, every start point and every XPrev is taken before any block is written back
-  for (RaAgentDev *a : work) {
-    DeviceProblem &pb = *a->prob;
-    const size_t Ba = sizeof(double) * (size_t)r * a->k;
-    DCORA_HIP(hipMemcpyAsync(a->XPrev.p, a->X.p, Ba, hipMemcpyDeviceToDevice, st));
-    launch_spmm(st, r, a->coupling.view(), buf1(Xg.p), 0, nullptr, buf1(pb.G.p), 0, nullptr, Gate{});
-    pb.has_G = true;
-    DCORA_HIP(hipMemcpyAsync(pb.X0.p, a->X.p, Ba, hipMemcpyDeviceToDevice, st));
-  }
-  std::string err;
-  if (work.size() == 1) {  // nothing to run beside: on the session's stream, no thread, no fork
-    const int rc = solve_block(*work[0], &err, false);
-    if (rc) set_last_error(err);
-    else last_solver = work[0]->prob.get();
-    return rc;
-  }
-  DCORA_HIP(hipEventRecord(fork_ev_, st));
-  for (RaAgentDev *a : work) DCORA_HIP(hipStreamWaitEvent(a->own_st, fork_ev_, 0));
-  std::vector<int> rcs(work.size(), DCORA_OK);
-  std::vector<std::string> errs(work.size());
-  // the solver paces each solve from the host (device_problem.hip): one host thread per concurrent solve
-  run_threads((int)work.size(), [&](int i) { rcs[(size_t)i] = solve_block(*work[(size_t)i], &errs[(size_t)i], true); });
-  last_solver = work.back()->prob.get();
-  for (size_t i = 0; i < work.size(); ++i) {
-    if (rcs[i]) {
-      set_last_error(errs[i]);
-      return rcs[i];
-    }
-    DCORA_HIP(hipStreamWaitEvent(st, work[i]->done, 0));
-  }
+int RaRbcdSession::write_back(AgentCore &core, hipStream_t run_on) {
+  RaAgentDev &a = static_cast<RaAgentDev &>(core);
+  double *res = nullptr;
+  const int rc = a.prob->result(&res);  // (the solver paces from the host: this waits for run_on)
+  if (rc) return rc;
+  DCORA_HIP(hipMemcpyAsync(a.X.p, res, sizeof(double) * (size_t)r * a.k, hipMemcpyDeviceToDevice, run_on));
+  launch_scatter_cols(run_on, r, a.k, a.own.p, a.X.p, Xg.p);
   return DCORA_OK;
 }
 

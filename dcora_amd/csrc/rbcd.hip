@@ -78,14 +78,10 @@ struct RbcdSession::MeasSplit {
 RbcdSession::~RbcdSession() {
   if (eval_host) (void)hipHostFree((void *)eval_host);
   if (x_stage) (void)hipHostFree((void *)x_stage);
-  for (AgentDev &a : agents) {
-    if (a.own) stream_release(opt.device, a.own);
-    if (a.done) (void)hipEventDestroy(a.done);
-  }
-  if (fork_ev_) (void)hipEventDestroy(fork_ev_);
+  for (AgentDev &a : agents) release_tick_resources(a);
   agents.clear();
   central.reset();
-  if (st && own_stream_) stream_release(opt.device, st);
+  release_stream();
 }
 
 int RbcdSession::init(const HostDataset &ds, const dcora_rbcd_options &o) {
@@ -117,11 +113,8 @@ int RbcdSession::init(const HostDataset &ds, const dcora_rbcd_options &o) {
     return DCORA_ERR_NO_DEVICE;
   }
   DCORA_HIP(hipSetDevice(o.device));
-  if (o.stream) {
-    st = (hipStream_t)o.stream;
-    own_stream_ = false;
-  } else {
-    const int rcs = stream_acquire(o.device, &st);
+  {
+    const int rcs = acquire_stream(o.stream);
     if (rcs) return rcs;
   }
   mg = make_mani(r, d, n, 0, 0);
@@ -174,6 +167,7 @@ int RbcdSession::init(const HostDataset &ds, const dcora_rbcd_options &o) {
     std::vector<int> cols;
     for (int p : a.public_poses)
       for (int c = 0; c < dh; ++c) cols.push_back(p * dh + c);
+    a.n_public_cols = (int)cols.size();
     DCORA_HIP(a.public_cols.alloc(std::max<size_t>(cols.size(), 1)));
     if (!cols.empty())
       DCORA_HIP(hipMemcpy(a.public_cols.p, cols.data(), sizeof(int) * cols.size(), hipMemcpyHostToDevice));
@@ -189,7 +183,7 @@ int RbcdSession::init(const HostDataset &ds, const dcora_rbcd_options &o) {
     DCORA_HIP(hipMemcpyAsync(col_start.p, cs.data(), sizeof(int) * (R + 1), hipMemcpyHostToDevice, st));
     DCORA_HIP(hipStreamSynchronize(st));
   }
-  DCORA_HIP(hipEventCreateWithFlags(&fork_ev_, hipEventDisableTiming));
+  if (const int rcf = create_fork_event()) return rcf;
   const int rc = assemble(
       split, nullptr,
       [&](const Assembly &A) {
@@ -202,9 +196,7 @@ int RbcdSession::init(const HostDataset &ds, const dcora_rbcd_options &o) {
             robust->Qpat[(size_t)a.id] = pattern_of(A.Q[i]);
             robust->Cpat[(size_t)a.id] = pattern_of(A.C[i]);
           }
-          if (!rca) rca = stream_acquire(o.device, &a.own);
-          if (!rca && hipEventCreateWithFlags(&a.done, hipEventDisableTiming) != hipSuccess) rca = DCORA_ERR_HIP;
-          return rca;
+          return rca ? rca : acquire_tick_resources(a);
         });
       },
       [&](const HostCsr &Qc) {  // (the evaluation's problem: Q of all poses, no preconditioner)
@@ -438,7 +430,7 @@ int RbcdSession::rebuild_values(const std::vector<PoseMeas> &meas) {
   DCORA_HIP(hipSetDevice(opt.device));
   // nothing of the session is in flight while its matrices and preconditioner images change
   for (const AgentDev &a : agents)
-    if (a.own) DCORA_HIP(hipStreamSynchronize(a.own));
+    if (a.own_st) DCORA_HIP(hipStreamSynchronize(a.own_st));
   DCORA_HIP(hipStreamSynchronize(st));
   const char *outside = "rbcd robust: the weights give a matrix entry outside the session's pattern";
   // host images of the uploads (by agent id), alive until the stream has been synchronised
@@ -516,7 +508,7 @@ int RbcdSession::compute_weights(double *shared_w, std::vector<double> *w, doubl
   }
   DCORA_HIP(hipSetDevice(opt.device));
   for (const AgentDev &a : agents)
-    if (a.own) DCORA_HIP(hipStreamSynchronize(a.own));
+    if (a.own_st) DCORA_HIP(hipStreamSynchronize(a.own_st));
   const size_t m = rs.edge_ids.size();
   w->assign(m, 0.0);
   for (int c = 0; c < 3; ++c) counts[c] = 0;
@@ -581,25 +573,12 @@ int RbcdSession::get_weights(double *w) const {
   return DCORA_OK;
 }
 
-// updateGamma / updateAlpha (ref src/Agent.cpp:1189-1200); the sequences are data-independent and identical for
-// every agent, so they live on the host
-void RbcdSession::advance_sequences() {
-  iteration++;
-  if (opt.acceleration) {
-    gamma = (1 + std::sqrt(1 + 4.0 * R * R * gamma * gamma)) / (2.0 * R);
-    alpha = 1.0 / (gamma * R);
-  }
-  seq_advanced_ = true;
-}
-
 // Agent::iterate(false) for every hosted agent except `selected`
 int RbcdSession::phase_nonselected(int selected) {
-  if (selected < 0 || selected >= R) {
-    set_last_error("rbcd: selected agent out of range");
-    return DCORA_ERR_BAD_ARG;
-  }
+  if (const int rc = check_selected(selected)) return rc;
   DCORA_HIP(hipSetDevice(opt.device));
   advance_sequences();
+  seq_advanced_ = true;
   set_marks_.assign(R, 0);
   staged_selected_ = -1;
   if (!opt.acceleration) return DCORA_OK;
@@ -645,10 +624,7 @@ int RbcdSession::update_nonselected_agent(AgentDev &a, bool restart) {
 
 // Agent::iterate(true) for `selected` when hosted here (ref src/Agent.cpp:535-551, 1158-1176, 1216-1278)
 int RbcdSession::phase_selected(int selected) {
-  if (selected < 0 || selected >= R) {
-    set_last_error("rbcd: selected agent out of range");
-    return DCORA_ERR_BAD_ARG;
-  }
+  if (const int rc = check_selected(selected)) return rc;
   DCORA_HIP(hipSetDevice(opt.device));
   if (!seq_advanced_) advance_sequences();
   seq_advanced_ = false;
@@ -662,6 +638,33 @@ int RbcdSession::phase_selected(int selected) {
   return DCORA_OK;
 }
 
+// which: the plain (0) or the auxiliary (1) cache of a detached agent holds every pose the agent requires
+static bool cache_complete(const AgentDev &a, int which) {
+  return std::find(a.got[which].begin(), a.got[which].end(), 0) == a.got[which].end();
+}
+
+// restartNesterovAcceleration of the selected agent: X = XPrev; updateX(true, false), which for a detached agent reads
+// the PLAIN cache (ref src/Agent.cpp:1237-1240); V = X; Y = X.  No G can be built from an incomplete cache: then
+// X = XPrev without the solve.  `success` of Agent::iterate is the FIRST updateX's result, this one's is discarded (ref
+// src/Agent.cpp:548-553): last_skipped stays what that one left.
+int RbcdSession::restart_step(AgentDev &a) {
+  DeviceProblem &pb = *a.prob;
+  const size_t off = (size_t)a.col0 * r;
+  if (a.detached && !cache_complete(a, 0)) {
+    const Buf2 Xprev{{XPrevg.p + off, XPrevg.p + off}};
+    nesterov(st, pb.m, 3, 0, -1, -1, alpha, gamma, Xg.p + off, Vg.p + off, Yg.p + off, XPrevg.p + off, nullptr, Xprev,
+             nullptr);
+    return DCORA_OK;
+  }
+  if (a.detached)
+    launch_spmm(st, r, a.coupling.view(), buf1(a.nbr[0].p), 0, nullptr, buf1(pb.G.p), 0, nullptr, Gate{});
+  pb.has_G = true;
+  last_solver = &pb;
+  DCORA_HIP(hipMemcpyAsync(pb.X0.p, XPrevg.p + off, sizeof(double) * (size_t)pb.nelem(), hipMemcpyDeviceToDevice, st));
+  const int rc = pb.optimize_dev(opt.local);
+  return rc ? rc : nesterov_solved(st, pb, 3, alpha, gamma, Xg.p + off, Vg.p + off, Yg.p + off, XPrevg.p + off);
+}
+
 int RbcdSession::update_selected_agent(AgentDev &a, bool restart) {
   int rc = DCORA_OK;
   {
@@ -673,12 +676,7 @@ int RbcdSession::update_selected_agent(AgentDev &a, bool restart) {
     // handed poses through Agent::updateNeighborStates, its own cache of them: the auxiliary one when it optimises
     // from Y (ref src/Agent.cpp:1234-1240)
     a.last_skipped = false;
-    auto cache_complete = [&](int which) {
-      for (char c : a.got[which])
-        if (!c) return false;
-      return true;
-    };
-    if (a.detached && !cache_complete(opt.acceleration ? 1 : 0)) {
+    if (a.detached && !cache_complete(a, opt.acceleration ? 1 : 0)) {
       // "cannot construct data matrices... Skip optimization" (ref src/Agent.cpp:1243-1249): only updateX is skipped;
       // updateGamma / updateAlpha / updateY have run before it and updateV and the restart follow (Agent::iterate, ref
       // src/Agent.cpp:535-596) -- X stays, Y <- proj((1 - alpha) X + alpha V), V <- proj(V + gamma (X - Y))
@@ -692,26 +690,7 @@ int RbcdSession::update_selected_agent(AgentDev &a, bool restart) {
         nesterov(st, pb.m, 2, 0, -1, -1, alpha, gamma, Xg.p + off, Vg.p + off, Yg.p + off, XPrevg.p + off, nullptr, Xself,
                  nullptr);
         a.v_feasible = true;
-        if (restart) {
-          // restartNesterovAcceleration: X = XPrev; updateX(true, false) reads the PLAIN cache; V = X; Y = X
-          const Buf2 Xprev{{XPrevg.p + off, XPrevg.p + off}};
-          bool solved = false;
-          if (cache_complete(0)) {
-            launch_spmm(st, r, a.coupling.view(), buf1(a.nbr[0].p), 0, nullptr, buf1(pb.G.p), 0, nullptr, Gate{});
-            pb.has_G = true;
-            last_solver = &pb;
-            DCORA_HIP(hipMemcpyAsync(pb.X0.p, XPrevg.p + off, B, hipMemcpyDeviceToDevice, st));
-            rc = pb.optimize_dev(opt.local);
-            if (!rc) rc = nesterov_solved(st, pb, 3, alpha, gamma, Xg.p + off, Vg.p + off, Yg.p + off, XPrevg.p + off);
-            if (rc) return rc;
-            // last_skipped stays true: `success` of Agent::iterate is the FIRST updateX's result, the restart's is
-            // discarded (ref src/Agent.cpp:548-553), so iterate() returns false and readyToTerminate stays false
-            solved = true;
-          }
-          if (!solved)
-            nesterov(st, pb.m, 3, 0, -1, -1, alpha, gamma, Xg.p + off, Vg.p + off, Yg.p + off, XPrevg.p + off, nullptr,
-                     Xprev, nullptr);
-        }
+        if (restart) return restart_step(a);
       }
       return DCORA_OK;
     }
@@ -729,29 +708,7 @@ int RbcdSession::update_selected_agent(AgentDev &a, bool restart) {
       if (!rc) rc = nesterov_solved(st, pb, 2, alpha, gamma, Xg.p + off, Vg.p + off, Yg.p + off, XPrevg.p + off);
       if (rc) return rc;
       a.v_feasible = true;  // V = proj(V + gamma (X - Y))
-      if (restart) {
-        // restartNesterovAcceleration: X = XPrev; updateX(true, false); V = X; Y = X
-        bool plain_ok = true;
-        if (a.detached) {  // updateX(.., false) reads the PLAIN cache (ref src/Agent.cpp:1237-1240)
-          if (cache_complete(0)) {
-            launch_spmm(st, r, a.coupling.view(), buf1(a.nbr[0].p), 0, nullptr, buf1(pb.G.p), 0, nullptr, Gate{});
-          } else {
-            // no G can be built from an incomplete cache: X = XPrev without the solve.  last_skipped is NOT raised: the
-            // first updateX of this iterate succeeded and that is what iterate() reports (ref src/Agent.cpp:548-553)
-            plain_ok = false;
-          }
-        }
-        if (plain_ok) {
-          DCORA_HIP(hipMemcpyAsync(pb.X0.p, XPrevg.p + off, B, hipMemcpyDeviceToDevice, st));
-          rc = pb.optimize_dev(opt.local);
-          if (!rc) rc = nesterov_solved(st, pb, 3, alpha, gamma, Xg.p + off, Vg.p + off, Yg.p + off, XPrevg.p + off);
-          if (rc) return rc;
-        } else {
-          const Buf2 Xprev{{XPrevg.p + off, XPrevg.p + off}};
-          nesterov(st, pb.m, 3, 0, -1, -1, alpha, gamma, Xg.p + off, Vg.p + off, Yg.p + off, XPrevg.p + off, nullptr,
-                   Xprev, nullptr);
-        }
-      }
+      if (restart) return restart_step(a);
     } else {
       DCORA_HIP(hipMemcpyAsync(XPrevg.p + off, Xg.p + off, B, hipMemcpyDeviceToDevice, st));
       DCORA_HIP(hipMemcpyAsync(pb.X0.p, Xg.p + off, B, hipMemcpyDeviceToDevice, st));
@@ -1007,11 +964,9 @@ int RbcdSession::phase_evaluate_dev(double *out_dev) {
 }
 
 int RbcdSession::iterate(int selected, double *cost2, double *gradnorm, double *block_norms, int *next_selected) {
-  if (selected < 0 || selected >= R) {
-    set_last_error("rbcd: selected agent out of range");
-    return DCORA_ERR_BAD_ARG;
-  }
-  int rc = phase_nonselected(selected);
+  int rc = check_selected(selected);
+  if (rc) return rc;
+  rc = phase_nonselected(selected);
   if (rc) return rc;
   // world_size == 1: the "pull" of public poses (ref examples/MultiRobotExample.cpp:236-258) is the identity,
   // all agents' blocks live in the same mirror Xg
@@ -1025,132 +980,47 @@ int RbcdSession::iterate(int selected, double *cost2, double *gradnorm, double *
   return DCORA_OK;
 }
 
-// Greedy colouring in agent order (smallest colour not used by a neighbour).  Agents of one colour share no
-// measurement, so their simultaneous updates equal the same updates done one after the other.
-int RbcdSession::agent_colours(int *colours, int *ncolours) const {
-  const int nc = greedy_agent_colours(R, [&](int b) -> const std::vector<int> & { return agents[(size_t)b].neighbors; },
-                                      colours);
-  if (ncolours) *ncolours = nc;
-  return DCORA_OK;
+// The tick's hooks (SessionCore::iterate_set).  A step staged by an interrupted round, an advance of the sequences that
+// waits for its phase_selected and the setX marks do not survive a tick.
+void RbcdSession::tick_begins() {
+  staged_selected_ = -1;
+  seq_advanced_ = false;
+  set_marks_.assign(R, 0);
 }
 
-// local solve of one agent on its own stream, from the G / X0 staged by iterate_set; the accepted iterate goes
-// back into the global mirror without a host round trip when the solver keeps its choice on the device
-int RbcdSession::solve_block(AgentDev &a, std::string *err, bool serial) {
-  auto fail = [&](int rc) {
-    if (err) *err = dcora_last_error();
-    return rc;
-  };
-  if (hipSetDevice(opt.device) != hipSuccess) return fail(DCORA_ERR_HIP);
+int RbcdSession::stage(AgentCore &core) {
+  AgentDev &a = static_cast<AgentDev &>(core);
   DeviceProblem &pb = *a.prob;
   const size_t off = (size_t)a.col0 * r;
   const size_t B = sizeof(double) * (size_t)pb.nelem();
-  hipStream_t keep = pb.st;
-  // serial: the set's solves one after the other on the session's stream (each may then run its tCG runs as ONE launch,
-  // k_tcg_run); otherwise side by side on the agents' own streams, on the launches per iteration
-  hipStream_t run_on = serial ? st : a.own;
-  pb.st = run_on;
-  pb.concurrent_solves = !serial;  // several solves share the device: no co-resident one-launch tCG run
-  int rc = pb.optimize_dev(opt.local);
-  pb.concurrent_solves = false;
-  if (!rc) {
-    if (group_kernels(pb.m)) {
-      rc = nesterov_solved(run_on, pb, 3, 0.0, 0.0, Xg.p + off, Vg.p + off, Yg.p + off, XPrevg.p + off);
-    } else {
-      double *Xres = nullptr;
-      rc = pb.result(&Xres);
-      if (!rc && hipMemcpyAsync(Xg.p + off, Xres, B, hipMemcpyDeviceToDevice, run_on) != hipSuccess) rc = DCORA_ERR_HIP;
-    }
-  }
-  if (!rc && !serial && hipEventRecord(a.done, a.own) != hipSuccess) rc = DCORA_ERR_HIP;
-  pb.st = keep;
-  return rc ? fail(rc) : DCORA_OK;
+  launch_spmm(st, r, a.coupling.view(), buf1(Xg.p), 0, nullptr, buf1(pb.G.p), 0, nullptr, Gate{});
+  pb.has_G = true;
+  DCORA_HIP(hipMemcpyAsync(XPrevg.p + off, Xg.p + off, B, hipMemcpyDeviceToDevice, st));
+  DCORA_HIP(hipMemcpyAsync(pb.X0.p, Xg.p + off, B, hipMemcpyDeviceToDevice, st));
+  return DCORA_OK;
 }
 
-// One tick in which the agents of `set` run Agent::iterate(true) at the same time, every one of them seeing the
-// neighbour states as they were when the tick began (what concurrently firing agents of the asynchronous mode see,
-// ref src/Agent.cpp:650-678; non-accelerated like that mode, :651-653).  With a set of mutually non-adjacent
-// agents (one colour of agent_colours) the result equals updating them one after the other.
-int RbcdSession::iterate_set(const int *set, int count, int allow_adjacent) {
-  staged_selected_ = -1;
-  if (opt.acceleration) {
-    set_last_error("rbcd: simultaneous updates need acceleration off (ref src/Agent.cpp:651-653)");
-    return DCORA_ERR_UNSUPPORTED;
-  }
-  if (!set || count < 1 || count > R) {
-    set_last_error("rbcd: bad agent set");
-    return DCORA_ERR_BAD_ARG;
-  }
-  std::vector<char> in(R, 0);
-  for (int i = 0; i < count; ++i) {
-    if (set[i] < 0 || set[i] >= R || in[set[i]]) {
-      set_last_error("rbcd: agent set has an id out of range or twice");
-      return DCORA_ERR_BAD_ARG;
-    }
-    in[set[i]] = 1;
-  }
-  if (!allow_adjacent)
-    for (int i = 0; i < count; ++i)
-      for (int q : agents[set[i]].neighbors)
-        if (in[q]) {
-          set_last_error("rbcd: agents " + std::to_string(set[i]) + " and " + std::to_string(q) +
-                         " share measurements; pass allow_adjacent to update them from one snapshot anyway");
-          return DCORA_ERR_BAD_ARG;
-        }
-  DCORA_HIP(hipSetDevice(opt.device));
-  iteration++;
-  seq_advanced_ = false;
-  set_marks_.assign(R, 0);
-  std::vector<AgentDev *> work;
-  for (int i = 0; i < count; ++i)
-    if (agents[set[i]].hosted) work.push_back(&agents[set[i]]);
-  if (work.empty()) return DCORA_OK;
-  // snapshot: every G and every start point is taken before any block is written back
-  for (AgentDev *a : work) {
-    DeviceProblem &pb = *a->prob;
-    const size_t off = (size_t)a->col0 * r;
-    const size_t B = sizeof(double) * (size_t)pb.nelem();
-    launch_spmm(st, r, a->coupling.view(), buf1(Xg.p), 0, nullptr, buf1(pb.G.p), 0, nullptr, Gate{});
-    pb.has_G = true;
-    DCORA_HIP(hipMemcpyAsync(XPrevg.p + off, Xg.p + off, B, hipMemcpyDeviceToDevice, st));
-    DCORA_HIP(hipMemcpyAsync(pb.X0.p, Xg.p + off, B, hipMemcpyDeviceToDevice, st));
-  }
-  // Blocks whose tCG runs fit ONE launch (dense preconditioner, n / 2 co-resident workgroups): one after the other on the
-  // session's stream -- 3 launches per RTR iteration each -- is faster on one device than side by side on the launches per
-  // iteration (sphere2500 / 5 agents: 2420 -> see DESIGN.md block updates/s); the staged G / start points make the order
-  // immaterial, and the two forms give the same bits.
-  bool serial = true;
-  for (AgentDev *a : work) serial = serial && a->prob->tcg_run_ok && a->prob->use_pc();
-  std::vector<int> rcs(work.size(), DCORA_OK);
-  std::vector<std::string> errs(work.size());
-  if (serial) {
-    for (size_t i = 0; i < work.size(); ++i) {
-      rcs[i] = solve_block(*work[i], &errs[i], true);
-      if (rcs[i]) {
-        set_last_error(errs[i]);
-        return rcs[i];
-      }
-    }
-    last_solver = work.back()->prob.get();
-    return DCORA_OK;
-  }
-  DCORA_HIP(hipEventRecord(fork_ev_, st));
-  for (AgentDev *a : work) DCORA_HIP(hipStreamWaitEvent(a->own, fork_ev_, 0));
-  if (work.size() == 1) {
-    rcs[0] = solve_block(*work[0], &errs[0]);
-  } else {
-    // the solver paces each solve from the host (device_problem.hip): one host thread per concurrent solve
-    run_threads((int)work.size(), [&](int i) { rcs[(size_t)i] = solve_block(*work[(size_t)i], &errs[(size_t)i]); });
-  }
-  last_solver = work.back()->prob.get();
-  for (size_t i = 0; i < work.size(); ++i) {
-    if (rcs[i]) {
-      set_last_error(errs[i]);
-      return rcs[i];
-    }
-    DCORA_HIP(hipStreamWaitEvent(st, work[i]->done, 0));
-  }
+// the accepted iterate goes back into the mirror without a host round trip when the solver keeps its choice on the device
+int RbcdSession::write_back(AgentCore &core, hipStream_t run_on) {
+  AgentDev &a = static_cast<AgentDev &>(core);
+  DeviceProblem &pb = *a.prob;
+  const size_t off = (size_t)a.col0 * r;
+  if (group_kernels(pb.m))
+    return nesterov_solved(run_on, pb, 3, 0.0, 0.0, Xg.p + off, Vg.p + off, Yg.p + off, XPrevg.p + off);
+  double *Xres = nullptr;
+  const int rc = pb.result(&Xres);
+  if (rc) return rc;
+  DCORA_HIP(hipMemcpyAsync(Xg.p + off, Xres, sizeof(double) * (size_t)pb.nelem(), hipMemcpyDeviceToDevice, run_on));
   return DCORA_OK;
+}
+
+// Blocks whose tCG runs fit ONE launch (dense preconditioner, n / 2 co-resident workgroups): one after the other on the
+// session's stream -- 3 launches per RTR iteration each -- is faster on one device than side by side on the launches per
+// iteration (sphere2500 / 5 agents: 2420 -> see DESIGN.md block updates/s), and the two forms give the same bits.
+bool RbcdSession::serial_set(const std::vector<AgentCore *> &work) {
+  bool serial = true;
+  for (const AgentCore *a : work) serial = serial && a->prob->tcg_run_ok && a->prob->use_pc();
+  return serial;
 }
 
 int RbcdSession::pack_public(int agent, double *packed_dev) {

@@ -1,0 +1,122 @@
+// What the pose-graph session (rbcd.h) and the range-aided one (ra_rbcd.h) share, stated once: the agent state every
+// RBCD agent has, the Nesterov sequences, the colouring, and the tick (simultaneous updates of a set of agents).  It is
+// also all the in-library exchange (exchange.h) needs from a session, so the same transport -- peer stores into
+// IPC-mapped halo buffers, flag words and evaluation scalars in the shared segment -- carries both kinds (ref
+// src/Agent.cpp:113-152, 844-906: getSharedStateDicts / updateNeighborStates are the same calls on either graph type).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "device_problem.h"
+
+namespace dcora {
+
+struct AgentCore {
+  bool hosted = false;                  // lives on this rank (agent a on rank a / ceil(R / world_size))
+  std::unique_ptr<DeviceProblem> prob;  // Q_aa, its preconditioner, solver workspace (hosted agents only)
+  DevCsr coupling;                      // rows: my columns (my ordering), cols: global columns (hosted agents only)
+  DevBuf<int> public_cols;              // my columns of the mirror that OTHER agents' measurements reach (all agents)
+  int n_public_cols = 0;
+  std::vector<int> neighbors;           // agents sharing a measurement with me (all agents)
+  hipStream_t own_st = nullptr;         // stream of my solve when several agents update at once (hosted agents only;
+  hipEvent_t done = nullptr;            // both owned by the session)
+};
+
+class SessionCore {
+ public:
+  int r = 0, R = 0;  // relaxation rank (rows of the mirror), agents
+  dcora_rbcd_options opt{};
+  hipStream_t st = nullptr;
+  DevBuf<double> Xg;  // the mirror, r x num_cols() column-major: own columns current, the neighbours' public ones after
+                      // the exchange's wait
+  double gamma = 0, alpha = 0;
+  int iteration = 0;
+  DeviceProblem *last_solver = nullptr;
+  double setup_ms = 0;
+
+  explicit SessionCore(const char *tag) : tag_(tag) {}
+  virtual ~SessionCore() {}
+  virtual AgentCore &agent_core(int a) = 0;
+  virtual long num_cols() const = 0;                  // columns of the mirror (the whole problem)
+  virtual int phase_nonselected(int selected) = 0;    // Agent::iterate(false) of the hosted non-selected agents
+  virtual int phase_selected(int selected) = 0;       // Agent::iterate(true) where the selected agent lives
+  // per hosted agent a: out[2a] = |Proj(X_a Q_aa + G_a)|^2, out[2a + 1] = <X_a, X_a Q_aa + G_a> (device, 2 R doubles)
+  virtual int phase_evaluate_dev(double *out_dev) = 0;
+  virtual int set_X(const double *Xh) = 0;
+  // the hosted agents' columns of the mirror into host_area (laid out like the mirror); synchronises
+  virtual int x_stage_hosted(double *host_area) = 0;
+
+  // greedy colouring of the agent graph in agent order: agents of one colour share no measurement, so their
+  // simultaneous updates equal the same updates done one after the other
+  int agent_colours(int *colours, int *ncolours);
+  // The tick: the agents of `set` run Agent::iterate(true) at the same time, every one of them seeing the mirror as it
+  // was when the tick began (what concurrently firing agents of the asynchronous mode see, ref src/Agent.cpp:650-678;
+  // non-accelerated like that mode, :651-653).  Every agent's G, start point and XPrev are staged on the session's
+  // stream before any block goes back into the mirror, and no solve reads the mirror: for agents that share no
+  // measurement the tick equals one-after-the-other updates, for adjacent ones (allow_adjacent) it is well defined.
+  int iterate_set(const int *set, int count, int allow_adjacent);
+
+ protected:
+  const char *tag_;  // "rbcd" / "ra_rbcd": the prefix of the messages
+  hipEvent_t fork_ev_ = nullptr;
+  bool own_stream_ = true;
+
+  // updateGamma / updateAlpha (ref src/Agent.cpp:1189-1200) and the round counter; the sequences are data-independent
+  // and identical for every agent, so they live on the host
+  void advance_sequences();
+  bool restart_now() const { return opt.acceleration && ((iteration + 1) % opt.restart_interval == 0); }
+  int check_selected(int selected) const;
+
+  // the session's stream (borrowed: the caller's, never released here), an agent's stream and event, the fork event
+  int acquire_stream(void *borrowed);
+  int acquire_tick_resources(AgentCore &a);
+  int create_fork_event();
+  void release_tick_resources(AgentCore &a);  // before the agent's problem goes
+  void release_stream();  // (with the fork event) after everything that runs on it has gone
+
+  // the three things a session kind supplies to the tick
+  virtual void tick_begins() {}  // (the set is valid: per-tick resets)
+  // G = X_mirror C_a^T, the start point and XPrev of one agent, enqueued on the session's stream
+  virtual int stage(AgentCore &a) = 0;
+  // the result of a's solve into its X and the mirror, enqueued on run_on
+  virtual int write_back(AgentCore &a, hipStream_t run_on) = 0;
+  // whether the set's solves run one after the other on the session's stream instead of side by side on the agents' own
+  virtual bool serial_set(const std::vector<AgentCore *> &work) = 0;
+
+ private:
+  int solve_block(AgentCore &a, std::string *err, bool serial);
+};
+
+
+// The coloured run loop of dcora_rbcd_run_coloured / dcora_ra_rbcd_run_coloured / dcora_exchange_run_coloured: a sweep is
+// one tick per colour (tick(set, count): the agents of that colour, in agent order), colours 0, 1, ... in order, followed
+// by one evaluation (evaluate(&cost2, &gradnorm)); it stops after the first sweep whose |rgrad| < rgrad_tol or after
+// max_sweeps.  Exactly the calls a caller of iterate_set / rbcd_tick and evaluate makes (the agents that fire together in
+// the asynchronous mode, ref src/Agent.cpp:650-678, made a schedule).  Trace entry s: the evaluation after sweep s.
+template <class Tick, class Evaluate>
+int run_coloured_sweeps(const std::vector<int> &colours, int ncolours, Tick &&tick, Evaluate &&evaluate, int max_sweeps,
+                        double rgrad_tol, int *sweeps_done, double *cost2_trace, double *gradnorm_trace) {
+  std::vector<std::vector<int>> sets((size_t)ncolours);
+  for (size_t a = 0; a < colours.size(); ++a) sets[(size_t)colours[a]].push_back((int)a);
+  int s = 0;
+  while (s < max_sweeps) {
+    for (const std::vector<int> &set : sets) {
+      const int rc = tick(set.data(), (int)set.size());
+      if (rc) return rc;
+    }
+    double c2 = 0, gn = 0;
+    const int rc = evaluate(&c2, &gn);
+    if (rc) return rc;
+    if (cost2_trace) cost2_trace[s] = c2;
+    if (gradnorm_trace) gradnorm_trace[s] = gn;
+    ++s;
+    if (gn < rgrad_tol) break;
+  }
+  if (sweeps_done) *sweeps_done = s;
+  return 0;
+}
+
+}  // namespace dcora
