@@ -1000,3 +1000,129 @@ RbcdSession.agent_iterate = _agent_iterate
 RbcdSession.agent_get_X = _agent_get_X
 RbcdSession.agent_set_X = _agent_set_X
 RbcdSession.agent_info = _agent_info
+
+
+# ---- agent status and the team's decisions (ref src/Agent.cpp:558-586, 1123-1156, 1280-1330) ----
+def team_params(**kw):
+    """capi.TeamParams with the reference's defaults (ref include/DCORA/Agent.h:113-125), fields overridden by kw"""
+    p = capi.TeamParams()
+    capi.lib().dcora_team_params_default(C.byref(p))
+    for k, v in kw.items():
+        if k not in dict(capi.TeamParams._fields_):
+            raise TypeError("unknown team parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+def _as_status(s):
+    if isinstance(s, capi.AgentStatus):
+        return s
+    return capi.AgentStatus(int(s["agent_id"]), int(s.get("state", capi.AGENT_INITIALIZED)),
+                            int(s.get("instance_number", 0)), int(s["iteration_number"]),
+                            int(bool(s["ready_to_terminate"])), float(s["relative_change"]))
+
+
+def team_ready_to_terminate(params, robust, weight_update_count, success, relative_change, accepted, rejected, total):
+    """the local rule of Agent::iterate (ref src/Agent.cpp:567-585)"""
+    ready = C.c_int()
+    check(capi.lib().dcora_team_ready_to_terminate(C.byref(params), int(bool(robust)), int(weight_update_count),
+                                                   int(bool(success)), float(relative_change), int(accepted),
+                                                   int(rejected), int(total), C.byref(ready)))
+    return bool(ready.value)
+
+
+def team_decide(params, robust, iteration_number, weight_update_count, inner_iter, latest_weight_update_iteration,
+                statuses, active=None):
+    """Agent::shouldTerminate and shouldUpdateMeasurementWeights (ref src/Agent.cpp:1123-1156, 1280-1330) on the host.
+    statuses: one entry per robot -- a status (capi.AgentStatus or the dict RbcdSession.agent_status returns) or None
+    where it is absent; active: flags per robot (None: all active).  Returns (should_terminate, should_update_weights)"""
+    n = len(statuses)
+    arr = (capi.AgentStatus * max(n, 1))()
+    have = np.zeros(max(n, 1), np.int32)
+    for q, s in enumerate(statuses):
+        if s is not None:
+            arr[q] = _as_status(s)
+            have[q] = 1
+    act = None if active is None else np.ascontiguousarray(active, np.int32)
+    term, upd = C.c_int(), C.c_int()
+    check(capi.lib().dcora_team_decide(C.byref(params), int(bool(robust)), int(iteration_number),
+                                       int(weight_update_count), int(inner_iter),
+                                       int(latest_weight_update_iteration), arr, have.ctypes.data_as(C.c_void_p),
+                                       None if act is None else act.ctypes.data_as(C.c_void_p), n, C.byref(term),
+                                       C.byref(upd)))
+    return bool(term.value), bool(upd.value)
+
+
+def max_translation_distance(X, Y, d):
+    """LiftedArray::maxTranslationDistance (ref src/manifold/Elements.cpp:59-69) of two r x (d+1) n lifted pose arrays,
+    on the device by the kernel of the agents' relative change"""
+    X, Y = np.asarray(X, np.float64), np.asarray(Y, np.float64)
+    if X.shape != Y.shape or X.ndim != 2 or X.shape[1] % (d + 1):
+        raise ValueError("max_translation_distance needs two r x (d+1) n arrays")
+    out = C.c_double()
+    check(capi.lib().dcora_max_translation_distance(X.shape[0], d, X.shape[1] // (d + 1), F(X), F(Y), C.byref(out)))
+    return out.value
+
+
+def _enable_team(self, params=None, **kw):
+    """opt in to the team protocol (dcora_rbcd_team_enable): every iterate(true) of an agent stores its status"""
+    self.team = params if params is not None else team_params(**kw)
+    check(capi.lib().dcora_rbcd_team_enable(self.h, C.byref(self.team)))
+    return self.team
+
+
+def _agent_status(self, agent):
+    """the agent's AgentStatus as a dict, or None when it has not optimised since the statuses were last cleared"""
+    st, known = capi.AgentStatus(), C.c_int()
+    check(capi.lib().dcora_rbcd_agent_status(self.h, agent, C.byref(st), C.byref(known)))
+    return st.as_dict() if known.value else None
+
+
+def _loop_closure_stats(self, agent):
+    c = np.zeros(3, np.int32)
+    check(capi.lib().dcora_rbcd_loop_closure_stats(self.h, agent, c))
+    return {"accepted": int(c[0]), "rejected": int(c[1]), "total": int(c[2])}
+
+
+def _should_terminate(self):
+    yes = C.c_int()
+    check(capi.lib().dcora_rbcd_should_terminate(self.h, C.byref(yes)))
+    return bool(yes.value)
+
+
+def _should_update_weights(self):
+    yes = C.c_int()
+    check(capi.lib().dcora_rbcd_should_update_weights(self.h, C.byref(yes)))
+    return bool(yes.value)
+
+
+def _team_info(self):
+    c = np.zeros(4, np.int32)
+    check(capi.lib().dcora_rbcd_team_info(self.h, c))
+    return {"inner_iter": int(c[0]), "latest_weight_update_iteration": int(c[1]), "weight_updates": int(c[2]),
+            "resets": int(c[3])}
+
+
+def _run_team(self):
+    """the agents' own loop (dcora_rbcd_run_team): until should_terminate(), each pass re-weights when
+    should_update_weights() says so, then iterates the greedily selected agent"""
+    n = max(int(self.team.max_num_iters), 1)
+    it, nupd, why = C.c_int(), C.c_int(), C.c_int()
+    cost, gn = np.zeros(n), np.zeros(n)
+    sel, upd = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    check(capi.lib().dcora_rbcd_run_team(self.h, C.byref(it), cost.ctypes.data_as(C.c_void_p),
+                                         gn.ctypes.data_as(C.c_void_p), sel.ctypes.data_as(C.c_void_p),
+                                         upd.ctypes.data_as(C.c_void_p), C.byref(nupd), C.byref(why)))
+    k = it.value
+    return dict(iters=k, cost=cost[:k], gradnorm=gn[:k], selected=sel[:k], updated=upd[:k],
+                weight_updates=nupd.value,
+                stop_reason={capi.TEAM_STOP_ALL_READY: "all_ready", capi.TEAM_STOP_MAX_ITERS: "max_iters"}[why.value])
+
+
+RbcdSession.enable_team = _enable_team
+RbcdSession.agent_status = _agent_status
+RbcdSession.loop_closure_stats = _loop_closure_stats
+RbcdSession.should_terminate = _should_terminate
+RbcdSession.should_update_weights = _should_update_weights
+RbcdSession.team_info = _team_info
+RbcdSession.run_team = _run_team

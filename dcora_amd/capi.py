@@ -49,6 +49,27 @@ class RobustParams(C.Structure):
                 ("TLSThreshold", C.c_double)]
 
 
+class TeamParams(C.Structure):
+    _fields_ = [("max_num_iters", C.c_int), ("rel_change_tol", C.c_double), ("robust_opt_num_weight_updates", C.c_int),
+                ("robust_opt_num_resets", C.c_int), ("robust_opt_inner_iters", C.c_int),
+                ("robust_opt_min_convergence_ratio", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+AGENT_WAIT_FOR_DATA, AGENT_WAIT_FOR_INITIALIZATION, AGENT_INITIALIZED = 0, 1, 2
+TEAM_STOP_ALL_READY, TEAM_STOP_MAX_ITERS = 1, 2
+
+
+class AgentStatus(C.Structure):
+    _fields_ = [("agent_id", C.c_int), ("state", C.c_int), ("instance_number", C.c_int), ("iteration_number", C.c_int),
+                ("ready_to_terminate", C.c_int), ("relative_change", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class RbcdOptions(C.Structure):
     _fields_ = [("num_robots", C.c_int), ("r", C.c_int), ("acceleration", C.c_int), ("restart_interval", C.c_int),
                 ("local", ROptParams), ("rank", C.c_int), ("world_size", C.c_int), ("device", C.c_int),
@@ -151,6 +172,19 @@ SIGNATURES = {
     "dcora_rbcd_robust_info": (C.c_int, [_vp, _PD, _PI]),
     "dcora_rbcd_create_robust_ranks": (C.c_int, [_vp, C.POINTER(RbcdOptions), C.POINTER(RobustParams), _vp, C.c_char_p,
                                                  C.POINTER(_vp), C.POINTER(_vp)]),
+    "dcora_team_params_default": (None, [C.POINTER(TeamParams)]),
+    "dcora_team_ready_to_terminate": (C.c_int, [C.POINTER(TeamParams), C.c_int, C.c_int, C.c_int, C.c_double, C.c_int,
+                                                C.c_int, C.c_int, _PI]),
+    "dcora_team_decide": (C.c_int, [C.POINTER(TeamParams), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                    C.POINTER(AgentStatus), _vp, _vp, C.c_int, _PI, _PI]),
+    "dcora_max_translation_distance": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, _dp, _PD]),
+    "dcora_rbcd_team_enable": (C.c_int, [_vp, C.POINTER(TeamParams)]),
+    "dcora_rbcd_agent_status": (C.c_int, [_vp, C.c_int, C.POINTER(AgentStatus), _PI]),
+    "dcora_rbcd_loop_closure_stats": (C.c_int, [_vp, C.c_int, _ip]),
+    "dcora_rbcd_should_terminate": (C.c_int, [_vp, _PI]),
+    "dcora_rbcd_should_update_weights": (C.c_int, [_vp, _PI]),
+    "dcora_rbcd_team_info": (C.c_int, [_vp, _ip]),
+    "dcora_rbcd_run_team": (C.c_int, [_vp, _PI, _vp, _vp, _vp, _vp, _PI, _PI]),
     "dcora_rbcd_X_device_ptr": (C.c_int, [_vp, C.POINTER(_vp)]),
     "dcora_rbcd_public_count": (C.c_int, [_vp, C.c_int, _PI]),
     "dcora_rbcd_public_indices": (C.c_int, [_vp, C.c_int, _ip]),

@@ -1155,9 +1155,106 @@ int dcora_rbcd_agent_info(dcora_rbcd_t s, int agent, int *num_poses, int *first_
     const AgentDev &a = s->s.agents[agent];
     if (num_poses) *num_poses = a.n;
     if (first_pose) *first_pose = a.col0 / (s->s.d + 1);
-    if (iteration_number)
-      *iteration_number = (int)s->s.agent_it.size() == s->s.R ? s->s.agent_it[agent] : s->s.iteration;
+    if (iteration_number) *iteration_number = s->s.agent_iteration_number(agent);
     return (int)DCORA_OK;
+  });
+}
+// ---- agent status and the team's decisions -------------------------------------------------------------------------
+// AgentParameters' defaults of the fields the rules read (ref include/DCORA/Agent.h:113-125)
+void dcora_team_params_default(dcora_team_params *p) {
+  if (p) *p = team_params_default();
+}
+// the local termination rule of Agent::iterate (ref src/Agent.cpp:567-585)
+int dcora_team_ready_to_terminate(const dcora_team_params *params, int robust, int weight_update_count, int success,
+                                  double relative_change, int accepted, int rejected, int total, int *ready) {
+  return abi_call({params, ready}, [&] {
+    *ready = team_ready_to_terminate(*params, robust != 0, weight_update_count, success != 0, relative_change, accepted,
+                                     rejected, total) ? 1 : 0;
+    return (int)DCORA_OK;
+  });
+}
+// Agent::shouldTerminate and Agent::shouldUpdateMeasurementWeights (ref src/Agent.cpp:1123-1156, 1280-1330)
+int dcora_team_decide(const dcora_team_params *params, int robust, int iteration_number, int weight_update_count,
+                      int inner_iter, int latest_weight_update_iteration, const dcora_agent_status *statuses,
+                      const int *have, const int *active, int num_robots, int *should_terminate,
+                      int *should_update_weights) {
+  return abi_call({params}, [&] {
+    if (num_robots < 0 || (num_robots > 0 && (!statuses || !have))) return bad("null argument");
+    const TeamView v{robust != 0, iteration_number, weight_update_count, inner_iter, latest_weight_update_iteration,
+                     statuses, have, active, num_robots};
+    if (should_terminate) *should_terminate = team_should_terminate(*params, v) ? 1 : 0;
+    if (should_update_weights) *should_update_weights = team_should_update_weights(*params, v) ? 1 : 0;
+    return (int)DCORA_OK;
+  });
+}
+// LiftedArray::maxTranslationDistance (ref src/manifold/Elements.cpp:59-69) through k_rel_change
+int dcora_max_translation_distance(int r, int d, int n, const double *X, const double *Y, double *out) {
+  return abi_call({X, Y, out}, [&] { return max_translation_distance(r, d, n, X, Y, out); });
+}
+namespace {
+int team_session(dcora_rbcd_t s) {
+  return s->s.team ? (int)DCORA_OK : bad("rbcd team: the session has not called dcora_rbcd_team_enable");
+}
+}  // namespace
+// the opt-in to Agent::iterate's status block (ref src/Agent.cpp:558-586) and the bookkeeping of :1417-1424
+int dcora_rbcd_team_enable(dcora_rbcd_t s, const dcora_team_params *params) {
+  return abi_call({s, params}, [&] { return s->s.team_enable(*params); });
+}
+// Agent::getStatus (ref include/DCORA/Agent.h:427-433) of one agent of the session
+int dcora_rbcd_agent_status(dcora_rbcd_t s, int agent, dcora_agent_status *status, int *known) {
+  return abi_call({s, status}, [&] {
+    const int rc = team_session(s);
+    if (rc) return rc;
+    if (!agent_ok(s, agent)) return bad("bad agent");
+    return s->s.team_agent_status(agent, status, known);
+  });
+}
+// Graph::statistics (ref src/Graph.cpp:475-521) of one agent
+int dcora_rbcd_loop_closure_stats(dcora_rbcd_t s, int agent, int counts[3]) {
+  return abi_call({s, counts}, [&] {
+    const int rc = team_session(s);
+    if (rc) return rc;
+    if (!agent_ok(s, agent)) return bad("bad agent");
+    for (int c = 0; c < 3; ++c) counts[c] = s->s.team->lc[(size_t)agent * 3 + c];
+    return (int)DCORA_OK;
+  });
+}
+// Agent::shouldTerminate (ref src/Agent.cpp:1123-1156) over the statuses the session holds
+int dcora_rbcd_should_terminate(dcora_rbcd_t s, int *yes) {
+  return abi_call({s, yes}, [&] {
+    const int rc = team_session(s);
+    return rc ? rc : s->s.team_decide(yes, nullptr);
+  });
+}
+// Agent::shouldUpdateMeasurementWeights (ref src/Agent.cpp:1280-1330) over the statuses the session holds
+int dcora_rbcd_should_update_weights(dcora_rbcd_t s, int *yes) {
+  return abi_call({s, yes}, [&] {
+    const int rc = team_session(s);
+    return rc ? rc : s->s.team_decide(nullptr, yes);
+  });
+}
+// mRobustOptInnerIter, mLatestWeightUpdateIteration, mWeightUpdateCount, mTrajectoryResetCount (ref
+// include/DCORA/Agent.h:720-735)
+int dcora_rbcd_team_info(dcora_rbcd_t s, int info[4]) {
+  return abi_call({s, info}, [&] {
+    const int rc = team_session(s);
+    if (rc) return rc;
+    info[0] = s->s.team_inner_iter();
+    info[1] = s->s.team->latest_weight_update_iteration;
+    info[2] = s->s.team_weight_updates();
+    info[3] = s->s.team->resets_done;
+    return (int)DCORA_OK;
+  });
+}
+// the optimisation loop of the agents (ref src/Agent.cpp:650-678 with :1123-1156, 1280-1330, 1397-1441) on the
+// synchronous schedule of dcora_rbcd_run
+int dcora_rbcd_run_team(dcora_rbcd_t s, int *iters_done, double *cost2_trace, double *gradnorm_trace,
+                        int *selected_trace, int *updated_trace, int *weight_updates, int *stop_reason) {
+  return abi_call({s}, [&] {
+    const int rc = team_session(s);
+    return rc ? rc
+              : s->s.run_team(iters_done, cost2_trace, gradnorm_trace, selected_trace, updated_trace, weight_updates,
+                              stop_reason);
   });
 }
 int dcora_rbcd_last_result(dcora_rbcd_t s, dcora_ropt_result *res) {

@@ -286,6 +286,15 @@ void launch_eval_finish(hipStream_t st, int R, const int *pose_start, const doub
                         int npA, EvalOut *out_dev, int seq, double *split_scratch = nullptr, int nposes = 0,
                         const double *agent_partials = nullptr, int wg_per_agent = 0);
 int eval_split_doubles();
+// ---- agent status (team_status.hip): out[b] = max over agent b's poses of |t_i(X) - t_i(XPrev)| for the agents of the
+// set, one launch (k_rel_change); X / XPrev laid out like the mirror, pose_start: the agents' global pose offsets
+struct RelChangeSet {
+  int count;
+  int agent[kMaxAgents];
+};
+void launch_rel_change(hipStream_t st, int r, int d, const double *X, const double *XPrev, const int *pose_start,
+                       const RelChangeSet &set, double *out);
+int max_translation_distance(int r, int d, int n, const double *X, const double *Y, double *out);
 int launch_g_retract(hipStream_t st, const ManiDesc &m, Buf2 X, const double *V, double alpha, Buf2 out, int selOut,
                      Buf2 grad, const double *HV, double *partials, Gate g);
 void launch_g_nesterov(hipStream_t st, const ManiDesc &m, int mode, int restart, int skip_lo, int skip_hi,

@@ -13,6 +13,7 @@
 #include "host_robust.h"
 #include "robust.h"
 #include "session_core.h"
+#include "team_rules.h"
 
 namespace dcora {
 
@@ -53,6 +54,31 @@ struct RobustSession {
   DevBuf<double> X_initial;      // the last set_X (robustOptNumResets: setXToInitialGuess)
   std::vector<HostCsr> Qpat, Cpat;  // creation patterns (rp, ci) of every hosted agent's Q_bb and coupling block
   HostCsr central_pat;
+};
+
+// Team protocol of a session that called dcora_rbcd_team_enable: every agent's status as Agent::iterate(true) stores it
+// (ref src/Agent.cpp:558-586) and the bookkeeping Agent::updateMeasurementWeights does on it (:1417-1424).  The relative
+// change comes from k_rel_change through host-mapped memory: a status is `pending` from its launch until the host has
+// seen the stream pass it (the evaluation epilogue's seq, or a synchronisation in the query), then it is settled by
+// team_ready_to_terminate with what the agent knew when it optimised.
+struct TeamState {
+  dcora_team_params params{};
+  double *rel_host = nullptr, *rel_dev = nullptr;  // kMaxAgents relative changes, written by k_rel_change
+  TeamState() = default;
+  TeamState(const TeamState &) = delete;
+  TeamState &operator=(const TeamState &) = delete;
+  ~TeamState() {
+    if (rel_host) (void)hipHostFree((void *)rel_host);
+  }
+  std::vector<dcora_agent_status> status;          // by agent; have[b] == 0: none since the last clear
+  std::vector<int> have;
+  struct Pending {
+    bool on = false, success = false;
+    int updates = 0, lc[3] = {0, 0, 0};
+  };
+  std::vector<Pending> pending;
+  std::vector<int> lc;  // 3 per agent: accepted, rejected, all loop closures (Graph::statistics, ref src/Graph.cpp:475-521)
+  int latest_weight_update_iteration = 0, resets_done = 0;
 };
 
 class RbcdSession : public SessionCore {
@@ -105,6 +131,17 @@ class RbcdSession : public SessionCore {
   // count poses of `neighbor` (frames local to it, each r x (d+1) column-major in `poses`) handed to `agent`
   int agent_update_neighbor(int agent, int neighbor, int count, const int *frames, const double *poses, bool aux);
   std::vector<int> agent_it;  // Agent::iteration_number() of every agent
+  int agent_iteration_number(int agent) const;
+  // ---- the team protocol (dcora_rbcd_team_enable) ----
+  std::unique_ptr<TeamState> team;
+  int team_enable(const dcora_team_params &p);
+  int team_agent_status(int agent, dcora_agent_status *status, int *known);
+  int team_decide(int *should_terminate, int *should_update_weights);
+  bool team_robust() const { return robust && robust->params.cost_type != DCORA_ROBUST_L2; }
+  int team_weight_updates() const { return robust ? robust->updates : 0; }
+  int team_inner_iter() const { return team_robust() ? inner_rounds : 0; }
+  int run_team(int *iters_done, double *cost2_trace, double *gradnorm_trace, int *selected_trace, int *updated_trace,
+               int *weight_updates, int *stop_reason);
   int pack_public(int agent, double *packed_dev);
   int unpack_public(int agent, const double *packed_dev);
 
@@ -126,6 +163,17 @@ class RbcdSession : public SessionCore {
   int stage(AgentCore &a) override;
   int write_back(AgentCore &a, hipStream_t run_on) override;
   bool serial_set(const std::vector<AgentCore *> &work) override;
+  int tick_done(const std::vector<AgentCore *> &work) override;
+  // the team protocol's steps: agents that just ran iterate(true) (one k_rel_change launch behind their updates),
+  // pending statuses settled (visible: the host has already seen the stream pass their launch), the loop-closure
+  // counts after a weight change, the statuses cleared, the bookkeeping restarted with the round counter
+  int team_note_optimized(const int *ids, int count);
+  int team_settle(bool visible);
+  void team_refresh_counts();
+  void team_clear_statuses();
+  void team_restart_rounds();
+  std::vector<int> lc_id_, lc_r1_, lc_r2_;  // the loop closures (every measurement but odometry): index, agents of its ends
+  std::vector<double> lc_w0_;               // their weights at creation (a session without robust state keeps them)
   // session assembly (rbcd.hip): the host matrices of the hosted agents -- Q[i] = Q_bb, C[i] = coupling block of agent
   // ids[i] -- as the host builders give them
   struct MeasSplit;

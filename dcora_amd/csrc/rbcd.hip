@@ -78,6 +78,7 @@ struct RbcdSession::MeasSplit {
 RbcdSession::~RbcdSession() {
   if (eval_host) (void)hipHostFree((void *)eval_host);
   if (x_stage) (void)hipHostFree((void *)x_stage);
+  team.reset();
   for (AgentDev &a : agents) release_tick_resources(a);
   agents.clear();
   central.reset();
@@ -141,6 +142,15 @@ int RbcdSession::init(const HostDataset &ds, const dcora_rbcd_options &o) {
 
   lap("buffers");
   const MeasSplit split(ds.meas, P);
+  for (size_t e = 0; e < ds.meas.size(); ++e) {
+    const PoseMeas &q = ds.meas[e];
+    const int r1 = P.robot_of(q.p1), r2 = P.robot_of(q.p2);
+    if (r1 == r2 && q.p2 == q.p1 + 1) continue;  // odometry
+    lc_id_.push_back((int)e);
+    lc_r1_.push_back(r1);
+    lc_r2_.push_back(r2);
+    lc_w0_.push_back(q.weight);
+  }
   agents.resize(R);
   std::vector<int> cs(R + 1);
   for (int b = 0; b < R; ++b) {
@@ -309,6 +319,7 @@ int RbcdSession::set_X(const double *Xh) {
   pending_reset_ = false;
   agent_it.assign(R, 0);
   set_marks_.assign(R, 0);
+  team_restart_rounds();
   for (AgentDev &a : agents) a.v_feasible = false;  // V = X as handed over: projected in the next round
   return DCORA_OK;
 }
@@ -327,6 +338,7 @@ int RbcdSession::set_acceleration(bool on) {
   pending_reset_ = false;
   agent_it.assign(R, 0);
   set_marks_.assign(R, 0);
+  team_restart_rounds();
   for (AgentDev &a : agents) a.v_feasible = false;
   return DCORA_OK;
 }
@@ -536,6 +548,7 @@ int RbcdSession::adopt_weights(std::vector<PoseMeas> &meas, bool from_device, bo
     DCORA_HIP(hipMemcpy(rs.edges.w.p, held.data(), sizeof(double) * m, hipMemcpyHostToDevice));
   }
   if (rc) return rc;
+  if (team) team_refresh_counts();
   if (reset_to_initial)
     DCORA_HIP(hipMemcpyAsync(Xg.p, rs.X_initial.p, sizeof(double) * (size_t)r * (d + 1) * n, hipMemcpyDeviceToDevice, st));
   return initialize_acceleration();
@@ -549,6 +562,12 @@ int RbcdSession::apply_weights(const std::vector<double> &w, bool reset_to_initi
   if (rc) return rc;
   rs.cost.update();
   rs.updates++;
+  // mLatestWeightUpdateIteration, mRobustOptInnerIter = 0, mTeamStatus.clear() (ref src/Agent.cpp:1418-1424)
+  inner_rounds = 0;
+  if (team) {
+    team->latest_weight_update_iteration = iteration;
+    team_clear_statuses();
+  }
   return DCORA_OK;
 }
 
@@ -631,7 +650,8 @@ int RbcdSession::phase_selected(int selected) {
   const bool restart = restart_now();
   AgentDev &a = agents[selected];
   if (a.hosted) {
-    const int rc = update_selected_agent(a, restart);
+    int rc = update_selected_agent(a, restart);
+    if (!rc && team) rc = team_note_optimized(&selected, 1);
     if (rc) return rc;
   }
   if (restart) gamma = alpha = 0;
@@ -763,6 +783,7 @@ int RbcdSession::agent_iterate(int agent, bool do_optimization) {
   int rc;
   if (do_optimization) {
     rc = update_selected_agent(a, restart);
+    if (!rc && team) rc = team_note_optimized(&agent, 1);
   } else {
     rc = opt.acceleration ? update_nonselected_agent(a, restart) : DCORA_OK;
   }
@@ -867,6 +888,7 @@ int RbcdSession::agent_set_X(int agent, const double *Xh) {
     pending_reset_ = false;
     agent_it.assign(R, 0);
     set_marks_.assign(R, 0);
+    team_restart_rounds();
   }
   return DCORA_OK;
 }
@@ -913,7 +935,7 @@ int RbcdSession::evaluate_central(double *cost2, double *gradnorm, double *block
     if (cost2) *cost2 = eval_host->cost2;
     if (gradnorm) *gradnorm = eval_host->gradnorm;
     if (next_selected) *next_selected = eval_host->next;
-    return DCORA_OK;
+    return team ? team_settle(true) : (int)DCORA_OK;
   }
   launch_rgrad(st, mg, buf1(Xg.p), buf1(c.EG0.p), buf1(c.RG0.p), Buf2{{nullptr, nullptr}}, 0, c.pB.p, Gate{});
   launch_block_dots(st, r, R, col_start.p, c.RG0.p, nullptr, evalbuf.p);
@@ -935,7 +957,7 @@ int RbcdSession::evaluate_central(double *cost2, double *gradnorm, double *block
   if (cost2) *cost2 = 2.0 * (0.5 * h[2 * R] + h[2 * R + 1]);
   if (gradnorm) *gradnorm = std::sqrt(g2);
   if (next_selected) *next_selected = arg;
-  return DCORA_OK;
+  return team ? team_settle(true) : (int)DCORA_OK;
 }
 
 int RbcdSession::last_result(dcora_ropt_result *res) {
@@ -1023,6 +1045,13 @@ bool RbcdSession::serial_set(const std::vector<AgentCore *> &work) {
   return serial;
 }
 
+int RbcdSession::tick_done(const std::vector<AgentCore *> &work) {
+  if (!team) return DCORA_OK;
+  std::vector<int> ids;
+  for (const AgentCore *a : work) ids.push_back(static_cast<const AgentDev *>(a)->id);
+  return team_note_optimized(ids.data(), (int)ids.size());
+}
+
 int RbcdSession::pack_public(int agent, double *packed_dev) {
   AgentDev &a = agents[agent];
   launch_gather_cols(st, r, (int)a.public_poses.size() * (d + 1), a.public_cols.p, Xg.p, packed_dev);
@@ -1043,6 +1072,178 @@ int RbcdSession::x_stage_hosted(double *host_area) {
                              hipMemcpyDeviceToHost, st));
   }
   DCORA_HIP(hipStreamSynchronize(st));
+  return DCORA_OK;
+}
+
+// ---- the team protocol ----------------------------------------------------------------------------------------------
+// Agent::iteration_number() of one agent: its own count inside a round of per-agent calls, the session's round counter
+// whenever the agents are level (the session-level calls advance whole rounds without touching agent_it)
+int RbcdSession::agent_iteration_number(int agent) const {
+  if ((int)agent_it.size() != R) return iteration;
+  for (int q = 0; q < R; ++q)
+    if (agents[(size_t)q].hosted && agent_it[(size_t)q] != agent_it[(size_t)agent]) return agent_it[(size_t)agent];
+  return iteration;
+}
+
+int RbcdSession::team_enable(const dcora_team_params &p) {
+  if (opt.world_size != 1) {
+    set_last_error("rbcd team: only single-process sessions (world_size 1) keep the team's statuses; the ranks of a "
+                   "job exchange their flags with dcora_exchange_all_ready");
+    return DCORA_ERR_UNSUPPORTED;
+  }
+  if (!team) {
+    std::unique_ptr<TeamState> t(new TeamState);
+    DCORA_HIP(hipSetDevice(opt.device));
+    DCORA_HIP(hipHostMalloc((void **)&t->rel_host, sizeof(double) * kMaxAgents, hipHostMallocMapped));
+    std::memset((void *)t->rel_host, 0, sizeof(double) * kMaxAgents);
+    DCORA_HIP(hipHostGetDevicePointer((void **)&t->rel_dev, (void *)t->rel_host, 0));
+    team = std::move(t);
+    team_clear_statuses();
+    team->latest_weight_update_iteration = 0;
+    team_refresh_counts();
+  }
+  team->params = p;
+  return DCORA_OK;
+}
+
+void RbcdSession::team_clear_statuses() {
+  if (!team) return;
+  team->status.assign((size_t)R, dcora_agent_status{});
+  team->have.assign((size_t)R, 0);
+  team->pending.assign((size_t)R, TeamState::Pending());
+}
+
+// the round counter restarts (set_X, set_acceleration, Agent::setX of every agent): what the team counts in rounds
+// restarts with it
+void RbcdSession::team_restart_rounds() {
+  inner_rounds = 0;
+  if (!team) return;
+  team->latest_weight_update_iteration = 0;
+  team_clear_statuses();
+}
+
+void RbcdSession::team_refresh_counts() {
+  team->lc.assign((size_t)R * 3, 0);
+  auto count = [&](int b, double w) {
+    int *c = &team->lc[(size_t)b * 3];
+    if (w == 1) c[0]++;
+    else if (w == 0) c[1]++;
+    c[2]++;
+  };
+  for (size_t k = 0; k < lc_id_.size(); ++k) {
+    const double w = robust ? robust->meas[(size_t)lc_id_[k]].weight : lc_w0_[k];
+    count(lc_r1_[k], w);
+    if (lc_r2_[k] != lc_r1_[k]) count(lc_r2_[k], w);
+  }
+}
+
+// Agent::iterate's status block (ref src/Agent.cpp:558-586) for the agents that just optimised: one launch behind
+// everything their updates enqueued on the session's stream, compares the X the round leaves with the XPrev it saved
+int RbcdSession::team_note_optimized(const int *ids, int count) {
+  RelChangeSet set{};
+  for (int i = 0; i < count && set.count < kMaxAgents; ++i) {
+    const int b = ids[i];
+    if (b < 0 || b >= R || !agents[(size_t)b].hosted) continue;
+    set.agent[set.count++] = b;
+    dcora_agent_status &s = team->status[(size_t)b];
+    s.agent_id = b;
+    s.state = DCORA_AGENT_INITIALIZED;
+    s.instance_number = 0;
+    s.iteration_number = iteration;
+    s.ready_to_terminate = 0;
+    s.relative_change = 0;
+    team->have[(size_t)b] = 1;
+    TeamState::Pending &p = team->pending[(size_t)b];
+    p.on = true;
+    p.success = !agents[(size_t)b].last_skipped;
+    p.updates = team_weight_updates();
+    for (int c = 0; c < 3; ++c) p.lc[c] = team->lc[(size_t)b * 3 + c];
+  }
+  launch_rel_change(st, r, d, Xg.p, XPrevg.p, pose_start.p, set, team->rel_dev);
+  DCORA_HIP(hipGetLastError());
+  return DCORA_OK;
+}
+
+int RbcdSession::team_settle(bool visible) {
+  bool any = false;
+  for (const TeamState::Pending &p : team->pending) any = any || p.on;
+  if (!any) return DCORA_OK;
+  if (!visible) {
+    DCORA_HIP(hipSetDevice(opt.device));
+    DCORA_HIP(hipStreamSynchronize(st));
+  }
+  std::atomic_thread_fence(std::memory_order_acquire);
+  for (int b = 0; b < R; ++b) {
+    TeamState::Pending &p = team->pending[(size_t)b];
+    if (!p.on) continue;
+    p.on = false;
+    dcora_agent_status &s = team->status[(size_t)b];
+    s.relative_change = const_cast<const volatile double *>(team->rel_host)[b];
+    s.ready_to_terminate = team_ready_to_terminate(team->params, team_robust(), p.updates, p.success,
+                                                   s.relative_change, p.lc[0], p.lc[1], p.lc[2]) ? 1 : 0;
+  }
+  return DCORA_OK;
+}
+
+int RbcdSession::team_agent_status(int agent, dcora_agent_status *status, int *known) {
+  const int rc = team_settle(false);
+  if (rc) return rc;
+  if (team->have[(size_t)agent]) {
+    *status = team->status[(size_t)agent];
+  } else {
+    *status = dcora_agent_status{};
+    status->agent_id = agent;
+    status->state = DCORA_AGENT_INITIALIZED;
+    status->iteration_number = agent_iteration_number(agent);
+  }
+  if (known) *known = team->have[(size_t)agent];
+  return DCORA_OK;
+}
+
+int RbcdSession::team_decide(int *should_terminate, int *should_update_weights) {
+  const int rc = team_settle(false);
+  if (rc) return rc;
+  const TeamView v{team_robust(), iteration, team_weight_updates(), team_inner_iter(),
+                   team->latest_weight_update_iteration, team->status.data(), team->have.data(), nullptr, R};
+  if (should_terminate) *should_terminate = team_should_terminate(team->params, v) ? 1 : 0;
+  if (should_update_weights) *should_update_weights = team_should_update_weights(team->params, v) ? 1 : 0;
+  return DCORA_OK;
+}
+
+// the agents' own loop (ref src/Agent.cpp:650-678 shape, the synchronous schedule of examples/MultiRobotExample.cpp):
+// stop and re-weight by the team rules instead of a central gradient norm and fixed counts
+int RbcdSession::run_team(int *iters_done, double *cost2_trace, double *gradnorm_trace, int *selected_trace,
+                          int *updated_trace, int *weight_updates, int *stop_reason) {
+  const int cap = team->params.max_num_iters;
+  int selected = 0, it = 0, nupd = 0;
+  for (;;) {
+    int stop = 0, upd = 0;
+    int rc = team_decide(&stop, nullptr);
+    if (rc) return rc;
+    if (stop || it >= cap) break;
+    rc = team_decide(nullptr, &upd);
+    if (rc) return rc;
+    if (updated_trace) updated_trace[it] = upd;
+    if (upd) {
+      const bool reset = team->resets_done < team->params.robust_opt_num_resets;
+      rc = update_weights(reset, nullptr);
+      if (rc) return rc;
+      if (reset) team->resets_done++;
+      nupd++;
+    }
+    double c2 = 0, gn = 0;
+    int nxt = selected;
+    rc = iterate(selected, &c2, &gn, nullptr, &nxt);
+    if (rc) return rc;
+    if (cost2_trace) cost2_trace[it] = c2;
+    if (gradnorm_trace) gradnorm_trace[it] = gn;
+    if (selected_trace) selected_trace[it] = selected;
+    selected = nxt;
+    ++it;
+  }
+  if (iters_done) *iters_done = it;
+  if (weight_updates) *weight_updates = nupd;
+  if (stop_reason) *stop_reason = iteration >= cap ? DCORA_TEAM_STOP_MAX_ITERS : DCORA_TEAM_STOP_ALL_READY;
   return DCORA_OK;
 }
 

@@ -34,6 +34,7 @@ class SessionCore {
                       // the exchange's wait
   double gamma = 0, alpha = 0;
   int iteration = 0;
+  int inner_rounds = 0;  // rounds since the owner last zeroed it (Agent::mRobustOptInnerIter, ref src/Agent.cpp:537-538)
   DeviceProblem *last_solver = nullptr;
   double setup_ms = 0;
 
@@ -85,6 +86,8 @@ class SessionCore {
   virtual int write_back(AgentCore &a, hipStream_t run_on) = 0;
   // whether the set's solves run one after the other on the session's stream instead of side by side on the agents' own
   virtual bool serial_set(const std::vector<AgentCore *> &work) = 0;
+  // the tick's updates are all enqueued (the session's stream waits for every one of them)
+  virtual int tick_done(const std::vector<AgentCore *> &work) { return DCORA_OK; }
 
  private:
   int solve_block(AgentCore &a, std::string *err, bool serial);

@@ -10,6 +10,7 @@ namespace dcora {
 
 void SessionCore::advance_sequences() {
   iteration++;
+  inner_rounds++;
   if (opt.acceleration) {
     gamma = (1 + std::sqrt(1 + 4.0 * R * R * gamma * gamma)) / (2.0 * R);
     alpha = 1.0 / (gamma * R);
@@ -111,6 +112,7 @@ int SessionCore::iterate_set(const int *set, int count, int allow_adjacent) {
         }
   DCORA_HIP(hipSetDevice(opt.device));
   iteration++;
+  inner_rounds++;
   tick_begins();
   std::vector<AgentCore *> work;
   for (int i = 0; i < count; ++i)
@@ -133,7 +135,7 @@ int SessionCore::iterate_set(const int *set, int count, int allow_adjacent) {
       if (failed(i)) return rcs[i];
     }
     last_solver = work.back()->prob.get();
-    return DCORA_OK;
+    return tick_done(work);
   }
   DCORA_HIP(hipEventRecord(fork_ev_, st));
   for (AgentCore *a : work) DCORA_HIP(hipStreamWaitEvent(a->own_st, fork_ev_, 0));
@@ -149,7 +151,7 @@ int SessionCore::iterate_set(const int *set, int count, int allow_adjacent) {
     if (failed(i)) return rcs[i];
     DCORA_HIP(hipStreamWaitEvent(st, work[i]->done, 0));
   }
-  return DCORA_OK;
+  return tick_done(work);
 }
 
 }  // namespace dcora

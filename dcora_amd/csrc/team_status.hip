@@ -1,0 +1,85 @@
+// The relative change of an agent's update on the device: LiftedArray::maxTranslationDistance(X, XPrev) of
+// Agent::iterate's status (ref src/Agent.cpp:564-565, src/manifold/Elements.cpp:59-69).
+#include "device_problem.h"
+#include "kernels.h"
+
+namespace dcora {
+
+// max over the 64 lanes, same value in every lane (the moves of wave_sum_dpp; a maximum does not depend on the order)
+__device__ __forceinline__ double wave_max_dpp(double v) {
+  v = fmax(v, dpp_move<0xB1>(v));   // quad_perm [1,0,3,2]
+  v = fmax(v, dpp_move<0x4E>(v));   // quad_perm [2,3,0,1]
+  v = fmax(v, dpp_move<0x141>(v));  // row_half_mirror
+  v = fmax(v, dpp_move<0x140>(v));  // row_mirror
+  return fmax(fmax(readlane_f64(v, 0), readlane_f64(v, 16)), fmax(readlane_f64(v, 32), readlane_f64(v, 48)));
+}
+
+// One workgroup per agent of the set, striding over the agent's poses: out[b] = max_i |t_i(X_b) - t_i(XPrev_b)|_2.
+// Translation i is column (d+1) i + d of the mirror: r contiguous doubles.  The norm of a pose is the square root of
+// its r squares summed in index order by one thread, the maximum of those is exact in any order: the result's bits do
+// not depend on the schedule, and nothing is atomic.  `out` may be host-mapped: the store is followed by a system fence,
+// so whatever the stream publishes next (the evaluation epilogue's seq) is seen after it.
+__global__ __launch_bounds__(kBlock) void k_rel_change(int r, int dh, const double *__restrict__ X,
+                                                       const double *__restrict__ XPrev,
+                                                       const int *__restrict__ pose_start, RelChangeSet set,
+                                                       double *out) {
+  __shared__ double s_max[kBlock / 64];
+  const int b = set.agent[blockIdx.x];
+  const int lo = pose_start[b], hi = pose_start[b + 1];
+  double m = 0;
+  for (int i = lo + (int)threadIdx.x; i < hi; i += kBlock) {
+    const size_t o = ((size_t)i * dh + (dh - 1)) * r;
+    double s = 0;
+    for (int k = 0; k < r; ++k) {
+      const double e = X[o + k] - XPrev[o + k];
+      s += e * e;
+    }
+    m = fmax(m, sqrt(s));
+  }
+  m = wave_max_dpp(m);
+  if ((threadIdx.x & 63) == 0) s_max[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < kBlock / 64; ++w) m = fmax(m, s_max[w]);
+    out[b] = m;
+    __threadfence_system();
+  }
+}
+
+void launch_rel_change(hipStream_t st, int r, int d, const double *X, const double *XPrev, const int *pose_start,
+                       const RelChangeSet &set, double *out) {
+  if (set.count < 1) return;
+  hipLaunchKernelGGL(k_rel_change, dim3(set.count), dim3(kBlock), 0, st, r, d + 1, X, XPrev, pose_start, set, out);
+}
+
+// LiftedArray::maxTranslationDistance of two host arrays through the same kernel (one agent holding all n poses)
+int max_translation_distance(int r, int d, int n, const double *X, const double *Y, double *out) {
+  if (r < 2 || r > 16 || (d != 2 && d != 3) || d > r || n < 1) {
+    set_last_error("max_translation_distance: needs 2 <= r <= 16, d in {2, 3}, d <= r, n >= 1");
+    return DCORA_ERR_BAD_ARG;
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+    set_last_error("no HIP device available: libdcora_hip has no CPU fallback");
+    return DCORA_ERR_NO_DEVICE;
+  }
+  const size_t N = (size_t)r * (d + 1) * n;
+  DevBuf<double> dX, dY, dout;
+  DevBuf<int> dps;
+  DCORA_HIP(dX.alloc(N));
+  DCORA_HIP(dY.alloc(N));
+  DCORA_HIP(dout.alloc(1));
+  DCORA_HIP(dps.alloc(2));
+  const int ps[2] = {0, n};
+  DCORA_HIP(hipMemcpy(dX.p, X, sizeof(double) * N, hipMemcpyHostToDevice));
+  DCORA_HIP(hipMemcpy(dY.p, Y, sizeof(double) * N, hipMemcpyHostToDevice));
+  DCORA_HIP(hipMemcpy(dps.p, ps, sizeof(ps), hipMemcpyHostToDevice));
+  RelChangeSet set{};
+  set.count = 1;
+  launch_rel_change(nullptr, r, d, dX.p, dY.p, dps.p, set, dout.p);
+  DCORA_HIP(hipGetLastError());
+  DCORA_HIP(hipMemcpy(out, dout.p, sizeof(double), hipMemcpyDeviceToHost));
+  return DCORA_OK;
+}
+
+}  // namespace dcora

@@ -209,6 +209,35 @@ def multi_robot_gnc_session(ds, X0, num_robots=5, r=5, robust=None, num_weight_u
                      close=s.close)
 
 
+def multi_robot_team_session(ds, X0, num_robots=5, r=5, robust=None, team=None, acceleration=True, params=None,
+                             fixed=None, device=0):
+    """multi_robot_gnc_session's robust flow driven by the agents' own rules instead of fixed counts (ref
+    src/Agent.cpp:558-586, 1123-1156, 1280-1441): RbcdSession.run_team re-weights when every agent has converged since
+    the last update (or the inner iterations run out) and stops when all agents are ready after the required number of
+    updates, or at max_num_iters.  team: a capi.TeamParams (default: the reference's, team_params()).
+
+    ds.vals[:, -1] (the weights) is updated in place.  Returns X, weights, the run's record and the final statuses."""
+    from . import robust as rb
+    from . import team_params
+    s = RbcdSession(ds, num_robots=num_robots, r=r, acceleration=acceleration, params=params, device=device,
+                    robust=robust or rb.RobustCostParameters("GNC_TLS"), fixed_weight=fixed)
+    try:
+        s.enable_team(team if team is not None else team_params())
+        s.set_X(np.asarray(X0, dtype=np.float64))
+        out = s.run_team()
+        X, w = s.get_X(), s.get_weights()
+        statuses = [s.agent_status(q) for q in range(num_robots)]
+        stats = [s.loop_closure_stats(q) for q in range(num_robots)]
+    finally:
+        s.close()
+    ds.vals[:, -1] = w
+    return {"X": X, "weights": w.copy(), "loop_closures": _gnc_mask(ds, num_robots, fixed), "run": out,
+            "statuses": statuses, "loop_closure_stats": stats,
+            "final": {"iterations": int(out["iters"]), "cost_2f": float(out["cost"][-1]) if out["iters"] else None,
+                      "gradnorm": float(out["gradnorm"][-1]) if out["iters"] else None,
+                      "weight_updates": int(out["weight_updates"]), "stop_reason": out["stop_reason"]}}
+
+
 def exchange_run(ex, max_iters=1000, rgrad_tol=0.1):
     """RbcdSession.run across the ranks: greedy passes through Exchange.iterate until |rgrad| < rgrad_tol, at most
     max_iters (the loop of dcora_rbcd_run, ref examples/MultiRobotExample.cpp:223-307)"""

@@ -32,6 +32,7 @@
 // plain / auxiliary caches on the device: stale poses are used as given, poses it does not require are ignored, an
 // incomplete cache skips the optimisation, ref src/Agent.cpp:844-906, 1234-1249).
 #pragma once
+#include <algorithm>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -75,6 +76,21 @@ struct AgentParameters {
   std::string logDirectory;
   int device = 0;
   GraphType graphType = GraphType::PoseGraph;
+  // the team rules' parameters (ref include/DCORA/Agent.h:113-125, the reference's defaults)
+  unsigned maxNumIters = 500;
+  double relChangeTol = 5e-3;
+  unsigned robustOptNumWeightUpdates = 10, robustOptNumResets = 0, robustOptInnerIters = 30;
+  double robustOptMinConvergenceRatio = 0.8;
+  dcora_team_params teamParams() const {
+    dcora_team_params p;
+    p.max_num_iters = (int)maxNumIters;
+    p.rel_change_tol = relChangeTol;
+    p.robust_opt_num_weight_updates = (int)robustOptNumWeightUpdates;
+    p.robust_opt_num_resets = (int)robustOptNumResets;
+    p.robust_opt_inner_iters = (int)robustOptInnerIters;
+    p.robust_opt_min_convergence_ratio = robustOptMinConvergenceRatio;
+    return p;
+  }
   AgentTeamHandle team;  // pose graphs, several robots: the caller's handle (makeAgentTeam()), the same in every robot's
   AgentParameters(unsigned dIn, unsigned rIn, const std::set<unsigned> &robotIDsIn,
                   GraphType graphTypeIn = GraphType::PoseGraph)
@@ -119,6 +135,9 @@ class AgentTeam : public std::enable_shared_from_this<AgentTeam> {
     o.local = params_.localOptimizationParams.c();
     o.device = params_.device;
     check_status(dcora_rbcd_create(dataset, &o, &session_), "AgentTeam");
+    // every iterate(true) stores the agent's status (ref src/Agent.cpp:558-586): what getStatus() hands out
+    const dcora_team_params tp = params_.teamParams();
+    check_status(dcora_rbcd_team_enable(session_, &tp), "AgentTeam");
   }
   void build_agents();
   AgentParameters params_;
@@ -390,14 +409,38 @@ class Agent {
                  "updateNeighborStates");
   }
   // ref include/DCORA/Agent.h:380-400: what the drivers pass around with the dictionaries
+  // (pose graphs: relativeChange and readyToTerminate are what the agent's last iterate(true) stored in the session,
+  // ref src/Agent.cpp:558-586)
   AgentStatus getStatus() {
     AgentStatus st;
     st.agentID = mID;
     st.state = (map_agent_ || !ra_ || ra_->initialized()) ? AgentState::INITIALIZED : AgentState::WAIT_FOR_INITIALIZATION;
+    st.instanceNumber = instance_number();
     st.iterationNumber = iteration_number();
+    if (!map_agent_ && !ra_) {
+      dcora_agent_status cs;
+      int known = 0;
+      check_status(dcora_rbcd_agent_status(session(), (int)mID, &cs, &known), "getStatus");
+      if (known) {
+        st.readyToTerminate = cs.ready_to_terminate != 0;
+        st.relativeChange = cs.relative_change;
+      }
+    }
     return st;
   }
   void setNeighborStatus(const AgentStatus &status) { neighbor_status_[status.agentID] = status; }
+  // ref include/DCORA/Agent.h:436-451
+  bool hasNeighborStatus(unsigned neighborID) const { return neighbor_status_.count(neighborID) != 0; }
+  AgentStatus getNeighborStatus(unsigned neighborID) const {
+    const auto it = neighbor_status_.find(neighborID);
+    if (it == neighbor_status_.end()) throw std::out_of_range("getNeighborStatus: no status of that robot");
+    return it->second;
+  }
+  // ref src/Agent.cpp:1123-1156 and 1280-1330: the team rules (dcora_team_decide) over this agent's own status and the
+  // statuses setNeighborStatus handed it; a robot whose status was never handed is absent.  (The facade's sessions
+  // optimise the L2 cost: shouldUpdateMeasurementWeights is false, as the reference's first test makes it.)
+  bool shouldTerminate() { return decide(true); }
+  bool shouldUpdateMeasurementWeights() { return decide(false); }
   // ref src/Agent.cpp:535 getSharedPose(index): pose `index` of this agent, r x (d+1)
   bool getSharedPose(unsigned index, Matrix *Mout) {
     Matrix X;
@@ -425,6 +468,46 @@ class Agent {
     return t;
   }
   dcora_rbcd_t session() const { return team()->session(); }
+  bool decide(bool terminate) {
+    unsigned R = 0;
+    for (unsigned id : params_.robotIDs) R = std::max(R, id + 1);
+    if (R == 0) R = params_.numRobots;
+    std::vector<dcora_agent_status> statuses(R);
+    std::vector<int> have(R, 0), active(R, 0);
+    auto put = [&](const AgentStatus &st) {
+      if (st.agentID >= R) return;
+      dcora_agent_status &c = statuses[st.agentID];
+      c.agent_id = (int)st.agentID;
+      c.state = (int)st.state;
+      c.instance_number = (int)st.instanceNumber;
+      c.iteration_number = (int)st.iterationNumber;
+      c.ready_to_terminate = st.readyToTerminate ? 1 : 0;
+      c.relative_change = st.relativeChange;
+      have[st.agentID] = 1;
+    };
+    if (params_.robotIDs.empty())
+      active.assign(R, 1);
+    else
+      for (unsigned id : params_.robotIDs) active[id] = 1;
+    for (const auto &kv : neighbor_status_)
+      if (kv.first != mID) put(kv.second);
+    int info[4] = {0, 0, 0, 0};
+    bool own_known = true;
+    if (!map_agent_ && !ra_) {
+      dcora_agent_status cs;
+      int known = 0;
+      check_status(dcora_rbcd_agent_status(session(), (int)mID, &cs, &known), "team rules");
+      check_status(dcora_rbcd_team_info(session(), info), "team rules");
+      own_known = known != 0;
+    }
+    if (own_known) put(getStatus());
+    const dcora_team_params tp = params_.teamParams();
+    int term = 0, upd = 0;
+    check_status(dcora_team_decide(&tp, 0, (int)iteration_number(), info[2], info[0], info[1], statuses.data(),
+                                   have.data(), active.data(), (int)R, &term, &upd),
+                 "team rules");
+    return terminate ? term != 0 : upd != 0;
+  }
   // (number of poses, first global pose)
   std::pair<unsigned, unsigned> info() const {
     if (!have_info_) {

@@ -575,6 +575,74 @@ int dcora_exchange_update_weights(dcora_exchange_t ex, int reset_to_initial, int
 int dcora_exchange_set_weights(dcora_exchange_t ex, const double *w);
 /* all m current weights of the job, the same on every rank */
 int dcora_exchange_get_weights(dcora_exchange_t ex, double *w);
+
+/* --- agent status, team termination and weight-update decisions (ref src/Agent.cpp:558-586, 1123-1156, 1280-1330) --- */
+/* the fields of AgentParameters the three rules read (ref include/DCORA/Agent.h:113-125); defaults: 500 iterations,
+ * relative change 5e-3, 10 weight updates, 0 resets, 30 inner iterations, convergence ratio 0.8 */
+typedef struct {
+  int max_num_iters;
+  double rel_change_tol;
+  int robust_opt_num_weight_updates, robust_opt_num_resets, robust_opt_inner_iters;
+  double robust_opt_min_convergence_ratio;
+} dcora_team_params;
+void dcora_team_params_default(dcora_team_params *p);
+/* AgentState (ref include/DCORA/Agent.h:149-155) */
+typedef enum {
+  DCORA_AGENT_WAIT_FOR_DATA = 0,
+  DCORA_AGENT_WAIT_FOR_INITIALIZATION = 1,
+  DCORA_AGENT_INITIALIZED = 2
+} dcora_agent_state;
+/* AgentStatus (ref include/DCORA/Agent.h:157-200) */
+typedef struct {
+  int agent_id, state, instance_number, iteration_number, ready_to_terminate;
+  double relative_change;
+} dcora_agent_status;
+/* The local rule of Agent::iterate (ref src/Agent.cpp:567-585), host only.  robust: cost type != L2.  *ready = 0 when
+ * success == 0, when relative_change > tolerance (rel_change_tol; 5 while robust and weight_update_count == 0), or when
+ * (accepted + rejected) / total < robust_opt_min_convergence_ratio in doubles, as written there: an agent without loop
+ * closures (0 / 0) passes. */
+int dcora_team_ready_to_terminate(const dcora_team_params *params, int robust, int weight_update_count, int success,
+                                  double relative_change, int accepted, int rejected, int total, int *ready);
+/* Agent::shouldTerminate and Agent::shouldUpdateMeasurementWeights (ref src/Agent.cpp:1123-1156, 1280-1330) in the
+ * reference's order of tests, host only.  statuses / have: num_robots entries, have[q] == 0: the status of robot q is
+ * absent; active (may be NULL: all active): robots with active[q] == 0 are skipped.  Either output may be NULL. */
+int dcora_team_decide(const dcora_team_params *params, int robust, int iteration_number, int weight_update_count,
+                      int inner_iter, int latest_weight_update_iteration, const dcora_agent_status *statuses,
+                      const int *have, const int *active, int num_robots, int *should_terminate,
+                      int *should_update_weights);
+/* LiftedArray::maxTranslationDistance (ref src/manifold/Elements.cpp:59-69) of two lifted pose arrays r x (d+1) n
+ * (column-major, host) on the device, by the kernel that computes the agents' relative change: max over the poses of
+ * the 2-norm of the translations' difference.  2 <= r <= 16, d in {2, 3}, d <= r, n >= 1. */
+int dcora_max_translation_distance(int r, int d, int n, const double *X, const double *Y, double *out);
+/* Opt-in to the team protocol on a pose-graph session of one process (world_size > 1: DCORA_ERR_UNSUPPORTED).  From
+ * here on every Agent::iterate(true) of an agent -- dcora_rbcd_iterate, dcora_rbcd_phase_selected,
+ * dcora_rbcd_agent_iterate(.., 1), dcora_rbcd_iterate_set and the run loops over them -- stores that agent's status
+ * (ref src/Agent.cpp:558-586): one more launch per round, no synchronisation.  The round counter of the robust inner
+ * iterations advances with every round (:537-538).  dcora_rbcd_update_weights clears the statuses, records the round as
+ * the latest weight update and zeroes that counter (:1417-1424); dcora_rbcd_set_weights only refreshes the loop-closure
+ * counts; dcora_rbcd_set_X, which restarts the rounds, restarts this bookkeeping with them.  A session that never
+ * calls this launches nothing new.  The entries below return DCORA_ERR_BAD_ARG before it. */
+int dcora_rbcd_team_enable(dcora_rbcd_t s, const dcora_team_params *params);
+/* the status `agent` stored at its last optimisation since the statuses were cleared (*known = 0: none, *status then
+ * holds the agent's id, state and iteration number only) */
+int dcora_rbcd_agent_status(dcora_rbcd_t s, int agent, dcora_agent_status *status, int *known);
+/* Graph::statistics (ref src/Graph.cpp:475-521) of `agent`: accepted (weight == 1), rejected (weight == 0) and all
+ * loop closures -- every measurement but odometry -- with an end at the agent */
+int dcora_rbcd_loop_closure_stats(dcora_rbcd_t s, int agent, int counts[3]);
+/* dcora_team_decide over the statuses the session holds (an agent that has not optimised since the last clear is
+ * absent), the session's round counter as the iteration number */
+int dcora_rbcd_should_terminate(dcora_rbcd_t s, int *yes);
+int dcora_rbcd_should_update_weights(dcora_rbcd_t s, int *yes);
+/* info[4]: robust inner iterations since the latest weight update (0 with the L2 cost), the round of the latest weight
+ * update, weight updates so far, trajectory resets dcora_rbcd_run_team has made */
+int dcora_rbcd_team_info(dcora_rbcd_t s, int info[4]);
+typedef enum { DCORA_TEAM_STOP_ALL_READY = 1, DCORA_TEAM_STOP_MAX_ITERS = 2 } dcora_team_stop_reason;
+/* The loop a team without a central evaluator runs, made of exactly these calls: until dcora_rbcd_should_terminate,
+ * each pass { if dcora_rbcd_should_update_weights: dcora_rbcd_update_weights(reset = resets made so far <
+ * robust_opt_num_resets), updated_trace[it] = 1; dcora_rbcd_iterate(selected) with the greedy next selection, first
+ * agent 0 }.  The traces (any may be NULL) hold max_num_iters entries, entry it belonging to pass it. */
+int dcora_rbcd_run_team(dcora_rbcd_t s, int *iters_done, double *cost2_trace, double *gradnorm_trace,
+                        int *selected_trace, int *updated_trace, int *weight_updates, int *stop_reason);
 /* RobustCost::weight(r) for n residuals after num_updates calls of RobustCost::update() (ref src/DCORA_robust.cpp:56-136) */
 int dcora_robust_weights(const dcora_robust_params *p, int num_updates, int n, const double *r, double *w);
 /* chi2inv (ref src/DCORA_utils.cpp:2103-2106), RobustCost::computeErrorThresholdAtQuantile (ref src/DCORA_robust.cpp:138-148) */
