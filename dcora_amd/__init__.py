@@ -685,6 +685,12 @@ class RbcdSession:
     def phase_selected(self, selected):
         check(capi.lib().dcora_rbcd_phase_selected(self.h, selected))
 
+    def debug_launches(self):
+        """kernel launches of the RBCD chain this session's iterate() calls have enqueued (debug counter)"""
+        out = C.c_longlong(0)
+        check(capi.lib().dcora_debug_rbcd_launches(self.h, C.byref(out)))
+        return int(out.value)
+
     def phase_evaluate_dev(self, ptr):
         check(capi.lib().dcora_rbcd_phase_evaluate_dev(self.h, C.c_void_p(ptr)))
 

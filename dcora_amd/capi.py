@@ -192,6 +192,7 @@ SIGNATURES = {
     "dcora_rbcd_unpack_public_dev": (C.c_int, [_vp, C.c_int, _vp]),
     "dcora_rbcd_phase_nonselected": (C.c_int, [_vp, C.c_int]),
     "dcora_rbcd_phase_selected": (C.c_int, [_vp, C.c_int]),
+    "dcora_debug_rbcd_launches": (C.c_int, [_vp, C.POINTER(C.c_longlong)]),
     "dcora_rbcd_phase_evaluate_dev": (C.c_int, [_vp, _vp]),
     "dcora_rbcd_synchronize": (C.c_int, [_vp]),
     "dcora_exchange_create": (C.c_int, [_vp, C.c_char_p, C.POINTER(_vp)]),

@@ -1302,6 +1302,12 @@ int dcora_rbcd_phase_nonselected(dcora_rbcd_t s, int selected) {
 int dcora_rbcd_phase_selected(dcora_rbcd_t s, int selected) {
   return abi_call({s}, [&] { return s->s.phase_selected(selected); });
 }
+int dcora_debug_rbcd_launches(dcora_rbcd_t s, long long *launches) {
+  return abi_call({s, launches}, [&] {
+    *launches = s->s.chain_launches;
+    return (int)DCORA_OK;
+  });
+}
 int dcora_rbcd_phase_evaluate_dev(dcora_rbcd_t s, double *out_dev) {
   return abi_call({s, out_dev}, [&] { return s->s.phase_evaluate_dev(out_dev); });
 }

@@ -216,6 +216,12 @@ class DeviceProblem {
   int enq_qapply(Buf2 X, int selX, const double *Gp, Buf2 Y, int selY, double *partials, Gate g);
   DevBuf<double> G;     // r x k (always allocated; zero when the problem has no linear term)
   bool has_G = false;
+  // G = Xsrc C of the next optimize_dev, to be formed by its start-point evaluation (C without long rows: the caller
+  // checks) -- or, where that evaluation is not k_fused_grad, by the k_spmm launch it replaces, ahead of the solve
+  void ride_G(const CsrDev &C, const double *Xsrc) {
+    ride_C_ = C;
+    ride_X_ = Xsrc;
+  }
   DevBuf<double> Minv;  // k x ldm dense inverse of Q + reg I (small blocks)
   int ldm = 0;
   SparsePrecond sp;     // partitioned sparse inverse (large blocks)
@@ -319,6 +325,8 @@ class DeviceProblem {
   struct RtrForm;
   int rtr_dev(const dcora_ropt_params &prm, TcgForm form);
   int rgd_dev(const dcora_ropt_params &prm);
+  CsrDev ride_C_{};        // ride_G: pending when ride_X_ is set
+  const double *ride_X_ = nullptr;
   int seq_ = 0;            // launch sequence number, monotonic across solves (HostFlags words are never reset)
   bool pending_ = false;   // an RTR solve has been enqueued and its statistics not yet fetched
   bool rgd_ = false;       // the last solve was RGD: its result is X1

@@ -687,13 +687,18 @@ int DeviceProblem::optimize(const dcora_ropt_params &prm, const double *X0h, dou
 int DeviceProblem::optimize_dev(const dcora_ropt_params &prm) {
   pending_ = false;
   rgd_ = prm.method != 0;
+  TcgForm form = TcgForm::generic;
+  if (fused) form = !use_pc() ? TcgForm::split : (tcg_run_ok && !concurrent_solves) ? TcgForm::run : TcgForm::pc;
+  // a G that was to ride in the start-point evaluation where that is not k_fused_grad (RtrForm::gf): its own launch
+  if (ride_X_ && (rgd_ || !has_precond || form == TcgForm::generic || has_bsr || Q.n_long != 0)) {
+    launch_spmm(st, m.r, ride_C_, buf1(ride_X_), 0, nullptr, buf1(G.p), 0, nullptr, Gate{});
+    ride_X_ = nullptr;
+  }
   if (rgd_) return rgd_dev(prm);
   if (!has_precond) {
     set_last_error("RTR requires the preconditioner (ref src/QuadraticProblem.cpp:78-82)");
     return DCORA_ERR_NO_PRECONDITIONER;
   }
-  TcgForm form = TcgForm::generic;
-  if (fused) form = !use_pc() ? TcgForm::split : (tcg_run_ok && !concurrent_solves) ? TcgForm::run : TcgForm::pc;
   return rtr_dev(prm, form);
 }
 
@@ -888,7 +893,19 @@ struct DeviceProblem::RtrForm {
       launch_rgrad(p.st, p.m, p.Xb(), p.EGb(), p.RGb(), p.Sb(), sel, p.pB.p, g());
       return nP;
     }
-    if (gf) return launch_fused_grad(p.st, p.m, Qv, p.Xb(), Gp, p.EGb(), p.RGb(), p.Sb(), sel, p.pA.p, p.pB.p, nullptr, g());
+    if (gf) {
+      GradRide ride;
+      if (sel == 0 && p.ride_X_) {  // (optimize_dev leaves it only where gf holds)
+        ride.c_rp = p.ride_C_.rp;
+        ride.c_ci = p.ride_C_.ci;
+        ride.c_v = p.ride_C_.v;
+        ride.c_X = p.ride_X_;
+        ride.G_out = p.G.p;
+        p.ride_X_ = nullptr;
+      }
+      return launch_fused_grad(p.st, p.m, Qv, p.Xb(), Gp, p.EGb(), p.RGb(), p.Sb(), sel, p.pA.p, p.pB.p, nullptr, g(),
+                               ride.c_rp ? &ride : nullptr);
+    }
     if (gfb)
       return launch_fused_grad_bsr(p.st, p.m.r, p.m.d, Qbv, p.Xb(), Gp, kNoBuf, p.RGb(), p.Sb(), sel, p.pA.p, p.pB.p,
                                    nullptr, g());

@@ -29,6 +29,9 @@ int solver_bc() {
   static const int v = is("DCORA_SOLVER_BC", "pc") ? 1 : is("DCORA_SOLVER_BC", "split") ? -1 : 0;
   return v;
 }
+bool chain_rides() {
+  return !is("DCORA_CHAIN", "launches");
+}
 bool factor_on_host() {
   static const bool v = is("DCORA_FACTOR", "host");
   return v;

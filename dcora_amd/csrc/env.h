@@ -1,5 +1,5 @@
 // The environment switches of the library -- ALL of them: nothing else in dcora_amd/csrc reads the environment.  Each is
-// read once per process, except DCORA_PRECOND and DCORA_SOLVER, which are read whenever a problem is created (the
+// read once per process, except DCORA_PRECOND, DCORA_SOLVER and DCORA_CHAIN, which are read whenever a problem is created (the
 // differential tests build the same problem on both paths in one process).  They force one of two LIVE paths (for differential tests and A/B measurements) or set an
 // operational limit; superseded kernel forms are not kept behind switches (DESIGN.md lists what was measured and
 // dropped).  INTEGRATION.md section 5 documents them for users.
@@ -13,6 +13,9 @@ int precond_mode();          // DCORA_PRECOND=dense|sparse -> 1 | 2 (0: chosen b
 bool generic_solver();       // DCORA_SOLVER=generic: the thread-per-variable path also where the fused kernels apply
 int solver_tcg();            // DCORA_SOLVER_TCG=launch|run -> -1 | +1: the dense tCG run as launches per iteration / as ONE launch (0: by size)
 int solver_bc();             // DCORA_SOLVER_BC=pc|split -> +1 | -1: one-launch / three-launch form of the dense tCG step
+// DCORA_CHAIN=launches: every step of an RBCD iteration as a launch of its own (false); default: G = X C of the
+// selected agent is formed by the start-point evaluation of its local solve.  Read whenever a session is created.
+bool chain_rides();
 bool factor_on_host();       // DCORA_FACTOR=host: sparse Cholesky of the preconditioner on host threads
 bool fill_on_host();         // DCORA_SP_FILL=host: stored weights formed by host threads and streamed in chunks
 bool lanczos_sync();         // DCORA_LANCZOS=sync: one host round trip per Lanczos step (the form used across ranks)

@@ -20,6 +20,7 @@ namespace dcora {
 constexpr int kMaxPartials = 1024;  // upper bound on per-kernel partial-sum slots
 constexpr int kBsrMaxGrid = 4096;   // workgroups (= partial slots) of the block-CSR Q-apply
 constexpr int kBlock = 256;
+constexpr int kSpmmTile = 1536;  // nnz k_spmm stages per pass: 18 KiB of LDS
 
 struct ManiDesc {
   int r, d, n, l, b, k, se;
@@ -111,6 +112,20 @@ struct Gate {
   const SolverCtl *ctl = nullptr;
   int seq = 0;
   int gate = 0;
+};
+
+// Kernel launches enqueued by the wrappers of the RBCD chain (debug counter: dcora_debug_rbcd_launches reads what a
+// session's calls added to it)
+extern std::atomic<long> g_chain_launches;
+inline void count_launch() { g_chain_launches.fetch_add(1, std::memory_order_relaxed); }
+
+// What may ride in a k_fused_grad launch instead of a launch of its own (DCORA_CHAIN): with c_rp
+// set, the start-point evaluation of a local solve forms G = Xsrc C itself (C: the agent's coupling block, no long
+// rows) -- k_spmm<false>'s sums in k_spmm's order -- and stores it to G_out.
+struct GradRide {
+  const int *c_rp = nullptr, *c_ci = nullptr;
+  const double *c_v = nullptr, *c_X = nullptr;
+  double *G_out = nullptr;
 };
 
 // ---- SpMM: Y = X * A (+ G); optional partial dots {sum (X*A) o X, sum X o G}, 2 per block ---------------
@@ -277,7 +292,8 @@ int launch_fused_grad_bsr(hipStream_t st, int r, int d, const BsrDev &A, Buf2 X,
                           int sel, double *pA, double *pB, double *posenorm, Gate g,
                           const int *agent_start = nullptr, int agents = 0, int *wg_per_agent = nullptr);
 int launch_fused_grad(hipStream_t st, const ManiDesc &m, const CsrDev &Q, Buf2 X, const double *G, Buf2 EG, Buf2 RG,
-                      Buf2 Sblk, int sel, double *pA, double *pB, double *posenorm, Gate g);
+                      Buf2 Sblk, int sel, double *pA, double *pB, double *posenorm, Gate g,
+                      const GradRide *ride = nullptr);
 int launch_g_rgrad(hipStream_t st, const ManiDesc &m, Buf2 X, Buf2 EG, Buf2 RG, Buf2 Sblk, int sel, double *partials,
                    double *posenorm, Gate g);
 void launch_ctl_init(hipStream_t st, SolverCtl *c, double tol, double Delta, double maxDelta, int max_outer,

@@ -44,6 +44,8 @@ __device__ __forceinline__ void sum_partials_n(const double *const (&p)[N], cons
   }
 }
 
+std::atomic<long> g_chain_launches{0};
+
 int vec_grid(long nelem) {
   long g = (nelem + kBlock - 1) / kBlock;
   if (g < 1) g = 1;
@@ -56,8 +58,6 @@ int vec_grid(long nelem) {
 // contiguous doubles of X(:, c) and share one (value, column) pair.  The CSR segment of the block's rows is
 // staged in LDS with fully coalesced loads (row blocks of a connection Laplacian are contiguous in CSR).
 // ------------------------------------------------------------------------------------------------------
-constexpr int kSpmmTile = 1536;  // nnz staged per pass: 18 KiB of LDS
-
 int spmm_grid(int nrows, int r) {
   const int RB = kBlock / r;
   long nrb = (nrows + RB - 1) / RB;
@@ -651,6 +651,7 @@ void launch_spmm_dir(hipStream_t st, int r, const CsrDev &A, const double *z, co
 
 void launch_spmm(hipStream_t st, int r, const CsrDev &A, Buf2 X, int selX, const double *G, Buf2 Y, int selY,
                  double *partials, Gate g) {
+  count_launch();
   const int main_grid = spmm_grid(A.nrows, r);
   const int grid = main_grid + A.n_long * kLongSplit;
   if (partials)
@@ -1661,6 +1662,7 @@ __global__ __launch_bounds__(kBlock) void k_rtr_decide(const double *pA, int npA
 
 void launch_rtr_init(hipStream_t st, const double *pA, int npA, const double *pB, int npB, SolverCtl *ctl,
                      HostFlags *hf, int seq, CtlInit ci, unsigned *tcg_sync, int nsync) {
+  count_launch();
   hipLaunchKernelGGL(k_rtr_init, dim3(1), dim3(kBlock), 0, st, pA, npA, pB, npB, ctl, hf, seq, ci, tcg_sync, nsync);
 }
 void launch_tcg_begin(hipStream_t st, long nelem, Buf2 grad, double *eta, double *Heta, double *res,
@@ -1681,6 +1683,7 @@ void launch_tcg_update2(hipStream_t st, long nelem, const double *z, double *del
 }
 void launch_rtr_decide(hipStream_t st, const double *pA, int npA, const double *pB, int npB, const double *pC,
                        int npC, SolverCtl *ctl, HostFlags *hf, int seq, unsigned *tcg_sync, int nsync) {
+  count_launch();
   hipLaunchKernelGGL(k_rtr_decide, dim3(1), dim3(kBlock), 0, st, pA, npA, pB, npB, pC, npC, ctl, hf, seq, tcg_sync,
                      nsync);
 }

@@ -142,6 +142,7 @@ class RbcdSession : public SessionCore {
   int team_inner_iter() const { return team_robust() ? inner_rounds : 0; }
   int run_team(int *iters_done, double *cost2_trace, double *gradnorm_trace, int *selected_trace, int *updated_trace,
                int *weight_updates, int *stop_reason);
+  long chain_launches = 0;  // kernel launches of the chain's wrappers enqueued by iterate() (debug counter)
   int pack_public(int agent, double *packed_dev);
   int unpack_public(int agent, const double *packed_dev);
 
@@ -150,6 +151,7 @@ class RbcdSession : public SessionCore {
   int x_stage_hosted(double *host_area) override;
 
  private:
+  bool chain_rides_ = false;  // env::chain_rides() when the session was created
   bool seq_advanced_ = false;  // phase_nonselected has advanced the sequences of the round phase_selected finishes
   int staged_selected_ = -1;  // agent whose Nesterov step rode in the non-selected agents' launch of this round
   int staged_iteration_ = -1; // the round it was staged in: honoured by update_selected_agent in that round only

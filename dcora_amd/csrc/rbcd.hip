@@ -88,6 +88,7 @@ RbcdSession::~RbcdSession() {
 int RbcdSession::init(const HostDataset &ds, const dcora_rbcd_options &o) {
   t0_ = std::chrono::steady_clock::now();
   opt = o;
+  chain_rides_ = env::chain_rides();
   d = ds.d;
   n = ds.n;
   r = o.r;
@@ -715,7 +716,12 @@ int RbcdSession::update_selected_agent(AgentDev &a, bool restart) {
       return DCORA_OK;
     }
     const double *nsrc = a.detached ? a.nbr[opt.acceleration ? 1 : 0].p : Xg.p;
-    launch_spmm(st, r, a.coupling.view(), buf1(nsrc), 0, nullptr, buf1(pb.G.p), 0, nullptr, Gate{});
+    // (chain: G is formed by the solve's start-point evaluation where that is k_fused_grad)
+    const CsrDev Cv = a.coupling.view();
+    if (chain_rides_ && !a.detached && Cv.n_long == 0)
+      pb.ride_G(Cv, nsrc);
+    else
+      launch_spmm(st, r, Cv, buf1(nsrc), 0, nullptr, buf1(pb.G.p), 0, nullptr, Gate{});
     pb.has_G = true;
     last_solver = &pb;
     if (opt.acceleration) {
@@ -988,6 +994,7 @@ int RbcdSession::phase_evaluate_dev(double *out_dev) {
 int RbcdSession::iterate(int selected, double *cost2, double *gradnorm, double *block_norms, int *next_selected) {
   int rc = check_selected(selected);
   if (rc) return rc;
+  const long launches0 = g_chain_launches.load(std::memory_order_relaxed);
   rc = phase_nonselected(selected);
   if (rc) return rc;
   // world_size == 1: the "pull" of public poses (ref examples/MultiRobotExample.cpp:236-258) is the identity,
@@ -996,6 +1003,7 @@ int RbcdSession::iterate(int selected, double *cost2, double *gradnorm, double *
   if (rc) return rc;
   int nxt = selected;
   rc = evaluate_central(cost2, gradnorm, block_norms, &nxt);
+  chain_launches += g_chain_launches.load(std::memory_order_relaxed) - launches0;
   if (rc) return rc;
   // greedy selection only when the selected agent has neighbours (:290-292)
   if (next_selected) *next_selected = (agents[selected].coupling.nnz > 0) ? nxt : selected;

@@ -437,11 +437,40 @@ __global__ __launch_bounds__(kBlock) void k_fused_hess(ManiDesc m, CsrDev Q, con
 // eight lanes per pose, operands handed over through LDS, exactly as k_fused_hess.  Saves one dependent launch per
 // evaluation (4 per local solve, 1 per central evaluation).
 // ------------------------------------------------------------------------------------------------------
-template <int D>
+// RIDE (GradRide, kernels.h): the start-point evaluation forms G from the agent's coupling block first -- every thread
+// for its own element, nothing another workgroup of the launch writes is read.
+// G of one output element as k_spmm<false> forms it: the row's entries in batches of 8 that restart at the tile
+// borders of k_spmm's row block (rows j0 .. j0 + kBlock / r - 1, kSpmmTile entries from rp[j0]), a batch's padding as
+// a zero weight on the segment's first entry, acc = fma(w, x, acc) in index order.
+__device__ __forceinline__ double coupling_row(const GradRide &c, int r, int j, int t) {
+  const int RB = kBlock / r;
+  const int pb0 = c.c_rp[(j / RB) * RB];
+  const int myb = c.c_rp[j], mye = c.c_rp[j + 1];
+  double acc = 0;
+  int lo = myb;
+  while (lo < mye) {
+    const int hi = min(mye, pb0 + ((lo - pb0) / kSpmmTile + 1) * kSpmmTile);
+    for (int p = lo; p < hi; p += 8) {
+      double x8[8], w8[8];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        const bool ok = p + q < hi;
+        const int pp = ok ? p + q : lo;
+        w8[q] = ok ? c.c_v[pp] : 0.0;
+        x8[q] = c.c_X[(size_t)c.c_ci[pp] * r + t];
+      }
+#pragma unroll
+      for (int q = 0; q < 8; ++q) acc = fma(w8[q], x8[q], acc);
+    }
+    lo = hi;
+  }
+  return acc;
+}
+template <int D, bool RIDE>
 __global__ __launch_bounds__(kBlock) void k_fused_grad(ManiDesc m, CsrDev Q, Buf2 Xb, const double *__restrict__ G,
                                                        Buf2 EGb, Buf2 RGb, Buf2 Sb, int sel,
                                                        double *__restrict__ pA, double *__restrict__ pB,
-                                                       double *__restrict__ posenorm, Gate g) {
+                                                       double *__restrict__ posenorm, Gate g, GradRide ride) {
   if (gated(g.ctl, g.seq, g.gate)) return;
   __shared__ int s_ci[kHessTile];
   __shared__ double s_v[kHessTile];
@@ -466,7 +495,15 @@ __global__ __launch_bounds__(kBlock) void k_fused_grad(ManiDesc m, CsrDev Q, Buf
   const int myb = act ? Q.rp[j] : 0, mye = act ? Q.rp[j + 1] : 0;
   const size_t oown = (size_t)j * r + t;
   const double x_own = act ? X[oown] : 0.0;
-  const double g_own = (act && G) ? G[oown] : 0.0;
+  double g_own = 0.0;
+  if (RIDE) {
+    if (act) {
+      g_own = coupling_row(ride, r, j, t);
+      ride.G_out[oown] = g_own;
+    }
+  } else {
+    g_own = (act && G) ? G[oown] : 0.0;
+  }
   // ---- phase 1: EG = X Q + G ----
   double acc = 0;
   for (int base = pbeg; base < pend; base += kHessTile) {
@@ -2399,6 +2436,7 @@ __global__ __launch_bounds__(kBlock) void k_eval_finish(int R, const int *__rest
 void launch_eval_finish(hipStream_t st, int R, const int *pose_start, const double *posenorm, const double *pA,
                         int npA, EvalOut *out_dev, int seq, double *split_scratch, int nposes,
                         const double *agent_partials, int wg_per_agent) {
+  count_launch();
   const bool split = !agent_partials && split_scratch && nposes >= 16384;
   if (split)
     hipLaunchKernelGGL(k_eval_partial, dim3(R * kEvalSplit), dim3(kBlock), 0, st, pose_start, posenorm, split_scratch);
@@ -2492,6 +2530,7 @@ int fused_update_grid(const ManiDesc &m) {
 int launch_fused_hess(hipStream_t st, const ManiDesc &m, const CsrDev &Q, const double *z, const double *d_old,
                       double *d_new, Buf2 X, Buf2 S, double *Hd, const double *p3, int np3, double *p1,
                       SolverCtl *ctl, int seq, int iter, const BsrDev *Ab) {
+  count_launch();
   if (Ab) {  // block structure available: 32 poses per workgroup
     const int gridb = (m.n + kPosesPerBlock - 1) / kPosesPerBlock;
     if (m.d == 3)
@@ -2664,6 +2703,7 @@ static int tcg_run_launch(hipStream_t st, const TcgRunArgs &a) {
 int launch_tcg_run(hipStream_t st, const ManiDesc &m, int ldm, const double *Minv, const CsrDev &Q, Buf2 grad, Buf2 X,
                    Buf2 S, double *d0, double *d1, double *Hd, double *eta, double *Heta, double *z, double *p1r,
                    double *p3, double *pC, unsigned *sync, SolverCtl *ctl, HostFlags *hf, int seq) {
+  count_launch();
   int fault = 0;
   bool skipped = false;
   for (int sk = g_tcg_run_fault_skip.load(); sk > 0;)
@@ -2712,6 +2752,7 @@ int launch_fused_pc(hipStream_t st, const ManiDesc &m, int ldm, const double *Mi
                     const double *delta, const double *Hd, double *eta, double *Heta, const double *res_old,
                     double *res_new, double *z, const double *p1, int np1, double *p3, SolverCtl *ctl, HostFlags *hf,
                     int seq, int iter, int first, double *pC) {
+  count_launch();
   return fused_pc_dispatch(st, m, ldm, Minv, grad, X, delta, Hd, eta, Heta, res_old, res_new, z, p1, np1, p3, ctl, hf,
                            seq, iter, first, pC, false);
 }
@@ -2745,14 +2786,21 @@ int launch_g_rgrad(hipStream_t st, const ManiDesc &m, Buf2 X, Buf2 EG, Buf2 RG, 
 // EG = X Q + G, RG = Proj_X(EG), S blocks, partials {<XQ,X>, <X,G>} in pA (2 per block) and |RG|^2 in pB (1 per
 // block); returns the number of blocks.  Small SE blocks without long rows only (the caller checks).
 int launch_fused_grad(hipStream_t st, const ManiDesc &m, const CsrDev &Q, Buf2 X, const double *G, Buf2 EG, Buf2 RG,
-                      Buf2 Sblk, int sel, double *pA, double *pB, double *posenorm, Gate g) {
+                      Buf2 Sblk, int sel, double *pA, double *pB, double *posenorm, Gate g, const GradRide *ride) {
   const int grid = fused_pose_blocks(m);
-  if (m.d == 3)
-    hipLaunchKernelGGL(k_fused_grad<3>, dim3(grid), dim3(kBlock), 0, st, m, Q, X, G, EG, RG, Sblk, sel, pA, pB, posenorm,
-                       g);
-  else
-    hipLaunchKernelGGL(k_fused_grad<2>, dim3(grid), dim3(kBlock), 0, st, m, Q, X, G, EG, RG, Sblk, sel, pA, pB, posenorm,
-                       g);
+  const GradRide rd = ride ? *ride : GradRide();
+  count_launch();
+#define DCORA_FUSED_GRAD(D_, RIDE_)                                                                                  \
+  hipLaunchKernelGGL((k_fused_grad<D_, RIDE_>), dim3(grid), dim3(kBlock), 0, st, m, Q, X, G, EG, RG, Sblk, sel, pA, pB, \
+                     posenorm, g, rd)
+  if (m.d == 3) {
+    if (rd.c_rp) DCORA_FUSED_GRAD(3, true);
+    else DCORA_FUSED_GRAD(3, false);
+  } else {
+    if (rd.c_rp) DCORA_FUSED_GRAD(2, true);
+    else DCORA_FUSED_GRAD(2, false);
+  }
+#undef DCORA_FUSED_GRAD
   return grid;
 }
 int launch_g_retract(hipStream_t st, const ManiDesc &m, Buf2 X, const double *V, double alpha, Buf2 out, int selOut,
@@ -2769,6 +2817,7 @@ int launch_g_retract(hipStream_t st, const ManiDesc &m, Buf2 X, const double *V,
 void launch_g_nesterov(hipStream_t st, const ManiDesc &m, int mode, int restart, int skip_lo, int skip_hi,
                        double alpha, double gamma, double *X, double *V, double *Y, double *XPrev, double *Yloc,
                        Buf2 Xloc, const SolverCtl *ctl, double *inner_Yloc) {
+  count_launch();
   GNesterovArgs a{mode, restart, skip_lo, skip_hi, alpha, gamma, X, V, Y, XPrev, Yloc, inner_Yloc, Xloc, ctl};
   const int grid = group_grid(m.n);
   if (m.d == 3)

@@ -48,6 +48,7 @@ __global__ __launch_bounds__(kBlock) void k_rel_change(int r, int dh, const doub
 
 void launch_rel_change(hipStream_t st, int r, int d, const double *X, const double *XPrev, const int *pose_start,
                        const RelChangeSet &set, double *out) {
+  count_launch();
   if (set.count < 1) return;
   hipLaunchKernelGGL(k_rel_change, dim3(set.count), dim3(kBlock), 0, st, r, d + 1, X, XPrev, pose_start, set, out);
 }

@@ -367,6 +367,10 @@ int dcora_rbcd_unpack_public_dev(dcora_rbcd_t s, int agent, const double *packed
 /* the three phases of dcora_rbcd_iterate for callers that exchange between them */
 int dcora_rbcd_phase_nonselected(dcora_rbcd_t s, int selected);
 int dcora_rbcd_phase_selected(dcora_rbcd_t s, int selected);
+/* debug counter (read-only): the kernel launches of the RBCD chain -- evaluations, Nesterov steps, G, the RTR
+ * bookkeeping and tCG kernels, the evaluation epilogue -- that this session's dcora_rbcd_iterate calls have enqueued
+ * since creation.  Meaningful while one session iterates at a time. */
+int dcora_debug_rbcd_launches(dcora_rbcd_t s, long long *launches);
 /* local part of the evaluation: for every hosted agent b, |Proj(X_b Q_bb + G_b)|^2 and <X_b, X_b Q_bb + G_b>
  * written to out_dev[2*b], out_dev[2*b+1] (device, 2*num_robots doubles, entries of non-hosted agents zero) */
 int dcora_rbcd_phase_evaluate_dev(dcora_rbcd_t s, double *out_dev);
