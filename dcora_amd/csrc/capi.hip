@@ -305,6 +305,22 @@ int dcora_debug_tcg_run_fault_at(int skip, int runs) {
   g_tcg_run_fault.store(runs < 0 ? 0 : runs);
   return DCORA_OK;
 }
+int dcora_debug_wg_sums(int nv, const double *in, double *out) {
+  return abi_call({in, out}, [&]() -> int {
+    if (no_device()) return DCORA_ERR_NO_DEVICE;
+    if (nv != 33 && nv != 41 && nv != 49) return bad("dcora_debug_wg_sums: nv is 33, 41 or 49 (8 r + 1 at r = 4, 5, 6)");
+    const size_t nin = (size_t)nv * 256, nout = (size_t)2 * nv * 17;
+    DevBuf<double> I, O;
+    DCORA_HIP(I.alloc(nin));
+    DCORA_HIP(O.alloc(nout));
+    DCORA_HIP(hipMemcpy(I.p, in, nin * sizeof(double), hipMemcpyHostToDevice));
+    DCORA_HIP(hipMemset(O.p, 0, nout * sizeof(double)));
+    if (launch_debug_wg_sums(nullptr, nv, I.p, O.p) < 0) return bad("dcora_debug_wg_sums: the launch failed");
+    DCORA_HIP(hipDeviceSynchronize());
+    DCORA_HIP(hipMemcpy(out, O.p, nout * sizeof(double), hipMemcpyDeviceToHost));
+    return DCORA_OK;
+  });
+}
 int dcora_problem_time_precond(dcora_problem_t p, int reps, double *avg_ms, double *bytes) {
   return abi_call({p, avg_ms, bytes}, [&] { return p->p.time_precond(reps, avg_ms, bytes); });
 }

@@ -277,6 +277,9 @@ int tcg_run_max_rows_nnz(const ManiDesc &m, const int *rowptr);  // host CSR row
 int launch_tcg_run(hipStream_t st, const ManiDesc &m, int ldm, const double *Minv, const CsrDev &Q, Buf2 grad, Buf2 X,
                    Buf2 S, double *d0, double *d1, double *Hd, double *eta, double *Heta, double *z, double *p1r,
                    double *p3, double *pC, unsigned *sync, SolverCtl *ctl, HostFlags *hf, int seq);
+// test entry: one workgroup of 256 threads sums nv = 8 r + 1 (r = 4, 5, 6) values per lane with k_tcg_run's reduce-scatter
+// row sums and with the DPP butterfly; in: nv x 256 (device), out: 2 x (nv x 16 row sums + nv totals); < 0: refused
+int launch_debug_wg_sums(hipStream_t st, int nv, const double *in, double *out);
 bool fused_pc_preferred(const ManiDesc &m, int ldm);  // sizes at which it beats B + C
 bool fused_pc_ready(const ManiDesc &m, int ldm);      // the current device grants the kernel its dynamic LDS
 int launch_fused_pc(hipStream_t st, const ManiDesc &m, int ldm, const double *Minv, Buf2 grad, Buf2 X,

@@ -1075,6 +1075,54 @@ __device__ __forceinline__ double row16_sum_dpp(double v) {
 }
 constexpr int kPcBlock = 256;  // 4 waves: wave w takes the 128-column steps w, w + 4, ... of ALL the workgroup's rows
 constexpr int kPcNW = kPcBlock / 64;
+// ---- the same 16-lane row sums for NV values per lane as a reduce-scatter (k_tcg_run) ----------------------------
+// row16_sum_dpp adds over the lane bits in the order 1, 2, 4, 8 and leaves every sum in all 16 lanes of its row; only
+// one lane stores it.  The tree is a tree over LOGICAL lanes (lane L of a wave holds columns 2 L, 2 L + 1 of a
+// 128-column step), so a wave may place logical lane L = l5..l0 in physical lane P = p5..p0 as it likes.  With
+//   l0 = p5, l1 = p4, l2 = p0, l3 = p1, l4 = p2, l5 = p3
+// level 1 (L ^ 1) pairs P ^ 32 and level 2 (L ^ 2) pairs P ^ 16: v_permlane32_swap / v_permlane16_swap exchange the
+// halves of TWO registers at once, so one add reduces two values and leaves the first in one half of the lanes, the
+// second in the other: NV values become (NV + 1) / 2 registers, then half as many again (an odd count is padded with a
+// zero register whose sums nobody stores).  Levels 3 and 4 (L ^ 4, L ^ 8) are the two quad_perm butterflies on what is
+// left.  The logical row (l5 l4) is (p3 p2): the lane with p1 = p0 = 0 of every quad holds the row sums of the values
+// 4 j + 2 p4 + p5 (register j).  Same pairs, same order, IEEE addition commutes: bitwise the butterfly's row sums.
+__device__ __forceinline__ int wg_sums_logical_lane(int p) { return ((p >> 5) & 1) | ((p >> 3) & 2) | ((p & 15) << 2); }
+template <bool HALF32>
+__device__ __forceinline__ double wg_sums_swap_add(double x, double y) {
+  typedef unsigned u2 __attribute__((ext_vector_type(2)));
+  u2 lo, hi;
+  if constexpr (HALF32) {  // lanes 32-63 of x <-> lanes 0-31 of y
+    lo = __builtin_amdgcn_permlane32_swap((unsigned)__double2loint(x), (unsigned)__double2loint(y), false, false);
+    hi = __builtin_amdgcn_permlane32_swap((unsigned)__double2hiint(x), (unsigned)__double2hiint(y), false, false);
+  } else {                 // the odd 16-lane rows of x <-> the even rows of y
+    lo = __builtin_amdgcn_permlane16_swap((unsigned)__double2loint(x), (unsigned)__double2loint(y), false, false);
+    hi = __builtin_amdgcn_permlane16_swap((unsigned)__double2hiint(x), (unsigned)__double2hiint(y), false, false);
+  }
+  return __hiloint2double((int)hi[0], (int)lo[0]) + __hiloint2double((int)hi[1], (int)lo[1]);
+}
+// v[NV]: the values of this lane's LOGICAL lane wg_sums_logical_lane(lane).  Fills sP[i][wave * 4 + logical row] for
+// every i < NV, exactly what `if ((lane & 15) == 0) sP[i][wave * 4 + (lane >> 4)] = row16_sum_dpp(v[i])` leaves when
+// physical and logical lanes coincide.  Every lane of the wave must take part.
+template <int NV>
+__device__ __forceinline__ void wg_row_sums(const double (&v)[NV], double (*sP)[4 * kPcNW], int wave, int lane) {
+  constexpr int N1 = (NV + 1) / 2, N2 = (N1 + 1) / 2;
+  double a[N1], b[N2];
+#pragma unroll
+  for (int j = 0; j < N1; ++j) a[j] = wg_sums_swap_add<true>(v[2 * j], 2 * j + 1 < NV ? v[2 * j + 1] : 0.0);
+#pragma unroll
+  for (int j = 0; j < N2; ++j) {
+    double s = wg_sums_swap_add<false>(a[2 * j], 2 * j + 1 < N1 ? a[2 * j + 1] : 0.0);
+    s += dpp_move<0xB1>(s);  // quad_perm [1,0,3,2]
+    s += dpp_move<0x4E>(s);  // quad_perm [2,3,0,1]
+    b[j] = s;
+  }
+  if ((lane & 3) == 0) {
+    const int sub = ((lane >> 3) & 2) | (lane >> 5), slot = wave * 4 + ((lane >> 2) & 3);
+#pragma unroll
+    for (int j = 0; j < N2; ++j)
+      if (4 * j + sub < NV) sP[4 * j + sub][slot] = b[j];
+  }
+}
 constexpr int kPcSB = 25;      // 16-byte loads of each staged operand in flight per thread and batch
 constexpr int kPcLoads = 32;   // 16-byte loads of the inverse's rows in flight per lane and batch
 
@@ -1416,15 +1464,21 @@ struct TcgRunArgs {
 #endif
 };
 #ifdef DCORA_RUN_STAMPS
+// (nothing is scheduled across a stamp: the FMAs of a product stay in front of theirs, its sums behind it)
 #define RUN_STAMP(i)                                                            \
   do {                                                                          \
+    __builtin_amdgcn_sched_barrier(0);                                          \
     if (a.stamps && blockIdx.x == 0 && threadIdx.x == 0 && (i) < 64) a.stamps[(i)] = wall_clock64(); \
+    __builtin_amdgcn_sched_barrier(0);                                          \
   } while (0)
 #else
 #define RUN_STAMP(i) \
   do {                \
   } while (0)
 #endif
+// stamps 0 .. 3: start, image of grad, first product + projection, grid step; then kRunStampsPerIter per iteration:
+// gather returned, A, grid step, own updates, image, FMAs, row sums, sums over the workgroup, projection, grid step
+constexpr int kRunStamp0 = 4, kRunStampsPerIter = 10;
 __device__ __forceinline__ double ld_coh(const double *p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -1503,7 +1557,10 @@ __device__ __forceinline__ bool run_grid_step(unsigned *sync, unsigned step, int
 template <int D, int R, int NS>
 __global__ __launch_bounds__(kPcBlock) void k_tcg_run(TcgRunArgs a) {
   constexpr int DH = D + 1, PB = 2, NR = PB * DH, RM = R;
-  extern __shared__ double s_res[];  // the residual image, column-major as in memory: cpad * R doubles, kept for the run
+  // the residual image, column-major as in memory: cpad * R doubles, kept for the run; 16-byte aligned, so the 2 R
+  // doubles a lane takes per step (16 R bytes from a multiple of 16 R) are read 16 bytes at a time
+  extern __shared__ __align__(16) double s_img[];
+  double *const s_res = s_img;
   __shared__ double s_P[NR * RM + 1][4 * kPcNW];
   __shared__ double s_Z[NR * RM + 1], s_R[NR * RM], s_W[NR * RM], s_D[NR * RM], s_H[NR * RM];
   __shared__ double s_red[16];
@@ -1539,7 +1596,13 @@ __global__ __launch_bounds__(kPcBlock) void k_tcg_run(TcgRunArgs a) {
   const __amdgpu_buffer_rsrc_t rs_h = __builtin_amdgcn_make_buffer_rsrc(a.Hd, 0, vec_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rs_m = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<double *>(a.Minv), 0, (unsigned)((size_t)k * ldm * sizeof(double)), 0x00020000);
-  const unsigned voff_t = threadIdx.x * 16u, voff_l = (unsigned)lane * 16u;
+  // the logical lane of the product: this lane holds columns 2 llane, 2 llane + 1 of a step (wg_row_sums)
+#ifdef DCORA_RUN_BUTTERFLY_SUMS
+  const int llane = lane;
+#else
+  const int llane = wg_sums_logical_lane(lane);
+#endif
+  const unsigned voff_t = threadIdx.x * 16u, voff_l = (unsigned)llane * 16u;
   // ---- once per run: the workgroup's rows of the inverse (registers), its matrix rows of Q (LDS), its poses ----
   double2 mreg[NS][NR];
 #pragma unroll
@@ -1577,42 +1640,45 @@ __global__ __launch_bounds__(kPcBlock) void k_tcg_run(TcgRunArgs a) {
   const double n0 = c_ngf;
   int status = TR_MAXITER, iters_done = 0;
   unsigned gstep = 0;
-  double acc[NR][RM];
+  double acc[NR * RM + 1];  // [q * RM + tq]: row q of the workgroup, row tq of the residual; the last one: |r|^2
   double nrm2 = 0;
-  // product of the workgroup's rows (registers) with the image, sums over the workgroup: s_Z
-  auto product = [&]() {
+  // product of the workgroup's rows (registers) with the image, sums over the workgroup: s_Z.  sb: the first of its
+  // three stamps in the profiling build (>= 64: none)
+  auto product = [&](int sb) {
 #pragma unroll
-    for (int q = 0; q < NR; ++q)
-#pragma unroll
-      for (int tq = 0; tq < RM; ++tq) acc[q][tq] = 0;
+    for (int i = 0; i < NR * RM; ++i) acc[i] = 0;
 #pragma unroll
     for (int u = 0; u < NS; ++u) {
       const int sidx = wave_u + kPcNW * u;
       if (sidx < nstep) {
-        const double *__restrict__ xs = s_res + (size_t)(sidx * 128 + 2 * lane) * r;
-        double x0[RM], x1[RM];
+        const double2 *__restrict__ xs = reinterpret_cast<const double2 *>(s_img) + (size_t)(sidx * 64 + llane) * r;
+        double x[2 * RM];  // x[tq]: column 2 llane, x[r + tq]: column 2 llane + 1
 #pragma unroll
         for (int tq = 0; tq < RM; ++tq) {
-          x0[tq] = xs[tq];
-          x1[tq] = xs[r + tq];
+          const double2 xx = xs[tq];
+          x[2 * tq] = xx.x;
+          x[2 * tq + 1] = xx.y;
         }
 #pragma unroll
         for (int tq = 0; tq < RM; ++tq)
 #pragma unroll
-          for (int q = 0; q < NR; ++q) acc[q][tq] = fma(x0[tq], mreg[u][q].x, fma(x1[tq], mreg[u][q].y, acc[q][tq]));
+          for (int q = 0; q < NR; ++q)
+            acc[q * RM + tq] = fma(x[tq], mreg[u][q].x, fma(x[r + tq], mreg[u][q].y, acc[q * RM + tq]));
       }
     }
+    RUN_STAMP(sb);
+#ifdef DCORA_RUN_BUTTERFLY_SUMS
+    acc[NR * RM] = nrm2;
 #pragma unroll
-    for (int q = 0; q < NR; ++q)
-#pragma unroll
-      for (int tq = 0; tq < RM; ++tq) {
-        const double v = row16_sum_dpp(acc[q][tq]);
-        if ((lane & 15) == 0) s_P[q * RM + tq][wave * 4 + (lane >> 4)] = v;
-      }
-    {
-      const double v = row16_sum_dpp(nrm2);
-      if ((lane & 15) == 0) s_P[NR * RM][wave * 4 + (lane >> 4)] = v;
+    for (int i = 0; i <= NR * RM; ++i) {
+      const double v = row16_sum_dpp(acc[i]);
+      if ((lane & 15) == 0) s_P[i][wave * 4 + (lane >> 4)] = v;
     }
+#else
+    acc[NR * RM] = __shfl(nrm2, llane);  // |r|^2 is summed over the staging's threads: logical lane = thread
+    wg_row_sums<NR * RM + 1>(acc, s_P, wave, lane);
+#endif
+    RUN_STAMP(sb + 1);
     __syncthreads();
     if ((int)threadIdx.x <= NR * RM) {
       double v = 0;
@@ -1621,6 +1687,7 @@ __global__ __launch_bounds__(kPcBlock) void k_tcg_run(TcgRunArgs a) {
       s_Z[threadIdx.x] = v;
     }
     __syncthreads();
+    RUN_STAMP(sb + 2);
   };
   // z = Proj_X(columns), partial <z, r> (wave 0 holds the per-pose lanes), published for the other workgroups
   auto project_z = [&]() {
@@ -1701,7 +1768,7 @@ __global__ __launch_bounds__(kPcBlock) void k_tcg_run(TcgRunArgs a) {
   if (own) s_R[lc * RM + t] = o_r;
   __syncthreads();
   RUN_STAMP(1);
-  product();
+  product(64);
   project_z();
   RUN_STAMP(2);
   if (c_max_inner <= 0) {  // (no inner iterations allowed: the launch form leaves eta = 0 behind as well)
@@ -1715,6 +1782,7 @@ __global__ __launch_bounds__(kPcBlock) void k_tcg_run(TcgRunArgs a) {
   // ---- the iterations ----
   for (int iter = 0;; ++iter) {
     const int par = iter & 1;
+    [[maybe_unused]] const int sb0 = kRunStamp0 + kRunStampsPerIter * iter;
     double *__restrict__ d_new = par ? a.d1 : a.d0;
     const double *__restrict__ d_old = par ? a.d0 : a.d1;
     // ======== A: delta = beta delta - z in the gather, H delta = Proj_X(delta Q - delta S), <delta, H delta> ========
@@ -1740,6 +1808,10 @@ __global__ __launch_bounds__(kPcBlock) void k_tcg_run(TcgRunArgs a) {
       const double pa = (l < np3) ? ld_coh(a.p3 + l) : 0.0, pb = (l + 64 < np3) ? ld_coh(a.p3 + l + 64) : 0.0;
       const double pcc = (l + 128 < np3) ? ld_coh(a.p3 + l + 128) : 0.0, pd = (l + 192 < np3) ? ld_coh(a.p3 + l + 192) : 0.0;
       const double z_r_new = wave_sum((pa + pb) + (pcc + pd));
+#ifdef DCORA_RUN_STAMPS
+      __builtin_amdgcn_s_waitcnt(0);  // the gather's loads have returned
+      RUN_STAMP(sb0);
+#endif
       double beta = 0;
       if (iter > 0) beta = tcg_beta(z_r_new, zr);
       const TcgDir dir = iter == 0 ? tcg_dir_start(z_r_new) : tcg_dir_next(z_r_new, beta, alpha, dPd, ePd);
@@ -1799,9 +1871,9 @@ __global__ __launch_bounds__(kPcBlock) void k_tcg_run(TcgRunArgs a) {
       __syncthreads();
       if (own) o_h = s_H[e];
     }
-    RUN_STAMP(4 + 7 * iter);
+    RUN_STAMP(sb0 + 1);
     if (!run_grid_step(a.sync, gstep++, &s_ok)) return give_up();
-    RUN_STAMP(5 + 7 * iter);
+    RUN_STAMP(sb0 + 2);
     // ======== PC: step length, updates, z = Proj_X(res Minv), stopping rules ========
     double2 xh[kPcSB];
 #pragma unroll
@@ -1852,7 +1924,7 @@ __global__ __launch_bounds__(kPcBlock) void k_tcg_run(TcgRunArgs a) {
       o_r = rr;
       s_R[lc * RM + t] = rr;
     }
-    RUN_STAMP(6 + 7 * iter);
+    RUN_STAMP(sb0 + 3);
     nrm2 = 0;
 #pragma unroll
     for (int u = 0; u < kPcSB; ++u) {
@@ -1867,9 +1939,8 @@ __global__ __launch_bounds__(kPcBlock) void k_tcg_run(TcgRunArgs a) {
       }
     }
     __syncthreads();
-    RUN_STAMP(7 + 7 * iter);
-    product();
-    RUN_STAMP(8 + 7 * iter);
+    RUN_STAMP(sb0 + 4);
+    product(sb0 + 5);
     {
       if (tcg_residual_done(sqrt(s_Z[NR * RM]), n0)) {
         status = tcg_residual_status(n0);
@@ -1884,12 +1955,48 @@ __global__ __launch_bounds__(kPcBlock) void k_tcg_run(TcgRunArgs a) {
       finish();
       return;
     }
-    RUN_STAMP(9 + 7 * iter);
+    RUN_STAMP(sb0 + 8);
     if (!run_grid_step(a.sync, gstep++, &s_ok)) return give_up();
-    RUN_STAMP(10 + 7 * iter);
+    RUN_STAMP(sb0 + 9);
   }
 }
 
+// test entry (dcora_debug_wg_sums): ONE workgroup sums NV values per logical lane (in[i * kPcBlock + wave * 64 + L])
+// with wg_row_sums and with row16_sum_dpp; out: per form (the reduce-scatter first) the NV x 16 row sums as k_tcg_run
+// keeps them in LDS, then the NV totals of its serial add
+template <int NV>
+__global__ __launch_bounds__(kPcBlock) void k_debug_wg_sums(const double *__restrict__ in, double *__restrict__ out) {
+  __shared__ double s_P[NV][4 * kPcNW];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  double v[NV];
+#pragma unroll
+  for (int form = 0; form < 2; ++form) {
+    const int src = wave * 64 + (form == 0 ? wg_sums_logical_lane(lane) : lane);
+#pragma unroll
+    for (int i = 0; i < NV; ++i) v[i] = in[(size_t)i * kPcBlock + src];
+    if (form == 0) {
+      wg_row_sums<NV>(v, s_P, wave, lane);
+    } else {
+#pragma unroll
+      for (int i = 0; i < NV; ++i) {
+        const double s = row16_sum_dpp(v[i]);
+        if ((lane & 15) == 0) s_P[i][wave * 4 + (lane >> 4)] = s;
+      }
+    }
+    __syncthreads();
+    double *__restrict__ o = out + (size_t)form * NV * (4 * kPcNW + 1);
+    if ((int)threadIdx.x < NV) {
+      double t = 0;
+#pragma unroll
+      for (int w = 0; w < 4 * kPcNW; ++w) {
+        t += s_P[threadIdx.x][w];
+        o[threadIdx.x * 4 * kPcNW + w] = s_P[threadIdx.x][w];
+      }
+      o[NV * 4 * kPcNW + threadIdx.x] = t;
+    }
+    __syncthreads();
+  }
+}
 
 // ------------------------------------------------------------------------------------------------------
 // RG = Proj_X(EG), S_i = sym(Y_i^T EG_i), partial |RG|^2
@@ -2727,14 +2834,15 @@ int launch_tcg_run(hipStream_t st, const ManiDesc &m, int ldm, const double *Min
       static double acc[64];
       static int n = 0;
       long long s0 = buf[0];
-      if (buf[3] > s0 && buf[5 + 7 * 3] > 0) {
-        for (int i = 0; i < 40; ++i) acc[i] += (double)(buf[i] - s0) * 0.01;
+      constexpr int kShown = kRunStamp0 + 4 * kRunStampsPerIter;
+      if (buf[3] > s0 && buf[kShown - 1] > 0) {
+        for (int i = 0; i < kShown; ++i) acc[i] += (double)(buf[i] - s0) * 0.01;
         ++n;
       }
       for (int i = 0; i < 64; ++i) buf[i] = 0;
       if (n == 500) {
-        fprintf(stderr, "k_tcg_run stamps (us from start, workgroup 0, mean of %d runs with >= 4 iterations):", n);
-        for (int i = 0; i < 34; ++i) fprintf(stderr, " %.2f", acc[i] / n);
+        fprintf(stderr, "k_tcg_run stamps (us from start, workgroup 0, mean of %d runs that went past their fourth iteration):", n);
+        for (int i = 0; i < kShown; ++i) fprintf(stderr, " %.2f", acc[i] / n);
         fprintf(stderr, "\n");
         n = -1000000;
       }
@@ -2747,6 +2855,13 @@ int launch_tcg_run(hipStream_t st, const ManiDesc &m, int ldm, const double *Min
   if (m.r == 5) return tcg_run_launch<5>(st, a);
   if (m.r == 6) return tcg_run_launch<6>(st, a);
   return -1;
+}
+int launch_debug_wg_sums(hipStream_t st, int nv, const double *in, double *out) {
+  if (nv == 33) hipLaunchKernelGGL((k_debug_wg_sums<33>), dim3(1), dim3(kPcBlock), 0, st, in, out);
+  else if (nv == 41) hipLaunchKernelGGL((k_debug_wg_sums<41>), dim3(1), dim3(kPcBlock), 0, st, in, out);
+  else if (nv == 49) hipLaunchKernelGGL((k_debug_wg_sums<49>), dim3(1), dim3(kPcBlock), 0, st, in, out);
+  else return -1;
+  return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 int launch_fused_pc(hipStream_t st, const ManiDesc &m, int ldm, const double *Minv, Buf2 grad, Buf2 X,
                     const double *delta, const double *Hd, double *eta, double *Heta, const double *res_old,

@@ -121,6 +121,11 @@ int dcora_problem_solver_info(dcora_problem_t p, double *info);
 int dcora_debug_tcg_run_fault(int runs);
 /* the same after `skip` launches of the run kernel that pass untouched (to hit the LAST iteration of a solve) */
 int dcora_debug_tcg_run_fault_at(int skip, int runs);
+/* test hook: one workgroup of 256 threads sums nv values per lane (nv = 33, 41, 49; in[i * 256 + 64 * wave + lane], host)
+ * over its 16-lane rows the way the one-launch tCG run does (a reduce-scatter over lane-swap instructions) and with the
+ * four-step DPP butterfly.  out (host, 2 * nv * 17 doubles): for each of the two, in that order, the nv x 16 row sums
+ * (out[i * 16 + 4 * wave + row]) followed by the nv totals of the serial add over the 16. */
+int dcora_debug_wg_sums(int nv, const double *in, double *out);
 /* PreCondition (ref :70-84, 261-297) */
 int dcora_problem_precondition(dcora_problem_t p, const double *X, const double *V, double *out);
 /* Retract (ref :125-136, 236-259) */
