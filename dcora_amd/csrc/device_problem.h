@@ -246,7 +246,7 @@ class DeviceProblem {
   std::vector<hipEvent_t> run_events;  // pairs (start, stop)
   size_t run_events_used = 0;
   int profile_tcg_read(double *launches, double *total_us);
-  bool fused = false;                  // SE layout, r <= 8: three-launch tCG iteration (solver_fused.hip)
+  bool fused = false;                  // SE layout, r <= 8: three-launch tCG iteration (fused_step.hip)
   bool group = false;                  // SE layout, r <= 8: 8-lanes-per-pose rgrad / retract kernels (any n)
   DevBuf<double> pA, pB, pC, p1, p2, p3, scal;
   DevBuf<SolverCtl> ctl;
@@ -318,6 +318,7 @@ class DeviceProblem {
 
   int time_qapply(int reps, double *avg_ms, double *bytes);
   int time_precond(int reps, double *avg_ms, double *bytes);
+  TcgOperands tcg_operands() const;  // what this problem's dense tCG launches share (kernels.h), from its workspace
   bool use_pc() const;  // dense preconditioner, step + product + projection in one launch (k_fused_pc)
 
  private:

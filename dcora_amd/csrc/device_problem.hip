@@ -807,6 +807,22 @@ int DeviceProblem::profile_tcg_read(double *launches, double *total_us) {
   return DCORA_OK;
 }
 
+// the operands of this problem's dense tCG launches (kernels.h), from its workspace
+TcgOperands DeviceProblem::tcg_operands() const {
+  TcgOperands o;
+  o.m = m;  o.ldm = ldm;  o.Minv = sparse_precond ? nullptr : Minv.p;
+  o.Q = Q.view();  o.has_bsr = has_bsr;
+  if (has_bsr) o.Qb = Qb.view();
+  o.grad = RGb();  o.X = Xb();  o.S = Sb();
+  o.d[0] = delta.p;  o.d[1] = delta2.p;  o.r[0] = res.p;  o.r[1] = res2.p;
+  o.Hd = Hd.p;  o.eta = eta.p;  o.Heta = Heta.p;  o.z = z.p;  o.Zpart = Zpart.p;  o.W = W.p;
+  o.p1 = p1.p;  o.p2 = p2.p;  o.p3 = p3.p;  o.pC = pC.p;
+  o.ctl = ctl.p;  o.hf = hf_dev;  o.sync = tcg_sync.p;
+  // without hubs the sparse preconditioner's two permutations ride in B (scatter of the residual) and C (gather of z)
+  if (sparse_precond && sp.foldable()) o.sf = sp.fold();
+  return o;
+}
+
 bool DeviceProblem::use_pc() const {
   const int forced = env::solver_bc();
   if (sparse_precond || !has_precond) return false;
@@ -820,7 +836,7 @@ bool DeviceProblem::use_pc() const {
 //   generic: the thread-per-variable kernels of kernels.hip, any layout -- per tCG iteration the Hessian SpMM with the
 //            direction update folded in (k_spmm_dir [+ k_hessfix], or k_spmm_dir_fix), k_tcg_update1, the
 //            preconditioner, k_tangent;
-//   split:   the fused kernels of solver_fused.hip (SE layout, r <= 8) -- per tCG iteration A (direction update +
+//   split:   the fused kernels of fused_step.hip (SE layout, r <= 8) -- per tCG iteration A (direction update +
 //            Q-apply + Riemannian Hessian correction + <d,Hd>), B (step length + vector updates + |r|^2 + dense
 //            preconditioner slices; with the sparse preconditioner its level replay follows), C (stopping rule + slice
 //            sum + tangent projection + <z,r>);
@@ -834,9 +850,8 @@ struct DeviceProblem::RtrForm {
   TcgForm form;
   int &seq;
   const int solve_first;
-  SolverCtl *const c;
-  const CsrDev Qv;
-  const BsrDev Qbv;
+  const TcgOperands o;  // what the fused launches share; the generic form reads its Q and direction buffers too
+  SolverCtl *const c;   // o.ctl, for the gates of every form
   const double *const Gp;
   const long N;
   const int nA, nP, nV, nPB;
@@ -847,32 +862,24 @@ struct DeviceProblem::RtrForm {
   const bool hess_fused;
   // fused forms
   const int nPG;
-  const double *const Mi;  // null: B only updates, the sparse levels follow
-  // without hubs the sparse preconditioner's two permutations ride in B (scatter of the residual) and C (gather of z)
-  const bool folded;
-  const SpFold sf;
-  const int nsl;
+  const bool folded;  // the sparse preconditioner's permutations ride in B and C (o.sf)
   const int nZ;  // <z, r> partial slots A sums in its prologue
   // cost + gradient of an evaluation in one launch where the kernel exists (small CSR blocks; large blocks: the same
   // on the block structure, k_spmm_bsrq<.., GRAD>), else Q-apply + rgrad
   const bool gf, gfb;
   unsigned *const sync_p;  // the run form's grid-step counters, zeroed by k_rtr_init / k_rtr_decide
   const int nsync;
-  double *const dbuf[2];
-  double *const rbuf[2];
 
   RtrForm(DeviceProblem &p_, TcgForm f, int &seq_)
-      : p(p_), form(f), seq(seq_), solve_first(seq_ + 1), c(p.ctl.p), Qv(p.Q.view()),
-        Qbv(p.has_bsr ? p.Qb.view() : BsrDev{}), Gp(p.has_G ? p.G.p : nullptr), N(p.nelem()), nA(p.npA()),
-        nP(p.npPose()), nV(p.npVec()), nPB(fused_pose_blocks(p.m)), sparse(p.sparse_precond),
+      : p(p_), form(f), seq(seq_), solve_first(seq_ + 1), o(p.tcg_operands()), c(o.ctl),
+        Gp(p.has_G ? p.G.p : nullptr), N(p.nelem()), nA(p.npA()), nP(p.npPose()), nV(p.npVec()),
+        nPB(fused_pose_blocks(p.m)), sparse(p.sparse_precond),
         sfg(f == TcgForm::generic && sparse ? p.sp.fold_generic() : SpFold()),
         hess_fused(f == TcgForm::generic && p.hess_one_launch()),
-        nPG(sparse ? fused_update_grid(p.m) : fused_precond_grid(p.m)), Mi(sparse ? nullptr : p.Minv.p),
-        folded(sparse && p.sp.foldable()), sf(folded ? p.sp.fold() : SpFold{}), nsl(sparse ? 1 : -1),
+        nPG(sparse ? fused_update_grid(p.m) : fused_precond_grid(p.m)), folded(sparse && p.sp.foldable()),
         nZ(f == TcgForm::pc || f == TcgForm::run ? fused_pc_blocks(p.m) : nPB),
         gf(f != TcgForm::generic && !p.has_bsr && p.Q.n_long == 0), gfb(f != TcgForm::generic && p.has_bsr),
-        sync_p(f == TcgForm::run ? p.tcg_sync.p : nullptr), nsync(f == TcgForm::run ? tcg_run_sync_words() : 0),
-        dbuf{p.delta.p, p.delta2.p}, rbuf{p.res.p, p.res2.p} {}
+        sync_p(f == TcgForm::run ? p.tcg_sync.p : nullptr), nsync(f == TcgForm::run ? tcg_run_sync_words() : 0) {}
 
   bool outer_done() const { return p.hf->outer_done_seq >= solve_first; }
   bool stopped(int tcg_first) const { return p.hf->tcg_done_seq >= tcg_first || outer_done(); }
@@ -903,11 +910,11 @@ struct DeviceProblem::RtrForm {
         ride.G_out = p.G.p;
         p.ride_X_ = nullptr;
       }
-      return launch_fused_grad(p.st, p.m, Qv, p.Xb(), Gp, p.EGb(), p.RGb(), p.Sb(), sel, p.pA.p, p.pB.p, nullptr, g(),
+      return launch_fused_grad(p.st, p.m, o.Q, p.Xb(), Gp, p.EGb(), p.RGb(), p.Sb(), sel, p.pA.p, p.pB.p, nullptr, g(),
                                ride.c_rp ? &ride : nullptr);
     }
     if (gfb)
-      return launch_fused_grad_bsr(p.st, p.m.r, p.m.d, Qbv, p.Xb(), Gp, kNoBuf, p.RGb(), p.Sb(), sel, p.pA.p, p.pB.p,
+      return launch_fused_grad_bsr(p.st, p.m.r, p.m.d, o.Qb, p.Xb(), Gp, kNoBuf, p.RGb(), p.Sb(), sel, p.pA.p, p.pB.p,
                                    nullptr, g());
     p.enq_qapply(p.Xb(), sel, Gp, p.EGb(), sel, p.pA.p, g());
     return p.enq_rgrad(p.Xb(), p.EGb(), p.RGb(), p.Sb(), sel, p.pB.p, g());
@@ -935,15 +942,13 @@ struct DeviceProblem::RtrForm {
       }
         [[fallthrough]];
       case TcgForm::pc:
-        if (launch_fused_pc(p.st, p.m, p.ldm, Mi, p.RGb(), p.Xb(), nullptr, nullptr, p.eta.p, p.Heta.p, nullptr, rbuf[0],
-                            p.z.p, nullptr, 0, p.p3.p, c, p.hf_dev, ++seq, 0, 1) < 0) {
+        if (launch_fused_pc(p.st, o, ++seq, 0, 1, 0, false) < 0) {
           set_last_error("k_fused_pc could not be launched on this device");
           return -1;
         }
         return seq;
       case TcgForm::split:
-        launch_fused_precond(p.st, p.m, p.ldm, Mi, p.RGb(), nullptr, nullptr, p.eta.p, p.Heta.p, nullptr, rbuf[0],
-                             p.Zpart.p, nullptr, 0, p.p2.p, c, p.hf_dev, ++seq, 0, 1, sf);
+        launch_fused_precond(p.st, o, ++seq, 0, 1, 0);
         return seq;
     }
     return -1;
@@ -964,8 +969,7 @@ struct DeviceProblem::RtrForm {
       e1 = p.run_events[p.run_events_used + 1];
       p.run_events_used += 2;
     }
-    if (launch_tcg_run(p.st, p.m, p.ldm, Mi, Qv, p.RGb(), p.Xb(), p.Sb(), dbuf[0], dbuf[1], p.Hd.p, p.eta.p, p.Heta.p,
-                       p.z.p, p.p1.p, p.p3.p, p.pC.p, p.tcg_sync.p, c, p.hf_dev, ++seq) < 0) {
+    if (launch_tcg_run(p.st, o, ++seq) < 0) {
       if (e1) p.run_events_used -= 2;
       return 0;
     }
@@ -979,13 +983,11 @@ struct DeviceProblem::RtrForm {
   void rest(bool rejected) {
     if (form != TcgForm::split) return;
     if (sparse && rejected) {
-      launch_fused_finish(p.st, p.m, p.Xb(), p.W.p, rbuf[0], p.z.p, nullptr, 0, p.p3.p, c, p.hf_dev, ++seq, 0, 1, 1,
-                          SpFold{});
+      launch_fused_finish(p.st, o, ++seq, 0, 1, 0, FinishZ::from_raw);
       return;
     }
-    if (sparse) p.sp.apply(p.st, p.m.r, buf1(rbuf[0]), p.Zpart.p, Gate{c, ++seq, 1}, folded);
-    launch_fused_finish(p.st, p.m, p.Xb(), p.Zpart.p, rbuf[0], p.z.p, nullptr, 0, p.p3.p, c, p.hf_dev, ++seq, 0, 1, nsl,
-                        sf, sparse ? p.W.p : nullptr);
+    if (sparse) p.sp.apply(p.st, p.m.r, buf1(o.res_new(0, 1)), p.Zpart.p, Gate{c, ++seq, 1}, folded);
+    launch_fused_finish(p.st, o, ++seq, 0, 1, 0, sparse ? FinishZ::keep_raw : FinishZ::slices);
   }
 
   // The sparse replay behind the verdict of the step kernel just enqueued (k_tcg_update1 / B), which decides whether
@@ -1017,13 +1019,13 @@ struct DeviceProblem::RtrForm {
     if (form == TcgForm::generic) {
       // the direction update (the tCG recurrence: iteration 0 starts it, later ones finish iteration j - 1) rides in
       // the Hessian SpMM (k_spmm_dir)
-      double *const dcur = dbuf[par];
+      double *const dcur = o.d[par];
       int nP1 = nP;
       if (hess_fused) {
-        nP1 = launch_spmm_dir_fix(p.st, p.m, Qv, p.Xb(), p.Sb(), p.z.p, dbuf[par ^ 1], dcur, p.Hd.p, p.p3.p, nP, p.p1.p,
+        nP1 = launch_spmm_dir_fix(p.st, p.m, o.Q, p.Xb(), p.Sb(), p.z.p, o.d[par ^ 1], dcur, p.Hd.p, p.p3.p, nP, p.p1.p,
                                   c, ++seq, j);
       } else {
-        launch_spmm_dir(p.st, p.m.r, Qv, p.z.p, dbuf[par ^ 1], dcur, p.W.p, p.p3.p, nP, c, ++seq, j);
+        launch_spmm_dir(p.st, p.m.r, o.Q, p.z.p, o.d[par ^ 1], dcur, p.W.p, p.p3.p, nP, c, ++seq, j);
         launch_hessfix(p.st, p.m, p.Xb(), p.Sb(), dcur, p.W.p, p.Hd.p, p.p1.p, Gate{c, ++seq, 2});
       }
       launch_tcg_update1(p.st, N, dcur, p.Hd.p, p.eta.p, p.Heta.p, p.res.p, p.p1.p, nP1, p.p2.p, c, p.hf_dev, ++seq, j,
@@ -1039,21 +1041,17 @@ struct DeviceProblem::RtrForm {
       if (j == max_inner - 1) launch_tcg_update2(p.st, N, p.z.p, dcur, p.p3.p, nP, c, p.hf_dev, ++seq, j);
       return 1;
     }
-    const int nP1 = launch_fused_hess(p.st, p.m, Qv, p.z.p, dbuf[par ^ 1], dbuf[par], p.Xb(), p.Sb(), p.Hd.p, p.p3.p,
-                                      nZ, p.p1.p, c, ++seq, j, p.has_bsr ? &Qbv : nullptr);
+    const int nP1 = launch_fused_hess(p.st, o, ++seq, j, nZ);
     if (form == TcgForm::pc) {
-      launch_fused_pc(p.st, p.m, p.ldm, Mi, p.RGb(), p.Xb(), dbuf[par], p.Hd.p, p.eta.p, p.Heta.p, rbuf[par],
-                      rbuf[par ^ 1], p.z.p, p.p1.p, nP1, p.p3.p, c, p.hf_dev, ++seq, j, 0, p.pC.p);
+      launch_fused_pc(p.st, o, ++seq, j, 0, nP1, true);
       return 1;
     }
-    launch_fused_precond(p.st, p.m, p.ldm, Mi, p.RGb(), dbuf[par], p.Hd.p, p.eta.p, p.Heta.p, rbuf[par], rbuf[par ^ 1],
-                         p.Zpart.p, p.p1.p, nP1, p.p2.p, c, p.hf_dev, ++seq, j, 0, sf);
+    launch_fused_precond(p.st, o, ++seq, j, 0, nP1);
     if (sparse) {
-      const int go = replay(buf1(rbuf[par ^ 1]), p.Zpart.p, folded, tcg_first);
+      const int go = replay(buf1(o.res_new(j, 0)), p.Zpart.p, folded, tcg_first);
       if (go <= 0) return go;
     }
-    launch_fused_finish(p.st, p.m, p.Xb(), p.Zpart.p, rbuf[par ^ 1], p.z.p, p.p2.p, nPG, p.p3.p, c, p.hf_dev, ++seq, j,
-                        0, nsl, sf);
+    launch_fused_finish(p.st, o, ++seq, j, 0, nPG);
     return 1;
   }
 
@@ -1276,9 +1274,8 @@ int DeviceProblem::time_precond(int reps, double *avg_ms, double *bytes) {
   DCORA_HIP(hipEventCreate(&e1));
   // The dense kernel is timed in its in-loop form (step length from the <d, H d> partials, vector updates, |r|^2),
   // not in the shorter form that opens a tCG run; the partials are set so that the step is a no-op.
-  constexpr bool step_form = true;
   const int nPB = fused_pose_blocks(m);
-  if (step_form && !sparse_precond) {
+  if (!sparse_precond) {
     std::vector<double> ones(std::max((size_t)nPB, (size_t)nelem()), 1.0);
     DCORA_HIP(hipMemcpyAsync(p1.p, ones.data(), sizeof(double) * nPB, hipMemcpyHostToDevice, st));
     // a non-zero residual, so that the one-launch form does not leave through its stopping rule
@@ -1287,18 +1284,17 @@ int DeviceProblem::time_precond(int reps, double *avg_ms, double *bytes) {
     DCORA_HIP(hipStreamSynchronize(st));
   }
   const bool bc_split = !use_pc();
+  // every launch is iteration 1 (odd: it reads d[1], r[1] and writes r[0]) on delta, res and res2
+  TcgOperands o = tcg_operands();
+  std::swap(o.d[0], o.d[1]);
+  std::swap(o.r[0], o.r[1]);
   auto run = [&]() {
     if (sparse_precond)
       sp.apply(st, m.r, buf1(RG0.p), Zt.p, Gate{});
     else if (!bc_split)  // the one-launch B + C of the dense path, in its in-loop form
-      launch_fused_pc(st, m, ldm, Minv.p, RGb(), Xb(), delta.p, Hd.p, eta.p, Heta.p, res.p, res2.p, z.p, p1.p,
-                      nPB, p3.p, ctl.p, hf_dev, 1, 1, 0);
-    else if (step_form)
-      launch_fused_precond(st, m, ldm, Minv.p, RGb(), delta.p, Hd.p, eta.p, Heta.p, res.p, res2.p, Zpart.p, p1.p, nPB,
-                           p2.p, ctl.p, hf_dev, 1, 1, 0);
+      launch_fused_pc(st, o, 1, 1, 0, nPB, false);
     else
-      launch_fused_precond(st, m, ldm, Minv.p, RGb(), nullptr, nullptr, eta.p, Heta.p, nullptr, res.p, Zpart.p,
-                           nullptr, 0, p2.p, ctl.p, hf_dev, 1, 0, 1);
+      launch_fused_precond(st, o, 1, 1, 0, nPB);
   };
   for (int i = 0; i < 3; ++i) run();
   DCORA_HIP(hipEventRecord(e0, st));

@@ -245,27 +245,47 @@ void launch_scale_shift(hipStream_t st, int n, double shift, const double *x, do
 void launch_scale(hipStream_t st, int n, const double *alpha_dev_inv_sqrt /*device: w /= sqrt(*p)*/,
                   const double *w, double *out);
 
-// ---- fused SE-layout solver kernels (solver_fused.hip): 8 lanes per pose, three launches per tCG iteration ----
+// ---- fused SE-layout solver kernels: 8 lanes per pose, three launches per tCG iteration (fused_step.hip), or one per
+// run (fused_run.hip); the evaluations are in fused_eval.hip, the manifold kernels in fused_pose.hip ----
 bool fused_supported(const ManiDesc &m);
 bool group_supported(const ManiDesc &m);    // 8-lanes-per-pose rgrad / retract / Nesterov kernels usable
 int fused_pose_blocks(const ManiDesc &m);   // partial slots written by hess / finish
 int fused_nsplit(const ManiDesc &m);        // row slices of the dense preconditioner product
 int fused_precond_grid(const ManiDesc &m);  // partial slots written by precond
 // Minv == nullptr: the kernel does the step / vector updates only (the sparse preconditioner follows as its own
-// launches); it then writes fused_update_grid(m) partial slots, and finish is called with nsplit = 1
+// launches); it then writes fused_update_grid(m) partial slots, and finish sums one slice
 int fused_update_grid(const ManiDesc &m);
-// returns the number of <d, H d> partials written (p1)
-int launch_fused_hess(hipStream_t st, const ManiDesc &m, const CsrDev &Q, const double *z, const double *d_old,
-                       double *d_new, Buf2 X, Buf2 S, double *Hd, const double *p3, int np3, double *p1,
-                       SolverCtl *ctl, int seq, int iter,
-                      const BsrDev *Ab = nullptr /* block-CSR copy of Q: 8-lanes-per-pose kernel */);
-void launch_fused_precond(hipStream_t st, const ManiDesc &m, int ldm, const double *Minv, Buf2 grad,
-                          const double *delta, const double *Hd, double *eta, double *Heta, const double *res_old,
-                          double *res_new, double *Zpart, const double *p1, int np1, double *p2, SolverCtl *ctl,
-                          HostFlags *hf, int seq, int iter, int first, SpFold sf = SpFold());
+// What every launch of one solve's dense tCG steps shares, stated once per solve.  The launches below take it with what
+// varies per launch: seq, the iteration, `first` (the launch opens a tCG run: res = grad, no step) and the number of
+// partials coming in.  With par = iter & 1, iteration `iter` reads the direction d[par ^ 1] and the residual r[par] and
+// writes d[par] and r[par ^ 1]; a run opens with its residual in r[0].  The launches below pick them themselves.
+struct TcgOperands {
+  ManiDesc m{};
+  int ldm = 0;
+  const double *Minv = nullptr;  // null: B only updates, the sparse levels follow
+  CsrDev Q;
+  BsrDev Qb;                     // block-CSR copy of Q (has_bsr): A runs its 8-lanes-per-pose kernel on it
+  bool has_bsr = false;
+  Buf2 grad{}, X{}, S{};
+  double *d[2] = {nullptr, nullptr}, *r[2] = {nullptr, nullptr};
+  double *Hd = nullptr, *eta = nullptr, *Heta = nullptr, *z = nullptr;
+  double *Zpart = nullptr;  // split-K slices of B, summed by C
+  double *W = nullptr;      // sparse preconditioner: the unprojected z0, kept for a rejected step
+  double *p1 = nullptr, *p2 = nullptr, *p3 = nullptr, *pC = nullptr;
+  SolverCtl *ctl = nullptr;
+  HostFlags *hf = nullptr;
+  SpFold sf;                 // the sparse preconditioner's permutations riding in B and C
+  unsigned *sync = nullptr;  // the one-launch run's grid-step counters
+  // the residual a step launch leaves (and the C launch behind it reads)
+  double *res_new(int iter, int first) const { return first ? r[0] : r[(iter & 1) ^ 1]; }
+};
+// A; np3: <z, r> partials coming in.  Returns the number of <d, H d> partials written (p1)
+int launch_fused_hess(hipStream_t st, const TcgOperands &o, int seq, int iter, int np3);
+// B; np1: <d, H d> partials coming in (ignored when first)
+void launch_fused_precond(hipStream_t st, const TcgOperands &o, int seq, int iter, int first, int np1);
 // B + C in one launch (dense preconditioner): returns the number of <z, r> partial slots written to p3
 int fused_pc_blocks(const ManiDesc &m);
-// ONE launch per tCG run (k_tcg_run, solver_fused.hip): the dense one-launch B + C form's sizes with n / 2 workgroups
+// ONE launch per tCG run (k_tcg_run, fused_run.hip): the dense one-launch B + C form's sizes with n / 2 workgroups
 // co-resident (cus = CUs of the device) and an even number of poses per k_fused_hess workgroup; max_rows_nnz: the most
 // CSR entries any workgroup's 2 (d+1) matrix rows hold.  tcg_run_sync_words: unsigned words of its grid-step counters.
 bool tcg_run_supported(const ManiDesc &m, int ldm, int cus, int max_rows_nnz);
@@ -274,22 +294,22 @@ extern std::atomic<int> g_tcg_run_fault;  // test hook: that many of the next ru
 extern std::atomic<int> g_tcg_run_fault_skip;  // ... after this many launches of the run kernel that pass untouched
 int tcg_run_max_rows_nnz(const ManiDesc &m, const int *rowptr);  // host CSR row pointers -> the figure above
 // returns the number of workgroups (= <z, r> and pC partial pairs), < 0 when the launch is refused
-int launch_tcg_run(hipStream_t st, const ManiDesc &m, int ldm, const double *Minv, const CsrDev &Q, Buf2 grad, Buf2 X,
-                   Buf2 S, double *d0, double *d1, double *Hd, double *eta, double *Heta, double *z, double *p1r,
-                   double *p3, double *pC, unsigned *sync, SolverCtl *ctl, HostFlags *hf, int seq);
+int launch_tcg_run(hipStream_t st, const TcgOperands &o, int seq);
 // test entry: one workgroup of 256 threads sums nv = 8 r + 1 (r = 4, 5, 6) values per lane with k_tcg_run's reduce-scatter
 // row sums and with the DPP butterfly; in: nv x 256 (device), out: 2 x (nv x 16 row sums + nv totals); < 0: refused
 int launch_debug_wg_sums(hipStream_t st, int nv, const double *in, double *out);
 bool fused_pc_preferred(const ManiDesc &m, int ldm);  // sizes at which it beats B + C
 bool fused_pc_ready(const ManiDesc &m, int ldm);      // the current device grants the kernel its dynamic LDS
-int launch_fused_pc(hipStream_t st, const ManiDesc &m, int ldm, const double *Minv, Buf2 grad, Buf2 X,
-                    const double *delta, const double *Hd, double *eta, double *Heta, const double *res_old,
-                    double *res_new, double *z, const double *p1, int np1, double *p3, SolverCtl *ctl, HostFlags *hf,
-                    int seq, int iter, int first, double *pC = nullptr /* set: the launch that ends a tCG run retracts */);
-void launch_fused_finish(hipStream_t st, const ManiDesc &m, Buf2 X, const double *Zpart, const double *res,
-                         double *z, const double *p2, int np2, double *p3, SolverCtl *ctl, HostFlags *hf, int seq,
-                         int iter, int first, int nsplit = -1 /* -1: fused_nsplit(m) */, SpFold sf = SpFold(),
-                         double *zraw = nullptr /* the unprojected P r, kept for a rejected step */);
+// retract: the launch that ends a tCG run retracts and leaves its {<eta, grad>, <eta, H eta>} partials in pC
+int launch_fused_pc(hipStream_t st, const TcgOperands &o, int seq, int iter, int first, int np1, bool retract);
+// C; np2: |r|^2 partials coming in (ignored when first).  What it sums and projects:
+enum class FinishZ {
+  slices,    // the slices B (or the sparse replay) left in Zpart
+  keep_raw,  // the same, and the unprojected sum is kept in W
+  from_raw   // what keep_raw left in W (the first block after a rejected step: the gradient did not move)
+};
+void launch_fused_finish(hipStream_t st, const TcgOperands &o, int seq, int iter, int first, int np2,
+                         FinishZ zsrc = FinishZ::slices);
 // group-style (8 lanes per pose) rgrad / retract / Nesterov; return the number of partial slots written
 int launch_fused_grad_bsr(hipStream_t st, int r, int d, const BsrDev &A, Buf2 X, const double *G, Buf2 EG, Buf2 RG, Buf2 S,
                           int sel, double *pA, double *pB, double *posenorm, Gate g,

@@ -4,7 +4,7 @@ An agent of the headline (sphere2500 / 5, n = 500, k = 2000) solves with the den
 k_fused_pc (form 1, "two launches") or inside the one-launch tCG run k_tcg_run (form 2, "one launch per run"); beyond
 fused_pc_preferred() the step, product and projection stay separate launches (form 0, "three launches"), and beyond
 kDensePrecondMaxK the preconditioner is the partitioned sparse inverse.  Every shape below states the form the rules of
-device_problem.hip / solver_fused.hip give it, checks that the device chose it, and only then compares the HIP path with
+device_problem.hip / fused_step.hip give it, checks that the device chose it, and only then compares the HIP path with
 the oracle: the operations at a random point, then whole RTR solves (iteration counts, exit reasons, optimum, iterate).
 Form 2 is checked a second time on the launches (DCORA_SOLVER_TCG=launch): both forms against the oracle, not only
 against each other.  Then the trust-region corners on the run form, and RBCD++ traces of the headline split."""

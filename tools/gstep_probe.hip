@@ -1,5 +1,5 @@
 // scratch: what does one grid-wide step cost among G resident workgroups of NT threads (G beyond one per CU)?  The step is
-// run_grid_step of solver_fused.hip (sharded arrival counters, replicated done words, bounded spin).
+// run_grid_step of fused_run.hip (sharded arrival counters, replicated done words, bounded spin).
 //   hipcc --offload-arch=gfx950 -O3 tools/gstep_probe.hip -o tools/bin/gstep_probe
 #include <hip/hip_runtime.h>
 #include <cstdio>
