@@ -514,6 +514,20 @@ def suboptimality_gap(r, d, n, X, psd, eta, lambda_min=None, l=0, b=0, lambda_bo
     return gap.value, neff.value
 
 
+def _session_certify(fn, h, k, eta):
+    """dcora_rbcd_certify / dcora_ra_rbcd_certify -> (psd, theta, v, lambda_min, info): the first four as
+    fast_verification returns them, info = the PSD test's figures (is_psd_device) and the Lanczos products"""
+    psd, th, lm, mv = C.c_int(), C.c_double(), C.c_double(), C.c_longlong()
+    v, i8 = np.zeros(k), np.zeros(8)
+    st = fn(h, float(eta), C.byref(psd), C.byref(th), C.byref(lm), v.ctypes.data_as(C.c_void_p), C.byref(mv),
+            i8.ctypes.data_as(C.c_void_p))
+    if st not in (0, 5):
+        check(st)
+    info = {"symbolic_ms": i8[0], "numeric_ms": i8[1], "arena_bytes": i8[2], "flops": i8[3], "levels": int(i8[4]),
+            "launches": int(i8[5]), "logdet": i8[6], "lookup_ms": i8[7], "matvecs": mv.value}
+    return bool(psd.value), th.value, v, lm.value, info
+
+
 def _run_coloured(fn, h, max_sweeps, rgrad_tol):
     """the coloured run loop of a session or an exchange: sweeps of one tick per colour, each followed by an evaluation"""
     it = C.c_int()
@@ -586,6 +600,11 @@ class RbcdSession:
         out = np.zeros(self.r * self.k)
         check(capi.lib().dcora_rbcd_get_X(self.h, out))
         return unF(out, self.r, self.k)
+
+    def certify(self, eta):
+        """fastVerification of S = Q - Lambda(X) on the device, with the Q the session holds now (its current weights) and
+        its current iterate (dcora_rbcd_certify) -> (psd, theta, v, lambda_min, info); the session is left as it was"""
+        return _session_certify(capi.lib().dcora_rbcd_certify, self.h, self.k, eta)
 
     def iterate(self, selected):
         c2, gn, nxt = C.c_double(), C.c_double(), C.c_int()
@@ -897,6 +916,10 @@ class RaRbcdSession:
         out = np.zeros(self.r * self.k)
         check(capi.lib().dcora_ra_rbcd_get_X(self.h, out))
         return unF(out, self.r, self.k)
+
+    def certify(self, eta):
+        """RbcdSession.certify on the merged problem (dcora_ra_rbcd_certify); v in the global RA ordering"""
+        return _session_certify(capi.lib().dcora_ra_rbcd_certify, self.h, self.k, eta)
 
     def _eval(self, fn, *first):
         c2, gn, nxt = C.c_double(), C.c_double(), C.c_int()

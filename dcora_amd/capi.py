@@ -163,6 +163,7 @@ SIGNATURES = {
     "dcora_rbcd_agent_last_skipped": (C.c_int, [_vp, C.c_int, _PI]),
     "dcora_rbcd_agent_info": (C.c_int, [_vp, C.c_int, _PI, _PI, _PI]),
     "dcora_rbcd_last_result": (C.c_int, [_vp, C.POINTER(ROptResult)]),
+    "dcora_rbcd_certify": (C.c_int, [_vp, C.c_double, _PI, _PD, _PD, _vp, C.POINTER(C.c_longlong), _vp]),
     "dcora_rbcd_profile_tcg_runs": (C.c_int, [_vp, C.c_int]),
     "dcora_rbcd_profile_tcg_read": (C.c_int, [_vp, _dp]),
     "dcora_rbcd_create_robust": (C.c_int, [_vp, C.POINTER(RbcdOptions), C.POINTER(RobustParams), _vp, C.POINTER(_vp)]),
@@ -228,6 +229,7 @@ SIGNATURES = {
     "dcora_ra_rbcd_info": (C.c_int, [_vp, _PI, _vp]),
     "dcora_ra_rbcd_set_X": (C.c_int, [_vp, _dp]),
     "dcora_ra_rbcd_get_X": (C.c_int, [_vp, _dp]),
+    "dcora_ra_rbcd_certify": (C.c_int, [_vp, C.c_double, _PI, _PD, _PD, _vp, C.POINTER(C.c_longlong), _vp]),
     "dcora_ra_rbcd_iterate": (C.c_int, [_vp, C.c_int, _PD, _PD, _vp, _PI]),
     "dcora_ra_rbcd_evaluate": (C.c_int, [_vp, _PD, _PD, _vp, _PI]),
     "dcora_ra_rbcd_run": (C.c_int, [_vp, C.c_int, C.c_double, _PI, _vp, _vp, _vp]),

@@ -1276,6 +1276,29 @@ int dcora_rbcd_run_team(dcora_rbcd_t s, int *iters_done, double *cost2_trace, do
 int dcora_rbcd_last_result(dcora_rbcd_t s, dcora_ropt_result *res) {
   return abi_call({s, res}, [&] { return s->s.last_result(res); });
 }
+namespace {
+// dcora_rbcd_certify / dcora_ra_rbcd_certify: the outputs of SessionCore::certify as dcora_cert_fast_verification
+// reports them (theta, lambda_min and v only when the certificate is refused)
+int session_certify_out(SessionCore &s, double eta, int *certified, double *theta, double *lambda_min, double *v,
+                        long long *matvecs, double *info8) {
+  CertifyResult res;
+  const int rc = s.certify(eta, &res, info8);
+  *certified = res.psd ? 1 : 0;
+  if (matvecs) *matvecs = res.matvecs;
+  if (!res.psd) {
+    if (theta) *theta = res.theta;
+    if (lambda_min) *lambda_min = res.lambda_min;
+    if (v && (long)res.v.size() == s.num_cols()) std::copy(res.v.begin(), res.v.end(), v);
+  }
+  return rc;
+}
+}  // namespace
+int dcora_rbcd_certify(dcora_rbcd_t s, double eta, int *certified, double *theta, double *lambda_min, double *v,
+                       long long *matvecs, double *info8) {
+  return abi_call({s, certified}, [&] {
+    return session_certify_out(s->s, eta, certified, theta, lambda_min, v, matvecs, info8);
+  });
+}
 int dcora_rbcd_X_device_ptr(dcora_rbcd_t s, double **X_dev) {
   return abi_call({s, X_dev}, [&] {
     *X_dev = s->s.Xg.p;
@@ -1548,6 +1571,12 @@ int dcora_ra_rbcd_run_coloured(dcora_ra_rbcd_t s, int max_sweeps, double rgrad_t
 }
 int dcora_ra_rbcd_last_result(dcora_ra_rbcd_t s, dcora_ropt_result *res) {
   return abi_call({s, res}, [&] { return s->s.last_result(res); });
+}
+int dcora_ra_rbcd_certify(dcora_ra_rbcd_t s, double eta, int *certified, double *theta, double *lambda_min, double *v,
+                          long long *matvecs, double *info8) {
+  return abi_call({s, certified}, [&] {
+    return session_certify_out(s->s, eta, certified, theta, lambda_min, v, matvecs, info8);
+  });
 }
 
 // ---- robust estimation ---------------------------------------------------------------------------------------

@@ -50,7 +50,11 @@ int device_min_eig(const HostCsr &S, int maxit, double min_eig_tol, int ncv, uin
 void lambda_entries(const ManiDesc &m, std::vector<int> &I, std::vector<int> &J);
 int device_dual_certificate(const dcora_dims &dims, const double *Xh, const HostCsr &Q, int device, HostCsr *S);
 int host_is_psd(const HostCsr &S, int block, bool *psd);
+// info8 (may be null): the PSD test's, as device_chol_is_pd fills it
 int device_fast_verification(const HostCsr &S, double eta, int block, int device, bool *psd, double *theta,
-                             std::vector<double> *x, double *lambda_min, long *matvecs);
+                             std::vector<double> *x, double *lambda_min, long *matvecs, double *info8 = nullptr);
+// its second half (the PSD test has refused M = S + eta I): minimum eigenpair of M, theta = v^T (A - shift I) v
+int device_verification_eigenpair(const HostCsr &M, double eta, const HostCsr &A, double shift, int device, double *theta,
+                                  std::vector<double> *x, double *lambda_min, long *matvecs);
 
 }  // namespace dcora

@@ -658,30 +658,39 @@ int host_is_psd(const HostCsr &S, int block, bool *psd) {
   return DCORA_OK;
 }
 
-// ref src/DCORA_utils.cpp:1713-1735
-int device_fast_verification(const HostCsr &S, double eta, int block, int device, bool *psd, double *theta,
-                             std::vector<double> *x, double *lambda_min, long *matvecs) {
-  HostCsr M = csr_shift_diag(S, eta);
-  // the PSD test: LL^T of S + eta I succeeds <=> PSD up to eta (ref src/DCORA_utils.cpp:1737-1747), factorised on the
-  // device (device_chol.h)
-  int rc = device_chol_is_pd(M, block, device, psd);
-  if (rc) return rc;
-  if (*psd) return DCORA_OK;
+// the half of fastVerification that runs when the PSD test has refused (ref src/DCORA_utils.cpp:1725-1733): the minimum
+// eigenpair of M = S + eta I and theta = v^T S v.  S is given as A - shift I: (S, 0) by the caller that holds S, (M, eta)
+// by the one that holds only M (session_cert.hip).
+int device_verification_eigenpair(const HostCsr &M, double eta, const HostCsr &A, double shift, int device, double *theta,
+                                  std::vector<double> *x, double *lambda_min, long *matvecs) {
   LanczosResult e;
-  rc = device_min_eig(M, 1000, eta, 20, 12345, device, &e);
+  const int rc = device_min_eig(M, 1000, eta, 20, 12345, device, &e);
   if (rc && rc != DCORA_ERR_NO_CONVERGENCE) return rc;
-  // theta = v^T S v
-  double th = 0;
-  for (int i = 0; i < S.n; ++i) {
+  double th = 0, vv = 0;
+  for (int i = 0; i < A.n; ++i) {
     double s = 0;
-    for (int p = S.rp[i]; p < S.rp[i + 1]; ++p) s += S.v[p] * e.v[S.ci[p]];
+    for (int p = A.rp[i]; p < A.rp[i + 1]; ++p) s += A.v[p] * e.v[A.ci[p]];
     th += e.v[i] * s;
+    vv += e.v[i] * e.v[i];
   }
+  if (shift != 0) th -= shift * vv;
   if (theta) *theta = th;
   if (x) *x = e.v;
   if (lambda_min) *lambda_min = e.lambda;
   if (matvecs) *matvecs = e.matvecs;
   return rc;
+}
+
+// ref src/DCORA_utils.cpp:1713-1735
+int device_fast_verification(const HostCsr &S, double eta, int block, int device, bool *psd, double *theta,
+                             std::vector<double> *x, double *lambda_min, long *matvecs, double *info8) {
+  HostCsr M = csr_shift_diag(S, eta);
+  // the PSD test: LL^T of S + eta I succeeds <=> PSD up to eta (ref src/DCORA_utils.cpp:1737-1747), factorised on the
+  // device (device_chol.h)
+  int rc = device_chol_is_pd(M, block, device, psd, info8);
+  if (rc) return rc;
+  if (*psd) return DCORA_OK;
+  return device_verification_eigenpair(M, eta, S, 0.0, device, theta, x, lambda_min, matvecs);
 }
 
 }  // namespace dcora

@@ -58,6 +58,11 @@ bool chol_numeric_host(const CholSymbolic &S, const double *vals, std::vector<do
 // device numeric factorisation of the matrix whose values (CSR order of the analysed pattern) are vals (host).
 // *pd = every pivot positive.  Symbolic analyses are cached on the pattern.
 int device_chol_is_pd(const HostCsr &A, int block, int device, bool *pd, double *info8 = nullptr);
+// the same from values that are on the device already (CSR order of `pattern`, whose own values are not read; complete
+// once the hipEvent_t `ready` has passed, null = now): no value crosses to the device, and the cache entry found is the
+// one the host-fed call finds for this pattern.  vals_dev is read until the call returns.
+int device_chol_is_pd_dev(const HostCsr &pattern, const double *vals_dev, void *ready, int block, int device,
+                          bool *pd, double *info8 = nullptr);
 
 // the factor itself, by pieces (sparse_precond.h), for the builder of the partitioned inverse: ordered with
 // top_unknowns (nd_top_default() for the replay).  DCORA_ERR_NOT_PD when a pivot is not positive.

@@ -1028,7 +1028,10 @@ int device_chol_prepare(const HostCsr &A, int block, int device) {
 }
 
 namespace {
-int factor_on_device(const HostCsr &A, int block, int top, int device, bool *pd, double *info8, PiecewiseFactor *panels) {
+// vals_dev (may be null): the values in A's CSR order, already on the device and complete once `ready` (may be null: now)
+// has passed; A then carries the pattern alone (the cache key and the analysis read nothing else) and no value is copied
+int factor_on_device(const HostCsr &A, int block, int top, int device, bool *pd, double *info8, PiecewiseFactor *panels,
+                     const double *vals_dev = nullptr, hipEvent_t ready = nullptr) {
   double *info6 = info8;
   if (A.n <= 0 || (int)A.rp.size() != A.n + 1) {
     set_last_error("sparse Cholesky: empty or malformed matrix");
@@ -1111,19 +1114,24 @@ int factor_on_device(const HostCsr &A, int block, int top, int device, bool *pd,
   }
   const long long nnz = (long long)S.a_dest.size();
   const auto t1b = std::chrono::steady_clock::now();
-  const double *vsrc = A.v.data();
-  if (img->vals_pinned) {
-    std::memcpy(img->vals_pinned, A.v.data(), (size_t)nnz * sizeof(double));
-    vsrc = img->vals_pinned;
+  const double *vin = img->vals.p;  // what k_chol_scatter reads
+  if (vals_dev) {
+    if (ready) DCORA_HIP(hipStreamWaitEvent(st, ready, 0));
+    vin = vals_dev;
+  } else {
+    const double *vsrc = A.v.data();
+    if (img->vals_pinned) {
+      std::memcpy(img->vals_pinned, A.v.data(), (size_t)nnz * sizeof(double));
+      vsrc = img->vals_pinned;
+    }
+    DCORA_HIP(hipMemcpyAsync(img->vals.p, vsrc, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice, st));
   }
-  DCORA_HIP(hipMemcpyAsync(img->vals.p, vsrc, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice, st));
   const auto t1x = std::chrono::steady_clock::now();
   DCORA_HIP(hipMemsetAsync(F, 0, arena_bytes, st));
   const auto t1y = std::chrono::steady_clock::now();
   DCORA_HIP(hipMemsetAsync(img->fail.p, 0, sizeof(int), st));
   DCORA_HIP(hipMemsetAsync(img->logdet.p, 0, sizeof(double), st));
-  hipLaunchKernelGGL(k_chol_scatter, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, st, nnz, img->dest.p,
-                     img->vals.p, F);
+  hipLaunchKernelGGL(k_chol_scatter, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, st, nnz, img->dest.p, vin, F);
   for (const Launch &L : img->plan) {
     const int *list = img->lists.p + L.list;
     switch (L.kind) {
@@ -1454,6 +1462,15 @@ int factor_on_device(const HostCsr &A, int block, int top, int device, bool *pd,
 
 int device_chol_is_pd(const HostCsr &A, int block, int device, bool *pd, double *info8) {
   return factor_on_device(A, block, 0, device, pd, info8, nullptr);
+}
+
+int device_chol_is_pd_dev(const HostCsr &pattern, const double *vals_dev, void *ready, int block, int device,
+                          bool *pd, double *info8) {
+  if (!vals_dev) {
+    set_last_error("sparse Cholesky: no device values");
+    return DCORA_ERR_BAD_ARG;
+  }
+  return factor_on_device(pattern, block, 0, device, pd, info8, nullptr, vals_dev, (hipEvent_t)ready);
 }
 
 int device_chol_piecewise_factor(const HostCsr &A, int block, int top_unknowns, int device, PiecewiseFactor *out,

@@ -50,6 +50,8 @@ class RaRbcdSession : public SessionCore {
   int phase_evaluate_dev(double *out_dev) override;
   AgentCore &agent_core(int a) override { return agents[(size_t)a]; }
   long num_cols() const override { return k; }
+  DeviceProblem *central_problem() override { return central.get(); }
+  int cert_block() const override { return 1; }
   int x_stage_hosted(double *host_area) override;
 
  private:

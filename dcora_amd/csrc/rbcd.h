@@ -148,6 +148,9 @@ class RbcdSession : public SessionCore {
 
   AgentCore &agent_core(int a) override { return agents[(size_t)a]; }
   long num_cols() const override { return (long)(d + 1) * n; }
+  DeviceProblem *central_problem() override { return central.get(); }
+  const HostCsr *central_pattern() const override { return robust ? &robust->central_pat : nullptr; }
+  int cert_block() const override { return d + 1; }
   int x_stage_hosted(double *host_area) override;
 
  private:

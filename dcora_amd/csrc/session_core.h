@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "device_problem.h"
+#include "session_cert.h"
 
 namespace dcora {
 
@@ -60,10 +61,19 @@ class SessionCore {
   // measurement the tick equals one-after-the-other updates, for adjacent ones (allow_adjacent) it is well defined.
   int iterate_set(const int *set, int count, int allow_adjacent);
 
+  // fastVerification (ref src/DCORA_utils.cpp:1713-1735) of S = Q - Lambda(X) on the session's current matrices -- the
+  // central Q as the last weight change left it -- at the mirror as it stands (session_cert.h).  Single-process sessions
+  // only; nothing of the session changes.
+  int certify(double eta, CertifyResult *out, double *info8);
+  virtual DeviceProblem *central_problem() = 0;                        // null on a rank of a multi-rank job
+  virtual const HostCsr *central_pattern() const { return nullptr; }  // host copy of its pattern, where one is kept
+  virtual int cert_block() const = 0;  // unknowns the factorisation orders together (d + 1 for poses)
+
  protected:
   const char *tag_;  // "rbcd" / "ra_rbcd": the prefix of the messages
   hipEvent_t fork_ev_ = nullptr;
   bool own_stream_ = true;
+  SessionCertState cert_;  // built by the first certify
 
   // updateGamma / updateAlpha (ref src/Agent.cpp:1189-1200) and the round counter; the sequences are data-independent
   // and identical for every agent, so they live on the host

@@ -30,6 +30,20 @@ int SessionCore::agent_colours(int *colours, int *ncolours) {
   return DCORA_OK;
 }
 
+int SessionCore::certify(double eta, CertifyResult *out, double *info8) {
+  DeviceProblem *central = opt.world_size == 1 ? central_problem() : nullptr;
+  if (!central) {
+    set_last_error(std::string(tag_) + ": certify serves single-process sessions (world_size 1); the ranks of a job "
+                   "certify together through dcora_exchange_certify");
+    return DCORA_ERR_UNSUPPORTED;
+  }
+  DCORA_HIP(hipSetDevice(opt.device));
+  // the mirror is complete: nothing of the session is in flight on an agent's own stream
+  for (int a = 0; a < R; ++a)
+    if (agent_core(a).own_st) DCORA_HIP(hipStreamSynchronize(agent_core(a).own_st));
+  return session_certify(cert_, *central, central_pattern(), Xg.p, cert_block(), eta, out, info8);
+}
+
 int SessionCore::acquire_stream(void *borrowed) {
   own_stream_ = !borrowed;
   if (borrowed) st = (hipStream_t)borrowed;

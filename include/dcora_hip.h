@@ -380,6 +380,22 @@ int dcora_debug_rbcd_launches(dcora_rbcd_t s, long long *launches);
  * written to out_dev[2*b], out_dev[2*b+1] (device, 2*num_robots doubles, entries of non-hosted agents zero) */
 int dcora_rbcd_phase_evaluate_dev(dcora_rbcd_t s, double *out_dev);
 int dcora_rbcd_synchronize(dcora_rbcd_t s);
+/* The certificate of a live single-process session, on the device: fastVerification(S, eta, &theta, &v) (ref
+ * src/DCORA_utils.cpp:1713-1735) on S = Q - Lambda(X) with the Q the session's central problem holds NOW -- the weights
+ * the last dcora_rbcd_update_weights / _set_weights left -- and the session's current iterate.  X Q, the Lambda blocks,
+ * the values of S + eta I (in the CSR order of the central pattern) and the Cholesky factorisation all run where the
+ * session's data is; an accepted certificate moves only the verdict to the host.  *certified (required) = 1: S + eta I
+ * has a Cholesky factorisation.  Otherwise *lambda_min and v (k doubles, the session's global ordering) are the minimum
+ * eigenpair of S + eta I and *theta = v^T S v, as dcora_cert_fast_verification reports them.  theta, lambda_min, v,
+ * matvecs (Lanczos products) and info8 (as dcora_cert_is_psd_device) may be NULL.  The factorisation orders d + 1
+ * unknowns together (range-aided sessions: 1) and shares its analysis cache with the host-fed calls: after
+ * dcora_cert_prepare on Q's pattern it starts with the numeric phase.  Where Q's pattern lacks an entry of Lambda or of
+ * the diagonal (a structural zero inside a rotation block, an isolated pose, a unit sphere without a range) the values
+ * are gathered on the pattern with those entries added, the one dcora_cert_dual_matrix produces: still on the device.
+ * The session is left as it was: a run after the call equals the run without it.
+ * world_size > 1: DCORA_ERR_UNSUPPORTED (the ranks certify together: dcora_exchange_certify). */
+int dcora_rbcd_certify(dcora_rbcd_t s, double eta, int *certified, double *theta, double *lambda_min, double *v,
+                       long long *matvecs, double *info8);
 /* Measurement hook (bench.py's `roofline`): while enabled, HIP events are recorded on the solver's stream around every
  * one-launch tCG run (k_tcg_run) of the session's agents; _read waits for the stream, returns {launches, sum of their
  * event times in us} since the last read and forgets them.  Not for timed regions: an event pair costs a few us. */
@@ -497,6 +513,9 @@ int dcora_ra_rbcd_destroy(dcora_ra_rbcd_t s);
 int dcora_ra_rbcd_info(dcora_ra_rbcd_t s, int *num_agents, int *robots);
 int dcora_ra_rbcd_set_X(dcora_ra_rbcd_t s, const double *X);
 int dcora_ra_rbcd_get_X(dcora_ra_rbcd_t s, double *X);
+/* dcora_rbcd_certify on the merged range-aided problem (v: k doubles in the global RA ordering) */
+int dcora_ra_rbcd_certify(dcora_ra_rbcd_t s, double eta, int *certified, double *theta, double *lambda_min, double *v,
+                          long long *matvecs, double *info8);
 /* as dcora_rbcd_iterate / _evaluate / _run / _last_result; `selected` indexes the agents of dcora_ra_rbcd_info */
 int dcora_ra_rbcd_iterate(dcora_ra_rbcd_t s, int selected, double *cost2, double *gradnorm, double *block_norms,
                           int *next_selected);
