@@ -585,7 +585,8 @@ int DeviceProblem::hessvec(const double *Xh, const double *Vh, double *out) {
   return download(Hd.p, out, nelem());
 }
 bool DeviceProblem::hess_one_launch() const {
-  if (spmm_dir_fix_grid(m, m.k) <= 0 || spmm_dir_fix_grid(m, m.k) + Q.n_long > 4 * kMaxPartials) return false;
+  const int main_grid = spmm_dir_fix_grid(m, m.k);
+  if (main_grid <= 0 || main_grid + Q.n_long > 4 * kMaxPartials) return false;
   for (int jl : Q.long_host) {
     const bool euclid = m.se ? (jl % (m.d + 1) == m.d) : (jl >= m.d * m.n + m.l);
     if (!euclid) return false;
@@ -833,9 +834,9 @@ bool DeviceProblem::use_pc() const {
 }
 
 // What an RTR solve enqueues in each tCG form; DeviceProblem::rtr_dev paces it.  The forms:
-//   generic: the thread-per-variable kernels of kernels.hip, any layout -- per tCG iteration the Hessian SpMM with the
-//            direction update folded in (k_spmm_dir [+ k_hessfix], or k_spmm_dir_fix), k_tcg_update1, the
-//            preconditioner, k_tangent;
+//   generic: the thread-per-variable kernels of kernels.hip and spmm_csr.hip, any layout -- per tCG iteration the
+//            Hessian SpMM with the direction update folded in (k_spmm_dir [+ k_hessfix], or k_spmm_dir_fix),
+//            k_tcg_update1, the preconditioner, k_tangent;
 //   split:   the fused kernels of fused_step.hip (SE layout, r <= 8) -- per tCG iteration A (direction update +
 //            Q-apply + Riemannian Hessian correction + <d,Hd>), B (step length + vector updates + |r|^2 + dense
 //            preconditioner slices; with the sparse preconditioner its level replay follows), C (stopping rule + slice

@@ -4,7 +4,7 @@
 #include <algorithm>
 #include <stdexcept>
 
-#include "kernels.h"
+#include "csr_rows.h"
 #include "tcg_rules.h"
 #include "pose_group.h"
 
@@ -20,34 +20,7 @@ namespace {
 // evaluation (4 per local solve, 1 per central evaluation).
 // ------------------------------------------------------------------------------------------------------
 // RIDE (GradRide, kernels.h): the start-point evaluation forms G from the agent's coupling block first -- every thread
-// for its own element, nothing another workgroup of the launch writes is read.
-// G of one output element as k_spmm<false> forms it: the row's entries in batches of 8 that restart at the tile
-// borders of k_spmm's row block (rows j0 .. j0 + kBlock / r - 1, kSpmmTile entries from rp[j0]), a batch's padding as
-// a zero weight on the segment's first entry, acc = fma(w, x, acc) in index order.
-__device__ __forceinline__ double coupling_row(const GradRide &c, int r, int j, int t) {
-  const int RB = kBlock / r;
-  const int pb0 = c.c_rp[(j / RB) * RB];
-  const int myb = c.c_rp[j], mye = c.c_rp[j + 1];
-  double acc = 0;
-  int lo = myb;
-  while (lo < mye) {
-    const int hi = min(mye, pb0 + ((lo - pb0) / kSpmmTile + 1) * kSpmmTile);
-    for (int p = lo; p < hi; p += 8) {
-      double x8[8], w8[8];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const bool ok = p + q < hi;
-        const int pp = ok ? p + q : lo;
-        w8[q] = ok ? c.c_v[pp] : 0.0;
-        x8[q] = c.c_X[(size_t)c.c_ci[pp] * r + t];
-      }
-#pragma unroll
-      for (int q = 0; q < 8; ++q) acc = fma(w8[q], x8[q], acc);
-    }
-    lo = hi;
-  }
-  return acc;
-}
+// for its own element (coupling_row, csr_rows.h), nothing another workgroup of the launch writes is read.
 template <int D, bool RIDE>
 __global__ __launch_bounds__(kBlock) void k_fused_grad(ManiDesc m, CsrDev Q, Buf2 Xb, const double *__restrict__ G,
                                                        Buf2 EGb, Buf2 RGb, Buf2 Sb, int sel,

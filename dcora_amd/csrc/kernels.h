@@ -128,21 +128,24 @@ struct GradRide {
   double *G_out = nullptr;
 };
 
-// ---- SpMM: Y = X * A (+ G); optional partial dots {sum (X*A) o X, sum X o G}, 2 per block ---------------
+// ---- CSR SpMM of the generic path (spmm_csr.hip; the row walk the kernels share is csr_rows.h) ------------
 int spmm_grid(int nrows, int r);
-// W = (-z + beta d_old) Q with the direction written to d_new and the tCG scalar recurrence of iteration `iter`
-// (tcg_rules.h) folded in
-// k_spmm_dir with k_hessfix folded in (one launch per tCG iteration of the generic layout); returns the number of
-// <delta, Hd> partial slots written to p1.  spmm_dir_fix_grid: 0 when r is too large for whole items per workgroup.
-int spmm_dir_fix_grid(const ManiDesc &m, int nrows);
+inline int spmm_slots(const CsrDev &A, int r) { return spmm_grid(A.nrows, r) + A.n_long; }  // partial slots written
+// Y = X * A (+ G); with partials != null the partial dots {sum (X*A) o X, sum X o G}, 2 per slot
+void launch_spmm(hipStream_t st, int r, const CsrDev &A, Buf2 X, int selX, const double *G, Buf2 Y, int selY,
+                 double *partials, Gate g);
+// k_spmm_dir: W = (-z + beta d_old) Q with the direction written to d_new and the tCG scalar recurrence of iteration
+// `iter` (tcg_rules.h) folded in; k_hessfix follows it.  Runs where launch_spmm_dir_fix does not apply
+// (DeviceProblem::hess_one_launch()): a long row that is not a Euclidean column, or r too large for whole items.
+void launch_spmm_dir(hipStream_t st, int r, const CsrDev &A, const double *z, const double *d_old, double *d_new,
+                     double *W, const double *p3, int np3, SolverCtl *ctl, int seq, int iter);
+// k_spmm_dir_fix: the same with k_hessfix folded in, Hd = Proj_X(W - d_new S): one launch per tCG iteration of the
+// generic layout.  Returns the number of <delta, Hd> partial slots written to p1.
 int launch_spmm_dir_fix(hipStream_t st, const ManiDesc &m, const CsrDev &A, Buf2 X, Buf2 Sblk, const double *z,
                         const double *d_old, double *d_new, double *Hd, const double *p3, int np3, double *p1,
                         SolverCtl *ctl, int seq, int iter);
-void launch_spmm_dir(hipStream_t st, int r, const CsrDev &A, const double *z, const double *d_old, double *d_new,
-                     double *W, const double *p3, int np3, SolverCtl *ctl, int seq, int iter);
-inline int spmm_slots(const CsrDev &A, int r) { return spmm_grid(A.nrows, r) + A.n_long; }  // partial slots written
-void launch_spmm(hipStream_t st, int r, const CsrDev &A, Buf2 X, int selX, const double *G, Buf2 Y, int selY,
-                 double *partials, Gate g);
+// its main grid; 0 when r is too large for whole items per workgroup
+int spmm_dir_fix_grid(const ManiDesc &m, int nrows);
 
 // BSR flavour for the SE layout (8 lanes per pose, one gather of the neighbour's r x (d+1) block per matrix block);
 // returns the number of partial slots written (2 doubles each)

@@ -1,6 +1,6 @@
-// Hand-written HIP kernels for gfx950 (MI355X): connection-Laplacian SpMM, per-pose manifold arithmetic
-// (tangent projection, Riemannian Hessian correction, QF retraction, polar projection), dense preconditioner
-// apply, and the device-resident scalar logic of the truncated-CG / trust-region solver.
+// Hand-written HIP kernels for gfx950 (MI355X): per-pose manifold arithmetic (tangent projection, Riemannian Hessian
+// correction, QF retraction, polar projection), dense preconditioner apply, and the device-resident scalar logic of the
+// truncated-CG / trust-region solver.  The connection-Laplacian SpMM of the same path is spmm_csr.hip.
 //
 // Design notes:
 //  * wavefront = 64; all block-level reductions are wave shuffles + one LDS hop, in a fixed order;
@@ -51,615 +51,6 @@ int vec_grid(long nelem) {
   if (g < 1) g = 1;
   if (g > kMaxPartials) g = kMaxPartials;
   return (int)g;
-}
-
-// ------------------------------------------------------------------------------------------------------
-// SpMM  Y = X * A (+ G).  One thread per output element (column j, component t): the r lanes of a row read r
-// contiguous doubles of X(:, c) and share one (value, column) pair.  The CSR segment of the block's rows is
-// staged in LDS with fully coalesced loads (row blocks of a connection Laplacian are contiguous in CSR).
-// ------------------------------------------------------------------------------------------------------
-int spmm_grid(int nrows, int r) {
-  const int RB = kBlock / r;
-  long nrb = (nrows + RB - 1) / RB;
-  if (nrb < 1) nrb = 1;
-  if (nrb > kMaxPartials) nrb = kMaxPartials;
-  return (int)nrb;
-}
-
-template <bool DOTS>
-__global__ __launch_bounds__(kBlock) void k_spmm(int r, CsrDev A, Buf2 Xb, int selX, const double *__restrict__ G,
-                                                 Buf2 Yb, int selY, double *__restrict__ partials, Gate g,
-                                                 int main_grid) {
-  if (gated(g.ctl, g.seq, g.gate)) return;
-  __shared__ int s_ci[kSpmmTile];
-  __shared__ double s_v[kSpmmTile];
-  __shared__ double s_red[16];
-  const double *__restrict__ X = pick(Xb, g.ctl, selX);
-  double *__restrict__ Y = pick(Yb, g.ctl, selY);
-  const int RB = kBlock / r;
-  const int nrb = (A.nrows + RB - 1) / RB;
-  const int lj = threadIdx.x / r, t = threadIdx.x - lj * r;
-  double d0 = 0, d1 = 0;
-  if ((int)blockIdx.x >= main_grid) {
-    // kLongSplit workgroups per long row (a landmark ranged from 7789 poses on tiers.pyfg: one workgroup was the
-    // longest of the launch): each takes a slice, the RB entry groups stride over it, partial sums meet in LDS and
-    // go to a scratch row; the last workgroup to arrive adds the slices in slice order (reproducible) and finishes
-    const int li = ((int)blockIdx.x - main_grid) / kLongSplit, sl = ((int)blockIdx.x - main_grid) % kLongSplit;
-    const int j = A.long_rows[li];
-    const int rb0 = A.rp[j], re0 = A.rp[j + 1];
-    const int per = (re0 - rb0 + kLongSplit - 1) / kLongSplit;
-    const int pb = rb0 + sl * per, pe = min(re0, pb + per);
-    double acc = 0;
-    if (lj < RB) {
-      // eight entries per step with every load in flight before the first use (index clamped, weight masked)
-      for (int p = pb + lj; p < pe; p += 8 * RB) {
-        int c8[8];
-        double w8[8], x8[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          const int pp = p + q * RB;
-          const bool ok = pp < pe;
-          c8[q] = A.ci[ok ? pp : rb0];
-          w8[q] = ok ? A.v[pp] : 0.0;
-        }
-#pragma unroll
-        for (int q = 0; q < 8; ++q) x8[q] = X[(size_t)c8[q] * r + t];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) acc += w8[q] * x8[q];
-      }
-    }
-    double *s_part = s_v;  // kBlock doubles
-    __shared__ int s_last;
-    __syncthreads();
-    s_part[threadIdx.x] = (lj < RB) ? acc : 0.0;
-    __syncthreads();
-    if ((int)threadIdx.x < r) {
-      double y = 0;
-      for (int q = 0; q < RB; ++q) y += s_part[q * r + threadIdx.x];
-      __hip_atomic_store(A.long_part + ((size_t)li * kLongSplit + sl) * 16 + threadIdx.x, y, __ATOMIC_RELAXED,
-                         __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __threadfence();
-    __syncthreads();
-    if (threadIdx.x == 0)
-      s_last = (__hip_atomic_fetch_add(A.long_cnt + li, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) ==
-                kLongSplit - 1);
-    __syncthreads();
-    if (!s_last) return;
-    if (threadIdx.x == 0) __hip_atomic_store(A.long_cnt + li, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if ((int)threadIdx.x < r) {
-      double y = 0;
-      for (int q = 0; q < kLongSplit; ++q)
-        y += __hip_atomic_load(A.long_part + ((size_t)li * kLongSplit + q) * 16 + threadIdx.x, __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
-      const size_t o = (size_t)j * r + threadIdx.x;
-      if (DOTS) {
-        const double x = X[o];
-        d0 = y * x;
-        if (G) d1 = x * G[o];
-      }
-      if (G) y += G[o];
-      Y[o] = y;
-    }
-    if (DOTS) {
-      const double a = block_sum(d0, s_red);
-      const double b = block_sum(d1, s_red);
-      if (threadIdx.x == 0) {
-        partials[2 * (main_grid + li)] = a;
-        partials[2 * (main_grid + li) + 1] = b;
-      }
-    }
-    return;
-  }
-  for (int rb = blockIdx.x; rb < nrb; rb += main_grid) {
-    const int j0 = rb * RB;
-    const int j1 = min(A.nrows, j0 + RB);
-    const int j = j0 + lj;
-    const bool active = (lj < RB) && (j < j1);
-    const int pbeg = A.rp[j0], pend = A.rp[j1];
-    int myb = active ? A.rp[j] : 0, mye = active ? A.rp[j + 1] : 0;
-    const bool is_long = A.n_long > 0 && (mye - myb > kLongRow);  // served by its own block
-    if (is_long) mye = myb;
-    double acc = 0;
-    for (int base = pbeg; base < pend; base += kSpmmTile) {
-      const int cnt = min(kSpmmTile, pend - base);
-      __syncthreads();
-      {
-        // all trips' loads of the tile are issued (clamped index, straight line) before any is stored to LDS:
-        // one memory round trip per tile instead of one per 256 entries
-        constexpr int SU = kSpmmTile / kBlock;
-        int ci_r[SU];
-        double v_r[SU];
-        const int last = base + cnt - 1;
-#pragma unroll
-        for (int u = 0; u < SU; ++u) {
-          const int i = min(base + (int)threadIdx.x + u * kBlock, last);
-          ci_r[u] = A.ci[i];
-          v_r[u] = A.v[i];
-        }
-#pragma unroll
-        for (int u = 0; u < SU; ++u) {
-          const int i = threadIdx.x + u * kBlock;
-          if (i < cnt) {
-            s_ci[i] = ci_r[u];
-            s_v[i] = v_r[u];
-          }
-        }
-      }
-      __syncthreads();
-      const int lo = max(myb, base) - base, hi = min(mye, base + cnt) - base;
-      // gathers in batches of 8 with every load issued before the first use (index clamped, weight masked)
-      for (int p = lo; p < hi; p += 8) {
-        double x8[8], w8[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          const bool ok = p + q < hi;
-          const int pp = ok ? p + q : lo;
-          w8[q] = ok ? s_v[pp] : 0.0;
-          x8[q] = X[(size_t)s_ci[pp] * r + t];
-        }
-#pragma unroll
-        for (int q = 0; q < 8; ++q) acc += w8[q] * x8[q];
-      }
-    }
-    if (active && !is_long) {
-      const size_t o = (size_t)j * r + t;
-      double y = acc;
-      if (DOTS) {
-        const double x = X[o];
-        d0 += acc * x;
-        if (G) d1 += x * G[o];
-      }
-      if (G) y += G[o];
-      Y[o] = y;
-    }
-  }
-  if (DOTS) {
-    const double a = block_sum(d0, s_red);
-    const double b = block_sum(d1, s_red);
-    if (threadIdx.x == 0) {
-      partials[2 * blockIdx.x] = a;
-      partials[2 * blockIdx.x + 1] = b;
-    }
-  }
-}
-
-// ------------------------------------------------------------------------------------------------------
-// Generic-layout tCG, iteration `iter`: the direction update of the previous iteration folded into the Hessian SpMM.
-//   delta_new = -z + beta delta_old   (beta = <z, r>_new / <z, r>_old from the partials p3; iter 0: delta_new = -z)
-//   W = delta_new Q                   (delta_new formed in the gather, written for the block's own columns)
-// and the scalar recurrence of ROPTLIB's tCG_TR (block 0, tcg_rules.h): iteration 0 starts it, later ones finish iteration
-// iter - 1 as k_tcg_update2 does after the last one.  delta_old and delta_new are different buffers: other workgroups
-// still gather the old direction.
-// ------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kBlock) void k_spmm_dir(int r, CsrDev A, const double *__restrict__ z,
-                                                     const double *__restrict__ d_old, double *__restrict__ d_new,
-                                                     double *__restrict__ W, const double *__restrict__ p3, int np3,
-                                                     SolverCtl *ctl, int seq, int iter, int main_grid) {
-  if (gated(ctl, seq, 2)) return;
-  __shared__ int s_ci[kSpmmTile];
-  __shared__ double s_v[kSpmmTile];
-  __shared__ double s_red[16];
-  __shared__ int s_last;
-  const int par = (iter - 1) & 1;
-  const double z_r_new = sum_partials(p3, np3, 1, 0, s_red);
-  const double beta = iter > 0 ? tcg_beta(z_r_new, ctl->z_r[par]) : 0.0;
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    if (iter == 0)
-      tcg_put_dir(ctl, 0, tcg_dir_start(z_r_new), 0.0);
-    else
-      tcg_put_dir(ctl, par ^ 1, tcg_dir_next(z_r_new, beta, ctl->alpha, ctl->d_Pd[par], ctl->e_Pd[par]), ctl->e_Pe_n);
-  }
-  const int RB = kBlock / r;
-  const int nrb = (A.nrows + RB - 1) / RB;
-  const int lj = threadIdx.x / r, t = threadIdx.x - lj * r;
-  auto dir = [&](size_t o) -> double { return iter > 0 ? fma(beta, d_old[o], -z[o]) : -z[o]; };
-  if ((int)blockIdx.x >= main_grid) {  // a slice of a long row (see k_spmm)
-    const int li = ((int)blockIdx.x - main_grid) / kLongSplit, sl = ((int)blockIdx.x - main_grid) % kLongSplit;
-    const int j = A.long_rows[li];
-    const int rb0 = A.rp[j], re0 = A.rp[j + 1];
-    const int per = (re0 - rb0 + kLongSplit - 1) / kLongSplit;
-    const int pb = rb0 + sl * per, pe = min(re0, pb + per);
-    double acc = 0;
-    if (lj < RB) {
-      for (int p = pb + lj; p < pe; p += 8 * RB) {
-        int c8[8];
-        double w8[8], x8[8], y8[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          const int pp = p + q * RB;
-          const bool ok = pp < pe;
-          c8[q] = A.ci[ok ? pp : rb0];
-          w8[q] = ok ? A.v[pp] : 0.0;
-        }
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          const size_t o = (size_t)c8[q] * r + t;
-          x8[q] = z[o];
-          y8[q] = iter > 0 ? d_old[o] : 0.0;
-        }
-#pragma unroll
-        for (int q = 0; q < 8; ++q) acc += w8[q] * fma(beta, y8[q], -x8[q]);
-      }
-    }
-    double *s_part = s_v;
-    __syncthreads();
-    s_part[threadIdx.x] = (lj < RB) ? acc : 0.0;
-    __syncthreads();
-    if ((int)threadIdx.x < r) {
-      double y = 0;
-      for (int q = 0; q < RB; ++q) y += s_part[q * r + threadIdx.x];
-      __hip_atomic_store(A.long_part + ((size_t)li * kLongSplit + sl) * 16 + threadIdx.x, y, __ATOMIC_RELAXED,
-                         __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __threadfence();
-    __syncthreads();
-    if (threadIdx.x == 0)
-      s_last = (__hip_atomic_fetch_add(A.long_cnt + li, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) ==
-                kLongSplit - 1);
-    __syncthreads();
-    if (!s_last) return;
-    if (threadIdx.x == 0) __hip_atomic_store(A.long_cnt + li, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if ((int)threadIdx.x < r) {
-      double y = 0;
-      for (int q = 0; q < kLongSplit; ++q)
-        y += __hip_atomic_load(A.long_part + ((size_t)li * kLongSplit + q) * 16 + threadIdx.x, __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
-      const size_t o = (size_t)j * r + threadIdx.x;
-      W[o] = y;
-      d_new[o] = dir(o);
-    }
-    return;
-  }
-  for (int rb = blockIdx.x; rb < nrb; rb += main_grid) {
-    const int j0 = rb * RB;
-    const int j1 = min(A.nrows, j0 + RB);
-    const int j = j0 + lj;
-    const bool active = (lj < RB) && (j < j1);
-    const int pbeg = A.rp[j0], pend = A.rp[j1];
-    int myb = active ? A.rp[j] : 0, mye = active ? A.rp[j + 1] : 0;
-    const bool is_long = A.n_long > 0 && (mye - myb > kLongRow);  // served by its own workgroups
-    if (is_long) mye = myb;
-    const double own = (active && !is_long) ? dir((size_t)j * r + t) : 0.0;
-    double acc = 0;
-    for (int base = pbeg; base < pend; base += kSpmmTile) {
-      const int cnt = min(kSpmmTile, pend - base);
-      __syncthreads();
-      {
-        constexpr int SU = kSpmmTile / kBlock;
-        int ci_r[SU];
-        double v_r[SU];
-        const int last = base + cnt - 1;
-#pragma unroll
-        for (int u = 0; u < SU; ++u) {
-          const int i = min(base + (int)threadIdx.x + u * kBlock, last);
-          ci_r[u] = A.ci[i];
-          v_r[u] = A.v[i];
-        }
-#pragma unroll
-        for (int u = 0; u < SU; ++u) {
-          const int i = threadIdx.x + u * kBlock;
-          if (i < cnt) {
-            s_ci[i] = ci_r[u];
-            s_v[i] = v_r[u];
-          }
-        }
-      }
-      __syncthreads();
-      const int lo = max(myb, base) - base, hi = min(mye, base + cnt) - base;
-      for (int p = lo; p < hi; p += 8) {
-        double x8[8], y8[8], w8[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          const bool ok = p + q < hi;
-          const int pp = ok ? p + q : lo;
-          w8[q] = ok ? s_v[pp] : 0.0;
-          const size_t o = (size_t)s_ci[pp] * r + t;
-          x8[q] = z[o];
-          y8[q] = iter > 0 ? d_old[o] : 0.0;
-        }
-#pragma unroll
-        for (int q = 0; q < 8; ++q) acc += w8[q] * fma(beta, y8[q], -x8[q]);
-      }
-    }
-    if (active && !is_long) {
-      const size_t o = (size_t)j * r + t;
-      W[o] = acc;
-      d_new[o] = own;
-    }
-  }
-}
-
-// ------------------------------------------------------------------------------------------------------
-// The same with ROPTLIB's EucHvToHv (k_hessfix) folded in: one launch per tCG iteration instead of two.
-//   delta_new = -z + beta delta_old,  W = delta_new Q,  Hd = Proj_X(W - delta_new S),  partial <delta_new, Hd>
-// A workgroup owns whole manifold items: its rows-per-block count is a multiple of the rotation block's width (d,
-// or d + 1 in the pose layout), so the d columns a Stiefel projection couples sit in one workgroup and meet in LDS.
-// Long rows (served by their own workgroups) must be Euclidean columns (spmm_dir_fix_ok): their Hd is W itself.
-// The arithmetic follows k_hessfix term by term (sub_AS, sym_gram, sub_AS); only the order in which the partial
-// sums of <delta, Hd> are added differs.
-// ------------------------------------------------------------------------------------------------------
-template <int D>
-__global__ __launch_bounds__(kBlock) void k_spmm_dir_fix(ManiDesc m, CsrDev A, Buf2 Xb, Buf2 Sb,
-                                                         const double *__restrict__ z,
-                                                         const double *__restrict__ d_old, double *__restrict__ d_new,
-                                                         double *__restrict__ Hd, const double *__restrict__ p3,
-                                                         int np3, double *__restrict__ p1, SolverCtl *ctl, int seq,
-                                                         int iter, int main_grid) {
-  __shared__ int s_ci[kSpmmTile];
-  __shared__ double s_v[kSpmmTile];
-  __shared__ double s_red[16];
-  __shared__ double s_V[kBlock], s_T[kBlock], s_Y[kBlock];
-  __shared__ int s_last;
-  const int r = m.r;
-  const int par = (iter - 1) & 1;
-  // Loads that depend on nothing are requested before the gate is looked at (one round trip instead of four in a row):
-  // the partials of <z, r>, its old value, the row pointers of the workgroup's first row block and the thread's own
-  // entries of z and delta.  The empty asm keeps the compiler from sinking them behind the early return.
-  const GateWords gw = gate_words(ctl);
-  double pv = ((int)threadIdx.x < np3) ? p3[threadIdx.x] : 0.0;
-  const double zr_old = iter > 0 ? ctl->z_r[par] : 1.0;
-  int rp_pre[4] = {0, 0, 0, 0};
-  double z_pre = 0, d_pre = 0;
-  {
-    const int al_ = m.se ? D + 1 : D;
-    const int RB_ = ((kBlock / r) / al_) * al_;
-    const int j0 = (int)blockIdx.x * RB_, lj_ = threadIdx.x / r;
-    if ((int)blockIdx.x < main_grid && j0 < A.nrows) {
-      const int j1 = min(A.nrows, j0 + RB_), j = j0 + lj_;
-      rp_pre[0] = A.rp[j0];
-      rp_pre[1] = A.rp[j1];
-      if (lj_ < RB_ && j < j1) {
-        rp_pre[2] = A.rp[j];
-        rp_pre[3] = A.rp[j + 1];
-        const size_t o = (size_t)j * r + (threadIdx.x - lj_ * r);
-        z_pre = z[o];
-        d_pre = iter > 0 ? d_old[o] : 0.0;
-      }
-    }
-  }
-  asm volatile("" ::"v"(pv), "v"(zr_old), "v"(rp_pre[0]), "v"(rp_pre[1]), "v"(rp_pre[2]), "v"(rp_pre[3]), "v"(z_pre),
-               "v"(d_pre), "s"(gw.outer), "s"(gw.tcg));
-  if (gated(gw, ctl, seq, 2)) return;
-  for (int i = threadIdx.x + blockDim.x; i < np3; i += blockDim.x) pv += p3[i];
-  const double z_r_new = block_sum(pv, s_red);
-  const double beta = iter > 0 ? tcg_beta(z_r_new, zr_old) : 0.0;
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    if (iter == 0)
-      tcg_put_dir(ctl, 0, tcg_dir_start(z_r_new), 0.0);
-    else
-      tcg_put_dir(ctl, par ^ 1, tcg_dir_next(z_r_new, beta, ctl->alpha, ctl->d_Pd[par], ctl->e_Pd[par]), ctl->e_Pe_n);
-  }
-  const double *X = pick(Xb, ctl, 0);
-  const double *Sblk = pick(Sb, ctl, 0);
-  const int al = m.se ? D + 1 : D;
-  const int RB = ((kBlock / r) / al) * al;
-  const int nrb = (A.nrows + RB - 1) / RB;
-  const int lj = threadIdx.x / r, t = threadIdx.x - lj * r;
-  auto dir = [&](size_t o) -> double { return iter > 0 ? fma(beta, d_old[o], -z[o]) : -z[o]; };
-  if ((int)blockIdx.x >= main_grid) {  // a slice of a long (Euclidean) row
-    const int li = ((int)blockIdx.x - main_grid) / kLongSplit, sl = ((int)blockIdx.x - main_grid) % kLongSplit;
-    const int j = A.long_rows[li];
-    const int rb0 = A.rp[j], re0 = A.rp[j + 1];
-    const int per = (re0 - rb0 + kLongSplit - 1) / kLongSplit;
-    const int pb = rb0 + sl * per, pe = min(re0, pb + per);
-    const int RBl = kBlock / r;
-    double acc = 0;
-    if (lj < RBl) {
-      for (int p = pb + lj; p < pe; p += 8 * RBl) {
-        int c8[8];
-        double w8[8], x8[8], y8[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          const int pp = p + q * RBl;
-          const bool ok = pp < pe;
-          c8[q] = A.ci[ok ? pp : rb0];
-          w8[q] = ok ? A.v[pp] : 0.0;
-        }
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          const size_t o = (size_t)c8[q] * r + t;
-          x8[q] = z[o];
-          y8[q] = iter > 0 ? d_old[o] : 0.0;
-        }
-#pragma unroll
-        for (int q = 0; q < 8; ++q) acc += w8[q] * fma(beta, y8[q], -x8[q]);
-      }
-    }
-    double *s_part = s_v;
-    __syncthreads();
-    s_part[threadIdx.x] = (lj < RBl) ? acc : 0.0;
-    __syncthreads();
-    if ((int)threadIdx.x < r) {
-      double y = 0;
-      for (int q = 0; q < RBl; ++q) y += s_part[q * r + threadIdx.x];
-      __hip_atomic_store(A.long_part + ((size_t)li * kLongSplit + sl) * 16 + threadIdx.x, y, __ATOMIC_RELAXED,
-                         __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __threadfence();
-    __syncthreads();
-    if (threadIdx.x == 0)
-      s_last = (__hip_atomic_fetch_add(A.long_cnt + li, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) ==
-                kLongSplit - 1);
-    __syncthreads();
-    if (!s_last) return;
-    if (threadIdx.x == 0) __hip_atomic_store(A.long_cnt + li, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (threadIdx.x < 64) {  // r <= 16: the row's r entries sit in the first wave
-      double dot = 0;
-      if ((int)threadIdx.x < r) {
-        double y = 0;
-        for (int q = 0; q < kLongSplit; ++q)
-          y += __hip_atomic_load(A.long_part + ((size_t)li * kLongSplit + q) * 16 + threadIdx.x, __ATOMIC_RELAXED,
-                                 __HIP_MEMORY_SCOPE_AGENT);
-        const size_t o = (size_t)j * r + threadIdx.x;
-        const double dn = dir(o);
-        Hd[o] = y;
-        d_new[o] = dn;
-        dot = dn * y;
-      }
-      // ONE slot per long row, written by whichever slice arrives last: a slot per slice would move the row's term
-      // around the partial array from run to run, and with it the order of the consumer's sum
-      dot = wave_sum(dot);
-      if (threadIdx.x == 0) p1[main_grid + li] = dot;
-    }
-    return;
-  }
-  const int n_rot_rows = m.se ? A.nrows : m.n * D;  // rows below this bound belong to pose items
-  double dacc = 0;
-  for (int rb = blockIdx.x; rb < nrb; rb += main_grid) {
-    const int j0 = rb * RB;
-    const int j1 = min(A.nrows, j0 + RB);
-    const int j = j0 + lj;
-    const bool active = (lj < RB) && (j < j1);
-    const bool first = rb == (int)blockIdx.x;  // requested in the prologue
-    const int pbeg = first ? rp_pre[0] : A.rp[j0], pend = first ? rp_pre[1] : A.rp[j1];
-    int myb = active ? (first ? rp_pre[2] : A.rp[j]) : 0, mye = active ? (first ? rp_pre[3] : A.rp[j + 1]) : 0;
-    const bool is_long = A.n_long > 0 && (mye - myb > kLongRow);  // served by its own workgroups
-    if (is_long) mye = myb;
-    const size_t o = (size_t)(active ? j : j0) * r + t;
-    const double own = !active ? 0.0 : !first ? dir(o) : iter > 0 ? fma(beta, d_pre, -z_pre) : -z_pre;
-    const double xo = active ? X[o] : 0.0;
-    double acc = 0;
-    for (int base = pbeg; base < pend; base += kSpmmTile) {
-      const int cnt = min(kSpmmTile, pend - base);
-      __syncthreads();
-      {
-        constexpr int SU = kSpmmTile / kBlock;
-        int ci_r[SU];
-        double v_r[SU];
-        const int last = base + cnt - 1;
-#pragma unroll
-        for (int u = 0; u < SU; ++u) {
-          const int i = min(base + (int)threadIdx.x + u * kBlock, last);
-          ci_r[u] = A.ci[i];
-          v_r[u] = A.v[i];
-        }
-#pragma unroll
-        for (int u = 0; u < SU; ++u) {
-          const int i = threadIdx.x + u * kBlock;
-          if (i < cnt) {
-            s_ci[i] = ci_r[u];
-            s_v[i] = v_r[u];
-          }
-        }
-      }
-      __syncthreads();
-      const int lo = max(myb, base) - base, hi = min(mye, base + cnt) - base;
-      for (int p = lo; p < hi; p += 8) {
-        double x8[8], y8[8], w8[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          const bool ok = p + q < hi;
-          const int pp = ok ? p + q : lo;
-          w8[q] = ok ? s_v[pp] : 0.0;
-          const size_t oc = (size_t)s_ci[pp] * r + t;
-          x8[q] = z[oc];
-          y8[q] = iter > 0 ? d_old[oc] : 0.0;
-        }
-#pragma unroll
-        for (int q = 0; q < 8; ++q) acc += w8[q] * fma(beta, y8[q], -x8[q]);
-      }
-    }
-    // ---- EucHvToHv on the block's own items ----
-    // kind: 0 rotation column `a` of pose `it`, 1 unit-sphere column, 2 Euclidean column
-    int kind = 2, a = 0, it = 0;
-    if (active && j < n_rot_rows) {
-      const int q = j / al;
-      a = j - q * al;
-      it = q;
-      kind = (a < D) ? 0 : 2;
-    } else if (active && !m.se && j < n_rot_rows + m.l) {
-      kind = 1;
-      it = j - n_rot_rows;
-    }
-    __syncthreads();
-    s_V[threadIdx.x] = own;
-    s_Y[threadIdx.x] = xo;
-    __syncthreads();
-    double T = acc;
-    const int l0 = lj - a;  // local row of the item's first column
-    if (kind == 0) {
-      double sres = 0;
-#pragma unroll
-      for (int b = 0; b < D; ++b) sres += s_V[(l0 + b) * r + t] * Sblk[(size_t)it * D * D + b + a * D];
-      T = acc - sres;
-    } else if (kind == 1) {
-      T = acc - own * Sblk[(size_t)m.n * D * D + it];
-    }
-    s_T[threadIdx.x] = T;
-    __syncthreads();
-    double hv = T;
-    if (kind == 0) {
-      // S2 = sym(Y^T T); hv = T - sum_a' Y(t, a') S2[a'][a]
-      double sres = 0;
-#pragma unroll
-      for (int b = 0; b < D; ++b) {
-        double pba = 0, pab = 0;  // P[b][a] = sum_t Y(t, b) T(t, a), P[a][b] = sum_t Y(t, a) T(t, b)
-        for (int u = 0; u < r; ++u) {
-          pba += s_Y[(l0 + b) * r + u] * s_T[(l0 + a) * r + u];
-          pab += s_Y[(l0 + a) * r + u] * s_T[(l0 + b) * r + u];
-        }
-        sres += s_Y[(l0 + b) * r + t] * (0.5 * (pba + pab));
-      }
-      hv = T - sres;
-    } else if (kind == 1) {
-      double yt = 0;
-      for (int u = 0; u < r; ++u) yt += s_Y[lj * r + u] * s_T[lj * r + u];
-      hv = T - xo * yt;
-    }
-    if (active && !is_long) {
-      Hd[o] = hv;
-      d_new[o] = own;
-      dacc += own * hv;
-    }
-  }
-  const double tot = block_sum(dacc, s_red);
-  if (threadIdx.x == 0) p1[blockIdx.x] = tot;
-}
-
-int spmm_dir_fix_grid(const ManiDesc &m, int nrows) {
-  const int al = m.se ? m.d + 1 : m.d;
-  const int RB = ((kBlock / m.r) / al) * al;
-  if (RB < al) return 0;
-  long nrb = (nrows + RB - 1) / RB;
-  if (nrb < 1) nrb = 1;
-  if (nrb > kMaxPartials) nrb = kMaxPartials;
-  return (int)nrb;
-}
-
-int launch_spmm_dir_fix(hipStream_t st, const ManiDesc &m, const CsrDev &A, Buf2 X, Buf2 Sblk, const double *z,
-                        const double *d_old, double *d_new, double *Hd, const double *p3, int np3, double *p1,
-                        SolverCtl *ctl, int seq, int iter) {
-  const int main_grid = spmm_dir_fix_grid(m, A.nrows);
-  const int grid = main_grid + A.n_long * kLongSplit;
-  if (m.d == 3)
-    hipLaunchKernelGGL(k_spmm_dir_fix<3>, dim3(grid), dim3(kBlock), 0, st, m, A, X, Sblk, z, d_old, d_new, Hd, p3, np3,
-                       p1, ctl, seq, iter, main_grid);
-  else
-    hipLaunchKernelGGL(k_spmm_dir_fix<2>, dim3(grid), dim3(kBlock), 0, st, m, A, X, Sblk, z, d_old, d_new, Hd, p3, np3,
-                       p1, ctl, seq, iter, main_grid);
-  return main_grid + A.n_long;
-}
-
-void launch_spmm_dir(hipStream_t st, int r, const CsrDev &A, const double *z, const double *d_old, double *d_new,
-                     double *W, const double *p3, int np3, SolverCtl *ctl, int seq, int iter) {
-  const int main_grid = spmm_grid(A.nrows, r);
-  const int grid = main_grid + A.n_long * kLongSplit;
-  hipLaunchKernelGGL(k_spmm_dir, dim3(grid), dim3(kBlock), 0, st, r, A, z, d_old, d_new, W, p3, np3, ctl, seq, iter,
-                     main_grid);
-}
-
-void launch_spmm(hipStream_t st, int r, const CsrDev &A, Buf2 X, int selX, const double *G, Buf2 Y, int selY,
-                 double *partials, Gate g) {
-  count_launch();
-  const int main_grid = spmm_grid(A.nrows, r);
-  const int grid = main_grid + A.n_long * kLongSplit;
-  if (partials)
-    hipLaunchKernelGGL(k_spmm<true>, dim3(grid), dim3(kBlock), 0, st, r, A, X, selX, G, Y, selY, partials, g,
-                       main_grid);
-  else
-    hipLaunchKernelGGL(k_spmm<false>, dim3(grid), dim3(kBlock), 0, st, r, A, X, selX, G, Y, selY, partials, g,
-                       main_grid);
 }
 
 // ------------------------------------------------------------------------------------------------------

@@ -7,7 +7,9 @@ kDensePrecondMaxK the preconditioner is the partitioned sparse inverse.  Every s
 device_problem.hip / fused_step.hip give it, checks that the device chose it, and only then compares the HIP path with
 the oracle: the operations at a random point, then whole RTR solves (iteration counts, exit reasons, optimum, iterate).
 Form 2 is checked a second time on the launches (DCORA_SOLVER_TCG=launch): both forms against the oracle, not only
-against each other.  Then the trust-region corners on the run form, and RBCD++ traces of the headline split."""
+against each other.  Then the trust-region corners on the run form, RBCD++ traces of the headline split, and the
+thread-per-variable (generic) solver on a block whose hub pose has long rotation rows: the two-launch Hessian product
+k_spmm_dir + k_hessfix, which no dataset of the suite reaches."""
 import os
 
 import numpy as np
@@ -22,7 +24,8 @@ TCG = {0: "three launches", 1: "two launches", 2: "one launch per run"}
 
 # (id, block, r, preconditioner, tCG form).  block: ("prefix", n) = the first n poses with their private measurements,
 # ("agent", b) = agent b of the contiguous 5-way split (bench.agent_block), ("hub", n, pose, nnz) = a prefix block with
-# measurements added from `pose` until the worst two-pose row pair of Q holds exactly `nnz` CSR entries.
+# measurements added from `pose` until the worst two-pose row pair of Q holds exactly `nnz` CSR entries, ("long", n,
+# pose, m) = a prefix block with measurements added from `pose` to m poses that were not its neighbours.
 # Form 2 (tcg_run_supported): d = 3, 4 <= r <= 6, fused_pc_preferred, grid (n + 1) / 2 <= 256, k <= 4 * 4 * 128 = 2048,
 # worst row pair <= kRunQCap = 1024.  Form 1 (fused_pc_preferred): k within one LDS chunk of the residual
 # (3200 / 2688 / 2304 columns at r = 5 / 6 / 7), r k <= 2 * 25 * 256 = 12800, r <= 7.  Dense while k <= 2200.
@@ -67,6 +70,28 @@ def worst_pair_nnz(Q, n, d=3):
     return max(int(Q.rp[min(n, p + 2) * dh] - Q.rp[p * dh]) for p in range(0, n, 2))
 
 
+def _edges_from(rng, hub, cand, count, zeros, kappa, tau):
+    """`count` measurements from `hub` to the poses popped off `cand`: random rotations, translations in +-[0.5, 1.5]
+    with the first `zeros` components exactly zero, the given precisions, weights in [0.5, 1.5]"""
+    from dcora_amd import synth
+    R = synth._rand_rot(rng, count)
+    t = rng.uniform(0.5, 1.5, (count, 3)) * rng.choice([-1.0, 1.0], (count, 3))
+    t[:, :zeros] = 0.0
+    j = [cand.pop() for _ in range(count)]
+    ids = np.array([[0, hub, 0, q] for q in j], np.int32).reshape(-1, 4)
+    vals = np.column_stack([R.transpose(0, 2, 1).reshape(count, 9), t, np.full(count, kappa), np.full(count, tau),
+                            rng.uniform(0.5, 1.5, count)])
+    return ids, vals
+
+
+def _long_edges(ids, vals, n, hub, m):
+    """measurements from `hub` to m distinct poses of the block that are not yet its neighbours"""
+    near = set(ids[ids[:, 1] == hub, 3]) | set(ids[ids[:, 3] == hub, 1]) | {hub}
+    rng = np.random.default_rng(hub + m)
+    cand = [int(j) for j in rng.permutation(n) if int(j) not in near]
+    return _edges_from(rng, hub, cand, m, 0, np.median(vals[:, 12]), np.median(vals[:, 13]))
+
+
 def _hub_edges(ds, ids, vals, n, hub, target):
     """measurements from `hub` to distinct new neighbours of the block until the row pair holding it has exactly
     `target` CSR entries.  A new neighbour adds 13 entries to the hub's rows (its 4 x 4 block of Q less the structural
@@ -74,7 +99,6 @@ def _hub_edges(ds, ids, vals, n, hub, target):
     and the first measurement leaving a pose fills the rotation-translation coupling of its diagonal block: so the
     count is measured on the built Q after every step rather than predicted."""
     import dcora_amd as da
-    from dcora_amd import synth
     p0 = hub - hub % 2
     near = set(ids[ids[:, 1] == hub, 3]) | set(ids[ids[:, 3] == hub, 1]) | set(range(p0, min(n, p0 + 2)))
     rng = np.random.default_rng(hub + target)
@@ -88,13 +112,8 @@ def _hub_edges(ds, ids, vals, n, hub, target):
 
     def add(count, zeros):
         nonlocal new_ids, new_vals
-        R = synth._rand_rot(rng, count)
-        t = rng.uniform(0.5, 1.5, (count, 3)) * rng.choice([-1.0, 1.0], (count, 3))
-        t[:, :zeros] = 0.0
-        j = [cand.pop() for _ in range(count)]
-        new_ids = np.r_[new_ids, np.array([[0, hub, 0, q] for q in j], np.int32).reshape(-1, 4)]
-        new_vals = np.r_[new_vals, np.column_stack([R.transpose(0, 2, 1).reshape(count, 9), t, np.full(count, kappa),
-                                                    np.full(count, tau), rng.uniform(0.5, 1.5, count)])]
+        hi, hv = _edges_from(rng, hub, cand, count, zeros, kappa, tau)
+        new_ids, new_vals = np.r_[new_ids, hi], np.r_[new_vals, hv]
 
     add(1, 0)
     rem = target - held()
@@ -130,8 +149,9 @@ def case(block, r):
         n = block[1]
         keep = (ds.ids[:, 1] < n) & (ds.ids[:, 3] < n)
         ids, vals, idso, valso = ds.ids[keep], ds.vals[keep], dso.ids[keep], dso.vals[keep]
-        if block[0] == "hub":
-            hi, hv = _hub_edges(ds, ids, vals, n, block[2], block[3])
+        if block[0] in ("hub", "long"):
+            hi, hv = (_hub_edges(ds, ids, vals, n, block[2], block[3]) if block[0] == "hub" else
+                      _long_edges(ids, vals, n, block[2], block[3]))
             ids, vals = np.r_[ids, hi], np.r_[vals, hv]
             idso, valso = np.r_[idso, hi], np.r_[valso, hv]
         Q = da.build_Q_pgo(ds, n=n, ids=ids, vals=vals)
@@ -150,14 +170,18 @@ def case(block, r):
     return _CASES[key]
 
 
-def make_problem(da, r, n, Q, G, form):
-    """the device problem; form "launch" keeps the run form off (the choice is read when the problem is created)"""
+def make_problem(da, r, n, Q, G, form, solver=None):
+    """the device problem; form "launch" keeps the run form off and solver "generic" the fused pose-graph kernels (both
+    choices are read when the problem is created)"""
     if form:
         os.environ["DCORA_SOLVER_TCG"] = form
+    if solver:
+        os.environ["DCORA_SOLVER"] = solver
     try:
         return da.QuadraticProblem(r, 3, n, Q, G=G, reg=0.1)
     finally:
         os.environ.pop("DCORA_SOLVER_TCG", None)
+        os.environ.pop("DCORA_SOLVER", None)
 
 
 PARAMS = [dict(), dict(RTR_iterations=4, RTR_tCG_iterations=3),
@@ -211,6 +235,57 @@ def test_dense_form_matches_oracle(env, sid, block, r, precond, form):
             assert P.solver_info()["tcg"] == want, (sid, variant)   # (the run form did not give up)
         finally:
             P.close()
+
+
+# (id, new neighbours of pose 150 in the 300-pose prefix, r, DCORA_SOLVER).  The rotation rows 600 .. 602 of the hub
+# hold 578 (m = 140) and 1098 (m = 270) entries, more than kLongRow = 512, and are no Euclidean columns: the generic
+# solver's Hessian product is k_spmm_dir + k_hessfix (hess_one_launch() is false), every Q-apply takes k_spmm's slices.
+# A slice (row / kLongSplit = 8) is 73 entries against a stride of 8 * (256 / 5) = 408 at r = 5, one masked trip, and
+# 138 against 8 * 16 = 128 at r = 16, two trips; the hub's row block holds 2735 and 3795 entries, two and three tiles
+# of kSpmmTile = 1536.
+LONG_ROWS = [
+    ("long150_r5", 140, 5, "generic"),   # r <= 8: the fused pose-graph kernels are switched off
+    ("long150_r16", 270, 16, None),      # r > 8 is generic by itself
+]
+
+
+@pytest.mark.parametrize("sid,m,r,solver", LONG_ROWS, ids=[s[0] for s in LONG_ROWS])
+def test_generic_solver_long_rotation_rows_match_oracle(env, sid, m, r, solver):
+    """long rows that are not Euclidean columns: the two-launch Hessian product of the generic tCG is the one in use;
+    f, RieGrad, HessVec, PreCondition and RTR solves from a random and a warm start against the oracle (from the warm
+    start the tCG runs go 4 to 8 iterations deep, and with 3 tCG iterations every run ends on the iteration limit),
+    and the same solve twice bit for bit: the order in which the slices of a row arrive must not show"""
+    da, _ = env
+    from dcora_amd import capi
+    n, Q, Po, G, X, V, Xw = case(("long", 300, 150, m), r)
+    nnz = np.diff(Q.rp)
+    assert max(nnz) > 512 and any(j % 4 != 3 for j in np.flatnonzero(nnz > 512)), sid
+    P = make_problem(da, r, n, Q, G, None, solver)
+    try:
+        # (solver_info() looks at the preconditioner form alone and says "two launches" under DCORA_SOLVER=generic)
+        assert P.qapply_info()["kernel"] == "k_spmm", (sid, P.qapply_info())
+        assert solver or P.solver_info()["tcg"] == TCG[0], (sid, P.solver_info())
+        with pytest.raises(capi.DcoraError):   # the one-launch product does not apply: k_spmm_dir + k_hessfix it is
+            P.HessVecSolverForm(X, V)
+        fo = Po.f(X)
+        assert abs(P.f(X) - fo) <= 1e-12 * abs(fo), sid
+        assert common.rel(P.RieGrad(X), Po.rgrad(X)) < 1e-12, sid
+        assert common.rel(P.HessVec(X, V), Po.hess(X, V)) < 1e-12, sid
+        assert common.rel(P.PreCondition(X, V), Po.precondition(X, V)) < 1e-9, sid
+        for i, kw in enumerate(PARAMS):
+            compare_solve(da, P, Po, X, kw, i < 2, (sid, "cold"))
+        for kw in PARAMS[:2]:
+            compare_solve(da, P, Po, Xw, kw, True, (sid, "warm"))
+        runs = []
+        for _ in range(2):
+            opt = da.QuadraticOptimizer(P, da.ROptParameters(**PARAMS[0]))
+            Xr = opt.optimize(Xw)
+            res = opt.getOptResult()
+            res.pop("elapsedMs")
+            runs.append((Xr, res))
+        assert np.array_equal(runs[0][0], runs[1][0]) and runs[0][1] == runs[1][1], (sid, runs[0][1], runs[1][1])
+    finally:
+        P.close()
 
 
 def test_trust_region_corners_on_the_run_form(env):
