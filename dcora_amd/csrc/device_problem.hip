@@ -834,7 +834,7 @@ bool DeviceProblem::use_pc() const {
 }
 
 // What an RTR solve enqueues in each tCG form; DeviceProblem::rtr_dev paces it.  The forms:
-//   generic: the thread-per-variable kernels of kernels.hip and spmm_csr.hip, any layout -- per tCG iteration the
+//   generic: the thread-per-variable kernels of manifold.hip, kernels.hip and spmm_csr.hip, any layout -- per tCG iteration the
 //            Hessian SpMM with the direction update folded in (k_spmm_dir [+ k_hessfix], or k_spmm_dir_fix),
 //            k_tcg_update1, the preconditioner, k_tangent;
 //   split:   the fused kernels of fused_step.hip (SE layout, r <= 8) -- per tCG iteration A (direction update +

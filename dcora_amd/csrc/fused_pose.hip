@@ -102,7 +102,7 @@ __global__ __launch_bounds__(kBlock) void k_g_retract(ManiDesc m, Buf2 Xb, const
   }
 }
 
-// RBCD++ Nesterov bookkeeping (modes as k_nesterov in kernels.hip)
+// RBCD++ Nesterov bookkeeping (modes as k_nesterov in manifold.hip)
 struct GNesterovArgs {
   int mode, restart, skip_lo, skip_hi;
   double alpha, gamma;

@@ -22,12 +22,26 @@ constexpr int kBsrMaxGrid = 4096;   // workgroups (= partial slots) of the block
 constexpr int kBlock = 256;
 constexpr int kSpmmTile = 1536;  // nnz k_spmm stages per pass: 18 KiB of LDS
 
+// One factor of the product manifold: a Stiefel block of d columns, a unit-sphere column or a Euclidean column
+enum class Factor : int { Stiefel, Sphere, Euclid };
+struct ManiItem {
+  Factor kind;
+  int col;  // its first column
+  int idx;  // its index among the factors of its kind
+};
 struct ManiDesc {
   int r, d, n, l, b, k, se;
   __host__ __device__ int rot_col(int i) const { return se ? i * (d + 1) : i * d; }
   __host__ __device__ int sphere_col(int i) const { return d * n + i; }
   __host__ __device__ int num_euc() const { return se ? n : n + b; }
   __host__ __device__ int euc_col(int e) const { return se ? e * (d + 1) + d : d * n + l + e; }
+  // the factors in the order the thread-per-variable kernels (manifold.hip) walk them: Stiefel, spheres, Euclidean
+  __host__ __device__ long num_items() const { return (long)n + l + num_euc(); }
+  __host__ __device__ __forceinline__ ManiItem item(long it) const {
+    if (it < n) return {Factor::Stiefel, rot_col((int)it), (int)it};
+    if (it < n + l) return {Factor::Sphere, sphere_col((int)(it - n)), (int)(it - n)};
+    return {Factor::Euclid, euc_col((int)(it - n - l)), (int)(it - n - l)};
+  }
 };
 // layout: 0 = SE ordering when l = b = 0 (DCORA_LAYOUT_AUTO), 1 = SE, 2 = RA whatever l and b are (a range-aided
 // graph without ranges or landmarks keeps the RA ordering: ref src/Graph.cpp:68-75)
@@ -153,7 +167,7 @@ int spmm_bsr_grid(int nbrows);
 void launch_spmm_bsr(hipStream_t st, int r, int d, const BsrDev &A, Buf2 X, int selX, const double *G, Buf2 Y,
                      int selY, double *partials, Gate g);
 
-// ---- per-pose kernels -------------------------------------------------------------------------------
+// ---- thread-per-variable manifold kernels (manifold.hip; their items: ManiDesc::num_items / item) ----
 int pose_grid(const ManiDesc &m);
 // RG = Proj_X(EG); Sblk_i = sym(Y_i^T EG_i) (spheres: y^T eg); partial |RG|^2 (1 per block)
 void launch_rgrad(hipStream_t st, const ManiDesc &m, Buf2 X, Buf2 EG, Buf2 RG, Buf2 Sblk, int sel,
@@ -186,7 +200,7 @@ void launch_retract(hipStream_t st, const ManiDesc &m, Buf2 X, const double *V, 
 void launch_polar(hipStream_t st, const ManiDesc &m, double c0, const double *A, double c1, const double *B,
                   double c2, const double *C, double *out);
 
-// RBCD++ Nesterov bookkeeping on a pose range (modes: see kernels.hip k_nesterov)
+// RBCD++ Nesterov bookkeeping on a pose range (modes: see manifold.hip k_nesterov)
 void launch_nesterov(hipStream_t st, const ManiDesc &m, int mode, int restart, int skip_lo, int skip_hi, double alpha,
                      double gamma, double *X, double *V, double *Y, double *XPrev, double *Yloc,
                      const double *Xloc);

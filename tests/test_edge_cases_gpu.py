@@ -121,7 +121,8 @@ def test_operators_at_the_widest_rank_on_a_real_graph(env):
 def test_range_aided_layout_in_its_four_presence_cases(env, d, l, b):
     """ref src/manifold/LiftedManifold.cpp:67-88: the product manifold St(r,d)^n x OB(r,l) x R^(r x n) x R^(r x b) is
     built in four ways, with and without unit-sphere variables and landmarks.  A random sparse positive semidefinite Q
-    of the layout's size stands in for the data matrix: every operator against the oracle, at r = d and r = d + 3"""
+    of the layout's size stands in for the data matrix: every operator against the oracle, at r = d, r = d + 3 and
+    r = 9 (the widest register block, RM = 16, of the thread-per-variable kernels: single columns beside it)"""
     import scipy.sparse as sp
     da, orc = env
     n = 12
@@ -130,7 +131,7 @@ def test_range_aided_layout_in_its_four_presence_cases(env, d, l, b):
     A = sp.random(3 * k, k, density=4.0 / k, random_state=np.random.RandomState(d + l + b), format="csr")
     Q = sp.csr_matrix(A.T @ A + 1e-3 * sp.identity(k))
     Q.sort_indices()
-    for r in (d, d + 3):
+    for r in (d, d + 3, 9):
         X = orc.project_to_manifold(r, d, n, rng.standard_normal((r, k)), l=l, b=b)
         V = rng.standard_normal((r, k))
         P = da.QuadraticProblem(r, d, n, da.Csr.from_scipy(Q), reg=0.05, l=l, b=b)

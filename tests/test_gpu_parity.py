@@ -159,6 +159,36 @@ def test_rbcd_matches_oracle(env):
     assert common.rel(s.get_X(), tr["X"]) < 1e-6
 
 
+def test_rbcd_matches_oracle_on_the_generic_kernels(env):
+    """the same loop on the thread-per-variable kernels (DCORA_SOLVER=generic, read at every call of the session):
+    k_nesterov in its four modes, across the two restarts"""
+    import os
+    da, orc = env
+    ds, dso = common.product_dataset("smallGrid3D"), common.oracle_dataset("smallGrid3D")
+    r = 5
+    X0 = common.random_point(r, ds.d, ds.n, 1, orc.project_to_manifold)
+    iters = 70  # crosses two restarts (interval 30)
+    tr = orc.run_rbcd(dso, X0, num_robots=5, r_min=r, max_iters=iters, staircase=0, rgrad_tol=1e-12)
+    before = os.environ.get("DCORA_SOLVER")
+    os.environ["DCORA_SOLVER"] = "generic"
+    try:
+        s = da.RbcdSession(ds, num_robots=5, r=r)
+        s.set_X(X0)
+        out = s.run(max_iters=iters, rgrad_tol=1e-12)
+        X = s.get_X()
+        s.close()
+    finally:
+        if before is None:
+            os.environ.pop("DCORA_SOLVER", None)
+        else:
+            os.environ["DCORA_SOLVER"] = before
+    assert out["iters"] == iters
+    assert np.array_equal(out["selected"], tr["selected"])
+    assert np.allclose(out["cost"], tr["cost"], rtol=1e-7)
+    assert np.allclose(out["gradnorm"], tr["gradnorm"], rtol=1e-5, atol=1e-8)
+    assert common.rel(X, tr["X"]) < 1e-6
+
+
 def test_certification(env):
     da, orc = env
     ds, dso = common.product_dataset("smallGrid3D"), common.oracle_dataset("smallGrid3D")
