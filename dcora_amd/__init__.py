@@ -1093,65 +1093,72 @@ def max_translation_distance(X, Y, d):
     return out.value
 
 
+def _team_fn(self, name):
+    """the team entry of a session (dcora_rbcd_<name>) or of a job's exchange (dcora_exchange_<name>)"""
+    return getattr(capi.lib(), ("dcora_exchange_" if isinstance(self, Exchange) else "dcora_rbcd_") + name)
+
+
 def _enable_team(self, params=None, **kw):
-    """opt in to the team protocol (dcora_rbcd_team_enable): every iterate(true) of an agent stores its status"""
+    """opt in to the team protocol (dcora_rbcd_team_enable; on an Exchange dcora_exchange_team_enable, SPMD): every
+    iterate(true) of an agent stores its status -- across the ranks of a job, on every rank"""
     self.team = params if params is not None else team_params(**kw)
-    check(capi.lib().dcora_rbcd_team_enable(self.h, C.byref(self.team)))
+    check(_team_fn(self, "team_enable")(self.h, C.byref(self.team)))
     return self.team
 
 
 def _agent_status(self, agent):
     """the agent's AgentStatus as a dict, or None when it has not optimised since the statuses were last cleared"""
     st, known = capi.AgentStatus(), C.c_int()
-    check(capi.lib().dcora_rbcd_agent_status(self.h, agent, C.byref(st), C.byref(known)))
+    check(_team_fn(self, "agent_status")(self.h, agent, C.byref(st), C.byref(known)))
     return st.as_dict() if known.value else None
 
 
 def _loop_closure_stats(self, agent):
     c = np.zeros(3, np.int32)
-    check(capi.lib().dcora_rbcd_loop_closure_stats(self.h, agent, c))
+    check(_team_fn(self, "loop_closure_stats")(self.h, agent, c))
     return {"accepted": int(c[0]), "rejected": int(c[1]), "total": int(c[2])}
 
 
 def _should_terminate(self):
     yes = C.c_int()
-    check(capi.lib().dcora_rbcd_should_terminate(self.h, C.byref(yes)))
+    check(_team_fn(self, "should_terminate")(self.h, C.byref(yes)))
     return bool(yes.value)
 
 
 def _should_update_weights(self):
     yes = C.c_int()
-    check(capi.lib().dcora_rbcd_should_update_weights(self.h, C.byref(yes)))
+    check(_team_fn(self, "should_update_weights")(self.h, C.byref(yes)))
     return bool(yes.value)
 
 
 def _team_info(self):
     c = np.zeros(4, np.int32)
-    check(capi.lib().dcora_rbcd_team_info(self.h, c))
+    check(_team_fn(self, "team_info")(self.h, c))
     return {"inner_iter": int(c[0]), "latest_weight_update_iteration": int(c[1]), "weight_updates": int(c[2]),
             "resets": int(c[3])}
 
 
 def _run_team(self):
-    """the agents' own loop (dcora_rbcd_run_team): until should_terminate(), each pass re-weights when
-    should_update_weights() says so, then iterates the greedily selected agent"""
+    """the agents' own loop (dcora_rbcd_run_team / dcora_exchange_run_team): until should_terminate(), each pass
+    re-weights when should_update_weights() says so, then iterates the greedily selected agent"""
     n = max(int(self.team.max_num_iters), 1)
     it, nupd, why = C.c_int(), C.c_int(), C.c_int()
     cost, gn = np.zeros(n), np.zeros(n)
     sel, upd = np.zeros(n, np.int32), np.zeros(n, np.int32)
-    check(capi.lib().dcora_rbcd_run_team(self.h, C.byref(it), cost.ctypes.data_as(C.c_void_p),
-                                         gn.ctypes.data_as(C.c_void_p), sel.ctypes.data_as(C.c_void_p),
-                                         upd.ctypes.data_as(C.c_void_p), C.byref(nupd), C.byref(why)))
+    check(_team_fn(self, "run_team")(self.h, C.byref(it), cost.ctypes.data_as(C.c_void_p),
+                                     gn.ctypes.data_as(C.c_void_p), sel.ctypes.data_as(C.c_void_p),
+                                     upd.ctypes.data_as(C.c_void_p), C.byref(nupd), C.byref(why)))
     k = it.value
     return dict(iters=k, cost=cost[:k], gradnorm=gn[:k], selected=sel[:k], updated=upd[:k],
                 weight_updates=nupd.value,
                 stop_reason={capi.TEAM_STOP_ALL_READY: "all_ready", capi.TEAM_STOP_MAX_ITERS: "max_iters"}[why.value])
 
 
-RbcdSession.enable_team = _enable_team
-RbcdSession.agent_status = _agent_status
-RbcdSession.loop_closure_stats = _loop_closure_stats
-RbcdSession.should_terminate = _should_terminate
-RbcdSession.should_update_weights = _should_update_weights
-RbcdSession.team_info = _team_info
-RbcdSession.run_team = _run_team
+for _cls in (RbcdSession, Exchange):  # the same records from a session and from the exchange of a multi-rank job
+    _cls.enable_team = _enable_team
+    _cls.agent_status = _agent_status
+    _cls.loop_closure_stats = _loop_closure_stats
+    _cls.should_terminate = _should_terminate
+    _cls.should_update_weights = _should_update_weights
+    _cls.team_info = _team_info
+    _cls.run_team = _run_team

@@ -217,6 +217,14 @@ SIGNATURES = {
     "dcora_exchange_certify": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_double, _PI, _PD, _PD, _dp,
                                          C.POINTER(C.c_longlong), _PI]),
     "dcora_exchange_host_selftest": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, _PD]),
+    "dcora_exchange_host_selftest_team": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _PD]),
+    "dcora_exchange_team_enable": (C.c_int, [_vp, C.POINTER(TeamParams)]),
+    "dcora_exchange_agent_status": (C.c_int, [_vp, C.c_int, C.POINTER(AgentStatus), _PI]),
+    "dcora_exchange_loop_closure_stats": (C.c_int, [_vp, C.c_int, _ip]),
+    "dcora_exchange_should_terminate": (C.c_int, [_vp, _PI]),
+    "dcora_exchange_should_update_weights": (C.c_int, [_vp, _PI]),
+    "dcora_exchange_team_info": (C.c_int, [_vp, _ip]),
+    "dcora_exchange_run_team": (C.c_int, [_vp, _PI, _vp, _vp, _vp, _vp, _PI, _PI]),
     "dcora_debug_exchange_leave_stale": (C.c_int, [C.c_char_p, C.c_int, C.c_int]),
     "dcora_debug_exchange_probe_fault": (C.c_int, [C.c_int]),
     "dcora_cert_prepare": (C.c_int, [C.POINTER(Dims), _ip, _ip, C.c_int, C.c_int]),

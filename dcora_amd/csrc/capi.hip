@@ -1503,6 +1503,74 @@ int dcora_exchange_get_weights(dcora_exchange_t ex, double *w) {
     return rc ? rc : ex->e.get_weights(w);
   });
 }
+// ---- the team protocol across the ranks (Exchange::team_enable) ----
+namespace {
+int team_exchange(dcora_exchange_t ex) {
+  return ex->e.team_on() ? (int)DCORA_OK : bad("exchange team: the exchange has not called dcora_exchange_team_enable");
+}
+}  // namespace
+int dcora_exchange_team_enable(dcora_exchange_t ex, const dcora_team_params *params) {
+  return abi_call({ex, params}, [&] { return ex->e.team_enable(*params); });
+}
+int dcora_exchange_agent_status(dcora_exchange_t ex, int agent, dcora_agent_status *status, int *known) {
+  return abi_call({ex, status}, [&] {
+    const int rc = team_exchange(ex);
+    if (rc) return rc;
+    RbcdSession &s = *ex->e.team_session();
+    if (agent < 0 || agent >= s.R) return bad("bad agent");
+    return s.team_agent_status(agent, status, known);
+  });
+}
+int dcora_exchange_loop_closure_stats(dcora_exchange_t ex, int agent, int counts[3]) {
+  return abi_call({ex, counts}, [&] {
+    const int rc = team_exchange(ex);
+    if (rc) return rc;
+    const RbcdSession &s = *ex->e.team_session();
+    if (agent < 0 || agent >= s.R) return bad("bad agent");
+    for (int c = 0; c < 3; ++c) counts[c] = s.team->lc[(size_t)agent * 3 + c];
+    return (int)DCORA_OK;
+  });
+}
+int dcora_exchange_should_terminate(dcora_exchange_t ex, int *yes) {
+  return abi_call({ex, yes}, [&] {
+    const int rc = team_exchange(ex);
+    return rc ? rc : ex->e.team_session()->team_decide(yes, nullptr);
+  });
+}
+int dcora_exchange_should_update_weights(dcora_exchange_t ex, int *yes) {
+  return abi_call({ex, yes}, [&] {
+    const int rc = team_exchange(ex);
+    return rc ? rc : ex->e.team_session()->team_decide(nullptr, yes);
+  });
+}
+int dcora_exchange_team_info(dcora_exchange_t ex, int info[4]) {
+  return abi_call({ex, info}, [&] {
+    const int rc = team_exchange(ex);
+    if (rc) return rc;
+    const RbcdSession &s = *ex->e.team_session();
+    info[0] = s.team_inner_iter();
+    info[1] = s.team->latest_weight_update_iteration;
+    info[2] = s.team_weight_updates();
+    info[3] = s.team->resets_done;
+    return (int)DCORA_OK;
+  });
+}
+int dcora_exchange_run_team(dcora_exchange_t ex, int *iters_done, double *cost2_trace, double *gradnorm_trace,
+                            int *selected_trace, int *updated_trace, int *weight_updates, int *stop_reason) {
+  return abi_call({ex}, [&] {
+    const int rc = team_exchange(ex);
+    return rc ? rc
+              : ex->e.run_team(iters_done, cost2_trace, gradnorm_trace, selected_trace, updated_trace, weight_updates,
+                               stop_reason);
+  });
+}
+int dcora_exchange_host_selftest_team(const char *job_name, int rank, int world_size, int num_agents, int rounds,
+                                      int skew_us, double *checksum) {
+  return abi_call({job_name}, [&] {
+    Exchange e;
+    return e.host_selftest_team(job_name, rank, world_size, num_agents, rounds, skew_us, checksum);
+  });
+}
 
 // ---- RBCD session, range-aided SLAM ----------------------------------------------------------------------------
 struct dcora_ra_rbcd_s {

@@ -25,10 +25,7 @@ constexpr int kMaxRanks = 64;
 constexpr uint32_t kShmMagic = 0x44434f52u;  // "DCOR"
 constexpr int kProbeDoubles = 512;           // the link check's payload: 4 KB
 
-struct alignas(64) ShmFlag {
-  volatile uint64_t seq;
-  uint64_t pad[7];
-};
+// (ShmFlag, ShmStatus: team_slots.h)
 struct alignas(64) ShmEval {
   volatile double g2, xeg;  // |Proj(X_b Q_bb + G_b)|^2, <X_b, X_b Q_bb + G_b>
   volatile uint64_t seq;
@@ -94,6 +91,28 @@ class Exchange {
   int set_weights(RbcdSession &s, const double *w);  // all m weights, the same on every rank
   int get_weights(double *w);                        // all m weights of the job, from the weights area
   int publish_weights(const RbcdSession &s);         // the owned edges' current weights into the area (creation)
+  // ---- the team protocol across the ranks (dcora_exchange_team_enable; pose-graph sessions) ----
+  // Every rank keeps every agent's status (TeamState, ranked).  Of an optimisation only two facts are not known
+  // everywhere: whether it succeeded and its relative change.  The hosting rank stores the first from the host, the
+  // ranked k_rel_change behind the agent's update stores the second and then the slot's sequence word; every rank
+  // (the hosting one too) collects them inside the collective call and settles the status by the same rule.
+  // Slot re-use.  Optimisation q of agent a goes into slot [q & 1][a], last used by q - 2.  Before the hosting rank
+  // touches it, it waits (bounded) until every rank's status_read_[rank][a] has reached q - 2: that one wait closes the
+  // hazard for ticks, which have no evaluation behind them and whose posts are scattered before the status is read.
+  // Greedy iterations would not need it -- nobody leaves evaluation k before everybody has entered it, and a rank
+  // says it has entered only after it has read status k, so even one slot per agent would do there; the word is then
+  // always there already and the wait costs one load per rank.  (rbcd_iterate reads the status inside evaluate, after
+  // the evaluation's kernels are enqueued and before its heartbeat: read before them, the hosting rank's host waited
+  // for its own update and its queue ran dry -- 18 us per iteration instead of the launch's 6.)
+  int team_enable(const dcora_team_params &p);
+  bool team_on() const { return pose_ && pose_->team && pose_->team->ranked; }
+  RbcdSession *team_session() const { return team_on() ? pose_ : nullptr; }
+  int run_team(int *iters_done, double *cost2_trace, double *gradnorm_trace, int *selected_trace, int *updated_trace,
+               int *weight_updates, int *stop_reason);
+  // the same slots and waits without a device (host stores stand in for the kernel's): rounds of one agent (round % R)
+  // behind an evaluation heartbeat, every third round a tick of non-adjacent agents without one; every rank collects,
+  // settles and decides by team_rules.h; checksum folds every status and both decisions of every round
+  int host_selftest_team(const char *job_name, int rank, int world, int R, int rounds, int skew_us, double *checksum);
   int barrier(double timeout_s = 120.0);
   int gather_X(double *Xh);
   // Agent::setX of every agent on every rank: sequence numbers restart with the Nesterov sequences
@@ -135,6 +154,17 @@ class Exchange {
   size_t off_red_ = 0;
   uint64_t red_seq_ = 0;
   ShmFlag *consumed_ = nullptr;  // [consumer rank][agent]: the last post of the agent that rank has scattered
+  ShmStatus *status_ = nullptr;      // [parity][agent]: the team's status area
+  ShmFlag *status_read_ = nullptr;   // [reader rank][agent]: the last optimisation of the agent whose status it has read
+  size_t off_status_ = 0, off_status_read_ = 0;
+  RbcdSession *pose_ = nullptr;      // the session when it is a pose-graph one (the team protocol serves those)
+  std::vector<double> job_w_;        // the job's weights as of the last weight change (the team's loop-closure counts)
+  std::vector<int> team_due_;        // agents whose status the evaluation of this rbcd_iterate has to collect
+  int team_clear_to_write(const int *agents, int count);  // before the agents optimise: their slots may be overwritten
+  int team_collect(const int *agents, int count);         // after their posts: every rank reads and settles
+  TeamSlots team_slots() const;
+  int team_wait_failed(int what, const std::string &who);  // a kTeamWait* result as this exchange's failure
+  void team_snapshot_weights();
   size_t off_flags_ = 0, off_evals_ = 0, off_staged_ = 0, off_x_ = 0, off_consumed_ = 0;
   size_t off_probe_flags_ = 0, off_probe_res_ = 0, off_probe_stage_ = 0;  // link check: [reader][writer] words / 4 KB
   size_t probe_off_ = 0;  // in a halo buffer: [writer] x (kProbeDoubles payload + 8 doubles of flag)

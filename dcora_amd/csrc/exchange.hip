@@ -201,19 +201,6 @@ bool creator_alive(const ShmHeader *h) {
   return now == 0 || h->creator_start == 0 || now == h->creator_start;  // (no /proc: the pid test alone)
 }
 
-// host polling with back-off: a burst of pause instructions, then the core is handed over between polls (a rank per
-// core is not guaranteed: the four-ranks-on-one-GPU rehearsal runs on whatever cores the container has)
-inline void polite_spin(unsigned &spins) {
-  ++spins;
-  if (spins < 2048u) {
-    __builtin_ia32_pause();
-  } else if (spins < 8192u) {
-    sched_yield();
-  } else {
-    usleep(50);
-  }
-}
-
 }  // namespace
 
 double exchange_timeout_s() { return env::exchange_timeout_s(); }
@@ -239,6 +226,10 @@ int Exchange::num_peers() const {
 
 Exchange::~Exchange() {
   if (s_) (void)hipSetDevice(s_->opt.device);
+  if (team_on()) {  // the team's status area and weights go with the segment: the session goes on without a team
+    (void)hipStreamSynchronize(s_->st);
+    pose_->team.reset();
+  }
   for (int q = 0; q < kMaxRanks; ++q)
     if (opened_[q] && peer_halo_[q]) (void)hipIpcCloseMemHandle(peer_halo_[q]);
   if (registered_ && map_) (void)hipHostUnregister(map_);
@@ -347,8 +338,8 @@ int Exchange::open_segment(const char *job_name, size_t bytes) {
   }
 }
 
-// shared segment: header | per-rank records | flags [2][R] | evaluation slots [2][R] | staged poses [2][R][slot] | X |
-// weights
+// shared segment: header | per-rank records | flags [2][R] | evaluation slots [2][R] | ... | statuses [2][R] and their
+// read words [world][R] | staged poses [2][R][slot] | X | weights
 int Exchange::map_segment(const char *job_name, size_t x_doubles, size_t w_doubles) {
   const int R = R_;
   size_t off = align_up(sizeof(ShmHeader), 64);
@@ -362,6 +353,10 @@ int Exchange::map_segment(const char *job_name, size_t x_doubles, size_t w_doubl
   off += sizeof(ShmFlag) * (size_t)world * R;
   off_red_ = off;
   off += sizeof(ShmRed) * 2 * (size_t)world;
+  off_status_ = off;  // the team's status area [2][R] and what every rank has read of it [world][R]
+  off += sizeof(ShmStatus) * 2 * R;
+  off_status_read_ = off;
+  off += sizeof(ShmFlag) * (size_t)world * R;
   off_probe_flags_ = off;  // link check: [reader][writer] flag words, then result words
   off += sizeof(ShmFlag) * (size_t)world * world;
   off_probe_res_ = off;
@@ -387,6 +382,8 @@ int Exchange::map_segment(const char *job_name, size_t x_doubles, size_t w_doubl
   evals_ = (ShmEval *)((char *)map_ + off_evals_);
   consumed_ = (ShmFlag *)((char *)map_ + off_consumed_);
   red_ = (ShmRed *)((char *)map_ + off_red_);
+  status_ = (ShmStatus *)((char *)map_ + off_status_);
+  status_read_ = (ShmFlag *)((char *)map_ + off_status_read_);
   staged_ = (double *)((char *)map_ + off_staged_);
   xarea_ = (double *)((char *)map_ + off_x_);
   return DCORA_OK;
@@ -415,6 +412,7 @@ int Exchange::barrier(double timeout_s) {
 
 int Exchange::init(SessionCore *s, const char *job_name, size_t weights) {
   s_ = s;
+  pose_ = dynamic_cast<RbcdSession *>(s);
   rank = s->opt.rank;
   world = s->opt.world_size;
   R_ = s->R;
@@ -888,6 +886,14 @@ int Exchange::evaluate(double *cost2, double *gradnorm, double *block_norms, int
     hipLaunchKernelGGL(k_eval_publish, dim3(1), dim3(64), 0, s_->st, n_hosted_, hosted_list_.p, evalbuf_.p, slots_dev,
                        want);
   DCORA_HIP(hipGetLastError());
+  // the team's statuses of the round (rbcd_iterate): read once the evaluation is enqueued behind the agent's update, so
+  // that the hosting rank's queue never drains while its host waits for its own kernel's word
+  if (!team_due_.empty()) {
+    const std::vector<int> due(std::move(team_due_));
+    team_due_.clear();
+    rc = team_collect(due.data(), (int)due.size());
+    if (rc) return rc;
+  }
   const auto t0 = Clock::now();
   ShmEval *sl = evals_ + (size_t)parity * per_parity;
   // Heartbeat of this rank: every rank -- also one that hosts no agent and therefore publishes nothing -- says that
@@ -943,31 +949,156 @@ int Exchange::rbcd_iterate(int selected, double *cost2, double *gradnorm, double
   std::vector<int> others;
   for (int a = 0; a < R; ++a)
     if (a != selected) others.push_back(a);
+  const bool team = team_on();
+  const long launches0 = g_chain_launches.load(std::memory_order_relaxed);
   int rc = s_->phase_nonselected(selected);  // Agent::iterate(false) of the hosted non-selected agents
   if (rc) return rc;
   rc = post(others.data(), (int)others.size());
   if (rc) return rc;
   rc = wait(others.data(), (int)others.size());  // the selected agent's pull (and everybody's for the evaluation)
   if (rc) return rc;
+  if (team && (rc = team_clear_to_write(&selected, 1))) return rc;
   rc = s_->phase_selected(selected);  // Agent::iterate(true) where the selected agent lives
   if (rc) return rc;
+  if (team) pose_->team_note_elsewhere(&selected, 1);
   rc = post(&selected, 1);
   if (rc) return rc;
   rc = wait(&selected, 1);
   if (rc) return rc;
+  if (team) team_due_.assign(1, selected);  // collected inside evaluate, before its waits
   int nxt = selected;
   rc = evaluate(cost2, gradnorm, block_norms, &nxt);
+  team_due_.clear();
+  if (pose_) pose_->chain_launches += g_chain_launches.load(std::memory_order_relaxed) - launches0;
   if (rc) return rc;
   if (next_selected) *next_selected = s_->agent_core(selected).neighbors.empty() ? selected : nxt;
   return DCORA_OK;
 }
 
 int Exchange::rbcd_tick(const int *set, int count, int allow_adjacent) {
-  int rc = s_->iterate_set(set, count, allow_adjacent);
+  const bool team = team_on();
+  int rc = DCORA_OK;
+  // (a set the session is about to refuse touches no slot)
+  bool valid = set && count >= 1 && count <= R_;
+  for (int i = 0; valid && i < count; ++i) valid = set[i] >= 0 && set[i] < R_;
+  if (team && valid && (rc = team_clear_to_write(set, count))) return rc;
+  rc = s_->iterate_set(set, count, allow_adjacent);
   if (rc) return rc;
+  if (team) pose_->team_note_elsewhere(set, count);
   rc = post(set, count);
   if (rc) return rc;
-  return wait(set, count);
+  rc = wait(set, count);
+  if (rc || !team) return rc;
+  return team_collect(set, count);
+}
+
+// ---- the team protocol across the ranks (exchange.h) ----------------------------------------------------------------
+void Exchange::team_snapshot_weights() {
+  if (!w_doubles_) return;
+  std::atomic_thread_fence(std::memory_order_acquire);
+  job_w_.resize(w_doubles_);
+  std::memcpy(job_w_.data(), (const char *)map_ + off_w_, sizeof(double) * w_doubles_);
+}
+
+// The job's weights are complete in the area whenever no update is under way; the closing barrier keeps a rank that
+// runs ahead from starting one (its kernel stores into the area) while another still copies.
+int Exchange::team_enable(const dcora_team_params &p) {
+  if (!pose_)
+    return usage("team_enable: the team protocol serves pose-graph sessions; a range-aided job has none",
+                 DCORA_ERR_UNSUPPORTED);
+  if (pose_->robust && w_doubles_ != pose_->robust->meas.size())
+    return usage("team_enable: a robust session needs the exchange it was created with (dcora_rbcd_create_robust_ranks)",
+                 DCORA_ERR_UNSUPPORTED);
+  team_snapshot_weights();
+  const int rc = pose_->team_enable_ranked(p, status_, (ShmStatus *)(dev_map_ + off_status_),
+                                           w_doubles_ ? job_w_.data() : nullptr);
+  if (rc) return rc;
+  return barrier();
+}
+
+TeamSlots Exchange::team_slots() const {
+  TeamSlots t;
+  t.status = status_;
+  t.read = status_read_;
+  t.failed = &hdr_->failed;
+  t.rank = rank;
+  t.world = world;
+  t.R = R_;
+  t.timeout_s = exchange_timeout_s();
+  return t;
+}
+
+int Exchange::team_wait_failed(int what, const std::string &who) {
+  return fail(what == kTeamWaitPeerFailed ? std::string("another rank failed") : who, DCORA_ERR_HIP);
+}
+
+// optimisation q = seq + 1 of a hosted agent will store into slot [q & 1]: every rank has read q - 2 out of it
+int Exchange::team_clear_to_write(const int *agents, int count) {
+  const TeamState &t = *pose_->team;
+  const TeamSlots slots = team_slots();
+  for (int i = 0; i < count; ++i) {
+    const int a = agents[i];
+    if (a < 0 || a >= R_ || !s_->agent_core(a).hosted) continue;
+    const uint64_t q = t.seq[(size_t)a] + 1;
+    if (q <= 2) continue;
+    int whom = 0;
+    if (const int rc = slots.read_wait(a, q - 2, &whom))
+      return team_wait_failed(rc, "rank " + std::to_string(whom) + " never read status " + std::to_string(q - 2) +
+                                      " of agent " + std::to_string(a));
+  }
+  return DCORA_OK;
+}
+
+int Exchange::team_collect(const int *agents, int count) {
+  const TeamState &t = *pose_->team;
+  const TeamSlots slots = team_slots();
+  for (int i = 0; i < count; ++i) {
+    const int a = agents[i];
+    const uint64_t q = t.seq[(size_t)a];
+    if (const int rc = slots.status_wait(q, a))
+      return team_wait_failed(rc, "the status of agent " + std::to_string(a) + " never arrived");
+    const ShmStatus *slot = slots.slot(q, a);
+    pose_->team_settle_published(a, slot->success != 0, slot->rel);
+    slots.mark_read(q, a);
+  }
+  return DCORA_OK;
+}
+
+// RbcdSession::run_team across the ranks: the same loop of the same rules on every rank's copy of the statuses
+int Exchange::run_team(int *iters_done, double *cost2_trace, double *gradnorm_trace, int *selected_trace,
+                       int *updated_trace, int *weight_updates, int *stop_reason) {
+  RbcdSession &s = *pose_;
+  TeamState &t = *s.team;
+  const int cap = t.params.max_num_iters;
+  int selected = 0, it = 0, nupd = 0;
+  for (;;) {
+    int stop = 0, upd = 0;
+    int rc = s.team_decide(&stop, &upd);
+    if (rc) return rc;
+    if (stop || it >= cap) break;
+    if (updated_trace) updated_trace[it] = upd;
+    if (upd) {
+      const bool reset = t.resets_done < t.params.robust_opt_num_resets;
+      int counts[3];
+      rc = update_weights(s, reset, counts);
+      if (rc) return rc;
+      if (reset) t.resets_done++;
+      nupd++;
+    }
+    double c2 = 0, gn = 0;
+    int nxt = selected;
+    rc = rbcd_iterate(selected, &c2, &gn, nullptr, &nxt);
+    if (rc) return rc;
+    if (cost2_trace) cost2_trace[it] = c2;
+    if (gradnorm_trace) gradnorm_trace[it] = gn;
+    if (selected_trace) selected_trace[it] = selected;
+    selected = nxt;
+    ++it;
+  }
+  if (iters_done) *iters_done = it;
+  if (weight_updates) *weight_updates = nupd;
+  if (stop_reason) *stop_reason = s.iteration >= cap ? DCORA_TEAM_STOP_MAX_ITERS : DCORA_TEAM_STOP_ALL_READY;
+  return DCORA_OK;
 }
 
 int Exchange::run_coloured(int max_sweeps, double rgrad_tol, int *sweeps_done, double *cost2_trace,
@@ -1013,6 +1144,13 @@ int Exchange::update_weights(RbcdSession &s, bool reset_to_initial, int counts[3
   if (rc) return fail(std::string("update_weights: ") + dcora_last_error(), rc);
   rc = allreduce_sum(cnt, 3);
   if (rc) return rc;
+  if (team_on()) {
+    // the team's loop-closure counts are of the whole job's weights: a copy of the area, complete now, and nobody
+    // starts the next update (whose kernel stores into the area) before every rank has made its copy
+    team_snapshot_weights();
+    rc = barrier();
+    if (rc) return rc;
+  }
   if (reset_to_initial) {  // (every rank's mirror becomes the last set_X at once, as Exchange::set_X does)
     rc = barrier();
     if (rc) return rc;
@@ -1033,7 +1171,14 @@ int Exchange::update_weights(RbcdSession &s, bool reset_to_initial, int counts[3
 int Exchange::set_weights(RbcdSession &s, const double *w) {
   if (!s.robust || !s.robust->ranked || &s != s_ || w_doubles_ != s.robust->meas.size())
     return usage("set_weights: the exchange's session is not a ranked robust session", DCORA_ERR_BAD_ARG);
+  // (the team's counts are refreshed from the job's weights inside: every rank is handed all m of them)
+  std::vector<double> before;
+  if (team_on()) {
+    before = job_w_;
+    std::copy(w, w + w_doubles_, job_w_.begin());
+  }
   const int rc = s.set_weights(w);
+  if (rc && team_on()) std::copy(before.begin(), before.end(), job_w_.begin());
   if (rc == DCORA_ERR_BAD_ARG) return rc;  // (refused on every rank alike, nothing changed)
   if (rc) return fail(std::string("set_weights: ") + dcora_last_error(), rc);
   return publish_weights(s);
@@ -1152,6 +1297,47 @@ int Exchange::host_selftest(const char *job_name, int rank_, int world_, int R, 
     }
   }
   if (checksum) *checksum = sum;
+  return barrier();
+}
+
+// The team's half of the rehearsal (dcora_hip.h, dcora_exchange_host_selftest_team): team_rehearsal (team_slots.h) on
+// this segment's status area -- the slots, sequence words, read words and waits of team_clear_to_write / team_collect,
+// with host stores where the ranked k_rel_change stores -- behind the bootstrap and the heartbeat of host_selftest.
+int Exchange::host_selftest_team(const char *job_name, int rank_, int world_, int R, int rounds, int skew_us,
+                                 double *checksum) {
+  rank = rank_;
+  world = world_;
+  R_ = R;
+  if (world < 1 || rank < 0 || rank >= world || world > kMaxRanks || R < 1 || R > kMaxAgents || rounds < 1 || skew_us < 0)
+    return fail("host selftest: bad arguments", DCORA_ERR_BAD_ARG);
+  slot_ = 16;
+  int rc = map_segment(job_name, 16);
+  if (rc) return rc;
+  rc = barrier();
+  if (rc) return rc;
+  if (rank == 0) shm_unlink(name_.c_str());
+  const int per = (R + world - 1) / world;
+  uint64_t beats = 0;
+  auto heartbeat = [&]() -> int {  // the evaluation's (Exchange::evaluate)
+    const uint64_t want = ++beats;
+    ShmEval *hb = evals_ + (size_t)(want & 1) * ((size_t)R + world) + R;
+    const auto t0 = Clock::now();
+    std::atomic_thread_fence(std::memory_order_release);
+    hb[rank].seq = want;
+    for (int p2 = 0; p2 < world; ++p2) {
+      unsigned spins = 0;
+      while (hb[p2].seq < want) {
+        polite_spin(spins);
+        if ((spins & 1023u) == 0) {
+          if (hdr_->failed.load()) return kTeamWaitPeerFailed;
+          if (since(t0) > exchange_timeout_s()) return kTeamWaitTimeout;
+        }
+      }
+    }
+    return kTeamWaitOk;
+  };
+  rc = team_rehearsal(team_slots(), per, rounds, skew_us, heartbeat, checksum);
+  if (rc) return team_wait_failed(rc, "host selftest: a status, a read word or a heartbeat never arrived");
   return barrier();
 }
 

@@ -15,6 +15,8 @@
 #include <climits>
 #include <vector>
 
+#include "team_slots.h"
+
 namespace dcora {
 
 constexpr int kMaxPartials = 1024;  // upper bound on per-kernel partial-sum slots
@@ -350,6 +352,16 @@ struct RelChangeSet {
 };
 void launch_rel_change(hipStream_t st, int r, int d, const double *X, const double *XPrev, const int *pose_start,
                        const RelChangeSet &set, double *out);
+// The ranked form (the team of a multi-rank job, exchange.h): the result goes into the agent's status slot of the job's
+// shared segment instead, followed by the slot's sequence word.  slots: the device view of the area, [2][R]; entry i of
+// the set publishes optimisation seq[i] of its agent into slot (seq[i] & 1) R + agent.
+struct RelChangePublish {
+  ShmStatus *slots;
+  int R;
+  uint64_t seq[kMaxAgents];
+};
+void launch_rel_change_ranked(hipStream_t st, int r, int d, const double *X, const double *XPrev, const int *pose_start,
+                              const RelChangeSet &set, const RelChangePublish &pub);
 int max_translation_distance(int r, int d, int n, const double *X, const double *Y, double *out);
 int launch_g_retract(hipStream_t st, const ManiDesc &m, Buf2 X, const double *V, double alpha, Buf2 out, int selOut,
                      Buf2 grad, const double *HV, double *partials, Gate g);

@@ -79,6 +79,16 @@ struct TeamState {
   std::vector<Pending> pending;
   std::vector<int> lc;  // 3 per agent: accepted, rejected, all loop closures (Graph::statistics, ref src/Graph.cpp:475-521)
   int latest_weight_update_iteration = 0, resets_done = 0;
+  // Ranked mode (the session is one rank of a job, enabled by Exchange::team_enable): every rank keeps the statuses of
+  // all R agents.  What an agent knew when it optimised -- round, weight-update count, loop-closure counts -- every
+  // rank knows; whether its update succeeded and its relative change only the hosting rank does, and those two travel
+  // through the agent's status slot of the job's segment (the ranked k_rel_change), collected by the exchange inside
+  // the collective call.  Nothing is read from rel_host.
+  bool ranked = false;
+  ShmStatus *slots = nullptr, *slots_dev = nullptr;  // [2][R], host and device view (owned by the exchange)
+  std::vector<uint64_t> seq;     // optimisations of agent a since the team was enabled: the same on every rank
+  const double *job_w = nullptr; // the job's m weights as of the last weight change (the exchange's copy); null on an
+                                 // L2 job, whose counts come from the creation weights
 };
 
 class RbcdSession : public SessionCore {
@@ -135,6 +145,12 @@ class RbcdSession : public SessionCore {
   // ---- the team protocol (dcora_rbcd_team_enable) ----
   std::unique_ptr<TeamState> team;
   int team_enable(const dcora_team_params &p);
+  // ... of a rank of a job (through its exchange only): the status area and the job's weights the exchange keeps
+  int team_enable_ranked(const dcora_team_params &p, ShmStatus *slots, ShmStatus *slots_dev, const double *job_w);
+  // ranked: the bookkeeping of team_note_optimized for those agents of ids that live on another rank, and the two facts
+  // the hosting rank published for one agent settled into its status
+  void team_note_elsewhere(const int *ids, int count);
+  void team_settle_published(int agent, bool success, double relative_change);
   int team_agent_status(int agent, dcora_agent_status *status, int *known);
   int team_decide(int *should_terminate, int *should_update_weights);
   bool team_robust() const { return robust && robust->params.cost_type != DCORA_ROBUST_L2; }
@@ -173,6 +189,7 @@ class RbcdSession : public SessionCore {
   // pending statuses settled (visible: the host has already seen the stream pass their launch), the loop-closure
   // counts after a weight change, the statuses cleared, the bookkeeping restarted with the round counter
   int team_note_optimized(const int *ids, int count);
+  void team_mark_optimized(int agent, bool success);
   int team_settle(bool visible);
   void team_refresh_counts();
   void team_clear_statuses();

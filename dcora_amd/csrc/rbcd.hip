@@ -760,6 +760,11 @@ int RbcdSession::agent_iterate(int agent, bool do_optimization) {
     set_last_error("rbcd: agent is hosted by another rank");
     return DCORA_ERR_BAD_ARG;
   }
+  if (team && team->ranked) {
+    set_last_error("rbcd team: the agents of a multi-rank team optimise through their exchange "
+                   "(dcora_exchange_rbcd_iterate / _rbcd_tick), which carries their statuses to every rank");
+    return DCORA_ERR_UNSUPPORTED;
+  }
   DCORA_HIP(hipSetDevice(opt.device));
   set_marks_.assign(R, 0);
   // Agent::iteration_number() of every agent; between rounds they are all equal to the session's round counter
@@ -1095,8 +1100,12 @@ int RbcdSession::agent_iteration_number(int agent) const {
 
 int RbcdSession::team_enable(const dcora_team_params &p) {
   if (opt.world_size != 1) {
-    set_last_error("rbcd team: only single-process sessions (world_size 1) keep the team's statuses; the ranks of a "
-                   "job exchange their flags with dcora_exchange_all_ready");
+    set_last_error("rbcd team: only single-process sessions (world_size 1) keep the team's statuses by themselves; "
+                   "the ranks of a job enable the team through their exchange (dcora_exchange_team_enable)");
+    return DCORA_ERR_UNSUPPORTED;
+  }
+  if (team && team->ranked) {
+    set_last_error("rbcd team: the session's team was enabled through its exchange (dcora_exchange_team_enable)");
     return DCORA_ERR_UNSUPPORTED;
   }
   if (!team) {
@@ -1110,6 +1119,27 @@ int RbcdSession::team_enable(const dcora_team_params &p) {
     team->latest_weight_update_iteration = 0;
     team_refresh_counts();
   }
+  team->params = p;
+  return DCORA_OK;
+}
+
+int RbcdSession::team_enable_ranked(const dcora_team_params &p, ShmStatus *slots, ShmStatus *slots_dev,
+                                    const double *job_w) {
+  if (team && !team->ranked) {
+    set_last_error("rbcd team: the session's team was enabled by dcora_rbcd_team_enable");
+    return DCORA_ERR_UNSUPPORTED;
+  }
+  if (!team) {
+    team.reset(new TeamState);
+    team->ranked = true;
+    team->slots = slots;
+    team->slots_dev = slots_dev;
+    team->seq.assign((size_t)R, 0);
+    team_clear_statuses();
+    team->latest_weight_update_iteration = 0;
+  }
+  team->job_w = job_w;
+  team_refresh_counts();
   team->params = p;
   return DCORA_OK;
 }
@@ -1139,7 +1169,9 @@ void RbcdSession::team_refresh_counts() {
     c[2]++;
   };
   for (size_t k = 0; k < lc_id_.size(); ++k) {
-    const double w = robust ? robust->meas[(size_t)lc_id_[k]].weight : lc_w0_[k];
+    // (a rank keeps only the weights of the edges touching its agents up to date: the job's come from its exchange)
+    const double w = team->job_w ? team->job_w[(size_t)lc_id_[k]]
+                                 : robust ? robust->meas[(size_t)lc_id_[k]].weight : lc_w0_[k];
     count(lc_r1_[k], w);
     if (lc_r2_[k] != lc_r1_[k]) count(lc_r2_[k], w);
   }
@@ -1149,33 +1181,72 @@ void RbcdSession::team_refresh_counts() {
 // everything their updates enqueued on the session's stream, compares the X the round leaves with the XPrev it saved
 int RbcdSession::team_note_optimized(const int *ids, int count) {
   RelChangeSet set{};
+  RelChangePublish pub{};
   for (int i = 0; i < count && set.count < kMaxAgents; ++i) {
     const int b = ids[i];
     if (b < 0 || b >= R || !agents[(size_t)b].hosted) continue;
+    const bool success = !agents[(size_t)b].last_skipped;
+    team_mark_optimized(b, success);
+    if (team->ranked) {
+      // the slot was released by Exchange::team_clear_to_write before the agent's update was enqueued
+      const uint64_t q = team->seq[(size_t)b];
+      team->slots[(size_t)(q & 1) * R + b].success = success ? 1u : 0u;
+      pub.seq[set.count] = q;
+    }
     set.agent[set.count++] = b;
-    dcora_agent_status &s = team->status[(size_t)b];
-    s.agent_id = b;
-    s.state = DCORA_AGENT_INITIALIZED;
-    s.instance_number = 0;
-    s.iteration_number = iteration;
-    s.ready_to_terminate = 0;
-    s.relative_change = 0;
-    team->have[(size_t)b] = 1;
-    TeamState::Pending &p = team->pending[(size_t)b];
-    p.on = true;
-    p.success = !agents[(size_t)b].last_skipped;
-    p.updates = team_weight_updates();
-    for (int c = 0; c < 3; ++c) p.lc[c] = team->lc[(size_t)b * 3 + c];
   }
-  launch_rel_change(st, r, d, Xg.p, XPrevg.p, pose_start.p, set, team->rel_dev);
+  if (team->ranked) {
+    std::atomic_thread_fence(std::memory_order_release);
+    pub.slots = team->slots_dev;
+    pub.R = R;
+    launch_rel_change_ranked(st, r, d, Xg.p, XPrevg.p, pose_start.p, set, pub);
+  } else {
+    launch_rel_change(st, r, d, Xg.p, XPrevg.p, pose_start.p, set, team->rel_dev);
+  }
   DCORA_HIP(hipGetLastError());
   return DCORA_OK;
+}
+
+// what every rank knows of an optimisation of agent b in this round (ranked: hosted here or not)
+void RbcdSession::team_mark_optimized(int b, bool success) {
+  dcora_agent_status &s = team->status[(size_t)b];
+  s.agent_id = b;
+  s.state = DCORA_AGENT_INITIALIZED;
+  s.instance_number = 0;
+  s.iteration_number = iteration;
+  s.ready_to_terminate = 0;
+  s.relative_change = 0;
+  team->have[(size_t)b] = 1;
+  TeamState::Pending &p = team->pending[(size_t)b];
+  p.on = true;
+  p.success = success;
+  p.updates = team_weight_updates();
+  for (int c = 0; c < 3; ++c) p.lc[c] = team->lc[(size_t)b * 3 + c];
+  if (team->ranked) team->seq[(size_t)b]++;
+}
+
+void RbcdSession::team_note_elsewhere(const int *ids, int count) {
+  for (int i = 0; i < count; ++i) {
+    const int b = ids[i];
+    if (b >= 0 && b < R && !agents[(size_t)b].hosted) team_mark_optimized(b, false);  // (success arrives with the slot)
+  }
+}
+
+void RbcdSession::team_settle_published(int b, bool success, double relative_change) {
+  TeamState::Pending &p = team->pending[(size_t)b];
+  if (!p.on) return;
+  p.on = false;
+  p.success = success;
+  dcora_agent_status &s = team->status[(size_t)b];
+  s.relative_change = relative_change;
+  s.ready_to_terminate = team_ready_to_terminate(team->params, team_robust(), p.updates, p.success, s.relative_change,
+                                                 p.lc[0], p.lc[1], p.lc[2]) ? 1 : 0;
 }
 
 int RbcdSession::team_settle(bool visible) {
   bool any = false;
   for (const TeamState::Pending &p : team->pending) any = any || p.on;
-  if (!any) return DCORA_OK;
+  if (!any || team->ranked) return DCORA_OK;  // (ranked: settled by the exchange's collective calls alone)
   if (!visible) {
     DCORA_HIP(hipSetDevice(opt.device));
     DCORA_HIP(hipStreamSynchronize(st));

@@ -3,6 +3,8 @@
 #include "device_problem.h"
 #include "kernels.h"
 
+#include <type_traits>
+
 namespace dcora {
 
 // max over the 64 lanes, same value in every lane (the moves of wave_sum_dpp; a maximum does not depend on the order)
@@ -19,10 +21,16 @@ __device__ __forceinline__ double wave_max_dpp(double v) {
 // its r squares summed in index order by one thread, the maximum of those is exact in any order: the result's bits do
 // not depend on the schedule, and nothing is atomic.  `out` may be host-mapped: the store is followed by a system fence,
 // so whatever the stream publishes next (the evaluation epilogue's seq) is seen after it.
+// Ranked (the team of a multi-rank job): the result is stored into the agent's status slot of the job's shared segment
+// and the slot's sequence word after it, as k_eval_publish stores an evaluation: that device store is the all-gather,
+// every rank's host reads the slot once the word has arrived.  The reduction is the same code: the same bits.
+struct RelNoPublish {};
+template <bool Ranked>
 __global__ __launch_bounds__(kBlock) void k_rel_change(int r, int dh, const double *__restrict__ X,
                                                        const double *__restrict__ XPrev,
                                                        const int *__restrict__ pose_start, RelChangeSet set,
-                                                       double *out) {
+                                                       double *out,
+                                                       std::conditional_t<Ranked, RelChangePublish, RelNoPublish> pub) {
   __shared__ double s_max[kBlock / 64];
   const int b = set.agent[blockIdx.x];
   const int lo = pose_start[b], hi = pose_start[b + 1];
@@ -41,8 +49,17 @@ __global__ __launch_bounds__(kBlock) void k_rel_change(int r, int dh, const doub
   __syncthreads();
   if (threadIdx.x == 0) {
     for (int w = 1; w < kBlock / 64; ++w) m = fmax(m, s_max[w]);
-    out[b] = m;
-    __threadfence_system();
+    if constexpr (Ranked) {
+      const uint64_t q = pub.seq[blockIdx.x];
+      ShmStatus *slot = pub.slots + (size_t)(q & 1) * pub.R + b;
+      __hip_atomic_store((double *)&slot->rel, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      __threadfence_system();
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __hip_atomic_store((uint64_t *)&slot->seq, q, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    } else {
+      out[b] = m;
+      __threadfence_system();
+    }
   }
 }
 
@@ -50,7 +67,16 @@ void launch_rel_change(hipStream_t st, int r, int d, const double *X, const doub
                        const RelChangeSet &set, double *out) {
   count_launch();
   if (set.count < 1) return;
-  hipLaunchKernelGGL(k_rel_change, dim3(set.count), dim3(kBlock), 0, st, r, d + 1, X, XPrev, pose_start, set, out);
+  hipLaunchKernelGGL(k_rel_change<false>, dim3(set.count), dim3(kBlock), 0, st, r, d + 1, X, XPrev, pose_start, set, out,
+                     RelNoPublish{});
+}
+
+void launch_rel_change_ranked(hipStream_t st, int r, int d, const double *X, const double *XPrev, const int *pose_start,
+                              const RelChangeSet &set, const RelChangePublish &pub) {
+  if (set.count < 1) return;
+  count_launch();
+  hipLaunchKernelGGL(k_rel_change<true>, dim3(set.count), dim3(kBlock), 0, st, r, d + 1, X, XPrev, pose_start, set,
+                     (double *)nullptr, pub);
 }
 
 // LiftedArray::maxTranslationDistance of two host arrays through the same kernel (one agent holding all n poses)

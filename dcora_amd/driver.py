@@ -275,6 +275,38 @@ def multi_robot_gnc_ranks(ds, X0, num_robots=5, r=5, robust=None, num_weight_upd
                      close=lambda: (ex.close(), s.close()))
 
 
+def multi_robot_team_ranks(ds, X0, num_robots=5, r=5, robust=None, team=None, acceleration=True, params=None,
+                           fixed=None, device=0, rank=0, world_size=1, job_name="team"):
+    """multi_robot_team_session on one rank of a multi-rank job (SPMD: every rank calls it with the same arguments but
+    rank): the ranks' robust sessions and their exchange (robust_ranked_session), the team enabled through the exchange
+    so that every rank holds every agent's status, Exchange.run_team re-weighting and stopping by the agents' rules.
+    The same outputs on every rank: X gathered, the job's weights, the statuses.
+
+    ds.vals[:, -1] (the weights) is updated in place.  Returns X, weights, the run's record and the final statuses."""
+    from . import robust as rb
+    from . import robust_ranked_session, team_params
+    s, ex = robust_ranked_session(ds, job_name, num_robots=num_robots, r=r,
+                                  robust=robust or rb.RobustCostParameters("GNC_TLS"), fixed_weight=fixed, rank=rank,
+                                  world_size=world_size, device=device, acceleration=acceleration, params=params)
+    try:
+        ex.enable_team(team if team is not None else team_params())
+        ex.set_X(np.asarray(X0, dtype=np.float64))
+        out = ex.run_team()
+        X, w = ex.gather_X(), ex.get_weights()
+        statuses = [ex.agent_status(q) for q in range(num_robots)]
+        stats = [ex.loop_closure_stats(q) for q in range(num_robots)]
+        ex.barrier()
+    finally:
+        ex.close()
+        s.close()
+    ds.vals[:, -1] = w
+    return {"X": X, "weights": w.copy(), "loop_closures": _gnc_mask(ds, num_robots, fixed), "run": out,
+            "statuses": statuses, "loop_closure_stats": stats,
+            "final": {"iterations": int(out["iters"]), "cost_2f": float(out["cost"][-1]) if out["iters"] else None,
+                      "gradnorm": float(out["gradnorm"][-1]) if out["iters"] else None,
+                      "weight_updates": int(out["weight_updates"]), "stop_reason": out["stop_reason"]}}
+
+
 def multi_robot_raslam_example(ra, X0, r_min=None, r_max=100, max_iters=1000, rgrad_tol=0.1, min_eig_tol=1e-3,
                                gradient_tolerance=1e-4, preconditioned_gradient_tolerance=1e-4, acceleration=True,
                                params=None, device=0, mode="rbcd++"):

@@ -483,6 +483,14 @@ int dcora_exchange_certify(dcora_exchange_t ex, int k, const int *rowptr, const 
  * job calls it, *checksum comes out identical on all of them.  For multi-process tests on machines without a GPU. */
 int dcora_exchange_host_selftest(const char *job_name, int rank, int world_size, int num_agents, int rounds,
                                  double *checksum);
+/* the team protocol's half of the same rehearsal (dcora_exchange_team_enable's status slots and waits, host stores in
+ * the device's place): per round one agent (round % num_agents) "optimises" behind an evaluation heartbeat, every
+ * third round a set of non-adjacent agents as a tick without one; the owner publishes a relative change and a success
+ * flag that are fixed functions of (round, agent), every rank collects, settles by dcora_team_ready_to_terminate and
+ * decides by dcora_team_decide.  Rank q sleeps q * skew_us per round.  *checksum folds every status and both decisions
+ * of every round: identical on every rank and for every skew. */
+int dcora_exchange_host_selftest_team(const char *job_name, int rank, int world_size, int num_agents, int rounds,
+                                      int skew_us, double *checksum);
 /* test hook: leaves under the job's name what a crashed job of the same shape would (an initialised segment whose
  * creator is gone); a job started afterwards under that name must not attach to it */
 int dcora_debug_exchange_leave_stale(const char *job_name, int world_size, int num_agents);
@@ -671,6 +679,29 @@ typedef enum { DCORA_TEAM_STOP_ALL_READY = 1, DCORA_TEAM_STOP_MAX_ITERS = 2 } dc
  * agent 0 }.  The traces (any may be NULL) hold max_num_iters entries, entry it belonging to pass it. */
 int dcora_rbcd_run_team(dcora_rbcd_t s, int *iters_done, double *cost2_trace, double *gradnorm_trace,
                         int *selected_trace, int *updated_trace, int *weight_updates, int *stop_reason);
+/* ---- the team protocol across the ranks of a job ----
+ * The entries above on a multi-rank pose-graph job, through its exchange: semantics are their dcora_rbcd_* namesakes',
+ * every rank holds every agent's status, and the outputs are identical on every rank.  Of an optimisation only its
+ * success and its relative change are known to the hosting rank alone: they travel through a status slot of the job's
+ * segment (the relative change stored by the kernel that computes it), every rank settles the status by
+ * dcora_team_ready_to_terminate.
+ * dcora_exchange_team_enable (SPMD): on the exchange of any pose-graph session -- dcora_exchange_create (an L2 team, its
+ * loop-closure counts from the creation weights) or dcora_rbcd_create_robust_ranks, world_size 1 included;
+ * DCORA_ERR_UNSUPPORTED on an exchange of dcora_exchange_create_ra.  Before it the other six return DCORA_ERR_BAD_ARG
+ * (the job goes on).  Once enabled, the session's agents optimise through dcora_exchange_rbcd_iterate / _rbcd_tick /
+ * _run_coloured / _run_team only.
+ * _agent_status, _loop_closure_stats, _should_terminate, _should_update_weights are LOCAL queries: once a collective
+ * call (dcora_exchange_rbcd_iterate, _rbcd_tick, _run_coloured, _update_weights, _set_weights, _set_X) has returned,
+ * they answer from this rank's copy without talking to anyone.  _team_info and _run_team are SPMD.
+ * dcora_exchange_run_team: dcora_rbcd_run_team's loop of dcora_exchange_update_weights and dcora_exchange_rbcd_iterate. */
+int dcora_exchange_team_enable(dcora_exchange_t ex, const dcora_team_params *params);
+int dcora_exchange_agent_status(dcora_exchange_t ex, int agent, dcora_agent_status *status, int *known);
+int dcora_exchange_loop_closure_stats(dcora_exchange_t ex, int agent, int counts[3]);
+int dcora_exchange_should_terminate(dcora_exchange_t ex, int *yes);
+int dcora_exchange_should_update_weights(dcora_exchange_t ex, int *yes);
+int dcora_exchange_team_info(dcora_exchange_t ex, int info[4]);
+int dcora_exchange_run_team(dcora_exchange_t ex, int *iters_done, double *cost2_trace, double *gradnorm_trace,
+                            int *selected_trace, int *updated_trace, int *weight_updates, int *stop_reason);
 /* RobustCost::weight(r) for n residuals after num_updates calls of RobustCost::update() (ref src/DCORA_robust.cpp:56-136) */
 int dcora_robust_weights(const dcora_robust_params *p, int num_updates, int n, const double *r, double *w);
 /* chi2inv (ref src/DCORA_utils.cpp:2103-2106), RobustCost::computeErrorThresholdAtQuantile (ref src/DCORA_robust.cpp:138-148) */
