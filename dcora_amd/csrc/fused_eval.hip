@@ -2,6 +2,7 @@
 // structure of Q (k_spmm_bsrq, which is also the block Q-apply), the evaluation epilogue of an RBCD pass
 // (k_eval_partial, k_eval_finish) and the start-of-solve control block (k_ctl_init).
 #include <algorithm>
+#include <cstddef>
 #include <stdexcept>
 
 #include "csr_rows.h"
@@ -21,22 +22,34 @@ namespace {
 // ------------------------------------------------------------------------------------------------------
 // RIDE (GradRide, kernels.h): the start-point evaluation forms G from the agent's coupling block first -- every thread
 // for its own element (coupling_row, csr_rows.h), nothing another workgroup of the launch writes is read.
+//
+// The loads ahead of the sums are three memory round trips (they were ten to twelve waits in a row: gate words one by
+// one, cur, row pointers, own element, tile, and the gather eight entries at a time, every index read predicated):
+//   1. the gate words, cur and the row pointers of Q, requested as one straight-line batch before the gate is looked
+//      at -- all of it memory that is valid whether or not the gate closes; a gated-off launch still writes nothing;
+//   2. the ci / v tile first, behind it the thread's own element of X and of G;
+//   3. the gather of a row in one batch of kGradGB entries (k_tcg_run's kRunGB) with the weights read from LDS where
+//      they are used; chunks of 8 only for what a row holds beyond it.
+// Only when a load is issued differs from the plain form: every sum keeps its operands, order and expression.
+// What the form costs and assumes: every thread issues the kGradGB gathers of a tile pass, also one without entries in
+// the pass (a zero weight on a column of the tile: finite X assumed, as the padding of a batch always did), and it
+// holds 142 registers -- right for this kernel's one workgroup per 12-16 poses, a wave per SIMD; a row block that had
+// to share a CU with others would want the narrower batch back.  tile_request reads Q.ci / Q.v at a clamped index
+// whatever the block holds: Q has entries (DeviceProblem runs the fused kernels on nnz > 0 only).
+// RIDE keeps coupling_row's own chain (row pointers -> indices -> gather) behind trip 2's requests: its loads riding
+// in trips 1-3 were built and did not pay in the trace (profiles/eval_chains.txt, section 4).
+constexpr int kGradGB = 24;
 template <int D, bool RIDE>
 __global__ __launch_bounds__(kBlock) void k_fused_grad(ManiDesc m, CsrDev Q, Buf2 Xb, const double *__restrict__ G,
                                                        Buf2 EGb, Buf2 RGb, Buf2 Sb, int sel,
                                                        double *__restrict__ pA, double *__restrict__ pB,
                                                        double *__restrict__ posenorm, Gate g, GradRide ride) {
-  if (gated(g.ctl, g.seq, g.gate)) return;
   __shared__ int s_ci[kHessTile];
   __shared__ double s_v[kHessTile];
   __shared__ double s_W[kBlock], s_X[kBlock];
   __shared__ double s_red[16];
   constexpr int DH = D + 1;
-  const int idx = g.ctl ? ((g.ctl->cur ^ sel) & 1) : 0;
-  const double *__restrict__ X = Xb.p[idx];
-  double *__restrict__ EG = EGb.p[idx];
-  double *__restrict__ RG = RGb.p[idx];
-  double *__restrict__ Sblk = Sb.p[idx];
+  constexpr int SU = kHessTile / kBlock;
   const int r = m.r;
   const int PB = fused_pb(r, DH);
   const int pose0 = blockIdx.x * PB;
@@ -46,12 +59,47 @@ __global__ __launch_bounds__(kBlock) void k_fused_grad(ManiDesc m, CsrDev Q, Buf
   const bool act = e < nout;
   const int lc = e / r, t = e - lc * r;
   const int j = j0 + lc;
+  // ---- trip 1 (the empty asm keeps the loads from sinking behind the early return).  Straight-line code, so that it
+  // is issued as one batch: a clamped row instead of a predicated load, and without a control block (the central
+  // evaluation) the three control words are read from Q.rp, which is there, and replaced ----
+  const bool has_ctl = g.ctl != nullptr;
+  const char *cb = has_ctl ? reinterpret_cast<const char *>(g.ctl) : reinterpret_cast<const char *>(Q.rp);
+  auto ctl_word = [&](size_t off) { return *reinterpret_cast<const int *>(cb + (has_ctl ? off : 0)); };
+  const int w_outer = ctl_word(offsetof(SolverCtl, outer_done_stamp));
+  const int w_tcg = ctl_word(offsetof(SolverCtl, tcg_done_stamp));
+  const int w_cur = ctl_word(offsetof(SolverCtl, cur));
+  const int jc = act ? j : j0;
   const int pbeg = Q.rp[j0], pend = Q.rp[j0 + ncol];
-  const int myb = act ? Q.rp[j] : 0, mye = act ? Q.rp[j + 1] : 0;
+  const int rb = Q.rp[jc], re = Q.rp[jc + 1];
+  asm volatile("" ::"s"(w_outer), "s"(w_tcg), "s"(w_cur), "s"(pbeg), "s"(pend), "v"(rb), "v"(re));
+  const GateWords gw{has_ctl ? w_outer : 0x7fffffff, has_ctl ? w_tcg : 0x7fffffff};
+  const int cur = has_ctl ? w_cur : 0;
+  const int myb = act ? rb : 0, mye = act ? re : 0;
+  if (gated(gw, g.ctl, g.seq, g.gate)) return;
+  // (a select between the two pointers of a pair, both kernel arguments: indexing the pair with idx is one more load)
+  const bool idx = g.ctl && ((cur ^ sel) & 1);
+  const double *__restrict__ X = idx ? Xb.p[1] : Xb.p[0];
+  double *__restrict__ EG = idx ? EGb.p[1] : EGb.p[0];
+  double *__restrict__ RG = idx ? RGb.p[1] : RGb.p[0];
+  double *__restrict__ Sblk = idx ? Sb.p[1] : Sb.p[0];
+  // ---- trip 2: the first tile, then the thread's own element of X and of G ----
+  int ci_r[SU];
+  double v_r[SU];
+  const int last = max(pend - 1, 0);
+  auto tile_request = [&](int base) {
+#pragma unroll
+    for (int u = 0; u < SU; ++u) {
+      const int i = min(base + (int)threadIdx.x + u * kBlock, last);
+      ci_r[u] = Q.ci[i];
+      v_r[u] = Q.v[i];
+    }
+  };
+  tile_request(pbeg);
   const size_t oown = (size_t)j * r + t;
-  const double x_own = act ? X[oown] : 0.0;
+  const double x_ld = X[(size_t)jc * r + (act ? t : 0)];
+  const double x_own = act ? x_ld : 0.0;
   double g_own = 0.0;
-  if (RIDE) {
+  if (RIDE) {  // (its own chain of row pointers, indices and gathers, with the tile in flight)
     if (act) {
       g_own = coupling_row(ride, r, j, t);
       ride.G_out[oown] = g_own;
@@ -63,37 +111,39 @@ __global__ __launch_bounds__(kBlock) void k_fused_grad(ManiDesc m, CsrDev Q, Buf
   double acc = 0;
   for (int base = pbeg; base < pend; base += kHessTile) {
     const int cnt = min(kHessTile, pend - base);
-    if (base != pbeg) __syncthreads();
-    {
-      constexpr int SU = kHessTile / kBlock;
-      int ci_r[SU];
-      double v_r[SU];
-      const int last = max(pend - 1, 0);
+    if (base != pbeg) {
+      __syncthreads();
+      tile_request(base);
+    }
 #pragma unroll
-      for (int u = 0; u < SU; ++u) {
-        const int i = min(base + (int)threadIdx.x + u * kBlock, last);
-        ci_r[u] = Q.ci[i];
-        v_r[u] = Q.v[i];
-      }
-#pragma unroll
-      for (int u = 0; u < SU; ++u) {
-        const int i = threadIdx.x + u * kBlock;
-        if (i < cnt) {
-          s_ci[i] = ci_r[u];
-          s_v[i] = v_r[u];
-        }
+    for (int u = 0; u < SU; ++u) {
+      const int i = threadIdx.x + u * kBlock;
+      if (i < cnt) {
+        s_ci[i] = ci_r[u];
+        s_v[i] = v_r[u];
       }
     }
     __syncthreads();
     const int lo = max(myb, base) - base, hi = min(mye, base + cnt) - base;
-    for (int p = lo; p < hi; p += 8) {
+    // ---- trip 3: the first kGradGB entries of the row in one batch ----
+    // (the index reads are clamped, not predicated -- a batch's padding gathers the row's last column again, or the
+    // tile's first, under a zero weight: one wait for all the index reads instead of one LDS round trip each)
+    double bg[kGradGB];
+#pragma unroll
+    for (int q = 0; q < kGradGB; ++q) bg[q] = X[(size_t)s_ci[max(min(lo + q, hi - 1), 0)] * r + t];
+    __builtin_amdgcn_sched_barrier(0);  // (every request of the trip before the first sum)
+#pragma unroll
+    for (int q = 0; q < kGradGB; ++q) {
+      const double wq = s_v[max(min(lo + q, hi - 1), 0)];  // (the weights come from LDS when they are used)
+      acc += ((lo + q < hi) ? wq : 0.0) * bg[q];
+    }
+    for (int p = lo + kGradGB; p < hi; p += 8) {
       double b8[8], w8[8];
 #pragma unroll
       for (int q = 0; q < 8; ++q) {
-        const bool ok = p + q < hi;
-        const size_t oo = ok ? (size_t)s_ci[p + q] * r + t : 0;
-        w8[q] = ok ? s_v[p + q] : 0.0;
-        b8[q] = X[oo];
+        const int pq = min(p + q, hi - 1);
+        w8[q] = (p + q < hi) ? s_v[pq] : 0.0;
+        b8[q] = X[(size_t)s_ci[pq] * r + t];
       }
 #pragma unroll
       for (int q = 0; q < 8; ++q) acc += w8[q] * b8[q];

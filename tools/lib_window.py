@@ -40,6 +40,16 @@ def window(s, X0, skip, count):
     return 1e6 * dt / count, h.hexdigest()[:16]
 
 
+def use_library(path):
+    """point the package at another build of the library, before its first use (record_eval_chains.py shares this)"""
+    import ctypes
+    from dcora_amd import capi
+    capi.LIB_PATH = os.path.abspath(path)
+    L = ctypes.CDLL(capi.LIB_PATH)
+    for name in [n for n in capi.SIGNATURES if not hasattr(L, n)]:  # (an older build lacks the newer entries)
+        del capi.SIGNATURES[name]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--lib", default=None)
@@ -47,11 +57,7 @@ def main():
     a = ap.parse_args()
     from dcora_amd import capi
     if a.lib:
-        import ctypes
-        capi.LIB_PATH = os.path.abspath(a.lib)
-        L = ctypes.CDLL(capi.LIB_PATH)
-        for name in [n for n in capi.SIGNATURES if not hasattr(L, n)]:  # (an older build lacks the newer entries)
-            del capi.SIGNATURES[name]
+        use_library(a.lib)
     import common
     import dcora_amd as da
     if da.device_count() < 1:
