@@ -1211,6 +1211,24 @@ namespace {
 int team_session(dcora_rbcd_t s) {
   return s->s.team ? (int)DCORA_OK : bad("rbcd team: the session has not called dcora_rbcd_team_enable");
 }
+// the team's queries over the session that holds the statuses: a single session's own, or the one of a job's rank
+// (dcora_rbcd_* and dcora_exchange_* differ in how they reach it and in the refusal above)
+int team_agent_status(RbcdSession &s, int agent, dcora_agent_status *status, int *known) {
+  if (agent < 0 || agent >= s.R) return bad("bad agent");
+  return s.team_agent_status(agent, status, known);
+}
+int team_loop_closure_stats(RbcdSession &s, int agent, int counts[3]) {
+  if (agent < 0 || agent >= s.R) return bad("bad agent");
+  for (int c = 0; c < 3; ++c) counts[c] = s.team->lc[(size_t)agent * 3 + c];
+  return (int)DCORA_OK;
+}
+int team_info(RbcdSession &s, int info[4]) {
+  info[0] = s.team_inner_iter();
+  info[1] = s.team->latest_weight_update_iteration;
+  info[2] = s.team_weight_updates();
+  info[3] = s.team->resets_done;
+  return (int)DCORA_OK;
+}
 }  // namespace
 // the opt-in to Agent::iterate's status block (ref src/Agent.cpp:558-586) and the bookkeeping of :1417-1424
 int dcora_rbcd_team_enable(dcora_rbcd_t s, const dcora_team_params *params) {
@@ -1220,19 +1238,14 @@ int dcora_rbcd_team_enable(dcora_rbcd_t s, const dcora_team_params *params) {
 int dcora_rbcd_agent_status(dcora_rbcd_t s, int agent, dcora_agent_status *status, int *known) {
   return abi_call({s, status}, [&] {
     const int rc = team_session(s);
-    if (rc) return rc;
-    if (!agent_ok(s, agent)) return bad("bad agent");
-    return s->s.team_agent_status(agent, status, known);
+    return rc ? rc : team_agent_status(s->s, agent, status, known);
   });
 }
 // Graph::statistics (ref src/Graph.cpp:475-521) of one agent
 int dcora_rbcd_loop_closure_stats(dcora_rbcd_t s, int agent, int counts[3]) {
   return abi_call({s, counts}, [&] {
     const int rc = team_session(s);
-    if (rc) return rc;
-    if (!agent_ok(s, agent)) return bad("bad agent");
-    for (int c = 0; c < 3; ++c) counts[c] = s->s.team->lc[(size_t)agent * 3 + c];
-    return (int)DCORA_OK;
+    return rc ? rc : team_loop_closure_stats(s->s, agent, counts);
   });
 }
 // Agent::shouldTerminate (ref src/Agent.cpp:1123-1156) over the statuses the session holds
@@ -1254,12 +1267,7 @@ int dcora_rbcd_should_update_weights(dcora_rbcd_t s, int *yes) {
 int dcora_rbcd_team_info(dcora_rbcd_t s, int info[4]) {
   return abi_call({s, info}, [&] {
     const int rc = team_session(s);
-    if (rc) return rc;
-    info[0] = s->s.team_inner_iter();
-    info[1] = s->s.team->latest_weight_update_iteration;
-    info[2] = s->s.team_weight_updates();
-    info[3] = s->s.team->resets_done;
-    return (int)DCORA_OK;
+    return rc ? rc : team_info(s->s, info);
   });
 }
 // the optimisation loop of the agents (ref src/Agent.cpp:650-678 with :1123-1156, 1280-1330, 1397-1441) on the
@@ -1515,20 +1523,13 @@ int dcora_exchange_team_enable(dcora_exchange_t ex, const dcora_team_params *par
 int dcora_exchange_agent_status(dcora_exchange_t ex, int agent, dcora_agent_status *status, int *known) {
   return abi_call({ex, status}, [&] {
     const int rc = team_exchange(ex);
-    if (rc) return rc;
-    RbcdSession &s = *ex->e.team_session();
-    if (agent < 0 || agent >= s.R) return bad("bad agent");
-    return s.team_agent_status(agent, status, known);
+    return rc ? rc : team_agent_status(*ex->e.team_session(), agent, status, known);
   });
 }
 int dcora_exchange_loop_closure_stats(dcora_exchange_t ex, int agent, int counts[3]) {
   return abi_call({ex, counts}, [&] {
     const int rc = team_exchange(ex);
-    if (rc) return rc;
-    const RbcdSession &s = *ex->e.team_session();
-    if (agent < 0 || agent >= s.R) return bad("bad agent");
-    for (int c = 0; c < 3; ++c) counts[c] = s.team->lc[(size_t)agent * 3 + c];
-    return (int)DCORA_OK;
+    return rc ? rc : team_loop_closure_stats(*ex->e.team_session(), agent, counts);
   });
 }
 int dcora_exchange_should_terminate(dcora_exchange_t ex, int *yes) {
@@ -1546,13 +1547,7 @@ int dcora_exchange_should_update_weights(dcora_exchange_t ex, int *yes) {
 int dcora_exchange_team_info(dcora_exchange_t ex, int info[4]) {
   return abi_call({ex, info}, [&] {
     const int rc = team_exchange(ex);
-    if (rc) return rc;
-    const RbcdSession &s = *ex->e.team_session();
-    info[0] = s.team_inner_iter();
-    info[1] = s.team->latest_weight_update_iteration;
-    info[2] = s.team_weight_updates();
-    info[3] = s.team->resets_done;
-    return (int)DCORA_OK;
+    return rc ? rc : team_info(*ex->e.team_session(), info);
   });
 }
 int dcora_exchange_run_team(dcora_exchange_t ex, int *iters_done, double *cost2_trace, double *gradnorm_trace,

@@ -11,47 +11,16 @@
 // word and enqueues the scatter into its mirror.  No collective, no ring, no host copy of pose data.
 // When IPC mapping (or its self-test) fails on any rank, all ranks fall back to staging the packed poses in the same
 // shared host segment (device store over PCIe, device load over PCIe on the consumer).
+// The host half of the protocol -- the segment's layout, the bounded wait and every host step -- is stated once in
+// exchange_slots.h (no HIP); this class wraps the steps with its error texts and statistics and launches the kernels.
 #pragma once
-#include <atomic>
-#include <cstdint>
 #include <string>
 #include <vector>
 
+#include "exchange_slots.h"
 #include "rbcd.h"
 
 namespace dcora {
-
-constexpr int kMaxRanks = 64;
-constexpr uint32_t kShmMagic = 0x44434f52u;  // "DCOR"
-constexpr int kProbeDoubles = 512;           // the link check's payload: 4 KB
-
-// (ShmFlag, ShmStatus: team_slots.h)
-struct alignas(64) ShmEval {
-  volatile double g2, xeg;  // |Proj(X_b Q_bb + G_b)|^2, <X_b, X_b Q_bb + G_b>
-  volatile uint64_t seq;
-  uint64_t pad[5];
-};
-struct alignas(64) ShmRank {
-  hipIpcMemHandle_t halo;  // 64 bytes
-  std::atomic<int> device, pid, ipc_ok, published;
-  std::atomic<uint64_t> bus;  // hash of the device's PCI bus id: two ranks with the same value share a GPU
-  std::atomic<int> fine;      // 1: this rank's halo buffer is fine-grained device memory
-  std::atomic<int> probe;     // link check: +round passed, -round failed
-  uint64_t pad[4];
-};
-struct alignas(64) ShmRed {  // one rank's contribution to a sum over the ranks
-  volatile uint64_t seq;
-  double vals[31];
-};
-struct ShmHeader {
-  std::atomic<uint32_t> magic;
-  uint32_t world, R;
-  uint64_t slot_doubles, total_bytes, x_doubles;
-  std::atomic<uint32_t> bar_count, bar_gen;
-  std::atomic<uint32_t> failed;  // a rank gave up: everybody waiting returns an error instead of spinning on
-  int32_t creator_pid;           // rank 0's process: a segment whose creator is gone is a stale one (crashed job)
-  uint64_t creator_start;        // ... and its start time (/proc/<pid>/stat): a recycled pid is not the creator
-};
 
 enum ExchangeMode { kExchangeIpc = 1, kExchangeStaged = 2 };
 
@@ -96,14 +65,7 @@ class Exchange {
   // everywhere: whether it succeeded and its relative change.  The hosting rank stores the first from the host, the
   // ranked k_rel_change behind the agent's update stores the second and then the slot's sequence word; every rank
   // (the hosting one too) collects them inside the collective call and settles the status by the same rule.
-  // Slot re-use.  Optimisation q of agent a goes into slot [q & 1][a], last used by q - 2.  Before the hosting rank
-  // touches it, it waits (bounded) until every rank's status_read_[rank][a] has reached q - 2: that one wait closes the
-  // hazard for ticks, which have no evaluation behind them and whose posts are scattered before the status is read.
-  // Greedy iterations would not need it -- nobody leaves evaluation k before everybody has entered it, and a rank
-  // says it has entered only after it has read status k, so even one slot per agent would do there; the word is then
-  // always there already and the wait costs one load per rank.  (rbcd_iterate reads the status inside evaluate, after
-  // the evaluation's kernels are enqueued and before its heartbeat: read before them, the hosting rank's host waited
-  // for its own update and its queue ran dry -- 18 us per iteration instead of the launch's 6.)
+  // (Slot re-use and the back-pressure on the read words: exchange_slots.h, at the steps.)
   int team_enable(const dcora_team_params &p);
   bool team_on() const { return pose_ && pose_->team && pose_->team->ranked; }
   RbcdSession *team_session() const { return team_on() ? pose_ : nullptr; }
@@ -117,8 +79,8 @@ class Exchange {
   int gather_X(double *Xh);
   // Agent::setX of every agent on every rank: sequence numbers restart with the Nesterov sequences
   int set_X(const double *Xh);
-  // host half of the protocol alone (bootstrap, barriers, flags, evaluation slots; host stores stand in for the
-  // device's): runs without a GPU, for the world-size-2 CPU test
+  // host half of the protocol alone, without a GPU: the bootstrap, then exchange_rehearsal (exchange_slots.h) -- the
+  // steps post_arr, wait_arr, evaluate and allreduce_sum make, host stores standing in for the device's
   int host_selftest(const char *job_name, int rank, int world, int R, int rounds, double *checksum);
   // test hook: what a crashed job of this shape leaves behind under the name (initialised, creator gone)
   int debug_leave_stale(const char *job_name, int world, int R);
@@ -139,34 +101,21 @@ class Exchange {
  private:
   SessionCore *s_ = nullptr;
   std::string name_;
-  void *map_ = nullptr;
-  size_t map_bytes_ = 0;
+  SegmentLayout lay_;        // where every area of the segment lies (exchange_slots.h)
+  void *map_ = nullptr;      // host view of the segment
+  char *dev_map_ = nullptr;  // device view of it: kernel arguments are lay_'s accessors on this base
   bool registered_ = false;
-  char *dev_map_ = nullptr;  // device view of the segment
   ShmHeader *hdr_ = nullptr;
-  ShmRank *ranks_ = nullptr;
-  ShmFlag *flags_ = nullptr;  // [parity][agent]
-  ShmEval *evals_ = nullptr;  // [parity][agent]
-  double *staged_ = nullptr;  // [parity][agent][slot]
-  double *xarea_ = nullptr;   // r x (d+1) n
-  size_t off_w_ = 0, w_doubles_ = 0;  // weights area: m doubles in dataset order, written by the edges' owners
-  ShmRed *red_ = nullptr;        // [parity][rank]
-  size_t off_red_ = 0;
   uint64_t red_seq_ = 0;
-  ShmFlag *consumed_ = nullptr;  // [consumer rank][agent]: the last post of the agent that rank has scattered
-  ShmStatus *status_ = nullptr;      // [parity][agent]: the team's status area
-  ShmFlag *status_read_ = nullptr;   // [reader rank][agent]: the last optimisation of the agent whose status it has read
-  size_t off_status_ = 0, off_status_read_ = 0;
   RbcdSession *pose_ = nullptr;      // the session when it is a pose-graph one (the team protocol serves those)
   std::vector<double> job_w_;        // the job's weights as of the last weight change (the team's loop-closure counts)
   std::vector<int> team_due_;        // agents whose status the evaluation of this rbcd_iterate has to collect
   int team_clear_to_write(const int *agents, int count);  // before the agents optimise: their slots may be overwritten
   int team_collect(const int *agents, int count);         // after their posts: every rank reads and settles
-  TeamSlots team_slots() const;
-  int team_wait_failed(int what, const std::string &who);  // a kTeamWait* result as this exchange's failure
+  ExchangeSlots slots() const { return ExchangeSlots{lay_, map_, rank, exchange_timeout_s()}; }
+  ShmRank &rank_record(int q) const { return *lay_.rank_record(map_, q); }
+  int wait_failed(int what, const std::string &who);  // a kWait* result as this exchange's failure (`who`: timed out)
   void team_snapshot_weights();
-  size_t off_flags_ = 0, off_evals_ = 0, off_staged_ = 0, off_x_ = 0, off_consumed_ = 0;
-  size_t off_probe_flags_ = 0, off_probe_res_ = 0, off_probe_stage_ = 0;  // link check: [reader][writer] words / 4 KB
   size_t probe_off_ = 0;  // in a halo buffer: [writer] x (kProbeDoubles payload + 8 doubles of flag)
   size_t devflag_off_ = 0;       // in a halo buffer, behind the slots and the self-test area: [parity][agent] x 64 bytes
   bool device_wait_ = true;      // the scatter kernel polls the flag itself (no host hop between post and scatter)
@@ -188,8 +137,9 @@ class Exchange {
   uint64_t eval_seq_ = 0;
 
   size_t halo_off(int parity, int agent) const { return ((size_t)parity * R_ + agent) * slot_; }
-  int open_segment(const char *job_name, size_t bytes);
+  int open_segment(const char *job_name);
   int map_segment(const char *job_name, size_t x_doubles, size_t w_doubles = 0);
+  int selftest_bootstrap(const char *job_name, int rank, int world, int R, bool args_ok);
   int setup_ipc(bool attempt);
   int link_check();
   bool probe_round(uint64_t seq, std::string *why);

@@ -3,14 +3,12 @@
 #include "env.h"
 
 #include <fcntl.h>
-#include <sched.h>
 #include <signal.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
 #include <unistd.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -21,8 +19,7 @@ namespace dcora {
 
 namespace {
 
-using Clock = std::chrono::steady_clock;
-inline double since(Clock::time_point t0) { return std::chrono::duration<double>(Clock::now() - t0).count(); }
+static_assert(sizeof(hipIpcMemHandle_t) == sizeof(ShmRank::halo), "ShmRank stores the IPC handle as 64 bytes");
 constexpr int kMaxDst = 8;
 struct PostDst {
   double *base[kMaxDst];
@@ -218,6 +215,10 @@ int Exchange::fail(const std::string &msg, int code) {
   return code;
 }
 
+int Exchange::wait_failed(int what, const std::string &who) {
+  return fail(what == kWaitPeerFailed ? std::string("another rank failed") : who, DCORA_ERR_HIP);
+}
+
 int Exchange::num_peers() const {
   std::set<int> p;
   for (const auto &v : dests_) p.insert(v.begin(), v.end());
@@ -233,7 +234,7 @@ Exchange::~Exchange() {
   for (int q = 0; q < kMaxRanks; ++q)
     if (opened_[q] && peer_halo_[q]) (void)hipIpcCloseMemHandle(peer_halo_[q]);
   if (registered_ && map_) (void)hipHostUnregister(map_);
-  if (map_) munmap(map_, map_bytes_);
+  if (map_) munmap(map_, lay_.total);
   if (rank == 0 && !name_.empty()) shm_unlink(name_.c_str());
 }
 
@@ -241,7 +242,8 @@ Exchange::~Exchange() {
 // once it is there.  A rank that opened the name BEFORE rank 0 replaced it holds a stale segment (a crashed job, a reused
 // job name): it recognises that by the creator's process being gone or by the name resolving to another inode by now,
 // drops the mapping and opens the name again.  Two LIVE jobs under one name on one node remain a caller's error.
-int Exchange::open_segment(const char *job_name, size_t bytes) {
+int Exchange::open_segment(const char *job_name) {
+  const size_t bytes = lay_.total;
   name_ = std::string("/dcora_") + job_name;
   const auto t0 = Clock::now();
   if (rank == 0) {
@@ -258,7 +260,6 @@ int Exchange::open_segment(const char *job_name, size_t bytes) {
       map_ = nullptr;
       return fail("mmap failed: " + std::string(std::strerror(errno)), DCORA_ERR_IO);
     }
-    map_bytes_ = bytes;
     hdr_ = (ShmHeader *)map_;
     std::memset(map_, 0, bytes);
     hdr_->world = (uint32_t)world;
@@ -332,82 +333,19 @@ int Exchange::open_segment(const char *job_name, size_t bytes) {
                   DCORA_ERR_BAD_ARG);
     }
     map_ = mp;
-    map_bytes_ = bytes;
     hdr_ = h;
     return DCORA_OK;
   }
 }
 
-// shared segment: header | per-rank records | flags [2][R] | evaluation slots [2][R] | ... | statuses [2][R] and their
-// read words [world][R] | staged poses [2][R][slot] | X | weights
 int Exchange::map_segment(const char *job_name, size_t x_doubles, size_t w_doubles) {
-  const int R = R_;
-  size_t off = align_up(sizeof(ShmHeader), 64);
-  const size_t off_ranks = off;
-  off += sizeof(ShmRank) * world;
-  off_flags_ = off;
-  off += sizeof(ShmFlag) * 2 * R;
-  off_evals_ = off;
-  off += sizeof(ShmEval) * 2 * (R + world);  // R agent slots + one heartbeat slot per rank, double-buffered
-  off_consumed_ = off;
-  off += sizeof(ShmFlag) * (size_t)world * R;
-  off_red_ = off;
-  off += sizeof(ShmRed) * 2 * (size_t)world;
-  off_status_ = off;  // the team's status area [2][R] and what every rank has read of it [world][R]
-  off += sizeof(ShmStatus) * 2 * R;
-  off_status_read_ = off;
-  off += sizeof(ShmFlag) * (size_t)world * R;
-  off_probe_flags_ = off;  // link check: [reader][writer] flag words, then result words
-  off += sizeof(ShmFlag) * (size_t)world * world;
-  off_probe_res_ = off;
-  off += sizeof(ShmFlag) * (size_t)world * world;
-  off = align_up(off, 4096);
-  off_probe_stage_ = off;  // ... and 4 KB per (reader, writer) for the staged transport's probe
-  off += sizeof(double) * kProbeDoubles * (size_t)world * world;
-  off = align_up(off, 4096);
-  off_staged_ = off;
-  off += sizeof(double) * 2 * R * slot_;
-  off = align_up(off, 4096);
-  off_x_ = off;
-  off += sizeof(double) * x_doubles;
-  off = align_up(off, 64);
-  off_w_ = off;
-  w_doubles_ = w_doubles;
-  off += sizeof(double) * w_doubles;
-  const size_t total = align_up(off, 4096);
-  const int rc = open_segment(job_name, total);
-  if (rc) return rc;
-  ranks_ = (ShmRank *)((char *)map_ + off_ranks);
-  flags_ = (ShmFlag *)((char *)map_ + off_flags_);
-  evals_ = (ShmEval *)((char *)map_ + off_evals_);
-  consumed_ = (ShmFlag *)((char *)map_ + off_consumed_);
-  red_ = (ShmRed *)((char *)map_ + off_red_);
-  status_ = (ShmStatus *)((char *)map_ + off_status_);
-  status_read_ = (ShmFlag *)((char *)map_ + off_status_read_);
-  staged_ = (double *)((char *)map_ + off_staged_);
-  xarea_ = (double *)((char *)map_ + off_x_);
-  return DCORA_OK;
+  lay_ = SegmentLayout(world, R_, slot_, x_doubles, w_doubles);
+  return open_segment(job_name);
 }
 
 int Exchange::barrier(double timeout_s) {
-  if (world == 1) return DCORA_OK;
-  timeout_s = std::min(timeout_s, exchange_timeout_s());
-  const auto t0 = Clock::now();
-  const uint32_t gen = hdr_->bar_gen.load(std::memory_order_acquire);
-  if (hdr_->bar_count.fetch_add(1, std::memory_order_acq_rel) + 1 == (uint32_t)world) {
-    hdr_->bar_count.store(0, std::memory_order_relaxed);
-    hdr_->bar_gen.fetch_add(1, std::memory_order_release);
-    return DCORA_OK;
-  }
-  unsigned spins = 0;
-  while (hdr_->bar_gen.load(std::memory_order_acquire) == gen) {
-    if ((++spins & 1023u) == 0) {
-      if (hdr_->failed.load()) return fail("another rank failed", DCORA_ERR_HIP);
-      if (since(t0) > timeout_s) return fail("barrier timed out", DCORA_ERR_HIP);
-      sched_yield();
-    }
-  }
-  return DCORA_OK;
+  const int rc = slots().barrier(timeout_s);
+  return rc ? wait_failed(rc, "barrier timed out") : DCORA_OK;
 }
 
 int Exchange::init(SessionCore *s, const char *job_name, size_t weights) {
@@ -451,7 +389,7 @@ int Exchange::init(SessionCore *s, const char *job_name, size_t weights) {
   int rc = map_segment(job_name, (size_t)s->r * (size_t)s->num_cols(), weights);
   if (rc) return rc;
   {
-    const hipError_t e = hipHostRegister(map_, map_bytes_, hipHostRegisterMapped | hipHostRegisterPortable);
+    const hipError_t e = hipHostRegister(map_, lay_.total, hipHostRegisterMapped | hipHostRegisterPortable);
     if (e != hipSuccess) return fail(std::string("hipHostRegister of the shared segment failed: ") + hipGetErrorString(e), DCORA_ERR_HIP);
     registered_ = true;
     DCORA_HIP(hipHostGetDevicePointer((void **)&dev_map_, map_, 0));
@@ -468,7 +406,7 @@ int Exchange::init(SessionCore *s, const char *job_name, size_t weights) {
       std::snprintf(bus, sizeof(bus), "device-%d", s->opt.device);
     }
     for (const char *c = bus; *c; ++c) h = (h ^ (uint64_t)(unsigned char)*c) * 1099511628211ull;
-    ranks_[rank].bus.store(h ? h : 1, std::memory_order_release);
+    rank_record(rank).bus.store(h ? h : 1, std::memory_order_release);
   }
   DCORA_HIP(evalbuf_.alloc(2 * R));
   DCORA_HIP(hipMemset(evalbuf_.p, 0, sizeof(double) * 2 * R));
@@ -484,11 +422,11 @@ int Exchange::init(SessionCore *s, const char *job_name, size_t weights) {
     if (rc != DCORA_OK && rc != DCORA_ERR_UNSUPPORTED) return rc;
     ok = rc == DCORA_OK;
   }
-  ranks_[rank].ipc_ok.store(ok ? 1 : -1, std::memory_order_release);
+  rank_record(rank).ipc_ok.store(ok ? 1 : -1, std::memory_order_release);
   int rc2 = barrier();
   if (rc2) return rc2;
   bool all = true;
-  for (int q = 0; q < world; ++q) all = all && ranks_[q].ipc_ok.load(std::memory_order_acquire) == 1;
+  for (int q = 0; q < world; ++q) all = all && rank_record(q).ipc_ok.load(std::memory_order_acquire) == 1;
   mode = all ? kExchangeIpc : kExchangeStaged;
   {
     // Who waits for a producer's flag.  With a GPU of its own the consumer's scatter kernel polls the flag itself: no
@@ -498,12 +436,12 @@ int Exchange::init(SessionCore *s, const char *job_name, size_t weights) {
     // DCORA_EXCHANGE_WAIT=device / host forces one or the other.
     bool shared_gpu = false;
     for (int q = 0; q < world; ++q)
-      if (q != rank && ranks_[q].bus.load(std::memory_order_acquire) == ranks_[rank].bus.load()) shared_gpu = true;
+      if (q != rank && rank_record(q).bus.load(std::memory_order_acquire) == rank_record(rank).bus.load()) shared_gpu = true;
     // A peer GPU's stores into a COARSE-grained halo buffer are not guaranteed visible to a kernel of this GPU that is
     // already running (lines may be served from the local L2; the host-wait form relies on the invalidate of the
     // kernel boundary): the kernel polls only where every rank's halo is fine-grained device memory.
     bool all_fine = true;
-    for (int q = 0; q < world; ++q) all_fine = all_fine && ranks_[q].fine.load(std::memory_order_acquire) == 1;
+    for (int q = 0; q < world; ++q) all_fine = all_fine && rank_record(q).fine.load(std::memory_order_acquire) == 1;
     const bool poll_is_safe = mode != kExchangeIpc || all_fine;
     const char *wm = env::exchange_wait();
     device_wait_ = (wm ? std::strcmp(wm, "host") != 0 : !shared_gpu) && poll_is_safe;
@@ -552,24 +490,26 @@ int Exchange::setup_ipc(bool attempt) {
     }
   }
   if (ok && hipMemset(halo_.p, 0, sizeof(double) * halo_doubles) != hipSuccess) no("hipMemset");
-  if (ok && hipIpcGetMemHandle(&ranks_[rank].halo, halo_.p) != hipSuccess) {
+  hipIpcMemHandle_t mine;
+  if (ok && hipIpcGetMemHandle(&mine, halo_.p) != hipSuccess) {
     (void)hipGetLastError();
     if (halo_finegrained_) {  // a runtime that exports no handle for fine-grained memory: once more with plain hipMalloc
       halo_.release();
       halo_finegrained_ = false;
       if (halo_.alloc(halo_doubles) != hipSuccess ||
           hipMemset(halo_.p, 0, sizeof(double) * halo_doubles) != hipSuccess ||
-          hipIpcGetMemHandle(&ranks_[rank].halo, halo_.p) != hipSuccess)
+          hipIpcGetMemHandle(&mine, halo_.p) != hipSuccess)
         no("hipIpcGetMemHandle");
     } else {
       no("hipIpcGetMemHandle");
     }
   }
   (void)hipGetLastError();
-  ranks_[rank].device.store(s_->opt.device);
-  ranks_[rank].pid.store((int)getpid());
-  ranks_[rank].fine.store(ok && halo_finegrained_ ? 1 : 0);
-  ranks_[rank].published.store(ok ? 1 : -1, std::memory_order_release);
+  if (ok) std::memcpy(rank_record(rank).halo, &mine, sizeof(mine));
+  rank_record(rank).device.store(s_->opt.device);
+  rank_record(rank).pid.store((int)getpid());
+  rank_record(rank).fine.store(ok && halo_finegrained_ ? 1 : 0);
+  rank_record(rank).published.store(ok ? 1 : -1, std::memory_order_release);
   int rc = barrier();
   if (rc) return rc;
   // whom do I write to: the owners of my hosted agents' neighbours
@@ -577,11 +517,11 @@ int Exchange::setup_ipc(bool attempt) {
   for (int a = 0; a < R; ++a) peers.insert(dests_[a].begin(), dests_[a].end());
   for (int q : peers) {
     if (!ok) break;
-    if (ranks_[q].published.load(std::memory_order_acquire) != 1) {
+    if (rank_record(q).published.load(std::memory_order_acquire) != 1) {
       no("rank " + std::to_string(q) + " has no halo handle");
       break;
     }
-    const int pd = ranks_[q].device.load();
+    const int pd = rank_record(q).device.load();
     if (pd != s_->opt.device) {
       int can = 0;
       if (hipDeviceCanAccessPeer(&can, s_->opt.device, pd) == hipSuccess && can) {
@@ -592,7 +532,7 @@ int Exchange::setup_ipc(bool attempt) {
     }
     void *p = nullptr;
     hipIpcMemHandle_t h;
-    std::memcpy(&h, &ranks_[q].halo, sizeof(h));
+    std::memcpy(&h, rank_record(q).halo, sizeof(h));
     if (hipIpcOpenMemHandle(&p, h, hipIpcMemLazyEnablePeerAccess) != hipSuccess) {
       (void)hipGetLastError();
       no("hipIpcOpenMemHandle of rank " + std::to_string(q));
@@ -639,9 +579,7 @@ bool Exchange::probe_round(uint64_t seq, std::string *why) {
     if (needed_[a]) writers.insert(owner_[a]);
   }
   auto pattern = [&](int writer, int reader) { return 1e6 * (double)seq + 4096.0 * writer + 64.0 * reader; };
-  auto hflag_dev = [&](int reader, int writer) {
-    return (volatile uint64_t *)(dev_map_ + off_probe_flags_ + sizeof(ShmFlag) * ((size_t)reader * world + writer));
-  };
+  auto hflag_dev = [&](int reader, int writer) { return &lay_.probe_flag(dev_map_, reader, writer)->seq; };
   bool ok = true;
   auto no = [&](const std::string &m) {
     if (ok && why) *why = m;
@@ -652,7 +590,7 @@ bool Exchange::probe_round(uint64_t seq, std::string *why) {
   for (int q : peers) {
     if (!ok) break;
     double *dst = ipc ? peer_halo_[q] + probe_off_ + (size_t)rank * (kProbeDoubles + 8)
-                      : (double *)(dev_map_ + off_probe_stage_) + ((size_t)q * world + rank) * kProbeDoubles;
+                      : lay_.probe_stage(dev_map_, q, rank);
     uint64_t *dflag = ipc ? (uint64_t *)(peer_halo_[q] + probe_off_ + (size_t)rank * (kProbeDoubles + 8) + kProbeDoubles) : nullptr;
     if (ipc && !peer_halo_[q]) {
       no("no mapping of rank " + std::to_string(q) + "'s halo buffer");
@@ -664,25 +602,16 @@ bool Exchange::probe_round(uint64_t seq, std::string *why) {
   const double budget_s = 3.0;
   for (int p : writers) {
     if (!ok) break;
-    const ShmFlag *hf = (const ShmFlag *)((char *)map_ + off_probe_flags_) + ((size_t)rank * world + p);
-    if (!device_wait_) {  // the host waits for the flag, as wait_arr does
-      const auto w0 = Clock::now();
-      unsigned spins = 0;
-      while (hf->seq < seq) {
-        polite_spin(spins);
-        if ((spins & 255u) == 0 && (hdr_->failed.load() || since(w0) > budget_s)) {
-          no("the probe flag of rank " + std::to_string(p) + " never arrived (host wait)");
-          break;
-        }
-      }
-      std::atomic_thread_fence(std::memory_order_acquire);
-      if (!ok) break;
+    // the host waits for the flag, as wait_arr does; on its own budget, and giving up is this rank's vote only
+    if (!device_wait_ && slots().wait(budget_s).reached(lay_.probe_flag(map_, rank, p)->seq, seq)) {
+      no("the probe flag of rank " + std::to_string(p) + " never arrived (host wait)");
+      break;
     }
     const double *src = ipc ? halo_.p + probe_off_ + (size_t)p * (kProbeDoubles + 8)
-                            : (const double *)(dev_map_ + off_probe_stage_) + ((size_t)rank * world + p) * kProbeDoubles;
+                            : lay_.probe_stage(dev_map_, rank, p);
     const uint64_t *flag = ipc ? (const uint64_t *)(halo_.p + probe_off_ + (size_t)p * (kProbeDoubles + 8) + kProbeDoubles)
                                : (const uint64_t *)hflag_dev(rank, p);
-    int *res = (int *)(dev_map_ + off_probe_res_ + sizeof(ShmFlag) * ((size_t)rank * world + p));
+    int *res = (int *)lay_.probe_result(dev_map_, rank, p);
     hipLaunchKernelGGL(k_probe_wait, dim3(1), dim3(256), 0, st, src, flag, seq, (long long)(budget_s * 1e8),
                        device_wait_ ? 1 : 0, pattern(p, rank), res);
   }
@@ -705,7 +634,7 @@ bool Exchange::probe_round(uint64_t seq, std::string *why) {
   }
   for (int p : writers) {
     if (!ok) break;
-    const volatile int *res = (const volatile int *)((char *)map_ + off_probe_res_ + sizeof(ShmFlag) * ((size_t)rank * world + p));
+    const volatile int *res = (const volatile int *)lay_.probe_result(map_, rank, p);
     if (*res != 1)
       no("probe of rank " + std::to_string(p) + (*res == 2 ? ": the flag never arrived" : *res == 3 ? ": the 4 KB pattern arrived damaged" : ": no result"));
     *(volatile int *)res = 0;
@@ -730,12 +659,12 @@ int Exchange::link_check() {
     // the vote carries the form of the wait this rank used (device_wait_ is rank-local: only ranks with a GPU of their
     // own poll on the device), so that the step down below is taken from SHARED state and is the same on every rank
     const int vote = 2 * round + (device_wait_ ? 1 : 0);
-    ranks_[rank].probe.store(mine ? vote : -vote, std::memory_order_release);
+    rank_record(rank).probe.store(mine ? vote : -vote, std::memory_order_release);
     int rc = barrier(30.0);
     if (rc) return rc;
     bool all = true, any_device_wait = false;
     for (int q = 0; q < world; ++q) {
-      const int v = ranks_[q].probe.load(std::memory_order_acquire);
+      const int v = rank_record(q).probe.load(std::memory_order_acquire);
       all = all && v > 0 && v / 2 == round;
       any_device_wait = any_device_wait || ((v < 0 ? -v : v) & 1);
     }
@@ -777,6 +706,7 @@ int Exchange::post_arr(const int *agents, int count, int r, const double *arr) {
   const auto t0 = Clock::now();
   DCORA_HIP(hipSetDevice(s_->opt.device));
   const int R = R_;
+  const ExchangeSlots sl = slots();
   for (int i = 0; i < count; ++i) {
     const int a = agents[i];
     if (a < 0 || a >= R) return usage("post: agent out of range", DCORA_ERR_BAD_ARG);
@@ -784,26 +714,11 @@ int Exchange::post_arr(const int *agents, int count, int r, const double *arr) {
     const AgentCore &ag = s_->agent_core(a);
     if (!ag.hosted || dests_[a].empty() || ag.n_public_cols == 0) continue;
     const int parity = (int)(q & 1);
-    // Back-pressure: the slot of this parity was last written by post q - 2; every rank that reads it must have
-    // scattered that post before it is overwritten (the evaluation's heartbeat used to be the only thing between a
-    // producer running ahead and a torn read: ticks of one set posted again and again, the per-phase C ABI).
-    if (q > 2) {
-      const auto b0 = Clock::now();
-      for (int p : dests_[a]) {
-        const ShmFlag *cf = consumed_ + (size_t)p * R + a;
-        unsigned spins = 0;
-        while (cf->seq + 2 < q) {
-          polite_spin(spins);
-          if ((spins & 1023u) == 0) {
-            if (hdr_->failed.load()) return fail("another rank failed", DCORA_ERR_HIP);
-            if (since(b0) > exchange_timeout_s())
-              return fail("rank " + std::to_string(p) + " never read post " + std::to_string(q - 2) + " of agent " +
-                              std::to_string(a),
-                          DCORA_ERR_HIP);
-          }
-        }
-      }
-    }
+    // back-pressure (ExchangeSlots::consumed_wait): post q - 2, the slot's last, has been scattered by all its readers
+    int whom = 0;
+    if (const int rc = sl.consumed_wait(sl.wait(), a, q, dests_[a].data(), (int)dests_[a].size(), &whom))
+      return wait_failed(rc, "rank " + std::to_string(whom) + " never read post " + std::to_string(q - 2) +
+                                 " of agent " + std::to_string(a));
     PostDst dst{}, dflag{};
     if (mode == kExchangeIpc) {
       for (int p : dests_[a]) {
@@ -811,12 +726,12 @@ int Exchange::post_arr(const int *agents, int count, int r, const double *arr) {
         dflag.base[dflag.n++] = peer_halo_[p] + devflag_off_ + ((size_t)parity * R + a) * 8;
       }
     } else {
-      dst.base[dst.n++] = (double *)(dev_map_ + off_staged_) + halo_off(parity, a);
+      dst.base[dst.n++] = lay_.staged(dev_map_, parity, a);
     }
     const int ncols = ag.n_public_cols;
     const long N = (long)ncols * r;
     const int grid = (int)std::min<long>((N + kBlock - 1) / kBlock, 64);
-    volatile uint64_t *flag = (volatile uint64_t *)(dev_map_ + off_flags_ + sizeof(ShmFlag) * ((size_t)parity * R + a));
+    volatile uint64_t *flag = &lay_.flag(dev_map_, parity, a)->seq;
     hipLaunchKernelGGL(k_post_public, dim3(grid), dim3(kBlock), 0, s_->st, r, ncols, ag.public_cols.p, arr, dst,
                        dflag, arrive_.p + a, flag, q);
     bytes_posted += 8.0 * N * dst.n;
@@ -831,6 +746,7 @@ int Exchange::wait_arr(const int *agents, int count, int r, double *arr) {
   const auto t0 = Clock::now();
   DCORA_HIP(hipSetDevice(s_->opt.device));
   const int R = R_;
+  const ExchangeSlots sl = slots();
   for (int i = 0; i < count; ++i) {
     const int a = agents[i];
     if (a < 0 || a >= R) return usage("wait: agent out of range", DCORA_ERR_BAD_ARG);
@@ -838,31 +754,21 @@ int Exchange::wait_arr(const int *agents, int count, int r, double *arr) {
     if (!needed_[a] || ag.n_public_cols == 0) continue;
     const uint64_t want = seq_[a];
     const int parity = (int)(want & 1);
-    const ShmFlag *f = flags_ + (size_t)parity * R + a;
-    if (!device_wait_) {  // DCORA_EXCHANGE_WAIT=host: the host waits for the flag, the kernel below finds it set
-      unsigned spins = 0;
-      const auto w0 = Clock::now();
-      while (f->seq < want) {
-        polite_spin(spins);
-        if ((spins & 1023u) == 0) {
-          if (hdr_->failed.load()) return fail("another rank failed", DCORA_ERR_HIP);
-          if (since(w0) > exchange_timeout_s())
-            return fail("public poses of agent " + std::to_string(a) + " never arrived", DCORA_ERR_HIP);
-        }
-      }
-      std::atomic_thread_fence(std::memory_order_acquire);
-    }
+    // DCORA_EXCHANGE_WAIT=host: the host waits for the flag, the kernel below finds it set
+    if (!device_wait_)
+      if (const int rc = sl.flag_wait(sl.wait(), a, want))
+        return wait_failed(rc, "public poses of agent " + std::to_string(a) + " never arrived");
     const bool ipc = mode == kExchangeIpc;
-    const double *src = ipc ? halo_.p + halo_off(parity, a) : (const double *)(dev_map_ + off_staged_) + halo_off(parity, a);
+    const double *src = ipc ? halo_.p + halo_off(parity, a) : lay_.staged(dev_map_, parity, a);
     // the flag the kernel polls: next to the slot in this rank's halo buffer (stored by the producer over xGMI), or the
     // host-visible word when the poses are staged in the shared segment
     const uint64_t *dflag = ipc ? (const uint64_t *)(halo_.p + devflag_off_ + ((size_t)parity * R + a) * 8)
-                                : (const uint64_t *)(dev_map_ + off_flags_ + sizeof(ShmFlag) * ((size_t)parity * R + a));
+                                : (const uint64_t *)&lay_.flag(dev_map_, parity, a)->seq;
     const int ncols = ag.n_public_cols;
     const long N = (long)ncols * r;
     const int grid = (int)std::min<long>((N + kBlock - 1) / kBlock, 32);
-    uint64_t *cons = (uint64_t *)(dev_map_ + off_consumed_ + sizeof(ShmFlag) * ((size_t)rank * R + a));
-    uint32_t *failed = (uint32_t *)(dev_map_ + offsetof(ShmHeader, failed));
+    uint64_t *cons = (uint64_t *)&lay_.consumed(dev_map_, rank, a)->seq;
+    uint32_t *failed = (uint32_t *)&lay_.header(dev_map_)->failed;
     // updateNeighborStates: into the local mirror of X
     hipLaunchKernelGGL(k_wait_scatter, dim3(grid), dim3(kBlock), 0, s_->st, r, ncols, ag.public_cols.p, src,
                        arr, dflag, want, arrive2_.p + a, cons, failed);
@@ -875,16 +781,12 @@ int Exchange::wait_arr(const int *agents, int count, int r, double *arr) {
 // distributed form of the central evaluation (ref examples/MultiRobotExample.cpp:264-305): every rank evaluates the
 // agents it hosts against the neighbours' public poses it holds, publishes two scalars per agent, reads everybody's
 int Exchange::evaluate(double *cost2, double *gradnorm, double *block_norms, int *next_selected) {
-  const int R = R_;
   int rc = s_->phase_evaluate_dev(evalbuf_.p);
   if (rc) return rc;
   const uint64_t want = ++eval_seq_;
-  const int parity = (int)(want & 1);
-  const size_t per_parity = (size_t)R + world;
-  ShmEval *slots_dev = (ShmEval *)(dev_map_ + off_evals_) + (size_t)parity * per_parity;
   if (n_hosted_)
-    hipLaunchKernelGGL(k_eval_publish, dim3(1), dim3(64), 0, s_->st, n_hosted_, hosted_list_.p, evalbuf_.p, slots_dev,
-                       want);
+    hipLaunchKernelGGL(k_eval_publish, dim3(1), dim3(64), 0, s_->st, n_hosted_, hosted_list_.p, evalbuf_.p,
+                       lay_.eval(dev_map_, (int)(want & 1), 0), want);
   DCORA_HIP(hipGetLastError());
   // the team's statuses of the round (rbcd_iterate): read once the evaluation is enqueued behind the agent's update, so
   // that the hosting rank's queue never drains while its host waits for its own kernel's word
@@ -894,51 +796,16 @@ int Exchange::evaluate(double *cost2, double *gradnorm, double *block_norms, int
     rc = team_collect(due.data(), (int)due.size());
     if (rc) return rc;
   }
-  const auto t0 = Clock::now();
-  ShmEval *sl = evals_ + (size_t)parity * per_parity;
-  // Heartbeat of this rank: every rank -- also one that hosts no agent and therefore publishes nothing -- says that
-  // it has entered evaluation `want`, and nobody leaves it before all have.  A rank can then never be lapped: the
-  // slot of parity `want` is overwritten at evaluation want + 2, which every writer enters only after all ranks have
-  // entered want + 1, i.e. after they have finished reading `want`.
-  std::atomic_thread_fence(std::memory_order_release);
-  sl[R + rank].seq = want;
-  for (int q = 0; q < world; ++q) {
-    unsigned spins = 0;
-    while (sl[R + q].seq < want) {
-      polite_spin(spins);
-      if ((spins & 1023u) == 0) {
-        if (hdr_->failed.load()) return fail("another rank failed", DCORA_ERR_HIP);
-        if (since(t0) > exchange_timeout_s()) return fail("rank " + std::to_string(q) + " never entered the evaluation", DCORA_ERR_HIP);
-      }
-    }
-  }
-  double g2 = 0, c2 = 0, best = -1;
-  int arg = 0;
-  for (int a = 0; a < R; ++a) {
-    unsigned spins = 0;
-    while (sl[a].seq < want) {
-      polite_spin(spins);
-      if ((spins & 1023u) == 0) {
-        if (hdr_->failed.load()) return fail("another rank failed", DCORA_ERR_HIP);
-        if (since(t0) > exchange_timeout_s()) return fail("evaluation of agent " + std::to_string(a) + " never arrived", DCORA_ERR_HIP);
-      }
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-    const double ga = sl[a].g2, xa = sl[a].xeg;
-    const double nb = std::sqrt(ga);
-    if (block_norms) block_norms[a] = nb;
-    g2 += ga;
-    c2 += xa;  // 2 f = sum_b <X_b, X_b Q_bb + G_b>
-    if (nb > best) {
-      best = nb;
-      arg = a;
-    }
-  }
-  eval_wait_s += since(t0);
+  // the heartbeat and the gather (ExchangeSlots, where the argument for the heartbeat stands), on one clock
+  const ExchangeSlots sl = slots();
+  const Wait w = sl.wait();
+  int whom = 0;
+  if ((rc = sl.heartbeat(w, want, &whom)))
+    return wait_failed(rc, "rank " + std::to_string(whom) + " never entered the evaluation");
+  if ((rc = sl.eval_gather(w, want, cost2, gradnorm, block_norms, next_selected, &whom)))
+    return wait_failed(rc, "evaluation of agent " + std::to_string(whom) + " never arrived");
+  eval_wait_s += since(w.t0);
   ++evals;
-  if (cost2) *cost2 = c2;
-  if (gradnorm) *gradnorm = std::sqrt(g2);
-  if (next_selected) *next_selected = arg;
   return DCORA_OK;
 }
 
@@ -994,10 +861,10 @@ int Exchange::rbcd_tick(const int *set, int count, int allow_adjacent) {
 
 // ---- the team protocol across the ranks (exchange.h) ----------------------------------------------------------------
 void Exchange::team_snapshot_weights() {
-  if (!w_doubles_) return;
+  if (!lay_.w_doubles) return;
   std::atomic_thread_fence(std::memory_order_acquire);
-  job_w_.resize(w_doubles_);
-  std::memcpy(job_w_.data(), (const char *)map_ + off_w_, sizeof(double) * w_doubles_);
+  job_w_.resize(lay_.w_doubles);
+  std::memcpy(job_w_.data(), lay_.weights(map_), sizeof(double) * lay_.w_doubles);
 }
 
 // The job's weights are complete in the area whenever no update is under way; the closing barrier keeps a rank that
@@ -1006,60 +873,44 @@ int Exchange::team_enable(const dcora_team_params &p) {
   if (!pose_)
     return usage("team_enable: the team protocol serves pose-graph sessions; a range-aided job has none",
                  DCORA_ERR_UNSUPPORTED);
-  if (pose_->robust && w_doubles_ != pose_->robust->meas.size())
+  if (pose_->robust && lay_.w_doubles != pose_->robust->meas.size())
     return usage("team_enable: a robust session needs the exchange it was created with (dcora_rbcd_create_robust_ranks)",
                  DCORA_ERR_UNSUPPORTED);
   team_snapshot_weights();
-  const int rc = pose_->team_enable_ranked(p, status_, (ShmStatus *)(dev_map_ + off_status_),
-                                           w_doubles_ ? job_w_.data() : nullptr);
+  const int rc = pose_->team_enable_ranked(p, lay_.status(map_, 0, 0), lay_.status(dev_map_, 0, 0),
+                                           lay_.w_doubles ? job_w_.data() : nullptr);
   if (rc) return rc;
   return barrier();
-}
-
-TeamSlots Exchange::team_slots() const {
-  TeamSlots t;
-  t.status = status_;
-  t.read = status_read_;
-  t.failed = &hdr_->failed;
-  t.rank = rank;
-  t.world = world;
-  t.R = R_;
-  t.timeout_s = exchange_timeout_s();
-  return t;
-}
-
-int Exchange::team_wait_failed(int what, const std::string &who) {
-  return fail(what == kTeamWaitPeerFailed ? std::string("another rank failed") : who, DCORA_ERR_HIP);
 }
 
 // optimisation q = seq + 1 of a hosted agent will store into slot [q & 1]: every rank has read q - 2 out of it
 int Exchange::team_clear_to_write(const int *agents, int count) {
   const TeamState &t = *pose_->team;
-  const TeamSlots slots = team_slots();
+  const ExchangeSlots sl = slots();
   for (int i = 0; i < count; ++i) {
     const int a = agents[i];
     if (a < 0 || a >= R_ || !s_->agent_core(a).hosted) continue;
     const uint64_t q = t.seq[(size_t)a] + 1;
     if (q <= 2) continue;
     int whom = 0;
-    if (const int rc = slots.read_wait(a, q - 2, &whom))
-      return team_wait_failed(rc, "rank " + std::to_string(whom) + " never read status " + std::to_string(q - 2) +
-                                      " of agent " + std::to_string(a));
+    if (const int rc = sl.status_read_wait(a, q - 2, &whom))
+      return wait_failed(rc, "rank " + std::to_string(whom) + " never read status " + std::to_string(q - 2) +
+                                 " of agent " + std::to_string(a));
   }
   return DCORA_OK;
 }
 
 int Exchange::team_collect(const int *agents, int count) {
   const TeamState &t = *pose_->team;
-  const TeamSlots slots = team_slots();
+  const ExchangeSlots sl = slots();
   for (int i = 0; i < count; ++i) {
     const int a = agents[i];
     const uint64_t q = t.seq[(size_t)a];
-    if (const int rc = slots.status_wait(q, a))
-      return team_wait_failed(rc, "the status of agent " + std::to_string(a) + " never arrived");
-    const ShmStatus *slot = slots.slot(q, a);
+    if (const int rc = sl.status_wait(q, a))
+      return wait_failed(rc, "the status of agent " + std::to_string(a) + " never arrived");
+    const ShmStatus *slot = sl.status_slot(q, a);
     pose_->team_settle_published(a, slot->success != 0, slot->rel);
-    slots.mark_read(q, a);
+    sl.mark_status_read(q, a);
   }
   return DCORA_OK;
 }
@@ -1122,11 +973,11 @@ int Exchange::set_X(const double *Xh) {
 
 // every rank's hosted blocks -> the shared segment -> every rank's copy of the whole X
 int Exchange::gather_X(double *Xh) {
-  int rc = s_->x_stage_hosted(xarea_);
+  int rc = s_->x_stage_hosted(lay_.x(map_));
   if (rc) return rc;
   rc = barrier();
   if (rc) return rc;
-  std::memcpy(Xh, xarea_, sizeof(double) * (size_t)s_->r * (size_t)s_->num_cols());
+  std::memcpy(Xh, lay_.x(map_), sizeof(double) * (size_t)s_->r * (size_t)s_->num_cols());
   return barrier();
 }
 
@@ -1136,11 +987,11 @@ int Exchange::gather_X(double *Xh) {
 // both of its ranks from bitwise-equal mirror columns.  The weights area is written by the kernel while no rank reads
 // it: get_weights ends with a barrier, and the allreduce below is passed only once every rank's stores have landed.
 int Exchange::update_weights(RbcdSession &s, bool reset_to_initial, int counts[3]) {
-  if (!s.robust || !s.robust->ranked || &s != s_ || w_doubles_ != s.robust->meas.size())
+  if (!s.robust || !s.robust->ranked || &s != s_ || lay_.w_doubles != s.robust->meas.size())
     return usage("update_weights: the exchange's session is not a ranked robust session", DCORA_ERR_BAD_ARG);
   std::vector<double> w;
   double cnt[3] = {0, 0, 0};
-  int rc = s.compute_weights((double *)(dev_map_ + off_w_), &w, cnt);
+  int rc = s.compute_weights(lay_.weights(dev_map_), &w, cnt);
   if (rc) return fail(std::string("update_weights: ") + dcora_last_error(), rc);
   rc = allreduce_sum(cnt, 3);
   if (rc) return rc;
@@ -1169,13 +1020,13 @@ int Exchange::update_weights(RbcdSession &s, bool reset_to_initial, int counts[3
 // or not finite, or nonzero where creation had 0): a refusal is the same on every rank and leaves the job as it was,
 // with the exchange usable.  The owners then store their edges' weights into the area.
 int Exchange::set_weights(RbcdSession &s, const double *w) {
-  if (!s.robust || !s.robust->ranked || &s != s_ || w_doubles_ != s.robust->meas.size())
+  if (!s.robust || !s.robust->ranked || &s != s_ || lay_.w_doubles != s.robust->meas.size())
     return usage("set_weights: the exchange's session is not a ranked robust session", DCORA_ERR_BAD_ARG);
   // (the team's counts are refreshed from the job's weights inside: every rank is handed all m of them)
   std::vector<double> before;
   if (team_on()) {
     before = job_w_;
-    std::copy(w, w + w_doubles_, job_w_.begin());
+    std::copy(w, w + lay_.w_doubles, job_w_.begin());
   }
   const int rc = s.set_weights(w);
   if (rc && team_on()) std::copy(before.begin(), before.end(), job_w_.begin());
@@ -1187,8 +1038,8 @@ int Exchange::set_weights(RbcdSession &s, const double *w) {
 // the weights the session holds for the edges this rank owns into the area (host stores), then a barrier
 int Exchange::publish_weights(const RbcdSession &s) {
   const RobustSession &rs = *s.robust;
-  double *area = (double *)((char *)map_ + off_w_);
-  for (size_t e = 0; e < rs.meas.size() && e < w_doubles_; ++e) {
+  double *area = lay_.weights(map_);
+  for (size_t e = 0; e < rs.meas.size() && e < lay_.w_doubles; ++e) {
     const PoseMeas &q = rs.meas[e];
     if (owner_[(size_t)s.P.robot_of(q.p1)] == rank) area[e] = q.weight;
   }
@@ -1197,9 +1048,9 @@ int Exchange::publish_weights(const RbcdSession &s) {
 }
 
 int Exchange::get_weights(double *w) {
-  if (w_doubles_ == 0) return usage("get_weights: the exchange was not created for a robust job", DCORA_ERR_BAD_ARG);
+  if (lay_.w_doubles == 0) return usage("get_weights: the exchange was not created for a robust job", DCORA_ERR_BAD_ARG);
   std::atomic_thread_fence(std::memory_order_acquire);
-  std::memcpy(w, (const char *)map_ + off_w_, sizeof(double) * w_doubles_);
+  std::memcpy(w, lay_.weights(map_), sizeof(double) * lay_.w_doubles);
   return barrier();  // nobody writes the area again before every rank has read it
 }
 
@@ -1216,99 +1067,38 @@ int Exchange::debug_leave_stale(const char *job_name, int world_, int R) {
   return DCORA_OK;
 }
 
-// The host half of the protocol on its own (no device): bootstrap through the segment, barriers, and `rounds` rounds
-// of post -> wait -> evaluation all-gather in which host stores stand in for the device's (same slots, same parity
-// double-buffering, same sequence numbers).  checksum is identical on every rank.
+// The host half of the protocol on its own (no device): the bootstrap through the segment, then exchange_rehearsal
+// (exchange_slots.h) -- `rounds` rounds of back-pressure -> post -> flag wait -> evaluation heartbeat and gather -> sum
+// over the ranks, the steps post_arr, wait_arr, evaluate and allreduce_sum make, with host stores in the device's place.
+// checksum is identical on every rank.
 int Exchange::host_selftest(const char *job_name, int rank_, int world_, int R, int rounds, double *checksum) {
-  rank = rank_;
-  world = world_;
-  R_ = R;
-  if (world < 1 || rank < 0 || rank >= world || world > kMaxRanks || R < 1 || R > kMaxAgents || rounds < 1)
-    return fail("host selftest: bad arguments", DCORA_ERR_BAD_ARG);
-  slot_ = 16;
-  int rc = map_segment(job_name, 16);
+  int rc = selftest_bootstrap(job_name, rank_, world_, R, rounds >= 1);
   if (rc) return rc;
-  rc = barrier();
-  if (rc) return rc;
-  if (rank == 0) shm_unlink(name_.c_str());
-  const int per = (R + world - 1) / world;
-  double sum = 0;
-  for (int q = 1; q <= rounds; ++q) {
-    const int parity = q & 1;
-    for (int a = 0; a < R; ++a) {
-      if (a / per != rank) continue;
-      double *dst = staged_ + ((size_t)parity * R + a) * slot_;
-      for (size_t i = 0; i < slot_; ++i) dst[i] = 1000.0 * q + 16.0 * a + (double)i;
-      std::atomic_thread_fence(std::memory_order_release);
-      flags_[(size_t)parity * R + a].seq = (uint64_t)q;
-    }
-    const auto t0 = Clock::now();
-    for (int a = 0; a < R; ++a) {
-      const ShmFlag *f = flags_ + (size_t)parity * R + a;
-      unsigned spins = 0;
-      while (f->seq < (uint64_t)q) {
-        if ((++spins & 1023u) == 0) {
-          if (hdr_->failed.load()) return fail("another rank failed", DCORA_ERR_HIP);
-          if (since(t0) > exchange_timeout_s()) return fail("host selftest: a post never arrived", DCORA_ERR_HIP);
-          sched_yield();
-        }
-      }
-      std::atomic_thread_fence(std::memory_order_acquire);
-      const double *src = staged_ + ((size_t)parity * R + a) * slot_;
-      for (size_t i = 0; i < slot_; ++i)
-        if (src[i] != 1000.0 * q + 16.0 * a + (double)i) return fail("host selftest: payload mismatch", DCORA_ERR_HIP);
-    }
-    const size_t per_parity = (size_t)R + world;
-    for (int a = 0; a < R; ++a) {
-      if (a / per != rank) continue;
-      ShmEval *e = evals_ + (size_t)parity * per_parity + a;
-      e->g2 = q + 0.5 * a;
-      e->xeg = q * 0.25 - a;
-      std::atomic_thread_fence(std::memory_order_release);
-      e->seq = (uint64_t)q;
-    }
-    {  // the rank's heartbeat (see Exchange::evaluate): a rank without agents must not be lapped either
-      ShmEval *hb = evals_ + (size_t)parity * per_parity + R;
-      std::atomic_thread_fence(std::memory_order_release);
-      hb[rank].seq = (uint64_t)q;
-      for (int p2 = 0; p2 < world; ++p2) {
-        unsigned spins = 0;
-        while (hb[p2].seq < (uint64_t)q) {
-          if ((++spins & 1023u) == 0) {
-            if (hdr_->failed.load()) return fail("another rank failed", DCORA_ERR_HIP);
-            if (since(t0) > exchange_timeout_s()) return fail("host selftest: a heartbeat never arrived", DCORA_ERR_HIP);
-            sched_yield();
-          }
-        }
-      }
-    }
-    for (int a = 0; a < R; ++a) {
-      const ShmEval *e = evals_ + (size_t)parity * per_parity + a;
-      unsigned spins = 0;
-      while (e->seq < (uint64_t)q) {
-        if ((++spins & 1023u) == 0) {
-          if (hdr_->failed.load()) return fail("another rank failed", DCORA_ERR_HIP);
-          if (since(t0) > exchange_timeout_s()) return fail("host selftest: an evaluation never arrived", DCORA_ERR_HIP);
-          sched_yield();
-        }
-      }
-      std::atomic_thread_fence(std::memory_order_acquire);
-      sum += e->g2 * (a + 1) + e->xeg;
-    }
-  }
-  if (checksum) *checksum = sum;
+  const char *what = "";
+  rc = exchange_rehearsal(slots(), (R + world - 1) / world, rounds, checksum, &what);
+  if (rc) return wait_failed(rc, what);
   return barrier();
 }
 
-// The team's half of the rehearsal (dcora_hip.h, dcora_exchange_host_selftest_team): team_rehearsal (team_slots.h) on
-// this segment's status area -- the slots, sequence words, read words and waits of team_clear_to_write / team_collect,
-// with host stores where the ranked k_rel_change stores -- behind the bootstrap and the heartbeat of host_selftest.
+// The team's half of the rehearsal (dcora_hip.h, dcora_exchange_host_selftest_team): team_rehearsal (exchange_slots.h)
+// on this segment's status area -- the slots, sequence words, read words and waits of team_clear_to_write /
+// team_collect, with host stores where the ranked k_rel_change stores -- behind the same bootstrap and the
+// evaluation's heartbeat.
 int Exchange::host_selftest_team(const char *job_name, int rank_, int world_, int R, int rounds, int skew_us,
                                  double *checksum) {
+  int rc = selftest_bootstrap(job_name, rank_, world_, R, rounds >= 1 && skew_us >= 0);
+  if (rc) return rc;
+  rc = team_rehearsal(slots(), (R + world - 1) / world, rounds, skew_us, checksum);
+  if (rc) return wait_failed(rc, "host selftest: a status, a read word or a heartbeat never arrived");
+  return barrier();
+}
+
+// what both rehearsals share with init: the segment of a job of this shape, every rank attached, the name removed
+int Exchange::selftest_bootstrap(const char *job_name, int rank_, int world_, int R, bool args_ok) {
   rank = rank_;
   world = world_;
   R_ = R;
-  if (world < 1 || rank < 0 || rank >= world || world > kMaxRanks || R < 1 || R > kMaxAgents || rounds < 1 || skew_us < 0)
+  if (world < 1 || rank < 0 || rank >= world || world > kMaxRanks || R < 1 || R > kMaxAgents || !args_ok)
     return fail("host selftest: bad arguments", DCORA_ERR_BAD_ARG);
   slot_ = 16;
   int rc = map_segment(job_name, 16);
@@ -1316,29 +1106,7 @@ int Exchange::host_selftest_team(const char *job_name, int rank_, int world_, in
   rc = barrier();
   if (rc) return rc;
   if (rank == 0) shm_unlink(name_.c_str());
-  const int per = (R + world - 1) / world;
-  uint64_t beats = 0;
-  auto heartbeat = [&]() -> int {  // the evaluation's (Exchange::evaluate)
-    const uint64_t want = ++beats;
-    ShmEval *hb = evals_ + (size_t)(want & 1) * ((size_t)R + world) + R;
-    const auto t0 = Clock::now();
-    std::atomic_thread_fence(std::memory_order_release);
-    hb[rank].seq = want;
-    for (int p2 = 0; p2 < world; ++p2) {
-      unsigned spins = 0;
-      while (hb[p2].seq < want) {
-        polite_spin(spins);
-        if ((spins & 1023u) == 0) {
-          if (hdr_->failed.load()) return kTeamWaitPeerFailed;
-          if (since(t0) > exchange_timeout_s()) return kTeamWaitTimeout;
-        }
-      }
-    }
-    return kTeamWaitOk;
-  };
-  rc = team_rehearsal(team_slots(), per, rounds, skew_us, heartbeat, checksum);
-  if (rc) return team_wait_failed(rc, "host selftest: a status, a read word or a heartbeat never arrived");
-  return barrier();
+  return DCORA_OK;
 }
 
 }  // namespace dcora

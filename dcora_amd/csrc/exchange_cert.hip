@@ -1,9 +1,6 @@
 // Certification across the ranks of an exchange (SURVEY 8(e) "Collective": row-block S v with the halo exchange of the
 // RBCD loop, scalar all-reduces for the Lanczos recurrences; ref src/DCORA_utils.cpp:1713-1735, 1809-1896).
-#include <sched.h>
-
 #include <atomic>
-#include <chrono>
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -16,9 +13,6 @@
 namespace dcora {
 
 namespace {
-
-using Clock = std::chrono::steady_clock;
-inline double since(Clock::time_point t0) { return std::chrono::duration<double>(Clock::now() - t0).count(); }
 
 // w += eta v - Lambda v on the variables of one agent, r = 1 vectors in the agent's ordering: Lambda is block diagonal
 // -- a d x d block (column-major) on the d rotation columns of every pose, a scalar on every unit sphere, nothing on
@@ -70,32 +64,10 @@ struct CertBlock {
 int Exchange::allreduce_sum(double *vals, int count) {
   if (count < 0 || count > 31) return usage("allreduce_sum: at most 31 values", DCORA_ERR_BAD_ARG);
   if (world == 1) return DCORA_OK;
-  const uint64_t q = ++red_seq_;
-  ShmRed *slots = red_ + (size_t)(q & 1) * world;
-  for (int i = 0; i < count; ++i) slots[rank].vals[i] = vals[i];
-  std::atomic_thread_fence(std::memory_order_release);
-  slots[rank].seq = q;
-  const auto t0 = Clock::now();
-  double acc[31] = {0};
-  for (int p = 0; p < world; ++p) {
-    unsigned spins = 0;
-    while (slots[p].seq < q) {
-      ++spins;
-      if (spins < 4096u) {
-        __builtin_ia32_pause();
-      } else {
-        sched_yield();
-        if ((spins & 255u) == 0) {
-          if (hdr_->failed.load()) return fail("another rank failed", DCORA_ERR_HIP);
-          if (since(t0) > exchange_timeout_s()) return fail("rank " + std::to_string(p) + " never joined a sum", DCORA_ERR_HIP);
-        }
-      }
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-    for (int i = 0; i < count; ++i) acc[i] += slots[p].vals[i];
-  }
-  for (int i = 0; i < count; ++i) vals[i] = acc[i];
-  return DCORA_OK;
+  const ExchangeSlots sl = slots();
+  int whom = 0;
+  const int rc = sl.allreduce_sum(sl.wait(), ++red_seq_, vals, count, &whom);
+  return rc ? wait_failed(rc, "rank " + std::to_string(whom) + " never joined a sum") : DCORA_OK;
 }
 
 int Exchange::certify(const HostCsr *Qglobal, double eta, int *certified, double *theta, double *lambda_min, double *v,
@@ -250,10 +222,10 @@ int Exchange::certify(const HostCsr *Qglobal, double eta, int *certified, double
     // the spectrum-shifted run; its start vector comes from the first row of M, which rank 0 holds
     std::vector<double> x0((size_t)ktot, 0.0);
     if (rank == 0) x0 = min_eig_second_start(M, seed);
-    std::memcpy(xarea_, x0.data(), rank == 0 ? sizeof(double) * ktot : 0);
+    std::memcpy(lay_.x(map_), x0.data(), rank == 0 ? sizeof(double) * ktot : 0);
     rc = barrier();
     if (rc) return rc;
-    std::memcpy(x0.data(), xarea_, sizeof(double) * ktot);
+    std::memcpy(x0.data(), lay_.x(map_), sizeof(double) * ktot);
     rc = barrier();
     if (rc) return rc;
     LanczosResult sh;
@@ -284,18 +256,18 @@ int Exchange::certify(const HostCsr *Qglobal, double eta, int *certified, double
     if (rc) return rc;
     if (out2[1] != 0) return fail("certify: the minimum eigenpair could not be computed", (int)out2[1]);
     res.lambda = out2[0];
-    if (rank == 0) std::memcpy(xarea_, vfull.data(), sizeof(double) * ktot);
+    if (rank == 0) std::memcpy(lay_.x(map_), vfull.data(), sizeof(double) * ktot);
     rc = barrier();
     if (rc) return rc;
-    std::memcpy(vfull.data(), xarea_, sizeof(double) * ktot);
+    std::memcpy(vfull.data(), lay_.x(map_), sizeof(double) * ktot);
     rc = barrier();
     if (rc) return rc;
   } else {
     if (distributed) *distributed = 1;
-    whole_of_local(res.v.data(), xarea_);  // every rank its own rows of the shared vector
+    whole_of_local(res.v.data(), lay_.x(map_));  // every rank its own rows of the shared vector
     rc = barrier();
     if (rc) return rc;
-    std::memcpy(vfull.data(), xarea_, sizeof(double) * ktot);
+    std::memcpy(vfull.data(), lay_.x(map_), sizeof(double) * ktot);
     rc = barrier();
     if (rc) return rc;
   }

@@ -15,7 +15,7 @@
 #include <climits>
 #include <vector>
 
-#include "team_slots.h"
+#include "exchange_slots.h"
 
 namespace dcora {
 
@@ -105,7 +105,6 @@ struct SolverCtl {
 };
 // how a tCG run ended (SolverCtl::tcg_status): ROPTLIB's tCGstatusSet, in its order
 enum TcgStatus : int { TR_NEGCURVTURE = 0, TR_EXCREGION = 1, TR_LCON = 2, TR_SCON = 3, TR_MAXITER = 4 };
-constexpr int kMaxAgents = 64;
 // results of one evaluation pass, in host-mapped memory
 struct EvalOut {
   double cost2, gradnorm;

@@ -240,10 +240,11 @@ def _selftest_rank(rank, world, job, R, rounds, tmpdir):
 
 @pytest.mark.parametrize("world,R", [(2, 5), (3, 8), (4, 5)])
 def test_exchange_host_protocol_between_processes(built, tmp_path, world, R):
-    """dcora_exchange_host_selftest in `world` processes: the bootstrap through the POSIX shared segment, the barriers,
-    the per-agent flag words with their parity double-buffering and the evaluation all-gather are the code the GPU
-    ranks run (dcora_amd/csrc/exchange.hip); host stores stand in for the device's.  (4 ranks / 5 agents: a rank
-    without agents takes part in every barrier and wait.)"""
+    """dcora_exchange_host_selftest in `world` processes: the bootstrap through the POSIX shared segment and the barriers
+    are Exchange's own, and every round goes through the host steps that post_arr, wait_arr, evaluate and allreduce_sum
+    call (dcora_amd/csrc/exchange_slots.h: the back-pressure on the consumed words, the flag wait with its parity
+    double-buffering, the evaluation's heartbeat and gather, the sum over the ranks); host stores stand in for the
+    device's.  (4 ranks / 5 agents: a rank without agents takes part in every barrier and wait.)"""
     import uuid
     import torch.multiprocessing as mp
     rounds = 50

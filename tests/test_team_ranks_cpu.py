@@ -1,6 +1,6 @@
 """The team protocol's transport between the ranks of a job, host half (dcora_exchange_host_selftest_team; no GPU): the
 status slots of the shared segment, their sequence and read words and the bounded waits are the code the GPU ranks run
-(dcora_amd/csrc/team_slots.h, exchange.hip), host stores stand in for the ranked k_rel_change.  Real processes, ranks
+(dcora_amd/csrc/exchange_slots.h, exchange.hip), host stores stand in for the ranked k_rel_change.  Real processes, ranks
 that drift apart, a rank without agents, a rank that dies; and the same header under ASan + UBSan as a plain program."""
 import os
 import subprocess
@@ -20,7 +20,7 @@ R, ROUNDS = 5, 60
 
 
 def script_checksum(R, rounds):
-    """the rehearsal's script (team_slots.h, team_rehearsal) through the rules as tests/team_rules_ref.py states them,
+    """the rehearsal's script (exchange_slots.h, team_rehearsal) through the rules as tests/team_rules_ref.py states them,
     folded in the library's order"""
     p = types.SimpleNamespace(max_num_iters=1 << 30, rel_change_tol=5e-3, robust_opt_num_weight_updates=3,
                               robust_opt_num_resets=0, robust_opt_inner_iters=7, robust_opt_min_convergence_ratio=0.8)
@@ -110,7 +110,7 @@ def test_a_rank_that_exits_mid_run_takes_the_others_out(built, tmp_path):
 
 
 def test_team_transport_under_asan_ubsan(tmp_path):
-    """team_slots.h -- slots, read words, waits, the rehearsal -- compiled with a program of its own under ASan + UBSan
+    """exchange_slots.h -- slots, read words, waits, the rehearsal -- compiled with a program of its own under ASan + UBSan
     and run as a plain executable in 3 processes: no report, every rank's checksum the scripted one"""
     exe = str(tmp_path / "san_host_team")
     cmd = ["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",

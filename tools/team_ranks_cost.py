@@ -3,11 +3,12 @@ one GPU, every rank holding two jobs -- the team off and on (Exchange.enable_tea
 k_rel_change behind the selected agent's update, on every rank one bounded spin on the agent's status slot before the
 evaluation) -- timed in alternating windows of RBCD iterations from the same start point, after a warm-up of both.
 
-    python tools/team_ranks_cost.py [--windows 5] [--iters 300]
+    python tools/team_ranks_cost.py [--windows 5] [--iters 300] [--lib PATH/libdcora_hip.so]
 
 Starts one process per rank (itself with --rank) and prints rank 0's JSON line: iterations per second of every window,
 their medians and spreads, the on/off gap.  The spread of the `off` windows among themselves is the noise floor the
-gap is read against; tools/team_status_cost.py gives the single-process figure (one launch)."""
+gap is read against; tools/team_status_cost.py gives the single-process figure (one launch).  --lib measures another
+build of the library (tools/lib_window.py's use_library): a process loads one, so the caller alternates runs."""
 import argparse
 import json
 import os
@@ -32,6 +33,9 @@ def spread(v):
 
 def rank_main(a):
     import numpy as np
+    if a.lib:
+        from lib_window import use_library
+        use_library(a.lib)
     import common
     import dcora_amd as da
     from dcora_amd import driver
@@ -69,7 +73,7 @@ def rank_main(a):
         so, sn = spread(rates["off"]), spread(rates["on"])
         us_off, us_on = 1e6 / so["median"], 1e6 / sn["median"]
         info = jobs["on"][1].info()
-        print(json.dumps({"case": "sphere2500/5 agents/r=5, 2 ranks on one GPU", "transport": info["transport"],
+        print(json.dumps({"lib": a.lib or "built", "case": "sphere2500/5 agents/r=5, 2 ranks on one GPU", "transport": info["transport"],
                           "wait": info["wait"], "iters_per_window": a.iters, "windows": a.windows,
                           "iters_per_s_off": rates["off"], "iters_per_s_on": rates["on"], "off": so, "on": sn,
                           "us_per_iter_off": us_off, "us_per_iter_on": us_on, "gap_us_per_iter": us_on - us_off,
@@ -81,19 +85,12 @@ def rank_main(a):
         s.close()
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--windows", type=int, default=5)
-    ap.add_argument("--iters", type=int, default=300)
-    ap.add_argument("--rank", type=int, default=-1)
-    ap.add_argument("--job", default="")
-    a = ap.parse_args()
-    if a.rank >= 0:
-        return rank_main(a)
+def launch_ranks(script, args):
+    """one process per rank of `script` with `args`, --rank and a fresh --job (tools/cert_ranks_timing.py shares this)"""
     job = "tc%s" % uuid.uuid4().hex[:10]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    procs = [subprocess.Popen([sys.executable, os.path.abspath(__file__), "--windows", str(a.windows), "--iters",
-                               str(a.iters), "--rank", str(k), "--job", job], env=env) for k in range(WORLD)]
+    procs = [subprocess.Popen([sys.executable, os.path.abspath(script)] + args + ["--rank", str(k), "--job", job],
+                              env=env) for k in range(WORLD)]
     rcs = []
     for p in procs:
         try:
@@ -104,6 +101,19 @@ def main():
             raise
     if any(rcs):
         raise SystemExit("a rank failed: %r" % rcs)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--windows", type=int, default=5)
+    ap.add_argument("--iters", type=int, default=300)
+    ap.add_argument("--lib", default=None)
+    ap.add_argument("--rank", type=int, default=-1)
+    ap.add_argument("--job", default="")
+    a = ap.parse_args()
+    if a.rank >= 0:
+        return rank_main(a)
+    launch_ranks(__file__, ["--windows", str(a.windows), "--iters", str(a.iters)] + (["--lib", a.lib] if a.lib else []))
 
 
 if __name__ == "__main__":
