@@ -15,27 +15,13 @@
 
 #include "device_problem.h"
 #include "sparse_precond.h"
+#include "dense_tiles.h"
 
 namespace dcora {
 
 namespace {
 
-constexpr int NB = kCholNb;
 constexpr int kEaRows = 8;  // rows of a child's Schur complement per workgroup of the extend-add
-
-// one piece of a batched inversion (blockIdx.z): offsets into the arrays the kernel is given
-struct InvJob {
-  int c, m;
-  long long l11, f;    // L11 inside the front arena, leading dimension of the front
-  long long yt, tinv;  // (L11^-1)^T (c x c) and the inverses of its 64 x 64 diagonal blocks
-  long long pk, mt;    // the packed panel; M = L11^-T L11^-1 (c x c) or -1
-};
-
-struct PieceDev {
-  long long off;
-  int c, m;
-  int parent, rel_off;
-};
 
 // F[dest[p]] = v[p] for the entries of the lower triangle
 __global__ __launch_bounds__(256) void k_chol_scatter(long long nnz, const long long *__restrict__ dest,
@@ -117,7 +103,6 @@ __device__ __forceinline__ double fast_rsqrt(double d) {
 // B(k, j) = fb(k, j); at step s lane l feeds A(l & 15, 4 s + (l >> 4)) and B(4 s + (l >> 4), l & 15) and it receives
 // D((l >> 4) + 4 v, l & 15) in d[v].  A result can be the B operand of the next product as it stands: step s wants rows
 // 4 s + (l >> 4) of B, which is d[s].
-typedef double v4f64 __attribute__((ext_vector_type(4)));
 template <class FA, class FB>
 __device__ __forceinline__ v4f64 mma16(v4f64 d, FA fa, FB fb) {
   const int lane = threadIdx.x & 63, lo = lane & 15, hi = lane >> 4;
@@ -295,87 +280,9 @@ __global__ __launch_bounds__(256) void k_chol_potrf(const PieceDev *__restrict__
   for (int e = tid; e < NB * NB; e += 256) O[e] = Li[e >> 6][e & 63];
 }
 
-
-
-// ---- the 64 x 64 x 64 product of two LDS tiles, As[k][i] and Bs[k][j]: acc(i, j) += sum_k As[k][i] Bs[k][j] ----
-// MMA = false: 4 x 4 outputs per thread by FMAs (8 LDS reads per 16 FMAs: the LDS port is the bound, 128 clocks per k
-// for the workgroup against 64 of FMA).  MMA = true: v_mfma_f64_16x16x4_f64, every wave owns a 32 x 32 quadrant as
-// 2 x 2 blocks; 4 LDS reads per 4 MFMAs (8192 flop), the matrix pipe is the bound.  The two forms keep their 16 sums
-// per thread in acc[4][4] under different maps (acc_row / acc_col).
-template <bool MMA>
-__device__ __forceinline__ int acc_row(int u, int v) {
-  if (MMA) return (int)(threadIdx.x >> 7) * 32 + (u >> 1) * 16 + (int)((threadIdx.x & 63) >> 4) + 4 * v;
-  return (int)(threadIdx.x >> 4) + 16 * u;
-}
-template <bool MMA>
-__device__ __forceinline__ int acc_col(int u, int v) {
-  if (MMA) return (int)((threadIdx.x >> 6) & 1) * 32 + (u & 1) * 16 + (int)(threadIdx.x & 15);
-  return (int)(threadIdx.x & 15) + 16 * v;
-}
-template <bool MMA>
-__device__ __forceinline__ void tile_inner(const double (*As)[NB + 1], const double (*Bs)[NB + 1], double acc[4][4]) {
-  if (MMA) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int r0 = (w >> 1) * 32 + (lane & 15), c0 = (w & 1) * 32 + (lane & 15), kq = lane >> 4;
-    v4f64 c[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) c[u] = v4f64{acc[u][0], acc[u][1], acc[u][2], acc[u][3]};
-#pragma unroll 4
-    for (int k0 = 0; k0 < NB; k0 += 4) {
-      const double a0 = As[k0 + kq][r0], a1 = As[k0 + kq][r0 + 16];
-      const double b0 = Bs[k0 + kq][c0], b1 = Bs[k0 + kq][c0 + 16];
-      c[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, c[0], 0, 0, 0);
-      c[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, c[1], 0, 0, 0);
-      c[2] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, c[2], 0, 0, 0);
-      c[3] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, c[3], 0, 0, 0);
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-#pragma unroll
-      for (int v = 0; v < 4; ++v) acc[u][v] = c[u][v];
-  } else {
-    const int ty = threadIdx.x >> 4, tx = threadIdx.x & 15;
-#pragma unroll 8
-    for (int k = 0; k < NB; ++k) {
-      double a[4], b[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) a[u] = As[k][ty + 16 * u];
-#pragma unroll
-      for (int v = 0; v < 4; ++v) b[v] = Bs[k][tx + 16 * v];
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-#pragma unroll
-        for (int v = 0; v < 4; ++v) acc[u][v] = fma(a[u], b[v], acc[u][v]);
-    }
-  }
-}
 constexpr int chol_superpanel_blocks() { return 8; }  // measured: 4 -> 157 ms, 8 -> 99 ms (1: a trailing update per block, 217)
-// the tile products run on the matrix pipe (MMA = true); the 4 x 4-per-thread FMA form of the same templates measured
-// 126 ms against 98 for the factorisation of the 100k lattice and is not instantiated
-#define DCORA_LAUNCH_MMA(KERNEL, grid, st, ...) hipLaunchKernelGGL((KERNEL<true>), grid, dim3(256), 0, st, __VA_ARGS__)
-
-// acc(i, j) = sum_k A[i][k] B[j][k]; A and B are row-major with k contiguous; rows beyond arows / brows and k beyond K
-// read as zero
-template <bool MMA>
-__device__ __forceinline__ void chol_tile_product(const double *__restrict__ Ag, long long lda, int arows,
-                                                  const double *__restrict__ Bg, long long ldb, int brows, int K,
-                                                  double (*As)[NB + 1], double (*Bs)[NB + 1], double acc[4][4]) {
-  const int tid = threadIdx.x;
-  for (int e = tid; e < NB * NB; e += 256) {
-    const int i = e >> 6, k = e & 63;
-    As[k][i] = (i < arows && k < K) ? Ag[(long long)i * lda + k] : 0.0;
-    Bs[k][i] = (i < brows && k < K) ? Bg[(long long)i * ldb + k] : 0.0;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int u = 0; u < 4; ++u)
-#pragma unroll
-    for (int v = 0; v < 4; ++v) acc[u][v] = 0;
-  tile_inner<MMA>(As, Bs, acc);
-}
 
 // panel below the diagonal block:  X = B L^-T, 64 rows per workgroup, in place
-template <bool MMA>
 __global__ __launch_bounds__(256) void k_chol_trsm(const PieceDev *__restrict__ pieces, const int *__restrict__ list,
                                                    int j0, double *__restrict__ F, const double *__restrict__ Linv,
                                                    const int *__restrict__ fail) {
@@ -389,89 +296,11 @@ __global__ __launch_bounds__(256) void k_chol_trsm(const PieceDev *__restrict__ 
   __shared__ double Bs[NB][NB + 1];
   double *__restrict__ A = F + P.off + (long long)r0 * f + j0;
   double acc[4][4];
-  chol_tile_product<MMA>(A, f, min(NB, f - r0), Linv + (size_t)blockIdx.y * NB * NB, NB, jb, jb, As, Bs, acc);
+  chol_tile_product(A, f, min(NB, f - r0), Linv + (size_t)blockIdx.y * NB * NB, NB, jb, jb, As, Bs, acc);
   __syncthreads();  // the tile is overwritten in place: every read of it (into LDS) is behind us
-#pragma unroll
-  for (int u = 0; u < 4; ++u)
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-      const int i = acc_row<MMA>(u, v), j = acc_col<MMA>(u, v);
-      if (r0 + i < f && j < jb) A[(long long)i * f + j] = acc[u][v];
-    }
-}
-
-__global__ __launch_bounds__(256) void k_count_nonzero(long long n, const double *__restrict__ v,
-                                                       unsigned long long *__restrict__ out) {
-  unsigned long long c = 0;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) c += v[i] != 0.0;
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
-  if ((threadIdx.x & 63) == 0 && c) atomicAdd(out, c);
-}
-
-// the first c columns of every front (diagonal block over the rows below), packed piece after piece
-__global__ __launch_bounds__(256) void k_chol_pack(const PieceDev *__restrict__ pieces,
-                                                   const long long *__restrict__ panel_off,
-                                                   const double *__restrict__ F, double *__restrict__ out) {
-  const PieceDev P = pieces[blockIdx.y];
-  const int f = P.c + P.m, c = P.c;
-  const long long n = (long long)f * c;
-  const double *__restrict__ M = F + P.off;
-  double *__restrict__ O = out + panel_off[blockIdx.y];
-  for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long long)gridDim.x * 256) {
-    const int i = (int)(e / c), j = (int)(e - (long long)i * c);
-    O[e] = (i >= c || j <= i) ? M[(long long)i * f + j] : 0.0;
-  }
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// Dense inverse of a small SPD matrix on the device (the dense preconditioner of blocks up to 8000 unknowns,
-// ref src/QuadraticProblem.cpp:70-84 applied as an explicit inverse): A = L L^T by the panel kernels above (the whole
-// matrix is one front), Y = L^-1 right-looking by block rows, A^-1 = Y^T Y.  Y is kept transposed (YT, upper block
-// triangular) so that every product below runs over contiguous rows of both operands.
-// ---------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_dense_scatter(int k, const int *__restrict__ rp, const int *__restrict__ ci,
-                                                       const double *__restrict__ v, double *__restrict__ A) {
-  const int i = blockIdx.x;
-  for (int p = rp[i] + threadIdx.x; p < rp[i + 1]; p += 256) {
-    const int j = ci[p];
-    if (j <= i) A[(size_t)i * k + j] = v[p];
-  }
-}
-
-// acc += A-rows x B-rows^T over K chunks of 64: A(ia, l) and B(ib, l), l in [l0, l1)
-template <bool MMA>
-__device__ __forceinline__ void tile_product_range(const double *__restrict__ Arow, const double *__restrict__ Brow,
-                                                   long long ld, int arows, int brows, int l0, int l1,
-                                                   double (*As)[NB + 1], double (*Bs)[NB + 1], double acc[4][4],
-                                                   long long ldb = -1) {
-  if (ldb < 0) ldb = ld;
-  const int tid = threadIdx.x;
-  // software pipeline over the 64-column steps: the operands of step l + 1 are requested (into registers) before the
-  // products of step l, so their latency hides behind 64 MFMAs per wave instead of standing between two steps
-  constexpr int PER = NB * NB / 256;  // entries of each operand per thread
-  const int kk = tid & 63, ib = tid >> 6;  // entry q of a thread: row ib + 4 q, column kk of the step
-  double ra[PER], rb[PER];
-  auto fetch = [&](int l) {
-    const int K = min(NB, l1 - l);
-#pragma unroll
-    for (int q = 0; q < PER; ++q) {
-      const int i = ib + 4 * q;
-      ra[q] = (i < arows && kk < K) ? Arow[(long long)i * ld + l + kk] : 0.0;
-      rb[q] = (i < brows && kk < K) ? Brow[(long long)i * ldb + l + kk] : 0.0;
-    }
-  };
-  if (l0 < l1) fetch(l0);
-  for (int l = l0; l < l1; l += NB) {
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < PER; ++q) {
-      As[kk][ib + 4 * q] = ra[q];
-      Bs[kk][ib + 4 * q] = rb[q];
-    }
-    __syncthreads();
-    if (l + NB < l1) fetch(l + NB);
-    tile_inner<MMA>(As, Bs, acc);
-  }
+  for_each_acc(acc, [&](int i, int j, double s) {
+    if (r0 + i < f && j < jb) A[(long long)i * f + j] = s;
+  });
 }
 
 // trailing update: C(ti, tj) -= sum_{l in [k0, base)} X(ti, l) X(tj, l) over 64 x 64 tiles of the lower triangle behind
@@ -481,7 +310,6 @@ __device__ __forceinline__ void tile_product_range(const double *__restrict__ Ar
 //   behind a super-panel (ncb = 0): K = the whole super-panel (up to 256 columns in 64-column steps through LDS), every
 //     tile of the trailing matrix, blockIdx.x = triangular index.  A rank-256 update reads and writes the trailing
 //     matrix once where four rank-64 updates did four times: the update is bound by exactly that traffic.
-template <bool MMA>
 __global__ __launch_bounds__(256) void k_chol_syrk(const PieceDev *__restrict__ pieces, const int *__restrict__ list,
                                                    int k0, int kcap, int ccap, int ncb, double *__restrict__ F,
                                                    const int *__restrict__ fail) {
@@ -508,237 +336,41 @@ __global__ __launch_bounds__(256) void k_chol_syrk(const PieceDev *__restrict__ 
   __shared__ double Bs[NB][NB + 1];
   double *__restrict__ M = F + P.off;
   double acc[4][4];
-#pragma unroll
-  for (int u = 0; u < 4; ++u)
-#pragma unroll
-    for (int v = 0; v < 4; ++v) acc[u][v] = 0;
-  tile_product_range<MMA>(M + (long long)ri0 * f, M + (long long)cj0 * f, f, min(NB, f - ri0), min(NB, f - cj0), k0, base,
-                          As, Bs, acc);
-#pragma unroll
-  for (int u = 0; u < 4; ++u)
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-      const int r = ri0 + acc_row<MMA>(u, v), c = cj0 + acc_col<MMA>(u, v);
-      if (r < f && c <= r && c < colend) M[(long long)r * f + c] -= acc[u][v];
-    }
+  zero_acc(acc);
+  tile_product_range(M + (long long)ri0 * f, f, min(NB, f - ri0), M + (long long)cj0 * f, f, min(NB, f - cj0), k0, base,
+                     As, Bs, acc);
+  for_each_acc(acc, [&](int i, int j, double s) {
+    const int r = ri0 + i, c = cj0 + j;
+    if (r < f && c <= r && c < colend) M[(long long)r * f + c] -= s;
+  });
 }
 
-
-// Y = L^-1 right-looking, one block row of L at a time; Y is kept transposed (YT(j, i) = Y(i, j)^T).  Step ib:
-//   finish:  YT(j, ib) = -TT(j, ib) Linv_ib^T for the block rows j < ib (TT accumulated in place), YT(ib, ib) = Linv_ib^T
-//   update:  TT(j, i) += YT(j, ib) L(i, ib)^T for every block row i > ib and j <= ib  -- (nb - ib - 1)(ib + 1) tiles
-template <bool MMA>
-__global__ __launch_bounds__(256) void k_dense_trtri_finish(int k, int ib, double *__restrict__ YT,
-                                                            const double *__restrict__ Linv,
-                                                            const InvJob *__restrict__ jobs = nullptr,
-                                                            int tstride = 1) {
-  if (jobs) {
-    const InvJob J = jobs[blockIdx.z];
-    k = J.c;
-    YT += J.yt;
-    Linv += J.tinv;
-    if (ib * NB >= k) return;
-  }
-  __shared__ double As[NB][NB + 1];
-  __shared__ double Bs[NB][NB + 1];
-  const int tid = threadIdx.x;
-  const int i0 = ib * NB, ni = min(NB, k - i0);
-  // (tstride: 64 x 64 blocks between the inverses of consecutive panels -- 1, or the batch size when the potrf of a batch
-  // of equal matrices stored them panel by panel)
-  const double *__restrict__ Li = Linv + (size_t)ib * NB * NB * tstride;
-  if ((int)blockIdx.x == ib) {  // diagonal block: the transpose of the inverse of the diagonal block of L
-    for (int e = tid; e < NB * NB; e += 256) {
-      const int a = e >> 6, b = e & 63;
-      if (a < ni && b < ni) YT[(size_t)(i0 + a) * k + i0 + b] = Li[b * NB + a];
-    }
-    return;
-  }
-  const int j0 = blockIdx.x * NB;
-  for (int e = tid; e < NB * NB; e += 256) {
-    const int a = e >> 6, mm = e & 63;
-    As[mm][a] = (mm < ni) ? YT[(size_t)(j0 + a) * k + i0 + mm] : 0.0;  // TT(a, m)
-    Bs[mm][a] = Li[a * NB + mm];                                       // Linv(b = a, m)
-  }
-  __syncthreads();
-  double acc[4][4];
-#pragma unroll
-  for (int u = 0; u < 4; ++u)
-#pragma unroll
-    for (int v = 0; v < 4; ++v) acc[u][v] = 0;
-  tile_inner<MMA>(As, Bs, acc);
-#pragma unroll
-  for (int u = 0; u < 4; ++u)
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-      const int b = acc_col<MMA>(u, v);
-      if (b < ni) YT[(size_t)(j0 + acc_row<MMA>(u, v)) * k + i0 + b] = -acc[u][v];
-    }
-}
-template <bool MMA>
-__global__ __launch_bounds__(256) void k_dense_trtri_update(int k, int ib, const double *__restrict__ L, long long ldl,
-                                                            double *__restrict__ YT,
-                                                            const InvJob *__restrict__ jobs = nullptr) {
-  if (jobs) {
-    const InvJob J = jobs[blockIdx.z];
-    k = J.c;
-    L += J.l11;
-    ldl = J.f;
-    YT += J.yt;
-    if ((ib + 1 + (int)blockIdx.x) * NB >= k) return;
-  }
-  __shared__ double As[NB][NB + 1];
-  __shared__ double Bs[NB][NB + 1];
-  const int i0 = (ib + 1 + blockIdx.x) * NB, j0 = blockIdx.y * NB, l0 = ib * NB;
-  const int ni = min(NB, k - i0);
-  double acc[4][4];
-#pragma unroll
-  for (int u = 0; u < 4; ++u)
-#pragma unroll
-    for (int v = 0; v < 4; ++v) acc[u][v] = 0;
-  tile_product_range<MMA>(YT + (size_t)j0 * k, L + (size_t)i0 * ldl, k, NB, ni, l0, l0 + NB, As, Bs, acc, ldl);
-#pragma unroll
-  for (int u = 0; u < 4; ++u)
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-      const int mm = acc_col<MMA>(u, v);
-      if (mm < ni) YT[(size_t)(j0 + acc_row<MMA>(u, v)) * k + i0 + mm] += acc[u][v];
-    }
+__global__ __launch_bounds__(256) void k_count_nonzero(long long n, const double *__restrict__ v,
+                                                       unsigned long long *__restrict__ out) {
+  unsigned long long c = 0;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) c += v[i] != 0.0;
+  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+  if ((threadIdx.x & 63) == 0 && c) atomicAdd(out, c);
 }
 
-// M = Y^T Y = YT YT^T: tile (ta, tb), tb <= ta, sums over the columns l >= block ta; both triangles are written
-template <bool MMA>
-__global__ __launch_bounds__(256) void k_dense_lauum(int k, const double *__restrict__ YT, double *__restrict__ M,
-                                                     int ldm, const InvJob *__restrict__ jobs = nullptr) {
-  if (jobs) {
-    const InvJob J = jobs[blockIdx.z];
-    if (J.mt < 0) return;
-    k = J.c;
-    if (ldm <= 0) ldm = J.c;  // (a batch of dense inverses passes its padded leading dimension)
-    YT += J.yt;
-    M += J.mt;
-  }
-  __shared__ double As[NB][NB + 1];
-  __shared__ double Bs[NB][NB + 1];
-  int ta = (int)((sqrtf(8.0f * (float)blockIdx.x + 1.0f) - 1.0f) * 0.5f);
-  while ((ta + 1) * (ta + 2) / 2 <= (int)blockIdx.x) ++ta;
-  while (ta * (ta + 1) / 2 > (int)blockIdx.x) --ta;
-  const int tb = blockIdx.x - ta * (ta + 1) / 2;
-  const int a0 = ta * NB, b0 = tb * NB;
-  if (a0 >= k) return;  // (batched: the grid is sized for the widest piece)
-  const int na = min(NB, k - a0), nb = min(NB, k - b0);
-  double acc[4][4];
-#pragma unroll
-  for (int u = 0; u < 4; ++u)
-#pragma unroll
-    for (int v = 0; v < 4; ++v) acc[u][v] = 0;
-  tile_product_range<MMA>(YT + (size_t)a0 * k, YT + (size_t)b0 * k, k, na, nb, a0, k, As, Bs, acc);
-#pragma unroll
-  for (int u = 0; u < 4; ++u)
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-      const int a = a0 + acc_row<MMA>(u, v), b = b0 + acc_col<MMA>(u, v);
-      if (a < k && b < k) {
-        M[(size_t)a * ldm + b] = acc[u][v];
-        M[(size_t)b * ldm + a] = acc[u][v];
-      }
-    }
-}
-
-// ---- inverses of a WIDE dissection piece on the device (the builder of the partitioned inverse, sparse_precond.h):
-//      from the factored front [L11; L21] (leading dimension f): YT = (L11^-1)^T with the right-looking kernels above,
-//      W = -L21 L11^-1, and for pieces without rows below M = L11^-T L11^-1 ----
-// inverse of the 64 x 64 diagonal blocks of a lower-triangular matrix, one workgroup per block
-__global__ __launch_bounds__(256) void k_tri_inv64(int c, const double *__restrict__ L, long long ldl,
-                                                   double *__restrict__ Linv,
-                                                   const InvJob *__restrict__ jobs = nullptr) {
-  if (jobs) {
-    const InvJob J = jobs[blockIdx.z];
-    c = J.c;
-    L += J.l11;
-    ldl = J.f;
-    Linv += J.tinv;
-    if ((int)blockIdx.x * NB >= c) return;
-  }
-  __shared__ double T[NB][NB + 1];
-  __shared__ double Li[NB][NB + 1];
-  const int b0 = blockIdx.x * NB, nb = min(NB, c - b0);
-  const int tid = threadIdx.x;
-  for (int e = tid; e < NB * NB; e += 256) {
-    const int i = e >> 6, j = e & 63;
-    T[i][j] = (i < nb && j <= i) ? L[(long long)(b0 + i) * ldl + b0 + j] : (i == j ? 1.0 : 0.0);
-  }
-  __syncthreads();
-  const int k = tid >> 2, kq = tid & 3;
-  for (int r = kq; r < k; r += 4) Li[r][k] = 0.0;
-  if (kq == 0) Li[k][k] = 1.0 / T[k][k];
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  for (int r = k + 1; r < NB; ++r) {
-    double s = 0;
-    for (int l = k + kq; l < r; l += 4) s += T[r][l] * Li[l][k];
-    s += __shfl_xor(s, 1);
-    s += __shfl_xor(s, 2);
-    if (kq == 0) Li[r][k] = -s / T[r][r];
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-  }
-  __syncthreads();
-  double *__restrict__ O = Linv + (size_t)blockIdx.x * NB * NB;
-  for (int e = tid; e < NB * NB; e += 256) O[e] = Li[e >> 6][e & 63];
-}
-// W(a, j) = -sum_{l >= j0} B(a, l) YT(j, l): tile (ta over the m rows below, tj over the c columns)
-template <bool MMA>
-__global__ __launch_bounds__(256) void k_piece_w(int c, int m, const double *__restrict__ B, long long ldb,
-                                                 const double *__restrict__ YT, double *__restrict__ W,
-                                                 const InvJob *__restrict__ jobs = nullptr) {
-  if (jobs) {  // B: the front arena, W: the packed panels (rows [c, c + m) of the piece's panel are W)
-    const InvJob J = jobs[blockIdx.z];
-    c = J.c;
-    m = J.m;
-    B += J.l11 + (long long)J.c * J.f;
-    ldb = J.f;
-    YT += J.yt;
-    W += J.pk + (long long)J.c * J.c;
-    if ((int)blockIdx.x * NB >= m || (int)blockIdx.y * NB >= c) return;
-  }
-  __shared__ double As[NB][NB + 1];
-  __shared__ double Bs[NB][NB + 1];
-  const int a0 = blockIdx.x * NB, j0 = blockIdx.y * NB;
-  const int na = min(NB, m - a0), nj = min(NB, c - j0);
-  double acc[4][4];
-#pragma unroll
-  for (int u = 0; u < 4; ++u)
-#pragma unroll
-    for (int v = 0; v < 4; ++v) acc[u][v] = 0;
-  tile_product_range<MMA>(B + (long long)a0 * ldb, YT + (long long)j0 * c, ldb, na, nj, j0, c, As, Bs, acc, c);
-#pragma unroll
-  for (int u = 0; u < 4; ++u)
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-      const int a = a0 + acc_row<MMA>(u, v), j = j0 + acc_col<MMA>(u, v);
-      if (a < m && j < c) W[(long long)a * c + j] = -acc[u][v];
-    }
-}
-// panel of an inverted piece: rows [0, c) = L11^-1 (lower; = YT transposed), rows [c, c + m) = W
-__global__ __launch_bounds__(256) void k_piece_pack_inverted(int c, int m, const double *__restrict__ YT,
-                                                             const double *__restrict__ W, double *__restrict__ out,
-                                                             const InvJob *__restrict__ jobs = nullptr) {
-  if (jobs) {  // batched: W is already in place (k_piece_w wrote it into the panel), only L11^-1 is transposed in
-    const InvJob J = jobs[blockIdx.z];
-    c = J.c;
-    m = 0;
-    YT += J.yt;
-    out += J.pk;
-  }
-  const long long n = (long long)(c + m) * c;
+// the first c columns of every front (diagonal block over the rows below), packed piece after piece
+__global__ __launch_bounds__(256) void k_chol_pack(const PieceDev *__restrict__ pieces,
+                                                   const long long *__restrict__ panel_off,
+                                                   const double *__restrict__ F, double *__restrict__ out) {
+  const PieceDev P = pieces[blockIdx.y];
+  const int f = P.c + P.m, c = P.c;
+  const long long n = (long long)f * c;
+  const double *__restrict__ M = F + P.off;
+  double *__restrict__ O = out + panel_off[blockIdx.y];
   for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long long)gridDim.x * 256) {
     const int i = (int)(e / c), j = (int)(e - (long long)i * c);
-    out[e] = i < c ? (j <= i ? YT[(long long)j * c + i] : 0.0) : W[(long long)(i - c) * c + j];
+    O[e] = (i >= c || j <= i) ? M[(long long)i * f + j] : 0.0;
   }
 }
 
-// ---- the NARROW pieces (c <= 64: the leaves and the small separators, thousands of them) all at once ----
-// rows [0, c) of the packed panel <- L11^-1 (lower triangle): one workgroup per piece, column k of the inverse by lane
-// group k as in k_tri_inv64
+// ---- the NARROW pieces (c <= 64: the leaves and the small separators, thousands of them) all at once; the wider ones go
+//      through the job list of dense_inverse.hip ----
+// rows [0, c) of the packed panel <- L11^-1 (lower triangle): one workgroup per piece
 __global__ __launch_bounds__(256) void k_small_inv(const PieceDev *__restrict__ pieces, const int *__restrict__ list,
                                                    const long long *__restrict__ panel_off,
                                                    const double *__restrict__ F, double *__restrict__ out,
@@ -755,21 +387,7 @@ __global__ __launch_bounds__(256) void k_small_inv(const PieceDev *__restrict__ 
     const int i = e >> 6, j = e & 63;
     T[i][j] = (i < c && j <= i) ? L[(long long)i * f + j] : (i == j ? 1.0 : 0.0);
   }
-  __syncthreads();
-  const int k = tid >> 2, kq = tid & 3;
-  for (int r = kq; r < k; r += 4) Li[r][k] = 0.0;
-  if (kq == 0) Li[k][k] = 1.0 / T[k][k];
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  for (int r = k + 1; r < NB; ++r) {
-    double sum = 0;
-    for (int l = k + kq; l < r; l += 4) sum += T[r][l] * Li[l][k];
-    sum += __shfl_xor(sum, 1);
-    sum += __shfl_xor(sum, 2);
-    if (kq == 0) Li[r][k] = -sum / T[r][r];
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-  }
-  __syncthreads();
+  tri_inv64_lds(T, Li);
   double *__restrict__ O = out + panel_off[s];
   for (int e = tid; e < c * c; e += 256) {
     const int i = e / c, j = e - i * c;
@@ -786,7 +404,6 @@ __global__ __launch_bounds__(256) void k_small_inv(const PieceDev *__restrict__ 
   }
 }
 // rows [c, c + m) of the packed panel <- W = -L21 L11^-1: 64 rows below per workgroup (blockIdx.x), piece blockIdx.y
-template <bool MMA>
 __global__ __launch_bounds__(256) void k_small_w(const PieceDev *__restrict__ pieces, const int *__restrict__ list,
                                                  const long long *__restrict__ panel_off,
                                                  const double *__restrict__ F, double *__restrict__ out) {
@@ -808,18 +425,11 @@ __global__ __launch_bounds__(256) void k_small_w(const PieceDev *__restrict__ pi
   }
   __syncthreads();
   double acc[4][4];
-#pragma unroll
-  for (int u = 0; u < 4; ++u)
-#pragma unroll
-    for (int v = 0; v < 4; ++v) acc[u][v] = 0;
-  tile_inner<MMA>(As, Bs, acc);
-#pragma unroll
-  for (int u = 0; u < 4; ++u)
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-      const int a = acc_row<MMA>(u, v), j = acc_col<MMA>(u, v);
-      if (a < na && j < c) O[(long long)(c + a0 + a) * c + j] = -acc[u][v];
-    }
+  zero_acc(acc);
+  tile_inner(As, Bs, acc);
+  for_each_acc(acc, [&](int a, int j, double sum) {
+    if (a < na && j < c) O[(long long)(c + a0 + a) * c + j] = -sum;
+  });
 }
 
 inline uint64_t mix64(uint64_t h, uint64_t w) {
@@ -984,9 +594,8 @@ size_t arena_keep_bytes() {
 
 }  // namespace
 
-namespace {
-void scratch_clear();  // the dense builds' recycled arenas (below)
-}
+void scratch_clear();  // dense_inverse.hip: the dense builds' recycled arenas
+
 void chol_cache_clear() {
   std::lock_guard<std::mutex> lk(g_mu);
   g_cache.clear();
@@ -1028,11 +637,382 @@ int device_chol_prepare(const HostCsr &A, int block, int device) {
 }
 
 namespace {
+using Clock = std::chrono::steady_clock;
+double ms_between(Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
+
+// ---- step 1: the image of the pattern, from the cache or built (and cached) now ----
+int find_or_build_image(const HostCsr &A, int block, int top, int device, bool any_order,
+                        std::shared_ptr<CholImage> *out, bool *hit) {
+  uint64_t h0 = 0x243F6A8885A308D3ull, h1 = 0x13198A2E03707344ull;
+  hash_ints(A.rp.data(), A.rp.size(), &h0, &h1);
+  hash_ints(A.ci.data(), A.ci.size(), &h0, &h1);
+  std::shared_ptr<CholImage> img;
+  {
+    std::lock_guard<std::mutex> lk(g_mu);
+    // a verdict alone (no panels asked for) does not care about the order: an analysis of the same pattern made for
+    // the preconditioner (dense top, device_chol.h) serves the PSD test of S = Q - Lambda, which has Q's pattern --
+    // the certificate of the 100k lattice saves the 0.25 s analysis and a second 18 GB arena
+    for (int pass = 0; pass < (any_order ? 2 : 1) && !img; ++pass)
+      for (auto it = g_cache.begin(); it != g_cache.end(); ++it)
+        if (it->h0 == h0 && it->h1 == h1 && it->n == A.n && it->nnz == A.nnz() && it->block == block &&
+            it->device == device && (it->top == top || pass == 1)) {
+          g_cache.splice(g_cache.begin(), g_cache, it);
+          img = g_cache.front().img;
+          break;
+        }
+  }
+  *hit = img != nullptr;
+  if (env::init_timing())
+    fprintf(stderr, "[factor] look-up: %s (n %d nnz %d block %d top %d, %zu cached, key %016llx)\n", img ? "hit" : "MISS", A.n,
+            A.nnz(), block, top, g_cache.size(), (unsigned long long)h0);
+  if (!img) {
+    const int rc = build_image(A, block, top, device, &img);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(g_mu);
+    g_cache.push_front(CacheSlot{h0, h1, A.n, A.nnz(), block, device, top, img});
+    while (g_cache.size() > 8) g_cache.pop_back();
+  }
+  *out = img;
+  return DCORA_OK;
+}
+
+// ---- step 2: the arena of the fronts: the image's own (kept between factorisations) or one for this call ----
+int choose_arena(const std::shared_ptr<CholImage> &img, DevBuf<double> *local, double **F) {
+  const size_t doubles = (size_t)img->sym.arena, bytes = doubles * sizeof(double);
+  if (bytes > arena_keep_bytes()) {
+    DCORA_HIP(local->alloc(doubles));
+    *F = local->p;
+    return DCORA_OK;
+  }
+  if (!img->arena.p) {
+    // the arenas kept by all cached images together stay within the same bound: idle images give theirs up
+    std::lock_guard<std::mutex> lk(g_mu);
+    size_t held = bytes;
+    for (CacheSlot &c : g_cache)
+      if (c.img != img && c.img->arena.p) {
+        held += c.img->arena.n * sizeof(double);
+        if (held > arena_keep_bytes() && c.img->mu.try_lock()) {
+          held -= c.img->arena.n * sizeof(double);
+          c.img->arena.release();
+          c.img->mu.unlock();
+        }
+      }
+  }
+  if (!img->arena.p) DCORA_HIP(img->arena.alloc(doubles));
+  *F = img->arena.p;
+  return DCORA_OK;
+}
+
+// ---- step 3: the numeric factorisation, enqueued, and its verdict ----
+struct EnqueueClock {
+  Clock::time_point start, copied, zeroed, enqueued;
+};
 // vals_dev (may be null): the values in A's CSR order, already on the device and complete once `ready` (may be null: now)
-// has passed; A then carries the pattern alone (the cache key and the analysis read nothing else) and no value is copied
+// has passed; A then carries the pattern alone
+int enqueue_factorisation(CholImage &img, hipStream_t st, double *F, const HostCsr &A, const double *vals_dev,
+                          hipEvent_t ready, EnqueueClock *clk) {
+  const long long nnz = (long long)img.sym.a_dest.size();
+  clk->start = Clock::now();
+  const double *vin = img.vals.p;  // what k_chol_scatter reads
+  if (vals_dev) {
+    if (ready) DCORA_HIP(hipStreamWaitEvent(st, ready, 0));
+    vin = vals_dev;
+  } else {
+    const double *vsrc = A.v.data();
+    if (img.vals_pinned) {
+      std::memcpy(img.vals_pinned, A.v.data(), (size_t)nnz * sizeof(double));
+      vsrc = img.vals_pinned;
+    }
+    DCORA_HIP(hipMemcpyAsync(img.vals.p, vsrc, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice, st));
+  }
+  clk->copied = Clock::now();
+  DCORA_HIP(hipMemsetAsync(F, 0, (size_t)img.sym.arena * sizeof(double), st));
+  clk->zeroed = Clock::now();
+  DCORA_HIP(hipMemsetAsync(img.fail.p, 0, sizeof(int), st));
+  DCORA_HIP(hipMemsetAsync(img.logdet.p, 0, sizeof(double), st));
+  hipLaunchKernelGGL(k_chol_scatter, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, st, nnz, img.dest.p, vin, F);
+  for (const Launch &L : img.plan) {
+    const int *list = img.lists.p + L.list;
+    switch (L.kind) {
+      case 0:
+        hipLaunchKernelGGL(k_chol_extend_add, dim3(L.gx, L.gy), dim3(256), 0, st, img.pieces.p, list, img.rel.p, F,
+                           img.fail.p);
+        break;
+      case 1:
+        hipLaunchKernelGGL(k_chol_potrf, dim3(L.gx), dim3(256), 0, st, img.pieces.p, list, L.j0, F, img.linv.p,
+                           img.fail.p, img.logdet.p, 0);
+        break;
+      case 2:
+        hipLaunchKernelGGL(k_chol_trsm, dim3(L.gx, L.gy), dim3(256), 0, st, img.pieces.p, list, L.j0, F, img.linv.p,
+                           img.fail.p);
+        break;
+      default:
+        hipLaunchKernelGGL(k_chol_syrk, dim3(L.gx, L.gy), dim3(256), 0, st, img.pieces.p, list, L.j0, L.kcap, L.ccap,
+                           L.ncb, F, img.fail.p);
+        break;
+    }
+  }
+  DCORA_HIP(hipGetLastError());
+  clk->enqueued = Clock::now();
+  return DCORA_OK;
+}
+int read_verdict(CholImage &img, hipStream_t st, int *failed, double *logdet) {
+  if (img.vals_pinned) {  // (the verdict comes back through the pinned buffer's tail: see CholImage)
+    double *tail = img.vals_pinned + img.sym.a_dest.size();
+    DCORA_HIP(hipMemcpyAsync(tail, img.fail.p, sizeof(int), hipMemcpyDeviceToHost, st));
+    DCORA_HIP(hipMemcpyAsync(tail + 1, img.logdet.p, sizeof(double), hipMemcpyDeviceToHost, st));
+    DCORA_HIP(hipStreamSynchronize(st));
+    std::memcpy(failed, tail, sizeof(int));
+    *logdet = tail[1];
+  } else {
+    DCORA_HIP(hipMemcpyAsync(failed, img.fail.p, sizeof(int), hipMemcpyDeviceToHost, st));
+    DCORA_HIP(hipMemcpyAsync(logdet, img.logdet.p, sizeof(double), hipMemcpyDeviceToHost, st));
+    DCORA_HIP(hipStreamSynchronize(st));
+  }
+  return DCORA_OK;
+}
+
+// ---- step 4: the factor handed over by pieces: packed on the device, the pieces inverted there by class, one copy to
+//      the host ----
+// one host block for all panels (and the wide pieces' M): not value-initialised -- the copy writes every entry, and
+// zeroing 3 GB first cost 0.76 s for the whole 100k lattice -- and handed to the pieces as views
+struct HostBlock {
+  double *panels = nullptr, *M = nullptr;
+  void *m_tokens = nullptr;  // reserved, unreadable addresses standing for the M that exist on the device only
+  size_t m_tokens_bytes = 0;
+  DevBuf<double> dev_panels, dev_M;  // device sources of a sink that fills on the device
+  ~HostBlock() {
+    std::free(panels);
+    std::free(M);
+    if (m_tokens) munmap(m_tokens, m_tokens_bytes);
+  }
+};
+// 2 MB-aligned and advised as huge pages: first touch and release of 3 GB in 4 KB pages cost 0.4 s each
+double *huge_alloc(size_t doubles) {
+  const size_t two_mb = (size_t)2 << 20;
+  const size_t bytes = ((std::max<size_t>(doubles, 1) * sizeof(double) + two_mb - 1) / two_mb) * two_mb;
+  void *p = std::aligned_alloc(two_mb, bytes);
+  if (p) (void)madvise(p, bytes, MADV_HUGEPAGE);
+  return (double *)p;
+}
+
+constexpr int kWide = 384;  // pieces of at least this many columns are inverted one after the other
+int piece_class(const CholPiece &P) { return P.c <= NB ? 0 : (P.c < kWide ? 1 : 2); }  // narrow, mid, wide
+
+struct HandOver {
+  CholImage &img;
+  hipStream_t st;
+  const double *F;
+  std::vector<long long> poff, moff;  // per piece: its packed panel; its M or -1
+  long long mtotal = 0;
+  DevBuf<long long> dpoff, dmoff;
+  DevBuf<double> packed, mall;  // the panels; with device sources the M of every piece
+};
+
+// the narrow pieces by two batched launches
+int invert_narrow_pieces(HandOver &h, const std::vector<int> &narrow, bool want_m) {
+  if (narrow.empty()) return DCORA_OK;
+  int mmax = 0;
+  for (int s : narrow) mmax = std::max(mmax, h.img.sym.pieces[s].m);
+  DevBuf<int> dlist;
+  DCORA_HIP(dlist.alloc(narrow.size()));
+  DCORA_HIP(hipMemcpyAsync(dlist.p, narrow.data(), narrow.size() * sizeof(int), hipMemcpyHostToDevice, h.st));
+  hipLaunchKernelGGL(k_small_inv, dim3((unsigned)narrow.size()), dim3(256), 0, h.st, h.img.pieces.p, dlist.p, h.dpoff.p, h.F,
+                     h.packed.p, (const long long *)h.dmoff.p, want_m ? h.mall.p : (double *)nullptr);
+  if (mmax > 0)
+    hipLaunchKernelGGL(k_small_w, dim3((mmax + NB - 1) / NB, (unsigned)narrow.size()), dim3(256), 0, h.st, h.img.pieces.p,
+                       dlist.p, h.dpoff.p, h.F, h.packed.p);
+  DCORA_HIP(hipStreamSynchronize(h.st));  // dlist lives on this frame
+  return DCORA_OK;
+}
+// wider pieces through the job list (enqueue_inverse_jobs).  together: ONE batch, a piece per blockIdx.z, their scratch
+// side by side (the two thousand pieces of 64 < c < 384 columns of the whole 100k lattice in 15 launches); otherwise a
+// batch per piece, one after the other in the scratch of the widest.  M (may be null) receives the M of the pieces whose
+// moff is set.
+int invert_pieces(HandOver &h, const std::vector<int> &which, bool together, double *M) {
+  if (which.empty()) return DCORA_OK;
+  std::vector<InvJob> jobs;
+  long long yt_total = 0, tinv_total = 0;
+  int cmax = 0, mmax = 0;
+  for (int s : which) {
+    const CholPiece &P = h.img.sym.pieces[s];
+    const long long yt = (long long)P.c * P.c, tinv = (long long)((P.c + NB - 1) / NB) * NB * NB;
+    jobs.push_back(InvJob{P.c, P.m, P.c, P.off, (long long)P.c + P.m, together ? yt_total : 0, together ? tinv_total : 0,
+                          h.poff[s], h.moff[s]});
+    yt_total = together ? yt_total + yt : std::max(yt_total, yt);
+    tinv_total = together ? tinv_total + tinv : std::max(tinv_total, tinv);
+    cmax = std::max(cmax, P.c);
+    mmax = std::max(mmax, P.m);
+  }
+  DevBuf<InvJob> djobs;
+  DevBuf<double> yt, tinv;
+  DCORA_HIP(djobs.alloc(jobs.size()));
+  DCORA_HIP(yt.alloc((size_t)yt_total));
+  DCORA_HIP(tinv.alloc((size_t)tinv_total));
+  DCORA_HIP(hipMemcpyAsync(djobs.p, jobs.data(), jobs.size() * sizeof(InvJob), hipMemcpyHostToDevice, h.st));
+  InvBatch b;
+  b.F = h.F;
+  b.yt = yt.p;
+  b.tinv = tinv.p;
+  b.packed = h.packed.p;
+  b.M = M;
+  b.want_m = M != nullptr;
+  if (together) {
+    b.jobs = djobs.p;
+    b.count = (int)jobs.size();
+    b.cmax = cmax;
+    b.mmax = mmax;
+    DCORA_HIP(hipMemsetAsync(yt.p, 0, (size_t)yt_total * sizeof(double), h.st));
+    enqueue_inverse_jobs(h.st, b);
+  } else {
+    for (size_t q = 0; q < jobs.size(); ++q) {
+      b.jobs = djobs.p + q;
+      b.count = 1;
+      b.cmax = jobs[q].c;
+      b.mmax = jobs[q].m;
+      DCORA_HIP(hipMemsetAsync(yt.p, 0, (size_t)jobs[q].c * jobs[q].c * sizeof(double), h.st));
+      enqueue_inverse_jobs(h.st, b);
+    }
+  }
+  DCORA_HIP(hipGetLastError());
+  DCORA_HIP(hipStreamSynchronize(h.st));  // the job list and the scratch live on this frame
+  return DCORA_OK;
+}
+
+int hand_over_panels(CholImage &img, hipStream_t st, const double *F, PiecewiseFactor *panels) {
+  const CholSymbolic &S = img.sym;
+  const bool init_timing = env::init_timing();
+  auto tl = Clock::now();
+  auto lap = [&](const char *what) {
+    if (!init_timing) return;
+    const auto now = Clock::now();
+    fprintf(stderr, "[factor] %-26s %9.1f ms\n", what, ms_between(tl, now));
+    tl = now;
+  };
+  const int np = (int)S.pieces.size();
+  HandOver h{img, st, F};
+  h.poff.assign((size_t)np + 1, 0);
+  h.moff.assign((size_t)np, -1);
+  int fmax = 1;
+  for (int s = 0; s < np; ++s) {
+    const CholPiece &P = S.pieces[s];
+    h.poff[s + 1] = h.poff[s] + (long long)(P.c + P.m) * P.c;
+    fmax = std::max(fmax, P.c + P.m);
+  }
+  const long long ptotal = h.poff[np];
+  DCORA_HIP(h.dpoff.alloc(h.poff.size()));
+  DCORA_HIP(h.packed.alloc((size_t)std::max<long long>(1, ptotal)));
+  DCORA_HIP(hipMemcpyAsync(h.dpoff.p, h.poff.data(), h.poff.size() * sizeof(long long), hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(k_chol_pack, dim3(std::min(64, (fmax + 7) / 8), np), dim3(256), 0, st, img.pieces.p, h.dpoff.p, F,
+                     h.packed.p);
+  // Without hubs every piece arrives inverted, the inverses formed here instead of by the host's threads (for the whole
+  // 100k lattice 310 Gflop, 7.7 s on 16 cores): the narrow ones (c <= 64) by two batched launches, the ones up to 384
+  // columns in one batch of the right-looking kernels, the wide ones one after the other.
+  const bool inverted = S.nhub == 0;
+  // device sources (asked for by the caller whose weight sink fills on the device): the M = L11^-T L11^-1 of every piece
+  // is formed here as well and stays here, like the panels; otherwise only the wide pieces' M, which go to the host --
+  // the schedule (host_partinv3.cpp) applies the two triangular products of a wide piece as this one symmetric product
+  const bool dev_src = panels->want_device_sources && inverted;
+  std::vector<int> by_class[3];
+  if (inverted)
+    for (int s = 0; s < np; ++s) {
+      const int cls = piece_class(S.pieces[s]);
+      by_class[cls].push_back(s);
+      if (dev_src || cls == 2) {
+        h.moff[s] = h.mtotal;
+        h.mtotal += (long long)S.pieces[s].c * S.pieces[s].c;
+      }
+    }
+  if (dev_src) {
+    DCORA_HIP(h.mall.alloc((size_t)std::max<long long>(1, h.mtotal)));
+    DCORA_HIP(h.dmoff.alloc((size_t)np));
+    DCORA_HIP(hipMemcpyAsync(h.dmoff.p, h.moff.data(), (size_t)np * sizeof(long long), hipMemcpyHostToDevice, st));
+  }
+  int rc = invert_narrow_pieces(h, by_class[0], dev_src);
+  if (rc) return rc;
+  rc = invert_pieces(h, by_class[1], true, dev_src ? h.mall.p : nullptr);
+  if (rc) return rc;
+  if (init_timing) {
+    long cnt[3] = {0, 0, 0};
+    double vol[3] = {0, 0, 0}, c2[3] = {0, 0, 0};
+    for (const CholPiece &P : S.pieces) {
+      const int b = piece_class(P);
+      ++cnt[b];
+      vol[b] += (double)(P.c + P.m) * P.c;
+      c2[b] += (double)P.c * P.c;
+    }
+    fprintf(stderr, "[factor] pieces: narrow %ld (%.0f MB panels, %.0f MB c^2), mid %ld (%.0f MB, %.0f MB), wide %ld (%.0f MB, %.0f MB)\n",
+            cnt[0], vol[0] * 8e-6, c2[0] * 8e-6, cnt[1], vol[1] * 8e-6, c2[1] * 8e-6, cnt[2], vol[2] * 8e-6, c2[2] * 8e-6);
+  }
+  DevBuf<double> mtop_own;  // the wide pieces' M on their way to the host
+  if (!dev_src && !by_class[2].empty()) DCORA_HIP(mtop_own.alloc((size_t)std::max<long long>(1, h.mtotal)));
+  rc = invert_pieces(h, by_class[2], false, dev_src ? h.mall.p : mtop_own.p);
+  if (rc) return rc;
+  DCORA_HIP(hipStreamSynchronize(st));
+  lap("pack + wide inverses");
+  auto blk = std::make_shared<HostBlock>();
+  blk->panels = huge_alloc((size_t)ptotal);
+  if (dev_src) {
+    blk->m_tokens_bytes = (size_t)std::max<long long>(1, h.mtotal) * sizeof(double);
+    void *tok = mmap(nullptr, blk->m_tokens_bytes, PROT_NONE, MAP_PRIVATE | MAP_ANONYMOUS | MAP_NORESERVE, -1, 0);
+    if (tok == MAP_FAILED) {
+      set_last_error("sparse Cholesky: could not reserve the address range of the device-resident M");
+      return DCORA_ERR_HIP;
+    }
+    blk->m_tokens = tok;
+  } else {
+    blk->M = huge_alloc((size_t)h.mtotal);
+  }
+  if (!blk->panels || (!dev_src && !blk->M)) {
+    set_last_error("sparse Cholesky: no host memory for the factor's panels");
+    return DCORA_ERR_HIP;
+  }
+  double *host = blk->panels, *hostM = dev_src ? (double *)blk->m_tokens : blk->M;
+  // non-zeros of the factor (reported as nnz(L)), counted where the factor is
+  DevBuf<unsigned long long> dnz;
+  DCORA_HIP(dnz.alloc(1));
+  DCORA_HIP(hipMemsetAsync(dnz.p, 0, sizeof(unsigned long long), st));
+  hipLaunchKernelGGL(k_count_nonzero, dim3(2048), dim3(256), 0, st, ptotal, h.packed.p, dnz.p);
+  unsigned long long nz_dev = 0;
+  DCORA_HIP(hipMemcpyAsync(&nz_dev, dnz.p, sizeof nz_dev, hipMemcpyDeviceToHost, st));
+  lap("host buffers");
+  DCORA_HIP(hipMemcpyAsync(host, h.packed.p, (size_t)ptotal * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (h.mtotal > 0 && !dev_src)
+    DCORA_HIP(hipMemcpyAsync(hostM, mtop_own.p, (size_t)h.mtotal * sizeof(double), hipMemcpyDeviceToHost, st));
+  DCORA_HIP(hipStreamSynchronize(st));
+  lap("download");
+  PiecewiseFactor &W = *panels;
+  W = PiecewiseFactor();
+  W.n = S.n;
+  W.nhub = S.nhub;
+  W.perm = S.perm;
+  W.iperm = S.iperm;
+  W.pieces.assign((size_t)np, PieceFactor());
+  W.block = blk;
+  for (int s = 0; s < np; ++s) {
+    const CholPiece &P = S.pieces[s];
+    PieceFactor &pf = W.pieces[s];
+    pf.c0 = P.c0;
+    pf.c = P.c;
+    pf.rows.assign(S.rows.begin() + P.rows_off, S.rows.begin() + P.rows_off + P.m);
+    pf.panel_view = host + h.poff[s];
+    pf.inverted = inverted;
+    if (h.moff[s] >= 0) pf.Mtop_view = hostM + h.moff[s];
+  }
+  W.nnzL = (long)nz_dev;
+  if (dev_src) {
+    W.m_on_device_only = true;
+    W.mirrors.push_back(MirrorRange{host, ptotal, h.packed.p});
+    W.mirrors.push_back(MirrorRange{hostM, h.mtotal, h.mall.p});
+    blk->dev_panels = std::move(h.packed);
+    blk->dev_M = std::move(h.mall);
+  }
+  lap("per-piece copies");
+  return DCORA_OK;
+}
+
 int factor_on_device(const HostCsr &A, int block, int top, int device, bool *pd, double *info8, PiecewiseFactor *panels,
                      const double *vals_dev = nullptr, hipEvent_t ready = nullptr) {
-  double *info6 = info8;
   if (A.n <= 0 || (int)A.rp.size() != A.n + 1) {
     set_last_error("sparse Cholesky: empty or malformed matrix");
     return DCORA_ERR_BAD_ARG;
@@ -1043,422 +1023,72 @@ int factor_on_device(const HostCsr &A, int block, int top, int device, bool *pd,
     return DCORA_ERR_NO_DEVICE;
   }
   DCORA_HIP(hipSetDevice(device));
-  const auto t0 = std::chrono::steady_clock::now();
-  constexpr bool use_cache = true;
-  uint64_t h0 = 0x243F6A8885A308D3ull, h1 = 0x13198A2E03707344ull;
-  hash_ints(A.rp.data(), A.rp.size(), &h0, &h1);
-  hash_ints(A.ci.data(), A.ci.size(), &h0, &h1);
+  const auto t0 = Clock::now();
   std::shared_ptr<CholImage> img;
   bool hit = false;
-  if (use_cache) {
-    std::lock_guard<std::mutex> lk(g_mu);
-    // a verdict alone (no panels asked for) does not care about the order: an analysis of the same pattern made for
-    // the preconditioner (dense top, device_chol.h) serves the PSD test of S = Q - Lambda, which has Q's pattern --
-    // the certificate of the 100k lattice saves the 0.25 s analysis and a second 18 GB arena
-    for (int pass = 0; pass < (panels ? 1 : 2) && !img; ++pass)
-      for (auto it = g_cache.begin(); it != g_cache.end(); ++it)
-        if (it->h0 == h0 && it->h1 == h1 && it->n == A.n && it->nnz == A.nnz() && it->block == block &&
-            it->device == device && (it->top == top || pass == 1)) {
-          g_cache.splice(g_cache.begin(), g_cache, it);
-          img = g_cache.front().img;
-          hit = true;
-          break;
-        }
-  }
-  if (env::init_timing())
-    fprintf(stderr, "[factor] look-up: %s (n %d nnz %d block %d top %d, %zu cached, key %016llx)\n", img ? "hit" : "MISS", A.n,
-            A.nnz(), block, top, g_cache.size(), (unsigned long long)h0);
-  if (!img) {
-    const int rc = build_image(A, block, top, device, &img);
-    if (rc) return rc;
-    if (use_cache) {
-      std::lock_guard<std::mutex> lk(g_mu);
-      g_cache.push_front(CacheSlot{h0, h1, A.n, A.nnz(), block, device, top, img});
-      while (g_cache.size() > 8) g_cache.pop_back();
-    }
-  }
-  const CholSymbolic &S = img->sym;
-  std::lock_guard<std::mutex> image_lock(img->mu);
-  const auto t1 = std::chrono::steady_clock::now();
-  hipStream_t st = nullptr;
-  int rc = stream_acquire(device, &st);
+  int rc = find_or_build_image(A, block, top, device, panels == nullptr, &img, &hit);
   if (rc) return rc;
-  struct Rel {
-    int device;
-    hipStream_t st;
-    ~Rel() { stream_release(device, st); }
-  } rel_guard{device, st};
+  std::lock_guard<std::mutex> image_lock(img->mu);
+  const auto t1 = Clock::now();
+  StreamLease lease(device);
+  rc = lease.acquire();
+  if (rc) return rc;
+  hipStream_t st = lease.st;
   DevBuf<double> local_arena;
   double *F = nullptr;
-  const size_t arena_bytes = (size_t)S.arena * sizeof(double);
-  if (arena_bytes <= arena_keep_bytes()) {
-    if (!img->arena.p) {
-      // the arenas kept by all cached images together stay within the same bound: idle images give theirs up
-      std::lock_guard<std::mutex> lk(g_mu);
-      size_t held = arena_bytes;
-      for (CacheSlot &c : g_cache)
-        if (c.img != img && c.img->arena.p) {
-          held += c.img->arena.n * sizeof(double);
-          if (held > arena_keep_bytes() && c.img->mu.try_lock()) {
-            held -= c.img->arena.n * sizeof(double);
-            c.img->arena.release();
-            c.img->mu.unlock();
-          }
-        }
-    }
-    if (!img->arena.p) DCORA_HIP(img->arena.alloc((size_t)S.arena));
-    F = img->arena.p;
-  } else {
-    DCORA_HIP(local_arena.alloc((size_t)S.arena));
-    F = local_arena.p;
-  }
-  const long long nnz = (long long)S.a_dest.size();
-  const auto t1b = std::chrono::steady_clock::now();
-  const double *vin = img->vals.p;  // what k_chol_scatter reads
-  if (vals_dev) {
-    if (ready) DCORA_HIP(hipStreamWaitEvent(st, ready, 0));
-    vin = vals_dev;
-  } else {
-    const double *vsrc = A.v.data();
-    if (img->vals_pinned) {
-      std::memcpy(img->vals_pinned, A.v.data(), (size_t)nnz * sizeof(double));
-      vsrc = img->vals_pinned;
-    }
-    DCORA_HIP(hipMemcpyAsync(img->vals.p, vsrc, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice, st));
-  }
-  const auto t1x = std::chrono::steady_clock::now();
-  DCORA_HIP(hipMemsetAsync(F, 0, arena_bytes, st));
-  const auto t1y = std::chrono::steady_clock::now();
-  DCORA_HIP(hipMemsetAsync(img->fail.p, 0, sizeof(int), st));
-  DCORA_HIP(hipMemsetAsync(img->logdet.p, 0, sizeof(double), st));
-  hipLaunchKernelGGL(k_chol_scatter, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, st, nnz, img->dest.p, vin, F);
-  for (const Launch &L : img->plan) {
-    const int *list = img->lists.p + L.list;
-    switch (L.kind) {
-      case 0:
-        hipLaunchKernelGGL(k_chol_extend_add, dim3(L.gx, L.gy), dim3(256), 0, st, img->pieces.p, list, img->rel.p, F,
-                           img->fail.p);
-        break;
-      case 1:
-        hipLaunchKernelGGL(k_chol_potrf, dim3(L.gx), dim3(256), 0, st, img->pieces.p, list, L.j0, F, img->linv.p,
-                           img->fail.p, img->logdet.p, 0);
-        break;
-      case 2:
-        DCORA_LAUNCH_MMA(k_chol_trsm, dim3(L.gx, L.gy), st, img->pieces.p, list, L.j0, F, img->linv.p,
-                           img->fail.p);
-        break;
-      default:
-        DCORA_LAUNCH_MMA(k_chol_syrk, dim3(L.gx, L.gy), st, img->pieces.p, list, L.j0, L.kcap, L.ccap, L.ncb, F,
-                           img->fail.p);
-        break;
-    }
-  }
-  DCORA_HIP(hipGetLastError());
-  const auto t1c = std::chrono::steady_clock::now();
+  rc = choose_arena(img, &local_arena, &F);
+  if (rc) return rc;
+  EnqueueClock clk;
+  rc = enqueue_factorisation(*img, st, F, A, vals_dev, ready, &clk);
+  if (rc) return rc;
   int failed = 0;
   double logdet = 0;
-  if (img->vals_pinned) {  // (the verdict comes back through the pinned buffer's tail: see CholImage)
-    double *tail = img->vals_pinned + nnz;
-    DCORA_HIP(hipMemcpyAsync(tail, img->fail.p, sizeof(int), hipMemcpyDeviceToHost, st));
-    DCORA_HIP(hipMemcpyAsync(tail + 1, img->logdet.p, sizeof(double), hipMemcpyDeviceToHost, st));
-    DCORA_HIP(hipStreamSynchronize(st));
-    std::memcpy(&failed, tail, sizeof(int));
-    logdet = tail[1];
-  } else {
-    DCORA_HIP(hipMemcpyAsync(&failed, img->fail.p, sizeof(int), hipMemcpyDeviceToHost, st));
-    DCORA_HIP(hipMemcpyAsync(&logdet, img->logdet.p, sizeof(double), hipMemcpyDeviceToHost, st));
-    DCORA_HIP(hipStreamSynchronize(st));
-  }
+  rc = read_verdict(*img, st, &failed, &logdet);
+  if (rc) return rc;
   *pd = failed == 0;
-  const bool init_timing = env::init_timing();
-  auto tl = std::chrono::steady_clock::now();
-  auto lap = [&](const char *what) {
-    if (!init_timing) return;
-    const auto now = std::chrono::steady_clock::now();
-    fprintf(stderr, "[factor] %-26s %9.1f ms\n", what, std::chrono::duration<double, std::milli>(now - tl).count());
-    tl = now;
-  };
-  if (init_timing)
+  const size_t arena_bytes = (size_t)img->sym.arena * sizeof(double);
+  if (env::init_timing()) {
+    const auto tl = Clock::now();
     fprintf(stderr, "[factor] %-26s %9.1f ms\n[factor] %-26s %9.1f ms (stream + arena %.1f, enqueue %.1f, wait %.1f; arena %.0f MB)\n",
-            "hash + analysis / look-up", std::chrono::duration<double, std::milli>(t1 - t0).count(),
-            "numeric factorisation", std::chrono::duration<double, std::milli>(tl - t1).count(),
-            std::chrono::duration<double, std::milli>(t1b - t1).count(),
-            std::chrono::duration<double, std::milli>(t1c - t1b).count(),
-            std::chrono::duration<double, std::milli>(tl - t1c).count(), arena_bytes / 1e6);
-  if (init_timing)
+            "hash + analysis / look-up", ms_between(t0, t1), "numeric factorisation", ms_between(t1, tl),
+            ms_between(t1, clk.start), ms_between(clk.start, clk.enqueued), ms_between(clk.enqueued, tl), arena_bytes / 1e6);
     fprintf(stderr, "[factor]   enqueue: copy of the values %.2f ms, arena memset %.2f ms, launches %.2f ms\n",
-            std::chrono::duration<double, std::milli>(t1x - t1b).count(),
-            std::chrono::duration<double, std::milli>(t1y - t1x).count(),
-            std::chrono::duration<double, std::milli>(t1c - t1y).count());
-  if (panels && failed == 0) {
-    // hand the factor over by pieces: pack the panels on the device, one copy to the host
-    const int np = (int)S.pieces.size();
-    std::vector<long long> poff((size_t)np + 1, 0);
-    int fmax = 1;
-    for (int s2 = 0; s2 < np; ++s2) {
-      const CholPiece &P = S.pieces[s2];
-      poff[s2 + 1] = poff[s2] + (long long)(P.c + P.m) * P.c;
-      fmax = std::max(fmax, P.c + P.m);
-    }
-    DevBuf<long long> dpoff;
-    DevBuf<double> packed;
-    DCORA_HIP(dpoff.alloc(poff.size()));
-    DCORA_HIP(packed.alloc((size_t)std::max<long long>(1, poff[np])));
-    DCORA_HIP(hipMemcpyAsync(dpoff.p, poff.data(), poff.size() * sizeof(long long), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_chol_pack, dim3(std::min(64, (fmax + 7) / 8), np), dim3(256), 0, st, img->pieces.p, dpoff.p, F,
-                       packed.p);
-    // wide pieces (no hubs): their inverses are formed here, on the device, instead of by the host's threads -- for the
-    // whole 100k lattice 310 Gflop, 7.7 s on the 16 cores of the container
-    // every piece arrives inverted: the narrow ones (c <= 64) by two batched launches, the ones up to 384 columns in one
-    // batch of the right-looking kernels, the wide ones one after the other (on the 16 host cores of the container the
-    // inverses of the whole 100k lattice, 310 Gflop, took 7.7 s)
-    constexpr bool invert_on_device = true, only_wide = false;
-    const int kWide = 384;
-    std::vector<int> wide, narrow;
-    std::vector<long long> moff((size_t)np, -1);
-    long long mtotal = 0;
-    // device sources (asked for by the caller whose weight sink fills on the device): every piece is inverted here, its
-    // M = L11^-T L11^-1 is formed here as well and stays here, like the panels
-    const bool dev_src = panels->want_device_sources && invert_on_device && S.nhub == 0 && !only_wide;
-    DevBuf<double> mall;
-    DevBuf<long long> dmoff;
-    if (dev_src) {
-      for (int s2 = 0; s2 < np; ++s2) {
-        moff[s2] = mtotal;
-        mtotal += (long long)S.pieces[s2].c * S.pieces[s2].c;
-      }
-      DCORA_HIP(mall.alloc((size_t)std::max<long long>(1, mtotal)));
-      DCORA_HIP(dmoff.alloc((size_t)np));
-      DCORA_HIP(hipMemcpyAsync(dmoff.p, moff.data(), (size_t)np * sizeof(long long), hipMemcpyHostToDevice, st));
-    }
-    if (invert_on_device && S.nhub == 0 && !only_wide) {
-      int mmax = 0;
-      for (int s2 = 0; s2 < np; ++s2)
-        if (S.pieces[s2].c <= NB) {
-          narrow.push_back(s2);
-          mmax = std::max(mmax, S.pieces[s2].m);
-        }
-      if (!narrow.empty()) {
-        DevBuf<int> dlist;
-        DCORA_HIP(dlist.alloc(narrow.size()));
-        DCORA_HIP(hipMemcpyAsync(dlist.p, narrow.data(), narrow.size() * sizeof(int), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_small_inv, dim3((unsigned)narrow.size()), dim3(256), 0, st, img->pieces.p, dlist.p, dpoff.p, F,
-                           packed.p, (const long long *)dmoff.p, dev_src ? mall.p : (double *)nullptr);
-        if (mmax > 0)
-          DCORA_LAUNCH_MMA(k_small_w, dim3((mmax + NB - 1) / NB, (unsigned)narrow.size()), st,
-                             img->pieces.p, dlist.p, dpoff.p, F, packed.p);
-        DCORA_HIP(hipStreamSynchronize(st));  // dlist and narrow live on this frame
-      }
-    }
-    // the pieces in between (64 < c < 384: two thousand of them for the whole 100k lattice) in ONE batch of the
-    // right-looking kernels, a piece per blockIdx.z: 15 launches for all of them
-    std::vector<int> mid;
-    if (invert_on_device && S.nhub == 0 && !only_wide) {
-      std::vector<InvJob> jobs;
-      long long yt_total = 0, tinv_total = 0;
-      int nbkmax = 0, mmax = 0, cmax = 0;
-      for (int s2 = 0; s2 < np; ++s2) {
-        const CholPiece &P = S.pieces[s2];
-        if (P.c <= NB || P.c >= kWide) continue;
-        const int nbk = (P.c + NB - 1) / NB;
-        InvJob J;
-        J.c = P.c;
-        J.m = P.m;
-        J.l11 = P.off;
-        J.f = (long long)P.c + P.m;
-        J.yt = yt_total;
-        J.tinv = tinv_total;
-        J.pk = poff[s2];
-        J.mt = dev_src ? moff[s2] : -1;
-        yt_total += (long long)P.c * P.c;
-        tinv_total += (long long)nbk * NB * NB;
-        nbkmax = std::max(nbkmax, nbk);
-        mmax = std::max(mmax, P.m);
-        cmax = std::max(cmax, P.c);
-        jobs.push_back(J);
-        mid.push_back(s2);
-      }
-      if (!jobs.empty()) {
-        const unsigned nj = (unsigned)jobs.size();
-        DevBuf<InvJob> djobs;
-        DevBuf<double> ytm, tinvm;
-        DCORA_HIP(djobs.alloc(jobs.size()));
-        DCORA_HIP(ytm.alloc((size_t)yt_total));
-        DCORA_HIP(tinvm.alloc((size_t)tinv_total));
-        DCORA_HIP(hipMemcpyAsync(djobs.p, jobs.data(), jobs.size() * sizeof(InvJob), hipMemcpyHostToDevice, st));
-        DCORA_HIP(hipMemsetAsync(ytm.p, 0, (size_t)yt_total * sizeof(double), st));
-        hipLaunchKernelGGL(k_tri_inv64, dim3(nbkmax, 1, nj), dim3(256), 0, st, 0, F, 0LL, tinvm.p, djobs.p);
-        for (int ib = 0; ib < nbkmax; ++ib) {
-          DCORA_LAUNCH_MMA(k_dense_trtri_finish, dim3(ib + 1, 1, nj), st, 0, ib, ytm.p, tinvm.p, djobs.p);
-          if (ib + 1 < nbkmax)
-            DCORA_LAUNCH_MMA(k_dense_trtri_update, dim3(nbkmax - ib - 1, ib + 1, nj), st, 0, ib, F, 0LL, ytm.p, djobs.p);
-        }
-        if (mmax > 0)
-          DCORA_LAUNCH_MMA(k_piece_w, dim3((mmax + NB - 1) / NB, nbkmax, nj), st, 0, 0, F, 0LL, ytm.p, packed.p, djobs.p);
-        hipLaunchKernelGGL(k_piece_pack_inverted, dim3(std::min(64, (cmax * cmax + 255) / 256), 1, nj), dim3(256), 0, st, 0,
-                           0, ytm.p, (const double *)nullptr, packed.p, djobs.p);
-        if (dev_src)
-          DCORA_LAUNCH_MMA(k_dense_lauum, dim3(nbkmax * (nbkmax + 1) / 2, 1, nj), st, 0, ytm.p, mall.p, 0, djobs.p);
-        DCORA_HIP(hipGetLastError());
-        DCORA_HIP(hipStreamSynchronize(st));  // the job list and the scratch arenas live on this frame
-      }
-    }
-    if (init_timing) {
-      long cnt[3] = {0, 0, 0};
-      double vol[3] = {0, 0, 0}, c2[3] = {0, 0, 0};
-      for (int s2 = 0; s2 < np; ++s2) {
-        const CholPiece &P = S.pieces[s2];
-        const int b = P.c <= NB ? 0 : (P.c < kWide ? 1 : 2);
-        ++cnt[b];
-        vol[b] += (double)(P.c + P.m) * P.c;
-        c2[b] += (double)P.c * P.c;
-      }
-      fprintf(stderr, "[factor] pieces: narrow %ld (%.0f MB panels, %.0f MB c^2), mid %ld (%.0f MB, %.0f MB), wide %ld (%.0f MB, %.0f MB)\n",
-              cnt[0], vol[0] * 8e-6, c2[0] * 8e-6, cnt[1], vol[1] * 8e-6, c2[1] * 8e-6, cnt[2], vol[2] * 8e-6, c2[2] * 8e-6);
-    }
-    if (invert_on_device && S.nhub == 0)
-      for (int s2 = 0; s2 < np; ++s2)
-        if (S.pieces[s2].c >= kWide) {
-          wide.push_back(s2);
-          // L11^-T L11^-1 of every wide piece: the schedule (host_partinv3.cpp) applies the two triangular
-          // products of a piece as this one symmetric product
-          if (!dev_src) {
-            moff[s2] = mtotal;
-            mtotal += (long long)S.pieces[s2].c * S.pieces[s2].c;
-          }
-        }
-    DevBuf<double> yt, wbuf, tinv, mtop_own;
-    if (!wide.empty()) {
-      long long cmax = 0, wmax = 1;
-      for (int s2 : wide) {
-        cmax = std::max<long long>(cmax, S.pieces[s2].c);
-        wmax = std::max(wmax, (long long)S.pieces[s2].m * S.pieces[s2].c);
-      }
-      DCORA_HIP(yt.alloc((size_t)(cmax * cmax)));
-      DCORA_HIP(wbuf.alloc((size_t)wmax));
-      DCORA_HIP(tinv.alloc((size_t)((cmax + NB - 1) / NB) * NB * NB));
-      if (!dev_src) DCORA_HIP(mtop_own.alloc((size_t)std::max<long long>(1, mtotal)));
-      for (int s2 : wide) {
-        const CholPiece &P = S.pieces[s2];
-        const int c = P.c, m = P.m, nbk = (c + NB - 1) / NB;
-        const long long f = (long long)c + m;
-        const double *L11 = F + P.off;
-        hipLaunchKernelGGL(k_tri_inv64, dim3(nbk), dim3(256), 0, st, c, L11, f, tinv.p);
-        DCORA_HIP(hipMemsetAsync(yt.p, 0, (size_t)c * c * sizeof(double), st));
-        for (int ib = 0; ib < nbk; ++ib) {
-          DCORA_LAUNCH_MMA(k_dense_trtri_finish, dim3(ib + 1), st, c, ib, yt.p, tinv.p);
-          if (ib + 1 < nbk)
-            DCORA_LAUNCH_MMA(k_dense_trtri_update, dim3(nbk - ib - 1, ib + 1), st, c, ib, L11, f, yt.p);
-        }
-        if (m > 0)
-          DCORA_LAUNCH_MMA(k_piece_w, dim3((m + NB - 1) / NB, nbk), st, c, m, L11 + (long long)c * f, f,
-                             yt.p, wbuf.p);
-        hipLaunchKernelGGL(k_piece_pack_inverted, dim3(std::min<long long>(4096, ((f * c) + 255) / 256)), dim3(256), 0,
-                           st, c, m, yt.p, wbuf.p, packed.p + poff[s2]);
-        DCORA_LAUNCH_MMA(k_dense_lauum, dim3(nbk * (nbk + 1) / 2), st, c, yt.p, (dev_src ? mall.p : mtop_own.p) + moff[s2], c);
-      }
-      DCORA_HIP(hipGetLastError());
-    }
-    DCORA_HIP(hipStreamSynchronize(st));
-    lap("pack + wide inverses");
-    // one host block for all panels (and the wide pieces' M): not value-initialised -- the copy below writes every
-    // entry, and zeroing 3 GB first cost 0.76 s for the whole 100k lattice -- and handed to the pieces as views
-    // (2 MB-aligned and advised as huge pages: first touch and release of 3 GB in 4 KB pages cost 0.4 s each)
-    struct HostBlock {
-      double *panels = nullptr, *M = nullptr;
-      void *m_tokens = nullptr;  // reserved, unreadable addresses standing for the M that exist on the device only
-      size_t m_tokens_bytes = 0;
-      DevBuf<double> dev_panels, dev_M;  // device sources of a sink that fills on the device
-      ~HostBlock() {
-        std::free(panels);
-        std::free(M);
-        if (m_tokens) munmap(m_tokens, m_tokens_bytes);
-      }
-    };
-    auto huge_alloc = [](size_t doubles) -> double * {
-      const size_t two_mb = (size_t)2 << 20;
-      const size_t bytes = ((std::max<size_t>(doubles, 1) * sizeof(double) + two_mb - 1) / two_mb) * two_mb;
-      void *p = std::aligned_alloc(two_mb, bytes);
-      if (p) (void)madvise(p, bytes, MADV_HUGEPAGE);
-      return (double *)p;
-    };
-    auto blk = std::make_shared<HostBlock>();
-    blk->panels = huge_alloc((size_t)poff[np]);
-    if (dev_src) {
-      blk->m_tokens_bytes = (size_t)std::max<long long>(1, mtotal) * sizeof(double);
-      void *tok = mmap(nullptr, blk->m_tokens_bytes, PROT_NONE, MAP_PRIVATE | MAP_ANONYMOUS | MAP_NORESERVE, -1, 0);
-      if (tok == MAP_FAILED) {
-        set_last_error("sparse Cholesky: could not reserve the address range of the device-resident M");
-        return DCORA_ERR_HIP;
-      }
-      blk->m_tokens = tok;
-    } else {
-      blk->M = huge_alloc((size_t)mtotal);
-    }
-    if (!blk->panels || (!dev_src && !blk->M)) {
-      set_last_error("sparse Cholesky: no host memory for the factor's panels");
-      return DCORA_ERR_HIP;
-    }
-    double *host = blk->panels, *hostM = dev_src ? (double *)blk->m_tokens : blk->M;
-    // non-zeros of the factor (reported as nnz(L)), counted where the factor is
-    DevBuf<unsigned long long> dnz;
-    DCORA_HIP(dnz.alloc(1));
-    DCORA_HIP(hipMemsetAsync(dnz.p, 0, sizeof(unsigned long long), st));
-    hipLaunchKernelGGL(k_count_nonzero, dim3(2048), dim3(256), 0, st, (long long)poff[np], packed.p, dnz.p);
-    unsigned long long nz_dev = 0;
-    DCORA_HIP(hipMemcpyAsync(&nz_dev, dnz.p, sizeof nz_dev, hipMemcpyDeviceToHost, st));
-    lap("host buffers");
-    DCORA_HIP(hipMemcpyAsync(host, packed.p, (size_t)poff[np] * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (mtotal > 0 && !dev_src)
-      DCORA_HIP(hipMemcpyAsync(hostM, mtop_own.p, (size_t)mtotal * sizeof(double), hipMemcpyDeviceToHost, st));
-    DCORA_HIP(hipStreamSynchronize(st));
-    lap("download");
-    std::vector<char> is_wide((size_t)np, 0);
-    for (int s2 : wide) is_wide[s2] = 1;
-    for (int s2 : narrow) is_wide[s2] = 1;  // narrow pieces arrive inverted as well
-    for (int s2 : mid) is_wide[s2] = 1;     // and so do the ones in between
-    PiecewiseFactor &W = *panels;
-    W = PiecewiseFactor();
-    W.n = S.n;
-    W.nhub = S.nhub;
-    W.perm = S.perm;
-    W.iperm = S.iperm;
-    W.pieces.assign((size_t)np, PieceFactor());
-    W.block = blk;
-    for (int s2 = 0; s2 < np; ++s2) {
-      const CholPiece &P = S.pieces[s2];
-      PieceFactor &pf = W.pieces[s2];
-      pf.c0 = P.c0;
-      pf.c = P.c;
-      pf.rows.assign(S.rows.begin() + P.rows_off, S.rows.begin() + P.rows_off + P.m);
-      pf.panel_view = host + poff[s2];
-      pf.inverted = is_wide[s2] != 0;
-      if (moff[s2] >= 0) pf.Mtop_view = hostM + moff[s2];
-    }
-    W.nnzL = (long)nz_dev;
-    if (dev_src) {
-      W.m_on_device_only = true;
-      W.mirrors.push_back(MirrorRange{host, (long long)poff[np], packed.p});
-      W.mirrors.push_back(MirrorRange{hostM, mtotal, mall.p});
-      blk->dev_panels = std::move(packed);
-      blk->dev_M = std::move(mall);
-    }
-    lap("per-piece copies");
+            ms_between(clk.start, clk.copied), ms_between(clk.copied, clk.zeroed), ms_between(clk.zeroed, clk.enqueued));
   }
-  if (info6) {
-    const auto t2 = std::chrono::steady_clock::now();
-    info6[0] = hit ? 0.0 : img->symbolic_ms;
-    info6[1] = std::chrono::duration<double, std::milli>(t2 - t1).count();
-    info6[2] = (double)arena_bytes;
-    info6[3] = S.flops;
-    info6[4] = (double)S.nlev;
-    info6[5] = (double)img->plan.size();
-    info6[6] = logdet;
-    info6[7] = std::chrono::duration<double, std::milli>(t1 - t0).count();  // pattern hash + cache look-up / analysis
+  if (panels && failed == 0) {
+    rc = hand_over_panels(*img, st, F, panels);
+    if (rc) return rc;
+  }
+  if (info8) {
+    info8[0] = hit ? 0.0 : img->symbolic_ms;
+    info8[1] = ms_between(t1, Clock::now());
+    info8[2] = (double)arena_bytes;
+    info8[3] = img->sym.flops;
+    info8[4] = (double)img->sym.nlev;
+    info8[5] = (double)img->plan.size();
+    info8[6] = logdet;
+    info8[7] = ms_between(t0, t1);  // pattern hash + cache look-up / analysis
   }
   return DCORA_OK;
 }
 }  // namespace
+
+void enqueue_dense_potrf(hipStream_t st, const PieceDev *pieces, const int *list, int count, int k, double *F,
+                         double *linv, int panel_stride, int *fail, double *logdet) {
+  const int nb = (k + NB - 1) / NB;
+  for (int p = 0; p < nb; ++p) {
+    const int j0 = p * NB, jb = std::min(NB, k - j0), rows = k - j0 - jb;
+    double *step_inv = linv + (size_t)p * panel_stride * NB * NB;
+    hipLaunchKernelGGL(k_chol_potrf, dim3(count), dim3(256), 0, st, pieces, list, j0, F, step_inv, fail, logdet, 1);
+    if (rows > 0) {
+      const int T = (rows + NB - 1) / NB;
+      hipLaunchKernelGGL(k_chol_trsm, dim3(T, count), dim3(256), 0, st, pieces, list, j0, F, (const double *)step_inv,
+                         (const int *)fail);
+      hipLaunchKernelGGL(k_chol_syrk, dim3(T * (T + 1) / 2, count), dim3(256), 0, st, pieces, list, j0, j0 + NB, -1, 0, F,
+                         (const int *)fail);
+    }
+  }
+}
 
 int device_chol_is_pd(const HostCsr &A, int block, int device, bool *pd, double *info8) {
   return factor_on_device(A, block, 0, device, pd, info8, nullptr);
@@ -1482,281 +1112,6 @@ int device_chol_piecewise_factor(const HostCsr &A, int block, int top_unknowns, 
     set_last_error("matrix is not positive definite");
     return DCORA_ERR_NOT_PD;
   }
-  return DCORA_OK;
-}
-
-// Scratch arenas of the dense builds, recycled process-wide: hipFree of a few hundred MB takes milliseconds (and waits for
-// the device), and sessions are created again and again (staircase levels, GNC rounds).  At most two idle arenas per
-// process are kept; chol_cache_clear() drops them.
-namespace {
-std::mutex g_scratch_mu;
-struct Scratch {
-  int device;
-  size_t bytes;
-  char *p;
-};
-std::vector<Scratch> g_scratch_idle;
-}  // namespace
-char *scratch_acquire(int device, size_t bytes) {
-  {
-    std::lock_guard<std::mutex> lk(g_scratch_mu);
-    for (size_t i = 0; i < g_scratch_idle.size(); ++i)
-      if (g_scratch_idle[i].device == device && g_scratch_idle[i].bytes >= bytes &&
-          g_scratch_idle[i].bytes <= 4 * bytes + (64u << 20)) {
-        char *p = g_scratch_idle[i].p;
-        g_scratch_idle.erase(g_scratch_idle.begin() + (long)i);
-        return p;
-      }
-  }
-  char *p = nullptr;
-  if (hipMalloc((void **)&p, bytes) != hipSuccess) return nullptr;
-  return p;
-}
-void scratch_release(int device, char *p, size_t bytes) {
-  if (!p) return;
-  {
-    std::lock_guard<std::mutex> lk(g_scratch_mu);
-    if (g_scratch_idle.size() < 2) {
-      g_scratch_idle.push_back(Scratch{device, bytes, p});
-      return;
-    }
-  }
-  (void)hipFree(p);
-}
-namespace {
-std::mutex g_pinned_mu;
-struct Pinned {
-  size_t bytes;
-  char *p;
-};
-std::vector<Pinned> g_pinned_idle;
-}  // namespace
-char *pinned_acquire(size_t bytes) {
-  bytes = (bytes + ((size_t)1 << 20) - 1) & ~(((size_t)1 << 20) - 1);
-  {
-    std::lock_guard<std::mutex> lk(g_pinned_mu);
-    for (size_t i = 0; i < g_pinned_idle.size(); ++i)
-      if (g_pinned_idle[i].bytes >= bytes && g_pinned_idle[i].bytes <= 4 * bytes) {
-        char *p = g_pinned_idle[i].p;
-        g_pinned_idle.erase(g_pinned_idle.begin() + (long)i);
-        return p;
-      }
-  }
-  char *p = nullptr;
-  if (hipHostMalloc((void **)&p, bytes, hipHostMallocDefault) != hipSuccess) {
-    (void)hipGetLastError();
-    return nullptr;
-  }
-  return p;
-}
-void pinned_release(char *p, size_t bytes) {
-  if (!p) return;
-  bytes = (bytes + ((size_t)1 << 20) - 1) & ~(((size_t)1 << 20) - 1);
-  {
-    std::lock_guard<std::mutex> lk(g_pinned_mu);
-    if (bytes <= ((size_t)32 << 20) && g_pinned_idle.size() < 3) {  // (large ones go back: pinned memory is the host's)
-      g_pinned_idle.push_back(Pinned{bytes, p});
-      return;
-    }
-  }
-  (void)hipHostFree(p);
-}
-namespace {
-void scratch_clear() {
-  std::lock_guard<std::mutex> lk(g_scratch_mu);
-  for (Scratch &s : g_scratch_idle) (void)hipFree(s.p);
-  g_scratch_idle.clear();
-}
-}  // namespace
-
-int device_dense_spd_inverse(const HostCsr &A, int device, double *Minv, int ldm, bool *pd) {
-  const int k = A.n;
-  const auto t_in = std::chrono::steady_clock::now();
-  auto lap = [&](const char *what) {
-    if (env::init_timing())
-      fprintf(stderr, "[dense inverse] %-10s at %7.2f ms\n", what,
-              std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_in).count());
-  };
-  DCORA_HIP(hipSetDevice(device));
-  hipStream_t st = nullptr;
-  int rc = stream_acquire(device, &st);
-  if (rc) return rc;
-  struct Rel {
-    int device;
-    hipStream_t st;
-    ~Rel() { stream_release(device, st); }
-  } rel_guard{device, st};
-  const int nb = (k + NB - 1) / NB;
-  // one allocation for everything (hipMalloc / hipFree synchronise the device: agents are set up concurrently)
-  const size_t nnz = A.ci.size();
-  auto up16 = [](size_t bytes) { return (bytes + 15) & ~(size_t)15; };
-  const size_t o_L = 0, o_YT = o_L + up16((size_t)k * k * 8), o_linv = o_YT + up16((size_t)k * k * 8),
-               o_v = o_linv + up16((size_t)nb * NB * NB * 8), o_logdet = o_v + up16(std::max<size_t>(1, nnz) * 8),
-               o_piece = o_logdet + 16, o_rp = o_piece + up16(sizeof(PieceDev)), o_ci = o_rp + up16(((size_t)k + 1) * 4),
-               o_fail = o_ci + up16(std::max<size_t>(1, nnz) * 4), o_list = o_fail + 16, total = o_list + 16;
-  struct Arena {
-    int device;
-    size_t bytes;
-    char *p;
-    ~Arena() { scratch_release(device, p, bytes); }
-  } arena{device, total, scratch_acquire(device, total)};
-  if (!arena.p) {
-    set_last_error("dense inverse: out of device memory");
-    return DCORA_ERR_HIP;
-  }
-  lap("arena");
-  struct {
-    double *p;
-  } L{(double *)(arena.p + o_L)}, YT{(double *)(arena.p + o_YT)}, linv{(double *)(arena.p + o_linv)},
-      v{(double *)(arena.p + o_v)}, logdet{(double *)(arena.p + o_logdet)};
-  struct {
-    int *p;
-  } rp{(int *)(arena.p + o_rp)}, ci{(int *)(arena.p + o_ci)}, fail{(int *)(arena.p + o_fail)},
-      list{(int *)(arena.p + o_list)};
-  struct {
-    PieceDev *p;
-  } piece{(PieceDev *)(arena.p + o_piece)};
-  const PieceDev one{0, k, 0, -1, 0};
-  const int zero_list = 0;
-  DCORA_HIP(hipMemcpyAsync(rp.p, A.rp.data(), ((size_t)k + 1) * sizeof(int), hipMemcpyHostToDevice, st));
-  DCORA_HIP(hipMemcpyAsync(ci.p, A.ci.data(), nnz * sizeof(int), hipMemcpyHostToDevice, st));
-  DCORA_HIP(hipMemcpyAsync(v.p, A.v.data(), nnz * sizeof(double), hipMemcpyHostToDevice, st));
-  DCORA_HIP(hipMemcpyAsync(piece.p, &one, sizeof one, hipMemcpyHostToDevice, st));
-  DCORA_HIP(hipMemcpyAsync(list.p, &zero_list, sizeof(int), hipMemcpyHostToDevice, st));
-  DCORA_HIP(hipMemsetAsync(L.p, 0, o_linv, st));  // L and YT
-  DCORA_HIP(hipMemsetAsync(fail.p, 0, sizeof(int), st));
-  DCORA_HIP(hipMemsetAsync(logdet.p, 0, sizeof(double), st));
-  DCORA_HIP(hipMemsetAsync(Minv, 0, (size_t)k * ldm * sizeof(double), st));
-  hipLaunchKernelGGL(k_dense_scatter, dim3(k), dim3(256), 0, st, k, rp.p, ci.p, v.p, L.p);
-  for (int p = 0; p < nb; ++p) {
-    const int j0 = p * NB, jb = std::min(NB, k - j0), rows = k - j0 - jb;
-    hipLaunchKernelGGL(k_chol_potrf, dim3(1), dim3(256), 0, st, piece.p, list.p, j0, L.p, linv.p + (size_t)p * NB * NB,
-                       fail.p, logdet.p, 1);
-    if (rows > 0) {
-      const int T = (rows + NB - 1) / NB;
-      DCORA_LAUNCH_MMA(k_chol_trsm, dim3(T, 1), st, piece.p, list.p, j0, L.p,
-                         linv.p + (size_t)p * NB * NB, fail.p);
-      DCORA_LAUNCH_MMA(k_chol_syrk, dim3(T * (T + 1) / 2, 1), st, piece.p, list.p, j0, j0 + NB, -1, 0, L.p, fail.p);
-    }
-  }
-  // (a failed factorisation leaves garbage behind the flag: the products below are harmless, the caller drops Minv)
-  for (int ib = 0; ib < nb; ++ib) {
-    DCORA_LAUNCH_MMA(k_dense_trtri_finish, dim3(ib + 1), st, k, ib, YT.p, linv.p);
-    if (ib + 1 < nb)
-      DCORA_LAUNCH_MMA(k_dense_trtri_update, dim3(nb - ib - 1, ib + 1), st, k, ib, L.p, (long long)k,
-                         YT.p);
-  }
-  DCORA_LAUNCH_MMA(k_dense_lauum, dim3(nb * (nb + 1) / 2), st, k, YT.p, Minv, ldm);
-  DCORA_HIP(hipGetLastError());
-  lap("enqueued");
-  int failed = 0;
-  DCORA_HIP(hipMemcpyAsync(&failed, fail.p, sizeof(int), hipMemcpyDeviceToHost, st));
-  DCORA_HIP(hipStreamSynchronize(st));
-  lap("done");
-  *pd = failed == 0;
-  return DCORA_OK;
-}
-
-// The same inverse for a BATCH of matrices of equal size in one set of launches (the agents of a session: five chains of
-// ~130 small dependent launches on five streams do not overlap on this part -- the hardware runs two or three queues at a
-// time, tools/stream_overlap.hip -- so five builds took 20 ms where one takes 3.5).  Every kernel of the single build
-// takes a list / job index: potrf one workgroup per matrix, the panel kernels a grid dimension over the matrices.  The
-// arithmetic per matrix is the single build's, kernel for kernel: the two give the same bits.
-int device_dense_spd_inverse_batch(const std::vector<const HostCsr *> &As, int device, const std::vector<double *> &Minv,
-                                   int ldm, std::vector<char> *pd) {
-  const int B = (int)As.size();
-  if (B == 0) return DCORA_OK;
-  const int k = As[0]->n;
-  for (const HostCsr *A : As)
-    if (A->n != k) {
-      set_last_error("dense inverse batch: matrices of different sizes");
-      return DCORA_ERR_BAD_ARG;
-    }
-  const auto t_in = std::chrono::steady_clock::now();
-  DCORA_HIP(hipSetDevice(device));
-  hipStream_t st = nullptr;
-  int rc = stream_acquire(device, &st);
-  if (rc) return rc;
-  struct Rel {
-    int device;
-    hipStream_t st;
-    ~Rel() { stream_release(device, st); }
-  } rel_guard{device, st};
-  const int nb = (k + NB - 1) / NB;
-  const size_t kk = (size_t)k * k;
-  size_t nnz_max = 1;
-  for (const HostCsr *A : As) nnz_max = std::max(nnz_max, A->ci.size());
-  auto up16 = [](size_t bytes) { return (bytes + 15) & ~(size_t)15; };
-  const size_t o_L = 0, o_YT = o_L + up16(B * kk * 8), o_tinv = o_YT + up16(B * kk * 8),
-               o_v = o_tinv + up16((size_t)B * nb * NB * NB * 8), o_logdet = o_v + up16(B * nnz_max * 8),
-               o_piece = o_logdet + 16, o_jobs = o_piece + up16(sizeof(PieceDev) * B),
-               o_rp = o_jobs + up16(sizeof(InvJob) * B), o_ci = o_rp + up16((size_t)B * (k + 1) * 4),
-               o_fail = o_ci + up16(B * nnz_max * 4), o_list = o_fail + 16, total = o_list + up16(4 * (size_t)B);
-  struct Arena {
-    int device;
-    size_t bytes;
-    char *p;
-    ~Arena() { scratch_release(device, p, bytes); }
-  } arena{device, total, scratch_acquire(device, total)};
-  if (!arena.p) {
-    set_last_error("dense inverse batch: out of device memory");
-    return DCORA_ERR_HIP;
-  }
-  double *L = (double *)(arena.p + o_L), *YT = (double *)(arena.p + o_YT), *tinv = (double *)(arena.p + o_tinv),
-         *v = (double *)(arena.p + o_v), *logdet = (double *)(arena.p + o_logdet);
-  int *rp = (int *)(arena.p + o_rp), *ci = (int *)(arena.p + o_ci), *fail = (int *)(arena.p + o_fail),
-      *list = (int *)(arena.p + o_list);
-  PieceDev *piece = (PieceDev *)(arena.p + o_piece);
-  InvJob *jobs = (InvJob *)(arena.p + o_jobs);
-  std::vector<PieceDev> hp((size_t)B);
-  std::vector<InvJob> hj((size_t)B);
-  std::vector<int> hl((size_t)B);
-  double *Mbase = Minv[0];
-  for (double *q : Minv) Mbase = std::min(Mbase, q);
-  for (int b = 0; b < B; ++b) {
-    hp[(size_t)b] = PieceDev{(long long)(b * kk), k, 0, -1, 0};
-    hj[(size_t)b] = InvJob{k, 0, (long long)(b * kk), (long long)k, (long long)(b * kk), (long long)b * NB * NB, 0,
-                          (long long)(Minv[(size_t)b] - Mbase)};
-    hl[(size_t)b] = b;
-    const HostCsr &A = *As[(size_t)b];
-    DCORA_HIP(hipMemcpyAsync(rp + (size_t)b * (k + 1), A.rp.data(), ((size_t)k + 1) * sizeof(int), hipMemcpyHostToDevice, st));
-    DCORA_HIP(hipMemcpyAsync(ci + (size_t)b * nnz_max, A.ci.data(), A.ci.size() * sizeof(int), hipMemcpyHostToDevice, st));
-    DCORA_HIP(hipMemcpyAsync(v + (size_t)b * nnz_max, A.v.data(), A.ci.size() * sizeof(double), hipMemcpyHostToDevice, st));
-    DCORA_HIP(hipMemsetAsync(Minv[(size_t)b], 0, (size_t)k * ldm * sizeof(double), st));
-  }
-  DCORA_HIP(hipMemcpyAsync(piece, hp.data(), sizeof(PieceDev) * B, hipMemcpyHostToDevice, st));
-  DCORA_HIP(hipMemcpyAsync(jobs, hj.data(), sizeof(InvJob) * B, hipMemcpyHostToDevice, st));
-  DCORA_HIP(hipMemcpyAsync(list, hl.data(), sizeof(int) * B, hipMemcpyHostToDevice, st));
-  DCORA_HIP(hipMemsetAsync(L, 0, o_tinv, st));  // L and YT of every matrix
-  DCORA_HIP(hipMemsetAsync(fail, 0, sizeof(int), st));
-  DCORA_HIP(hipMemsetAsync(logdet, 0, sizeof(double), st));
-  for (int b = 0; b < B; ++b)
-    hipLaunchKernelGGL(k_dense_scatter, dim3(k), dim3(256), 0, st, k, rp + (size_t)b * (k + 1), ci + (size_t)b * nnz_max,
-                       v + (size_t)b * nnz_max, L + b * kk);
-  for (int p = 0; p < nb; ++p) {
-    const int j0 = p * NB, jb = std::min(NB, k - j0), rows = k - j0 - jb;
-    double *step_inv = tinv + (size_t)p * B * NB * NB;  // panel p of matrix b at (p B + b) 64 x 64 blocks
-    hipLaunchKernelGGL(k_chol_potrf, dim3(B), dim3(256), 0, st, piece, list, j0, L, step_inv, fail, logdet, 1);
-    if (rows > 0) {
-      const int T = (rows + NB - 1) / NB;
-      DCORA_LAUNCH_MMA(k_chol_trsm, dim3(T, B), st, piece, list, j0, L, step_inv, fail);
-      DCORA_LAUNCH_MMA(k_chol_syrk, dim3(T * (T + 1) / 2, B), st, piece, list, j0, j0 + NB, -1, 0, L, fail);
-    }
-  }
-  for (int ib = 0; ib < nb; ++ib) {
-    DCORA_LAUNCH_MMA(k_dense_trtri_finish, dim3(ib + 1, 1, B), st, 0, ib, YT, tinv, jobs, B);
-    if (ib + 1 < nb) DCORA_LAUNCH_MMA(k_dense_trtri_update, dim3(nb - ib - 1, ib + 1, B), st, 0, ib, L, 0LL, YT, jobs);
-  }
-  DCORA_LAUNCH_MMA(k_dense_lauum, dim3(nb * (nb + 1) / 2, 1, B), st, 0, YT, Mbase, ldm, jobs);
-  DCORA_HIP(hipGetLastError());
-  int failed = 0;
-  DCORA_HIP(hipMemcpyAsync(&failed, fail, sizeof(int), hipMemcpyDeviceToHost, st));
-  DCORA_HIP(hipStreamSynchronize(st));
-  // (one flag for the batch: a failure anywhere stops every later launch, the caller then builds one by one)
-  pd->assign((size_t)B, failed == 0 ? 1 : 0);
-  if (env::init_timing())
-    fprintf(stderr, "[dense inverse] batch of %d (k = %d) in %.2f ms\n", B, k,
-            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_in).count());
   return DCORA_OK;
 }
 
