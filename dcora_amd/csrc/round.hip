@@ -66,14 +66,30 @@ __device__ void so_project(double (&A)[D * D]) {
 #pragma unroll
   for (int j = 1; j < D; ++j)
     if (sig[j] < sig[jmin]) jmin = j;
-  // rank-deficient blocks do not occur on iterates of the solver (Y_i has orthonormal columns and R0 is a
-  // d-frame); a zero column is left as it is
 #pragma unroll
   for (int j = 0; j < D; ++j)
     if (sig[j] > 0) {
       const double inv = 1.0 / sig[j];
 #pragma unroll
       for (int i = 0; i < D; ++i) A[j * D + i] *= inv;
+    }
+  // a block of rank D - 1 (R0^T Y_i = diag(1, 0) for R0 = [e1 e2], Y_i = [e1 e3]) leaves one zero column: the frame is
+  // completed by the direction orthogonal to the others, which is then the least singular direction, so the flip
+  // below picks its sign.  (Rank <= D - 2 has no nearest rotation; such a block stays singular.)
+#pragma unroll
+  for (int j = 0; j < D; ++j)
+    if (!(sig[j] > 0)) {
+      jmin = j;
+      if (D == 2) {
+        const int o = 1 - j;
+        A[j * D + 0] = -A[o * D + 1];
+        A[j * D + 1] = A[o * D + 0];
+      } else {
+        const int a = (j + 1) % D, b = (j + 2) % D;
+        A[j * D + 0] = A[a * D + 1] * A[b * D + 2] - A[a * D + 2] * A[b * D + 1];
+        A[j * D + 1] = A[a * D + 2] * A[b * D + 0] - A[a * D + 0] * A[b * D + 2];
+        A[j * D + 2] = A[a * D + 0] * A[b * D + 1] - A[a * D + 1] * A[b * D + 0];
+      }
     }
   double P[D * D];
 #pragma unroll
