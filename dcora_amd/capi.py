@@ -231,6 +231,7 @@ SIGNATURES = {
     "dcora_debug_tcg_run_fault": (C.c_int, [C.c_int]),
     "dcora_debug_tcg_run_fault_at": (C.c_int, [C.c_int, C.c_int]),
     "dcora_debug_wg_sums": (C.c_int, [C.c_int, _dp, _dp]),
+    "dcora_debug_run_image": (C.c_int, [C.c_int, C.c_int, _ip, _ip, _PI]),
     "dcora_problem_solver_info": (C.c_int, [_vp, _dp]),
     "dcora_ra_rbcd_create": (C.c_int, [_vp, C.POINTER(RbcdOptions), C.POINTER(_vp)]),
     "dcora_ra_rbcd_destroy": (C.c_int, [_vp]),

@@ -321,6 +321,14 @@ int dcora_debug_wg_sums(int nv, const double *in, double *out) {
     return DCORA_OK;
   });
 }
+int dcora_debug_run_image(int r, int k, int *off, int *lanes, int *bytes) {
+  return abi_call({off, lanes, bytes}, [&]() -> int {
+    const int b = tcg_run_image_map(r, k, off, lanes);
+    if (b < 0) return bad("dcora_debug_run_image: r is 4, 5 or 6 and 1 <= k <= 2048");
+    *bytes = b;
+    return DCORA_OK;
+  });
+}
 int dcora_problem_time_precond(dcora_problem_t p, int reps, double *avg_ms, double *bytes) {
   return abi_call({p, avg_ms, bytes}, [&] { return p->p.time_precond(reps, avg_ms, bytes); });
 }

@@ -24,7 +24,7 @@ namespace {
 // zero register whose sums nobody stores).  Levels 3 and 4 (L ^ 4, L ^ 8) are the two quad_perm butterflies on what is
 // left.  The logical row (l5 l4) is (p3 p2): the lane with p1 = p0 = 0 of every quad holds the row sums of the values
 // 4 j + 2 p4 + p5 (register j).  Same pairs, same order, IEEE addition commutes: bitwise the butterfly's row sums.
-__device__ __forceinline__ int wg_sums_logical_lane(int p) { return ((p >> 5) & 1) | ((p >> 3) & 2) | ((p & 15) << 2); }
+__host__ __device__ __forceinline__ int wg_sums_logical_lane(int p) { return ((p >> 5) & 1) | ((p >> 3) & 2) | ((p & 15) << 2); }
 template <bool HALF32>
 __device__ __forceinline__ double wg_sums_swap_add(double x, double y) {
   typedef unsigned u2 __attribute__((ext_vector_type(2)));
@@ -81,6 +81,17 @@ __device__ __forceinline__ void wg_row_sums(const double (&v)[NV], double (*sP)[
 constexpr int kRunShards = 32, kRunCopies = 64, kRunStride = 32;  // sync words 128 B apart
 constexpr int kRunSyncWords = (kRunShards + 1 + kRunCopies + 1) * kRunStride;
 constexpr int kRunQCap = 1024;  // CSR entries of a workgroup's 2 (d+1) matrix rows staged in LDS once per run
+constexpr int kRunNS = 4;       // 128-column steps per wave held in registers: k <= 4 * 4 * 128 = 2048
+// ---- where the residual image lies in LDS ----
+// Pair i (doubles 2 i, 2 i + 1 of the column-major residual) lies at byte run_img_off(i) of the dynamic LDS: every write
+// of the image (first staging, zero fill, the update per iteration) and the product's reads go through it, and
+// tests/test_run_image_cpu.py enumerates from it which 16-byte slots of the 256-byte bank row a group of 16 lanes
+// hits.  The map is the plain one.  With wg_row_sums' lane map the product's ds_read_b128 are 2-way conflicted at
+// r = 5 (8-way at r = 4, 4-way at r = 6); one 16-byte pad behind every 160 pairs makes the r = 5 reads and writes
+// conflict-free, and was measured slower: the pad's place depends on the thread, so every piece of the update pays for
+// its address (profiles/run_image.txt).  Behind the image lies one spare pair (the update's threads without a pair).
+__host__ __device__ constexpr int run_img_off(int i) { return 16 * i; }
+constexpr size_t run_img_bytes(int r, int cpad) { return (size_t)run_img_off(cpad * r / 2) + 16; }
 struct TcgRunArgs {
   ManiDesc m;
   int ldm;
@@ -91,7 +102,7 @@ struct TcgRunArgs {
   unsigned *sync;  // zeroed by the single-block kernel in front of the run (k_rtr_init / k_rtr_decide)
   SolverCtl *ctl;
   HostFlags *hf;
-  int seq, pbA;    // pbA: poses per workgroup of k_fused_hess at this r (the tree its <delta, H delta> partials follow)
+  int seq;
   int fault;       // test hook (dcora_debug_tcg_run_fault): workgroup 0 leaves before the first grid step
 #ifdef DCORA_RUN_STAMPS
   long long *stamps;  // profiling build only: wall_clock64 of workgroup 0 at the phase boundaries of a run
@@ -134,19 +145,30 @@ constexpr unsigned kRunAbortBit = 0x80000000u;
 __device__ __forceinline__ bool run_grid_step(unsigned *sync, unsigned step, int *s_ok) {
   __builtin_amdgcn_s_waitcnt(0);  // this wave's write-through stores are acknowledged
   __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned *shard = sync, *top = sync + kRunShards * kRunStride, *done = top + kRunStride,
-             *abort_w = done + kRunCopies * kRunStride;
+  // wave 0 enters the arrival: lane 0 counts, and where it completed the count with the abort bit clear the wave's 64
+  // lanes publish the 64 copies of the done word with ONE store instruction (lane 0 alone stored them one after the
+  // other, and the workgroups polling the late copies left that much later); polling and giving up stay on lane 0
+  static_assert(kRunCopies == 64, "one copy of the done word per lane of wave 0");
+  if (threadIdx.x < 64) {
+    unsigned *shard = sync, *top = sync + kRunShards * kRunStride, *done = top + kRunStride;
     const int i = blockIdx.x, G = gridDim.x, sh = i % kRunShards;
     const unsigned in_shard = (unsigned)((G - sh + kRunShards - 1) / kRunShards), want = step + 1;
     const unsigned shards_used = (unsigned)(G < kRunShards ? G : kRunShards);
-    const unsigned a = __hip_atomic_fetch_add(shard + sh * kRunStride, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (a + 1 == want * in_shard) {
-      const unsigned b = __hip_atomic_fetch_add(top, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (!(b & kRunAbortBit) && b + 1 == want * shards_used)
-        for (int c = 0; c < kRunCopies; ++c)
-          __hip_atomic_store(done + c * kRunStride, want, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    int last = 0;
+    if (threadIdx.x == 0) {
+      const unsigned a = __hip_atomic_fetch_add(shard + sh * kRunStride, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (a + 1 == want * in_shard) {
+        const unsigned b = __hip_atomic_fetch_add(top, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        last = !(b & kRunAbortBit) && b + 1 == want * shards_used;
+      }
     }
+    if (__builtin_amdgcn_readfirstlane(last))
+      __hip_atomic_store(done + threadIdx.x * kRunStride, want, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  if (threadIdx.x == 0) {
+    unsigned *top = sync + kRunShards * kRunStride, *done = top + kRunStride, *abort_w = done + kRunCopies * kRunStride;
+    const int i = blockIdx.x, G = gridDim.x;
+    const unsigned want = step + 1, shards_used = (unsigned)(G < kRunShards ? G : kRunShards);
     long long t0 = wall_clock64();
     const unsigned *p = done + (i % kRunCopies) * kRunStride;
     int ok = 1;
@@ -191,10 +213,15 @@ __device__ __forceinline__ bool run_grid_step(unsigned *sync, unsigned step, int
 template <int D, int R, int NS>
 __global__ __launch_bounds__(kPcBlock) void k_tcg_run(TcgRunArgs a) {
   constexpr int DH = D + 1, PB = 2, NR = PB * DH, RM = R;
-  // the residual image, column-major as in memory: cpad * R doubles, kept for the run; 16-byte aligned, so the 2 R
-  // doubles a lane takes per step (16 R bytes from a multiple of 16 R) are read 16 bytes at a time
+  // pieces of kPcBlock pairs that hold the largest residual of the form (NS * kPcNW * 128 columns of R doubles): 4 R of
+  // them; the per-iteration update of the image takes them kImgGroup at a time
+  constexpr int kImgGroup = R == 6 ? 1 : 4;
+  constexpr int kImgPieces = kImgGroup == 1 ? kPcSB : NS * kPcNW * 128 * R / 2 / kPcBlock;
+  static_assert(kImgPieces <= kPcSB && kImgPieces % kImgGroup == 0, "the image's pieces come in whole groups");
+  // the residual image, column-major as in memory: cpad * R doubles in pairs of 16 bytes at run_img_off, kept for the
+  // run; 16-byte aligned, so the 2 R doubles a lane takes per step are read 16 bytes at a time
   extern __shared__ __align__(16) double s_img[];
-  double *const s_res = s_img;
+  auto img_pair = [&](int i) { return reinterpret_cast<double2 *>(s_img) + run_img_off(i) / 16; };
   __shared__ double s_P[NR * RM + 1][4 * kPcNW];
   __shared__ double s_Z[NR * RM + 1], s_R[NR * RM], s_W[NR * RM], s_D[NR * RM], s_H[NR * RM];
   __shared__ double s_red[16];
@@ -285,7 +312,7 @@ __global__ __launch_bounds__(kPcBlock) void k_tcg_run(TcgRunArgs a) {
     for (int u = 0; u < NS; ++u) {
       const int sidx = wave_u + kPcNW * u;
       if (sidx < nstep) {
-        const double2 *__restrict__ xs = reinterpret_cast<const double2 *>(s_img) + (size_t)(sidx * 64 + llane) * r;
+        const double2 *__restrict__ xs = img_pair((sidx * 64 + llane) * r);
         double x[2 * RM];  // x[tq]: column 2 llane, x[r + tq]: column 2 llane + 1
 #pragma unroll
         for (int tq = 0; tq < RM; ++tq) {
@@ -395,10 +422,10 @@ __global__ __launch_bounds__(kPcBlock) void k_tcg_run(TcgRunArgs a) {
       const double2 x = xg[u];
       nrm2 = fma(x.x, x.x, nrm2);
       nrm2 = fma(x.y, x.y, nrm2);
-      reinterpret_cast<double2 *>(s_res)[i] = x;
+      *img_pair(i) = x;  // (the upper half of the last pair of an odd count reads as zero: the buffer ends there)
     }
   }
-  for (long i = 2L * npair + threadIdx.x; i < (long)cpad * r; i += kPcBlock) s_res[i] = 0.0;
+  for (int i = npair + (int)threadIdx.x; i < cpad * r / 2; i += kPcBlock) *img_pair(i) = double2{0.0, 0.0};
   if (own) s_R[lc * RM + t] = o_r;
   __syncthreads();
   RUN_STAMP(1);
@@ -502,34 +529,37 @@ __global__ __launch_bounds__(kPcBlock) void k_tcg_run(TcgRunArgs a) {
         const double rs = row16_sum_dpp(dacc);  // the 16-lane row sum k_fused_hess's block sum starts from
         if (lane == 0) st_coh(a.p1r + blockIdx.x, rs);
       }
-      __syncthreads();
-      if (own) o_h = s_H[e];
     }
     RUN_STAMP(sb0 + 1);
-    if (!run_grid_step(a.sync, gstep++, &s_ok)) return give_up();
+    if (!run_grid_step(a.sync, gstep++, &s_ok)) return give_up();  // (its barriers also order s_H for the read below)
     RUN_STAMP(sb0 + 2);
     // ======== PC: step length, updates, z = Proj_X(res Minv), stopping rules ========
-    double2 xh[kPcSB];
+    // the row sums of <delta, H delta> are requested ahead of the all-gather of H delta: loads return in the order of
+    // their requests, so d_Hd, alpha, the boundary test and the own updates are done while the all-gather is still
+    // landing, and its pieces go into the image in ascending u as they arrive
+    constexpr int rows_per = fused_pb(R, DH) / 2;  // rows of a k_fused_hess workgroup at this r: 8, 6, 5
+    static_assert(rows_per <= 8, "the row sums of one k_fused_hess workgroup are loaded as 8 values");
+    const int nrows = gridDim.x, nblk = (nrows + rows_per - 1) / rows_per;
+    double rs16[16];
+    {
+      const int b0 = min(lane, nblk - 1) * rows_per;  // (lanes beyond the partials load the last one's and drop it)
 #pragma unroll
-    for (int u = 0; u < kPcSB; ++u) xh[u] = pc_ld16_coh(rs_h, voff_t, (unsigned)u * kPcBlock * 16u);
+      for (int ri = 0; ri < 16; ++ri) rs16[ri] = (ri < rows_per && b0 + ri < nrows) ? ld_coh(a.p1r + b0 + ri) : 0.0;
+    }
+    __builtin_amdgcn_sched_barrier(0);  // (nothing of the all-gather is requested ahead of the row sums)
+    double2 xh[kImgPieces];
+#pragma unroll
+    for (int u = 0; u < kImgPieces; ++u) xh[u] = pc_ld16_coh(rs_h, voff_t, (unsigned)u * kPcBlock * 16u);
+    __builtin_amdgcn_sched_barrier(0);
+    if (own) o_h = s_H[e];
     double d_Hd;
     {
       // k_fused_hess's partial of workgroup w: rows 2 w' .. of its pbA poses, wave by wave; then the wave sum over them
-      const int rows_per = a.pbA / 2, nrows = gridDim.x, nblk = (nrows + rows_per - 1) / rows_per;
       double part = 0;
       if (lane < nblk) {
-        const int b0 = lane * rows_per;
-        double wsum[4] = {0, 0, 0, 0};
+        double wsum[4];
 #pragma unroll
-        for (int w = 0; w < 4; ++w) {
-          double rs4[4];
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const int ri = w * 4 + q;
-            rs4[q] = (ri < rows_per && b0 + ri < nrows) ? ld_coh(a.p1r + b0 + ri) : 0.0;
-          }
-          wsum[w] = (rs4[0] + rs4[1]) + (rs4[2] + rs4[3]);
-        }
+        for (int w = 0; w < 4; ++w) wsum[w] = (rs16[4 * w] + rs16[4 * w + 1]) + (rs16[4 * w + 2] + rs16[4 * w + 3]);
         double tsum = 0;
 #pragma unroll
         for (int w = 0; w < 4; ++w) tsum += wsum[w];
@@ -559,17 +589,46 @@ __global__ __launch_bounds__(kPcBlock) void k_tcg_run(TcgRunArgs a) {
       s_R[lc * RM + t] = rr;
     }
     RUN_STAMP(sb0 + 3);
+    // res += alpha H delta, kImgGroup pieces at a time without a branch among them: the LDS reads of a group are in
+    // flight together (piece by piece, each behind a test of its own, the update was one LDS round trip per piece).  A
+    // thread whose pair lies beyond the residual goes through the spare pair behind the image and adds nothing
     nrm2 = 0;
+    if constexpr (kImgGroup == 1) {  // (r = 6: no registers for a group; the pieces one by one, as ever)
 #pragma unroll
-    for (int u = 0; u < kPcSB; ++u) {
-      const int i = u * kPcBlock + (int)threadIdx.x;
-      if (i < npair) {
-        double2 x = reinterpret_cast<double2 *>(s_res)[i];
-        x.x = fma(alpha, xh[u].x, x.x);
-        x.y = fma(alpha, xh[u].y, x.y);
-        nrm2 = fma(x.x, x.x, nrm2);
-        nrm2 = fma(x.y, x.y, nrm2);
-        reinterpret_cast<double2 *>(s_res)[i] = x;
+      for (int u = 0; u < kImgPieces; ++u) {
+        const int i = u * kPcBlock + (int)threadIdx.x;
+        if (i < npair) {
+          double2 x = *img_pair(i);
+          x.x = fma(alpha, xh[u].x, x.x);
+          x.y = fma(alpha, xh[u].y, x.y);
+          nrm2 = fma(x.x, x.x, nrm2);
+          nrm2 = fma(x.y, x.y, nrm2);
+          *img_pair(i) = x;
+        }
+      }
+    } else {
+#pragma unroll
+      for (int u0 = 0; u0 < kImgPieces; u0 += kImgGroup) {
+        if (u0 * kPcBlock < npair) {
+          double2 *pp[kImgGroup];
+          double2 x[kImgGroup];
+#pragma unroll
+          for (int j = 0; j < kImgGroup; ++j) {
+            const int i = (u0 + j) * kPcBlock + (int)threadIdx.x;
+            pp[j] = i < npair ? img_pair(i) : img_pair(cpad * r / 2);
+            x[j] = *pp[j];
+          }
+          __builtin_amdgcn_sched_barrier(0);  // (every read of the group is requested before the first is waited for)
+#pragma unroll
+          for (int j = 0; j < kImgGroup; ++j) {
+            x[j].x = fma(alpha, xh[u0 + j].x, x[j].x);
+            x[j].y = fma(alpha, xh[u0 + j].y, x[j].y);
+            const double n2 = fma(x[j].y, x[j].y, fma(x[j].x, x[j].x, nrm2));
+            nrm2 = (u0 + j) * kPcBlock + (int)threadIdx.x < npair ? n2 : nrm2;
+          }
+#pragma unroll
+          for (int j = 0; j < kImgGroup; ++j) *pp[j] = x[j];
+        }
       }
     }
     __syncthreads();
@@ -635,7 +694,6 @@ __global__ __launch_bounds__(kPcBlock) void k_debug_wg_sums(const double *__rest
 }  // namespace
 
 // ---- the one-launch tCG run ------------------------------------------------------------------------------
-constexpr int kRunNS = 4;  // 128-column steps per wave held in registers: k <= 4 * 4 * 128 = 2048
 int tcg_run_sync_words() { return kRunSyncWords; }
 std::atomic<int> g_tcg_run_fault{0};
 std::atomic<int> g_tcg_run_fault_skip{0};
@@ -663,7 +721,7 @@ template <int R>
 static int tcg_run_launch(hipStream_t st, const TcgRunArgs &a) {
   static LdsGrant grant;
   const int cpad = ((a.m.k + 127) / 128) * 128;
-  const size_t lds = (size_t)cpad * R * sizeof(double);
+  const size_t lds = run_img_bytes(R, cpad);
   if (!grant.granted(reinterpret_cast<const void *>(&k_tcg_run<3, R, kRunNS>), lds, 40 * 1024)) return -1;
   const int grid = (a.m.n + 1) / 2;
   hipLaunchKernelGGL((k_tcg_run<3, R, kRunNS>), dim3(grid), dim3(kPcBlock), lds, st, a);
@@ -686,7 +744,7 @@ int launch_tcg_run(hipStream_t st, const TcgOperands &o, int seq) {
     }
   const ManiDesc &m = o.m;
   TcgRunArgs a{m, o.ldm, o.Minv, o.Q, o.grad, o.X, o.S, o.d[0], o.d[1], o.Hd, o.eta, o.Heta, o.z, o.p1, o.p3, o.pC,
-               o.sync, o.ctl, o.hf, seq, fused_pb(m.r, m.d + 1), fault};
+               o.sync, o.ctl, o.hf, seq, fault};
 #ifdef DCORA_RUN_STAMPS
   {
     static long long *buf = nullptr;
@@ -724,6 +782,13 @@ int launch_debug_wg_sums(hipStream_t st, int nv, const double *in, double *out) 
   else if (nv == 49) hipLaunchKernelGGL((k_debug_wg_sums<49>), dim3(1), dim3(kPcBlock), 0, st, in, out);
   else return -1;
   return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+int tcg_run_image_map(int r, int k, int *off, int *lanes) {
+  if (r < 4 || r > 6 || k < 1 || k > kRunNS * kPcNW * 128) return -1;
+  const int cpad = ((k + 127) / 128) * 128;
+  for (int i = 0; i < cpad * r / 2; ++i) off[i] = run_img_off(i);
+  for (int p = 0; p < 64; ++p) lanes[p] = wg_sums_logical_lane(p);
+  return (int)run_img_bytes(r, cpad);
 }
 
 }  // namespace dcora

@@ -316,6 +316,10 @@ int launch_tcg_run(hipStream_t st, const TcgOperands &o, int seq);
 // test entry: one workgroup of 256 threads sums nv = 8 r + 1 (r = 4, 5, 6) values per lane with k_tcg_run's reduce-scatter
 // row sums and with the DPP butterfly; in: nv x 256 (device), out: 2 x (nv x 16 row sums + nv totals); < 0: refused
 int launch_debug_wg_sums(hipStream_t st, int nv, const double *in, double *out);
+// test entry (host only): where k_tcg_run keeps its residual image in LDS at rank r and k columns.  off: the byte offset
+// of each of the ceil(k / 128) * 64 r pairs of doubles; lanes: the logical lane of each of a wave's 64 lanes in the
+// product.  Returns the bytes of dynamic LDS the launch asks for; < 0: no run form at these sizes
+int tcg_run_image_map(int r, int k, int *off, int *lanes);
 bool fused_pc_preferred(const ManiDesc &m, int ldm);  // sizes at which it beats B + C
 bool fused_pc_ready(const ManiDesc &m, int ldm);      // the current device grants the kernel its dynamic LDS
 // retract: the launch that ends a tCG run retracts and leaves its {<eta, grad>, <eta, H eta>} partials in pC

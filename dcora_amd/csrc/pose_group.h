@@ -251,7 +251,7 @@ constexpr int kBsrTile = 160;                // matrix blocks staged per pass (2
 
 // poses per block of the two-phase kernels: phase 1 runs one thread per output element (pose, column, row),
 // phase 2 eight lanes per pose
-__host__ __device__ inline int fused_pb(int r, int dh) {
+__host__ __device__ constexpr int fused_pb(int r, int dh) {
   const int pb = kBlock / (dh * r);
   return pb > kPosesPerBlock ? kPosesPerBlock : pb;
 }

@@ -126,6 +126,11 @@ int dcora_debug_tcg_run_fault_at(int skip, int runs);
  * four-step DPP butterfly.  out (host, 2 * nv * 17 doubles): for each of the two, in that order, the nv x 16 row sums
  * (out[i * 16 + 4 * wave + row]) followed by the nv totals of the serial add over the 16. */
 int dcora_debug_wg_sums(int nv, const double *in, double *out);
+/* test hook (host only, no device needed): the LDS image of the one-launch tCG run at rank r (4, 5, 6) and k <= 2048
+ * columns.  off (ceil(k / 128) * 64 * r ints): the byte offset of every pair of doubles of the column-major residual;
+ * lanes (64 ints): the logical lane (columns 2 L, 2 L + 1 of a 128-column step) of each lane of a wave in the product;
+ * bytes: the dynamic LDS the launch asks for. */
+int dcora_debug_run_image(int r, int k, int *off, int *lanes, int *bytes);
 /* PreCondition (ref :70-84, 261-297) */
 int dcora_problem_precondition(dcora_problem_t p, const double *X, const double *V, double *out);
 /* Retract (ref :125-136, 236-259) */
