@@ -4,7 +4,8 @@ src/DCORA_utils.cpp:1737-1747 isSparseSymmetricMatrixPSD = "CHOLMOD's LL^T succe
 CPU: the symbolic analysis (ordering, closed piece structures, scatter map, level / slot schedule) executed by plain
 host loops reproduces P A P^T = L L^T.  GPU: verdict against the oracle's and the host factorisation's, log det of
 the factored matrix against scipy's sparse LU, on the reference's datasets; the positive verdict at BASELINE config 5's
-full size (400 000 unknowns), which the host factorisation cannot deliver."""
+full size (400 000 unknowns), which the host factorisation cannot deliver.  ONE non-positive pivot, late, in a chosen
+structure, and the log-determinant against an exact value: test_exact_factors_gpu.py."""
 import os
 
 import numpy as np
