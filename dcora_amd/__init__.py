@@ -119,7 +119,8 @@ class RADataset:
     Q: ref src/Graph.cpp:824-1188).  X is r x k in the RA ordering [Y1..Yn | s1..sl | p1..pn | L1..Lb]."""
 
     def handle(self):
-        """a fresh dcora_radataset_t of the file (the caller destroys it)"""
+        """a fresh dcora_radataset_t of the file, with the pose-pose weights of set_pose_pose_weights if any (the caller
+        destroys it)"""
         L = capi.lib()
         path, tmp = self.path, None
         if str(path).endswith(".gz"):
@@ -133,6 +134,12 @@ class RADataset:
         finally:
             if tmp:
                 os.unlink(tmp)
+        w = getattr(self, "pose_pose_weights", None)
+        if w is not None:
+            st = L.dcora_radataset_set_pose_pose_weights(h, w)
+            if st:
+                L.dcora_radataset_destroy(h)
+                check(st)
         return h
 
     def __init__(self, path, init_seed=20250310):
@@ -170,6 +177,51 @@ class RADataset:
             check(L.dcora_radataset_agent_columns(h, rb, dims3, vp(own), C.byref(ka)))
             self.agent_columns[rb] = (tuple(int(x) for x in dims3), own[:ka.value].copy())
         L.dcora_radataset_destroy(h)
+
+    def loop_closures(self):
+        """one flag per pose-pose measurement (the order of dcora_radataset_copy): True for a loop closure, False for
+        odometry -- both poses of one robot and consecutive in its own numbering (as driver.loop_closure_mask)"""
+        h = self.handle()
+        try:
+            mask = np.zeros(max(self.num_pose_pose, 1), np.int32)
+            check(capi.lib().dcora_radataset_loop_closures(h, mask))
+        finally:
+            capi.lib().dcora_radataset_destroy(h)
+        return mask[:self.num_pose_pose].astype(bool)
+
+    def set_pose_pose_weights(self, w):
+        """the weights of the pose-pose measurements (each finite and >= 0): kept by this object, applied to every
+        handle() -- so every session created afterwards sees them -- and to Q, which is rebuilt.  None: the file's (1)."""
+        if w is not None:
+            w = np.ascontiguousarray(w, np.float64).copy()
+            if w.shape != (self.num_pose_pose,):
+                raise ValueError("set_pose_pose_weights needs one weight per pose-pose measurement")
+        old = getattr(self, "pose_pose_weights", None)
+        self.pose_pose_weights = w
+        try:
+            h = self.handle()
+        except Exception:
+            self.pose_pose_weights = old
+            raise
+        try:
+            q = C.c_void_p()
+            check(capi.lib().dcora_radataset_build_Q(h, C.byref(q)))
+            self.Q = Csr(*capi.take_csr(q))
+        finally:
+            capi.lib().dcora_radataset_destroy(h)
+
+    def pose_pose(self):
+        """(ids m_pp x 2, vals m_pp x (d*d + d + 3): R column-major, t, kappa, tau, weight) as dcora_radataset_copy
+        writes the pose-pose measurements"""
+        h = self.handle()
+        try:
+            m, wd = self.num_pose_pose, self.d * self.d + self.d + 3
+            ids, vals = np.zeros((max(m, 1), 2), np.int32), np.zeros((max(m, 1), wd))
+            vp = lambda a: a.ctypes.data_as(C.c_void_p)
+            check(capi.lib().dcora_radataset_copy(h, vp(ids), vp(vals), None, None, None, None))
+        finally:
+            capi.lib().dcora_radataset_destroy(h)
+        return ids[:m], vals[:m]
 
     def colours(self):
         """(colours, number of colours) of the agents -- the robots owning poses, in id order -- as a session of this
@@ -877,8 +929,13 @@ class RaRbcdSession:
     """the agents of a multi-robot range-aided SLAM problem + the synchronous RBCD++ driver on the device
     (ref examples/MultiRobotExample_RASLAM.cpp); X is the merged r x k matrix in the RA ordering"""
 
-    def __init__(self, ra, r, acceleration=True, restart_interval=30, params=None, device=0, rank=0, world_size=1):
+    def __init__(self, ra, r, acceleration=True, restart_interval=30, params=None, device=0, rank=0, world_size=1,
+                 robust=None, fixed_weight=None):
+        """robust: a robust.RobustCostParameters -> a session whose pose-pose weights update in place (update_weights /
+        set_weights / get_weights / robust_info, as RbcdSession's); it starts with weight 1 on every loop closure
+        (ra.loop_closures()) whose fixed_weight flag (one per pose-pose measurement, default none) is off"""
         self.ra, self.r, self.k = ra, r, ra.k
+        self.m = ra.num_pose_pose
         o = RbcdOptions()
         capi.lib().dcora_rbcd_options_default(C.byref(o))
         o.r, o.acceleration, o.restart_interval, o.device = r, int(acceleration), restart_interval, device
@@ -888,7 +945,17 @@ class RaRbcdSession:
         dsh = ra.handle()
         self.h = C.c_void_p()
         try:
-            check(capi.lib().dcora_ra_rbcd_create(dsh, C.byref(o), C.byref(self.h)))
+            if robust is None:
+                check(capi.lib().dcora_ra_rbcd_create(dsh, C.byref(o), C.byref(self.h)))
+            else:
+                fx = None
+                if fixed_weight is not None:
+                    fx = np.ascontiguousarray(fixed_weight, np.int32)
+                    if fx.shape != (self.m,):
+                        raise ValueError("fixed_weight needs one flag per pose-pose measurement")
+                check(capi.lib().dcora_ra_rbcd_create_robust(dsh, C.byref(o), C.byref(robust.c),
+                                                             None if fx is None else fx.ctypes.data_as(C.c_void_p),
+                                                             C.byref(self.h)))
         finally:
             capi.lib().dcora_radataset_destroy(dsh)
         n = C.c_int()
@@ -965,6 +1032,29 @@ class RaRbcdSession:
         r = ROptResult()
         check(capi.lib().dcora_ra_rbcd_last_result(self.h, C.byref(r)))
         return r.as_dict()
+
+    # ---- robust sessions (created with robust=...): RbcdSession's four calls, weights in pose-pose order ----
+    def update_weights(self, reset_to_initial=False):
+        c = np.zeros(3, np.int32)
+        check(capi.lib().dcora_ra_rbcd_update_weights(self.h, int(bool(reset_to_initial)),
+                                                      c.ctypes.data_as(C.c_void_p)))
+        return {"accepted": int(c[0]), "rejected": int(c[1]), "undecided": int(c[2])}
+
+    def set_weights(self, w):
+        w = np.ascontiguousarray(w, np.float64)
+        if w.shape != (self.m,):
+            raise ValueError("set_weights needs one weight per pose-pose measurement")
+        check(capi.lib().dcora_ra_rbcd_set_weights(self.h, w))
+
+    def get_weights(self):
+        w = np.zeros(max(self.m, 1))
+        check(capi.lib().dcora_ra_rbcd_get_weights(self.h, w))
+        return w[:self.m]
+
+    def robust_info(self):
+        mu, n = C.c_double(), C.c_int()
+        check(capi.lib().dcora_ra_rbcd_robust_info(self.h, C.byref(mu), C.byref(n)))
+        return {"mu": mu.value, "updates": n.value}
 
 
 def align_lifted_trajectory_to_frame(X, anchor, d, n, global_alignment=True, device=0):

@@ -247,6 +247,15 @@ SIGNATURES = {
     "dcora_ra_rbcd_agent_colours": (C.c_int, [_vp, _ip, _PI]),
     "dcora_ra_rbcd_run_coloured": (C.c_int, [_vp, C.c_int, C.c_double, _PI, _vp, _vp]),
     "dcora_ra_rbcd_last_result": (C.c_int, [_vp, C.POINTER(ROptResult)]),
+    "dcora_radataset_loop_closures": (C.c_int, [_vp, _ip]),
+    "dcora_radataset_set_pose_pose_weights": (C.c_int, [_vp, _dp]),
+    "dcora_ra_measurement_errors": (C.c_int, [_vp, C.c_int, _dp, _dp, C.c_int]),
+    "dcora_ra_rbcd_create_robust": (C.c_int, [_vp, C.POINTER(RbcdOptions), C.POINTER(RobustParams), _vp,
+                                              C.POINTER(_vp)]),
+    "dcora_ra_rbcd_update_weights": (C.c_int, [_vp, C.c_int, _vp]),
+    "dcora_ra_rbcd_set_weights": (C.c_int, [_vp, _dp]),
+    "dcora_ra_rbcd_get_weights": (C.c_int, [_vp, _dp]),
+    "dcora_ra_rbcd_robust_info": (C.c_int, [_vp, _PD, _PI]),
     "dcora_problem_time_qapply": (C.c_int, [_vp, C.c_int, _PD, _PD]),
     "dcora_problem_time_qapply_rotating": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int, _PD]),
     "dcora_problem_qapply_info": (C.c_int, [_vp, _dp]),

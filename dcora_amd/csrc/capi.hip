@@ -987,6 +987,21 @@ int dcora_radataset_agent_colours(dcora_radataset_t h, int *colours, int *ncolou
     return DCORA_OK;
   });
 }
+int dcora_radataset_loop_closures(dcora_radataset_t h, int *mask) {
+  return abi_call({h, mask}, [&] {
+    ra_loop_closures(h->ds, mask);
+    return DCORA_OK;
+  });
+}
+int dcora_radataset_set_pose_pose_weights(dcora_radataset_t h, const double *w) {
+  return abi_call({h, w}, [&]() -> int {
+    const size_t m = h->ds.pose_pose.size();
+    for (size_t e = 0; e < m; ++e)
+      if (!std::isfinite(w[e]) || w[e] < 0) return bad("pose-pose weights must be finite and >= 0");
+    for (size_t e = 0; e < m; ++e) h->ds.pose_pose[e].weight = w[e];
+    return DCORA_OK;
+  });
+}
 int dcora_graph_extract_agent_blocks(int k, const int *rp, const int *ci, const double *v, int k_a, const int *own,
                                      dcora_csr_t *Qaa, dcora_csr_t *C) {
   return abi_call({rp, ci, v, own, Qaa, C}, [&]() -> int {
@@ -1649,6 +1664,58 @@ int dcora_ra_rbcd_certify(dcora_ra_rbcd_t s, double eta, int *certified, double 
     return session_certify_out(s->s, eta, certified, theta, lambda_min, v, matvecs, info8);
   });
 }
+// Agent::initializeRobustOptimization (ref src/Agent.cpp:1332-1346) of every agent of a RangeAidedSLAMGraph at creation
+int dcora_ra_rbcd_create_robust(dcora_radataset_t ds, const dcora_rbcd_options *opt, const dcora_robust_params *robust,
+                                const int *fixed_weight, dcora_ra_rbcd_t *out) {
+  return abi_call({ds, opt, robust, out}, [&]() -> int {
+    if (opt->world_size != 1) {
+      set_last_error("ra_rbcd robust: dcora_ra_rbcd_create_robust makes single-process sessions (world_size 1); "
+                     "re-weighting a range-aided problem across ranks is not supported");
+      return DCORA_ERR_UNSUPPORTED;
+    }
+    return create(out, [&](dcora_ra_rbcd_s &h) { return h.s.init_robust(ds->ds, *opt, *robust, fixed_weight); });
+  });
+}
+namespace {
+// the refusals of the robust entries, as robust_session states them for pose-graph sessions
+int ra_robust_session(dcora_ra_rbcd_t s) {
+  if (s->s.robust) return DCORA_OK;
+  if (s->s.opt.world_size != 1) {
+    set_last_error("ra_rbcd robust: only single-process sessions (world_size 1) update weights");
+    return DCORA_ERR_UNSUPPORTED;
+  }
+  return bad("ra_rbcd robust: the session was not created by dcora_ra_rbcd_create_robust");
+}
+}  // namespace
+// Agent::updateMeasurementWeights (ref src/Agent.cpp:1397-1441) of every agent
+int dcora_ra_rbcd_update_weights(dcora_ra_rbcd_t s, int reset_to_initial, int counts[3]) {
+  return abi_call({s}, [&] {
+    const int rc = ra_robust_session(s);
+    return rc ? rc : s->s.update_weights(reset_to_initial != 0, counts);
+  });
+}
+// Agent::setMeasurementWeight (ref src/Agent.cpp:1443-1454) of every pose-pose measurement
+int dcora_ra_rbcd_set_weights(dcora_ra_rbcd_t s, const double *w) {
+  return abi_call({s, w}, [&] {
+    const int rc = ra_robust_session(s);
+    return rc ? rc : s->s.set_weights(w);
+  });
+}
+int dcora_ra_rbcd_get_weights(dcora_ra_rbcd_t s, double *w) {
+  return abi_call({s, w}, [&] {
+    const int rc = ra_robust_session(s);
+    return rc ? rc : s->s.get_weights(w);
+  });
+}
+int dcora_ra_rbcd_robust_info(dcora_ra_rbcd_t s, double *mu, int *updates) {
+  return abi_call({s}, [&] {
+    const int rc = ra_robust_session(s);
+    if (rc) return rc;
+    if (mu) *mu = s->s.robust->cost.mu();
+    if (updates) *updates = s->s.robust->updates;
+    return (int)DCORA_OK;
+  });
+}
 
 // ---- robust estimation ---------------------------------------------------------------------------------------
 void dcora_robust_params_default(dcora_robust_params *p) {
@@ -1790,6 +1857,12 @@ int dcora_measurement_errors(dcora_dataset_t ds, int r, const double *X, double 
   return abi_call({ds, X, out}, [&] {
     if (r < ds->ds.d || r > 16) return bad("measurement_errors: need d <= r <= 16");
     return measurement_errors(ds->ds, r, X, out, device);
+  });
+}
+int dcora_ra_measurement_errors(dcora_radataset_t ds, int r, const double *X, double *out, int device) {
+  return abi_call({ds, X, out}, [&] {
+    if (r < ds->ds.d || r > 16) return bad("measurement_errors: need d <= r <= 16");
+    return ra_measurement_errors(ds->ds, r, X, out, device);
   });
 }
 int dcora_solve_pgo(dcora_dataset_t ds, const dcora_ropt_params *params, const double *T0, double *Tout,

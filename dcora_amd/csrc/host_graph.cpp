@@ -459,6 +459,7 @@ HostCsr build_Q_ra(const HostRADataset &ds) {
     put_sym(ci, cj, -tau);
   };
   for (const PoseMeas &e : ds.pose_pose) {
+    if (e.weight == 0.0) continue;  // no entries: the pattern of Q is that of the measurements with a weight
     const int i = e.p1, j = e.p2;
     const double kap = e.weight * e.kappa, tau = e.weight * e.tau;
     for (int a = 0; a < d; ++a)
@@ -522,6 +523,18 @@ void ra_agent_columns(const HostRADataset &ds, int robot, int dims3[3], std::vec
         for (int c = 0; c < d; ++c) own.push_back(d * i + c);
         own.push_back(d * n + l + i);
       }
+  }
+}
+
+void ra_loop_closures(const HostRADataset &ds, int *mask) {
+  std::vector<int> local((size_t)ds.n, 0);  // a pose's number among its robot's poses
+  std::map<int, int> count;
+  for (int i = 0; i < ds.n; ++i) local[(size_t)i] = count[ds.pose_robot[(size_t)i]]++;
+  for (size_t e = 0; e < ds.pose_pose.size(); ++e) {
+    const PoseMeas &q = ds.pose_pose[e];
+    const bool odometry = ds.pose_robot[(size_t)q.p1] == ds.pose_robot[(size_t)q.p2] &&
+                          local[(size_t)q.p2] == local[(size_t)q.p1] + 1;
+    mask[e] = odometry ? 0 : 1;
   }
 }
 

@@ -65,6 +65,10 @@ struct HostRADataset {
 // Columns (global RA ordering) owned by `robot`, listed in that agent's own RA ordering
 // [rotations of its poses | its unit spheres | translations of its poses | its landmarks]; dims3 = {n_a, l_a, b_a}
 void ra_agent_columns(const HostRADataset &ds, int robot, int dims3[3], std::vector<int> &own);
+// One flag per pose-pose measurement: 1 for a loop closure, 0 for odometry -- both poses of one robot and consecutive in
+// that robot's own numbering (what Agent::updateMeasurementWeights re-weights on a RangeAidedSLAMGraph, ref
+// src/Agent.cpp:1397-1441; the RA counterpart of driver.loop_closure_mask)
+void ra_loop_closures(const HostRADataset &ds, int *mask);
 // The agent's share of a global quadratic form: Qaa = Q[own, own] in the agent's ordering and the coupling
 // C = Q[own, everything else] with GLOBAL column indices, so that the agent's linear term is G_a = X_global C^T
 // (the same restriction the reference assembles edge by edge, ref src/Graph.cpp:824-1772)

@@ -7,6 +7,17 @@
 // source robot of their range); an agent's columns are scattered over the global RA ordering, so each agent keeps its
 // X / V / Y / XPrev in its own RA ordering [rotations | unit spheres | translations | landmarks] and the global
 // iterate is a mirror that the coupling products (G_a = X_global C_a^T) and the central evaluation read.
+//
+// Robust sessions (dcora_ra_rbcd_create_robust; single-process only) run the agents' GNC loop in place, as the reference's
+// Agent does on a RangeAidedSLAMGraph just as on a pose graph: Agent::initializeRobustOptimization at creation,
+// Agent::updateMeasurementWeights / setMeasurementWeight afterwards (ref src/Agent.cpp:1332-1346, 1397-1441, 1443-1454),
+// over the graph's pose-pose loop closures only (computeMeasurementResidual, :1349-1395, refuses every other measurement
+// type; range and pose-landmark weights never change).  A weight change rebuilds the VALUES of every agent's Q_aa, of
+// its coupling block and of the central Q on the patterns recorded at creation, through the path creation takes.  What
+// depends on the patterns stays as created: neighbours, public columns and colours (a weight of 0 on the only
+// measurement joining two agents would take them apart in a fresh session; the live session keeps its creation adjacency,
+// as the reference keeps a weight-0 measurement in its graph), the one-launch tCG eligibility, the hub rows of the
+// Q-apply and the sparse / dense choice of the preconditioner.
 #pragma once
 #include <memory>
 #include <string>
@@ -14,6 +25,8 @@
 
 #include "device_problem.h"
 #include "host_graph.h"
+#include "host_robust.h"
+#include "robust.h"
 #include "session_core.h"
 
 namespace dcora {
@@ -27,6 +40,22 @@ struct RaAgentDev : AgentCore {
   double reg = 0;
 };
 
+// Robust state of a session created by dcora_ra_rbcd_create_robust (RobustSession of rbcd.h, in pose-pose order)
+struct RaRobustSession {
+  explicit RaRobustSession(const dcora_robust_params &p) : cost(p), params(p) {}
+  RobustCost cost;
+  dcora_robust_params params;
+  int updates = 0;
+  HostRADataset ds;             // the dataset with the current pose-pose weights
+  std::vector<char> update;     // loop closures whose weight is not fixed: what updateMeasurementWeights rewrites
+  std::vector<char> meas_zero;  // weight 0 at creation: the patterns do not hold these measurements
+  RobustEdges edges;            // device copy of the pose-pose measurements and of their weights
+  DevBuf<double> X_initial;     // the last set_X, r x k global (robustOptNumResets: setXToInitialGuess)
+  std::vector<HostCsr> Qpat, Cpat;  // creation patterns (rp, ci) of every agent's Q_aa and coupling block
+  HostCsr central_pat;
+  HostCsr live_pat;  // the central Q's entries as the current weights give them (no explicit zeros): what certify reads
+};
+
 class RaRbcdSession : public SessionCore {
  public:
   int d = 0, n = 0, l = 0, b = 0, k = 0;
@@ -37,6 +66,13 @@ class RaRbcdSession : public SessionCore {
   RaRbcdSession() : SessionCore("ra_rbcd") {}
   ~RaRbcdSession();
   int init(const HostRADataset &ds, const dcora_rbcd_options &o);
+  // robust sessions: weight 1 on every loop closure that is not fixed (fixed: m_pp flags or null), then init
+  std::unique_ptr<RaRobustSession> robust;
+  int init_robust(const HostRADataset &ds, const dcora_rbcd_options &o, const dcora_robust_params &p, const int *fixed);
+  // updateMeasurementWeights on the current iterate; counts (may be null): accepted, rejected, undecided closures
+  int update_weights(bool reset_to_initial, int counts[3]);
+  int set_weights(const double *w);  // all m_pp weights; refused (session untouched) when one is negative or not finite
+  int get_weights(double *w) const;
   int set_X(const double *Xh) override;  // r x k global; V = Y = XPrev = X for every agent
   int get_X(double *Xh);
   // one pass of the driver's loop body with agent index `selected` (position in the sorted robot list)
@@ -51,10 +87,16 @@ class RaRbcdSession : public SessionCore {
   AgentCore &agent_core(int a) override { return agents[(size_t)a]; }
   long num_cols() const override { return k; }
   DeviceProblem *central_problem() override { return central.get(); }
+  const HostCsr *central_pattern() const override { return robust ? &robust->central_pat : nullptr; }
+  const HostCsr *central_live_pattern() const override { return robust ? &robust->live_pat : nullptr; }
   int cert_block() const override { return 1; }
   int x_stage_hosted(double *host_area) override;
 
  private:
+  // the one path from a dataset's measurements to the session's matrices, at creation and on every re-weight
+  int assemble(const HostRADataset &ds, bool creation);
+  int adopt_weights(HostRADataset &ds, bool from_device, bool reset_to_initial);
+  int gather_agents();         // every hosted agent's X from the mirror, V = Y = XPrev = X (enqueued)
   int scatter(RaAgentDev &a);  // my X into the global mirror
   int solve(RaAgentDev &a, const double *start, double **result);
   // the tick: a set of one hosted agent has nothing to run beside and stays on the session's stream

@@ -75,15 +75,12 @@ int RaRbcdSession::init(const HostRADataset &ds, const dcora_rbcd_options &o) {
     const int rcs = acquire_stream(nullptr);
     if (rcs) return rcs;
   }
-  const HostCsr Q = build_Q_ra(ds);
   const size_t N = (size_t)r * k;
   DCORA_HIP(Xg.alloc(N));
   DCORA_HIP(hipMemset(Xg.p, 0, sizeof(double) * N));
   DCORA_HIP(evalbuf.alloc(R + 8));
   agents.resize(R);
   const int per = (R + o.world_size - 1) / o.world_size;  // consecutive agents share a rank
-  std::vector<int> owner_of((size_t)k, -1);               // global column -> agent
-  std::vector<std::set<int>> pub((size_t)R), nbr((size_t)R);
   int idx = 0;
   for (int robot : robots) {
     RaAgentDev &a = agents[idx];
@@ -91,42 +88,83 @@ int RaRbcdSession::init(const HostRADataset &ds, const dcora_rbcd_options &o) {
     a.hosted = (idx / per) == o.rank;
     int dims3[3];
     ra_agent_columns(ds, robot, dims3, a.own_host);
-    for (int c : a.own_host) owner_of[(size_t)c] = idx;
-    ++idx;
-  }
-  idx = 0;
-  for (int robot : robots) {
-    RaAgentDev &a = agents[idx];
-    const int me = idx++;
-    int dims3[3];
-    std::vector<int> own;
-    ra_agent_columns(ds, robot, dims3, own);
     a.n = dims3[0];
     a.l = dims3[1];
     a.b = dims3[2];
-    a.k = (int)own.size();
-    HostCsr Qaa, C;
-    extract_agent_blocks(Q, own, &Qaa, &C);
-    // the columns of OTHER agents my coupling block reaches are their public variables; their owners my neighbours
-    for (int c : C.ci) {
-      const int q = owner_of[(size_t)c];
-      if (q >= 0 && q != me) {
-        pub[(size_t)q].insert(c);
-        nbr[(size_t)me].insert(q);
-        nbr[(size_t)q].insert(me);
-      }
+    a.k = (int)a.own_host.size();
+    ++idx;
+  }
+  const int rc = assemble(ds, true);
+  if (rc) return rc;
+  iteration = 0;
+  gamma = alpha = 0;
+  setup_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return DCORA_OK;
+}
+
+// The one path from a dataset's measurements to the session's matrices, at creation and on every re-weight
+// (Graph::clearDataMatrices + constructDataMatrices, ref src/Agent.cpp:1416): build_Q_ra, every agent's Q_aa and coupling
+// block cut out of it, the agent's regularisation recomputed from its Q_aa (the reference recomputes it whenever the data
+// matrices are rebuilt, ref src/Graph.cpp:1906, 1921), the central Q.
+// Creation: the device problems, buffers and tick resources are made, who neighbours whom is read off the coupling
+// blocks, and a robust session records the patterns.
+// Re-weight (single-process robust sessions; the caller has synchronised every stream): the matrices as the builders give
+// them (no explicit zeros) go to build_preconditioner, so the cache sees the keys of a fresh session -- a new image is
+// attached, an image somebody else still holds is never written --, and their values scattered onto the creation
+// patterns (a weight of 0 leaves explicit zeros) are what is uploaded.  Nothing on the device is touched before every
+// matrix has been found to fit its pattern.
+int RaRbcdSession::assemble(const HostRADataset &ds, bool creation) {
+  const dcora_rbcd_options &o = opt;
+  const HostCsr Q = build_Q_ra(ds);
+  std::vector<HostCsr> Qaa((size_t)R), C((size_t)R);
+  for (int i = 0; i < R; ++i) extract_agent_blocks(Q, agents[(size_t)i].own_host, &Qaa[(size_t)i], &C[(size_t)i]);
+  // re-weight: host images of the uploads, alive until the stream has been synchronised
+  std::vector<HostCsr> Qs, Cs;
+  std::vector<std::vector<double>> stage;
+  HostCsr Qcs;
+  std::vector<double> cstage;
+  if (creation) {
+    if (robust) {
+      robust->Qpat.assign((size_t)R, HostCsr());
+      robust->Cpat.assign((size_t)R, HostCsr());
     }
+  } else {
+    Qs.resize((size_t)R);
+    Cs.resize((size_t)R);
+    stage.resize((size_t)R);
+    bool ok = scatter_on_pattern(Q, robust->central_pat, &Qcs);
+    for (int i = 0; i < R && ok; ++i)
+      ok = scatter_on_pattern(Qaa[(size_t)i], robust->Qpat[(size_t)i], &Qs[(size_t)i]) &&
+           scatter_on_pattern(C[(size_t)i], robust->Cpat[(size_t)i], &Cs[(size_t)i]);
+    if (!ok) {
+      set_last_error("ra_rbcd robust: the weights give a matrix entry outside the session's pattern");
+      return DCORA_ERR_BAD_ARG;
+    }
+  }
+  int rc = DCORA_OK;
+  for (int i = 0; i < R && !rc; ++i) {
+    RaAgentDev &a = agents[(size_t)i];
     if (!a.hosted) continue;  // agents of other ranks: their columns and public variables are all this rank keeps
-    int rc = device_precond_regularization(Qaa, o.device, &a.reg);  // ref src/Graph.cpp:1901-1960, per agent
-    if (rc) return rc;
+    rc = device_precond_regularization(Qaa[(size_t)i], o.device, &a.reg);  // ref src/Graph.cpp:1901-1960, per agent
+    if (rc) break;
+    if (!creation) {
+      rc = a.prob->set_values(Qs[(size_t)i], st, &stage[(size_t)i]);
+      if (!rc) rc = a.coupling.set_values(Cs[(size_t)i], st);
+      if (!rc) rc = a.prob->build_preconditioner(Qaa[(size_t)i], a.reg);
+      continue;
+    }
     a.prob.reset(new DeviceProblem);
     dcora_dims dims{r, d, a.n, a.l, a.b, DCORA_LAYOUT_RA};  // an agent without ranges / landmarks keeps the RA ordering
-    rc = a.prob->init(dims, Qaa, nullptr, a.reg, o.device, st);
-    if (rc) return rc;
-    rc = a.coupling.upload(C);
-    if (rc) return rc;
-    DCORA_HIP(a.own.alloc(own.size()));
-    DCORA_HIP(hipMemcpy(a.own.p, own.data(), sizeof(int) * own.size(), hipMemcpyHostToDevice));
+    rc = a.prob->init(dims, Qaa[(size_t)i], nullptr, a.reg, o.device, st);
+    if (rc) break;
+    rc = a.coupling.upload(C[(size_t)i]);
+    if (rc) break;
+    if (robust) {
+      robust->Qpat[(size_t)i] = pattern_of(Qaa[(size_t)i]);
+      robust->Cpat[(size_t)i] = pattern_of(C[(size_t)i]);
+    }
+    DCORA_HIP(a.own.alloc(a.own_host.size()));
+    DCORA_HIP(hipMemcpy(a.own.p, a.own_host.data(), sizeof(int) * a.own_host.size(), hipMemcpyHostToDevice));
     const size_t Na = (size_t)r * a.k;
     DCORA_HIP(a.X.alloc(Na));
     DCORA_HIP(a.V.alloc(Na));
@@ -134,12 +172,33 @@ int RaRbcdSession::init(const HostRADataset &ds, const dcora_rbcd_options &o) {
     DCORA_HIP(a.XPrev.alloc(Na));
     DCORA_HIP(a.tmp.alloc(Na));
     rc = acquire_tick_resources(a);
-    if (rc) return rc;
   }
-  {
-    const int rc = create_fork_event();
+  if (!creation) {
+    if (!rc) rc = central->set_values(Qcs, st, &cstage);
+    const hipError_t synced = hipStreamSynchronize(st);  // (also after a failure: copies may be in flight)
     if (rc) return rc;
+    DCORA_HIP(synced);
+    robust->live_pat = pattern_of(Q);  // the next certificate is a fresh session's: over the entries these weights give
+    cert_.reset();
+    return DCORA_OK;
   }
+  if (rc) return rc;
+  rc = create_fork_event();
+  if (rc) return rc;
+  // the columns of OTHER agents an agent's coupling block reaches are their public variables; their owners its neighbours
+  std::vector<int> owner_of((size_t)k, -1);  // global column -> agent
+  for (int i = 0; i < R; ++i)
+    for (int c : agents[(size_t)i].own_host) owner_of[(size_t)c] = i;
+  std::vector<std::set<int>> pub((size_t)R), nbr((size_t)R);
+  for (int me = 0; me < R; ++me)
+    for (int c : C[(size_t)me].ci) {
+      const int q = owner_of[(size_t)c];
+      if (q >= 0 && q != me) {
+        pub[(size_t)q].insert(c);
+        nbr[(size_t)me].insert(q);
+        nbr[(size_t)q].insert(me);
+      }
+    }
   for (int i = 0; i < R; ++i) {
     RaAgentDev &a = agents[(size_t)i];
     a.neighbors.assign(nbr[(size_t)i].begin(), nbr[(size_t)i].end());
@@ -151,19 +210,149 @@ int RaRbcdSession::init(const HostRADataset &ds, const dcora_rbcd_options &o) {
   if (o.world_size == 1) {  // the central evaluation of the one-process loop; ranks evaluate agent by agent
     central.reset(new DeviceProblem);
     dcora_dims dims{r, d, n, l, b, DCORA_LAYOUT_RA};
-    int rc = central->init(dims, Q, nullptr, -1.0, o.device, st);
+    rc = central->init(dims, Q, nullptr, -1.0, o.device, st);
     if (rc) return rc;
+    if (robust) robust->live_pat = robust->central_pat = pattern_of(Q);
   }
-  iteration = 0;
-  gamma = alpha = 0;
-  setup_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return DCORA_OK;
 }
 
-int RaRbcdSession::set_X(const double *Xh) {
+// ---- robust sessions -------------------------------------------------------------------------------------------------
+// Agent::initializeRobustOptimization for every agent (ref src/Agent.cpp:1332-1346): weight 1 on every loop closure whose
+// weight is not fixed (ra_loop_closures: every pose-pose measurement but odometry).  With weights 1 the patterns are the
+// largest any later weights can give: they are kept, and a weight change only rewrites values.
+int RaRbcdSession::init_robust(const HostRADataset &ds, const dcora_rbcd_options &o, const dcora_robust_params &p,
+                               const int *fixed) {
+  if (o.world_size != 1) {
+    set_last_error("ra_rbcd robust: only single-process sessions (world_size 1) update weights");
+    return DCORA_ERR_UNSUPPORTED;
+  }
+  if (p.cost_type < DCORA_ROBUST_L2 || p.cost_type > DCORA_ROBUST_GNC_TLS) {
+    set_last_error("ra_rbcd robust: unknown robust cost type");
+    return DCORA_ERR_BAD_ARG;
+  }
+  const size_t m = ds.pose_pose.size();
+  for (const PoseMeas &q : ds.pose_pose)
+    if (q.p1 < 0 || q.p1 >= ds.n || q.p2 < 0 || q.p2 >= ds.n) {
+      set_last_error("ra_rbcd robust: pose index out of range");
+      return DCORA_ERR_BAD_ARG;
+    }
+  if (ds.pose_robot.size() != (size_t)ds.n) {
+    set_last_error("ra_rbcd robust: the dataset has no pose owners");
+    return DCORA_ERR_BAD_ARG;
+  }
+  robust.reset(new RaRobustSession(p));
+  RaRobustSession &rs = *robust;
+  rs.ds = ds;
+  std::vector<int> lc(m);
+  ra_loop_closures(ds, lc.data());
+  rs.update.assign(m, 0);
+  rs.meas_zero.assign(m, 0);
+  for (size_t e = 0; e < m; ++e) {
+    PoseMeas &q = rs.ds.pose_pose[e];
+    if (lc[e] && !(fixed && fixed[e])) {
+      rs.update[e] = 1;
+      q.weight = 1.0;
+    }
+    rs.meas_zero[e] = q.weight == 0.0;
+  }
+  int rc = init(rs.ds, o);
+  if (rc) return rc;
+  rc = rs.edges.upload_ra(rs.ds, rs.update);
+  if (rc) return rc;
+  DCORA_HIP(rs.X_initial.alloc((size_t)r * k));
+  DCORA_HIP(hipMemsetAsync(rs.X_initial.p, 0, sizeof(double) * (size_t)r * k, st));
+  DCORA_HIP(hipStreamSynchronize(st));
+  return DCORA_OK;
+}
+
+// Agent::updateMeasurementWeights for every agent (ref src/Agent.cpp:1397-1441): the weights of the current iterate
+// (k_robust_weights reads the mirror Xg in the RA ordering), the data matrices rebuilt, RobustCost::update, optionally X
+// back to the last set_X (robustOptNumResets), acceleration re-initialised
+int RaRbcdSession::update_weights(bool reset_to_initial, int counts[3]) {
+  RaRobustSession &rs = *robust;
   DCORA_HIP(hipSetDevice(opt.device));
-  const size_t B = sizeof(double) * (size_t)r * k;
-  DCORA_HIP(hipMemcpyAsync(Xg.p, Xh, B, hipMemcpyHostToDevice, st));
+  for (const RaAgentDev &a : agents)
+    if (a.own_st) DCORA_HIP(hipStreamSynchronize(a.own_st));  // the mirror is complete
+  const size_t m = rs.ds.pose_pose.size();
+  std::vector<double> w(m, 0.0);
+  double cnt[3] = {0, 0, 0};
+  if (m) {
+    launch_robust_weights(st, rs.edges, r, Xg.p, rs.params, rs.cost.mu());
+    DCORA_HIP(hipGetLastError());
+    DCORA_HIP(hipMemcpyAsync(w.data(), rs.edges.w.p, sizeof(double) * m, hipMemcpyDeviceToHost, st));
+    DCORA_HIP(hipMemcpyAsync(cnt, rs.edges.counts.p, sizeof(double) * 3, hipMemcpyDeviceToHost, st));
+  }
+  DCORA_HIP(hipStreamSynchronize(st));
+  HostRADataset next = rs.ds;
+  for (size_t e = 0; e < m; ++e) next.pose_pose[e].weight = w[e];
+  const int rc = adopt_weights(next, true, reset_to_initial);
+  if (rc) return rc;
+  rs.cost.update();
+  rs.updates++;
+  inner_rounds = 0;  // mRobustOptInnerIter = 0 (ref src/Agent.cpp:1418-1424)
+  if (counts)
+    for (int c = 0; c < 3; ++c) counts[c] = (int)cnt[c];
+  return DCORA_OK;
+}
+
+// The shared tail of both ways to change weights: the matrices rebuilt for ds (rs.ds with the new weights), the device's
+// weights made the ones the matrices hold -- the old ones after a refusal, the new ones unless the device computed them
+// itself (from_device) --, optionally X back to the last set_X, acceleration re-initialised (Agent::
+// initializeAcceleration, ref src/Agent.cpp:1178-1187: XPrev = V = Y = X, gamma = alpha = 0; the round counter goes on)
+int RaRbcdSession::adopt_weights(HostRADataset &ds, bool from_device, bool reset_to_initial) {
+  RaRobustSession &rs = *robust;
+  const size_t m = ds.pose_pose.size();
+  int rc = DCORA_OK;
+  // a pattern holds every entry of its creation weights; only a weight that was 0 then can reach outside it
+  for (size_t e = 0; e < m && !rc; ++e)
+    if (rs.meas_zero[e] && ds.pose_pose[e].weight != 0.0) {
+      set_last_error("ra_rbcd robust: a weight that was 0 at creation cannot become nonzero (the session's patterns "
+                     "do not hold that measurement)");
+      rc = DCORA_ERR_BAD_ARG;
+    }
+  DCORA_HIP(hipSetDevice(opt.device));
+  // nothing of the session is in flight while its matrices and preconditioner images change
+  for (const RaAgentDev &a : agents)
+    if (a.own_st) DCORA_HIP(hipStreamSynchronize(a.own_st));
+  DCORA_HIP(hipStreamSynchronize(st));
+  if (!rc) rc = assemble(ds, false);
+  if (!rc) std::swap(rs.ds.pose_pose, ds.pose_pose);
+  if (m && (rc || !from_device)) {
+    std::vector<double> held(m);
+    for (size_t e = 0; e < m; ++e) held[e] = rs.ds.pose_pose[e].weight;
+    DCORA_HIP(hipMemcpy(rs.edges.w.p, held.data(), sizeof(double) * m, hipMemcpyHostToDevice));
+  }
+  if (rc) return rc;
+  if (reset_to_initial)
+    DCORA_HIP(hipMemcpyAsync(Xg.p, rs.X_initial.p, sizeof(double) * (size_t)r * k, hipMemcpyDeviceToDevice, st));
+  rc = gather_agents();  // (after a reset the agents' own X comes from the mirror; otherwise it is what they hold)
+  if (rc) return rc;
+  DCORA_HIP(hipStreamSynchronize(st));
+  gamma = alpha = 0;
+  return DCORA_OK;
+}
+
+int RaRbcdSession::set_weights(const double *w) {
+  RaRobustSession &rs = *robust;
+  const size_t m = rs.ds.pose_pose.size();
+  for (size_t e = 0; e < m; ++e)
+    if (!std::isfinite(w[e]) || w[e] < 0) {
+      set_last_error("ra_rbcd robust: weights must be finite and >= 0");
+      return DCORA_ERR_BAD_ARG;
+    }
+  HostRADataset next = rs.ds;
+  for (size_t e = 0; e < m; ++e) next.pose_pose[e].weight = w[e];
+  return adopt_weights(next, false, false);
+}
+
+int RaRbcdSession::get_weights(double *w) const {
+  const RaRobustSession &rs = *robust;
+  for (size_t e = 0; e < rs.ds.pose_pose.size(); ++e) w[e] = rs.ds.pose_pose[e].weight;
+  return DCORA_OK;
+}
+
+int RaRbcdSession::gather_agents() {
   for (RaAgentDev &a : agents) {
     if (!a.hosted) continue;
     const size_t Ba = sizeof(double) * (size_t)r * a.k;
@@ -172,6 +361,16 @@ int RaRbcdSession::set_X(const double *Xh) {
     DCORA_HIP(hipMemcpyAsync(a.Y.p, a.X.p, Ba, hipMemcpyDeviceToDevice, st));
     DCORA_HIP(hipMemcpyAsync(a.XPrev.p, a.X.p, Ba, hipMemcpyDeviceToDevice, st));
   }
+  return DCORA_OK;
+}
+
+int RaRbcdSession::set_X(const double *Xh) {
+  DCORA_HIP(hipSetDevice(opt.device));
+  const size_t B = sizeof(double) * (size_t)r * k;
+  DCORA_HIP(hipMemcpyAsync(Xg.p, Xh, B, hipMemcpyHostToDevice, st));
+  if (robust) DCORA_HIP(hipMemcpyAsync(robust->X_initial.p, Xg.p, B, hipMemcpyDeviceToDevice, st));
+  const int rc = gather_agents();
+  if (rc) return rc;
   DCORA_HIP(hipStreamSynchronize(st));
   gamma = alpha = 0;
   iteration = 0;

@@ -1,6 +1,7 @@
 // Robust pose-graph optimisation around the local solver:
 //   measurement_errors : computeMeasurementError of every edge at once (ref src/DCORA_utils.cpp:2095-2101;
-//                        Agent::computeMeasurementResidual, ref src/Agent.cpp:1342-1389, with lifted poses)
+//                        Agent::computeMeasurementResidual, ref src/Agent.cpp:1342-1389, with lifted poses), in the SE
+//                        ordering of a pose graph or the RA ordering of a range-aided graph's pose-pose measurements
 //   solve_pgo          : solvePGO (ref src/DCORA_solver.cpp:304-328) -- chordal start, one optimize() at rank d
 //   solve_robust_pgo   : solveRobustPGO (ref :330-409) -- GNC-TLS outer loop around solve_pgo
 #include <algorithm>
@@ -19,32 +20,58 @@ namespace {
 struct EdgeDev {
   const int *p1, *p2;
   const double *R, *t, *kappa, *tau;  // R: d*d per edge (column-major), t: d per edge
+  int n, l;                           // poses and unit spheres of the problem: read by the RA ordering only
 };
 struct RankedEdges {
   const int *own, *gidx;  // the rank owns the edge (hosts the agent of p1); its index in the dataset
   double *shared_w;       // device view of the exchange's weights area (m doubles, dataset order)
 };
-// kappa |Y1 R - Y2|^2 + tau |p2 - p1 - Y1 t|^2 of edge e with Y r x d, p r-vectors (SE ordering): one expression for
-// both kernels below, so the session's weight update sees the residuals dcora_measurement_errors reports, bit for bit
-template <int D>
+// Where pose p lives in X (r rows, column-major): its rotation's D columns and its translation column.
+// SE ordering [Y1 p1 ... Yn pn]: columns (D+1) p .. (D+1) p + D.  RA ordering [Y1..Yn | s1..sl | p1..pn | L1..Lb]:
+// rotation at D p, translation at D n + l + p.
+struct SeCols {
+  template <int D>
+  static __device__ __forceinline__ const double *rot(const EdgeDev &, const double *X, int p, int r) {
+    return X + (size_t)p * (D + 1) * r;
+  }
+  template <int D>
+  static __device__ __forceinline__ const double *trans(const EdgeDev &, const double *X, int p, int r) {
+    return X + (size_t)p * (D + 1) * r + (size_t)D * r;
+  }
+};
+struct RaCols {
+  template <int D>
+  static __device__ __forceinline__ const double *rot(const EdgeDev &E, const double *X, int p, int r) {
+    return X + (size_t)p * D * r;
+  }
+  template <int D>
+  static __device__ __forceinline__ const double *trans(const EdgeDev &E, const double *X, int p, int r) {
+    return X + ((size_t)D * E.n + E.l + p) * r;
+  }
+};
+// kappa |Y1 R - Y2|^2 + tau |p2 - p1 - Y1 t|^2 of edge e with Y r x d, p r-vectors, addressed through Cols: one
+// expression for every kernel below and both orderings, so the sessions' weight updates see the residuals
+// dcora_measurement_errors / dcora_ra_measurement_errors report, bit for bit (Agent::computeMeasurementResidual, ref
+// src/Agent.cpp:1349-1395: pose-pose measurements only, on either graph type)
+template <int D, class Cols>
 __device__ __forceinline__ double edge_error(int r, int e, const EdgeDev &E, const double *__restrict__ X) {
-  constexpr int DH = D + 1;
-  const double *X1 = X + (size_t)E.p1[e] * DH * r, *X2 = X + (size_t)E.p2[e] * DH * r;
+  const double *Y1 = Cols::template rot<D>(E, X, E.p1[e], r), *Y2 = Cols::template rot<D>(E, X, E.p2[e], r);
+  const double *T1 = Cols::template trans<D>(E, X, E.p1[e], r), *T2 = Cols::template trans<D>(E, X, E.p2[e], r);
   const double *Re = E.R + (size_t)e * D * D, *te = E.t + (size_t)e * D;
   double rot = 0, tr = 0;
   for (int q = 0; q < r; ++q) {
     double y1[D];
 #pragma unroll
-    for (int a = 0; a < D; ++a) y1[a] = X1[(size_t)a * r + q];
+    for (int a = 0; a < D; ++a) y1[a] = Y1[(size_t)a * r + q];
 #pragma unroll
     for (int c = 0; c < D; ++c) {
       double s = 0;
 #pragma unroll
       for (int a = 0; a < D; ++a) s += y1[a] * Re[c * D + a];
-      const double dlt = s - X2[(size_t)c * r + q];
+      const double dlt = s - Y2[(size_t)c * r + q];
       rot += dlt * dlt;
     }
-    double s = X2[(size_t)D * r + q] - X1[(size_t)D * r + q];
+    double s = T2[q] - T1[q];
 #pragma unroll
     for (int a = 0; a < D; ++a) s -= y1[a] * te[a];
     tr += s * s;
@@ -53,12 +80,12 @@ __device__ __forceinline__ double edge_error(int r, int e, const EdgeDev &E, con
 }
 
 // one thread per edge
-template <int D>
+template <int D, class Cols>
 __global__ __launch_bounds__(kBlock) void k_measurement_errors(int r, int m, EdgeDev E, const double *__restrict__ X,
                                                                double *__restrict__ out) {
   const int e = blockIdx.x * kBlock + threadIdx.x;
   if (e >= m) return;
-  out[e] = edge_error<D>(r, e, E, X);
+  out[e] = edge_error<D, Cols>(r, e, E, X);
 }
 
 // RobustCost::weight (host_robust.cpp, ref src/DCORA_robust.cpp:56-100) with the same operations in the same order
@@ -89,7 +116,7 @@ __device__ double robust_weight(const dcora_robust_params &p, double mu, double 
 // Ranked (a session of one rank, RobustEdges::upload_ranked): the edges are those touching a hosted agent, X is the
 // rank's mirror; the edges the rank owns also store their weight into the shared segment at their dataset index
 // (plain stores, then a system-scope fence), and only they are counted, so that the job counts every edge once.
-template <int D, bool Ranked>
+template <int D, bool Ranked, class Cols>
 __global__ __launch_bounds__(kBlock) void k_robust_weights(int r, int m, EdgeDev E, const int *__restrict__ upd,
                                                            const double *__restrict__ X, dcora_robust_params p,
                                                            double mu, double *__restrict__ w,
@@ -98,7 +125,7 @@ __global__ __launch_bounds__(kBlock) void k_robust_weights(int r, int m, EdgeDev
   const int e = blockIdx.x * kBlock + threadIdx.x;
   double acc = 0, rej = 0, und = 0;
   if (e < m && upd[e]) {
-    const double we = robust_weight(p, mu, sqrt(edge_error<D>(r, e, E, X)));
+    const double we = robust_weight(p, mu, sqrt(edge_error<D, Cols>(r, e, E, X)));
     w[e] = we;
     const double w_tol = 1e-8;
     if (!Ranked || rk.own[e]) {
@@ -130,7 +157,9 @@ int no_device() {
   return DCORA_OK;
 }
 
-EdgeDev edge_view(const EdgeTable &T) { return EdgeDev{T.dp1.p, T.dp2.p, T.dR.p, T.dt.p, T.dk.p, T.dta.p}; }
+EdgeDev edge_view(const EdgeTable &T, int n = 0, int l = 0) {
+  return EdgeDev{T.dp1.p, T.dp2.p, T.dR.p, T.dt.p, T.dk.p, T.dta.p, n, l};
+}
 
 template <class T>
 int to_device(const std::vector<T> &h, DevBuf<T> *dev) {
@@ -182,6 +211,18 @@ int RobustEdges::upload(const HostDataset &ds, const std::vector<char> &update) 
   return DCORA_OK;
 }
 
+// the pose-pose measurements of a range-aided dataset, read from X in the RA ordering
+int RobustEdges::upload_ra(const HostRADataset &ds, const std::vector<char> &update) {
+  HostDataset pp;
+  pp.d = ds.d;
+  pp.n = ds.n;
+  pp.meas = ds.pose_pose;
+  ra = true;
+  n = ds.n;
+  l = ds.l;
+  return upload(pp, update);
+}
+
 // the edges of one rank: ids (dataset order) are those touching a hosted agent, own[i] flags the ones it owns
 int RobustEdges::upload_ranked(const HostDataset &ds, const std::vector<char> &update, const std::vector<int> &ids,
                                const std::vector<char> &own) {
@@ -204,28 +245,35 @@ int RobustEdges::upload_ranked(const HostDataset &ds, const std::vector<char> &u
 void launch_robust_weights(hipStream_t st, const RobustEdges &T, int r, const double *X, const dcora_robust_params &p,
                            double mu, double *shared_w) {
   if (T.m == 0) return;
-  const EdgeDev E = edge_view(T);
+  const EdgeDev E = edge_view(T, T.n, T.l);
   const int grid = (T.m + kBlock - 1) / kBlock;
   const RankedEdges rk{T.down.p, T.dgidx.p, shared_w};
   auto go = [&](auto kernel) {
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, st, r, T.m, E, T.dupd.p, X, p, mu, T.w.p, T.partials.p, rk);
   };
-  if (T.ranked) {
+  if (T.ra) {  // (single-process sessions only: never ranked)
     if (T.d == 3)
-      go(k_robust_weights<3, true>);
+      go(k_robust_weights<3, false, RaCols>);
     else
-      go(k_robust_weights<2, true>);
+      go(k_robust_weights<2, false, RaCols>);
+  } else if (T.ranked) {
+    if (T.d == 3)
+      go(k_robust_weights<3, true, SeCols>);
+    else
+      go(k_robust_weights<2, true, SeCols>);
   } else {
     if (T.d == 3)
-      go(k_robust_weights<3, false>);
+      go(k_robust_weights<3, false, SeCols>);
     else
-      go(k_robust_weights<2, false>);
+      go(k_robust_weights<2, false, SeCols>);
   }
   launch_sum_partials(st, T.partials.p, grid, 3, 3, T.counts.p);
 }
 
-// X: r x (d+1) n host (SE ordering, r >= d); out: one squared error per measurement (weights not applied)
-int measurement_errors(const HostDataset &ds, int r, const double *X, double *out, int device) {
+namespace {
+// the errors of ds.meas at X (r x cols host, poses addressed through Cols; n, l: what RaCols reads)
+template <class Cols>
+int errors_on_device(const HostDataset &ds, int n, int l, size_t cols, int r, const double *X, double *out, int device) {
   int rc = no_device();
   if (rc) return rc;
   DCORA_HIP(hipSetDevice(device));
@@ -240,19 +288,34 @@ int measurement_errors(const HostDataset &ds, int r, const double *X, double *ou
   rc = T.upload(ds);
   if (rc) return rc;
   DevBuf<double> dX, dout;
-  const size_t N = (size_t)r * (d + 1) * ds.n;
+  const size_t N = (size_t)r * cols;
   DCORA_HIP(dX.alloc(N));
   DCORA_HIP(dout.alloc(m));
   DCORA_HIP(hipMemcpy(dX.p, X, sizeof(double) * N, hipMemcpyHostToDevice));
-  const EdgeDev E = edge_view(T);
+  const EdgeDev E = edge_view(T, n, l);
   const int grid = (m + kBlock - 1) / kBlock;
   if (d == 3)
-    hipLaunchKernelGGL(k_measurement_errors<3>, dim3(grid), dim3(kBlock), 0, nullptr, r, m, E, dX.p, dout.p);
+    hipLaunchKernelGGL((k_measurement_errors<3, Cols>), dim3(grid), dim3(kBlock), 0, nullptr, r, m, E, dX.p, dout.p);
   else
-    hipLaunchKernelGGL(k_measurement_errors<2>, dim3(grid), dim3(kBlock), 0, nullptr, r, m, E, dX.p, dout.p);
+    hipLaunchKernelGGL((k_measurement_errors<2, Cols>), dim3(grid), dim3(kBlock), 0, nullptr, r, m, E, dX.p, dout.p);
   DCORA_HIP(hipDeviceSynchronize());
   DCORA_HIP(hipMemcpy(out, dout.p, sizeof(double) * m, hipMemcpyDeviceToHost));
   return DCORA_OK;
+}
+}  // namespace
+
+// X: r x (d+1) n host (SE ordering, r >= d); out: one squared error per measurement (weights not applied)
+int measurement_errors(const HostDataset &ds, int r, const double *X, double *out, int device) {
+  return errors_on_device<SeCols>(ds, 0, 0, (size_t)(ds.d + 1) * ds.n, r, X, out, device);
+}
+
+// the same of a range-aided dataset's pose-pose measurements; X: r x k host in the global RA ordering
+int ra_measurement_errors(const HostRADataset &ds, int r, const double *X, double *out, int device) {
+  HostDataset pp;
+  pp.d = ds.d;
+  pp.n = ds.n;
+  pp.meas = ds.pose_pose;
+  return errors_on_device<RaCols>(pp, ds.n, ds.l, (size_t)ds.k(), r, X, out, device);
 }
 
 // T0 (d x (d+1) n) may be null => chordal initialisation; Tout d x (d+1) n

@@ -17,7 +17,8 @@
 namespace dcora {
 
 // what a session keeps between certificates; all of it depends on the central pattern alone, so a re-weight (new
-// values on the creation pattern) leaves it valid
+// values on the creation pattern) leaves it valid -- unless the session certifies over the live entries only
+// (session_certify's `live`), whose owner calls reset() when they change
 struct SessionCertState {
   bool built = false;
   // the pattern of S + eta I: Q's entries, the entries of Lambda, every diagonal (Q's own pattern where Q stores all of
@@ -35,6 +36,18 @@ struct SessionCertState {
   ~SessionCertState() {
     if (ready) (void)hipEventDestroy(ready);
   }
+  void reset() {  // as never built (no certificate in flight)
+    if (ready) (void)hipEventDestroy(ready);
+    ready = nullptr;
+    built = false;
+    pat = HostCsr();
+    qidx.release();
+    slot.release();
+    diag.release();
+    XQ.release();
+    L.release();
+    vals.release();
+  }
 };
 
 struct CertifyResult {
@@ -47,8 +60,11 @@ struct CertifyResult {
 // central: the session's central problem (its stream: the session's; nothing else of the session in flight on another
 // stream); pattern: the host copy of its CSR pattern where the session keeps one (else taken back from the device once);
 // X: the mirror, r x k in the central problem's ordering (device); block: unknowns ordered together by the factorisation.
+// live (may be null: all of them): the stored entries the session's current weights give, a sub-pattern of `pattern` --
+// a re-weighted session whose creation pattern keeps explicit zeros certifies over these alone, i.e. over the matrix a
+// fresh session with its weights would hold, to the same bits (the factorisation and the Lanczos runs see that pattern).
 // Writes nothing the session reads.  info8 (may be null): as device_chol_is_pd fills it.
-int session_certify(SessionCertState &cs, DeviceProblem &central, const HostCsr *pattern, const double *X, int block,
-                    double eta, CertifyResult *out, double *info8);
+int session_certify(SessionCertState &cs, DeviceProblem &central, const HostCsr *pattern, const HostCsr *live,
+                    const double *X, int block, double eta, CertifyResult *out, double *info8);
 
 }  // namespace dcora

@@ -34,7 +34,7 @@ __global__ __launch_bounds__(kBlock) void k_cert_values(int nnz, const double *_
 }
 
 // the pattern of S + eta I and its three tables (host), the buffers of the device path
-int build_state(SessionCertState &cs, DeviceProblem &central, const HostCsr *pattern) {
+int build_state(SessionCertState &cs, DeviceProblem &central, const HostCsr *pattern, const HostCsr *live) {
   const ManiDesc &m = central.m;
   const DevCsr &Q = central.Q;
   const int k = Q.nrows, nnzq = Q.nnz;
@@ -47,7 +47,10 @@ int build_state(SessionCertState &cs, DeviceProblem &central, const HostCsr *pat
     DCORA_HIP(hipMemcpy(own.rp.data(), Q.rp.p, sizeof(int) * ((size_t)k + 1), hipMemcpyDeviceToHost));
     if (nnzq) DCORA_HIP(hipMemcpy(own.ci.data(), Q.ci.p, sizeof(int) * (size_t)nnzq, hipMemcpyDeviceToHost));
     pattern = &own;
+    live = nullptr;
   }
+  // the entries of Q that S is built over: all the stored ones, or the live ones among them (a sub-pattern)
+  const HostCsr *used = (live && live->n == k) ? live : pattern;
   // what the host assembly hands to the PSD test and dcora_cert_prepare analyses: Q's entries, the entries of Lambda,
   // every diagonal -- Q's own pattern unless Q lacks one of them (a rotation block with a structural zero, an isolated
   // pose, a unit sphere without a range)
@@ -56,9 +59,9 @@ int build_state(SessionCertState &cs, DeviceProblem &central, const HostCsr *pat
   I.reserve((size_t)nnzq + LI.size());
   J.reserve((size_t)nnzq + LI.size());
   for (int i = 0; i < k; ++i)
-    for (int p = pattern->rp[i]; p < pattern->rp[i + 1]; ++p) {
+    for (int p = used->rp[i]; p < used->rp[i + 1]; ++p) {
       I.push_back(i);
-      J.push_back(pattern->ci[p]);
+      J.push_back(used->ci[p]);
     }
   I.insert(I.end(), LI.begin(), LI.end());
   J.insert(J.end(), LJ.begin(), LJ.end());
@@ -71,8 +74,17 @@ int build_state(SessionCertState &cs, DeviceProblem &central, const HostCsr *pat
   };
   std::vector<int> qidx((size_t)nnz, -1), slot((size_t)nnz, -1);
   std::vector<unsigned char> diag((size_t)nnz, 0);
-  for (int i = 0; i < k; ++i)
-    for (int p = pattern->rp[i]; p < pattern->rp[i + 1]; ++p) qidx[(size_t)find(i, pattern->ci[p])] = p;
+  for (int i = 0; i < k; ++i) {
+    int p = pattern->rp[i];  // (both rows are sorted: one walk finds every used entry among the stored ones)
+    for (int u = used->rp[i]; u < used->rp[i + 1]; ++u) {
+      while (p < pattern->rp[i + 1] && pattern->ci[p] < used->ci[u]) ++p;
+      if (p == pattern->rp[i + 1] || pattern->ci[p] != used->ci[u]) {
+        set_last_error("session certify: the live pattern is not part of the stored one");
+        return DCORA_ERR_BAD_ARG;
+      }
+      qidx[(size_t)find(i, used->ci[u])] = p;
+    }
+  }
   for (size_t q = 0; q < LI.size(); ++q) slot[(size_t)find(LI[q], LJ[q])] = (int)q;
   for (int i = 0; i < k; ++i) diag[(size_t)find(i, i)] = 1;
   DCORA_HIP(cs.qidx.alloc((size_t)nnz));
@@ -104,15 +116,15 @@ int fetch(hipStream_t st, const double *dev, size_t count, double *host) {
 
 }  // namespace
 
-int session_certify(SessionCertState &cs, DeviceProblem &central, const HostCsr *pattern, const double *X, int block,
-                    double eta, CertifyResult *out, double *info8) {
+int session_certify(SessionCertState &cs, DeviceProblem &central, const HostCsr *pattern, const HostCsr *live,
+                    const double *X, int block, double eta, CertifyResult *out, double *info8) {
   const ManiDesc &m = central.m;
   const int device = central.device;
   hipStream_t st = central.st;
   DCORA_HIP(hipSetDevice(device));
   *out = CertifyResult();
   if (!cs.built) {
-    const int rc = build_state(cs, central, pattern);
+    const int rc = build_state(cs, central, pattern, live);
     if (rc) return rc;
   }
   const int nnz = cs.pat.nnz();  // k at least: every diagonal is stored

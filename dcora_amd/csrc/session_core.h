@@ -67,6 +67,8 @@ class SessionCore {
   int certify(double eta, CertifyResult *out, double *info8);
   virtual DeviceProblem *central_problem() = 0;                        // null on a rank of a multi-rank job
   virtual const HostCsr *central_pattern() const { return nullptr; }  // host copy of its pattern, where one is kept
+  // the stored entries the current weights give, where the session certifies over those alone (session_cert.h)
+  virtual const HostCsr *central_live_pattern() const { return nullptr; }
   virtual int cert_block() const = 0;  // unknowns the factorisation orders together (d + 1 for poses)
 
  protected:

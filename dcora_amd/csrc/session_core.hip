@@ -41,7 +41,8 @@ int SessionCore::certify(double eta, CertifyResult *out, double *info8) {
   // the mirror is complete: nothing of the session is in flight on an agent's own stream
   for (int a = 0; a < R; ++a)
     if (agent_core(a).own_st) DCORA_HIP(hipStreamSynchronize(agent_core(a).own_st));
-  return session_certify(cert_, *central, central_pattern(), Xg.p, cert_block(), eta, out, info8);
+  return session_certify(cert_, *central, central_pattern(), central_live_pattern(), Xg.p, cert_block(), eta, out,
+                         info8);
 }
 
 int SessionCore::acquire_stream(void *borrowed) {

@@ -169,10 +169,11 @@ def _counts(c):
     return c["accepted"], c["rejected"]
 
 
-def _gnc_loop(ds, lc, X0, num_weight_updates, inner_iters, max_final_iters, set_X, run, reweight, read, close):
-    """The one flow of the three GNC drivers: set_X(X0); num_weight_updates rounds of run(inner_iters) -- the record
+def _gnc_loop(ds, lc, X0, num_weight_updates, inner_iters, max_final_iters, set_X, run, reweight, read, close,
+              store=None):
+    """The one flow of the GNC drivers: set_X(X0); num_weight_updates rounds of run(inner_iters) -- the record
     of RbcdSession.run -- then reweight(round) -> (accepted, rejected); run(max_final_iters) with the final weights;
-    read() -> X, weights; close(), whatever happened.  ds.vals[:, -1] receives the weights."""
+    read() -> X, weights; close(), whatever happened.  ds.vals[:, -1] receives the weights (or store(weights))."""
     rounds = []
     try:
         set_X(np.asarray(X0, dtype=np.float64))
@@ -185,7 +186,10 @@ def _gnc_loop(ds, lc, X0, num_weight_updates, inner_iters, max_final_iters, set_
         X, w = read()
     finally:
         close()
-    ds.vals[:, -1] = w
+    if store is None:
+        ds.vals[:, -1] = w
+    else:
+        store(w)
     return {"X": X, "weights": w.copy(), "loop_closures": lc, "rounds": rounds,
             "final": {"iterations": int(out["iters"]), "cost_2f": float(out["cost"][-1]),
                       "gradnorm": float(out["gradnorm"][-1])}}
@@ -207,6 +211,27 @@ def multi_robot_gnc_session(ds, X0, num_robots=5, r=5, robust=None, num_weight_u
                      set_X=s.set_X, run=lambda iters: s.run(max_iters=iters, rgrad_tol=rgrad_tol),
                      reweight=lambda u: _counts(s.update_weights()), read=lambda: (s.get_X(), s.get_weights()),
                      close=s.close)
+
+
+def gnc_ra_session(ra, X0, r, robust=None, num_weight_updates=10, inner_iters=30, rgrad_tol=0.1, max_final_iters=1000,
+                   acceleration=True, restart_interval=30, params=None, fixed=None, device=0):
+    """multi_robot_gnc_session's flow on a multi-robot range-aided problem (RADataset), in ONE RaRbcdSession: the
+    reference's agents run the same robust outer loop on a RangeAidedSLAMGraph as on a pose graph (ref
+    src/Agent.cpp:1280-1441), over the pose-pose loop closures only (:1349-1395).  X0 is r x k in the global RA ordering;
+    weights, loop_closures and fixed are in pose-pose order.
+
+    ra keeps the final weights (set_pose_pose_weights).  Returns X, weights, per-round records."""
+    from . import RaRbcdSession
+    from . import robust as rb
+    lc = ra.loop_closures()
+    if fixed is not None:
+        lc &= ~np.asarray(fixed, bool)
+    s = RaRbcdSession(ra, r, acceleration=acceleration, restart_interval=restart_interval, params=params, device=device,
+                      robust=robust or rb.RobustCostParameters("GNC_TLS"), fixed_weight=fixed)
+    return _gnc_loop(ra, lc, X0, num_weight_updates, inner_iters, max_final_iters, set_X=s.set_X,
+                     run=lambda iters: s.run(max_iters=iters, rgrad_tol=rgrad_tol),
+                     reweight=lambda u: _counts(s.update_weights()), read=lambda: (s.get_X(), s.get_weights()),
+                     close=s.close, store=ra.set_pose_pose_weights)
 
 
 def multi_robot_team_session(ds, X0, num_robots=5, r=5, robust=None, team=None, acceleration=True, params=None,

@@ -80,6 +80,19 @@ def measurement_errors(ds, X, device=0):
     return out
 
 
+def ra_measurement_errors(ra, X, device=0):
+    """measurement_errors for the pose-pose measurements of a range-aided dataset (RADataset): X is r x k in the global
+    RA ordering; one squared error per pose-pose measurement, weights not applied (dcora_ra_measurement_errors)"""
+    X = np.asarray(X, dtype=np.float64)
+    out = np.zeros(max(ra.num_pose_pose, 1))
+    h = ra.handle()
+    try:
+        check(capi.lib().dcora_ra_measurement_errors(h, X.shape[0], F(X), out, device))
+    finally:
+        capi.lib().dcora_radataset_destroy(h)
+    return out[:ra.num_pose_pose]
+
+
 def solvePGO(ds, params, T0=None, device=0):
     """solvePGO (ref src/DCORA_solver.cpp:304-328); returns (T, result dict)"""
     h = ds.handle()

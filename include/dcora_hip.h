@@ -616,6 +616,39 @@ int dcora_exchange_update_weights(dcora_exchange_t ex, int reset_to_initial, int
 int dcora_exchange_set_weights(dcora_exchange_t ex, const double *w);
 /* all m current weights of the job, the same on every rank */
 int dcora_exchange_get_weights(dcora_exchange_t ex, double *w);
+/* --- robust range-aided sessions: the same GNC loop inside a live dcora_ra_rbcd session.  The reference's Agent runs
+ *     initializeRobustOptimization / updateMeasurementWeights / setMeasurementWeight (ref src/Agent.cpp:1332-1346,
+ *     1397-1441, 1443-1454) on a RangeAidedSLAMGraph as on a pose graph, over the pose-pose loop closures only
+ *     (computeMeasurementResidual, :1349-1395, refuses every other type): range and pose-landmark weights never change.
+ *     Weights are in pose-pose order (dcora_radataset_copy).  Single-process sessions only. --- */
+/* Host only.  mask: one flag per pose-pose measurement, 1 for a loop closure, 0 for odometry -- both poses of one robot
+ * (dcora_radataset_ownership) and consecutive in that robot's own numbering.  The RA counterpart of the contiguous
+ * partition's rule above. */
+int dcora_radataset_loop_closures(dcora_radataset_t ds, int *mask);
+/* Host only.  w: m_pp weights, each finite and >= 0 (else DCORA_ERR_BAD_ARG, the dataset left as it was).
+ * dcora_radataset_build_Q, dcora_radataset_copy and every session created afterwards see them; a pose-pose measurement
+ * of weight 0 contributes no entry to Q. */
+int dcora_radataset_set_pose_pose_weights(dcora_radataset_t ds, const double *w);
+/* out: m_pp squared errors kappa |Y1 R - Y2|^2 + tau |p2 - p1 - Y1 t|^2 (weights not applied) at X, r x k in the global
+ * RA ordering, d <= r <= 16: dcora_measurement_errors with the RA addressing, the same expression bit for bit */
+int dcora_ra_measurement_errors(dcora_radataset_t ds, int r, const double *X, double *out, int device);
+/* dcora_ra_rbcd_create with Agent::initializeRobustOptimization: weight 1 on every loop closure
+ * (dcora_radataset_loop_closures) whose fixed_weight flag (m_pp ints, may be NULL) is 0.  The patterns of every agent's
+ * Q_aa, of its coupling block and of the central Q are those of these weights, the largest any later weights can give;
+ * neighbours, public columns and colours stay those of creation whatever the weights become (a weight of 0 on the only
+ * measurement joining two agents would separate them in a fresh session; the reference, too, keeps a weight-0
+ * measurement in its graph).  opt->world_size > 1: DCORA_ERR_UNSUPPORTED. */
+int dcora_ra_rbcd_create_robust(dcora_radataset_t ds, const dcora_rbcd_options *opt, const dcora_robust_params *robust,
+                                const int *fixed_weight, dcora_ra_rbcd_t *out);
+/* The contracts of dcora_rbcd_update_weights / _set_weights / _get_weights / _robust_info.  The weights come from the
+ * mirror (the global iterate); every agent's Q_aa, its regularisation (recomputed as the reference does whenever the
+ * data matrices are rebuilt, ref src/Graph.cpp:1906, 1921), its preconditioner, its coupling block and the central Q
+ * are rebuilt through the path creation takes; reset_to_initial: X = the last dcora_ra_rbcd_set_X.  On a session of
+ * dcora_ra_rbcd_create: DCORA_ERR_BAD_ARG (DCORA_ERR_UNSUPPORTED when its world_size > 1). */
+int dcora_ra_rbcd_update_weights(dcora_ra_rbcd_t s, int reset_to_initial, int counts[3]);
+int dcora_ra_rbcd_set_weights(dcora_ra_rbcd_t s, const double *w);
+int dcora_ra_rbcd_get_weights(dcora_ra_rbcd_t s, double *w);
+int dcora_ra_rbcd_robust_info(dcora_ra_rbcd_t s, double *mu, int *updates);
 
 /* --- agent status, team termination and weight-update decisions (ref src/Agent.cpp:558-586, 1123-1156, 1280-1330) --- */
 /* the fields of AgentParameters the three rules read (ref include/DCORA/Agent.h:113-125); defaults: 500 iterations,
