@@ -189,6 +189,18 @@ class RADataset:
             capi.lib().dcora_radataset_destroy(h)
         return mask[:self.num_pose_pose].astype(bool)
 
+    def loop_closure_stats(self, robot):
+        """Graph::statistics (ref src/Graph.cpp:475-521) of one robot on the current weights, host only: accepted
+        (weight 1), rejected (weight 0) and all loop closures -- pose-pose loop closures, pose-landmark measurements and
+        ranges -- with an end at the robot: what a session of this dataset starts with (RaRbcdSession.loop_closure_stats)"""
+        h = self.handle()
+        try:
+            c = np.zeros(3, np.int32)
+            check(capi.lib().dcora_radataset_loop_closure_stats(h, int(robot), c))
+        finally:
+            capi.lib().dcora_radataset_destroy(h)
+        return {"accepted": int(c[0]), "rejected": int(c[1]), "total": int(c[2])}
+
     def set_pose_pose_weights(self, w):
         """the weights of the pose-pose measurements (each finite and >= 0): kept by this object, applied to every
         handle() -- so every session created afterwards sees them -- and to Q, which is rebuilt.  None: the file's (1)."""
@@ -222,6 +234,22 @@ class RADataset:
         finally:
             capi.lib().dcora_radataset_destroy(h)
         return ids[:m], vals[:m]
+
+    def measurements(self):
+        """all three measurement lists as dcora_radataset_copy writes them, a dict of (ids, vals) pairs: pose_pose (as
+        pose_pose()), pose_landmark (ids m x 2: pose, landmark; vals m x (d + 2): t, tau, weight) and ranges (ids m x 5:
+        type1, i, type2, j, unit sphere, type 0 a pose and 1 a landmark; vals m x 3: range, precision, weight)"""
+        h = self.handle()
+        try:
+            d = self.d
+            shapes = [(self.num_pose_pose, 2, d * d + d + 3), (self.num_pose_landmark, 2, d + 2), (self.num_range, 5, 3)]
+            arrs = [(np.zeros((max(m, 1), wi), np.int32), np.zeros((max(m, 1), wv))) for m, wi, wv in shapes]
+            vp = lambda a: a.ctypes.data_as(C.c_void_p)
+            check(capi.lib().dcora_radataset_copy(h, *[vp(a) for pair in arrs for a in pair]))
+        finally:
+            capi.lib().dcora_radataset_destroy(h)
+        return {name: (ids[:m], vals[:m])
+                for name, (m, _, _), (ids, vals) in zip(("pose_pose", "pose_landmark", "ranges"), shapes, arrs)}
 
     def colours(self):
         """(colours, number of colours) of the agents -- the robots owning poses, in id order -- as a session of this
@@ -1183,13 +1211,29 @@ def max_translation_distance(X, Y, d):
     return out.value
 
 
+def ra_max_translation_distance(X, Y, d, n, l=0, b=0):
+    """the same over the poses of two r x k arrays in the RA ordering [rotations | l unit spheres | translations |
+    b landmarks], k = (d+1) n + l + b, by the kernel of a range-aided agent's relative change: unit spheres and
+    landmarks never count"""
+    X, Y = np.asarray(X, np.float64), np.asarray(Y, np.float64)
+    if X.shape != Y.shape or X.ndim != 2 or X.shape[1] != (d + 1) * n + l + b:
+        raise ValueError("ra_max_translation_distance needs two r x ((d+1) n + l + b) arrays")
+    out = C.c_double()
+    check(capi.lib().dcora_ra_max_translation_distance(X.shape[0], d, n, l, b, F(X), F(Y), C.byref(out)))
+    return out.value
+
+
 def _team_fn(self, name):
-    """the team entry of a session (dcora_rbcd_<name>) or of a job's exchange (dcora_exchange_<name>)"""
-    return getattr(capi.lib(), ("dcora_exchange_" if isinstance(self, Exchange) else "dcora_rbcd_") + name)
+    """the team entry of a session (dcora_rbcd_<name>, dcora_ra_rbcd_<name>) or of a job's exchange
+    (dcora_exchange_<name>)"""
+    prefix = ("dcora_exchange_" if isinstance(self, Exchange) else
+              "dcora_ra_rbcd_" if isinstance(self, RaRbcdSession) else "dcora_rbcd_")
+    return getattr(capi.lib(), prefix + name)
 
 
 def _enable_team(self, params=None, **kw):
-    """opt in to the team protocol (dcora_rbcd_team_enable; on an Exchange dcora_exchange_team_enable, SPMD): every
+    """opt in to the team protocol (dcora_rbcd_team_enable / dcora_ra_rbcd_team_enable; on an Exchange
+    dcora_exchange_team_enable, SPMD): every
     iterate(true) of an agent stores its status -- across the ranks of a job, on every rank"""
     self.team = params if params is not None else team_params(**kw)
     check(_team_fn(self, "team_enable")(self.h, C.byref(self.team)))
@@ -1229,7 +1273,8 @@ def _team_info(self):
 
 
 def _run_team(self):
-    """the agents' own loop (dcora_rbcd_run_team / dcora_exchange_run_team): until should_terminate(), each pass
+    """the agents' own loop (dcora_rbcd_run_team / dcora_ra_rbcd_run_team / dcora_exchange_run_team): until
+    should_terminate(), each pass
     re-weights when should_update_weights() says so, then iterates the greedily selected agent"""
     n = max(int(self.team.max_num_iters), 1)
     it, nupd, why = C.c_int(), C.c_int(), C.c_int()
@@ -1244,7 +1289,8 @@ def _run_team(self):
                 stop_reason={capi.TEAM_STOP_ALL_READY: "all_ready", capi.TEAM_STOP_MAX_ITERS: "max_iters"}[why.value])
 
 
-for _cls in (RbcdSession, Exchange):  # the same records from a session and from the exchange of a multi-rank job
+# the same records from a session of either kind and from the exchange of a multi-rank job
+for _cls in (RbcdSession, RaRbcdSession, Exchange):
     _cls.enable_team = _enable_team
     _cls.agent_status = _agent_status
     _cls.loop_closure_stats = _loop_closure_stats

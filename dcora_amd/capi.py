@@ -256,6 +256,15 @@ SIGNATURES = {
     "dcora_ra_rbcd_set_weights": (C.c_int, [_vp, _dp]),
     "dcora_ra_rbcd_get_weights": (C.c_int, [_vp, _dp]),
     "dcora_ra_rbcd_robust_info": (C.c_int, [_vp, _PD, _PI]),
+    "dcora_ra_max_translation_distance": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _PD]),
+    "dcora_radataset_loop_closure_stats": (C.c_int, [_vp, C.c_int, _ip]),
+    "dcora_ra_rbcd_team_enable": (C.c_int, [_vp, C.POINTER(TeamParams)]),
+    "dcora_ra_rbcd_agent_status": (C.c_int, [_vp, C.c_int, C.POINTER(AgentStatus), _PI]),
+    "dcora_ra_rbcd_loop_closure_stats": (C.c_int, [_vp, C.c_int, _ip]),
+    "dcora_ra_rbcd_should_terminate": (C.c_int, [_vp, _PI]),
+    "dcora_ra_rbcd_should_update_weights": (C.c_int, [_vp, _PI]),
+    "dcora_ra_rbcd_team_info": (C.c_int, [_vp, _ip]),
+    "dcora_ra_rbcd_run_team": (C.c_int, [_vp, _PI, _vp, _vp, _vp, _vp, _PI, _PI]),
     "dcora_problem_time_qapply": (C.c_int, [_vp, C.c_int, _PD, _PD]),
     "dcora_problem_time_qapply_rotating": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int, _PD]),
     "dcora_problem_qapply_info": (C.c_int, [_vp, _dp]),

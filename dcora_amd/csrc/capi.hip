@@ -1002,6 +1002,22 @@ int dcora_radataset_set_pose_pose_weights(dcora_radataset_t h, const double *w) 
     return DCORA_OK;
   });
 }
+// Graph::statistics (ref src/Graph.cpp:475-521) of one robot of the file, host only
+int dcora_radataset_loop_closure_stats(dcora_radataset_t h, int robot, int counts[3]) {
+  return abi_call({h, counts}, [&] {
+    std::vector<TeamLoopClosure> lcs;
+    ra_team_loop_closures(h->ds, &lcs);
+    // robots 0 (this one) and 1 (everybody else): the counter's agents
+    std::vector<int> c(6, 0);
+    for (TeamLoopClosure &q : lcs) {
+      q.a1 = q.a1 == robot ? 0 : 1;
+      q.a2 = q.a2 == robot ? 0 : 1;
+      team_count_loop_closure(c.data(), q, q.w0);
+    }
+    for (int i = 0; i < 3; ++i) counts[i] = c[(size_t)i];
+    return DCORA_OK;
+  });
+}
 int dcora_graph_extract_agent_blocks(int k, const int *rp, const int *ci, const double *v, int k_a, const int *own,
                                      dcora_csr_t *Qaa, dcora_csr_t *C) {
   return abi_call({rp, ci, v, own, Qaa, C}, [&]() -> int {
@@ -1230,22 +1246,27 @@ int dcora_team_decide(const dcora_team_params *params, int robust, int iteration
 int dcora_max_translation_distance(int r, int d, int n, const double *X, const double *Y, double *out) {
   return abi_call({X, Y, out}, [&] { return max_translation_distance(r, d, n, X, Y, out); });
 }
+// the same over the poses of two arrays in the RA ordering, through k_rel_change's range-aided form
+int dcora_ra_max_translation_distance(int r, int d, int n, int l, int b, const double *X, const double *Y,
+                                      double *out) {
+  return abi_call({X, Y, out}, [&] { return ra_max_translation_distance(r, d, n, l, b, X, Y, out); });
+}
 namespace {
 int team_session(dcora_rbcd_t s) {
   return s->s.team ? (int)DCORA_OK : bad("rbcd team: the session has not called dcora_rbcd_team_enable");
 }
 // the team's queries over the session that holds the statuses: a single session's own, or the one of a job's rank
 // (dcora_rbcd_* and dcora_exchange_* differ in how they reach it and in the refusal above)
-int team_agent_status(RbcdSession &s, int agent, dcora_agent_status *status, int *known) {
+int team_agent_status(SessionCore &s, int agent, dcora_agent_status *status, int *known) {
   if (agent < 0 || agent >= s.R) return bad("bad agent");
   return s.team_agent_status(agent, status, known);
 }
-int team_loop_closure_stats(RbcdSession &s, int agent, int counts[3]) {
+int team_loop_closure_stats(SessionCore &s, int agent, int counts[3]) {
   if (agent < 0 || agent >= s.R) return bad("bad agent");
   for (int c = 0; c < 3; ++c) counts[c] = s.team->lc[(size_t)agent * 3 + c];
   return (int)DCORA_OK;
 }
-int team_info(RbcdSession &s, int info[4]) {
+int team_info(SessionCore &s, int info[4]) {
   info[0] = s.team_inner_iter();
   info[1] = s.team->latest_weight_update_iteration;
   info[2] = s.team_weight_updates();
@@ -1714,6 +1735,63 @@ int dcora_ra_rbcd_robust_info(dcora_ra_rbcd_t s, double *mu, int *updates) {
     if (mu) *mu = s->s.robust->cost.mu();
     if (updates) *updates = s->s.robust->updates;
     return (int)DCORA_OK;
+  });
+}
+// ---- agent status and the team's decisions on a range-aided session (the dcora_rbcd_* namesakes' contracts) ----
+namespace {
+int ra_team_session(dcora_ra_rbcd_t s) {
+  return s->s.team ? (int)DCORA_OK : bad("ra_rbcd team: the session has not called dcora_ra_rbcd_team_enable");
+}
+}  // namespace
+// the opt-in to Agent::iterate's status block (ref src/Agent.cpp:558-586) and the bookkeeping of :1417-1424
+int dcora_ra_rbcd_team_enable(dcora_ra_rbcd_t s, const dcora_team_params *params) {
+  return abi_call({s, params}, [&] { return s->s.team_enable(*params); });
+}
+// Agent::getStatus (ref include/DCORA/Agent.h:427-433) of one agent of the session
+int dcora_ra_rbcd_agent_status(dcora_ra_rbcd_t s, int agent, dcora_agent_status *status, int *known) {
+  return abi_call({s, status}, [&] {
+    const int rc = ra_team_session(s);
+    return rc ? rc : team_agent_status(s->s, agent, status, known);
+  });
+}
+// Graph::statistics (ref src/Graph.cpp:475-521) of one agent's RangeAidedSLAMGraph
+int dcora_ra_rbcd_loop_closure_stats(dcora_ra_rbcd_t s, int agent, int counts[3]) {
+  return abi_call({s, counts}, [&] {
+    const int rc = ra_team_session(s);
+    return rc ? rc : team_loop_closure_stats(s->s, agent, counts);
+  });
+}
+// Agent::shouldTerminate (ref src/Agent.cpp:1123-1156) over the statuses the session holds
+int dcora_ra_rbcd_should_terminate(dcora_ra_rbcd_t s, int *yes) {
+  return abi_call({s, yes}, [&] {
+    const int rc = ra_team_session(s);
+    return rc ? rc : s->s.team_decide(yes, nullptr);
+  });
+}
+// Agent::shouldUpdateMeasurementWeights (ref src/Agent.cpp:1280-1330) over the statuses the session holds
+int dcora_ra_rbcd_should_update_weights(dcora_ra_rbcd_t s, int *yes) {
+  return abi_call({s, yes}, [&] {
+    const int rc = ra_team_session(s);
+    return rc ? rc : s->s.team_decide(nullptr, yes);
+  });
+}
+// mRobustOptInnerIter, mLatestWeightUpdateIteration, mWeightUpdateCount, mTrajectoryResetCount (ref
+// include/DCORA/Agent.h:720-735)
+int dcora_ra_rbcd_team_info(dcora_ra_rbcd_t s, int info[4]) {
+  return abi_call({s, info}, [&] {
+    const int rc = ra_team_session(s);
+    return rc ? rc : team_info(s->s, info);
+  });
+}
+// the optimisation loop of the agents (ref src/Agent.cpp:650-678 with :1123-1156, 1280-1330, 1397-1441) on the
+// synchronous schedule of dcora_ra_rbcd_run
+int dcora_ra_rbcd_run_team(dcora_ra_rbcd_t s, int *iters_done, double *cost2_trace, double *gradnorm_trace,
+                           int *selected_trace, int *updated_trace, int *weight_updates, int *stop_reason) {
+  return abi_call({s}, [&] {
+    const int rc = ra_team_session(s);
+    return rc ? rc
+              : s->s.run_team(iters_done, cost2_trace, gradnorm_trace, selected_trace, updated_trace, weight_updates,
+                              stop_reason);
   });
 }
 

@@ -915,7 +915,7 @@ int Exchange::team_collect(const int *agents, int count) {
   return DCORA_OK;
 }
 
-// RbcdSession::run_team across the ranks: the same loop of the same rules on every rank's copy of the statuses
+// SessionCore::run_team across the ranks: the same loop of the same rules on every rank's copy of the statuses
 int Exchange::run_team(int *iters_done, double *cost2_trace, double *gradnorm_trace, int *selected_trace,
                        int *updated_trace, int *weight_updates, int *stop_reason) {
   RbcdSession &s = *pose_;

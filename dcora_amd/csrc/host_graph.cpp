@@ -538,6 +538,21 @@ void ra_loop_closures(const HostRADataset &ds, int *mask) {
   }
 }
 
+void ra_team_loop_closures(const HostRADataset &ds, std::vector<TeamLoopClosure> *out) {
+  out->clear();
+  std::vector<int> lc(ds.pose_pose.size());
+  ra_loop_closures(ds, lc.data());
+  for (size_t e = 0; e < ds.pose_pose.size(); ++e) {
+    const PoseMeas &q = ds.pose_pose[e];
+    if (lc[e]) out->push_back({(int)e, ds.pose_robot[(size_t)q.p1], ds.pose_robot[(size_t)q.p2], q.weight});
+  }
+  for (const PoseLandmarkMeasH &q : ds.pose_landmark)
+    out->push_back({-1, ds.pose_robot[(size_t)q.i], ds.landmark_robot[(size_t)q.j], q.weight});
+  for (const RangeMeasH &q : ds.ranges)
+    out->push_back({-1, q.type1 ? ds.landmark_robot[(size_t)q.i] : ds.pose_robot[(size_t)q.i],
+                    q.type2 ? ds.landmark_robot[(size_t)q.j] : ds.pose_robot[(size_t)q.j], q.weight});
+}
+
 void extract_agent_blocks(const HostCsr &Q, const std::vector<int> &own, HostCsr *Qaa, HostCsr *C) {
   const int ka = (int)own.size();
   std::vector<int> local((size_t)Q.n, -1);

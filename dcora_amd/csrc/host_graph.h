@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "host_sparse.h"
+#include "team_rules.h"
 
 namespace dcora {
 
@@ -69,6 +70,11 @@ void ra_agent_columns(const HostRADataset &ds, int robot, int dims3[3], std::vec
 // that robot's own numbering (what Agent::updateMeasurementWeights re-weights on a RangeAidedSLAMGraph, ref
 // src/Agent.cpp:1397-1441; the RA counterpart of driver.loop_closure_mask)
 void ra_loop_closures(const HostRADataset &ds, int *mask);
+// The loop closures of Graph::statistics on a RangeAidedSLAMGraph (ref src/Graph.cpp:121-134, 475-521): every measurement
+// but pose-pose odometry (ra_loop_closures' rule) -- pose-pose loop closures (id: index in pose_pose), pose-landmark
+// measurements and ranges (id -1: their weights are the file's and never change).  a1 / a2: the owner ROBOTS of the two
+// ends, a range's by their types; w0: the dataset's weight.
+void ra_team_loop_closures(const HostRADataset &ds, std::vector<TeamLoopClosure> *out);
 // The agent's share of a global quadratic form: Qaa = Q[own, own] in the agent's ordering and the coupling
 // C = Q[own, everything else] with GLOBAL column indices, so that the agent's linear term is G_a = X_global C^T
 // (the same restriction the reference assembles edge by edge, ref src/Graph.cpp:824-1772)

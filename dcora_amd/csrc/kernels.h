@@ -365,7 +365,16 @@ struct RelChangePublish {
 };
 void launch_rel_change_ranked(hipStream_t st, int r, int d, const double *X, const double *XPrev, const int *pose_start,
                               const RelChangeSet &set, const RelChangePublish &pub);
+// The range-aided form (ra_rbcd.h): every agent of the set has its own X / XPrev (r x k_a, its own RA ordering), n poses
+// and the column of its first translation, toff = d n_a + l_a; unit spheres and landmarks never count.  out[agent[i]].
+struct RaRelChangeSet {
+  int count;
+  int agent[kMaxAgents], n[kMaxAgents], toff[kMaxAgents];
+  const double *X[kMaxAgents], *XPrev[kMaxAgents];
+};
+void launch_rel_change_ra(hipStream_t st, int r, const RaRelChangeSet &set, double *out);
 int max_translation_distance(int r, int d, int n, const double *X, const double *Y, double *out);
+int ra_max_translation_distance(int r, int d, int n, int l, int b, const double *X, const double *Y, double *out);
 int launch_g_retract(hipStream_t st, const ManiDesc &m, Buf2 X, const double *V, double alpha, Buf2 out, int selOut,
                      Buf2 grad, const double *HV, double *partials, Gate g);
 void launch_g_nesterov(hipStream_t st, const ManiDesc &m, int mode, int restart, int skip_lo, int skip_hi,

@@ -94,6 +94,18 @@ int RaRbcdSession::init(const HostRADataset &ds, const dcora_rbcd_options &o) {
     a.k = (int)a.own_host.size();
     ++idx;
   }
+  // the team's loop closures, the agents (positions in the sorted robot list) owning their ends for the robots
+  ra_team_loop_closures(ds, &team_lcs_);
+  {
+    const std::vector<int> sorted(robots.begin(), robots.end());
+    auto agent_of = [&](int robot) {
+      return (int)(std::lower_bound(sorted.begin(), sorted.end(), robot) - sorted.begin());
+    };
+    for (TeamLoopClosure &q : team_lcs_) {  // (every owner is one of `robots`: checked above)
+      q.a1 = agent_of(q.a1);
+      q.a2 = agent_of(q.a2);
+    }
+  }
   const int rc = assemble(ds, true);
   if (rc) return rc;
   iteration = 0;
@@ -290,7 +302,7 @@ int RaRbcdSession::update_weights(bool reset_to_initial, int counts[3]) {
   if (rc) return rc;
   rs.cost.update();
   rs.updates++;
-  inner_rounds = 0;  // mRobustOptInnerIter = 0 (ref src/Agent.cpp:1418-1424)
+  team_weights_updated();  // (ref src/Agent.cpp:1418-1424)
   if (counts)
     for (int c = 0; c < 3; ++c) counts[c] = (int)cnt[c];
   return DCORA_OK;
@@ -324,6 +336,7 @@ int RaRbcdSession::adopt_weights(HostRADataset &ds, bool from_device, bool reset
     DCORA_HIP(hipMemcpy(rs.edges.w.p, held.data(), sizeof(double) * m, hipMemcpyHostToDevice));
   }
   if (rc) return rc;
+  if (team) team_refresh_counts();
   if (reset_to_initial)
     DCORA_HIP(hipMemcpyAsync(Xg.p, rs.X_initial.p, sizeof(double) * (size_t)r * k, hipMemcpyDeviceToDevice, st));
   rc = gather_agents();  // (after a reset the agents' own X comes from the mirror; otherwise it is what they hold)
@@ -374,6 +387,7 @@ int RaRbcdSession::set_X(const double *Xh) {
   DCORA_HIP(hipStreamSynchronize(st));
   gamma = alpha = 0;
   iteration = 0;
+  team_restart_rounds();
   return DCORA_OK;
 }
 
@@ -464,6 +478,10 @@ int RaRbcdSession::phase_selected(int selected) {
       DCORA_HIP(hipMemcpyAsync(a.X.p, res, Ba, hipMemcpyDeviceToDevice, st));
     }
     scatter(a);
+    if (team) {  // behind both solves of a restart round: the X the round leaves against the XPrev it saved
+      const int rc = team_note_optimized(&selected, 1);
+      if (rc) return rc;
+    }
   }
   if (restart) gamma = alpha = 0;
   return DCORA_OK;
@@ -518,6 +536,7 @@ int RaRbcdSession::set_acceleration(bool on) {
   }
   gamma = alpha = 0;
   iteration = 0;
+  team_restart_rounds();
   return DCORA_OK;
 }
 
@@ -540,6 +559,32 @@ int RaRbcdSession::write_back(AgentCore &core, hipStream_t run_on) {
   if (rc) return rc;
   DCORA_HIP(hipMemcpyAsync(a.X.p, res, sizeof(double) * (size_t)r * a.k, hipMemcpyDeviceToDevice, run_on));
   launch_scatter_cols(run_on, r, a.k, a.own.p, a.X.p, Xg.p);
+  return DCORA_OK;
+}
+
+// the tick's updates are all enqueued and the session's stream waits for every one of them
+int RaRbcdSession::tick_done(const std::vector<AgentCore *> &work) {
+  if (!team) return DCORA_OK;
+  std::vector<int> ids;
+  for (const AgentCore *a : work) ids.push_back((int)(static_cast<const RaAgentDev *>(a) - agents.data()));
+  return team_note_optimized(ids.data(), (int)ids.size());
+}
+
+// Agent::iterate's maxTranslationDistance(X, XPrev) (ref src/Agent.cpp:564-565) of agents just marked, over their poses
+// only: one launch on the session's stream, every agent's own two buffers and its translations' first column by value
+int RaRbcdSession::team_launch_rel_change(const std::vector<int> &ids) {
+  RaRelChangeSet set{};
+  for (int b : ids) {
+    const RaAgentDev &a = agents[(size_t)b];
+    set.agent[set.count] = b;
+    set.X[set.count] = a.X.p;
+    set.XPrev[set.count] = a.XPrev.p;
+    set.n[set.count] = a.n;
+    set.toff[set.count] = d * a.n + a.l;
+    set.count++;
+  }
+  launch_rel_change_ra(st, r, set, team->rel_dev);
+  DCORA_HIP(hipGetLastError());
   return DCORA_OK;
 }
 
@@ -591,7 +636,7 @@ int RaRbcdSession::evaluate(double *cost2, double *gradnorm, double *block_norms
   if (cost2) *cost2 = 2.0 * (0.5 * h[0] + h[1]);
   if (gradnorm) *gradnorm = std::sqrt(h[2]);
   if (next_selected) *next_selected = arg;
-  return DCORA_OK;
+  return team ? team_settle(true) : (int)DCORA_OK;  // (the stream has been synchronised past the statuses' launch)
 }
 
 int RaRbcdSession::last_result(dcora_ropt_result *res) {

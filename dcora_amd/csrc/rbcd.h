@@ -56,41 +56,6 @@ struct RobustSession {
   HostCsr central_pat;
 };
 
-// Team protocol of a session that called dcora_rbcd_team_enable: every agent's status as Agent::iterate(true) stores it
-// (ref src/Agent.cpp:558-586) and the bookkeeping Agent::updateMeasurementWeights does on it (:1417-1424).  The relative
-// change comes from k_rel_change through host-mapped memory: a status is `pending` from its launch until the host has
-// seen the stream pass it (the evaluation epilogue's seq, or a synchronisation in the query), then it is settled by
-// team_ready_to_terminate with what the agent knew when it optimised.
-struct TeamState {
-  dcora_team_params params{};
-  double *rel_host = nullptr, *rel_dev = nullptr;  // kMaxAgents relative changes, written by k_rel_change
-  TeamState() = default;
-  TeamState(const TeamState &) = delete;
-  TeamState &operator=(const TeamState &) = delete;
-  ~TeamState() {
-    if (rel_host) (void)hipHostFree((void *)rel_host);
-  }
-  std::vector<dcora_agent_status> status;          // by agent; have[b] == 0: none since the last clear
-  std::vector<int> have;
-  struct Pending {
-    bool on = false, success = false;
-    int updates = 0, lc[3] = {0, 0, 0};
-  };
-  std::vector<Pending> pending;
-  std::vector<int> lc;  // 3 per agent: accepted, rejected, all loop closures (Graph::statistics, ref src/Graph.cpp:475-521)
-  int latest_weight_update_iteration = 0, resets_done = 0;
-  // Ranked mode (the session is one rank of a job, enabled by Exchange::team_enable): every rank keeps the statuses of
-  // all R agents.  What an agent knew when it optimised -- round, weight-update count, loop-closure counts -- every
-  // rank knows; whether its update succeeded and its relative change only the hosting rank does, and those two travel
-  // through the agent's status slot of the job's segment (the ranked k_rel_change), collected by the exchange inside
-  // the collective call.  Nothing is read from rel_host.
-  bool ranked = false;
-  ShmStatus *slots = nullptr, *slots_dev = nullptr;  // [2][R], host and device view (owned by the exchange)
-  std::vector<uint64_t> seq;     // optimisations of agent a since the team was enabled: the same on every rank
-  const double *job_w = nullptr; // the job's m weights as of the last weight change (the exchange's copy); null on an
-                                 // L2 job, whose counts come from the creation weights
-};
-
 class RbcdSession : public SessionCore {
  public:
   int d = 0, n = 0;
@@ -142,22 +107,15 @@ class RbcdSession : public SessionCore {
   int agent_update_neighbor(int agent, int neighbor, int count, const int *frames, const double *poses, bool aux);
   std::vector<int> agent_it;  // Agent::iteration_number() of every agent
   int agent_iteration_number(int agent) const;
-  // ---- the team protocol (dcora_rbcd_team_enable) ----
-  std::unique_ptr<TeamState> team;
-  int team_enable(const dcora_team_params &p);
-  // ... of a rank of a job (through its exchange only): the status area and the job's weights the exchange keeps
+  // ---- the team protocol (session_core.h); what stays here is the half of a rank of a job, through its exchange only:
+  // the status area and the job's weights the exchange keeps
   int team_enable_ranked(const dcora_team_params &p, ShmStatus *slots, ShmStatus *slots_dev, const double *job_w);
   // ranked: the bookkeeping of team_note_optimized for those agents of ids that live on another rank, and the two facts
   // the hosting rank published for one agent settled into its status
   void team_note_elsewhere(const int *ids, int count);
   void team_settle_published(int agent, bool success, double relative_change);
-  int team_agent_status(int agent, dcora_agent_status *status, int *known);
-  int team_decide(int *should_terminate, int *should_update_weights);
-  bool team_robust() const { return robust && robust->params.cost_type != DCORA_ROBUST_L2; }
-  int team_weight_updates() const { return robust ? robust->updates : 0; }
-  int team_inner_iter() const { return team_robust() ? inner_rounds : 0; }
-  int run_team(int *iters_done, double *cost2_trace, double *gradnorm_trace, int *selected_trace, int *updated_trace,
-               int *weight_updates, int *stop_reason);
+  bool team_robust() const override { return robust && robust->params.cost_type != DCORA_ROBUST_L2; }
+  int team_weight_updates() const override { return robust ? robust->updates : 0; }
   long chain_launches = 0;  // kernel launches of the chain's wrappers enqueued by iterate() (debug counter)
   int pack_public(int agent, double *packed_dev);
   int unpack_public(int agent, const double *packed_dev);
@@ -185,17 +143,15 @@ class RbcdSession : public SessionCore {
   int write_back(AgentCore &a, hipStream_t run_on) override;
   bool serial_set(const std::vector<AgentCore *> &work) override;
   int tick_done(const std::vector<AgentCore *> &work) override;
-  // the team protocol's steps: agents that just ran iterate(true) (one k_rel_change launch behind their updates),
-  // pending statuses settled (visible: the host has already seen the stream pass their launch), the loop-closure
-  // counts after a weight change, the statuses cleared, the bookkeeping restarted with the round counter
-  int team_note_optimized(const int *ids, int count);
-  void team_mark_optimized(int agent, bool success);
-  int team_settle(bool visible);
-  void team_refresh_counts();
-  void team_clear_statuses();
-  void team_restart_rounds();
-  std::vector<int> lc_id_, lc_r1_, lc_r2_;  // the loop closures (every measurement but odometry): index, agents of its ends
-  std::vector<double> lc_w0_;               // their weights at creation (a session without robust state keeps them)
+  // the session kind's part of the team protocol (session_core.h)
+  int team_launch_rel_change(const std::vector<int> &ids) override;
+  double team_lc_weight(const TeamLoopClosure &q) const override;
+  bool team_last_success(int agent) const override { return !agents[(size_t)agent].last_skipped; }
+  int team_iteration_number(int agent) const override { return agent_iteration_number(agent); }
+  int team_update_weights(bool reset_to_initial) override { return update_weights(reset_to_initial, nullptr); }
+  int team_iterate(int selected, double *cost2, double *gradnorm, int *next_selected) override {
+    return iterate(selected, cost2, gradnorm, nullptr, next_selected);
+  }
   // session assembly (rbcd.hip): the host matrices of the hosted agents -- Q[i] = Q_bb, C[i] = coupling block of agent
   // ids[i] -- as the host builders give them
   struct MeasSplit;

@@ -147,10 +147,7 @@ int RbcdSession::init(const HostDataset &ds, const dcora_rbcd_options &o) {
     const PoseMeas &q = ds.meas[e];
     const int r1 = P.robot_of(q.p1), r2 = P.robot_of(q.p2);
     if (r1 == r2 && q.p2 == q.p1 + 1) continue;  // odometry
-    lc_id_.push_back((int)e);
-    lc_r1_.push_back(r1);
-    lc_r2_.push_back(r2);
-    lc_w0_.push_back(q.weight);
+    team_lcs_.push_back(TeamLoopClosure{(int)e, r1, r2, q.weight});
   }
   agents.resize(R);
   std::vector<int> cs(R + 1);
@@ -564,11 +561,7 @@ int RbcdSession::apply_weights(const std::vector<double> &w, bool reset_to_initi
   rs.cost.update();
   rs.updates++;
   // mLatestWeightUpdateIteration, mRobustOptInnerIter = 0, mTeamStatus.clear() (ref src/Agent.cpp:1418-1424)
-  inner_rounds = 0;
-  if (team) {
-    team->latest_weight_update_iteration = iteration;
-    team_clear_statuses();
-  }
+  team_weights_updated();
   return DCORA_OK;
 }
 
@@ -1098,31 +1091,6 @@ int RbcdSession::agent_iteration_number(int agent) const {
   return iteration;
 }
 
-int RbcdSession::team_enable(const dcora_team_params &p) {
-  if (opt.world_size != 1) {
-    set_last_error("rbcd team: only single-process sessions (world_size 1) keep the team's statuses by themselves; "
-                   "the ranks of a job enable the team through their exchange (dcora_exchange_team_enable)");
-    return DCORA_ERR_UNSUPPORTED;
-  }
-  if (team && team->ranked) {
-    set_last_error("rbcd team: the session's team was enabled through its exchange (dcora_exchange_team_enable)");
-    return DCORA_ERR_UNSUPPORTED;
-  }
-  if (!team) {
-    std::unique_ptr<TeamState> t(new TeamState);
-    DCORA_HIP(hipSetDevice(opt.device));
-    DCORA_HIP(hipHostMalloc((void **)&t->rel_host, sizeof(double) * kMaxAgents, hipHostMallocMapped));
-    std::memset((void *)t->rel_host, 0, sizeof(double) * kMaxAgents);
-    DCORA_HIP(hipHostGetDevicePointer((void **)&t->rel_dev, (void *)t->rel_host, 0));
-    team = std::move(t);
-    team_clear_statuses();
-    team->latest_weight_update_iteration = 0;
-    team_refresh_counts();
-  }
-  team->params = p;
-  return DCORA_OK;
-}
-
 int RbcdSession::team_enable_ranked(const dcora_team_params &p, ShmStatus *slots, ShmStatus *slots_dev,
                                     const double *job_w) {
   if (team && !team->ranked) {
@@ -1144,53 +1112,16 @@ int RbcdSession::team_enable_ranked(const dcora_team_params &p, ShmStatus *slots
   return DCORA_OK;
 }
 
-void RbcdSession::team_clear_statuses() {
-  if (!team) return;
-  team->status.assign((size_t)R, dcora_agent_status{});
-  team->have.assign((size_t)R, 0);
-  team->pending.assign((size_t)R, TeamState::Pending());
-}
-
-// the round counter restarts (set_X, set_acceleration, Agent::setX of every agent): what the team counts in rounds
-// restarts with it
-void RbcdSession::team_restart_rounds() {
-  inner_rounds = 0;
-  if (!team) return;
-  team->latest_weight_update_iteration = 0;
-  team_clear_statuses();
-}
-
-void RbcdSession::team_refresh_counts() {
-  team->lc.assign((size_t)R * 3, 0);
-  auto count = [&](int b, double w) {
-    int *c = &team->lc[(size_t)b * 3];
-    if (w == 1) c[0]++;
-    else if (w == 0) c[1]++;
-    c[2]++;
-  };
-  for (size_t k = 0; k < lc_id_.size(); ++k) {
-    // (a rank keeps only the weights of the edges touching its agents up to date: the job's come from its exchange)
-    const double w = team->job_w ? team->job_w[(size_t)lc_id_[k]]
-                                 : robust ? robust->meas[(size_t)lc_id_[k]].weight : lc_w0_[k];
-    count(lc_r1_[k], w);
-    if (lc_r2_[k] != lc_r1_[k]) count(lc_r2_[k], w);
-  }
-}
-
-// Agent::iterate's status block (ref src/Agent.cpp:558-586) for the agents that just optimised: one launch behind
-// everything their updates enqueued on the session's stream, compares the X the round leaves with the XPrev it saved
-int RbcdSession::team_note_optimized(const int *ids, int count) {
+// the session's relative-change launch for agents just marked: one launch behind everything their updates enqueued on
+// the session's stream, compares the X the round leaves with the XPrev it saved.  Ranked: into the agents' status slots
+int RbcdSession::team_launch_rel_change(const std::vector<int> &ids) {
   RelChangeSet set{};
   RelChangePublish pub{};
-  for (int i = 0; i < count && set.count < kMaxAgents; ++i) {
-    const int b = ids[i];
-    if (b < 0 || b >= R || !agents[(size_t)b].hosted) continue;
-    const bool success = !agents[(size_t)b].last_skipped;
-    team_mark_optimized(b, success);
+  for (int b : ids) {
     if (team->ranked) {
       // the slot was released by Exchange::team_clear_to_write before the agent's update was enqueued
       const uint64_t q = team->seq[(size_t)b];
-      team->slots[(size_t)(q & 1) * R + b].success = success ? 1u : 0u;
+      team->slots[(size_t)(q & 1) * R + b].success = team->pending[(size_t)b].success ? 1u : 0u;
       pub.seq[set.count] = q;
     }
     set.agent[set.count++] = b;
@@ -1207,22 +1138,9 @@ int RbcdSession::team_note_optimized(const int *ids, int count) {
   return DCORA_OK;
 }
 
-// what every rank knows of an optimisation of agent b in this round (ranked: hosted here or not)
-void RbcdSession::team_mark_optimized(int b, bool success) {
-  dcora_agent_status &s = team->status[(size_t)b];
-  s.agent_id = b;
-  s.state = DCORA_AGENT_INITIALIZED;
-  s.instance_number = 0;
-  s.iteration_number = iteration;
-  s.ready_to_terminate = 0;
-  s.relative_change = 0;
-  team->have[(size_t)b] = 1;
-  TeamState::Pending &p = team->pending[(size_t)b];
-  p.on = true;
-  p.success = success;
-  p.updates = team_weight_updates();
-  for (int c = 0; c < 3; ++c) p.lc[c] = team->lc[(size_t)b * 3 + c];
-  if (team->ranked) team->seq[(size_t)b]++;
+// (a rank keeps only the weights of the edges touching its agents up to date: the job's come from its exchange)
+double RbcdSession::team_lc_weight(const TeamLoopClosure &q) const {
+  return team->job_w ? team->job_w[(size_t)q.id] : robust ? robust->meas[(size_t)q.id].weight : q.w0;
 }
 
 void RbcdSession::team_note_elsewhere(const int *ids, int count) {
@@ -1241,89 +1159,6 @@ void RbcdSession::team_settle_published(int b, bool success, double relative_cha
   s.relative_change = relative_change;
   s.ready_to_terminate = team_ready_to_terminate(team->params, team_robust(), p.updates, p.success, s.relative_change,
                                                  p.lc[0], p.lc[1], p.lc[2]) ? 1 : 0;
-}
-
-int RbcdSession::team_settle(bool visible) {
-  bool any = false;
-  for (const TeamState::Pending &p : team->pending) any = any || p.on;
-  if (!any || team->ranked) return DCORA_OK;  // (ranked: settled by the exchange's collective calls alone)
-  if (!visible) {
-    DCORA_HIP(hipSetDevice(opt.device));
-    DCORA_HIP(hipStreamSynchronize(st));
-  }
-  std::atomic_thread_fence(std::memory_order_acquire);
-  for (int b = 0; b < R; ++b) {
-    TeamState::Pending &p = team->pending[(size_t)b];
-    if (!p.on) continue;
-    p.on = false;
-    dcora_agent_status &s = team->status[(size_t)b];
-    s.relative_change = const_cast<const volatile double *>(team->rel_host)[b];
-    s.ready_to_terminate = team_ready_to_terminate(team->params, team_robust(), p.updates, p.success,
-                                                   s.relative_change, p.lc[0], p.lc[1], p.lc[2]) ? 1 : 0;
-  }
-  return DCORA_OK;
-}
-
-int RbcdSession::team_agent_status(int agent, dcora_agent_status *status, int *known) {
-  const int rc = team_settle(false);
-  if (rc) return rc;
-  if (team->have[(size_t)agent]) {
-    *status = team->status[(size_t)agent];
-  } else {
-    *status = dcora_agent_status{};
-    status->agent_id = agent;
-    status->state = DCORA_AGENT_INITIALIZED;
-    status->iteration_number = agent_iteration_number(agent);
-  }
-  if (known) *known = team->have[(size_t)agent];
-  return DCORA_OK;
-}
-
-int RbcdSession::team_decide(int *should_terminate, int *should_update_weights) {
-  const int rc = team_settle(false);
-  if (rc) return rc;
-  const TeamView v{team_robust(), iteration, team_weight_updates(), team_inner_iter(),
-                   team->latest_weight_update_iteration, team->status.data(), team->have.data(), nullptr, R};
-  if (should_terminate) *should_terminate = team_should_terminate(team->params, v) ? 1 : 0;
-  if (should_update_weights) *should_update_weights = team_should_update_weights(team->params, v) ? 1 : 0;
-  return DCORA_OK;
-}
-
-// the agents' own loop (ref src/Agent.cpp:650-678 shape, the synchronous schedule of examples/MultiRobotExample.cpp):
-// stop and re-weight by the team rules instead of a central gradient norm and fixed counts
-int RbcdSession::run_team(int *iters_done, double *cost2_trace, double *gradnorm_trace, int *selected_trace,
-                          int *updated_trace, int *weight_updates, int *stop_reason) {
-  const int cap = team->params.max_num_iters;
-  int selected = 0, it = 0, nupd = 0;
-  for (;;) {
-    int stop = 0, upd = 0;
-    int rc = team_decide(&stop, nullptr);
-    if (rc) return rc;
-    if (stop || it >= cap) break;
-    rc = team_decide(nullptr, &upd);
-    if (rc) return rc;
-    if (updated_trace) updated_trace[it] = upd;
-    if (upd) {
-      const bool reset = team->resets_done < team->params.robust_opt_num_resets;
-      rc = update_weights(reset, nullptr);
-      if (rc) return rc;
-      if (reset) team->resets_done++;
-      nupd++;
-    }
-    double c2 = 0, gn = 0;
-    int nxt = selected;
-    rc = iterate(selected, &c2, &gn, nullptr, &nxt);
-    if (rc) return rc;
-    if (cost2_trace) cost2_trace[it] = c2;
-    if (gradnorm_trace) gradnorm_trace[it] = gn;
-    if (selected_trace) selected_trace[it] = selected;
-    selected = nxt;
-    ++it;
-  }
-  if (iters_done) *iters_done = it;
-  if (weight_updates) *weight_updates = nupd;
-  if (stop_reason) *stop_reason = iteration >= cap ? DCORA_TEAM_STOP_MAX_ITERS : DCORA_TEAM_STOP_ALL_READY;
-  return DCORA_OK;
 }
 
 }  // namespace dcora

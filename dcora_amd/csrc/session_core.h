@@ -12,6 +12,7 @@
 
 #include "device_problem.h"
 #include "session_cert.h"
+#include "team_rules.h"
 
 namespace dcora {
 
@@ -24,6 +25,42 @@ struct AgentCore {
   std::vector<int> neighbors;           // agents sharing a measurement with me (all agents)
   hipStream_t own_st = nullptr;         // stream of my solve when several agents update at once (hosted agents only;
   hipEvent_t done = nullptr;            // both owned by the session)
+};
+
+// Team protocol of a session that called dcora_rbcd_team_enable / dcora_ra_rbcd_team_enable: every agent's status as
+// Agent::iterate(true) stores it (ref src/Agent.cpp:558-586) and the bookkeeping Agent::updateMeasurementWeights does on
+// it (:1417-1424).  The relative change comes from k_rel_change, in the session kind's form of it, through host-mapped
+// memory: a status is `pending` from its launch until the host has seen the stream pass it (an evaluation the host has
+// waited for, or a synchronisation in the query), then it is settled by team_ready_to_terminate with what the agent
+// knew when it optimised.
+struct TeamState {
+  dcora_team_params params{};
+  double *rel_host = nullptr, *rel_dev = nullptr;  // kMaxAgents relative changes, written by k_rel_change
+  TeamState() = default;
+  TeamState(const TeamState &) = delete;
+  TeamState &operator=(const TeamState &) = delete;
+  ~TeamState() {
+    if (rel_host) (void)hipHostFree((void *)rel_host);
+  }
+  std::vector<dcora_agent_status> status;          // by agent; have[b] == 0: none since the last clear
+  std::vector<int> have;
+  struct Pending {
+    bool on = false, success = false;
+    int updates = 0, lc[3] = {0, 0, 0};
+  };
+  std::vector<Pending> pending;
+  std::vector<int> lc;  // 3 per agent: accepted, rejected, all loop closures (Graph::statistics, ref src/Graph.cpp:475-521)
+  int latest_weight_update_iteration = 0, resets_done = 0;
+  // Ranked mode (the session is one rank of a job, enabled by Exchange::team_enable): every rank keeps the statuses of
+  // all R agents.  What an agent knew when it optimised -- round, weight-update count, loop-closure counts -- every
+  // rank knows; whether its update succeeded and its relative change only the hosting rank does, and those two travel
+  // through the agent's status slot of the job's segment (the ranked k_rel_change), collected by the exchange inside
+  // the collective call.  Nothing is read from rel_host.
+  bool ranked = false;
+  ShmStatus *slots = nullptr, *slots_dev = nullptr;  // [2][R], host and device view (owned by the exchange)
+  std::vector<uint64_t> seq;     // optimisations of agent a since the team was enabled: the same on every rank
+  const double *job_w = nullptr; // the job's m weights as of the last weight change (the exchange's copy); null on an
+                                 // L2 job, whose counts come from the creation weights
 };
 
 class SessionCore {
@@ -71,6 +108,20 @@ class SessionCore {
   virtual const HostCsr *central_live_pattern() const { return nullptr; }
   virtual int cert_block() const = 0;  // unknowns the factorisation orders together (d + 1 for poses)
 
+  // ---- the team protocol of a single-process session (dcora_rbcd_team_enable / dcora_ra_rbcd_team_enable): the
+  // bookkeeping of Agent::iterate's status block, shouldTerminate, shouldUpdateMeasurementWeights and
+  // updateMeasurementWeights (ref src/Agent.cpp:558-586, 1123-1156, 1280-1330, 1417-1424), the same on either graph type
+  std::unique_ptr<TeamState> team;
+  int team_enable(const dcora_team_params &p);
+  int team_agent_status(int agent, dcora_agent_status *status, int *known);
+  int team_decide(int *should_terminate, int *should_update_weights);
+  virtual bool team_robust() const = 0;         // cost type != L2
+  virtual int team_weight_updates() const = 0;  // mWeightUpdateCount
+  int team_inner_iter() const { return team_robust() ? inner_rounds : 0; }
+  // the agents' own loop: stop and re-weight by the team rules instead of a central gradient norm and fixed counts
+  int run_team(int *iters_done, double *cost2_trace, double *gradnorm_trace, int *selected_trace, int *updated_trace,
+               int *weight_updates, int *stop_reason);
+
  protected:
   const char *tag_;  // "rbcd" / "ra_rbcd": the prefix of the messages
   hipEvent_t fork_ev_ = nullptr;
@@ -100,6 +151,27 @@ class SessionCore {
   virtual bool serial_set(const std::vector<AgentCore *> &work) = 0;
   // the tick's updates are all enqueued (the session's stream waits for every one of them)
   virtual int tick_done(const std::vector<AgentCore *> &work) { return DCORA_OK; }
+
+  // the team protocol's steps: agents that just ran iterate(true) (one launch of the relative-change kernel behind their
+  // updates), pending statuses settled (visible: the host has already seen the stream pass their launch), the
+  // loop-closure counts after a weight change, the statuses cleared, the weight update of this round recorded, the
+  // bookkeeping restarted with the round counter
+  int team_note_optimized(const int *ids, int count);
+  void team_mark_optimized(int agent, bool success);
+  int team_settle(bool visible);
+  void team_refresh_counts();
+  void team_clear_statuses();
+  void team_weights_updated();
+  void team_restart_rounds();
+  std::vector<TeamLoopClosure> team_lcs_;  // the session's loop closures, filled at creation
+  // what a session kind supplies to the team protocol:
+  // its relative-change kernel for these hosted agents, just marked, enqueued on the session's stream
+  virtual int team_launch_rel_change(const std::vector<int> &ids) = 0;
+  virtual double team_lc_weight(const TeamLoopClosure &q) const = 0;  // the current weight of one of team_lcs_
+  virtual bool team_last_success(int agent) const { return true; }    // `success` of the agent's last local update
+  virtual int team_iteration_number(int agent) const { return iteration; }
+  virtual int team_update_weights(bool reset_to_initial) = 0;
+  virtual int team_iterate(int selected, double *cost2, double *gradnorm, int *next_selected) = 0;
 
  private:
   int solve_block(AgentCore &a, std::string *err, bool serial);

@@ -1,7 +1,9 @@
 // The session core on the host (see session_core.h).
 #include "session_core.h"
 
+#include <atomic>
 #include <cmath>
+#include <cstring>
 
 #include "host_graph.h"
 #include "host_threads.h"
@@ -167,6 +169,177 @@ int SessionCore::iterate_set(const int *set, int count, int allow_adjacent) {
     DCORA_HIP(hipStreamWaitEvent(st, work[i]->done, 0));
   }
   return tick_done(work);
+}
+
+// ---- the team protocol ----------------------------------------------------------------------------------------------
+int SessionCore::team_enable(const dcora_team_params &p) {
+  const std::string tag = std::string(tag_) + " team: ";
+  if (opt.world_size != 1) {
+    set_last_error(tag + "only single-process sessions (world_size 1) keep the team's statuses by themselves; "
+                   "the ranks of a pose-graph job enable the team through their exchange (dcora_exchange_team_enable)");
+    return DCORA_ERR_UNSUPPORTED;
+  }
+  if (team && team->ranked) {
+    set_last_error(tag + "the session's team was enabled through its exchange (dcora_exchange_team_enable)");
+    return DCORA_ERR_UNSUPPORTED;
+  }
+  if (!team) {
+    std::unique_ptr<TeamState> t(new TeamState);
+    DCORA_HIP(hipSetDevice(opt.device));
+    DCORA_HIP(hipHostMalloc((void **)&t->rel_host, sizeof(double) * kMaxAgents, hipHostMallocMapped));
+    std::memset((void *)t->rel_host, 0, sizeof(double) * kMaxAgents);
+    DCORA_HIP(hipHostGetDevicePointer((void **)&t->rel_dev, (void *)t->rel_host, 0));
+    team = std::move(t);
+    team_clear_statuses();
+    team->latest_weight_update_iteration = 0;
+    team_refresh_counts();
+  }
+  team->params = p;
+  return DCORA_OK;
+}
+
+void SessionCore::team_clear_statuses() {
+  if (!team) return;
+  team->status.assign((size_t)R, dcora_agent_status{});
+  team->have.assign((size_t)R, 0);
+  team->pending.assign((size_t)R, TeamState::Pending());
+}
+
+// a weight update has been made in this round: mLatestWeightUpdateIteration, mRobustOptInnerIter = 0,
+// mTeamStatus.clear() (ref src/Agent.cpp:1418-1424)
+void SessionCore::team_weights_updated() {
+  inner_rounds = 0;
+  if (!team) return;
+  team->latest_weight_update_iteration = iteration;
+  team_clear_statuses();
+}
+
+// the round counter restarts (set_X, set_acceleration, Agent::setX of every agent): what the team counts in rounds
+// restarts with it
+void SessionCore::team_restart_rounds() {
+  inner_rounds = 0;
+  if (!team) return;
+  team->latest_weight_update_iteration = 0;
+  team_clear_statuses();
+}
+
+void SessionCore::team_refresh_counts() {
+  team->lc.assign((size_t)R * 3, 0);
+  for (const TeamLoopClosure &q : team_lcs_) team_count_loop_closure(team->lc.data(), q, team_lc_weight(q));
+}
+
+// Agent::iterate's status block (ref src/Agent.cpp:558-586) for the agents that just optimised: marked, then the session
+// kind's one launch behind everything their updates enqueued on the session's stream
+int SessionCore::team_note_optimized(const int *ids, int count) {
+  std::vector<int> marked;
+  for (int i = 0; i < count && (int)marked.size() < kMaxAgents; ++i) {
+    const int b = ids[i];
+    if (b < 0 || b >= R || !agent_core(b).hosted) continue;
+    team_mark_optimized(b, team_last_success(b));
+    marked.push_back(b);
+  }
+  return team_launch_rel_change(marked);
+}
+
+// what every rank knows of an optimisation of agent b in this round (ranked: hosted here or not)
+void SessionCore::team_mark_optimized(int b, bool success) {
+  dcora_agent_status &s = team->status[(size_t)b];
+  s.agent_id = b;
+  s.state = DCORA_AGENT_INITIALIZED;
+  s.instance_number = 0;
+  s.iteration_number = iteration;
+  s.ready_to_terminate = 0;
+  s.relative_change = 0;
+  team->have[(size_t)b] = 1;
+  TeamState::Pending &p = team->pending[(size_t)b];
+  p.on = true;
+  p.success = success;
+  p.updates = team_weight_updates();
+  for (int c = 0; c < 3; ++c) p.lc[c] = team->lc[(size_t)b * 3 + c];
+  if (team->ranked) team->seq[(size_t)b]++;
+}
+
+int SessionCore::team_settle(bool visible) {
+  bool any = false;
+  for (const TeamState::Pending &p : team->pending) any = any || p.on;
+  if (!any || team->ranked) return DCORA_OK;  // (ranked: settled by the exchange's collective calls alone)
+  if (!visible) {
+    DCORA_HIP(hipSetDevice(opt.device));
+    DCORA_HIP(hipStreamSynchronize(st));
+  }
+  std::atomic_thread_fence(std::memory_order_acquire);
+  for (int b = 0; b < R; ++b) {
+    TeamState::Pending &p = team->pending[(size_t)b];
+    if (!p.on) continue;
+    p.on = false;
+    dcora_agent_status &s = team->status[(size_t)b];
+    s.relative_change = const_cast<const volatile double *>(team->rel_host)[b];
+    s.ready_to_terminate = team_ready_to_terminate(team->params, team_robust(), p.updates, p.success,
+                                                   s.relative_change, p.lc[0], p.lc[1], p.lc[2]) ? 1 : 0;
+  }
+  return DCORA_OK;
+}
+
+int SessionCore::team_agent_status(int agent, dcora_agent_status *status, int *known) {
+  const int rc = team_settle(false);
+  if (rc) return rc;
+  if (team->have[(size_t)agent]) {
+    *status = team->status[(size_t)agent];
+  } else {
+    *status = dcora_agent_status{};
+    status->agent_id = agent;
+    status->state = DCORA_AGENT_INITIALIZED;
+    status->iteration_number = team_iteration_number(agent);
+  }
+  if (known) *known = team->have[(size_t)agent];
+  return DCORA_OK;
+}
+
+int SessionCore::team_decide(int *should_terminate, int *should_update_weights) {
+  const int rc = team_settle(false);
+  if (rc) return rc;
+  const TeamView v{team_robust(), iteration, team_weight_updates(), team_inner_iter(),
+                   team->latest_weight_update_iteration, team->status.data(), team->have.data(), nullptr, R};
+  if (should_terminate) *should_terminate = team_should_terminate(team->params, v) ? 1 : 0;
+  if (should_update_weights) *should_update_weights = team_should_update_weights(team->params, v) ? 1 : 0;
+  return DCORA_OK;
+}
+
+// the agents' own loop (ref src/Agent.cpp:650-678 shape, the synchronous schedule of examples/MultiRobotExample.cpp):
+// stop and re-weight by the team rules instead of a central gradient norm and fixed counts
+int SessionCore::run_team(int *iters_done, double *cost2_trace, double *gradnorm_trace, int *selected_trace,
+                          int *updated_trace, int *weight_updates, int *stop_reason) {
+  const int cap = team->params.max_num_iters;
+  int selected = 0, it = 0, nupd = 0;
+  for (;;) {
+    int stop = 0, upd = 0;
+    int rc = team_decide(&stop, nullptr);
+    if (rc) return rc;
+    if (stop || it >= cap) break;
+    rc = team_decide(nullptr, &upd);
+    if (rc) return rc;
+    if (updated_trace) updated_trace[it] = upd;
+    if (upd) {
+      const bool reset = team->resets_done < team->params.robust_opt_num_resets;
+      rc = team_update_weights(reset);
+      if (rc) return rc;
+      if (reset) team->resets_done++;
+      nupd++;
+    }
+    double c2 = 0, gn = 0;
+    int nxt = selected;
+    rc = team_iterate(selected, &c2, &gn, &nxt);
+    if (rc) return rc;
+    if (cost2_trace) cost2_trace[it] = c2;
+    if (gradnorm_trace) gradnorm_trace[it] = gn;
+    if (selected_trace) selected_trace[it] = selected;
+    selected = nxt;
+    ++it;
+  }
+  if (iters_done) *iters_done = it;
+  if (weight_updates) *weight_updates = nupd;
+  if (stop_reason) *stop_reason = iteration >= cap ? DCORA_TEAM_STOP_MAX_ITERS : DCORA_TEAM_STOP_ALL_READY;
+  return DCORA_OK;
 }
 
 }  // namespace dcora

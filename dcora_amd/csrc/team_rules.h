@@ -32,6 +32,26 @@ inline bool team_ready_to_terminate(const dcora_team_params &p, bool robust, int
   return ready;
 }
 
+// Graph::statistics (ref src/Graph.cpp:475-521) over private_lcs_ and shared_lcs_, which by Graph::addMeasurement
+// (:121-134) hold every measurement but pose-pose odometry.  One entry per such measurement: the agents owning its two
+// ends (it counts at each, once when they are the same), its weight at creation, and id: where its current weight is
+// kept when a session re-weights it (a measurement index; < 0: the weight never changes).
+struct TeamLoopClosure {
+  int id, a1, a2;
+  double w0;
+};
+// counts: 3 per agent -- accepted (weight == 1 exactly), rejected (weight == 0 exactly), all
+inline void team_count_loop_closure(int *counts, const TeamLoopClosure &q, double weight) {
+  auto count = [&](int a) {
+    int *c = counts + 3 * (long)a;
+    if (weight == 1) c[0]++;
+    else if (weight == 0) c[1]++;
+    c[2]++;
+  };
+  count(q.a1);
+  if (q.a2 != q.a1) count(q.a2);
+}
+
 struct TeamView {
   bool robust;
   int iteration_number, weight_update_count, inner_iter, latest_weight_update_iteration;

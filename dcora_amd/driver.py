@@ -263,6 +263,39 @@ def multi_robot_team_session(ds, X0, num_robots=5, r=5, robust=None, team=None, 
                       "weight_updates": int(out["weight_updates"]), "stop_reason": out["stop_reason"]}}
 
 
+def ra_team_session(ra, X0, r, robust=None, team=None, acceleration=True, restart_interval=30, params=None,
+                    fixed=None, device=0):
+    """multi_robot_team_session's flow on a multi-robot range-aided problem (RADataset), in ONE RaRbcdSession: the
+    reference's agents run the same status block, termination and weight-update rules on a RangeAidedSLAMGraph as on a
+    pose graph (ref src/Agent.cpp:558-586, 1123-1156, 1280-1441), re-weighting the pose-pose loop closures only.  X0 is
+    r x k in the global RA ordering; weights, loop_closures and fixed are in pose-pose order, statuses and
+    loop_closure_stats by agent (position in the sorted robot list).
+
+    ra keeps the final weights (set_pose_pose_weights).  Returns the record of multi_robot_team_session."""
+    from . import RaRbcdSession, team_params
+    from . import robust as rb
+    lc = ra.loop_closures()
+    if fixed is not None:
+        lc &= ~np.asarray(fixed, bool)
+    s = RaRbcdSession(ra, r, acceleration=acceleration, restart_interval=restart_interval, params=params, device=device,
+                      robust=robust or rb.RobustCostParameters("GNC_TLS"), fixed_weight=fixed)
+    try:
+        s.enable_team(team if team is not None else team_params())
+        s.set_X(np.asarray(X0, dtype=np.float64))
+        out = s.run_team()
+        X, w = s.get_X(), s.get_weights()
+        statuses = [s.agent_status(q) for q in range(s.R)]
+        stats = [s.loop_closure_stats(q) for q in range(s.R)]
+    finally:
+        s.close()
+    ra.set_pose_pose_weights(w)
+    return {"X": X, "weights": w.copy(), "loop_closures": lc, "run": out,
+            "statuses": statuses, "loop_closure_stats": stats,
+            "final": {"iterations": int(out["iters"]), "cost_2f": float(out["cost"][-1]) if out["iters"] else None,
+                      "gradnorm": float(out["gradnorm"][-1]) if out["iters"] else None,
+                      "weight_updates": int(out["weight_updates"]), "stop_reason": out["stop_reason"]}}
+
+
 def exchange_run(ex, max_iters=1000, rgrad_tol=0.1):
     """RbcdSession.run across the ranks: greedy passes through Exchange.iterate until |rgrad| < rgrad_tol, at most
     max_iters (the loop of dcora_rbcd_run, ref examples/MultiRobotExample.cpp:223-307)"""

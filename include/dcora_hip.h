@@ -717,6 +717,48 @@ typedef enum { DCORA_TEAM_STOP_ALL_READY = 1, DCORA_TEAM_STOP_MAX_ITERS = 2 } dc
  * agent 0 }.  The traces (any may be NULL) hold max_num_iters entries, entry it belonging to pass it. */
 int dcora_rbcd_run_team(dcora_rbcd_t s, int *iters_done, double *cost2_trace, double *gradnorm_trace,
                         int *selected_trace, int *updated_trace, int *weight_updates, int *stop_reason);
+/* ---- the team protocol on a range-aided session of one process ----
+ * The reference's agents run the same three rules on a RangeAidedSLAMGraph as on a pose graph: the status block of
+ * Agent::iterate (ref src/Agent.cpp:558-586), shouldTerminate (:1123-1156), shouldUpdateMeasurementWeights (:1280-1330)
+ * and the bookkeeping of updateMeasurementWeights (:1417-1424).  The contracts are the dcora_rbcd_* namesakes'.
+ * dcora_ra_max_translation_distance: LiftedArray::maxTranslationDistance(*X.GetLiftedPoseArray(), ...) (ref
+ * src/Agent.cpp:564-565, src/manifold/Elements.cpp:59-69) of two arrays r x k, k = (d+1) n + l + b, in the RA ordering
+ * [rotations | l unit spheres | translations | b landmarks] (column-major, host) by the kernel that computes a
+ * range-aided agent's relative change: over the POSES only (translation i is column d n + l + i), unit spheres and
+ * landmarks never count.  2 <= r <= 16, d in {2, 3}, d <= r, n >= 1, l >= 0, b >= 0. */
+int dcora_ra_max_translation_distance(int r, int d, int n, int l, int b, const double *X, const double *Y,
+                                      double *out);
+/* Graph::statistics (ref src/Graph.cpp:475-521) of `robot` on the dataset's current weights, host only (no device):
+ * accepted (weight == 1), rejected (weight == 0) and all loop closures with an end at the robot.  By
+ * Graph::addMeasurement (ref :121-134) a loop closure is every measurement but pose-pose odometry
+ * (dcora_radataset_loop_closures' rule): pose-pose loop closures, pose-landmark measurements and ranges, each counted
+ * at the owner of either end (a range's ends by their types), once when both are the robot's.  These are the counts a
+ * session of this dataset starts with for that robot. */
+int dcora_radataset_loop_closure_stats(dcora_radataset_t ds, int robot, int counts[3]);
+/* Opt-in (ref src/Agent.cpp:558-586, 1417-1424) on a session of dcora_ra_rbcd_create (an L2 team) or
+ * dcora_ra_rbcd_create_robust; world_size > 1: DCORA_ERR_UNSUPPORTED.  From here on every Agent::iterate(true) of an
+ * agent -- dcora_ra_rbcd_iterate, _run, _iterate_set, _run_coloured, _run_team -- stores that agent's status (state
+ * INITIALIZED, instance 0, the session's round, the relative change over the agent's poses): one more launch per
+ * round or tick, no synchronisation.  dcora_ra_rbcd_update_weights clears the statuses, records the round as the
+ * latest weight update and zeroes the inner counter; dcora_ra_rbcd_set_weights only refreshes the loop-closure counts
+ * (range and pose-landmark weights are the file's, pose-pose weights the session's current ones);
+ * dcora_ra_rbcd_set_X and _set_acceleration restart this bookkeeping with the rounds.  A session that never calls
+ * this launches nothing new.  The six entries below return DCORA_ERR_BAD_ARG before it. */
+int dcora_ra_rbcd_team_enable(dcora_ra_rbcd_t s, const dcora_team_params *params);
+/* Agent::getStatus (ref include/DCORA/Agent.h:427-433); `agent`: position in the sorted robot list */
+int dcora_ra_rbcd_agent_status(dcora_ra_rbcd_t s, int agent, dcora_agent_status *status, int *known);
+/* Graph::statistics (ref src/Graph.cpp:475-521) of the agent, on the session's current weights */
+int dcora_ra_rbcd_loop_closure_stats(dcora_ra_rbcd_t s, int agent, int counts[3]);
+/* Agent::shouldTerminate (ref src/Agent.cpp:1123-1156), Agent::shouldUpdateMeasurementWeights (ref :1280-1330) */
+int dcora_ra_rbcd_should_terminate(dcora_ra_rbcd_t s, int *yes);
+int dcora_ra_rbcd_should_update_weights(dcora_ra_rbcd_t s, int *yes);
+/* info[4] as dcora_rbcd_team_info (ref include/DCORA/Agent.h:720-735) */
+int dcora_ra_rbcd_team_info(dcora_ra_rbcd_t s, int info[4]);
+/* dcora_rbcd_run_team's loop (ref src/Agent.cpp:650-678) of dcora_ra_rbcd_update_weights and dcora_ra_rbcd_iterate:
+ * traces of max_num_iters entries, greedy selection starting with agent 0, reset = resets made <
+ * robust_opt_num_resets */
+int dcora_ra_rbcd_run_team(dcora_ra_rbcd_t s, int *iters_done, double *cost2_trace, double *gradnorm_trace,
+                           int *selected_trace, int *updated_trace, int *weight_updates, int *stop_reason);
 /* ---- the team protocol across the ranks of a job ----
  * The entries above on a multi-rank pose-graph job, through its exchange: semantics are their dcora_rbcd_* namesakes',
  * every rank holds every agent's status, and the outputs are identical on every rank.  Of an optimisation only its
