@@ -189,6 +189,18 @@ class RADataset:
             capi.lib().dcora_radataset_destroy(h)
         return mask[:self.num_pose_pose].astype(bool)
 
+    def rank_edges(self, rank, world_size):
+        """(touches, owns), one flag per pose-pose measurement each, of rank `rank` of a robust job of world_size ranks
+        (ra_robust_ranked_session; host only): either pose belongs to an agent the rank hosts; it hosts the owner of p1"""
+        h = self.handle()
+        try:
+            t = np.zeros(max(self.num_pose_pose, 1), np.int32)
+            o = np.zeros(max(self.num_pose_pose, 1), np.int32)
+            check(capi.lib().dcora_radataset_rank_edges(h, int(rank), int(world_size), t, o))
+        finally:
+            capi.lib().dcora_radataset_destroy(h)
+        return t[:self.num_pose_pose].astype(bool), o[:self.num_pose_pose].astype(bool)
+
     def loop_closure_stats(self, robot):
         """Graph::statistics (ref src/Graph.cpp:475-521) of one robot on the current weights, host only: accepted
         (weight 1), rejected (weight 0) and all loop closures -- pose-pose loop closures, pose-landmark measurements and
@@ -814,7 +826,7 @@ class Exchange:
     def __init__(self, session, job_name, _handle=None):
         self.s = session
         self.h = C.c_void_p()
-        if _handle is not None:  # (made together with its session: robust_ranked_session)
+        if _handle is not None:  # (made together with its session: robust_ranked_session / ra_robust_ranked_session)
             self.h = _handle
             return
         create = capi.lib().dcora_exchange_create_ra if isinstance(session, RaRbcdSession) else capi.lib().dcora_exchange_create
@@ -906,7 +918,7 @@ class Exchange:
     def barrier(self):
         check(capi.lib().dcora_exchange_barrier(self.h))
 
-    # ---- robust jobs (robust_ranked_session) ----
+    # ---- robust jobs (robust_ranked_session / ra_robust_ranked_session: m is then the pose-pose count) ----
     def update_weights(self, reset_to_initial=False):
         """Agent::updateMeasurementWeights of every agent on every rank (collective); returns the loop closures'
         {accepted, rejected, undecided} counts of the whole job"""
@@ -953,12 +965,28 @@ def robust_ranked_session(ds, job_name, num_robots=5, r=5, robust=None, fixed_we
     return s, Exchange(s, job_name, _handle=hx)
 
 
+def ra_robust_ranked_session(ra, job_name, r, robust=None, fixed_weight=None, rank=0, world_size=1, device=0,
+                             acceleration=True, restart_interval=30, params=None):
+    """(RaRbcdSession, Exchange) of one rank of a robust multi-rank range-aided job (dcora_ra_rbcd_create_robust_ranks):
+    robust_ranked_session's contract with the robust session of RaRbcdSession(robust=...) for the agents this rank
+    hosts.  Every rank calls this with the same arguments but rank; the job's weights (pose-pose order) change through
+    the exchange (update_weights / set_weights / get_weights), collectively.  The session's get_weights() is this
+    rank's view (NaN for pose-pose measurements touching none of its agents)."""
+    from . import robust as rb
+    s = RaRbcdSession(ra, r, acceleration=acceleration, restart_interval=restart_interval, params=params,
+                      device=device, rank=rank, world_size=world_size,
+                      robust=robust or rb.RobustCostParameters("GNC_TLS"), fixed_weight=fixed_weight,
+                      _ranked_job=job_name)
+    hx, s._exchange_handle = s._exchange_handle, None
+    return s, Exchange(s, job_name, _handle=hx)
+
+
 class RaRbcdSession:
     """the agents of a multi-robot range-aided SLAM problem + the synchronous RBCD++ driver on the device
     (ref examples/MultiRobotExample_RASLAM.cpp); X is the merged r x k matrix in the RA ordering"""
 
     def __init__(self, ra, r, acceleration=True, restart_interval=30, params=None, device=0, rank=0, world_size=1,
-                 robust=None, fixed_weight=None):
+                 robust=None, fixed_weight=None, _ranked_job=None):
         """robust: a robust.RobustCostParameters -> a session whose pose-pose weights update in place (update_weights /
         set_weights / get_weights / robust_info, as RbcdSession's); it starts with weight 1 on every loop closure
         (ra.loop_closures()) whose fixed_weight flag (one per pose-pose measurement, default none) is off"""
@@ -970,20 +998,24 @@ class RaRbcdSession:
         o.rank, o.world_size = rank, world_size
         if params is not None:
             o.local = params.c
+        fx = None
+        if robust is not None and fixed_weight is not None:
+            fx = np.ascontiguousarray(fixed_weight, np.int32)
+            if fx.shape != (self.m,):
+                raise ValueError("fixed_weight needs one flag per pose-pose measurement")
+        fxp = None if fx is None else fx.ctypes.data_as(C.c_void_p)
         dsh = ra.handle()
         self.h = C.c_void_p()
         try:
             if robust is None:
                 check(capi.lib().dcora_ra_rbcd_create(dsh, C.byref(o), C.byref(self.h)))
-            else:
-                fx = None
-                if fixed_weight is not None:
-                    fx = np.ascontiguousarray(fixed_weight, np.int32)
-                    if fx.shape != (self.m,):
-                        raise ValueError("fixed_weight needs one flag per pose-pose measurement")
-                check(capi.lib().dcora_ra_rbcd_create_robust(dsh, C.byref(o), C.byref(robust.c),
-                                                             None if fx is None else fx.ctypes.data_as(C.c_void_p),
-                                                             C.byref(self.h)))
+            elif _ranked_job is None:
+                check(capi.lib().dcora_ra_rbcd_create_robust(dsh, C.byref(o), C.byref(robust.c), fxp, C.byref(self.h)))
+            else:  # (ra_robust_ranked_session: made together with its exchange, whose handle goes to _exchange_handle)
+                self._exchange_handle = C.c_void_p()
+                check(capi.lib().dcora_ra_rbcd_create_robust_ranks(dsh, C.byref(o), C.byref(robust.c), fxp,
+                                                                   _ranked_job.encode(), C.byref(self.h),
+                                                                   C.byref(self._exchange_handle)))
         finally:
             capi.lib().dcora_radataset_destroy(dsh)
         n = C.c_int()

@@ -256,6 +256,9 @@ SIGNATURES = {
     "dcora_ra_rbcd_set_weights": (C.c_int, [_vp, _dp]),
     "dcora_ra_rbcd_get_weights": (C.c_int, [_vp, _dp]),
     "dcora_ra_rbcd_robust_info": (C.c_int, [_vp, _PD, _PI]),
+    "dcora_ra_rbcd_create_robust_ranks": (C.c_int, [_vp, C.POINTER(RbcdOptions), C.POINTER(RobustParams), _vp,
+                                                    C.c_char_p, C.POINTER(_vp), C.POINTER(_vp)]),
+    "dcora_radataset_rank_edges": (C.c_int, [_vp, C.c_int, C.c_int, _ip, _ip]),
     "dcora_ra_max_translation_distance": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _PD]),
     "dcora_radataset_loop_closure_stats": (C.c_int, [_vp, C.c_int, _ip]),
     "dcora_ra_rbcd_team_enable": (C.c_int, [_vp, C.POINTER(TeamParams)]),

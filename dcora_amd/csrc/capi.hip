@@ -38,7 +38,7 @@ struct dcora_rbcd_s {
 };
 struct dcora_exchange_s {
   Exchange e;
-  RbcdSession *ranked = nullptr;  // the robust session it was created with (dcora_rbcd_create_robust_ranks)
+  bool ranked = false;  // created with its robust session (dcora_rbcd_ / dcora_ra_rbcd_create_robust_ranks)
 };
 
 namespace {
@@ -993,6 +993,25 @@ int dcora_radataset_loop_closures(dcora_radataset_t h, int *mask) {
     return DCORA_OK;
   });
 }
+// the host rule of a ranked robust session (ra_rank_edges): one flag per pose-pose measurement
+int dcora_radataset_rank_edges(dcora_radataset_t h, int rank, int world_size, int *touches, int *owns) {
+  return abi_call({h, touches, owns}, [&]() -> int {
+    if (world_size < 1 || rank < 0 || rank >= world_size) return bad("rank_edges: bad rank / world_size");
+    if (h->ds.pose_robot.size() != (size_t)h->ds.n) return bad("rank_edges: the dataset has no pose owners");
+    for (const PoseMeas &q : h->ds.pose_pose)
+      if (q.p1 < 0 || q.p1 >= h->ds.n || q.p2 < 0 || q.p2 >= h->ds.n) return bad("rank_edges: pose index out of range");
+    std::vector<int> ids;
+    std::vector<char> own;
+    ra_rank_edges(h->ds, rank, world_size, &ids, &own);
+    std::fill(touches, touches + h->ds.pose_pose.size(), 0);
+    std::fill(owns, owns + h->ds.pose_pose.size(), 0);
+    for (size_t i = 0; i < ids.size(); ++i) {
+      touches[ids[i]] = 1;
+      owns[ids[i]] = own[i] ? 1 : 0;
+    }
+    return DCORA_OK;
+  });
+}
 int dcora_radataset_set_pose_pose_weights(dcora_radataset_t h, const double *w) {
   return abi_call({h, w}, [&]() -> int {
     const size_t m = h->ds.pose_pose.size();
@@ -1077,9 +1096,9 @@ int dcora_rbcd_create_robust_ranks(dcora_dataset_t ds, const dcora_rbcd_options 
     std::unique_ptr<dcora_exchange_s> x(new dcora_exchange_s);
     rc = x->e.init(&h->s, job_name, ds->ds.meas.size());
     if (rc) return rc;
-    rc = x->e.publish_weights(h->s);
+    rc = x->e.publish_weights();
     if (rc) return rc;
-    x->ranked = &h->s;
+    x->ranked = true;
     *session = h.release();
     *ex = x.release();
     return (int)DCORA_OK;
@@ -1104,7 +1123,9 @@ int local_robust_session(dcora_rbcd_t s, const char *collective) {
   return DCORA_ERR_UNSUPPORTED;
 }
 int ranked_exchange(dcora_exchange_t ex) {
-  return ex->ranked ? DCORA_OK : bad("exchange robust: the exchange was not created by dcora_rbcd_create_robust_ranks");
+  return ex->ranked ? DCORA_OK
+                    : bad("exchange robust: the exchange was not created by dcora_rbcd_create_robust_ranks or "
+                          "dcora_ra_rbcd_create_robust_ranks");
 }
 }  // namespace
 // Agent::updateMeasurementWeights (ref src/Agent.cpp:1397-1441) of every agent
@@ -1540,13 +1561,13 @@ int dcora_exchange_barrier(dcora_exchange_t ex) {
 int dcora_exchange_update_weights(dcora_exchange_t ex, int reset_to_initial, int counts[3]) {
   return abi_call({ex, counts}, [&] {
     const int rc = ranked_exchange(ex);
-    return rc ? rc : ex->e.update_weights(*ex->ranked, reset_to_initial != 0, counts);
+    return rc ? rc : ex->e.update_weights(reset_to_initial != 0, counts);
   });
 }
 int dcora_exchange_set_weights(dcora_exchange_t ex, const double *w) {
   return abi_call({ex, w}, [&] {
     const int rc = ranked_exchange(ex);
-    return rc ? rc : ex->e.set_weights(*ex->ranked, w);
+    return rc ? rc : ex->e.set_weights(w);
   });
 }
 int dcora_exchange_get_weights(dcora_exchange_t ex, double *w) {
@@ -1691,14 +1712,33 @@ int dcora_ra_rbcd_create_robust(dcora_radataset_t ds, const dcora_rbcd_options *
   return abi_call({ds, opt, robust, out}, [&]() -> int {
     if (opt->world_size != 1) {
       set_last_error("ra_rbcd robust: dcora_ra_rbcd_create_robust makes single-process sessions (world_size 1); "
-                     "re-weighting a range-aided problem across ranks is not supported");
+                     "a multi-rank job creates its sessions with dcora_ra_rbcd_create_robust_ranks");
       return DCORA_ERR_UNSUPPORTED;
     }
     return create(out, [&](dcora_ra_rbcd_s &h) { return h.s.init_robust(ds->ds, *opt, *robust, fixed_weight); });
   });
 }
+// the robust session of one rank of a range-aided job and its exchange, created together: weight updates are collective
+int dcora_ra_rbcd_create_robust_ranks(dcora_radataset_t ds, const dcora_rbcd_options *opt,
+                                      const dcora_robust_params *robust, const int *fixed_weight, const char *job_name,
+                                      dcora_ra_rbcd_t *session, dcora_exchange_t *ex) {
+  return abi_call({ds, opt, robust, job_name, session, ex}, [&]() -> int {
+    std::unique_ptr<dcora_ra_rbcd_s> h(new dcora_ra_rbcd_s);  // (destroyed on every failure below)
+    int rc = h->s.init_robust(ds->ds, *opt, *robust, fixed_weight, true);
+    if (rc) return rc;
+    std::unique_ptr<dcora_exchange_s> x(new dcora_exchange_s);
+    rc = x->e.init(&h->s, job_name, ds->ds.pose_pose.size());
+    if (rc) return rc;
+    rc = x->e.publish_weights();
+    if (rc) return rc;
+    x->ranked = true;
+    *session = h.release();
+    *ex = x.release();
+    return (int)DCORA_OK;
+  });
+}
 namespace {
-// the refusals of the robust entries, as robust_session states them for pose-graph sessions
+// the refusals of the robust entries, as robust_session / local_robust_session state them for pose-graph sessions
 int ra_robust_session(dcora_ra_rbcd_t s) {
   if (s->s.robust) return DCORA_OK;
   if (s->s.opt.world_size != 1) {
@@ -1707,18 +1747,25 @@ int ra_robust_session(dcora_ra_rbcd_t s) {
   }
   return bad("ra_rbcd robust: the session was not created by dcora_ra_rbcd_create_robust");
 }
+int ra_local_robust_session(dcora_ra_rbcd_t s, const char *collective) {
+  const int rc = ra_robust_session(s);
+  if (rc || !s->s.robust->ranked) return rc;
+  set_last_error(std::string("ra_rbcd robust: the session belongs to a multi-rank job "
+                             "(dcora_ra_rbcd_create_robust_ranks): its weights change through ") + collective);
+  return DCORA_ERR_UNSUPPORTED;
+}
 }  // namespace
 // Agent::updateMeasurementWeights (ref src/Agent.cpp:1397-1441) of every agent
 int dcora_ra_rbcd_update_weights(dcora_ra_rbcd_t s, int reset_to_initial, int counts[3]) {
   return abi_call({s}, [&] {
-    const int rc = ra_robust_session(s);
+    const int rc = ra_local_robust_session(s, "dcora_exchange_update_weights");
     return rc ? rc : s->s.update_weights(reset_to_initial != 0, counts);
   });
 }
 // Agent::setMeasurementWeight (ref src/Agent.cpp:1443-1454) of every pose-pose measurement
 int dcora_ra_rbcd_set_weights(dcora_ra_rbcd_t s, const double *w) {
   return abi_call({s, w}, [&] {
-    const int rc = ra_robust_session(s);
+    const int rc = ra_local_robust_session(s, "dcora_exchange_set_weights");
     return rc ? rc : s->s.set_weights(w);
   });
 }

@@ -32,7 +32,8 @@ extern std::atomic<int> g_probe_fault_rounds;  // test hook of the link check (d
 class Exchange {
  public:
   ~Exchange();
-  // weights: doubles of the segment's weights area (the m weights of a robust job, dcora_rbcd_create_robust_ranks)
+  // weights: doubles of the segment's weights area (the m weights of a robust job, dcora_rbcd_create_robust_ranks /
+  // dcora_ra_rbcd_create_robust_ranks)
   int init(SessionCore *s, const char *job_name, size_t weights = 0);
   int post(const int *agents, int count);
   int wait(const int *agents, int count);
@@ -53,13 +54,14 @@ class Exchange {
   int rbcd_tick(const int *set, int count, int allow_adjacent);
   // coloured sweeps across the ranks (run_coloured_sweeps): rbcd_tick per colour of the greedy colouring, then evaluate
   int run_coloured(int max_sweeps, double rgrad_tol, int *sweeps_done, double *cost2_trace, double *gradnorm_trace);
-  // Robust jobs (the session s was created by init_robust(..., ranked = true) and is the exchange's session):
-  // Agent::updateMeasurementWeights of every agent on every rank.  Each rank weights the edges touching its agents from
-  // its mirror, the owners store theirs into the weights area, counts are summed over the ranks.
-  int update_weights(RbcdSession &s, bool reset_to_initial, int counts[3]);
-  int set_weights(RbcdSession &s, const double *w);  // all m weights, the same on every rank
-  int get_weights(double *w);                        // all m weights of the job, from the weights area
-  int publish_weights(const RbcdSession &s);         // the owned edges' current weights into the area (creation)
+  // Robust jobs (the exchange's session was created by init_robust(..., ranked = true), of either kind: the session's
+  // part comes through SessionCore's weight hooks): Agent::updateMeasurementWeights of every agent on every rank.  Each
+  // rank weights the edges touching its agents from its mirror, the owners store theirs into the weights area, counts
+  // are summed over the ranks.  Weights are in the job's order: the dataset's, or a range-aided one's pose-pose.
+  int update_weights(bool reset_to_initial, int counts[3]);
+  int set_weights(const double *w);  // all m weights, the same on every rank
+  int get_weights(double *w);        // all m weights of the job, from the weights area
+  int publish_weights();             // the owned edges' current weights into the area (creation)
   // ---- the team protocol across the ranks (dcora_exchange_team_enable; pose-graph sessions) ----
   // Every rank keeps every agent's status (TeamState, ranked).  Of an optimisation only two facts are not known
   // everywhere: whether it succeeded and its relative change.  The hosting rank stores the first from the host, the

@@ -931,7 +931,7 @@ int Exchange::run_team(int *iters_done, double *cost2_trace, double *gradnorm_tr
     if (upd) {
       const bool reset = t.resets_done < t.params.robust_opt_num_resets;
       int counts[3];
-      rc = update_weights(s, reset, counts);
+      rc = update_weights(reset, counts);
       if (rc) return rc;
       if (reset) t.resets_done++;
       nupd++;
@@ -986,8 +986,9 @@ int Exchange::gather_X(double *Xh) {
 // RobustCost::update, X back to the last set_X if asked, acceleration re-initialised.  A shared edge is weighted on
 // both of its ranks from bitwise-equal mirror columns.  The weights area is written by the kernel while no rank reads
 // it: get_weights ends with a barrier, and the allreduce below is passed only once every rank's stores have landed.
-int Exchange::update_weights(RbcdSession &s, bool reset_to_initial, int counts[3]) {
-  if (!s.robust || !s.robust->ranked || &s != s_ || lay_.w_doubles != s.robust->meas.size())
+int Exchange::update_weights(bool reset_to_initial, int counts[3]) {
+  SessionCore &s = *s_;
+  if (!s.weights_ranked() || lay_.w_doubles != s.weights_count())
     return usage("update_weights: the exchange's session is not a ranked robust session", DCORA_ERR_BAD_ARG);
   std::vector<double> w;
   double cnt[3] = {0, 0, 0};
@@ -1016,11 +1017,12 @@ int Exchange::update_weights(RbcdSession &s, bool reset_to_initial, int counts[3
   return DCORA_OK;
 }
 
-// Every rank receives the same w, and RbcdSession::set_weights checks all m weights before anything changes (negative
+// Every rank receives the same w, and the session's set_weights checks all of them before anything changes (negative
 // or not finite, or nonzero where creation had 0): a refusal is the same on every rank and leaves the job as it was,
 // with the exchange usable.  The owners then store their edges' weights into the area.
-int Exchange::set_weights(RbcdSession &s, const double *w) {
-  if (!s.robust || !s.robust->ranked || &s != s_ || lay_.w_doubles != s.robust->meas.size())
+int Exchange::set_weights(const double *w) {
+  SessionCore &s = *s_;
+  if (!s.weights_ranked() || lay_.w_doubles != s.weights_count())
     return usage("set_weights: the exchange's session is not a ranked robust session", DCORA_ERR_BAD_ARG);
   // (the team's counts are refreshed from the job's weights inside: every rank is handed all m of them)
   std::vector<double> before;
@@ -1032,16 +1034,17 @@ int Exchange::set_weights(RbcdSession &s, const double *w) {
   if (rc && team_on()) std::copy(before.begin(), before.end(), job_w_.begin());
   if (rc == DCORA_ERR_BAD_ARG) return rc;  // (refused on every rank alike, nothing changed)
   if (rc) return fail(std::string("set_weights: ") + dcora_last_error(), rc);
-  return publish_weights(s);
+  return publish_weights();
 }
 
-// the weights the session holds for the edges this rank owns into the area (host stores), then a barrier
-int Exchange::publish_weights(const RbcdSession &s) {
-  const RobustSession &rs = *s.robust;
+// the weights the session holds for the measurements this rank owns into the area (host stores), then a barrier
+int Exchange::publish_weights() {
+  if (!s_->weights_ranked() || lay_.w_doubles != s_->weights_count())
+    return usage("publish_weights: the exchange's session is not a ranked robust session", DCORA_ERR_BAD_ARG);
   double *area = lay_.weights(map_);
-  for (size_t e = 0; e < rs.meas.size() && e < lay_.w_doubles; ++e) {
-    const PoseMeas &q = rs.meas[e];
-    if (owner_[(size_t)s.P.robot_of(q.p1)] == rank) area[e] = q.weight;
+  for (size_t e = 0; e < lay_.w_doubles; ++e) {
+    double w = 0;
+    if (s_->weight_owned(e, &w)) area[e] = w;
   }
   std::atomic_thread_fence(std::memory_order_release);
   return barrier();

@@ -538,6 +538,29 @@ void ra_loop_closures(const HostRADataset &ds, int *mask) {
   }
 }
 
+int ra_rank_of_agent(int agent, int num_agents, int world_size) {
+  const int per = (num_agents + world_size - 1) / world_size;  // consecutive agents share a rank
+  return agent / per;
+}
+
+void ra_rank_edges(const HostRADataset &ds, int rank, int world_size, std::vector<int> *ids, std::vector<char> *own) {
+  const std::set<int> with_poses(ds.pose_robot.begin(), ds.pose_robot.end());
+  const std::vector<int> robots(with_poses.begin(), with_poses.end());
+  auto rank_of = [&](int pose) {
+    const int robot = ds.pose_robot[(size_t)pose];
+    const int agent = (int)(std::lower_bound(robots.begin(), robots.end(), robot) - robots.begin());
+    return ra_rank_of_agent(agent, (int)robots.size(), world_size);
+  };
+  ids->clear();
+  own->clear();
+  for (size_t e = 0; e < ds.pose_pose.size(); ++e) {
+    const bool h1 = rank_of(ds.pose_pose[e].p1) == rank, h2 = rank_of(ds.pose_pose[e].p2) == rank;
+    if (!h1 && !h2) continue;
+    ids->push_back((int)e);
+    own->push_back(h1 ? 1 : 0);
+  }
+}
+
 void ra_team_loop_closures(const HostRADataset &ds, std::vector<TeamLoopClosure> *out) {
   out->clear();
   std::vector<int> lc(ds.pose_pose.size());

@@ -70,6 +70,13 @@ void ra_agent_columns(const HostRADataset &ds, int robot, int dims3[3], std::vec
 // that robot's own numbering (what Agent::updateMeasurementWeights re-weights on a RangeAidedSLAMGraph, ref
 // src/Agent.cpp:1397-1441; the RA counterpart of driver.loop_closure_mask)
 void ra_loop_closures(const HostRADataset &ds, int *mask);
+// The rank hosting agent `agent` (position in the sorted list of robots owning poses) of a job of num_agents agents:
+// consecutive agents share a rank, ceil(num_agents / world_size) each (RaRbcdSession::init)
+int ra_rank_of_agent(int agent, int num_agents, int world_size);
+// The pose-pose measurements one rank of a robust range-aided job weights: ids (pose-pose order) of those touching an
+// agent it hosts -- either pose is owned by one --, own[i] set when it hosts the owner of p1.  Every measurement has
+// exactly one owning rank; a rank past the last agent's has none.
+void ra_rank_edges(const HostRADataset &ds, int rank, int world_size, std::vector<int> *ids, std::vector<char> *own);
 // The loop closures of Graph::statistics on a RangeAidedSLAMGraph (ref src/Graph.cpp:121-134, 475-521): every measurement
 // but pose-pose odometry (ra_loop_closures' rule) -- pose-pose loop closures (id: index in pose_pose), pose-landmark
 // measurements and ranges (id -1: their weights are the file's and never change).  a1 / a2: the owner ROBOTS of the two

@@ -8,12 +8,15 @@
 // X / V / Y / XPrev in its own RA ordering [rotations | unit spheres | translations | landmarks] and the global
 // iterate is a mirror that the coupling products (G_a = X_global C_a^T) and the central evaluation read.
 //
-// Robust sessions (dcora_ra_rbcd_create_robust; single-process only) run the agents' GNC loop in place, as the reference's
+// Robust sessions (dcora_ra_rbcd_create_robust for one process, dcora_ra_rbcd_create_robust_ranks for one rank of a job,
+// whose weight changes are collective: Exchange::update_weights) run the agents' GNC loop in place, as the reference's
 // Agent does on a RangeAidedSLAMGraph just as on a pose graph: Agent::initializeRobustOptimization at creation,
 // Agent::updateMeasurementWeights / setMeasurementWeight afterwards (ref src/Agent.cpp:1332-1346, 1397-1441, 1443-1454),
 // over the graph's pose-pose loop closures only (computeMeasurementResidual, :1349-1395, refuses every other measurement
 // type; range and pose-landmark weights never change).  A weight change rebuilds the VALUES of every agent's Q_aa, of
-// its coupling block and of the central Q on the patterns recorded at creation, through the path creation takes.  What
+// its coupling block and of the central Q on the patterns recorded at creation, through the path creation takes.  A rank
+// of a job has the matrices of its hosted agents only, and those hold the measurements touching them: the weight it keeps
+// for any other measurement is the last it was told (creation, set_weights) and reaches no device matrix.  What
 // depends on the patterns stays as created: neighbours, public columns and colours (a weight of 0 on the only
 // measurement joining two agents would take them apart in a fresh session; the live session keeps its creation adjacency,
 // as the reference keeps a weight-0 measurement in its graph), the one-launch tCG eligibility, the hub rows of the
@@ -46,7 +49,8 @@ struct RaAgentDev : AgentCore {
   double reg = 0;
 };
 
-// Robust state of a session created by dcora_ra_rbcd_create_robust (RobustSession of rbcd.h, in pose-pose order)
+// Robust state of a session created by dcora_ra_rbcd_create_robust or dcora_ra_rbcd_create_robust_ranks (RobustSession of
+// rbcd.h, in pose-pose order)
 struct RaRobustSession {
   explicit RaRobustSession(const dcora_robust_params &p) : cost(p), params(p) {}
   RobustCost cost;
@@ -56,8 +60,11 @@ struct RaRobustSession {
   std::vector<char> update;     // loop closures whose weight is not fixed: what updateMeasurementWeights rewrites
   std::vector<char> meas_zero;  // weight 0 at creation: the patterns do not hold these measurements
   RobustEdges edges;            // device copy of the pose-pose measurements and of their weights
+  bool ranked = false;          // created by dcora_ra_rbcd_create_robust_ranks
+  std::vector<int> edge_ids;    // the measurements in `edges` (pose-pose order): all, or those touching a hosted agent
+  std::vector<char> owned;      // ranked, per pose-pose measurement: this rank hosts the agent of p1 (ra_rank_edges)
   DevBuf<double> X_initial;     // the last set_X, r x k global (robustOptNumResets: setXToInitialGuess)
-  std::vector<HostCsr> Qpat, Cpat;  // creation patterns (rp, ci) of every agent's Q_aa and coupling block
+  std::vector<HostCsr> Qpat, Cpat;  // creation patterns (rp, ci) of every hosted agent's Q_aa and coupling block
   HostCsr central_pat;
   HostCsr live_pat;  // the central Q's entries as the current weights give them (no explicit zeros): what certify reads
 };
@@ -74,11 +81,21 @@ class RaRbcdSession : public SessionCore {
   int init(const HostRADataset &ds, const dcora_rbcd_options &o);
   // robust sessions: weight 1 on every loop closure that is not fixed (fixed: m_pp flags or null), then init
   std::unique_ptr<RaRobustSession> robust;
-  int init_robust(const HostRADataset &ds, const dcora_rbcd_options &o, const dcora_robust_params &p, const int *fixed);
+  // ranked: a rank of a multi-rank job (world_size >= 1), its weight updates driven by the exchange
+  int init_robust(const HostRADataset &ds, const dcora_rbcd_options &o, const dcora_robust_params &p, const int *fixed,
+                  bool ranked = false);
   // updateMeasurementWeights on the current iterate; counts (may be null): accepted, rejected, undecided closures
   int update_weights(bool reset_to_initial, int counts[3]);
-  int set_weights(const double *w);  // all m_pp weights; refused (session untouched) when one is negative or not finite
-  int get_weights(double *w) const;
+  // its two halves, as RbcdSession has them: the weights of the session's edges on the device (ranked: the owned ones
+  // also into shared_w, counts over the owned ones), then the matrices rebuilt and the rest of the update
+  int compute_weights(double *shared_w, std::vector<double> *w, double counts[3]) override;
+  int apply_weights(const std::vector<double> &w, bool reset_to_initial) override;
+  // all m_pp weights; refused (session untouched) when one is negative or not finite
+  int set_weights(const double *w) override;
+  int get_weights(double *w) const;  // ranked: NaN for the measurements touching no hosted agent
+  bool weights_ranked() const override { return robust && robust->ranked; }
+  size_t weights_count() const override { return robust ? robust->ds.pose_pose.size() : 0; }
+  bool weight_owned(size_t e, double *w) const override;
   int set_X(const double *Xh) override;  // r x k global; V = Y = XPrev = X for every agent
   int get_X(double *Xh);
   // one pass of the driver's loop body with agent index `selected` (position in the sorted robot list)

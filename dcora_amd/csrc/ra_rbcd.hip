@@ -80,12 +80,11 @@ int RaRbcdSession::init(const HostRADataset &ds, const dcora_rbcd_options &o) {
   DCORA_HIP(hipMemset(Xg.p, 0, sizeof(double) * N));
   DCORA_HIP(evalbuf.alloc(R + 8));
   agents.resize(R);
-  const int per = (R + o.world_size - 1) / o.world_size;  // consecutive agents share a rank
   int idx = 0;
   for (int robot : robots) {
     RaAgentDev &a = agents[idx];
     a.robot = robot;
-    a.hosted = (idx / per) == o.rank;
+    a.hosted = ra_rank_of_agent(idx, R, o.world_size) == o.rank;  // consecutive agents share a rank
     int dims3[3];
     ra_agent_columns(ds, robot, dims3, a.own_host);
     a.n = dims3[0];
@@ -120,11 +119,14 @@ int RaRbcdSession::init(const HostRADataset &ds, const dcora_rbcd_options &o) {
 // matrices are rebuilt, ref src/Graph.cpp:1906, 1921), the central Q.
 // Creation: the device problems, buffers and tick resources are made, who neighbours whom is read off the coupling
 // blocks, and a robust session records the patterns.
-// Re-weight (single-process robust sessions; the caller has synchronised every stream): the matrices as the builders give
+// Re-weight (robust sessions; the caller has synchronised every stream): the matrices as the builders give
 // them (no explicit zeros) go to build_preconditioner, so the cache sees the keys of a fresh session -- a new image is
 // attached, an image somebody else still holds is never written --, and their values scattered onto the creation
 // patterns (a weight of 0 leaves explicit zeros) are what is uploaded.  Nothing on the device is touched before every
 // matrix has been found to fit its pattern.
+// A rank of a job (world_size > 1) has no central problem, and patterns and device matrices of its hosted agents only.
+// A hosted agent's rows of Q hold the measurements touching that agent and no other, so the weights this rank keeps for
+// the rest of the job (the last it was told) reach nothing that is uploaded.
 int RaRbcdSession::assemble(const HostRADataset &ds, bool creation) {
   const dcora_rbcd_options &o = opt;
   const HostCsr Q = build_Q_ra(ds);
@@ -144,10 +146,11 @@ int RaRbcdSession::assemble(const HostRADataset &ds, bool creation) {
     Qs.resize((size_t)R);
     Cs.resize((size_t)R);
     stage.resize((size_t)R);
-    bool ok = scatter_on_pattern(Q, robust->central_pat, &Qcs);
+    bool ok = !central || scatter_on_pattern(Q, robust->central_pat, &Qcs);
     for (int i = 0; i < R && ok; ++i)
-      ok = scatter_on_pattern(Qaa[(size_t)i], robust->Qpat[(size_t)i], &Qs[(size_t)i]) &&
-           scatter_on_pattern(C[(size_t)i], robust->Cpat[(size_t)i], &Cs[(size_t)i]);
+      ok = !agents[(size_t)i].hosted ||
+           (scatter_on_pattern(Qaa[(size_t)i], robust->Qpat[(size_t)i], &Qs[(size_t)i]) &&
+            scatter_on_pattern(C[(size_t)i], robust->Cpat[(size_t)i], &Cs[(size_t)i]));
     if (!ok) {
       set_last_error("ra_rbcd robust: the weights give a matrix entry outside the session's pattern");
       return DCORA_ERR_BAD_ARG;
@@ -186,12 +189,14 @@ int RaRbcdSession::assemble(const HostRADataset &ds, bool creation) {
     rc = acquire_tick_resources(a);
   }
   if (!creation) {
-    if (!rc) rc = central->set_values(Qcs, st, &cstage);
+    if (!rc && central) rc = central->set_values(Qcs, st, &cstage);
     const hipError_t synced = hipStreamSynchronize(st);  // (also after a failure: copies may be in flight)
     if (rc) return rc;
     DCORA_HIP(synced);
-    robust->live_pat = pattern_of(Q);  // the next certificate is a fresh session's: over the entries these weights give
-    cert_.reset();
+    if (central) {
+      robust->live_pat = pattern_of(Q);  // the next certificate is a fresh session's: over these weights' entries
+      cert_.reset();
+    }
     return DCORA_OK;
   }
   if (rc) return rc;
@@ -233,10 +238,13 @@ int RaRbcdSession::assemble(const HostRADataset &ds, bool creation) {
 // Agent::initializeRobustOptimization for every agent (ref src/Agent.cpp:1332-1346): weight 1 on every loop closure whose
 // weight is not fixed (ra_loop_closures: every pose-pose measurement but odometry).  With weights 1 the patterns are the
 // largest any later weights can give: they are kept, and a weight change only rewrites values.
+// A rank of a multi-rank job (ranked) builds the patterns of its hosted agents only and uploads the pose-pose
+// measurements touching them (ra_rank_edges), to be read from its mirror in the RA ordering of the whole problem.
 int RaRbcdSession::init_robust(const HostRADataset &ds, const dcora_rbcd_options &o, const dcora_robust_params &p,
-                               const int *fixed) {
-  if (o.world_size != 1) {
-    set_last_error("ra_rbcd robust: only single-process sessions (world_size 1) update weights");
+                               const int *fixed, bool ranked) {
+  if (o.world_size != 1 && !ranked) {
+    set_last_error("ra_rbcd robust: only single-process sessions (world_size 1) update weights here; a multi-rank job "
+                   "creates its sessions with dcora_ra_rbcd_create_robust_ranks");
     return DCORA_ERR_UNSUPPORTED;
   }
   if (p.cost_type < DCORA_ROBUST_L2 || p.cost_type > DCORA_ROBUST_GNC_TLS) {
@@ -270,7 +278,17 @@ int RaRbcdSession::init_robust(const HostRADataset &ds, const dcora_rbcd_options
   }
   int rc = init(rs.ds, o);
   if (rc) return rc;
-  rc = rs.edges.upload_ra(rs.ds, rs.update);
+  rs.ranked = ranked;
+  rs.owned.assign(m, 0);
+  if (ranked) {
+    std::vector<char> own;
+    ra_rank_edges(rs.ds, o.rank, o.world_size, &rs.edge_ids, &own);
+    for (size_t i = 0; i < rs.edge_ids.size(); ++i) rs.owned[(size_t)rs.edge_ids[i]] = own[i];
+    rc = rs.edges.upload_ra_ranked(rs.ds, rs.update, rs.edge_ids, own);
+  } else {
+    for (size_t e = 0; e < m; ++e) rs.edge_ids.push_back((int)e);
+    rc = rs.edges.upload_ra(rs.ds, rs.update);
+  }
   if (rc) return rc;
   DCORA_HIP(rs.X_initial.alloc((size_t)r * k));
   DCORA_HIP(hipMemsetAsync(rs.X_initial.p, 0, sizeof(double) * (size_t)r * k, st));
@@ -282,29 +300,50 @@ int RaRbcdSession::init_robust(const HostRADataset &ds, const dcora_rbcd_options
 // (k_robust_weights reads the mirror Xg in the RA ordering), the data matrices rebuilt, RobustCost::update, optionally X
 // back to the last set_X (robustOptNumResets), acceleration re-initialised
 int RaRbcdSession::update_weights(bool reset_to_initial, int counts[3]) {
+  std::vector<double> w;
+  double cnt[3] = {0, 0, 0};
+  int rc = compute_weights(nullptr, &w, cnt);
+  if (rc) return rc;
+  rc = apply_weights(w, reset_to_initial);
+  if (rc) return rc;
+  if (counts)
+    for (int c = 0; c < 3; ++c) counts[c] = (int)cnt[c];
+  return DCORA_OK;
+}
+
+// w: the weights of the session's edges (RaRobustSession::edge_ids order), counts as launch_robust_weights gives them
+int RaRbcdSession::compute_weights(double *shared_w, std::vector<double> *w, double counts[3]) {
   RaRobustSession &rs = *robust;
+  if (rs.ranked && !shared_w && !rs.edge_ids.empty()) {
+    set_last_error("ra_rbcd robust: a ranked session's weights are computed by its exchange "
+                   "(dcora_exchange_update_weights)");
+    return DCORA_ERR_UNSUPPORTED;
+  }
   DCORA_HIP(hipSetDevice(opt.device));
   for (const RaAgentDev &a : agents)
     if (a.own_st) DCORA_HIP(hipStreamSynchronize(a.own_st));  // the mirror is complete
-  const size_t m = rs.ds.pose_pose.size();
-  std::vector<double> w(m, 0.0);
-  double cnt[3] = {0, 0, 0};
+  const size_t m = rs.edge_ids.size();
+  w->assign(m, 0.0);
+  for (int c = 0; c < 3; ++c) counts[c] = 0;
   if (m) {
-    launch_robust_weights(st, rs.edges, r, Xg.p, rs.params, rs.cost.mu());
+    launch_robust_weights(st, rs.edges, r, Xg.p, rs.params, rs.cost.mu(), shared_w);
     DCORA_HIP(hipGetLastError());
-    DCORA_HIP(hipMemcpyAsync(w.data(), rs.edges.w.p, sizeof(double) * m, hipMemcpyDeviceToHost, st));
-    DCORA_HIP(hipMemcpyAsync(cnt, rs.edges.counts.p, sizeof(double) * 3, hipMemcpyDeviceToHost, st));
+    DCORA_HIP(hipMemcpyAsync(w->data(), rs.edges.w.p, sizeof(double) * m, hipMemcpyDeviceToHost, st));
+    DCORA_HIP(hipMemcpyAsync(counts, rs.edges.counts.p, sizeof(double) * 3, hipMemcpyDeviceToHost, st));
   }
   DCORA_HIP(hipStreamSynchronize(st));
+  return DCORA_OK;
+}
+
+int RaRbcdSession::apply_weights(const std::vector<double> &w, bool reset_to_initial) {
+  RaRobustSession &rs = *robust;
   HostRADataset next = rs.ds;
-  for (size_t e = 0; e < m; ++e) next.pose_pose[e].weight = w[e];
+  for (size_t i = 0; i < rs.edge_ids.size(); ++i) next.pose_pose[(size_t)rs.edge_ids[i]].weight = w[i];
   const int rc = adopt_weights(next, true, reset_to_initial);
   if (rc) return rc;
   rs.cost.update();
   rs.updates++;
   team_weights_updated();  // (ref src/Agent.cpp:1418-1424)
-  if (counts)
-    for (int c = 0; c < 3; ++c) counts[c] = (int)cnt[c];
   return DCORA_OK;
 }
 
@@ -314,10 +353,10 @@ int RaRbcdSession::update_weights(bool reset_to_initial, int counts[3]) {
 // initializeAcceleration, ref src/Agent.cpp:1178-1187: XPrev = V = Y = X, gamma = alpha = 0; the round counter goes on)
 int RaRbcdSession::adopt_weights(HostRADataset &ds, bool from_device, bool reset_to_initial) {
   RaRobustSession &rs = *robust;
-  const size_t m = ds.pose_pose.size();
+  const size_t m_pp = ds.pose_pose.size(), m = rs.edge_ids.size();
   int rc = DCORA_OK;
   // a pattern holds every entry of its creation weights; only a weight that was 0 then can reach outside it
-  for (size_t e = 0; e < m && !rc; ++e)
+  for (size_t e = 0; e < m_pp && !rc; ++e)
     if (rs.meas_zero[e] && ds.pose_pose[e].weight != 0.0) {
       set_last_error("ra_rbcd robust: a weight that was 0 at creation cannot become nonzero (the session's patterns "
                      "do not hold that measurement)");
@@ -332,7 +371,7 @@ int RaRbcdSession::adopt_weights(HostRADataset &ds, bool from_device, bool reset
   if (!rc) std::swap(rs.ds.pose_pose, ds.pose_pose);
   if (m && (rc || !from_device)) {
     std::vector<double> held(m);
-    for (size_t e = 0; e < m; ++e) held[e] = rs.ds.pose_pose[e].weight;
+    for (size_t i = 0; i < m; ++i) held[i] = rs.ds.pose_pose[(size_t)rs.edge_ids[i]].weight;
     DCORA_HIP(hipMemcpy(rs.edges.w.p, held.data(), sizeof(double) * m, hipMemcpyHostToDevice));
   }
   if (rc) return rc;
@@ -361,8 +400,15 @@ int RaRbcdSession::set_weights(const double *w) {
 
 int RaRbcdSession::get_weights(double *w) const {
   const RaRobustSession &rs = *robust;
-  for (size_t e = 0; e < rs.ds.pose_pose.size(); ++e) w[e] = rs.ds.pose_pose[e].weight;
+  if (rs.ranked)
+    for (size_t e = 0; e < rs.ds.pose_pose.size(); ++e) w[e] = std::nan("");
+  for (int e : rs.edge_ids) w[e] = rs.ds.pose_pose[(size_t)e].weight;
   return DCORA_OK;
+}
+
+bool RaRbcdSession::weight_owned(size_t e, double *w) const {
+  *w = robust->ds.pose_pose[e].weight;
+  return robust->owned[e] != 0;
 }
 
 int RaRbcdSession::gather_agents() {

@@ -86,9 +86,17 @@ class RbcdSession : public SessionCore {
   int update_weights(bool reset_to_initial, int counts[3]);
   // its two halves: the weights of the session's edges on the device (ranked: the owned ones also into shared_w,
   // counts over the owned ones), then the matrices rebuilt and the rest of the update
-  int compute_weights(double *shared_w, std::vector<double> *w, double counts[3]);
-  int apply_weights(const std::vector<double> &w, bool reset_to_initial);
-  int set_weights(const double *w);  // all m weights; refused (session untouched) when one is negative or not finite
+  int compute_weights(double *shared_w, std::vector<double> *w, double counts[3]) override;
+  int apply_weights(const std::vector<double> &w, bool reset_to_initial) override;
+  // all m weights; refused (session untouched) when one is negative or not finite
+  int set_weights(const double *w) override;
+  bool weights_ranked() const override { return robust && robust->ranked; }
+  size_t weights_count() const override { return robust ? robust->meas.size() : 0; }
+  bool weight_owned(size_t e, double *w) const override {
+    const PoseMeas &q = robust->meas[e];
+    *w = q.weight;
+    return agents[(size_t)P.robot_of(q.p1)].hosted;
+  }
   int get_weights(double *w) const;  // ranked: NaN for the edges touching no hosted agent
   int set_X(const double *Xh) override;
   int get_X(double *Xh);

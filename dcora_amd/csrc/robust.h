@@ -15,7 +15,7 @@ struct EdgeTable {
 struct RobustEdges : EdgeTable {
   int m = 0, d = 0;
   bool ranked = false;         // the edges of one rank of a multi-rank session (upload_ranked)
-  bool ra = false;             // X is in the RA ordering of a problem with n poses and l unit spheres (upload_ra)
+  bool ra = false;             // X is in the RA ordering of a problem with n poses and l unit spheres (upload_ra*)
   int n = 0, l = 0;
   DevBuf<int> dupd;  // dupd: the weight is rewritten by the update (a loop closure whose weight is not fixed)
   DevBuf<int> down, dgidx;     // ranked: the rank owns the edge (hosts the agent of p1); the edge's dataset index
@@ -26,6 +26,9 @@ struct RobustEdges : EdgeTable {
   // the edges ids (dataset order) of ds only; own: one flag per id
   int upload_ranked(const HostDataset &ds, const std::vector<char> &update, const std::vector<int> &ids,
                     const std::vector<char> &own);
+  // ... of ds.pose_pose, read from a mirror in the RA ordering of the whole problem (a rank of a range-aided job)
+  int upload_ra_ranked(const HostRADataset &ds, const std::vector<char> &update, const std::vector<int> &ids,
+                       const std::vector<char> &own);
 };
 // w[e] = RobustCost::weight(sqrt(error_e(X))) with RobustCost's mu for the edges flagged dupd; counts[3] = accepted,
 // rejected, undecided among them (per-block partials summed by one more launch: deterministic, no atomics).

@@ -113,9 +113,10 @@ __device__ double robust_weight(const dcora_robust_params &p, double mu, double 
 // Agent::updateMeasurementWeights on the session's iterate (ref src/Agent.cpp:1397-1413): one thread per edge, the
 // edges flagged upd (loop closures whose weight is not fixed) get RobustCost::weight(sqrt(error)); the rest keep theirs.
 // Per-block partials of {accepted (w > 1 - 1e-8), rejected (w < 1e-8), undecided} among the updated edges.
-// Ranked (a session of one rank, RobustEdges::upload_ranked): the edges are those touching a hosted agent, X is the
-// rank's mirror; the edges the rank owns also store their weight into the shared segment at their dataset index
-// (plain stores, then a system-scope fence), and only they are counted, so that the job counts every edge once.
+// Ranked (a session of one rank, RobustEdges::upload_ranked / upload_ra_ranked, in either ordering): the edges are those
+// touching a hosted agent, X is the rank's mirror; the edges the rank owns also store their weight into the shared
+// segment at their dataset index (plain stores, then a system-scope fence), and only they are counted, so that the job
+// counts every edge once.
 template <int D, bool Ranked, class Cols>
 __global__ __launch_bounds__(kBlock) void k_robust_weights(int r, int m, EdgeDev E, const int *__restrict__ upd,
                                                            const double *__restrict__ X, dcora_robust_params p,
@@ -242,31 +243,41 @@ int RobustEdges::upload_ranked(const HostDataset &ds, const std::vector<char> &u
   return rc ? rc : to_device(ids, &dgidx);
 }
 
+// ... of a range-aided job: ids index ds.pose_pose, and the poses are read from the rank's mirror, which has the RA
+// ordering of the WHOLE problem (n, l are the job's, not the rank's)
+int RobustEdges::upload_ra_ranked(const HostRADataset &ds, const std::vector<char> &update, const std::vector<int> &ids,
+                                  const std::vector<char> &own) {
+  HostDataset pp;
+  pp.d = ds.d;
+  pp.n = ds.n;
+  pp.meas = ds.pose_pose;
+  ra = true;
+  n = ds.n;
+  l = ds.l;
+  return upload_ranked(pp, update, ids, own);
+}
+
+namespace {
+using WeightsKernel = void (*)(int, int, EdgeDev, const int *, const double *, dcora_robust_params, double, double *,
+                               double *, RankedEdges);
+// the kernel of one (ordering, ranked) pair in dimension D: every combination is a form of the one template
+template <int D>
+WeightsKernel weights_kernel(bool ra, bool ranked) {
+  static const WeightsKernel forms[2][2] = {
+      {k_robust_weights<D, false, SeCols>, k_robust_weights<D, true, SeCols>},
+      {k_robust_weights<D, false, RaCols>, k_robust_weights<D, true, RaCols>}};
+  return forms[ra ? 1 : 0][ranked ? 1 : 0];
+}
+}  // namespace
+
 void launch_robust_weights(hipStream_t st, const RobustEdges &T, int r, const double *X, const dcora_robust_params &p,
                            double mu, double *shared_w) {
   if (T.m == 0) return;
   const EdgeDev E = edge_view(T, T.n, T.l);
   const int grid = (T.m + kBlock - 1) / kBlock;
   const RankedEdges rk{T.down.p, T.dgidx.p, shared_w};
-  auto go = [&](auto kernel) {
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, st, r, T.m, E, T.dupd.p, X, p, mu, T.w.p, T.partials.p, rk);
-  };
-  if (T.ra) {  // (single-process sessions only: never ranked)
-    if (T.d == 3)
-      go(k_robust_weights<3, false, RaCols>);
-    else
-      go(k_robust_weights<2, false, RaCols>);
-  } else if (T.ranked) {
-    if (T.d == 3)
-      go(k_robust_weights<3, true, SeCols>);
-    else
-      go(k_robust_weights<2, true, SeCols>);
-  } else {
-    if (T.d == 3)
-      go(k_robust_weights<3, false, SeCols>);
-    else
-      go(k_robust_weights<2, false, SeCols>);
-  }
+  const WeightsKernel kernel = T.d == 3 ? weights_kernel<3>(T.ra, T.ranked) : weights_kernel<2>(T.ra, T.ranked);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, st, r, T.m, E, T.dupd.p, X, p, mu, T.w.p, T.partials.p, rk);
   launch_sum_partials(st, T.partials.p, grid, 3, 3, T.counts.p);
 }
 

@@ -108,6 +108,19 @@ class SessionCore {
   virtual const HostCsr *central_live_pattern() const { return nullptr; }
   virtual int cert_block() const = 0;  // unknowns the factorisation orders together (d + 1 for poses)
 
+  // ---- what the exchange's collective weight update needs from a robust session of either kind (exchange.h).  The
+  // job's measurements are the re-weightable ones in the kind's order: the dataset's, or a range-aided one's pose-pose.
+  // The calls below are a robust session's (the exchange makes them on a ranked one only).
+  virtual bool weights_ranked() const = 0;  // a ranked robust session: the exchange changes its weights
+  virtual size_t weights_count() const = 0;  // measurements of the job (doubles of the weights area)
+  // the weights of the session's edges on the device from the mirror (ranked: the owned ones also into shared_w,
+  // counts over the owned ones), then the matrices rebuilt and the rest of the update
+  virtual int compute_weights(double *shared_w, std::vector<double> *w, double counts[3]) = 0;
+  virtual int apply_weights(const std::vector<double> &w, bool reset_to_initial) = 0;
+  virtual int set_weights(const double *w) = 0;  // all weights_count() of them, checked before anything changes
+  // whether this rank owns measurement e (hosts the agent of its first pose); *w: the weight the session holds for it
+  virtual bool weight_owned(size_t e, double *w) const = 0;
+
   // ---- the team protocol of a single-process session (dcora_rbcd_team_enable / dcora_ra_rbcd_team_enable): the
   // bookkeeping of Agent::iterate's status block, shouldTerminate, shouldUpdateMeasurementWeights and
   // updateMeasurementWeights (ref src/Agent.cpp:558-586, 1123-1156, 1280-1330, 1417-1424), the same on either graph type

@@ -333,6 +333,29 @@ def multi_robot_gnc_ranks(ds, X0, num_robots=5, r=5, robust=None, num_weight_upd
                      close=lambda: (ex.close(), s.close()))
 
 
+def gnc_ra_ranks(ra, X0, r, robust=None, num_weight_updates=10, inner_iters=30, rgrad_tol=0.1, max_final_iters=1000,
+                 acceleration=True, restart_interval=30, params=None, fixed=None, device=0, rank=0, world_size=1,
+                 job_name="ra_gnc"):
+    """gnc_ra_session on one rank of a multi-rank job (SPMD: every rank calls it with the same arguments but rank): the
+    ranks' robust range-aided sessions and their exchange (ra_robust_ranked_session), the inner loops through
+    Exchange.iterate, every updateMeasurementWeights collective.  The same outputs on every rank: X gathered, the
+    job's pose-pose weights.
+
+    ra keeps the final weights (set_pose_pose_weights).  Returns X, weights, per-round records."""
+    from . import ra_robust_ranked_session
+    from . import robust as rb
+    lc = ra.loop_closures()
+    if fixed is not None:
+        lc &= ~np.asarray(fixed, bool)
+    s, ex = ra_robust_ranked_session(ra, job_name, r, robust=robust or rb.RobustCostParameters("GNC_TLS"),
+                                     fixed_weight=fixed, rank=rank, world_size=world_size, device=device,
+                                     acceleration=acceleration, restart_interval=restart_interval, params=params)
+    return _gnc_loop(ra, lc, X0, num_weight_updates, inner_iters, max_final_iters, set_X=ex.set_X,
+                     run=lambda iters: exchange_run(ex, max_iters=iters, rgrad_tol=rgrad_tol),
+                     reweight=lambda u: _counts(ex.update_weights()), read=lambda: (ex.gather_X(), ex.get_weights()),
+                     close=lambda: (ex.close(), s.close()), store=ra.set_pose_pose_weights)
+
+
 def multi_robot_team_ranks(ds, X0, num_robots=5, r=5, robust=None, team=None, acceleration=True, params=None,
                            fixed=None, device=0, rank=0, world_size=1, job_name="team"):
     """multi_robot_team_session on one rank of a multi-rank job (SPMD: every rank calls it with the same arguments but

@@ -517,9 +517,10 @@ int dcora_ra_rbcd_create(dcora_radataset_t ds, const dcora_rbcd_options *opt, dc
 /* the same exchange for the agents of a multi-robot range-aided SLAM problem (ref examples/MultiRobotExample_RASLAM.cpp;
  * ownership by robot symbol, src/DCORA_utils.cpp:1370-1512): the session was created by dcora_ra_rbcd_create with
  * rank / world_size (agent i on rank i / ceil(R / world_size)); an agent's public variables are its poses, unit spheres
- * and landmarks that other agents' measurements reach.  Every dcora_exchange_* call but the weight updates of robust
- * jobs works as for pose graphs: _set_X / _rbcd_iterate / _rbcd_tick / _run_coloured / _evaluate / _gather_X / _post /
- * _wait / _all_ready / _certify (k = the merged problem's columns, Q = dcora_radataset_build_Q on rank 0). */
+ * and landmarks that other agents' measurements reach.  Every dcora_exchange_* call but the team protocol works as for
+ * pose graphs: _set_X / _rbcd_iterate / _rbcd_tick / _run_coloured / _evaluate / _gather_X / _post / _wait /
+ * _all_ready / _certify (k = the merged problem's columns, Q = dcora_radataset_build_Q on rank 0); the weight updates
+ * of a robust job on the exchange dcora_ra_rbcd_create_robust_ranks makes. */
 int dcora_exchange_create_ra(dcora_ra_rbcd_t s, const char *job_name, dcora_exchange_t *out);
 int dcora_ra_rbcd_destroy(dcora_ra_rbcd_t s);
 /* number of agents and (robots != NULL) their robot ids ('A' = 0, ...) */
@@ -611,8 +612,9 @@ int dcora_rbcd_create_robust_ranks(dcora_dataset_t ds, const dcora_rbcd_options 
  * every rank's X back to the last dcora_exchange_set_X.  A failure on one rank fails the other ranks' next collective
  * call (within DCORA_EXCHANGE_TIMEOUT_S), never a hang. */
 int dcora_exchange_update_weights(dcora_exchange_t ex, int reset_to_initial, int counts[3]);
-/* all m weights in dataset order, the same vector on every rank; checked in full on every rank before anything changes
- * (the refusals of dcora_rbcd_set_weights, DCORA_ERR_BAD_ARG everywhere, the job left as it was) */
+/* all m weights in dataset order (a range-aided job: m_pp, pose-pose order), the same vector on every rank; checked in
+ * full on every rank before anything changes (the refusals of dcora_rbcd_set_weights, DCORA_ERR_BAD_ARG everywhere, the
+ * job left as it was) */
 int dcora_exchange_set_weights(dcora_exchange_t ex, const double *w);
 /* all m current weights of the job, the same on every rank */
 int dcora_exchange_get_weights(dcora_exchange_t ex, double *w);
@@ -620,7 +622,8 @@ int dcora_exchange_get_weights(dcora_exchange_t ex, double *w);
  *     initializeRobustOptimization / updateMeasurementWeights / setMeasurementWeight (ref src/Agent.cpp:1332-1346,
  *     1397-1441, 1443-1454) on a RangeAidedSLAMGraph as on a pose graph, over the pose-pose loop closures only
  *     (computeMeasurementResidual, :1349-1395, refuses every other type): range and pose-landmark weights never change.
- *     Weights are in pose-pose order (dcora_radataset_copy).  Single-process sessions only. --- */
+ *     Weights are in pose-pose order (dcora_radataset_copy).  world_size 1 here, any world_size through
+ *     dcora_ra_rbcd_create_robust_ranks below. --- */
 /* Host only.  mask: one flag per pose-pose measurement, 1 for a loop closure, 0 for odometry -- both poses of one robot
  * (dcora_radataset_ownership) and consecutive in that robot's own numbering.  The RA counterpart of the contiguous
  * partition's rule above. */
@@ -637,7 +640,7 @@ int dcora_ra_measurement_errors(dcora_radataset_t ds, int r, const double *X, do
  * Q_aa, of its coupling block and of the central Q are those of these weights, the largest any later weights can give;
  * neighbours, public columns and colours stay those of creation whatever the weights become (a weight of 0 on the only
  * measurement joining two agents would separate them in a fresh session; the reference, too, keeps a weight-0
- * measurement in its graph).  opt->world_size > 1: DCORA_ERR_UNSUPPORTED. */
+ * measurement in its graph).  opt->world_size > 1: DCORA_ERR_UNSUPPORTED (see dcora_ra_rbcd_create_robust_ranks). */
 int dcora_ra_rbcd_create_robust(dcora_radataset_t ds, const dcora_rbcd_options *opt, const dcora_robust_params *robust,
                                 const int *fixed_weight, dcora_ra_rbcd_t *out);
 /* The contracts of dcora_rbcd_update_weights / _set_weights / _get_weights / _robust_info.  The weights come from the
@@ -649,6 +652,26 @@ int dcora_ra_rbcd_update_weights(dcora_ra_rbcd_t s, int reset_to_initial, int co
 int dcora_ra_rbcd_set_weights(dcora_ra_rbcd_t s, const double *w);
 int dcora_ra_rbcd_get_weights(dcora_ra_rbcd_t s, double *w);
 int dcora_ra_rbcd_robust_info(dcora_ra_rbcd_t s, double *mu, int *updates);
+/* Robust sessions of a multi-rank range-aided job: dcora_rbcd_create_robust_ranks' contract on a dcora_ra_rbcd session.
+ * The session of rank opt->rank of opt->world_size (world_size 1 included: that session is the one
+ * dcora_ra_rbcd_create_robust makes), together with its exchange (dcora_exchange_create_ra under job_name), whose
+ * dcora_exchange_update_weights / _set_weights / _get_weights take and give the job's m_pp weights in pose-pose order and
+ * give on W ranks exactly what the single-process session gives (weights, counts and X bit for bit).  Each rank weights
+ * the pose-pose measurements touching an agent it hosts (dcora_radataset_rank_edges) from its mirror; the rank hosting
+ * the owner of p1 publishes the weight.  A rank's matrices hold only the measurements touching its agents: for any other
+ * it keeps the last weight it was told (creation, dcora_exchange_set_weights), which reaches none of them.  On such a
+ * session dcora_ra_rbcd_update_weights and dcora_ra_rbcd_set_weights return DCORA_ERR_UNSUPPORTED (they are not
+ * collective); dcora_ra_rbcd_get_weights gives this rank's view: the weight of every pose-pose measurement touching one
+ * of its agents, NaN for all others; dcora_ra_rbcd_robust_info is unchanged.  dcora_exchange_team_enable keeps refusing
+ * the exchange.  Destroy the exchange before the session. */
+int dcora_ra_rbcd_create_robust_ranks(dcora_radataset_t ds, const dcora_rbcd_options *opt,
+                                      const dcora_robust_params *robust, const int *fixed_weight, const char *job_name,
+                                      dcora_ra_rbcd_t *session, dcora_exchange_t *ex);
+/* Host only.  The rule of dcora_ra_rbcd_create_robust_ranks for rank `rank` of world_size: one flag per pose-pose
+ * measurement each.  touches: either pose is owned by an agent the rank hosts (agent i -- position in the sorted list of
+ * robots owning poses -- on rank i / ceil(R / world_size)); owns: it hosts the owner of p1.  Every measurement is owned
+ * by exactly one rank; a rank beyond the last agent's has none. */
+int dcora_radataset_rank_edges(dcora_radataset_t ds, int rank, int world_size, int *touches, int *owns);
 
 /* --- agent status, team termination and weight-update decisions (ref src/Agent.cpp:558-586, 1123-1156, 1280-1330) --- */
 /* the fields of AgentParameters the three rules read (ref include/DCORA/Agent.h:113-125); defaults: 500 iterations,
