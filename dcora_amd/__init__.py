@@ -1255,9 +1255,17 @@ def ra_max_translation_distance(X, Y, d, n, l=0, b=0):
     return out.value
 
 
+def debug_launch_count():
+    """kernel launches of the RBCD chain's wrappers in this process so far (dcora_debug_launch_count): the counter
+    RbcdSession.debug_launches reads, for sessions and exchanges of either kind"""
+    out = C.c_longlong()
+    check(capi.lib().dcora_debug_launch_count(C.byref(out)))
+    return out.value
+
+
 def _team_fn(self, name):
-    """the team entry of a session (dcora_rbcd_<name>, dcora_ra_rbcd_<name>) or of a job's exchange
-    (dcora_exchange_<name>)"""
+    """the team entry of a session (dcora_rbcd_<name>, dcora_ra_rbcd_<name>) or of a job's exchange of either kind
+    (dcora_exchange_<name>: Exchange(session, ...), robust_ranked_session, ra_robust_ranked_session)"""
     prefix = ("dcora_exchange_" if isinstance(self, Exchange) else
               "dcora_ra_rbcd_" if isinstance(self, RaRbcdSession) else "dcora_rbcd_")
     return getattr(capi.lib(), prefix + name)
@@ -1322,6 +1330,18 @@ def _run_team(self):
 
 
 # the same records from a session of either kind and from the exchange of a multi-rank job
+def _enable_team_ra(self, params=None, **kw):
+    """Exchange.enable_team for the exchange of a range-aided job (dcora_exchange_team_enable_ra, SPMD; enable_team keeps
+    refusing such an exchange): Exchange(RaRbcdSession, ...) or the exchange of ra_robust_ranked_session.  Afterwards
+    agent_status, loop_closure_stats, should_terminate, should_update_weights, team_info and run_team are the exchange's
+    as on a pose-graph job"""
+    self.team = params if params is not None else team_params(**kw)
+    check(capi.lib().dcora_exchange_team_enable_ra(self.h, C.byref(self.team)))
+    return self.team
+
+
+Exchange.enable_team_ra = _enable_team_ra
+
 for _cls in (RbcdSession, RaRbcdSession, Exchange):
     _cls.enable_team = _enable_team
     _cls.agent_status = _agent_status

@@ -194,6 +194,7 @@ SIGNATURES = {
     "dcora_rbcd_phase_nonselected": (C.c_int, [_vp, C.c_int]),
     "dcora_rbcd_phase_selected": (C.c_int, [_vp, C.c_int]),
     "dcora_debug_rbcd_launches": (C.c_int, [_vp, C.POINTER(C.c_longlong)]),
+    "dcora_debug_launch_count": (C.c_int, [C.POINTER(C.c_longlong)]),
     "dcora_rbcd_phase_evaluate_dev": (C.c_int, [_vp, _vp]),
     "dcora_rbcd_synchronize": (C.c_int, [_vp]),
     "dcora_exchange_create": (C.c_int, [_vp, C.c_char_p, C.POINTER(_vp)]),
@@ -219,6 +220,7 @@ SIGNATURES = {
     "dcora_exchange_host_selftest": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, _PD]),
     "dcora_exchange_host_selftest_team": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _PD]),
     "dcora_exchange_team_enable": (C.c_int, [_vp, C.POINTER(TeamParams)]),
+    "dcora_exchange_team_enable_ra": (C.c_int, [_vp, C.POINTER(TeamParams)]),
     "dcora_exchange_agent_status": (C.c_int, [_vp, C.c_int, C.POINTER(AgentStatus), _PI]),
     "dcora_exchange_loop_closure_stats": (C.c_int, [_vp, C.c_int, _ip]),
     "dcora_exchange_should_terminate": (C.c_int, [_vp, _PI]),

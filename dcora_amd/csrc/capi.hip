@@ -1420,6 +1420,12 @@ int dcora_debug_rbcd_launches(dcora_rbcd_t s, long long *launches) {
     return (int)DCORA_OK;
   });
 }
+int dcora_debug_launch_count(long long *launches) {
+  return abi_call({launches}, [&] {
+    *launches = g_chain_launches.load(std::memory_order_relaxed);
+    return (int)DCORA_OK;
+  });
+}
 int dcora_rbcd_phase_evaluate_dev(dcora_rbcd_t s, double *out_dev) {
   return abi_call({s, out_dev}, [&] { return s->s.phase_evaluate_dev(out_dev); });
 }
@@ -1579,11 +1585,16 @@ int dcora_exchange_get_weights(dcora_exchange_t ex, double *w) {
 // ---- the team protocol across the ranks (Exchange::team_enable) ----
 namespace {
 int team_exchange(dcora_exchange_t ex) {
-  return ex->e.team_on() ? (int)DCORA_OK : bad("exchange team: the exchange has not called dcora_exchange_team_enable");
+  return ex->e.team_on() ? (int)DCORA_OK
+                         : bad("exchange team: the exchange has not called dcora_exchange_team_enable / "
+                               "dcora_exchange_team_enable_ra");
 }
 }  // namespace
 int dcora_exchange_team_enable(dcora_exchange_t ex, const dcora_team_params *params) {
-  return abi_call({ex, params}, [&] { return ex->e.team_enable(*params); });
+  return abi_call({ex, params}, [&] { return ex->e.team_enable(*params, false); });
+}
+int dcora_exchange_team_enable_ra(dcora_exchange_t ex, const dcora_team_params *params) {
+  return abi_call({ex, params}, [&] { return ex->e.team_enable(*params, true); });
 }
 int dcora_exchange_agent_status(dcora_exchange_t ex, int agent, dcora_agent_status *status, int *known) {
   return abi_call({ex, status}, [&] {

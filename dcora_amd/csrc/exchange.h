@@ -62,15 +62,17 @@ class Exchange {
   int set_weights(const double *w);  // all m weights, the same on every rank
   int get_weights(double *w);        // all m weights of the job, from the weights area
   int publish_weights();             // the owned edges' current weights into the area (creation)
-  // ---- the team protocol across the ranks (dcora_exchange_team_enable; pose-graph sessions) ----
+  // ---- the team protocol across the ranks (dcora_exchange_team_enable on a pose-graph job, dcora_exchange_team_enable_ra
+  // on a range-aided one; everything after the enabling call is the same for both kinds) ----
   // Every rank keeps every agent's status (TeamState, ranked).  Of an optimisation only two facts are not known
   // everywhere: whether it succeeded and its relative change.  The hosting rank stores the first from the host, the
   // ranked k_rel_change behind the agent's update stores the second and then the slot's sequence word; every rank
   // (the hosting one too) collects them inside the collective call and settles the status by the same rule.
   // (Slot re-use and the back-pressure on the read words: exchange_slots.h, at the steps.)
-  int team_enable(const dcora_team_params &p);
-  bool team_on() const { return pose_ && pose_->team && pose_->team->ranked; }
-  RbcdSession *team_session() const { return team_on() ? pose_ : nullptr; }
+  // range_aided: which of the two entries calls; each serves its own session kind and refuses the other's exchange
+  int team_enable(const dcora_team_params &p, bool range_aided);
+  bool team_on() const { return s_ && s_->team && s_->team->ranked; }
+  SessionCore *team_session() const { return team_on() ? s_ : nullptr; }
   int run_team(int *iters_done, double *cost2_trace, double *gradnorm_trace, int *selected_trace, int *updated_trace,
                int *weight_updates, int *stop_reason);
   // the same slots and waits without a device (host stores stand in for the kernel's): rounds of one agent (round % R)
@@ -109,7 +111,7 @@ class Exchange {
   bool registered_ = false;
   ShmHeader *hdr_ = nullptr;
   uint64_t red_seq_ = 0;
-  RbcdSession *pose_ = nullptr;      // the session when it is a pose-graph one (the team protocol serves those)
+  RbcdSession *pose_ = nullptr;      // the session when it is a pose-graph one (its chain_launches counter)
   std::vector<double> job_w_;        // the job's weights as of the last weight change (the team's loop-closure counts)
   std::vector<int> team_due_;        // agents whose status the evaluation of this rbcd_iterate has to collect
   int team_clear_to_write(const int *agents, int count);  // before the agents optimise: their slots may be overwritten

@@ -229,7 +229,7 @@ Exchange::~Exchange() {
   if (s_) (void)hipSetDevice(s_->opt.device);
   if (team_on()) {  // the team's status area and weights go with the segment: the session goes on without a team
     (void)hipStreamSynchronize(s_->st);
-    pose_->team.reset();
+    s_->team.reset();
   }
   for (int q = 0; q < kMaxRanks; ++q)
     if (opened_[q] && peer_halo_[q]) (void)hipIpcCloseMemHandle(peer_halo_[q]);
@@ -827,7 +827,7 @@ int Exchange::rbcd_iterate(int selected, double *cost2, double *gradnorm, double
   if (team && (rc = team_clear_to_write(&selected, 1))) return rc;
   rc = s_->phase_selected(selected);  // Agent::iterate(true) where the selected agent lives
   if (rc) return rc;
-  if (team) pose_->team_note_elsewhere(&selected, 1);
+  if (team) s_->team_note_elsewhere(&selected, 1);
   rc = post(&selected, 1);
   if (rc) return rc;
   rc = wait(&selected, 1);
@@ -851,7 +851,7 @@ int Exchange::rbcd_tick(const int *set, int count, int allow_adjacent) {
   if (team && valid && (rc = team_clear_to_write(set, count))) return rc;
   rc = s_->iterate_set(set, count, allow_adjacent);
   if (rc) return rc;
-  if (team) pose_->team_note_elsewhere(set, count);
+  if (team) s_->team_note_elsewhere(set, count);
   rc = post(set, count);
   if (rc) return rc;
   rc = wait(set, count);
@@ -869,15 +869,18 @@ void Exchange::team_snapshot_weights() {
 
 // The job's weights are complete in the area whenever no update is under way; the closing barrier keeps a rank that
 // runs ahead from starting one (its kernel stores into the area) while another still copies.
-int Exchange::team_enable(const dcora_team_params &p) {
-  if (!pose_)
-    return usage("team_enable: the team protocol serves pose-graph sessions; a range-aided job has none",
-                 DCORA_ERR_UNSUPPORTED);
-  if (pose_->robust && lay_.w_doubles != pose_->robust->meas.size())
-    return usage("team_enable: a robust session needs the exchange it was created with (dcora_rbcd_create_robust_ranks)",
-                 DCORA_ERR_UNSUPPORTED);
+int Exchange::team_enable(const dcora_team_params &p, bool range_aided) {
+  if (!pose_ && !range_aided)
+    return usage("team_enable: dcora_exchange_team_enable serves pose-graph sessions; a range-aided job enables its team "
+                 "through dcora_exchange_team_enable_ra", DCORA_ERR_UNSUPPORTED);
+  if (pose_ && range_aided)
+    return usage("team_enable: dcora_exchange_team_enable_ra serves range-aided sessions; a pose-graph job enables its "
+                 "team through dcora_exchange_team_enable", DCORA_ERR_UNSUPPORTED);
+  if (s_->weights_ranked() && lay_.w_doubles != s_->weights_count())
+    return usage("team_enable: a robust session needs the exchange it was created with (dcora_rbcd_create_robust_ranks / "
+                 "dcora_ra_rbcd_create_robust_ranks)", DCORA_ERR_UNSUPPORTED);
   team_snapshot_weights();
-  const int rc = pose_->team_enable_ranked(p, lay_.status(map_, 0, 0), lay_.status(dev_map_, 0, 0),
+  const int rc = s_->team_enable_ranked(p, lay_.status(map_, 0, 0), lay_.status(dev_map_, 0, 0),
                                            lay_.w_doubles ? job_w_.data() : nullptr);
   if (rc) return rc;
   return barrier();
@@ -885,7 +888,7 @@ int Exchange::team_enable(const dcora_team_params &p) {
 
 // optimisation q = seq + 1 of a hosted agent will store into slot [q & 1]: every rank has read q - 2 out of it
 int Exchange::team_clear_to_write(const int *agents, int count) {
-  const TeamState &t = *pose_->team;
+  const TeamState &t = *s_->team;
   const ExchangeSlots sl = slots();
   for (int i = 0; i < count; ++i) {
     const int a = agents[i];
@@ -901,7 +904,7 @@ int Exchange::team_clear_to_write(const int *agents, int count) {
 }
 
 int Exchange::team_collect(const int *agents, int count) {
-  const TeamState &t = *pose_->team;
+  const TeamState &t = *s_->team;
   const ExchangeSlots sl = slots();
   for (int i = 0; i < count; ++i) {
     const int a = agents[i];
@@ -909,7 +912,7 @@ int Exchange::team_collect(const int *agents, int count) {
     if (const int rc = sl.status_wait(q, a))
       return wait_failed(rc, "the status of agent " + std::to_string(a) + " never arrived");
     const ShmStatus *slot = sl.status_slot(q, a);
-    pose_->team_settle_published(a, slot->success != 0, slot->rel);
+    s_->team_settle_published(a, slot->success != 0, slot->rel);
     sl.mark_status_read(q, a);
   }
   return DCORA_OK;
@@ -918,7 +921,7 @@ int Exchange::team_collect(const int *agents, int count) {
 // SessionCore::run_team across the ranks: the same loop of the same rules on every rank's copy of the statuses
 int Exchange::run_team(int *iters_done, double *cost2_trace, double *gradnorm_trace, int *selected_trace,
                        int *updated_trace, int *weight_updates, int *stop_reason) {
-  RbcdSession &s = *pose_;
+  SessionCore &s = *s_;
   TeamState &t = *s.team;
   const int cap = t.params.max_num_iters;
   int selected = 0, it = 0, nupd = 0;

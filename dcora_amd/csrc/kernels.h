@@ -373,6 +373,9 @@ struct RaRelChangeSet {
   const double *X[kMaxAgents], *XPrev[kMaxAgents];
 };
 void launch_rel_change_ra(hipStream_t st, int r, const RaRelChangeSet &set, double *out);
+// Its ranked form (a rank of a range-aided job): entry i publishes optimisation pub.seq[i] of agent[i] into its status
+// slot as launch_rel_change_ranked does; the reduction is the one above, the same bits.
+void launch_rel_change_ra_ranked(hipStream_t st, int r, const RaRelChangeSet &set, const RelChangePublish &pub);
 int max_translation_distance(int r, int d, int n, const double *X, const double *Y, double *out);
 int ra_max_translation_distance(int r, int d, int n, int l, int b, const double *X, const double *Y, double *out);
 int launch_g_retract(hipStream_t st, const ManiDesc &m, Buf2 X, const double *V, double alpha, Buf2 out, int selOut,

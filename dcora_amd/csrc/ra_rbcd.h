@@ -22,11 +22,14 @@
 // as the reference keeps a weight-0 measurement in its graph), the one-launch tCG eligibility, the hub rows of the
 // Q-apply and the sparse / dense choice of the preconditioner.
 //
-// The team protocol (dcora_ra_rbcd_team_enable; single-process only) is the session core's: the reference's agents run
-// the status block of Agent::iterate, shouldTerminate and shouldUpdateMeasurementWeights on either graph type (ref
-// src/Agent.cpp:558-586, 1123-1156, 1280-1330).  What is this kind's own: the relative change is taken over the agent's
-// poses in ITS ordering (k_rel_change's RA form), and its loop closures are every measurement but pose-pose odometry --
-// pose-pose closures, pose-landmark measurements, ranges (ref src/Graph.cpp:121-134, 475-521).
+// The team protocol (dcora_ra_rbcd_team_enable in one process, dcora_exchange_team_enable_ra on the ranks of a job) is
+// the session core's: the reference's agents run the status block of Agent::iterate, shouldTerminate and
+// shouldUpdateMeasurementWeights on either graph type (ref src/Agent.cpp:558-586, 1123-1156, 1280-1330).  What is this
+// kind's own: the relative change is taken over the agent's poses in ITS ordering (k_rel_change's RA form), and its loop closures are every measurement but pose-pose odometry --
+// pose-pose closures, pose-landmark measurements, ranges (ref src/Graph.cpp:121-134, 475-521).  On a rank of a job the
+// relative change goes into the agent's status slot (the ranked RA form) and a pose-pose closure's weight is the job's.
+// This kind has no per-agent entry that optimises an agent outside the exchange (RbcdSession::agent_iterate has no
+// namesake here; iterate refuses a rank), so nothing else has to refuse on a ranked team.
 #pragma once
 #include <memory>
 #include <string>
@@ -114,7 +117,7 @@ class RaRbcdSession : public SessionCore {
   const HostCsr *central_live_pattern() const override { return robust ? &robust->live_pat : nullptr; }
   int cert_block() const override { return 1; }
   int x_stage_hosted(double *host_area) override;
-  // the team protocol (session_core.h; dcora_ra_rbcd_team_enable): an L2 team on a plain session
+  // the team protocol (session_core.h): an L2 team on a plain session
   bool team_robust() const override { return robust && robust->params.cost_type != DCORA_ROBUST_L2; }
   int team_weight_updates() const override { return robust ? robust->updates : 0; }
 
@@ -133,9 +136,8 @@ class RaRbcdSession : public SessionCore {
   // the session kind's part of the team protocol: k_rel_change's RA form over the agents' own X / XPrev; the loop
   // closures are ra_team_loop_closures' with agents for robots, a pose-pose one's current weight the robust state's
   int team_launch_rel_change(const std::vector<int> &ids) override;
-  double team_lc_weight(const TeamLoopClosure &q) const override {
-    return q.id >= 0 && robust ? robust->ds.pose_pose[(size_t)q.id].weight : q.w0;
-  }
+  // (a rank of a job: the job's weights the exchange keeps, never the rank's own partial ones)
+  double team_lc_weight(const TeamLoopClosure &q) const override;
   int team_update_weights(bool reset_to_initial) override { return update_weights(reset_to_initial, nullptr); }
   int team_iterate(int selected, double *cost2, double *gradnorm, int *next_selected) override {
     return iterate(selected, cost2, gradnorm, nullptr, next_selected);

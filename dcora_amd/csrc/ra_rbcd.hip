@@ -629,9 +629,19 @@ int RaRbcdSession::team_launch_rel_change(const std::vector<int> &ids) {
     set.toff[set.count] = d * a.n + a.l;
     set.count++;
   }
-  launch_rel_change_ra(st, r, set, team->rel_dev);
+  if (team->ranked)  // a rank of a job: into the agents' status slots of the segment, as the pose-graph kind does
+    launch_rel_change_ra_ranked(st, r, set, team_publish_slots(ids));
+  else
+    launch_rel_change_ra(st, r, set, team->rel_dev);
   DCORA_HIP(hipGetLastError());
   return DCORA_OK;
+}
+
+// A rank keeps current weights only of the measurements touching its hosted agents: on a team of a job the counts of
+// all R agents come from the exchange's copy of the job's weights, which is in pose-pose order like q.id.
+double RaRbcdSession::team_lc_weight(const TeamLoopClosure &q) const {
+  if (q.id < 0) return q.w0;  // pose-landmark measurements and ranges: never re-weighted
+  return team->job_w ? team->job_w[(size_t)q.id] : robust ? robust->ds.pose_pose[(size_t)q.id].weight : q.w0;
 }
 
 int RaRbcdSession::x_stage_hosted(double *host_area) {

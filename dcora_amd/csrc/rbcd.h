@@ -115,13 +115,7 @@ class RbcdSession : public SessionCore {
   int agent_update_neighbor(int agent, int neighbor, int count, const int *frames, const double *poses, bool aux);
   std::vector<int> agent_it;  // Agent::iteration_number() of every agent
   int agent_iteration_number(int agent) const;
-  // ---- the team protocol (session_core.h); what stays here is the half of a rank of a job, through its exchange only:
-  // the status area and the job's weights the exchange keeps
-  int team_enable_ranked(const dcora_team_params &p, ShmStatus *slots, ShmStatus *slots_dev, const double *job_w);
-  // ranked: the bookkeeping of team_note_optimized for those agents of ids that live on another rank, and the two facts
-  // the hosting rank published for one agent settled into its status
-  void team_note_elsewhere(const int *ids, int count);
-  void team_settle_published(int agent, bool success, double relative_change);
+  // ---- the team protocol (session_core.h), one process or a rank of a job alike
   bool team_robust() const override { return robust && robust->params.cost_type != DCORA_ROBUST_L2; }
   int team_weight_updates() const override { return robust ? robust->updates : 0; }
   long chain_launches = 0;  // kernel launches of the chain's wrappers enqueued by iterate() (debug counter)

@@ -1091,49 +1091,15 @@ int RbcdSession::agent_iteration_number(int agent) const {
   return iteration;
 }
 
-int RbcdSession::team_enable_ranked(const dcora_team_params &p, ShmStatus *slots, ShmStatus *slots_dev,
-                                    const double *job_w) {
-  if (team && !team->ranked) {
-    set_last_error("rbcd team: the session's team was enabled by dcora_rbcd_team_enable");
-    return DCORA_ERR_UNSUPPORTED;
-  }
-  if (!team) {
-    team.reset(new TeamState);
-    team->ranked = true;
-    team->slots = slots;
-    team->slots_dev = slots_dev;
-    team->seq.assign((size_t)R, 0);
-    team_clear_statuses();
-    team->latest_weight_update_iteration = 0;
-  }
-  team->job_w = job_w;
-  team_refresh_counts();
-  team->params = p;
-  return DCORA_OK;
-}
-
 // the session's relative-change launch for agents just marked: one launch behind everything their updates enqueued on
 // the session's stream, compares the X the round leaves with the XPrev it saved.  Ranked: into the agents' status slots
 int RbcdSession::team_launch_rel_change(const std::vector<int> &ids) {
   RelChangeSet set{};
-  RelChangePublish pub{};
-  for (int b : ids) {
-    if (team->ranked) {
-      // the slot was released by Exchange::team_clear_to_write before the agent's update was enqueued
-      const uint64_t q = team->seq[(size_t)b];
-      team->slots[(size_t)(q & 1) * R + b].success = team->pending[(size_t)b].success ? 1u : 0u;
-      pub.seq[set.count] = q;
-    }
-    set.agent[set.count++] = b;
-  }
-  if (team->ranked) {
-    std::atomic_thread_fence(std::memory_order_release);
-    pub.slots = team->slots_dev;
-    pub.R = R;
-    launch_rel_change_ranked(st, r, d, Xg.p, XPrevg.p, pose_start.p, set, pub);
-  } else {
+  for (int b : ids) set.agent[set.count++] = b;
+  if (team->ranked)
+    launch_rel_change_ranked(st, r, d, Xg.p, XPrevg.p, pose_start.p, set, team_publish_slots(ids));
+  else
     launch_rel_change(st, r, d, Xg.p, XPrevg.p, pose_start.p, set, team->rel_dev);
-  }
   DCORA_HIP(hipGetLastError());
   return DCORA_OK;
 }
@@ -1141,24 +1107,6 @@ int RbcdSession::team_launch_rel_change(const std::vector<int> &ids) {
 // (a rank keeps only the weights of the edges touching its agents up to date: the job's come from its exchange)
 double RbcdSession::team_lc_weight(const TeamLoopClosure &q) const {
   return team->job_w ? team->job_w[(size_t)q.id] : robust ? robust->meas[(size_t)q.id].weight : q.w0;
-}
-
-void RbcdSession::team_note_elsewhere(const int *ids, int count) {
-  for (int i = 0; i < count; ++i) {
-    const int b = ids[i];
-    if (b >= 0 && b < R && !agents[(size_t)b].hosted) team_mark_optimized(b, false);  // (success arrives with the slot)
-  }
-}
-
-void RbcdSession::team_settle_published(int b, bool success, double relative_change) {
-  TeamState::Pending &p = team->pending[(size_t)b];
-  if (!p.on) return;
-  p.on = false;
-  p.success = success;
-  dcora_agent_status &s = team->status[(size_t)b];
-  s.relative_change = relative_change;
-  s.ready_to_terminate = team_ready_to_terminate(team->params, team_robust(), p.updates, p.success, s.relative_change,
-                                                 p.lc[0], p.lc[1], p.lc[2]) ? 1 : 0;
 }
 
 }  // namespace dcora

@@ -27,10 +27,10 @@ struct AgentCore {
   hipEvent_t done = nullptr;            // both owned by the session)
 };
 
-// Team protocol of a session that called dcora_rbcd_team_enable / dcora_ra_rbcd_team_enable: every agent's status as
-// Agent::iterate(true) stores it (ref src/Agent.cpp:558-586) and the bookkeeping Agent::updateMeasurementWeights does on
-// it (:1417-1424).  The relative change comes from k_rel_change, in the session kind's form of it, through host-mapped
-// memory: a status is `pending` from its launch until the host has seen the stream pass it (an evaluation the host has
+// Team protocol of a session that called dcora_rbcd_team_enable / dcora_ra_rbcd_team_enable, or whose exchange called
+// dcora_exchange_team_enable / _team_enable_ra (ranked, below): every agent's status as Agent::iterate(true) stores it
+// (ref src/Agent.cpp:558-586) and the bookkeeping Agent::updateMeasurementWeights does on it (:1417-1424).  The relative
+// change comes from k_rel_change, in the session kind's form of it, through host-mapped memory: a status is `pending` from its launch until the host has seen the stream pass it (an evaluation the host has
 // waited for, or a synchronisation in the query), then it is settled by team_ready_to_terminate with what the agent
 // knew when it optimised.
 struct TeamState {
@@ -131,6 +131,13 @@ class SessionCore {
   virtual bool team_robust() const = 0;         // cost type != L2
   virtual int team_weight_updates() const = 0;  // mWeightUpdateCount
   int team_inner_iter() const { return team_robust() ? inner_rounds : 0; }
+  // ---- the half of a rank of a job, of either kind, through its exchange only (Exchange::team_enable): the status area
+  // and the job's weights the exchange keeps
+  int team_enable_ranked(const dcora_team_params &p, ShmStatus *slots, ShmStatus *slots_dev, const double *job_w);
+  // ranked: the bookkeeping of team_note_optimized for those agents of ids that live on another rank, and the two facts
+  // the hosting rank published for one agent settled into its status
+  void team_note_elsewhere(const int *ids, int count);
+  void team_settle_published(int agent, bool success, double relative_change);
   // the agents' own loop: stop and re-weight by the team rules instead of a central gradient norm and fixed counts
   int run_team(int *iters_done, double *cost2_trace, double *gradnorm_trace, int *selected_trace, int *updated_trace,
                int *weight_updates, int *stop_reason);
@@ -176,6 +183,7 @@ class SessionCore {
   void team_clear_statuses();
   void team_weights_updated();
   void team_restart_rounds();
+  RelChangePublish team_publish_slots(const std::vector<int> &ids);  // ranked: what team_launch_rel_change publishes
   std::vector<TeamLoopClosure> team_lcs_;  // the session's loop closures, filled at creation
   // what a session kind supplies to the team protocol:
   // its relative-change kernel for these hosted agents, just marked, enqueued on the session's stream

@@ -176,11 +176,12 @@ int SessionCore::team_enable(const dcora_team_params &p) {
   const std::string tag = std::string(tag_) + " team: ";
   if (opt.world_size != 1) {
     set_last_error(tag + "only single-process sessions (world_size 1) keep the team's statuses by themselves; "
-                   "the ranks of a pose-graph job enable the team through their exchange (dcora_exchange_team_enable)");
+                   "the ranks of a job, pose-graph or range-aided, enable the team through their exchange "
+                   "(dcora_exchange_team_enable, on a range-aided job dcora_exchange_team_enable_ra)");
     return DCORA_ERR_UNSUPPORTED;
   }
   if (team && team->ranked) {
-    set_last_error(tag + "the session's team was enabled through its exchange (dcora_exchange_team_enable)");
+    set_last_error(tag + "the session's team was enabled through its exchange (dcora_exchange_team_enable / _ra)");
     return DCORA_ERR_UNSUPPORTED;
   }
   if (!team) {
@@ -194,6 +195,28 @@ int SessionCore::team_enable(const dcora_team_params &p) {
     team->latest_weight_update_iteration = 0;
     team_refresh_counts();
   }
+  team->params = p;
+  return DCORA_OK;
+}
+
+// The half of a rank of a job, through its exchange only: the status area and the job's weights the exchange keeps.
+int SessionCore::team_enable_ranked(const dcora_team_params &p, ShmStatus *slots, ShmStatus *slots_dev,
+                                    const double *job_w) {
+  if (team && !team->ranked) {
+    set_last_error(std::string(tag_) + " team: the session's team was enabled by dcora_" + tag_ + "_team_enable");
+    return DCORA_ERR_UNSUPPORTED;
+  }
+  if (!team) {
+    team.reset(new TeamState);
+    team->ranked = true;
+    team->slots = slots;
+    team->slots_dev = slots_dev;
+    team->seq.assign((size_t)R, 0);
+    team_clear_statuses();
+    team->latest_weight_update_iteration = 0;
+  }
+  team->job_w = job_w;
+  team_refresh_counts();
   team->params = p;
   return DCORA_OK;
 }
@@ -257,6 +280,43 @@ void SessionCore::team_mark_optimized(int b, bool success) {
   p.updates = team_weight_updates();
   for (int c = 0; c < 3; ++c) p.lc[c] = team->lc[(size_t)b * 3 + c];
   if (team->ranked) team->seq[(size_t)b]++;
+}
+
+// ranked: what team_note_optimized keeps for those agents of ids that live on another rank
+void SessionCore::team_note_elsewhere(const int *ids, int count) {
+  for (int i = 0; i < count; ++i) {
+    const int b = ids[i];
+    if (b >= 0 && b < R && !agent_core(b).hosted) team_mark_optimized(b, false);  // (success arrives with the slot)
+  }
+}
+
+// ranked, for hosted agents just marked: `success` into the slot their optimisation publishes into (released by
+// Exchange::team_clear_to_write before the agent's update was enqueued), visible before the kernel's stores; the
+// ranked k_rel_change's argument
+RelChangePublish SessionCore::team_publish_slots(const std::vector<int> &ids) {
+  RelChangePublish pub{};
+  int i = 0;
+  for (int b : ids) {
+    const uint64_t q = team->seq[(size_t)b];
+    team->slots[(size_t)(q & 1) * R + b].success = team->pending[(size_t)b].success ? 1u : 0u;
+    pub.seq[i++] = q;
+  }
+  std::atomic_thread_fence(std::memory_order_release);
+  pub.slots = team->slots_dev;
+  pub.R = R;
+  return pub;
+}
+
+// ranked: the two facts the hosting rank published for one agent settled into its status
+void SessionCore::team_settle_published(int b, bool success, double relative_change) {
+  TeamState::Pending &p = team->pending[(size_t)b];
+  if (!p.on) return;
+  p.on = false;
+  p.success = success;
+  dcora_agent_status &s = team->status[(size_t)b];
+  s.relative_change = relative_change;
+  s.ready_to_terminate = team_ready_to_terminate(team->params, team_robust(), p.updates, p.success, s.relative_change,
+                                                 p.lc[0], p.lc[1], p.lc[2]) ? 1 : 0;
 }
 
 int SessionCore::team_settle(bool visible) {

@@ -89,27 +89,36 @@ __global__ __launch_bounds__(kBlock) void k_rel_change(int r, Poses where, doubl
   }
 }
 
+namespace {
+// Every (ranked, layout) form of the kernel is launched from here: Pub names the ranked half (RelChangePublish: into the
+// status slots; RelNoPublish: into `out`), Poses the layout.  The one-process forms count a launch for an empty set too,
+// the ranked ones only a launch that is made (a rank that hosts none of the agents enqueues nothing).
+template <class Poses, class Pub>
+void launch_rel_change_form(hipStream_t st, int r, const Poses &where, double *out, const Pub &pub) {
+  constexpr bool ranked = std::is_same_v<Pub, RelChangePublish>;
+  if (!ranked) count_launch();
+  if (where.set.count < 1) return;
+  if (ranked) count_launch();
+  hipLaunchKernelGGL((k_rel_change<ranked, Poses>), dim3(where.set.count), dim3(kBlock), 0, st, r, where, out, pub);
+}
+}  // namespace
+
 void launch_rel_change(hipStream_t st, int r, int d, const double *X, const double *XPrev, const int *pose_start,
                        const RelChangeSet &set, double *out) {
-  count_launch();
-  if (set.count < 1) return;
-  hipLaunchKernelGGL((k_rel_change<false, SePoses>), dim3(set.count), dim3(kBlock), 0, st, r,
-                     SePoses{d + 1, X, XPrev, pose_start, set}, out, RelNoPublish{});
+  launch_rel_change_form(st, r, SePoses{d + 1, X, XPrev, pose_start, set}, out, RelNoPublish{});
 }
 
 void launch_rel_change_ranked(hipStream_t st, int r, int d, const double *X, const double *XPrev, const int *pose_start,
                               const RelChangeSet &set, const RelChangePublish &pub) {
-  if (set.count < 1) return;
-  count_launch();
-  hipLaunchKernelGGL((k_rel_change<true, SePoses>), dim3(set.count), dim3(kBlock), 0, st, r,
-                     SePoses{d + 1, X, XPrev, pose_start, set}, (double *)nullptr, pub);
+  launch_rel_change_form(st, r, SePoses{d + 1, X, XPrev, pose_start, set}, (double *)nullptr, pub);
 }
 
 void launch_rel_change_ra(hipStream_t st, int r, const RaRelChangeSet &set, double *out) {
-  count_launch();
-  if (set.count < 1) return;
-  hipLaunchKernelGGL((k_rel_change<false, RaPoses>), dim3(set.count), dim3(kBlock), 0, st, r, RaPoses{set}, out,
-                     RelNoPublish{});
+  launch_rel_change_form(st, r, RaPoses{set}, out, RelNoPublish{});
+}
+
+void launch_rel_change_ra_ranked(hipStream_t st, int r, const RaRelChangeSet &set, const RelChangePublish &pub) {
+  launch_rel_change_form(st, r, RaPoses{set}, (double *)nullptr, pub);
 }
 
 namespace {

@@ -388,6 +388,41 @@ def multi_robot_team_ranks(ds, X0, num_robots=5, r=5, robust=None, team=None, ac
                       "weight_updates": int(out["weight_updates"]), "stop_reason": out["stop_reason"]}}
 
 
+def ra_team_ranks(ra, X0, r, robust=None, team=None, acceleration=True, restart_interval=30, params=None, fixed=None,
+                  device=0, rank=0, world_size=1, job_name="ra_team"):
+    """ra_team_session on one rank of a multi-rank job (SPMD: every rank calls it with the same arguments but rank): the
+    ranks' robust range-aided sessions and their exchange (ra_robust_ranked_session), the team enabled through the
+    exchange so that every rank holds every agent's status, Exchange.run_team re-weighting and stopping by the agents'
+    rules.  The same outputs on every rank: X gathered, the job's pose-pose weights, the statuses.
+
+    ra keeps the final weights (set_pose_pose_weights).  Returns the record of multi_robot_team_ranks."""
+    from . import ra_robust_ranked_session, team_params
+    from . import robust as rb
+    lc = ra.loop_closures()
+    if fixed is not None:
+        lc &= ~np.asarray(fixed, bool)
+    s, ex = ra_robust_ranked_session(ra, job_name, r, robust=robust or rb.RobustCostParameters("GNC_TLS"),
+                                     fixed_weight=fixed, rank=rank, world_size=world_size, device=device,
+                                     acceleration=acceleration, restart_interval=restart_interval, params=params)
+    try:
+        ex.enable_team_ra(team if team is not None else team_params())
+        ex.set_X(np.asarray(X0, dtype=np.float64))
+        out = ex.run_team()
+        X, w = ex.gather_X(), ex.get_weights()
+        statuses = [ex.agent_status(q) for q in range(s.R)]
+        stats = [ex.loop_closure_stats(q) for q in range(s.R)]
+        ex.barrier()
+    finally:
+        ex.close()
+        s.close()
+    ra.set_pose_pose_weights(w)
+    return {"X": X, "weights": w.copy(), "loop_closures": lc, "run": out,
+            "statuses": statuses, "loop_closure_stats": stats,
+            "final": {"iterations": int(out["iters"]), "cost_2f": float(out["cost"][-1]) if out["iters"] else None,
+                      "gradnorm": float(out["gradnorm"][-1]) if out["iters"] else None,
+                      "weight_updates": int(out["weight_updates"]), "stop_reason": out["stop_reason"]}}
+
+
 def multi_robot_raslam_example(ra, X0, r_min=None, r_max=100, max_iters=1000, rgrad_tol=0.1, min_eig_tol=1e-3,
                                gradient_tolerance=1e-4, preconditioned_gradient_tolerance=1e-4, acceleration=True,
                                params=None, device=0, mode="rbcd++"):

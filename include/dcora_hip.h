@@ -381,6 +381,8 @@ int dcora_rbcd_phase_selected(dcora_rbcd_t s, int selected);
  * bookkeeping and tCG kernels, the evaluation epilogue -- that this session's dcora_rbcd_iterate calls have enqueued
  * since creation.  Meaningful while one session iterates at a time. */
 int dcora_debug_rbcd_launches(dcora_rbcd_t s, long long *launches);
+/* the same counter of the whole process (every session and exchange of either kind, since the library was loaded) */
+int dcora_debug_launch_count(long long *launches);
 /* local part of the evaluation: for every hosted agent b, |Proj(X_b Q_bb + G_b)|^2 and <X_b, X_b Q_bb + G_b>
  * written to out_dev[2*b], out_dev[2*b+1] (device, 2*num_robots doubles, entries of non-hosted agents zero) */
 int dcora_rbcd_phase_evaluate_dev(dcora_rbcd_t s, double *out_dev);
@@ -662,8 +664,8 @@ int dcora_ra_rbcd_robust_info(dcora_ra_rbcd_t s, double *mu, int *updates);
  * it keeps the last weight it was told (creation, dcora_exchange_set_weights), which reaches none of them.  On such a
  * session dcora_ra_rbcd_update_weights and dcora_ra_rbcd_set_weights return DCORA_ERR_UNSUPPORTED (they are not
  * collective); dcora_ra_rbcd_get_weights gives this rank's view: the weight of every pose-pose measurement touching one
- * of its agents, NaN for all others; dcora_ra_rbcd_robust_info is unchanged.  dcora_exchange_team_enable keeps refusing
- * the exchange.  Destroy the exchange before the session. */
+ * of its agents, NaN for all others; dcora_ra_rbcd_robust_info is unchanged.  dcora_exchange_team_enable_ra serves the
+ * exchange (below).  Destroy the exchange before the session. */
 int dcora_ra_rbcd_create_robust_ranks(dcora_radataset_t ds, const dcora_rbcd_options *opt,
                                       const dcora_robust_params *robust, const int *fixed_weight, const char *job_name,
                                       dcora_ra_rbcd_t *session, dcora_exchange_t *ex);
@@ -783,14 +785,23 @@ int dcora_ra_rbcd_team_info(dcora_ra_rbcd_t s, int info[4]);
 int dcora_ra_rbcd_run_team(dcora_ra_rbcd_t s, int *iters_done, double *cost2_trace, double *gradnorm_trace,
                            int *selected_trace, int *updated_trace, int *weight_updates, int *stop_reason);
 /* ---- the team protocol across the ranks of a job ----
- * The entries above on a multi-rank pose-graph job, through its exchange: semantics are their dcora_rbcd_* namesakes',
- * every rank holds every agent's status, and the outputs are identical on every rank.  Of an optimisation only its
+ * The entries above on a multi-rank job of either kind, through its exchange: semantics are their dcora_rbcd_* /
+ * dcora_ra_rbcd_* namesakes', every rank holds every agent's status, and the outputs are identical on every rank.  Of an optimisation only its
  * success and its relative change are known to the hosting rank alone: they travel through a status slot of the job's
  * segment (the relative change stored by the kernel that computes it), every rank settles the status by
  * dcora_team_ready_to_terminate.
  * dcora_exchange_team_enable (SPMD): on the exchange of any pose-graph session -- dcora_exchange_create (an L2 team, its
  * loop-closure counts from the creation weights) or dcora_rbcd_create_robust_ranks, world_size 1 included;
- * DCORA_ERR_UNSUPPORTED on an exchange of dcora_exchange_create_ra.  Before it the other six return DCORA_ERR_BAD_ARG
+ * DCORA_ERR_UNSUPPORTED on a range-aided exchange, as before.
+ * dcora_exchange_team_enable_ra (SPMD): the same on the exchange of any range-aided session -- dcora_exchange_create_ra
+ * (an L2 team) or dcora_ra_rbcd_create_robust_ranks, world_size 1 included; DCORA_ERR_UNSUPPORTED on a pose-graph
+ * exchange.  There `agent` is the position in the sorted robot list, the loop closures of an agent are every measurement
+ * but pose-pose odometry (pose-pose closures, pose-landmark measurements, ranges) as for dcora_ra_rbcd_team_*, only the
+ * pose-pose ones are re-weighted, and the counts of all agents come from the job's weights (a rank's own session knows
+ * only its agents').  The six entries below serve both kinds.
+ * Either entry returns DCORA_ERR_UNSUPPORTED, on every rank alike and with the exchange usable afterwards, when the
+ * session's own dcora_rbcd_team_enable / dcora_ra_rbcd_team_enable came first or when a robust ranked session is given an
+ * exchange it was not created with.  Before it the other six return DCORA_ERR_BAD_ARG
  * (the job goes on).  Once enabled, the session's agents optimise through dcora_exchange_rbcd_iterate / _rbcd_tick /
  * _run_coloured / _run_team only.
  * _agent_status, _loop_closure_stats, _should_terminate, _should_update_weights are LOCAL queries: once a collective
@@ -798,6 +809,7 @@ int dcora_ra_rbcd_run_team(dcora_ra_rbcd_t s, int *iters_done, double *cost2_tra
  * they answer from this rank's copy without talking to anyone.  _team_info and _run_team are SPMD.
  * dcora_exchange_run_team: dcora_rbcd_run_team's loop of dcora_exchange_update_weights and dcora_exchange_rbcd_iterate. */
 int dcora_exchange_team_enable(dcora_exchange_t ex, const dcora_team_params *params);
+int dcora_exchange_team_enable_ra(dcora_exchange_t ex, const dcora_team_params *params);
 int dcora_exchange_agent_status(dcora_exchange_t ex, int agent, dcora_agent_status *status, int *known);
 int dcora_exchange_loop_closure_stats(dcora_exchange_t ex, int agent, int counts[3]);
 int dcora_exchange_should_terminate(dcora_exchange_t ex, int *yes);
