@@ -620,6 +620,28 @@ def _session_certify(fn, h, k, eta):
     return bool(psd.value), th.value, v, lm.value, info
 
 
+def _session_lift(self, fn, rank_fn, theta, v, gradient_tolerance, preconditioned_gradient_tolerance,
+                  is_second_order, central_reg):
+    """dcora_rbcd_lift / dcora_ra_rbcd_lift -> (escaped, info); self.r follows the session's rank"""
+    v = np.ascontiguousarray(v, np.float64)
+    if v.shape != (self.k,):
+        raise ValueError("lift needs the certificate's v: k numbers")
+    p = capi.LiftParams()
+    check(capi.lib().dcora_lift_params_default(C.byref(p)))
+    p.gradient_tolerance = gradient_tolerance
+    p.preconditioned_gradient_tolerance = preconditioned_gradient_tolerance
+    p.is_second_order = int(bool(is_second_order))
+    if central_reg is not None:
+        p.central_reg = central_reg
+    esc, i8, r = C.c_int(), np.zeros(8), C.c_int()
+    check(fn(self.h, float(theta), v, C.byref(p), C.byref(esc), i8.ctypes.data_as(C.c_void_p)))
+    check(rank_fn(self.h, C.byref(r)))
+    self.r = r.value
+    info = {"trials": int(i8[0]), "alpha": i8[1], "f_before": i8[2], "f_after": i8[3],
+            "precond_built": bool(i8[4]), "precond_ms": i8[5], "redimension_ms": i8[6], "total_ms": i8[7]}
+    return bool(esc.value), info
+
+
 def _run_coloured(fn, h, max_sweeps, rgrad_tol):
     """the coloured run loop of a session or an exchange: sweeps of one tick per colour, each followed by an evaluation"""
     it = C.c_int()
@@ -697,6 +719,14 @@ class RbcdSession:
         """fastVerification of S = Q - Lambda(X) on the device, with the Q the session holds now (its current weights) and
         its current iterate (dcora_rbcd_certify) -> (psd, theta, v, lambda_min, info); the session is left as it was"""
         return _session_certify(capi.lib().dcora_rbcd_certify, self.h, self.k, eta)
+
+    def lift(self, theta, v, gradient_tolerance=1e-6, preconditioned_gradient_tolerance=1e-6, is_second_order=False,
+             central_reg=None):
+        """The staircase's step in place (dcora_rbcd_lift): escapeSaddle along the refused certificate's (theta, v) into
+        rank r + 1 inside this session, which keeps its matrices, preconditioners, weights, GNC state and team
+        -> (escaped, info).  escaped False: nothing has changed.  self.r is the session's rank afterwards."""
+        return _session_lift(self, capi.lib().dcora_rbcd_lift, capi.lib().dcora_rbcd_rank, theta, v, gradient_tolerance,
+                             preconditioned_gradient_tolerance, is_second_order, central_reg)
 
     def iterate(self, selected):
         c2, gn, nxt = C.c_double(), C.c_double(), C.c_int()
@@ -1047,6 +1077,13 @@ class RaRbcdSession:
     def certify(self, eta):
         """RbcdSession.certify on the merged problem (dcora_ra_rbcd_certify); v in the global RA ordering"""
         return _session_certify(capi.lib().dcora_ra_rbcd_certify, self.h, self.k, eta)
+
+    def lift(self, theta, v, gradient_tolerance=1e-4, preconditioned_gradient_tolerance=1e-4, is_second_order=False,
+             central_reg=None):
+        """RbcdSession.lift on the merged problem (dcora_ra_rbcd_lift); v in the global RA ordering.  The tolerances
+        default to multi_robot_raslam_example's."""
+        return _session_lift(self, capi.lib().dcora_ra_rbcd_lift, capi.lib().dcora_ra_rbcd_rank, theta, v,
+                             gradient_tolerance, preconditioned_gradient_tolerance, is_second_order, central_reg)
 
     def _eval(self, fn, *first):
         c2, gn, nxt = C.c_double(), C.c_double(), C.c_int()

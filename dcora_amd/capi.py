@@ -58,7 +58,12 @@ class TeamParams(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
-AGENT_WAIT_FOR_DATA, AGENT_WAIT_FOR_INITIALIZATION, AGENT_INITIALIZED = 0, 1, 2
+class LiftParams(C.Structure):
+    _fields_ = [("gradient_tolerance", C.c_double), ("preconditioned_gradient_tolerance", C.c_double),
+                ("is_second_order", C.c_int), ("central_reg", C.c_double)]
+
+
+AGENT_WAIT_FOR_DATA,AGENT_WAIT_FOR_INITIALIZATION, AGENT_INITIALIZED = 0, 1, 2
 TEAM_STOP_ALL_READY, TEAM_STOP_MAX_ITERS = 1, 2
 
 
@@ -164,6 +169,11 @@ SIGNATURES = {
     "dcora_rbcd_agent_info": (C.c_int, [_vp, C.c_int, _PI, _PI, _PI]),
     "dcora_rbcd_last_result": (C.c_int, [_vp, C.POINTER(ROptResult)]),
     "dcora_rbcd_certify": (C.c_int, [_vp, C.c_double, _PI, _PD, _PD, _vp, C.POINTER(C.c_longlong), _vp]),
+    "dcora_lift_params_default": (C.c_int, [C.POINTER(LiftParams)]),
+    "dcora_rbcd_lift": (C.c_int, [_vp, C.c_double, _dp, C.POINTER(LiftParams), _PI, _vp]),
+    "dcora_rbcd_rank": (C.c_int, [_vp, _PI]),
+    "dcora_ra_rbcd_lift": (C.c_int, [_vp, C.c_double, _dp, C.POINTER(LiftParams), _PI, _vp]),
+    "dcora_ra_rbcd_rank": (C.c_int, [_vp, _PI]),
     "dcora_rbcd_profile_tcg_runs": (C.c_int, [_vp, C.c_int]),
     "dcora_rbcd_profile_tcg_read": (C.c_int, [_vp, _dp]),
     "dcora_rbcd_create_robust": (C.c_int, [_vp, C.POINTER(RbcdOptions), C.POINTER(RobustParams), _vp, C.POINTER(_vp)]),

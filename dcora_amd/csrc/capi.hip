@@ -1372,6 +1372,29 @@ int dcora_rbcd_certify(dcora_rbcd_t s, double eta, int *certified, double *theta
     return session_certify_out(s->s, eta, certified, theta, lambda_min, v, matvecs, info8);
   });
 }
+// The staircase's step in place (ref examples/MultiRobotExample.cpp:352-366, examples/MultiRobotExample_RASLAM.cpp,
+// src/QuadraticProblem.cpp:138-234): SessionCore::lift of either kind
+int dcora_lift_params_default(dcora_lift_params *p) {
+  return abi_call({p}, [&] {
+    p->gradient_tolerance = 1e-6;
+    p->preconditioned_gradient_tolerance = 1e-6;
+    p->is_second_order = 0;
+    p->central_reg = -1.0;
+    return (int)DCORA_OK;
+  });
+}
+// (ref examples/MultiRobotExample.cpp:352-366, examples/MultiRobotExample_RASLAM.cpp, src/QuadraticProblem.cpp:138-234)
+int dcora_rbcd_lift(dcora_rbcd_t s, double theta, const double *v, const dcora_lift_params *p, int *escaped,
+                    double *info8) {
+  return abi_call({s, v, p, escaped}, [&] { return s->s.lift(theta, v, *p, escaped, info8); });
+}
+// (ref examples/MultiRobotExample.cpp:352-366, examples/MultiRobotExample_RASLAM.cpp, src/QuadraticProblem.cpp:138-234)
+int dcora_rbcd_rank(dcora_rbcd_t s, int *r) {
+  return abi_call({s, r}, [&] {
+    *r = s->s.r;
+    return (int)DCORA_OK;
+  });
+}
 int dcora_rbcd_X_device_ptr(dcora_rbcd_t s, double **X_dev) {
   return abi_call({s, X_dev}, [&] {
     *X_dev = s->s.Xg.p;
@@ -1715,6 +1738,18 @@ int dcora_ra_rbcd_certify(dcora_ra_rbcd_t s, double eta, int *certified, double 
                           long long *matvecs, double *info8) {
   return abi_call({s, certified}, [&] {
     return session_certify_out(s->s, eta, certified, theta, lambda_min, v, matvecs, info8);
+  });
+}
+// (ref examples/MultiRobotExample.cpp:352-366, examples/MultiRobotExample_RASLAM.cpp, src/QuadraticProblem.cpp:138-234)
+int dcora_ra_rbcd_lift(dcora_ra_rbcd_t s, double theta, const double *v, const dcora_lift_params *p, int *escaped,
+                       double *info8) {
+  return abi_call({s, v, p, escaped}, [&] { return s->s.lift(theta, v, *p, escaped, info8); });
+}
+// (ref examples/MultiRobotExample.cpp:352-366, examples/MultiRobotExample_RASLAM.cpp, src/QuadraticProblem.cpp:138-234)
+int dcora_ra_rbcd_rank(dcora_ra_rbcd_t s, int *r) {
+  return abi_call({s, r}, [&] {
+    *r = s->s.r;
+    return (int)DCORA_OK;
   });
 }
 // Agent::initializeRobustOptimization (ref src/Agent.cpp:1332-1346) of every agent of a RangeAidedSLAMGraph at creation

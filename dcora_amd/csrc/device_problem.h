@@ -93,6 +93,7 @@ struct DevCsr {
   DevBuf<double> v, long_part;
   int upload(const HostCsr &A);
   int upload(int nrows, int ncols, const int *rp, const int *ci, const double *v);
+  int download(HostCsr *A) const;  // the uploaded matrix back on the host (synchronous)
   // new values on the uploaded pattern, asynchronous on st (A.v stays alive until st has been synchronised).  The
   // long-row side structures (n_long, long_rows, long_cnt) come from rp alone, so they stand as they are.
   int set_values(const HostCsr &A, hipStream_t st);
@@ -229,6 +230,7 @@ class DeviceProblem {
   bool precond_cache_hit = false;  // owner of the dense inverse Minv.p points to (cache)
   bool sparse_precond = false;
   bool has_precond = false;
+  bool precond_stale = false;  // set_values has changed Q since build_preconditioner last ran
   double precond_setup_ms = 0;
   long precond_nnzL = 0;
 
@@ -265,6 +267,13 @@ class DeviceProblem {
   ~DeviceProblem();
   // Q as host CSR; G host (may be null); reg < 0 => no preconditioner; stream may be shared (null => own)
   int init(const dcora_dims &dims, const HostCsr &Qh, const double *Gh, double reg, int device_, hipStream_t shared);
+  // The problem at another relaxation rank, in place: what init derives from r is rebuilt -- m, the arena and its
+  // slices, fused / group / the block form's use, the sparse preconditioner's attachment, the one-launch tCG run's
+  // eligibility and counters -- and everything else stays: device, stream, host-flag slot and launch sequence, Q and Qb,
+  // the preconditioner image, ride_G cleared and has_G off (the new G is zero).  A pending solve is fetched first.  No
+  // kernel changes: only the template instances the new rank picks.  The new workspace is built aside and swapped in
+  // at the end, so a failure leaves the problem as it was.
+  int rerank(int r_new);
   int set_G_host(const double *Gh);
   int build_preconditioner(const HostCsr &Qh, double reg);
   // The values of a matrix with Q's own pattern into every image the problem keeps of Q: the CSR values and, when
@@ -303,6 +312,11 @@ class DeviceProblem {
   int optimize(const dcora_ropt_params &prm, const double *X0h, double *Xout, dcora_ropt_result *res);
   int escape_saddle(const double *Xopt, double theta, const double *v, double gtol, double pgtol, bool second_order,
                     double *Xout, int *success);
+  // The same search with everything on the device: Xprev ((r - 1) x k) and v (k) are device pointers (not slices of this
+  // problem's X0 / X1 / eta), the accepted point is left in X1.  stats (may be null): trials, accepted alpha (0: none),
+  // f before, f after.  The host form is upload + this + download.
+  int escape_saddle_dev(const double *Xprev, const double *v, double theta, double gtol, double pgtol,
+                        bool second_order, int *success, double stats[4]);
 
   // ---- device-resident solve: X0.p holds the start point.  Returns without synchronising: the result lies in X0 / X1
   // as ctl->cur picks (RTR) or in X1 (RGD); fetch_result() finishes a pending solve and returns its statistics.
@@ -336,6 +350,19 @@ class DeviceProblem {
   int cur_after_fetch_ = 0;
   int upload(const double *h, double *d, size_t n);
   int download(const double *d, double *h, size_t n);
+  // The workspace block, stated once for init and rerank: the slices of the arena a manifold asks for, in arena order;
+  // a zeroed arena for them, built aside (enqueued on st); the buffers made to borrow their slices of it.
+  struct WsSlot {
+    DevBuf<double> *b;
+    size_t n;
+  };
+  std::vector<WsSlot> ws_plan(const ManiDesc &mm, bool fused_);
+  int ws_build(const std::vector<WsSlot> &plan, DevBuf<double> *arena_new);
+  void ws_adopt(const std::vector<WsSlot> &plan, DevBuf<double> &&arena_new);
+  // eligibility of the one-launch tCG run at a manifold, and its zeroed counters where eligible (aside, enqueued on st)
+  int run_form(const ManiDesc &mm, bool fused_, bool has_bsr_, bool *ok, DevBuf<unsigned> *sync);
+  int run_rows_nnz_ = 0;  // tcg_run_max_rows_nnz of Q's pattern (SE layout), kept from init: it does not depend on r
+  int cus_ = 0;           // compute units of the device, asked once
 };
 
 }  // namespace dcora

@@ -70,6 +70,19 @@ int DevBsr::upload(const HostBsr &B) {
   return DCORA_OK;
 }
 int DevCsr::upload(const HostCsr &A) { return upload(A.n, A.ncols, A.rp.data(), A.ci.data(), A.v.data()); }
+int DevCsr::download(HostCsr *A) const {
+  A->n = nrows;
+  A->ncols = ncols;
+  A->rp.resize((size_t)nrows + 1);
+  A->ci.resize((size_t)nnz);
+  A->v.resize((size_t)nnz);
+  DCORA_HIP(hipMemcpy(A->rp.data(), rp.p, sizeof(int) * ((size_t)nrows + 1), hipMemcpyDeviceToHost));
+  if (nnz) {
+    DCORA_HIP(hipMemcpy(A->ci.data(), ci.p, sizeof(int) * (size_t)nnz, hipMemcpyDeviceToHost));
+    DCORA_HIP(hipMemcpy(A->v.data(), v.p, sizeof(double) * (size_t)nnz, hipMemcpyDeviceToHost));
+  }
+  return DCORA_OK;
+}
 int DevCsr::set_values(const HostCsr &A, hipStream_t st) {
   if (A.n != nrows || A.ncols != ncols || A.nnz() != nnz || (int)A.v.size() != nnz) {
     set_last_error("set_values: the matrix does not have the uploaded pattern");
@@ -168,6 +181,11 @@ int DeviceProblem::download(const double *d, double *h, size_t n) {
   return DCORA_OK;
 }
 
+// (the fused Hessian kernel stages the first matrix tile with clamped, unconditional loads: it needs nnz > 0)
+static bool fused_eligible(const ManiDesc &mm, int nnz) {
+  return fused_supported(mm) && nnz > 0 && !env::generic_solver();
+}
+
 int DeviceProblem::init(const dcora_dims &dims, const HostCsr &Qh, const double *Gh, double reg, int device_,
                         hipStream_t shared) {
   if (dims.r < 1 || dims.r > 16 || (dims.d != 2 && dims.d != 3) || dims.n < 0 || dims.l < 0 || dims.b < 0) {
@@ -214,43 +232,15 @@ int DeviceProblem::init(const dcora_dims &dims, const HostCsr &Qh, const double 
     if (rc) return rc;
     has_bsr = true;
   }
-  const size_t N = (size_t)nelem();
-  const size_t NS = (size_t)m.n * m.d * m.d + m.l + 1;
-  // (the fused Hessian kernel stages the first matrix tile with clamped, unconditional loads: it needs nnz > 0)
-  fused = fused_supported(m) && Qh.nnz() > 0 && !env::generic_solver();
+  fused = fused_eligible(m, Q.nnz);
   group = group_supported(m) && !env::generic_solver();
-  // One allocation for the whole solver workspace, zeroed by one memset: the reference re-creates its problem on
-  // every Agent::updateX (ref src/Agent.cpp:1252), so creation must cost a fraction of a solve -- thirty hipMalloc
-  // and ten synchronous hipMemset calls took 4-8 ms.
+  run_rows_nnz_ = m.se ? tcg_run_max_rows_nnz(m, Qh.rp.data()) : 0;
   {
-    struct Slot {
-      DevBuf<double> *b;
-      size_t n;
-    };
-    std::vector<Slot> slots;
-    for (DevBuf<double> *b : {&G, &X0, &X1, &EG0, &EG1, &RG0, &RG1, &delta, &eta, &Heta, &res, &z, &Hd, &W, &Zt})
-      slots.push_back({b, N});
-    slots.push_back({&delta2, N});
-    if (fused) {
-      slots.push_back({&res2, N});
-      slots.push_back({&Zpart, (size_t)fused_nsplit(m) * N});  // slice 0 doubles as Z of the sparse preconditioner
-    }
-    slots.push_back({&S0, NS});
-    slots.push_back({&S1, NS});
-    // 2 doubles per slot; the Q-apply may add up to kMaxPartials / 2 long-row blocks to its kMaxPartials row blocks
-    for (DevBuf<double> *b : {&pB, &pC, &p1, &p2, &p3}) slots.push_back({b, (size_t)4 * kMaxPartials});
-    slots.push_back({&pA, 2 * (size_t)kBsrMaxGrid});  // the block-CSR Q-apply runs up to kBsrMaxGrid workgroups
-    slots.push_back({&scal, 64});
-    auto pad = [](size_t n) { return (n + 31) & ~(size_t)31; };  // 256-byte aligned slices
-    size_t total = 0;
-    for (const Slot &sl : slots) total += pad(sl.n);
-    DCORA_HIP(arena.alloc(total));
-    DCORA_HIP(hipMemsetAsync(arena.p, 0, total * sizeof(double), st));
-    size_t off = 0;
-    for (const Slot &sl : slots) {
-      sl.b->borrow(arena.p + off, sl.n);
-      off += pad(sl.n);
-    }
+    const std::vector<WsSlot> plan = ws_plan(m, fused);
+    DevBuf<double> fresh;
+    rc = ws_build(plan, &fresh);
+    if (rc) return rc;
+    ws_adopt(plan, std::move(fresh));
   }
   DCORA_HIP(ctl.alloc(1));
   {
@@ -268,22 +258,118 @@ int DeviceProblem::init(const dcora_dims &dims, const HostCsr &Qh, const double 
     if (rc) return rc;
   }
   lap("precond");
-  // the one-launch tCG run: dense inverse, the whole residual in one LDS image, n / 2 workgroups co-resident
-  if (fused && has_precond && !sparse_precond && !has_bsr && Q.n_long == 0 && env::solver_tcg() >= 0) {
+  return run_form(m, fused, has_bsr, &tcg_run_ok, &tcg_sync);
+}
+
+// One allocation for the whole solver workspace, zeroed by one memset: the reference re-creates its problem on
+// every Agent::updateX (ref src/Agent.cpp:1252), so creation must cost a fraction of a solve -- thirty hipMalloc
+// and ten synchronous hipMemset calls took 4-8 ms.
+std::vector<DeviceProblem::WsSlot> DeviceProblem::ws_plan(const ManiDesc &mm, bool fused_) {
+  const size_t N = (size_t)mm.r * mm.k;
+  const size_t NS = (size_t)mm.n * mm.d * mm.d + mm.l + 1;
+  std::vector<WsSlot> slots;
+  for (DevBuf<double> *b : {&G, &X0, &X1, &EG0, &EG1, &RG0, &RG1, &delta, &eta, &Heta, &res, &z, &Hd, &W, &Zt})
+    slots.push_back({b, N});
+  slots.push_back({&delta2, N});
+  if (fused_) {
+    slots.push_back({&res2, N});
+    slots.push_back({&Zpart, (size_t)fused_nsplit(mm) * N});  // slice 0 doubles as Z of the sparse preconditioner
+  }
+  slots.push_back({&S0, NS});
+  slots.push_back({&S1, NS});
+  // 2 doubles per slot; the Q-apply may add up to kMaxPartials / 2 long-row blocks to its kMaxPartials row blocks
+  for (DevBuf<double> *b : {&pB, &pC, &p1, &p2, &p3}) slots.push_back({b, (size_t)4 * kMaxPartials});
+  slots.push_back({&pA, 2 * (size_t)kBsrMaxGrid});  // the block-CSR Q-apply runs up to kBsrMaxGrid workgroups
+  slots.push_back({&scal, 64});
+  return slots;
+}
+static size_t ws_pad(size_t n) { return (n + 31) & ~(size_t)31; }  // 256-byte aligned slices
+int DeviceProblem::ws_build(const std::vector<WsSlot> &plan, DevBuf<double> *arena_new) {
+  size_t total = 0;
+  for (const WsSlot &sl : plan) total += ws_pad(sl.n);
+  DCORA_HIP(arena_new->alloc(total));
+  DCORA_HIP(hipMemsetAsync(arena_new->p, 0, total * sizeof(double), st));
+  return DCORA_OK;
+}
+void DeviceProblem::ws_adopt(const std::vector<WsSlot> &plan, DevBuf<double> &&arena_new) {
+  for (DevBuf<double> *b : {&res2, &Zpart}) b->release();  // (not in every plan)
+  arena = std::move(arena_new);
+  size_t off = 0;
+  for (const WsSlot &sl : plan) {
+    sl.b->borrow(arena.p + off, sl.n);
+    off += ws_pad(sl.n);
+  }
+}
+
+// the one-launch tCG run: dense inverse, the whole residual in one LDS image, n / 2 workgroups co-resident
+int DeviceProblem::run_form(const ManiDesc &mm, bool fused_, bool has_bsr_, bool *ok, DevBuf<unsigned> *sync) {
+  *ok = false;
+  if (!(fused_ && has_precond && !sparse_precond && !has_bsr_ && Q.n_long == 0 && env::solver_tcg() >= 0))
+    return DCORA_OK;
+  if (cus_ == 0) {
     hipDeviceProp_t prop;
     DCORA_HIP(hipGetDeviceProperties(&prop, device));
-    tcg_run_ok = tcg_run_supported(m, ldm, prop.multiProcessorCount, tcg_run_max_rows_nnz(m, Qh.rp.data()));
-    if (tcg_run_ok) {
-      DCORA_HIP(tcg_sync.alloc((size_t)tcg_run_sync_words()));
-      DCORA_HIP(hipMemsetAsync(tcg_sync.p, 0, sizeof(unsigned) * (size_t)tcg_run_sync_words(), st));
-    }
+    cus_ = prop.multiProcessorCount;
   }
+  if (!tcg_run_supported(mm, ldm, cus_, run_rows_nnz_)) return DCORA_OK;
+  DCORA_HIP(sync->alloc((size_t)tcg_run_sync_words()));
+  DCORA_HIP(hipMemsetAsync(sync->p, 0, sizeof(unsigned) * (size_t)tcg_run_sync_words(), st));
+  *ok = true;
+  return DCORA_OK;
+}
+
+int DeviceProblem::rerank(int r_new) {
+  if (r_new < 1 || r_new > 16) {
+    set_last_error("rerank: need 1 <= r <= 16");
+    return DCORA_ERR_BAD_ARG;
+  }
+  DCORA_HIP(hipSetDevice(device));
+  if (pending_) {
+    const int rc = fetch_result(nullptr);
+    if (rc) return rc;
+  }
+  DCORA_HIP(hipStreamSynchronize(st));  // nothing in flight reads the workspace that goes
+  ManiDesc mn = m;
+  mn.r = r_new;
+  const bool fused_n = fused_eligible(mn, Q.nnz);
+  const bool group_n = group_supported(mn) && !env::generic_solver();
+  const bool bsr_n = Qb.nbrows > 0 && r_new <= 8;  // (the block form was uploaded: every other condition of init held)
+  // aside: the arena, the replay vectors of the sparse preconditioner, the counters of the one-launch tCG run
+  const std::vector<WsSlot> plan = ws_plan(mn, fused_n);
+  DevBuf<double> arena_n;
+  int rc = ws_build(plan, &arena_n);
+  if (rc) return rc;
+  SparsePrecond sp_n;
+  if (sparse_precond) {
+    rc = sp_n.attach(sp.im, r_new);
+    if (rc) return rc;
+    DCORA_HIP(hipStreamSynchronize(nullptr));  // (its memsets run on the null stream)
+  }
+  bool run_n = false;
+  DevBuf<unsigned> sync_n;
+  rc = run_form(mn, fused_n, bsr_n, &run_n, &sync_n);
+  if (rc) return rc;
+  DCORA_HIP(hipStreamSynchronize(st));  // the zeroed workspace is visible to every stream
+  // the swap: nothing below fails
+  m = mn;
+  fused = fused_n;
+  group = group_n;
+  has_bsr = bsr_n;
+  ws_adopt(plan, std::move(arena_n));
+  if (sparse_precond) sp = std::move(sp_n);
+  tcg_run_ok = run_n;
+  tcg_sync = std::move(sync_n);
+  has_G = false;
+  ride_X_ = nullptr;
+  rgd_ = false;
+  cur_after_fetch_ = 0;
   return DCORA_OK;
 }
 
 int DeviceProblem::set_values(const HostCsr &Q_on_pattern, hipStream_t stream, std::vector<double> *stage) {
   const int rc = Q.set_values(Q_on_pattern, stream);
-  if (rc || !has_bsr) return rc;
+  if (!rc) precond_stale = has_precond;
+  if (rc || Qb.nbrows == 0) return rc;  // (the block form is kept current also while a rank above 8 leaves it unused)
   *stage = std::move(bsr_from_csr(Q_on_pattern, m.d + 1).bv);
   if (stage->size() != Qb.bv.n) {
     set_last_error("set_values: the matrix does not have the uploaded pattern");
@@ -495,6 +581,7 @@ int DeviceProblem::build_preconditioner(const HostCsr &Qh, double reg) {
     Minv.borrow(ent.dense->p, ent.dense->n);
   }
   has_precond = true;
+  precond_stale = false;
   precond_setup_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   if (env::init_timing()) fprintf(stderr, "[precond] attached after %.1f ms\n", precond_setup_ms);
   return DCORA_OK;
@@ -1188,26 +1275,46 @@ int DeviceProblem::escape_saddle(const double *Xopt, double theta, const double 
     set_last_error("escapeSaddle needs the preconditioner");
     return DCORA_ERR_NO_PRECONDITIONER;
   }
-  DCORA_HIP(hipSetDevice(device));
-  const int r = m.r, k = m.k;
-  std::vector<double> Xp((size_t)r * k, 0.0), Xd((size_t)r * k, 0.0);
-  for (int j = 0; j < k; ++j) {
-    for (int t = 0; t < r - 1; ++t) Xp[(size_t)j * r + t] = Xopt[(size_t)j * (r - 1) + t];
-    Xd[(size_t)j * r + (r - 1)] = v[j];
+  if (m.r < 2) {
+    set_last_error("escapeSaddle needs a problem of rank 2 at least (the point has one row less)");
+    return DCORA_ERR_BAD_ARG;
   }
-  int rc = upload(Xp.data(), X0.p, nelem());
+  DCORA_HIP(hipSetDevice(device));
+  // the point and v staged in two slices the search does not use
+  int rc = upload(Xopt, W.p, (size_t)(m.r - 1) * m.k);
   if (rc) return rc;
-  rc = upload(Xd.data(), eta.p, nelem());
+  rc = upload(v, Hd.p, (size_t)m.k);
   if (rc) return rc;
-  DCORA_HIP(hipStreamSynchronize(st));
+  DCORA_HIP(hipStreamSynchronize(st));  // (the caller's pageable buffers have been read)
+  rc = escape_saddle_dev(W.p, Hd.p, theta, gtol, pgtol, second_order, success, nullptr);
+  if (rc || !*success) return rc;
+  return download(X1.p, Xout, nelem());
+}
+
+int DeviceProblem::escape_saddle_dev(const double *Xprev, const double *v, double theta, double gtol, double pgtol,
+                                     bool second_order, int *success, double stats[4]) {
+  *success = 0;
+  if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
+  if (!has_precond) {
+    set_last_error("escapeSaddle needs the preconditioner");
+    return DCORA_ERR_NO_PRECONDITIONER;
+  }
+  if (m.r < 2) {
+    set_last_error("escapeSaddle needs a problem of rank 2 at least (the point has one row less)");
+    return DCORA_ERR_BAD_ARG;
+  }
+  DCORA_HIP(hipSetDevice(device));
+  // X_plus = [X; 0] into X0, the direction [0; v^T] into eta: one launch
+  launch_lift_images(st, m.r - 1, m.k, Xprev, v, X0.p, eta.p);
+  DCORA_HIP(hipGetLastError());
   double FX = 0;
-  rc = eval_dev(X0.p, &FX, nullptr);
+  int rc = eval_dev(X0.p, &FX, nullptr);
   if (rc) return rc;
+  if (stats) stats[2] = stats[3] = FX;
   const double alpha_min = 1e-6;
   // ref :165-169: SE-Sync's second-order step when asked for, else Algorithm 7 of the DC2-PGO report
   double alpha = second_order ? std::max(16 * alpha_min, 100 * gtol / std::fabs(theta)) : 1.0;
   std::vector<double> alphas, fvals;
-  *success = 0;
   while (alpha >= alpha_min) {
     launch_retract(st, m, buf1(X0.p), eta.p, alpha, buf1(X1.p), 0, buf1(RG0.p), nullptr, nullptr, Gate{});
     enqueue_egrad(X1.p, EG1.p, pA.p);
@@ -1223,9 +1330,11 @@ int DeviceProblem::escape_saddle(const double *Xopt, double theta, const double 
     const double FXt = 0.5 * s[0] + s[1], gn = std::sqrt(s[2]), pgn = std::sqrt(s[3]);
     alphas.push_back(alpha);
     fvals.push_back(FXt);
+    if (stats) stats[0] = (double)alphas.size();
     if (FXt < FX && gn > gtol && pgn > pgtol) {
       *success = 1;
-      return download(X1.p, Xout, nelem());
+      if (stats) stats[1] = alpha, stats[3] = FXt;
+      return DCORA_OK;
     }
     alpha /= 2;
   }
@@ -1233,7 +1342,7 @@ int DeviceProblem::escape_saddle(const double *Xopt, double theta, const double 
   if (fvals[idx] < FX) {
     launch_retract(st, m, buf1(X0.p), eta.p, alphas[idx], buf1(X1.p), 0, buf1(RG0.p), nullptr, nullptr, Gate{});
     *success = 1;
-    return download(X1.p, Xout, nelem());
+    if (stats) stats[1] = alphas[idx], stats[3] = fvals[idx];
   }
   return DCORA_OK;
 }

@@ -350,6 +350,7 @@ int Exchange::barrier(double timeout_s) {
 
 int Exchange::init(SessionCore *s, const char *job_name, size_t weights) {
   s_ = s;
+  s->exchange_attached = true;  // (the segment and the halo slots below are sized by the session's rank: no lift)
   pose_ = dynamic_cast<RbcdSession *>(s);
   rank = s->opt.rank;
   world = s->opt.world_size;

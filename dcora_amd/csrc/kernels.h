@@ -239,6 +239,9 @@ void launch_sum_partials(hipStream_t st, const double *partials, int np, int str
 void launch_dot(hipStream_t st, long nelem, const double *x, const double *y, double *partials);
 void launch_gather_cols(hipStream_t st, int r, int ncols, const int *src_col, const double *X, double *out);
 void launch_scatter_cols(hipStream_t st, int r, int ncols, const int *dst_col, const double *in, double *X);
+// Both images escapeSaddle starts from (ref src/QuadraticProblem.cpp:148-160), from X (r x k column-major) and v (k):
+// Xplus (r + 1) x k with column j = [x_j; 0], dir (r + 1) x k with column j = [0; v_j]  (lift.hip)
+void launch_lift_images(hipStream_t st, int r, long k, const double *X, const double *v, double *Xplus, double *dir);
 // out[2a] = |A[:, cs[a]:cs[a+1]]|^2, out[2a+1] = <A, B> over the same columns (B may be null)
 void launch_block_dots(hipStream_t st, int r, int nagents, const int *col_start, const double *A, const double *B,
                        double *out);

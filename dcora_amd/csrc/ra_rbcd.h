@@ -125,6 +125,13 @@ class RaRbcdSession : public SessionCore {
   // the one path from a dataset's measurements to the session's matrices, at creation and on every re-weight
   int assemble(const HostRADataset &ds, bool creation);
   int adopt_weights(HostRADataset &ds, bool from_device, bool reset_to_initial);
+  // set_X's body for a point on the host or on the device (kind: the copy into the mirror)
+  int adopt_X(const double *X, hipMemcpyKind kind);
+  // SessionCore::lift's hooks: the mirror, X_initial and the agents' X, V, Y, XPrev, tmp re-dimensioned; the central
+  // preconditioner's regularisation is device_precond_regularization(central Q), as driver.py passes
+  int lift_default_reg(const HostCsr &Qc, double *reg) override;
+  int lift_buffers(int r_new) override;
+  int lift_adopt(const double *X_dev) override { return adopt_X(X_dev, hipMemcpyDeviceToDevice); }
   int gather_agents();         // every hosted agent's X from the mirror, V = Y = XPrev = X (enqueued)
   int scatter(RaAgentDev &a);  // my X into the global mirror
   int solve(RaAgentDev &a, const double *start, double **result);

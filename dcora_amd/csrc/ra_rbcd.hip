@@ -423,10 +423,39 @@ int RaRbcdSession::gather_agents() {
   return DCORA_OK;
 }
 
-int RaRbcdSession::set_X(const double *Xh) {
+int RaRbcdSession::set_X(const double *Xh) { return adopt_X(Xh, hipMemcpyHostToDevice); }
+
+// ---- the staircase step in place: SessionCore::lift's hooks ------------------------------------------------------
+int RaRbcdSession::lift_default_reg(const HostCsr &Qc, double *reg) {
+  return device_precond_regularization(Qc, opt.device, reg);
+}
+
+int RaRbcdSession::lift_buffers(int r_new) {
+  DevBuf<double> X, XI;
+  DCORA_HIP(X.alloc((size_t)r_new * k));
+  if (robust) DCORA_HIP(XI.alloc((size_t)r_new * k));
+  std::vector<DevBuf<double>> own((size_t)R * 5);  // per hosted agent: X, V, Y, XPrev, tmp
+  for (int i = 0; i < R; ++i)
+    for (int q = 0; q < 5 && agents[(size_t)i].hosted; ++q)
+      DCORA_HIP(own[(size_t)i * 5 + q].alloc((size_t)r_new * agents[(size_t)i].k));
+  // the swap: nothing below fails
+  Xg = std::move(X);
+  if (robust) robust->X_initial = std::move(XI);
+  for (int i = 0; i < R; ++i) {
+    RaAgentDev &a = agents[(size_t)i];
+    if (!a.hosted) continue;
+    DevBuf<double> *mine[5] = {&a.X, &a.V, &a.Y, &a.XPrev, &a.tmp};
+    for (int q = 0; q < 5; ++q) *mine[q] = std::move(own[(size_t)i * 5 + q]);
+  }
+  r = r_new;
+  opt.r = r_new;
+  return DCORA_OK;
+}
+
+int RaRbcdSession::adopt_X(const double *X, hipMemcpyKind kind) {
   DCORA_HIP(hipSetDevice(opt.device));
   const size_t B = sizeof(double) * (size_t)r * k;
-  DCORA_HIP(hipMemcpyAsync(Xg.p, Xh, B, hipMemcpyHostToDevice, st));
+  DCORA_HIP(hipMemcpyAsync(Xg.p, X, B, kind, st));
   if (robust) DCORA_HIP(hipMemcpyAsync(robust->X_initial.p, Xg.p, B, hipMemcpyDeviceToDevice, st));
   const int rc = gather_agents();
   if (rc) return rc;

@@ -136,6 +136,13 @@ class RbcdSession : public SessionCore {
   int staged_iteration_ = -1; // the round it was staged in: honoured by update_selected_agent in that round only
   bool pending_reset_ = false;  // gamma = alpha = 0 after a restart round, applied when the next round begins
   std::vector<char> set_marks_;  // agents that received Agent::setX since the last round
+  // set_X's body for a point on the host or on the device (kind: the copy into the mirror)
+  int adopt_X(const double *X, hipMemcpyKind kind);
+  // SessionCore::lift's hooks: Xg, Vg, Yg, XPrevg, X_initial and the staging buffer of get_X re-dimensioned, the agents'
+  // handed neighbour caches dropped; the central preconditioner's regularisation is the agents' (driver.py passes 0.1)
+  int lift_default_reg(const HostCsr &Qc, double *reg) override;
+  int lift_buffers(int r_new) override;
+  int lift_adopt(const double *X_dev) override { return adopt_X(X_dev, hipMemcpyDeviceToDevice); }
   int update_nonselected_agent(AgentDev &a, bool restart);
   int update_selected_agent(AgentDev &a, bool restart);
   int restart_step(AgentDev &a);

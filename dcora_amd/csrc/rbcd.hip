@@ -301,11 +301,13 @@ int RbcdSession::attach_preconditioners(const std::vector<HostCsr> &Q, const std
 }
 
 // Agent::setX + initializeAcceleration for every agent (ref src/Agent.cpp:64-77, 1178-1187)
-int RbcdSession::set_X(const double *Xh) {
+int RbcdSession::set_X(const double *Xh) { return adopt_X(Xh, hipMemcpyHostToDevice); }
+
+int RbcdSession::adopt_X(const double *X, hipMemcpyKind kind) {
   staged_selected_ = -1;  // a step staged by an interrupted round does not survive a new start point
   DCORA_HIP(hipSetDevice(opt.device));
   const size_t B = sizeof(double) * (size_t)r * (d + 1) * n;
-  DCORA_HIP(hipMemcpyAsync(Xg.p, Xh, B, hipMemcpyHostToDevice, st));
+  DCORA_HIP(hipMemcpyAsync(Xg.p, X, B, kind, st));
   DCORA_HIP(hipMemcpyAsync(Vg.p, Xg.p, B, hipMemcpyDeviceToDevice, st));
   DCORA_HIP(hipMemcpyAsync(Yg.p, Xg.p, B, hipMemcpyDeviceToDevice, st));
   DCORA_HIP(hipMemcpyAsync(XPrevg.p, Xg.p, B, hipMemcpyDeviceToDevice, st));
@@ -348,6 +350,41 @@ int RbcdSession::get_X(double *Xh) {
   DCORA_HIP(hipMemcpyAsync(x_stage, Xg.p, B, hipMemcpyDeviceToHost, st));
   DCORA_HIP(hipStreamSynchronize(st));
   std::memcpy(Xh, x_stage, B);
+  return DCORA_OK;
+}
+
+// ---- the staircase step in place: SessionCore::lift's hooks -------------------------------------------------------
+int RbcdSession::lift_default_reg(const HostCsr &, double *reg) {
+  *reg = kPrecondReg;
+  return DCORA_OK;
+}
+
+int RbcdSession::lift_buffers(int r_new) {
+  const size_t N = (size_t)r_new * (d + 1) * n;
+  DevBuf<double> X, V, Y, XP, XI;
+  for (DevBuf<double> *b : {&X, &V, &Y, &XP}) DCORA_HIP(b->alloc(N));
+  if (robust) DCORA_HIP(XI.alloc(N));
+  double *stage_new = nullptr;
+  DCORA_HIP(hipHostMalloc((void **)&stage_new, sizeof(double) * N, hipHostMallocDefault));
+  // the swap: nothing below fails
+  Xg = std::move(X);
+  Vg = std::move(V);
+  Yg = std::move(Y);
+  XPrevg = std::move(XP);
+  if (robust) robust->X_initial = std::move(XI);
+  if (x_stage) (void)hipHostFree((void *)x_stage);
+  x_stage = stage_new;
+  r = r_new;
+  opt.r = r_new;
+  mg = make_mani(r, d, n, 0, 0);
+  for (AgentDev &a : agents) {  // handed neighbour poses have the old rank: the agents read the mirror again
+    a.detached = false;
+    a.last_skipped = false;
+    for (int w = 0; w < 2; ++w) {
+      a.nbr[w].release();
+      a.got[w].clear();
+    }
+  }
   return DCORA_OK;
 }
 

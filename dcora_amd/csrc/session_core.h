@@ -102,6 +102,27 @@ class SessionCore {
   // central Q as the last weight change left it -- at the mirror as it stands (session_cert.h).  Single-process sessions
   // only; nothing of the session changes.
   int certify(double eta, CertifyResult *out, double *info8);
+  // The Riemannian staircase's step in place (ref examples/MultiRobotExample.cpp:352-366, where a level is a new set of
+  // agents; src/QuadraticProblem.cpp:138-234): the session goes from rank r to r + 1 along the certificate's direction
+  // (theta, v: what certify returned, v on the host) and keeps everything that does not depend on r -- matrices,
+  // preconditioners, regularisations, neighbours, public columns, colours, robust weights with mu and the update count,
+  // the team with its parameters and loop-closure counts, the certificate's tables.
+  //   a. every stream of the session is synchronised;
+  //   b. the central problem gets its preconditioner (escapeSaddle's PreCondition) if it has none, or if a re-weight
+  //      changed the central Q since it was built: of the matrix the device holds, with p.central_reg or the kind's
+  //      default (lift_default_reg: what the two Python drivers pass);
+  //   c. the central problem is re-ranked and runs the device escape from the mirror;
+  //   d. no escape: its re-rank is undone, *escaped = 0, nothing of the session has changed;
+  //   e. escaped: every hosted agent's problem is re-ranked, the kind's buffers re-dimensioned (lift_buffers), and the
+  //      accepted point adopted as set_X adopts one (lift_adopt): mirror, agents' blocks, V = Y = XPrev = X, sequences
+  //      and round counters restarted, X_initial of a robust session, team statuses cleared.  Handed neighbour caches
+  //      are dropped; device pointers into the session's buffers handed out earlier (X_device_ptr) are void.
+  // Refused, the session untouched: a rank of a job, a ranked robust / team session or a session an exchange was created
+  // on (DCORA_ERR_UNSUPPORTED: the exchange's halo layout is sized by r); r = 16, v null or not finite, theta or a
+  // tolerance not finite (DCORA_ERR_BAD_ARG).  info8 (may be null): trials, accepted alpha, f before, f after, 1 if the
+  // central preconditioner was built in this call, its ms, ms of the re-dimensioning, ms total.
+  int lift(double theta, const double *v, const dcora_lift_params &p, int *escaped, double *info8);
+  bool exchange_attached = false;  // an Exchange was created on this session
   virtual DeviceProblem *central_problem() = 0;                        // null on a rank of a multi-rank job
   virtual const HostCsr *central_pattern() const { return nullptr; }  // host copy of its pattern, where one is kept
   // the stored entries the current weights give, where the session certifies over those alone (session_cert.h)
@@ -160,6 +181,15 @@ class SessionCore {
   int create_fork_event();
   void release_tick_resources(AgentCore &a);  // before the agent's problem goes
   void release_stream();  // (with the fork event) after everything that runs on it has gone
+
+  // what a session kind supplies to lift:
+  // the regularisation of the central preconditioner where the caller names none
+  virtual int lift_default_reg(const HostCsr &Qc, double *reg) = 0;
+  // the buffers the kind owns at rank r_new, allocated aside and swapped in, with r, opt.r and what else the kind
+  // derives from r; their contents are undefined until lift_adopt.  On failure nothing has changed.
+  virtual int lift_buffers(int r_new) = 0;
+  // set_X of a point that lies on the device (r x num_cols(), the mirror's ordering): everything set_X leaves
+  virtual int lift_adopt(const double *X_dev) = 0;
 
   // the three things a session kind supplies to the tick
   virtual void tick_begins() {}  // (the set is valid: per-tick resets)

@@ -1,7 +1,9 @@
 // The session core on the host (see session_core.h).
 #include "session_core.h"
 
+#include <algorithm>
 #include <atomic>
+#include <chrono>
 #include <cmath>
 #include <cstring>
 
@@ -45,6 +47,105 @@ int SessionCore::certify(double eta, CertifyResult *out, double *info8) {
     if (agent_core(a).own_st) DCORA_HIP(hipStreamSynchronize(agent_core(a).own_st));
   return session_certify(cert_, *central, central_pattern(), central_live_pattern(), Xg.p, cert_block(), eta, out,
                          info8);
+}
+
+int SessionCore::lift(double theta, const double *v, const dcora_lift_params &p, int *escaped, double *info8) {
+  const std::string tag = std::string(tag_) + " lift: ";
+  using clock = std::chrono::steady_clock;
+  auto ms_since = [](clock::time_point t) { return std::chrono::duration<double, std::milli>(clock::now() - t).count(); };
+  *escaped = 0;
+  if (info8) std::fill(info8, info8 + 8, 0.0);
+  DeviceProblem *central = opt.world_size == 1 ? central_problem() : nullptr;
+  if (!central || weights_ranked() || (team && team->ranked) || exchange_attached) {
+    set_last_error(tag + "serves single-process sessions without an exchange (the exchange's halo layout is sized by "
+                   "the rank); a collective lift across the ranks of a job is not available");
+    return DCORA_ERR_UNSUPPORTED;
+  }
+  if (r + 1 > 16) {
+    set_last_error(tag + "the session is at rank 16, the largest the kernels are built for");
+    return DCORA_ERR_BAD_ARG;
+  }
+  const long k = num_cols();
+  bool finite = v && std::isfinite(theta) && std::isfinite(p.gradient_tolerance) &&
+                std::isfinite(p.preconditioned_gradient_tolerance) && std::isfinite(p.central_reg);
+  for (long j = 0; finite && j < k; ++j) finite = std::isfinite(v[j]);
+  if (!finite) {
+    set_last_error(tag + "v must be k finite numbers, theta, the tolerances and central_reg finite");
+    return DCORA_ERR_BAD_ARG;
+  }
+  const auto t0 = clock::now();
+  DCORA_HIP(hipSetDevice(opt.device));
+  // a. nothing of the session is in flight
+  for (int a = 0; a < R; ++a)
+    if (agent_core(a).own_st) DCORA_HIP(hipStreamSynchronize(agent_core(a).own_st));
+  DCORA_HIP(hipStreamSynchronize(st));
+  // b. escapeSaddle's PreCondition: of the central Q as the device holds it now (the current weights)
+  if (!central->has_precond || central->precond_stale) {
+    const auto tb = clock::now();
+    HostCsr Qc;
+    int rc = central->Q.download(&Qc);
+    if (rc) return rc;
+    double reg = p.central_reg;
+    if (reg < 0 && (rc = lift_default_reg(Qc, &reg))) return rc;
+    rc = central->build_preconditioner(Qc, reg);
+    if (rc) return rc;
+    if (info8) info8[4] = 1, info8[5] = ms_since(tb);
+  }
+  // c. the central problem at r + 1, the escape from the mirror; v is all that comes from the host
+  const int r_old = r, r_new = r + 1;
+  int rc = central->rerank(r_new);
+  if (rc) return rc;
+  int ok = 0;
+  double stats[4] = {0, 0, 0, 0};
+  // (v into a slice of the central workspace the search does not use)
+  if (hipMemcpyAsync(central->Hd.p, v, sizeof(double) * (size_t)k, hipMemcpyHostToDevice, st) != hipSuccess) {
+    set_last_error(tag + "the copy of v to the device failed");
+    rc = DCORA_ERR_HIP;
+  }
+  if (!rc)
+    rc = central->escape_saddle_dev(Xg.p, central->Hd.p, theta, p.gradient_tolerance,
+                                    p.preconditioned_gradient_tolerance, p.is_second_order != 0, &ok, stats);
+  if (info8) std::copy(stats, stats + 4, info8);
+  // what has been re-ranked goes back to r_old (the error that led here is the one reported)
+  auto undo = [&](int upto) {
+    const std::string keep = dcora_last_error();
+    for (int a = 0; a < upto; ++a)
+      if (agent_core(a).hosted) (void)agent_core(a).prob->rerank(r_old);
+    (void)central->rerank(r_old);
+    set_last_error(keep);
+  };
+  if (rc || !ok) {  // d.
+    undo(0);
+    if (info8) info8[7] = ms_since(t0);
+    return rc;
+  }
+  // e. the agents' problems, the kind's buffers and the certificate's r-sized buffer, each built aside
+  const auto te = clock::now();
+  for (int a = 0; a < R; ++a) {
+    if (!agent_core(a).hosted) continue;
+    rc = agent_core(a).prob->rerank(r_new);
+    if (rc) {
+      undo(a);
+      return rc;
+    }
+  }
+  DevBuf<double> xq;
+  if (cert_.built && hipSuccess != xq.alloc((size_t)r_new * (size_t)k)) {
+    set_last_error(tag + "out of device memory");
+    rc = DCORA_ERR_HIP;
+  }
+  if (!rc) rc = lift_buffers(r_new);
+  if (rc) {
+    undo(R);
+    return rc;
+  }
+  if (cert_.built) cert_.XQ = std::move(xq);
+  rc = lift_adopt(central->X1.p);
+  if (rc) return rc;
+  DCORA_HIP(hipStreamSynchronize(st));
+  *escaped = 1;
+  if (info8) info8[6] = ms_since(te), info8[7] = ms_since(t0);
+  return DCORA_OK;
 }
 
 int SessionCore::acquire_stream(void *borrowed) {

@@ -98,6 +98,104 @@ def multi_robot_example(ds, X0, num_robots=5, r_min=5, r_max=100, max_iters=1000
             "selected": cat(selected, np.int32), "rank_trace": cat(rank, np.int32)}
 
 
+def _staircase_session(s, X0, k, r_min, r_max, max_iters, rgrad_tol, min_eig_tol, gradient_tolerance,
+                       preconditioned_gradient_tolerance, mode, ts, gap=None, before_certify=None):
+    """The staircase of the two drivers above in ONE session of either kind: each level is run / run_coloured, certify
+    (the session's own, on the device) and lift (the escape into the next rank in place) -- the reference makes a new
+    set of agents per level (examples/MultiRobotExample.cpp:352-366), this keeps them.  The level records are the
+    existing drivers'; the iterate comes to the host once, after the last level (gap(X, psd, lmin) -> the bound of
+    that level's record; the earlier levels carry None)."""
+    X = np.asarray(X0, dtype=np.float64)
+    if X.shape != (r_min, k):
+        raise ValueError("X0 must be r_min x k")
+    levels, cost, gradnorm, selected, rank = [], [], [], [], []
+    certified, theta, total = False, 0.0, 0
+    try:
+        s.set_X(X)
+        while s.r < r_max:
+            r = s.r
+            t0 = time.perf_counter()
+            out = _run_level(s, mode, max_iters, rgrad_tol)
+            t1 = time.perf_counter()
+            total += out["iters"]
+            cost.append(out["cost"])
+            gradnorm.append(out["gradnorm"])
+            selected.append(out["selected"])
+            rank.append(np.full(out["iters"], r, np.int32))
+            if before_certify is not None:
+                before_certify()
+            psd, theta, v, lmin, _ = s.certify(min_eig_tol)
+            t2 = time.perf_counter()
+            lev = {"rank": r, "iterations": int(out["iters"]), "cost_2f": float(out["cost"][-1]),
+                   "gradnorm": float(out["gradnorm"][-1]), "setup_s": t0 - ts, "rbcd_s": t1 - t0,
+                   "certification_s": t2 - t1, "certified": bool(psd), "theta": float(theta), "mode": mode,
+                   "suboptimality_gap_f": None, "n_eff": None, "lambda_min": float(lmin)}
+            levels.append(lev)
+            if psd:
+                certified = True
+                break
+            if theta >= -min_eig_tol / 2:  # :333-335: the eigenvalue computation did not reach the precision to escape
+                raise RuntimeError("escape direction computation did not converge to the desired precision")
+            escaped, info = s.lift(theta, v, gradient_tolerance, preconditioned_gradient_tolerance)
+            lev["escape_s"] = time.perf_counter() - t2
+            lev["escaped"] = escaped
+            lev["lift"] = info
+            if not escaped:  # :367-370: no descent found along the escape direction
+                break
+            ts = time.perf_counter()
+        X = s.get_X()
+    finally:
+        s.close()
+    if levels and gap is not None:
+        last = levels[-1]
+        last["suboptimality_gap_f"], last["n_eff"] = gap(X, last["certified"], last.pop("lambda_min"))
+    for lev in levels:
+        lev.pop("lambda_min", None)
+    cat = lambda parts, dt: np.concatenate(parts) if parts else np.zeros(0, dt)
+    return {"X": X, "rank": X.shape[0], "certified": certified, "theta": float(theta), "total_iters": int(total),
+            "suboptimality_gap_f": levels[-1]["suboptimality_gap_f"] if levels else None, "levels": levels,
+            "cost": cat(cost, float), "gradnorm": cat(gradnorm, float), "selected": cat(selected, np.int32),
+            "rank_trace": cat(rank, np.int32)}
+
+
+def multi_robot_staircase_session(ds, X0, num_robots=5, r_min=5, r_max=100, max_iters=1000, rgrad_tol=0.1,
+                                  min_eig_tol=1e-3, gradient_tolerance=1e-6, preconditioned_gradient_tolerance=1e-6,
+                                  acceleration=True, params=None, device=0, mode="rbcd++", robust=None, fixed=None):
+    """multi_robot_example's staircase (same arguments, same outputs) in ONE RbcdSession: the levels are run /
+    run_coloured, RbcdSession.certify and RbcdSession.lift, so the agents, their matrices and preconditioners -- and,
+    with robust=..., the weights and the GNC state -- live through every level, and the iterate stays on the device
+    until the last one.  r_max is capped by the session's largest rank, 16."""
+    _check_mode(mode)
+    d, n = ds.d, ds.n
+    ts = time.perf_counter()
+    # the certificate's analysis on another host thread while the agents iterate, as multi_robot_example starts it
+    prep = threading.Thread(target=lambda: cert_prepare(build_Q_pgo(ds), d, n, block=d + 1, device=device), daemon=True)
+    prep.start()
+    s = RbcdSession(ds, num_robots=num_robots, r=r_min, acceleration=acceleration and mode == "rbcd++", params=params,
+                    device=device, robust=robust, fixed_weight=fixed)
+    return _staircase_session(
+        s, X0, (d + 1) * n, r_min, min(r_max, 16), max_iters, rgrad_tol, min_eig_tol, gradient_tolerance,
+        preconditioned_gradient_tolerance, mode, ts, before_certify=prep.join,
+        gap=lambda X, psd, lmin: suboptimality_gap(X.shape[0], d, n, X, psd, min_eig_tol, lmin))
+
+
+def raslam_staircase_session(ra, X0, r_min=None, r_max=100, max_iters=1000, rgrad_tol=0.1, min_eig_tol=1e-3,
+                             gradient_tolerance=1e-4, preconditioned_gradient_tolerance=1e-4, acceleration=True,
+                             params=None, device=0, mode="rbcd++", robust=None, fixed=None):
+    """multi_robot_raslam_example's staircase (same arguments, same outputs, plus the traces) in ONE RaRbcdSession:
+    RaRbcdSession.certify and RaRbcdSession.lift between the levels' runs."""
+    from . import RaRbcdSession, ROptParameters
+    _check_mode(mode)
+    r_min = ra.d if r_min is None else r_min
+    if params is None:
+        params = ROptParameters(RTR_iterations=200, RTR_tCG_iterations=200, gradnorm_tol=1e-4)
+    ts = time.perf_counter()
+    s = RaRbcdSession(ra, r_min, acceleration=acceleration and mode == "rbcd++", params=params, device=device,
+                      robust=robust, fixed_weight=fixed)
+    return _staircase_session(s, X0, ra.k, r_min, min(r_max, 16), max_iters, rgrad_tol, min_eig_tol,
+                              gradient_tolerance, preconditioned_gradient_tolerance, mode, ts)
+
+
 def _check_mode(mode):
     if mode not in ("rbcd++", "coloured"):
         raise ValueError('mode must be "rbcd++" or "coloured"')

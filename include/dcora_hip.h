@@ -403,6 +403,36 @@ int dcora_rbcd_synchronize(dcora_rbcd_t s);
  * world_size > 1: DCORA_ERR_UNSUPPORTED (the ranks certify together: dcora_exchange_certify). */
 int dcora_rbcd_certify(dcora_rbcd_t s, double eta, int *certified, double *theta, double *lambda_min, double *v,
                        long long *matvecs, double *info8);
+/* The Riemannian staircase's step inside a live single-process session (ref examples/MultiRobotExample.cpp:352-366,
+ * examples/MultiRobotExample_RASLAM.cpp, src/QuadraticProblem.cpp:138-234).  The reference makes a new set of agents
+ * per level; here the session that dcora_rbcd_certify has refused goes from rank r to r + 1 in place: escapeSaddle of
+ * the whole-graph problem along (theta, v) -- what the certificate returned, v: k doubles on the host -- runs on the
+ * device from the session's iterate, which never crosses to the host, and the accepted point becomes the session's
+ * iterate as dcora_rbcd_set_X would make it (V = Y = XPrev = X, Nesterov sequences and round counters restarted, a
+ * robust session's X_initial, team statuses cleared).  Everything that does not depend on r stays: matrices,
+ * preconditioners, neighbours, colours, the robust weights with mu and the update count, the team with its parameters
+ * and loop-closure counts, the certificate's tables.  Poses handed over with dcora_rbcd_agent_update_neighbor are
+ * dropped, and a pointer obtained from dcora_rbcd_X_device_ptr is void after a lift that escaped.
+ * The search is src/QuadraticProblem.cpp:161-233's: the first trial step, in order, that lowers f with both gradient
+ * norms above their tolerances; else the trial of least f if it lowers f; else *escaped = 0 and the session is as it
+ * was.  The whole-graph problem's preconditioner is built on the first call and again after a weight change, of the
+ * matrix the session holds, with central_reg or, where that is negative, the kind's default: 0.1 on a pose graph, the
+ * reference's lambda_max / (1e6 - 1) rule (dcora_graph_precond_regularization) on a range-aided session.
+ * info8 (may be NULL): trials, accepted alpha, f before, f after, 1 if the preconditioner was built in this call, its
+ * ms, ms of the re-dimensioning, ms total.
+ * DCORA_ERR_UNSUPPORTED: world_size > 1, a ranked robust / team session, a session with an exchange.
+ * DCORA_ERR_BAD_ARG: r = 16; v or params NULL; v, theta or a tolerance not finite. */
+typedef struct {
+  double gradient_tolerance, preconditioned_gradient_tolerance;
+  int is_second_order;
+  double central_reg;
+} dcora_lift_params;
+int dcora_lift_params_default(dcora_lift_params *p); /* 1e-6, 1e-6, 0, -1 (= the kind's default) */
+int dcora_rbcd_lift(dcora_rbcd_t s, double theta, const double *v, const dcora_lift_params *p, int *escaped,
+                    double *info8);
+/* the session's current relaxation rank: the r of the staircase loop after the lifts so far (ref
+ * examples/MultiRobotExample.cpp:352-366, examples/MultiRobotExample_RASLAM.cpp, src/QuadraticProblem.cpp:138-234) */
+int dcora_rbcd_rank(dcora_rbcd_t s, int *r);
 /* Measurement hook (bench.py's `roofline`): while enabled, HIP events are recorded on the solver's stream around every
  * one-launch tCG run (k_tcg_run) of the session's agents; _read waits for the stream, returns {launches, sum of their
  * event times in us} since the last read and forgets them.  Not for timed regions: an event pair costs a few us. */
@@ -532,6 +562,12 @@ int dcora_ra_rbcd_get_X(dcora_ra_rbcd_t s, double *X);
 /* dcora_rbcd_certify on the merged range-aided problem (v: k doubles in the global RA ordering) */
 int dcora_ra_rbcd_certify(dcora_ra_rbcd_t s, double eta, int *certified, double *theta, double *lambda_min, double *v,
                           long long *matvecs, double *info8);
+/* dcora_rbcd_lift / dcora_rbcd_rank on a range-aided session (ref examples/MultiRobotExample.cpp:352-366,
+ * examples/MultiRobotExample_RASLAM.cpp, src/QuadraticProblem.cpp:138-234): v in the global RA ordering; every agent's
+ * X, V, Y, XPrev in its own ordering are re-dimensioned with the mirror */
+int dcora_ra_rbcd_lift(dcora_ra_rbcd_t s, double theta, const double *v, const dcora_lift_params *p, int *escaped,
+                       double *info8);
+int dcora_ra_rbcd_rank(dcora_ra_rbcd_t s, int *r);
 /* as dcora_rbcd_iterate / _evaluate / _run / _last_result; `selected` indexes the agents of dcora_ra_rbcd_info */
 int dcora_ra_rbcd_iterate(dcora_ra_rbcd_t s, int selected, double *cost2, double *gradnorm, double *block_norms,
                           int *next_selected);
