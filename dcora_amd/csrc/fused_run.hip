@@ -265,21 +265,47 @@ __global__ __launch_bounds__(kPcBlock) void k_tcg_run(TcgRunArgs a) {
 #endif
   const unsigned voff_t = threadIdx.x * 16u, voff_l = (unsigned)llane * 16u;
   // ---- once per run: the workgroup's rows of the inverse (registers), its matrix rows of Q (LDS), its poses ----
+  // Loads return in the order of their requests.  Everything the first product needs beside the rows -- the gradient
+  // image, the CSR entries of the workgroup's matrix rows, X, S, the own gradient element -- is requested AHEAD of the
+  // 32 sixteen-byte loads of the rows (128 KB per workgroup) and with no wait among the requests: the image and |r|^2
+  // are built while the rows are still in flight, and step u of the first product waits for mreg[u][*] only.  (Rows
+  // first, the image reached LDS only behind the rows, and the CSR staging and the row pointers paid three dependent
+  // round trips behind that: profiles/run_waits.txt.)  DCORA_RUN_ROWS_FIRST: the order before.
   double2 mreg[NS][NR];
+  auto load_rows = [&]() {
 #pragma unroll
-  for (int u = 0; u < NS; ++u)
+    for (int u = 0; u < NS; ++u)
 #pragma unroll
-    for (int q = 0; q < NR; ++q)
-      mreg[u][q] = pc_ld16(rs_m, voff_l, (unsigned)(((size_t)(j0 + q) * ldm + (size_t)(wave_u + kPcNW * u) * 128) * 8));
+      for (int q = 0; q < NR; ++q)
+        mreg[u][q] = pc_ld16(rs_m, voff_l, (unsigned)(((size_t)(j0 + q) * ldm + (size_t)(wave_u + kPcNW * u) * 128) * 8));
+  };
+  const int pbeg = a.Q.rp[j0], pend = a.Q.rp[j0 + nrow];
+#ifdef DCORA_RUN_ROWS_FIRST
+  load_rows();
+#endif
   double2 xg[kPcSB];
 #pragma unroll
   for (int u = 0; u < kPcSB; ++u) xg[u] = pc_ld16(rs_g, voff_t, (unsigned)u * kPcBlock * 16u);
-  const int pbeg = a.Q.rp[j0], pend = a.Q.rp[j0 + nrow];
+#ifdef DCORA_RUN_ROWS_FIRST
   for (int i = threadIdx.x; i < pend - pbeg; i += kPcBlock) {
     s_ci[i] = a.Q.ci[pbeg + i];
     s_v[i] = a.Q.v[pbeg + i];
   }
   const int myb = own ? a.Q.rp[j0 + lc] - pbeg : 0, mye = own ? a.Q.rp[j0 + lc + 1] - pbeg : 0;
+#else
+  // the CSR entries into registers, every thread kRunQCap / kPcBlock of them (a thread beyond the end loads the last
+  // entry again and stores nothing); the row pointers of a thread beyond the rows are those of the last row's end
+  constexpr int kStage = kRunQCap / kPcBlock;
+  int st_ci[kStage];
+  double st_v[kStage];
+#pragma unroll
+  for (int u = 0; u < kStage; ++u) {
+    const int i = min(u * kPcBlock + (int)threadIdx.x, pend - pbeg - 1);
+    st_ci[u] = a.Q.ci[pbeg + i];
+    st_v[u] = a.Q.v[pbeg + i];
+  }
+  const int rp_b = a.Q.rp[j0 + min(lc, nrow)], rp_e = a.Q.rp[j0 + min(lc + 1, nrow)];
+#endif
   Row<D> Y;
   ld_row<D>(X + o, r, tt, pact, Y);
   double S[D][D];
@@ -291,6 +317,20 @@ __global__ __launch_bounds__(kPcBlock) void k_tcg_run(TcgRunArgs a) {
       for (int b = 0; b < D; ++b) S[aa][b] = (g < npose) ? Sblk[(size_t)(pose0 + g) * D * D + aa + b * D] : 0.0;
   }
   double o_r = own ? grad[oown] : 0.0, o_eta = 0, o_Heta = 0, o_d = 0, o_h = 0;
+#ifndef DCORA_RUN_ROWS_FIRST
+  __builtin_amdgcn_sched_barrier(0);  // (no request of the rows moves ahead of the others)
+  load_rows();
+  __builtin_amdgcn_sched_barrier(0);
+  const int myb = own ? rp_b - pbeg : 0, mye = own ? rp_e - pbeg : 0;
+#pragma unroll
+  for (int u = 0; u < kStage; ++u) {
+    const int i = u * kPcBlock + (int)threadIdx.x;
+    if (i < pend - pbeg) {
+      s_ci[i] = st_ci[u];
+      s_v[i] = st_v[u];
+    }
+  }
+#endif
   // image geometry (one chunk: the host admits the form only where the whole residual fits)
   const int cpad = ((k + 127) / 128) * 128;
   const long Nc = (long)k * r;
@@ -747,15 +787,23 @@ int launch_tcg_run(hipStream_t st, const TcgOperands &o, int seq) {
                o.sync, o.ctl, o.hf, seq, fault};
 #ifdef DCORA_RUN_STAMPS
   {
-    static long long *buf = nullptr;
-    if (!buf) (void)hipHostMalloc((void **)&buf, 64 * sizeof(long long), hipHostMallocMapped);
+    // a ring of stamp blocks: launch c writes block c % kRing, and the host reads a block when it comes round again,
+    // kRing launches later (it enqueues ahead of the device: with one block it wiped the stamps of a run in flight,
+    // and which stamps it wiped depended on the build)
+    constexpr int kRing = 16;
+    static long long *ring = nullptr;
+    if (!ring && hipHostMalloc((void **)&ring, kRing * 64 * sizeof(long long), hipHostMallocMapped) == hipSuccess)
+      for (int i = 0; i < kRing * 64; ++i) ring[i] = 0;
     static int count = 0;
-    if (buf && count > 0) {  // the stamps of the run before (the stream is in order; racy by a run at most: a profile)
+    long long *buf = ring ? ring + (size_t)(count % kRing) * 64 : nullptr;
+    if (buf && count >= kRing) {  // the stamps of the run kRing launches back
       static double acc[64];
       static int n = 0;
       long long s0 = buf[0];
       constexpr int kShown = kRunStamp0 + 4 * kRunStampsPerIter;
-      if (buf[3] > s0 && buf[kShown - 1] > 0) {
+      bool whole = s0 > 0;
+      for (int i = 1; i < kShown; ++i) whole = whole && buf[i] >= buf[i - 1];
+      if (whole) {
         for (int i = 0; i < kShown; ++i) acc[i] += (double)(buf[i] - s0) * 0.01;
         ++n;
       }

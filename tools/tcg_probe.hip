@@ -10,8 +10,16 @@
 // Modes: 0 barriers only (no data); 1 + neighbour gather; 2 + all-gather by 8-byte agent-scope loads; 3 + all-gather by
 // 16-byte loads with sc1 (inline asm).  Spins are bounded (fail flag).  build:
 //   hipcc --offload-arch=gfx950 -O3 tools/tcg_probe.hip -o tools/bin/tcg_probe
+// usage: tcg_probe [depth [gap [modes]]]
+//   depth 1, 2, 4, 8: loads of the done word that lane 0 keeps in flight while it polls (all modes; 1: one at a time)
+//   gap:   s_sleep(1) slots between the first `depth` requests (they return in request order, so the spacing holds)
+//   modes: bit mask of the modes to run (default: all five)
+// It first prints the round trip of one coherent load of a done word, taken by lane 0 of each of the 250 workgroups
+// over 1000 dependent loads while the others do the same: what one poll costs, and what a deeper poll can save.
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cstdio>
+#include <cstdlib>
 #include <vector>
 
 typedef unsigned v4u __attribute__((ext_vector_type(4)));
@@ -22,7 +30,44 @@ struct Sync {
 };
 __device__ inline unsigned ldu(const unsigned *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-__device__ inline bool grid_step(const Sync &s, int phase, unsigned epoch, int *fail) {
+// Wave 0 waits for the done word `p` to reach `want` with K loads of it in flight: slot j holds the oldest load when
+// it is tested and is requested again at once, so the word is sampled K times per round trip.  The first kPollHead
+// rounds are straight-line code and every test and branch is scalar: there the compiler counts its waits,
+// vmcnt(K - 1) in front of every test.  (At the head of a LOOP it waits for vmcnt(0), the newest load: the loop's exits
+// are routed through its header.  So the loop behind the head drains the K loads once per round -- a step that waits
+// longer than kPollHead round trips is late anyway.)  false: 2 ms have passed.
+constexpr int kPollHead = 8;
+template <int K>
+__device__ inline bool poll_done(const unsigned *p, unsigned want, int gap) {
+  const unsigned t0 = (unsigned)wall_clock64();
+  unsigned v[K];
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+    v[j] = ldu(p);
+    if (j + 1 < K)
+      for (int g = 0; g < gap; ++g) __builtin_amdgcn_s_sleep(1);
+  }
+#pragma unroll
+  for (int s = 0; s < kPollHead; ++s)
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+      if ((unsigned)__builtin_amdgcn_readfirstlane((int)v[j]) >= want) return true;
+      v[j] = ldu(p);
+      __builtin_amdgcn_s_sleep(1);
+    }
+  for (unsigned spins = 0;;) {
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+      if ((unsigned)__builtin_amdgcn_readfirstlane((int)v[j]) >= want) return true;
+      v[j] = ldu(p);
+      __builtin_amdgcn_s_sleep(1);
+    }
+    if ((++spins & (64u / K - 1u)) == 0 && (unsigned)wall_clock64() - t0 > 200000u) return false;  // 2 ms at 100 MHz
+  }
+}
+
+template <int K>
+__device__ inline bool grid_step(const Sync &s, int phase, unsigned epoch, int *fail, int gap) {
   // every wave has drained its stores (s_waitcnt) before the barrier below
   __builtin_amdgcn_s_waitcnt(0);
   __syncthreads();
@@ -38,24 +83,33 @@ __device__ inline bool grid_step(const Sync &s, int phase, unsigned epoch, int *
         for (int c = 0; c < kCopies; ++c)
           __hip_atomic_store(s.done + ((size_t)phase * kCopies + c) * kStride, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    const long long t0 = wall_clock64();
-    const unsigned *p = s.done + ((size_t)phase * kCopies + (i % kCopies)) * kStride;
-    while (ldu(p) < epoch) {
-      __builtin_amdgcn_s_sleep(1);
-      if (wall_clock64() - t0 > 200000) {  // 2 ms at 100 MHz: somebody is not resident
-        *fail = 1;
-        ok = false;
-        break;
-      }
+  }
+  // the whole of wave 0 polls (every lane the same word: one request), so that all control flow of the poll is scalar
+  if (__builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6) == 0) {
+    const unsigned *p = s.done + ((size_t)phase * kCopies + (blockIdx.x % kCopies)) * kStride;
+    if (!poll_done<K>(p, epoch, gap)) {  // somebody is not resident
+      if (threadIdx.x == 0) *fail = 1;
+      ok = false;
     }
   }
   __syncthreads();
   return ok;
 }
 
-template <int MODE>
+// round trip of one coherent load of a done word: lane 0 of every workgroup, `n` loads one after the other
+__global__ __launch_bounds__(256) void k_round_trip(const unsigned *done, int n, float *us) {
+  if (threadIdx.x != 0) return;
+  const unsigned *p = done + (size_t)(blockIdx.x % kCopies) * kStride;
+  unsigned acc = 0;
+  const long long t0 = wall_clock64();
+  for (int i = 0; i < n; ++i) acc += ldu(p + (acc & 1u));  // (the next address waits for this value: both words are zero)
+  const long long t1 = wall_clock64();
+  us[blockIdx.x] = (float)(t1 - t0) * 0.01f / n + (acc == 12345u ? 1.f : 0.f);
+}
+
+template <int MODE, int K>
 __global__ __launch_bounds__(256) void k_persist(int iters, double *h, double *z, Sync s, unsigned epoch0, int *fail,
-                                                 double *out) {
+                                                 double *out, int gap) {
   __shared__ double s_img[kN];
   __shared__ double s_red[4];
   const int tid = threadIdx.x, wg = blockIdx.x;
@@ -72,7 +126,7 @@ __global__ __launch_bounds__(256) void k_persist(int iters, double *h, double *z
     }
     // (the value every reader must see this iteration: it + 1 in every slot -- a stale line would show the iteration before)
     if (tid < kPer) __hip_atomic_store(h + (size_t)wg * kPer + tid, (g != 0.123 ? 0.0 : 1.0) + it + 1.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (!grid_step(s, 0, epoch, fail)) return;
+    if (!grid_step<K>(s, 0, epoch, fail, gap)) return;
     // ---- phase B ----
     double acc = 0;
     if (MODE == 2) {
@@ -125,13 +179,13 @@ __global__ __launch_bounds__(256) void k_persist(int iters, double *h, double *z
     if (MODE >= 2) acc += s_img[(tid * 37) % kN];
     if (tid < kPer) __hip_atomic_store(z + (size_t)wg * kPer + tid, acc * 1e-9 + it, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     carry += acc;
-    if (!grid_step(s, 1, epoch, fail)) return;
+    if (!grid_step<K>(s, 1, epoch, fail, gap)) return;
   }
   if (carry == 12345.678) out[0] = carry;
 }
 
-template <int MODE>
-void run(const char *name, int iters) {
+template <int MODE, int K>
+void run(const char *name, int iters, int gap) {
   double *h, *z, *out;
   int *fail;
   (void)hipMalloc(&h, kN * 8);
@@ -153,13 +207,13 @@ void run(const char *name, int iters) {
   (void)hipEventCreate(&e0);
   (void)hipEventCreate(&e1);
   unsigned epoch = 0;
-  hipLaunchKernelGGL(k_persist<MODE>, dim3(kWG), dim3(256), 0, 0, iters, h, z, s, epoch, fail, out);
+  hipLaunchKernelGGL((k_persist<MODE, K>), dim3(kWG), dim3(256), 0, 0, iters, h, z, s, epoch, fail, out, gap);
   epoch += iters;
   (void)hipDeviceSynchronize();
   const int reps = 10;
   (void)hipEventRecord(e0);
   for (int r = 0; r < reps; ++r) {
-    hipLaunchKernelGGL(k_persist<MODE>, dim3(kWG), dim3(256), 0, 0, iters, h, z, s, epoch, fail, out);
+    hipLaunchKernelGGL((k_persist<MODE, K>), dim3(kWG), dim3(256), 0, 0, iters, h, z, s, epoch, fail, out, gap);
     epoch += iters;
   }
   (void)hipEventRecord(e1);
@@ -173,13 +227,47 @@ void run(const char *name, int iters) {
   (void)hipFree(h); (void)hipFree(z); (void)hipFree(out); (void)hipFree(fail); (void)hipFree(pool);
 }
 
-int main() {
-  for (int iters : {1, 7, 50}) {
-    run<0>("barriers only", iters);
-    run<1>("+ neighbour gather (17 x 40 doubles)", iters);
-    run<2>("+ all-gather of 80 KB, 8-byte agent loads", iters);
-    run<3>("+ all-gather of 80 KB, 16-byte sc1 loads", iters);
-    run<4>("+ all-gather, acquire fence + plain loads", iters);
+void round_trip() {
+  unsigned *pool;
+  float *us;
+  const size_t words = (size_t)kCopies * kStride + 1;
+  (void)hipExtMallocWithFlags((void **)&pool, words * 4, hipDeviceMallocFinegrained);
+  (void)hipMemset(pool, 0, words * 4);
+  (void)hipMalloc(&us, kWG * sizeof(float));
+  std::vector<float> h(kWG);
+  for (int rep = 0; rep < 3; ++rep) {
+    hipLaunchKernelGGL(k_round_trip, dim3(kWG), dim3(256), 0, 0, pool, 1000, us);
+    (void)hipMemcpy(h.data(), us, kWG * sizeof(float), hipMemcpyDeviceToHost);
+    std::sort(h.begin(), h.end());
+    printf("round trip of one coherent load of a done word, 250 workgroups polling: min %.3f median %.3f max %.3f us\n", h[0],
+           h[kWG / 2], h[kWG - 1]);
+  }
+  (void)hipFree(pool); (void)hipFree(us);
+}
+
+template <int K>
+void run_all(int gap, int modes) {
+  printf("poll depth %d, gap %d\n", K, gap);
+  for (int rep = 0; rep < 3; ++rep)  // (three times over: the spread of a figure is read off its repeats)
+    for (int iters : {1, 7, 50}) {
+      if (modes & 1) run<0, K>("barriers only", iters, gap);
+      if (modes & 2) run<1, K>("+ neighbour gather (17 x 40 doubles)", iters, gap);
+      if (modes & 4) run<2, K>("+ all-gather of 80 KB, 8-byte agent loads", iters, gap);
+      if (modes & 8) run<3, K>("+ all-gather of 80 KB, 16-byte sc1 loads", iters, gap);
+      if (modes & 16) run<4, K>("+ all-gather, acquire fence + plain loads", iters, gap);
+    }
+}
+
+int main(int argc, char **argv) {
+  const int depth = argc > 1 ? atoi(argv[1]) : 1, gap = argc > 2 ? atoi(argv[2]) : 0, modes = argc > 3 ? atoi(argv[3]) : 31;
+  round_trip();
+  if (depth == 1) run_all<1>(gap, modes);
+  else if (depth == 2) run_all<2>(gap, modes);
+  else if (depth == 4) run_all<4>(gap, modes);
+  else if (depth == 8) run_all<8>(gap, modes);
+  else {
+    fprintf(stderr, "depth must be 1, 2, 4 or 8\n");
+    return 2;
   }
   return 0;
 }
