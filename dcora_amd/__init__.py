@@ -728,6 +728,11 @@ class RbcdSession:
         return _session_lift(self, capi.lib().dcora_rbcd_lift, capi.lib().dcora_rbcd_rank, theta, v, gradient_tolerance,
                              preconditioned_gradient_tolerance, is_second_order, central_reg)
 
+    def reserve_rank(self, r_reserve):
+        """room for the ranks to come (dcora_rbcd_reserve_rank): an Exchange created on this session afterwards can
+        lift the job up to r_reserve; d <= r <= r_reserve <= 16, before the exchange exists"""
+        check(capi.lib().dcora_rbcd_reserve_rank(self.h, int(r_reserve)))
+
     def iterate(self, selected):
         c2, gn, nxt = C.c_double(), C.c_double(), C.c_int()
         bn = np.zeros(self.R)
@@ -948,6 +953,30 @@ class Exchange:
     def barrier(self):
         check(capi.lib().dcora_exchange_barrier(self.h))
 
+    def lift(self, theta, v, gradient_tolerance=1e-6, preconditioned_gradient_tolerance=1e-6, is_second_order=False):
+        """The staircase's step of the whole job (dcora_exchange_lift; SPMD: the same theta, v -- k numbers, as certify
+        returns them -- and tolerances on every rank): the session lift's search over trial points the ranks form
+        together, the preconditioned norm taken with the agents' own preconditioners -> (escaped, info).  escaped
+        False: the job is as it was.  The session's r follows its rank.  Needs room: reserve_rank on the session before
+        the exchange is created, or r_reserve of robust_ranked_session / ra_robust_ranked_session."""
+        v = None if v is None else np.ascontiguousarray(v, np.float64)
+        if v is not None and v.shape != (self.s.k,):
+            raise ValueError("lift needs the certificate's v: k numbers")
+        p = capi.LiftParams()
+        check(capi.lib().dcora_lift_params_default(C.byref(p)))
+        p.gradient_tolerance = gradient_tolerance
+        p.preconditioned_gradient_tolerance = preconditioned_gradient_tolerance
+        p.is_second_order = int(bool(is_second_order))
+        esc, i8, r = C.c_int(), np.zeros(8), C.c_int()
+        check(capi.lib().dcora_exchange_lift(self.h, float(theta), None if v is None else v.ctypes.data_as(C.c_void_p),
+                                             C.byref(p), C.byref(esc), i8.ctypes.data_as(C.c_void_p)))
+        rank_fn = capi.lib().dcora_ra_rbcd_rank if isinstance(self.s, RaRbcdSession) else capi.lib().dcora_rbcd_rank
+        check(rank_fn(self.s.h, C.byref(r)))
+        self.s.r = r.value
+        info = {"trials": int(i8[0]), "alpha": i8[1], "f_before": i8[2], "f_after": i8[3],
+                "redimension_ms": i8[6], "total_ms": i8[7]}
+        return bool(esc.value), info
+
     # ---- robust jobs (robust_ranked_session / ra_robust_ranked_session: m is then the pose-pose count) ----
     def update_weights(self, reset_to_initial=False):
         """Agent::updateMeasurementWeights of every agent on every rank (collective); returns the loop closures'
@@ -972,12 +1001,12 @@ class Exchange:
 
 
 def robust_ranked_session(ds, job_name, num_robots=5, r=5, robust=None, fixed_weight=None, rank=0, world_size=1,
-                          device=0, acceleration=True, restart_interval=30, params=None, stream=None):
+                          device=0, acceleration=True, restart_interval=30, params=None, stream=None, r_reserve=0):
     """(RbcdSession, Exchange) of one rank of a robust multi-rank job (dcora_rbcd_create_robust_ranks): the robust
     session of RbcdSession(robust=...) for the agents this rank hosts, and its exchange under job_name.  Every rank
     calls this with the same arguments but rank; weights change through the exchange (update_weights / set_weights /
     get_weights), collectively.  The session's get_weights() is this rank's view (NaN for measurements touching none
-    of its agents)."""
+    of its agents).  r_reserve: room for Exchange.lift up to that rank (dcora_rbcd_create_robust_ranks_reserved)."""
     from . import robust as rb
     robust = robust or rb.RobustCostParameters("GNC_TLS")
     o = _rbcd_options(num_robots, r, acceleration, restart_interval, params, rank, world_size, device, stream)
@@ -985,9 +1014,10 @@ def robust_ranked_session(ds, job_name, num_robots=5, r=5, robust=None, fixed_we
     dsh = ds.handle()
     hs, hx = C.c_void_p(), C.c_void_p()
     try:
-        check(capi.lib().dcora_rbcd_create_robust_ranks(dsh, C.byref(o), C.byref(robust.c),
-                                                        None if fx is None else fx.ctypes.data_as(C.c_void_p),
-                                                        job_name.encode(), C.byref(hs), C.byref(hx)))
+        check(capi.lib().dcora_rbcd_create_robust_ranks_reserved(dsh, C.byref(o), C.byref(robust.c),
+                                                                 None if fx is None else fx.ctypes.data_as(C.c_void_p),
+                                                                 int(r_reserve), job_name.encode(), C.byref(hs),
+                                                                 C.byref(hx)))
     finally:
         capi.lib().dcora_dataset_destroy(dsh)
     s = RbcdSession.__new__(RbcdSession)
@@ -996,17 +1026,18 @@ def robust_ranked_session(ds, job_name, num_robots=5, r=5, robust=None, fixed_we
 
 
 def ra_robust_ranked_session(ra, job_name, r, robust=None, fixed_weight=None, rank=0, world_size=1, device=0,
-                             acceleration=True, restart_interval=30, params=None):
+                             acceleration=True, restart_interval=30, params=None, r_reserve=0):
     """(RaRbcdSession, Exchange) of one rank of a robust multi-rank range-aided job (dcora_ra_rbcd_create_robust_ranks):
     robust_ranked_session's contract with the robust session of RaRbcdSession(robust=...) for the agents this rank
     hosts.  Every rank calls this with the same arguments but rank; the job's weights (pose-pose order) change through
     the exchange (update_weights / set_weights / get_weights), collectively.  The session's get_weights() is this
-    rank's view (NaN for pose-pose measurements touching none of its agents)."""
+    rank's view (NaN for pose-pose measurements touching none of its agents).  r_reserve: room for Exchange.lift up to
+    that rank (dcora_ra_rbcd_create_robust_ranks_reserved)."""
     from . import robust as rb
     s = RaRbcdSession(ra, r, acceleration=acceleration, restart_interval=restart_interval, params=params,
                       device=device, rank=rank, world_size=world_size,
                       robust=robust or rb.RobustCostParameters("GNC_TLS"), fixed_weight=fixed_weight,
-                      _ranked_job=job_name)
+                      _ranked_job=job_name, _r_reserve=r_reserve)
     hx, s._exchange_handle = s._exchange_handle, None
     return s, Exchange(s, job_name, _handle=hx)
 
@@ -1016,7 +1047,7 @@ class RaRbcdSession:
     (ref examples/MultiRobotExample_RASLAM.cpp); X is the merged r x k matrix in the RA ordering"""
 
     def __init__(self, ra, r, acceleration=True, restart_interval=30, params=None, device=0, rank=0, world_size=1,
-                 robust=None, fixed_weight=None, _ranked_job=None):
+                 robust=None, fixed_weight=None, _ranked_job=None, _r_reserve=0):
         """robust: a robust.RobustCostParameters -> a session whose pose-pose weights update in place (update_weights /
         set_weights / get_weights / robust_info, as RbcdSession's); it starts with weight 1 on every loop closure
         (ra.loop_closures()) whose fixed_weight flag (one per pose-pose measurement, default none) is off"""
@@ -1043,9 +1074,10 @@ class RaRbcdSession:
                 check(capi.lib().dcora_ra_rbcd_create_robust(dsh, C.byref(o), C.byref(robust.c), fxp, C.byref(self.h)))
             else:  # (ra_robust_ranked_session: made together with its exchange, whose handle goes to _exchange_handle)
                 self._exchange_handle = C.c_void_p()
-                check(capi.lib().dcora_ra_rbcd_create_robust_ranks(dsh, C.byref(o), C.byref(robust.c), fxp,
-                                                                   _ranked_job.encode(), C.byref(self.h),
-                                                                   C.byref(self._exchange_handle)))
+                check(capi.lib().dcora_ra_rbcd_create_robust_ranks_reserved(dsh, C.byref(o), C.byref(robust.c), fxp,
+                                                                            int(_r_reserve), _ranked_job.encode(),
+                                                                            C.byref(self.h),
+                                                                            C.byref(self._exchange_handle)))
         finally:
             capi.lib().dcora_radataset_destroy(dsh)
         n = C.c_int()
@@ -1084,6 +1116,10 @@ class RaRbcdSession:
         default to multi_robot_raslam_example's."""
         return _session_lift(self, capi.lib().dcora_ra_rbcd_lift, capi.lib().dcora_ra_rbcd_rank, theta, v,
                              gradient_tolerance, preconditioned_gradient_tolerance, is_second_order, central_reg)
+
+    def reserve_rank(self, r_reserve):
+        """RbcdSession.reserve_rank on a range-aided session (dcora_ra_rbcd_reserve_rank)"""
+        check(capi.lib().dcora_ra_rbcd_reserve_rank(self.h, int(r_reserve)))
 
     def _eval(self, fn, *first):
         c2, gn, nxt = C.c_double(), C.c_double(), C.c_int()

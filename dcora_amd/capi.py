@@ -173,6 +173,10 @@ SIGNATURES = {
     "dcora_rbcd_lift": (C.c_int, [_vp, C.c_double, _dp, C.POINTER(LiftParams), _PI, _vp]),
     "dcora_rbcd_rank": (C.c_int, [_vp, _PI]),
     "dcora_ra_rbcd_lift": (C.c_int, [_vp, C.c_double, _dp, C.POINTER(LiftParams), _PI, _vp]),
+    "dcora_exchange_lift": (C.c_int, [_vp, C.c_double, _vp, C.POINTER(LiftParams), _PI, _vp]),
+    "dcora_rbcd_reserve_rank": (C.c_int, [_vp, C.c_int]),
+    "dcora_ra_rbcd_reserve_rank": (C.c_int, [_vp, C.c_int]),
+    "dcora_debug_lift_images": (C.c_int, [C.c_int, C.c_int, _dp, C.c_int, _dp, _vp, C.c_int, _dp, _dp]),
     "dcora_ra_rbcd_rank": (C.c_int, [_vp, _PI]),
     "dcora_rbcd_profile_tcg_runs": (C.c_int, [_vp, C.c_int]),
     "dcora_rbcd_profile_tcg_read": (C.c_int, [_vp, _dp]),
@@ -183,6 +187,8 @@ SIGNATURES = {
     "dcora_rbcd_robust_info": (C.c_int, [_vp, _PD, _PI]),
     "dcora_rbcd_create_robust_ranks": (C.c_int, [_vp, C.POINTER(RbcdOptions), C.POINTER(RobustParams), _vp, C.c_char_p,
                                                  C.POINTER(_vp), C.POINTER(_vp)]),
+    "dcora_rbcd_create_robust_ranks_reserved": (C.c_int, [_vp, C.POINTER(RbcdOptions), C.POINTER(RobustParams), _vp,
+                                                          C.c_int, C.c_char_p, C.POINTER(_vp), C.POINTER(_vp)]),
     "dcora_team_params_default": (None, [C.POINTER(TeamParams)]),
     "dcora_team_ready_to_terminate": (C.c_int, [C.POINTER(TeamParams), C.c_int, C.c_int, C.c_int, C.c_double, C.c_int,
                                                 C.c_int, C.c_int, _PI]),
@@ -270,6 +276,8 @@ SIGNATURES = {
     "dcora_ra_rbcd_robust_info": (C.c_int, [_vp, _PD, _PI]),
     "dcora_ra_rbcd_create_robust_ranks": (C.c_int, [_vp, C.POINTER(RbcdOptions), C.POINTER(RobustParams), _vp,
                                                     C.c_char_p, C.POINTER(_vp), C.POINTER(_vp)]),
+    "dcora_ra_rbcd_create_robust_ranks_reserved": (C.c_int, [_vp, C.POINTER(RbcdOptions), C.POINTER(RobustParams), _vp,
+                                                             C.c_int, C.c_char_p, C.POINTER(_vp), C.POINTER(_vp)]),
     "dcora_radataset_rank_edges": (C.c_int, [_vp, C.c_int, C.c_int, _ip, _ip]),
     "dcora_ra_max_translation_distance": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _PD]),
     "dcora_radataset_loop_closure_stats": (C.c_int, [_vp, C.c_int, _ip]),

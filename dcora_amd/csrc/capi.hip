@@ -1089,10 +1089,19 @@ int dcora_rbcd_create_robust(dcora_dataset_t ds, const dcora_rbcd_options *opt, 
 int dcora_rbcd_create_robust_ranks(dcora_dataset_t ds, const dcora_rbcd_options *opt, const dcora_robust_params *robust,
                                    const int *fixed_weight, const char *job_name, dcora_rbcd_t *session,
                                    dcora_exchange_t *ex) {
+  return dcora_rbcd_create_robust_ranks_reserved(ds, opt, robust, fixed_weight, 0, job_name, session, ex);
+}
+// ... with room for the ranks to come (SessionCore::reserve_rank between the two)
+int dcora_rbcd_create_robust_ranks_reserved(dcora_dataset_t ds, const dcora_rbcd_options *opt,
+                                            const dcora_robust_params *robust, const int *fixed_weight, int r_reserve,
+                                            const char *job_name, dcora_rbcd_t *session, dcora_exchange_t *ex) {
   return abi_call({ds, opt, robust, job_name, session, ex}, [&]() -> int {
+    if (reserve_rank_check(ds->ds.d, opt->r, r_reserve, true))
+      return bad("rbcd robust: r_reserve is 0 (no reserve) or d <= r <= r_reserve <= 16");
     std::unique_ptr<dcora_rbcd_s> h(new dcora_rbcd_s);
     int rc = h->s.init_robust(ds->ds, *opt, *robust, fixed_weight, true);
     if (rc) return rc;
+    if (r_reserve && (rc = h->s.reserve_rank(r_reserve))) return rc;
     std::unique_ptr<dcora_exchange_s> x(new dcora_exchange_s);
     rc = x->e.init(&h->s, job_name, ds->ds.meas.size());
     if (rc) return rc;
@@ -1395,6 +1404,42 @@ int dcora_rbcd_rank(dcora_rbcd_t s, int *r) {
     return (int)DCORA_OK;
   });
 }
+int dcora_rbcd_reserve_rank(dcora_rbcd_t s, int r_reserve) {
+  return abi_call({s}, [&] { return s->s.reserve_rank(r_reserve); });
+}
+// the agent form of k_lift_images on host arrays (tests/test_lift_images_gpu.py)
+int dcora_debug_lift_images(int r, int ka, const double *Xa, int kglobal, const double *v, const int *cols, int col0,
+                            double *Xplus, double *dir) {
+  return abi_call({Xa, v, Xplus, dir}, [&]() -> int {
+    if (r < 1 || r + 1 > kMaxRank || ka < 1 || kglobal < 1) return bad("dcora_debug_lift_images: 1 <= r <= 15, ka >= 1");
+    for (int j = 0; j < ka; ++j) {
+      const long c = cols ? (long)cols[j] : (long)col0 + j;
+      if (c < 0 || c >= kglobal) return bad("dcora_debug_lift_images: a column outside the global v");
+    }
+    const size_t nx = (size_t)r * ka, ni = (size_t)(r + 1) * ka;
+    DevBuf<double> X, V, P, D;
+    DevBuf<int> Cm;
+    DCORA_HIP(X.alloc(nx));
+    DCORA_HIP(V.alloc((size_t)kglobal));
+    DCORA_HIP(P.alloc(ni));
+    DCORA_HIP(D.alloc(ni));
+    DCORA_HIP(hipMemcpy(X.p, Xa, sizeof(double) * nx, hipMemcpyHostToDevice));
+    DCORA_HIP(hipMemcpy(V.p, v, sizeof(double) * (size_t)kglobal, hipMemcpyHostToDevice));
+    if (cols) {
+      DCORA_HIP(Cm.alloc((size_t)ka));
+      DCORA_HIP(hipMemcpy(Cm.p, cols, sizeof(int) * (size_t)ka, hipMemcpyHostToDevice));
+    }
+    // (NaN where the kernel must write: an element it skips shows)
+    DCORA_HIP(hipMemset(P.p, 0xff, sizeof(double) * ni));
+    DCORA_HIP(hipMemset(D.p, 0xff, sizeof(double) * ni));
+    launch_lift_images_agent(nullptr, r, ka, X.p, V.p, cols ? Cm.p : nullptr, col0, P.p, D.p);
+    DCORA_HIP(hipGetLastError());
+    DCORA_HIP(hipDeviceSynchronize());
+    DCORA_HIP(hipMemcpy(Xplus, P.p, sizeof(double) * ni, hipMemcpyDeviceToHost));
+    DCORA_HIP(hipMemcpy(dir, D.p, sizeof(double) * ni, hipMemcpyDeviceToHost));
+    return (int)DCORA_OK;
+  });
+}
 int dcora_rbcd_X_device_ptr(dcora_rbcd_t s, double **X_dev) {
   return abi_call({s, X_dev}, [&] {
     *X_dev = s->s.Xg.p;
@@ -1549,6 +1594,12 @@ int dcora_exchange_set_X(dcora_exchange_t ex, const double *X) {
 }
 int dcora_exchange_gather_X(dcora_exchange_t ex, double *X) {
   return abi_call({ex, X}, [&] { return ex->e.gather_X(X); });
+}
+// the staircase's step of the whole job (ref examples/MultiRobotExample.cpp:352-366, src/QuadraticProblem.cpp:138-234);
+// a NULL v is refused like a non-finite one, on every rank alike
+int dcora_exchange_lift(dcora_exchange_t ex, double theta, const double *v, const dcora_lift_params *params,
+                        int *escaped, double *info8) {
+  return abi_call({ex, params, escaped}, [&] { return ex->e.lift(theta, v, *params, escaped, info8); });
 }
 int dcora_exchange_host_selftest(const char *job_name, int rank, int world_size, int num_agents, int rounds,
                                  double *checksum) {
@@ -1746,6 +1797,9 @@ int dcora_ra_rbcd_lift(dcora_ra_rbcd_t s, double theta, const double *v, const d
   return abi_call({s, v, p, escaped}, [&] { return s->s.lift(theta, v, *p, escaped, info8); });
 }
 // (ref examples/MultiRobotExample.cpp:352-366, examples/MultiRobotExample_RASLAM.cpp, src/QuadraticProblem.cpp:138-234)
+int dcora_ra_rbcd_reserve_rank(dcora_ra_rbcd_t s, int r_reserve) {
+  return abi_call({s}, [&] { return s->s.reserve_rank(r_reserve); });
+}
 int dcora_ra_rbcd_rank(dcora_ra_rbcd_t s, int *r) {
   return abi_call({s, r}, [&] {
     *r = s->s.r;
@@ -1768,10 +1822,19 @@ int dcora_ra_rbcd_create_robust(dcora_radataset_t ds, const dcora_rbcd_options *
 int dcora_ra_rbcd_create_robust_ranks(dcora_radataset_t ds, const dcora_rbcd_options *opt,
                                       const dcora_robust_params *robust, const int *fixed_weight, const char *job_name,
                                       dcora_ra_rbcd_t *session, dcora_exchange_t *ex) {
+  return dcora_ra_rbcd_create_robust_ranks_reserved(ds, opt, robust, fixed_weight, 0, job_name, session, ex);
+}
+int dcora_ra_rbcd_create_robust_ranks_reserved(dcora_radataset_t ds, const dcora_rbcd_options *opt,
+                                               const dcora_robust_params *robust, const int *fixed_weight,
+                                               int r_reserve, const char *job_name, dcora_ra_rbcd_t *session,
+                                               dcora_exchange_t *ex) {
   return abi_call({ds, opt, robust, job_name, session, ex}, [&]() -> int {
+    if (reserve_rank_check(ds->ds.d, opt->r, r_reserve, true))
+      return bad("ra_rbcd robust: r_reserve is 0 (no reserve) or d <= r <= r_reserve <= 16");
     std::unique_ptr<dcora_ra_rbcd_s> h(new dcora_ra_rbcd_s);  // (destroyed on every failure below)
     int rc = h->s.init_robust(ds->ds, *opt, *robust, fixed_weight, true);
     if (rc) return rc;
+    if (r_reserve && (rc = h->s.reserve_rank(r_reserve))) return rc;
     std::unique_ptr<dcora_exchange_s> x(new dcora_exchange_s);
     rc = x->e.init(&h->s, job_name, ds->ds.pose_pose.size());
     if (rc) return rc;

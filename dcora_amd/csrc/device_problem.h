@@ -317,6 +317,12 @@ class DeviceProblem {
   // f before, f after.  The host form is upload + this + download.
   int escape_saddle_dev(const double *Xprev, const double *v, double theta, double gtol, double pgtol,
                         bool second_order, int *success, double stats[4]);
+  // One trial of that search in the halves it is enqueued in, from the images in X0 ([X; 0]) and eta ([0; v^T]):
+  // X1 = Retract(X0, alpha eta); then, into out4 on the device, <X1 Q, X1>, <X1, G>, |rgrad(X1)|^2 and
+  // |Proj(rgrad(X1) M^-1)|^2 with this problem's preconditioner.  escape_saddle_dev runs them back to back; the ranks
+  // of a job (Exchange::lift) exchange the trial points' public columns and form every agent's G in between.
+  void escape_trial_point(double alpha);
+  void escape_trial_scalars(double *out4);
 
   // ---- device-resident solve: X0.p holds the start point.  Returns without synchronising: the result lies in X0 / X1
   // as ctl->cur picks (RTR) or in X1 (RGD); fetch_result() finishes a pending solve and returns its statistics.

@@ -3,6 +3,7 @@
 
 #include "device_problem.h"
 #include "env.h"
+#include "escape_rule.h"
 #include "device_chol.h"
 #include "host_threads.h"
 #include "precond_cache.h"
@@ -1311,40 +1312,46 @@ int DeviceProblem::escape_saddle_dev(const double *Xprev, const double *v, doubl
   int rc = eval_dev(X0.p, &FX, nullptr);
   if (rc) return rc;
   if (stats) stats[2] = stats[3] = FX;
-  const double alpha_min = 1e-6;
-  // ref :165-169: SE-Sync's second-order step when asked for, else Algorithm 7 of the DC2-PGO report
-  double alpha = second_order ? std::max(16 * alpha_min, 100 * gtol / std::fabs(theta)) : 1.0;
-  std::vector<double> alphas, fvals;
-  while (alpha >= alpha_min) {
-    launch_retract(st, m, buf1(X0.p), eta.p, alpha, buf1(X1.p), 0, buf1(RG0.p), nullptr, nullptr, Gate{});
-    enqueue_egrad(X1.p, EG1.p, pA.p);
-    launch_rgrad(st, m, buf1(X1.p), buf1(EG1.p), buf1(RG1.p), buf1(S1.p), 0, pB.p, Gate{});
-    enqueue_precond(X1.p, RG1.p, z.p);
-    launch_dot(st, nelem(), z.p, z.p, p3.p);
-    launch_sum_partials(st, pA.p, npA(), 2, 2, scal.p);
-    launch_sum_partials(st, pB.p, npPose(), 1, 1, scal.p + 2);
-    launch_sum_partials(st, p3.p, npVec(), 1, 1, scal.p + 3);
+  EscapeSearch search(theta, gtol, pgtol, second_order, FX);
+  while (search.more()) {
+    escape_trial_point(search.alpha);
+    escape_trial_scalars(scal.p);
     double s[4];
     rc = download(scal.p, s, 4);
     if (rc) return rc;
-    const double FXt = 0.5 * s[0] + s[1], gn = std::sqrt(s[2]), pgn = std::sqrt(s[3]);
-    alphas.push_back(alpha);
-    fvals.push_back(FXt);
-    if (stats) stats[0] = (double)alphas.size();
-    if (FXt < FX && gn > gtol && pgn > pgtol) {
+    const double FXt = 0.5 * s[0] + s[1];
+    const bool accepted = search.offer(FXt, std::sqrt(s[2]), std::sqrt(s[3]));
+    if (stats) stats[0] = (double)search.trials();
+    if (accepted) {
       *success = 1;
-      if (stats) stats[1] = alpha, stats[3] = FXt;
+      if (stats) stats[1] = search.alphas.back(), stats[3] = FXt;
       return DCORA_OK;
     }
-    alpha /= 2;
   }
-  const size_t idx = std::min_element(fvals.begin(), fvals.end()) - fvals.begin();
-  if (fvals[idx] < FX) {
-    launch_retract(st, m, buf1(X0.p), eta.p, alphas[idx], buf1(X1.p), 0, buf1(RG0.p), nullptr, nullptr, Gate{});
+  const int idx = search.fallback();
+  if (idx >= 0) {
+    escape_trial_point(search.alphas[(size_t)idx]);
     *success = 1;
-    if (stats) stats[1] = alphas[idx], stats[3] = fvals[idx];
+    if (stats) stats[1] = search.alphas[(size_t)idx], stats[3] = search.fvals[(size_t)idx];
   }
   return DCORA_OK;
+}
+
+// One trial of the search, in the two halves its callers enqueue (between them the ranks of a job exchange the public
+// columns of their trial points and form G): X1 = Retract(X0, alpha eta) ...
+void DeviceProblem::escape_trial_point(double alpha) {
+  launch_retract(st, m, buf1(X0.p), eta.p, alpha, buf1(X1.p), 0, buf1(RG0.p), nullptr, nullptr, Gate{});
+}
+// ... and its four scalars into out4 (device): <X1 Q, X1>, <X1, G>, |rgrad(X1)|^2, |Proj(rgrad(X1) M^-1)|^2 -- each
+// summed from its partial slots in slot order by one workgroup (no atomics: the same bits whatever the schedule)
+void DeviceProblem::escape_trial_scalars(double *out4) {
+  enqueue_egrad(X1.p, EG1.p, pA.p);
+  launch_rgrad(st, m, buf1(X1.p), buf1(EG1.p), buf1(RG1.p), buf1(S1.p), 0, pB.p, Gate{});
+  enqueue_precond(X1.p, RG1.p, z.p);
+  launch_dot(st, nelem(), z.p, z.p, p3.p);
+  launch_sum_partials(st, pA.p, npA(), 2, 2, out4);
+  launch_sum_partials(st, pB.p, npPose(), 1, 1, out4 + 2);
+  launch_sum_partials(st, p3.p, npVec(), 1, 1, out4 + 3);
 }
 
 int DeviceProblem::time_qapply(int reps, double *avg_ms, double *bytes) {

@@ -79,6 +79,27 @@ class Exchange {
   // behind an evaluation heartbeat, every third round a tick of non-adjacent agents without one; every rank collects,
   // settles and decides by team_rules.h; checksum folds every status and both decisions of every round
   int host_selftest_team(const char *job_name, int rank, int world, int R, int rounds, int skew_us, double *checksum);
+  // The Riemannian staircase's step across the ranks (SessionCore::lift's contract carried over the job; ref
+  // examples/MultiRobotExample.cpp:352-366, src/QuadraticProblem.cpp:138-234).  SPMD: every rank calls it with the same
+  // theta, v (k doubles, global ordering, as certify returns it) and parameters.  The search is EscapeSearch
+  // (escape_rule.h), one statement for this and the single-process lift.  Per trial every rank retracts the blocks of
+  // its hosted agents at rank r + 1 (SessionCore::lift_trial_point), the public columns travel with the ordinary post
+  // and wait of all agents at r + 1 rows, and the trial's three scalars -- 2 f, |rgrad|^2, |P grad|^2 -- are each
+  // rank's sums over its agents in agent order, added over the ranks in rank order (allreduce_sum): the same bits
+  // and so the same branch on every rank.  f([X; 0]) is the same evaluation of the current iterate.
+  // The preconditioned norm is NOT escapeSaddle's: no rank holds the whole graph, so
+  //   |P grad|^2 := sum_a |Proj(rgrad_a M_a^-1)|^2,  M_a^-1 the image agent a's solves use (its own regularisation);
+  // p.central_reg is ignored.  A one-rank exchange takes this same path.
+  // Escaped: every hosted problem is at r + 1, the kind's buffers are re-dimensioned and the accepted point is adopted
+  // on every rank at once, between barriers as set_X does, with set_X's consequences; matrices, preconditioners,
+  // weights, mu and its update count, team parameters and counts, and this exchange with its transport stay.  No
+  // escape, or an error on any rank: every problem is back at r, the session's mirror was never written (the trials
+  // ran in a mirror of their own).  Refused alike on every rank, the job untouched: r = 16, v null or not finite,
+  // theta or a tolerance not finite (DCORA_ERR_BAD_ARG); r + 1 beyond max(r at creation, reserve)
+  // (DCORA_ERR_UNSUPPORTED).  info8 (may be null): trials, accepted alpha, f before, f after, 0, 0, ms of the
+  // re-dimensioning, ms total.
+  int lift(double theta, const double *v, const dcora_lift_params &p, int *escaped, double *info8);
+  int rank_capacity() const { return r_cap_; }  // the largest rank the job's segment and halo slots hold
   int barrier(double timeout_s = 120.0);
   int gather_X(double *Xh);
   // Agent::setX of every agent on every rank: sequence numbers restart with the Nesterov sequences
@@ -125,6 +146,7 @@ class Exchange {
   bool device_wait_ = true;      // the scatter kernel polls the flag itself (no host hop between post and scatter)
   DevBuf<unsigned> arrive2_;     // last-workgroup counters of the scatter kernels
   int R_ = 0;
+  int r_cap_ = 0;                  // max(the session's rank at creation, its reserve): what slot_ and the X area hold
   size_t slot_ = 0;                // doubles per agent slot
   DevBuf<double> halo_;            // [parity][agent][slot] + self-test area (fine-grained device memory)
   bool halo_finegrained_ = false;

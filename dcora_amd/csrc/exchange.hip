@@ -350,7 +350,7 @@ int Exchange::barrier(double timeout_s) {
 
 int Exchange::init(SessionCore *s, const char *job_name, size_t weights) {
   s_ = s;
-  s->exchange_attached = true;  // (the segment and the halo slots below are sized by the session's rank: no lift)
+  s->exchange_attached = true;  // (from here on the session lifts through this exchange only, within its reserve)
   pose_ = dynamic_cast<RbcdSession *>(s);
   rank = s->opt.rank;
   world = s->opt.world_size;
@@ -371,7 +371,10 @@ int Exchange::init(SessionCore *s, const char *job_name, size_t weights) {
     if (v.hosted != (owner_[a] == rank)) return fail("agent-to-rank map out of step with the session", DCORA_ERR_BAD_ARG);
   }
   n_hosted_ = (int)hosted.size();
-  slot_ = align_up(maxcols * (size_t)s->r, 16);
+  // (slots and the X area by the larger of the session's rank and its reserve: room for Exchange::lift)
+  r_cap_ = SegmentLayout::rank_capacity(s->r, s->reserve_r);
+  lay_ = SegmentLayout::for_job(world, R, maxcols, s->r, s->reserve_r, (size_t)s->num_cols(), weights);
+  slot_ = lay_.slot;
   dests_.assign(R, {});
   needed_.assign(R, 0);
   for (int a = 0; a < R; ++a) {
@@ -387,7 +390,7 @@ int Exchange::init(SessionCore *s, const char *job_name, size_t weights) {
     if ((int)dests_[a].size() > kMaxDst) return fail("an agent has neighbours on more than 8 other ranks", DCORA_ERR_UNSUPPORTED);
   seq_.assign(R, 0);
 
-  int rc = map_segment(job_name, (size_t)s->r * (size_t)s->num_cols(), weights);
+  int rc = open_segment(job_name);  // (of lay_: the job's layout, above)
   if (rc) return rc;
   {
     const hipError_t e = hipHostRegister(map_, lay_.total, hipHostRegisterMapped | hipHostRegisterPortable);

@@ -26,6 +26,15 @@ constexpr int kMaxAgents = 64;
 constexpr uint32_t kShmMagic = 0x44434f52u;  // "DCOR"
 constexpr int kProbeDoubles = 512;           // the link check's payload: 4 KB
 
+// What dcora_rbcd_reserve_rank / dcora_ra_rbcd_reserve_rank and the *_reserved creators accept for a session of
+// dimension d at rank r: 0 (no reserve; the creators only) or d <= r <= r_reserve <= 16, the largest rank the kernels
+// are built for.  The codes are DCORA_OK and DCORA_ERR_BAD_ARG, stated as numbers: this header includes no other.
+constexpr int kMaxRank = 16;
+inline int reserve_rank_check(int d, int r, int r_reserve, bool zero_is_none) {
+  if (zero_is_none && r_reserve == 0) return 0;
+  return d <= r && r <= r_reserve && r_reserve <= kMaxRank ? 0 : 1;
+}
+
 // ---- the records of the segment -------------------------------------------------------------------------------------
 struct alignas(64) ShmFlag {
   volatile uint64_t seq;
@@ -101,6 +110,18 @@ struct SegmentLayout {
     off_x = take(4096, sizeof(double) * x_doubles);
     off_w = take(64, sizeof(double) * w_doubles);
     total = take(4096, 0);
+  }
+
+  // The segment of a job whose sessions are at rank r and have reserved reserve_r (SessionCore::reserve_r; 0: none):
+  // the agent slots (maxcols public columns at the most) and the X area (k columns) are sized by the larger of the
+  // two, so that the job can lift up to it without another segment; every other area does not depend on the rank.
+  static int rank_capacity(int r, int reserve_r) { return r > reserve_r ? r : reserve_r; }
+  static size_t slot_doubles(size_t maxcols, int r, int reserve_r) {
+    return (maxcols * (size_t)rank_capacity(r, reserve_r) + 15) / 16 * 16;
+  }
+  static SegmentLayout for_job(int world_, int R_, size_t maxcols, int r, int reserve_r, size_t k, size_t w_doubles_) {
+    return SegmentLayout(world_, R_, slot_doubles(maxcols, r, reserve_r), (size_t)rank_capacity(r, reserve_r) * k,
+                         w_doubles_);
   }
 
   template <class T>

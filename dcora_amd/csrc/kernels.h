@@ -242,6 +242,10 @@ void launch_scatter_cols(hipStream_t st, int r, int ncols, const int *dst_col, c
 // Both images escapeSaddle starts from (ref src/QuadraticProblem.cpp:148-160), from X (r x k column-major) and v (k):
 // Xplus (r + 1) x k with column j = [x_j; 0], dir (r + 1) x k with column j = [0; v_j]  (lift.hip)
 void launch_lift_images(hipStream_t st, int r, long k, const double *X, const double *v, double *Xplus, double *dir);
+// The agent form: X is one agent's block (r x k, its own ordering), v the GLOBAL eigenvector, read through the agent's
+// column map -- cols[j] when cols is given (a range-aided agent's scattered columns), else col0 + j (a contiguous range)
+void launch_lift_images_agent(hipStream_t st, int r, long k, const double *X, const double *v, const int *cols, long col0,
+                              double *Xplus, double *dir);
 // out[2a] = |A[:, cs[a]:cs[a+1]]|^2, out[2a+1] = <A, B> over the same columns (B may be null)
 void launch_block_dots(hipStream_t st, int r, int nagents, const int *col_start, const double *A, const double *B,
                        double *out);

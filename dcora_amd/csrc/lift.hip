@@ -1,8 +1,12 @@
 // The two images a saddle escape into the next rank starts from (ref src/QuadraticProblem.cpp:148-160), formed on the
-// device so that the point never crosses to the host: from X, r x k column-major, and the eigenvector v (k)
-//   Xplus (r + 1) x k : column j = [x_j; 0]      the point, one zero row appended
-//   dir   (r + 1) x k : column j = [0;  v_j]     the descent direction, v in the new row
+// device so that the point never crosses to the host: from X, r x k column-major, and the eigenvector v
+//   Xplus (r + 1) x k : column j = [x_j; 0]          the point, one zero row appended
+//   dir   (r + 1) x k : column j = [0;  v_col(j)]    the descent direction, v in the new row
 // Both orderings (SE: pose by pose, RA: rotations | spheres | translations | landmarks) are the same column walk.
+// The whole-graph form reads v where it reads X (col(j) = j).  The agent form (a rank of a job lifts the blocks of the
+// agents it hosts, Exchange::lift) reads the GLOBAL v through the agent's column map: a contiguous range that starts at
+// col0 (a pose-graph agent), or the agent's list of global columns (a range-aided agent: its rotations, spheres,
+// translations and landmarks lie scattered through the global RA ordering).
 #include "kernels.h"
 
 #include <cstdint>
@@ -18,7 +22,8 @@ namespace {
 // consecutive pairs.  An odd (r + 1) k leaves one last element on its own: it is stored narrow, and nothing of a column
 // k is read.  Images whose base is not 16-byte aligned take narrow stores throughout.
 __global__ __launch_bounds__(kBlock) void k_lift_images(int r, long k, const double *__restrict__ X,
-                                                        const double *__restrict__ v, double *__restrict__ Xplus,
+                                                        const double *__restrict__ v, const int *__restrict__ cols,
+                                                        long col0, double *__restrict__ Xplus,
                                                         double *__restrict__ dir, int wide) {
   const int rn = r + 1;
   const long total = (long)rn * k, npairs = (total + 1) / 2;
@@ -31,7 +36,7 @@ __global__ __launch_bounds__(kBlock) void k_lift_images(int r, long k, const dou
       if (t < r)
         x[h] = X[j * r + t];
       else
-        w[h] = v[j];
+        w[h] = v[cols ? (long)cols[j] : col0 + j];
     }
     if (have == 2 && wide) {
       *reinterpret_cast<double2 *>(Xplus + 2 * p) = make_double2(x[0], x[1]);
@@ -47,11 +52,17 @@ __global__ __launch_bounds__(kBlock) void k_lift_images(int r, long k, const dou
 
 }  // namespace
 
-void launch_lift_images(hipStream_t st, int r, long k, const double *X, const double *v, double *Xplus, double *dir) {
+void launch_lift_images_agent(hipStream_t st, int r, long k, const double *X, const double *v, const int *cols, long col0,
+                              double *Xplus, double *dir) {
   if (k <= 0) return;
   const int wide = (((uintptr_t)Xplus | (uintptr_t)dir) & 15) == 0 ? 1 : 0;
   const long npairs = ((long)(r + 1) * k + 1) / 2;
-  hipLaunchKernelGGL(k_lift_images, dim3(vec_grid(npairs)), dim3(kBlock), 0, st, r, k, X, v, Xplus, dir, wide);
+  hipLaunchKernelGGL(k_lift_images, dim3(vec_grid(npairs)), dim3(kBlock), 0, st, r, k, X, v, cols, col0, Xplus, dir,
+                     wide);
+}
+
+void launch_lift_images(hipStream_t st, int r, long k, const double *X, const double *v, double *Xplus, double *dir) {
+  launch_lift_images_agent(st, r, k, X, v, nullptr, 0, Xplus, dir);
 }
 
 }  // namespace dcora

@@ -112,6 +112,7 @@ class RaRbcdSession : public SessionCore {
   int phase_evaluate_dev(double *out_dev) override;
   AgentCore &agent_core(int a) override { return agents[(size_t)a]; }
   long num_cols() const override { return k; }
+  int dim() const override { return d; }
   DeviceProblem *central_problem() override { return central.get(); }
   const HostCsr *central_pattern() const override { return robust ? &robust->central_pat : nullptr; }
   const HostCsr *central_live_pattern() const override { return robust ? &robust->live_pat : nullptr; }
@@ -132,6 +133,9 @@ class RaRbcdSession : public SessionCore {
   int lift_default_reg(const HostCsr &Qc, double *reg) override;
   int lift_buffers(int r_new) override;
   int lift_adopt(const double *X_dev) override { return adopt_X(X_dev, hipMemcpyDeviceToDevice); }
+  // the collective lift's: an agent's block is its own X, its columns the `own` list (scattered through the RA ordering)
+  void lift_agent_view(AgentCore &a, const double **X_a, const int **cols, long *col0) override;
+  int lift_scatter_block(AgentCore &a, int rows, const double *block, double *mirror) override;
   int gather_agents();         // every hosted agent's X from the mirror, V = Y = XPrev = X (enqueued)
   int scatter(RaAgentDev &a);  // my X into the global mirror
   int solve(RaAgentDev &a, const double *start, double **result);

@@ -452,6 +452,19 @@ int RaRbcdSession::lift_buffers(int r_new) {
   return DCORA_OK;
 }
 
+void RaRbcdSession::lift_agent_view(AgentCore &core, const double **X_a, const int **cols, long *col0) {
+  const RaAgentDev &a = static_cast<const RaAgentDev &>(core);
+  *X_a = a.X.p;
+  *cols = a.own.p;
+  *col0 = 0;
+}
+
+int RaRbcdSession::lift_scatter_block(AgentCore &core, int rows, const double *block, double *mirror) {
+  const RaAgentDev &a = static_cast<const RaAgentDev &>(core);
+  launch_scatter_cols(st, rows, a.k, a.own.p, block, mirror);
+  return DCORA_OK;
+}
+
 int RaRbcdSession::adopt_X(const double *X, hipMemcpyKind kind) {
   DCORA_HIP(hipSetDevice(opt.device));
   const size_t B = sizeof(double) * (size_t)r * k;

@@ -124,6 +124,7 @@ class RbcdSession : public SessionCore {
 
   AgentCore &agent_core(int a) override { return agents[(size_t)a]; }
   long num_cols() const override { return (long)(d + 1) * n; }
+  int dim() const override { return d; }
   DeviceProblem *central_problem() override { return central.get(); }
   const HostCsr *central_pattern() const override { return robust ? &robust->central_pat : nullptr; }
   int cert_block() const override { return d + 1; }
@@ -143,6 +144,9 @@ class RbcdSession : public SessionCore {
   int lift_default_reg(const HostCsr &Qc, double *reg) override;
   int lift_buffers(int r_new) override;
   int lift_adopt(const double *X_dev) override { return adopt_X(X_dev, hipMemcpyDeviceToDevice); }
+  // the collective lift's: an agent's block is its contiguous range of the mirror
+  void lift_agent_view(AgentCore &a, const double **X_a, const int **cols, long *col0) override;
+  int lift_scatter_block(AgentCore &a, int rows, const double *block, double *mirror) override;
   int update_nonselected_agent(AgentDev &a, bool restart);
   int update_selected_agent(AgentDev &a, bool restart);
   int restart_step(AgentDev &a);

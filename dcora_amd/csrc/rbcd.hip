@@ -388,6 +388,20 @@ int RbcdSession::lift_buffers(int r_new) {
   return DCORA_OK;
 }
 
+void RbcdSession::lift_agent_view(AgentCore &core, const double **X_a, const int **cols, long *col0) {
+  const AgentDev &a = static_cast<const AgentDev &>(core);
+  *X_a = Xg.p + (size_t)a.col0 * r;
+  *cols = nullptr;
+  *col0 = a.col0;
+}
+
+int RbcdSession::lift_scatter_block(AgentCore &core, int rows, const double *block, double *mirror) {
+  const AgentDev &a = static_cast<const AgentDev &>(core);
+  DCORA_HIP(hipMemcpyAsync(mirror + (size_t)a.col0 * rows, block, sizeof(double) * (size_t)rows * (d + 1) * a.n,
+                           hipMemcpyDeviceToDevice, st));
+  return DCORA_OK;
+}
+
 // ---- robust sessions -------------------------------------------------------------------------------------------
 // Agent::initializeRobustOptimization for every agent (ref src/Agent.cpp:1332-1346): weight 1 on every loop closure
 // whose weight is not fixed.  A loop closure is every measurement but odometry, i.e. but p2 == p1 + 1 inside one agent

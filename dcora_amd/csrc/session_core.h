@@ -118,11 +118,43 @@ class SessionCore {
   //      and round counters restarted, X_initial of a robust session, team statuses cleared.  Handed neighbour caches
   //      are dropped; device pointers into the session's buffers handed out earlier (X_device_ptr) are void.
   // Refused, the session untouched: a rank of a job, a ranked robust / team session or a session an exchange was created
-  // on (DCORA_ERR_UNSUPPORTED: the exchange's halo layout is sized by r); r = 16, v null or not finite, theta or a
-  // tolerance not finite (DCORA_ERR_BAD_ARG).  info8 (may be null): trials, accepted alpha, f before, f after, 1 if the
-  // central preconditioner was built in this call, its ms, ms of the re-dimensioning, ms total.
+  // on (DCORA_ERR_UNSUPPORTED: those lift together, through their exchange -- Exchange::lift); r = 16, v null or not
+  // finite, theta or a tolerance not finite (DCORA_ERR_BAD_ARG).  info8 (may be null): trials, accepted alpha, f before,
+  // f after, 1 if the central preconditioner was built in this call, its ms, ms of the re-dimensioning, ms total.
   int lift(double theta, const double *v, const dcora_lift_params &p, int *escaped, double *info8);
   bool exchange_attached = false;  // an Exchange was created on this session
+
+  // ---- room for the ranks to come: an exchange created on this session sizes its halo slots, its staged slots and its
+  // gather_X area by max(r, reserve_r), so that the job can lift up to that rank (Exchange::lift).  0: a job that will
+  // never lift, laid out exactly as before.  Legal (d <= r <= r_reserve <= 16, else DCORA_ERR_BAD_ARG) until an
+  // exchange exists (then DCORA_ERR_UNSUPPORTED: its segment is mapped and its IPC handles are open).
+  int reserve_r = 0;
+  int reserve_rank(int r_reserve);
+  virtual int dim() const = 0;  // d
+
+  // ---- the session's half of the collective lift (Exchange::lift, where the flow stands): the escape of
+  // SessionCore::lift carried by the hosted agents' own problems, each at rank r + 1 on its block of
+  // [X; 0] + alpha [0; v^T], against a trial mirror of r + 1 rows that holds the hosted blocks and, after the exchange's
+  // post and wait, the neighbours' public columns.  The session itself -- mirror, sequences, counters -- is not
+  // touched before lift_trial_commit.
+  //   begin:   every stream synchronised, every hosted agent's problem re-ranked, v on the device, the two images of
+  //            every hosted block (k_lift_images, agent form) in its problem's X0 / eta
+  //   point:   X1 = Retract(X0, alpha eta) of every hosted block and its columns into the trial mirror; *mirror: what
+  //            the exchange posts from and waits into.  alpha = 0 is the current iterate through the same kernel: f
+  //            before and f of a trial then come from one arithmetic path, and a direction of zeros gives trial
+  //            points that equal it bit for bit -- no trial "lowers" f by the rounding of a projection
+  //   scalars: G_a from the trial mirror, then per hosted agent <X_a Q_aa, X_a> + <X_a, G_a>, |rgrad_a|^2 and
+  //            |Proj(rgrad_a M_a^-1)|^2 with the agent's own preconditioner; ONE host wait; out3: their sums over the
+  //            hosted agents in agent order (2 f's share, |rgrad|^2's, |P grad|^2's)
+  //   commit:  the central problem of a one-rank job re-ranked, the kind's buffers re-dimensioned (lift_buffers), the
+  //            trial mirror adopted as set_X adopts a point (lift_adopt); *redim_ms: what that took plus the
+  //            agents' re-ranks of begin -- the re-dimensioning as SessionCore::lift's info8[6] counts it
+  //   abort:   every re-ranked problem back at r (the error that led here stays the one reported)
+  int lift_trial_begin(const double *v_host);
+  int lift_trial_point(double alpha, double **mirror);
+  int lift_trial_scalars(double out3[3]);
+  int lift_trial_commit(double *redim_ms);
+  void lift_trial_abort();
   virtual DeviceProblem *central_problem() = 0;                        // null on a rank of a multi-rank job
   virtual const HostCsr *central_pattern() const { return nullptr; }  // host copy of its pattern, where one is kept
   // the stored entries the current weights give, where the session certifies over those alone (session_cert.h)
@@ -190,6 +222,19 @@ class SessionCore {
   virtual int lift_buffers(int r_new) = 0;
   // set_X of a point that lies on the device (r x num_cols(), the mirror's ordering): everything set_X leaves
   virtual int lift_adopt(const double *X_dev) = 0;
+  // ... and to the collective lift: a hosted agent's block (r x k_a, its own ordering) and where its columns lie in the
+  // global ordering -- *cols when the kind keeps a list (range-aided agents), else the contiguous range from *col0;
+  virtual void lift_agent_view(AgentCore &a, const double **X_a, const int **cols, long *col0) = 0;
+  // a hosted agent's block of `rows` rows into its columns of a mirror of `rows` rows (enqueued on st)
+  virtual int lift_scatter_block(AgentCore &a, int rows, const double *block, double *mirror) = 0;
+  struct LiftTrial {
+    int r_old = 0;
+    bool central_reranked = false;
+    double rerank_ms = 0;            // what the hosted agents' re-ranks took in lift_trial_begin
+    DevBuf<double> mirror, v, scal;  // (r + 1) x num_cols(), num_cols(), 4 per hosted agent
+    std::vector<int> hosted;         // in agent order
+  };
+  std::unique_ptr<LiftTrial> lift_trial_;  // between lift_trial_begin and commit / abort
 
   // the three things a session kind supplies to the tick
   virtual void tick_begins() {}  // (the set is valid: per-tick resets)

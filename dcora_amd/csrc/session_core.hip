@@ -7,6 +7,8 @@
 #include <cmath>
 #include <cstring>
 
+#include "escape_rule.h"
+#include "exchange_slots.h"
 #include "host_graph.h"
 #include "host_threads.h"
 
@@ -57,19 +59,17 @@ int SessionCore::lift(double theta, const double *v, const dcora_lift_params &p,
   if (info8) std::fill(info8, info8 + 8, 0.0);
   DeviceProblem *central = opt.world_size == 1 ? central_problem() : nullptr;
   if (!central || weights_ranked() || (team && team->ranked) || exchange_attached) {
-    set_last_error(tag + "serves single-process sessions without an exchange (the exchange's halo layout is sized by "
-                   "the rank); a collective lift across the ranks of a job is not available");
+    set_last_error(tag + "serves single-process sessions without an exchange; the ranks of a job, and a session an "
+                   "exchange was created on, lift together through dcora_exchange_lift");
     return DCORA_ERR_UNSUPPORTED;
   }
-  if (r + 1 > 16) {
+  if (r + 1 > kMaxRank) {
     set_last_error(tag + "the session is at rank 16, the largest the kernels are built for");
     return DCORA_ERR_BAD_ARG;
   }
   const long k = num_cols();
-  bool finite = v && std::isfinite(theta) && std::isfinite(p.gradient_tolerance) &&
-                std::isfinite(p.preconditioned_gradient_tolerance) && std::isfinite(p.central_reg);
-  for (long j = 0; finite && j < k; ++j) finite = std::isfinite(v[j]);
-  if (!finite) {
+  if (!lift_args_finite(theta, v, k, p.gradient_tolerance, p.preconditioned_gradient_tolerance) ||
+      !std::isfinite(p.central_reg)) {
     set_last_error(tag + "v must be k finite numbers, theta, the tolerances and central_reg finite");
     return DCORA_ERR_BAD_ARG;
   }
@@ -145,6 +145,158 @@ int SessionCore::lift(double theta, const double *v, const dcora_lift_params &p,
   DCORA_HIP(hipStreamSynchronize(st));
   *escaped = 1;
   if (info8) info8[6] = ms_since(te), info8[7] = ms_since(t0);
+  return DCORA_OK;
+}
+
+int SessionCore::reserve_rank(int r_reserve) {
+  const std::string tag = std::string(tag_) + " reserve_rank: ";
+  if (exchange_attached) {
+    set_last_error(tag + "an exchange exists on the session: its segment is mapped and its halo buffers are shared "
+                   "(reserve before dcora_exchange_create / _create_ra, or create with a *_ranks_reserved entry)");
+    return DCORA_ERR_UNSUPPORTED;
+  }
+  if (reserve_rank_check(dim(), r, r_reserve, false)) {
+    set_last_error(tag + "need d <= r <= r_reserve <= 16");
+    return DCORA_ERR_BAD_ARG;
+  }
+  reserve_r = r_reserve;
+  return DCORA_OK;
+}
+
+// ---- the session's half of the collective lift (session_core.h) -----------------------------------------------------
+int SessionCore::lift_trial_begin(const double *v_host) {
+  const std::string tag = std::string(tag_) + " lift: ";
+  DCORA_HIP(hipSetDevice(opt.device));
+  for (int a = 0; a < R; ++a)
+    if (agent_core(a).own_st) DCORA_HIP(hipStreamSynchronize(agent_core(a).own_st));
+  DCORA_HIP(hipStreamSynchronize(st));
+  std::unique_ptr<LiftTrial> t(new LiftTrial);
+  t->r_old = r;
+  const int r_new = r + 1;
+  const size_t k = (size_t)num_cols();
+  for (int a = 0; a < R; ++a) {
+    if (!agent_core(a).hosted) continue;
+    if (!agent_core(a).prob->has_precond) {
+      set_last_error(tag + "agent " + std::to_string(a) + " has no preconditioner");
+      return DCORA_ERR_NO_PRECONDITIONER;
+    }
+    t->hosted.push_back(a);
+  }
+  if (hipSuccess != t->mirror.alloc((size_t)r_new * k) || hipSuccess != t->v.alloc(k) ||
+      hipSuccess != t->scal.alloc(4 * std::max<size_t>(t->hosted.size(), 1))) {
+    (void)hipGetLastError();
+    set_last_error(tag + "out of device memory");
+    return DCORA_ERR_HIP;
+  }
+  // (columns no hosted agent owns and no neighbour publishes are read by nobody: zero, as a fresh mirror has them)
+  DCORA_HIP(hipMemsetAsync(t->mirror.p, 0, sizeof(double) * (size_t)r_new * k, st));
+  DCORA_HIP(hipMemcpyAsync(t->v.p, v_host, sizeof(double) * k, hipMemcpyHostToDevice, st));
+  DCORA_HIP(hipStreamSynchronize(st));  // (the caller's pageable v has been read)
+  lift_trial_ = std::move(t);
+  const auto tr = std::chrono::steady_clock::now();
+  for (size_t i = 0; i < lift_trial_->hosted.size(); ++i) {
+    AgentCore &a = agent_core(lift_trial_->hosted[i]);
+    int rc = a.prob->rerank(r_new);
+    if (rc) {
+      // (what has been re-ranked so far goes back; the agents behind never left r)
+      const std::string keep = dcora_last_error();
+      for (size_t q = 0; q < i; ++q) (void)agent_core(lift_trial_->hosted[q]).prob->rerank(r);
+      set_last_error(keep);
+      lift_trial_.reset();
+      return rc;
+    }
+  }
+  lift_trial_->rerank_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tr).count();
+  for (int id : lift_trial_->hosted) {
+    AgentCore &a = agent_core(id);
+    const double *Xa = nullptr;
+    const int *cols = nullptr;
+    long col0 = 0;
+    lift_agent_view(a, &Xa, &cols, &col0);
+    DeviceProblem &pb = *a.prob;
+    launch_lift_images_agent(st, r, pb.m.k, Xa, lift_trial_->v.p, cols, col0, pb.X0.p, pb.eta.p);
+  }
+  DCORA_HIP(hipGetLastError());
+  return DCORA_OK;
+}
+
+int SessionCore::lift_trial_point(double alpha, double **mirror) {
+  LiftTrial &t = *lift_trial_;
+  DCORA_HIP(hipSetDevice(opt.device));
+  for (int id : t.hosted) {
+    AgentCore &a = agent_core(id);
+    DeviceProblem &pb = *a.prob;
+    pb.escape_trial_point(alpha);
+    const int rc = lift_scatter_block(a, t.r_old + 1, pb.X1.p, t.mirror.p);
+    if (rc) return rc;
+  }
+  DCORA_HIP(hipGetLastError());
+  *mirror = t.mirror.p;
+  return DCORA_OK;
+}
+
+int SessionCore::lift_trial_scalars(double out3[3]) {
+  LiftTrial &t = *lift_trial_;
+  DCORA_HIP(hipSetDevice(opt.device));
+  const int r_new = t.r_old + 1;
+  for (size_t i = 0; i < t.hosted.size(); ++i) {
+    AgentCore &a = agent_core(t.hosted[i]);
+    DeviceProblem &pb = *a.prob;
+    launch_spmm(st, r_new, a.coupling.view(), buf1(t.mirror.p), 0, nullptr, buf1(pb.G.p), 0, nullptr, Gate{});
+    pb.has_G = true;
+    pb.escape_trial_scalars(t.scal.p + 4 * i);
+  }
+  DCORA_HIP(hipGetLastError());
+  std::vector<double> h(4 * std::max<size_t>(t.hosted.size(), 1), 0.0);
+  if (!t.hosted.empty())
+    DCORA_HIP(hipMemcpyAsync(h.data(), t.scal.p, sizeof(double) * 4 * t.hosted.size(), hipMemcpyDeviceToHost, st));
+  DCORA_HIP(hipStreamSynchronize(st));  // the trial's one wait (a rank without agents still drains its scatters)
+  out3[0] = out3[1] = out3[2] = 0;
+  for (size_t i = 0; i < t.hosted.size(); ++i) {  // agent order
+    out3[0] += h[4 * i] + h[4 * i + 1];
+    out3[1] += h[4 * i + 2];
+    out3[2] += h[4 * i + 3];
+  }
+  return DCORA_OK;
+}
+
+void SessionCore::lift_trial_abort() {
+  if (!lift_trial_) return;
+  const std::string keep = dcora_last_error();
+  (void)hipSetDevice(opt.device);
+  for (int id : lift_trial_->hosted) (void)agent_core(id).prob->rerank(lift_trial_->r_old);
+  if (lift_trial_->central_reranked) (void)central_problem()->rerank(lift_trial_->r_old);
+  lift_trial_.reset();
+  set_last_error(keep);
+}
+
+int SessionCore::lift_trial_commit(double *redim_ms) {
+  const auto te = std::chrono::steady_clock::now();
+  LiftTrial &t = *lift_trial_;
+  const int r_new = t.r_old + 1;
+  DCORA_HIP(hipSetDevice(opt.device));
+  int rc = DCORA_OK;
+  if (DeviceProblem *central = central_problem()) {  // (a one-rank job keeps its whole-graph evaluation)
+    rc = central->rerank(r_new);
+    if (rc) return rc;
+    t.central_reranked = true;
+  }
+  DevBuf<double> xq;
+  if (cert_.built && hipSuccess != xq.alloc((size_t)r_new * (size_t)num_cols())) {
+    set_last_error(std::string(tag_) + " lift: out of device memory");
+    return DCORA_ERR_HIP;
+  }
+  rc = lift_buffers(r_new);
+  if (rc) return rc;
+  if (cert_.built) cert_.XQ = std::move(xq);
+  // (the session is at r + 1 from here on: nothing is left for lift_trial_abort to take back)
+  const std::unique_ptr<LiftTrial> done(std::move(lift_trial_));
+  rc = lift_adopt(done->mirror.p);
+  if (rc) return rc;
+  DCORA_HIP(hipStreamSynchronize(st));
+  // (what SessionCore::lift counts in the same slot: the agents' re-ranks, made when the trials began, with the rest)
+  if (redim_ms)
+    *redim_ms = done->rerank_ms + std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - te).count();
   return DCORA_OK;
 }
 

@@ -9,6 +9,7 @@
         certified: done;  else escapeSaddle into rank r + 1       (:352-366)   dcora_problem_escape_saddle
 
 Everything numerical runs on the device; this file is the control flow of the example program."""
+import sys
 import threading
 import time
 
@@ -452,6 +453,119 @@ def gnc_ra_ranks(ra, X0, r, robust=None, num_weight_updates=10, inner_iters=30, 
                      run=lambda iters: exchange_run(ex, max_iters=iters, rgrad_tol=rgrad_tol),
                      reweight=lambda u: _counts(ex.update_weights()), read=lambda: (ex.gather_X(), ex.get_weights()),
                      close=lambda: (ex.close(), s.close()), store=ra.set_pose_pose_weights)
+
+
+class _RanksJob:
+    """one rank's (session, exchange) of a job behind the calls _staircase_session makes on a session: run /
+    run_coloured across the ranks, Exchange.certify with the global Q on rank 0 (q_now(): the job's current matrix,
+    called on every rank because reading a robust job's weights is collective) and Exchange.lift"""
+
+    def __init__(self, s, ex, k, rank, q_now):
+        self.s, self.ex, self.k, self.rank, self.q_now = s, ex, k, rank, q_now
+
+    @property
+    def r(self):
+        return self.s.r
+
+    def set_X(self, X):
+        self.ex.set_X(X)
+
+    def get_X(self):
+        return self.ex.gather_X()
+
+    def run(self, max_iters, rgrad_tol):
+        return exchange_run(self.ex, max_iters=max_iters, rgrad_tol=rgrad_tol)
+
+    def run_coloured(self, max_sweeps, rgrad_tol):
+        return self.ex.run_coloured(max_sweeps=max_sweeps, rgrad_tol=rgrad_tol)
+
+    def certify(self, eta):
+        Q = self.q_now()
+        cert, theta, lmin, v, mv, dist = self.ex.certify(Q if self.rank == 0 else None, eta, self.k)
+        return cert, theta, v, lmin, {"matvecs": mv, "distributed": dist}
+
+    def lift(self, theta, v, gradient_tolerance, preconditioned_gradient_tolerance):
+        return self.ex.lift(theta, v, gradient_tolerance, preconditioned_gradient_tolerance)
+
+    def close(self):
+        # (reached from a `finally`: after an error of the exchange the barrier raises as well -- the exchange and the
+        # session are closed all the same, and the first error stays the one the caller sees)
+        try:
+            if sys.exc_info()[0] is None:
+                self.ex.barrier()
+        finally:
+            self.ex.close()
+            self.s.close()
+
+
+def multi_robot_staircase_ranks(ds, X0, num_robots=5, r_min=5, r_max=100, max_iters=1000, rgrad_tol=0.1,
+                                min_eig_tol=1e-3, gradient_tolerance=1e-6, preconditioned_gradient_tolerance=1e-6,
+                                acceleration=True, params=None, device=0, mode="rbcd++", robust=None, fixed=None, rank=0,
+                                world_size=1, job_name="staircase"):
+    """multi_robot_staircase_session on one rank of a multi-rank job (SPMD: every rank calls it with the same arguments
+    but rank; ref examples/MultiRobotExample.cpp:223-370): per level exchange_run (or the coloured sweeps),
+    Exchange.certify and Exchange.lift, robust or plain -- the job never leaves the library between its levels.  The
+    sessions reserve min(r_max, 16) rows before their exchange is created.  The same outputs on every rank.
+    With robust=..., ds.vals[:, -1] (the weights) is updated in place before every certificate, as
+    multi_robot_gnc_ranks leaves them."""
+    from . import Exchange, robust_ranked_session
+    _check_mode(mode)
+    d, n = ds.d, ds.n
+    r_top = max(min(r_max, 16), r_min)
+    ts = time.perf_counter()
+    accel = acceleration and mode == "rbcd++"
+    if robust is None:
+        s = RbcdSession(ds, num_robots=num_robots, r=r_min, acceleration=accel, params=params, device=device, rank=rank,
+                        world_size=world_size)
+        s.reserve_rank(r_top)
+        ex = Exchange(s, job_name)
+        Q = build_Q_pgo(ds) if rank == 0 else None
+        q_now = lambda: Q
+    else:
+        s, ex = robust_ranked_session(ds, job_name, num_robots=num_robots, r=r_min, robust=robust, fixed_weight=fixed,
+                                      rank=rank, world_size=world_size, device=device, acceleration=accel, params=params,
+                                      r_reserve=r_top)
+
+        def q_now():
+            ds.vals[:, -1] = ex.get_weights()
+            return build_Q_pgo(ds) if rank == 0 else None
+    return _staircase_session(
+        _RanksJob(s, ex, (d + 1) * n, rank, q_now), X0, (d + 1) * n, r_min, r_top, max_iters, rgrad_tol, min_eig_tol,
+        gradient_tolerance, preconditioned_gradient_tolerance, mode, ts,
+        gap=lambda X, psd, lmin: suboptimality_gap(X.shape[0], d, n, X, psd, min_eig_tol, lmin))
+
+
+def raslam_staircase_ranks(ra, X0, r_min=None, r_max=100, max_iters=1000, rgrad_tol=0.1, min_eig_tol=1e-3,
+                           gradient_tolerance=1e-4, preconditioned_gradient_tolerance=1e-4, acceleration=True,
+                           params=None, device=0, mode="rbcd++", robust=None, fixed=None, rank=0, world_size=1,
+                           job_name="ra_staircase"):
+    """raslam_staircase_session on one rank of a multi-rank range-aided job (SPMD, as multi_robot_staircase_ranks; ref
+    examples/MultiRobotExample_RASLAM.cpp): exchange_run, Exchange.certify and Exchange.lift per level.  With
+    robust=..., ra keeps the job's current pose-pose weights (set_pose_pose_weights before every certificate), as
+    gnc_ra_ranks leaves them."""
+    from . import Exchange, RaRbcdSession, ROptParameters, ra_robust_ranked_session
+    _check_mode(mode)
+    r_min = ra.d if r_min is None else r_min
+    r_top = max(min(r_max, 16), r_min)
+    if params is None:
+        params = ROptParameters(RTR_iterations=200, RTR_tCG_iterations=200, gradnorm_tol=1e-4)
+    ts = time.perf_counter()
+    accel = acceleration and mode == "rbcd++"
+    if robust is None:
+        s = RaRbcdSession(ra, r_min, acceleration=accel, params=params, device=device, rank=rank, world_size=world_size)
+        s.reserve_rank(r_top)
+        ex = Exchange(s, job_name)
+        q_now = lambda: ra.Q
+    else:
+        s, ex = ra_robust_ranked_session(ra, job_name, r_min, robust=robust, fixed_weight=fixed, rank=rank,
+                                         world_size=world_size, device=device, acceleration=accel, params=params,
+                                         r_reserve=r_top)
+
+        def q_now():
+            ra.set_pose_pose_weights(ex.get_weights())
+            return ra.Q
+    return _staircase_session(_RanksJob(s, ex, ra.k, rank, q_now), X0, ra.k, r_min, r_top, max_iters, rgrad_tol,
+                              min_eig_tol, gradient_tolerance, preconditioned_gradient_tolerance, mode, ts)
 
 
 def multi_robot_team_ranks(ds, X0, num_robots=5, r=5, robust=None, team=None, acceleration=True, params=None,

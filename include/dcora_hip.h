@@ -420,7 +420,8 @@ int dcora_rbcd_certify(dcora_rbcd_t s, double eta, int *certified, double *theta
  * reference's lambda_max / (1e6 - 1) rule (dcora_graph_precond_regularization) on a range-aided session.
  * info8 (may be NULL): trials, accepted alpha, f before, f after, 1 if the preconditioner was built in this call, its
  * ms, ms of the re-dimensioning, ms total.
- * DCORA_ERR_UNSUPPORTED: world_size > 1, a ranked robust / team session, a session with an exchange.
+ * DCORA_ERR_UNSUPPORTED: world_size > 1, a ranked robust / team session, a session with an exchange -- those lift
+ * together through dcora_exchange_lift (below).
  * DCORA_ERR_BAD_ARG: r = 16; v or params NULL; v, theta or a tolerance not finite. */
 typedef struct {
   double gradient_tolerance, preconditioned_gradient_tolerance;
@@ -433,6 +434,20 @@ int dcora_rbcd_lift(dcora_rbcd_t s, double theta, const double *v, const dcora_l
 /* the session's current relaxation rank: the r of the staircase loop after the lifts so far (ref
  * examples/MultiRobotExample.cpp:352-366, examples/MultiRobotExample_RASLAM.cpp, src/QuadraticProblem.cpp:138-234) */
 int dcora_rbcd_rank(dcora_rbcd_t s, int *r);
+/* Room for the ranks to come (a job that will climb the staircase through dcora_exchange_lift): an exchange created on
+ * the session afterwards sizes its halo slots, its staged slots and its gather_X area by max(r, r_reserve) instead of
+ * r, so that the job can lift up to r_reserve without another segment; nothing else of the layout, no allocation of
+ * the session and no launch depends on it, and a session that never calls this is laid out exactly as before.  Legal
+ * between the session's creation and dcora_exchange_create.  Every rank of a job reserves the same rank.
+ * DCORA_ERR_BAD_ARG unless d <= r <= r_reserve <= 16; DCORA_ERR_UNSUPPORTED once an exchange exists on the session
+ * (its segment is unlinked after creation and its IPC mappings are fixed: an exchange does not grow). */
+int dcora_rbcd_reserve_rank(dcora_rbcd_t s, int r_reserve);
+/* Debug entry of the tests: the agent form of the lift's image kernel (k_lift_images).  From Xa (r x ka column-major:
+ * one agent's block), the global v (kglobal doubles) and the agent's column map -- cols (ka global column indices) or,
+ * with cols NULL, the contiguous range starting at col0 -- Xplus = [Xa; 0] and dir = [0; v_a^T], each (r + 1) x ka.
+ * All arrays on the host.  DCORA_ERR_BAD_ARG: r outside 1..15, ka < 1 or a column outside 0..kglobal-1. */
+int dcora_debug_lift_images(int r, int ka, const double *Xa, int kglobal, const double *v, const int *cols, int col0,
+                            double *Xplus, double *dir);
 /* Measurement hook (bench.py's `roofline`): while enabled, HIP events are recorded on the solver's stream around every
  * one-launch tCG run (k_tcg_run) of the session's agents; _read waits for the stream, returns {launches, sum of their
  * event times in us} since the last read and forgets them.  Not for timed regions: an event pair costs a few us. */
@@ -496,6 +511,35 @@ int dcora_exchange_run_coloured(dcora_exchange_t ex, int max_sweeps, double rgra
  * host each block (collective; X is valid on every rank) */
 int dcora_exchange_set_X(dcora_exchange_t ex, const double *X);
 int dcora_exchange_gather_X(dcora_exchange_t ex, double *X);
+/* The Riemannian staircase's step of a whole job (ref examples/MultiRobotExample.cpp:352-366,
+ * examples/MultiRobotExample_RASLAM.cpp, src/QuadraticProblem.cpp:138-234): dcora_rbcd_lift's contract carried across
+ * the ranks, on the exchange of a pose-graph or a range-aided session.  SPMD: every rank calls it with the same theta,
+ * the same v (k doubles on the host, global ordering, as dcora_exchange_certify returns it) and the same params.  The
+ * job goes from rank r to r + 1 without leaving the library: no agent's X crosses to the host, no session and no
+ * exchange is destroyed, and a robust job keeps mu, its update count and its team.
+ * The search is src/QuadraticProblem.cpp:161-233's, the statement dcora_rbcd_lift runs: first step length and halving;
+ * the first trial that lowers f with both gradient norms above their tolerances; else the trial of least f if it
+ * lowers f; else *escaped = 0.  Per trial each rank retracts the blocks of [X; 0] + alpha [0; v^T] of the agents it
+ * hosts at rank r + 1, the public columns travel with the ordinary post and wait of all agents, and every scalar a
+ * decision uses is summed over the ranks in rank order, so that all ranks decide alike.
+ * ONE DIFFERENCE from the reference and from dcora_rbcd_lift: no rank holds the whole graph, so the third test uses
+ * the agents' own preconditioners, |P grad|^2 := sum_a |Proj(rgrad_a M_a^-1)|^2 with the images the agents' solves
+ * use (their own regularisation).  params->central_reg is ignored here, at any world_size: the exchange of a
+ * one-rank job takes this same path.
+ * Escaped: every hosted agent's problem is at r + 1, the sessions' buffers are re-dimensioned and the accepted point is
+ * adopted on every rank at once as dcora_exchange_set_X adopts one (V = Y = XPrev = X, Nesterov sequences and round
+ * counters restarted, a robust job's X_initial, team statuses cleared on every rank alike); dcora_rbcd_rank /
+ * dcora_ra_rbcd_rank report r + 1.  Matrices, preconditioners, weights, mu and its update count, team parameters and
+ * loop-closure counts, and the exchange with its transport stay.
+ * No escape, or an error on any rank: the job is as it was (the trials ran beside the sessions' mirrors), and its next
+ * iterates are those of a job that never called this.  A failure on one rank raises the segment's `failed` word as in
+ * every collective call; every wait is bounded by DCORA_EXCHANGE_TIMEOUT_S.
+ * Refused on every rank alike, the job untouched: DCORA_ERR_BAD_ARG for r = 16, v or params NULL, v, theta or a
+ * tolerance not finite; DCORA_ERR_UNSUPPORTED when r + 1 exceeds max(r at the exchange's creation, the reserve):
+ * reserve with dcora_rbcd_reserve_rank / dcora_ra_rbcd_reserve_rank or the *_create_robust_ranks_reserved entries.
+ * info8 (may be NULL): trials, accepted alpha, f before, f after, 0, 0, ms of the re-dimensioning, ms total. */
+int dcora_exchange_lift(dcora_exchange_t ex, double theta, const double *v, const dcora_lift_params *params,
+                        int *escaped, double *info8);
 /* host barrier over the ranks of the job (does not synchronise the device) */
 int dcora_exchange_barrier(dcora_exchange_t ex);
 /* Agent::shouldTerminate's team condition (ref src/Agent.cpp:1137-1153: terminate only when EVERY robot reports
@@ -568,6 +612,8 @@ int dcora_ra_rbcd_certify(dcora_ra_rbcd_t s, double eta, int *certified, double 
 int dcora_ra_rbcd_lift(dcora_ra_rbcd_t s, double theta, const double *v, const dcora_lift_params *p, int *escaped,
                        double *info8);
 int dcora_ra_rbcd_rank(dcora_ra_rbcd_t s, int *r);
+/* dcora_rbcd_reserve_rank on a range-aided session: legal until dcora_exchange_create_ra */
+int dcora_ra_rbcd_reserve_rank(dcora_ra_rbcd_t s, int r_reserve);
 /* as dcora_rbcd_iterate / _evaluate / _run / _last_result; `selected` indexes the agents of dcora_ra_rbcd_info */
 int dcora_ra_rbcd_iterate(dcora_ra_rbcd_t s, int selected, double *cost2, double *gradnorm, double *block_norms,
                           int *next_selected);
@@ -643,6 +689,11 @@ int dcora_rbcd_robust_info(dcora_rbcd_t s, double *mu, int *updates);
 int dcora_rbcd_create_robust_ranks(dcora_dataset_t ds, const dcora_rbcd_options *opt, const dcora_robust_params *robust,
                                    const int *fixed_weight, const char *job_name, dcora_rbcd_t *session,
                                    dcora_exchange_t *ex);
+/* The same with room for the ranks to come (dcora_rbcd_reserve_rank between the session and its exchange): r_reserve 0
+ * is dcora_rbcd_create_robust_ranks, which calls this with 0; else d <= opt->r <= r_reserve <= 16 (DCORA_ERR_BAD_ARG). */
+int dcora_rbcd_create_robust_ranks_reserved(dcora_dataset_t ds, const dcora_rbcd_options *opt,
+                                            const dcora_robust_params *robust, const int *fixed_weight, int r_reserve,
+                                            const char *job_name, dcora_rbcd_t *session, dcora_exchange_t *ex);
 /* dcora_rbcd_update_weights of every agent on every rank, on the iterate that the last dcora_exchange_wait left in each
  * rank's mirror: each rank weights the measurements touching its agents (one launch; a measurement shared by two ranks
  * is weighted on both, to the same bits), the rank hosting p1 publishes the weight in the exchange's shared segment,
@@ -705,6 +756,11 @@ int dcora_ra_rbcd_robust_info(dcora_ra_rbcd_t s, double *mu, int *updates);
 int dcora_ra_rbcd_create_robust_ranks(dcora_radataset_t ds, const dcora_rbcd_options *opt,
                                       const dcora_robust_params *robust, const int *fixed_weight, const char *job_name,
                                       dcora_ra_rbcd_t *session, dcora_exchange_t *ex);
+/* dcora_rbcd_create_robust_ranks_reserved on a range-aided job (r_reserve 0: dcora_ra_rbcd_create_robust_ranks) */
+int dcora_ra_rbcd_create_robust_ranks_reserved(dcora_radataset_t ds, const dcora_rbcd_options *opt,
+                                               const dcora_robust_params *robust, const int *fixed_weight,
+                                               int r_reserve, const char *job_name, dcora_ra_rbcd_t *session,
+                                               dcora_exchange_t *ex);
 /* Host only.  The rule of dcora_ra_rbcd_create_robust_ranks for rank `rank` of world_size: one flag per pose-pose
  * measurement each.  touches: either pose is owned by an agent the rank hosts (agent i -- position in the sorted list of
  * robots owning poses -- on rank i / ceil(R / world_size)); owns: it hosts the owner of p1.  Every measurement is owned
