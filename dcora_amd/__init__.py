@@ -671,8 +671,121 @@ def _fixed_flags(ds, fixed_weight):
     return fx
 
 
-class RbcdSession:
+class _Session:
+    """what RbcdSession and RaRbcdSession share: the calls that differ only in the prefix of their entry point
+    (_prefix: dcora_rbcd_ / dcora_ra_rbcd_) and in one word of a message (_per)"""
+    _prefix = None
+    _per = "measurement"   # what a weight belongs to, in set_weights' message
+
+    def _fn(self, name):
+        return getattr(capi.lib(), self._prefix + name)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self._fn("destroy")(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_X(self, X):
+        check(self._fn("set_X")(self.h, F(X)))
+
+    def get_X(self):
+        out = np.zeros(self.r * self.k)
+        check(self._fn("get_X")(self.h, out))
+        return unF(out, self.r, self.k)
+
+    def certify(self, eta):
+        """fastVerification of S = Q - Lambda(X) on the device, with the Q the session holds now (its current weights) and
+        its current iterate (dcora_rbcd_certify / dcora_ra_rbcd_certify) -> (psd, theta, v, lambda_min, info); v in the
+        session's global ordering; the session is left as it was"""
+        return _session_certify(self._fn("certify"), self.h, self.k, eta)
+
+    def _lift(self, theta, v, gradient_tolerance, preconditioned_gradient_tolerance, is_second_order, central_reg):
+        return _session_lift(self, self._fn("lift"), self._fn("rank"), theta, v, gradient_tolerance,
+                             preconditioned_gradient_tolerance, is_second_order, central_reg)
+
+    def reserve_rank(self, r_reserve):
+        """room for the ranks to come (dcora_rbcd_reserve_rank / dcora_ra_rbcd_reserve_rank): an Exchange created on
+        this session afterwards can lift the job up to r_reserve; d <= r <= r_reserve <= 16, before the exchange exists"""
+        check(self._fn("reserve_rank")(self.h, int(r_reserve)))
+
+    def _eval(self, fn, *first):
+        c2, gn, nxt = C.c_double(), C.c_double(), C.c_int()
+        bn = np.zeros(self.R)
+        check(fn(self.h, *first, C.byref(c2), C.byref(gn), bn.ctypes.data_as(C.c_void_p), C.byref(nxt)))
+        return c2.value, gn.value, bn, nxt.value
+
+    def iterate(self, selected):
+        return self._eval(self._fn("iterate"), selected)
+
+    def evaluate(self):
+        return self._eval(self._fn("evaluate"))
+
+    def run(self, max_iters=1000, rgrad_tol=0.1):
+        it = C.c_int()
+        cost, gn = np.zeros(max_iters), np.zeros(max_iters)
+        sel = np.zeros(max_iters, np.int32)
+        check(self._fn("run")(self.h, max_iters, rgrad_tol, C.byref(it), cost.ctypes.data_as(C.c_void_p),
+                              gn.ctypes.data_as(C.c_void_p), sel.ctypes.data_as(C.c_void_p)))
+        n = it.value
+        return dict(iters=n, cost=cost[:n], gradnorm=gn[:n], selected=sel[:n])
+
+    def iterate_set(self, agents, allow_adjacent=False):
+        """the agents of the set update at the same time from one snapshot of their neighbours' states"""
+        a = np.ascontiguousarray(agents, dtype=np.int32)
+        check(self._fn("iterate_set")(self.h, a, a.size, int(allow_adjacent)))
+
+    def set_acceleration(self, on):
+        check(self._fn("set_acceleration")(self.h, int(bool(on))))
+
+    def colours(self):
+        col, nc = np.zeros(self.R, np.int32), C.c_int()
+        check(self._fn("agent_colours")(self.h, col, C.byref(nc)))
+        return col, nc.value
+
+    def run_coloured(self, max_sweeps=1000, rgrad_tol=0.1):
+        """sweeps of iterate_set per colour of colours(), each followed by evaluate(), until |rgrad| < rgrad_tol
+        (dcora_rbcd_run_coloured / dcora_ra_rbcd_run_coloured; acceleration off); iters counts sweeps"""
+        return _run_coloured(self._fn("run_coloured"), self.h, max_sweeps, rgrad_tol)
+
+    def last_result(self):
+        r = ROptResult()
+        check(self._fn("last_result")(self.h, C.byref(r)))
+        return r.as_dict()
+
+    # ---- robust sessions (created with robust=...); weights in the job's order (range-aided: pose-pose) ----
+    def update_weights(self, reset_to_initial=False):
+        """Agent::updateMeasurementWeights of every agent on the current iterate; returns the loop closures'
+        {accepted, rejected, undecided} counts"""
+        c = np.zeros(3, np.int32)
+        check(self._fn("update_weights")(self.h, int(bool(reset_to_initial)), c.ctypes.data_as(C.c_void_p)))
+        return {"accepted": int(c[0]), "rejected": int(c[1]), "undecided": int(c[2])}
+
+    def set_weights(self, w):
+        w = np.ascontiguousarray(w, np.float64)
+        if w.shape != (self.m,):
+            raise ValueError("set_weights needs one weight per " + self._per)
+        check(self._fn("set_weights")(self.h, w))
+
+    def get_weights(self):
+        w = np.zeros(max(self.m, 1))  # (never an empty buffer: its pointer would be NULL)
+        check(self._fn("get_weights")(self.h, w))
+        return w[:self.m]
+
+    def robust_info(self):
+        mu, n = C.c_double(), C.c_int()
+        check(self._fn("robust_info")(self.h, C.byref(mu), C.byref(n)))
+        return {"mu": mu.value, "updates": n.value}
+
+
+class RbcdSession(_Session):
     """Agents + synchronous RBCD++ driver on the device (ref examples/MultiRobotExample.cpp:121-307)"""
+    _prefix = "dcora_rbcd_"
 
     def __init__(self, ds, num_robots=5, r=5, acceleration=True, restart_interval=30, params=None, rank=0,
                  world_size=1, device=0, stream=None, robust=None, fixed_weight=None):
@@ -696,112 +809,12 @@ class RbcdSession:
             capi.lib().dcora_dataset_destroy(dsh)
         self.m = ds.m
 
-    def close(self):
-        if getattr(self, "h", None):
-            capi.lib().dcora_rbcd_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def set_X(self, X):
-        check(capi.lib().dcora_rbcd_set_X(self.h, F(X)))
-
-    def get_X(self):
-        out = np.zeros(self.r * self.k)
-        check(capi.lib().dcora_rbcd_get_X(self.h, out))
-        return unF(out, self.r, self.k)
-
-    def certify(self, eta):
-        """fastVerification of S = Q - Lambda(X) on the device, with the Q the session holds now (its current weights) and
-        its current iterate (dcora_rbcd_certify) -> (psd, theta, v, lambda_min, info); the session is left as it was"""
-        return _session_certify(capi.lib().dcora_rbcd_certify, self.h, self.k, eta)
-
     def lift(self, theta, v, gradient_tolerance=1e-6, preconditioned_gradient_tolerance=1e-6, is_second_order=False,
              central_reg=None):
         """The staircase's step in place (dcora_rbcd_lift): escapeSaddle along the refused certificate's (theta, v) into
         rank r + 1 inside this session, which keeps its matrices, preconditioners, weights, GNC state and team
         -> (escaped, info).  escaped False: nothing has changed.  self.r is the session's rank afterwards."""
-        return _session_lift(self, capi.lib().dcora_rbcd_lift, capi.lib().dcora_rbcd_rank, theta, v, gradient_tolerance,
-                             preconditioned_gradient_tolerance, is_second_order, central_reg)
-
-    def reserve_rank(self, r_reserve):
-        """room for the ranks to come (dcora_rbcd_reserve_rank): an Exchange created on this session afterwards can
-        lift the job up to r_reserve; d <= r <= r_reserve <= 16, before the exchange exists"""
-        check(capi.lib().dcora_rbcd_reserve_rank(self.h, int(r_reserve)))
-
-    def iterate(self, selected):
-        c2, gn, nxt = C.c_double(), C.c_double(), C.c_int()
-        bn = np.zeros(self.R)
-        check(capi.lib().dcora_rbcd_iterate(self.h, selected, C.byref(c2), C.byref(gn),
-                                            bn.ctypes.data_as(C.c_void_p), C.byref(nxt)))
-        return c2.value, gn.value, bn, nxt.value
-
-    def iterate_set(self, agents, allow_adjacent=False):
-        """the agents of the set update at the same time from one snapshot of their neighbours' states"""
-        a = np.ascontiguousarray(agents, dtype=np.int32)
-        check(capi.lib().dcora_rbcd_iterate_set(self.h, a, a.size, int(allow_adjacent)))
-
-    def set_acceleration(self, on):
-        check(capi.lib().dcora_rbcd_set_acceleration(self.h, int(bool(on))))
-
-    def colours(self):
-        col, nc = np.zeros(self.R, np.int32), C.c_int()
-        check(capi.lib().dcora_rbcd_agent_colours(self.h, col, C.byref(nc)))
-        return col, nc.value
-
-    def evaluate(self):
-        c2, gn, nxt = C.c_double(), C.c_double(), C.c_int()
-        bn = np.zeros(self.R)
-        check(capi.lib().dcora_rbcd_evaluate(self.h, C.byref(c2), C.byref(gn), bn.ctypes.data_as(C.c_void_p),
-                                             C.byref(nxt)))
-        return c2.value, gn.value, bn, nxt.value
-
-    def run(self, max_iters=1000, rgrad_tol=0.1):
-        it = C.c_int()
-        cost, gn = np.zeros(max_iters), np.zeros(max_iters)
-        sel = np.zeros(max_iters, np.int32)
-        check(capi.lib().dcora_rbcd_run(self.h, max_iters, rgrad_tol, C.byref(it), cost.ctypes.data_as(C.c_void_p),
-                                        gn.ctypes.data_as(C.c_void_p), sel.ctypes.data_as(C.c_void_p)))
-        n = it.value
-        return dict(iters=n, cost=cost[:n], gradnorm=gn[:n], selected=sel[:n])
-
-    def run_coloured(self, max_sweeps=1000, rgrad_tol=0.1):
-        """sweeps of iterate_set per colour of colours(), each followed by evaluate(), until |rgrad| < rgrad_tol
-        (dcora_rbcd_run_coloured; acceleration off); iters counts sweeps"""
-        return _run_coloured(capi.lib().dcora_rbcd_run_coloured, self.h, max_sweeps, rgrad_tol)
-
-    def last_result(self):
-        r = ROptResult()
-        check(capi.lib().dcora_rbcd_last_result(self.h, C.byref(r)))
-        return r.as_dict()
-
-    # ---- robust sessions (created with robust=...) ----
-    def update_weights(self, reset_to_initial=False):
-        """Agent::updateMeasurementWeights of every agent on the current iterate; returns the loop closures'
-        {accepted, rejected, undecided} counts"""
-        c = np.zeros(3, np.int32)
-        check(capi.lib().dcora_rbcd_update_weights(self.h, int(bool(reset_to_initial)), c.ctypes.data_as(C.c_void_p)))
-        return {"accepted": int(c[0]), "rejected": int(c[1]), "undecided": int(c[2])}
-
-    def set_weights(self, w):
-        w = np.ascontiguousarray(w, np.float64)
-        if w.shape != (self.m,):
-            raise ValueError("set_weights needs one weight per measurement")
-        check(capi.lib().dcora_rbcd_set_weights(self.h, w))
-
-    def get_weights(self):
-        w = np.zeros(self.m)
-        check(capi.lib().dcora_rbcd_get_weights(self.h, w))
-        return w
-
-    def robust_info(self):
-        mu, n = C.c_double(), C.c_int()
-        check(capi.lib().dcora_rbcd_robust_info(self.h, C.byref(mu), C.byref(n)))
-        return {"mu": mu.value, "updates": n.value}
+        return self._lift(theta, v, gradient_tolerance, preconditioned_gradient_tolerance, is_second_order, central_reg)
 
     # ---- multi-process pieces ----
     def X_device_ptr(self):
@@ -857,6 +870,7 @@ class Exchange:
     """neighbour exchange of public poses between the ranks of one node (dcora_exchange_*): the session must have been
     created with rank / world_size; every rank creates the exchange under the same job name"""
     IPC, STAGED = 1, 2
+    _prefix = "dcora_exchange_"
 
     def __init__(self, session, job_name, _handle=None):
         self.s = session
@@ -1042,9 +1056,12 @@ def ra_robust_ranked_session(ra, job_name, r, robust=None, fixed_weight=None, ra
     return s, Exchange(s, job_name, _handle=hx)
 
 
-class RaRbcdSession:
+class RaRbcdSession(_Session):
     """the agents of a multi-robot range-aided SLAM problem + the synchronous RBCD++ driver on the device
-    (ref examples/MultiRobotExample_RASLAM.cpp); X is the merged r x k matrix in the RA ordering"""
+    (ref examples/MultiRobotExample_RASLAM.cpp); X is the merged r x k matrix in the RA ordering; a robust session's
+    weights are in pose-pose order"""
+    _prefix = "dcora_ra_rbcd_"
+    _per = "pose-pose measurement"
 
     def __init__(self, ra, r, acceleration=True, restart_interval=30, params=None, device=0, rank=0, world_size=1,
                  robust=None, fixed_weight=None, _ranked_job=None, _r_reserve=0):
@@ -1087,107 +1104,11 @@ class RaRbcdSession:
         check(capi.lib().dcora_ra_rbcd_info(self.h, C.byref(n), rb.ctypes.data_as(C.c_void_p)))
         self.robots = rb.tolist()
 
-    def close(self):
-        if getattr(self, "h", None):
-            capi.lib().dcora_ra_rbcd_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def set_X(self, X):
-        check(capi.lib().dcora_ra_rbcd_set_X(self.h, F(X)))
-
-    def get_X(self):
-        out = np.zeros(self.r * self.k)
-        check(capi.lib().dcora_ra_rbcd_get_X(self.h, out))
-        return unF(out, self.r, self.k)
-
-    def certify(self, eta):
-        """RbcdSession.certify on the merged problem (dcora_ra_rbcd_certify); v in the global RA ordering"""
-        return _session_certify(capi.lib().dcora_ra_rbcd_certify, self.h, self.k, eta)
-
     def lift(self, theta, v, gradient_tolerance=1e-4, preconditioned_gradient_tolerance=1e-4, is_second_order=False,
              central_reg=None):
         """RbcdSession.lift on the merged problem (dcora_ra_rbcd_lift); v in the global RA ordering.  The tolerances
         default to multi_robot_raslam_example's."""
-        return _session_lift(self, capi.lib().dcora_ra_rbcd_lift, capi.lib().dcora_ra_rbcd_rank, theta, v,
-                             gradient_tolerance, preconditioned_gradient_tolerance, is_second_order, central_reg)
-
-    def reserve_rank(self, r_reserve):
-        """RbcdSession.reserve_rank on a range-aided session (dcora_ra_rbcd_reserve_rank)"""
-        check(capi.lib().dcora_ra_rbcd_reserve_rank(self.h, int(r_reserve)))
-
-    def _eval(self, fn, *first):
-        c2, gn, nxt = C.c_double(), C.c_double(), C.c_int()
-        bn = np.zeros(self.R)
-        check(fn(self.h, *first, C.byref(c2), C.byref(gn), bn.ctypes.data_as(C.c_void_p), C.byref(nxt)))
-        return c2.value, gn.value, bn, nxt.value
-
-    def iterate(self, selected):
-        return self._eval(capi.lib().dcora_ra_rbcd_iterate, selected)
-
-    def evaluate(self):
-        return self._eval(capi.lib().dcora_ra_rbcd_evaluate)
-
-    def run(self, max_iters=1000, rgrad_tol=0.1):
-        it = C.c_int()
-        cost, gn = np.zeros(max_iters), np.zeros(max_iters)
-        sel = np.zeros(max_iters, np.int32)
-        check(capi.lib().dcora_ra_rbcd_run(self.h, max_iters, rgrad_tol, C.byref(it),
-                                           cost.ctypes.data_as(C.c_void_p), gn.ctypes.data_as(C.c_void_p),
-                                           sel.ctypes.data_as(C.c_void_p)))
-        n = it.value
-        return dict(iters=n, cost=cost[:n], gradnorm=gn[:n], selected=sel[:n])
-
-    def iterate_set(self, agents, allow_adjacent=False):
-        """the agents of the set update at the same time from one snapshot of the mirror (acceleration off)"""
-        a = np.ascontiguousarray(agents, dtype=np.int32)
-        check(capi.lib().dcora_ra_rbcd_iterate_set(self.h, a, a.size, int(allow_adjacent)))
-
-    def set_acceleration(self, on):
-        check(capi.lib().dcora_ra_rbcd_set_acceleration(self.h, int(bool(on))))
-
-    def colours(self):
-        col, nc = np.zeros(self.R, np.int32), C.c_int()
-        check(capi.lib().dcora_ra_rbcd_agent_colours(self.h, col, C.byref(nc)))
-        return col, nc.value
-
-    def run_coloured(self, max_sweeps=1000, rgrad_tol=0.1):
-        """sweeps of iterate_set per colour of colours(), each followed by evaluate(), until |rgrad| < rgrad_tol
-        (dcora_ra_rbcd_run_coloured); iters counts sweeps"""
-        return _run_coloured(capi.lib().dcora_ra_rbcd_run_coloured, self.h, max_sweeps, rgrad_tol)
-
-    def last_result(self):
-        r = ROptResult()
-        check(capi.lib().dcora_ra_rbcd_last_result(self.h, C.byref(r)))
-        return r.as_dict()
-
-    # ---- robust sessions (created with robust=...): RbcdSession's four calls, weights in pose-pose order ----
-    def update_weights(self, reset_to_initial=False):
-        c = np.zeros(3, np.int32)
-        check(capi.lib().dcora_ra_rbcd_update_weights(self.h, int(bool(reset_to_initial)),
-                                                      c.ctypes.data_as(C.c_void_p)))
-        return {"accepted": int(c[0]), "rejected": int(c[1]), "undecided": int(c[2])}
-
-    def set_weights(self, w):
-        w = np.ascontiguousarray(w, np.float64)
-        if w.shape != (self.m,):
-            raise ValueError("set_weights needs one weight per pose-pose measurement")
-        check(capi.lib().dcora_ra_rbcd_set_weights(self.h, w))
-
-    def get_weights(self):
-        w = np.zeros(max(self.m, 1))
-        check(capi.lib().dcora_ra_rbcd_get_weights(self.h, w))
-        return w[:self.m]
-
-    def robust_info(self):
-        mu, n = C.c_double(), C.c_int()
-        check(capi.lib().dcora_ra_rbcd_robust_info(self.h, C.byref(mu), C.byref(n)))
-        return {"mu": mu.value, "updates": n.value}
+        return self._lift(theta, v, gradient_tolerance, preconditioned_gradient_tolerance, is_second_order, central_reg)
 
 
 def align_lifted_trajectory_to_frame(X, anchor, d, n, global_alignment=True, device=0):
@@ -1339,9 +1260,7 @@ def debug_launch_count():
 def _team_fn(self, name):
     """the team entry of a session (dcora_rbcd_<name>, dcora_ra_rbcd_<name>) or of a job's exchange of either kind
     (dcora_exchange_<name>: Exchange(session, ...), robust_ranked_session, ra_robust_ranked_session)"""
-    prefix = ("dcora_exchange_" if isinstance(self, Exchange) else
-              "dcora_ra_rbcd_" if isinstance(self, RaRbcdSession) else "dcora_rbcd_")
-    return getattr(capi.lib(), prefix + name)
+    return getattr(capi.lib(), self._prefix + name)
 
 
 def _enable_team(self, params=None, **kw):

@@ -69,7 +69,7 @@ std::vector<PoseMeas> view_meas(int d, int m, const int *ids, const double *vals
   }
   return out;
 }
-int bad(const char *msg) {
+int bad(const std::string &msg) {
   set_last_error(msg);
   return DCORA_ERR_BAD_ARG;
 }
@@ -116,17 +116,86 @@ int run_passes(Session &s, int max_iters, double rgrad_tol, int *iters_done, dou
   return DCORA_OK;
 }
 // dcora_rbcd_run_coloured / dcora_ra_rbcd_run_coloured: sweeps of one tick per colour, each followed by the session's
-// central evaluation (evaluate: that call of the session)
-template <class Evaluate>
-int run_coloured(SessionCore &s, Evaluate &&evaluate, int max_sweeps, double rgrad_tol, int *sweeps_done,
-                 double *cost2_trace, double *gradnorm_trace) {
+// central evaluation
+template <class Session>
+int run_coloured(Session &s, int max_sweeps, double rgrad_tol, int *sweeps_done, double *cost2_trace,
+                 double *gradnorm_trace) {
   std::vector<int> colours((size_t)s.R, 0);
   int nc = 0;
   const int rc = s.agent_colours(colours.data(), &nc);
   if (rc) return rc;
   return run_coloured_sweeps(
-      colours, nc, [&](const int *set, int count) { return s.iterate_set(set, count, 0); }, evaluate, max_sweeps,
-      rgrad_tol, sweeps_done, cost2_trace, gradnorm_trace);
+      colours, nc, [&](const int *set, int count) { return s.iterate_set(set, count, 0); },
+      [&](double *c2, double *gn) { return s.evaluate(c2, gn, nullptr, nullptr); }, max_sweeps, rgrad_tol, sweeps_done,
+      cost2_trace, gradnorm_trace);
+}
+
+// ---- robust and team sessions of either kind: the messages name the kind by the session's tag ("rbcd" / "ra_rbcd"),
+// which is also the middle of its entries' names (dcora_<tag>_...)
+std::string robust_tag(const SessionCore &s) { return std::string(s.tag()) + " robust: "; }
+// dcora_rbcd_create_robust / dcora_ra_rbcd_create_robust (H: the handle, ds: the kind's dataset handle)
+template <class H, class Dataset>
+int create_robust(Dataset ds, const dcora_rbcd_options *opt, const dcora_robust_params *robust, const int *fixed_weight,
+                  H **out) {
+  return create(out, [&](H &h) -> int {
+    if (opt->world_size != 1) {
+      const std::string entry = std::string("dcora_") + h.s.tag() + "_create_robust";
+      set_last_error(robust_tag(h.s) + entry + " makes single-process sessions (world_size 1); a multi-rank job "
+                     "creates its sessions with " + entry + "_ranks");
+      return DCORA_ERR_UNSUPPORTED;
+    }
+    return h.s.init_robust(ds->ds, *opt, *robust, fixed_weight);
+  });
+}
+// the robust session of one rank and its exchange, created together (weight updates are collective), with room for the
+// ranks to come (SessionCore::reserve_rank between the two)
+template <class H, class Dataset>
+int create_robust_ranks(Dataset ds, const dcora_rbcd_options *opt, const dcora_robust_params *robust,
+                        const int *fixed_weight, int r_reserve, const char *job_name, H **session,
+                        dcora_exchange_t *ex) {
+  std::unique_ptr<H> h(new H);  // (destroyed on every failure below)
+  if (reserve_rank_check(ds->ds.d, opt->r, r_reserve, true))
+    return bad(robust_tag(h->s) + "r_reserve is 0 (no reserve) or d <= r <= r_reserve <= 16");
+  int rc = h->s.init_robust(ds->ds, *opt, *robust, fixed_weight, true);
+  if (rc) return rc;
+  if (r_reserve && (rc = h->s.reserve_rank(r_reserve))) return rc;
+  std::unique_ptr<dcora_exchange_s> x(new dcora_exchange_s);
+  rc = x->e.init(&h->s, job_name, h->s.weights_count());
+  if (rc) return rc;
+  rc = x->e.publish_weights();
+  if (rc) return rc;
+  x->ranked = true;
+  *session = h.release();
+  *ex = x.release();
+  return DCORA_OK;
+}
+// the robust entries' refusals: multi-process sessions first, then sessions without robust state
+int robust_session(const SessionCore &s) {
+  if (s.robust) return DCORA_OK;
+  if (s.opt.world_size != 1) {
+    set_last_error(robust_tag(s) + "only single-process sessions (world_size 1) update weights");
+    return DCORA_ERR_UNSUPPORTED;
+  }
+  return bad(robust_tag(s) + "the session was not created by dcora_" + s.tag() + "_create_robust");
+}
+// ... and the session-level weight changes, which are not collective, on a session of a _create_robust_ranks entry
+int local_robust_session(const SessionCore &s, const char *collective) {
+  const int rc = robust_session(s);
+  if (rc || !s.robust->ranked) return rc;
+  set_last_error(robust_tag(s) + "the session belongs to a multi-rank job (dcora_" + s.tag() +
+                 "_create_robust_ranks): its weights change through " + collective);
+  return DCORA_ERR_UNSUPPORTED;
+}
+int robust_info(const SessionCore &s, double *mu, int *updates) {
+  const int rc = robust_session(s);
+  if (rc) return rc;
+  if (mu) *mu = s.robust->cost.mu();
+  if (updates) *updates = s.robust->updates;
+  return DCORA_OK;
+}
+int team_session(const SessionCore &s) {
+  return s.team ? (int)DCORA_OK
+                : bad(std::string(s.tag()) + " team: the session has not called dcora_" + s.tag() + "_team_enable");
 }
 }  // namespace
 
@@ -1076,14 +1145,7 @@ int dcora_rbcd_create(dcora_dataset_t ds, const dcora_rbcd_options *opt, dcora_r
 // Agent::initializeRobustOptimization (ref src/Agent.cpp:1332-1346) of every agent at creation
 int dcora_rbcd_create_robust(dcora_dataset_t ds, const dcora_rbcd_options *opt, const dcora_robust_params *robust,
                              const int *fixed_weight, dcora_rbcd_t *out) {
-  return abi_call({ds, opt, robust, out}, [&]() -> int {
-    if (opt->world_size != 1) {
-      set_last_error("rbcd robust: dcora_rbcd_create_robust makes single-process sessions (world_size 1); a multi-rank "
-                     "job creates its sessions with dcora_rbcd_create_robust_ranks");
-      return DCORA_ERR_UNSUPPORTED;
-    }
-    return create(out, [&](dcora_rbcd_s &h) { return h.s.init_robust(ds->ds, *opt, *robust, fixed_weight); });
-  });
+  return abi_call({ds, opt, robust, out}, [&] { return create_robust(ds, opt, robust, fixed_weight, out); });
 }
 // the robust session of one rank and its exchange, created together: weight updates are collective
 int dcora_rbcd_create_robust_ranks(dcora_dataset_t ds, const dcora_rbcd_options *opt, const dcora_robust_params *robust,
@@ -1095,42 +1157,11 @@ int dcora_rbcd_create_robust_ranks(dcora_dataset_t ds, const dcora_rbcd_options 
 int dcora_rbcd_create_robust_ranks_reserved(dcora_dataset_t ds, const dcora_rbcd_options *opt,
                                             const dcora_robust_params *robust, const int *fixed_weight, int r_reserve,
                                             const char *job_name, dcora_rbcd_t *session, dcora_exchange_t *ex) {
-  return abi_call({ds, opt, robust, job_name, session, ex}, [&]() -> int {
-    if (reserve_rank_check(ds->ds.d, opt->r, r_reserve, true))
-      return bad("rbcd robust: r_reserve is 0 (no reserve) or d <= r <= r_reserve <= 16");
-    std::unique_ptr<dcora_rbcd_s> h(new dcora_rbcd_s);
-    int rc = h->s.init_robust(ds->ds, *opt, *robust, fixed_weight, true);
-    if (rc) return rc;
-    if (r_reserve && (rc = h->s.reserve_rank(r_reserve))) return rc;
-    std::unique_ptr<dcora_exchange_s> x(new dcora_exchange_s);
-    rc = x->e.init(&h->s, job_name, ds->ds.meas.size());
-    if (rc) return rc;
-    rc = x->e.publish_weights();
-    if (rc) return rc;
-    x->ranked = true;
-    *session = h.release();
-    *ex = x.release();
-    return (int)DCORA_OK;
+  return abi_call({ds, opt, robust, job_name, session, ex}, [&] {
+    return create_robust_ranks(ds, opt, robust, fixed_weight, r_reserve, job_name, session, ex);
   });
 }
 namespace {
-// the robust entries' refusals: multi-process sessions first, then sessions without robust state
-int robust_session(dcora_rbcd_t s) {
-  if (s->s.robust) return DCORA_OK;
-  if (s->s.opt.world_size != 1) {
-    set_last_error("rbcd robust: only single-process sessions (world_size 1) update weights");
-    return DCORA_ERR_UNSUPPORTED;
-  }
-  return bad("rbcd robust: the session was not created by dcora_rbcd_create_robust");
-}
-// ... and the session-level weight changes, which are not collective, on a session of dcora_rbcd_create_robust_ranks
-int local_robust_session(dcora_rbcd_t s, const char *collective) {
-  const int rc = robust_session(s);
-  if (rc || !s->s.robust->ranked) return rc;
-  set_last_error(std::string("rbcd robust: the session belongs to a multi-rank job (dcora_rbcd_create_robust_ranks): "
-                             "its weights change through ") + collective);
-  return DCORA_ERR_UNSUPPORTED;
-}
 int ranked_exchange(dcora_exchange_t ex) {
   return ex->ranked ? DCORA_OK
                     : bad("exchange robust: the exchange was not created by dcora_rbcd_create_robust_ranks or "
@@ -1140,31 +1171,25 @@ int ranked_exchange(dcora_exchange_t ex) {
 // Agent::updateMeasurementWeights (ref src/Agent.cpp:1397-1441) of every agent
 int dcora_rbcd_update_weights(dcora_rbcd_t s, int reset_to_initial, int counts[3]) {
   return abi_call({s}, [&] {
-    const int rc = local_robust_session(s, "dcora_exchange_update_weights");
+    const int rc = local_robust_session(s->s, "dcora_exchange_update_weights");
     return rc ? rc : s->s.update_weights(reset_to_initial != 0, counts);
   });
 }
 // Agent::setMeasurementWeight (ref src/Agent.cpp:1443-1454) of every measurement
 int dcora_rbcd_set_weights(dcora_rbcd_t s, const double *w) {
   return abi_call({s, w}, [&] {
-    const int rc = local_robust_session(s, "dcora_exchange_set_weights");
+    const int rc = local_robust_session(s->s, "dcora_exchange_set_weights");
     return rc ? rc : s->s.set_weights(w);
   });
 }
 int dcora_rbcd_get_weights(dcora_rbcd_t s, double *w) {
   return abi_call({s, w}, [&] {
-    const int rc = robust_session(s);
+    const int rc = robust_session(s->s);
     return rc ? rc : s->s.get_weights(w);
   });
 }
 int dcora_rbcd_robust_info(dcora_rbcd_t s, double *mu, int *updates) {
-  return abi_call({s}, [&] {
-    const int rc = robust_session(s);
-    if (rc) return rc;
-    if (mu) *mu = s->s.robust->cost.mu();
-    if (updates) *updates = s->s.robust->updates;
-    return (int)DCORA_OK;
-  });
+  return abi_call({s}, [&] { return robust_info(s->s, mu, updates); });
 }
 int dcora_rbcd_destroy(dcora_rbcd_t s) {
   delete s;
@@ -1200,13 +1225,11 @@ int dcora_rbcd_agent_colours(dcora_rbcd_t s, int *colours, int *ncolours) {
 int dcora_rbcd_run_coloured(dcora_rbcd_t s, int max_sweeps, double rgrad_tol, int *sweeps_done, double *cost2_trace,
                             double *gradnorm_trace) {
   return abi_call({s}, [&] {
-    return run_coloured(
-        s->s, [&](double *c2, double *gn) { return s->s.evaluate_central(c2, gn, nullptr, nullptr); }, max_sweeps,
-        rgrad_tol, sweeps_done, cost2_trace, gradnorm_trace);
+    return run_coloured(s->s, max_sweeps, rgrad_tol, sweeps_done, cost2_trace, gradnorm_trace);
   });
 }
 int dcora_rbcd_evaluate(dcora_rbcd_t s, double *cost2, double *gradnorm, double *block_norms, int *next_selected) {
-  return abi_call({s}, [&] { return s->s.evaluate_central(cost2, gradnorm, block_norms, next_selected); });
+  return abi_call({s}, [&] { return s->s.evaluate(cost2, gradnorm, block_norms, next_selected); });
 }
 int dcora_rbcd_agent_iterate(dcora_rbcd_t s, int agent, int do_optimization) {
   return abi_call({s}, [&] { return s->s.agent_iterate(agent, do_optimization != 0); });
@@ -1282,9 +1305,6 @@ int dcora_ra_max_translation_distance(int r, int d, int n, int l, int b, const d
   return abi_call({X, Y, out}, [&] { return ra_max_translation_distance(r, d, n, l, b, X, Y, out); });
 }
 namespace {
-int team_session(dcora_rbcd_t s) {
-  return s->s.team ? (int)DCORA_OK : bad("rbcd team: the session has not called dcora_rbcd_team_enable");
-}
 // the team's queries over the session that holds the statuses: a single session's own, or the one of a job's rank
 // (dcora_rbcd_* and dcora_exchange_* differ in how they reach it and in the refusal above)
 int team_agent_status(SessionCore &s, int agent, dcora_agent_status *status, int *known) {
@@ -1311,28 +1331,28 @@ int dcora_rbcd_team_enable(dcora_rbcd_t s, const dcora_team_params *params) {
 // Agent::getStatus (ref include/DCORA/Agent.h:427-433) of one agent of the session
 int dcora_rbcd_agent_status(dcora_rbcd_t s, int agent, dcora_agent_status *status, int *known) {
   return abi_call({s, status}, [&] {
-    const int rc = team_session(s);
+    const int rc = team_session(s->s);
     return rc ? rc : team_agent_status(s->s, agent, status, known);
   });
 }
 // Graph::statistics (ref src/Graph.cpp:475-521) of one agent
 int dcora_rbcd_loop_closure_stats(dcora_rbcd_t s, int agent, int counts[3]) {
   return abi_call({s, counts}, [&] {
-    const int rc = team_session(s);
+    const int rc = team_session(s->s);
     return rc ? rc : team_loop_closure_stats(s->s, agent, counts);
   });
 }
 // Agent::shouldTerminate (ref src/Agent.cpp:1123-1156) over the statuses the session holds
 int dcora_rbcd_should_terminate(dcora_rbcd_t s, int *yes) {
   return abi_call({s, yes}, [&] {
-    const int rc = team_session(s);
+    const int rc = team_session(s->s);
     return rc ? rc : s->s.team_decide(yes, nullptr);
   });
 }
 // Agent::shouldUpdateMeasurementWeights (ref src/Agent.cpp:1280-1330) over the statuses the session holds
 int dcora_rbcd_should_update_weights(dcora_rbcd_t s, int *yes) {
   return abi_call({s, yes}, [&] {
-    const int rc = team_session(s);
+    const int rc = team_session(s->s);
     return rc ? rc : s->s.team_decide(nullptr, yes);
   });
 }
@@ -1340,7 +1360,7 @@ int dcora_rbcd_should_update_weights(dcora_rbcd_t s, int *yes) {
 // include/DCORA/Agent.h:720-735)
 int dcora_rbcd_team_info(dcora_rbcd_t s, int info[4]) {
   return abi_call({s, info}, [&] {
-    const int rc = team_session(s);
+    const int rc = team_session(s->s);
     return rc ? rc : team_info(s->s, info);
   });
 }
@@ -1349,7 +1369,7 @@ int dcora_rbcd_team_info(dcora_rbcd_t s, int info[4]) {
 int dcora_rbcd_run_team(dcora_rbcd_t s, int *iters_done, double *cost2_trace, double *gradnorm_trace,
                         int *selected_trace, int *updated_trace, int *weight_updates, int *stop_reason) {
   return abi_call({s}, [&] {
-    const int rc = team_session(s);
+    const int rc = team_session(s->s);
     return rc ? rc
               : s->s.run_team(iters_done, cost2_trace, gradnorm_trace, selected_trace, updated_trace, weight_updates,
                               stop_reason);
@@ -1777,9 +1797,7 @@ int dcora_ra_rbcd_agent_colours(dcora_ra_rbcd_t s, int *colours, int *ncolours) 
 int dcora_ra_rbcd_run_coloured(dcora_ra_rbcd_t s, int max_sweeps, double rgrad_tol, int *sweeps_done,
                                double *cost2_trace, double *gradnorm_trace) {
   return abi_call({s}, [&] {
-    return run_coloured(
-        s->s, [&](double *c2, double *gn) { return s->s.evaluate(c2, gn, nullptr, nullptr); }, max_sweeps, rgrad_tol,
-        sweeps_done, cost2_trace, gradnorm_trace);
+    return run_coloured(s->s, max_sweeps, rgrad_tol, sweeps_done, cost2_trace, gradnorm_trace);
   });
 }
 int dcora_ra_rbcd_last_result(dcora_ra_rbcd_t s, dcora_ropt_result *res) {
@@ -1809,14 +1827,7 @@ int dcora_ra_rbcd_rank(dcora_ra_rbcd_t s, int *r) {
 // Agent::initializeRobustOptimization (ref src/Agent.cpp:1332-1346) of every agent of a RangeAidedSLAMGraph at creation
 int dcora_ra_rbcd_create_robust(dcora_radataset_t ds, const dcora_rbcd_options *opt, const dcora_robust_params *robust,
                                 const int *fixed_weight, dcora_ra_rbcd_t *out) {
-  return abi_call({ds, opt, robust, out}, [&]() -> int {
-    if (opt->world_size != 1) {
-      set_last_error("ra_rbcd robust: dcora_ra_rbcd_create_robust makes single-process sessions (world_size 1); "
-                     "a multi-rank job creates its sessions with dcora_ra_rbcd_create_robust_ranks");
-      return DCORA_ERR_UNSUPPORTED;
-    }
-    return create(out, [&](dcora_ra_rbcd_s &h) { return h.s.init_robust(ds->ds, *opt, *robust, fixed_weight); });
-  });
+  return abi_call({ds, opt, robust, out}, [&] { return create_robust(ds, opt, robust, fixed_weight, out); });
 }
 // the robust session of one rank of a range-aided job and its exchange, created together: weight updates are collective
 int dcora_ra_rbcd_create_robust_ranks(dcora_radataset_t ds, const dcora_rbcd_options *opt,
@@ -1828,77 +1839,34 @@ int dcora_ra_rbcd_create_robust_ranks_reserved(dcora_radataset_t ds, const dcora
                                                const dcora_robust_params *robust, const int *fixed_weight,
                                                int r_reserve, const char *job_name, dcora_ra_rbcd_t *session,
                                                dcora_exchange_t *ex) {
-  return abi_call({ds, opt, robust, job_name, session, ex}, [&]() -> int {
-    if (reserve_rank_check(ds->ds.d, opt->r, r_reserve, true))
-      return bad("ra_rbcd robust: r_reserve is 0 (no reserve) or d <= r <= r_reserve <= 16");
-    std::unique_ptr<dcora_ra_rbcd_s> h(new dcora_ra_rbcd_s);  // (destroyed on every failure below)
-    int rc = h->s.init_robust(ds->ds, *opt, *robust, fixed_weight, true);
-    if (rc) return rc;
-    if (r_reserve && (rc = h->s.reserve_rank(r_reserve))) return rc;
-    std::unique_ptr<dcora_exchange_s> x(new dcora_exchange_s);
-    rc = x->e.init(&h->s, job_name, ds->ds.pose_pose.size());
-    if (rc) return rc;
-    rc = x->e.publish_weights();
-    if (rc) return rc;
-    x->ranked = true;
-    *session = h.release();
-    *ex = x.release();
-    return (int)DCORA_OK;
+  return abi_call({ds, opt, robust, job_name, session, ex}, [&] {
+    return create_robust_ranks(ds, opt, robust, fixed_weight, r_reserve, job_name, session, ex);
   });
 }
-namespace {
-// the refusals of the robust entries, as robust_session / local_robust_session state them for pose-graph sessions
-int ra_robust_session(dcora_ra_rbcd_t s) {
-  if (s->s.robust) return DCORA_OK;
-  if (s->s.opt.world_size != 1) {
-    set_last_error("ra_rbcd robust: only single-process sessions (world_size 1) update weights");
-    return DCORA_ERR_UNSUPPORTED;
-  }
-  return bad("ra_rbcd robust: the session was not created by dcora_ra_rbcd_create_robust");
-}
-int ra_local_robust_session(dcora_ra_rbcd_t s, const char *collective) {
-  const int rc = ra_robust_session(s);
-  if (rc || !s->s.robust->ranked) return rc;
-  set_last_error(std::string("ra_rbcd robust: the session belongs to a multi-rank job "
-                             "(dcora_ra_rbcd_create_robust_ranks): its weights change through ") + collective);
-  return DCORA_ERR_UNSUPPORTED;
-}
-}  // namespace
 // Agent::updateMeasurementWeights (ref src/Agent.cpp:1397-1441) of every agent
 int dcora_ra_rbcd_update_weights(dcora_ra_rbcd_t s, int reset_to_initial, int counts[3]) {
   return abi_call({s}, [&] {
-    const int rc = ra_local_robust_session(s, "dcora_exchange_update_weights");
+    const int rc = local_robust_session(s->s, "dcora_exchange_update_weights");
     return rc ? rc : s->s.update_weights(reset_to_initial != 0, counts);
   });
 }
 // Agent::setMeasurementWeight (ref src/Agent.cpp:1443-1454) of every pose-pose measurement
 int dcora_ra_rbcd_set_weights(dcora_ra_rbcd_t s, const double *w) {
   return abi_call({s, w}, [&] {
-    const int rc = ra_local_robust_session(s, "dcora_exchange_set_weights");
+    const int rc = local_robust_session(s->s, "dcora_exchange_set_weights");
     return rc ? rc : s->s.set_weights(w);
   });
 }
 int dcora_ra_rbcd_get_weights(dcora_ra_rbcd_t s, double *w) {
   return abi_call({s, w}, [&] {
-    const int rc = ra_robust_session(s);
+    const int rc = robust_session(s->s);
     return rc ? rc : s->s.get_weights(w);
   });
 }
 int dcora_ra_rbcd_robust_info(dcora_ra_rbcd_t s, double *mu, int *updates) {
-  return abi_call({s}, [&] {
-    const int rc = ra_robust_session(s);
-    if (rc) return rc;
-    if (mu) *mu = s->s.robust->cost.mu();
-    if (updates) *updates = s->s.robust->updates;
-    return (int)DCORA_OK;
-  });
+  return abi_call({s}, [&] { return robust_info(s->s, mu, updates); });
 }
 // ---- agent status and the team's decisions on a range-aided session (the dcora_rbcd_* namesakes' contracts) ----
-namespace {
-int ra_team_session(dcora_ra_rbcd_t s) {
-  return s->s.team ? (int)DCORA_OK : bad("ra_rbcd team: the session has not called dcora_ra_rbcd_team_enable");
-}
-}  // namespace
 // the opt-in to Agent::iterate's status block (ref src/Agent.cpp:558-586) and the bookkeeping of :1417-1424
 int dcora_ra_rbcd_team_enable(dcora_ra_rbcd_t s, const dcora_team_params *params) {
   return abi_call({s, params}, [&] { return s->s.team_enable(*params); });
@@ -1906,28 +1874,28 @@ int dcora_ra_rbcd_team_enable(dcora_ra_rbcd_t s, const dcora_team_params *params
 // Agent::getStatus (ref include/DCORA/Agent.h:427-433) of one agent of the session
 int dcora_ra_rbcd_agent_status(dcora_ra_rbcd_t s, int agent, dcora_agent_status *status, int *known) {
   return abi_call({s, status}, [&] {
-    const int rc = ra_team_session(s);
+    const int rc = team_session(s->s);
     return rc ? rc : team_agent_status(s->s, agent, status, known);
   });
 }
 // Graph::statistics (ref src/Graph.cpp:475-521) of one agent's RangeAidedSLAMGraph
 int dcora_ra_rbcd_loop_closure_stats(dcora_ra_rbcd_t s, int agent, int counts[3]) {
   return abi_call({s, counts}, [&] {
-    const int rc = ra_team_session(s);
+    const int rc = team_session(s->s);
     return rc ? rc : team_loop_closure_stats(s->s, agent, counts);
   });
 }
 // Agent::shouldTerminate (ref src/Agent.cpp:1123-1156) over the statuses the session holds
 int dcora_ra_rbcd_should_terminate(dcora_ra_rbcd_t s, int *yes) {
   return abi_call({s, yes}, [&] {
-    const int rc = ra_team_session(s);
+    const int rc = team_session(s->s);
     return rc ? rc : s->s.team_decide(yes, nullptr);
   });
 }
 // Agent::shouldUpdateMeasurementWeights (ref src/Agent.cpp:1280-1330) over the statuses the session holds
 int dcora_ra_rbcd_should_update_weights(dcora_ra_rbcd_t s, int *yes) {
   return abi_call({s, yes}, [&] {
-    const int rc = ra_team_session(s);
+    const int rc = team_session(s->s);
     return rc ? rc : s->s.team_decide(nullptr, yes);
   });
 }
@@ -1935,7 +1903,7 @@ int dcora_ra_rbcd_should_update_weights(dcora_ra_rbcd_t s, int *yes) {
 // include/DCORA/Agent.h:720-735)
 int dcora_ra_rbcd_team_info(dcora_ra_rbcd_t s, int info[4]) {
   return abi_call({s, info}, [&] {
-    const int rc = ra_team_session(s);
+    const int rc = team_session(s->s);
     return rc ? rc : team_info(s->s, info);
   });
 }
@@ -1944,7 +1912,7 @@ int dcora_ra_rbcd_team_info(dcora_ra_rbcd_t s, int info[4]) {
 int dcora_ra_rbcd_run_team(dcora_ra_rbcd_t s, int *iters_done, double *cost2_trace, double *gradnorm_trace,
                            int *selected_trace, int *updated_trace, int *weight_updates, int *stop_reason) {
   return abi_call({s}, [&] {
-    const int rc = ra_team_session(s);
+    const int rc = team_session(s->s);
     return rc ? rc
               : s->s.run_team(iters_done, cost2_trace, gradnorm_trace, selected_trace, updated_trace, weight_updates,
                               stop_reason);

@@ -52,26 +52,6 @@ struct RaAgentDev : AgentCore {
   double reg = 0;
 };
 
-// Robust state of a session created by dcora_ra_rbcd_create_robust or dcora_ra_rbcd_create_robust_ranks (RobustSession of
-// rbcd.h, in pose-pose order)
-struct RaRobustSession {
-  explicit RaRobustSession(const dcora_robust_params &p) : cost(p), params(p) {}
-  RobustCost cost;
-  dcora_robust_params params;
-  int updates = 0;
-  HostRADataset ds;             // the dataset with the current pose-pose weights
-  std::vector<char> update;     // loop closures whose weight is not fixed: what updateMeasurementWeights rewrites
-  std::vector<char> meas_zero;  // weight 0 at creation: the patterns do not hold these measurements
-  RobustEdges edges;            // device copy of the pose-pose measurements and of their weights
-  bool ranked = false;          // created by dcora_ra_rbcd_create_robust_ranks
-  std::vector<int> edge_ids;    // the measurements in `edges` (pose-pose order): all, or those touching a hosted agent
-  std::vector<char> owned;      // ranked, per pose-pose measurement: this rank hosts the agent of p1 (ra_rank_edges)
-  DevBuf<double> X_initial;     // the last set_X, r x k global (robustOptNumResets: setXToInitialGuess)
-  std::vector<HostCsr> Qpat, Cpat;  // creation patterns (rp, ci) of every hosted agent's Q_aa and coupling block
-  HostCsr central_pat;
-  HostCsr live_pat;  // the central Q's entries as the current weights give them (no explicit zeros): what certify reads
-};
-
 class RaRbcdSession : public SessionCore {
  public:
   int d = 0, n = 0, l = 0, b = 0, k = 0;
@@ -82,23 +62,11 @@ class RaRbcdSession : public SessionCore {
   RaRbcdSession() : SessionCore("ra_rbcd") {}
   ~RaRbcdSession();
   int init(const HostRADataset &ds, const dcora_rbcd_options &o);
-  // robust sessions: weight 1 on every loop closure that is not fixed (fixed: m_pp flags or null), then init
-  std::unique_ptr<RaRobustSession> robust;
-  // ranked: a rank of a multi-rank job (world_size >= 1), its weight updates driven by the exchange
+  // robust sessions (RobustState, session_core.h; the job's measurements are the pose-pose ones): weight 1 on every
+  // loop closure that is not fixed (fixed: m_pp flags or null), then init.  ranked: a rank of a multi-rank job
+  // (world_size >= 1), its weight updates driven by the exchange
   int init_robust(const HostRADataset &ds, const dcora_rbcd_options &o, const dcora_robust_params &p, const int *fixed,
                   bool ranked = false);
-  // updateMeasurementWeights on the current iterate; counts (may be null): accepted, rejected, undecided closures
-  int update_weights(bool reset_to_initial, int counts[3]);
-  // its two halves, as RbcdSession has them: the weights of the session's edges on the device (ranked: the owned ones
-  // also into shared_w, counts over the owned ones), then the matrices rebuilt and the rest of the update
-  int compute_weights(double *shared_w, std::vector<double> *w, double counts[3]) override;
-  int apply_weights(const std::vector<double> &w, bool reset_to_initial) override;
-  // all m_pp weights; refused (session untouched) when one is negative or not finite
-  int set_weights(const double *w) override;
-  int get_weights(double *w) const;  // ranked: NaN for the measurements touching no hosted agent
-  bool weights_ranked() const override { return robust && robust->ranked; }
-  size_t weights_count() const override { return robust ? robust->ds.pose_pose.size() : 0; }
-  bool weight_owned(size_t e, double *w) const override;
   int set_X(const double *Xh) override;  // r x k global; V = Y = XPrev = X for every agent
   int get_X(double *Xh);
   // one pass of the driver's loop body with agent index `selected` (position in the sorted robot list)
@@ -114,18 +82,17 @@ class RaRbcdSession : public SessionCore {
   long num_cols() const override { return k; }
   int dim() const override { return d; }
   DeviceProblem *central_problem() override { return central.get(); }
-  const HostCsr *central_pattern() const override { return robust ? &robust->central_pat : nullptr; }
-  const HostCsr *central_live_pattern() const override { return robust ? &robust->live_pat : nullptr; }
   int cert_block() const override { return 1; }
   int x_stage_hosted(double *host_area) override;
-  // the team protocol (session_core.h): an L2 team on a plain session
-  bool team_robust() const override { return robust && robust->params.cost_type != DCORA_ROBUST_L2; }
-  int team_weight_updates() const override { return robust ? robust->updates : 0; }
 
  private:
   // the one path from a dataset's measurements to the session's matrices, at creation and on every re-weight
   int assemble(const HostRADataset &ds, bool creation);
-  int adopt_weights(HostRADataset &ds, bool from_device, bool reset_to_initial);
+  // a robust session's part (session_core.h)
+  HostRADataset robust_ds_;  // the dataset as created; the pose-pose weights live in robust->w
+  int robust_upload_edges() override;
+  int robust_rebuild(const std::vector<double> &w) override;
+  int robust_restart_acceleration() override;
   // set_X's body for a point on the host or on the device (kind: the copy into the mirror)
   int adopt_X(const double *X, hipMemcpyKind kind);
   // SessionCore::lift's hooks: the mirror, X_initial and the agents' X, V, Y, XPrev, tmp re-dimensioned; the central
@@ -145,11 +112,8 @@ class RaRbcdSession : public SessionCore {
   bool serial_set(const std::vector<AgentCore *> &work) override { return work.size() == 1; }
   int tick_done(const std::vector<AgentCore *> &work) override;
   // the session kind's part of the team protocol: k_rel_change's RA form over the agents' own X / XPrev; the loop
-  // closures are ra_team_loop_closures' with agents for robots, a pose-pose one's current weight the robust state's
+  // closures are ra_team_loop_closures' with agents for robots
   int team_launch_rel_change(const std::vector<int> &ids) override;
-  // (a rank of a job: the job's weights the exchange keeps, never the rank's own partial ones)
-  double team_lc_weight(const TeamLoopClosure &q) const override;
-  int team_update_weights(bool reset_to_initial) override { return update_weights(reset_to_initial, nullptr); }
   int team_iterate(int selected, double *cost2, double *gradnorm, int *next_selected) override {
     return iterate(selected, cost2, gradnorm, nullptr, next_selected);
   }

@@ -234,181 +234,52 @@ int RaRbcdSession::assemble(const HostRADataset &ds, bool creation) {
   return DCORA_OK;
 }
 
-// ---- robust sessions -------------------------------------------------------------------------------------------------
-// Agent::initializeRobustOptimization for every agent (ref src/Agent.cpp:1332-1346): weight 1 on every loop closure whose
-// weight is not fixed (ra_loop_closures: every pose-pose measurement but odometry).  With weights 1 the patterns are the
-// largest any later weights can give: they are kept, and a weight change only rewrites values.
-// A rank of a multi-rank job (ranked) builds the patterns of its hosted agents only and uploads the pose-pose
-// measurements touching them (ra_rank_edges), to be read from its mirror in the RA ordering of the whole problem.
+// ---- robust sessions (RobustState, session_core.h): what is this kind's own -------------------------------------------
+// The loop closures are ra_loop_closures': every pose-pose measurement but odometry.  A rank of a multi-rank job (ranked)
+// builds the patterns of its hosted agents only and uploads the pose-pose measurements touching them (ra_rank_edges), to
+// be read from its mirror in the RA ordering of the whole problem.
 int RaRbcdSession::init_robust(const HostRADataset &ds, const dcora_rbcd_options &o, const dcora_robust_params &p,
                                const int *fixed, bool ranked) {
-  if (o.world_size != 1 && !ranked) {
-    set_last_error("ra_rbcd robust: only single-process sessions (world_size 1) update weights here; a multi-rank job "
-                   "creates its sessions with dcora_ra_rbcd_create_robust_ranks");
-    return DCORA_ERR_UNSUPPORTED;
-  }
-  if (p.cost_type < DCORA_ROBUST_L2 || p.cost_type > DCORA_ROBUST_GNC_TLS) {
-    set_last_error("ra_rbcd robust: unknown robust cost type");
-    return DCORA_ERR_BAD_ARG;
-  }
-  const size_t m = ds.pose_pose.size();
-  for (const PoseMeas &q : ds.pose_pose)
-    if (q.p1 < 0 || q.p1 >= ds.n || q.p2 < 0 || q.p2 >= ds.n) {
-      set_last_error("ra_rbcd robust: pose index out of range");
-      return DCORA_ERR_BAD_ARG;
-    }
+  int rc = robust_check_args(ds.pose_pose, ds.n, o, p, ranked);
+  if (rc) return rc;
   if (ds.pose_robot.size() != (size_t)ds.n) {
     set_last_error("ra_rbcd robust: the dataset has no pose owners");
     return DCORA_ERR_BAD_ARG;
   }
-  robust.reset(new RaRobustSession(p));
-  RaRobustSession &rs = *robust;
-  rs.ds = ds;
+  const size_t m = ds.pose_pose.size();
   std::vector<int> lc(m);
   ra_loop_closures(ds, lc.data());
-  rs.update.assign(m, 0);
-  rs.meas_zero.assign(m, 0);
-  for (size_t e = 0; e < m; ++e) {
-    PoseMeas &q = rs.ds.pose_pose[e];
-    if (lc[e] && !(fixed && fixed[e])) {
-      rs.update[e] = 1;
-      q.weight = 1.0;
-    }
-    rs.meas_zero[e] = q.weight == 0.0;
-  }
-  int rc = init(rs.ds, o);
-  if (rc) return rc;
-  rs.ranked = ranked;
-  rs.owned.assign(m, 0);
-  if (ranked) {
-    std::vector<char> own;
-    ra_rank_edges(rs.ds, o.rank, o.world_size, &rs.edge_ids, &own);
-    for (size_t i = 0; i < rs.edge_ids.size(); ++i) rs.owned[(size_t)rs.edge_ids[i]] = own[i];
-    rc = rs.edges.upload_ra_ranked(rs.ds, rs.update, rs.edge_ids, own);
-  } else {
-    for (size_t e = 0; e < m; ++e) rs.edge_ids.push_back((int)e);
-    rc = rs.edges.upload_ra(rs.ds, rs.update);
-  }
-  if (rc) return rc;
-  DCORA_HIP(rs.X_initial.alloc((size_t)r * k));
-  DCORA_HIP(hipMemsetAsync(rs.X_initial.p, 0, sizeof(double) * (size_t)r * k, st));
-  DCORA_HIP(hipStreamSynchronize(st));
-  return DCORA_OK;
+  robust_begin(ds.pose_pose, std::vector<char>(lc.begin(), lc.end()), p, fixed, ranked);
+  robust_ds_ = ds;
+  for (size_t e = 0; e < m; ++e) robust_ds_.pose_pose[e].weight = robust->w[e];
+  rc = init(robust_ds_, o);
+  return rc ? rc : robust_finish();
 }
 
-// Agent::updateMeasurementWeights for every agent (ref src/Agent.cpp:1397-1441): the weights of the current iterate
-// (k_robust_weights reads the mirror Xg in the RA ordering), the data matrices rebuilt, RobustCost::update, optionally X
-// back to the last set_X (robustOptNumResets), acceleration re-initialised
-int RaRbcdSession::update_weights(bool reset_to_initial, int counts[3]) {
-  std::vector<double> w;
-  double cnt[3] = {0, 0, 0};
-  int rc = compute_weights(nullptr, &w, cnt);
-  if (rc) return rc;
-  rc = apply_weights(w, reset_to_initial);
-  if (rc) return rc;
-  if (counts)
-    for (int c = 0; c < 3; ++c) counts[c] = (int)cnt[c];
-  return DCORA_OK;
+int RaRbcdSession::robust_upload_edges() {
+  RobustState &rs = *robust;
+  if (!rs.ranked) {
+    for (size_t e = 0; e < rs.w.size(); ++e) rs.edge_ids.push_back((int)e);
+    return rs.edges.upload_ra(robust_ds_, rs.update);
+  }
+  std::vector<char> own;
+  ra_rank_edges(robust_ds_, opt.rank, opt.world_size, &rs.edge_ids, &own);
+  for (size_t i = 0; i < rs.edge_ids.size(); ++i) rs.owned[(size_t)rs.edge_ids[i]] = own[i];
+  return rs.edges.upload_ra_ranked(robust_ds_, rs.update, rs.edge_ids, own);
 }
 
-// w: the weights of the session's edges (RaRobustSession::edge_ids order), counts as launch_robust_weights gives them
-int RaRbcdSession::compute_weights(double *shared_w, std::vector<double> *w, double counts[3]) {
-  RaRobustSession &rs = *robust;
-  if (rs.ranked && !shared_w && !rs.edge_ids.empty()) {
-    set_last_error("ra_rbcd robust: a ranked session's weights are computed by its exchange "
-                   "(dcora_exchange_update_weights)");
-    return DCORA_ERR_UNSUPPORTED;
-  }
-  DCORA_HIP(hipSetDevice(opt.device));
-  for (const RaAgentDev &a : agents)
-    if (a.own_st) DCORA_HIP(hipStreamSynchronize(a.own_st));  // the mirror is complete
-  const size_t m = rs.edge_ids.size();
-  w->assign(m, 0.0);
-  for (int c = 0; c < 3; ++c) counts[c] = 0;
-  if (m) {
-    launch_robust_weights(st, rs.edges, r, Xg.p, rs.params, rs.cost.mu(), shared_w);
-    DCORA_HIP(hipGetLastError());
-    DCORA_HIP(hipMemcpyAsync(w->data(), rs.edges.w.p, sizeof(double) * m, hipMemcpyDeviceToHost, st));
-    DCORA_HIP(hipMemcpyAsync(counts, rs.edges.counts.p, sizeof(double) * 3, hipMemcpyDeviceToHost, st));
-  }
-  DCORA_HIP(hipStreamSynchronize(st));
-  return DCORA_OK;
+int RaRbcdSession::robust_rebuild(const std::vector<double> &w) {
+  HostRADataset next = robust_ds_;
+  for (size_t e = 0; e < w.size(); ++e) next.pose_pose[e].weight = w[e];
+  return assemble(next, false);
 }
 
-int RaRbcdSession::apply_weights(const std::vector<double> &w, bool reset_to_initial) {
-  RaRobustSession &rs = *robust;
-  HostRADataset next = rs.ds;
-  for (size_t i = 0; i < rs.edge_ids.size(); ++i) next.pose_pose[(size_t)rs.edge_ids[i]].weight = w[i];
-  const int rc = adopt_weights(next, true, reset_to_initial);
-  if (rc) return rc;
-  rs.cost.update();
-  rs.updates++;
-  team_weights_updated();  // (ref src/Agent.cpp:1418-1424)
-  return DCORA_OK;
-}
-
-// The shared tail of both ways to change weights: the matrices rebuilt for ds (rs.ds with the new weights), the device's
-// weights made the ones the matrices hold -- the old ones after a refusal, the new ones unless the device computed them
-// itself (from_device) --, optionally X back to the last set_X, acceleration re-initialised (Agent::
-// initializeAcceleration, ref src/Agent.cpp:1178-1187: XPrev = V = Y = X, gamma = alpha = 0; the round counter goes on)
-int RaRbcdSession::adopt_weights(HostRADataset &ds, bool from_device, bool reset_to_initial) {
-  RaRobustSession &rs = *robust;
-  const size_t m_pp = ds.pose_pose.size(), m = rs.edge_ids.size();
-  int rc = DCORA_OK;
-  // a pattern holds every entry of its creation weights; only a weight that was 0 then can reach outside it
-  for (size_t e = 0; e < m_pp && !rc; ++e)
-    if (rs.meas_zero[e] && ds.pose_pose[e].weight != 0.0) {
-      set_last_error("ra_rbcd robust: a weight that was 0 at creation cannot become nonzero (the session's patterns "
-                     "do not hold that measurement)");
-      rc = DCORA_ERR_BAD_ARG;
-    }
-  DCORA_HIP(hipSetDevice(opt.device));
-  // nothing of the session is in flight while its matrices and preconditioner images change
-  for (const RaAgentDev &a : agents)
-    if (a.own_st) DCORA_HIP(hipStreamSynchronize(a.own_st));
-  DCORA_HIP(hipStreamSynchronize(st));
-  if (!rc) rc = assemble(ds, false);
-  if (!rc) std::swap(rs.ds.pose_pose, ds.pose_pose);
-  if (m && (rc || !from_device)) {
-    std::vector<double> held(m);
-    for (size_t i = 0; i < m; ++i) held[i] = rs.ds.pose_pose[(size_t)rs.edge_ids[i]].weight;
-    DCORA_HIP(hipMemcpy(rs.edges.w.p, held.data(), sizeof(double) * m, hipMemcpyHostToDevice));
-  }
-  if (rc) return rc;
-  if (team) team_refresh_counts();
-  if (reset_to_initial)
-    DCORA_HIP(hipMemcpyAsync(Xg.p, rs.X_initial.p, sizeof(double) * (size_t)r * k, hipMemcpyDeviceToDevice, st));
-  rc = gather_agents();  // (after a reset the agents' own X comes from the mirror; otherwise it is what they hold)
+int RaRbcdSession::robust_restart_acceleration() {
+  const int rc = gather_agents();  // (after a reset the agents' own X comes from the mirror; otherwise it is what they hold)
   if (rc) return rc;
   DCORA_HIP(hipStreamSynchronize(st));
   gamma = alpha = 0;
   return DCORA_OK;
-}
-
-int RaRbcdSession::set_weights(const double *w) {
-  RaRobustSession &rs = *robust;
-  const size_t m = rs.ds.pose_pose.size();
-  for (size_t e = 0; e < m; ++e)
-    if (!std::isfinite(w[e]) || w[e] < 0) {
-      set_last_error("ra_rbcd robust: weights must be finite and >= 0");
-      return DCORA_ERR_BAD_ARG;
-    }
-  HostRADataset next = rs.ds;
-  for (size_t e = 0; e < m; ++e) next.pose_pose[e].weight = w[e];
-  return adopt_weights(next, false, false);
-}
-
-int RaRbcdSession::get_weights(double *w) const {
-  const RaRobustSession &rs = *robust;
-  if (rs.ranked)
-    for (size_t e = 0; e < rs.ds.pose_pose.size(); ++e) w[e] = std::nan("");
-  for (int e : rs.edge_ids) w[e] = rs.ds.pose_pose[(size_t)e].weight;
-  return DCORA_OK;
-}
-
-bool RaRbcdSession::weight_owned(size_t e, double *w) const {
-  *w = robust->ds.pose_pose[e].weight;
-  return robust->owned[e] != 0;
 }
 
 int RaRbcdSession::gather_agents() {
@@ -677,13 +548,6 @@ int RaRbcdSession::team_launch_rel_change(const std::vector<int> &ids) {
     launch_rel_change_ra(st, r, set, team->rel_dev);
   DCORA_HIP(hipGetLastError());
   return DCORA_OK;
-}
-
-// A rank keeps current weights only of the measurements touching its hosted agents: on a team of a job the counts of
-// all R agents come from the exchange's copy of the job's weights, which is in pose-pose order like q.id.
-double RaRbcdSession::team_lc_weight(const TeamLoopClosure &q) const {
-  if (q.id < 0) return q.w0;  // pose-landmark measurements and ranges: never re-weighted
-  return team->job_w ? team->job_w[(size_t)q.id] : robust ? robust->ds.pose_pose[(size_t)q.id].weight : q.w0;
 }
 
 int RaRbcdSession::x_stage_hosted(double *host_area) {

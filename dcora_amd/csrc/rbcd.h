@@ -34,28 +34,6 @@ struct AgentDev : AgentCore {    // prob: Q_bb, (Q_bb + 0.1 I)^-1, solver worksp
   bool last_skipped = false;
 };
 
-// Robust state of a session created by dcora_rbcd_create_robust (world_size 1) or dcora_rbcd_create_robust_ranks (one
-// rank of a job, whose updates are collective: Exchange::update_weights): the agents' GNC loop inside one live session
-// (Agent::initializeRobustOptimization / updateMeasurementWeights, ref src/Agent.cpp:1332-1346, 1397-1441).
-// A weight change rebuilds the VALUES of Q_bb, the coupling blocks and the central Q on their creation patterns (a
-// weight of 0 leaves explicit zeros), and the preconditioners through the path creation takes.  A rank's matrices hold
-// only the edges touching its hosted agents: the weights of all other edges in `meas` are not kept up to date.
-struct RobustSession {
-  explicit RobustSession(const dcora_robust_params &p) : cost(p), params(p) {}
-  RobustCost cost;
-  dcora_robust_params params;
-  int updates = 0;
-  std::vector<PoseMeas> meas;    // the dataset (global pose indices) with the current weights
-  std::vector<char> update;      // loop closures whose weight is not fixed: what updateMeasurementWeights rewrites
-  std::vector<char> meas_zero;   // weight 0 at creation: the patterns do not hold these measurements
-  RobustEdges edges;             // device copy of the measurements and of the weights
-  bool ranked = false;           // created by dcora_rbcd_create_robust_ranks
-  std::vector<int> edge_ids;     // the measurements in `edges` (dataset order): all, or those touching a hosted agent
-  DevBuf<double> X_initial;      // the last set_X (robustOptNumResets: setXToInitialGuess)
-  std::vector<HostCsr> Qpat, Cpat;  // creation patterns (rp, ci) of every hosted agent's Q_bb and coupling block
-  HostCsr central_pat;
-};
-
 class RbcdSession : public SessionCore {
  public:
   int d = 0, n = 0;
@@ -77,33 +55,16 @@ class RbcdSession : public SessionCore {
   RbcdSession() : SessionCore("rbcd") { R = 1; }
   ~RbcdSession();
   int init(const HostDataset &ds, const dcora_rbcd_options &o);
-  // robust sessions: weight 1 on every loop closure that is not fixed (fixed: m flags or null), then init
-  std::unique_ptr<RobustSession> robust;
-  // ranked: a rank of a multi-rank job (world_size >= 1), its weight updates driven by the exchange
+  // robust sessions (RobustState, session_core.h): weight 1 on every loop closure that is not fixed (fixed: m flags or
+  // null), then init.  ranked: a rank of a multi-rank job (world_size >= 1), its weight updates driven by the exchange
   int init_robust(const HostDataset &ds, const dcora_rbcd_options &o, const dcora_robust_params &p, const int *fixed,
                   bool ranked = false);
-  // updateMeasurementWeights on the current iterate; counts (may be null): accepted, rejected, undecided closures
-  int update_weights(bool reset_to_initial, int counts[3]);
-  // its two halves: the weights of the session's edges on the device (ranked: the owned ones also into shared_w,
-  // counts over the owned ones), then the matrices rebuilt and the rest of the update
-  int compute_weights(double *shared_w, std::vector<double> *w, double counts[3]) override;
-  int apply_weights(const std::vector<double> &w, bool reset_to_initial) override;
-  // all m weights; refused (session untouched) when one is negative or not finite
-  int set_weights(const double *w) override;
-  bool weights_ranked() const override { return robust && robust->ranked; }
-  size_t weights_count() const override { return robust ? robust->meas.size() : 0; }
-  bool weight_owned(size_t e, double *w) const override {
-    const PoseMeas &q = robust->meas[e];
-    *w = q.weight;
-    return agents[(size_t)P.robot_of(q.p1)].hosted;
-  }
-  int get_weights(double *w) const;  // ranked: NaN for the edges touching no hosted agent
   int set_X(const double *Xh) override;
   int get_X(double *Xh);
   int set_acceleration(bool on);
   int phase_nonselected(int selected) override;
   int phase_selected(int selected) override;
-  int evaluate_central(double *cost2, double *gradnorm, double *block_norms, int *next_selected);
+  int evaluate(double *cost2, double *gradnorm, double *block_norms, int *next_selected);
   int phase_evaluate_dev(double *out_dev) override;
   int iterate(int selected, double *cost2, double *gradnorm, double *block_norms, int *next_selected);
   // Agent::iterate(doOptimization) of one agent; the agents of a session advance in lockstep (one call per agent
@@ -115,9 +76,6 @@ class RbcdSession : public SessionCore {
   int agent_update_neighbor(int agent, int neighbor, int count, const int *frames, const double *poses, bool aux);
   std::vector<int> agent_it;  // Agent::iteration_number() of every agent
   int agent_iteration_number(int agent) const;
-  // ---- the team protocol (session_core.h), one process or a rank of a job alike
-  bool team_robust() const override { return robust && robust->params.cost_type != DCORA_ROBUST_L2; }
-  int team_weight_updates() const override { return robust ? robust->updates : 0; }
   long chain_launches = 0;  // kernel launches of the chain's wrappers enqueued by iterate() (debug counter)
   int pack_public(int agent, double *packed_dev);
   int unpack_public(int agent, const double *packed_dev);
@@ -126,7 +84,6 @@ class RbcdSession : public SessionCore {
   long num_cols() const override { return (long)(d + 1) * n; }
   int dim() const override { return d; }
   DeviceProblem *central_problem() override { return central.get(); }
-  const HostCsr *central_pattern() const override { return robust ? &robust->central_pat : nullptr; }
   int cert_block() const override { return d + 1; }
   int x_stage_hosted(double *host_area) override;
 
@@ -158,10 +115,8 @@ class RbcdSession : public SessionCore {
   int tick_done(const std::vector<AgentCore *> &work) override;
   // the session kind's part of the team protocol (session_core.h)
   int team_launch_rel_change(const std::vector<int> &ids) override;
-  double team_lc_weight(const TeamLoopClosure &q) const override;
   bool team_last_success(int agent) const override { return !agents[(size_t)agent].last_skipped; }
   int team_iteration_number(int agent) const override { return agent_iteration_number(agent); }
-  int team_update_weights(bool reset_to_initial) override { return update_weights(reset_to_initial, nullptr); }
   int team_iterate(int selected, double *cost2, double *gradnorm, int *next_selected) override {
     return iterate(selected, cost2, gradnorm, nullptr, next_selected);
   }
@@ -178,9 +133,11 @@ class RbcdSession : public SessionCore {
   int attach_preconditioners(const std::vector<HostCsr> &Q, const std::function<int(size_t)> &attach);
   std::chrono::steady_clock::time_point t0_;  // init began
   void lap(const char *what) const;
-  int rebuild_values(const std::vector<PoseMeas> &meas);
-  int adopt_weights(std::vector<PoseMeas> &meas, bool from_device, bool reset_to_initial);
-  int initialize_acceleration();
+  // a robust session's part (session_core.h)
+  HostDataset robust_ds_;  // the dataset (global pose indices) as created; the weights live in robust->w
+  int robust_upload_edges() override;
+  int robust_rebuild(const std::vector<double> &w) override;
+  int robust_restart_acceleration() override;
 };
 
 }  // namespace dcora

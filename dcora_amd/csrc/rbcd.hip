@@ -402,97 +402,61 @@ int RbcdSession::lift_scatter_block(AgentCore &core, int rows, const double *blo
   return DCORA_OK;
 }
 
-// ---- robust sessions -------------------------------------------------------------------------------------------
-// Agent::initializeRobustOptimization for every agent (ref src/Agent.cpp:1332-1346): weight 1 on every loop closure
-// whose weight is not fixed.  A loop closure is every measurement but odometry, i.e. but p2 == p1 + 1 inside one agent
-// of the contiguous partition (driver.loop_closure_mask).  With weights 1 the patterns are the largest any later
-// weights can give: they are kept, and a weight change only rewrites values.
-// A rank of a multi-rank job (ranked) builds the patterns of its hosted agents only and uploads the edges touching them.
+// ---- robust sessions (RobustState, session_core.h): what is this kind's own -----------------------------------------
+// A loop closure is every measurement but odometry, i.e. but p2 == p1 + 1 inside one agent of the contiguous partition
+// (driver.loop_closure_mask).  A rank of a multi-rank job (ranked) builds the patterns of its hosted agents only and
+// uploads the edges touching them.
 int RbcdSession::init_robust(const HostDataset &ds, const dcora_rbcd_options &o, const dcora_robust_params &p,
                              const int *fixed, bool ranked) {
-  if (o.world_size != 1 && !ranked) {
-    set_last_error("rbcd robust: only single-process sessions (world_size 1) update weights here; a multi-rank job "
-                   "creates its sessions with dcora_rbcd_create_robust_ranks");
-    return DCORA_ERR_UNSUPPORTED;
-  }
   if (o.num_robots < 1 || ds.n / o.num_robots < 1) {
     set_last_error("rbcd: bad num_robots / rank / world_size");
     return DCORA_ERR_BAD_ARG;
   }
-  if (p.cost_type < DCORA_ROBUST_L2 || p.cost_type > DCORA_ROBUST_GNC_TLS) {
-    set_last_error("rbcd robust: unknown robust cost type");
-    return DCORA_ERR_BAD_ARG;
-  }
-  for (const PoseMeas &q : ds.meas)
-    if (q.p1 < 0 || q.p1 >= ds.n || q.p2 < 0 || q.p2 >= ds.n) {
-      set_last_error("rbcd robust: pose index out of range");
-      return DCORA_ERR_BAD_ARG;
-    }
-  robust.reset(new RobustSession(p));
-  RobustSession &rs = *robust;
+  int rc = robust_check_args(ds.meas, ds.n, o, p, ranked);
+  if (rc) return rc;
   Partition Pt;
   Pt.R = o.num_robots;
   Pt.n = ds.n;
   Pt.per = ds.n / o.num_robots;
-  HostDataset rds = ds;
-  const size_t m = rds.meas.size();
-  rs.update.assign(m, 0);
+  const size_t m = ds.meas.size();
+  std::vector<char> lc(m);
   for (size_t e = 0; e < m; ++e) {
-    PoseMeas &q = rds.meas[e];
-    const bool odometry = Pt.robot_of(q.p1) == Pt.robot_of(q.p2) && q.p2 == q.p1 + 1;
-    if (odometry || (fixed && fixed[e])) continue;
-    rs.update[e] = 1;
-    q.weight = 1.0;
+    const PoseMeas &q = ds.meas[e];
+    lc[e] = !(Pt.robot_of(q.p1) == Pt.robot_of(q.p2) && q.p2 == q.p1 + 1);
   }
-  rs.meas = rds.meas;
-  rs.meas_zero.assign(m, 0);
-  for (size_t e = 0; e < m; ++e) rs.meas_zero[e] = rds.meas[e].weight == 0.0;
-  rs.Qpat.assign((size_t)o.num_robots, HostCsr());
-  rs.Cpat.assign((size_t)o.num_robots, HostCsr());
-  int rc = init(rds, o);
-  if (rc) return rc;
-  rs.ranked = ranked;
-  if (ranked) {
-    // the edges touching a hosted agent; the rank owns those whose p1 it hosts (every edge has one owner in the job)
-    std::vector<char> own;
-    for (size_t e = 0; e < m; ++e) {
-      const PoseMeas &q = rds.meas[e];
-      const bool h1 = agents[(size_t)P.robot_of(q.p1)].hosted, h2 = agents[(size_t)P.robot_of(q.p2)].hosted;
-      if (!h1 && !h2) continue;
-      rs.edge_ids.push_back((int)e);
-      own.push_back(h1 ? 1 : 0);
-    }
-    rc = rs.edges.upload_ranked(rds, rs.update, rs.edge_ids, own);
-  } else {
-    for (size_t e = 0; e < m; ++e) rs.edge_ids.push_back((int)e);
-    rc = rs.edges.upload(rds, rs.update);
-  }
-  if (rc) return rc;
-  DCORA_HIP(rs.X_initial.alloc((size_t)r * (d + 1) * n));
-  DCORA_HIP(hipMemsetAsync(rs.X_initial.p, 0, sizeof(double) * (size_t)r * (d + 1) * n, st));
-  DCORA_HIP(hipStreamSynchronize(st));
-  return DCORA_OK;
+  robust_begin(ds.meas, lc, p, fixed, ranked);
+  robust_ds_ = ds;
+  for (size_t e = 0; e < m; ++e) robust_ds_.meas[e].weight = robust->w[e];
+  robust->Qpat.assign((size_t)o.num_robots, HostCsr());
+  robust->Cpat.assign((size_t)o.num_robots, HostCsr());
+  rc = init(robust_ds_, o);
+  return rc ? rc : robust_finish();
 }
 
-// Graph::clearDataMatrices + constructDataMatrices with new weights (ref src/Agent.cpp:1416) through the assembly of
-// creation.  The matrices as the builders give them (no explicit zeros) go to the preconditioners, so the cache sees the
-// keys of a fresh session: a new image is attached, an image somebody else still holds is never written.  Their values
-// scattered onto the creation patterns (a weight of 0 leaves explicit zeros) are what is uploaded.  Together: every
-// value of the re-weighted session equals a fresh session's bit for bit.
-int RbcdSession::rebuild_values(const std::vector<PoseMeas> &meas) {
-  RobustSession &rs = *robust;
-  // a pattern holds every entry of its creation weights; only a weight that was 0 then can reach outside it
-  for (size_t e = 0; e < meas.size(); ++e)
-    if (rs.meas_zero[e] && meas[e].weight != 0.0) {
-      set_last_error("rbcd robust: a weight that was 0 at creation cannot become nonzero (the session's patterns "
-                     "do not hold that measurement)");
-      return DCORA_ERR_BAD_ARG;
-    }
-  DCORA_HIP(hipSetDevice(opt.device));
-  // nothing of the session is in flight while its matrices and preconditioner images change
-  for (const AgentDev &a : agents)
-    if (a.own_st) DCORA_HIP(hipStreamSynchronize(a.own_st));
-  DCORA_HIP(hipStreamSynchronize(st));
+// the edges touching a hosted agent (a single process: all); the rank owns those whose p1 it hosts
+int RbcdSession::robust_upload_edges() {
+  RobustState &rs = *robust;
+  std::vector<char> own;
+  for (size_t e = 0; e < robust_ds_.meas.size(); ++e) {
+    const PoseMeas &q = robust_ds_.meas[e];
+    const bool h1 = agents[(size_t)P.robot_of(q.p1)].hosted, h2 = agents[(size_t)P.robot_of(q.p2)].hosted;
+    rs.owned[e] = h1 ? 1 : 0;
+    if (!h1 && !h2) continue;
+    rs.edge_ids.push_back((int)e);
+    own.push_back(rs.owned[e]);
+  }
+  return rs.ranked ? rs.edges.upload_ranked(robust_ds_, rs.update, rs.edge_ids, own)
+                   : rs.edges.upload(robust_ds_, rs.update);
+}
+
+// Through the assembly of creation.  The matrices as the builders give them (no explicit zeros) go to the
+// preconditioners, so the cache sees the keys of a fresh session: a new image is attached, an image somebody else still
+// holds is never written.  Their values scattered onto the creation patterns (a weight of 0 leaves explicit zeros) are
+// what is uploaded.  Together: every value of the re-weighted session equals a fresh session's bit for bit.
+int RbcdSession::robust_rebuild(const std::vector<double> &w) {
+  RobustState &rs = *robust;
+  std::vector<PoseMeas> meas = robust_ds_.meas;
+  for (size_t e = 0; e < meas.size(); ++e) meas[e].weight = w[e];
   const char *outside = "rbcd robust: the weights give a matrix entry outside the session's pattern";
   // host images of the uploads (by agent id), alive until the stream has been synchronised
   std::vector<HostCsr> Qs((size_t)R), Cs((size_t)R);
@@ -529,9 +493,8 @@ int RbcdSession::rebuild_values(const std::vector<PoseMeas> &meas) {
   return DCORA_OK;
 }
 
-// Agent::initializeAcceleration for every agent (ref src/Agent.cpp:1178-1187): XPrev = V = Y = X, gamma = alpha = 0,
 // no staged Nesterov step; unlike set_acceleration the iteration counter goes on (mIterationNumber)
-int RbcdSession::initialize_acceleration() {
+int RbcdSession::robust_restart_acceleration() {
   staged_selected_ = -1;
   const size_t B = sizeof(double) * (size_t)r * (d + 1) * n;
   DCORA_HIP(hipMemcpyAsync(Vg.p, Xg.p, B, hipMemcpyDeviceToDevice, st));
@@ -542,98 +505,6 @@ int RbcdSession::initialize_acceleration() {
   seq_advanced_ = false;
   pending_reset_ = false;
   for (AgentDev &a : agents) a.v_feasible = false;
-  return DCORA_OK;
-}
-
-// Agent::updateMeasurementWeights for every agent (ref src/Agent.cpp:1397-1441): the weights of the current iterate
-// (k_robust_weights reads the mirror Xg), the data matrices rebuilt, RobustCost::update, optionally X back to the
-// last set_X (robustOptNumResets), acceleration re-initialised
-int RbcdSession::update_weights(bool reset_to_initial, int counts[3]) {
-  std::vector<double> w;
-  double cnt[3] = {0, 0, 0};
-  int rc = compute_weights(nullptr, &w, cnt);
-  if (rc) return rc;
-  rc = apply_weights(w, reset_to_initial);
-  if (rc) return rc;
-  if (counts)
-    for (int c = 0; c < 3; ++c) counts[c] = (int)cnt[c];
-  return DCORA_OK;
-}
-
-// w: the weights of the session's edges (RobustSession::edge_ids order), counts as launch_robust_weights gives them
-int RbcdSession::compute_weights(double *shared_w, std::vector<double> *w, double counts[3]) {
-  RobustSession &rs = *robust;
-  if (rs.ranked && !shared_w && !rs.edge_ids.empty()) {
-    set_last_error("rbcd robust: a ranked session's weights are computed by its exchange (dcora_exchange_update_weights)");
-    return DCORA_ERR_UNSUPPORTED;
-  }
-  DCORA_HIP(hipSetDevice(opt.device));
-  for (const AgentDev &a : agents)
-    if (a.own_st) DCORA_HIP(hipStreamSynchronize(a.own_st));
-  const size_t m = rs.edge_ids.size();
-  w->assign(m, 0.0);
-  for (int c = 0; c < 3; ++c) counts[c] = 0;
-  if (m) {
-    launch_robust_weights(st, rs.edges, r, Xg.p, rs.params, rs.cost.mu(), shared_w);
-    DCORA_HIP(hipGetLastError());
-    DCORA_HIP(hipMemcpyAsync(w->data(), rs.edges.w.p, sizeof(double) * m, hipMemcpyDeviceToHost, st));
-    DCORA_HIP(hipMemcpyAsync(counts, rs.edges.counts.p, sizeof(double) * 3, hipMemcpyDeviceToHost, st));
-  }
-  DCORA_HIP(hipStreamSynchronize(st));
-  return DCORA_OK;
-}
-
-// The shared tail of both ways to change weights: the matrices rebuilt for meas (rs.meas with the new weights), the
-// device's weights made the ones the matrices hold -- the old ones after a refusal, the new ones unless the device
-// computed them itself (from_device) --, optionally X back to the last set_X, acceleration re-initialised
-int RbcdSession::adopt_weights(std::vector<PoseMeas> &meas, bool from_device, bool reset_to_initial) {
-  RobustSession &rs = *robust;
-  const int rc = rebuild_values(meas);
-  if (!rc) rs.meas.swap(meas);
-  const size_t m = rs.edge_ids.size();
-  if (m && (rc || !from_device)) {
-    std::vector<double> held(m);
-    for (size_t i = 0; i < m; ++i) held[i] = rs.meas[(size_t)rs.edge_ids[i]].weight;
-    DCORA_HIP(hipMemcpy(rs.edges.w.p, held.data(), sizeof(double) * m, hipMemcpyHostToDevice));
-  }
-  if (rc) return rc;
-  if (team) team_refresh_counts();
-  if (reset_to_initial)
-    DCORA_HIP(hipMemcpyAsync(Xg.p, rs.X_initial.p, sizeof(double) * (size_t)r * (d + 1) * n, hipMemcpyDeviceToDevice, st));
-  return initialize_acceleration();
-}
-
-int RbcdSession::apply_weights(const std::vector<double> &w, bool reset_to_initial) {
-  RobustSession &rs = *robust;
-  std::vector<PoseMeas> meas = rs.meas;
-  for (size_t i = 0; i < rs.edge_ids.size(); ++i) meas[(size_t)rs.edge_ids[i]].weight = w[i];
-  const int rc = adopt_weights(meas, true, reset_to_initial);
-  if (rc) return rc;
-  rs.cost.update();
-  rs.updates++;
-  // mLatestWeightUpdateIteration, mRobustOptInnerIter = 0, mTeamStatus.clear() (ref src/Agent.cpp:1418-1424)
-  team_weights_updated();
-  return DCORA_OK;
-}
-
-int RbcdSession::set_weights(const double *w) {
-  RobustSession &rs = *robust;
-  const size_t m = rs.meas.size();
-  for (size_t e = 0; e < m; ++e)
-    if (!std::isfinite(w[e]) || w[e] < 0) {
-      set_last_error("rbcd robust: weights must be finite and >= 0");
-      return DCORA_ERR_BAD_ARG;
-    }
-  std::vector<PoseMeas> meas = rs.meas;
-  for (size_t e = 0; e < m; ++e) meas[e].weight = w[e];
-  return adopt_weights(meas, false, false);
-}
-
-int RbcdSession::get_weights(double *w) const {
-  const RobustSession &rs = *robust;
-  if (rs.ranked)
-    for (size_t e = 0; e < rs.meas.size(); ++e) w[e] = std::nan("");
-  for (int e : rs.edge_ids) w[e] = rs.meas[(size_t)e].weight;
   return DCORA_OK;
 }
 
@@ -949,7 +820,7 @@ int RbcdSession::agent_set_X(int agent, const double *Xh) {
 }
 
 // central evaluation of the driver (ref examples/MultiRobotExample.cpp:264-305): 2 f, |rgrad|, greedy selection
-int RbcdSession::evaluate_central(double *cost2, double *gradnorm, double *block_norms, int *next_selected) {
+int RbcdSession::evaluate(double *cost2, double *gradnorm, double *block_norms, int *next_selected) {
   if (!central) {
     set_last_error("central evaluation needs world_size == 1");
     return DCORA_ERR_UNSUPPORTED;
@@ -1051,7 +922,7 @@ int RbcdSession::iterate(int selected, double *cost2, double *gradnorm, double *
   rc = phase_selected(selected);
   if (rc) return rc;
   int nxt = selected;
-  rc = evaluate_central(cost2, gradnorm, block_norms, &nxt);
+  rc = evaluate(cost2, gradnorm, block_norms, &nxt);
   chain_launches += g_chain_launches.load(std::memory_order_relaxed) - launches0;
   if (rc) return rc;
   // greedy selection only when the selected agent has neighbours (:290-292)
@@ -1153,11 +1024,6 @@ int RbcdSession::team_launch_rel_change(const std::vector<int> &ids) {
     launch_rel_change(st, r, d, Xg.p, XPrevg.p, pose_start.p, set, team->rel_dev);
   DCORA_HIP(hipGetLastError());
   return DCORA_OK;
-}
-
-// (a rank keeps only the weights of the edges touching its agents up to date: the job's come from its exchange)
-double RbcdSession::team_lc_weight(const TeamLoopClosure &q) const {
-  return team->job_w ? team->job_w[(size_t)q.id] : robust ? robust->meas[(size_t)q.id].weight : q.w0;
 }
 
 }  // namespace dcora

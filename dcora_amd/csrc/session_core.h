@@ -11,6 +11,8 @@
 #include <vector>
 
 #include "device_problem.h"
+#include "host_robust.h"
+#include "robust.h"
 #include "session_cert.h"
 #include "team_rules.h"
 
@@ -63,6 +65,32 @@ struct TeamState {
                                  // L2 job, whose counts come from the creation weights
 };
 
+// Robust state of a session created by dcora_rbcd_create_robust / dcora_ra_rbcd_create_robust (world_size 1) or by
+// dcora_rbcd_create_robust_ranks / dcora_ra_rbcd_create_robust_ranks (one rank of a job, whose updates are collective:
+// Exchange::update_weights): the agents' GNC loop inside one live session (Agent::initializeRobustOptimization /
+// updateMeasurementWeights, ref src/Agent.cpp:1332-1346, 1397-1441).  The job's measurements are the re-weightable ones
+// in the kind's order: the dataset's, or a range-aided one's pose-pose.  A weight change rebuilds the VALUES of every
+// agent's matrix, of its coupling block and of the central Q on their creation patterns (a weight of 0 leaves explicit
+// zeros), and the preconditioners through the path creation takes.  A rank's matrices hold only the measurements
+// touching its hosted agents: the weight it keeps for any other is the last it was told and reaches no device matrix.
+struct RobustState {
+  explicit RobustState(const dcora_robust_params &p) : cost(p), params(p) {}
+  RobustCost cost;
+  dcora_robust_params params;
+  int updates = 0;
+  std::vector<double> w;         // the job's current weights
+  std::vector<char> update;      // loop closures whose weight is not fixed: what updateMeasurementWeights rewrites
+  std::vector<char> meas_zero;   // weight 0 at creation: the patterns do not hold these measurements
+  RobustEdges edges;             // device copy of the measurements and of the weights
+  bool ranked = false;           // created by one of the _create_robust_ranks entries
+  std::vector<int> edge_ids;     // the measurements in `edges` (job order): all, or those touching a hosted agent
+  std::vector<char> owned;       // per measurement: this rank hosts the agent of p1 (every one has one owner in the job)
+  DevBuf<double> X_initial;      // the last set_X, laid out like the mirror (robustOptNumResets: setXToInitialGuess)
+  std::vector<HostCsr> Qpat, Cpat;  // creation patterns (rp, ci) of every hosted agent's matrix and coupling block
+  HostCsr central_pat;
+  HostCsr live_pat;  // range-aided: the central Q's entries as the current weights give them (what certify reads)
+};
+
 class SessionCore {
  public:
   int r = 0, R = 0;  // relaxation rank (rows of the mirror), agents
@@ -77,6 +105,7 @@ class SessionCore {
   double setup_ms = 0;
 
   explicit SessionCore(const char *tag) : tag_(tag) {}
+  const char *tag() const { return tag_; }
   virtual ~SessionCore() {}
   virtual AgentCore &agent_core(int a) = 0;
   virtual long num_cols() const = 0;                  // columns of the mirror (the whole problem)
@@ -156,23 +185,28 @@ class SessionCore {
   int lift_trial_commit(double *redim_ms);
   void lift_trial_abort();
   virtual DeviceProblem *central_problem() = 0;                        // null on a rank of a multi-rank job
-  virtual const HostCsr *central_pattern() const { return nullptr; }  // host copy of its pattern, where one is kept
-  // the stored entries the current weights give, where the session certifies over those alone (session_cert.h)
-  virtual const HostCsr *central_live_pattern() const { return nullptr; }
   virtual int cert_block() const = 0;  // unknowns the factorisation orders together (d + 1 for poses)
 
-  // ---- what the exchange's collective weight update needs from a robust session of either kind (exchange.h).  The
-  // job's measurements are the re-weightable ones in the kind's order: the dataset's, or a range-aided one's pose-pose.
-  // The calls below are a robust session's (the exchange makes them on a ranked one only).
-  virtual bool weights_ranked() const = 0;  // a ranked robust session: the exchange changes its weights
-  virtual size_t weights_count() const = 0;  // measurements of the job (doubles of the weights area)
-  // the weights of the session's edges on the device from the mirror (ranked: the owned ones also into shared_w,
-  // counts over the owned ones), then the matrices rebuilt and the rest of the update
-  virtual int compute_weights(double *shared_w, std::vector<double> *w, double counts[3]) = 0;
-  virtual int apply_weights(const std::vector<double> &w, bool reset_to_initial) = 0;
-  virtual int set_weights(const double *w) = 0;  // all weights_count() of them, checked before anything changes
+  // ---- robust sessions (session_robust.hip), stated once for both kinds; null on a plain session.  The calls below
+  // are a robust session's.
+  std::unique_ptr<RobustState> robust;
+  bool weights_ranked() const { return robust && robust->ranked; }  // the exchange changes its weights
+  size_t weights_count() const { return robust ? robust->w.size() : 0; }  // measurements of the job
+  // updateMeasurementWeights on the current iterate; counts (may be null): accepted, rejected, undecided closures
+  int update_weights(bool reset_to_initial, int counts[3]);
+  // its two halves, which the exchange's collective update calls one by one: the weights of the session's edges on the
+  // device from the mirror (ranked: the owned ones also into shared_w, counts over the owned ones), then the matrices
+  // rebuilt and the rest of the update
+  int compute_weights(double *shared_w, std::vector<double> *w, double counts[3]);
+  int apply_weights(const std::vector<double> &w, bool reset_to_initial);
+  // all weights_count() of them; refused (session untouched) when one is negative or not finite
+  int set_weights(const double *w);
+  int get_weights(double *w) const;  // ranked: NaN for the measurements touching no hosted agent
   // whether this rank owns measurement e (hosts the agent of its first pose); *w: the weight the session holds for it
-  virtual bool weight_owned(size_t e, double *w) const = 0;
+  bool weight_owned(size_t e, double *w) const {
+    *w = robust->w[e];
+    return robust->owned[e] != 0;
+  }
 
   // ---- the team protocol of a single-process session (dcora_rbcd_team_enable / dcora_ra_rbcd_team_enable): the
   // bookkeeping of Agent::iterate's status block, shouldTerminate, shouldUpdateMeasurementWeights and
@@ -181,8 +215,8 @@ class SessionCore {
   int team_enable(const dcora_team_params &p);
   int team_agent_status(int agent, dcora_agent_status *status, int *known);
   int team_decide(int *should_terminate, int *should_update_weights);
-  virtual bool team_robust() const = 0;         // cost type != L2
-  virtual int team_weight_updates() const = 0;  // mWeightUpdateCount
+  bool team_robust() const { return robust && robust->params.cost_type != DCORA_ROBUST_L2; }
+  int team_weight_updates() const { return robust ? robust->updates : 0; }  // mWeightUpdateCount
   int team_inner_iter() const { return team_robust() ? inner_rounds : 0; }
   // ---- the half of a rank of a job, of either kind, through its exchange only (Exchange::team_enable): the status area
   // and the job's weights the exchange keeps
@@ -236,6 +270,28 @@ class SessionCore {
   };
   std::unique_ptr<LiftTrial> lift_trial_;  // between lift_trial_begin and commit / abort
 
+  // robust sessions, for the kinds' init_robust.  robust_check_args: what both kinds refuse.  robust_begin: the state,
+  // with weight 1 on every loop closure (lc: one flag per measurement) that is not fixed (fixed: one flag per
+  // measurement, or null) and the creation weight on the rest; the kind then creates itself from robust->w.
+  // robust_finish: the edges on the device, X_initial.
+  int robust_check_args(const std::vector<PoseMeas> &meas, int num_poses, const dcora_rbcd_options &o,
+                        const dcora_robust_params &p, bool ranked) const;
+  void robust_begin(const std::vector<PoseMeas> &meas, const std::vector<char> &lc, const dcora_robust_params &p,
+                    const int *fixed, bool ranked);
+  int robust_finish();
+  // the shared tail of both ways to change weights (w: all of the job's, swapped in when they are adopted)
+  int adopt_weights(std::vector<double> &w, bool from_device, bool reset_to_initial);
+  // what a session kind supplies to them:
+  // edge_ids and owned filled (ranked: the measurements touching a hosted agent; else all) and those measurements
+  // uploaded through the kind's entry of RobustEdges
+  virtual int robust_upload_edges() = 0;
+  // Graph::clearDataMatrices + constructDataMatrices (ref src/Agent.cpp:1416) for the job's weights w on the creation
+  // patterns; every stream of the session has been drained
+  virtual int robust_rebuild(const std::vector<double> &w) = 0;
+  // Agent::initializeAcceleration of every agent (ref src/Agent.cpp:1178-1187): XPrev = V = Y = X, gamma = alpha = 0;
+  // the round counter goes on
+  virtual int robust_restart_acceleration() = 0;
+
   // the three things a session kind supplies to the tick
   virtual void tick_begins() {}  // (the set is valid: per-tick resets)
   // G = X_mirror C_a^T, the start point and XPrev of one agent, enqueued on the session's stream
@@ -263,10 +319,9 @@ class SessionCore {
   // what a session kind supplies to the team protocol:
   // its relative-change kernel for these hosted agents, just marked, enqueued on the session's stream
   virtual int team_launch_rel_change(const std::vector<int> &ids) = 0;
-  virtual double team_lc_weight(const TeamLoopClosure &q) const = 0;  // the current weight of one of team_lcs_
+  double team_lc_weight(const TeamLoopClosure &q) const;  // the current weight of one of team_lcs_
   virtual bool team_last_success(int agent) const { return true; }    // `success` of the agent's last local update
   virtual int team_iteration_number(int agent) const { return iteration; }
-  virtual int team_update_weights(bool reset_to_initial) = 0;
   virtual int team_iterate(int selected, double *cost2, double *gradnorm, int *next_selected) = 0;
 
  private:

@@ -47,8 +47,10 @@ int SessionCore::certify(double eta, CertifyResult *out, double *info8) {
   // the mirror is complete: nothing of the session is in flight on an agent's own stream
   for (int a = 0; a < R; ++a)
     if (agent_core(a).own_st) DCORA_HIP(hipStreamSynchronize(agent_core(a).own_st));
-  return session_certify(cert_, *central, central_pattern(), central_live_pattern(), Xg.p, cert_block(), eta, out,
-                         info8);
+  // a robust session keeps a host copy of the central pattern and, where it certifies over those alone, of the stored
+  // entries the current weights give (session_cert.h; an empty live pattern is none)
+  return session_certify(cert_, *central, robust ? &robust->central_pat : nullptr,
+                         robust ? &robust->live_pat : nullptr, Xg.p, cert_block(), eta, out, info8);
 }
 
 int SessionCore::lift(double theta, const double *v, const dcora_lift_params &p, int *escaped, double *info8) {
@@ -634,7 +636,7 @@ int SessionCore::run_team(int *iters_done, double *cost2_trace, double *gradnorm
     if (updated_trace) updated_trace[it] = upd;
     if (upd) {
       const bool reset = team->resets_done < team->params.robust_opt_num_resets;
-      rc = team_update_weights(reset);
+      rc = update_weights(reset, nullptr);
       if (rc) return rc;
       if (reset) team->resets_done++;
       nupd++;
