@@ -928,6 +928,22 @@ class Exchange:
                                                     C.byref(dist)))
         return bool(cert.value), th.value, lm.value, v, mv.value, bool(dist.value)
 
+    def certify_live(self, eta):
+        """The same certificate of the matrices the ranks hold on the device now, with the job's current weights
+        (dcora_exchange_certify_live; SPMD, the same eta on every rank): no Q is passed in, no X crosses to a host.
+        -> (certified, theta, lambda_min of S + eta I, v, matvecs, distributed, info); info: the PSD test's eight
+        numbers (as is_psd_device reports them), "rounds" through the segment's X area, "ms" to the verdict on rank 0"""
+        cert, dist = C.c_int(), C.c_int()
+        th, lm, mv = C.c_double(), C.c_double(), C.c_longlong()
+        v, i10 = np.zeros(self.s.k), np.zeros(10)
+        check(capi.lib().dcora_exchange_certify_live(self.h, float(eta), C.byref(cert), C.byref(th), C.byref(lm),
+                                                     v.ctypes.data_as(C.c_void_p), C.byref(mv), C.byref(dist),
+                                                     i10.ctypes.data_as(C.c_void_p)))
+        info = {"symbolic_ms": i10[0], "numeric_ms": i10[1], "arena_bytes": i10[2], "flops": i10[3],
+                "levels": int(i10[4]), "launches": int(i10[5]), "logdet": i10[6], "lookup_ms": i10[7],
+                "rounds": int(i10[8]), "ms": float(i10[9]), "info10": i10}
+        return bool(cert.value), th.value, lm.value, v, mv.value, bool(dist.value), info
+
     def post(self, agents):
         a = np.ascontiguousarray(agents, dtype=np.int32)
         check(capi.lib().dcora_exchange_post(self.h, a, a.size))

@@ -233,6 +233,10 @@ SIGNATURES = {
     "dcora_exchange_get_weights": (C.c_int, [_vp, _dp]),
     "dcora_exchange_certify": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_double, _PI, _PD, _PD, _dp,
                                          C.POINTER(C.c_longlong), _PI]),
+    "dcora_exchange_certify_live": (C.c_int, [_vp, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dcora_debug_cert_rows": (C.c_int, [C.POINTER(Dims), _ip, _ip, _dp, C.POINTER(Dims), _ip, _dp, C.c_double,
+                                        C.c_longlong, C.c_longlong, C.c_longlong, _vp, _vp, C.POINTER(C.c_longlong),
+                                        C.c_longlong]),
     "dcora_exchange_host_selftest": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, _PD]),
     "dcora_exchange_host_selftest_team": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _PD]),
     "dcora_exchange_team_enable": (C.c_int, [_vp, C.POINTER(TeamParams)]),

@@ -1640,6 +1640,56 @@ int dcora_exchange_certify(dcora_exchange_t ex, int k, const int *rowptr, const 
     return ex->e.certify(nullptr, eta, certified, theta, lambda_min, v, matvecs, distributed);
   });
 }
+// the certificate of the matrices the ranks hold (ref src/DCORA_utils.cpp:1713-1735, 1898-1982,
+// examples/MultiRobotExample.cpp:321-335); a NULL certified is refused inside, like a bad eta, on every rank alike
+int dcora_exchange_certify_live(dcora_exchange_t ex, double eta, int *certified, double *theta, double *lambda_min,
+                                double *v, long long *matvecs, int *distributed, double *info10) {
+  return abi_call({ex}, [&] {
+    return ex->e.certify_live(eta, certified, theta, lambda_min, v, matvecs, distributed, info10);
+  });
+}
+// the table builder of dcora_exchange_certify_live on host arrays, a host loop in the kernel's place
+// (tests/test_certify_ranks_cpu.py)
+int dcora_debug_cert_rows(const dcora_dims *dims, const int *rp, const int *ci, const double *vals,
+                          const dcora_dims *agent_dims, const int *cols, const double *lambda, double eta, long long lo,
+                          long long hi, long long round_size, double *window, unsigned char *written,
+                          long long *nnz_pattern, long long corrupt_entry) {
+  return abi_call({dims, rp, ci, vals, agent_dims, cols, lambda}, [&]() -> int {
+    if (!layout_ok(dims) || !layout_ok(agent_dims)) return bad("dims: layout SE needs l = b = 0");
+    const ManiDesc mg = make_mani(*dims), ma = make_mani(*agent_dims);
+    if (mg.k < 1 || ma.k < 1 || ma.k > mg.k || ma.d != mg.d) return bad("dcora_debug_cert_rows: bad dims");
+    if (rp[0] != 0) return bad("dcora_debug_cert_rows: rowptr[0] must be 0");
+    for (int i = 0; i < mg.k; ++i)
+      if (rp[i + 1] < rp[i]) return bad("dcora_debug_cert_rows: rowptr decreases");
+    for (int p = 0; p < rp[mg.k]; ++p)
+      if (ci[p] < 0 || ci[p] >= mg.k) return bad("dcora_debug_cert_rows: column index out of range");
+    const std::vector<int> own(cols, cols + ma.k);
+    for (int c : own)
+      if (c < 0 || c >= mg.k) return bad("dcora_debug_cert_rows: a column outside the job");
+    const HostCsr Q = view_csr(mg.k, rp, ci, vals);
+    const HostCsr P = dual_certificate_pattern(mg, Q);
+    if (nnz_pattern) *nnz_pattern = P.nnz();
+    HostCsr Qaa, C;
+    extract_agent_blocks(Q, own, &Qaa, &C);
+    CertRowTable t;
+    int rc = build_cert_row_table(P, own, Qaa, C, ma, &t);
+    if (rc) return rc;
+    if (corrupt_entry >= 0 && corrupt_entry < (long long)t.size()) t.src[(size_t)corrupt_entry] = Qaa.nnz() + C.nnz() + 7;
+    rc = check_cert_row_table(t, P.nnz(), Qaa.nnz(), C.nnz(), (long)ma.n * ma.d * ma.d + ma.l);
+    if (rc) return rc;
+    if (lo < 0 || hi < lo || hi > P.nnz()) return bad("dcora_debug_cert_rows: the window leaves the value array");
+    if (hi > lo && (!window || !written)) return bad("null argument");
+    // the job's walk: round c carries [lo + c round_size, lo + (c + 1) round_size), each through its own window base
+    const long long step = round_size > 0 ? round_size : std::max<long long>(hi - lo, 1);
+    for (long long a = lo; a < hi; a += step) {
+      const long long b = std::min(hi, a + step);
+      size_t first = 0, last = 0;
+      cert_row_window(t.pos, (long)a, (long)b, &first, &last);
+      cert_rows_host(t, first, last, Qaa.v.data(), C.v.data(), lambda, eta, (long)a, window + (a - lo), written + (a - lo));
+    }
+    return (int)DCORA_OK;
+  });
+}
 int dcora_exchange_all_ready(dcora_exchange_t ex, int ready, int *all_ready) {
   return abi_call({ex, all_ready}, [&] {
     double notready = ready ? 0.0 : 1.0;

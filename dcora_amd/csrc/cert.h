@@ -44,10 +44,16 @@ class DeviceLanczos {
 };
 
 std::vector<double> min_eig_second_start(const HostCsr &S, uint64_t seed);
+// the spectrum-shifted run would have to resolve min_eig_tol on a spectrum of width lambda_lm: below this ratio a
+// 20-vector Krylov space is given no chance and the shift-and-invert fallback is taken at once (device_min_eig)
+inline bool min_eig_shifted_run_hopeless(double min_eig_tol, double lambda_lm) { return min_eig_tol / lambda_lm < 1e-8; }
 int device_min_eig(const HostCsr &S, int maxit, double min_eig_tol, int ncv, uint64_t seed, int device,
                    LanczosResult *out);
 // (row, col) of Lambda's entries, in the order of launch_lambda_blocks's values (cert.hip)
 void lambda_entries(const ManiDesc &m, std::vector<int> &I, std::vector<int> &J);
+// the pattern of S + eta I over the entries Q stores: Q's entries, the entries of Lambda, every diagonal (no values) --
+// what the host assembly hands to the PSD test and dcora_cert_prepare analyses
+HostCsr dual_certificate_pattern(const ManiDesc &m, const HostCsr &Q);
 int device_dual_certificate(const dcora_dims &dims, const double *Xh, const HostCsr &Q, int device, HostCsr *S);
 int host_is_psd(const HostCsr &S, int block, bool *psd);
 // info8 (may be null): the PSD test's, as device_chol_is_pd fills it

@@ -420,7 +420,7 @@ int device_min_eig(const HostCsr &S, int maxit, double min_eig_tol, int ncv, uin
   // 2e6, the ratio at 5e-10) the reference's run spends its 1000 restarts -- 10 020 matvecs, 0.6 s per certificate here --
   // and then takes the shift-and-invert fallback below anyway; this goes there at once.  The eigenpair returned is the
   // fallback's either way.
-  const bool hopeless = min_eig_tol / lambda_lm < 1e-8;
+  const bool hopeless = min_eig_shifted_run_hopeless(min_eig_tol, lambda_lm);
   if (hopeless) {
     sh.ok = false;
     sh.v.assign((size_t)k, 0.0);
@@ -522,6 +522,19 @@ void lambda_entries(const ManiDesc &m, std::vector<int> &I, std::vector<int> &J)
     I.push_back(m.sphere_col(i));
     J.push_back(m.sphere_col(i));
   }
+}
+
+HostCsr dual_certificate_pattern(const ManiDesc &m, const HostCsr &Q) {
+  std::vector<int> I, J;
+  I.reserve((size_t)Q.nnz() + (size_t)m.n * m.d * m.d + m.l);
+  J.reserve(I.capacity());
+  for (int i = 0; i < Q.n; ++i)
+    for (int p = Q.rp[i]; p < Q.rp[i + 1]; ++p) {
+      I.push_back(i);
+      J.push_back(Q.ci[p]);
+    }
+  lambda_entries(m, I, J);
+  return pattern_of(csr_shift_diag(csr_from_coo(Q.n, Q.n, I, J, std::vector<double>(I.size(), 1.0)), 1.0));
 }
 
 int device_dual_certificate(const dcora_dims &dims, const double *Xh, const HostCsr &Q, int device, HostCsr *S) {

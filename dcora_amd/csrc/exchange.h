@@ -17,6 +17,7 @@
 #include <string>
 #include <vector>
 
+#include "cert_rows.h"
 #include "exchange_slots.h"
 #include "rbcd.h"
 
@@ -28,6 +29,28 @@ enum ExchangeMode { kExchangeIpc = 1, kExchangeStaged = 2 };
 // (DCORA_EXCHANGE_TIMEOUT_S, default 120: a rank that died takes the job down within this time, never a hang)
 double exchange_timeout_s();
 extern std::atomic<int> g_probe_fault_rounds;  // test hook of the link check (dcora_debug_exchange_probe_fault)
+
+// What certify_live keeps between certificates: the job-wide pattern of S + eta I and, per hosted agent, the table of
+// its rows (cert_rows.h) on the device.  Built by the first call; valid for the life of the job.
+struct LiveCertState {
+  struct Agent {
+    int id = 0;
+    std::vector<int> pos_host;  // the table's positions, ascending: which entries a window takes
+    DevBuf<int> pos, src, slot;
+    DevBuf<unsigned char> diag;
+  };
+  bool built = false;
+  HostCsr pat;                 // v: where the values land on rank 0 when the PSD test has refused
+  std::vector<Agent> agents;   // the hosted ones, in agent order
+  DevBuf<double> vals;         // rank 0: the values of S + eta I in pat's CSR order
+  hipEvent_t ready = nullptr;  // rank 0: vals complete (the factorisation runs on a stream of its own)
+  LiveCertState() = default;
+  LiveCertState(const LiveCertState &) = delete;
+  LiveCertState &operator=(const LiveCertState &) = delete;
+  ~LiveCertState() {
+    if (ready) (void)hipEventDestroy(ready);
+  }
+};
 
 class Exchange {
  public:
@@ -49,6 +72,14 @@ class Exchange {
   // allreduce_sum.  v (may be null): the eigenvector, (d+1) n doubles, the same on every rank.
   int certify(const HostCsr *Qglobal, double eta, int *certified, double *theta, double *lambda_min, double *v,
               long long *matvecs, int *distributed);
+  // The same certificate from the matrices the ranks hold on the device NOW (dcora_exchange_certify_live): no Q is
+  // passed in and no X crosses to a host.  Every rank forms the values of its own rows of M = (Q - Lambda) + eta I in
+  // the CSR order of the job-wide pattern (k_cert_rows, gather form, no atomics); they reach rank 0 through the X area
+  // of the segment in rounds of x_doubles entries (kernel end, stream synchronise, barrier, copy, barrier); rank 0
+  // factorises them where they land.  Refused: the row-block Lanczos stage of certify, with M downloaded once on
+  // rank 0.  info10 (may be null): the PSD test's eight, the rounds, ms from entry to the verdict on rank 0.
+  int certify_live(double eta, int *certified, double *theta, double *lambda_min, double *v, long long *matvecs,
+                   int *distributed, double *info10);
   int evaluate(double *cost2, double *gradnorm, double *block_norms, int *next_selected);
   int rbcd_iterate(int selected, double *cost2, double *gradnorm, double *block_norms, int *next_selected);
   int rbcd_tick(const int *set, int count, int allow_adjacent);
@@ -169,6 +200,18 @@ class Exchange {
   int setup_ipc(bool attempt);
   int link_check();
   bool probe_round(uint64_t seq, std::string *why);
+  // the two halves both certificates share (exchange_cert.hip): post and wait of all agents with the Lambda blocks of
+  // the hosted ones; the minimum eigenpair of M = S + eta I by all ranks once the PSD test has refused (M: rank 0's).
+  // skip_hopeless: device_min_eig's rule for the spectrum-shifted run (min_eig_shifted_run_hopeless) holds for the
+  // row-block run too -- certify_live's choice; certify keeps making the run
+  struct CertRows;
+  int cert_rows_begin(CertRows *rows);
+  int cert_min_eigenpair(CertRows &rows, const HostCsr &M, double eta, bool skip_hopeless, double *theta,
+                         double *lambda_min, double *v, long long *matvecs, int *distributed);
+  int live_cert_build();  // the pattern and the tables, on the first certify_live
+  int certify_live_run(double eta, int *certified, double *theta, double *lambda_min, double *v, long long *matvecs,
+                       int *distributed, double *info10);  // certify_live behind its refusals
+  LiveCertState live_;
   int fail(const std::string &msg, int code);   // a transport / peer failure: raises `failed` for every rank
   int usage(const std::string &msg, int code);  // a refused call (bad argument, unsupported): this call only
 };

@@ -83,6 +83,7 @@ class RaRbcdSession : public SessionCore {
   int dim() const override { return d; }
   DeviceProblem *central_problem() override { return central.get(); }
   int cert_block() const override { return 1; }
+  ManiDesc global_manifold() const override { return make_mani(r, d, n, l, b, DCORA_LAYOUT_RA); }
   int x_stage_hosted(double *host_area) override;
 
  private:

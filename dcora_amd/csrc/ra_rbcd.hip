@@ -230,6 +230,8 @@ int RaRbcdSession::assemble(const HostRADataset &ds, bool creation) {
     rc = central->init(dims, Q, nullptr, -1.0, o.device, st);
     if (rc) return rc;
     if (robust) robust->live_pat = robust->central_pat = pattern_of(Q);
+  } else {
+    job_pat = pattern_of(Q);  // (what the job-wide certificate is laid out on: Exchange::certify_live)
   }
   return DCORA_OK;
 }

@@ -85,6 +85,7 @@ class RbcdSession : public SessionCore {
   int dim() const override { return d; }
   DeviceProblem *central_problem() override { return central.get(); }
   int cert_block() const override { return d + 1; }
+  ManiDesc global_manifold() const override { return mg; }
   int x_stage_hosted(double *host_area) override;
 
  private:

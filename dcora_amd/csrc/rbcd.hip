@@ -263,6 +263,10 @@ int RbcdSession::assemble(const MeasSplit &split, const std::function<void(size_
       }
       central_rc = central_ready(build_Q_pgo(d, n, 0, split.global));
       if (central_rc) central_err = dcora_last_error();
+    } else if (job_pat.n == 0) {
+      // a rank of a job, at creation: no central problem, but the whole Q's pattern is what the job-wide certificate is
+      // laid out on (Exchange::certify_live) -- taken here, beside the agents' builds, and never again
+      job_pat = pattern_of(build_Q_pgo(d, n, 0, split.global));
     }
   });
   if (rc) return rc;

@@ -54,18 +54,9 @@ int build_state(SessionCertState &cs, DeviceProblem &central, const HostCsr *pat
   // what the host assembly hands to the PSD test and dcora_cert_prepare analyses: Q's entries, the entries of Lambda,
   // every diagonal -- Q's own pattern unless Q lacks one of them (a rotation block with a structural zero, an isolated
   // pose, a unit sphere without a range)
-  std::vector<int> I, J, LI, LJ;
+  std::vector<int> LI, LJ;
   lambda_entries(m, LI, LJ);
-  I.reserve((size_t)nnzq + LI.size());
-  J.reserve((size_t)nnzq + LI.size());
-  for (int i = 0; i < k; ++i)
-    for (int p = used->rp[i]; p < used->rp[i + 1]; ++p) {
-      I.push_back(i);
-      J.push_back(used->ci[p]);
-    }
-  I.insert(I.end(), LI.begin(), LI.end());
-  J.insert(J.end(), LJ.begin(), LJ.end());
-  cs.pat = pattern_of(csr_shift_diag(csr_from_coo(k, k, I, J, std::vector<double>(I.size(), 1.0)), 1.0));
+  cs.pat = dual_certificate_pattern(m, *used);
   const HostCsr &P = cs.pat;
   const int nnz = P.nnz();
   auto find = [&](int i, int j) -> int {  // (every entry asked for is there)

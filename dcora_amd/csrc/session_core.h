@@ -186,6 +186,11 @@ class SessionCore {
   void lift_trial_abort();
   virtual DeviceProblem *central_problem() = 0;                        // null on a rank of a multi-rank job
   virtual int cert_block() const = 0;  // unknowns the factorisation orders together (d + 1 for poses)
+  // A rank of a multi-rank job: the pattern (rp, ci) of the job's whole Q as its creation-time weights give it, kept
+  // from the assembly at creation -- what the job-wide certificate (Exchange::certify_live) is laid out on.  Empty in a
+  // single-process session, whose central problem holds that pattern.
+  HostCsr job_pat;
+  virtual ManiDesc global_manifold() const = 0;  // of the whole problem, at the current r
 
   // ---- robust sessions (session_robust.hip), stated once for both kinds; null on a plain session.  The calls below
   // are a robust session's.

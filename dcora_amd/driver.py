@@ -455,13 +455,21 @@ def gnc_ra_ranks(ra, X0, r, robust=None, num_weight_updates=10, inner_iters=30, 
                      close=lambda: (ex.close(), s.close()), store=ra.set_pose_pose_weights)
 
 
+def _check_certificate(certificate):
+    if certificate not in ("host", "live"):
+        raise ValueError('certificate must be "host" or "live"')
+    return certificate == "live"
+
+
 class _RanksJob:
     """one rank's (session, exchange) of a job behind the calls _staircase_session makes on a session: run /
     run_coloured across the ranks, Exchange.certify with the global Q on rank 0 (q_now(): the job's current matrix,
-    called on every rank because reading a robust job's weights is collective) and Exchange.lift"""
+    called on every rank because reading a robust job's weights is collective) and Exchange.lift.  certificate="live":
+    Exchange.certify_live instead -- the certificate of the matrices the ranks hold; q_now is never called and no Q is
+    built on the host"""
 
-    def __init__(self, s, ex, k, rank, q_now):
-        self.s, self.ex, self.k, self.rank, self.q_now = s, ex, k, rank, q_now
+    def __init__(self, s, ex, k, rank, q_now, certificate="host"):
+        self.s, self.ex, self.k, self.rank, self.q_now, self.certificate = s, ex, k, rank, q_now, certificate
 
     @property
     def r(self):
@@ -480,6 +488,9 @@ class _RanksJob:
         return self.ex.run_coloured(max_sweeps=max_sweeps, rgrad_tol=rgrad_tol)
 
     def certify(self, eta):
+        if self.certificate == "live":
+            cert, theta, lmin, v, mv, dist, info = self.ex.certify_live(eta)
+            return cert, theta, v, lmin, {"matvecs": mv, "distributed": dist, "rounds": info["rounds"]}
         Q = self.q_now()
         cert, theta, lmin, v, mv, dist = self.ex.certify(Q if self.rank == 0 else None, eta, self.k)
         return cert, theta, v, lmin, {"matvecs": mv, "distributed": dist}
@@ -501,15 +512,19 @@ class _RanksJob:
 def multi_robot_staircase_ranks(ds, X0, num_robots=5, r_min=5, r_max=100, max_iters=1000, rgrad_tol=0.1,
                                 min_eig_tol=1e-3, gradient_tolerance=1e-6, preconditioned_gradient_tolerance=1e-6,
                                 acceleration=True, params=None, device=0, mode="rbcd++", robust=None, fixed=None, rank=0,
-                                world_size=1, job_name="staircase"):
+                                world_size=1, job_name="staircase", certificate="host"):
     """multi_robot_staircase_session on one rank of a multi-rank job (SPMD: every rank calls it with the same arguments
     but rank; ref examples/MultiRobotExample.cpp:223-370): per level exchange_run (or the coloured sweeps),
     Exchange.certify and Exchange.lift, robust or plain -- the job never leaves the library between its levels.  The
     sessions reserve min(r_max, 16) rows before their exchange is created.  The same outputs on every rank.
     With robust=..., ds.vals[:, -1] (the weights) is updated in place before every certificate, as
-    multi_robot_gnc_ranks leaves them."""
+    multi_robot_gnc_ranks leaves them.
+    certificate: "host" -- Exchange.certify on the global Q, rebuilt on the host from the job's weights before every
+    certificate; "live" -- Exchange.certify_live, the certificate of the matrices the ranks hold on the device: no Q is
+    built on the host and ds is not written."""
     from . import Exchange, robust_ranked_session
     _check_mode(mode)
+    live = _check_certificate(certificate)
     d, n = ds.d, ds.n
     r_top = max(min(r_max, 16), r_min)
     ts = time.perf_counter()
@@ -519,7 +534,7 @@ def multi_robot_staircase_ranks(ds, X0, num_robots=5, r_min=5, r_max=100, max_it
                         world_size=world_size)
         s.reserve_rank(r_top)
         ex = Exchange(s, job_name)
-        Q = build_Q_pgo(ds) if rank == 0 else None
+        Q = build_Q_pgo(ds) if rank == 0 and not live else None
         q_now = lambda: Q
     else:
         s, ex = robust_ranked_session(ds, job_name, num_robots=num_robots, r=r_min, robust=robust, fixed_weight=fixed,
@@ -530,7 +545,7 @@ def multi_robot_staircase_ranks(ds, X0, num_robots=5, r_min=5, r_max=100, max_it
             ds.vals[:, -1] = ex.get_weights()
             return build_Q_pgo(ds) if rank == 0 else None
     return _staircase_session(
-        _RanksJob(s, ex, (d + 1) * n, rank, q_now), X0, (d + 1) * n, r_min, r_top, max_iters, rgrad_tol, min_eig_tol,
+        _RanksJob(s, ex, (d + 1) * n, rank, q_now, certificate), X0, (d + 1) * n, r_min, r_top, max_iters, rgrad_tol, min_eig_tol,
         gradient_tolerance, preconditioned_gradient_tolerance, mode, ts,
         gap=lambda X, psd, lmin: suboptimality_gap(X.shape[0], d, n, X, psd, min_eig_tol, lmin))
 
@@ -538,13 +553,14 @@ def multi_robot_staircase_ranks(ds, X0, num_robots=5, r_min=5, r_max=100, max_it
 def raslam_staircase_ranks(ra, X0, r_min=None, r_max=100, max_iters=1000, rgrad_tol=0.1, min_eig_tol=1e-3,
                            gradient_tolerance=1e-4, preconditioned_gradient_tolerance=1e-4, acceleration=True,
                            params=None, device=0, mode="rbcd++", robust=None, fixed=None, rank=0, world_size=1,
-                           job_name="ra_staircase"):
+                           job_name="ra_staircase", certificate="host"):
     """raslam_staircase_session on one rank of a multi-rank range-aided job (SPMD, as multi_robot_staircase_ranks; ref
     examples/MultiRobotExample_RASLAM.cpp): exchange_run, Exchange.certify and Exchange.lift per level.  With
     robust=..., ra keeps the job's current pose-pose weights (set_pose_pose_weights before every certificate), as
-    gnc_ra_ranks leaves them."""
+    gnc_ra_ranks leaves them.  certificate: as multi_robot_staircase_ranks ("live": ra is not written)."""
     from . import Exchange, RaRbcdSession, ROptParameters, ra_robust_ranked_session
     _check_mode(mode)
+    _check_certificate(certificate)
     r_min = ra.d if r_min is None else r_min
     r_top = max(min(r_max, 16), r_min)
     if params is None:
@@ -564,7 +580,7 @@ def raslam_staircase_ranks(ra, X0, r_min=None, r_max=100, max_iters=1000, rgrad_
         def q_now():
             ra.set_pose_pose_weights(ex.get_weights())
             return ra.Q
-    return _staircase_session(_RanksJob(s, ex, ra.k, rank, q_now), X0, ra.k, r_min, r_top, max_iters, rgrad_tol,
+    return _staircase_session(_RanksJob(s, ex, ra.k, rank, q_now, certificate), X0, ra.k, r_min, r_top, max_iters, rgrad_tol,
                               min_eig_tol, gradient_tolerance, preconditioned_gradient_tolerance, mode, ts)
 
 

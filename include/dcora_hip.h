@@ -559,6 +559,42 @@ int dcora_exchange_all_ready(dcora_exchange_t ex, int ready, int *all_ready);
 int dcora_exchange_certify(dcora_exchange_t ex, int k, const int *rowptr, const int *colidx, const double *vals,
                            double eta, int *certified, double *theta, double *lambda_min, double *v, long long *matvecs,
                            int *distributed);
+/* The same certificate of the matrices the job really holds (ref src/DCORA_utils.cpp:1713-1735, 1898-1982, called where
+ * examples/MultiRobotExample.cpp:321-335 certifies): no Q is passed in and no X crosses to a host.  SPMD, every rank
+ * with the same eta, on the exchange of a pose-graph or a range-aided session, robust or plain, at any world_size, with
+ * either transport, after any number of dcora_exchange_lift / _update_weights / _set_weights calls.  Every rank forms
+ * the values of ITS rows of M = (Q - Lambda) + eta I from its agents' device matrices as they are now -- the current
+ * weights, explicit zeros where a weight is 0 -- and the Lambda blocks of its agents, in the CSR order of the job-wide
+ * pattern (the one dcora_cert_dual_matrix gives for the job's creation-time Q: Q's entries, Lambda's, every diagonal),
+ * one thread per stored entry, no atomics: the same bits on every call.  The values reach rank 0 through the X area of
+ * the segment (max(r at creation, reserve) * k doubles) in as many rounds as they need; rank 0 factorises them on its
+ * device (blocks of d + 1 unknowns on a pose graph, 1 on a range-aided job; the analysis cache is the one
+ * dcora_cert_prepare fills) and the verdict goes to every rank.  Refused: the row-block Lanczos stage of
+ * dcora_exchange_certify, with M downloaded once on rank 0 -- and with dcora_cert_min_eig's rule for a spectrum so wide
+ * (eta / lambda_max < 1e-8: tiers.pyfg) that the spectrum-shifted run is not attempted: rank 0's shift-and-invert run
+ * on the downloaded values supplies the eigenpair, *distributed = 0; an accepted certificate moves nothing but the verdict.
+ * Outputs as dcora_exchange_certify's, the same bits on every rank; certified is required, the others may be NULL.
+ * info10 (may be NULL): [0..7] as dcora_cert_is_psd_device reports, [8] the rounds through the X area, [9] ms from entry
+ * to the verdict on rank 0.  The job is left as it was: its next iterates are those of a job that never called this.
+ * DCORA_ERR_BAD_ARG, decided from the arguments alone before any collective step (the job untouched, the segment's
+ * `failed` word not raised): certified NULL, eta not finite or negative.  A failure on one rank raises `failed` as in
+ * every collective call; every wait is bounded by DCORA_EXCHANGE_TIMEOUT_S. */
+int dcora_exchange_certify_live(dcora_exchange_t ex, double eta, int *certified, double *theta, double *lambda_min,
+                                double *v, long long *matvecs, int *distributed, double *info10);
+/* Debug entry of the tests, all arrays on the host, no device: the addressing of dcora_exchange_certify_live for ONE
+ * agent.  dims and (rowptr, colidx, vals): the job's global Q (k rows); agent_dims and cols: the agent's own dimensions
+ * (its n, l, b and layout) and the global column of each of its ka columns, in its ordering; lambda: its Lambda values
+ * as the device leaves them (n_a d x d blocks column-major, then l_a scalars).  The agent's Q_aa and coupling block are
+ * cut out of Q, the table of its rows is built and checked as the job builds it, and a host loop in the kernel's place
+ * writes the entries whose positions lie in [lo, hi) of the value array to window[pos - lo] and counts them up in
+ * written[pos - lo] (hi - lo doubles / bytes; the caller zeroes them).  round_size > 0: [lo, hi) is walked as the job
+ * walks the value array, in rounds of round_size entries, each round a window of its own.  *nnz_pattern (may be NULL): stored entries of
+ * the job-wide pattern.  corrupt_entry >= 0: test hook, the source index of that table entry is pushed past its array
+ * before the check.  DCORA_ERR_BAD_ARG: a table that fails its check, a window outside the value array, bad dims. */
+int dcora_debug_cert_rows(const dcora_dims *dims, const int *rowptr, const int *colidx, const double *vals,
+                          const dcora_dims *agent_dims, const int *cols, const double *lambda, double eta, long long lo,
+                          long long hi, long long round_size, double *window, unsigned char *written,
+                          long long *nnz_pattern, long long corrupt_entry);
 /* the host half of the protocol alone, without a device: bootstrap through the shared segment, barriers, and
  * `rounds` rounds of post -> wait -> evaluation all-gather with host stores in the device's place; every rank of the
  * job calls it, *checksum comes out identical on all of them.  For multi-process tests on machines without a GPU. */
