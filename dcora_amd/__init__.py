@@ -671,6 +671,16 @@ def _fixed_flags(ds, fixed_weight):
     return fx
 
 
+def _round_anchor(anchor, r, d):
+    """an anchor passed to round(): r x (d+1) numbers, column-major for the library (None stays None)"""
+    if anchor is None:
+        return None
+    a = np.asarray(anchor, dtype=np.float64)
+    if a.shape != (r, d + 1):
+        raise ValueError("round needs an anchor of r x (d+1) numbers")
+    return F(a)
+
+
 class _Session:
     """what RbcdSession and RaRbcdSession share: the calls that differ only in the prefix of their entry point
     (_prefix: dcora_rbcd_ / dcora_ra_rbcd_) and in one word of a message (_per)"""
@@ -704,6 +714,31 @@ class _Session:
         its current iterate (dcora_rbcd_certify / dcora_ra_rbcd_certify) -> (psd, theta, v, lambda_min, info); v in the
         session's global ordering; the session is left as it was"""
         return _session_certify(self._fn("certify"), self.h, self.k, eta)
+
+    def round(self, anchor_pose=0, anchor=None, cost=False):
+        """The last step of a solve on the device, where the iterate lies (dcora_rbcd_round / dcora_ra_rbcd_round): the
+        current iterate rounded to SE(d) in the frame of the lifted pose anchor_pose (read on the device; 0 is what the
+        reference's drivers share) or of `anchor` (r x (d+1), setGlobalAnchor), the anchor's translation at the origin.
+        -> dict: trajectory (d x (d+1) n, SE ordering); on a range-aided session unit_spheres (d x l, rotated only) and
+        landmarks (d x b); with cost=True cost_2f -- 2 f of the rounded solution on the matrix the session holds now, its
+        current weights included (sphere columns normalised in the point evaluated) -- and gradnorm; info: kernel_ms,
+        eval_ms, ms.  The session is left as it was."""
+        d, n, l, b = self._round_dims()
+        a = _round_anchor(anchor, self.r, d)
+        T, i4, c2 = np.zeros(d * (d + 1) * n), np.zeros(4), C.c_double()
+        tail = (None if a is None else a.ctypes.data_as(C.c_void_p), T.ctypes.data_as(C.c_void_p))
+        S, Lm = np.zeros(max(d * l, 1)), np.zeros(max(d * b, 1))
+        if self._prefix == "dcora_ra_rbcd_":
+            tail += (S.ctypes.data_as(C.c_void_p), Lm.ctypes.data_as(C.c_void_p))
+        check(self._fn("round")(self.h, int(anchor_pose), *tail, C.byref(c2) if cost else None,
+                                i4.ctypes.data_as(C.c_void_p)))
+        out = {"trajectory": unF(T, d, (d + 1) * n),
+               "info": {"kernel_ms": float(i4[1]), "eval_ms": float(i4[2]), "ms": float(i4[3])}}
+        if self._prefix == "dcora_ra_rbcd_":
+            out["unit_spheres"], out["landmarks"] = unF(S[:d * l], d, l), unF(Lm[:d * b], d, b)
+        if cost:
+            out["cost_2f"], out["gradnorm"] = c2.value, float(i4[0])
+        return out
 
     def _lift(self, theta, v, gradient_tolerance, preconditioned_gradient_tolerance, is_second_order, central_reg):
         return _session_lift(self, self._fn("lift"), self._fn("rank"), theta, v, gradient_tolerance,
@@ -808,6 +843,9 @@ class RbcdSession(_Session):
         finally:
             capi.lib().dcora_dataset_destroy(dsh)
         self.m = ds.m
+
+    def _round_dims(self):
+        return self.ds.d, self.ds.n, 0, 0
 
     def lift(self, theta, v, gradient_tolerance=1e-6, preconditioned_gradient_tolerance=1e-6, is_second_order=False,
              central_reg=None):
@@ -983,6 +1021,23 @@ class Exchange:
     def barrier(self):
         check(capi.lib().dcora_exchange_barrier(self.h))
 
+    def round(self, anchor_pose=0, anchor=None):
+        """The sessions' round() across the ranks of the job (dcora_exchange_round; collective, the same arguments on
+        every rank): every rank rounds the states of the agents it hosts against the shared anchor -- the lifted pose
+        anchor_pose, sent by the rank that hosts it, or `anchor` (r x (d+1)) -- and every rank returns everything
+        -> dict: trajectory and, on a range-aided job, unit_spheres and landmarks: the bits a single-process session at
+        the same iterate returns.  No rounded cost: no rank holds the whole problem."""
+        d, n, l, b = self.s._round_dims()
+        a = _round_anchor(anchor, self.s.r, d)
+        T, S, Lm = np.zeros(d * (d + 1) * n), np.zeros(max(d * l, 1)), np.zeros(max(d * b, 1))
+        check(capi.lib().dcora_exchange_round(self.h, int(anchor_pose), None if a is None else a.ctypes.data_as(C.c_void_p),
+                                              T.ctypes.data_as(C.c_void_p), S.ctypes.data_as(C.c_void_p),
+                                              Lm.ctypes.data_as(C.c_void_p)))
+        out = {"trajectory": unF(T, d, (d + 1) * n)}
+        if isinstance(self.s, RaRbcdSession):
+            out["unit_spheres"], out["landmarks"] = unF(S[:d * l], d, l), unF(Lm[:d * b], d, b)
+        return out
+
     def lift(self, theta, v, gradient_tolerance=1e-6, preconditioned_gradient_tolerance=1e-6, is_second_order=False):
         """The staircase's step of the whole job (dcora_exchange_lift; SPMD: the same theta, v -- k numbers, as certify
         returns them -- and tolerances on every rank): the session lift's search over trial points the ranks form
@@ -1119,6 +1174,9 @@ class RaRbcdSession(_Session):
         rb = np.zeros(self.R, np.int32)
         check(capi.lib().dcora_ra_rbcd_info(self.h, C.byref(n), rb.ctypes.data_as(C.c_void_p)))
         self.robots = rb.tolist()
+
+    def _round_dims(self):
+        return self.ra.d, self.ra.n, self.ra.l, self.ra.b
 
     def lift(self, theta, v, gradient_tolerance=1e-4, preconditioned_gradient_tolerance=1e-4, is_second_order=False,
              central_reg=None):

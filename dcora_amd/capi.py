@@ -172,6 +172,9 @@ SIGNATURES = {
     "dcora_lift_params_default": (C.c_int, [C.POINTER(LiftParams)]),
     "dcora_rbcd_lift": (C.c_int, [_vp, C.c_double, _dp, C.POINTER(LiftParams), _PI, _vp]),
     "dcora_rbcd_rank": (C.c_int, [_vp, _PI]),
+    "dcora_rbcd_round": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp]),
+    "dcora_ra_rbcd_round": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dcora_exchange_round": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp]),
     "dcora_ra_rbcd_lift": (C.c_int, [_vp, C.c_double, _dp, C.POINTER(LiftParams), _PI, _vp]),
     "dcora_exchange_lift": (C.c_int, [_vp, C.c_double, _vp, C.POINTER(LiftParams), _PI, _vp]),
     "dcora_rbcd_reserve_rank": (C.c_int, [_vp, C.c_int]),

@@ -1417,6 +1417,14 @@ int dcora_rbcd_lift(dcora_rbcd_t s, double theta, const double *v, const dcora_l
                     double *info8) {
   return abi_call({s, v, p, escaped}, [&] { return s->s.lift(theta, v, *p, escaped, info8); });
 }
+// the drivers' last step on the live session: getSharedPose(0) -> setGlobalAnchor -> getTrajectoryInGlobalFrame (ref
+// examples/MultiRobotExample.cpp:341-347, src/Agent.cpp:1014-1033): SessionCore::round
+int dcora_rbcd_round(dcora_rbcd_t s, int anchor_pose, const double *anchor, double *trajectory, double *cost2,
+                     double *info4) {
+  return abi_call({s, trajectory}, [&] {
+    return s->s.round(anchor_pose, anchor, trajectory, nullptr, nullptr, cost2, info4);
+  });
+}
 // (ref examples/MultiRobotExample.cpp:352-366, examples/MultiRobotExample_RASLAM.cpp, src/QuadraticProblem.cpp:138-234)
 int dcora_rbcd_rank(dcora_rbcd_t s, int *r) {
   return abi_call({s, r}, [&] {
@@ -1614,6 +1622,13 @@ int dcora_exchange_set_X(dcora_exchange_t ex, const double *X) {
 }
 int dcora_exchange_gather_X(dcora_exchange_t ex, double *X) {
   return abi_call({ex, X}, [&] { return ex->e.gather_X(X); });
+}
+// every agent's own trajectory against the shared anchor, on the rank that hosts it (ref
+// examples/MultiRobotExample.cpp:341-347, examples/MultiRobotExample_RASLAM.cpp:488-495, src/Agent.cpp:1014-1033); a NULL
+// trajectory is refused inside, before any collective step, on every rank alike
+int dcora_exchange_round(dcora_exchange_t ex, int anchor_pose, const double *anchor, double *trajectory,
+                         double *unit_spheres, double *landmarks) {
+  return abi_call({ex}, [&] { return ex->e.round(anchor_pose, anchor, trajectory, unit_spheres, landmarks); });
 }
 // the staircase's step of the whole job (ref examples/MultiRobotExample.cpp:352-366, src/QuadraticProblem.cpp:138-234);
 // a NULL v is refused like a non-finite one, on every rank alike
@@ -1860,6 +1875,14 @@ int dcora_ra_rbcd_certify(dcora_ra_rbcd_t s, double eta, int *certified, double 
   });
 }
 // (ref examples/MultiRobotExample.cpp:352-366, examples/MultiRobotExample_RASLAM.cpp, src/QuadraticProblem.cpp:138-234)
+// (ref examples/MultiRobotExample_RASLAM.cpp:488-495, src/Agent.cpp:1014-1033; the evaluated point's sphere columns as
+// projectSolutionRASLAM's, src/DCORA_utils.cpp:1984-2031)
+int dcora_ra_rbcd_round(dcora_ra_rbcd_t s, int anchor_pose, const double *anchor, double *trajectory,
+                        double *unit_spheres, double *landmarks, double *cost2, double *info4) {
+  return abi_call({s, trajectory}, [&] {
+    return s->s.round(anchor_pose, anchor, trajectory, unit_spheres, landmarks, cost2, info4);
+  });
+}
 int dcora_ra_rbcd_lift(dcora_ra_rbcd_t s, double theta, const double *v, const dcora_lift_params *p, int *escaped,
                        double *info8) {
   return abi_call({s, v, p, escaped}, [&] { return s->s.lift(theta, v, *p, escaped, info8); });

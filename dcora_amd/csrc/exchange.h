@@ -130,6 +130,16 @@ class Exchange {
   // (DCORA_ERR_UNSUPPORTED).  info8 (may be null): trials, accepted alpha, f before, f after, 0, 0, ms of the
   // re-dimensioning, ms total.
   int lift(double theta, const double *v, const dcora_lift_params &p, int *escaped, double *info8);
+  // The last step of a solve across the ranks (ref examples/MultiRobotExample.cpp:341-347,
+  // examples/MultiRobotExample_RASLAM.cpp:488-495, src/Agent.cpp:1014-1033): SessionCore::round's rounding, every state
+  // by the rank that hosts it (a rank's mirror is current only in its hosted and the neighbours' public columns).  SPMD.
+  // An anchor named by anchor_pose travels from its hosting rank through allreduce_sum -- zeros from the others, pieces
+  // of at most 31 doubles, added in rank order: x + 0 keeps x's bits, a -0 arrives as +0 and changes no sum --, a passed
+  // one (r x (d + 1), host) is every rank's as it is.  The pieces are assembled through the X area as gather_X
+  // assembles X (d / r of its room); every rank returns everything.  No rounded cost: no rank holds a central problem.
+  // Refused before any collective step, alike on every rank (DCORA_ERR_BAD_ARG): trajectory null, anchor_pose outside
+  // 0 .. n - 1, a non-finite anchor.
+  int round(int anchor_pose, const double *anchor, double *trajectory, double *unit_spheres, double *landmarks);
   int rank_capacity() const { return r_cap_; }  // the largest rank the job's segment and halo slots hold
   int barrier(double timeout_s = 120.0);
   int gather_X(double *Xh);

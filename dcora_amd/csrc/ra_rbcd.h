@@ -104,6 +104,7 @@ class RaRbcdSession : public SessionCore {
   // the collective lift's: an agent's block is its own X, its columns the `own` list (scattered through the RA ordering)
   void lift_agent_view(AgentCore &a, const double **X_a, const int **cols, long *col0) override;
   int lift_scatter_block(AgentCore &a, int rows, const double *block, double *mirror) override;
+  void round_agent_map(AgentCore &a, RoundAgentMap *map) override;  // (from its `own` list)
   int gather_agents();         // every hosted agent's X from the mirror, V = Y = XPrev = X (enqueued)
   int scatter(RaAgentDev &a);  // my X into the global mirror
   int solve(RaAgentDev &a, const double *start, double **result);

@@ -332,6 +332,20 @@ void RaRbcdSession::lift_agent_view(AgentCore &core, const double **X_a, const i
   *col0 = 0;
 }
 
+// the agent's ordering is ra_agent_columns': [rotations | unit spheres | translations | landmarks], or the SE ordering
+// where it owns neither a unit sphere nor a landmark
+void RaRbcdSession::round_agent_map(AgentCore &core, RoundAgentMap *map) {
+  const RaAgentDev &a = static_cast<const RaAgentDev &>(core);
+  const std::vector<int> &own = a.own_host;
+  map->n = a.n, map->l = a.l, map->b = a.b, map->se = (a.l == 0 && a.b == 0) ? 1 : 0;
+  map->pose.resize((size_t)a.n);
+  map->sphere.resize((size_t)a.l);
+  map->landmark.resize((size_t)a.b);
+  for (int j = 0; j < a.n; ++j) map->pose[(size_t)j] = own[(size_t)(map->se ? (d + 1) * j : d * j)] / d;
+  for (int j = 0; j < a.l; ++j) map->sphere[(size_t)j] = own[(size_t)(d * a.n + j)] - d * n;
+  for (int j = 0; j < a.b; ++j) map->landmark[(size_t)j] = own[(size_t)(d * a.n + a.l + a.n + j)] - (d * n + l + n);
+}
+
 int RaRbcdSession::lift_scatter_block(AgentCore &core, int rows, const double *block, double *mirror) {
   const RaAgentDev &a = static_cast<const RaAgentDev &>(core);
   launch_scatter_cols(st, rows, a.k, a.own.p, block, mirror);

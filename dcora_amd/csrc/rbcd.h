@@ -105,6 +105,7 @@ class RbcdSession : public SessionCore {
   // the collective lift's: an agent's block is its contiguous range of the mirror
   void lift_agent_view(AgentCore &a, const double **X_a, const int **cols, long *col0) override;
   int lift_scatter_block(AgentCore &a, int rows, const double *block, double *mirror) override;
+  void round_agent_map(AgentCore &a, RoundAgentMap *map) override;  // (its poses are a contiguous range)
   int update_nonselected_agent(AgentDev &a, bool restart);
   int update_selected_agent(AgentDev &a, bool restart);
   int restart_step(AgentDev &a);

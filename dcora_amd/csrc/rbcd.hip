@@ -399,6 +399,15 @@ void RbcdSession::lift_agent_view(AgentCore &core, const double **X_a, const int
   *col0 = a.col0;
 }
 
+void RbcdSession::round_agent_map(AgentCore &core, RoundAgentMap *map) {
+  const AgentDev &a = static_cast<const AgentDev &>(core);
+  map->n = a.n, map->l = map->b = 0, map->se = 1;
+  map->pose.resize((size_t)a.n);
+  for (int j = 0; j < a.n; ++j) map->pose[(size_t)j] = a.col0 / (d + 1) + j;
+  map->sphere.clear();
+  map->landmark.clear();
+}
+
 int RbcdSession::lift_scatter_block(AgentCore &core, int rows, const double *block, double *mirror) {
   const AgentDev &a = static_cast<const AgentDev &>(core);
   DCORA_HIP(hipMemcpyAsync(mirror + (size_t)a.col0 * rows, block, sizeof(double) * (size_t)rows * (d + 1) * a.n,

@@ -14,6 +14,7 @@
 #include "host_robust.h"
 #include "robust.h"
 #include "session_cert.h"
+#include "session_round.h"
 #include "team_rules.h"
 
 namespace dcora {
@@ -153,6 +154,30 @@ class SessionCore {
   int lift(double theta, const double *v, const dcora_lift_params &p, int *escaped, double *info8);
   bool exchange_attached = false;  // an Exchange was created on this session
 
+  // The last step of a solve where the iterate lies (session_round.h): the mirror rounded into the frame of an anchor
+  // -- the lifted pose anchor_pose of the current iterate, read on the device (anchor null; 0 is the pose the
+  // reference's drivers share), or r x (d + 1) doubles from the host (setGlobalAnchor) -- whose translation is the
+  // origin.  trajectory: d x (d+1) n, SE ordering; unit_spheres (d x l, rotated only) and landmarks (d x b) may be null.
+  // cost2 (may be null): 2 f of the rounded solution through central_problem()->eval_dev on the lifted rounded point
+  // (sphere columns normalised), i.e. on the session's own matrix with its current weights.  info4 (may be null):
+  // |rgrad| at that point, ms of the kernels, ms of the evaluation, ms total.  Runs on the session's stream; writes
+  // nothing the session reads: a run after the call equals the run without it, bit for bit.  Refused, the session
+  // untouched: a rank of a job (DCORA_ERR_UNSUPPORTED: those round through Exchange::round); trajectory null,
+  // anchor_pose outside 0 .. n - 1, a non-finite anchor (DCORA_ERR_BAD_ARG).
+  int round(int anchor_pose, const double *anchor, double *trajectory, double *unit_spheres, double *landmarks,
+            double *cost2, double *info4);
+  int round_check_args(int anchor_pose, const double *anchor, const double *trajectory) const;
+  // ---- the session's half of the collective rounding (Exchange::round, where the flow stands).  A rank's mirror is
+  // current only in its hosted agents' columns and the neighbours' public ones, so every state is rounded by the rank
+  // that hosts it, from the agent's own block (lift_agent_view), with the kernel of round.
+  //   fetch_anchor: the r x (d + 1) words of global pose anchor_pose into out where this rank hosts it (else out is left
+  //                 as it is: the caller's zeros); synchronises
+  //   hosted:       the hosted agents' poses, unit spheres and landmarks rounded against the anchor (host, r x (d + 1))
+  //                 and stored at their global places of the three host areas (traj: d x (d+1) n in the SE ordering,
+  //                 spheres: d x l, landmarks: d x b; the latter two may be null); synchronises
+  int round_fetch_anchor(int anchor_pose, double *out);
+  int round_hosted(const double *anchor, double *traj_area, double *spheres_area, double *landmarks_area);
+
   // ---- room for the ranks to come: an exchange created on this session sizes its halo slots, its staged slots and its
   // gather_X area by max(r, reserve_r), so that the job can lift up to that rank (Exchange::lift).  0: a job that will
   // never lift, laid out exactly as before.  Legal (d <= r <= r_reserve <= 16, else DCORA_ERR_BAD_ARG) until an
@@ -239,6 +264,8 @@ class SessionCore {
   hipEvent_t fork_ev_ = nullptr;
   bool own_stream_ = true;
   SessionCertState cert_;  // built by the first certify
+  SessionRoundState round_;  // built by the first round
+  int round_buffers(const ManiDesc &m, bool with_lifted);
 
   // updateGamma / updateAlpha (ref src/Agent.cpp:1189-1200) and the round counter; the sequences are data-independent
   // and identical for every agent, so they live on the host
@@ -266,6 +293,13 @@ class SessionCore {
   virtual void lift_agent_view(AgentCore &a, const double **X_a, const int **cols, long *col0) = 0;
   // a hosted agent's block of `rows` rows into its columns of a mirror of `rows` rows (enqueued on st)
   virtual int lift_scatter_block(AgentCore &a, int rows, const double *block, double *mirror) = 0;
+  // ... and to the collective rounding: the dimensions and ordering of a hosted agent's block and the global indices
+  // of its poses, unit spheres and landmarks, in the block's order
+  struct RoundAgentMap {
+    int n = 0, l = 0, b = 0, se = 1;
+    std::vector<int> pose, sphere, landmark;
+  };
+  virtual void round_agent_map(AgentCore &a, RoundAgentMap *map) = 0;
   struct LiftTrial {
     int r_old = 0;
     bool central_reranked = false;

@@ -100,12 +100,16 @@ def multi_robot_example(ds, X0, num_robots=5, r_min=5, r_max=100, max_iters=1000
 
 
 def _staircase_session(s, X0, k, r_min, r_max, max_iters, rgrad_tol, min_eig_tol, gradient_tolerance,
-                       preconditioned_gradient_tolerance, mode, ts, gap=None, before_certify=None):
+                       preconditioned_gradient_tolerance, mode, ts, gap=None, before_certify=None,
+                       round_on_device=False):
     """The staircase of the two drivers above in ONE session of either kind: each level is run / run_coloured, certify
     (the session's own, on the device) and lift (the escape into the next rank in place) -- the reference makes a new
     set of agents per level (examples/MultiRobotExample.cpp:352-366), this keeps them.  The level records are the
     existing drivers'; the iterate comes to the host once, after the last level (gap(X, psd, lmin) -> the bound of
-    that level's record; the earlier levels carry None)."""
+    that level's record; the earlier levels carry None).
+    round_on_device: the solve's last step on the device too -- s.round(cost=True) before the session closes: the result
+    also carries trajectory (unit_spheres and landmarks on a range-aided session), rounded_cost_2f and rounded_gradnorm
+    (None on a multi-rank job, where no rank holds the whole problem), in the frame of pose 0 of the final iterate."""
     X = np.asarray(X0, dtype=np.float64)
     if X.shape != (r_min, k):
         raise ValueError("X0 must be r_min x k")
@@ -145,6 +149,7 @@ def _staircase_session(s, X0, k, r_min, r_max, max_iters, rgrad_tol, min_eig_tol
                 break
             ts = time.perf_counter()
         X = s.get_X()
+        rounded = s.round(cost=True) if round_on_device else None
     finally:
         s.close()
     if levels and gap is not None:
@@ -153,19 +158,27 @@ def _staircase_session(s, X0, k, r_min, r_max, max_iters, rgrad_tol, min_eig_tol
     for lev in levels:
         lev.pop("lambda_min", None)
     cat = lambda parts, dt: np.concatenate(parts) if parts else np.zeros(0, dt)
-    return {"X": X, "rank": X.shape[0], "certified": certified, "theta": float(theta), "total_iters": int(total),
-            "suboptimality_gap_f": levels[-1]["suboptimality_gap_f"] if levels else None, "levels": levels,
-            "cost": cat(cost, float), "gradnorm": cat(gradnorm, float), "selected": cat(selected, np.int32),
-            "rank_trace": cat(rank, np.int32)}
+    res = {"X": X, "rank": X.shape[0], "certified": certified, "theta": float(theta), "total_iters": int(total),
+           "suboptimality_gap_f": levels[-1]["suboptimality_gap_f"] if levels else None, "levels": levels,
+           "cost": cat(cost, float), "gradnorm": cat(gradnorm, float), "selected": cat(selected, np.int32),
+           "rank_trace": cat(rank, np.int32)}
+    if rounded is not None:
+        for key in ("trajectory", "unit_spheres", "landmarks"):
+            if key in rounded:
+                res[key] = rounded[key]
+        res["rounded_cost_2f"], res["rounded_gradnorm"] = rounded.get("cost_2f"), rounded.get("gradnorm")
+    return res
 
 
 def multi_robot_staircase_session(ds, X0, num_robots=5, r_min=5, r_max=100, max_iters=1000, rgrad_tol=0.1,
                                   min_eig_tol=1e-3, gradient_tolerance=1e-6, preconditioned_gradient_tolerance=1e-6,
-                                  acceleration=True, params=None, device=0, mode="rbcd++", robust=None, fixed=None):
+                                  acceleration=True, params=None, device=0, mode="rbcd++", robust=None, fixed=None,
+                                  round_on_device=False):
     """multi_robot_example's staircase (same arguments, same outputs) in ONE RbcdSession: the levels are run /
     run_coloured, RbcdSession.certify and RbcdSession.lift, so the agents, their matrices and preconditioners -- and,
     with robust=..., the weights and the GNC state -- live through every level, and the iterate stays on the device
-    until the last one.  r_max is capped by the session's largest rank, 16."""
+    until the last one.  r_max is capped by the session's largest rank, 16.  round_on_device: RbcdSession.round ends the
+    solve (trajectory, rounded_cost_2f, rounded_gradnorm in the result)."""
     _check_mode(mode)
     d, n = ds.d, ds.n
     ts = time.perf_counter()
@@ -177,14 +190,16 @@ def multi_robot_staircase_session(ds, X0, num_robots=5, r_min=5, r_max=100, max_
     return _staircase_session(
         s, X0, (d + 1) * n, r_min, min(r_max, 16), max_iters, rgrad_tol, min_eig_tol, gradient_tolerance,
         preconditioned_gradient_tolerance, mode, ts, before_certify=prep.join,
-        gap=lambda X, psd, lmin: suboptimality_gap(X.shape[0], d, n, X, psd, min_eig_tol, lmin))
+        gap=lambda X, psd, lmin: suboptimality_gap(X.shape[0], d, n, X, psd, min_eig_tol, lmin),
+        round_on_device=round_on_device)
 
 
 def raslam_staircase_session(ra, X0, r_min=None, r_max=100, max_iters=1000, rgrad_tol=0.1, min_eig_tol=1e-3,
                              gradient_tolerance=1e-4, preconditioned_gradient_tolerance=1e-4, acceleration=True,
-                             params=None, device=0, mode="rbcd++", robust=None, fixed=None):
+                             params=None, device=0, mode="rbcd++", robust=None, fixed=None, round_on_device=False):
     """multi_robot_raslam_example's staircase (same arguments, same outputs, plus the traces) in ONE RaRbcdSession:
-    RaRbcdSession.certify and RaRbcdSession.lift between the levels' runs."""
+    RaRbcdSession.certify and RaRbcdSession.lift between the levels' runs.  round_on_device: RaRbcdSession.round ends
+    the solve (trajectory, unit_spheres, landmarks, rounded_cost_2f, rounded_gradnorm in the result)."""
     from . import RaRbcdSession, ROptParameters
     _check_mode(mode)
     r_min = ra.d if r_min is None else r_min
@@ -194,7 +209,8 @@ def raslam_staircase_session(ra, X0, r_min=None, r_max=100, max_iters=1000, rgra
     s = RaRbcdSession(ra, r_min, acceleration=acceleration and mode == "rbcd++", params=params, device=device,
                       robust=robust, fixed_weight=fixed)
     return _staircase_session(s, X0, ra.k, r_min, min(r_max, 16), max_iters, rgrad_tol, min_eig_tol,
-                              gradient_tolerance, preconditioned_gradient_tolerance, mode, ts)
+                              gradient_tolerance, preconditioned_gradient_tolerance, mode, ts,
+                              round_on_device=round_on_device)
 
 
 def _check_mode(mode):
@@ -498,6 +514,9 @@ class _RanksJob:
     def lift(self, theta, v, gradient_tolerance, preconditioned_gradient_tolerance):
         return self.ex.lift(theta, v, gradient_tolerance, preconditioned_gradient_tolerance)
 
+    def round(self, cost=False):
+        return self.ex.round()  # (no rounded cost across ranks: no rank holds the whole problem)
+
     def close(self):
         # (reached from a `finally`: after an error of the exchange the barrier raises as well -- the exchange and the
         # session are closed all the same, and the first error stays the one the caller sees)
@@ -512,7 +531,7 @@ class _RanksJob:
 def multi_robot_staircase_ranks(ds, X0, num_robots=5, r_min=5, r_max=100, max_iters=1000, rgrad_tol=0.1,
                                 min_eig_tol=1e-3, gradient_tolerance=1e-6, preconditioned_gradient_tolerance=1e-6,
                                 acceleration=True, params=None, device=0, mode="rbcd++", robust=None, fixed=None, rank=0,
-                                world_size=1, job_name="staircase", certificate="host"):
+                                world_size=1, job_name="staircase", certificate="host", round_on_device=False):
     """multi_robot_staircase_session on one rank of a multi-rank job (SPMD: every rank calls it with the same arguments
     but rank; ref examples/MultiRobotExample.cpp:223-370): per level exchange_run (or the coloured sweeps),
     Exchange.certify and Exchange.lift, robust or plain -- the job never leaves the library between its levels.  The
@@ -521,7 +540,10 @@ def multi_robot_staircase_ranks(ds, X0, num_robots=5, r_min=5, r_max=100, max_it
     multi_robot_gnc_ranks leaves them.
     certificate: "host" -- Exchange.certify on the global Q, rebuilt on the host from the job's weights before every
     certificate; "live" -- Exchange.certify_live, the certificate of the matrices the ranks hold on the device: no Q is
-    built on the host and ds is not written."""
+    built on the host and ds is not written.
+    round_on_device: Exchange.round ends the solve -- every rank rounds its own agents' states against pose 0 and every
+    rank's result carries the whole trajectory (rounded_cost_2f and rounded_gradnorm are None: no rank holds the whole
+    problem)."""
     from . import Exchange, robust_ranked_session
     _check_mode(mode)
     live = _check_certificate(certificate)
@@ -547,17 +569,19 @@ def multi_robot_staircase_ranks(ds, X0, num_robots=5, r_min=5, r_max=100, max_it
     return _staircase_session(
         _RanksJob(s, ex, (d + 1) * n, rank, q_now, certificate), X0, (d + 1) * n, r_min, r_top, max_iters, rgrad_tol, min_eig_tol,
         gradient_tolerance, preconditioned_gradient_tolerance, mode, ts,
-        gap=lambda X, psd, lmin: suboptimality_gap(X.shape[0], d, n, X, psd, min_eig_tol, lmin))
+        gap=lambda X, psd, lmin: suboptimality_gap(X.shape[0], d, n, X, psd, min_eig_tol, lmin),
+        round_on_device=round_on_device)
 
 
 def raslam_staircase_ranks(ra, X0, r_min=None, r_max=100, max_iters=1000, rgrad_tol=0.1, min_eig_tol=1e-3,
                            gradient_tolerance=1e-4, preconditioned_gradient_tolerance=1e-4, acceleration=True,
                            params=None, device=0, mode="rbcd++", robust=None, fixed=None, rank=0, world_size=1,
-                           job_name="ra_staircase", certificate="host"):
+                           job_name="ra_staircase", certificate="host", round_on_device=False):
     """raslam_staircase_session on one rank of a multi-rank range-aided job (SPMD, as multi_robot_staircase_ranks; ref
     examples/MultiRobotExample_RASLAM.cpp): exchange_run, Exchange.certify and Exchange.lift per level.  With
     robust=..., ra keeps the job's current pose-pose weights (set_pose_pose_weights before every certificate), as
-    gnc_ra_ranks leaves them.  certificate: as multi_robot_staircase_ranks ("live": ra is not written)."""
+    gnc_ra_ranks leaves them.  certificate: as multi_robot_staircase_ranks ("live": ra is not written).
+    round_on_device: as multi_robot_staircase_ranks, with unit_spheres and landmarks."""
     from . import Exchange, RaRbcdSession, ROptParameters, ra_robust_ranked_session
     _check_mode(mode)
     _check_certificate(certificate)
@@ -581,7 +605,8 @@ def raslam_staircase_ranks(ra, X0, r_min=None, r_max=100, max_iters=1000, rgrad_
             ra.set_pose_pose_weights(ex.get_weights())
             return ra.Q
     return _staircase_session(_RanksJob(s, ex, ra.k, rank, q_now, certificate), X0, ra.k, r_min, r_top, max_iters, rgrad_tol,
-                              min_eig_tol, gradient_tolerance, preconditioned_gradient_tolerance, mode, ts)
+                              min_eig_tol, gradient_tolerance, preconditioned_gradient_tolerance, mode, ts,
+                              round_on_device=round_on_device)
 
 
 def multi_robot_team_ranks(ds, X0, num_robots=5, r=5, robust=None, team=None, acceleration=True, params=None,

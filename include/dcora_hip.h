@@ -442,6 +442,25 @@ int dcora_rbcd_rank(dcora_rbcd_t s, int *r);
  * DCORA_ERR_BAD_ARG unless d <= r <= r_reserve <= 16; DCORA_ERR_UNSUPPORTED once an exchange exists on the session
  * (its segment is unlinked after creation and its IPC mappings are fixed: an exchange does not grow). */
 int dcora_rbcd_reserve_rank(dcora_rbcd_t s, int r_reserve);
+/* The last step of a solve, on the device where the iterate lies: the session's current iterate rounded to SE(d) in
+ * the frame of an anchor, as the reference's drivers end -- agents[0]->getSharedPose(0, &M), setGlobalAnchor(M) on every
+ * agent, then each agent's getTrajectoryInGlobalFrame (ref examples/MultiRobotExample.cpp:341-347,
+ * examples/MultiRobotExample_RASLAM.cpp:488-495, src/Agent.cpp:1014-1033; the alignment: src/DCORA_utils.cpp:2262-2289):
+ *   T_i = [ Proj_SO(d)(R0^T Y_i) | R0^T p_i - R0^T p_anchor ].
+ * anchor NULL: the lifted pose anchor_pose (a global pose index; 0 is what the reference's drivers share) of the current
+ * iterate is the anchor, read on the device -- no host round trip precedes the kernel.  anchor given: r x (d+1) doubles
+ * on the host, column-major (setGlobalAnchor(M)).  Either way the anchor's translation is the origin.
+ * trajectory: d x (d+1) n doubles, the SE ordering (what dcora_round_align_trajectory returns for the same X and anchor,
+ * up to rounding: every element here is one sum in index order through fma).
+ * cost2 (may be NULL): 2 f of the rounded solution on the matrix the session holds NOW (its current robust weights),
+ * evaluated at the lifted rounded point R0 [R_i | t_i], which is feasible at rank r and has the rounded solution's cost:
+ * no rank-d problem is created and no Q is uploaded.  This is the number to set against the certified lower bound.
+ * info4 (may be NULL): the Riemannian gradient norm at that point, ms of the rounding kernels, ms of the evaluation, ms
+ * total.  The session is left as it was: a run after the call equals the run without it, bit for bit.
+ * DCORA_ERR_BAD_ARG: trajectory NULL, anchor_pose outside 0 .. n - 1, a non-finite anchor.
+ * DCORA_ERR_UNSUPPORTED: world_size > 1 (the ranks round together: dcora_exchange_round). */
+int dcora_rbcd_round(dcora_rbcd_t s, int anchor_pose, const double *anchor, double *trajectory, double *cost2,
+                     double *info4);
 /* Debug entry of the tests: the agent form of the lift's image kernel (k_lift_images).  From Xa (r x ka column-major:
  * one agent's block), the global v (kglobal doubles) and the agent's column map -- cols (ka global column indices) or,
  * with cols NULL, the contiguous range starting at col0 -- Xplus = [Xa; 0] and dir = [0; v_a^T], each (r + 1) x ka.
@@ -540,6 +559,21 @@ int dcora_exchange_gather_X(dcora_exchange_t ex, double *X);
  * info8 (may be NULL): trials, accepted alpha, f before, f after, 0, 0, ms of the re-dimensioning, ms total. */
 int dcora_exchange_lift(dcora_exchange_t ex, double theta, const double *v, const dcora_lift_params *params,
                         int *escaped, double *info8);
+/* dcora_rbcd_round / dcora_ra_rbcd_round across the ranks of a job (ref examples/MultiRobotExample.cpp:341-347,
+ * examples/MultiRobotExample_RASLAM.cpp:488-495: every agent rounds its OWN trajectory against the shared anchor;
+ * src/Agent.cpp:1014-1033).  Collective and SPMD, every rank with the same arguments.  An anchor named by anchor_pose
+ * travels from the rank that hosts it to every rank through the segment's sums (the others add zeros, in rank order: the
+ * hosting rank's bits arrive, a -0 as +0, which changes no sum of the kernel); a passed anchor (r x (d+1), host) is used
+ * as it is.  Every rank rounds the poses, unit spheres and landmarks of the agents it hosts from those agents' own
+ * blocks with the single-process kernel, the pieces are assembled through the segment's X area as dcora_exchange_gather_X
+ * assembles X (they need d / r of its room), and every rank returns the whole trajectory (d x (d+1) n) and, on a
+ * range-aided job, unit_spheres (d x l) and landmarks (d x b) where those are not NULL: the bits a single-process
+ * session at the same iterate returns.  There is no rounded cost across ranks: no rank holds the whole problem.
+ * The job is left as it was.  DCORA_ERR_BAD_ARG, decided from the arguments alone before any collective step:
+ * trajectory NULL, anchor_pose outside 0 .. n - 1, a non-finite anchor.  A failure on one rank raises `failed` as in
+ * every collective call; every wait is bounded by DCORA_EXCHANGE_TIMEOUT_S. */
+int dcora_exchange_round(dcora_exchange_t ex, int anchor_pose, const double *anchor, double *trajectory,
+                         double *unit_spheres, double *landmarks);
 /* host barrier over the ranks of the job (does not synchronise the device) */
 int dcora_exchange_barrier(dcora_exchange_t ex);
 /* Agent::shouldTerminate's team condition (ref src/Agent.cpp:1137-1153: terminate only when EVERY robot reports
@@ -648,6 +682,13 @@ int dcora_ra_rbcd_certify(dcora_ra_rbcd_t s, double eta, int *certified, double 
 int dcora_ra_rbcd_lift(dcora_ra_rbcd_t s, double theta, const double *v, const dcora_lift_params *p, int *escaped,
                        double *info8);
 int dcora_ra_rbcd_rank(dcora_ra_rbcd_t s, int *r);
+/* dcora_rbcd_round on a range-aided session (ref examples/MultiRobotExample_RASLAM.cpp:488-495,
+ * src/Agent.cpp:1014-1033): trajectory d x (d+1) n in the SE ordering; unit_spheres (d x l, may be NULL): R0^T s, rotated
+ * only, as getStatesInLocalFrame and dcora_round_align_trajectory return them; landmarks (d x b, may be NULL): rotated
+ * and shifted.  The point behind cost2 is [T | s / |s| | L]: its sphere columns are NORMALISED, as projectSolutionRASLAM
+ * normalises them (ref src/DCORA_utils.cpp:1984-2031) -- the returned unit_spheres are not. */
+int dcora_ra_rbcd_round(dcora_ra_rbcd_t s, int anchor_pose, const double *anchor, double *trajectory,
+                        double *unit_spheres, double *landmarks, double *cost2, double *info4);
 /* dcora_rbcd_reserve_rank on a range-aided session: legal until dcora_exchange_create_ra */
 int dcora_ra_rbcd_reserve_rank(dcora_ra_rbcd_t s, int r_reserve);
 /* as dcora_rbcd_iterate / _evaluate / _run / _last_result; `selected` indexes the agents of dcora_ra_rbcd_info */
