@@ -257,6 +257,8 @@ SIGNATURES = {
     "dcora_debug_tcg_run_fault_at": (C.c_int, [C.c_int, C.c_int]),
     "dcora_debug_wg_sums": (C.c_int, [C.c_int, _dp, _dp]),
     "dcora_debug_run_image": (C.c_int, [C.c_int, C.c_int, _ip, _ip, _PI]),
+    "dcora_debug_group_retract": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_double, _vp, _vp, _dp, _dp, _PI]),
+    "dcora_debug_nesterov": (C.c_int, [C.c_int] * 8 + [C.c_double] * 2 + [_dp] * 7 + [C.c_int, _vp]),
     "dcora_problem_solver_info": (C.c_int, [_vp, _dp]),
     "dcora_ra_rbcd_create": (C.c_int, [_vp, C.POINTER(RbcdOptions), C.POINTER(_vp)]),
     "dcora_ra_rbcd_destroy": (C.c_int, [_vp]),

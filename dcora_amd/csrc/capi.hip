@@ -390,6 +390,86 @@ int dcora_debug_wg_sums(int nv, const double *in, double *out) {
     return DCORA_OK;
   });
 }
+// the 8-lanes-per-pose retraction and both Nesterov kernels on host arrays (tests/test_group_factors_gpu.py)
+int dcora_debug_group_retract(int r, int d, int n, const double *X, const double *V, double alpha, const double *grad,
+                              const double *HV, double *out, double *partials_out, int *npartials_out) {
+  return abi_call({X, V, out, partials_out, npartials_out}, [&]() -> int {
+    if (no_device()) return DCORA_ERR_NO_DEVICE;
+    if ((d != 2 && d != 3) || r < d || n < 1) return bad("dcora_debug_group_retract: d is 2 or 3, r >= d, n >= 1");
+    if ((grad == nullptr) != (HV == nullptr)) return bad("dcora_debug_group_retract: grad and HV come together");
+    const ManiDesc m = make_mani(r, d, n, 0, 0, 1);
+    if (!group_supported(m)) return bad("dcora_debug_group_retract: the group kernels need the SE layout at r <= 8");
+    const size_t nx = (size_t)r * (d + 1) * n, np = (size_t)2 * kMaxPartials;
+    DevBuf<double> Xd, Vd, Gd, Hd, Od, Pd;
+    for (DevBuf<double> *b : {&Xd, &Vd, &Od}) DCORA_HIP(b->alloc(nx));
+    DCORA_HIP(hipMemcpy(Xd.p, X, sizeof(double) * nx, hipMemcpyHostToDevice));
+    DCORA_HIP(hipMemcpy(Vd.p, V, sizeof(double) * nx, hipMemcpyHostToDevice));
+    DCORA_HIP(hipMemset(Od.p, 0xff, sizeof(double) * nx));  // (NaN where the kernel must write)
+    if (grad) {
+      for (DevBuf<double> *b : {&Gd, &Hd}) DCORA_HIP(b->alloc(nx));
+      DCORA_HIP(Pd.alloc(np));
+      DCORA_HIP(hipMemcpy(Gd.p, grad, sizeof(double) * nx, hipMemcpyHostToDevice));
+      DCORA_HIP(hipMemcpy(Hd.p, HV, sizeof(double) * nx, hipMemcpyHostToDevice));
+      DCORA_HIP(hipMemset(Pd.p, 0xff, sizeof(double) * np));
+    }
+    const int grid = launch_g_retract(nullptr, m, buf1(Xd.p), Vd.p, alpha, buf1(Od.p), 0, buf1(Gd.p), Hd.p, Pd.p, Gate{});
+    DCORA_HIP(hipGetLastError());
+    DCORA_HIP(hipDeviceSynchronize());
+    DCORA_HIP(hipMemcpy(out, Od.p, sizeof(double) * nx, hipMemcpyDeviceToHost));
+    if (grad) DCORA_HIP(hipMemcpy(partials_out, Pd.p, sizeof(double) * 2 * grid, hipMemcpyDeviceToHost));
+    *npartials_out = grad ? grid : 0;
+    return DCORA_OK;
+  });
+}
+int dcora_debug_nesterov(int form, int r, int d, int n, int mode, int restart_bits, int skip_lo, int skip_hi,
+                         double alpha, double gamma, double *X, double *V, double *Y, double *XPrev, double *Yloc,
+                         const double *Xloc0, const double *Xloc1, int cur, double *inner_Yloc) {
+  return abi_call({X, V, Y, XPrev, Yloc, Xloc0, Xloc1}, [&]() -> int {
+    if (no_device()) return DCORA_ERR_NO_DEVICE;
+    if ((d != 2 && d != 3) || r < d || r > kMaxRank || n < 1 || mode < 0 || mode > 3)
+      return bad("dcora_debug_nesterov: d is 2 or 3, d <= r <= 16, n >= 1, mode is 0 .. 3");
+    if (form != 0 && form != 1) return bad("dcora_debug_nesterov: form is 0 (k_nesterov) or 1 (k_g_nesterov)");
+    const ManiDesc m = make_mani(r, d, n, 0, 0, 1);
+    if (form == 1 && !group_supported(m)) return bad("dcora_debug_nesterov: form 1 needs the SE layout at r <= 8");
+    if (form == 1 && (cur < -1 || cur > 1)) return bad("dcora_debug_nesterov: cur is 0, 1 or -1 (no control block)");
+    if (form == 0 && inner_Yloc) return bad("dcora_debug_nesterov: form 0 has no inner_Yloc");
+    if (inner_Yloc && (skip_lo < 0 || skip_hi < skip_lo || skip_hi > n))
+      return bad("dcora_debug_nesterov: inner_Yloc holds the poses [skip_lo, skip_hi) of the n");
+    const size_t nx = (size_t)r * (d + 1) * n, ni = inner_Yloc ? (size_t)r * (d + 1) * (skip_hi - skip_lo) : 0;
+    double *state[5] = {X, V, Y, XPrev, Yloc};
+    DevBuf<double> S[5], L[2], I;
+    DevBuf<SolverCtl> ctl;
+    for (int i = 0; i < 5; ++i) {
+      DCORA_HIP(S[i].alloc(nx));
+      DCORA_HIP(hipMemcpy(S[i].p, state[i], sizeof(double) * nx, hipMemcpyHostToDevice));
+    }
+    for (int i = 0; i < 2; ++i) {
+      DCORA_HIP(L[i].alloc(nx));
+      DCORA_HIP(hipMemcpy(L[i].p, i ? Xloc1 : Xloc0, sizeof(double) * nx, hipMemcpyHostToDevice));
+    }
+    if (ni) {
+      DCORA_HIP(I.alloc(ni));
+      DCORA_HIP(hipMemcpy(I.p, inner_Yloc, sizeof(double) * ni, hipMemcpyHostToDevice));
+    }
+    if (form == 1 && cur >= 0) {
+      SolverCtl c{};
+      c.cur = cur;
+      DCORA_HIP(ctl.alloc(1));
+      DCORA_HIP(hipMemcpy(ctl.p, &c, sizeof(c), hipMemcpyHostToDevice));
+    }
+    if (form == 1)
+      launch_g_nesterov(nullptr, m, mode, restart_bits, skip_lo, skip_hi, alpha, gamma, S[0].p, S[1].p, S[2].p, S[3].p,
+                        S[4].p, Buf2{{L[0].p, L[1].p}}, ctl.p, ni ? I.p : nullptr);
+    else  // as rbcd.hip calls it
+      launch_nesterov(nullptr, m, mode, restart_bits & 1, skip_lo, skip_hi, alpha, gamma, S[0].p, S[1].p, S[2].p, S[3].p,
+                      S[4].p, L[0].p);
+    DCORA_HIP(hipGetLastError());
+    DCORA_HIP(hipDeviceSynchronize());
+    for (int i = 0; i < 5; ++i) DCORA_HIP(hipMemcpy(state[i], S[i].p, sizeof(double) * nx, hipMemcpyDeviceToHost));
+    if (ni) DCORA_HIP(hipMemcpy(inner_Yloc, I.p, sizeof(double) * ni, hipMemcpyDeviceToHost));
+    return DCORA_OK;
+  });
+}
 int dcora_debug_run_image(int r, int k, int *off, int *lanes, int *bytes) {
   return abi_call({off, lanes, bytes}, [&]() -> int {
     const int b = tcg_run_image_map(r, k, off, lanes);

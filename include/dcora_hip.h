@@ -126,6 +126,20 @@ int dcora_debug_tcg_run_fault_at(int skip, int runs);
  * four-step DPP butterfly.  out (host, 2 * nv * 17 doubles): for each of the two, in that order, the nv x 16 row sums
  * (out[i * 16 + 4 * wave + row]) followed by the nv totals of the serial add over the 16. */
 int dcora_debug_wg_sums(int nv, const double *in, double *out);
+/* test hook: Retr_X(alpha V) by the 8-lanes-per-pose kernel (k_g_retract) on host arrays in the SE ordering, r x (d+1) n
+ * each, r <= 8 (DCORA_ERR_BAD_ARG otherwise).  grad and HV are given together or both NULL.  Given: partials_out (host,
+ * room for 2 * 1024 doubles) receives the kernel's pairs {<V, grad>, <V, HV>} of *npartials_out workgroups, in slot order.
+ * NULL: the kernel gets no partial buffer, partials_out is not written and *npartials_out = 0. */
+int dcora_debug_group_retract(int r, int d, int n, const double *X, const double *V, double alpha, const double *grad,
+                              const double *HV, double *out, double *partials_out, int *npartials_out);
+/* test hook: one launch of the RBCD++ Nesterov bookkeeping on host arrays (SE ordering, r x (d+1) n each; X, V, Y, XPrev,
+ * Yloc in and out).  form 1: k_g_nesterov (r <= 8) with all bits of restart_bits; cur = 0 / 1 builds a control block on
+ * the device whose `cur` picks Xloc0 / Xloc1, cur = -1 passes none (Xloc0 is read); inner_Yloc (NULL, or in / out,
+ * r x (d+1) (skip_hi - skip_lo)) as in the session's mode-0 launch.  form 0: k_nesterov (r <= 16) with restart_bits & 1
+ * and Xloc0, as the session calls it; inner_Yloc must be NULL. */
+int dcora_debug_nesterov(int form, int r, int d, int n, int mode, int restart_bits, int skip_lo, int skip_hi,
+                         double alpha, double gamma, double *X, double *V, double *Y, double *XPrev, double *Yloc,
+                         const double *Xloc0, const double *Xloc1, int cur, double *inner_Yloc);
 /* test hook (host only, no device needed): the LDS image of the one-launch tCG run at rank r (4, 5, 6) and k <= 2048
  * columns.  off (ceil(k / 128) * 64 * r ints): the byte offset of every pair of doubles of the column-major residual;
  * lanes (64 ints): the logical lane (columns 2 L, 2 L + 1 of a 128-column step) of each lane of a wave in the product;

@@ -19,14 +19,34 @@ PQ_KINDS = [("kappa=%g" % k, k, 1.0) for k in KAPPAS] + [("clustered", None, 1.0
 SO_TAILS = [0.5, 1e-3, 1e-6, 1e-9, "close"]
 SO_DR = [(2, 2), (3, 3), (2, 5), (3, 5)]
 
+# tests/golden/block_factors_near.npz: the near-orthonormal family of the 8-lanes-per-pose kernels (r <= 8).  A group is
+# one (d, r) at one delta = |A^T A - I|_F, on both sides of row_polar's Gram radius 0.25; every entry is a multiple of
+# NEAR_QUANTUM.  The nd_* groups carry the cases with non-dyadic coefficients (alpha = ND_ALPHA, gamma = ND_GAMMA).
+NEAR_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "block_factors_near.npz")
+NEAR_DR = [(d, r) for d, r in PQ_DR if r <= 8]
+NEAR_DELTAS = [1e-6, 1e-3, 0.03, 0.1, 0.2, 0.245, 0.255, 0.4]
+NEAR_QUANTUM = 2.0 ** -40
+GRAM_RADIUS = 0.25  # kPolarGramRadius of dcora_amd/csrc/pose_group.h
+ND_DR = [(2, 4), (3, 5), (3, 8)]
+ND_ALPHA, ND_GAMMA = 0.37, 0.61
+ND_SPREADS = [0.02, 0.1, 0.3, 0.6, 1.0]  # of v (mode 1) / of the step (mode 2) around x: both branches of row_polar
+
 _cache = {}
 
 
+def _load(key, path):
+    if key not in _cache:
+        with np.load(path) as z:
+            _cache[key] = {k: z[k] for k in z.files}
+    return _cache[key]
+
+
 def load():
-    if "fx" not in _cache:
-        with np.load(PATH) as z:
-            _cache["fx"] = {k: z[k] for k in z.files}
-    return _cache["fx"]
+    return _load("fx", PATH)
+
+
+def load_near():
+    return _load("near", NEAR_PATH)
 
 
 def _blocks(flat, off, cnt, rows, cols):
@@ -48,6 +68,55 @@ class PQGroup:
 
     def tol(self, what):
         return max(self.oracle_err[what], EPS * self.cond)
+
+
+class NearGroup(PQGroup):
+    """a group of block_factors_near.npz: PQGroup's fields, with delta instead of kind"""
+    def __init__(self, fx, i):
+        self.d, self.r, self.delta = int(fx["nr_d"][i]), int(fx["nr_r"][i]), float(fx["nr_delta"][i])
+        self.name = "d=%d r=%d delta=%g" % (self.d, self.r, self.delta)
+        self.cond = float(fx["nr_cond"][i])
+        off, cnt = int(fx["nr_off"][i]), int(fx["nr_cnt"][i])
+        self.inp, self.polar, self.qf = (_blocks(fx["nr_" + k], off, cnt, self.r, self.d) for k in ("in", "polar", "qf"))
+        self.oracle_err = {"polar": float(fx["nr_polar_oracle_err"][i]), "qf": float(fx["nr_qf_oracle_err"][i])}
+
+
+class NDGroup:
+    """mode 1: the polar factor of c0 a + alpha b (a = x, b = v, c0 = fl(1 - alpha)); mode 2: of a + gamma (b - c) (a = v,
+    b = Xloc, c = y) -- the combination formed exactly from the float64 inputs.  smin: its smallest singular value and
+    fwd: the norm sum of the forward-error term, per block"""
+    def __init__(self, fx, i):
+        self.d, self.r, self.mode = int(fx["nd_d"][i]), int(fx["nd_r"][i]), int(fx["nd_mode"][i])
+        self.name = "d=%d r=%d mode %d non-dyadic" % (self.d, self.r, self.mode)
+        self.cond, self.oracle_err = float(fx["nd_cond"][i]), float(fx["nd_oracle_err"][i])
+        off, cnt = int(fx["nd_off"][i]), int(fx["nd_cnt"][i])
+        self.a, self.b, self.c, self.ref = (_blocks(fx["nd_" + k], off, cnt, self.r, self.d) for k in ("a", "b", "c", "ref"))
+        o = int(fx["nd_cnt"][:i].sum())  # smin, dist: one entry per block
+        self.smin, self.dist = fx["nd_smin"][o:o + cnt], fx["nd_dist"][o:o + cnt]
+
+    def tol(self):
+        return max(self.oracle_err, EPS * self.cond)
+
+    def forward(self):
+        """per block: the error of forming the combination in float64 (u = 2^-53 per rounding, with or without FMA)
+        times the polar factor's Lipschitz constant 1 / sigma_min.
+        mode 1, fl(fl(c0 x) + fl(alpha v)): at most 2 u (|c0 x|_F + |alpha v|_F);
+        mode 2, fl(v + fl(gamma fl(x - y))): at most u |v|_F + 3 u |gamma (x - y)|_F <= 3 u (|v|_F + |gamma (x - y)|_F)"""
+        nrm = lambda M: np.sqrt((M ** 2).sum(axis=(1, 2)))
+        u = EPS / 2
+        if self.mode == 1:
+            return 2 * u * (nrm((1.0 - ND_ALPHA) * self.a) + nrm(ND_ALPHA * self.b)) / self.smin
+        return 3 * u * (nrm(self.a) + nrm(ND_GAMMA * (self.b - self.c))) / self.smin
+
+
+def near_groups(fx, d=None, r=None):
+    return [NearGroup(fx, i) for i in range(len(fx["nr_d"]))
+            if (d is None or fx["nr_d"][i] == d) and (r is None or fx["nr_r"][i] == r)]
+
+
+def nd_groups(fx, d, r, mode):
+    return [NDGroup(fx, i) for i in range(len(fx["nd_d"]))
+            if fx["nd_d"][i] == d and fx["nd_r"][i] == r and fx["nd_mode"][i] == mode]
 
 
 class SOGroup:

@@ -1,5 +1,6 @@
 """Regenerates tests/golden/block_factors.npz: per-block polar, QF and SO(d) factors at 50 digits (mpmath), rounded to
 float64, with what the CPU oracle achieves on the same inputs.  Run on the CPU:  python tests/golden/make_block_factors.py
+It also writes tests/golden/block_factors_near.npz (the last section below); with --near it writes only that file.
 
 The three references share nothing with oracle/ or dcora_amd/csrc (those are Hestenes-Jacobi / two-pass MGS in IEEE
 double; these are mpmath's Golub-Kahan SVD and a Gram-Schmidt at mp.dps = 50):
@@ -20,6 +21,20 @@ Families (4 blocks per group unless stated):
         reference then being computed from R0^T Y_i formed in mpmath.  Exact rank d - 1 blocks (r = d, groups of 24):
         diag(1,0), diag(0,1), [[0,1],[0,0]] and diag(1,.5,0) with three column permutations of it, each multiplied from
         the left by signed permutation matrices of both determinants.
+
+block_factors_near.npz, for the 8-lanes-per-pose kernels (row_polar, row_qf of dcora_amd/csrc/pose_group.h):
+  nr_*  near-orthonormal blocks at the (d, r) above with r <= 8: A = U diag(sqrt(1 + x_i)) V^T, x of mixed signs with
+        |x|_2 = delta, so |A^T A - I|_F = delta, for delta in {1e-6, 1e-3, 0.03, 0.1, 0.2, 0.245, 0.255, 0.4}: inside
+        row_polar's Gram radius 0.25 (two to five Newton-Schulz steps), 2 % clear of it on both sides, and well past it.
+        Every entry is rounded to a multiple of 2^-40 BEFORE the references are computed: A - E, 2 A - E and
+        E + (2 A - 2 E) / 2 with E = eye(r, d) are then exact in float64, with or without FMA contraction, so a test can
+        hand a kernel inputs whose combination is the stored block bit for bit.  Polar and QF references, cond and the
+        oracle's errors per group as for pq_*.
+  nd_*  inputs that are NOT quantised, for alpha = 0.37 and gamma = 0.61: (a, b) = (x, v) of a mode-1 Nesterov step and
+        (a, b, c) = (v, Xloc, y) of a mode-2 step, 15 blocks per (d, r) in {(2, 4), (3, 5), (3, 8)}, with the polar factor
+        of fl(1 - alpha) a + alpha b resp. a + gamma (b - c), the combination being formed exactly (mpmath) from the
+        float64 inputs; sigma_min and |G - I|_F of the combination per block.  The oracle's error of these groups is
+        measured on the combination rounded to float64 against that block's own factor.
 
 Left out, because the factor is not unique there: rank-deficient blocks for polar and QF; SO(d) blocks with det < 0 and
 sigma_{d-1} = sigma_d; SO(d) blocks of rank <= d - 2.
@@ -205,6 +220,107 @@ def make_so_rankdef(d):
     return np.array(ins), np.array(refs), cond
 
 
+# ---- the near-orthonormal family (block_factors_near.npz) -------------------------------------------------------------------
+def make_near_group(d, r, di):
+    """A = U diag(sqrt(1 + x_i)) V^T with |x|_2 = delta and mixed signs, so |A^T A - I|_F = delta; every entry rounded to
+    a multiple of 2^-40; references and cond of the rounded blocks"""
+    delta = bf.NEAR_DELTAS[di]
+    rng = _rng(4, d, r, di)
+    A_in, P_ref, Q_ref, cond = [], [], [], 0.0
+    for _ in range(NB):
+        U, V = _frame(rng, r, d), _frame(rng, d, d)
+        x = rng.uniform(0.3, 1.0, d) * (-1.0) ** (np.arange(d) + rng.integers(2))
+        x *= delta / np.linalg.norm(x)
+        A = _np(U * mp.diag([mp.sqrt(1 + mp.mpf(float(t))) for t in x]) * V.T)
+        A = np.round(A / bf.NEAR_QUANTUM) * bf.NEAR_QUANTUM
+        s = mp.svd_r(_mp(A), compute_uv=False)
+        cond = max(cond, float(s[0] / s[d - 1]))
+        A_in.append(A)
+        P_ref.append(ref_polar(A))
+        Q_ref.append(ref_qf(A))
+    return np.array(A_in), np.array(P_ref), np.array(Q_ref), cond
+
+
+ND_NB = 15  # blocks per non-dyadic group
+
+
+def make_nd_group(d, r, mode):
+    """unquantised inputs of a mode-1 (y = P(c0 x + alpha v), c0 = fl(1 - alpha)) or a mode-2 (v = P(v + gamma (Xloc - y)))
+    launch with alpha = 0.37, gamma = 0.61, the 50-digit polar factor of the combination formed exactly from them, its
+    sigma_min and |G - I|_F per block, its cond over the group, and the combination rounded to float64 (for the oracle)"""
+    rng = _rng(5, d, r, mode)
+    al, ga = mp.mpf(bf.ND_ALPHA), mp.mpf(bf.ND_GAMMA)
+    c0 = mp.mpf(1.0 - bf.ND_ALPHA)
+    a_, b_, c_, ref, smin, dist, comb, cond = [], [], [], [], [], [], [], 0.0
+    for i in range(ND_NB):
+        spread = bf.ND_SPREADS[i % len(bf.ND_SPREADS)]
+        x = np.linalg.qr(rng.standard_normal((r, d)))[0]
+        w = x + spread * rng.standard_normal((r, d)) / np.sqrt(r)
+        if mode == 1:  # a = x, b = v
+            a, b, c = x, w, np.zeros((r, d))
+            M = c0 * _mp(a) + al * _mp(b)
+        else:  # a = v, b = Xloc, c = y
+            a, b, c = x, w, np.linalg.qr(x + 0.1 * rng.standard_normal((r, d)))[0]
+            M = _mp(a) + ga * (_mp(b) - _mp(c))
+        U, s, Vh = mp.svd_r(M, full_matrices=False, compute_uv=True)
+        cond = max(cond, float(s[0] / s[d - 1]))
+        G = M.T * M - mp.eye(d)
+        for k, v in zip((a_, b_, c_, ref, smin, dist, comb),
+                        (a, b, c, _np(U * Vh), float(s[d - 1]), float(mp.sqrt(mp.fsum(g * g for g in G))), _np(M))):
+            k.append(v)
+    return tuple(np.array(v) for v in (a_, b_, c_, ref, smin, dist, comb)) + (cond,)
+
+
+def main_near():
+    out = {}
+    orth = 0.0
+    fl = lambda v: v.transpose(0, 2, 1).reshape(-1)  # column-major blocks, one after another
+    meta = {k: [] for k in ("d", "r", "delta", "off", "cnt", "cond", "polar_oracle_err", "qf_oracle_err")}
+    data = {k: [] for k in ("in", "polar", "qf")}
+    off = 0
+    for d, r in bf.NEAR_DR:
+        for di, delta in enumerate(bf.NEAR_DELTAS):
+            A, P, Q, cond = make_near_group(d, r, di)
+            Po, Qo = bf.oracle_polar(A), bf.oracle_qf(A)
+            orth = max(orth, bf.orth_err(Po).max(), bf.orth_err(Qo).max())
+            for k, v in zip(meta, (d, r, delta, off, NB, cond, bf.block_err(Po, P).max(), bf.block_err(Qo, Q).max())):
+                meta[k].append(v)
+            for k, v in zip(data, (A, P, Q)):
+                data[k].append(fl(v))
+            off += NB * r * d
+            print("near d=%d r=%d delta=%-6g cond %.3f  oracle polar %.2e  qf %.2e" % (d, r, delta, cond, meta[
+                "polar_oracle_err"][-1], meta["qf_oracle_err"][-1]), flush=True)
+    for k, v in meta.items():
+        out["nr_" + k] = np.array(v, dtype=np.int32 if k in ("d", "r", "off", "cnt") else np.float64)
+    for k, v in data.items():
+        out["nr_" + k] = np.concatenate(v)
+    meta = {k: [] for k in ("d", "r", "mode", "off", "cnt", "cond", "oracle_err")}
+    data = {k: [] for k in ("a", "b", "c", "ref", "smin", "dist")}
+    off, nd_orth = 0, 0.0
+    for d, r in bf.ND_DR:
+        for mode in (1, 2):
+            a, b, c, ref, smin, dist, comb, cond = make_nd_group(d, r, mode)
+            # the oracle cannot take the exact combination: its error is measured on the combination rounded to float64
+            Po = bf.oracle_polar(comb)
+            nd_orth = max(nd_orth, bf.orth_err(Po).max())
+            oerr = bf.block_err(Po, np.array([ref_polar(M) for M in comb])).max()
+            for k, v in zip(meta, (d, r, mode, off, ND_NB, cond, oerr)):
+                meta[k].append(v)
+            for k, v in zip(data, (fl(a), fl(b), fl(c), fl(ref), smin, dist)):
+                data[k].append(v)
+            off += ND_NB * r * d
+            print("nd d=%d r=%d mode %d cond %.3f  oracle %.2e  |G - I| %.3f .. %.3f" % (d, r, mode, cond, oerr,
+                                                                                        dist.min(), dist.max()), flush=True)
+    for k, v in meta.items():
+        out["nd_" + k] = np.array(v, dtype=np.float64 if k in ("cond", "oracle_err") else np.int32)
+    for k, v in data.items():
+        out["nd_" + k] = np.concatenate(v)
+    out["oracle_orth"], out["nd_oracle_orth"] = np.array(orth), np.array(nd_orth)
+    np.savez_compressed(bf.NEAR_PATH, **out)
+    print("wrote %s: %d bytes, oracle_orth %.2e (nr_*) %.2e (nd_*)" % (bf.NEAR_PATH, os.path.getsize(bf.NEAR_PATH), orth,
+                                                                       nd_orth))
+
+
 # ---- assembly --------------------------------------------------------------------------------------------------------------
 def main():
     out = {}
@@ -268,4 +384,8 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] not in ([], ["--near"]):
+        sys.exit("usage: make_block_factors.py [--near]")
+    if not sys.argv[1:]:
+        main()
+    main_near()
