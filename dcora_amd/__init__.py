@@ -740,6 +740,26 @@ class _Session:
             out["cost_2f"], out["gradnorm"] = c2.value, float(i4[0])
         return out
 
+    def project(self):
+        """How CORA ends a certified solve, in place (dcora_rbcd_project / dcora_ra_rbcd_project; ref
+        projectSolutionRASLAM): the session goes from rank r to rank d at Proj(V_d^T X), V_d the top-d eigenvectors of
+        X X^T with the reflection rule folded in, and keeps its matrices, preconditioners, weights and team; afterwards
+        self.r == d.  At r == d nothing of the session changes (projected False, basis None).  -> dict: projected,
+        reflected, positive_dets, sigma (r singular values of X), basis (r x d, the new iterate is Proj(basis^T X)), gram
+        (r x r, X X^T as the device formed it), cost_2f and gradnorm of the adopted point on the matrix the session holds
+        now, ms_kernels, ms_redimension, ms_total, gram_chunk (columns per workgroup of the Gram kernel)."""
+        r, d = self.r, self._round_dims()[0]
+        sg, B, G, i8, c2, rr = np.zeros(r), np.zeros(r * d), np.zeros(r * r), np.zeros(8), C.c_double(), C.c_int()
+        check(self._fn("project")(self.h, *(a.ctypes.data_as(C.c_void_p) for a in (sg, B, G)), C.byref(c2),
+                                  i8.ctypes.data_as(C.c_void_p)))
+        check(self._fn("rank")(self.h, C.byref(rr)))
+        self.r = rr.value
+        projected = bool(i8[0])
+        return dict(projected=projected, reflected=bool(i8[1]), positive_dets=int(i8[2]), sigma=sg,
+                    basis=unF(B, r, d) if projected else None, gram=unF(G, r, r), cost_2f=c2.value,
+                    gradnorm=float(i8[3]), ms_kernels=float(i8[4]), ms_redimension=float(i8[5]), ms_total=float(i8[6]),
+                    gram_chunk=int(i8[7]))
+
     def _lift(self, theta, v, gradient_tolerance, preconditioned_gradient_tolerance, is_second_order, central_reg):
         return _session_lift(self, self._fn("lift"), self._fn("rank"), theta, v, gradient_tolerance,
                              preconditioned_gradient_tolerance, is_second_order, central_reg)

@@ -179,6 +179,9 @@ SIGNATURES = {
     "dcora_exchange_lift": (C.c_int, [_vp, C.c_double, _vp, C.POINTER(LiftParams), _PI, _vp]),
     "dcora_rbcd_reserve_rank": (C.c_int, [_vp, C.c_int]),
     "dcora_ra_rbcd_reserve_rank": (C.c_int, [_vp, C.c_int]),
+    "dcora_rbcd_project": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "dcora_ra_rbcd_project": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "dcora_debug_project_gram": (C.c_int, [C.c_int, C.c_longlong, _dp, _dp, _PI]),
     "dcora_debug_lift_images": (C.c_int, [C.c_int, C.c_int, _dp, C.c_int, _dp, _vp, C.c_int, _dp, _dp]),
     "dcora_ra_rbcd_rank": (C.c_int, [_vp, _PI]),
     "dcora_rbcd_profile_tcg_runs": (C.c_int, [_vp, C.c_int]),

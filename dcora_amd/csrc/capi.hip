@@ -1505,6 +1505,31 @@ int dcora_rbcd_round(dcora_rbcd_t s, int anchor_pose, const double *anchor, doub
     return s->s.round(anchor_pose, anchor, trajectory, nullptr, nullptr, cost2, info4);
   });
 }
+// the certified flow's last step on the live session (ref examples/SingleRobotExample_RASLAM.cpp:220-234,
+// src/DCORA_utils.cpp:1984-2031): SessionCore::project of either kind
+int dcora_rbcd_project(dcora_rbcd_t s, double *sigma, double *basis, double *gram, double *cost2, double *info8) {
+  return abi_call({s}, [&] { return s->s.project(sigma, basis, gram, cost2, info8); });
+}
+// k_gram_mfma / k_gram_finish on a host array (tests/test_session_project_gpu.py)
+int dcora_debug_project_gram(int r, long long k, const double *X, double *gram, int *chunk) {
+  return abi_call({X, gram}, [&]() -> int {
+    if (r < 1 || r > kMaxRank || k < 1) return bad("dcora_debug_project_gram: 1 <= r <= 16, k >= 1");
+    if (chunk) *chunk = kGramCols;
+    DevBuf<double> Xd, P, G;
+    DCORA_HIP(Xd.alloc((size_t)r * (size_t)k));
+    DCORA_HIP(P.alloc(256 * (size_t)gram_workgroups(k)));
+    DCORA_HIP(G.alloc((size_t)r * r));
+    DCORA_HIP(hipMemcpy(Xd.p, X, sizeof(double) * (size_t)r * (size_t)k, hipMemcpyHostToDevice));
+    // (NaN where the kernels must write: an element they skip shows)
+    DCORA_HIP(hipMemset(P.p, 0xff, sizeof(double) * 256 * (size_t)gram_workgroups(k)));
+    DCORA_HIP(hipMemset(G.p, 0xff, sizeof(double) * (size_t)r * r));
+    launch_gram(nullptr, r, k, Xd.p, P.p, G.p);
+    DCORA_HIP(hipGetLastError());
+    DCORA_HIP(hipDeviceSynchronize());
+    DCORA_HIP(hipMemcpy(gram, G.p, sizeof(double) * (size_t)r * r, hipMemcpyDeviceToHost));
+    return (int)DCORA_OK;
+  });
+}
 // (ref examples/MultiRobotExample.cpp:352-366, examples/MultiRobotExample_RASLAM.cpp, src/QuadraticProblem.cpp:138-234)
 int dcora_rbcd_rank(dcora_rbcd_t s, int *r) {
   return abi_call({s, r}, [&] {
@@ -1962,6 +1987,10 @@ int dcora_ra_rbcd_round(dcora_ra_rbcd_t s, int anchor_pose, const double *anchor
   return abi_call({s, trajectory}, [&] {
     return s->s.round(anchor_pose, anchor, trajectory, unit_spheres, landmarks, cost2, info4);
   });
+}
+int dcora_ra_rbcd_project(dcora_ra_rbcd_t s, double *sigma, double *basis, double *gram, double *cost2,
+                          double *info8) {
+  return abi_call({s}, [&] { return s->s.project(sigma, basis, gram, cost2, info8); });
 }
 int dcora_ra_rbcd_lift(dcora_ra_rbcd_t s, double theta, const double *v, const dcora_lift_params *p, int *escaped,
                        double *info8) {

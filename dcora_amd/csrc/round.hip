@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "device_problem.h"
+#include "small_eig.h"
 #include "so_project.h"
 
 namespace dcora {
@@ -134,44 +135,6 @@ __global__ __launch_bounds__(kBlock) void k_project_rotations(ManiDesc m, double
   so_project<D>(M);
 #pragma unroll
   for (int e = 0; e < D * D; ++e) blk[e] = M[e];
-}
-
-// cyclic Jacobi eigen-decomposition of a small symmetric matrix (host): G = V diag(w) V^T
-void jacobi_eig(int n, std::vector<double> &G, std::vector<double> &V) {
-  V.assign((size_t)n * n, 0.0);
-  for (int i = 0; i < n; ++i) V[(size_t)i * n + i] = 1.0;
-  for (int sweep = 0; sweep < 100; ++sweep) {
-    double off = 0;
-    for (int p = 0; p < n - 1; ++p)
-      for (int q = p + 1; q < n; ++q) off = std::max(off, std::fabs(G[(size_t)q * n + p]));
-    double diag = 0;
-    for (int i = 0; i < n; ++i) diag = std::max(diag, std::fabs(G[(size_t)i * n + i]));
-    if (off <= 1e-16 * std::max(diag, 1e-300)) break;
-    for (int p = 0; p < n - 1; ++p)
-      for (int q = p + 1; q < n; ++q) {
-        const double apq = G[(size_t)q * n + p];
-        if (std::fabs(apq) <= 1e-300) continue;
-        const double app = G[(size_t)p * n + p], aqq = G[(size_t)q * n + q];
-        const double zeta = (aqq - app) / (2.0 * apq);
-        const double t = (zeta >= 0 ? 1.0 : -1.0) / (std::fabs(zeta) + std::sqrt(1.0 + zeta * zeta));
-        const double c = 1.0 / std::sqrt(1.0 + t * t), s = c * t;
-        for (int i = 0; i < n; ++i) {  // columns p, q
-          const double x = G[(size_t)p * n + i], y = G[(size_t)q * n + i];
-          G[(size_t)p * n + i] = c * x - s * y;
-          G[(size_t)q * n + i] = s * x + c * y;
-        }
-        for (int i = 0; i < n; ++i) {  // rows p, q
-          const double x = G[(size_t)i * n + p], y = G[(size_t)i * n + q];
-          G[(size_t)i * n + p] = c * x - s * y;
-          G[(size_t)i * n + q] = s * x + c * y;
-        }
-        for (int i = 0; i < n; ++i) {
-          const double x = V[(size_t)p * n + i], y = V[(size_t)q * n + i];
-          V[(size_t)p * n + i] = c * x - s * y;
-          V[(size_t)q * n + i] = s * x + c * y;
-        }
-      }
-  }
 }
 
 int check_device(int device) {

@@ -14,6 +14,7 @@
 #include "host_robust.h"
 #include "robust.h"
 #include "session_cert.h"
+#include "session_project.h"
 #include "session_round.h"
 #include "team_rules.h"
 
@@ -178,6 +179,24 @@ class SessionCore {
   int round_fetch_anchor(int anchor_pose, double *out);
   int round_hosted(const double *anchor, double *traj_area, double *spheres_area, double *landmarks_area);
 
+  // How CORA ends a certified solve, in place (session_project.h; ref examples/SingleRobotExample_RASLAM.cpp:220-234,
+  // projectSolutionRASLAM src/DCORA_utils.cpp:1984-2031): the session goes from rank r to rank d at Proj(V_d^T X), V_d
+  // the top-d eigenvectors of G = X X^T with the reflection rule folded in, and keeps everything lift keeps.
+  //   a. every stream of the session is synchronised;
+  //   b. G on the device in one pass over the mirror, its eigenproblem on the host (stable order among equal values);
+  //   c. r == d: the reference passes X through -- sigma, gram and cost2 are produced, nothing of the session changes;
+  //   d. the determinant count under V_d, the reflection (npos < n / 2), the projected point in a d x k buffer aside;
+  //   e. the central problem and every hosted agent's problem re-ranked to d, the kind's buffers re-dimensioned
+  //      (lift_buffers), the point adopted as set_X adopts one (lift_adopt).  A failure on the way takes the re-ranks
+  //      back, as in lift.
+  // Every output may be null.  sigma: r singular values of X, descending; basis: r x d column-major, V_d as applied
+  // (only where projected); gram: r x r, G as the device formed it; cost2: 2 f of the adopted point through
+  // central_problem()->eval_dev (the session's current matrices and weights); info8: projected, reflected, rotation
+  // blocks with positive determinant before the reflection, |rgrad| at the adopted point, ms of the projection
+  // kernels, ms of the re-dimensioning, ms total, columns per workgroup of the Gram kernel.  Refused, the session
+  // untouched, as lift (DCORA_ERR_UNSUPPORTED): the projection across the ranks of a job does not exist yet.
+  int project(double *sigma, double *basis, double *gram, double *cost2, double *info8);
+
   // ---- room for the ranks to come: an exchange created on this session sizes its halo slots, its staged slots and its
   // gather_X area by max(r, reserve_r), so that the job can lift up to that rank (Exchange::lift).  0: a job that will
   // never lift, laid out exactly as before.  Legal (d <= r <= r_reserve <= 16, else DCORA_ERR_BAD_ARG) until an
@@ -266,6 +285,8 @@ class SessionCore {
   SessionCertState cert_;  // built by the first certify
   SessionRoundState round_;  // built by the first round
   int round_buffers(const ManiDesc &m, bool with_lifted);
+  SessionProjectState project_;  // built by the first project
+  int project_buffers(const ManiDesc &m);
 
   // updateGamma / updateAlpha (ref src/Agent.cpp:1189-1200) and the round counter; the sequences are data-independent
   // and identical for every agent, so they live on the host

@@ -7,27 +7,12 @@
 #include <cstring>
 
 #include "device_chol.h"
+#include "round_quad.h"
 #include "session_core.h"
-#include "so_project.h"
 
 namespace dcora {
 
 namespace {
-
-constexpr int kQuad = 4;  // lanes per pose: lane c owns column c of the pose's block (k_spmm_bsrq's assignment)
-
-// where column c (c < D: rotation, c == D: translation) of pose i lies in the block
-template <int D>
-struct SeCols {
-  __device__ __forceinline__ long col(int i, int c) const { return (long)i * (D + 1) + c; }
-};
-template <int D>
-struct RaCols {
-  int n, l;
-  __device__ __forceinline__ long col(int i, int c) const {
-    return c < D ? (long)D * i + c : (long)D * n + l + i;
-  }
-};
 
 // the anchor into LDS: sm[a r + q] = R0(q, a) for a < D, sm[D r + q] = p_anchor(q).  Every workgroup reads the same
 // r (D + 1) words, so every one of them forms the same frame.
@@ -81,23 +66,8 @@ __global__ __launch_bounds__(kBlock) void k_round_states(int r, int n, Cols cols
 #pragma unroll
     for (int a = 0; a < D; ++a) m[a] -= t0[a];
   }
-  // column cc of M = R0^T Y_i from lane cc of the quad: quad_perm [cc, cc, cc, cc]
-  double A[D * D];
-#pragma unroll
-  for (int a = 0; a < D; ++a) {
-    A[0 * D + a] = dpp_move<0x00>(m[a]);
-    A[1 * D + a] = dpp_move<0x55>(m[a]);
-    if (D == 3) A[(D - 1) * D + a] = dpp_move<0xAA>(m[a]);
-  }
-  so_project<D>(A);
   double v[D];
-#pragma unroll
-  for (int a = 0; a < D; ++a) {
-    v[a] = m[a];
-#pragma unroll
-    for (int cc = 0; cc < D; ++cc)
-      if (c == cc) v[a] = A[cc * D + a];
-  }
+  quad_so_project<D>(m, c, v);
   if (!valid) return;
   double *__restrict__ o = traj + ((long)i * (D + 1) + c) * D;
 #pragma unroll
@@ -145,16 +115,7 @@ __global__ __launch_bounds__(kBlock) void k_round_points(int r, int count, const
 #pragma unroll
   for (int a = 0; a < D; ++a) out[j * D + a] = m[a];
   if (!lifted) return;
-  if (normalise) {
-    double s = 0.0;
-#pragma unroll
-    for (int a = 0; a < D; ++a) s = fma(m[a], m[a], s);
-    s = sqrt(s);
-    if (s > 0) {
-#pragma unroll
-      for (int a = 0; a < D; ++a) m[a] /= s;
-    }
-  }
+  if (normalise) unit_or_zero<D>(m);
   double *__restrict__ z = lifted + j * r;
   for (int q = 0; q < r; ++q) {
     double s = 0.0;

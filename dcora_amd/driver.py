@@ -101,7 +101,7 @@ def multi_robot_example(ds, X0, num_robots=5, r_min=5, r_max=100, max_iters=1000
 
 def _staircase_session(s, X0, k, r_min, r_max, max_iters, rgrad_tol, min_eig_tol, gradient_tolerance,
                        preconditioned_gradient_tolerance, mode, ts, gap=None, before_certify=None,
-                       round_on_device=False):
+                       round_on_device=False, project_on_device=False):
     """The staircase of the two drivers above in ONE session of either kind: each level is run / run_coloured, certify
     (the session's own, on the device) and lift (the escape into the next rank in place) -- the reference makes a new
     set of agents per level (examples/MultiRobotExample.cpp:352-366), this keeps them.  The level records are the
@@ -109,7 +109,12 @@ def _staircase_session(s, X0, k, r_min, r_max, max_iters, rgrad_tol, min_eig_tol
     that level's record; the earlier levels carry None).
     round_on_device: the solve's last step on the device too -- s.round(cost=True) before the session closes: the result
     also carries trajectory (unit_spheres and landmarks on a range-aided session), rounded_cost_2f and rounded_gradnorm
-    (None on a multi-rank job, where no rank holds the whole problem), in the frame of pose 0 of the final iterate."""
+    (None on a multi-rank job, where no rank holds the whole problem), in the frame of pose 0 of the final iterate.
+    project_on_device: how CORA ends a certified solve (ref examples/SingleRobotExample_RASLAM.cpp:220-234), on the
+    session too -- after a certified level s.project() takes the session to rank d in place, the level's own run
+    parameters refine the point there, and round_on_device then rounds the refined point.  The result also carries
+    sigma (the singular values of the certified X), projected_cost_2f, refined_cost_2f and refine_iters (None where no
+    level was certified); every other key is what it is without the option."""
     X = np.asarray(X0, dtype=np.float64)
     if X.shape != (r_min, k):
         raise ValueError("X0 must be r_min x k")
@@ -149,6 +154,15 @@ def _staircase_session(s, X0, k, r_min, r_max, max_iters, rgrad_tol, min_eig_tol
                 break
             ts = time.perf_counter()
         X = s.get_X()
+        projected = None
+        if project_on_device:
+            projected = dict(sigma=None, projected_cost_2f=None, refined_cost_2f=None, refine_iters=None)
+            if certified:
+                pr = s.project()
+                refine = _run_level(s, mode, max_iters, rgrad_tol)
+                refined = float(refine["cost"][-1]) if refine["iters"] else s.evaluate()[0]
+                projected = dict(sigma=pr["sigma"], projected_cost_2f=pr["cost_2f"], refined_cost_2f=refined,
+                                 refine_iters=int(refine["iters"]))
         rounded = s.round(cost=True) if round_on_device else None
     finally:
         s.close()
@@ -162,6 +176,8 @@ def _staircase_session(s, X0, k, r_min, r_max, max_iters, rgrad_tol, min_eig_tol
            "suboptimality_gap_f": levels[-1]["suboptimality_gap_f"] if levels else None, "levels": levels,
            "cost": cat(cost, float), "gradnorm": cat(gradnorm, float), "selected": cat(selected, np.int32),
            "rank_trace": cat(rank, np.int32)}
+    if projected is not None:
+        res.update(projected)
     if rounded is not None:
         for key in ("trajectory", "unit_spheres", "landmarks"):
             if key in rounded:
@@ -173,12 +189,14 @@ def _staircase_session(s, X0, k, r_min, r_max, max_iters, rgrad_tol, min_eig_tol
 def multi_robot_staircase_session(ds, X0, num_robots=5, r_min=5, r_max=100, max_iters=1000, rgrad_tol=0.1,
                                   min_eig_tol=1e-3, gradient_tolerance=1e-6, preconditioned_gradient_tolerance=1e-6,
                                   acceleration=True, params=None, device=0, mode="rbcd++", robust=None, fixed=None,
-                                  round_on_device=False):
+                                  round_on_device=False, project_on_device=False):
     """multi_robot_example's staircase (same arguments, same outputs) in ONE RbcdSession: the levels are run /
     run_coloured, RbcdSession.certify and RbcdSession.lift, so the agents, their matrices and preconditioners -- and,
     with robust=..., the weights and the GNC state -- live through every level, and the iterate stays on the device
     until the last one.  r_max is capped by the session's largest rank, 16.  round_on_device: RbcdSession.round ends the
-    solve (trajectory, rounded_cost_2f, rounded_gradnorm in the result)."""
+    solve (trajectory, rounded_cost_2f, rounded_gradnorm in the result).  project_on_device: after a certified level
+    RbcdSession.project takes the session to rank d in place and the level's run parameters refine the point there
+    (sigma, projected_cost_2f, refined_cost_2f, refine_iters in the result; the rounding is then of the refined point)."""
     _check_mode(mode)
     d, n = ds.d, ds.n
     ts = time.perf_counter()
@@ -191,15 +209,17 @@ def multi_robot_staircase_session(ds, X0, num_robots=5, r_min=5, r_max=100, max_
         s, X0, (d + 1) * n, r_min, min(r_max, 16), max_iters, rgrad_tol, min_eig_tol, gradient_tolerance,
         preconditioned_gradient_tolerance, mode, ts, before_certify=prep.join,
         gap=lambda X, psd, lmin: suboptimality_gap(X.shape[0], d, n, X, psd, min_eig_tol, lmin),
-        round_on_device=round_on_device)
+        round_on_device=round_on_device, project_on_device=project_on_device)
 
 
 def raslam_staircase_session(ra, X0, r_min=None, r_max=100, max_iters=1000, rgrad_tol=0.1, min_eig_tol=1e-3,
                              gradient_tolerance=1e-4, preconditioned_gradient_tolerance=1e-4, acceleration=True,
-                             params=None, device=0, mode="rbcd++", robust=None, fixed=None, round_on_device=False):
+                             params=None, device=0, mode="rbcd++", robust=None, fixed=None, round_on_device=False,
+                             project_on_device=False):
     """multi_robot_raslam_example's staircase (same arguments, same outputs, plus the traces) in ONE RaRbcdSession:
     RaRbcdSession.certify and RaRbcdSession.lift between the levels' runs.  round_on_device: RaRbcdSession.round ends
-    the solve (trajectory, unit_spheres, landmarks, rounded_cost_2f, rounded_gradnorm in the result)."""
+    the solve (trajectory, unit_spheres, landmarks, rounded_cost_2f, rounded_gradnorm in the result).  project_on_device:
+    RaRbcdSession.project and a refinement at rank d after a certified level, as multi_robot_staircase_session."""
     from . import RaRbcdSession, ROptParameters
     _check_mode(mode)
     r_min = ra.d if r_min is None else r_min
@@ -210,7 +230,7 @@ def raslam_staircase_session(ra, X0, r_min=None, r_max=100, max_iters=1000, rgra
                       robust=robust, fixed_weight=fixed)
     return _staircase_session(s, X0, ra.k, r_min, min(r_max, 16), max_iters, rgrad_tol, min_eig_tol,
                               gradient_tolerance, preconditioned_gradient_tolerance, mode, ts,
-                              round_on_device=round_on_device)
+                              round_on_device=round_on_device, project_on_device=project_on_device)
 
 
 def _check_mode(mode):

@@ -475,6 +475,32 @@ int dcora_rbcd_reserve_rank(dcora_rbcd_t s, int r_reserve);
  * DCORA_ERR_UNSUPPORTED: world_size > 1 (the ranks round together: dcora_exchange_round). */
 int dcora_rbcd_round(dcora_rbcd_t s, int anchor_pose, const double *anchor, double *trajectory, double *cost2,
                      double *info4);
+/* How CORA ends a certified solve, on the live session (ref examples/SingleRobotExample_RASLAM.cpp:220-234,
+ * projectSolutionRASLAM src/DCORA_utils.cpp:1984-2031): the session goes from rank r to rank d, in place, at
+ *   Proj(V_d^T X),   V_d = the top-d eigenvectors of G = X X^T (r x r), its last column negated where fewer than n / 2
+ * (integer division) of the blocks V_d^T Y_i have a positive determinant;
+ * rotation blocks projected to SO(d), unit-sphere columns normalised (a zero column stays zero), translation and
+ * landmark columns truncated only.  G is formed on the device in one pass over X, without floating-point atomics and
+ * with a fixed number of columns per workgroup: the same X gives the same G bit for bit, on any device; its r x r
+ * eigenproblem is solved on the host (equal eigenvalues keep the order of their index).  Everything dcora_rbcd_lift
+ * keeps is kept (matrices, preconditioners, robust weights, mu and the update count, the team and its parameters, a
+ * reserved rank); everything dcora_rbcd_set_X resets is reset.  Afterwards dcora_rbcd_rank reports d and the session
+ * behaves as a session created at rank d and handed the same point.  (A session created above rank 8 keeps the CSR
+ * form of its matrices, as after any re-rank.)
+ * r == d: the reference passes X through unprojected; sigma, gram and cost2 are produced, info8[0] = 0 and nothing of
+ * the session changes.
+ * Every output may be NULL.  sigma: r doubles, the singular values of X, descending (square roots of G's eigenvalues,
+ * round-off below zero clamped).  basis: r x d doubles column-major, V_d as applied (written only where the session was
+ * projected): the new iterate is exactly Proj(basis^T X).  gram: r x r doubles, G as the device formed it.  cost2: 2 f
+ * of the adopted point on the matrix the session holds NOW (its current robust weights).  info8: projected (0 / 1),
+ * reflected (0 / 1), rotation blocks with positive determinant before the reflection decision, |rgrad| at the adopted
+ * point, ms of the projection kernels, ms of the re-dimensioning, ms total, columns per workgroup of the Gram kernel.
+ * DCORA_ERR_UNSUPPORTED, the session untouched: a rank of a job, a ranked robust or team session, a session an exchange
+ * was created on (the projection across the ranks of a job does not exist yet). */
+int dcora_rbcd_project(dcora_rbcd_t s, double *sigma, double *basis, double *gram, double *cost2, double *info8);
+/* Debug entry of the tests: the one-pass Gram kernel of dcora_rbcd_project on a host array.  X: r x k column-major,
+ * 1 <= r <= 16, k >= 1; gram: r x r; *chunk (may be NULL): columns per workgroup. */
+int dcora_debug_project_gram(int r, long long k, const double *X, double *gram, int *chunk);
 /* Debug entry of the tests: the agent form of the lift's image kernel (k_lift_images).  From Xa (r x ka column-major:
  * one agent's block), the global v (kglobal doubles) and the agent's column map -- cols (ka global column indices) or,
  * with cols NULL, the contiguous range starting at col0 -- Xplus = [Xa; 0] and dir = [0; v_a^T], each (r + 1) x ka.
@@ -703,6 +729,9 @@ int dcora_ra_rbcd_rank(dcora_ra_rbcd_t s, int *r);
  * normalises them (ref src/DCORA_utils.cpp:1984-2031) -- the returned unit_spheres are not. */
 int dcora_ra_rbcd_round(dcora_ra_rbcd_t s, int anchor_pose, const double *anchor, double *trajectory,
                         double *unit_spheres, double *landmarks, double *cost2, double *info4);
+/* dcora_rbcd_project on a range-aided session: X, the projected point and basis^T X in the global RA ordering
+ * [rotations | unit spheres | translations | landmarks] */
+int dcora_ra_rbcd_project(dcora_ra_rbcd_t s, double *sigma, double *basis, double *gram, double *cost2, double *info8);
 /* dcora_rbcd_reserve_rank on a range-aided session: legal until dcora_exchange_create_ra */
 int dcora_ra_rbcd_reserve_rank(dcora_ra_rbcd_t s, int r_reserve);
 /* as dcora_rbcd_iterate / _evaluate / _run / _last_result; `selected` indexes the agents of dcora_ra_rbcd_info */
