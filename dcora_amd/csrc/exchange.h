@@ -19,7 +19,7 @@
 
 #include "cert_rows.h"
 #include "exchange_slots.h"
-#include "rbcd.h"
+#include "session_core.h"
 
 namespace dcora {
 
@@ -173,7 +173,6 @@ class Exchange {
   bool registered_ = false;
   ShmHeader *hdr_ = nullptr;
   uint64_t red_seq_ = 0;
-  RbcdSession *pose_ = nullptr;      // the session when it is a pose-graph one (its chain_launches counter)
   std::vector<double> job_w_;        // the job's weights as of the last weight change (the team's loop-closure counts)
   std::vector<int> team_due_;        // agents whose status the evaluation of this rbcd_iterate has to collect
   int team_clear_to_write(const int *agents, int count);  // before the agents optimise: their slots may be overwritten

@@ -351,7 +351,6 @@ int Exchange::barrier(double timeout_s) {
 int Exchange::init(SessionCore *s, const char *job_name, size_t weights) {
   s_ = s;
   s->exchange_attached = true;  // (from here on the session lifts through this exchange only, within its reserve)
-  pose_ = dynamic_cast<RbcdSession *>(s);
   rank = s->opt.rank;
   world = s->opt.world_size;
   R_ = s->R;
@@ -840,7 +839,7 @@ int Exchange::rbcd_iterate(int selected, double *cost2, double *gradnorm, double
   int nxt = selected;
   rc = evaluate(cost2, gradnorm, block_norms, &nxt);
   team_due_.clear();
-  if (pose_) pose_->chain_launches += g_chain_launches.load(std::memory_order_relaxed) - launches0;
+  s_->chain_launches += g_chain_launches.load(std::memory_order_relaxed) - launches0;
   if (rc) return rc;
   if (next_selected) *next_selected = s_->agent_core(selected).neighbors.empty() ? selected : nxt;
   return DCORA_OK;
@@ -874,10 +873,11 @@ void Exchange::team_snapshot_weights() {
 // The job's weights are complete in the area whenever no update is under way; the closing barrier keeps a rank that
 // runs ahead from starting one (its kernel stores into the area) while another still copies.
 int Exchange::team_enable(const dcora_team_params &p, bool range_aided) {
-  if (!pose_ && !range_aided)
+  const bool pose_graph = s_->kind() == SessionKind::PoseGraph;
+  if (!pose_graph && !range_aided)
     return usage("team_enable: dcora_exchange_team_enable serves pose-graph sessions; a range-aided job enables its team "
                  "through dcora_exchange_team_enable_ra", DCORA_ERR_UNSUPPORTED);
-  if (pose_ && range_aided)
+  if (pose_graph && range_aided)
     return usage("team_enable: dcora_exchange_team_enable_ra serves range-aided sessions; a pose-graph job enables its "
                  "team through dcora_exchange_team_enable", DCORA_ERR_UNSUPPORTED);
   if (s_->weights_ranked() && lay_.w_doubles != s_->weights_count())

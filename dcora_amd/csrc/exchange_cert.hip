@@ -14,7 +14,6 @@
 #include "cert.h"
 #include "device_chol.h"
 #include "exchange.h"
-#include "ra_rbcd.h"
 
 namespace dcora {
 
@@ -223,12 +222,10 @@ struct Exchange::CertRows {
 };
 
 // The pose-graph and the range-aided session through one flow: what differs is where an agent's variables sit in the
-// global ordering (a contiguous range / scattered: CertBlock) and the layout its Lambda blocks act on.  Post and wait of
+// global ordering (a contiguous range / scattered: the session's AgentBlock) and the layout its Lambda blocks act on.  Post and wait of
 // all agents -- every rank's mirror holds its neighbours' current public poses --, then the Lambda blocks of the hosted
 // agents: EG_b = X_b Q_bb + X C_b, Lambda = SymBlockDiag(X_b^T EG_b).
 int Exchange::cert_rows_begin(CertRows *rows) {
-  RbcdSession *pgo = dynamic_cast<RbcdSession *>(s_);
-  RaRbcdSession *ras = dynamic_cast<RaRbcdSession *>(s_);
   hipStream_t st = s_->st;
   const int R = s_->R, r = s_->r;
   double *mirror = s_->Xg.p;
@@ -241,34 +238,24 @@ int Exchange::cert_rows_begin(CertRows *rows) {
   if (rc) return rc;
   std::vector<CertBlock> &blocks = rows->blocks;
   int nloc = 0, lo = -1;
-  if (pgo) {
-    for (AgentDev &a : pgo->agents) {
-      if (!a.hosted) continue;
-      CertBlock B;
-      B.k = (pgo->d + 1) * a.n;
-      B.loc0 = nloc;
-      B.col0 = a.col0;
-      B.prob = a.prob.get();
-      B.coupling = a.coupling.view();
-      B.X = pgo->Xg.p + (size_t)a.col0 * r;
-      if (lo < 0) lo = a.col0;
-      nloc += B.k;
-      blocks.push_back(std::move(B));
-    }
-  } else {
-    for (RaAgentDev &a : ras->agents) {
-      if (!a.hosted) continue;
-      CertBlock B;
-      B.k = a.k;
-      B.loc0 = nloc;
-      B.own_dev = a.own.p;
-      B.prob = a.prob.get();
-      B.coupling = a.coupling.view();
-      B.X = a.X.p;
-      rows->row_map.insert(rows->row_map.end(), a.own_host.begin(), a.own_host.end());
-      nloc += B.k;
-      blocks.push_back(std::move(B));
-    }
+  for (int a = 0; a < R; ++a) {
+    AgentCore &core = s_->agent_core(a);
+    if (!core.hosted) continue;
+    const AgentBlock blk = s_->agent_block(a);
+    CertBlock B;
+    B.k = blk.k;
+    B.loc0 = nloc;
+    B.col0 = (int)blk.col0;
+    B.own_dev = blk.cols_dev;
+    B.prob = core.prob.get();
+    B.coupling = core.coupling.view();
+    B.X = blk.X;
+    if (!blk.contiguous())
+      rows->row_map.insert(rows->row_map.end(), blk.cols_host, blk.cols_host + blk.k);
+    else if (lo < 0)
+      lo = (int)blk.col0;
+    nloc += B.k;
+    blocks.push_back(std::move(B));
   }
   rows->nloc = nloc;
   rows->lo = lo < 0 ? 0 : lo;
@@ -287,13 +274,11 @@ int Exchange::cert_rows_begin(CertRows *rows) {
 
 int Exchange::certify(const HostCsr *Qglobal, double eta, int *certified, double *theta, double *lambda_min, double *v,
                       long long *matvecs, int *distributed) {
-  RbcdSession *pgo = dynamic_cast<RbcdSession *>(s_);
-  RaRbcdSession *ras = dynamic_cast<RaRbcdSession *>(s_);
-  if (!pgo && !ras) return usage("certify: unknown session kind", DCORA_ERR_UNSUPPORTED);
   const int device = s_->opt.device;
   DCORA_HIP(hipSetDevice(device));
   const int r = s_->r, ktot = (int)s_->num_cols();
-  const dcora_dims dims = pgo ? dcora_dims{r, pgo->d, pgo->n, 0, 0} : dcora_dims{r, ras->d, ras->n, ras->l, ras->b, DCORA_LAYOUT_RA};
+  const ManiDesc mg = s_->global_manifold();
+  const dcora_dims dims{r, mg.d, mg.n, mg.l, mg.b, mg.se ? DCORA_LAYOUT_AUTO : DCORA_LAYOUT_RA};
   const int chol_block = s_->cert_block();
   if (certified) *certified = 0;
   if (theta) *theta = 0;
@@ -487,8 +472,6 @@ int Exchange::cert_min_eigenpair(CertRows &rows, const HostCsr &M, double eta, b
 // problem's in a one-rank job.  The agents' patterns are taken back from the device once: the matrices the kernel will
 // read.  No pass over the dataset.
 int Exchange::live_cert_build() {
-  RbcdSession *pgo = dynamic_cast<RbcdSession *>(s_);
-  RaRbcdSession *ras = dynamic_cast<RaRbcdSession *>(s_);
   LiveCertState &cs = live_;
   HostCsr central;
   const HostCsr *Qpat = &s_->job_pat;
@@ -510,14 +493,9 @@ int Exchange::live_cert_build() {
   for (int a = 0; a < s_->R; ++a) {
     AgentCore &core = s_->agent_core(a);
     if (!core.hosted) continue;
-    std::vector<int> own;
-    if (pgo) {
-      const AgentDev &ad = pgo->agents[(size_t)a];
-      own.resize((size_t)(pgo->d + 1) * ad.n);
-      for (size_t i = 0; i < own.size(); ++i) own[i] = ad.col0 + (int)i;
-    } else {
-      own = ras->agents[(size_t)a].own_host;
-    }
+    const AgentBlock blk = s_->agent_block(a);
+    std::vector<int> own((size_t)blk.k);
+    for (int i = 0; i < blk.k; ++i) own[(size_t)i] = (int)blk.global_col(i);
     HostCsr Qaa, C;
     int rc = core.prob->Q.download(&Qaa);
     if (!rc) rc = core.coupling.download(&C);
@@ -557,8 +535,6 @@ int Exchange::certify_live(double eta, int *certified, double *theta, double *la
   // refusals, from the arguments alone: no collective step has begun and the job is untouched
   if (!certified) return usage("certify_live: certified is required", DCORA_ERR_BAD_ARG);
   if (!std::isfinite(eta) || eta < 0) return usage("certify_live: eta must be finite and not negative", DCORA_ERR_BAD_ARG);
-  if (!dynamic_cast<RbcdSession *>(s_) && !dynamic_cast<RaRbcdSession *>(s_))
-    return usage("certify_live: unknown session kind", DCORA_ERR_UNSUPPORTED);
   // from here on a failure on this rank is the job's: the others leave their waits by the `failed` word
   const int rc = certify_live_run(eta, certified, theta, lambda_min, v, matvecs, distributed, info10);
   if (rc && hdr_) hdr_->failed.store(1);

@@ -59,7 +59,7 @@ class RaRbcdSession : public SessionCore {
   std::unique_ptr<DeviceProblem> central;  // global Q: cost and Riemannian gradient of the merged problem
   DevBuf<double> evalbuf;
 
-  RaRbcdSession() : SessionCore("ra_rbcd") {}
+  RaRbcdSession() : SessionCore(SessionKind::RangeAided) {}
   ~RaRbcdSession();
   int init(const HostRADataset &ds, const dcora_rbcd_options &o);
   // robust sessions (RobustState, session_core.h; the job's measurements are the pose-pose ones): weight 1 on every
@@ -84,7 +84,9 @@ class RaRbcdSession : public SessionCore {
   DeviceProblem *central_problem() override { return central.get(); }
   int cert_block() const override { return 1; }
   ManiDesc global_manifold() const override { return make_mani(r, d, n, l, b, DCORA_LAYOUT_RA); }
-  int x_stage_hosted(double *host_area) override;
+  // its own X with the `own` list; its ordering is ra_agent_columns': [rotations | unit spheres | translations |
+  // landmarks], or the SE ordering where it owns neither a unit sphere nor a landmark
+  AgentBlock agent_block(int a) override;
 
  private:
   // the one path from a dataset's measurements to the session's matrices, at creation and on every re-weight
@@ -96,15 +98,11 @@ class RaRbcdSession : public SessionCore {
   int robust_restart_acceleration() override;
   // set_X's body for a point on the host or on the device (kind: the copy into the mirror)
   int adopt_X(const double *X, hipMemcpyKind kind);
-  // SessionCore::lift's hooks: the mirror, X_initial and the agents' X, V, Y, XPrev, tmp re-dimensioned; the central
+  // the rank change's hooks: the mirror, X_initial and the agents' X, V, Y, XPrev, tmp re-dimensioned; the central
   // preconditioner's regularisation is device_precond_regularization(central Q), as driver.py passes
   int lift_default_reg(const HostCsr &Qc, double *reg) override;
   int lift_buffers(int r_new) override;
   int lift_adopt(const double *X_dev) override { return adopt_X(X_dev, hipMemcpyDeviceToDevice); }
-  // the collective lift's: an agent's block is its own X, its columns the `own` list (scattered through the RA ordering)
-  void lift_agent_view(AgentCore &a, const double **X_a, const int **cols, long *col0) override;
-  int lift_scatter_block(AgentCore &a, int rows, const double *block, double *mirror) override;
-  void round_agent_map(AgentCore &a, RoundAgentMap *map) override;  // (from its `own` list)
   int gather_agents();         // every hosted agent's X from the mirror, V = Y = XPrev = X (enqueued)
   int scatter(RaAgentDev &a);  // my X into the global mirror
   int solve(RaAgentDev &a, const double *start, double **result);

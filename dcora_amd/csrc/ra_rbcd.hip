@@ -325,31 +325,16 @@ int RaRbcdSession::lift_buffers(int r_new) {
   return DCORA_OK;
 }
 
-void RaRbcdSession::lift_agent_view(AgentCore &core, const double **X_a, const int **cols, long *col0) {
-  const RaAgentDev &a = static_cast<const RaAgentDev &>(core);
-  *X_a = a.X.p;
-  *cols = a.own.p;
-  *col0 = 0;
-}
-
-// the agent's ordering is ra_agent_columns': [rotations | unit spheres | translations | landmarks], or the SE ordering
-// where it owns neither a unit sphere nor a landmark
-void RaRbcdSession::round_agent_map(AgentCore &core, RoundAgentMap *map) {
-  const RaAgentDev &a = static_cast<const RaAgentDev &>(core);
-  const std::vector<int> &own = a.own_host;
-  map->n = a.n, map->l = a.l, map->b = a.b, map->se = (a.l == 0 && a.b == 0) ? 1 : 0;
-  map->pose.resize((size_t)a.n);
-  map->sphere.resize((size_t)a.l);
-  map->landmark.resize((size_t)a.b);
-  for (int j = 0; j < a.n; ++j) map->pose[(size_t)j] = own[(size_t)(map->se ? (d + 1) * j : d * j)] / d;
-  for (int j = 0; j < a.l; ++j) map->sphere[(size_t)j] = own[(size_t)(d * a.n + j)] - d * n;
-  for (int j = 0; j < a.b; ++j) map->landmark[(size_t)j] = own[(size_t)(d * a.n + a.l + a.n + j)] - (d * n + l + n);
-}
-
-int RaRbcdSession::lift_scatter_block(AgentCore &core, int rows, const double *block, double *mirror) {
-  const RaAgentDev &a = static_cast<const RaAgentDev &>(core);
-  launch_scatter_cols(st, rows, a.k, a.own.p, block, mirror);
-  return DCORA_OK;
+AgentBlock RaRbcdSession::agent_block(int id) {
+  const RaAgentDev &a = agents[(size_t)id];
+  AgentBlock blk;
+  blk.X = a.X.p;
+  blk.k = a.k;
+  blk.n = a.n, blk.l = a.l, blk.b = a.b;
+  blk.se = (a.l == 0 && a.b == 0) ? 1 : 0;
+  blk.cols_dev = a.own.p;
+  blk.cols_host = a.own_host.data();
+  return blk;
 }
 
 int RaRbcdSession::adopt_X(const double *X, hipMemcpyKind kind) {
@@ -563,19 +548,6 @@ int RaRbcdSession::team_launch_rel_change(const std::vector<int> &ids) {
   else
     launch_rel_change_ra(st, r, set, team->rel_dev);
   DCORA_HIP(hipGetLastError());
-  return DCORA_OK;
-}
-
-int RaRbcdSession::x_stage_hosted(double *host_area) {
-  DCORA_HIP(hipSetDevice(opt.device));
-  std::vector<double> whole((size_t)r * k);
-  DCORA_HIP(hipMemcpyAsync(whole.data(), Xg.p, sizeof(double) * whole.size(), hipMemcpyDeviceToHost, st));
-  DCORA_HIP(hipStreamSynchronize(st));
-  for (const RaAgentDev &a : agents) {
-    if (!a.hosted) continue;
-    for (int c : a.own_host)
-      std::copy(&whole[(size_t)c * r], &whole[(size_t)c * r] + r, host_area + (size_t)c * r);
-  }
   return DCORA_OK;
 }
 

@@ -52,7 +52,7 @@ class RbcdSession : public SessionCore {
   dcora_ropt_result last{};
   int last_result(dcora_ropt_result *res);
 
-  RbcdSession() : SessionCore("rbcd") { R = 1; }
+  RbcdSession() : SessionCore(SessionKind::PoseGraph) { R = 1; }
   ~RbcdSession();
   int init(const HostDataset &ds, const dcora_rbcd_options &o);
   // robust sessions (RobustState, session_core.h): weight 1 on every loop closure that is not fixed (fixed: m flags or
@@ -76,7 +76,6 @@ class RbcdSession : public SessionCore {
   int agent_update_neighbor(int agent, int neighbor, int count, const int *frames, const double *poses, bool aux);
   std::vector<int> agent_it;  // Agent::iteration_number() of every agent
   int agent_iteration_number(int agent) const;
-  long chain_launches = 0;  // kernel launches of the chain's wrappers enqueued by iterate() (debug counter)
   int pack_public(int agent, double *packed_dev);
   int unpack_public(int agent, const double *packed_dev);
 
@@ -86,7 +85,7 @@ class RbcdSession : public SessionCore {
   DeviceProblem *central_problem() override { return central.get(); }
   int cert_block() const override { return d + 1; }
   ManiDesc global_manifold() const override { return mg; }
-  int x_stage_hosted(double *host_area) override;
+  AgentBlock agent_block(int a) override;  // (its contiguous range of the mirror, SE ordering)
 
  private:
   bool chain_rides_ = false;  // env::chain_rides() when the session was created
@@ -97,15 +96,11 @@ class RbcdSession : public SessionCore {
   std::vector<char> set_marks_;  // agents that received Agent::setX since the last round
   // set_X's body for a point on the host or on the device (kind: the copy into the mirror)
   int adopt_X(const double *X, hipMemcpyKind kind);
-  // SessionCore::lift's hooks: Xg, Vg, Yg, XPrevg, X_initial and the staging buffer of get_X re-dimensioned, the agents'
+  // the rank change's hooks: Xg, Vg, Yg, XPrevg, X_initial and the staging buffer of get_X re-dimensioned, the agents'
   // handed neighbour caches dropped; the central preconditioner's regularisation is the agents' (driver.py passes 0.1)
   int lift_default_reg(const HostCsr &Qc, double *reg) override;
   int lift_buffers(int r_new) override;
   int lift_adopt(const double *X_dev) override { return adopt_X(X_dev, hipMemcpyDeviceToDevice); }
-  // the collective lift's: an agent's block is its contiguous range of the mirror
-  void lift_agent_view(AgentCore &a, const double **X_a, const int **cols, long *col0) override;
-  int lift_scatter_block(AgentCore &a, int rows, const double *block, double *mirror) override;
-  void round_agent_map(AgentCore &a, RoundAgentMap *map) override;  // (its poses are a contiguous range)
   int update_nonselected_agent(AgentDev &a, bool restart);
   int update_selected_agent(AgentDev &a, bool restart);
   int restart_step(AgentDev &a);

@@ -392,27 +392,14 @@ int RbcdSession::lift_buffers(int r_new) {
   return DCORA_OK;
 }
 
-void RbcdSession::lift_agent_view(AgentCore &core, const double **X_a, const int **cols, long *col0) {
-  const AgentDev &a = static_cast<const AgentDev &>(core);
-  *X_a = Xg.p + (size_t)a.col0 * r;
-  *cols = nullptr;
-  *col0 = a.col0;
-}
-
-void RbcdSession::round_agent_map(AgentCore &core, RoundAgentMap *map) {
-  const AgentDev &a = static_cast<const AgentDev &>(core);
-  map->n = a.n, map->l = map->b = 0, map->se = 1;
-  map->pose.resize((size_t)a.n);
-  for (int j = 0; j < a.n; ++j) map->pose[(size_t)j] = a.col0 / (d + 1) + j;
-  map->sphere.clear();
-  map->landmark.clear();
-}
-
-int RbcdSession::lift_scatter_block(AgentCore &core, int rows, const double *block, double *mirror) {
-  const AgentDev &a = static_cast<const AgentDev &>(core);
-  DCORA_HIP(hipMemcpyAsync(mirror + (size_t)a.col0 * rows, block, sizeof(double) * (size_t)rows * (d + 1) * a.n,
-                           hipMemcpyDeviceToDevice, st));
-  return DCORA_OK;
+AgentBlock RbcdSession::agent_block(int id) {
+  const AgentDev &a = agents[(size_t)id];
+  AgentBlock blk;
+  blk.X = Xg.p + (size_t)a.col0 * r;
+  blk.k = (d + 1) * a.n;
+  blk.n = a.n;
+  blk.col0 = a.col0;
+  return blk;
 }
 
 // ---- robust sessions (RobustState, session_core.h): what is this kind's own -----------------------------------------
@@ -1001,18 +988,6 @@ int RbcdSession::pack_public(int agent, double *packed_dev) {
 int RbcdSession::unpack_public(int agent, const double *packed_dev) {
   AgentDev &a = agents[agent];
   launch_scatter_cols(st, r, (int)a.public_poses.size() * (d + 1), a.public_cols.p, packed_dev, Xg.p);
-  return DCORA_OK;
-}
-
-int RbcdSession::x_stage_hosted(double *host_area) {
-  DCORA_HIP(hipSetDevice(opt.device));
-  for (const AgentDev &a : agents) {
-    if (!a.hosted) continue;
-    const size_t off = (size_t)a.col0 * r;
-    DCORA_HIP(hipMemcpyAsync(host_area + off, Xg.p + off, sizeof(double) * (size_t)r * (d + 1) * a.n,
-                             hipMemcpyDeviceToHost, st));
-  }
-  DCORA_HIP(hipStreamSynchronize(st));
   return DCORA_OK;
 }
 

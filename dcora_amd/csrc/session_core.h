@@ -3,6 +3,8 @@
 // also all the in-library exchange (exchange.h) needs from a session, so the same transport -- peer stores into
 // IPC-mapped halo buffers, flag words and evaluation scalars in the shared segment -- carries both kinds (ref
 // src/Agent.cpp:113-152, 844-906: getSharedStateDicts / updateNeighborStates are the same calls on either graph type).
+// Where a hosted agent's block lies (agent_block), how a session changes rank (RankChange, redimension) and what "nothing
+// of the session is in flight" means (drain) are stated here once, for the session's own calls and for the exchange's.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -10,8 +12,10 @@
 #include <string>
 #include <vector>
 
+#include "agent_block.h"
 #include "device_problem.h"
 #include "host_robust.h"
+#include "rank_change.h"
 #include "robust.h"
 #include "session_cert.h"
 #include "session_project.h"
@@ -93,6 +97,8 @@ struct RobustState {
   HostCsr live_pat;  // range-aided: the central Q's entries as the current weights give them (what certify reads)
 };
 
+enum class SessionKind { PoseGraph, RangeAided };
+
 class SessionCore {
  public:
   int r = 0, R = 0;  // relaxation rank (rows of the mirror), agents
@@ -106,7 +112,8 @@ class SessionCore {
   DeviceProblem *last_solver = nullptr;
   double setup_ms = 0;
 
-  explicit SessionCore(const char *tag) : tag_(tag) {}
+  explicit SessionCore(SessionKind kind) : kind_(kind), tag_(kind == SessionKind::PoseGraph ? "rbcd" : "ra_rbcd") {}
+  SessionKind kind() const { return kind_; }
   const char *tag() const { return tag_; }
   virtual ~SessionCore() {}
   virtual AgentCore &agent_core(int a) = 0;
@@ -116,8 +123,15 @@ class SessionCore {
   // per hosted agent a: out[2a] = |Proj(X_a Q_aa + G_a)|^2, out[2a + 1] = <X_a, X_a Q_aa + G_a> (device, 2 R doubles)
   virtual int phase_evaluate_dev(double *out_dev) = 0;
   virtual int set_X(const double *Xh) = 0;
-  // the hosted agents' columns of the mirror into host_area (laid out like the mirror); synchronises
-  virtual int x_stage_hosted(double *host_area) = 0;
+  // where hosted agent a's block lies now (agent_block.h): a view for the call at hand, void after a rank change
+  virtual AgentBlock agent_block(int a) = 0;
+  // the hosted agents' columns of the mirror into host_area (laid out like the mirror): a contiguous block is copied
+  // straight from the device, listed ones go through one download of the whole mirror; synchronises
+  int x_stage_hosted(double *host_area);
+  // nothing of the session is in flight: every agent's own stream is synchronised, then (then_session) the session's
+  int drain(bool then_session);
+  long chain_launches = 0;  // kernel launches of the chain's wrappers enqueued by the iterate() of the session or of its
+                            // exchange (debug counter; only the pose-graph kind reports it)
 
   // greedy colouring of the agent graph in agent order: agents of one colour share no measurement, so their
   // simultaneous updates equal the same updates done one after the other
@@ -144,9 +158,10 @@ class SessionCore {
   //      default (lift_default_reg: what the two Python drivers pass);
   //   c. the central problem is re-ranked and runs the device escape from the mirror;
   //   d. no escape: its re-rank is undone, *escaped = 0, nothing of the session has changed;
-  //   e. escaped: every hosted agent's problem is re-ranked, the kind's buffers re-dimensioned (lift_buffers), and the
-  //      accepted point adopted as set_X adopts one (lift_adopt): mirror, agents' blocks, V = Y = XPrev = X, sequences
-  //      and round counters restarted, X_initial of a robust session, team statuses cleared.  Handed neighbour caches
+  //   e. escaped: every hosted agent's problem is re-ranked and the session re-dimensioned (redimension): the kind's
+  //      buffers (lift_buffers), the accepted point adopted as set_X adopts one (lift_adopt) -- mirror, agents' blocks,
+  //      V = Y = XPrev = X, sequences and round counters restarted, X_initial of a robust session, team statuses
+  //      cleared.  Handed neighbour caches
   //      are dropped; device pointers into the session's buffers handed out earlier (X_device_ptr) are void.
   // Refused, the session untouched: a rank of a job, a ranked robust / team session or a session an exchange was created
   // on (DCORA_ERR_UNSUPPORTED: those lift together, through their exchange -- Exchange::lift); r = 16, v null or not
@@ -170,7 +185,7 @@ class SessionCore {
   int round_check_args(int anchor_pose, const double *anchor, const double *trajectory) const;
   // ---- the session's half of the collective rounding (Exchange::round, where the flow stands).  A rank's mirror is
   // current only in its hosted agents' columns and the neighbours' public ones, so every state is rounded by the rank
-  // that hosts it, from the agent's own block (lift_agent_view), with the kernel of round.
+  // that hosts it, from the agent's own block (agent_block), with the kernel of round.
   //   fetch_anchor: the r x (d + 1) words of global pose anchor_pose into out where this rank hosts it (else out is left
   //                 as it is: the caller's zeros); synchronises
   //   hosted:       the hosted agents' poses, unit spheres and landmarks rounded against the anchor (host, r x (d + 1))
@@ -186,9 +201,8 @@ class SessionCore {
   //   b. G on the device in one pass over the mirror, its eigenproblem on the host (stable order among equal values);
   //   c. r == d: the reference passes X through -- sigma, gram and cost2 are produced, nothing of the session changes;
   //   d. the determinant count under V_d, the reflection (npos < n / 2), the projected point in a d x k buffer aside;
-  //   e. the central problem and every hosted agent's problem re-ranked to d, the kind's buffers re-dimensioned
-  //      (lift_buffers), the point adopted as set_X adopts one (lift_adopt).  A failure on the way takes the re-ranks
-  //      back, as in lift.
+  //   e. the central problem and every hosted agent's problem re-ranked to d, the session re-dimensioned (redimension)
+  //      at the point.  A failure on the way takes the re-ranks back, as in lift.
   // Every output may be null.  sigma: r singular values of X, descending; basis: r x d column-major, V_d as applied
   // (only where projected); gram: r x r, G as the device formed it; cost2: 2 f of the adopted point through
   // central_problem()->eval_dev (the session's current matrices and weights); info8: projected, reflected, rotation
@@ -219,10 +233,11 @@ class SessionCore {
   //   scalars: G_a from the trial mirror, then per hosted agent <X_a Q_aa, X_a> + <X_a, G_a>, |rgrad_a|^2 and
   //            |Proj(rgrad_a M_a^-1)|^2 with the agent's own preconditioner; ONE host wait; out3: their sums over the
   //            hosted agents in agent order (2 f's share, |rgrad|^2's, |P grad|^2's)
-  //   commit:  the central problem of a one-rank job re-ranked, the kind's buffers re-dimensioned (lift_buffers), the
-  //            trial mirror adopted as set_X adopts a point (lift_adopt); *redim_ms: what that took plus the
-  //            agents' re-ranks of begin -- the re-dimensioning as SessionCore::lift's info8[6] counts it
-  //   abort:   every re-ranked problem back at r (the error that led here stays the one reported)
+  //   commit:  the central problem of a one-rank job re-ranked, the session re-dimensioned (redimension) at the trial
+  //            mirror; *redim_ms: what that took plus the agents' re-ranks of begin -- the re-dimensioning as
+  //            SessionCore::lift's info8[6] counts it
+  //   abort:   the trial's RankChange rolled back: every re-ranked problem at r again (the error that led here stays the
+  //            one reported)
   int lift_trial_begin(const double *v_host);
   int lift_trial_point(double alpha, double **mirror);
   int lift_trial_scalars(double out3[3]);
@@ -279,6 +294,7 @@ class SessionCore {
                int *weight_updates, int *stop_reason);
 
  protected:
+  const SessionKind kind_;
   const char *tag_;  // "rbcd" / "ra_rbcd": the prefix of the messages
   hipEvent_t fork_ev_ = nullptr;
   bool own_stream_ = true;
@@ -301,7 +317,7 @@ class SessionCore {
   void release_tick_resources(AgentCore &a);  // before the agent's problem goes
   void release_stream();  // (with the fork event) after everything that runs on it has gone
 
-  // what a session kind supplies to lift:
+  // what a session kind supplies to a rank change (lift, the collective lift, project):
   // the regularisation of the central preconditioner where the caller names none
   virtual int lift_default_reg(const HostCsr &Qc, double *reg) = 0;
   // the buffers the kind owns at rank r_new, allocated aside and swapped in, with r, opt.r and what else the kind
@@ -309,24 +325,20 @@ class SessionCore {
   virtual int lift_buffers(int r_new) = 0;
   // set_X of a point that lies on the device (r x num_cols(), the mirror's ordering): everything set_X leaves
   virtual int lift_adopt(const double *X_dev) = 0;
-  // ... and to the collective lift: a hosted agent's block (r x k_a, its own ordering) and where its columns lie in the
-  // global ordering -- *cols when the kind keeps a list (range-aided agents), else the contiguous range from *col0;
-  virtual void lift_agent_view(AgentCore &a, const double **X_a, const int **cols, long *col0) = 0;
-  // a hosted agent's block of `rows` rows into its columns of a mirror of `rows` rows (enqueued on st)
-  virtual int lift_scatter_block(AgentCore &a, int rows, const double *block, double *mirror) = 0;
-  // ... and to the collective rounding: the dimensions and ordering of a hosted agent's block and the global indices
-  // of its poses, unit spheres and landmarks, in the block's order
-  struct RoundAgentMap {
-    int n = 0, l = 0, b = 0, se = 1;
-    std::vector<int> pose, sphere, landmark;
-  };
-  virtual void round_agent_map(AgentCore &a, RoundAgentMap *map) = 0;
+  // The re-dimensioning of a rank change whose problems `change` holds, in this order: the certificate's XQ at r_new
+  // aside (where a certificate was built), lift_buffers, the swap of XQ, change.commit() -- the point of no return --,
+  // lift_adopt of the device point X_dev, the session's stream synchronised.  A failure before the commit leaves the
+  // session as it was and `change` to its roll-back; after a failed lift_adopt the session stays at r_new.  what:
+  // "lift" / "project", for the message.
+  int redimension(const char *what, int r_new, const double *X_dev, RankChange<DeviceProblem> &change);
+  // a block of `rows` rows in blk's ordering into blk's columns of a mirror of `rows` rows (enqueued on st)
+  int scatter_block(const AgentBlock &blk, int rows, const double *block, double *mirror);
   struct LiftTrial {
-    int r_old = 0;
-    bool central_reranked = false;
+    explicit LiftTrial(int r_old) : change(r_old) {}
     double rerank_ms = 0;            // what the hosted agents' re-ranks took in lift_trial_begin
     DevBuf<double> mirror, v, scal;  // (r + 1) x num_cols(), num_cols(), 4 per hosted agent
     std::vector<int> hosted;         // in agent order
+    RankChange<DeviceProblem> change;  // (the last member: the re-ranks go back before the buffers go)
   };
   std::unique_ptr<LiftTrial> lift_trial_;  // between lift_trial_begin and commit / abort
 

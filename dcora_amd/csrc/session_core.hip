@@ -36,6 +36,65 @@ int SessionCore::agent_colours(int *colours, int *ncolours) {
   return DCORA_OK;
 }
 
+int SessionCore::drain(bool then_session) {
+  for (int a = 0; a < R; ++a)
+    if (agent_core(a).own_st) DCORA_HIP(hipStreamSynchronize(agent_core(a).own_st));
+  if (then_session) DCORA_HIP(hipStreamSynchronize(st));
+  return DCORA_OK;
+}
+
+int SessionCore::redimension(const char *what, int r_new, const double *X_dev, RankChange<DeviceProblem> &change) {
+  DevBuf<double> xq;
+  if (cert_.built && hipSuccess != xq.alloc((size_t)r_new * (size_t)num_cols())) {
+    (void)hipGetLastError();
+    set_last_error(std::string(tag_) + " " + what + ": out of device memory");
+    return DCORA_ERR_HIP;
+  }
+  int rc = lift_buffers(r_new);
+  if (rc) return rc;
+  if (cert_.built) cert_.XQ = std::move(xq);
+  change.commit();  // (the session is at r_new from here on: nothing is left to take back)
+  rc = lift_adopt(X_dev);
+  if (rc) return rc;
+  DCORA_HIP(hipStreamSynchronize(st));
+  return DCORA_OK;
+}
+
+int SessionCore::scatter_block(const AgentBlock &blk, int rows, const double *block, double *mirror) {
+  if (blk.contiguous())
+    DCORA_HIP(hipMemcpyAsync(mirror + (size_t)blk.col0 * rows, block, sizeof(double) * (size_t)rows * blk.k,
+                             hipMemcpyDeviceToDevice, st));
+  else
+    launch_scatter_cols(st, rows, blk.k, blk.cols_dev, block, mirror);
+  return DCORA_OK;
+}
+
+int SessionCore::x_stage_hosted(double *host_area) {
+  DCORA_HIP(hipSetDevice(opt.device));
+  bool listed = false;
+  for (int a = 0; a < R; ++a) {
+    if (!agent_core(a).hosted) continue;
+    const AgentBlock blk = agent_block(a);
+    if (blk.contiguous())
+      DCORA_HIP(hipMemcpyAsync(host_area + (size_t)blk.col0 * r, blk.X, sizeof(double) * (size_t)r * blk.k,
+                               hipMemcpyDeviceToHost, st));
+    else
+      listed = true;
+  }
+  std::vector<double> whole(listed ? (size_t)r * (size_t)num_cols() : 0);
+  if (listed) DCORA_HIP(hipMemcpyAsync(whole.data(), Xg.p, sizeof(double) * whole.size(), hipMemcpyDeviceToHost, st));
+  DCORA_HIP(hipStreamSynchronize(st));
+  for (int a = 0; listed && a < R; ++a) {
+    if (!agent_core(a).hosted) continue;
+    const AgentBlock blk = agent_block(a);
+    for (int j = 0; j < blk.k; ++j) {
+      const size_t c = (size_t)blk.cols_host[j];
+      std::copy(&whole[c * r], &whole[c * r] + r, host_area + c * r);
+    }
+  }
+  return DCORA_OK;
+}
+
 int SessionCore::certify(double eta, CertifyResult *out, double *info8) {
   DeviceProblem *central = opt.world_size == 1 ? central_problem() : nullptr;
   if (!central) {
@@ -45,8 +104,8 @@ int SessionCore::certify(double eta, CertifyResult *out, double *info8) {
   }
   DCORA_HIP(hipSetDevice(opt.device));
   // the mirror is complete: nothing of the session is in flight on an agent's own stream
-  for (int a = 0; a < R; ++a)
-    if (agent_core(a).own_st) DCORA_HIP(hipStreamSynchronize(agent_core(a).own_st));
+  int rc = drain(false);
+  if (rc) return rc;
   // a robust session keeps a host copy of the central pattern and, where it certifies over those alone, of the stored
   // entries the current weights give (session_cert.h; an empty live pattern is none)
   return session_certify(cert_, *central, robust ? &robust->central_pat : nullptr,
@@ -78,14 +137,13 @@ int SessionCore::lift(double theta, const double *v, const dcora_lift_params &p,
   const auto t0 = clock::now();
   DCORA_HIP(hipSetDevice(opt.device));
   // a. nothing of the session is in flight
-  for (int a = 0; a < R; ++a)
-    if (agent_core(a).own_st) DCORA_HIP(hipStreamSynchronize(agent_core(a).own_st));
-  DCORA_HIP(hipStreamSynchronize(st));
+  int rc = drain(true);
+  if (rc) return rc;
   // b. escapeSaddle's PreCondition: of the central Q as the device holds it now (the current weights)
   if (!central->has_precond || central->precond_stale) {
     const auto tb = clock::now();
     HostCsr Qc;
-    int rc = central->Q.download(&Qc);
+    rc = central->Q.download(&Qc);
     if (rc) return rc;
     double reg = p.central_reg;
     if (reg < 0 && (rc = lift_default_reg(Qc, &reg))) return rc;
@@ -94,8 +152,9 @@ int SessionCore::lift(double theta, const double *v, const dcora_lift_params &p,
     if (info8) info8[4] = 1, info8[5] = ms_since(tb);
   }
   // c. the central problem at r + 1, the escape from the mirror; v is all that comes from the host
-  const int r_old = r, r_new = r + 1;
-  int rc = central->rerank(r_new);
+  const int r_new = r + 1;
+  RankChange<DeviceProblem> change(r);  // (what it holds goes back to r on every way out before the commit)
+  rc = change.add(central, r_new);
   if (rc) return rc;
   int ok = 0;
   double stats[4] = {0, 0, 0, 0};
@@ -108,43 +167,20 @@ int SessionCore::lift(double theta, const double *v, const dcora_lift_params &p,
     rc = central->escape_saddle_dev(Xg.p, central->Hd.p, theta, p.gradient_tolerance,
                                     p.preconditioned_gradient_tolerance, p.is_second_order != 0, &ok, stats);
   if (info8) std::copy(stats, stats + 4, info8);
-  // what has been re-ranked goes back to r_old (the error that led here is the one reported)
-  auto undo = [&](int upto) {
-    const std::string keep = dcora_last_error();
-    for (int a = 0; a < upto; ++a)
-      if (agent_core(a).hosted) (void)agent_core(a).prob->rerank(r_old);
-    (void)central->rerank(r_old);
-    set_last_error(keep);
-  };
   if (rc || !ok) {  // d.
-    undo(0);
+    change.rollback();
     if (info8) info8[7] = ms_since(t0);
     return rc;
   }
-  // e. the agents' problems, the kind's buffers and the certificate's r-sized buffer, each built aside
+  // e. the agents' problems, then the session re-dimensioned at the accepted point
   const auto te = clock::now();
   for (int a = 0; a < R; ++a) {
     if (!agent_core(a).hosted) continue;
-    rc = agent_core(a).prob->rerank(r_new);
-    if (rc) {
-      undo(a);
-      return rc;
-    }
+    rc = change.add(agent_core(a).prob.get(), r_new);
+    if (rc) return rc;
   }
-  DevBuf<double> xq;
-  if (cert_.built && hipSuccess != xq.alloc((size_t)r_new * (size_t)k)) {
-    set_last_error(tag + "out of device memory");
-    rc = DCORA_ERR_HIP;
-  }
-  if (!rc) rc = lift_buffers(r_new);
-  if (rc) {
-    undo(R);
-    return rc;
-  }
-  if (cert_.built) cert_.XQ = std::move(xq);
-  rc = lift_adopt(central->X1.p);
+  rc = redimension("lift", r_new, central->X1.p, change);
   if (rc) return rc;
-  DCORA_HIP(hipStreamSynchronize(st));
   *escaped = 1;
   if (info8) info8[6] = ms_since(te), info8[7] = ms_since(t0);
   return DCORA_OK;
@@ -169,11 +205,9 @@ int SessionCore::reserve_rank(int r_reserve) {
 int SessionCore::lift_trial_begin(const double *v_host) {
   const std::string tag = std::string(tag_) + " lift: ";
   DCORA_HIP(hipSetDevice(opt.device));
-  for (int a = 0; a < R; ++a)
-    if (agent_core(a).own_st) DCORA_HIP(hipStreamSynchronize(agent_core(a).own_st));
-  DCORA_HIP(hipStreamSynchronize(st));
-  std::unique_ptr<LiftTrial> t(new LiftTrial);
-  t->r_old = r;
+  int rc = drain(true);
+  if (rc) return rc;
+  std::unique_ptr<LiftTrial> t(new LiftTrial(r));  // (leaving before it is the session's takes its re-ranks back)
   const int r_new = r + 1;
   const size_t k = (size_t)num_cols();
   for (int a = 0; a < R; ++a) {
@@ -194,30 +228,18 @@ int SessionCore::lift_trial_begin(const double *v_host) {
   DCORA_HIP(hipMemsetAsync(t->mirror.p, 0, sizeof(double) * (size_t)r_new * k, st));
   DCORA_HIP(hipMemcpyAsync(t->v.p, v_host, sizeof(double) * k, hipMemcpyHostToDevice, st));
   DCORA_HIP(hipStreamSynchronize(st));  // (the caller's pageable v has been read)
-  lift_trial_ = std::move(t);
   const auto tr = std::chrono::steady_clock::now();
-  for (size_t i = 0; i < lift_trial_->hosted.size(); ++i) {
-    AgentCore &a = agent_core(lift_trial_->hosted[i]);
-    int rc = a.prob->rerank(r_new);
-    if (rc) {
-      // (what has been re-ranked so far goes back; the agents behind never left r)
-      const std::string keep = dcora_last_error();
-      for (size_t q = 0; q < i; ++q) (void)agent_core(lift_trial_->hosted[q]).prob->rerank(r);
-      set_last_error(keep);
-      lift_trial_.reset();
-      return rc;
-    }
+  for (int id : t->hosted) {  // (a failure: what has been re-ranked so far goes back; the agents behind never left r)
+    rc = t->change.add(agent_core(id).prob.get(), r_new);
+    if (rc) return rc;
   }
-  lift_trial_->rerank_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tr).count();
-  for (int id : lift_trial_->hosted) {
-    AgentCore &a = agent_core(id);
-    const double *Xa = nullptr;
-    const int *cols = nullptr;
-    long col0 = 0;
-    lift_agent_view(a, &Xa, &cols, &col0);
-    DeviceProblem &pb = *a.prob;
-    launch_lift_images_agent(st, r, pb.m.k, Xa, lift_trial_->v.p, cols, col0, pb.X0.p, pb.eta.p);
+  t->rerank_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tr).count();
+  for (int id : t->hosted) {
+    const AgentBlock blk = agent_block(id);
+    DeviceProblem &pb = *agent_core(id).prob;
+    launch_lift_images_agent(st, r, pb.m.k, blk.X, t->v.p, blk.cols_dev, blk.col0, pb.X0.p, pb.eta.p);
   }
+  lift_trial_ = std::move(t);
   DCORA_HIP(hipGetLastError());
   return DCORA_OK;
 }
@@ -226,10 +248,9 @@ int SessionCore::lift_trial_point(double alpha, double **mirror) {
   LiftTrial &t = *lift_trial_;
   DCORA_HIP(hipSetDevice(opt.device));
   for (int id : t.hosted) {
-    AgentCore &a = agent_core(id);
-    DeviceProblem &pb = *a.prob;
+    DeviceProblem &pb = *agent_core(id).prob;
     pb.escape_trial_point(alpha);
-    const int rc = lift_scatter_block(a, t.r_old + 1, pb.X1.p, t.mirror.p);
+    const int rc = scatter_block(agent_block(id), t.change.r_old() + 1, pb.X1.p, t.mirror.p);
     if (rc) return rc;
   }
   DCORA_HIP(hipGetLastError());
@@ -240,7 +261,7 @@ int SessionCore::lift_trial_point(double alpha, double **mirror) {
 int SessionCore::lift_trial_scalars(double out3[3]) {
   LiftTrial &t = *lift_trial_;
   DCORA_HIP(hipSetDevice(opt.device));
-  const int r_new = t.r_old + 1;
+  const int r_new = t.change.r_old() + 1;
   for (size_t i = 0; i < t.hosted.size(); ++i) {
     AgentCore &a = agent_core(t.hosted[i]);
     DeviceProblem &pb = *a.prob;
@@ -264,41 +285,27 @@ int SessionCore::lift_trial_scalars(double out3[3]) {
 
 void SessionCore::lift_trial_abort() {
   if (!lift_trial_) return;
-  const std::string keep = dcora_last_error();
   (void)hipSetDevice(opt.device);
-  for (int id : lift_trial_->hosted) (void)agent_core(id).prob->rerank(lift_trial_->r_old);
-  if (lift_trial_->central_reranked) (void)central_problem()->rerank(lift_trial_->r_old);
-  lift_trial_.reset();
-  set_last_error(keep);
+  lift_trial_.reset();  // (its RankChange rolls back)
 }
 
 int SessionCore::lift_trial_commit(double *redim_ms) {
   const auto te = std::chrono::steady_clock::now();
   LiftTrial &t = *lift_trial_;
-  const int r_new = t.r_old + 1;
+  const int r_new = t.change.r_old() + 1;
   DCORA_HIP(hipSetDevice(opt.device));
   int rc = DCORA_OK;
   if (DeviceProblem *central = central_problem()) {  // (a one-rank job keeps its whole-graph evaluation)
-    rc = central->rerank(r_new);
+    rc = t.change.add(central, r_new);
     if (rc) return rc;
-    t.central_reranked = true;
   }
-  DevBuf<double> xq;
-  if (cert_.built && hipSuccess != xq.alloc((size_t)r_new * (size_t)num_cols())) {
-    set_last_error(std::string(tag_) + " lift: out of device memory");
-    return DCORA_ERR_HIP;
-  }
-  rc = lift_buffers(r_new);
+  // (a failure before redimension's commit leaves the re-ranks to lift_trial_abort; after it nothing is left to it)
+  rc = redimension("lift", r_new, t.mirror.p, t.change);
   if (rc) return rc;
-  if (cert_.built) cert_.XQ = std::move(xq);
-  // (the session is at r + 1 from here on: nothing is left for lift_trial_abort to take back)
-  const std::unique_ptr<LiftTrial> done(std::move(lift_trial_));
-  rc = lift_adopt(done->mirror.p);
-  if (rc) return rc;
-  DCORA_HIP(hipStreamSynchronize(st));
   // (what SessionCore::lift counts in the same slot: the agents' re-ranks, made when the trials began, with the rest)
   if (redim_ms)
-    *redim_ms = done->rerank_ms + std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - te).count();
+    *redim_ms = t.rerank_ms + std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - te).count();
+  lift_trial_.reset();
   return DCORA_OK;
 }
 

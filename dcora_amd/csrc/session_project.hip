@@ -237,10 +237,8 @@ int SessionCore::project(double *sigma, double *basis, double *gram, double *cos
   const long k = m.k;
   DCORA_HIP(hipSetDevice(opt.device));
   // a. nothing of the session is in flight
-  for (int a = 0; a < R; ++a)
-    if (agent_core(a).own_st) DCORA_HIP(hipStreamSynchronize(agent_core(a).own_st));
-  DCORA_HIP(hipStreamSynchronize(st));
-  int rc = project_buffers(m);
+  int rc = drain(true);
+  if (!rc) rc = project_buffers(m);
   if (rc) return rc;
   SessionProjectState &ps = project_;
   // b. G in one pass, down to the host; its eigenvectors
@@ -292,52 +290,23 @@ int SessionCore::project(double *sigma, double *basis, double *gram, double *cos
   DCORA_HIP(hipStreamSynchronize(st));
   DCORA_HIP(hipEventElapsedTime(&rest_ms, ps.ev2, ps.ev3));
   if (basis) std::copy(V.begin(), V.begin() + (size_t)r_old * d, basis);
-  // e. the swap: the central problem and every hosted agent's at rank d, the kind's buffers and the certificate's
-  // r-sized buffer, each built aside.  What has been re-ranked goes back to r_old (the error that led here is the one
-  // reported)
+  // e. the swap: the central problem and every hosted agent's at rank d, then the session re-dimensioned at the point.
+  // What has been re-ranked goes back to r_old on every way out before the commit.
   const auto te = clock::now();
-  auto undo = [&](int upto) {
-    const std::string keep = dcora_last_error();
-    for (int a = 0; a < upto; ++a)
-      if (agent_core(a).hosted) (void)agent_core(a).prob->rerank(r_old);
-    (void)central->rerank(r_old);
-    set_last_error(keep);
-  };
-  rc = central->rerank(d);
+  RankChange<DeviceProblem> change(r_old);
+  rc = change.add(central, d);
+  for (int a = 0; a < R && !rc; ++a)
+    if (agent_core(a).hosted) rc = change.add(agent_core(a).prob.get(), d);
   if (rc) return rc;
-  for (int a = 0; a < R; ++a) {
-    if (!agent_core(a).hosted) continue;
-    rc = agent_core(a).prob->rerank(d);
-    if (rc) {
-      undo(a);
-      return rc;
-    }
-  }
   double redim_ms = ms_since(te);
   // 2 f and |rgrad| of the point on the session's current matrices and weights
   if (cost2 || info8) {
     rc = central->eval_dev(ps.point.p, &f, &gn);
-    if (rc) {
-      undo(R);
-      return rc;
-    }
+    if (rc) return rc;
   }
   const auto tf = clock::now();
-  DevBuf<double> xq;
-  if (cert_.built && hipSuccess != xq.alloc((size_t)d * (size_t)k)) {
-    (void)hipGetLastError();
-    set_last_error(tag + "out of device memory");
-    rc = DCORA_ERR_HIP;
-  }
-  if (!rc) rc = lift_buffers(d);
-  if (rc) {
-    undo(R);
-    return rc;
-  }
-  if (cert_.built) cert_.XQ = std::move(xq);
-  rc = lift_adopt(ps.point.p);
+  rc = redimension("project", d, ps.point.p, change);
   if (rc) return rc;
-  DCORA_HIP(hipStreamSynchronize(st));
   redim_ms += ms_since(tf);
   if (cost2) *cost2 = 2.0 * f;
   if (info8) {

@@ -80,8 +80,8 @@ int SessionCore::compute_weights(double *shared_w, std::vector<double> *w, doubl
     return DCORA_ERR_UNSUPPORTED;
   }
   DCORA_HIP(hipSetDevice(opt.device));
-  for (int a = 0; a < R; ++a)
-    if (agent_core(a).own_st) DCORA_HIP(hipStreamSynchronize(agent_core(a).own_st));  // the mirror is complete
+  const int rc = drain(false);  // the mirror is complete
+  if (rc) return rc;
   const size_t m = rs.edge_ids.size();
   w->assign(m, 0.0);
   for (int c = 0; c < 3; ++c) counts[c] = 0;
@@ -110,9 +110,8 @@ int SessionCore::adopt_weights(std::vector<double> &w, bool from_device, bool re
     }
   DCORA_HIP(hipSetDevice(opt.device));
   // nothing of the session is in flight while its matrices and preconditioner images change
-  for (int a = 0; a < R; ++a)
-    if (agent_core(a).own_st) DCORA_HIP(hipStreamSynchronize(agent_core(a).own_st));
-  DCORA_HIP(hipStreamSynchronize(st));
+  const int drained = drain(true);
+  if (drained) return drained;
   if (!rc) rc = robust_rebuild(w);
   if (!rc) rs.w.swap(w);
   const size_t m = rs.edge_ids.size();

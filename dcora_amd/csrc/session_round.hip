@@ -231,8 +231,8 @@ int SessionCore::round(int anchor_pose, const double *anchor, double *trajectory
   const ManiDesc m = global_manifold();
   DCORA_HIP(hipSetDevice(opt.device));
   // the mirror is complete: nothing of the session is in flight on an agent's own stream
-  for (int a = 0; a < R; ++a)
-    if (agent_core(a).own_st) DCORA_HIP(hipStreamSynchronize(agent_core(a).own_st));
+  rc = drain(false);
+  if (rc) return rc;
   rc = round_buffers(m, cost2 != nullptr);
   if (rc) return rc;
   SessionRoundState &rs = round_;
@@ -287,24 +287,23 @@ int SessionCore::round(int anchor_pose, const double *anchor, double *trajectory
 
 // ---- the session's half of the collective rounding (session_core.h) ------------------------------------------------
 int SessionCore::round_fetch_anchor(int anchor_pose, double *out) {
-  const int d = dim();
+  const ManiDesc m = global_manifold();
+  const int d = m.d;
   DCORA_HIP(hipSetDevice(opt.device));
-  RoundAgentMap map;
+  BlockStates states;
   for (int a = 0; a < R; ++a) {
     AgentCore &ac = agent_core(a);
     if (!ac.hosted) continue;
-    round_agent_map(ac, &map);
-    for (int j = 0; j < map.n; ++j) {
-      if (map.pose[(size_t)j] != anchor_pose) continue;
-      if (ac.own_st) DCORA_HIP(hipStreamSynchronize(ac.own_st));
-      const double *Xa = nullptr;
-      const int *cols = nullptr;
-      long col0 = 0;
-      lift_agent_view(ac, &Xa, &cols, &col0);
-      const long rot = map.se ? (long)j * (d + 1) : (long)j * d;
-      const long trans = map.se ? rot + d : (long)d * map.n + map.l + j;
-      DCORA_HIP(hipMemcpyAsync(out, Xa + rot * r, sizeof(double) * (size_t)r * d, hipMemcpyDeviceToHost, st));
-      DCORA_HIP(hipMemcpyAsync(out + (size_t)r * d, Xa + trans * r, sizeof(double) * (size_t)r, hipMemcpyDeviceToHost, st));
+    const AgentBlock blk = agent_block(a);
+    agent_block_states(blk, d, m.n, m.l, &states);
+    for (int j = 0; j < blk.n; ++j) {
+      if (states.pose[(size_t)j] != anchor_pose) continue;
+      if (ac.own_st) DCORA_HIP(hipStreamSynchronize(ac.own_st));  // (the one agent that holds the pose)
+      const long rot = blk.se ? (long)j * (d + 1) : (long)j * d;
+      const long trans = blk.se ? rot + d : (long)d * blk.n + blk.l + j;
+      DCORA_HIP(hipMemcpyAsync(out, blk.X + rot * r, sizeof(double) * (size_t)r * d, hipMemcpyDeviceToHost, st));
+      DCORA_HIP(hipMemcpyAsync(out + (size_t)r * d, blk.X + trans * r, sizeof(double) * (size_t)r, hipMemcpyDeviceToHost,
+                               st));
       DCORA_HIP(hipStreamSynchronize(st));
       return DCORA_OK;
     }
@@ -316,9 +315,8 @@ int SessionCore::round_hosted(const double *anchor, double *traj_area, double *s
   const ManiDesc m = global_manifold();
   const int d = m.d;
   DCORA_HIP(hipSetDevice(opt.device));
-  for (int a = 0; a < R; ++a)
-    if (agent_core(a).own_st) DCORA_HIP(hipStreamSynchronize(agent_core(a).own_st));
-  const int rc = round_buffers(m, false);
+  int rc = drain(false);
+  if (!rc) rc = round_buffers(m, false);
   if (rc) return rc;
   SessionRoundState &rs = round_;
   DCORA_HIP(hipMemcpyAsync(rs.anchor.p, anchor, sizeof(double) * (size_t)m.r * (d + 1), hipMemcpyHostToDevice, st));
@@ -326,25 +324,21 @@ int SessionCore::round_hosted(const double *anchor, double *traj_area, double *s
   an.rot = rs.anchor.p;
   an.trans = rs.anchor.p + (size_t)m.r * d;
   // the hosted agents one behind the other in the outputs (they hold the whole problem's states: room enough)
-  std::vector<RoundAgentMap> maps;
+  std::vector<BlockStates> maps;
   long np = 0, ns = 0, nl = 0;
   for (int a = 0; a < R; ++a) {
-    AgentCore &ac = agent_core(a);
-    if (!ac.hosted) continue;
+    if (!agent_core(a).hosted) continue;
+    const AgentBlock ab = agent_block(a);
     maps.emplace_back();
-    RoundAgentMap &map = maps.back();
-    round_agent_map(ac, &map);
-    const int *cols = nullptr;
-    long col0 = 0;
+    agent_block_states(ab, d, m.n, m.l, &maps.back());
     RoundBlock blk;
-    lift_agent_view(ac, &blk.X, &cols, &col0);
-    blk.n = map.n, blk.l = map.l, blk.b = map.b, blk.se = map.se;
+    blk.X = ab.X, blk.n = ab.n, blk.l = ab.l, blk.b = ab.b, blk.se = ab.se;
     RoundOut out;
     out.traj = rs.traj.p + (size_t)np * d * (d + 1);
     out.spheres = rs.spheres.p + (size_t)ns * d;
     out.landmarks = rs.landmarks.p + (size_t)nl * d;
     launch_round_block(st, m.r, d, blk, an, out);
-    np += map.n, ns += map.l, nl += map.b;
+    np += ab.n, ns += ab.l, nl += ab.b;
   }
   DCORA_HIP(hipGetLastError());
   std::vector<double> ht((size_t)np * d * (d + 1)), hs((size_t)ns * d), hl((size_t)nl * d);
@@ -359,16 +353,13 @@ int SessionCore::round_hosted(const double *anchor, double *traj_area, double *s
   DCORA_HIP(e2);
   np = ns = nl = 0;
   const size_t pose_doubles = (size_t)d * (d + 1);
-  for (const RoundAgentMap &map : maps) {
-    for (int j = 0; j < map.n; ++j, ++np)
-      std::memcpy(traj_area + (size_t)map.pose[(size_t)j] * pose_doubles, &ht[(size_t)np * pose_doubles],
-                  sizeof(double) * pose_doubles);
-    for (int j = 0; j < map.l; ++j, ++ns)
-      if (spheres_area)
-        std::memcpy(spheres_area + (size_t)map.sphere[(size_t)j] * d, &hs[(size_t)ns * d], sizeof(double) * d);
-    for (int j = 0; j < map.b; ++j, ++nl)
-      if (landmarks_area)
-        std::memcpy(landmarks_area + (size_t)map.landmark[(size_t)j] * d, &hl[(size_t)nl * d], sizeof(double) * d);
+  for (const BlockStates &map : maps) {
+    for (int g : map.pose)
+      std::memcpy(traj_area + (size_t)g * pose_doubles, &ht[(size_t)np++ * pose_doubles], sizeof(double) * pose_doubles);
+    for (int g : map.sphere)
+      if (spheres_area) std::memcpy(spheres_area + (size_t)g * d, &hs[(size_t)ns++ * d], sizeof(double) * d);
+    for (int g : map.landmark)
+      if (landmarks_area) std::memcpy(landmarks_area + (size_t)g * d, &hl[(size_t)nl++ * d], sizeof(double) * d);
   }
   return DCORA_OK;
 }
