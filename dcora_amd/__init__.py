@@ -1082,6 +1082,26 @@ class Exchange:
                 "redimension_ms": i8[6], "total_ms": i8[7]}
         return bool(esc.value), info
 
+    def project(self):
+        """The sessions' project() across the ranks of the job (dcora_exchange_project; collective): the job goes from
+        rank r to rank d at Proj(V_d^T X) without leaving the library and keeps what lift keeps.  G = X X^T is the sum
+        of the agents' own X_a X_a^T, formed by the ranks that host them and added in agent order on every rank: the
+        same bits on every rank and for any number of ranks.  -> the dict RbcdSession.project returns (basis None where
+        not projected; positive_dets counts over the job; cost_2f and gradnorm are evaluate() at the adopted point);
+        everything but the three times is identical on every rank.  The session's r follows its rank."""
+        r, d = self.s.r, self.s._round_dims()[0]
+        sg, B, G, i8, c2, rr = np.zeros(r), np.zeros(r * d), np.zeros(r * r), np.zeros(8), C.c_double(), C.c_int()
+        check(capi.lib().dcora_exchange_project(self.h, *(a.ctypes.data_as(C.c_void_p) for a in (sg, B, G)),
+                                                C.byref(c2), i8.ctypes.data_as(C.c_void_p)))
+        rank_fn = capi.lib().dcora_ra_rbcd_rank if isinstance(self.s, RaRbcdSession) else capi.lib().dcora_rbcd_rank
+        check(rank_fn(self.s.h, C.byref(rr)))
+        self.s.r = rr.value
+        projected = bool(i8[0])
+        return dict(projected=projected, reflected=bool(i8[1]), positive_dets=int(i8[2]), sigma=sg,
+                    basis=unF(B, r, d) if projected else None, gram=unF(G, r, r), cost_2f=c2.value,
+                    gradnorm=float(i8[3]), ms_kernels=float(i8[4]), ms_redimension=float(i8[5]), ms_total=float(i8[6]),
+                    gram_chunk=int(i8[7]))
+
     # ---- robust jobs (robust_ranked_session / ra_robust_ranked_session: m is then the pose-pose count) ----
     def update_weights(self, reset_to_initial=False):
         """Agent::updateMeasurementWeights of every agent on every rank (collective); returns the loop closures'

@@ -182,6 +182,10 @@ SIGNATURES = {
     "dcora_rbcd_project": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "dcora_ra_rbcd_project": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "dcora_debug_project_gram": (C.c_int, [C.c_int, C.c_longlong, _dp, _dp, _PI]),
+    "dcora_exchange_project": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "dcora_debug_project_gram_blocks": (C.c_int, [C.c_int, C.c_int, _vp, _dp, _dp, _PI]),
+    "dcora_debug_exchange_project_sums": (C.c_int, [C.c_int]),
+    "dcora_debug_project_gram_time": (C.c_int, [C.c_int, C.c_int, _vp, C.c_int, _dp, _dp]),
     "dcora_debug_lift_images": (C.c_int, [C.c_int, C.c_int, _dp, C.c_int, _dp, _vp, C.c_int, _dp, _dp]),
     "dcora_ra_rbcd_rank": (C.c_int, [_vp, _PI]),
     "dcora_rbcd_profile_tcg_runs": (C.c_int, [_vp, C.c_int]),

@@ -1530,6 +1530,97 @@ int dcora_debug_project_gram(int r, long long k, const double *X, double *gram, 
     return (int)DCORA_OK;
   });
 }
+// k_gram_blocks_mfma / k_gram_blocks_finish on host arrays (tests/test_project_ranks_gpu.py)
+int dcora_debug_project_gram_blocks(int r, int nblocks, const long long *k, const double *X, double *grams,
+                                    int *chunk) {
+  return abi_call({k, X, grams}, [&]() -> int {
+    if (r < 1 || r > kMaxRank || nblocks < 1)
+      return bad("dcora_debug_project_gram_blocks: 1 <= r <= 16, nblocks >= 1, every k >= 0");
+    for (int b = 0; b < nblocks; ++b)
+      if (k[b] < 0) return bad("dcora_debug_project_gram_blocks: 1 <= r <= 16, nblocks >= 1, every k >= 0");
+    if (chunk) *chunk = kGramCols;
+    size_t cols = 0;
+    long nwg = 0;
+    for (int b = 0; b < nblocks; ++b) cols += (size_t)k[b], nwg += gram_workgroups_of((long)k[b]);
+    DevBuf<double> Xd, P, G;
+    DevBuf<GramBlock> T;
+    const size_t np = 256 * (size_t)std::max<long>(nwg, 1), ng = (size_t)nblocks * r * r;
+    DCORA_HIP(Xd.alloc((size_t)r * std::max<size_t>(cols, 1)));
+    DCORA_HIP(P.alloc(np));
+    DCORA_HIP(G.alloc(ng));
+    DCORA_HIP(T.alloc((size_t)nblocks + 1));
+    std::vector<GramBlock> table;
+    size_t c0 = 0;
+    long w0 = 0;
+    for (int b = 0; b < nblocks; ++b) {
+      table.push_back(GramBlock{Xd.p + (size_t)r * c0, (long)k[b], w0});
+      c0 += (size_t)k[b], w0 += gram_workgroups_of((long)k[b]);
+    }
+    table.push_back(GramBlock{nullptr, 0, w0});
+    if (cols) DCORA_HIP(hipMemcpy(Xd.p, X, sizeof(double) * (size_t)r * cols, hipMemcpyHostToDevice));
+    DCORA_HIP(hipMemcpy(T.p, table.data(), sizeof(GramBlock) * table.size(), hipMemcpyHostToDevice));
+    // (NaN where the kernels must write: an element they skip shows)
+    DCORA_HIP(hipMemset(P.p, 0xff, sizeof(double) * np));
+    DCORA_HIP(hipMemset(G.p, 0xff, sizeof(double) * ng));
+    launch_gram_blocks(nullptr, r, nblocks, nwg, T.p, P.p, G.p);
+    DCORA_HIP(hipGetLastError());
+    DCORA_HIP(hipDeviceSynchronize());
+    DCORA_HIP(hipMemcpy(grams, G.p, sizeof(double) * ng, hipMemcpyDeviceToHost));
+    return (int)DCORA_OK;
+  });
+}
+// the block-list pair against a loop of launch_gram over the same blocks, alternated, in event time
+// (tools/project_ranks_cost.py)
+int dcora_debug_project_gram_time(int r, int nblocks, const long long *k, int reps, double *loop_us, double *pair_us) {
+  return abi_call({k, loop_us, pair_us}, [&]() -> int {
+    if (r < 1 || r > kMaxRank || nblocks < 1 || reps < 1)
+      return bad("dcora_debug_project_gram_time: 1 <= r <= 16, nblocks >= 1, reps >= 1, every k >= 1");
+    size_t cols = 0;
+    long nwg = 0;
+    for (int b = 0; b < nblocks; ++b) {
+      if (k[b] < 1) return bad("dcora_debug_project_gram_time: 1 <= r <= 16, nblocks >= 1, reps >= 1, every k >= 1");
+      cols += (size_t)k[b], nwg += gram_workgroups_of((long)k[b]);
+    }
+    DevBuf<double> Xd, P, G;
+    DevBuf<GramBlock> T;
+    DCORA_HIP(Xd.alloc((size_t)r * cols));
+    DCORA_HIP(P.alloc(256 * (size_t)nwg));
+    DCORA_HIP(G.alloc((size_t)nblocks * r * r));
+    DCORA_HIP(T.alloc((size_t)nblocks + 1));
+    std::vector<GramBlock> table;
+    size_t c0 = 0;
+    long w0 = 0;
+    for (int b = 0; b < nblocks; ++b) {
+      table.push_back(GramBlock{Xd.p + (size_t)r * c0, (long)k[b], w0});
+      c0 += (size_t)k[b], w0 += gram_workgroups_of((long)k[b]);
+    }
+    table.push_back(GramBlock{nullptr, 0, w0});
+    DCORA_HIP(hipMemset(Xd.p, 0, sizeof(double) * (size_t)r * cols));
+    DCORA_HIP(hipMemcpy(T.p, table.data(), sizeof(GramBlock) * table.size(), hipMemcpyHostToDevice));
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    DCORA_HIP(hipEventCreate(&e0));
+    DCORA_HIP(hipEventCreate(&e1));
+    for (int i = 0; i < 2 * reps + 2; ++i) {  // (the first of each form warms up and is not kept)
+      const bool pair = i & 1;
+      DCORA_HIP(hipEventRecord(e0, nullptr));
+      if (pair)
+        launch_gram_blocks(nullptr, r, nblocks, nwg, T.p, P.p, G.p);
+      else
+        for (int b = 0; b < nblocks; ++b)
+          launch_gram(nullptr, r, table[(size_t)b].k, table[(size_t)b].X, P.p + 256 * table[(size_t)b].wg0,
+                      G.p + (size_t)b * r * r);
+      DCORA_HIP(hipEventRecord(e1, nullptr));
+      DCORA_HIP(hipEventSynchronize(e1));
+      float ms = 0;
+      DCORA_HIP(hipEventElapsedTime(&ms, e0, e1));
+      if (i >= 2) (pair ? pair_us : loop_us)[(i - 2) / 2] = 1e3 * ms;
+    }
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    DCORA_HIP(hipGetLastError());
+    return (int)DCORA_OK;
+  });
+}
 // (ref examples/MultiRobotExample.cpp:352-366, examples/MultiRobotExample_RASLAM.cpp, src/QuadraticProblem.cpp:138-234)
 int dcora_rbcd_rank(dcora_rbcd_t s, int *r) {
   return abi_call({s, r}, [&] {
@@ -1740,6 +1831,16 @@ int dcora_exchange_round(dcora_exchange_t ex, int anchor_pose, const double *anc
 int dcora_exchange_lift(dcora_exchange_t ex, double theta, const double *v, const dcora_lift_params *params,
                         int *escaped, double *info8) {
   return abi_call({ex, params, escaped}, [&] { return ex->e.lift(theta, v, *params, escaped, info8); });
+}
+// the certified flow's last step of the whole job (ref examples/SingleRobotExample_RASLAM.cpp:220-234,
+// projectSolutionRASLAM src/DCORA_utils.cpp:1984-2031): Exchange::project on either session kind
+int dcora_exchange_project(dcora_exchange_t ex, double *sigma, double *basis, double *gram, double *cost2,
+                           double *info8) {
+  return abi_call({ex}, [&] { return ex->e.project(sigma, basis, gram, cost2, info8); });
+}
+int dcora_debug_exchange_project_sums(int on) {
+  g_project_gram_sums.store(on ? 1 : 0);
+  return DCORA_OK;
 }
 int dcora_exchange_host_selftest(const char *job_name, int rank, int world_size, int num_agents, int rounds,
                                  double *checksum) {

@@ -29,6 +29,9 @@ enum ExchangeMode { kExchangeIpc = 1, kExchangeStaged = 2 };
 // (DCORA_EXCHANGE_TIMEOUT_S, default 120: a rank that died takes the job down within this time, never a hang)
 double exchange_timeout_s();
 extern std::atomic<int> g_probe_fault_rounds;  // test hook of the link check (dcora_debug_exchange_probe_fault)
+// test / measurement hook of Exchange::project (dcora_debug_exchange_project_sums): the per-agent Gram matrices travel
+// through allreduce_sum pieces instead of the X area
+extern std::atomic<int> g_project_gram_sums;
 
 // What certify_live keeps between certificates: the job-wide pattern of S + eta I and, per hosted agent, the table of
 // its rows (cert_rows.h) on the device.  Built by the first call; valid for the life of the job.
@@ -140,6 +143,28 @@ class Exchange {
   // Refused before any collective step, alike on every rank (DCORA_ERR_BAD_ARG): trajectory null, anchor_pose outside
   // 0 .. n - 1, a non-finite anchor.
   int round(int anchor_pose, const double *anchor, double *trajectory, double *unit_spheres, double *landmarks);
+  // How CORA ends a certified solve, across the ranks (SessionCore::project's contract carried over the job; ref
+  // examples/SingleRobotExample_RASLAM.cpp:220-234, projectSolutionRASLAM src/DCORA_utils.cpp:1984-2031).  SPMD.
+  //   a. every rank drains its session;
+  //   b. G = X X^T = sum_a G_a: every rank forms G_a of the agents it hosts from their own blocks in one launch pair
+  //      (launch_gram_blocks); the matrices reach every rank per agent and unchanged (project_sum_grams) and every rank
+  //      adds them in agent order 0 .. R - 1.  A rank never sums its own agents first: G has the same bits on every
+  //      rank, for any number of ranks, either transport and a one-rank exchange.  (Not the single-process session's G
+  //      bit for bit unless R = 1: that one sums workgroups over the whole mirror's columns.)
+  //   c. the r x r eigenproblem on every rank's host: the same input, the same code, the same V_d; no broadcast;
+  //   d. r == d: X passes through; sigma and gram are produced, cost2 and |rgrad| are evaluate()'s, the job is untouched;
+  //   e. poses with det(V_d^T Y_i) > 0 over the hosted blocks, summed as doubles (allreduce_sum: integers, exact); the
+  //      reflection rule on the JOB's n, the same branch everywhere;
+  //   f. the hosted blocks projected into a zeroed trial mirror of d rows, everybody's public columns at d rows through
+  //      post_arr / wait_arr of all agents, as lift's trial points travel;
+  //   g. between barriers, as lift commits: every hosted problem (and a one-rank job's central one) re-ranked to d, the
+  //      session re-dimensioned at the trial mirror.  What lift keeps is kept -- r_cap_ too: a projected job can lift
+  //      again up to its old capacity; certify_live's tables stay valid;
+  //   h. cost2 and info8[3]: evaluate() at the adopted point, what a following evaluate returns bit for bit.
+  // An error on any rank before the commit: nothing of its session was written, `failed` is raised for the ranks that
+  // wait.  Outputs as SessionCore::project, every one may be null and every one but the three times of info8 has the
+  // same bits on every rank; info8[2] counts over the job.
+  int project(double *sigma, double *basis, double *gram, double *cost2, double *info8);
   int rank_capacity() const { return r_cap_; }  // the largest rank the job's segment and halo slots hold
   int barrier(double timeout_s = 120.0);
   int gather_X(double *Xh);
@@ -221,6 +246,9 @@ class Exchange {
   int certify_live_run(double eta, int *certified, double *theta, double *lambda_min, double *v, long long *matvecs,
                        int *distributed, double *info10);  // certify_live behind its refusals
   LiveCertState live_;
+  // project's step b (exchange_project.hip): mine = the hosted agents' r x r matrices in agent order -> *G, their sum
+  // over all agents in agent order
+  int project_sum_grams(const std::vector<int> &hosted, const std::vector<double> &mine, int r, std::vector<double> *G);
   int fail(const std::string &msg, int code);   // a transport / peer failure: raises `failed` for every rank
   int usage(const std::string &msg, int code);  // a refused call (bad argument, unsupported): this call only
 };

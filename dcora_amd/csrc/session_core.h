@@ -208,8 +208,27 @@ class SessionCore {
   // central_problem()->eval_dev (the session's current matrices and weights); info8: projected, reflected, rotation
   // blocks with positive determinant before the reflection, |rgrad| at the adopted point, ms of the projection
   // kernels, ms of the re-dimensioning, ms total, columns per workgroup of the Gram kernel.  Refused, the session
-  // untouched, as lift (DCORA_ERR_UNSUPPORTED): the projection across the ranks of a job does not exist yet.
+  // untouched, as lift (DCORA_ERR_UNSUPPORTED): the ranks of a job project together, through Exchange::project.
   int project(double *sigma, double *basis, double *gram, double *cost2, double *info8);
+  // ---- the session's half of the collective projection (Exchange::project, where the flow stands).  A rank's mirror
+  // is current only in its hosted agents' columns and the neighbours' public ones, so every step works on the hosted
+  // agents' own blocks (agent_block).  The session itself is not touched before project_trial_commit.
+  //   grams:  every stream synchronised; G_a = X_a X_a^T of every hosted agent in one launch pair (launch_gram_blocks);
+  //           *hosted: the agents in agent order, *grams: their r x r matrices one after another (host); synchronises
+  //   dets:   *npos = the hosted poses with det(basis^T Y_i) > 0 (basis: r x d, host); synchronises
+  //   point:  Proj(basis^T X_a) of every hosted block into the trial mirror of d rows, zero elsewhere; *mirror: what the
+  //           exchange posts from and waits into; synchronises
+  //   commit: every hosted agent's problem, and the central one of a one-rank job, re-ranked to d and the session
+  //           re-dimensioned (redimension) at the trial mirror; *redim_ms: what that took
+  //   abort:  the trial dropped; a commit that failed before redimension's point of no return has its re-ranks taken
+  //           back (the error that led here stays the one reported)
+  //   ms:     event time of the trial's kernels so far
+  int project_trial_grams(std::vector<int> *hosted, std::vector<double> *grams);
+  int project_trial_dets(const double *basis, double *npos);
+  int project_trial_point(const double *basis, double **mirror);
+  int project_trial_commit(double *redim_ms);
+  void project_trial_abort();
+  double project_trial_ms() const { return project_trial_ ? project_trial_->kernel_ms : 0.0; }
 
   // ---- room for the ranks to come: an exchange created on this session sizes its halo slots, its staged slots and its
   // gather_X area by max(r, reserve_r), so that the job can lift up to that rank (Exchange::lift).  0: a job that will
@@ -341,6 +360,14 @@ class SessionCore {
     RankChange<DeviceProblem> change;  // (the last member: the re-ranks go back before the buffers go)
   };
   std::unique_ptr<LiftTrial> lift_trial_;  // between lift_trial_begin and commit / abort
+  struct ProjectTrial {
+    explicit ProjectTrial(int r_old) : change(r_old) {}
+    double kernel_ms = 0;
+    DevBuf<double> mirror;    // d x num_cols()
+    std::vector<int> hosted;  // in agent order
+    RankChange<DeviceProblem> change;  // (the last member, as in LiftTrial)
+  };
+  std::unique_ptr<ProjectTrial> project_trial_;  // between project_trial_grams and commit / abort
 
   // robust sessions, for the kinds' init_robust.  robust_check_args: what both kinds refuse.  robust_begin: the state,
   // with weight 1 on every loop closure (lc: one flag per measurement) that is not fixed (fixed: one flag per

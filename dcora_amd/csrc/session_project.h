@@ -29,6 +29,20 @@ inline long gram_workgroups(long k) { return k > 0 ? (k + kGramCols - 1) / kGram
 // doubles.  Enqueued on st; nothing synchronises.
 void launch_gram(hipStream_t st, int r, long k, const double *X, double *partials, double *G);
 
+// The same for a list of blocks in ONE launch pair (what a rank of a job needs: one matrix per hosted agent, see
+// Exchange::project).  table (device): nblocks + 1 entries, entry b = {X of block b (r x k column-major), k >= 0, the
+// sum of gram_workgroups_of(k) over the blocks before it}, the last entry's wg0 the total nwg.  partials: 256 nwg
+// doubles; grams: nblocks x r x r.  Chunks are counted from each block's first column and every block has a finishing
+// workgroup of its own, so grams[b] is bit for bit what launch_gram gives on block b alone -- wherever the block
+// stands in the list and whatever stands beside it.  A block with k = 0 owns no workgroup and yields zeros.
+struct GramBlock {
+  const double *X;
+  long k, wg0;
+};
+inline long gram_workgroups_of(long k) { return (k + kGramCols - 1) / kGramCols; }
+void launch_gram_blocks(hipStream_t st, int r, int nblocks, long nwg, const GramBlock *table, double *partials,
+                        double *grams);
+
 // *count += the number of poses of blk with det(basis^T Y_i) > 0; basis: r x d column-major, device
 void launch_project_dets(hipStream_t st, int r, int d, const RoundBlock &blk, const double *basis, int *count);
 
@@ -40,6 +54,9 @@ struct SessionProjectState {
   DevBuf<double> partials, gram, basis, point;
   DevBuf<int> count;
   size_t partials_cap = 0, point_cap = 0;
+  DevBuf<double> grams;    // the collective form: one r x r matrix per hosted agent ...
+  DevBuf<GramBlock> table;  // ... and the block list of their launch pair
+  size_t grams_cap = 0, table_cap = 0;
   hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;  // around the Gram kernels / the rest
   SessionProjectState() = default;
   SessionProjectState(const SessionProjectState &) = delete;

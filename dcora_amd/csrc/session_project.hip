@@ -30,11 +30,11 @@ static_assert(kGramCols % (4 * kGramWaves) == 0 && kGramSteps % kGramUnroll == 0
 // step's X X^T to the wave's 16 x 16 accumulator: lane l holds D((l >> 4) + 4 v, l & 15) in register v.  The waves'
 // accumulators meet in LDS and are added in wave order; partials[256 w + i + 16 j] is the workgroup's share of G(i, j).
 // Loads of a group of kGramUnroll steps are issued before its first product.
-__global__ __launch_bounds__(kBlock) void k_gram_mfma(int r, long k, const double *__restrict__ X,
-                                                      double *__restrict__ partials) {
-  __shared__ double sm[kGramWaves][256];
+template <class Ptr, class Sm>
+__device__ __forceinline__ void gram_chunk(int r, long k, Ptr X, long chunk, Sm &sm,
+                                           double *__restrict__ out) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, lo = lane & 15, hi = lane >> 4;
-  const long c_begin = (long)blockIdx.x * kGramCols + (long)wave * kGramWaveCols;
+  const long c_begin = chunk * kGramCols + (long)wave * kGramWaveCols;
   const bool row = lo < r;
   gram_v4f64 acc = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll 1
@@ -55,19 +55,61 @@ __global__ __launch_bounds__(kBlock) void k_gram_mfma(int r, long k, const doubl
   double t = sm[0][threadIdx.x];
 #pragma unroll
   for (int w = 1; w < kGramWaves; ++w) t += sm[w][threadIdx.x];
-  partials[(long)blockIdx.x * 256 + threadIdx.x] = t;
+  out[threadIdx.x] = t;
 }
 
-// G(a, b) = the partials of (min(a, b), max(a, b)) added in workgroup order: one workgroup, one thread per entry, so
-// G(a, b) and G(b, a) are the same sum and G is symmetric bit for bit
-__global__ __launch_bounds__(256) void k_gram_finish(int r, long nwg, const double *__restrict__ partials,
-                                                     double *__restrict__ G) {
+// G(a, b) = the partials of (min(a, b), max(a, b)) added in chunk order by ONE thread, so G(a, b) and G(b, a) are the
+// same sum and G is symmetric bit for bit
+__device__ __forceinline__ void gram_finish_sum(int r, long nwg, const double *__restrict__ partials,
+                                                double *__restrict__ G) {
   const int a = threadIdx.x & 15, b = threadIdx.x >> 4;
   if (a >= r || b >= r) return;
   const int e = (a < b ? a : b) + 16 * (a < b ? b : a);
   double t = 0.0;
   for (long w = 0; w < nwg; ++w) t += partials[w * 256 + e];
   G[a + r * b] = t;
+}
+
+__global__ __launch_bounds__(kBlock) void k_gram_mfma(int r, long k, const double *__restrict__ X,
+                                                      double *__restrict__ partials) {
+  __shared__ double sm[kGramWaves][256];
+  gram_chunk(r, k, X, (long)blockIdx.x, sm, partials + (long)blockIdx.x * 256);
+}
+
+// one workgroup, one thread per entry
+__global__ __launch_bounds__(256) void k_gram_finish(int r, long nwg, const double *__restrict__ partials,
+                                                     double *__restrict__ G) {
+  gram_finish_sum(r, nwg, partials, G);
+}
+
+// The block-list form: table[b] = {X, k, first workgroup} of block b, table[nblocks].wg0 the number of workgroups.
+// Workgroup w belongs to the block b with table[b].wg0 <= w < table[b + 1].wg0 (a block of no columns owns none) and
+// takes that block's chunk w - table[b].wg0: kGramCols columns counted from the BLOCK's first column, through
+// gram_chunk, so partials[256 w ...] holds what k_gram_mfma of the block alone writes for that chunk, bit for bit.
+__global__ __launch_bounds__(kBlock) void k_gram_blocks_mfma(int r, int nblocks, const GramBlock *__restrict__ table,
+                                                             double *__restrict__ partials) {
+  __shared__ double sm[kGramWaves][256];
+  const long w = blockIdx.x;
+  int lo = 0, hi = nblocks;  // (uniform: the search runs on the scalar unit)
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (table[mid].wg0 <= w)
+      lo = mid;
+    else
+      hi = mid;
+  }
+  const GramBlock blk = table[lo];
+  // (a pointer read from memory: said to be global, so that the loads are global loads as in k_gram_mfma, not flat ones)
+  typedef const __attribute__((address_space(1))) double *GlobalPtr;
+  gram_chunk(r, blk.k, (GlobalPtr)blk.X, w - blk.wg0, sm, partials + w * 256);
+}
+
+// one workgroup PER BLOCK: its partials in chunk order by k_gram_finish's rule; the blocks' sums run side by side
+__global__ __launch_bounds__(256) void k_gram_blocks_finish(int r, const GramBlock *__restrict__ table,
+                                                            const double *__restrict__ partials,
+                                                            double *__restrict__ grams) {
+  const long w0 = table[blockIdx.x].wg0, w1 = table[blockIdx.x + 1].wg0;
+  gram_finish_sum(r, w1 - w0, partials + w0 * 256, grams + (size_t)blockIdx.x * r * r);
 }
 
 // the frame into LDS: sm[a r + q] = V_d(q, a).  Every workgroup reads the same r D words.
@@ -184,6 +226,14 @@ void launch_gram(hipStream_t st, int r, long k, const double *X, double *partial
   hipLaunchKernelGGL(k_gram_finish, dim3(1), dim3(256), 0, st, r, nwg, partials, G);
 }
 
+void launch_gram_blocks(hipStream_t st, int r, int nblocks, long nwg, const GramBlock *table, double *partials,
+                        double *grams) {
+  if (nblocks <= 0) return;
+  if (nwg > 0)
+    hipLaunchKernelGGL(k_gram_blocks_mfma, dim3((unsigned)nwg), dim3(kBlock), 0, st, r, nblocks, table, partials);
+  hipLaunchKernelGGL(k_gram_blocks_finish, dim3((unsigned)nblocks), dim3(256), 0, st, r, table, partials, grams);
+}
+
 void launch_project_dets(hipStream_t st, int r, int d, const RoundBlock &blk, const double *basis, int *count) {
   if (d == 3)
     launch_project_dets_d<3>(st, r, blk, basis, count);
@@ -227,8 +277,8 @@ int SessionCore::project(double *sigma, double *basis, double *gram, double *cos
   }
   DeviceProblem *central = opt.world_size == 1 ? central_problem() : nullptr;
   if (!central || weights_ranked() || (team && team->ranked) || exchange_attached) {
-    set_last_error(tag + "serves single-process sessions without an exchange; the projection across the ranks of a "
-                   "job (dcora_exchange_project) does not exist yet");
+    set_last_error(tag + "serves single-process sessions without an exchange; the ranks of a job, and a session an "
+                   "exchange was created on, project together through dcora_exchange_project");
     return DCORA_ERR_UNSUPPORTED;
   }
   const auto t_begin = clock::now();
@@ -314,6 +364,143 @@ int SessionCore::project(double *sigma, double *basis, double *gram, double *cos
     info8[4] = (double)gram_ms + (double)rest_ms, info8[5] = redim_ms, info8[6] = ms_since(t_begin);
   }
   return DCORA_OK;
+}
+
+// ---- the session's half of the collective projection (session_core.h) ------------------------------------------------
+namespace {
+RoundBlock round_block_of(const AgentBlock &ab) {
+  RoundBlock blk;
+  blk.X = ab.X, blk.n = ab.n, blk.l = ab.l, blk.b = ab.b, blk.se = ab.se;
+  return blk;
+}
+}  // namespace
+
+int SessionCore::project_trial_grams(std::vector<int> *hosted, std::vector<double> *grams) {
+  const std::string tag = std::string(tag_) + " project: ";
+  DCORA_HIP(hipSetDevice(opt.device));
+  const ManiDesc m = global_manifold();
+  int rc = drain(true);
+  if (!rc) rc = project_buffers(m);
+  if (rc) return rc;
+  std::unique_ptr<ProjectTrial> t(new ProjectTrial(r));
+  std::vector<GramBlock> table;
+  long nwg = 0;
+  for (int a = 0; a < R; ++a) {
+    if (!agent_core(a).hosted) continue;
+    const AgentBlock ab = agent_block(a);
+    t->hosted.push_back(a);
+    table.push_back(GramBlock{ab.X, (long)ab.k, nwg});
+    nwg += gram_workgroups_of(ab.k);
+  }
+  const size_t nh = t->hosted.size();
+  table.push_back(GramBlock{nullptr, 0, nwg});
+  SessionProjectState &ps = project_;
+  const size_t np = 256 * (size_t)std::max<long>(nwg, 1), ng = 256 * std::max<size_t>(nh, 1);
+  if (ps.partials_cap < np) {
+    DCORA_HIP(ps.partials.alloc(np));
+    ps.partials_cap = np;
+  }
+  if (ps.grams_cap < ng) {
+    DCORA_HIP(ps.grams.alloc(ng));
+    ps.grams_cap = ng;
+  }
+  if (ps.table_cap < table.size()) {
+    DCORA_HIP(ps.table.alloc(table.size()));
+    ps.table_cap = table.size();
+  }
+  const size_t rr = (size_t)r * r;
+  grams->assign(nh * rr, 0.0);
+  DCORA_HIP(hipMemcpyAsync(ps.table.p, table.data(), sizeof(GramBlock) * table.size(), hipMemcpyHostToDevice, st));
+  DCORA_HIP(hipEventRecord(ps.ev0, st));
+  launch_gram_blocks(st, r, (int)nh, nwg, ps.table.p, ps.partials.p, ps.grams.p);
+  DCORA_HIP(hipGetLastError());
+  DCORA_HIP(hipEventRecord(ps.ev1, st));
+  if (nh) DCORA_HIP(hipMemcpyAsync(grams->data(), ps.grams.p, sizeof(double) * nh * rr, hipMemcpyDeviceToHost, st));
+  DCORA_HIP(hipStreamSynchronize(st));
+  float ms = 0;
+  DCORA_HIP(hipEventElapsedTime(&ms, ps.ev0, ps.ev1));
+  t->kernel_ms = ms;
+  *hosted = t->hosted;
+  project_trial_ = std::move(t);
+  return DCORA_OK;
+}
+
+int SessionCore::project_trial_dets(const double *basis, double *npos) {
+  ProjectTrial &t = *project_trial_;
+  SessionProjectState &ps = project_;
+  DCORA_HIP(hipSetDevice(opt.device));
+  const int d = dim();
+  int count = 0;
+  DCORA_HIP(hipEventRecord(ps.ev2, st));
+  DCORA_HIP(hipMemcpyAsync(ps.basis.p, basis, sizeof(double) * (size_t)r * d, hipMemcpyHostToDevice, st));
+  DCORA_HIP(hipMemsetAsync(ps.count.p, 0, sizeof(int), st));
+  for (int id : t.hosted) launch_project_dets(st, r, d, round_block_of(agent_block(id)), ps.basis.p, ps.count.p);
+  DCORA_HIP(hipGetLastError());
+  DCORA_HIP(hipEventRecord(ps.ev3, st));
+  DCORA_HIP(hipMemcpyAsync(&count, ps.count.p, sizeof(int), hipMemcpyDeviceToHost, st));
+  DCORA_HIP(hipStreamSynchronize(st));
+  float ms = 0;
+  DCORA_HIP(hipEventElapsedTime(&ms, ps.ev2, ps.ev3));
+  t.kernel_ms += ms;
+  *npos = (double)count;
+  return DCORA_OK;
+}
+
+int SessionCore::project_trial_point(const double *basis, double **mirror) {
+  ProjectTrial &t = *project_trial_;
+  SessionProjectState &ps = project_;
+  DCORA_HIP(hipSetDevice(opt.device));
+  const int d = dim();
+  const size_t k = (size_t)num_cols();
+  if (hipSuccess != t.mirror.alloc((size_t)d * k)) {
+    (void)hipGetLastError();
+    set_last_error(std::string(tag_) + " project: out of device memory");
+    return DCORA_ERR_HIP;
+  }
+  // (columns no hosted agent owns and no neighbour publishes are read by nobody: zero, as a fresh mirror has them)
+  DCORA_HIP(hipMemsetAsync(t.mirror.p, 0, sizeof(double) * (size_t)d * k, st));
+  DCORA_HIP(hipEventRecord(ps.ev2, st));
+  DCORA_HIP(hipMemcpyAsync(ps.basis.p, basis, sizeof(double) * (size_t)r * d, hipMemcpyHostToDevice, st));
+  size_t off = 0;  // the hosted blocks one behind the other in the point buffer (d x num_cols(): room enough)
+  for (int id : t.hosted) {
+    const AgentBlock ab = agent_block(id);
+    launch_project_block(st, r, d, round_block_of(ab), ps.basis.p, ps.point.p + off);
+    const int rc = scatter_block(ab, d, ps.point.p + off, t.mirror.p);
+    if (rc) return rc;
+    off += (size_t)d * ab.k;
+  }
+  DCORA_HIP(hipGetLastError());
+  DCORA_HIP(hipEventRecord(ps.ev3, st));
+  DCORA_HIP(hipStreamSynchronize(st));
+  float ms = 0;
+  DCORA_HIP(hipEventElapsedTime(&ms, ps.ev2, ps.ev3));
+  t.kernel_ms += ms;
+  *mirror = t.mirror.p;
+  return DCORA_OK;
+}
+
+int SessionCore::project_trial_commit(double *redim_ms) {
+  const auto te = std::chrono::steady_clock::now();
+  ProjectTrial &t = *project_trial_;
+  const int d = dim();
+  DCORA_HIP(hipSetDevice(opt.device));
+  int rc = DCORA_OK;
+  for (int id : t.hosted)
+    if ((rc = t.change.add(agent_core(id).prob.get(), d))) return rc;
+  if (DeviceProblem *central = central_problem())  // (a one-rank job keeps its whole-graph evaluation)
+    if ((rc = t.change.add(central, d))) return rc;
+  // (a failure before redimension's commit leaves the re-ranks to project_trial_abort; after it nothing is left to it)
+  rc = redimension("project", d, t.mirror.p, t.change);
+  if (rc) return rc;
+  if (redim_ms) *redim_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - te).count();
+  project_trial_.reset();
+  return DCORA_OK;
+}
+
+void SessionCore::project_trial_abort() {
+  if (!project_trial_) return;
+  (void)hipSetDevice(opt.device);
+  project_trial_.reset();  // (its RankChange rolls back)
 }
 
 }  // namespace dcora

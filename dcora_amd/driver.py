@@ -537,6 +537,12 @@ class _RanksJob:
     def round(self, cost=False):
         return self.ex.round()  # (no rounded cost across ranks: no rank holds the whole problem)
 
+    def project(self):
+        return self.ex.project()
+
+    def evaluate(self):
+        return self.ex.evaluate()
+
     def close(self):
         # (reached from a `finally`: after an error of the exchange the barrier raises as well -- the exchange and the
         # session are closed all the same, and the first error stays the one the caller sees)
@@ -563,7 +569,25 @@ def multi_robot_staircase_ranks(ds, X0, num_robots=5, r_min=5, r_max=100, max_it
     built on the host and ds is not written.
     round_on_device: Exchange.round ends the solve -- every rank rounds its own agents' states against pose 0 and every
     rank's result carries the whole trajectory (rounded_cost_2f and rounded_gradnorm are None: no rank holds the whole
-    problem)."""
+    problem).  multi_robot_staircase_ranks_projected ends a certified solve with the projection to rank d as well."""
+    return _multi_robot_staircase_ranks(False, **locals())
+
+
+def multi_robot_staircase_ranks_projected(ds, X0, round_on_device=True, **kw):
+    """multi_robot_staircase_ranks (its arguments, SPMD) ended as CORA ends a certified solve (ref
+    examples/SingleRobotExample_RASLAM.cpp:220-234), what project_on_device=True is to multi_robot_staircase_session:
+    after a certified level Exchange.project takes the whole job to rank d in place, the level's own run parameters
+    refine it there and (round_on_device) Exchange.round rounds the refined point.  Every key of
+    multi_robot_staircase_ranks is what it is there; the result also carries sigma, projected_cost_2f,
+    refined_cost_2f and refine_iters (None where no level was certified), the same on every rank."""
+    return _multi_robot_staircase_ranks(True, ds=ds, X0=X0, round_on_device=round_on_device, **kw)
+
+
+def _multi_robot_staircase_ranks(project_on_device, ds, X0, num_robots=5, r_min=5, r_max=100, max_iters=1000,
+                                 rgrad_tol=0.1, min_eig_tol=1e-3, gradient_tolerance=1e-6,
+                                 preconditioned_gradient_tolerance=1e-6, acceleration=True, params=None, device=0,
+                                 mode="rbcd++", robust=None, fixed=None, rank=0, world_size=1, job_name="staircase",
+                                 certificate="host", round_on_device=False):
     from . import Exchange, robust_ranked_session
     _check_mode(mode)
     live = _check_certificate(certificate)
@@ -590,7 +614,7 @@ def multi_robot_staircase_ranks(ds, X0, num_robots=5, r_min=5, r_max=100, max_it
         _RanksJob(s, ex, (d + 1) * n, rank, q_now, certificate), X0, (d + 1) * n, r_min, r_top, max_iters, rgrad_tol, min_eig_tol,
         gradient_tolerance, preconditioned_gradient_tolerance, mode, ts,
         gap=lambda X, psd, lmin: suboptimality_gap(X.shape[0], d, n, X, psd, min_eig_tol, lmin),
-        round_on_device=round_on_device)
+        round_on_device=round_on_device, project_on_device=project_on_device)
 
 
 def raslam_staircase_ranks(ra, X0, r_min=None, r_max=100, max_iters=1000, rgrad_tol=0.1, min_eig_tol=1e-3,
@@ -601,7 +625,21 @@ def raslam_staircase_ranks(ra, X0, r_min=None, r_max=100, max_iters=1000, rgrad_
     examples/MultiRobotExample_RASLAM.cpp): exchange_run, Exchange.certify and Exchange.lift per level.  With
     robust=..., ra keeps the job's current pose-pose weights (set_pose_pose_weights before every certificate), as
     gnc_ra_ranks leaves them.  certificate: as multi_robot_staircase_ranks ("live": ra is not written).
-    round_on_device: as multi_robot_staircase_ranks, with unit_spheres and landmarks."""
+    round_on_device: as multi_robot_staircase_ranks, with unit_spheres and landmarks.
+    raslam_staircase_ranks_projected ends a certified solve with the projection to rank d as well."""
+    return _raslam_staircase_ranks(False, **locals())
+
+
+def raslam_staircase_ranks_projected(ra, X0, round_on_device=True, **kw):
+    """raslam_staircase_ranks (its arguments, SPMD) ended with Exchange.project, the refinement at rank d and
+    (round_on_device) Exchange.round: multi_robot_staircase_ranks_projected for a range-aided job"""
+    return _raslam_staircase_ranks(True, ra=ra, X0=X0, round_on_device=round_on_device, **kw)
+
+
+def _raslam_staircase_ranks(project_on_device, ra, X0, r_min=None, r_max=100, max_iters=1000, rgrad_tol=0.1,
+                            min_eig_tol=1e-3, gradient_tolerance=1e-4, preconditioned_gradient_tolerance=1e-4,
+                            acceleration=True, params=None, device=0, mode="rbcd++", robust=None, fixed=None, rank=0,
+                            world_size=1, job_name="ra_staircase", certificate="host", round_on_device=False):
     from . import Exchange, RaRbcdSession, ROptParameters, ra_robust_ranked_session
     _check_mode(mode)
     _check_certificate(certificate)
@@ -626,7 +664,7 @@ def raslam_staircase_ranks(ra, X0, r_min=None, r_max=100, max_iters=1000, rgrad_
             return ra.Q
     return _staircase_session(_RanksJob(s, ex, ra.k, rank, q_now, certificate), X0, ra.k, r_min, r_top, max_iters, rgrad_tol,
                               min_eig_tol, gradient_tolerance, preconditioned_gradient_tolerance, mode, ts,
-                              round_on_device=round_on_device)
+                              round_on_device=round_on_device, project_on_device=project_on_device)
 
 
 def multi_robot_team_ranks(ds, X0, num_robots=5, r=5, robust=None, team=None, acceleration=True, params=None,

@@ -496,7 +496,7 @@ int dcora_rbcd_round(dcora_rbcd_t s, int anchor_pose, const double *anchor, doub
  * reflected (0 / 1), rotation blocks with positive determinant before the reflection decision, |rgrad| at the adopted
  * point, ms of the projection kernels, ms of the re-dimensioning, ms total, columns per workgroup of the Gram kernel.
  * DCORA_ERR_UNSUPPORTED, the session untouched: a rank of a job, a ranked robust or team session, a session an exchange
- * was created on (the projection across the ranks of a job does not exist yet). */
+ * was created on (those project together, through dcora_exchange_project below). */
 int dcora_rbcd_project(dcora_rbcd_t s, double *sigma, double *basis, double *gram, double *cost2, double *info8);
 /* Debug entry of the tests: the one-pass Gram kernel of dcora_rbcd_project on a host array.  X: r x k column-major,
  * 1 <= r <= 16, k >= 1; gram: r x r; *chunk (may be NULL): columns per workgroup. */
@@ -614,6 +614,45 @@ int dcora_exchange_lift(dcora_exchange_t ex, double theta, const double *v, cons
  * every collective call; every wait is bounded by DCORA_EXCHANGE_TIMEOUT_S. */
 int dcora_exchange_round(dcora_exchange_t ex, int anchor_pose, const double *anchor, double *trajectory,
                          double *unit_spheres, double *landmarks);
+/* dcora_rbcd_project / dcora_ra_rbcd_project across the ranks of a job: how CORA ends a certified solve (ref
+ * examples/SingleRobotExample_RASLAM.cpp:220-234, projectSolutionRASLAM src/DCORA_utils.cpp:1984-2031), on the exchange
+ * of a pose-graph or a range-aided session -- plain or robust, with or without the ranked team, at any world_size (a
+ * one-rank exchange takes this same path).  Collective and SPMD.  The job goes from rank r to rank d at Proj(V_d^T X)
+ * without leaving the library: no X crosses to a host and no session or exchange is destroyed.
+ *   G = X X^T = sum over the agents of G_a = X_a X_a^T.  Every rank forms G_a of the agents it hosts, from their own
+ * blocks, in one launch pair; the matrices reach every rank per agent and unchanged (through the segment) and every rank
+ * adds them in agent order 0 .. R - 1.  G therefore has the same bits on every rank, for any number of ranks and either
+ * transport; it is the single-process session's G bit for bit only where the job has one agent (that one sums
+ * workgroups over the whole mirror).  Every rank solves the same r x r eigenproblem: the same V_d, no broadcast.  The
+ * blocks with positive determinant are counted by the hosting ranks and summed over the job (integers: exact); the
+ * reflection rule uses the job's n.  Every rank projects its hosted blocks, the public columns travel at d rows with the
+ * ordinary post and wait of all agents, and every rank adopts the point at once between barriers, as dcora_exchange_lift
+ * does, with what that keeps (matrices, preconditioners, robust weights with mu and the update count, team parameters
+ * and loop-closure counts, the exchange, its transport and its rank capacity: a projected job can lift again) and what
+ * it resets (statuses, sequences, round counters; X_initial is the adopted point).
+ * r == d: nothing of the job changes; sigma and gram are produced, cost2 and info8[3] are dcora_exchange_evaluate's.
+ * Outputs as dcora_rbcd_project, every one may be NULL: sigma (r), basis (r x d, where projected), gram (r x r), cost2
+ * and info8[3] (dcora_exchange_evaluate at the adopted point, bit for bit what a following call returns), info8 =
+ * {projected, reflected, positive determinants before the reflection over the JOB, |rgrad|, ms of the projection kernels
+ * on this rank, ms of the re-dimensioning, ms total, columns per workgroup of the Gram kernel}.  Everything but the three
+ * times has the same bits on every rank.
+ * An error on any rank before the adoption leaves the job as it was (the point was formed beside the sessions'
+ * mirrors) and raises the segment's `failed` word as in every collective call; every wait is bounded by
+ * DCORA_EXCHANGE_TIMEOUT_S. */
+int dcora_exchange_project(dcora_exchange_t ex, double *sigma, double *basis, double *gram, double *cost2,
+                           double *info8);
+/* Debug entry of the tests: the block-list Gram kernel pair of dcora_exchange_project on host arrays.  X: the blocks one
+ * after another, block b r x k[b] column-major (k[b] >= 0); grams: nblocks x r x r, block b's bit for bit what
+ * dcora_debug_project_gram gives on that block alone (zeros for k[b] = 0); *chunk (may be NULL): columns per workgroup. */
+int dcora_debug_project_gram_blocks(int r, int nblocks, const long long *k, const double *X, double *grams, int *chunk);
+/* Measurement entry (tools/project_ranks_cost.py): the block-list pair against a loop of the single-block pair over the
+ * same blocks (every k[b] >= 1, zeros as data), alternated `reps` times after one warm-up each; loop_us, pair_us: reps
+ * event times in microseconds. */
+int dcora_debug_project_gram_time(int r, int nblocks, const long long *k, int reps, double *loop_us, double *pair_us);
+/* test / measurement hook: while on, dcora_exchange_project moves the per-agent Gram matrices through the segment's
+ * sums (pieces of 31 doubles, zeros from the ranks that do not host the agent) instead of its X area; the same bits
+ * either way.  Every rank of the job calls it with the same value. */
+int dcora_debug_exchange_project_sums(int on);
 /* host barrier over the ranks of the job (does not synchronise the device) */
 int dcora_exchange_barrier(dcora_exchange_t ex);
 /* Agent::shouldTerminate's team condition (ref src/Agent.cpp:1137-1153: terminate only when EVERY robot reports
