@@ -460,6 +460,42 @@ def _solver_info(self):
 QuadraticProblem.solver_info = _solver_info
 
 
+def _gather_info(self):
+    """how the one-launch tCG run gathers its neighbours' columns (DCORA_GATHER): the column-slot map of its 2-pose
+    workgroups and whether the run uses it ('columns') or every row gathers its own entries ('entries')"""
+    info = np.zeros(5)
+    check(capi.lib().dcora_problem_gather_info(self.h, info))
+    return {"map": bool(info[0]), "workgroups": int(info[1]), "overflow": int(info[2]), "max_poses": int(info[3]),
+            "gather": "columns" if info[4] else "entries"}
+
+
+QuadraticProblem.gather_info = _gather_info
+
+
+def _debug_rerank(self, r_new):
+    """test hook: the problem at rank r_new in place, as a session's lift or projection leaves it (G = 0 afterwards)"""
+    check(capi.lib().dcora_debug_problem_rerank(self.h, int(r_new)))
+    self.r = int(r_new)
+    self._G = None
+
+
+QuadraticProblem.debug_rerank = _debug_rerank
+
+
+def column_slots(rp, ci, n, dh, pb, cap_cols):
+    """the column-slot map of a workgroup tiling (host only): dict of lp, list, count, overflow, slot"""
+    rp = np.ascontiguousarray(rp, dtype=np.int32)
+    ci = np.ascontiguousarray(ci, dtype=np.int32)
+    nwg = (n + pb - 1) // pb
+    cap = nwg * max(1, min(n, cap_cols // dh))
+    out = {"lp": np.zeros(nwg + 1, np.int32), "list": np.zeros(cap, np.int32), "count": np.zeros(nwg, np.int32),
+           "overflow": np.zeros(nwg, np.int32), "slot": np.zeros(len(ci), np.int32)}
+    check(capi.lib().dcora_debug_column_slots(rp, ci, n, dh, pb, cap_cols, cap, out["lp"], out["list"], out["count"],
+                                              out["overflow"], out["slot"]))
+    out["list"] = out["list"][:out["lp"][-1]]
+    return out
+
+
 def time_qapply_rotating(problems, reps=60):
     """average launch time of the Q-apply over several problems in turn on one stream (HBM-cold when their bytes
     exceed the Infinity Cache)"""

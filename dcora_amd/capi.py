@@ -260,6 +260,9 @@ SIGNATURES = {
     "dcora_debug_exchange_leave_stale": (C.c_int, [C.c_char_p, C.c_int, C.c_int]),
     "dcora_debug_exchange_probe_fault": (C.c_int, [C.c_int]),
     "dcora_cert_prepare": (C.c_int, [C.POINTER(Dims), _ip, _ip, C.c_int, C.c_int]),
+    "dcora_problem_gather_info": (C.c_int, [_vp, _dp]),
+    "dcora_debug_problem_rerank": (C.c_int, [_vp, C.c_int]),
+    "dcora_debug_column_slots": (C.c_int, [_ip, _ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip, _ip, _ip, _ip, _ip]),
     "dcora_debug_tcg_run_fault": (C.c_int, [C.c_int]),
     "dcora_debug_tcg_run_fault_at": (C.c_int, [C.c_int, C.c_int]),
     "dcora_debug_wg_sums": (C.c_int, [C.c_int, _dp, _dp]),

@@ -6,6 +6,7 @@
 
 #include "../../include/dcora_hip.h"
 #include "cert.h"
+#include "column_slots.h"
 #include "device_chol.h"
 #include "device_problem.h"
 #include "host_graph.h"
@@ -361,6 +362,37 @@ int dcora_problem_solver_info(dcora_problem_t p, double *info) {
   return abi_call({p, info}, [&]() -> int {
     const DeviceProblem &P = p->p;
     info[0] = !P.use_pc() ? 0 : (P.tcg_run_ok ? 2 : 1);
+    return DCORA_OK;
+  });
+}
+// the column-slot map the one-launch run gathers by: info[0] = 1 a map was built for this problem, info[1] its workgroups,
+// info[2] those that overflow, info[3] the most pose blocks a workgroup names, info[4] = 1 the run form applies and fetches columns
+// once per workgroup (a map without overflow), 0: every row gathers its entries' columns, or there is no run form
+int dcora_problem_gather_info(dcora_problem_t p, double *info) {
+  return abi_call({p, info}, [&]() -> int {
+    const DeviceProblem &P = p->p;
+    info[0] = P.run_cols.p ? 1 : 0;
+    info[1] = P.run_cols_nwg;
+    info[2] = P.run_cols_overflow;
+    info[3] = P.run_cols_max;
+    info[4] = P.run_cols_used() && P.tcg_run_ok ? 1 : 0;
+    return DCORA_OK;
+  });
+}
+int dcora_debug_problem_rerank(dcora_problem_t p, int r_new) {
+  return abi_call({p}, [&] { return p->p.rerank(r_new); });
+}
+int dcora_debug_column_slots(const int *rowptr, const int *colidx, int n, int dh, int pb, int cap_cols, int list_cap,
+                             int *lp, int *list, int *count, int *overflow, int *slot) {
+  return abi_call({rowptr, colidx, lp, list, count, overflow, slot}, [&]() -> int {
+    if (n < 1 || dh < 1 || pb < 1 || cap_cols < dh) return bad("dcora_debug_column_slots: n, dh, pb >= 1 and cap_cols >= dh");
+    const ColumnSlots cs = column_slots(rowptr, colidx, n, dh, pb, cap_cols);
+    if ((int)cs.list.size() > list_cap) return bad("dcora_debug_column_slots: list_cap is too small");
+    std::copy(cs.lp.begin(), cs.lp.end(), lp);
+    std::copy(cs.list.begin(), cs.list.end(), list);
+    std::copy(cs.count.begin(), cs.count.end(), count);
+    for (int w = 0; w < cs.nwg; ++w) overflow[w] = cs.overflow[(size_t)w];
+    for (size_t i = 0; i < cs.slot.size(); ++i) slot[i] = cs.slot[i];
     return DCORA_OK;
   });
 }

@@ -243,6 +243,13 @@ class DeviceProblem {
   bool tcg_run_ok = false;
   bool concurrent_solves = false;
   DevBuf<unsigned> tcg_sync;
+  // The column-slot map of the run's 2-pose tiling (column_slots.h): lp, the lists and the entries' slots in one
+  // allocation.  Built from Q's pattern where the run form applies (at init, or at the rerank that first makes it apply),
+  // unless DCORA_GATHER=entries; it depends on neither r nor Q's values, so a later rerank and set_values keep it.  The run uses it only when no workgroup
+  // overflows: one that did would need both gathers in one kernel, which costs the kernel scratch.
+  DevBuf<int> run_cols;
+  int run_cols_nwg = 0, run_cols_nlist = 0, run_cols_overflow = 0, run_cols_max = 0;
+  bool run_cols_used() const { return run_cols.p != nullptr && run_cols_overflow == 0; }
   // measurement (bench.py's roofline): HIP events on the solver's stream around every k_tcg_run launch while switched on
   bool profile_tcg_runs = false;
   std::vector<hipEvent_t> run_events;  // pairs (start, stop)
@@ -367,6 +374,14 @@ class DeviceProblem {
   void ws_adopt(const std::vector<WsSlot> &plan, DevBuf<double> &&arena_new);
   // eligibility of the one-launch tCG run at a manifold, and its zeroed counters where eligible (aside, enqueued on st)
   int run_form(const ManiDesc &mm, bool fused_, bool has_bsr_, bool *ok, DevBuf<unsigned> *sync);
+  // the map of a pattern (host pointers), built and uploaded aside; adopted where nothing can fail any more
+  struct RunColsBuilt {
+    DevBuf<int> img;
+    int nwg = 0, nlist = 0, overflow = 0, max = 0;
+  };
+  int build_run_cols(const int *rp, const int *ci, int nnz, RunColsBuilt *out) const;
+  void adopt_run_cols(RunColsBuilt &&b);
+  bool gather_columns_ = true;  // DCORA_GATHER as it stood when the problem was created
   int run_rows_nnz_ = 0;  // tcg_run_max_rows_nnz of Q's pattern (SE layout), kept from init: it does not depend on r
   int cus_ = 0;           // compute units of the device, asked once
 };

@@ -2,6 +2,7 @@
 #include <atomic>
 
 #include "device_problem.h"
+#include "column_slots.h"
 #include "env.h"
 #include "escape_rule.h"
 #include "device_chol.h"
@@ -236,6 +237,7 @@ int DeviceProblem::init(const dcora_dims &dims, const HostCsr &Qh, const double 
   fused = fused_eligible(m, Q.nnz);
   group = group_supported(m) && !env::generic_solver();
   run_rows_nnz_ = m.se ? tcg_run_max_rows_nnz(m, Qh.rp.data()) : 0;
+  gather_columns_ = env::gather_columns();
   {
     const std::vector<WsSlot> plan = ws_plan(m, fused);
     DevBuf<double> fresh;
@@ -259,7 +261,12 @@ int DeviceProblem::init(const dcora_dims &dims, const HostCsr &Qh, const double 
     if (rc) return rc;
   }
   lap("precond");
-  return run_form(m, fused, has_bsr, &tcg_run_ok, &tcg_sync);
+  rc = run_form(m, fused, has_bsr, &tcg_run_ok, &tcg_sync);
+  if (rc || !tcg_run_ok) return rc;
+  RunColsBuilt cols;
+  rc = build_run_cols(Qh.rp.data(), Qh.ci.data(), Qh.nnz(), &cols);
+  if (!rc) adopt_run_cols(std::move(cols));
+  return rc;
 }
 
 // One allocation for the whole solver workspace, zeroed by one memset: the reference re-creates its problem on
@@ -300,6 +307,32 @@ void DeviceProblem::ws_adopt(const std::vector<WsSlot> &plan, DevBuf<double> &&a
     sl.b->borrow(arena.p + off, sl.n);
     off += ws_pad(sl.n);
   }
+}
+
+// the column-slot map of the one-launch run's tiling (init and rerank build it where the run form applies: SE layout,
+// d = 3, at most 256 workgroups of 2 poses)
+int DeviceProblem::build_run_cols(const int *rp, const int *ci, int nnz, RunColsBuilt *out) const {
+  if (!m.se || m.d != 3 || m.n < 1 || (m.n + 1) / 2 > 256 || nnz == 0 || !gather_columns_) return DCORA_OK;
+  const ColumnSlots cs = column_slots(rp, ci, m.n, m.d + 1, 2, tcg_run_col_cap());
+  std::vector<int> img;
+  img.reserve(cs.lp.size() + cs.list.size() + cs.slot.size());
+  img.insert(img.end(), cs.lp.begin(), cs.lp.end());
+  img.insert(img.end(), cs.list.begin(), cs.list.end());
+  for (uint16_t sl : cs.slot) img.push_back((int)sl);
+  DCORA_HIP(out->img.alloc(img.size()));
+  DCORA_HIP(hipMemcpy(out->img.p, img.data(), sizeof(int) * img.size(), hipMemcpyHostToDevice));
+  out->nwg = cs.nwg;
+  out->nlist = (int)cs.list.size();
+  out->overflow = cs.n_overflow;
+  out->max = cs.max_count;
+  return DCORA_OK;
+}
+void DeviceProblem::adopt_run_cols(RunColsBuilt &&b) {
+  run_cols = std::move(b.img);
+  run_cols_nwg = b.nwg;
+  run_cols_nlist = b.nlist;
+  run_cols_overflow = b.overflow;
+  run_cols_max = b.max;
 }
 
 // the one-launch tCG run: dense inverse, the whole residual in one LDS image, n / 2 workgroups co-resident
@@ -350,6 +383,14 @@ int DeviceProblem::rerank(int r_new) {
   DevBuf<unsigned> sync_n;
   rc = run_form(mn, fused_n, bsr_n, &run_n, &sync_n);
   if (rc) return rc;
+  RunColsBuilt cols_n;  // the run form applies at this rank first: its map, from the pattern Q holds on the device
+  if (run_n && !run_cols.p && gather_columns_) {
+    std::vector<int> rp((size_t)Q.nrows + 1), ci((size_t)Q.nnz);
+    DCORA_HIP(hipMemcpy(rp.data(), Q.rp.p, sizeof(int) * rp.size(), hipMemcpyDeviceToHost));
+    if (Q.nnz) DCORA_HIP(hipMemcpy(ci.data(), Q.ci.p, sizeof(int) * ci.size(), hipMemcpyDeviceToHost));
+    rc = build_run_cols(rp.data(), ci.data(), Q.nnz, &cols_n);
+    if (rc) return rc;
+  }
   DCORA_HIP(hipStreamSynchronize(st));  // the zeroed workspace is visible to every stream
   // the swap: nothing below fails
   m = mn;
@@ -360,6 +401,7 @@ int DeviceProblem::rerank(int r_new) {
   if (sparse_precond) sp = std::move(sp_n);
   tcg_run_ok = run_n;
   tcg_sync = std::move(sync_n);
+  if (cols_n.img.p) adopt_run_cols(std::move(cols_n));
   has_G = false;
   ride_X_ = nullptr;
   rgd_ = false;
@@ -907,6 +949,11 @@ TcgOperands DeviceProblem::tcg_operands() const {
   o.Hd = Hd.p;  o.eta = eta.p;  o.Heta = Heta.p;  o.z = z.p;  o.Zpart = Zpart.p;  o.W = W.p;
   o.p1 = p1.p;  o.p2 = p2.p;  o.p3 = p3.p;  o.pC = pC.p;
   o.ctl = ctl.p;  o.hf = hf_dev;  o.sync = tcg_sync.p;
+  if (run_cols_used()) {
+    o.cols.lp = run_cols.p;
+    o.cols.list = run_cols.p + run_cols_nwg + 1;
+    o.cols.slot = o.cols.list + run_cols_nlist;
+  }
   // without hubs the sparse preconditioner's two permutations ride in B (scatter of the residual) and C (gather of z)
   if (sparse_precond && sp.foldable()) o.sf = sp.fold();
   return o;

@@ -32,6 +32,9 @@ int solver_bc() {
 bool chain_rides() {
   return !is("DCORA_CHAIN", "launches");
 }
+bool gather_columns() {
+  return !is("DCORA_GATHER", "entries");
+}
 bool factor_on_host() {
   static const bool v = is("DCORA_FACTOR", "host");
   return v;

@@ -82,6 +82,14 @@ constexpr int kRunShards = 32, kRunCopies = 64, kRunStride = 32;  // sync words 
 constexpr int kRunSyncWords = (kRunShards + 1 + kRunCopies + 1) * kRunStride;
 constexpr int kRunQCap = 1024;  // CSR entries of a workgroup's 2 (d+1) matrix rows staged in LDS once per run
 constexpr int kRunNS = 4;       // 128-column steps per wave held in registers: k <= 4 * 4 * 128 = 2048
+// The most columns a workgroup's list of neighbour pose blocks may hold (column_slots.h): 16 pose blocks of d + 1 = 4.
+// What the staged nd = beta d_old - z of those columns takes in LDS is kRunColCap * r doubles, 3 KB at r = 6.  The LDS
+// free at r = 6, k = 2048: 160 KB - the image (2048 * 6 * 8 + 16 = 98 320 B) - s_P (49 * 16 * 8 = 6 272 B) - s_Z, s_R,
+// s_W, s_D, s_H (1 928 B) - s_ci, s_v (12 288 B) - s_red, s_ok (132 B) = 44 900 B, so LDS is not what bounds the cap:
+// every listed pair of doubles is loaded by a thread of its own (ONE 16-byte load per thread and vector), and at
+// r = 6 sixteen blocks are 16 * 2 r = 192 of the 256 threads.  A map in which a workgroup names more pose blocks sends the
+// problem's runs to the other gather (launch_tcg_run): both gathers in one kernel cost it scratch.
+constexpr int kRunColCap = 64;
 // ---- where the residual image lies in LDS ----
 // Pair i (doubles 2 i, 2 i + 1 of the column-major residual) lies at byte run_img_off(i) of the dynamic LDS: every write
 // of the image (first staging, zero fill, the update per iteration) and the product's reads go through it, and
@@ -104,6 +112,7 @@ struct TcgRunArgs {
   HostFlags *hf;
   int seq;
   int fault;       // test hook (dcora_debug_tcg_run_fault): workgroup 0 leaves before the first grid step
+  ColSlotsDev cols;  // the column-slot map of the 2-pose tiling, no workgroup of it overflowing (lp null: the gather goes entry by entry)
 #ifdef DCORA_RUN_STAMPS
   long long *stamps;  // profiling build only: wall_clock64 of workgroup 0 at the phase boundaries of a run
 #endif
@@ -210,7 +219,9 @@ __device__ __forceinline__ bool run_grid_step(unsigned *sync, unsigned step, int
   return *s_ok != 0;
 }
 
-template <int D, int R, int NS>
+// COLS: phase A fetches every neighbour column once per workgroup (the launch carries a column-slot map in which no
+// workgroup overflows); otherwise every row gathers its entries' columns itself
+template <int D, int R, int NS, bool COLS>
 __global__ __launch_bounds__(kPcBlock) void k_tcg_run(TcgRunArgs a) {
   constexpr int DH = D + 1, PB = 2, NR = PB * DH, RM = R;
   // pieces of kPcBlock pairs that hold the largest residual of the form (NS * kPcNW * 128 columns of R doubles): 4 R of
@@ -228,6 +239,12 @@ __global__ __launch_bounds__(kPcBlock) void k_tcg_run(TcgRunArgs a) {
   __shared__ int s_ci[kRunQCap];
   __shared__ double s_v[kRunQCap];
   __shared__ int s_ok;
+  // nd = beta d_old - z of the workgroup's listed pose blocks, block after block as in memory: column slot s, row t of
+  // the vector at s * R + t (column_slots.h); pair i is written by thread i
+  static_assert((DH * R) % 2 == 0, "a pose block is a whole number of 16-byte pairs, 16-byte aligned");
+  constexpr int kBlkPairs = DH * R / 2;
+  static_assert(kRunColCap / DH * kBlkPairs <= kPcBlock, "one thread per listed pair");
+  __shared__ double2 s_N[COLS ? kRunColCap * R / 2 : 1];
   SolverCtl *ctl = a.ctl;
   const int seq = a.seq;
   RUN_STAMP(0);
@@ -280,6 +297,17 @@ __global__ __launch_bounds__(kPcBlock) void k_tcg_run(TcgRunArgs a) {
         mreg[u][q] = pc_ld16(rs_m, voff_l, (unsigned)(((size_t)(j0 + q) * ldm + (size_t)(wave_u + kPcNW * u) * 128) * 8));
   };
   const int pbeg = a.Q.rp[j0], pend = a.Q.rp[j0 + nrow];
+  // COLS: the workgroup's list of neighbour pose blocks.  Thread i loads pair i of the listed blocks; ONE register is
+  // kept for the run, coff: the byte offset of this thread's pair in a vector, kNoPair where it loads none
+  constexpr unsigned kNoPair = 0xffffffffu;
+  [[maybe_unused]] unsigned coff = kNoPair;
+  if constexpr (COLS) {
+    // (the host launches this form only where no list exceeds the cap: the min is a bound on s_N, not a path)
+    const int cl_b = a.cols.lp[blockIdx.x], cl_n = min(a.cols.lp[blockIdx.x + 1] - cl_b, kRunColCap / DH);
+    if (e < cl_n * kBlkPairs) coff = (unsigned)((a.cols.list[cl_b + e / kBlkPairs] * kBlkPairs + e % kBlkPairs) * 16);
+  }
+  // (with a list s_ci holds the entries' column SLOTS: the same loads through another pointer)
+  const int *__restrict__ ci_src = COLS ? a.cols.slot : a.Q.ci;
 #ifdef DCORA_RUN_ROWS_FIRST
   load_rows();
 #endif
@@ -288,20 +316,21 @@ __global__ __launch_bounds__(kPcBlock) void k_tcg_run(TcgRunArgs a) {
   for (int u = 0; u < kPcSB; ++u) xg[u] = pc_ld16(rs_g, voff_t, (unsigned)u * kPcBlock * 16u);
 #ifdef DCORA_RUN_ROWS_FIRST
   for (int i = threadIdx.x; i < pend - pbeg; i += kPcBlock) {
-    s_ci[i] = a.Q.ci[pbeg + i];
+    s_ci[i] = ci_src[pbeg + i];
     s_v[i] = a.Q.v[pbeg + i];
   }
   const int myb = own ? a.Q.rp[j0 + lc] - pbeg : 0, mye = own ? a.Q.rp[j0 + lc + 1] - pbeg : 0;
 #else
   // the CSR entries into registers, every thread kRunQCap / kPcBlock of them (a thread beyond the end loads the last
-  // entry again and stores nothing); the row pointers of a thread beyond the rows are those of the last row's end
+  // entry again and stores nothing); the row pointers of a thread beyond the rows are those of the last row's end.
+  // With a list of pose blocks s_ci holds the entries' column SLOTS: the same loads through another pointer
   constexpr int kStage = kRunQCap / kPcBlock;
   int st_ci[kStage];
   double st_v[kStage];
 #pragma unroll
   for (int u = 0; u < kStage; ++u) {
     const int i = min(u * kPcBlock + (int)threadIdx.x, pend - pbeg - 1);
-    st_ci[u] = a.Q.ci[pbeg + i];
+    st_ci[u] = ci_src[pbeg + i];
     st_v[u] = a.Q.v[pbeg + i];
   }
   const int rp_b = a.Q.rp[j0 + min(lc, nrow)], rp_e = a.Q.rp[j0 + min(lc + 1, nrow)];
@@ -469,6 +498,20 @@ __global__ __launch_bounds__(kPcBlock) void k_tcg_run(TcgRunArgs a) {
   if (own) s_R[lc * RM + t] = o_r;
   __syncthreads();
   RUN_STAMP(1);
+  // COLS: the first kColGB entries of this thread's row -- weight and where the entry's nd lies in s_N -- stay in
+  // registers for the run (this form has them to spare): an iteration reads s_N only, one LDS round trip behind the
+  // staging's barrier where reading s_ci and s_v again made it two
+  constexpr int kColGB = 24;
+  [[maybe_unused]] int nq[kColGB];
+  [[maybe_unused]] double wq[kColGB];
+  if constexpr (COLS) {
+#pragma unroll
+    for (int q = 0; q < kColGB; ++q) {
+      const bool ok = myb + q < mye;
+      wq[q] = ok ? s_v[myb + q] : 0.0;
+      nq[q] = (ok ? s_ci[myb + q] : 0) * r + t;
+    }
+  }
   product(64);
   project_z();
   RUN_STAMP(2);
@@ -492,54 +535,98 @@ __global__ __launch_bounds__(kPcBlock) void k_tcg_run(TcgRunArgs a) {
       // up to kRunGB entries of a matrix row, beside the partials' -- in chunks of 8 behind the partials' sum an
       // iteration paid three to four dependent round trips here
       constexpr int kRunGB = 24;
-      double ga[kRunGB], gz[kRunGB];
-      double z_own = 0;
-      if (own) {
-        z_own = ld_coh(a.z + oown);
+      double z_own = 0, beta = 0, accw = 0, dn = 0;
+      // what every thread does between the requests and the products: <z, r> from the workgroups' partials, beta, the
+      // tCG scalars of the new direction (once per iteration, in whichever branch below)
+      auto direction = [&]() {
+        const int np3 = gridDim.x;
+        const int l = lane;
+        const double pa = (l < np3) ? ld_coh(a.p3 + l) : 0.0, pb = (l + 64 < np3) ? ld_coh(a.p3 + l + 64) : 0.0;
+        const double pcc = (l + 128 < np3) ? ld_coh(a.p3 + l + 128) : 0.0, pd = (l + 192 < np3) ? ld_coh(a.p3 + l + 192) : 0.0;
+        const double z_r_new = wave_sum((pa + pb) + (pcc + pd));
+#ifdef DCORA_RUN_STAMPS
+        __builtin_amdgcn_s_waitcnt(0);  // the gather's loads have returned
+        RUN_STAMP(sb0);
+#endif
+        if (iter > 0) beta = tcg_beta(z_r_new, zr);
+        const TcgDir dir = iter == 0 ? tcg_dir_start(z_r_new) : tcg_dir_next(z_r_new, beta, alpha, dPd, ePd);
+        zr = dir.z_r;
+        ePd = dir.e_Pd;
+        dPd = dir.d_Pd;
+        ePe = iter == 0 ? 0.0 : ePen;
+      };
+      // Every term of a row's sum is w * nd with nd = beta d_old - z of the entry's column, as ONE fma each (what the
+      // compiler contracts `accw += w * (beta * ga - gz)` to, stated so that it does not depend on where nd is formed):
+      // the staged nd of a listed column is the nd every row naming it would form itself, bit for bit.
+      if (own) z_own = ld_coh(a.z + oown);
+      if constexpr (COLS) {
+        // ALL threads request the listed blocks of z and d_old, every pair of doubles once (one 16-byte sc1 load per
+        // thread and vector: a pose block is 16-byte aligned), instead of every CSR entry's column by every row that
+        // names it; in the same trip as the partials
+        double2 cz{0.0, 0.0}, cd{0.0, 0.0};
+        if (coff != kNoPair) {
+          cz = pc_ld16_coh(__builtin_amdgcn_make_buffer_rsrc(a.z, 0, vec_bytes, 0x00020000), coff, 0);
+          if (iter > 0)
+            cd = pc_ld16_coh(__builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(d_old), 0, vec_bytes, 0x00020000),
+                             coff, 0);
+        }
+        direction();
+        if (coff != kNoPair) s_N[e] = double2{fma(beta, cd.x, -cz.x), fma(beta, cd.y, -cz.y)};
+        __syncthreads();
+        if (own) {
+          // the same entries in the same order, the batch of kRunGB and chunks of 8 padded with zero weights as on the
+          // other path; a padded term reads s_N[t] (slot 0, always written: the list holds the own poses) where the other
+          // path reads element t of column 0 -- either way 0 * a finite value added to the sum
+          static_assert(kColGB == kRunGB, "the batch kept in registers is the other gather's batch");
+          const double *__restrict__ sN0 = reinterpret_cast<const double *>(s_N), *__restrict__ sN = sN0 + t;
 #pragma unroll
-        for (int q = 0; q < kRunGB; ++q) {
-          const bool ok = myb + q < mye;
-          const size_t oo = ok ? (size_t)s_ci[myb + q] * r + t : 0;
-          gz[q] = ld_coh(a.z + oo);
-          ga[q] = (iter > 0) ? ld_coh(d_old + oo) : 0.0;
+          for (int q = 0; q < kRunGB; ++q) accw = fma(wq[q], sN0[nq[q]], accw);
+          for (int p = myb + kRunGB; p < mye; p += 8) {
+            double n8[8], w8[8];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+              const bool ok = p + q < mye;
+              w8[q] = ok ? s_v[p + q] : 0.0;
+              n8[q] = sN[(ok ? s_ci[p + q] : 0) * r];
+            }
+#pragma unroll
+            for (int q = 0; q < 8; ++q) accw = fma(w8[q], n8[q], accw);
+          }
+        }
+      } else {
+        double ga[kRunGB], gz[kRunGB];
+        if (own) {
+#pragma unroll
+          for (int q = 0; q < kRunGB; ++q) {
+            const bool ok = myb + q < mye;
+            const size_t oo = ok ? (size_t)s_ci[myb + q] * r + t : 0;
+            gz[q] = ld_coh(a.z + oo);
+            ga[q] = (iter > 0) ? ld_coh(d_old + oo) : 0.0;
+          }
+        }
+        direction();
+        if (own) {
+#pragma unroll
+          for (int q = 0; q < kRunGB; ++q) {
+            const double w = (myb + q < mye) ? s_v[myb + q] : 0.0;  // (the weights come from LDS when they are used)
+            accw = fma(w, fma(beta, ga[q], -gz[q]), accw);
+          }
+          for (int p = myb + kRunGB; p < mye; p += 8) {
+            double a8[8], b8[8], w8[8];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+              const bool ok = p + q < mye;
+              const size_t oo = ok ? (size_t)s_ci[p + q] * r + t : 0;
+              w8[q] = ok ? s_v[p + q] : 0.0;
+              b8[q] = ld_coh(a.z + oo);
+              a8[q] = (iter > 0) ? ld_coh(d_old + oo) : 0.0;
+            }
+#pragma unroll
+            for (int q = 0; q < 8; ++q) accw = fma(w8[q], fma(beta, a8[q], -b8[q]), accw);
+          }
         }
       }
-      const int np3 = gridDim.x;
-      const int l = lane;
-      const double pa = (l < np3) ? ld_coh(a.p3 + l) : 0.0, pb = (l + 64 < np3) ? ld_coh(a.p3 + l + 64) : 0.0;
-      const double pcc = (l + 128 < np3) ? ld_coh(a.p3 + l + 128) : 0.0, pd = (l + 192 < np3) ? ld_coh(a.p3 + l + 192) : 0.0;
-      const double z_r_new = wave_sum((pa + pb) + (pcc + pd));
-#ifdef DCORA_RUN_STAMPS
-      __builtin_amdgcn_s_waitcnt(0);  // the gather's loads have returned
-      RUN_STAMP(sb0);
-#endif
-      double beta = 0;
-      if (iter > 0) beta = tcg_beta(z_r_new, zr);
-      const TcgDir dir = iter == 0 ? tcg_dir_start(z_r_new) : tcg_dir_next(z_r_new, beta, alpha, dPd, ePd);
-      zr = dir.z_r;
-      ePd = dir.e_Pd;
-      dPd = dir.d_Pd;
-      ePe = iter == 0 ? 0.0 : ePen;
-      double accw = 0, dn = 0;
       if (own) {
-#pragma unroll
-        for (int q = 0; q < kRunGB; ++q) {
-          const double w = (myb + q < mye) ? s_v[myb + q] : 0.0;  // (the weights come from LDS when they are used)
-          accw += w * (beta * ga[q] - gz[q]);
-        }
-        for (int p = myb + kRunGB; p < mye; p += 8) {
-          double a8[8], b8[8], w8[8];
-#pragma unroll
-          for (int q = 0; q < 8; ++q) {
-            const bool ok = p + q < mye;
-            const size_t oo = ok ? (size_t)s_ci[p + q] * r + t : 0;
-            w8[q] = ok ? s_v[p + q] : 0.0;
-            b8[q] = ld_coh(a.z + oo);
-            a8[q] = (iter > 0) ? ld_coh(d_old + oo) : 0.0;
-          }
-#pragma unroll
-          for (int q = 0; q < 8; ++q) accw += w8[q] * (beta * a8[q] - b8[q]);
-        }
         dn = (iter > 0) ? beta * o_d - z_own : -z_own;
         st_coh(d_new + oown, dn);
         o_d = dn;
@@ -735,6 +822,7 @@ __global__ __launch_bounds__(kPcBlock) void k_debug_wg_sums(const double *__rest
 
 // ---- the one-launch tCG run ------------------------------------------------------------------------------
 int tcg_run_sync_words() { return kRunSyncWords; }
+int tcg_run_col_cap() { return kRunColCap; }
 std::atomic<int> g_tcg_run_fault{0};
 std::atomic<int> g_tcg_run_fault_skip{0};
 int tcg_run_max_rows_nnz(const ManiDesc &m, const int *rp) {
@@ -757,14 +845,14 @@ bool tcg_run_supported(const ManiDesc &m, int ldm, int cus, int max_rows_nnz) {
   if ((grid + rows_per - 1) / rows_per > 64) return false;         // <delta, H delta> partials in one wave
   return max_rows_nnz <= kRunQCap;
 }
-template <int R>
+template <int R, bool COLS>
 static int tcg_run_launch(hipStream_t st, const TcgRunArgs &a) {
   static LdsGrant grant;
   const int cpad = ((a.m.k + 127) / 128) * 128;
   const size_t lds = run_img_bytes(R, cpad);
-  if (!grant.granted(reinterpret_cast<const void *>(&k_tcg_run<3, R, kRunNS>), lds, 40 * 1024)) return -1;
+  if (!grant.granted(reinterpret_cast<const void *>(&k_tcg_run<3, R, kRunNS, COLS>), lds, 40 * 1024)) return -1;
   const int grid = (a.m.n + 1) / 2;
-  hipLaunchKernelGGL((k_tcg_run<3, R, kRunNS>), dim3(grid), dim3(kPcBlock), lds, st, a);
+  hipLaunchKernelGGL((k_tcg_run<3, R, kRunNS, COLS>), dim3(grid), dim3(kPcBlock), lds, st, a);
   if (hipGetLastError() != hipSuccess) return -1;
   return grid;
 }
@@ -784,7 +872,7 @@ int launch_tcg_run(hipStream_t st, const TcgOperands &o, int seq) {
     }
   const ManiDesc &m = o.m;
   TcgRunArgs a{m, o.ldm, o.Minv, o.Q, o.grad, o.X, o.S, o.d[0], o.d[1], o.Hd, o.eta, o.Heta, o.z, o.p1, o.p3, o.pC,
-               o.sync, o.ctl, o.hf, seq, fault};
+               o.sync, o.ctl, o.hf, seq, fault, o.cols};
 #ifdef DCORA_RUN_STAMPS
   {
     // a ring of stamp blocks: launch c writes block c % kRing, and the host reads a block when it comes round again,
@@ -819,9 +907,10 @@ int launch_tcg_run(hipStream_t st, const TcgOperands &o, int seq) {
     a.stamps = buf;
   }
 #endif
-  if (m.r == 4) return tcg_run_launch<4>(st, a);
-  if (m.r == 5) return tcg_run_launch<5>(st, a);
-  if (m.r == 6) return tcg_run_launch<6>(st, a);
+  const bool cols = a.cols.lp != nullptr;
+  if (m.r == 4) return cols ? tcg_run_launch<4, true>(st, a) : tcg_run_launch<4, false>(st, a);
+  if (m.r == 5) return cols ? tcg_run_launch<5, true>(st, a) : tcg_run_launch<5, false>(st, a);
+  if (m.r == 6) return cols ? tcg_run_launch<6, true>(st, a) : tcg_run_launch<6, false>(st, a);
   return -1;
 }
 int launch_debug_wg_sums(hipStream_t st, int nv, const double *in, double *out) {

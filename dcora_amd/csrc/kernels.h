@@ -73,6 +73,15 @@ struct CsrDev {
   int *long_cnt = nullptr;         // n_long arrival counters (zero between launches)
 };
 
+// device view of the column-slot map of a workgroup tiling (column_slots.h): per workgroup w the poses
+// list[lp[w] .. lp[w + 1]) whose column blocks its rows name (empty: the workgroup gathers entry by entry), per CSR
+// entry its column's slot in that list.  lp == nullptr: no map
+struct ColSlotsDev {
+  const int *lp = nullptr;
+  const int *list = nullptr;
+  const int *slot = nullptr;  // (as wide as ci: a kernel stages one or the other through the same loads)
+};
+
 // block-CSR view of a pose-graph matrix: (d+1) x (d+1) dense blocks, column-major inside a block (HostBsr, host_sparse.h)
 struct BsrDev {
   int nbrows = 0;
@@ -301,6 +310,7 @@ struct TcgOperands {
   HostFlags *hf = nullptr;
   SpFold sf;                 // the sparse preconditioner's permutations riding in B and C
   unsigned *sync = nullptr;  // the one-launch run's grid-step counters
+  ColSlotsDev cols;          // the one-launch run's column-slot map (null: its gather goes entry by entry)
   // the residual a step launch leaves (and the C launch behind it reads)
   double *res_new(int iter, int first) const { return first ? r[0] : r[(iter & 1) ^ 1]; }
 };
@@ -315,6 +325,7 @@ int fused_pc_blocks(const ManiDesc &m);
 // CSR entries any workgroup's 2 (d+1) matrix rows hold.  tcg_run_sync_words: unsigned words of its grid-step counters.
 bool tcg_run_supported(const ManiDesc &m, int ldm, int cus, int max_rows_nnz);
 int tcg_run_sync_words();
+int tcg_run_col_cap();  // the most columns a workgroup's list of the run's column-slot map may hold (2-pose tiling)
 extern std::atomic<int> g_tcg_run_fault;  // test hook: that many of the next runs lose workgroup 0 before the first step
 extern std::atomic<int> g_tcg_run_fault_skip;  // ... after this many launches of the run kernel that pass untouched
 int tcg_run_max_rows_nnz(const ManiDesc &m, const int *rowptr);  // host CSR row pointers -> the figure above

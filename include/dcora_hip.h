@@ -116,6 +116,25 @@ int dcora_debug_hessvec_solver_form(dcora_problem_t p, const double *X, const do
  * iteration (or the sparse preconditioner), 1 = two launches (Hessian product; step + dense preconditioner + projection),
  * 2 = the whole tCG run of an RTR iteration in ONE launch (dense preconditioner, n / 2 workgroups co-resident). */
 int dcora_problem_solver_info(dcora_problem_t p, double *info);
+/* How the one-launch tCG run gathers its neighbours' columns on this problem (DCORA_GATHER):
+ * info[0] = 1 a column-slot map of the run's 2-pose workgroups was built, info[1] its workgroups, info[2] those naming
+ * more pose blocks than the map holds per workgroup (overflow), info[3] the most pose blocks a workgroup names, info[4] = 1
+ * the run form applies here and fetches every neighbour column once per workgroup (a map, no overflow), 0 every row
+ * gathers its own entries, or the problem has no run form.
+ * info: 5 doubles. */
+int dcora_problem_gather_info(dcora_problem_t p, double *info);
+/* test hook: the problem at another relaxation rank, in place (what a session's lift and projection do to their agents'
+ * problems): Q, the preconditioner and the stream stay, the workspace and the solver forms are those of r_new, G is
+ * zero afterwards. */
+int dcora_debug_problem_rerank(dcora_problem_t p, int r_new);
+/* test hook (host only, no device needed): the column-slot map of a workgroup tiling.  rowptr / colidx: the pattern of
+ * an n dh x n dh SE-layout matrix (dh = d + 1); pb poses per workgroup, ceil(n / pb) workgroups; cap_cols: the most
+ * columns a workgroup's list may hold.  lp (workgroups + 1) / list (room for list_cap): per workgroup the ascending
+ * distinct poses its rows name, its own among them; empty where it overflows.  count, overflow (workgroups): the poses
+ * it names, and whether they exceed cap_cols / dh.  slot (one per entry): position of the entry's pose in the list
+ * times dh plus its column within the pose; 65535 in an overflow workgroup. */
+int dcora_debug_column_slots(const int *rowptr, const int *colidx, int n, int dh, int pb, int cap_cols, int list_cap,
+                             int *lp, int *list, int *count, int *overflow, int *slot);
 /* test hook: the next `runs` one-launch tCG runs of this process lose a workgroup before their first grid-wide step, as
  * if the grid were not co-resident: the run must give up within milliseconds and the solve continue on the launches */
 int dcora_debug_tcg_run_fault(int runs);
