@@ -2,7 +2,7 @@
 //   * dual certificate S(X) = Q - Lambda(X): Q X^T by the SpMM kernel, Lambda blocks by a per-pose kernel;
 //   * minimum eigenpair: thick-restart Lanczos (nev = 1, ncv = 20, largest magnitude, spectrum shift) whose
 //     mat-vecs, re-orthogonalisation GEMVs and basis updates run on the GPU; only the <= 20 x 20 projected
-//     eigenproblem is solved on the host;
+//     eigenproblem is solved on the host (the recurrence: lanczos_restart.h; the plan of its runs: min_eig_plan.h);
 //   * PSD test: sparse Cholesky of S + eta I on the host (setup-class code shared with the preconditioner).
 #include <algorithm>
 #include <cmath>
@@ -14,6 +14,7 @@
 #include "env.h"
 #include "device_chol.h"
 #include "device_problem.h"
+#include "ra_rbcd.h"
 
 namespace dcora {
 
@@ -27,42 +28,6 @@ __global__ __launch_bounds__(kBlock) void k_basis_combine(int n, int m, int keep
       for (int i = 0; i < m; ++i) s += V[(size_t)i * n + t] * Z[(size_t)c * m + i];
       out[(size_t)c * n + t] = s;
     }
-}
-
-void jacobi_eig(int m, std::vector<double> A, std::vector<double> &Z, std::vector<double> &w) {
-  Z.assign((size_t)m * m, 0.0);
-  for (int i = 0; i < m; ++i) Z[(size_t)i * m + i] = 1;
-  for (int sweep = 0; sweep < 100; ++sweep) {
-    double off = 0, dg = 0;
-    for (int i = 0; i < m; ++i) {
-      dg += A[(size_t)i * m + i] * A[(size_t)i * m + i];
-      for (int j = i + 1; j < m; ++j) off += A[(size_t)i * m + j] * A[(size_t)i * m + j];
-    }
-    if (off == 0 || off <= 1e-32 * (dg + off)) break;
-    for (int p = 0; p < m - 1; ++p)
-      for (int q = p + 1; q < m; ++q) {
-        const double apq = A[(size_t)p * m + q];
-        if (apq == 0) continue;
-        const double zeta = (A[(size_t)q * m + q] - A[(size_t)p * m + p]) / (2 * apq);
-        const double t = (zeta >= 0 ? 1.0 : -1.0) / (std::fabs(zeta) + std::sqrt(1 + zeta * zeta));
-        const double c = 1 / std::sqrt(1 + t * t), s = c * t;
-        for (int k = 0; k < m; ++k) {
-          const double akp = A[(size_t)k * m + p], akq = A[(size_t)k * m + q];
-          A[(size_t)k * m + p] = c * akp - s * akq;
-          A[(size_t)k * m + q] = s * akp + c * akq;
-        }
-        for (int k = 0; k < m; ++k) {
-          const double apk = A[(size_t)p * m + k], aqk = A[(size_t)q * m + k];
-          A[(size_t)p * m + k] = c * apk - s * aqk;
-          A[(size_t)q * m + k] = s * apk + c * aqk;
-          const double zkp = Z[(size_t)k * m + p], zkq = Z[(size_t)k * m + q];
-          Z[(size_t)k * m + p] = c * zkp - s * zkq;
-          Z[(size_t)k * m + q] = s * zkp + c * zkq;
-        }
-      }
-  }
-  w.resize(m);
-  for (int i = 0; i < m; ++i) w[i] = A[(size_t)i * m + i];
 }
 
 inline uint64_t splitmix(uint64_t &s) {
@@ -96,8 +61,8 @@ int DeviceLanczos::init(const HostCsr &S, int device_) {
 int DeviceLanczos::init_rows(int n_local, int n_global_, int lo_, int device_, hipStream_t stream) {
   device = device_;
   n = n_local;
-  n_global = n_global_;
-  lo = lo_;
+  ranks.n_global = n_global_;
+  ranks.lo = lo_;
   st = stream;
   own_stream = false;
   DCORA_HIP(hipSetDevice(device));
@@ -113,259 +78,242 @@ DeviceLanczos::~DeviceLanczos() {
   if (st && own_stream) (void)hipStreamDestroy(st);
 }
 
-// Thick-restart Lanczos for the largest-magnitude eigenpair of (S - shift I).  Convergence test and the
-// number of Ritz vectors kept per restart follow Spectra's SymEigsSolver for nev = 1:
-// |beta_m y_m| < tol max(eps^(2/3), |theta|), keep = ncv / 2.
+int LanczosRanks::reduce(hipStream_t st, double *dev, int count) const {
+  if (!allreduce) return DCORA_OK;
+  std::vector<double> tmp((size_t)count);
+  DCORA_HIP(hipMemcpyAsync(tmp.data(), dev, sizeof(double) * count, hipMemcpyDeviceToHost, st));
+  DCORA_HIP(hipStreamSynchronize(st));
+  const int rc = allreduce(tmp.data(), count);
+  if (rc) return rc;
+  DCORA_HIP(hipMemcpyAsync(dev, tmp.data(), sizeof(double) * count, hipMemcpyHostToDevice, st));
+  DCORA_HIP(hipStreamSynchronize(st));  // tmp leaves scope
+  return DCORA_OK;
+}
+
+// per step 64 coefficients (two passes of 32) and the norm; raised by a step whose direction was dead
+struct DeviceLanczos::CycleStore {
+  DevBuf<double> h, beta;
+  DevBuf<int> dead;
+};
+
+double DeviceLanczos::whole_vector(uint64_t s, const double *given) {
+  double nn = 0;
+  for (double &x : whole_) {
+    x = given ? *given++ : (u01(s) - 0.5);
+    nn += x * x;
+  }
+  ranks.slice(whole_.data(), n, local_.data());
+  return std::sqrt(nn);
+}
+
+int DeviceLanczos::apply(int j) {
+  double *vj = V.p + (size_t)j * n;
+  const bool inverse = !op && inverse_op;
+  if (op) {
+    const int rc = op(vj, w.p);
+    if (rc) return rc;
+  } else if (inverse) {
+    inverse_op->apply(st, 1, buf1(vj), w.p, Gate{});
+  } else {
+    launch_spmm(st, 1, Sd.view(), buf1(vj), 0, nullptr, buf1(w.p), 0, nullptr, Gate{});
+  }
+  if (!inverse && shift_ != 0) launch_scale_shift(st, n, shift_, vj, w.p);
+  ++*matvecs_;
+  return DCORA_OK;
+}
+
+int DeviceLanczos::orthogonalise(int nv, double *coeff) {
+  launch_lanczos_proj(st, n, nv, V.p, w.p, part.p);
+  launch_sum_partials(st, part.p, npart_, 24, nv, coeff);
+  const int rc = ranks.reduce(st, coeff, nv);
+  if (rc) return rc;
+  launch_lanczos_sub(st, n, nv, V.p, coeff, w.p);
+  return DCORA_OK;
+}
+
+int DeviceLanczos::norm2() {
+  launch_dot(st, n, w.p, w.p, part.p);
+  launch_sum_partials(st, part.p, npart_, 1, 1, small.p + 64);
+  return ranks.reduce(st, small.p + 64, 1);
+}
+
+int DeviceLanczos::fresh_direction(int j) {
+  whole_vector(seed_ + 7919 * (j + 1), nullptr);
+  DCORA_HIP(hipMemcpyAsync(w.p, local_.data(), sizeof(double) * n, hipMemcpyHostToDevice, st));
+  for (int pass = 0; pass < 2; ++pass) {
+    const int rc = orthogonalise(j + 1, small.p);
+    if (rc) return rc;
+  }
+  const int rc = norm2();
+  if (rc) return rc;
+  launch_scale(st, n, small.p + 64, w.p, V.p + (size_t)(j + 1) * n);
+  DCORA_HIP(hipStreamSynchronize(st));
+  return DCORA_OK;
+}
+
+// One Lanczos step = operator, two passes of projection against the whole basis, the norm, the next vector.  The slow
+// form reads the coefficients and the norm back after every step (needed when the sums go over ranks, and to handle a
+// vanishing norm); the fast form keeps them on the device -- the subtraction sums the projection's partials in its
+// prologue, the next vector is scaled by the kernel that sums <w, w> -- and the host reads a whole restart cycle's
+// coefficients at once: 8 launches and no host round trip per step instead of 11 launches, two copies and a wait.
+int DeviceLanczos::slow_step(LanczosRestart &T, int j) {
+  int rc = apply(j);
+  if (rc) return rc;
+  for (int pass = 0; pass < 2; ++pass) {
+    rc = orthogonalise(j + 1, small.p + 32 * pass);
+    if (rc) return rc;
+  }
+  rc = norm2();
+  if (rc) return rc;
+  double hbuf[64], b2 = 0;
+  DCORA_HIP(hipMemcpyAsync(hbuf, small.p, sizeof(double) * 64, hipMemcpyDeviceToHost, st));
+  DCORA_HIP(hipMemcpyAsync(&b2, small.p + 64, sizeof(double), hipMemcpyDeviceToHost, st));
+  DCORA_HIP(hipStreamSynchronize(st));
+  // a dead direction is an invariant subspace (the remainder is rounding noise of the orthogonalisation, or exactly
+  // zero): continue with a fresh random direction orthogonalised against the basis
+  if (!T.take_step(j, hbuf, hbuf + 32, b2)) return fresh_direction(j);
+  launch_axpby(st, n, 1.0 / T.beta, w.p, 0.0, nullptr, V.p + (size_t)(j + 1) * n);
+  return DCORA_OK;
+}
+
+int DeviceLanczos::fast_cycle(LanczosRestart &T) {
+  CycleStore &c = *cycle_;
+  const int m = T.m;
+  const bool fused = npart_ <= kLanczosFuseParts;
+  // (the dot's partials go behind the projection's in `part`: k_lanczos_sub_sum still reads those)
+  double *dotpart = fused ? part.p + (size_t)npart_ * 24 : part.p;
+  for (int j = T.k; j < m; ++j) {
+    const int rc = apply(j);
+    if (rc) return rc;
+    const int nv = j + 1;
+    double *hrow = c.h.p + (size_t)j * 64;
+    for (int pass = 0; pass < 2; ++pass) {
+      launch_lanczos_proj(st, n, nv, V.p, w.p, part.p);
+      if (fused) {
+        launch_lanczos_sub_sum(st, n, nv, V.p, part.p, npart_, hrow + 32 * pass, w.p, pass == 1 ? dotpart : nullptr);
+      } else {
+        launch_sum_partials(st, part.p, npart_, 24, nv, small.p + 32 * pass);
+        launch_lanczos_keep(st, nv, small.p + 32 * pass, hrow + 32 * pass);
+        launch_lanczos_sub(st, n, nv, V.p, small.p + 32 * pass, w.p);
+      }
+    }
+    if (!fused) launch_dot(st, n, w.p, w.p, part.p);
+    launch_lanczos_next(st, n, dotpart, npart_, c.beta.p + j, c.dead.p, w.p, V.p + (size_t)(j + 1) * n, hrow, nv);
+  }
+  std::vector<double> hh((size_t)m * 64), bb((size_t)m);
+  int dead = 0;
+  DCORA_HIP(hipMemcpyAsync(hh.data(), c.h.p, sizeof(double) * hh.size(), hipMemcpyDeviceToHost, st));
+  DCORA_HIP(hipMemcpyAsync(bb.data(), c.beta.p, sizeof(double) * bb.size(), hipMemcpyDeviceToHost, st));
+  DCORA_HIP(hipMemcpyAsync(&dead, c.dead.p, sizeof(int), hipMemcpyDeviceToHost, st));
+  DCORA_HIP(hipStreamSynchronize(st));
+  int jdead = m;
+  if (dead)
+    for (int j = T.k; j < m; ++j)
+      if (!(bb[(size_t)j] >= 1e-300)) {
+        jdead = j;
+        break;
+      }
+  for (int j = T.k; j < jdead; ++j) T.take_live_step(j, &hh[(size_t)j * 64], &hh[(size_t)j * 64 + 32], bb[(size_t)j]);
+  if (jdead < m) {  // a norm vanished at step jdead: that step and the rest of the cycle again, on the slow path
+    DCORA_HIP(hipMemsetAsync(c.dead.p, 0, sizeof(int), st));
+    *matvecs_ -= m - jdead;
+    for (int j = jdead; j < m; ++j) {
+      const int rc = slow_step(T, j);
+      if (rc) return rc;
+    }
+  }
+  return DCORA_OK;
+}
+
+int DeviceLanczos::combine(const std::vector<double> &cols, int count) {
+  const int m = (int)cols.size() / count;
+  DCORA_HIP(hipMemcpyAsync(small.p + 128, cols.data(), sizeof(double) * cols.size(), hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(k_basis_combine, dim3(vec_grid(n)), dim3(kBlock), 0, st, n, m, count, V.p, small.p + 128, Vtmp.p);
+  return DCORA_OK;
+}
+
+// Thick-restart Lanczos for the largest-magnitude eigenpair of (S - shift I): the recurrence of lanczos_restart.h over
+// a basis on the device.
 int DeviceLanczos::largest_magnitude(double shift, int ncv, int maxit, double tol, const double *x0, uint64_t seed,
                                      LanczosResult *out) {
   DCORA_HIP(hipSetDevice(device));
   out->ok = false;
   out->v.assign(n, 0.0);
   out->matvecs = 0;
-  const bool rows = (bool)allreduce;          // row-block form: sums over the ranks after every local reduction
-  const int ng = rows ? n_global : n;         // order of the whole problem
+  const int ng = ranks.order(n);
   if (ng == 0) return DCORA_OK;
-  const int m = std::min(std::min(ncv, kMaxNcv), ng);
-  const int keep = std::max(1, std::min(m - 1, m / 2));
-  std::vector<double> H((size_t)m * m, 0.0), Z, th, host_v((size_t)std::max(n, 1)), hbuf(64);
-  // a vector of the whole problem from the seeded stream (or x0, given for the whole problem), this rank's slice of it
-  std::vector<int> local_of;  // row_map inverted (scattered rows only)
-  if (rows && !row_map.empty()) {
-    local_of.assign((size_t)ng, -1);
-    for (int i = 0; i < n; ++i) local_of[(size_t)row_map[(size_t)i]] = i;
-  }
-  auto whole_vector = [&](uint64_t s, const double *given, double *norm) {
-    double nn = 0;
-    for (int i = 0; i < ng; ++i) {
-      const double x = given ? given[i] : (u01(s) - 0.5);
-      if (!local_of.empty()) {
-        if (local_of[(size_t)i] >= 0) host_v[(size_t)local_of[(size_t)i]] = x;
-      } else if (i >= lo && i < lo + n) {
-        host_v[(size_t)(i - lo)] = x;
-      }
-      nn += x * x;
-    }
-    *norm = std::sqrt(nn);
-  };
-  if (!rows) lo = 0;
+  LanczosRestart T(std::min(ncv, kMaxNcv), ng);
+  const int m = T.m;
+  shift_ = shift;
+  seed_ = seed;
+  matvecs_ = &out->matvecs;
+  npart_ = vec_grid(n);
+  whole_.assign((size_t)ng, 0.0);
+  local_.assign((size_t)std::max(n, 1), 0.0);
   {
-    double nn = 0;
-    whole_vector(seed ? seed : 1, x0, &nn);
-    for (double &x : host_v) x /= nn;
-    DCORA_HIP(hipMemcpyAsync(V.p, host_v.data(), sizeof(double) * n, hipMemcpyHostToDevice, st));
+    const double nn = whole_vector(seed ? seed : 1, x0);
+    for (double &x : local_) x /= nn;
+    DCORA_HIP(hipMemcpyAsync(V.p, local_.data(), sizeof(double) * n, hipMemcpyHostToDevice, st));
     DCORA_HIP(hipStreamSynchronize(st));
   }
-  // sums over the ranks of `count` doubles that sit on the device at dev (no-op on one rank)
-  auto reduce_dev = [&](double *dev, int count) -> int {
-    if (!rows) return DCORA_OK;
-    std::vector<double> tmp((size_t)count);
-    DCORA_HIP(hipMemcpyAsync(tmp.data(), dev, sizeof(double) * count, hipMemcpyDeviceToHost, st));
-    DCORA_HIP(hipStreamSynchronize(st));
-    const int rc2 = allreduce(tmp.data(), count);
-    if (rc2) return rc2;
-    DCORA_HIP(hipMemcpyAsync(dev, tmp.data(), sizeof(double) * count, hipMemcpyHostToDevice, st));
-    DCORA_HIP(hipStreamSynchronize(st));  // tmp leaves scope
-    return DCORA_OK;
-  };
-  const double eps23 = std::pow(2.220446049250313e-16, 2.0 / 3.0);
-  const int npart = vec_grid(n);
-  const CsrDev Sv = Sd.view();
-  int k = 0;
-  double beta = 0;
-  std::vector<int> ord(m);
-  // One Lanczos step = matvec, two passes of projection against the whole basis, the norm, the next vector.  The slow
-  // form reads the coefficients and the norm back after every step (needed when the sums go over ranks, and to handle a
-  // vanishing norm); the fast form keeps them on the device -- the subtraction sums the projection's partials in its
-  // prologue, the next vector is scaled by the kernel that sums <w, w> -- and the host reads a whole restart cycle's
-  // coefficients at once: 8 launches and no host round trip per step instead of 11 launches, two copies and a wait.
-  const bool lanczos_slow = env::lanczos_sync();
-  const bool fast = !rows && !lanczos_slow;
-  DevBuf<double> hdev, bdev;
-  DevBuf<int> fdev;
-  if (fast) {
-    DCORA_HIP(hdev.alloc((size_t)m * 64));
-    DCORA_HIP(bdev.alloc((size_t)m));
-    DCORA_HIP(fdev.alloc(1));
-    DCORA_HIP(hipMemsetAsync(fdev.p, 0, sizeof(int), st));
+  CycleStore cycle;
+  cycle_ = !ranks.allreduce && !env::lanczos_sync() ? &cycle : nullptr;
+  if (cycle_) {
+    DCORA_HIP(cycle.h.alloc((size_t)m * 64));
+    DCORA_HIP(cycle.beta.alloc((size_t)m));
+    DCORA_HIP(cycle.dead.alloc(1));
+    DCORA_HIP(hipMemsetAsync(cycle.dead.p, 0, sizeof(int), st));
   }
-  auto matvec = [&](int j) -> int {
-    double *vj = V.p + (size_t)j * n;
-    if (op) {
-      const int orc = op(vj, w.p);
-      if (orc) return orc;
-      if (shift != 0) launch_scale_shift(st, n, shift, vj, w.p);
-    } else if (inverse_op) {
-      inverse_op->apply(st, 1, buf1(vj), w.p, Gate{});
-    } else {
-      launch_spmm(st, 1, Sv, buf1(vj), 0, nullptr, buf1(w.p), 0, nullptr, Gate{});
-      if (shift != 0) launch_scale_shift(st, n, shift, vj, w.p);
-    }
-    out->matvecs++;
-    return DCORA_OK;
-  };
-  auto slow_step = [&](int j) -> int {
-    int orc = matvec(j);
-    if (orc) return orc;
-    const int nv = j + 1;
-    for (int pass = 0; pass < 2; ++pass) {
-      launch_lanczos_proj(st, n, nv, V.p, w.p, part.p);
-      launch_sum_partials(st, part.p, npart, 24, nv, small.p + 32 * pass);
-      const int rrc = reduce_dev(small.p + 32 * pass, nv);
-      if (rrc) return rrc;
-      launch_lanczos_sub(st, n, nv, V.p, small.p + 32 * pass, w.p);
-    }
-    launch_dot(st, n, w.p, w.p, part.p);
-    launch_sum_partials(st, part.p, npart, 1, 1, small.p + 64);
-    {
-      const int rrc = reduce_dev(small.p + 64, 1);
-      if (rrc) return rrc;
-    }
-    DCORA_HIP(hipMemcpyAsync(hbuf.data(), small.p, sizeof(double) * 64, hipMemcpyDeviceToHost, st));
-    double b2 = 0;
-    DCORA_HIP(hipMemcpyAsync(&b2, small.p + 64, sizeof(double), hipMemcpyDeviceToHost, st));
-    DCORA_HIP(hipStreamSynchronize(st));
-    for (int i = 0; i < nv; ++i) {
-      const double h = hbuf[i] + hbuf[32 + i];
-      H[(size_t)i * m + j] = h;
-      H[(size_t)j * m + i] = h;
-    }
-    beta = std::sqrt(b2);
-    double h2 = 0;
-    for (int i = 0; i < nv; ++i) h2 += H[(size_t)i * m + j] * H[(size_t)i * m + j];
-    if (!(beta > kLanczosDead * std::sqrt(h2 + b2)) || beta < 1e-300) {
-      // invariant subspace (the remainder is rounding noise of the orthogonalisation, or exactly zero): continue with
-      // a fresh random direction orthogonalised against the basis
-      double unused = 0;
-      whole_vector(seed + 7919 * (j + 1), nullptr, &unused);
-      DCORA_HIP(hipMemcpyAsync(w.p, host_v.data(), sizeof(double) * n, hipMemcpyHostToDevice, st));
-      for (int pass = 0; pass < 2; ++pass) {
-        launch_lanczos_proj(st, n, nv, V.p, w.p, part.p);
-        launch_sum_partials(st, part.p, npart, 24, nv, small.p);
-        const int rrc = reduce_dev(small.p, nv);
-        if (rrc) return rrc;
-        launch_lanczos_sub(st, n, nv, V.p, small.p, w.p);
-      }
-      launch_dot(st, n, w.p, w.p, part.p);
-      launch_sum_partials(st, part.p, npart, 1, 1, small.p + 64);
-      {
-        const int rrc = reduce_dev(small.p + 64, 1);
-        if (rrc) return rrc;
-      }
-      launch_scale(st, n, small.p + 64, w.p, V.p + (size_t)(j + 1) * n);
-      DCORA_HIP(hipStreamSynchronize(st));
-      beta = 0;
-    } else {
-      launch_axpby(st, n, 1.0 / beta, w.p, 0.0, nullptr, V.p + (size_t)(j + 1) * n);
-    }
-    return DCORA_OK;
-  };
-  auto fast_step = [&](int j) -> int {
-    const int orc = matvec(j);
-    if (orc) return orc;
-    const int nv = j + 1;
-    for (int pass = 0; pass < 2; ++pass) {
-      double *hout = hdev.p + (size_t)j * 64 + 32 * pass;
-      launch_lanczos_proj(st, n, nv, V.p, w.p, part.p);
-      if (npart <= kLanczosFuseParts) {
-        // (the dot's partials go behind the projection's in `part`: this kernel still reads those)
-        launch_lanczos_sub_sum(st, n, nv, V.p, part.p, npart, hout, w.p, pass == 1 ? part.p + (size_t)npart * 24 : nullptr);
-      } else {
-        launch_sum_partials(st, part.p, npart, 24, nv, small.p + 32 * pass);
-        launch_lanczos_keep(st, nv, small.p + 32 * pass, hout);
-        launch_lanczos_sub(st, n, nv, V.p, small.p + 32 * pass, w.p);
-      }
-    }
-    if (npart <= kLanczosFuseParts) {
-      launch_lanczos_next(st, n, part.p + (size_t)npart * 24, npart, bdev.p + j, fdev.p, w.p, V.p + (size_t)(j + 1) * n,
-                          hdev.p + (size_t)j * 64, nv);
-    } else {
-      launch_dot(st, n, w.p, w.p, part.p);
-      launch_lanczos_next(st, n, part.p, npart, bdev.p + j, fdev.p, w.p, V.p + (size_t)(j + 1) * n, hdev.p + (size_t)j * 64, nv);
-    }
-    return DCORA_OK;
-  };
   for (int it = 0; it <= maxit; ++it) {
-    if (!fast) {
-      for (int j = k; j < m; ++j) {
-        const int src = slow_step(j);
-        if (src) return src;
-      }
+    if (cycle_) {
+      const int rc = fast_cycle(T);
+      if (rc) return rc;
     } else {
-      for (int j = k; j < m; ++j) {
-        const int frc = fast_step(j);
-        if (frc) return frc;
-      }
-      std::vector<double> hh((size_t)m * 64), bb((size_t)m);
-      int dead = 0;
-      DCORA_HIP(hipMemcpyAsync(hh.data(), hdev.p, sizeof(double) * hh.size(), hipMemcpyDeviceToHost, st));
-      DCORA_HIP(hipMemcpyAsync(bb.data(), bdev.p, sizeof(double) * bb.size(), hipMemcpyDeviceToHost, st));
-      DCORA_HIP(hipMemcpyAsync(&dead, fdev.p, sizeof(int), hipMemcpyDeviceToHost, st));
-      DCORA_HIP(hipStreamSynchronize(st));
-      int jdead = m;
-      if (dead)
-        for (int j = k; j < m; ++j)
-          if (!(bb[(size_t)j] >= 1e-300)) {
-            jdead = j;
-            break;
-          }
-      for (int j = k; j < jdead; ++j) {
-        for (int i = 0; i <= j; ++i) {
-          const double h = hh[(size_t)j * 64 + i] + hh[(size_t)j * 64 + 32 + i];
-          H[(size_t)i * m + j] = h;
-          H[(size_t)j * m + i] = h;
-        }
-        beta = bb[(size_t)j];
-      }
-      if (jdead < m) {  // a norm vanished at step jdead: that step and the rest of the cycle again, on the slow path
-        DCORA_HIP(hipMemsetAsync(fdev.p, 0, sizeof(int), st));
-        out->matvecs -= m - jdead;
-        for (int j = jdead; j < m; ++j) {
-          const int src = slow_step(j);
-          if (src) return src;
-        }
+      for (int j = T.k; j < m; ++j) {
+        const int rc = slow_step(T, j);
+        if (rc) return rc;
       }
     }
-    jacobi_eig(m, H, Z, th);
-    std::iota(ord.begin(), ord.end(), 0);
-    std::sort(ord.begin(), ord.end(), [&](int a, int b) { return std::fabs(th[a]) > std::fabs(th[b]); });
-    const int b0 = ord[0];
-    const double resid = std::fabs(beta * Z[(size_t)(m - 1) * m + b0]);
-    const bool conv = resid < tol * std::max(eps23, std::fabs(th[b0]));
-    if (conv || it == maxit || m == ng) {
-      out->ok = conv || (m == ng);
-      out->lambda = th[b0];
-      std::vector<double> zc(m);
-      for (int i = 0; i < m; ++i) zc[i] = Z[(size_t)i * m + b0];
-      DCORA_HIP(hipMemcpyAsync(small.p + 128, zc.data(), sizeof(double) * m, hipMemcpyHostToDevice, st));
-      hipLaunchKernelGGL(k_basis_combine, dim3(vec_grid(n)), dim3(kBlock), 0, st, n, m, 1, V.p, small.p + 128,
-                         Vtmp.p);
+    const bool conv = T.solve(tol);
+    if (conv || it == maxit || T.spans_everything()) {
+      out->ok = conv || T.spans_everything();
+      out->lambda = T.theta();
+      const std::vector<double> zc = T.ritz_coefficients(1);
+      int rc = combine(zc, 1);
+      if (rc) return rc;
       DCORA_HIP(hipMemcpyAsync(out->v.data(), Vtmp.p, sizeof(double) * n, hipMemcpyDeviceToHost, st));
       DCORA_HIP(hipStreamSynchronize(st));
       double nn = 0;
       for (double x : out->v) nn += x * x;
-      if (rows) {
-        const int rrc = allreduce(&nn, 1);
-        if (rrc) return rrc;
-      }
+      rc = ranks.sum(&nn, 1);
+      if (rc) return rc;
       nn = std::sqrt(nn);
       for (double &x : out->v) x /= nn;
       return DCORA_OK;
     }
     // thick restart: V[:, 0:keep] = V Z[:, ord[0:keep]], V[:, keep] = v_{m}
-    std::vector<double> Zk((size_t)m * keep);
-    for (int c = 0; c < keep; ++c)
-      for (int i = 0; i < m; ++i) Zk[(size_t)c * m + i] = Z[(size_t)i * m + ord[c]];
-    DCORA_HIP(hipMemcpyAsync(small.p + 128, Zk.data(), sizeof(double) * m * keep, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_basis_combine, dim3(vec_grid(n)), dim3(kBlock), 0, st, n, m, keep, V.p, small.p + 128,
-                       Vtmp.p);
-    DCORA_HIP(hipMemcpyAsync(V.p, Vtmp.p, sizeof(double) * (size_t)n * keep, hipMemcpyDeviceToDevice, st));
-    DCORA_HIP(hipMemcpyAsync(V.p + (size_t)keep * n, V.p + (size_t)m * n, sizeof(double) * n,
+    const std::vector<double> Zk = T.ritz_coefficients(T.keep);
+    const int rc = combine(Zk, T.keep);
+    if (rc) return rc;
+    DCORA_HIP(hipMemcpyAsync(V.p, Vtmp.p, sizeof(double) * (size_t)n * T.keep, hipMemcpyDeviceToDevice, st));
+    DCORA_HIP(hipMemcpyAsync(V.p + (size_t)T.keep * n, V.p + (size_t)m * n, sizeof(double) * n,
                              hipMemcpyDeviceToDevice, st));
     DCORA_HIP(hipStreamSynchronize(st));
-    std::fill(H.begin(), H.end(), 0.0);
-    for (int c = 0; c < keep; ++c) H[(size_t)c * m + c] = th[ord[c]];
-    k = keep;
+    T.restart();
   }
+  return DCORA_OK;
+}
+
+// default when the eigenvalue computation is unsuccessful: ref src/Graph.cpp:1923, 1932-1939
+int device_precond_regularization(const HostCsr &Q, int device, double *reg) {
+  *reg = 1e-1;
+  DeviceLanczos L;
+  int rc = L.init(Q, device);
+  if (rc) return rc;
+  LanczosResult e;
+  rc = L.largest_magnitude(0.0, std::min(6, Q.n), 10000, 1e-3, nullptr, 1, &e);
+  if (rc) return rc;
+  if (e.ok && e.lambda > 0) *reg = e.lambda / (1e6 - 1);
   return DCORA_OK;
 }
 
@@ -388,121 +336,112 @@ std::vector<double> min_eig_second_start(const HostCsr &S, uint64_t seed) {
   return x0;
 }
 
-// ref src/DCORA_utils.cpp:1809-1896
+namespace {
+// One attempt of the shift-and-invert fallback (ref :1878-1888 -> :1751-1805): Lanczos on (S - sigma I)^-1.  The solve
+// per step is the partitioned sparse inverse of the SPD matrix S - sigma I replayed on the device (sparse_precond.h), one
+// right-hand side; a matrix that is not positive definite is an outcome, not an error.
+int inverse_attempt(DeviceLanczos &L, const HostCsr &S, double sigma, int ncv, uint64_t seed, int nthreads,
+                    LanczosResult *si, ShiftLadder::Outcome *outcome) {
+  PartInvHost P;
+  DeviceWeightSink sink(L.device);  // the stored weights stream to the device while they are formed
+  P.sink = &sink;
+  const int brc = build_partitioned_inverse_auto(csr_shift_diag(S, -sigma), 1, nthreads, L.device, &P);
+  *outcome = ShiftLadder::Outcome::not_pd;
+  if (brc) return brc == DCORA_ERR_NOT_PD ? DCORA_OK : brc;
+  SparsePrecond inv;
+  auto img = std::make_shared<SpImage>();
+  int rc = img->upload(P, &sink);
+  if (rc) return rc;
+  rc = inv.attach(img, 1);
+  if (rc) return rc;
+  const MinEigPlan::Run run = MinEigPlan::inverse_run(ncv);
+  L.inverse_op = &inv;
+  rc = L.largest_magnitude(run.shift, run.ncv, run.maxit, run.tol, nullptr, seed, si);
+  L.inverse_op = nullptr;
+  if (rc) return rc;
+  if (env::init_timing())
+    fprintf(stderr, "[min_eig] shift-and-invert at sigma %.3g: %ld solves, converged %d\n", sigma, si->matvecs, (int)si->ok);
+  *outcome = si->ok ? ShiftLadder::Outcome::converged : ShiftLadder::Outcome::factored_but_not_converged;
+  return DCORA_OK;
+}
+}  // namespace
+
+// min_eig_plan.h with its runs on this device
 int device_min_eig(const HostCsr &S, int maxit, double min_eig_tol, int ncv, uint64_t seed, int device,
                    LanczosResult *out) {
+  using After = MinEigPlan::AfterFirst;
+  const MinEigPlan plan{MinEigPlan::Shortcut::always, MinEigPlan::OnFailedFirst::error};
   DeviceLanczos L;
   int rc = L.init(S, device);
   if (rc) return rc;
   const int k = S.n;
   ncv = std::min(ncv, k);
+  auto lanczos = [&](const MinEigPlan::Run &run, const double *x0, LanczosResult *res) {
+    return L.largest_magnitude(run.shift, run.ncv, run.maxit, run.tol, x0, seed, res);
+  };
   LanczosResult lm;
-  rc = L.largest_magnitude(0.0, ncv, maxit, 1e-4, nullptr, seed, &lm);
+  rc = lanczos(plan.first_run(ncv, maxit), nullptr, &lm);
   if (rc) return rc;
-  if (!lm.ok) {
+  const After after = plan.after_first_run(lm.ok, lm.lambda, min_eig_tol, true);
+  if (after == After::failed_first) {
     set_last_error("min_eig: could not compute the largest-magnitude eigenvalue of S");
     *out = lm;
     return DCORA_ERR_NO_CONVERGENCE;
   }
-  if (lm.lambda < 0) {
+  if (after == After::done_negative || after == After::done_zero) {
     *out = lm;
     return DCORA_OK;
   }
   const double lambda_lm = lm.lambda;
-  if (lambda_lm == 0) {  // S = 0: every vector is an eigenvector of the eigenvalue 0
-    *out = lm;
-    return DCORA_OK;
-  }
   const std::vector<double> x0 = min_eig_second_start(S, seed);
-  LanczosResult sh;
-  // The spectrum-shifted run resolves the smallest eigenvalue to min_eig_tol on a spectrum of width lambda_lm.  When that
-  // ratio is hopeless for a 20-vector Krylov space (tiers.pyfg: the landmark every pose ranges to puts lambda_lm at
-  // 2e6, the ratio at 5e-10) the reference's run spends its 1000 restarts -- 10 020 matvecs, 0.6 s per certificate here --
-  // and then takes the shift-and-invert fallback below anyway; this goes there at once.  The eigenpair returned is the
-  // fallback's either way.
-  const bool hopeless = min_eig_shifted_run_hopeless(min_eig_tol, lambda_lm);
-  if (hopeless) {
-    sh.ok = false;
-    sh.v.assign((size_t)k, 0.0);
-    sh.lambda = 0;
-  } else {
-    rc = L.largest_magnitude(2 * lambda_lm, ncv, maxit, min_eig_tol / lambda_lm, x0.data(), seed, &sh);
+  const MinEigPlan::Run shifted = plan.shifted_run(lambda_lm, min_eig_tol, ncv, maxit);
+  LanczosResult sh;  // (the shortcut: the run not made counts as not converged; the eigenpair is the fallback's either way)
+  sh.v.assign((size_t)k, 0.0);
+  if (after == After::shifted) {
+    rc = lanczos(shifted, x0.data(), &sh);
     if (rc) return rc;
   }
   sh.matvecs += lm.matvecs;
   if (env::init_timing())
     fprintf(stderr, "[min_eig] k %d: largest-magnitude run %ld matvecs (lambda %.3e), shifted run %ld matvecs, converged %d\n", k,
             lm.matvecs, lm.lambda, sh.matvecs - lm.matvecs, (int)sh.ok);
-  if (!sh.ok) {
-    // Shift-and-invert fallback (ref :1878-1888 -> :1751-1805): Lanczos on (S - sigma I)^-1, sigma = -10, halved
-    // on failure with the floor -2 eta.  The solve per step is the partitioned sparse inverse of the SPD matrix
-    // S - sigma I replayed on the device (sparse_precond.h), one right-hand side.
-    // The factorisation is a Cholesky (the reference's Spectra run factors S - sigma I by a sparse LU, which exists for
-    // any shift): S - sigma I must be positive definite, i.e. sigma < lambda_min.  When the very first shift, -10, is
-    // refused, lambda_min lies below it: the shift moves OUTWARD by factors of ten -- at most to -lambda_lm, below
-    // which nothing of the spectrum can lie -- until the matrix factors.
-    double sigma = -10.0;
-    bool outward = false;
-    const int nthreads = std::max(1, std::min(host_cpus_available(), 32));
-    for (int i = 0; i < 24; ++i) {
-      PartInvHost P;
-      DeviceWeightSink sink(device);  // the stored weights stream to the device while they are formed
-      P.sink = &sink;
-      const int brc = build_partitioned_inverse_auto(csr_shift_diag(S, -sigma), 1, nthreads, device, &P);
-      if (brc && brc != DCORA_ERR_NOT_PD) return brc;
-      if (brc == DCORA_ERR_NOT_PD && (i == 0 || outward)) {
-        outward = true;
-        if (-sigma > 2.0 * lambda_lm + 10.0) break;  // (cannot happen in exact arithmetic)
-        sigma *= 10.0;
-        continue;
-      }
-      if (brc == DCORA_OK) {
-        SparsePrecond inv;
-        auto img = std::make_shared<SpImage>();
-        rc = img->upload(P, &sink);
-        if (rc) return rc;
-        rc = inv.attach(img, 1);
-        if (rc) return rc;
-        L.inverse_op = &inv;
-        LanczosResult si;
-        rc = L.largest_magnitude(0.0, ncv, 1000, 1e-10, nullptr, seed, &si);
-        L.inverse_op = nullptr;
-        if (rc) return rc;
-        if (env::init_timing())
-          fprintf(stderr, "[min_eig] shift-and-invert at sigma %.3g: %ld solves, converged %d\n", sigma, si.matvecs, (int)si.ok);
-        if (si.ok) {
-          si.matvecs += sh.matvecs;
-          si.lambda = sigma + 1.0 / si.lambda;
-          *out = si;
-          return DCORA_OK;
-        }
-      }
-      if (outward) break;  // factored far out but Lanczos on the inverse did not converge: the shifted run below
-      if (i >= 9) break;
-      sigma /= 2;
-      if (i == 8 || sigma > -2 * min_eig_tol) sigma = -2 * min_eig_tol;
-    }
-    if (hopeless) {
-      // the shortcut skipped the reference's first attempt and the fallback delivered nothing: make that attempt now
-      LanczosResult late;
-      rc = L.largest_magnitude(2 * lambda_lm, ncv, maxit, min_eig_tol / lambda_lm, x0.data(), seed, &late);
+  if (sh.ok) {
+    sh.lambda = plan.shifted_eigenvalue(sh.lambda, lambda_lm);
+    *out = sh;
+    return DCORA_OK;
+  }
+  const int nthreads = std::max(1, std::min(host_cpus_available(), 32));
+  ShiftLadder ladder(lambda_lm, min_eig_tol, after == After::fallback_hopeless);
+  while (ladder.step() != ShiftLadder::Step::end) {
+    LanczosResult res;
+    ShiftLadder::Outcome outcome = ShiftLadder::Outcome::factored_but_not_converged;
+    if (ladder.step() == ShiftLadder::Step::invert) {
+      rc = inverse_attempt(L, S, ladder.sigma(), ncv, seed, nthreads, &res, &outcome);
       if (rc) return rc;
-      late.matvecs += sh.matvecs;
-      if (late.ok) {
-        late.lambda += 2 * lambda_lm;
-        *out = late;
+      if (outcome == ShiftLadder::Outcome::converged) {
+        res.matvecs += sh.matvecs;
+        res.lambda = plan.inverse_eigenvalue(res.lambda, ladder.sigma());
+        *out = res;
         return DCORA_OK;
       }
-      sh = late;
+    } else {
+      // the shortcut skipped the reference's first attempt and the fallback delivered nothing: make that attempt now
+      rc = lanczos(shifted, x0.data(), &res);
+      if (rc) return rc;
+      res.matvecs += sh.matvecs;
+      if (res.ok) {
+        res.lambda = plan.shifted_eigenvalue(res.lambda, lambda_lm);
+        *out = res;
+        return DCORA_OK;
+      }
+      sh = res;
     }
-    set_last_error("min_eig: neither the spectrum-shifted nor the shift-and-invert Lanczos run converged");
-    *out = sh;
-    out->lambda += 2 * lambda_lm;
-    return DCORA_ERR_NO_CONVERGENCE;
+    ladder.next(outcome);
   }
-  sh.lambda += 2 * lambda_lm;
+  set_last_error("min_eig: neither the spectrum-shifted nor the shift-and-invert Lanczos run converged");
   *out = sh;
-  return DCORA_OK;
+  out->lambda = plan.shifted_eigenvalue(sh.lambda, lambda_lm);
+  return DCORA_ERR_NO_CONVERGENCE;
 }
 
 // ref src/DCORA_utils.cpp:1898-1982

@@ -14,6 +14,7 @@
 // The host half of the protocol -- the segment's layout, the bounded wait and every host step -- is stated once in
 // exchange_slots.h (no HIP); this class wraps the steps with its error texts and statistics and launches the kernels.
 #pragma once
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -236,12 +237,14 @@ class Exchange {
   bool probe_round(uint64_t seq, std::string *why);
   // the two halves both certificates share (exchange_cert.hip): post and wait of all agents with the Lambda blocks of
   // the hosted ones; the minimum eigenpair of M = S + eta I by all ranks once the PSD test has refused (M: rank 0's).
-  // skip_hopeless: device_min_eig's rule for the spectrum-shifted run (min_eig_shifted_run_hopeless) holds for the
-  // row-block run too -- certify_live's choice; certify keeps making the run
+  // skip_hopeless: the plan's shortcut past the spectrum-shifted run (min_eig_plan.h, Shortcut::when_asked) is asked
+  // for -- certify_live's choice; certify keeps making the run.  share_whole_vector: one vector of the whole problem
+  // through the segment's X area, to every rank
   struct CertRows;
   int cert_rows_begin(CertRows *rows);
   int cert_min_eigenpair(CertRows &rows, const HostCsr &M, double eta, bool skip_hopeless, double *theta,
                          double *lambda_min, double *v, long long *matvecs, int *distributed);
+  int share_whole_vector(const std::function<void(double *x_area)> &store, double *whole);
   int live_cert_build();  // the pattern and the tables, on the first certify_live
   int certify_live_run(double eta, int *certified, double *theta, double *lambda_min, double *v, long long *matvecs,
                        int *distributed, double *info10);  // certify_live behind its refusals

@@ -322,6 +322,16 @@ int Exchange::certify(const HostCsr *Qglobal, double eta, int *certified, double
   return cert_min_eigenpair(rows, M, eta, false, theta, lambda_min, v, matvecs, distributed);
 }
 
+// One vector of the whole problem from the ranks to every rank, through the segment's X area: `store` writes this
+// rank's part there (all of it on rank 0, or every rank its own rows), barrier, every rank copies it out, barrier.
+int Exchange::share_whole_vector(const std::function<void(double *x_area)> &store, double *whole) {
+  store(lay_.x(map_));
+  int rc = barrier();
+  if (rc) return rc;
+  std::memcpy(whole, lay_.x(map_), sizeof(double) * s_->num_cols());
+  return barrier();
+}
+
 // ---- minimum eigenpair of M = S + eta I by all ranks (M: on rank 0, for the second run's start vector and the
 // shift-and-invert fallback; the operator is the ranks' own matrices and Lambda blocks) ----
 int Exchange::cert_min_eigenpair(CertRows &rows, const HostCsr &M, double eta, bool skip_hopeless, double *theta,
@@ -339,8 +349,8 @@ int Exchange::cert_min_eigenpair(CertRows &rows, const HostCsr &M, double eta, b
   DeviceLanczos L;
   rc = L.init_rows(nloc, ktot, lo, device, st);
   if (rc) return rc;
-  L.row_map = row_map;
-  L.allreduce = [this](double *vals, int count) { return allreduce_sum(vals, count); };
+  L.ranks.row_map = row_map;
+  L.ranks.allreduce = [this](double *vals, int count) { return allreduce_sum(vals, count); };
   L.op = [&](const double *vj, double *w) -> int {
     for (CertBlock &B : blocks) {
       if (B.own_dev)
@@ -364,52 +374,42 @@ int Exchange::cert_min_eigenpair(CertRows &rows, const HostCsr &M, double eta, b
     DCORA_HIP(hipGetLastError());
     return DCORA_OK;
   };
-  // this rank's rows of a vector of the whole problem, and back
-  auto local_of_whole = [&](const double *whole, double *local) {
-    for (int i = 0; i < nloc; ++i) local[i] = whole[row_map.empty() ? (size_t)lo + i : (size_t)row_map[(size_t)i]];
-  };
-  auto whole_of_local = [&](const double *local, double *whole) {
-    for (int i = 0; i < nloc; ++i) whole[row_map.empty() ? (size_t)lo + i : (size_t)row_map[(size_t)i]] = local[i];
-  };
+  // The plan of min_eig_plan.h with collective runs.  Every quantity its decisions read was summed in rank order, so
+  // every rank decides alike.  The shortcut is certify_live's choice (as on one GPU, a spectrum as wide as tiers.pyfg's
+  // 2e6 gives the spectrum-shifted run no chance worth up to 1000 restarts of collective steps); certify keeps making
+  // the run.  The fallback needs a factorisation of the whole matrix and is rank 0's, which holds it.
+  using After = MinEigPlan::AfterFirst;
+  const MinEigPlan plan{MinEigPlan::Shortcut::when_asked, MinEigPlan::OnFailedFirst::fallback};
   const uint64_t seed = 12345;
   const int ncv = std::min(20, ktot);
-  LanczosResult lm, res;
-  rc = L.largest_magnitude(0.0, ncv, 1000, 1e-4, nullptr, seed, &lm);
+  auto lanczos = [&](const MinEigPlan::Run &run, const double *x0, LanczosResult *res) {
+    return L.largest_magnitude(run.shift, run.ncv, run.maxit, run.tol, x0, seed, res);
+  };
+  LanczosResult res;
+  rc = lanczos(plan.first_run(ncv, 1000), nullptr, &res);
   if (rc) return rc;
-  bool ok = lm.ok;
-  long mv = lm.matvecs;
-  if (ok && lm.lambda < 0) {
-    res = lm;
-  } else if (ok && skip_hopeless && min_eig_shifted_run_hopeless(eta, lm.lambda)) {
-    // as on one GPU (device_min_eig): a spectrum this wide (tiers.pyfg: 2e6) gives the spectrum-shifted run no chance
-    // worth up to 1000 restarts of collective steps; rank 0's shift-and-invert run below delivers the eigenpair.
-    // (lm.lambda was summed in rank order: every rank decides alike)
-    ok = false;
-  } else if (ok) {
-    // the spectrum-shifted run; its start vector comes from the first row of M, which rank 0 holds
+  long mv = res.matvecs;
+  const After after = plan.after_first_run(res.ok, res.lambda, eta, skip_hopeless);
+  bool fallback = plan.goes_to_fallback(after);
+  if (after == After::shifted) {
+    // its start vector comes from the first row of M, which rank 0 holds
+    const double lambda_lm = res.lambda;
     std::vector<double> x0((size_t)ktot, 0.0);
     if (rank == 0) x0 = min_eig_second_start(M, seed);
-    std::memcpy(lay_.x(map_), x0.data(), rank == 0 ? sizeof(double) * ktot : 0);
-    rc = barrier();
+    rc = share_whole_vector([&](double *x) { std::memcpy(x, x0.data(), rank == 0 ? sizeof(double) * ktot : 0); }, x0.data());
     if (rc) return rc;
-    std::memcpy(x0.data(), lay_.x(map_), sizeof(double) * ktot);
-    rc = barrier();
+    rc = lanczos(plan.shifted_run(lambda_lm, eta, ncv, 1000), x0.data(), &res);
     if (rc) return rc;
-    LanczosResult sh;
-    rc = L.largest_magnitude(2 * lm.lambda, ncv, 1000, eta / lm.lambda, x0.data(), seed, &sh);
-    if (rc) return rc;
-    mv += sh.matvecs;
-    ok = sh.ok;
-    sh.lambda += 2 * lm.lambda;
-    res = sh;
+    mv += res.matvecs;
+    fallback = !res.ok;
+    res.lambda = plan.shifted_eigenvalue(res.lambda, lambda_lm);
   }
-  double flag = ok ? 0 : 1;  // (identical on all ranks: every quantity the test reads was summed in rank order)
+  double flag = fallback ? 1 : 0;  // (identical on all ranks)
   rc = allreduce_sum(&flag, 1);
   if (rc) return rc;
   std::vector<double> vfull((size_t)ktot, 0.0);
   if (flag != 0) {
-    // neither run converged: the shift-and-invert fallback (ref :1878-1888) needs a factorisation of the whole matrix
-    // and stays on rank 0, which holds it
+    // the shortcut, or a collective run that did not converge (ref :1878-1888)
     double out2[3] = {0, 0, 0};  // {lambda; error code; rank 0's matvecs: the count is the same on every rank}
     if (rank == 0) {
       LanczosResult e;
@@ -424,19 +424,17 @@ int Exchange::cert_min_eigenpair(CertRows &rows, const HostCsr &M, double eta, b
     if (out2[1] != 0) return fail("certify: the minimum eigenpair could not be computed", (int)out2[1]);
     res.lambda = out2[0];
     mv += (long)out2[2];
-    if (rank == 0) std::memcpy(lay_.x(map_), vfull.data(), sizeof(double) * ktot);
-    rc = barrier();
-    if (rc) return rc;
-    std::memcpy(vfull.data(), lay_.x(map_), sizeof(double) * ktot);
-    rc = barrier();
+    rc = share_whole_vector([&](double *x) { std::memcpy(x, vfull.data(), rank == 0 ? sizeof(double) * ktot : 0); },
+                            vfull.data());
     if (rc) return rc;
   } else {
     if (distributed) *distributed = 1;
-    whole_of_local(res.v.data(), lay_.x(map_));  // every rank its own rows of the shared vector
-    rc = barrier();
-    if (rc) return rc;
-    std::memcpy(vfull.data(), lay_.x(map_), sizeof(double) * ktot);
-    rc = barrier();
+    // every rank its own rows of the shared vector
+    rc = share_whole_vector(
+        [&](double *x) {
+          for (int i = 0; i < nloc; ++i) x[row_map.empty() ? (size_t)lo + i : (size_t)row_map[(size_t)i]] = res.v[(size_t)i];
+        },
+        vfull.data());
     if (rc) return rc;
   }
   // theta = v^T S v = v^T M v - eta (|v| = 1), with the row-block operator
@@ -445,7 +443,7 @@ int Exchange::cert_min_eigenpair(CertRows &rows, const HostCsr &M, double eta, b
     DCORA_HIP(vl.alloc((size_t)std::max(nloc, 1)));
     DCORA_HIP(wl.alloc((size_t)std::max(nloc, 1)));
     std::vector<double> vloc((size_t)std::max(nloc, 1));
-    local_of_whole(vfull.data(), vloc.data());
+    L.ranks.slice(vfull.data(), nloc, vloc.data());
     if (nloc > 0) DCORA_HIP(hipMemcpyAsync(vl.p, vloc.data(), sizeof(double) * nloc, hipMemcpyHostToDevice, st));
     rc = L.op(vl.p, wl.p);
     if (rc) return rc;

@@ -119,6 +119,7 @@ class RaRbcdSession : public SessionCore {
   }
 };
 
+// lambda_max(Q) / (1e6 - 1) by a Lanczos run on the device (cert.hip, with the other clients of that eigensolver)
 int device_precond_regularization(const HostCsr &Q, int device, double *reg);
 
 }  // namespace dcora

@@ -11,18 +11,6 @@
 
 namespace dcora {
 
-int device_precond_regularization(const HostCsr &Q, int device, double *reg) {
-  *reg = 1e-1;  // default when the eigenvalue computation is unsuccessful (ref src/Graph.cpp:1923, 1932-1939)
-  DeviceLanczos L;
-  int rc = L.init(Q, device);
-  if (rc) return rc;
-  LanczosResult e;
-  rc = L.largest_magnitude(0.0, std::min(6, Q.n), 10000, 1e-3, nullptr, 1, &e);
-  if (rc) return rc;
-  if (e.ok && e.lambda > 0) *reg = e.lambda / (1e6 - 1);
-  return DCORA_OK;
-}
-
 RaRbcdSession::~RaRbcdSession() {
   for (RaAgentDev &a : agents) release_tick_resources(a);
   agents.clear();

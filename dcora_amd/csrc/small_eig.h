@@ -46,6 +46,46 @@ inline void jacobi_eig(int n, std::vector<double> &G, std::vector<double> &V) {
   }
 }
 
+// The form the certificate's Lanczos recurrence has used since its first version (lanczos_restart.h): A = Z diag(w) Z^T
+// with the eigenvectors as the COLUMNS of the row-major Z, the sweeps ended by the off-diagonal's share of the Frobenius
+// norm, not by its largest entry.  Kept beside the form above because the two stop after different sweeps: the
+// eigensolver's Ritz values, and with them every certificate's bits, follow this one.
+inline void jacobi_eig(int m, std::vector<double> A, std::vector<double> &Z, std::vector<double> &w) {
+  Z.assign((size_t)m * m, 0.0);
+  for (int i = 0; i < m; ++i) Z[(size_t)i * m + i] = 1;
+  for (int sweep = 0; sweep < 100; ++sweep) {
+    double off = 0, dg = 0;
+    for (int i = 0; i < m; ++i) {
+      dg += A[(size_t)i * m + i] * A[(size_t)i * m + i];
+      for (int j = i + 1; j < m; ++j) off += A[(size_t)i * m + j] * A[(size_t)i * m + j];
+    }
+    if (off == 0 || off <= 1e-32 * (dg + off)) break;
+    for (int p = 0; p < m - 1; ++p)
+      for (int q = p + 1; q < m; ++q) {
+        const double apq = A[(size_t)p * m + q];
+        if (apq == 0) continue;
+        const double zeta = (A[(size_t)q * m + q] - A[(size_t)p * m + p]) / (2 * apq);
+        const double t = (zeta >= 0 ? 1.0 : -1.0) / (std::fabs(zeta) + std::sqrt(1 + zeta * zeta));
+        const double c = 1 / std::sqrt(1 + t * t), s = c * t;
+        for (int k = 0; k < m; ++k) {
+          const double akp = A[(size_t)k * m + p], akq = A[(size_t)k * m + q];
+          A[(size_t)k * m + p] = c * akp - s * akq;
+          A[(size_t)k * m + q] = s * akp + c * akq;
+        }
+        for (int k = 0; k < m; ++k) {
+          const double apk = A[(size_t)p * m + k], aqk = A[(size_t)q * m + k];
+          A[(size_t)p * m + k] = c * apk - s * aqk;
+          A[(size_t)q * m + k] = s * apk + c * aqk;
+          const double zkp = Z[(size_t)k * m + p], zkq = Z[(size_t)k * m + q];
+          Z[(size_t)k * m + p] = c * zkp - s * zkq;
+          Z[(size_t)k * m + q] = s * zkp + c * zkq;
+        }
+      }
+  }
+  w.resize(m);
+  for (int i = 0; i < m; ++i) w[i] = A[(size_t)i * m + i];
+}
+
 // The eigenvalues of G (n x n, symmetric, column-major) in descending order in w, their eigenvectors as the columns of
 // V (n x n, column-major) in that order.  Equal eigenvalues keep the order of their index (a stable sort on the value
 // alone), so the choice among ties is the same call after call.
